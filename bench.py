@@ -16,7 +16,13 @@ Raytracing::trace call of the reference (primary, reflection, refraction, shadow
 
 The timed frame is the CONTRACT frame: RGBA8 plus the aux buffers PixelData carries
 (normal, depth, object id: reference src/raytracing.rs:57-70), resident in HBM at the end.
-Extra keys (rank 0, N = 1): `rgba_only_ms` (aux buffers not requested), `rr_render_host_ms`
+
+A plain run sets up, warms up, times the K steps, writes the last step's frame if `--dump-outputs DIR` is given
+(DIR/rgba.npy, normal.npy, depth.npy, object_id.npy: float32 / float64, see dump_outputs) and prints the line with the
+headline (`value` Mrays/s, `ms_per_step`) and what the timed steps themselves counted.  Everything else -- the CPU
+baseline, the rooflines, the extra keys and other configs below, the N > 1 checks -- comes only with `--full`.
+
+Extra keys (`--full`, rank 0, N = 1): `rgba_only_ms` (aux buffers not requested), `rr_render_host_ms`
 (the same frame through rr_render into host memory, PCIe included), `update_transforms_ms` / `pick_ms` (the animation step and
 the pick query on the resident scene), and `other_configs`: every other BASELINE config at its own size and sample count
 (C1 spheres 256x256x1 mc=0, C2 monkey 800x600x16, and the stand-ins helmet_syn 1280x720x64, lotus_syn 1280x720x512 + DOF for
@@ -24,14 +30,14 @@ C3 / C5), each with its device time, launches and -- where profiles/ holds SQ co
 `roofline.kernels` prices EVERY kernel build of the frame (k_trace_closest / k_shade / k_trace_shadow, level 1 `<true>` and the deeper
 levels `<false>`) from its live launch times.
 
-N > 1 additionally reports what shows that RCCL really saw N ranks (`dist_backend`, `world_size` as torch.distributed
+N > 1 with `--full` additionally reports what shows that RCCL really saw N ranks (`dist_backend`, `world_size` as torch.distributed
 reports it, every rank's device), `frame_checksum_matches_single_gpu` (rank 0 renders the whole frame alone after the
 timed region and compares), `gather_ms` / `render_only_ms` (timed apart, after the timed region), and `one_process`:
 the same frame through rr_render_multi over the same N devices from ONE host process (the form the reference host is,
 src/renderer.rs:105-172), run by a helper process that rank 0 starts before it touches the GPU.  `--one-process` runs
 that form alone.
 
-Rank 0 prints ONE JSON line with `roofline` and `cpu_baseline` (the C++ restatement in
+Rank 0 prints ONE JSON line; with `--full` it holds `roofline` and `cpu_baseline` (the C++ restatement in
 oracle/ timed on the host cores over a bounded sample of the same frame).
 
 `roofline`: the dominant kernel is the level-1 build of the closest-hit kernel,
@@ -410,6 +416,29 @@ def finish_one_process_helper(helper, timeout=300):
         return {"error": "unparsable result line", "stdout_tail": out[-400:]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(frame, out_dir):
+    """--dump-outputs: the frame the last timed step left on rank 0, one DIR/<buffer>.npy per buffer the caller receives: rgba
+    (H, W, 4), normal (H, W, 3) and depth (H, W, 1) as float32, object_id (H, W, 1) as float64.  A frame larger than 64 MB in
+    that form is sampled: the same fixed, seeded set of pixels from every buffer, as rows (n, C), with their flat indices
+    y * W + x in DIR/pixel_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() for k, v in frame.items()}
+    arrays = {k: a.astype(np.float64 if k == "object_id" else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        h, w = arrays["rgba"].shape[:2]
+        bytes_per_pixel = total // (h * w) + 8   # + its pixel_index entry
+        n = (DUMP_LIMIT_BYTES - 4096) // bytes_per_pixel   # (4096: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        arrays = {k: a.reshape(h * w, -1)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -422,16 +451,19 @@ def main():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--spp", type=int, default=128)
     ap.add_argument("--monte-carlo", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: cpu_baseline, roofline, "
+                                                        "the extra keys and other_configs (N = 1), the N > 1 checks and the one-process leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's frame to DIR/<buffer>.npy (float32 / float64)")
     ap.add_argument("--cpu-spp", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip rgba_only / rr_render_host / other_configs (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip rgba_only / rr_render_host / other_configs (profiling runs)")
     ap.add_argument("--rgba-only", action="store_true", help="developer A/B: time the frame without the aux buffers")
     ap.add_argument("--binning", action="store_true", help="developer A/B: bin deeper levels by (origin cell, direction octant) before tracing")
     ap.add_argument("--tile", default="32x8")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank) or gloo (rehearsal: ranks may share a GPU)")
     ap.add_argument("--one-process", action="store_true", help="time rr_render_multi over --gpus devices from this ONE process (no torch.distributed)")
     ap.add_argument("--same-device", action="store_true", help="--one-process rehearsal: all handles on device 0")
-    ap.add_argument("--no-one-process", action="store_true", help="N > 1: skip the rr_render_multi leg")
+    ap.add_argument("--no-one-process", action="store_true", help="N > 1 with --full: skip the rr_render_multi leg")
     ap.add_argument("--one-process-helper", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.one_process or args.one_process_helper:
@@ -446,7 +478,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # the one-process leg runs in a helper that must exist BEFORE this process touches the GPU (a GPU process may not exec)
-    helper = start_one_process_helper(args, world) if (world > 1 and rank == 0 and not args.no_one_process) else None
+    helper = start_one_process_helper(args, world) if (world > 1 and rank == 0 and args.full and not args.no_one_process) else None
     if world != args.gpus:
         if world == 1 and args.gpus > 1:
             raise SystemExit("--gpus N > 1 must be launched with torch.distributed.run (one rank per GPU)")
@@ -512,10 +544,12 @@ def main():
     elapsed = float(tmax.item())
     primary, secondary, shadow, shaded = [float(v) for v in work.tolist()]
     rays = primary + secondary + shadow
+    if args.dump_outputs and rank == 0 and frame is not None:
+        dump_outputs(frame, args.dump_outputs)   # before anything below renders into the same persistent buffers
 
-    # ---- N > 1, outside the timed region: what shows the collective really ran over N ranks, and the gather timed apart
+    # ---- N > 1, --full, outside the timed region: what shows the collective really ran over N ranks, and the gather timed apart
     dist_info = None
-    if world > 1:
+    if world > 1 and args.full:
         me = {"rank": rank, "local_rank": local_rank, "device_index": torch.cuda.current_device(),
               "device": torch.cuda.get_device_name(torch.cuda.current_device()), "pid": os.getpid(), "region_pixels": tf.n_pixels()}
         everyone = [None] * world
@@ -560,10 +594,10 @@ def main():
             "rays_per_frame": {"primary": primary / args.steps, "secondary": secondary / args.steps, "shadow": shadow / args.steps},
         }
         ab = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb, ab = cpu_baseline(fs, cam, args)
             result["cpu_baseline"] = cb
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             # N > 1: no CPU timing, only the byte model (per-ray figures) from a small oracle sample
             from rustray_amd.camera import Camera as _Cam
             st = dict(fs.meta["camera"]); st["width"], st["height"] = 320, 180
@@ -572,7 +606,7 @@ def main():
         # roofline of the dominant kernel (rank 0's launches), see the module docstring: the level-1 build of the closest-hit
         # kernel, `k_trace_closest<true>` in the rocprofv3 kernel stats (one launch per batch, the frame is one batch) -- and, beside
         # it under `kernels`, every kernel build of the frame with its own live launch time
-        roof = kernel_rooflines(fs.name, args.width, args.height, args.spp, acc, args.steps, capi.source_id())
+        roof = kernel_rooflines(fs.name, args.width, args.height, args.spp, acc, args.steps, capi.source_id()) if args.full else None
         if roof is not None:
             hbm, hbm_path = newest_profile("r[0-9][0-9]_hbm_traffic.json")
             h1 = (hbm or {}).get("kernels", {}).get("k_trace_closest<true>")
@@ -596,7 +630,7 @@ def main():
         if dist_info is not None:
             dist_info["frame_checksum_matches_single_gpu"] = dist_info.get("frame_checksum_single_gpu") == result.get("frame_checksum")
             result.update(dist_info)
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             result.update(extras(args, ds, camc, cfg, step, fence))
     if world > 1:
         dist.barrier()

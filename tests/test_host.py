@@ -8,10 +8,15 @@ import pytest
 from rustray_amd.camera import Camera, approx_equal
 from rustray_amd.flat import FlatScene, Material, make_config
 from rustray_amd.renderer import region_pixels
-from tests.helpers import SCENES, load_scene
+from tests.helpers import GOLDEN, SCENES, load_scene
 
-REF = "/root/reference"
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+
+@pytest.fixture(scope="module")
+def ref_root(tmp_path_factory):
+    """A tree laid out like the reference's, holding the scene files the loader tests read (tests/golden/scene_files.npz,
+    written by tests/golden/make_scene_files.py: the reference's own files, byte for byte)."""
+    from tests.golden.make_scene_files import write_tree
+    return write_tree(os.path.join(GOLDEN, "scene_files.npz"), str(tmp_path_factory.mktemp("reference")))
 
 
 def test_flat_scene_npz_round_trip(tmp_path):
@@ -58,11 +63,10 @@ def test_monkey_scene_semantics():
     assert np.allclose(t.astype(np.float64) @ fs.items[0].trans_inv.astype(np.float64), np.eye(4), atol=1e-5)
 
 
-@needs_reference
 @pytest.mark.parametrize("name,path,w,h", [("spheres", "scene/spheres.json", 256, 256), ("monkey", "scene/monkey.json", 800, 600)])
-def test_loader_reproduces_committed_fixture(name, path, w, h):
+def test_loader_reproduces_committed_fixture(name, path, w, h, ref_root):
     from rustray_amd.scene import load_scene as load_ref
-    sc = load_ref(path, w, h, root=REF)
+    sc = load_ref(path, w, h, root=ref_root)
     fs, g = sc.flatten(), load_scene(name)
     assert len(fs.items) == len(g.items)
     for a, b in zip(fs.items, g.items):
@@ -73,7 +77,6 @@ def test_loader_reproduces_committed_fixture(name, path, w, h):
         assert np.array_equal(a.positions, b.positions) and np.array_equal(a.indices, b.indices)
 
 
-@needs_reference
 def test_auto_camera_and_spot_light_for_kbert():
     """kbert.json has no camera block: find_optimal_camera_pos runs (src/scene.rs:1426-1547)."""
     fs = load_scene("kbert")
@@ -130,11 +133,10 @@ def test_synthetic_scenes_are_deterministic_and_sized():
     assert lo.meta["config"]["aperture_size"] == 16.0 and lo.meta["config"]["focal_length"] == 20.0
 
 
-@needs_reference
-def test_gltf_loader_semantics():
+def test_gltf_loader_semantics(ref_root):
     """monkey.glb through the glTF path (reference src/scene.rs:722-978)."""
     from rustray_amd.scene import load_scene as load_ref
-    sc = load_ref("scene/models/monkey/monkey.glb", 320, 180, root=REF)
+    sc = load_ref("scene/models/monkey/monkey.glb", 320, 180, root=ref_root)
     fs = sc.flatten()
     assert [it.id for it in fs.items] == [3, 5]                 # lights take ids 1, 2; then (object, material) pairs
     assert len(fs.meshes[0].indices) == 15744 and len(fs.meshes[0].positions) == 3 * 15744   # de-indexed (:853-892)
@@ -146,7 +148,7 @@ def test_gltf_loader_semantics():
     assert all(abs(s - 0.8 * b) < 1e-6 for s, b in zip(m.specular_color, m.base_color))
     assert abs(sc.cam.fov - 0.39959648) < 1e-6 and not sc.cam.is_default_cam()
     # world-space vertices: the node scale 3.024 is baked in, item transforms stay identity
-    obj = load_ref("scene/models/monkey/monkey.obj", 64, 64, root=REF).flatten()
+    obj = load_ref("scene/models/monkey/monkey.obj", 64, 64, root=ref_root).flatten()
     assert np.allclose(fs.meshes[0].positions.max(0), obj.meshes[0].positions.max(0), rtol=1e-4)
     assert np.array_equal(fs.items[0].trans, np.eye(4, dtype=np.float32))
     uv = fs.meshes[1].uvs

@@ -12,7 +12,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --no-cpu-baseline --no-extras $*"
 if [ "$mode" != "quick" ]; then
-  python3 $R/bench.py "$@" > $out/bench_n1.json 2> $out/bench_n1.err || { echo "bench failed"; tail -5 $out/bench_n1.err; exit 1; }
+  python3 $R/bench.py --full "$@" > $out/bench_n1.json 2> $out/bench_n1.err || { echo "bench failed"; tail -5 $out/bench_n1.err; exit 1; }
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $B --steps 3 --warmup 1 > $out/stats_bench.json 2> $out/stats.err || { echo "stats pass failed"; exit 1; }
 pass() { # name, counters...

@@ -14,7 +14,7 @@ tools/profile_round.sh ${R}_spheres quick --scene spheres --width 256 --height 2
 python tools/strong_scaling_probe.py > $G/${R}/scaling.txt 2>&1
 python tools/update_probe.py > $G/${R}/update_probe.txt 2>&1; python tools/update_probe.py helmet_syn >> $G/${R}/update_probe.txt 2>&1
 for n in 2 4; do
-  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2961$n bench.py --gpus $n --steps 3 --warmup 1 --dist-backend gloo --no-cpu-baseline > $G/${R}/gloo_$n.json 2> $out/gloo_$n.err || { echo "gloo $n failed"; tail -5 $out/gloo_$n.err; }
+  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2961$n bench.py --gpus $n --steps 3 --warmup 1 --dist-backend gloo --full --no-cpu-baseline > $G/${R}/gloo_$n.json 2> $out/gloo_$n.err || { echo "gloo $n failed"; tail -5 $out/gloo_$n.err; }
 done
 python bench.py --one-process --gpus 2 --same-device --steps 2 > $G/${R}/one_process.json 2> $out/one_process.err || tail -3 $out/one_process.err
 echo final done
