@@ -8,6 +8,7 @@
 #include "../../include/rustray_hip.h"
 #include "rr_bvh.h"
 #include "rr_device.h"
+#include "rr_frame_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,10 +26,10 @@
 #include <limits>
 #include <map>
 #include <memory>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "rr_kernels.hip"
@@ -119,6 +120,11 @@ extern "C" int rr_test_fault(const char* point, int kind, int skip) {
         if (e_ != hipSuccess)                                                                           \
             return fail(e_ == hipErrorOutOfMemory ? RR_ERR_OUT_OF_MEMORY : RR_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+#define RR_TRY(expr)                                                                                    \
+    do {                                                                                                \
+        const int rc_ = (expr);                                                                         \
+        if (rc_ != RR_OK) return rc_;                                                                   \
+    } while (0)
 
 // ---------------------------------------------------------------------------
 // device buffer helper
@@ -145,7 +151,8 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
-struct TimedLaunch { hipEvent_t a, b; int kind; }; // kind: 0 closest-hit (deeper levels), 4 (level 1); 1 shadow, 6 (level 1); 2 shade, 5 (level 1); 3 binning
+enum TimerKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_BINNING }; // what a timed launch ran (resolve_timers)
+struct TimedLaunch { hipEvent_t a, b; TimerKernel kernel; bool level1; }; // level1: the kernel's level-1 build
 struct ItemHost { uint32_t kind; int32_t material, material_cache; bool visible, flip_normals, mesh_has_normals, mesh_degenerate; int32_t mesh; };
 
 struct rr_scene {
@@ -688,8 +695,9 @@ static int ensure_tlas_reach(rr_scene* s, const double need[3]) {
     HIP_TRY(hipDeviceSynchronize());
     return upload_tlas(s, trees);
 }
-// bound on the primary-ray origins of a camera (primary_ray: view_inv * (proj_inv * (sx, sy, -1, 1)).xyz1, |sx|, |sy| <= smax)
-static void camera_reach(const rr_camera* cam, const rr_config* cfg, double need[3]) {
+// the top level padded for the primary-ray origins of a camera: a bound on them (primary_ray: view_inv * (proj_inv * (sx, sy, -1, 1)).xyz1, |sx|, |sy| <= smax)
+static int ensure_camera_reach(rr_scene* s, const rr_camera* cam, const rr_config* cfg) {
+    double need[3];
     const double aperture = cfg ? std::max(1.0, (double)cfg->aperture_size) : 1.0;
     const double smax = 1.0 + 2.0 * (1.0 + aperture * cam->width / 800.0) * (2.0 / std::max(1u, std::min(cam->width, cam->height)));
     const double v[4] = {smax, smax, 1.0, 1.0};
@@ -703,6 +711,7 @@ static void camera_reach(const rr_camera* cam, const rr_config* cfg, double need
         for (int k = 0; k < 3; k++) m += std::fabs((double)cam->view_inverse[4 * k + c]) * pp[k];
         need[c] = m * 1.001;
     }
+    return ensure_tlas_reach(s, need);
 }
 
 // DSceneView::flat_normals from the items and triangles on the device (k_world_normals); after every upload of the items' transforms
@@ -1147,36 +1156,68 @@ static hipEvent_t take_event(rr_scene* s) {
     return e;
 }
 struct ScopedTimer {
-    rr_scene* s; hipStream_t st; int kind; hipEvent_t a = nullptr, b = nullptr;
-    ScopedTimer(rr_scene* s_, hipStream_t st_, int kind_) : s(s_), st(st_), kind(kind_) {
+    rr_scene* s; hipStream_t st; TimerKernel kernel; bool level1; hipEvent_t a = nullptr, b = nullptr;
+    ScopedTimer(rr_scene* s_, hipStream_t st_, TimerKernel kernel_, bool level1_) : s(s_), st(st_), kernel(kernel_), level1(level1_) {
         if (s->profiling) { a = take_event(s); b = take_event(s); (void)hipEventRecord(a, st); }
     }
-    ~ScopedTimer() { if (s->profiling) { (void)hipEventRecord(b, st); s->timed.push_back(TimedLaunch{a, b, kind}); } }
+    ~ScopedTimer() { if (s->profiling) { (void)hipEventRecord(b, st); s->timed.push_back(TimedLaunch{a, b, kernel, level1}); } }
+};
+
+// the rr_frame_stats fields of each TimerKernel: every launch, and the launches of its level-1 build (binning: time only)
+static const struct {
+    double rr_frame_stats::*ms; uint64_t rr_frame_stats::*launches;
+    double rr_frame_stats::*ms_level1; uint64_t rr_frame_stats::*launches_level1;
+} k_timer_fields[] = {
+    {&rr_frame_stats::ms_trace_closest, &rr_frame_stats::launches_trace_closest, &rr_frame_stats::ms_trace_closest_level1, &rr_frame_stats::launches_trace_closest_level1},
+    {&rr_frame_stats::ms_trace_shadow, &rr_frame_stats::launches_trace_shadow, &rr_frame_stats::ms_trace_shadow_level1, &rr_frame_stats::launches_trace_shadow_level1},
+    {&rr_frame_stats::ms_shade, &rr_frame_stats::launches_shade, &rr_frame_stats::ms_shade_level1, &rr_frame_stats::launches_shade_level1},
+    {&rr_frame_stats::ms_binning, nullptr, nullptr, nullptr},
 };
 
 static void resolve_timers(rr_scene* s) {
     for (auto& t : s->timed) {
         float ms = 0.0f;
         if (hipEventSynchronize(t.b) == hipSuccess && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
-            if (t.kind == 0 || t.kind == 4) { s->stats.ms_trace_closest += ms; s->stats.launches_trace_closest++; }
-            if (t.kind == 4) { s->stats.ms_trace_closest_level1 += ms; s->stats.launches_trace_closest_level1++; }
-            if (t.kind == 1 || t.kind == 6) { s->stats.ms_trace_shadow += ms; s->stats.launches_trace_shadow++; }
-            if (t.kind == 6) { s->stats.ms_trace_shadow_level1 += ms; s->stats.launches_trace_shadow_level1++; }
-            if (t.kind == 2 || t.kind == 5) { s->stats.ms_shade += ms; s->stats.launches_shade++; }
-            if (t.kind == 5) { s->stats.ms_shade_level1 += ms; s->stats.launches_shade_level1++; }
-            else if (t.kind == 3) { s->stats.ms_binning += ms; }
+            const auto& f = k_timer_fields[t.kernel];
+            s->stats.*f.ms += ms;
+            if (f.launches) s->stats.*f.launches += 1;
+            if (t.level1) { s->stats.*f.ms_level1 += ms; s->stats.*f.launches_level1 += 1; }
         }
         s->event_pool.push_back(t.a); s->event_pool.push_back(t.b);
     }
     s->timed.clear();
 }
 
+// ---- the output buffers of a frame, in rr_frame order, and their bytes per pixel: rgba8, normal (3 x f32), depth, object_id
+static const size_t OUT_ELEM[4] = {4, 12, 4, 4};
+static void* out_buffer(const rr_frame& f, int k) {
+    void* const b[4] = {f.rgba8, f.normal, f.depth, f.object_id};
+    return b[k];
+}
+// The device frame behind a frame for the host: s->tmp_out[k] of np pixels for every buffer `host` asks for, zeroed on request.
+static int stage_outputs(rr_scene* s, const rr_frame& host, size_t np, bool zero, rr_frame* dev) {
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++) {
+        if (!out_buffer(host, k)) continue;
+        HIP_TRY(s->tmp_out[k].reserve(np * OUT_ELEM[k]));
+        p[k] = s->tmp_out[k].p;
+        if (zero) HIP_TRY(hipMemsetAsync(p[k], 0, np * OUT_ELEM[k], nullptr));
+    }
+    *dev = rr_frame{(uint8_t*)p[0], (float*)p[1], (float*)p[2], (uint32_t*)p[3]};
+    return RR_OK;
+}
+// dev -> host for every buffer both have (np pixels each), on stream st; returns when they are on the host
+static int copy_outputs(const rr_frame& host, const rr_frame& dev, size_t np, hipStream_t st) {
+    for (int k = 0; k < 4; k++)
+        if (out_buffer(host, k) && out_buffer(dev, k))
+            HIP_TRY(hipMemcpyAsync(out_buffer(host, k), out_buffer(dev, k), np * OUT_ELEM[k], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RR_OK;
+}
+
 // Progressive preview (rr_render_progressive): after every device batch that ends on a whole slice of samples the
-// accumulators are resolved over the samples finished so far and handed to the caller.
-struct PassHook {
-    rr_pass_fn fn; void* user; uint32_t min_passes;
-    void* host[4]; size_t bytes[4];
-};
+// accumulators are resolved over the samples finished so far and handed to the caller (the device frame -> `host`).
+struct PassHook { rr_pass_fn fn; void* user; uint32_t min_passes; const rr_frame* host; };
 
 // The ONE place that launches the closest-hit kernel: the frame path (run_level), rr_pick and rr_trace_rays all come through here, so a
 // change to the kernel's arguments cannot leave one caller behind.  (Round 3, scratch run r3c50: a variant whose LEVEL-1 build stored
@@ -1201,81 +1242,71 @@ static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t
     return RR_OK;
 }
 
-static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
-                                const rr_region* rg, const rr_frame* out, bool frame_layout, hipStream_t st, const volatile int* cancel,
-                                const PassHook* hook = nullptr) {
-    HIP_TRY(hipSetDevice(s->device));
-    if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
-    const uint32_t W = cam->width, H = cam->height;
-    if ((uint64_t)W * H > (1ull << 30)) return fail(RR_ERR_UNSUPPORTED, "frame of %ux%u pixels", W, H);
-    // ---- region map
-    if (memcmp(&s->region_cached, rg, sizeof *rg) != 0 || s->region_w != W || s->region_h != H) {
-        std::vector<uint32_t> order;
-        fill_region(W, H, *rg, &s->h_region_xy, &order);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(s->region_xy.reserve(std::max<size_t>(s->h_region_xy.size(), 1) * 4));
-        HIP_TRY(s->trace_order.reserve(std::max<size_t>(order.size(), 1) * 4));
-        if (!s->h_region_xy.empty()) {
-            // slot_xy[j] = pixel of accumulator slot j; slot_out[j] = its index in the compact output order
-            std::vector<uint32_t> slot_xy(order.size());
-            for (size_t j = 0; j < order.size(); j++) slot_xy[j] = s->h_region_xy[order[j]];
-            HIP_TRY(hipMemcpy(s->region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(s->trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
-        }
-        s->region_cached = *rg; s->region_w = W; s->region_h = H;
-    }
-    const uint32_t npix = (uint32_t)s->h_region_xy.size();
-    resolve_timers(s); // launches of an earlier frame nobody asked about must not leak into this frame's stats
-    memset(&s->stats, 0, sizeof s->stats);
-    s->stats_final = false;
-    if (npix == 0) return RR_OK;
+// ---- the steps of a frame (render_region_locked)
 
-    { // the top level's boxes must be padded for this camera's distance from the origin
-        double need[3];
-        camera_reach(cam, cfg, need);
-        int rc = ensure_tlas_reach(s, need);
-        if (rc != RR_OK) return rc;
+// the region's accumulator slots on the device (slot -> pixel, slot -> output index), uploaded when the region changes
+static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_region& rg, hipStream_t st) {
+    if (memcmp(&s->region_cached, &rg, sizeof rg) == 0 && s->region_w == W && s->region_h == H) return RR_OK;
+    std::vector<uint32_t> order;
+    fill_region(W, H, rg, &s->h_region_xy, &order);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(s->region_xy.reserve(std::max<size_t>(s->h_region_xy.size(), 1) * 4));
+    HIP_TRY(s->trace_order.reserve(std::max<size_t>(order.size(), 1) * 4));
+    if (!s->h_region_xy.empty()) {
+        // slot_xy[j] = pixel of accumulator slot j; slot_out[j] = its index in the compact output order
+        std::vector<uint32_t> slot_xy(order.size());
+        for (size_t j = 0; j < order.size(); j++) slot_xy[j] = s->h_region_xy[order[j]];
+        HIP_TRY(hipMemcpy(s->region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
     }
+    s->region_cached = rg; s->region_w = W; s->region_h = H;
+    return RR_OK;
+}
 
-    // ---- frame constants
+// the frame constants of a camera and config (n_region_pixels is the caller's)
+static DFrame make_frame(const rr_camera* cam, const rr_config* cfg) {
     DFrame fr;
     memset(&fr, 0, sizeof fr);
     memcpy(fr.proj_inv, cam->projection_inverse, 64);
     memcpy(fr.view_inv, cam->view_inverse, 64);
-    fr.width = W; fr.height = H; fr.samples = cfg->samples; fr.cell_size = cell_size_of(cfg->samples);
+    fr.width = cam->width; fr.height = cam->height; fr.samples = cfg->samples; fr.cell_size = cell_size_of(cfg->samples);
     fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u; fr.gamma = cfg->gamma_correction ? 1u : 0u;
     fr.dof = (cfg->aperture_size > 1.0f && cfg->focal_length > 1.0f) ? 1u : 0u;
     fr.focal_length = cfg->focal_length; fr.aperture_size = cfg->aperture_size; fr.fog_density = cfg->fog_density;
     for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
     fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
-    fr.n_region_pixels = npix;
+    return fr;
+}
 
-    // ---- the shade kernel's constants (scene view + frame), read from device memory
-    {
-        DShadeConst hc;
-        hc.sc = s->view; hc.fr = fr;
-        HIP_TRY(s->shade_const.reserve(sizeof hc));
-        HIP_TRY(hipMemcpyAsync(s->shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st)); // `hc` is a stack local
-    }
+// the shade kernel's constants (scene view + frame), read from device memory
+static int upload_shade_const(rr_scene* s, const DFrame& fr, hipStream_t st) {
+    DShadeConst hc;
+    hc.sc = s->view; hc.fr = fr;
+    HIP_TRY(s->shade_const.reserve(sizeof hc));
+    HIP_TRY(hipMemcpyAsync(s->shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // `hc` is a stack local
+    return RR_OK;
+}
 
-    // ---- sample table
+static int upload_sample_table(rr_scene* s, uint16_t samples, const uint16_t* sample_xy, hipStream_t st) {
     if (!sample_xy) { // the built-in table depends on the sample count only: built once per count, not once per frame
-        if (s->table_samples != cfg->samples) {
+        if (s->table_samples != samples) {
             s->table_samples = 0; // the cache names a sample count only once its table is complete
-            try { s->table_cache.resize((size_t)cfg->samples * 2); }
+            try { s->table_cache.resize((size_t)samples * 2); }
             catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sub-sample table"); }
-            const int rct = rr_sample_table(cfg->samples, s->table_cache.data(), nullptr);
-            if (rct != RR_OK) return rct;
-            s->table_samples = cfg->samples;
+            RR_TRY(rr_sample_table(samples, s->table_cache.data(), nullptr));
+            s->table_samples = samples;
         }
         sample_xy = s->table_cache.data();
     }
-    HIP_TRY(s->sample_xy.reserve((size_t)cfg->samples * 4));
-    HIP_TRY(hipMemcpyAsync(s->sample_xy.p, sample_xy, (size_t)cfg->samples * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(s->sample_xy.reserve((size_t)samples * 4));
+    HIP_TRY(hipMemcpyAsync(s->sample_xy.p, sample_xy, (size_t)samples * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st)); // the caller's table may be a temporary
+    return RR_OK;
+}
 
-    // ---- accumulators
+// zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all
+static int reset_accumulators(rr_scene* s, uint32_t npix, const rr_frame* out, hipStream_t st, DAccum* acc) {
     HIP_TRY(s->acc_rgb.reserve((size_t)npix * 24));
     HIP_TRY(s->acc_normal.reserve((size_t)npix * 24));
     HIP_TRY(s->acc_depth.reserve((size_t)npix * 8));
@@ -1287,104 +1318,57 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     HIP_TRY(hipMemsetAsync(s->acc_depth.p, 0, (size_t)npix * 8, st));
     HIP_TRY(hipMemsetAsync(s->acc_id.p, 0, (size_t)npix * 4, st));
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, RR_CNT_WORDS * 8, st));
-    DAccum acc{s->acc_rgb.as<long long>(), s->acc_normal.as<long long>(), s->acc_depth.as<long long>(), s->acc_id.as<uint32_t>(), (unsigned long long)npix,
-               s->acc_flags.as<uint32_t>()};
-    // aux outputs the caller did not ask for are not accumulated at all
-    if (!out->normal) acc.normal = nullptr;
-    if (!out->depth) acc.depth = nullptr;
-    if (!out->object_id) acc.object_id = nullptr;
+    *acc = DAccum{s->acc_rgb.as<long long>(), out->normal ? s->acc_normal.as<long long>() : nullptr, out->depth ? s->acc_depth.as<long long>() : nullptr,
+                  out->object_id ? s->acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->acc_flags.as<uint32_t>()};
+    return RR_OK;
+}
 
-    // ---- ray memory.  All live depth levels of a batch sit in ONE arena of ray records (56 B each), level d + 1
-    // stacked behind level d.  A level of n rays spawns at most 2 n children; if they fit behind it the level is
-    // shaded in one go, otherwise in slices whose children fit, each slice's subtree finished (depth first) before
-    // the next slice starts.  So capacity never limits correctness, only how large the launches can be -- and launch
-    // size matters: the persistent trace kernels lose 8-15 % to ramp-up and tail per launch at 12 M rays
-    // (reserving the worst case 2^(d-1) growth per level, as the first version did, capped batches there).
-    const uint32_t R = cfg->max_recursion;
-    // Arena memory: a quarter of what is free on the device, at most 64 GB (MI355X has 288 GB of HBM3E),
-    // unless rr_tuning::queue_budget_bytes says otherwise.  Memory already held by this scene's arena counts as free.
-    uint64_t budget;
-    if (s->tuning.queue_budget_bytes) budget = s->tuning.queue_budget_bytes;
-    else {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        budget = std::min<uint64_t>((free_b + 56ull * s->arena_cap + s->hit1.bytes) / 4, 64ull << 30);
-    }
-    const uint64_t total_primary = (uint64_t)npix * cfg->samples;
-    const uint64_t LEVEL_MAX = 0x7fffff00ull; // ray indices are 32-bit
-    // Level 1 (the primary rays) needs only its 16-B hit records: the rays themselves are derived from their index
-    // (primary_ray).  The arena holds the deeper levels; 2 arena rays per primary ray cover every level of a typical
-    // frame at once (sponza_syn: all deeper levels together hold 4 % of the primaries), sliced when a scene branches more.
-    const uint64_t per_primary = 16ull + 2ull * 56ull;
-    uint64_t B = std::max<uint64_t>(budget / per_primary, 4096);
-    B = std::min<uint64_t>(B, std::min<uint64_t>(total_primary, LEVEL_MAX));
-    if (hook && hook->min_passes > 1) B = std::min<uint64_t>(B, std::max<uint64_t>(npix, (total_primary + hook->min_passes - 1) / hook->min_passes));
-    // equal batches (a frame that needs 1.2 batches would otherwise end with a small, poorly filled one)
-    { const uint64_t nb = (total_primary + B - 1) / B; B = (total_primary + nb - 1) / nb; }
-    if (B > npix) B = ((B + npix - 1) / npix) * npix; // whole sample slices when possible
-    // Sample grouping: a packet of 64 primary rays = 64/G neighbouring pixels x G samples of each (primary_ray), so the
-    // rays of a wave - and the shadow rays and children they spawn - start almost identical and their walks stay
-    // together.  The largest group the sample count allows is best (closest-hit -30 % on sponza_syn at G = 64 against
-    // one sample of 64 pixels), given that the wave merges its accumulator adds per pixel first (accum_merged): 64
-    // lanes adding to one address otherwise cost more than the walks gain.  Needs whole groups per batch.
-    uint32_t G = 1;
-    {
-        const uint32_t forced = s->tuning.sample_group; // 0 = automatic
-        for (uint32_t g = forced ? forced : 64u; g >= 2; g >>= 1)
-            if (g <= 64 && !(g & (g - 1)) && cfg->samples % g == 0 && npix % (RR_WAVE / g) == 0 && (uint64_t)npix * g <= B) { G = g; break; }
-        if (forced && G != forced) G = 1;
-    }
-    if (G > 1) {
-        // whole groups per batch, batches as equal as whole groups allow
-        const uint64_t unit = (uint64_t)npix * G, units_max = B / unit, total_units = total_primary / unit;
-        const uint64_t nb = (total_units + units_max - 1) / units_max;
-        B = ((total_units + nb - 1) / nb) * unit;
-    }
-    B = std::min<uint64_t>(B, total_primary);
-    // arena (levels 2 and deeper): 2 rays per primary ray, or 7 where that stays under 16 GB (a branching scene then fits
-    // on its first frame too), or `arena_factor` after a frame that had to slice -- always within the budget
-    const uint64_t after_hits = budget > 16ull * B ? (budget - 16ull * B) / 56ull : 0ull;
-    const uint64_t roomy = std::min<uint64_t>(7 * B, (16ull << 30) / 56ull);
-    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(2 * B, roomy), (uint64_t)s->arena_factor * B);
-    const uint64_t M = std::min<uint64_t>(std::min<uint64_t>(want, std::max<uint64_t>(2 * B, after_hits)) + 2ull * RR_BLOCK * (R + 1), LEVEL_MAX);
+// Ray memory (rr_frame_plan.h): a quarter of what is free on the device, at most 64 GB (MI355X has 288 GB of HBM3E),
+// unless rr_tuning::queue_budget_bytes says otherwise.  Memory already held by this scene's arena counts as free.
+static int queue_budget(rr_scene* s, uint64_t* budget) {
+    if (s->tuning.queue_budget_bytes) { *budget = s->tuning.queue_budget_bytes; return RR_OK; }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    *budget = std::min<uint64_t>((free_b + 56ull * s->arena_cap + s->hit1.bytes) / 4, 64ull << 30);
+    return RR_OK;
+}
+
+// the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue (grown, never shrunk)
+static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan) {
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan& p = *plan = plan_frame(FramePlanInputs{npix, cfg->samples, cfg->max_recursion, budget, s->tuning.sample_group, min_passes,
+                                                            s->arena_factor, s->n_enabled_lights, s->tuning.shade_chunk_rays});
     const size_t elem[4] = {16, 16, 8, 16};
-    if (M > s->arena_cap) {
-        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(M * elem[k]));
-        s->arena_cap = M;
+    if (p.M > s->arena_cap) {
+        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(p.M * elem[k]));
+        s->arena_cap = p.M;
     }
-    HIP_TRY(s->hit1.reserve(B * 16));
-    // (the shadow queue holds one 48-B ray per hit of the chunk and ENABLED light: with many lights the chunk shrinks so that
-    // the queue stays within 16 GB -- the reference has no limit on lights, src/raytracing.rs:814)
-    const uint64_t chunk_by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(s->n_enabled_lights, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
-    const uint64_t chunk = std::min<uint64_t>(s->tuning.shade_chunk_rays ? std::max<uint64_t>(65536, s->tuning.shade_chunk_rays) : (64ull << 20), chunk_by_lights);
-    // level 1: fixed shadow slots, (enabled light, hit of the chunk), the chunk padded to whole workgroup iterations;
-    // deeper levels: the dense sharded queue (a shard's static share of the chunk, one slack group per shard)
-    const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, std::max<uint64_t>(M, B)) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(s->n_enabled_lights, 1u));
-    if (sq_need > s->sq_cap) {
-        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(sq_need * 16));
-        HIP_TRY(s->sq_valid.reserve((sq_need / RR_WAVE + 1) * 8));
-        s->sq_cap = sq_need;
+    HIP_TRY(s->hit1.reserve(p.B * 16));
+    if (p.sq_need > s->sq_cap) {
+        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(p.sq_need * 16));
+        HIP_TRY(s->sq_valid.reserve((p.sq_need / RR_WAVE + 1) * 8));
+        s->sq_cap = p.sq_need;
     }
-    auto queue_at = [&](uint64_t base) {
-        DRayQueue q;
-        q.r0 = s->arena[0].as<float4>() + base; q.r1 = s->arena[1].as<float4>() + base;
-        q.r2 = s->arena[2].as<uint2>() + base; q.hit = s->arena[3].as<uint4>() + base;
-        return q;
-    };
-    DShadowQueue SQ{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()};
+    return RR_OK;
+}
 
-    uint32_t* pool = s->pool.as<uint32_t>();
-    unsigned long long* counters = s->counters.as<unsigned long long>();
-    const int shadow_grid = s->n_cus * RR_SHADOW_WAVES; // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
-    const int shade_grid_max = s->n_cus * 2 * RR_SHADE_WAVES;
-    const uint32_t L = s->n_enabled_lights;
-
+// Per-batch counters (level sizes, fetch heads, shadow shard counts) come out of zeroed segments of POOL_WORDS words.  A segment
+// is never recycled inside a batch (launches still in flight and the levels above in the recursion hold pointers into it); a
+// batch with more launches than one segment serves (a deeply branching scene in a very small ray arena) gets another one.
+struct CounterPool {
+    rr_scene* s; hipStream_t st;
+    uint32_t* pool = nullptr;
     uint32_t next_word = 0;
     size_t pool_segment = 0; // 0 = s->pool, k = s->pool_more[k - 1]
-    // Per-batch counters come out of zeroed segments of POOL_WORDS words.  A segment is never recycled inside a batch
-    // (launches still in flight and the levels above in the recursion hold pointers into it); a batch with more
-    // launches than one segment serves (a deeply branching scene in a very small ray arena) gets another one.
-    auto words = [&](uint32_t n) -> uint32_t* {
+    int start_batch() {
+        pool = s->pool.as<uint32_t>(); pool_segment = 0;
+        HIP_TRY(hipMemsetAsync(pool, 0, POOL_WORDS * 4, st));
+        next_word = 0;
+        return RR_OK;
+    }
+    // n zeroed words; nullptr = no memory for another segment
+    uint32_t* take(uint32_t n) {
         if (next_word + n > POOL_WORDS) {
             if (pool_segment == s->pool_more.size()) {
                 if (s->pool_more.size() >= 255) return nullptr; // 4 GB of counters: something else is wrong
@@ -1396,148 +1380,200 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
             next_word = 0;
         }
         uint32_t* p = pool + next_word; next_word += n; return p;
-    };
-    // One depth level: rays [base, base + n) of the arena, their count also in the device word `count`.
-    // The size of the next level is read back once per slice (4 bytes + stream sync), so launches are sized by the
-    // rays that exist and empty levels are never launched.
-    // depth level 1 = the batch's primary rays [pr.first, pr.first + pr.n): only hit records (hit1); its children start the arena
-    DPrimary pr{s->sample_xy.as<uint16_t>(), 0ull, 0u, 1u};
-    std::function<int(uint32_t, uint64_t, uint64_t, uint32_t*)> run_level =
-        [&](uint32_t d, uint64_t base, uint64_t n, uint32_t* count) -> int {
-        DRayQueue qin = queue_at(base);
-        if (d == 1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->hit1.as<uint4>(); }
-        {
-            uint32_t* head = words(1);
-            if (!head) return fail(RR_ERR_UNSUPPORTED, "out of memory for the per-launch counters of a batch");
-            ScopedTimer t(s, st, d == 1 ? 4 : 0);
-            const int rcl = launch_trace_closest(s, d == 1, qin, count, head, n, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), pr, counters, st);
-            if (rcl != RR_OK) return rcl;
-        }
-        const bool spawns = d <= R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
-        const uint64_t child_base = d == 1 ? 0 : base + n;
-        // Children of a slice may use the space behind this level minus what the deeper levels need to make progress
-        // themselves (one 256-ray slice = 512 children per spawning level below): the recursion can then never get stuck.
-        uint64_t slice = n;
-        if (spawns) {
-            const uint64_t keep = 2ull * RR_BLOCK * (R - d); // spawning levels below d + 1's parent: d + 1 .. R
-            const uint64_t room = M - child_base;
-            if (room < keep + 2ull * RR_BLOCK) return fail(RR_ERR_OUT_OF_MEMORY, "ray arena of %llu rays is too small for depth level %u", (unsigned long long)M, d);
-            if (2 * n > room - keep) { slice = ((room - keep) / 2 / RR_BLOCK) * RR_BLOCK; s->stats.sliced_levels++; }
-        }
-        for (uint64_t s0 = 0; s0 < n; s0 += slice) {
-            const uint64_t s1 = std::min<uint64_t>(s0 + slice, n);
-            uint32_t* child_count = words(1);
-            if (!child_count) return fail(RR_ERR_UNSUPPORTED, "out of memory for the per-launch counters of a batch");
-            const DRayQueue qout = queue_at(child_base);
-            for (uint64_t c0 = s0; c0 < s1; c0 += chunk) {
-                if (cancel && *cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
-                const uint64_t c1 = std::min<uint64_t>(c0 + chunk, s1);
-                const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)shade_grid_max);
-                // level 1: shadow slots of this chunk = L x (the chunk padded to whole workgroup iterations), one validity word per 64
-                // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
-                // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
-                // take the dense queue of the deeper levels, which has no such limit
-                const bool sq_fixed = d == 1 && s->view.n_items >= RR_BEAM_MIN_ITEMS && s->view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
-                const uint32_t sq_chunk_cap = sq_fixed ? (uint32_t)(((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK) * RR_BLOCK) : 0u;
-                unsigned long long* sq_valid = s->sq_valid.as<unsigned long long>();
-                // deeper levels: shadow sub-queues, a shard gets the packets with (packet % RR_SQ_SHARDS == shard), L rays per hit at most
-                const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK; // 256-ray groups, dealt round-robin to the shards
-                const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * std::max(L, 1u));
-                next_word = (next_word + 31u) & ~31u; // the append counters start on a 128-B line
-                uint32_t* sq_counts = words(RR_SQ_SHARDS * RR_SQ_STRIDE);
-                uint32_t* shead = words(1);
-                if (!sq_counts || !shead) return fail(RR_ERR_UNSUPPORTED, "out of memory for the per-launch counters of a batch");
-                {
-                    ScopedTimer t(s, st, d == 1 ? 5 : 2);
-                    if (d == 1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), pr, qin, count,
-                                                   (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, acc, counters);
-                    else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), pr, qin, count,
-                                            (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, acc, counters);
-                }
-                // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
-                // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
-                // rays are still being traced, instead of leaving the device idle for a host round trip per level.
-                if (spawns && c1 == s1) {
-                    HIP_TRY(hipMemcpyAsync(s->h_count, child_count, 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipEventRecord(s->count_ready, st));
-                }
-                if (L) {
-                    ScopedTimer t(s, st, sq_fixed ? 6 : 1); // (by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
-                    if (sq_fixed) {
-                        const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
-                        const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)shadow_grid);
-                        hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->view, SQ, sq_counts, segcap, sq_valid, sq_packets, shead, acc);
-                    } else {
-                        const uint64_t sq_ub = (c1 - c0) * L;
-                        const int sgrid = (int)std::min<uint64_t>((sq_ub + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)shadow_grid);
-                        hipLaunchKernelGGL(k_trace_shadow<false>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->view, SQ, sq_counts, segcap, sq_valid, 0u, shead, acc);
-                    }
-                }
-            }
-            if (!spawns) continue;
-            HIP_TRY(hipEventSynchronize(s->count_ready));
-            const uint64_t m = *s->h_count;
-            if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
-            if (m == 0) continue;
-            // On request (rr_tuning::bin_min_rays) deeper levels are traced in bins of (origin cell, direction octant) when
-            // the sorted copy fits behind the unsorted one (rr_kernels.hip: ray binning; off by default, it does not pay).
-            uint64_t level_base = child_base;
-            const uint64_t bin_min = s->tuning.bin_min_rays;
-            if (bin_min != 0 && m >= bin_min && M - child_base >= 3 * m + 2ull * RR_BLOCK * (R + 1)) {
-                next_word = (next_word + 31u) & ~31u;
-                int* bounds = (int*)words(8);
-                uint32_t* hist = words(RR_BIN_COUNT);
-                if (bounds && hist) {
-                    const int init[8] = {0x7f7fffff, 0x7f7fffff, 0x7f7fffff, (int)0x80800000, (int)0x80800000, (int)0x80800000, 0, 0}; // ordered(+FLT_MAX) x3, ordered(-FLT_MAX) x3
-                    HIP_TRY(hipMemcpyAsync(bounds, init, sizeof init, hipMemcpyHostToDevice, st));
-                    const DRayQueue qsrc = queue_at(child_base), qdst = queue_at(child_base + m);
-                    const int g = (int)std::min<uint64_t>((m + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8);
-                    ScopedTimer t(s, st, 3);
-                    hipLaunchKernelGGL(k_bin_bounds, dim3(g), dim3(RR_BLOCK), 0, st, qsrc, (uint32_t)m, bounds);
-                    hipLaunchKernelGGL(k_bin_count, dim3(g), dim3(RR_BLOCK), 0, st, qsrc, (uint32_t)m, bounds, hist);
-                    hipLaunchKernelGGL(k_bin_prefix, dim3(1), dim3(1024), 0, st, hist);
-                    hipLaunchKernelGGL(k_bin_scatter, dim3(g), dim3(RR_BLOCK), 0, st, qsrc, qdst, (uint32_t)m, hist);
-                    level_base = child_base + m;
-                    s->stats.binned_rays += m;
-                }
-            }
-            { const int rc2 = run_level(d + 1, level_base, m, child_count); if (rc2 != RR_OK) return rc2; }
-        }
-        return RR_OK;
-    };
+    }
+    void align_line() { next_word = (next_word + 31u) & ~31u; } // the next words start on a 128-B line
+};
+static int counters_exhausted() { return fail(RR_ERR_UNSUPPORTED, "out of memory for the per-launch counters of a batch"); }
 
-    HIP_TRY(hipEventRecord(s->frame_a, st));
+// what the depth levels of a frame share
+struct FrameRun {
+    rr_scene* s; hipStream_t st;
+    FramePlan plan; uint32_t R;
+    DShadowQueue SQ; DAccum acc;
+    CounterPool pool;
+    DPrimary pr; // the batch being traced: depth level 1
+    const volatile int* cancel;
+    int shadow_grid, shade_grid_max;
+    DRayQueue queue_at(uint64_t base) const {
+        return DRayQueue{s->arena[0].as<float4>() + base, s->arena[1].as<float4>() + base, s->arena[2].as<uint2>() + base, s->arena[3].as<uint4>() + base};
+    }
+};
+
+// On request (rr_tuning::bin_min_rays) a deeper level of m rays at child_base is traced in bins of (origin cell, direction octant)
+// when the sorted copy fits behind the unsorted one (rr_kernels.hip: ray binning; off by default, it does not pay).
+// *level_base = child_base + m (the sorted copy) when the level was binned.
+static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* level_base) {
+    rr_scene* s = f.s;
+    const uint64_t bin_min = s->tuning.bin_min_rays;
+    if (bin_min == 0 || m < bin_min || f.plan.M - child_base < 3 * m + 2ull * RR_BLOCK * (f.R + 1)) return RR_OK;
+    f.pool.align_line();
+    int* bounds = (int*)f.pool.take(8);
+    uint32_t* hist = f.pool.take(RR_BIN_COUNT);
+    if (!bounds || !hist) return RR_OK;
+    const int init[8] = {0x7f7fffff, 0x7f7fffff, 0x7f7fffff, (int)0x80800000, (int)0x80800000, (int)0x80800000, 0, 0}; // ordered(+FLT_MAX) x3, ordered(-FLT_MAX) x3
+    HIP_TRY(hipMemcpyAsync(bounds, init, sizeof init, hipMemcpyHostToDevice, f.st));
+    const DRayQueue qsrc = f.queue_at(child_base), qdst = f.queue_at(child_base + m);
+    const int g = (int)std::min<uint64_t>((m + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8);
+    ScopedTimer t(s, f.st, TK_BINNING, false);
+    hipLaunchKernelGGL(k_bin_bounds, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds);
+    hipLaunchKernelGGL(k_bin_count, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds, hist);
+    hipLaunchKernelGGL(k_bin_prefix, dim3(1), dim3(1024), 0, f.st, hist);
+    hipLaunchKernelGGL(k_bin_scatter, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, qdst, (uint32_t)m, hist);
+    *level_base = child_base + m;
+    s->stats.binned_rays += m;
+    return RR_OK;
+}
+
+// One depth level: rays [base, base + n) of the arena, their count also in the device word `count`.
+// The size of the next level is read back once per slice (4 bytes + stream sync), so launches are sized by the
+// rays that exist and empty levels are never launched.
+// depth level 1 = the batch's primary rays [pr.first, pr.first + pr.n): only hit records (hit1); its children start the arena
+static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_t* count) {
+    rr_scene* s = f.s;
+    const hipStream_t st = f.st;
+    const uint32_t L = s->n_enabled_lights;
+    unsigned long long* counters = s->counters.as<unsigned long long>();
+    DRayQueue qin = f.queue_at(base);
+    if (d == 1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->hit1.as<uint4>(); }
+    {
+        uint32_t* head = f.pool.take(1);
+        if (!head) return counters_exhausted();
+        ScopedTimer t(s, st, TK_CLOSEST, d == 1);
+        RR_TRY(launch_trace_closest(s, d == 1, qin, count, head, n, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, counters, st));
+    }
+    const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
+    const uint64_t M = f.plan.M, child_base = d == 1 ? 0 : base + n;
+    const uint64_t slice = level_slice(M, child_base, n, d, f.R);
+    if (slice == 0) return fail(RR_ERR_OUT_OF_MEMORY, "ray arena of %llu rays is too small for depth level %u", (unsigned long long)M, d);
+    if (slice < n) s->stats.sliced_levels++;
+    for (uint64_t s0 = 0; s0 < n; s0 += slice) {
+        const uint64_t s1 = std::min<uint64_t>(s0 + slice, n);
+        uint32_t* child_count = f.pool.take(1);
+        if (!child_count) return counters_exhausted();
+        const DRayQueue qout = f.queue_at(child_base);
+        for (uint64_t c0 = s0; c0 < s1; c0 += f.plan.chunk) {
+            if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+            const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
+            const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);
+            // level 1: shadow slots of this chunk = L x (the chunk padded to whole workgroup iterations), one validity word per 64
+            // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
+            // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
+            // take the dense queue of the deeper levels, which has no such limit
+            const bool sq_fixed = d == 1 && s->view.n_items >= RR_BEAM_MIN_ITEMS && s->view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
+            const uint32_t sq_chunk_cap = sq_fixed ? (uint32_t)(((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK) * RR_BLOCK) : 0u;
+            unsigned long long* sq_valid = s->sq_valid.as<unsigned long long>();
+            // deeper levels: shadow sub-queues, a shard gets the packets with (packet % RR_SQ_SHARDS == shard), L rays per hit at most
+            const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK; // 256-ray groups, dealt round-robin to the shards
+            const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * std::max(L, 1u));
+            f.pool.align_line(); // the append counters start on a 128-B line
+            uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
+            uint32_t* shead = f.pool.take(1);
+            if (!sq_counts || !shead) return counters_exhausted();
+            {
+                ScopedTimer t(s, st, TK_SHADE, d == 1);
+                if (d == 1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, qin, count,
+                                               (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+                else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, qin, count,
+                                        (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+            }
+            // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
+            // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
+            // rays are still being traced, instead of leaving the device idle for a host round trip per level.
+            if (spawns && c1 == s1) {
+                HIP_TRY(hipMemcpyAsync(s->h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(s->count_ready, st));
+            }
+            if (L) {
+                ScopedTimer t(s, st, TK_SHADOW, sq_fixed); // (by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
+                if (sq_fixed) {
+                    const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
+                    const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
+                    hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->view, f.SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
+                } else {
+                    const uint64_t sq_ub = (c1 - c0) * L;
+                    const int sgrid = (int)std::min<uint64_t>((sq_ub + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
+                    hipLaunchKernelGGL(k_trace_shadow<false>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->view, f.SQ, sq_counts, segcap, sq_valid, 0u, shead, f.acc);
+                }
+            }
+        }
+        if (!spawns) continue;
+        HIP_TRY(hipEventSynchronize(s->count_ready));
+        const uint64_t m = *s->h_count;
+        if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
+        if (m == 0) continue;
+        uint64_t level_base = child_base;
+        RR_TRY(bin_level(f, child_base, m, &level_base));
+        RR_TRY(run_level(f, d + 1, level_base, m, child_count));
+    }
+    return RR_OK;
+}
+
+static void launch_resolve(const FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout) {
+    const uint32_t npix = fr.n_region_pixels;
+    hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->region_xy.as<uint32_t>(), f.s->trace_order.as<uint32_t>(),
+                       f.acc, out->rgba8, out->normal, out->depth, out->object_id, frame_layout ? 1u : 0u);
+}
+
+// The frame's batches of primary rays, in order.  After a batch that ends on a whole slice of samples the pass hook
+// (if any) gets the frame resolved over the samples finished so far.
+static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout, const PassHook* hook) {
+    rr_scene* s = f.s;
+    const uint32_t npix = fr.n_region_pixels;
+    const uint64_t B = f.plan.B, total_primary = f.plan.total_primary;
     for (uint64_t first = 0; first < total_primary; first += B) {
-        if (cancel && *cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+        if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
         const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
-        pool = s->pool.as<uint32_t>(); pool_segment = 0;
-        HIP_TRY(hipMemsetAsync(pool, 0, POOL_WORDS * 4, st));
-        next_word = 0;
-        uint32_t* level1_count = words(1);
+        RR_TRY(f.pool.start_batch());
+        uint32_t* level1_count = f.pool.take(1);
         // The batch covers primary indices [first, first + n_batch): index i -> sample i / npix, pixel i % npix.
-        pr.first = first; pr.n = n_batch;
-        pr.group = (n_batch % ((uint64_t)npix * G) == 0 && first % npix == 0) ? G : 1u;
+        f.pr.first = first; f.pr.n = n_batch;
+        f.pr.group = batch_group(f.plan, npix, first, n_batch);
         s->stats.batches++;
-        const int rcl = run_level(1, 0, n_batch, level1_count);
-        if (rcl != RR_OK) return rcl;
+        RR_TRY(run_level(f, 1, 0, n_batch, level1_count));
         HIP_TRY(hipGetLastError());
         // batches are stream-ordered; only a caller that can cancel needs the host to keep pace with the device
-        if (cancel && first + B < total_primary) HIP_TRY(hipStreamSynchronize(st));
+        if (f.cancel && first + B < total_primary) HIP_TRY(hipStreamSynchronize(f.st));
         const uint64_t done = first + n_batch;
         if (hook && hook->fn && done < total_primary && done % npix == 0) {
             DFrame pf = fr;
             pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
-            hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, pf, s->region_xy.as<uint32_t>(), s->trace_order.as<uint32_t>(), acc,
-                               out->rgba8, out->normal, out->depth, out->object_id, frame_layout ? 1u : 0u);
-            void* const dev[4] = {out->rgba8, out->normal, out->depth, out->object_id};
-            for (int k = 0; k < 4; k++)
-                if (hook->host[k] && dev[k]) HIP_TRY(hipMemcpyAsync(hook->host[k], dev[k], hook->bytes[k], hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
+            launch_resolve(f, pf, out, frame_layout);
+            RR_TRY(copy_outputs(*hook->host, *out, (size_t)fr.width * fr.height, f.st));
             if (hook->fn(hook->user, done, total_primary) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
         }
     }
-    hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, fr, s->region_xy.as<uint32_t>(), s->trace_order.as<uint32_t>(), acc,
-                       out->rgba8, out->normal, out->depth, out->object_id, frame_layout ? 1u : 0u);
+    return RR_OK;
+}
+
+static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                                const rr_region* rg, const rr_frame* out, bool frame_layout, hipStream_t st, const volatile int* cancel,
+                                const PassHook* hook = nullptr) {
+    HIP_TRY(hipSetDevice(s->device));
+    if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
+    const uint32_t W = cam->width, H = cam->height;
+    if ((uint64_t)W * H > (1ull << 30)) return fail(RR_ERR_UNSUPPORTED, "frame of %ux%u pixels", W, H);
+    RR_TRY(update_region_map(s, W, H, *rg, st));
+    const uint32_t npix = (uint32_t)s->h_region_xy.size();
+    resolve_timers(s); // launches of an earlier frame nobody asked about must not leak into this frame's stats
+    memset(&s->stats, 0, sizeof s->stats);
+    s->stats_final = false;
+    if (npix == 0) return RR_OK;
+    RR_TRY(ensure_camera_reach(s, cam, cfg)); // the top level's boxes must be padded for this camera's distance from the origin
+    DFrame fr = make_frame(cam, cfg);
+    fr.n_region_pixels = npix;
+    RR_TRY(upload_shade_const(s, fr, st));
+    RR_TRY(upload_sample_table(s, cfg->samples, sample_xy, st));
+    DAccum acc;
+    RR_TRY(reset_accumulators(s, npix, out, st, &acc));
+    FramePlan plan;
+    RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
+    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
+               CounterPool{s, st}, DPrimary{s->sample_xy.as<uint16_t>(), 0ull, 0u, 1u}, cancel,
+               s->n_cus * RR_SHADOW_WAVES, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
+               s->n_cus * 2 * RR_SHADE_WAVES};
+    HIP_TRY(hipEventRecord(s->frame_a, st));
+    RR_TRY(run_batches(f, fr, out, frame_layout, hook));
+    launch_resolve(f, fr, out, frame_layout);
     HIP_TRY(hipEventRecord(s->frame_b, st));
     HIP_TRY(hipGetLastError());
     // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)
@@ -1547,10 +1583,8 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
 
 extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
                                        const rr_region* rg, const rr_frame* out, void* hip_stream, const volatile int* cancel) try {
-    int rc = check_frame_args(s, cam, cfg, sample_xy);
-    if (rc != RR_OK) return rc;
-    rc = check_region(cam->width, cam->height, rg);
-    if (rc != RR_OK) return rc;
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
+    RR_TRY(check_region(cam->width, cam->height, rg));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     std::lock_guard<std::mutex> lk(s->mu);
     return render_region_locked(s, cam, cfg, sample_xy, rg, out, false, (hipStream_t)hip_stream, cancel);
@@ -1558,26 +1592,18 @@ extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const 
 
 static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
                           const volatile int* cancel, rr_pass_fn fn, void* user, uint32_t min_passes) {
-    int rc = check_frame_args(s, cam, cfg, sample_xy);
-    if (rc != RR_OK) return rc;
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
     const size_t np = (size_t)cam->width * cam->height;
-    const size_t bytes[4] = {np * 4, np * 12, np * 4, np * 4};
-    void* host[4] = {out->rgba8, out->normal, out->depth, out->object_id};
     rr_frame dev{};
-    void** devp[4] = {(void**)&dev.rgba8, (void**)&dev.normal, (void**)&dev.depth, (void**)&dev.object_id};
-    for (int k = 0; k < 4; k++)
-        if (host[k]) { HIP_TRY(s->tmp_out[k].reserve(bytes[k])); *devp[k] = s->tmp_out[k].p; }
+    RR_TRY(stage_outputs(s, *out, np, false, &dev));
     rr_region whole{8, 8, 1, 0}; // 8x8 tiles: one wave = one tile of primary rays
-    PassHook hook{fn, user, min_passes, {host[0], host[1], host[2], host[3]}, {bytes[0], bytes[1], bytes[2], bytes[3]}};
-    rc = render_region_locked(s, cam, cfg, sample_xy, &whole, &dev, true, nullptr, cancel, fn ? &hook : nullptr);
-    if (rc != RR_OK) return rc;
+    PassHook hook{fn, user, min_passes, out};
+    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &whole, &dev, true, nullptr, cancel, fn ? &hook : nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    for (int k = 0; k < 4; k++)
-        if (host[k]) HIP_TRY(hipMemcpy(host[k], s->tmp_out[k].p, bytes[k], hipMemcpyDeviceToHost));
-    return RR_OK;
+    return copy_outputs(*out, dev, np, nullptr);
 }
 
 extern "C" int rr_render(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
@@ -1591,16 +1617,6 @@ extern "C" int rr_render_progressive(rr_scene* s, const rr_camera* cam, const rr
     return render_to_host(s, cam, cfg, sample_xy, out, cancel, on_pass, user, min_passes);
 } RR_GUARD_END("rr_render_progressive")
 
-static int collect_stats_locked(rr_scene* s);
-extern "C" int rr_scene_last_stats(const rr_scene* cs, rr_frame_stats* out) try {
-    if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    rr_scene* s = const_cast<rr_scene*>(cs);
-    std::lock_guard<std::mutex> lk(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->stats_final) { const int rc = collect_stats_locked(s); if (rc != RR_OK) return rc; }
-    *out = s->stats;
-    return RR_OK;
-} RR_GUARD_END("rr_scene_last_stats")
 // the device counters and launch timers of the frame (or pass) that ran last, into s->stats
 static int collect_stats_locked(rr_scene* s) {
     float ms = 0.0f;
@@ -1612,6 +1628,15 @@ static int collect_stats_locked(rr_scene* s) {
     s->stats.shadow_rays = c[RR_CNT_SHADOW]; s->stats.shaded_hits = c[RR_CNT_SHADED];
     return RR_OK;
 }
+extern "C" int rr_scene_last_stats(const rr_scene* cs, rr_frame_stats* out) try {
+    if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    rr_scene* s = const_cast<rr_scene*>(cs);
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->stats_final) { const int rc = collect_stats_locked(s); if (rc != RR_OK) return rc; }
+    *out = s->stats;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_last_stats")
 
 // The frame filled in TILE BY TILE, every pixel final when it appears: what the reference's GUI shows (shuffled 2x2 cells, each rendered with all of
 // its samples: src/renderer.rs:125-172, drained by Run::apply_pixels, src/run.rs:506-545).  Pass k of n_passes renders the 32x8-pixel tiles with
@@ -1619,19 +1644,14 @@ static int collect_stats_locked(rr_scene* s) {
 extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
                                            uint32_t n_passes, rr_pass_fn on_pass, void* user, const volatile int* cancel) try {
     if (!on_pass) return fail(RR_ERR_INVALID_ARGUMENT, "on_pass is required (use rr_render for a one-shot frame)");
-    int rc = check_frame_args(s, cam, cfg, sample_xy);
-    if (rc != RR_OK) return rc;
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
     const uint32_t W = cam->width, H = cam->height, TW = 32, TH = 8;
     const size_t np = (size_t)W * H;
-    const size_t bytes[4] = {np * 4, np * 12, np * 4, np * 4};
-    void* host[4] = {out->rgba8, out->normal, out->depth, out->object_id};
     rr_frame dev{};
-    void** devp[4] = {(void**)&dev.rgba8, (void**)&dev.normal, (void**)&dev.depth, (void**)&dev.object_id};
-    for (int k = 0; k < 4; k++)
-        if (host[k]) { HIP_TRY(s->tmp_out[k].reserve(bytes[k])); *devp[k] = s->tmp_out[k].p; HIP_TRY(hipMemsetAsync(s->tmp_out[k].p, 0, bytes[k], nullptr)); }
+    RR_TRY(stage_outputs(s, *out, np, true, &dev));
     const uint32_t n_tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
     const uint32_t P = std::max(1u, std::min(n_passes ? n_passes : 16u, n_tiles));
     rr_frame_stats sum{};
@@ -1639,11 +1659,9 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
     for (uint32_t k = 0; k < P; k++) {
         if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled");
         const rr_region rg{TW, TH, P, k};
-        rc = render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, true, nullptr, cancel);
-        if (rc != RR_OK) return rc;
+        RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, true, nullptr, cancel));
         HIP_TRY(hipStreamSynchronize(nullptr));
-        rc = collect_stats_locked(s);
-        if (rc != RR_OK) return rc;
+        RR_TRY(collect_stats_locked(s));
         {   // the frame's statistics are the sums over its passes
             const rr_frame_stats& a = s->stats;
             sum.primary_rays += a.primary_rays; sum.secondary_rays += a.secondary_rays; sum.shadow_rays += a.shadow_rays; sum.shaded_hits += a.shaded_hits;
@@ -1654,8 +1672,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
             sum.ms_shade_level1 += a.ms_shade_level1; sum.launches_shade_level1 += a.launches_shade_level1;
             sum.ms_trace_shadow_level1 += a.ms_trace_shadow_level1; sum.launches_trace_shadow_level1 += a.launches_trace_shadow_level1;
         }
-        for (int b = 0; b < 4; b++)
-            if (host[b]) HIP_TRY(hipMemcpy(host[b], s->tmp_out[b].p, bytes[b], hipMemcpyDeviceToHost));
+        RR_TRY(copy_outputs(*out, dev, np, nullptr));
         done += rr_region_pixel_count(W, H, &rg);
         s->stats = sum; s->stats_final = true;
         if (k + 1 < P && on_pass(user, done * cfg->samples, (uint64_t)np * cfg->samples) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
@@ -1690,36 +1707,51 @@ extern "C" int rr_scene_get_tuning(const rr_scene* s, rr_tuning* t) try {
 // ---------------------------------------------------------------------------
 // multi-GPU epilogue: compact per-rank buffers (concatenated in rank order) -> frame order
 // ---------------------------------------------------------------------------
-struct GatherMap { DevBuf index; uint32_t w, h, tw, th, n; int device; };
+// One gather map per (frame size, tiles, ranks, device), each buffer uploaded on first use: per frame pixel its index in the
+// concatenation of all ranks' buffers (k_gather_frame), and its rank and its index among that rank's pixels (k_gather_packed).
+struct GatherMap { DevBuf index, rank, local; };
+using GatherKey = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int>; // width, height, tile_w, tile_h, n_ranks, device
 static std::mutex g_gather_mu;
-static std::vector<GatherMap*> g_gather_maps;
+static std::map<GatherKey, GatherMap>& g_gather_maps = *new std::map<GatherKey, GatherMap>(); // never destroyed: no hipFree after the HIP runtime's teardown
+static int upload_u32(DevBuf* b, const std::vector<uint32_t>& v) {
+    DevBuf d;
+    HIP_TRY(d.reserve(v.size() * 4));
+    HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+    *b = std::move(d);
+    return RR_OK;
+}
+// the map of `key` with `index` (packed = false) or `rank` and `local` (packed = true) on the device; under g_gather_mu
+static int gather_map(const GatherKey& key, bool packed, GatherMap** out) {
+    GatherMap& gm = g_gather_maps[key];
+    *out = &gm;
+    if (packed ? gm.rank.p != nullptr : gm.index.p != nullptr) return RR_OK;
+    const auto [width, height, tile_w, tile_h, n_ranks, device] = key;
+    const uint32_t np = width * height;
+    std::vector<uint32_t> rank(np), local(np), offset(n_ranks), xy;
+    uint32_t base = 0;
+    for (uint32_t r = 0; r < n_ranks; r++) {
+        fill_region(width, height, rr_region{tile_w, tile_h, n_ranks, r}, &xy);
+        for (uint32_t p = 0; p < xy.size(); p++) { const size_t o = (size_t)(xy[p] >> 16) * width + (xy[p] & 0xffffu); rank[o] = r; local[o] = p; }
+        offset[r] = base; base += (uint32_t)xy.size();
+    }
+    if (packed) { // `rank` last: it is what marks the pair as uploaded
+        RR_TRY(upload_u32(&gm.local, local));
+        return upload_u32(&gm.rank, rank);
+    }
+    for (uint32_t o = 0; o < np; o++) local[o] += offset[rank[o]];
+    return upload_u32(&gm.index, local);
+}
 
 extern "C" int rr_deinterleave_device(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n_ranks,
                                       uint32_t elem_bytes, const void* src, void* dst, int device, void* hip_stream) try {
-    rr_region probe{tile_w, tile_h, n_ranks, 0};
-    int rc = check_region(width, height, &probe);
-    if (rc != RR_OK) return rc;
+    const rr_region probe{tile_w, tile_h, n_ranks, 0};
+    RR_TRY(check_region(width, height, &probe));
     if (!src || !dst || elem_bytes == 0 || (elem_bytes & 3u)) return fail(RR_ERR_INVALID_ARGUMENT, "bad buffers or elem_bytes %u", elem_bytes);
     HIP_TRY(hipSetDevice(device));
     std::lock_guard<std::mutex> lk(g_gather_mu);
     GatherMap* gm = nullptr;
-    for (GatherMap* m : g_gather_maps)
-        if (m->w == width && m->h == height && m->tw == tile_w && m->th == tile_h && m->n == n_ranks && m->device == device) gm = m;
+    RR_TRY(gather_map(GatherKey{width, height, tile_w, tile_h, n_ranks, device}, false, &gm));
     const uint32_t np = width * height;
-    if (!gm) {
-        std::vector<uint32_t> index(np), xy;
-        uint32_t base = 0;
-        for (uint32_t r = 0; r < n_ranks; r++) {
-            rr_region rg{tile_w, tile_h, n_ranks, r};
-            fill_region(width, height, rg, &xy);
-            for (uint32_t p = 0; p < xy.size(); p++) index[(size_t)(xy[p] >> 16) * width + (xy[p] & 0xffffu)] = base + p;
-            base += (uint32_t)xy.size();
-        }
-        gm = new GatherMap{DevBuf(), width, height, tile_w, tile_h, n_ranks, device};
-        HIP_TRY(gm->index.reserve((size_t)np * 4));
-        HIP_TRY(hipMemcpy(gm->index.p, index.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-        g_gather_maps.push_back(gm);
-    }
     const uint32_t words = elem_bytes / 4;
     const uint64_t total = (uint64_t)np * words;
     hipLaunchKernelGGL(k_gather_frame, dim3((uint32_t)((total + RR_BLOCK - 1) / RR_BLOCK)), dim3(RR_BLOCK), 0, (hipStream_t)hip_stream,
@@ -1729,14 +1761,11 @@ extern "C" int rr_deinterleave_device(uint32_t width, uint32_t height, uint32_t 
 } RR_GUARD_END("rr_deinterleave_device")
 
 // The gathered packs of a multi-rank frame -> the four frame-order buffers, one launch (k_gather_packed).
-struct GatherMap2 { DevBuf rank, local; uint32_t w, h, tw, th, n; int device; };
-static std::vector<GatherMap2*> g_gather_maps2;
 extern "C" int rr_deinterleave_packed_device(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n_ranks,
                                              const void* packs, uint64_t pack_stride, const uint64_t* section_offset, const uint32_t* elem_bytes,
                                              void* const* dst, int device, void* hip_stream) try {
-    rr_region probe{tile_w, tile_h, n_ranks, 0};
-    int rc = check_region(width, height, &probe);
-    if (rc != RR_OK) return rc;
+    const rr_region probe{tile_w, tile_h, n_ranks, 0};
+    RR_TRY(check_region(width, height, &probe));
     if (!packs || !section_offset || !elem_bytes || !dst) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     DPackedGather g{};
     for (int k = 0; k < 4; k++) {
@@ -1748,23 +1777,9 @@ extern "C" int rr_deinterleave_packed_device(uint32_t width, uint32_t height, ui
     if (g.words_total == 0) return fail(RR_ERR_INVALID_ARGUMENT, "no buffer to move");
     HIP_TRY(hipSetDevice(device));
     std::lock_guard<std::mutex> lk(g_gather_mu);
-    GatherMap2* gm = nullptr;
-    for (GatherMap2* m : g_gather_maps2)
-        if (m->w == width && m->h == height && m->tw == tile_w && m->th == tile_h && m->n == n_ranks && m->device == device) gm = m;
+    GatherMap* gm = nullptr;
+    RR_TRY(gather_map(GatherKey{width, height, tile_w, tile_h, n_ranks, device}, true, &gm));
     const uint32_t np = width * height;
-    if (!gm) {
-        std::vector<uint32_t> rank(np), local(np), xy;
-        for (uint32_t r = 0; r < n_ranks; r++) {
-            rr_region rg{tile_w, tile_h, n_ranks, r};
-            fill_region(width, height, rg, &xy);
-            for (uint32_t p = 0; p < xy.size(); p++) { const size_t o = (size_t)(xy[p] >> 16) * width + (xy[p] & 0xffffu); rank[o] = r; local[o] = p; }
-        }
-        gm = new GatherMap2{DevBuf(), DevBuf(), width, height, tile_w, tile_h, n_ranks, device};
-        HIP_TRY(gm->rank.reserve((size_t)np * 4)); HIP_TRY(gm->local.reserve((size_t)np * 4));
-        HIP_TRY(hipMemcpy(gm->rank.p, rank.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(gm->local.p, local.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-        g_gather_maps2.push_back(gm);
-    }
     g.src_rank = gm->rank.as<uint32_t>(); g.src_local = gm->local.as<uint32_t>();
     g.packs = (const char*)packs; g.pack_stride = pack_stride; g.n_pixels = np;
     const uint64_t total = (uint64_t)np * g.words_total;
@@ -1832,13 +1847,11 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
     for (uint32_t i = 0; i < n_scenes; i++) {
         if (!scenes[i]) return fail(RR_ERR_INVALID_ARGUMENT, "scene %u is NULL", i);
         for (uint32_t j = 0; j < i; j++) if (scenes[j] == scenes[i]) return fail(RR_ERR_INVALID_ARGUMENT, "scene handle %u is passed twice", i);
-        int rc = check_frame_args(scenes[i], cam, cfg, sample_xy);
-        if (rc != RR_OK) return rc;
+        RR_TRY(check_frame_args(scenes[i], cam, cfg, sample_xy));
     }
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     const uint32_t W = cam->width, H = cam->height, TW = 32, TH = 8; // interleaved 32x8 tiles: tile_index % n == device slot
     const size_t np = (size_t)W * H;
-    const size_t esz[4] = {4, 12, 4, 4};
     void* host[4] = {out->rgba8, out->normal, out->depth, out->object_id};
     std::vector<uint64_t> count(n_scenes), offset(n_scenes);
     uint64_t total = 0;
@@ -1867,9 +1880,11 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
     };
     // device 0: the concatenation of the compact buffers (rank order) and the frame-order buffers
     HIP_TRY(hipSetDevice(s0->device));
-    { int rc = own_stream(s0); if (rc != RR_OK) return rc; }
+    RR_TRY(own_stream(s0));
     for (int k = 0; k < 4; k++)
-        if (host[k]) { HIP_TRY(s0->multi_cat[k].reserve(np * esz[k])); HIP_TRY(s0->tmp_out[k].reserve(np * esz[k])); }
+        if (host[k]) HIP_TRY(s0->multi_cat[k].reserve(np * OUT_ELEM[k]));
+    rr_frame frame_dev{};
+    RR_TRY(stage_outputs(s0, *out, np, false, &frame_dev));
     // every device renders its tiles into its own compact buffers on its own stream, then pushes them towards device 0
     std::vector<int> rcs(n_scenes, RR_OK);
     std::vector<std::string> errs(n_scenes);
@@ -1877,22 +1892,21 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
         rr_scene* s = scenes[i];
         auto body = [&]() -> int {
             HIP_TRY(hipSetDevice(s->device));
-            { int rc = own_stream(s); if (rc != RR_OK) return rc; }
+            RR_TRY(own_stream(s));
             rr_frame dev{};
             void** devp[4] = {(void**)&dev.rgba8, (void**)&dev.normal, (void**)&dev.depth, (void**)&dev.object_id};
             for (int k = 0; k < 4; k++) {
                 if (!host[k]) continue;
-                if (i == 0) *devp[k] = (char*)s0->multi_cat[k].p + offset[0] * esz[k]; // device 0 renders straight into its slot
-                else { HIP_TRY(s->multi_part[k].reserve(std::max<uint64_t>(count[i], 1) * esz[k])); *devp[k] = s->multi_part[k].p; }
+                if (i == 0) *devp[k] = (char*)s0->multi_cat[k].p + offset[0] * OUT_ELEM[k]; // device 0 renders straight into its slot
+                else { HIP_TRY(s->multi_part[k].reserve(std::max<uint64_t>(count[i], 1) * OUT_ELEM[k])); *devp[k] = s->multi_part[k].p; }
             }
             rr_region rg{TW, TH, n_scenes, i};
-            int rc = render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, false, s->multi_stream, cancel);
-            if (rc != RR_OK) return rc;
+            RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, false, s->multi_stream, cancel));
             if (i != 0)
                 for (int k = 0; k < 4; k++) {
                     if (!host[k] || !count[i]) continue;
-                    const size_t bytes = count[i] * esz[k];
-                    void* dst = (char*)s0->multi_cat[k].p + offset[i] * esz[k];
+                    const size_t bytes = count[i] * OUT_ELEM[k];
+                    void* dst = (char*)s0->multi_cat[k].p + offset[i] * OUT_ELEM[k];
                     if (direct[i] && s->device == s0->device) HIP_TRY(hipMemcpyAsync(dst, s->multi_part[k].p, bytes, hipMemcpyDeviceToDevice, s->multi_stream));
                     else if (direct[i]) HIP_TRY(hipMemcpyPeerAsync(dst, s0->device, s->multi_part[k].p, s->device, bytes, s->multi_stream));
                     else { // no peer access: device -> pinned host here, host -> device 0 after the join
@@ -1928,16 +1942,11 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
         if (direct[i]) continue;
         for (int k = 0; k < 4; k++)
             if (host[k] && count[i])
-                HIP_TRY(hipMemcpyAsync((char*)s0->multi_cat[k].p + offset[i] * esz[k], scenes[i]->multi_stage[k], count[i] * esz[k], hipMemcpyHostToDevice, s0->multi_stream));
-    }
-    for (int k = 0; k < 4; k++) {
-        if (!host[k]) continue;
-        int rc = rr_deinterleave_device(W, H, TW, TH, n_scenes, (uint32_t)esz[k], s0->multi_cat[k].p, s0->tmp_out[k].p, s0->device, s0->multi_stream);
-        if (rc != RR_OK) return rc;
+                HIP_TRY(hipMemcpyAsync((char*)s0->multi_cat[k].p + offset[i] * OUT_ELEM[k], scenes[i]->multi_stage[k], count[i] * OUT_ELEM[k], hipMemcpyHostToDevice, s0->multi_stream));
     }
     for (int k = 0; k < 4; k++)
-        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], s0->tmp_out[k].p, np * esz[k], hipMemcpyDeviceToHost, s0->multi_stream));
-    HIP_TRY(hipStreamSynchronize(s0->multi_stream));
+        if (host[k]) RR_TRY(rr_deinterleave_device(W, H, TW, TH, n_scenes, (uint32_t)OUT_ELEM[k], s0->multi_cat[k].p, out_buffer(frame_dev, k), s0->device, s0->multi_stream));
+    RR_TRY(copy_outputs(*out, frame_dev, np, s0->multi_stream));
     s0->stats.multi_devices = n_scenes; s0->stats.multi_peer_links = n_peer; s0->stats.multi_staged_links = n_staged;
     s0->stats.ms_multi_exchange = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_joined).count();
     return RR_OK;
@@ -1990,17 +1999,10 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
     if (x < 0 || y < 0 || (uint32_t)x >= cam->width || (uint32_t)y >= cam->height) return fail(RR_ERR_INVALID_ARGUMENT, "pixel (%d,%d) outside %ux%u", x, y, cam->width, cam->height);
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    {
-        double need[3];
-        camera_reach(cam, nullptr, need);
-        int rc = ensure_tlas_reach(s, need);
-        if (rc != RR_OK) return rc;
-    }
-    DFrame fr;
-    memset(&fr, 0, sizeof fr);
-    memcpy(fr.proj_inv, cam->projection_inverse, 64);
-    memcpy(fr.view_inv, cam->view_inverse, 64);
-    fr.width = cam->width; fr.height = cam->height; fr.samples = 1; fr.cell_size = 1; fr.n_region_pixels = 1;
+    RR_TRY(ensure_camera_reach(s, cam, nullptr));
+    const rr_config none{}; // a pick has no frame config
+    DFrame fr = make_frame(cam, &none);
+    fr.samples = 1; fr.cell_size = 1; fr.n_region_pixels = 1;
     DevBuf scratch;
     HIP_TRY(scratch.reserve(256 + sizeof(DShadeConst)));
     // layout: [0] region_xy, [4] sample_xy (2 x u16), [64] hit, [96] count, [100] head, [128] counters, [256] scene view + frame constants
@@ -2013,8 +2015,7 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
     DShadeConst hc;
     hc.sc = s->view; hc.fr = fr;
     HIP_TRY(hipMemcpy(b + 256, &hc, sizeof hc, hipMemcpyHostToDevice));
-    { const int rc = launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), (const uint32_t*)b, pr, (unsigned long long*)(b + 128), nullptr);
-      if (rc != RR_OK) return rc; }
+    RR_TRY(launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), (const uint32_t*)b, pr, (unsigned long long*)(b + 128), nullptr));
     uint32_t hit[4];
     HIP_TRY(hipMemcpy(hit, b + 64, 16, hipMemcpyDeviceToHost));
     scratch.release();
@@ -2047,8 +2048,7 @@ extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* dir
                 const double a = std::fabs((double)origins[3 * (size_t)i + c]) * 1.001;
                 if (std::isfinite(a)) need[c] = std::max(need[c], a);
             }
-        int rc = ensure_tlas_reach(s, need);
-        if (rc != RR_OK) return rc;
+        RR_TRY(ensure_tlas_reach(s, need));
     }
     for (uint32_t i = 0; i < n; i++) {
         r0[i] = make_float4(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], 1.0f);
@@ -2071,9 +2071,8 @@ extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* dir
         HIP_TRY(hipMemcpy(bc.as<char>() + 256, &hc, sizeof hc, hipMemcpyHostToDevice));
     }
     DPrimary pr{nullptr, 0ull, 0u, 1u};
-    { const int rc = launch_trace_closest(s, false, q, bc.as<uint32_t>(), bc.as<uint32_t>() + 1, n, (const DShadeConst*)(bc.as<char>() + 256), nullptr, pr,
-                                          (unsigned long long*)(bc.as<char>() + 128), nullptr);
-      if (rc != RR_OK) return rc; }
+    RR_TRY(launch_trace_closest(s, false, q, bc.as<uint32_t>(), bc.as<uint32_t>() + 1, n, (const DShadeConst*)(bc.as<char>() + 256), nullptr, pr,
+                                (unsigned long long*)(bc.as<char>() + 128), nullptr));
     std::vector<uint4> hits(n);
     HIP_TRY(hipMemcpy(hits.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) {

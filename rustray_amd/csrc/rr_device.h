@@ -4,6 +4,11 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+// ---- launch geometry, shared by the kernels and the host's sizing of them (rr_frame_plan.h)
+#define RR_BLOCK 256    // threads per workgroup of every frame kernel
+#define RR_WAVE 64      // lanes per wave = rays per packet
+#define RR_SQ_SHARDS 32 // sub-queues of the shadow queue, one append counter each
+
 // ---- acceleration structures -------------------------------------------------------------
 // BVH2 node, 64 B, one cache line per visit.  Both children's boxes live in the
 // parent, so a traversal step is one 4 x dwordx4 fetch.

@@ -1,0 +1,104 @@
+// rr_frame_plan.h — how a frame is cut into device batches and how its ray memory is sized: plain host arithmetic,
+// no HIP calls (rr_api.hip render_region_locked runs it; tests/native/frame_plan_test.cpp checks it on the CPU).
+//
+// All live depth levels of a batch sit in ONE arena of ray records (56 B each), level d + 1 stacked behind level d.
+// A level of n rays spawns at most 2 n children; if they fit behind it the level is shaded in one go, otherwise in
+// slices whose children fit, each slice's subtree finished (depth first) before the next slice starts.  So capacity
+// never limits correctness, only how large the launches can be -- and launch size matters: the persistent trace
+// kernels lose 8-15 % to ramp-up and tail per launch at 12 M rays (reserving the worst case 2^(d-1) growth per
+// level, as the first version did, capped batches there).
+#pragma once
+#include "rr_device.h"
+
+#include <algorithm>
+#include <cstdint>
+
+struct FramePlanInputs {
+    uint32_t npix;             // accumulator slots of the region (>= 1)
+    uint32_t samples;          // per pixel (>= 1)
+    uint32_t max_recursion;    // R
+    uint64_t queue_budget;     // bytes for level 1's hit records and the arena (rr_api.hip queue_budget)
+    uint32_t sample_group;     // rr_tuning::sample_group: 0 = automatic
+    uint32_t min_passes;       // progressive passes asked for; 0 without a pass hook
+    uint32_t arena_factor;     // arena rays per primary ray after a frame that had to slice levels
+    uint32_t n_enabled_lights;
+    uint64_t shade_chunk_rays; // rr_tuning::shade_chunk_rays: 0 = 64 Mi
+};
+
+struct FramePlan {
+    uint64_t total_primary; // npix * samples
+    uint64_t B;             // primary rays per batch (every batch but the last holds exactly B)
+    uint32_t G;             // samples of one pixel per 64-ray packet
+    uint64_t M;             // arena rays (levels 2 and deeper)
+    uint64_t chunk;         // rays per shade launch
+    uint64_t sq_need;       // shadow queue rays
+};
+
+static const uint64_t RR_LEVEL_MAX = 0x7fffff00ull; // ray indices are 32-bit
+
+inline FramePlan plan_frame(const FramePlanInputs& in) {
+    const uint32_t npix = in.npix, R = in.max_recursion, L = in.n_enabled_lights;
+    const uint64_t budget = in.queue_budget;
+    const uint64_t total_primary = (uint64_t)npix * in.samples;
+    // Level 1 (the primary rays) needs only its 16-B hit records: the rays themselves are derived from their index
+    // (primary_ray).  The arena holds the deeper levels; 2 arena rays per primary ray cover every level of a typical
+    // frame at once (sponza_syn: all deeper levels together hold 4 % of the primaries), sliced when a scene branches more.
+    const uint64_t per_primary = 16ull + 2ull * 56ull;
+    uint64_t B = std::max<uint64_t>(budget / per_primary, 4096);
+    B = std::min<uint64_t>(B, std::min<uint64_t>(total_primary, RR_LEVEL_MAX));
+    if (in.min_passes > 1) B = std::min<uint64_t>(B, std::max<uint64_t>(npix, (total_primary + in.min_passes - 1) / in.min_passes));
+    // equal batches (a frame that needs 1.2 batches would otherwise end with a small, poorly filled one)
+    { const uint64_t nb = (total_primary + B - 1) / B; B = (total_primary + nb - 1) / nb; }
+    if (B > npix) B = ((B + npix - 1) / npix) * npix; // whole sample slices when possible
+    // Sample grouping: a packet of 64 primary rays = 64/G neighbouring pixels x G samples of each (primary_ray), so the
+    // rays of a wave - and the shadow rays and children they spawn - start almost identical and their walks stay
+    // together.  The largest group the sample count allows is best (closest-hit -30 % on sponza_syn at G = 64 against
+    // one sample of 64 pixels), given that the wave merges its accumulator adds per pixel first (accum_merged): 64
+    // lanes adding to one address otherwise cost more than the walks gain.  Needs whole groups per batch.
+    uint32_t G = 1;
+    {
+        const uint32_t forced = in.sample_group; // 0 = automatic
+        for (uint32_t g = forced ? forced : 64u; g >= 2; g >>= 1)
+            if (g <= 64 && !(g & (g - 1)) && in.samples % g == 0 && npix % (RR_WAVE / g) == 0 && (uint64_t)npix * g <= B) { G = g; break; }
+        if (forced && G != forced) G = 1;
+    }
+    if (G > 1) {
+        // whole groups per batch, batches as equal as whole groups allow
+        const uint64_t unit = (uint64_t)npix * G, units_max = B / unit, total_units = total_primary / unit;
+        const uint64_t nb = (total_units + units_max - 1) / units_max;
+        B = ((total_units + nb - 1) / nb) * unit;
+    }
+    B = std::min<uint64_t>(B, total_primary);
+    // arena (levels 2 and deeper): 2 rays per primary ray, or 7 where that stays under 16 GB (a branching scene then fits
+    // on its first frame too), or `arena_factor` after a frame that had to slice -- always within the budget
+    const uint64_t after_hits = budget > 16ull * B ? (budget - 16ull * B) / 56ull : 0ull;
+    const uint64_t roomy = std::min<uint64_t>(7 * B, (16ull << 30) / 56ull);
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(2 * B, roomy), (uint64_t)in.arena_factor * B);
+    const uint64_t M = std::min<uint64_t>(std::min<uint64_t>(want, std::max<uint64_t>(2 * B, after_hits)) + 2ull * RR_BLOCK * (R + 1), RR_LEVEL_MAX);
+    // (the shadow queue holds one 48-B ray per hit of the chunk and ENABLED light: with many lights the chunk shrinks so that
+    // the queue stays within 16 GB -- the reference has no limit on lights, src/raytracing.rs:814)
+    const uint64_t chunk_by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(L, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
+    const uint64_t chunk = std::min<uint64_t>(in.shade_chunk_rays ? std::max<uint64_t>(65536, in.shade_chunk_rays) : (64ull << 20), chunk_by_lights);
+    // level 1: fixed shadow slots, (enabled light, hit of the chunk), the chunk padded to whole workgroup iterations;
+    // deeper levels: the dense sharded queue (a shard's static share of the chunk, one slack group per shard)
+    const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, std::max<uint64_t>(M, B)) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(L, 1u));
+    return FramePlan{total_primary, B, G, M, chunk, sq_need};
+}
+
+// The sample group of the batch [first, first + n): G where the batch holds whole groups of whole sample slices, else 1.
+inline uint32_t batch_group(const FramePlan& p, uint32_t npix, uint64_t first, uint64_t n) {
+    return (n % ((uint64_t)npix * p.G) == 0 && first % npix == 0) ? p.G : 1u;
+}
+
+// Rays per slice of depth level d (n rays, its children from arena index child_base on), in an arena of M rays for
+// R = max_recursion: n when the children of the whole level fit, else a positive whole number of workgroups;
+// 0 = the arena is too small for level d.  The deepest level (d > R) spawns nothing (k_shade: depth <= max_recursion).
+// Children of a slice may use the space behind this level minus what the deeper levels need to make progress
+// themselves (one 256-ray slice = 512 children per spawning level below): the recursion can then never get stuck.
+inline uint64_t level_slice(uint64_t M, uint64_t child_base, uint64_t n, uint32_t d, uint32_t R) {
+    if (d > R) return n;
+    const uint64_t keep = 2ull * RR_BLOCK * (R - d); // spawning levels below d + 1's parent: d + 1 .. R
+    const uint64_t room = M - child_base;
+    if (room < keep + 2ull * RR_BLOCK) return 0;
+    return 2 * n > room - keep ? ((room - keep) / 2 / RR_BLOCK) * RR_BLOCK : n;
+}

@@ -22,8 +22,6 @@
 #include "rr_device.h"
 #include "rr_math.h"
 
-#define RR_BLOCK 256
-#define RR_SQ_SHARDS 32 // sub-queues of the shadow queue, one append counter each
 #define RR_DEPTH_WIDE ((int)0x80000000) // k_shade: this lane's depth term does not fit its 32-bit sum (accum_depth_wide_merged)
 #define RR_FIXED_SLOT_LIGHTS 32u // level 1 keeps fixed shadow slots for up to this many enabled lights (one bit per light in k_shade's sq_wrote)
 #ifndef RR_SQ_STRIDE
@@ -38,7 +36,6 @@
 #ifndef RR_SHADOW_WAVES
 #define RR_SHADOW_WAVES RR_TRACE_WAVES
 #endif
-#define RR_WAVE 64
 #ifndef RR_DYN_FETCH
 #define RR_DYN_FETCH 4
 #endif
