@@ -318,13 +318,19 @@ void rr_scene_destroy(rr_scene* scene);
 
 /* Replace item transforms in place (animation / GUI edits between frames:
  * reference ShapeBasics::apply_mat, src/shape/mod.rs:748-753; Scene::apply_frame
- * src/scene.rs:1695-1713).  trans / trans_inv hold n_items * 16 floats. */
+ * src/scene.rs:1695-1713).  trans / trans_inv hold n_items * 16 floats.
+ * All or nothing, as rr_scene_update_materials: an update that fails (a non-finite matrix anywhere: RR_ERR_INVALID_ARGUMENT;
+ * a device or host failure part-way) leaves the scene rendering exactly what it rendered before the call.  Should putting
+ * the old scene back fail as well, the scene is marked broken: every frame call (rr_render and its progressive forms,
+ * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
+ * until an update of the same kind succeeds. */
 int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float* trans_inv);
 
 /* Replace every material in place (GUI edits between frames: reference Material::apply_diff, src/shape/mod.rs:182-242,
  * driven from src/run.rs:1132-1133).  `materials` holds the same n_materials records, in the same order, as the
  * flat scene the handle was created from (full materials and material caches alike); texture slots may name any
- * texture uploaded at creation.  Meshes, acceleration structures and texture images are not touched. */
+ * texture uploaded at creation.  Meshes, acceleration structures and texture images are not touched.  A failed update
+ * leaves the scene as it was (see rr_scene_update_transforms). */
 int rr_scene_update_materials(rr_scene* scene, const rr_material* materials, uint32_t n_materials);
 
 /* Compatibility switches: behaviours of EARLIER reference binaries that the source at HEAD no longer has.  Default 0 = HEAD.
@@ -374,7 +380,10 @@ int rr_multi_lock_order(rr_scene* const* scenes, uint32_t n_scenes, uint32_t* or
  * `out` hold the frame resolved over the samples finished so far (colour, normal and depth are means; object_id is
  * only final after the last batch) and `on_pass(user, samples_done, samples_total)` is called on the calling
  * thread.  A non-zero return stops the frame: the call returns RR_ERR_CANCELLED and `out` keeps the last preview.
- * The finished frame is bit-identical to rr_render's. */
+ * The finished frame is bit-identical to rr_render's.
+ * Inside on_pass the frame still holds the scene: rr_scene_last_stats on that scene is allowed and reports the passes finished so far
+ * (the work counters; timings come with the finished frame); every other call on that scene returns RR_ERR_INVALID_ARGUMENT (re-entry),
+ * and the scene must not be destroyed there.  Calls on other scenes are not restricted. */
 typedef int (*rr_pass_fn)(void* user, uint64_t primary_samples_done, uint64_t primary_samples_total);
 int rr_render_progressive(rr_scene* scene, const rr_camera* camera, const rr_config* config,
                           const uint16_t* sample_xy, const rr_frame* out, uint32_t min_passes,
@@ -384,8 +393,9 @@ int rr_render_progressive(rr_scene* scene, const rr_camera* camera, const rr_con
  * rendered with all of its samples: src/renderer.rs:125-172).  Pass k of n_passes (0 = 16; at most the number of tiles) renders the 32x8-pixel
  * tiles with (tile_index % n_passes == k), an interleaved subset of the frame, and after each pass but the last the host buffers of `out` hold the
  * frame so far (pixels not rendered yet are zero) and `on_pass(user, samples_done, samples_total)` is called on the calling thread; a non-zero
- * return stops the frame (RR_ERR_CANCELLED, `out` keeps what was finished).  The finished frame is bit-identical to rr_render's;
- * rr_scene_last_stats reports the sums over the passes. */
+ * return stops the frame (RR_ERR_CANCELLED, `out` keeps what was finished).  A frame cancelled before its first pass leaves every buffer of
+ * `out` zero.  The finished frame is bit-identical to rr_render's; rr_scene_last_stats reports the sums over the passes (inside on_pass:
+ * over the passes so far).  What on_pass may call is as for rr_render_progressive. */
 int rr_render_progressive_tiles(rr_scene* scene, const rr_camera* camera, const rr_config* config,
                                 const uint16_t* sample_xy, const rr_frame* out, uint32_t n_passes,
                                 rr_pass_fn on_pass, void* user, const volatile int* cancel);

@@ -90,17 +90,23 @@ struct Workers {
     void join_and_rethrow() { join(); if (first) std::rethrow_exception(first); }
 };
 
-// Test-only fault injection (tests/test_abi.py, tests/test_gpu_guard.py): rr_test_fault("point", kind, skip) arms ONE fault; the
-// (skip + 1)-th crossing of RR_FAULT_POINT("point") on any thread throws std::bad_alloc (kind 1), std::runtime_error (2) or
-// an int (3) and disarms.  Not armed (always, outside the tests): one relaxed atomic load per crossing, and the points sit
-// outside every per-ray and per-triangle loop.
+// Test-only fault injection (tests/test_abi.py, tests/test_gpu_guard.py, tests/test_gpu_scene_edits.py): rr_test_fault("point", kind, skip)
+// arms ONE fault; the (skip + 1)-th crossing of RR_FAULT_POINT("point") on any thread throws std::bad_alloc (kind 1), std::runtime_error (2)
+// or an int (3) and disarms.  Kinds 4, 5, 6 throw as 1, 2, 3 and stay armed: every later crossing throws too, until the next call of
+// rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host,
+// update_transforms.host (before the update writes anything), update_transforms.derive (after the items' upload),
+// update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
+// and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload).  Not armed (always, outside the tests): one
+// acquire load per crossing (it pairs with the release store of rr_test_fault: a thread that sees the kind sees the point's name), and
+// the points sit outside every per-ray and per-triangle loop.
 static std::atomic<int> g_fault_kind{0};
 static std::atomic<int> g_fault_skip{0};
 static char g_fault_point[64] = "";
 static void fault_point(const char* name) {
-    if (g_fault_kind.load(std::memory_order_relaxed) == 0 || strcmp(name, g_fault_point) != 0) return;
+    if (g_fault_kind.load(std::memory_order_acquire) == 0 || strcmp(name, g_fault_point) != 0) return;
     if (g_fault_skip.fetch_sub(1) > 0) return;
-    const int kind = g_fault_kind.exchange(0);
+    int kind = g_fault_kind.load(std::memory_order_acquire);
+    kind = kind > 3 ? kind - 3 : g_fault_kind.exchange(0);
     if (kind == 1) throw std::bad_alloc();
     if (kind == 2) throw std::runtime_error(std::string("injected fault at ") + name);
     if (kind == 3) throw 42;
@@ -108,10 +114,10 @@ static void fault_point(const char* name) {
 #define RR_FAULT_POINT(name) fault_point(name)
 extern "C" int rr_test_fault(const char* point, int kind, int skip) {
     g_fault_kind.store(0);
-    if (!point || kind < 0 || kind > 3 || strlen(point) >= sizeof g_fault_point) return fail(RR_ERR_INVALID_ARGUMENT, "rr_test_fault: bad arguments");
+    if (!point || kind < 0 || kind > 6 || strlen(point) >= sizeof g_fault_point) return fail(RR_ERR_INVALID_ARGUMENT, "rr_test_fault: bad arguments");
     strcpy(g_fault_point, point);
     g_fault_skip.store(skip < 0 ? 0 : skip);
-    g_fault_kind.store(kind);
+    g_fault_kind.store(kind, std::memory_order_release);
     return RR_OK;
 }
 #define HIP_TRY(expr)                                                                                   \
@@ -125,6 +131,22 @@ extern "C" int rr_test_fault(const char* point, int kind, int skip) {
         const int rc_ = (expr);                                                                         \
         if (rc_ != RR_OK) return rc_;                                                                   \
     } while (0)
+
+// The scene whose on_pass callback (rr_render_progressive, rr_render_progressive_tiles) runs on this thread, if any.  The frame
+// holds that scene's mutex across the callback: rr_scene_last_stats serves the scene without it, and every other entry point that
+// would take it refuses instead of deadlocking on a non-recursive std::mutex.
+static thread_local const rr_scene* tl_in_pass = nullptr;
+struct InPass {
+    const rr_scene* prev;
+    explicit InPass(const rr_scene* s) : prev(tl_in_pass) { tl_in_pass = s; }
+    ~InPass() { tl_in_pass = prev; }
+    InPass(const InPass&) = delete;
+    InPass& operator=(const InPass&) = delete;
+};
+static int not_in_pass(const rr_scene* s, const char* fn) {
+    if (s && tl_in_pass == s) return fail(RR_ERR_INVALID_ARGUMENT, "%s: re-entry from on_pass of the same scene (only rr_scene_last_stats may be called there)", fn);
+    return RR_OK;
+}
 
 // ---------------------------------------------------------------------------
 // device buffer helper
@@ -175,11 +197,16 @@ struct rr_scene {
     uint32_t n_materials = 0;
     uint32_t n_enabled_lights = 0;
     uint32_t tlas_node_capacity = 0;
-    std::vector<float4> h_item_boxes; // padded world boxes per item (lo, hi), filled by build_tlas
+    std::vector<float4> h_item_boxes; // padded world boxes per item (lo, hi), built by build_tlas, kept by upload_tlas
     DevBuf item_boxes;
     DevBuf sq_valid; // one 64-bit word per (enabled light, 64 shadow slots): which lanes hold a ray
     double tlas_reach[3] = {0.0, 0.0, 0.0}; // the top level's boxes are padded for ray origins within +-tlas_reach (build_tlas)
     double tlas_floor[3] = {0.0, 0.0, 0.0}; // ... and never for less than this: the items' own extent
+    bool tlas_stale = false; // a top-level upload failed part-way: the device trees match no tlas_reach, the next frame rebuilds them
+    // An update that failed and could not be rolled back either (update_all_or_nothing): the device holds a mix of two scenes, and every
+    // frame call refuses until an update of that kind succeeds.  geometry: items, flat normals, top level; materials: materials, item flags.
+    bool broken_geometry = false, broken_materials = false;
+    std::vector<DMaterial> h_dmat; // the material records on the device (rr_scene_update_materials puts them back after a failed update)
     int tlas_depth_limit = RR_TLAS_MAX_DEPTH, blas_depth_limit = RR_BLAS_MAX_DEPTH; // shares of the traversal stack, see rr_scene_create
     // frame state (grown on demand, reused across frames)
     DevBuf hit1;      // hit records of depth level 1 (the primary rays are derived from their index, not stored)
@@ -551,13 +578,18 @@ static void padded_world_box(const DItem& it, const WorldBox& b, const double re
 }
 
 // Builds the top-level tree over s->h_items for ray origins within +-reach (grown to cover the items themselves: the
-// origins of secondary and shadow rays lie on them).
-struct TlasTrees { std::vector<DNode4> corner, surface; int32_t root = (int32_t)0x80000000, root_surface = (int32_t)0x80000000; bool has_surface = false; };
-static int tlas_tree(rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4);
-static int build_tlas(rr_scene* s, const double want_reach[3], TlasTrees* trees) {
+// origins of secondary and shadow rays lie on them).  Writes nothing of the scene: the reach it was built for, the
+// RR_VIEW_NAN_BALLS hint and the item boxes travel in TlasTrees, and upload_tlas keeps them once the device has the trees.
+struct TlasTrees {
+    std::vector<DNode4> corner, surface; int32_t root = (int32_t)0x80000000, root_surface = (int32_t)0x80000000; bool has_surface = false;
+    double reach[3] = {0.0, 0.0, 0.0}; bool nan_balls = false; std::vector<float4> item_boxes;
+};
+static int tlas_tree(const rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4);
+static int build_tlas(const rr_scene* s, const double want_reach[3], TlasTrees* trees) {
     uint32_t n = (uint32_t)s->h_items.size();
     *trees = TlasTrees();
-    for (int c = 0; c < 3; c++) s->tlas_reach[c] = want_reach[c];
+    double* reach_c = trees->reach;
+    for (int c = 0; c < 3; c++) reach_c[c] = want_reach[c];
     if (n == 0) return RR_OK; // empty scene: every walk ends at once (both roots RR_SENTINEL)
     // two boxes per item: the box of its local box's corners -- what the tree is built over and what shadow packets are tested against:
     // the shadow query orders items by the distance at which the LOCAL box is entered, and prunes by it, which only a world box that
@@ -569,12 +601,11 @@ static int build_tlas(rr_scene* s, const double want_reach[3], TlasTrees* trees)
         surf[i] = exact_world_box(s->h_items[i], s->h_spans.size() == 9 * (size_t)n ? &s->h_spans[9 * (size_t)i] : nullptr);
         for (int c = 0; c < 3; c++) {
             const double m = std::max(std::fabs(exact[i].lo[c]), std::fabs(exact[i].hi[c])) * 1.001 + 0.01; // + the shadow bias along the normal
-            if (std::isfinite(m)) s->tlas_reach[c] = std::max(s->tlas_reach[c], m);
+            if (std::isfinite(m)) reach_c[c] = std::max(reach_c[c], m);
         }
     }
     // Can some ball's ray_toi_with_ball overflow (b * b, a * c beyond f32: delta = NaN and the ball answers Some(NaN))?  Judged with six
     // orders of magnitude to spare on the ray directions; a hint for trace_shadow_blockers only (the closest-hit walks detect the NaN itself).
-    s->view.compat &= ~RR_VIEW_NAN_BALLS;
     for (uint32_t i = 0; i < n; i++) {
         const DItem& it = s->h_items[i];
         if (!(it.flags & RR_IF_SPHERE)) continue;
@@ -584,21 +615,22 @@ static int build_tlas(rr_scene* s, const double want_reach[3], TlasTrees* trees)
             nmax = std::max(nmax, std::fabs((double)rows[r].x) + std::fabs((double)rows[r].y) + std::fabs((double)rows[r].z));
             tmax = std::max(tmax, std::fabs((double)rows[r].w));
         }
-        const double reach = std::max(s->tlas_reach[0], std::max(s->tlas_reach[1], s->tlas_reach[2]));
+        const double reach = std::max(reach_c[0], std::max(reach_c[1], reach_c[2]));
         const double on = nmax * reach + tmax, dn = nmax * 1e6, rad = std::fabs((double)it.radius);
         const bool affine = it.inv3.x == 0.0f && it.inv3.y == 0.0f && it.inv3.z == 0.0f && it.inv3.w == 1.0f;
-        if (!affine || !(on * dn < 1e18) || !(rad * dn < 1e18) || !(on < 1e18) || !(rad < 1e18)) s->view.compat |= RR_VIEW_NAN_BALLS;
+        if (!affine || !(on * dn < 1e18) || !(rad * dn < 1e18) || !(on < 1e18) || !(rad < 1e18)) trees->nan_balls = true;
     }
     std::vector<float> lo(3 * (size_t)n), hi(3 * (size_t)n);
-    s->h_item_boxes.resize(4 * (size_t)n); // [0, 2n): corner boxes (lo, hi); [2n, 4n): surface boxes
+    std::vector<float4>& boxes = trees->item_boxes;
+    boxes.resize(4 * (size_t)n); // [0, 2n): corner boxes (lo, hi); [2n, 4n): surface boxes
     for (uint32_t i = 0; i < n; i++) {
-        padded_world_box(s->h_items[i], exact[i], s->tlas_reach, &lo[3 * (size_t)i], &hi[3 * (size_t)i]);
-        s->h_item_boxes[2 * (size_t)i] = make_float4(lo[3 * (size_t)i], lo[3 * (size_t)i + 1], lo[3 * (size_t)i + 2], 0.0f);
-        s->h_item_boxes[2 * (size_t)i + 1] = make_float4(hi[3 * (size_t)i], hi[3 * (size_t)i + 1], hi[3 * (size_t)i + 2], 0.0f);
+        padded_world_box(s->h_items[i], exact[i], reach_c, &lo[3 * (size_t)i], &hi[3 * (size_t)i]);
+        boxes[2 * (size_t)i] = make_float4(lo[3 * (size_t)i], lo[3 * (size_t)i + 1], lo[3 * (size_t)i + 2], 0.0f);
+        boxes[2 * (size_t)i + 1] = make_float4(hi[3 * (size_t)i], hi[3 * (size_t)i + 1], hi[3 * (size_t)i + 2], 0.0f);
         float tl[3], th[3];
-        padded_world_box(s->h_items[i], surf[i], s->tlas_reach, tl, th);
-        s->h_item_boxes[2 * ((size_t)n + i)] = make_float4(tl[0], tl[1], tl[2], 0.0f);
-        s->h_item_boxes[2 * ((size_t)n + i) + 1] = make_float4(th[0], th[1], th[2], 0.0f);
+        padded_world_box(s->h_items[i], surf[i], reach_c, tl, th);
+        boxes[2 * ((size_t)n + i)] = make_float4(tl[0], tl[1], tl[2], 0.0f);
+        boxes[2 * ((size_t)n + i) + 1] = make_float4(th[0], th[1], th[2], 0.0f);
     }
     int rc = tlas_tree(s, lo.data(), hi.data(), n, &trees->corner, &trees->root);
     if (rc != RR_OK) return rc;
@@ -607,11 +639,11 @@ static int build_tlas(rr_scene* s, const double want_reach[3], TlasTrees* trees)
     // mesh walks entered.  Shadow queries keep the tree over the corner boxes (their order is the local boxes' entry distance).
     bool differs = false;
     for (size_t k = 0; k < 2 * (size_t)n && !differs; k++)
-        differs = memcmp(&s->h_item_boxes[k], &s->h_item_boxes[2 * (size_t)n + k], sizeof(float4)) != 0;
+        differs = memcmp(&boxes[k], &boxes[2 * (size_t)n + k], sizeof(float4)) != 0;
     trees->has_surface = differs;
     if (differs) {
         for (uint32_t i = 0; i < n; i++) {
-            const float4 tl = s->h_item_boxes[2 * ((size_t)n + i)], th = s->h_item_boxes[2 * ((size_t)n + i) + 1];
+            const float4 tl = boxes[2 * ((size_t)n + i)], th = boxes[2 * ((size_t)n + i) + 1];
             lo[3 * (size_t)i] = tl.x; lo[3 * (size_t)i + 1] = tl.y; lo[3 * (size_t)i + 2] = tl.z;
             hi[3 * (size_t)i] = th.x; hi[3 * (size_t)i + 1] = th.y; hi[3 * (size_t)i + 2] = th.z;
         }
@@ -622,7 +654,7 @@ static int build_tlas(rr_scene* s, const double want_reach[3], TlasTrees* trees)
 }
 
 // One top-level tree over the items' boxes lo / hi (n * 3 floats): binned SAH, one item per leaf, collapsed to 4-wide nodes.
-static int tlas_tree(rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4) {
+static int tlas_tree(const rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4) {
     tlas4->clear();
     rr::BvhResult r;
     if (!rr::build_bvh(lo, hi, n, 1, s->tlas_depth_limit, &r))
@@ -665,13 +697,20 @@ static int tlas_tree(rr_scene* s, const float* lo, const float* hi, uint32_t n, 
 }
 
 // The two trees into the scene's node buffer (the corner tree in its first half, the surface tree in the second: tlas_node_capacity
-// nodes each), the item boxes, and the roots into the view.  Blocking copies.
-static int upload_tlas(rr_scene* s, const TlasTrees& t) {
+// nodes each) and the item boxes; then, and only then, the scene keeps what they were built for: the reach, the NaN-ball hint, the host
+// copy of the boxes and the roots in the view.  A failed copy leaves all of that as it was and marks the device trees stale.
+// Blocking copies.
+static int upload_tlas(rr_scene* s, TlasTrees& t) {
     if (t.corner.size() > s->tlas_node_capacity || t.surface.size() > s->tlas_node_capacity)
         return fail(RR_ERR_DEVICE, "top-level rebuild needs %zu / %zu nodes, capacity %u", t.corner.size(), t.surface.size(), s->tlas_node_capacity);
+    s->tlas_stale = true;
     if (!t.corner.empty()) HIP_TRY(hipMemcpy(s->tnodes4.p, t.corner.data(), t.corner.size() * sizeof(DNode4), hipMemcpyHostToDevice));
     if (!t.surface.empty()) HIP_TRY(hipMemcpy(s->tnodes4.as<DNode4>() + s->tlas_node_capacity, t.surface.data(), t.surface.size() * sizeof(DNode4), hipMemcpyHostToDevice));
-    if (!s->h_item_boxes.empty()) HIP_TRY(hipMemcpy(s->item_boxes.p, s->h_item_boxes.data(), s->h_item_boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if (!t.item_boxes.empty()) HIP_TRY(hipMemcpy(s->item_boxes.p, t.item_boxes.data(), t.item_boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    s->tlas_stale = false;
+    for (int c = 0; c < 3; c++) s->tlas_reach[c] = t.reach[c];
+    s->view.compat = t.nan_balls ? (s->view.compat | RR_VIEW_NAN_BALLS) : (s->view.compat & ~RR_VIEW_NAN_BALLS);
+    s->h_item_boxes.swap(t.item_boxes);
     s->view.tlas_root4 = t.root;
     s->view.tnodes4c = t.has_surface ? s->tnodes4.as<DNode4>() + s->tlas_node_capacity : s->tnodes4.as<DNode4>();
     s->view.tlas_root4c = t.has_surface ? t.root_surface : t.root;
@@ -679,9 +718,10 @@ static int upload_tlas(rr_scene* s, const TlasTrees& t) {
 }
 
 // Ray origins of the coming launch reach out to +-need: rebuilds the top level when its boxes were padded for less
-// (a camera far outside the scene), or for more than 16x as much (the camera came back).
+// (a camera far outside the scene), or for more than 16x as much (the camera came back), or when an upload failed part-way.
+// s->tlas_reach changes with the upload only (upload_tlas): after a failure the next frame from this camera rebuilds again.
 static int ensure_tlas_reach(rr_scene* s, const double need[3]) {
-    bool grow = false, shrink = false;
+    bool grow = false, shrink = s->tlas_stale;
     for (int c = 0; c < 3; c++) {
         if (need[c] > s->tlas_reach[c]) grow = true;
         if (s->tlas_reach[c] > 16.0 * std::max(need[c], s->tlas_floor[c])) shrink = true;
@@ -692,6 +732,7 @@ static int ensure_tlas_reach(rr_scene* s, const double need[3]) {
     TlasTrees trees;
     int rc = build_tlas(s, want, &trees);
     if (rc != RR_OK) return rc;
+    RR_FAULT_POINT("tlas_reach.upload");
     HIP_TRY(hipDeviceSynchronize());
     return upload_tlas(s, trees);
 }
@@ -868,6 +909,7 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     for (uint32_t i = 0; i < fs->n_materials; i++) dmat[i] = make_dmaterial(fs->materials[i], s->tex_width, s->h_textures);
     HIP_TRY(s->materials.reserve(std::max<size_t>(dmat.size(), 1) * sizeof(DMaterial)));
     if (!dmat.empty()) HIP_TRY(hipMemcpy(s->materials.p, dmat.data(), dmat.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
+    s->h_dmat.swap(dmat);
 
     // ---- lights (disabled lights keep their slot: the slot is the RNG stream of their shadow jitter)
     std::vector<DLight> dl(fs->n_lights);
@@ -1037,11 +1079,11 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
         const double none[3] = {0.0, 0.0, 0.0};
         rc = build_tlas(s.get(), none, &trees);
         if (rc != RR_OK) return rc;
-        for (int c = 0; c < 3; c++) s->tlas_floor[c] = s->tlas_reach[c];
+        for (int c = 0; c < 3; c++) s->tlas_floor[c] = trees.reach[c];
         s->tlas_node_capacity = std::max<uint32_t>((uint32_t)std::max(trees.corner.size(), trees.surface.size()), fs->n_items ? fs->n_items : 1u); // room for rebuilds after transform updates
         HIP_TRY(s->tnodes4.reserve(2 * (size_t)s->tlas_node_capacity * sizeof(DNode4)));
         HIP_TRY(hipMemset(s->tnodes4.p, 0, 2 * (size_t)s->tlas_node_capacity * sizeof(DNode4)));
-        HIP_TRY(s->item_boxes.reserve(std::max<size_t>(s->h_item_boxes.size() * sizeof(float4), 16)));
+        HIP_TRY(s->item_boxes.reserve(std::max<size_t>(trees.item_boxes.size() * sizeof(float4), 16)));
         s->view.tnodes4 = s->tnodes4.as<DNode4>();
         rc = upload_tlas(s.get(), trees);
         if (rc != RR_OK) return rc;
@@ -1076,40 +1118,108 @@ extern "C" void rr_scene_destroy(rr_scene* s) {
     } catch (...) { (void)guard_fail("rr_scene_destroy"); }
 }
 
+// ---------------------------------------------------------------------------
+// scene edits: all or nothing
+// ---------------------------------------------------------------------------
+// Runs apply(); when it fails -- a status code or an exception -- runs restore(), which puts back everything apply may have written,
+// and returns apply's status and message.  When restore fails as well the scene holds a mix of before and after: *broken is set, and
+// frame calls refuse (check_intact) until an update of the same kind succeeds.
+template <class Apply, class Restore>
+static int all_or_nothing(const char* fn, bool* broken, Apply apply, Restore restore) {
+    int rc;
+    try { rc = apply(); } catch (...) { rc = guard_fail(fn); }
+    if (rc == RR_OK) { *broken = false; return RR_OK; }
+    std::string msg;
+    try { msg = tl_error; } catch (...) { /* the code still says what happened */ }
+    int rrc;
+    try { rrc = restore(); } catch (...) { rrc = guard_fail(fn); }
+    if (rrc != RR_OK) {
+        *broken = true;
+        return fail(rc, "%s; rolling back failed too (%s): the scene is broken until an update succeeds", msg.c_str(), tl_error.c_str());
+    }
+    try { tl_error = msg; } catch (...) {}
+    return rc;
+}
+// every frame call on a scene: a scene that a failed update left mixed is not rendered
+static int check_intact(const rr_scene* s) {
+    if (s->broken_geometry || s->broken_materials)
+        return fail(RR_ERR_DEVICE, "the scene is broken: a failed %s update could not be rolled back (update again, or create the scene anew)",
+                    s->broken_geometry ? "transform" : "material");
+    return RR_OK;
+}
+
+// The items' records to the device, then what derives from their transforms there: the update's way there and its way back.
+static int upload_items_and_derive(rr_scene* s) {
+    HIP_TRY(hipDeviceSynchronize()); // no frame may be in flight on the records that change (a caller that renders asynchronously through rr_render_region_device)
+    HIP_TRY(hipMemcpyAsync(s->items.p, s->h_items.data(), s->h_items.size() * sizeof(DItem), hipMemcpyHostToDevice, nullptr));
+    RR_FAULT_POINT("update_transforms.derive");
+    return derive_from_transforms(s);
+}
+
+// All or nothing: every matrix is checked before anything is written, and a failure after the first write puts the items, their
+// flat normals and spans, the top level and the view back as they were (derive_from_transforms and build_tlas are deterministic).
 extern "C" int rr_scene_update_transforms(rr_scene* s, const float* trans, const float* trans_inv) try {
     if (!s || !trans || !trans_inv) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_update_transforms"));
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
     RR_FAULT_POINT("update_transforms.host");
-    uint32_t n = (uint32_t)s->h_items.size();
+    const uint32_t n = (uint32_t)s->h_items.size();
     bool general_w = false;
     for (uint32_t i = 0; i < n; i++) {
         const float *t = trans + 16 * (size_t)i, *ti = trans_inv + 16 * (size_t)i;
         if (!finite16(t) || !finite16(ti)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: non-finite transform", i);
-        fill_item_matrices(s->h_items[i], t, ti);
         if (!(ti[3] == 0.0f && ti[7] == 0.0f && ti[11] == 0.0f && ti[15] == 1.0f)) general_w = true;
     }
-    HIP_TRY(hipDeviceSynchronize()); // no frame may be in flight on the records that change (a caller that renders asynchronously through rr_render_region_device)
-    HIP_TRY(hipMemcpyAsync(s->items.p, s->h_items.data(), n * sizeof(DItem), hipMemcpyHostToDevice, nullptr));
-    { int rc = derive_from_transforms(s); if (rc != RR_OK) return rc; }
-    s->view.general_w = general_w ? 1u : 0u;
-    {
+    // what the update writes, for the way back
+    const std::vector<DItem> items0 = s->h_items;
+    const std::vector<double> spans0 = s->h_spans;
+    const std::vector<float4> boxes0 = s->h_item_boxes;
+    double reach0[3], floor0[3];
+    memcpy(reach0, s->tlas_reach, sizeof reach0); memcpy(floor0, s->tlas_floor, sizeof floor0);
+    const DSceneView view0 = s->view;
+    auto apply = [&]() -> int {
+        for (uint32_t i = 0; i < n; i++) fill_item_matrices(s->h_items[i], trans + 16 * (size_t)i, trans_inv + 16 * (size_t)i);
+        RR_TRY(upload_items_and_derive(s));
+        s->view.general_w = general_w ? 1u : 0u;
         TlasTrees trees;
         const double none[3] = {0.0, 0.0, 0.0};
-        int rc = build_tlas(s, none, &trees); // the next frame's camera grows the reach again if it has to
-        if (rc != RR_OK) return rc;
+        RR_TRY(build_tlas(s, none, &trees)); // the next frame's camera grows the reach again if it has to
+        RR_FAULT_POINT("update_transforms.upload_tlas");
+        RR_TRY(upload_tlas(s, trees));
         for (int c = 0; c < 3; c++) s->tlas_floor[c] = s->tlas_reach[c];
-        rc = upload_tlas(s, trees);
-        if (rc != RR_OK) return rc;
-    }
-    return RR_OK;
+        return RR_OK;
+    };
+    auto restore = [&]() -> int {
+        s->h_items = items0; s->h_spans = spans0; s->h_item_boxes = boxes0;
+        memcpy(s->tlas_reach, reach0, sizeof reach0); memcpy(s->tlas_floor, floor0, sizeof floor0);
+        s->view = view0;
+        RR_TRY(upload_items_and_derive(s)); // the flat normals and spans of before, bit for bit
+        TlasTrees trees;
+        RR_TRY(build_tlas(s, reach0, &trees)); // reach0 already covers the items: the same reach, boxes and trees as before
+        RR_TRY(upload_tlas(s, trees));
+        s->view = view0;
+        return RR_OK;
+    };
+    return all_or_nothing("rr_scene_update_transforms", &s->broken_geometry, apply, restore);
 } RR_GUARD_END("rr_scene_update_transforms")
+
+// The material records and the items' records (their flag words) to the device: the update's way there and its way back.
+static int copy_material_records(rr_scene* s, const std::vector<DMaterial>& dmat, const std::vector<DItem>& items) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (!dmat.empty()) HIP_TRY(hipMemcpy(s->materials.p, dmat.data(), dmat.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
+    RR_FAULT_POINT("update_materials.device");
+    if (!items.empty()) HIP_TRY(hipMemcpy(s->items.p, items.data(), items.size() * sizeof(DItem), hipMemcpyHostToDevice));
+    return RR_OK;
+}
 
 // Material edits between frames (GUI sliders: reference src/run.rs:1132-1133 writes through Material::apply_diff,
 // src/shape/mod.rs:182-242): every material record is replaced and the item flag words derived from the material
-// caches are rebuilt; geometry, acceleration structures and texture images stay as uploaded.
+// caches are rebuilt; geometry, acceleration structures and texture images stay as uploaded.  All or nothing: after a failed copy the
+// records of before are copied back.
 extern "C" int rr_scene_update_materials(rr_scene* s, const rr_material* materials, uint32_t n_materials) try {
     if (!s || !materials) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_update_materials"));
     std::lock_guard<std::mutex> lk(s->mu);
     if (n_materials != s->n_materials) return fail(RR_ERR_INVALID_ARGUMENT, "%u materials, the scene was created with %u", n_materials, s->n_materials);
     for (uint32_t i = 0; i < n_materials; i++)
@@ -1122,14 +1232,19 @@ extern "C" int rr_scene_update_materials(rr_scene* s, const rr_material* materia
     HIP_TRY(hipSetDevice(s->device));
     std::vector<DMaterial> dmat(n_materials);
     for (uint32_t i = 0; i < n_materials; i++) dmat[i] = make_dmaterial(materials[i], s->tex_width, s->h_textures);
-    s->view.any_alpha_occluder = 0u;
+    // the item flag words and the alpha-occluder hint of the new materials: the scene keeps them once both copies have succeeded
+    std::vector<DItem> items = s->h_items;
+    uint32_t any_alpha_occluder = 0u;
     for (size_t i = 0; i < s->item_host.size(); i++) {
-        s->h_items[i].flags = item_flags(s->item_host[i], materials[s->item_host[i].material_cache], materials[s->item_host[i].material], s->tex_width);
-        if (s->h_items[i].flags & RR_IF_OCCLUDER_ALPHA_TEX) s->view.any_alpha_occluder = 1u;
+        items[i].flags = item_flags(s->item_host[i], materials[s->item_host[i].material_cache], materials[s->item_host[i].material], s->tex_width);
+        if (items[i].flags & RR_IF_OCCLUDER_ALPHA_TEX) any_alpha_occluder = 1u;
     }
-    HIP_TRY(hipDeviceSynchronize());
-    if (n_materials) HIP_TRY(hipMemcpy(s->materials.p, dmat.data(), dmat.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    if (!s->h_items.empty()) HIP_TRY(hipMemcpy(s->items.p, s->h_items.data(), s->h_items.size() * sizeof(DItem), hipMemcpyHostToDevice));
+    auto apply = [&]() -> int { return copy_material_records(s, dmat, items); };
+    auto restore = [&]() -> int { return copy_material_records(s, s->h_dmat, s->h_items); }; // the host copies still hold the records of before
+    RR_TRY(all_or_nothing("rr_scene_update_materials", &s->broken_materials, apply, restore));
+    s->h_items.swap(items);
+    s->h_dmat.swap(dmat);
+    s->view.any_alpha_occluder = any_alpha_occluder;
     return RR_OK;
 } RR_GUARD_END("rr_scene_update_materials")
 
@@ -1539,6 +1654,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool 
             pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
             launch_resolve(f, pf, out, frame_layout);
             RR_TRY(copy_outputs(*hook->host, *out, (size_t)fr.width * fr.height, f.st));
+            InPass in_pass(s);
             if (hook->fn(hook->user, done, total_primary) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
         }
     }
@@ -1548,6 +1664,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool 
 static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
                                 const rr_region* rg, const rr_frame* out, bool frame_layout, hipStream_t st, const volatile int* cancel,
                                 const PassHook* hook = nullptr) {
+    RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
     const uint32_t W = cam->width, H = cam->height;
@@ -1586,6 +1703,7 @@ extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const 
     RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
     RR_TRY(check_region(cam->width, cam->height, rg));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, "rr_render_region_device"));
     std::lock_guard<std::mutex> lk(s->mu);
     return render_region_locked(s, cam, cfg, sample_xy, rg, out, false, (hipStream_t)hip_stream, cancel);
 } RR_GUARD_END("rr_render_region_device")
@@ -1594,6 +1712,7 @@ static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cf
                           const volatile int* cancel, rr_pass_fn fn, void* user, uint32_t min_passes) {
     RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, fn ? "rr_render_progressive" : "rr_render"));
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
     const size_t np = (size_t)cam->width * cam->height;
@@ -1617,19 +1736,29 @@ extern "C" int rr_render_progressive(rr_scene* s, const rr_camera* cam, const rr
     return render_to_host(s, cam, cfg, sample_xy, out, cancel, on_pass, user, min_passes);
 } RR_GUARD_END("rr_render_progressive")
 
+// the device's work counters of the frame (or pass) that ran last, or of the batches so far inside on_pass
+static int read_counters(const rr_scene* s, rr_frame_stats* st) {
+    unsigned long long c[RR_CNT_WORDS];
+    HIP_TRY(hipMemcpy(c, s->counters.p, sizeof c, hipMemcpyDeviceToHost));
+    st->primary_rays = c[RR_CNT_PRIMARY]; st->secondary_rays = c[RR_CNT_SECONDARY];
+    st->shadow_rays = c[RR_CNT_SHADOW]; st->shaded_hits = c[RR_CNT_SHADED];
+    return RR_OK;
+}
 // the device counters and launch timers of the frame (or pass) that ran last, into s->stats
 static int collect_stats_locked(rr_scene* s) {
     float ms = 0.0f;
     if (hipEventSynchronize(s->frame_b) == hipSuccess && hipEventElapsedTime(&ms, s->frame_a, s->frame_b) == hipSuccess) s->stats.ms_total = ms;
     resolve_timers(s);
-    unsigned long long c[RR_CNT_WORDS];
-    HIP_TRY(hipMemcpy(c, s->counters.p, sizeof c, hipMemcpyDeviceToHost));
-    s->stats.primary_rays = c[RR_CNT_PRIMARY]; s->stats.secondary_rays = c[RR_CNT_SECONDARY];
-    s->stats.shadow_rays = c[RR_CNT_SHADOW]; s->stats.shaded_hits = c[RR_CNT_SHADED];
-    return RR_OK;
+    return read_counters(s, &s->stats);
 }
 extern "C" int rr_scene_last_stats(const rr_scene* cs, rr_frame_stats* out) try {
     if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (tl_in_pass == cs) { // inside on_pass of this scene: its frame holds s->mu on this thread and the stream is idle -- the passes so far
+        rr_frame_stats st = cs->stats;
+        if (!cs->stats_final) RR_TRY(read_counters(cs, &st));
+        *out = st;
+        return RR_OK;
+    }
     rr_scene* s = const_cast<rr_scene*>(cs);
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
@@ -1646,10 +1775,13 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
     if (!on_pass) return fail(RR_ERR_INVALID_ARGUMENT, "on_pass is required (use rr_render for a one-shot frame)");
     RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, "rr_render_progressive_tiles"));
     std::lock_guard<std::mutex> lk(s->mu);
     HIP_TRY(hipSetDevice(s->device));
     const uint32_t W = cam->width, H = cam->height, TW = 32, TH = 8;
     const size_t np = (size_t)W * H;
+    for (int k = 0; k < 4; k++) // pixels not rendered yet are zero, also when the frame stops before its first pass
+        if (out_buffer(*out, k)) memset(out_buffer(*out, k), 0, np * OUT_ELEM[k]);
     rr_frame dev{};
     RR_TRY(stage_outputs(s, *out, np, true, &dev));
     const uint32_t n_tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
@@ -1675,7 +1807,10 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
         RR_TRY(copy_outputs(*out, dev, np, nullptr));
         done += rr_region_pixel_count(W, H, &rg);
         s->stats = sum; s->stats_final = true;
-        if (k + 1 < P && on_pass(user, done * cfg->samples, (uint64_t)np * cfg->samples) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
+        if (k + 1 < P) {
+            InPass in_pass(s);
+            if (on_pass(user, done * cfg->samples, (uint64_t)np * cfg->samples) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
+        }
     }
     return RR_OK;
 } RR_GUARD_END("rr_render_progressive_tiles")
@@ -1683,6 +1818,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
 extern "C" int rr_scene_set_compat(rr_scene* s, uint32_t flags) try {
     if (!s) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (flags & ~RR_COMPAT_OCCLUDER_ALPHA_SHADOWS) return fail(RR_ERR_INVALID_ARGUMENT, "unknown compatibility flags 0x%x", flags);
+    RR_TRY(not_in_pass(s, "rr_scene_set_compat"));
     std::lock_guard<std::mutex> lk(s->mu);
     s->view.compat = (s->view.compat & RR_VIEW_NAN_BALLS) | flags; // the scene view is passed to the kernels by value with every launch
     return RR_OK;
@@ -1692,6 +1828,7 @@ extern "C" int rr_scene_set_tuning(rr_scene* s, const rr_tuning* t) try {
     if (!s || !t) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (t->struct_size != sizeof(rr_tuning)) return fail(RR_ERR_INVALID_ARGUMENT, "rr_tuning::struct_size %u, library expects %zu", t->struct_size, sizeof(rr_tuning));
     if (t->sample_group > 64u || (t->sample_group & (t->sample_group - 1u))) return fail(RR_ERR_INVALID_ARGUMENT, "sample_group %u is not 0 or a power of two <= 64", t->sample_group);
+    RR_TRY(not_in_pass(s, "rr_scene_set_tuning"));
     std::lock_guard<std::mutex> lk(s->mu);
     s->tuning = *t;
     s->profiling = t->kernel_timing != 0;
@@ -1848,6 +1985,7 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
         if (!scenes[i]) return fail(RR_ERR_INVALID_ARGUMENT, "scene %u is NULL", i);
         for (uint32_t j = 0; j < i; j++) if (scenes[j] == scenes[i]) return fail(RR_ERR_INVALID_ARGUMENT, "scene handle %u is passed twice", i);
         RR_TRY(check_frame_args(scenes[i], cam, cfg, sample_xy));
+        RR_TRY(not_in_pass(scenes[i], "rr_render_multi"));
     }
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     const uint32_t W = cam->width, H = cam->height, TW = 32, TH = 8; // interleaved 32x8 tiles: tile_index % n == device slot
@@ -1997,7 +2135,9 @@ extern "C" int rr_post_process(uint32_t width, uint32_t height, int cavity, int 
 extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_result* out) try {
     if (!s || !cam || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (x < 0 || y < 0 || (uint32_t)x >= cam->width || (uint32_t)y >= cam->height) return fail(RR_ERR_INVALID_ARGUMENT, "pixel (%d,%d) outside %ux%u", x, y, cam->width, cam->height);
+    RR_TRY(not_in_pass(s, "rr_pick"));
     std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_TRY(ensure_camera_reach(s, cam, nullptr));
     const rr_config none{}; // a pick has no frame config
@@ -2036,7 +2176,9 @@ extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* dir
     if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
     if (n == 0) return RR_OK;
     if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
+    RR_TRY(not_in_pass(s, "rr_trace_rays"));
     std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_FAULT_POINT("trace_rays.host");
     std::vector<float4> r0(n), r1(n);

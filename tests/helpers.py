@@ -41,3 +41,30 @@ def compare_frames(a: dict, b: dict, rgb_tol: int = 1):
         res["nan_mismatch"] = int((np.isnan(na) != np.isnan(nb)).sum())
         res["max_normal_abs"] = float(np.nanmax(d)) if d.size else 0.0
     return res
+
+
+def assert_frames_identical(a: dict, b: dict, what: str = ""):
+    """rgba, depth, normal and object_id equal bit for bit (floats compared as their bit patterns, NaN payloads included)."""
+    for k in ("rgba", "depth", "normal", "object_id"):
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.dtype == np.float32:
+            x, y = x.view(np.uint32), y.view(np.uint32)
+        assert x.shape == y.shape and np.array_equal(x, y), f"{what}: {k} differs in {int((x != y).sum())} values"
+
+
+def item_transforms(fs: FlatScene, dx: float = 0.0):
+    """(n, 4, 4) float32 transforms and inverses of the scene's items (math layout), every item moved by (dx, 0, 0)."""
+    t = np.stack([np.asarray(it.trans, np.float64) for it in fs.items]) if fs.items else np.zeros((0, 4, 4))
+    ti = np.stack([np.asarray(it.trans_inv, np.float64) for it in fs.items]) if fs.items else np.zeros((0, 4, 4))
+    move, back = np.eye(4), np.eye(4)
+    move[0, 3], back[0, 3] = dx, -dx
+    return (move @ t).astype(np.float32), (ti @ back).astype(np.float32)
+
+
+def with_transforms(fs: FlatScene, t, ti) -> FlatScene:
+    """A copy of the scene whose items carry the given transforms (what a freshly created scene is built from)."""
+    import copy
+    out = copy.deepcopy(fs)
+    for it, a, b in zip(out.items, t, ti):
+        it.trans, it.trans_inv = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return out

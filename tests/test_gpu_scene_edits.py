@@ -1,5 +1,6 @@
 """Scene life cycle through the C ABI on the GPU: degenerate scenes (empty meshes, no items), repeated create / destroy
-without leaking HBM, material edits between frames (rr_scene_update_materials vs a freshly created scene)."""
+without leaking HBM, material edits between frames (rr_scene_update_materials vs a freshly created scene), and updates that
+are refused or fail part-way: they leave the scene rendering exactly what it rendered before."""
 import copy
 import ctypes as C
 
@@ -7,7 +8,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import Item, MeshData, make_config
-from tests.helpers import camera_for, compare_frames, load_scene
+from tests.helpers import assert_frames_identical, camera_for, compare_frames, item_transforms, load_scene, with_transforms
 
 pytestmark = pytest.mark.gpu
 
@@ -116,3 +117,190 @@ def test_tuning_is_validated(hip):
         ds.set_tuning(sample_group=4, kernel_timing=1)
         g = rr_tuning()
         assert hip.lib().rr_scene_get_tuning(ds._h, C.byref(g)) == 0 and g.sample_group == 4 and g.kernel_timing == 1
+
+
+def edit_scene(name):
+    """The two scenes of the edit tests: kbert_room (8 items: the per-ray top level) and a fuzzer scene of 42 items (the packet form)."""
+    if name == "kbert_room":
+        fs = load_scene("kbert_room")
+        assert len(fs.items) <= 16
+    else:
+        from tools.fuzz_parity import rich_scene
+        fs = rich_scene(9110)
+        assert len(fs.items) >= 17
+    return fs
+
+
+EDIT_SCENES = ["kbert_room", "rich9110"]
+EDIT_CFG = dict(samples=2, monte_carlo=True, seed=11)
+
+
+@pytest.mark.parametrize("name", EDIT_SCENES)
+def test_refused_transform_update_leaves_the_scene_as_it_was(hip, name):
+    """rr_scene_update_transforms checked each matrix in the loop that wrote it: a NaN in item 3 was refused with items 0..2 already
+    holding the new matrices on the host, and the next material update uploaded them without their flat normals and top level."""
+    fs = edit_scene(name)
+    cam = camera_for(fs, 72, 48).c_struct()
+    cfg = make_config(**EDIT_CFG)
+    t, ti = item_transforms(fs, 3.0)
+    bad = t.copy()
+    bad[3, 0, 1] = np.nan
+    moved_fs = with_transforms(fs, t, ti)   # (before fs.c_struct(): its ctypes arrays do not deep-copy)
+    with hip.DeviceScene(fs, 0) as ds, hip.DeviceScene(moved_fs, 0) as fresh:
+        f0 = ds.render(cam, cfg)
+        with pytest.raises(hip.RustrayHipError) as e:
+            ds.update_transforms(bad, ti)
+        assert e.value.code == -1 and "item 3" in str(e.value)
+        assert_frames_identical(ds.render(cam, cfg), f0, "after the refused update")
+        ds.update_materials(fs.materials)   # a no-op edit: uploads the host's item records
+        assert_frames_identical(ds.render(cam, cfg), f0, "after a no-op material update")
+        ds.update_transforms(t, ti)
+        moved = ds.render(cam, cfg)
+        assert_frames_identical(moved, fresh.render(cam, cfg), "moved in place vs a fresh scene")
+        assert not np.array_equal(moved["rgba"], f0["rgba"])
+
+
+def _fault(hip, point, kind, skip=0):
+    L = hip.lib()
+    L.rr_test_fault.argtypes = [C.c_char_p, C.c_int, C.c_int]
+    assert L.rr_test_fault(point.encode(), kind, skip) == 0
+
+
+@pytest.mark.parametrize("name", EDIT_SCENES)
+def test_material_update_failing_between_its_copies_leaves_the_scene_as_it_was(hip, name):
+    """A fault between the materials' copy and the items' copy: the materials of before are copied back, the item flags and the
+    alpha-occluder hint stay as they were, and the next update works."""
+    fs = edit_scene(name)
+    cam = camera_for(fs, 72, 48).c_struct()
+    cfg = make_config(**EDIT_CFG)
+    edited = copy.deepcopy(fs)
+    for i, it in enumerate(edited.items):
+        for idx in (it.material, it.material_cache):
+            m = edited.materials[idx]
+            if i % 2 == 0:
+                m.alpha = 0.0          # a flag of the item (RR_IF_CACHE_ALPHA_POS) and a material record change together
+            else:
+                m.base_color, m.cast_shadow = (0.2, 0.8, 0.3), False
+    with hip.DeviceScene(fs, 0) as ds, hip.DeviceScene(edited, 0) as fresh:
+        f0 = ds.render(cam, cfg)
+        try:
+            for kind, code in ((1, -5), (2, -4)):
+                _fault(hip, "update_materials.device", kind)
+                with pytest.raises(hip.RustrayHipError) as e:
+                    ds.update_materials(edited.materials)
+                assert e.value.code == code, str(e.value)
+                assert_frames_identical(ds.render(cam, cfg), f0, f"after a failed material update (kind {kind})")
+        finally:
+            _fault(hip, "", 0)
+        ds.update_materials(edited.materials)
+        after = ds.render(cam, cfg)
+        assert_frames_identical(after, fresh.render(cam, cfg), "edited in place vs a fresh scene")
+        assert not np.array_equal(after["rgba"], f0["rgba"])
+
+
+def _visible_first(fs, object_id):
+    """Item indices, those covering most pixels of the unedited frame first: an edit of an item nobody sees tests nothing."""
+    ids, counts = np.unique(np.asarray(object_id), return_counts=True)
+    cover = dict(zip(ids.tolist(), counts.tolist()))
+    return sorted(range(len(fs.items)), key=lambda i: (-cover.get(fs.items[i].id, 0), i))
+
+
+def _pick(fs, order, pred):
+    for i in order:
+        it = fs.items[i]
+        if pred(it, fs.materials[it.material], fs.materials[it.material_cache]):
+            return i
+    raise AssertionError("no item fits the edit")
+
+
+def _both(fs, i, **kw):
+    """Sets fields on an item's full material and its material cache, as Material::apply_diff + update_material_cache do."""
+    it = fs.items[i]
+    for idx in (it.material, it.material_cache):
+        for k, v in kw.items():
+            setattr(fs.materials[idx], k, v)
+
+
+def _shape(t):
+    return tuple(np.asarray(t).shape[:2])
+
+
+def flag_edit_steps(fs, name, case, object_id):
+    """The scenes an in-place edit walks through, one per step: every flag item_flags derives from a material, and the material
+    record's texture filter and slot.  Each step starts from the one before; the edited item is the most visible one that fits
+    (object_id: the unedited frame).  `fs` must not have been through c_struct() (its ctypes arrays do not deep-copy)."""
+    cur = copy.deepcopy(fs)
+    order = _visible_first(cur, object_id)
+    if case == "alpha_map":        # RR_IF_OCCLUDER_ALPHA_TEX and view.any_alpha_occluder, both ways
+        caster = _pick(cur, order, lambda it, m, c: c.cast_shadow and it.visible and m.texture[4] < 0)
+        amap = int(np.argmin([np.asarray(t)[..., 3].min() for t in cur.textures]))   # the texture with the most transparent texel
+        off = copy.deepcopy(cur)
+        for m in off.materials:
+            m.texture[4] = -1
+        if any(m.texture[4] >= 0 for m in cur.materials):   # the rich scene has alpha maps already: clear them, then add one back
+            off2on = copy.deepcopy(off)
+            off2on.materials[off2on.items[caster].material].texture[4] = amap
+            return [off, off2on]
+        on = copy.deepcopy(cur)
+        on.materials[on.items[caster].material].texture[4] = amap
+        return [on, off]
+    if case == "cache_alpha_half":   # RR_IF_SOLID_BASE goes with alpha < 1 under backface culling
+        i = _pick(cur, order, lambda it, m, c: it.visible and c.alpha == 1.0 and c.backface_cullig)
+        _both(cur, i, alpha=0.5)
+    elif case == "smooth":           # RR_IF_SMOOTH, on a mesh that has normals
+        i = _pick(cur, order, lambda it, m, c: it.visible and it.kind == 1 and cur.meshes[it.mesh].normals is not None
+                  and len(cur.meshes[it.mesh].normals) > 0)
+        _both(cur, i, smooth_shading=not cur.materials[cur.items[i].material_cache].smooth_shading)
+    elif case == "reflection_only":  # RR_IF_CACHE_REFL_ONLY
+        i = _pick(cur, order, lambda it, m, c: it.visible and not c.reflection_only)
+        _both(cur, i, reflection_only=True)
+    elif case == "no_shadow":        # RR_IF_CACHE_CAST_SHADOW
+        i = _pick(cur, order, lambda it, m, c: it.visible and c.cast_shadow)
+        _both(cur, i, cast_shadow=False)
+    elif case == "cache_alpha_zero":  # RR_IF_CACHE_ALPHA_POS
+        i = _pick(cur, order, lambda it, m, c: it.visible and c.alpha > 0.0)
+        _both(cur, i, alpha=0.0)
+    elif case == "filter_and_size":  # the material record: RR_MF_NEAREST and a texture descriptor of another size
+        i = _pick(cur, order, lambda it, m, c: it.visible and m.texture[0] >= 0)
+        m = cur.materials[cur.items[i].material]
+        old = _shape(cur.textures[m.texture[0]])
+        others = [k for k, t in enumerate(cur.textures) if _shape(t) != old]
+        if name != "kbert_room":
+            others = [k for k in others if any(v & (v - 1) for v in _shape(cur.textures[k]))] or others
+        m.texture[0] = others[0]
+        m.texture_filtering_nearest = not m.texture_filtering_nearest
+    else:
+        raise ValueError(case)
+    return [cur]
+
+
+def frames_differ(a, b):
+    return any(not np.array_equal(np.ascontiguousarray(a[k]).view(np.uint8), np.ascontiguousarray(b[k]).view(np.uint8))
+               for k in ("rgba", "depth", "normal", "object_id"))
+
+
+FLAG_CASES = ["alpha_map", "cache_alpha_half", "smooth", "reflection_only", "no_shadow", "cache_alpha_zero", "filter_and_size"]
+
+
+@pytest.mark.parametrize("case", FLAG_CASES)
+@pytest.mark.parametrize("name", EDIT_SCENES)
+def test_material_flag_edits_in_place_equal_a_fresh_scene_and_the_oracle(hip, oracle, name, case):
+    fs = edit_scene(name)
+    work = copy.deepcopy(fs)   # edited copies are made from this one (fs goes through c_struct() below)
+    cam = camera_for(fs, 72, 48).c_struct()
+    cfg = make_config(samples=2, monte_carlo=True, seed=5)
+    with hip.DeviceScene(fs, 0) as ds:
+        prev = ds.render(cam, cfg)
+        for k, edited in enumerate(flag_edit_steps(work, name, case, prev["object_id"])):
+            ds.update_materials(edited.materials)
+            got = ds.render(cam, cfg)
+            st = ds.stats()
+            assert frames_differ(got, prev), f"{case} step {k}: the edit does not change the frame, so it tests nothing"
+            with hip.DeviceScene(edited, 0) as fresh:
+                assert_frames_identical(got, fresh.render(cam, cfg), f"{case} step {k}: in place vs a fresh scene")
+            ref = oracle.render(edited.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+            res = compare_frames(got, ref)
+            assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, (case, k, res)
+            c = ref["counters"]
+            assert (st["primary_rays"], st["secondary_rays"], st["shaded_hits"]) == (c["rays_primary"], c["rays_secondary"], c["shaded_hits"]), (case, k)
+            prev = got
