@@ -36,7 +36,9 @@ extern "C" {
  * version, and rr_abi_version() reports what the loaded library was built with, so a caller compiled against an older
  * header (round 1: a shorter rr_frame_stats, rr_scene_set_profiling) fails at the first call instead of being written
  * past its structs.  2: rr_frame_stats grew (level-1 timing, binning, multi-GPU exchange), rr_tuning, rr_abi_version.
- * 3: rr_frame_stats carries the level-1 share of the shade and shadow kernels too (one roofline per kernel build in bench.py). */
+ * 3: rr_frame_stats carries the level-1 share of the shade and shadow kernels too (one roofline per kernel build in bench.py).
+ * rr_scene_update_lights, rr_scene_update_item_flags and rr_scene_add_textures came later without a change of any struct, so the
+ * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them). */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -332,6 +334,32 @@ int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float*
  * texture uploaded at creation.  Meshes, acceleration structures and texture images are not touched.  A failed update
  * leaves the scene as it was (see rr_scene_update_transforms). */
 int rr_scene_update_materials(rr_scene* scene, const rr_material* materials, uint32_t n_materials);
+
+/* The edits below, like the two above, leave the handle rendering bit for bit what a handle freshly created from the edited flat
+ * scene renders (every frame call, rr_pick, rr_trace_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
+ * frames still in flight on the device (rr_render_region_device) before it overwrites what they read, and returns
+ * RR_ERR_INVALID_ARGUMENT when called from on_pass of the same scene.  Every handle that takes part in a multi-GPU frame must
+ * receive the same edits. */
+
+/* Replace the whole light list (the GUI's light "+", edits and "delete": reference src/run.rs:1294-1409).  n_lights may differ
+ * from the count at creation and may be 0 (lights may then be NULL); a light type beyond RR_LIGHT_SPOT is refused, as by
+ * rr_scene_create.  Order is semantic: a light's index is the RNG stream of its shadow jitter, disabled lights keep their slot, and
+ * deleting a light shifts the streams of the lights after it (as Vec::remove does in the reference).  All or nothing, as
+ * rr_scene_update_transforms; a scene broken by a failed roll-back refuses frames until a light update succeeds. */
+int rr_scene_update_lights(rr_scene* scene, const rr_light* lights, uint32_t n_lights);
+
+/* Set ShapeBasics::visible and flip_normals of every item (the GUI's "Visible" and "flip normals" checkboxes, reference
+ * src/run.rs:1464-1489): n_items must equal the scene's item count, both arrays are required, a value is 0 or non-zero.  Hidden
+ * items keep their place in the acceleration structure (they cost traversal, not hits); nothing is rebuilt.  Later material updates
+ * keep these values.  All or nothing; a scene broken by a failed roll-back refuses frames until an item flag update succeeds. */
+int rr_scene_update_item_flags(rr_scene* scene, const uint8_t* visible, const uint8_t* flip_normals, uint32_t n_items);
+
+/* Append images to the scene's texture list (a material's texture "+", reference src/run.rs:936-947); *first_index receives the
+ * index of the first new one.  Textures are checked as by rr_scene_create.  The existing images keep their indices; the new ones
+ * take the indices (and layout) a scene created with the longer list gives them, and are used once a following
+ * rr_scene_update_materials names them.  Adding 0 textures changes nothing.  A failure leaves the scene as it was.  Texture memory
+ * never shrinks: images no material names any more stay resident until the scene is destroyed. */
+int rr_scene_add_textures(rr_scene* scene, const rr_texture* textures, uint32_t n_textures, uint32_t* first_index);
 
 /* Compatibility switches: behaviours of EARLIER reference binaries that the source at HEAD no longer has.  Default 0 = HEAD.
  * RR_COMPAT_OCCLUDER_ALPHA_SHADOWS: a shadow is attenuated by the OCCLUDER's material.alpha, where HEAD takes the

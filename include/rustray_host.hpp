@@ -419,7 +419,21 @@ public:
     bool ok() const { return h_ != nullptr; }
     const std::string& error() const { return error_; }
 
+    // Edits in place between frames (include/rustray_hip.h); each returns the rr_status and keeps rr_last_error() in error() on failure.
+    // The whole light list, in Scene::lights order (a light's index is the RNG stream of its shadow jitter).
+    int update_lights(const std::vector<rr_light>& lights) { return check(rr_scene_update_lights(h_, lights.data(), (uint32_t)lights.size())); }
+    // ShapeBasics::visible / flip_normals of every item, in Scene::items order.
+    int update_item_flags(const std::vector<uint8_t>& visible, const std::vector<uint8_t>& flip_normals) {
+        if (visible.size() != flip_normals.size()) { error_ = "update_item_flags: visible and flip_normals differ in length"; return RR_ERR_INVALID_ARGUMENT; }
+        return check(rr_scene_update_item_flags(h_, visible.data(), flip_normals.data(), (uint32_t)visible.size()));
+    }
+    // Appends images to the texture list; *first_index: the index of the first (name it in a following material update).
+    int add_textures(const std::vector<rr_texture>& textures, uint32_t* first_index) {
+        return check(rr_scene_add_textures(h_, textures.data(), (uint32_t)textures.size(), first_index));
+    }
+
 private:
+    int check(int rc) { if (rc != RR_OK) error_ = rr_last_error(); return rc; }
     rr_scene* h_ = nullptr;
     std::string error_;
 };
@@ -441,6 +455,14 @@ public:
         const rr_camera c = camera.c_struct();
         if (rr_pick(scene->handle(), &c, x, y, &r) != RR_OK || !r.hit) return std::nullopt;
         return std::make_pair(r.object_id, r.distance);
+    }
+
+    // The GUI's light and item edits (reference src/run.rs:1294-1409, :1464-1489), applied to the resident scene before the next
+    // RendererManager::restart: `lights` is the edited Scene::lights, the flags are ShapeBasics::visible / flip_normals per item.
+    // false = refused or failed (scene->error() says why); the scene then renders what it rendered before.
+    bool update_lights(const std::vector<rr_light>& lights) { return scene->update_lights(lights) == RR_OK; }
+    bool update_item_flags(const std::vector<uint8_t>& visible, const std::vector<uint8_t>& flip_normals) {
+        return scene->update_item_flags(visible, flip_normals) == RR_OK;
     }
 };
 

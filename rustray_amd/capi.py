@@ -12,7 +12,8 @@ import subprocess
 
 import numpy as np
 
-from .flat import (RR_ABI_VERSION, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_material, rr_pick_result, rr_region, rr_tuning)
+from .flat import (RR_ABI_VERSION, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_light, rr_material, rr_pick_result, rr_region,
+                   rr_texture, rr_tuning)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUSTRAY_HIP_LIB") or os.path.join(_HERE, "librustray_hip.so")  # override: developer A/B builds
@@ -20,7 +21,7 @@ _LIB = None
 
 # every symbol include/rustray_hip.h declares (tests/test_abi.py checks the list against the header)
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
-           "rr_scene_update_materials", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
+           "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
            "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_scene_last_stats", "rr_post_process", "rr_post_process_device"]
 
@@ -92,6 +93,10 @@ def lib():
         L.rr_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_scene_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.rr_scene_update_item_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.rr_scene_add_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.rr_scene_set_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
         L.rr_scene_get_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
         L.rr_post_process.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -226,6 +231,32 @@ class DeviceScene:
         """rr_scene_update_materials: `materials` = the flat scene's material list (same length and order), edited."""
         arr = (rr_material * len(materials))(*[m.c_struct() if hasattr(m, "c_struct") else m for m in materials])
         _check(lib().rr_scene_update_materials(self._h, arr, len(materials)))
+
+    def update_lights(self, lights):
+        """rr_scene_update_lights: the whole light list (flat.Light or rr_light), any length, in the order that gives each light its RNG stream."""
+        n = len(lights)
+        arr = (rr_light * max(n, 1))(*[l.c_struct() if hasattr(l, "c_struct") else l for l in lights])
+        _check(lib().rr_scene_update_lights(self._h, arr if n else None, n))
+
+    def update_item_flags(self, visible, flip_normals):
+        """rr_scene_update_item_flags: ShapeBasics::visible / flip_normals of every item (sequences of the scene's item count)."""
+        v = np.ascontiguousarray([1 if x else 0 for x in visible], np.uint8)
+        f = np.ascontiguousarray([1 if x else 0 for x in flip_normals], np.uint8)
+        if len(v) != len(f):
+            raise ValueError(f"{len(v)} visible flags, {len(f)} flip_normals flags")
+        _check(lib().rr_scene_update_item_flags(self._h, v.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), len(v)))
+
+    def add_textures(self, images) -> int:
+        """rr_scene_add_textures: appends (H, W, 4) uint8 images to the texture list; returns the index of the first."""
+        keep = [np.ascontiguousarray(t, np.uint8) for t in images]
+        arr = (rr_texture * max(len(keep), 1))()
+        for i, t in enumerate(keep):
+            assert t.ndim == 3 and t.shape[2] == 4
+            arr[i].width, arr[i].height = t.shape[1], t.shape[0]
+            arr[i].rgba8 = t.ctypes.data if t.size else None
+        first = C.c_uint32(0)
+        _check(lib().rr_scene_add_textures(self._h, arr, len(keep), C.byref(first)))
+        return int(first.value)
 
     def set_tuning(self, **kw):
         """rr_scene_set_tuning: sample_group, queue_budget_bytes, shade_chunk_rays, kernel_timing, multi_force_staged, bin_min_rays (others keep their value)."""

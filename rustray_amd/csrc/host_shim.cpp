@@ -105,3 +105,51 @@ extern "C" int rh_animation_frame(uint32_t fps, uint64_t t1_ms, const float* tr0
     *exists = an.frame_exists(frame) ? 1 : 0;
     return an.frame_transforms(names, frame, trans, trans_inv) ? 1 : 0;
 }
+
+// A resident scene behind Raytracing for the edit tests: rh_scene_create, the edits through Raytracing / DeviceScene, one frame
+// through RendererManager (rh_scene_render), rh_scene_destroy.
+struct RhScene { std::shared_ptr<DeviceScene> scene; std::shared_ptr<Raytracing> rt; };
+
+extern "C" void* rh_scene_create(const rr_flat_scene* fs, int device) {
+    auto* h = new RhScene;
+    h->scene = std::make_shared<DeviceScene>(*fs, device);
+    if (!h->scene->ok()) { delete h; return nullptr; }
+    h->rt = std::make_shared<Raytracing>(h->scene);
+    return h;
+}
+
+extern "C" void rh_scene_destroy(void* h) { delete (RhScene*)h; }
+
+extern "C" int rh_update_lights(void* h, const rr_light* lights, uint32_t n) {
+    return ((RhScene*)h)->rt->update_lights(std::vector<rr_light>(lights, lights + n)) ? 0 : -1;
+}
+
+extern "C" int rh_update_item_flags(void* h, const uint8_t* visible, const uint8_t* flip_normals, uint32_t n) {
+    return ((RhScene*)h)->rt->update_item_flags(std::vector<uint8_t>(visible, visible + n), std::vector<uint8_t>(flip_normals, flip_normals + n)) ? 0 : -1;
+}
+
+extern "C" int rh_add_textures(void* h, const rr_texture* textures, uint32_t n, uint32_t* first_index) {
+    return ((RhScene*)h)->scene->add_textures(std::vector<rr_texture>(textures, textures + n), first_index);
+}
+
+// one whole frame (min_passes passes) into the caller's buffers
+extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
+                               const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,
+                               uint8_t* rgba, float* normal, float* depth, uint32_t* ids) {
+    RhScene* s = (RhScene*)hv;
+    s->rt->camera = make_camera(fov, eye, up, dir, cnear, cfar);
+    s->rt->config = RaytracingConfig();
+    s->rt->config.apply(from_c(cfg));
+    s->rt->config.seed = cfg->seed;
+    RendererManager mgr((int32_t)w, (int32_t)h, s->rt);
+    mgr.min_passes = min_passes;
+    mgr.start();
+    mgr.wait();
+    std::vector<uint8_t> im; std::vector<float> nr, dp; std::vector<uint32_t> id;
+    mgr.frame(&im, &nr, &dp, &id);
+    std::memcpy(rgba, im.data(), im.size());
+    std::memcpy(normal, nr.data(), nr.size() * 4);
+    std::memcpy(depth, dp.data(), dp.size() * 4);
+    std::memcpy(ids, id.data(), id.size() * 4);
+    return mgr.failed() || !mgr.is_done() ? -2 : 0;
+}

@@ -96,7 +96,9 @@ struct Workers {
 // rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host,
 // update_transforms.host (before the update writes anything), update_transforms.derive (after the items' upload),
 // update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
-// and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload).  Not armed (always, outside the tests): one
+// and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload), update_lights.device (after the light
+// records' copy), update_item_flags.device (after the items' copy), add_textures.device (after the grown pool's upload, before it
+// replaces the old one).  Not armed (always, outside the tests): one
 // acquire load per crossing (it pairs with the release store of rr_test_fault: a thread that sees the kind sees the point's name), and
 // the points sit outside every per-ray and per-triangle loop.
 static std::atomic<int> g_fault_kind{0};
@@ -205,8 +207,10 @@ struct rr_scene {
     bool tlas_stale = false; // a top-level upload failed part-way: the device trees match no tlas_reach, the next frame rebuilds them
     // An update that failed and could not be rolled back either (update_all_or_nothing): the device holds a mix of two scenes, and every
     // frame call refuses until an update of that kind succeeds.  geometry: items, flat normals, top level; materials: materials, item flags.
-    bool broken_geometry = false, broken_materials = false;
+    // lights: the light records; item_flags: the items' records after a failed rr_scene_update_item_flags.
+    bool broken_geometry = false, broken_materials = false, broken_lights = false, broken_item_flags = false;
     std::vector<DMaterial> h_dmat; // the material records on the device (rr_scene_update_materials puts them back after a failed update)
+    std::vector<DLight> h_lights;  // the light records on the device (rr_scene_update_lights puts them back after a failed update)
     int tlas_depth_limit = RR_TLAS_MAX_DEPTH, blas_depth_limit = RR_BLAS_MAX_DEPTH; // shares of the traversal stack, see rr_scene_create
     // frame state (grown on demand, reused across frames)
     DevBuf hit1;      // hit records of depth level 1 (the primary rays are derived from their index, not stored)
@@ -476,6 +480,16 @@ static uint32_t item_flags(const ItemHost& it, const rr_material& cache, const r
         if (it.mesh_degenerate) f |= RR_IF_UV_MAY_BE_NAN;
     }
     return f;
+}
+
+// Light (reference src/scene.rs:40-51) -> device record.  Disabled lights keep their slot: the slot is the RNG stream of their shadow jitter.
+static DLight make_dlight(const rr_light& l) {
+    DLight d;
+    memset(&d, 0, sizeof d);
+    for (int k = 0; k < 3; k++) { d.pos[k] = l.pos[k]; d.dir[k] = l.dir[k]; d.color[k] = l.color[k]; }
+    d.intensity = l.intensity; d.max_angle = l.max_angle;
+    d.type = l.light_type | (l.enabled ? 0u : 0x80u);
+    return d;
 }
 
 static void fill_item_matrices(DItem& d, const float* trans, const float* inv) {
@@ -915,14 +929,12 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     std::vector<DLight> dl(fs->n_lights);
     s->n_enabled_lights = 0;
     for (uint32_t i = 0; i < fs->n_lights; i++) {
-        const rr_light& l = fs->lights[i];
-        for (int k = 0; k < 3; k++) { dl[i].pos[k] = l.pos[k]; dl[i].dir[k] = l.dir[k]; dl[i].color[k] = l.color[k]; }
-        dl[i].intensity = l.intensity; dl[i].max_angle = l.max_angle;
-        dl[i].type = l.light_type | (l.enabled ? 0u : 0x80u);
-        if (l.enabled) s->n_enabled_lights++;
+        dl[i] = make_dlight(fs->lights[i]);
+        if (fs->lights[i].enabled) s->n_enabled_lights++;
     }
     HIP_TRY(s->lights.reserve(std::max<size_t>(dl.size(), 1) * sizeof(DLight)));
     if (!dl.empty()) HIP_TRY(hipMemcpy(s->lights.p, dl.data(), dl.size() * sizeof(DLight), hipMemcpyHostToDevice));
+    s->h_lights.swap(dl);
 
     // ---- shares of the traversal stack (RR_STACK_DEPTH entries per lane): a top level over n items never needs more
     // than n - 1 pending entries, so a scene of few items leaves more levels to its per-mesh trees (a 320 k-triangle
@@ -1142,9 +1154,9 @@ static int all_or_nothing(const char* fn, bool* broken, Apply apply, Restore res
 }
 // every frame call on a scene: a scene that a failed update left mixed is not rendered
 static int check_intact(const rr_scene* s) {
-    if (s->broken_geometry || s->broken_materials)
+    if (s->broken_geometry || s->broken_materials || s->broken_lights || s->broken_item_flags)
         return fail(RR_ERR_DEVICE, "the scene is broken: a failed %s update could not be rolled back (update again, or create the scene anew)",
-                    s->broken_geometry ? "transform" : "material");
+                    s->broken_geometry ? "transform" : s->broken_materials ? "material" : s->broken_lights ? "light" : "item flag");
     return RR_OK;
 }
 
@@ -1247,6 +1259,128 @@ extern "C" int rr_scene_update_materials(rr_scene* s, const rr_material* materia
     s->view.any_alpha_occluder = any_alpha_occluder;
     return RR_OK;
 } RR_GUARD_END("rr_scene_update_materials")
+
+// The light records to `buf` (the scene's buffer, or a larger one that replaces it): the update's way there and its way back.
+static int copy_light_records(rr_scene* s, DevBuf& buf, const std::vector<DLight>& dl) {
+    HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the records
+    if (!dl.empty()) HIP_TRY(hipMemcpy(buf.p, dl.data(), dl.size() * sizeof(DLight), hipMemcpyHostToDevice));
+    RR_FAULT_POINT("update_lights.device");
+    return RR_OK;
+}
+
+// Light edits between frames (the GUI's light panel: reference src/run.rs:1294-1409 adds, edits and deletes `Scene::lights`): the
+// whole list is replaced; its length may change.  A light's index is the RNG stream of its shadow jitter, so the list is taken in
+// the caller's order, as rr_scene_create takes it.  A list longer than the buffer holds goes to a new buffer that replaces the old
+// one only after the copy.  All or nothing: after a failed copy the records of before are copied back.
+extern "C" int rr_scene_update_lights(rr_scene* s, const rr_light* lights, uint32_t n_lights) try {
+    if (!s || (n_lights && !lights)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_update_lights"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (uint32_t i = 0; i < n_lights; i++) // as validate_scene
+        if (lights[i].light_type > RR_LIGHT_SPOT) return fail(RR_ERR_INVALID_ARGUMENT, "light %u: type %u", i, lights[i].light_type);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<DLight> dl(n_lights);
+    uint32_t n_enabled = 0;
+    for (uint32_t i = 0; i < n_lights; i++) {
+        dl[i] = make_dlight(lights[i]);
+        if (lights[i].enabled) n_enabled++;
+    }
+    DevBuf grown;
+    const bool grow = (size_t)n_lights * sizeof(DLight) > s->lights.bytes;
+    if (grow) HIP_TRY(grown.reserve((size_t)n_lights * sizeof(DLight)));
+    auto apply = [&]() -> int { return copy_light_records(s, grow ? grown : s->lights, dl); };
+    auto restore = [&]() -> int { return copy_light_records(s, s->lights, s->h_lights); };
+    RR_TRY(all_or_nothing("rr_scene_update_lights", &s->broken_lights, apply, restore));
+    // the device holds the new records: the frame path reads the count, the enabled count (shadow-queue plan, fixed shadow slots) and the pointer together
+    if (grow) s->lights = std::move(grown); // frees the old buffer: nothing reads it since the synchronisation in copy_light_records
+    s->h_lights.swap(dl);
+    s->n_enabled_lights = n_enabled;
+    s->view.lights = s->lights.as<DLight>();
+    s->view.n_lights = n_lights;
+    s->view.n_enabled_lights = n_enabled;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_update_lights")
+
+// The items' records (their flag words) to the device: the update's way there and its way back.
+static int copy_item_flag_records(rr_scene* s, const std::vector<DItem>& items) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (!items.empty()) HIP_TRY(hipMemcpy(s->items.p, items.data(), items.size() * sizeof(DItem), hipMemcpyHostToDevice));
+    RR_FAULT_POINT("update_item_flags.device");
+    return RR_OK;
+}
+
+// The GUI's "Visible" and "flip normals" checkboxes (reference src/run.rs:1464-1489, ShapeBasics::visible / flip_normals): only
+// RR_IF_VISIBLE and RR_IF_FLIP_NORMALS of each item's flag word change.  The kernels read both per candidate and per hit
+// (rr_kernels.hip), the flat world normals hold both signs, and hidden items keep their place in the top level: nothing is re-derived.
+// item_host keeps the new values, from which rr_scene_update_materials rebuilds the flag words.  All or nothing, as the others.
+extern "C" int rr_scene_update_item_flags(rr_scene* s, const uint8_t* visible, const uint8_t* flip_normals, uint32_t n_items) try {
+    if (!s || !visible || !flip_normals) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_update_item_flags"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (n_items != s->h_items.size()) return fail(RR_ERR_INVALID_ARGUMENT, "%u items, the scene was created with %zu", n_items, s->h_items.size());
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<DItem> items = s->h_items;
+    for (uint32_t i = 0; i < n_items; i++)
+        items[i].flags = (items[i].flags & ~(uint32_t)(RR_IF_VISIBLE | RR_IF_FLIP_NORMALS)) | (visible[i] ? (uint32_t)RR_IF_VISIBLE : 0u) |
+                         (flip_normals[i] ? (uint32_t)RR_IF_FLIP_NORMALS : 0u);
+    auto apply = [&]() -> int { return copy_item_flag_records(s, items); };
+    auto restore = [&]() -> int { return copy_item_flag_records(s, s->h_items); };
+    RR_TRY(all_or_nothing("rr_scene_update_item_flags", &s->broken_item_flags, apply, restore));
+    s->h_items.swap(items);
+    for (uint32_t i = 0; i < n_items; i++) { s->item_host[i].visible = visible[i] != 0; s->item_host[i].flip_normals = flip_normals[i] != 0; }
+    return RR_OK;
+} RR_GUARD_END("rr_scene_update_item_flags")
+
+// A material's texture "+" (reference src/run.rs:936-947 loads a new image): the images are appended to the scene's texture list,
+// in order, and *first_index is the index of the first.  rr_scene_create lays the RGBA8 pool out in list order, so the existing
+// images keep their offsets and the new ones get those a scene created with the longer list gives them.  The grown pool and
+// descriptor array are built aside (device-to-device copy of the old pool, upload of the new images) and replace the old ones only
+// once complete: a failure leaves the scene as it was, with nothing to roll back.  Texture memory never shrinks.
+extern "C" int rr_scene_add_textures(rr_scene* s, const rr_texture* textures, uint32_t n_textures, uint32_t* first_index) try {
+    if (!s || !first_index || (n_textures && !textures)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_add_textures"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (uint32_t i = 0; i < n_textures; i++) { // as validate_scene
+        const rr_texture& t = textures[i];
+        if ((uint64_t)t.width * t.height > 0 && !t.rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "texture %u has no pixels", i);
+        if (t.width > 32768u || t.height > 32768u) return fail(RR_ERR_UNSUPPORTED, "texture %u is %ux%u", i, t.width, t.height);
+    }
+    const uint32_t first = (uint32_t)s->tex_width.size();
+    if (n_textures == 0) { *first_index = first; return RR_OK; }
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<DTexture> dtex = s->h_textures;
+    std::vector<uint32_t> widths = s->tex_width;
+    const uint64_t old_texels = dtex.empty() ? 0 : dtex.back().offset + (uint64_t)dtex.back().width * dtex.back().height;
+    uint64_t n_texels = old_texels;
+    for (uint32_t i = 0; i < n_textures; i++) {
+        DTexture d;
+        d.offset = n_texels; d.width = textures[i].width; d.height = textures[i].height;
+        dtex.push_back(d);
+        widths.push_back(textures[i].width);
+        n_texels += (uint64_t)textures[i].width * textures[i].height;
+    }
+    DevBuf texels, descs;
+    HIP_TRY(texels.reserve(std::max<uint64_t>(n_texels, 1) * 4));
+    HIP_TRY(descs.reserve(dtex.size() * sizeof(DTexture)));
+    if (old_texels) HIP_TRY(hipMemcpy(texels.p, s->texels.p, old_texels * 4, hipMemcpyDeviceToDevice)); // frames in flight only read the old pool
+    for (uint32_t i = 0; i < n_textures; i++) {
+        const uint64_t n = (uint64_t)textures[i].width * textures[i].height;
+        if (n) HIP_TRY(hipMemcpy(texels.as<uint32_t>() + dtex[first + i].offset, textures[i].rgba8, n * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(descs.p, dtex.data(), dtex.size() * sizeof(DTexture), hipMemcpyHostToDevice));
+    RR_FAULT_POINT("add_textures.device");
+    HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the pool that is freed below
+    // the pool and the descriptors of the longer list replace the old ones (frees them); material records keep their descriptors
+    // (the old images did not move) and name the new images after a rr_scene_update_materials
+    s->texels = std::move(texels);
+    s->textures = std::move(descs);
+    s->h_textures.swap(dtex);
+    s->tex_width.swap(widths);
+    s->view.texels = s->texels.as<uint32_t>();
+    s->view.textures = s->textures.as<DTexture>();
+    *first_index = first;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_add_textures")
 
 // ---------------------------------------------------------------------------
 // frame

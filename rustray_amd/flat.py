@@ -225,6 +225,16 @@ class Light:
     max_angle: float = float(np.float32(np.pi) / np.float32(2.0))
     light_type: int = RR_LIGHT_POINT
     enabled: bool = True
+    id: int = 0   # Light::id (src/scene.rs:40-51): names the light for Scene.delete_light_by_id; does not cross the ABI
+
+    def c_struct(self) -> "rr_light":
+        c = rr_light()
+        c.pos[:] = [np.float32(v) for v in self.pos]
+        c.dir[:] = [np.float32(v) for v in self.dir]
+        c.color[:] = [np.float32(v) for v in self.color]
+        c.intensity, c.max_angle = np.float32(self.intensity), np.float32(self.max_angle)
+        c.light_type, c.enabled = self.light_type, int(self.enabled)
+        return c
 
 
 def _colmajor(m: np.ndarray):
@@ -288,12 +298,7 @@ class FlatScene:
             c.visible, c.flip_normals = int(it.visible), int(it.flip_normals)
         lights = (rr_light * max(1, len(self.lights)))()
         for i, l in enumerate(self.lights):
-            c = lights[i]
-            c.pos[:] = [np.float32(v) for v in l.pos]
-            c.dir[:] = [np.float32(v) for v in l.dir]
-            c.color[:] = [np.float32(v) for v in l.color]
-            c.intensity, c.max_angle = np.float32(l.intensity), np.float32(l.max_angle)
-            c.light_type, c.enabled = l.light_type, int(l.enabled)
+            lights[i] = l.c_struct()
         fs = rr_flat_scene()
         fs.abi_version = RR_ABI_VERSION
         fs.n_items, fs.n_meshes, fs.n_materials = len(self.items), len(self.meshes), len(self.materials)

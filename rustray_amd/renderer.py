@@ -22,6 +22,58 @@ from . import capi
 from .camera import Camera
 from .flat import FlatScene, make_config, rr_config, rr_region
 
+# the in-place steps of Raytracing.apply_scene, in the order they run; RECREATE stands alone
+IN_PLACE_STEPS = ("add_textures", "update_materials", "update_transforms", "update_item_flags", "update_lights")
+RECREATE = "recreate"
+
+
+def _bits(a, dtype=np.float32) -> bytes:
+    return np.ascontiguousarray(np.asarray(a, dtype)).tobytes()
+
+
+def _same_array(a, b) -> bool:
+    if a is b:
+        return True
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _same_mesh(a, b) -> bool:
+    return a is b or all(_same_array(getattr(a, k), getattr(b, k)) for k in ("positions", "indices", "uvs", "uv_indices", "normals", "normal_indices"))
+
+
+def plan_scene_update(old: FlatScene, new: FlatScene) -> list:
+    """What turns a handle created from `old` into one that renders what a handle created from `new` renders, at the least cost
+    (Run::restart_rendering after a GUI edit, reference src/run.rs:395-420).  Returns [RECREATE] when the item list (count, kind,
+    id, mesh or material indices, radius, local box), a mesh, the material count or an existing texture image differs, or the
+    texture list got shorter; else the IN_PLACE_STEPS whose part differs, in their order (empty: nothing to do).  Values are
+    compared as the bits that cross the ABI."""
+    if len(old.items) != len(new.items) or len(old.materials) != len(new.materials) or len(old.meshes) != len(new.meshes):
+        return [RECREATE]
+    if len(new.textures) < len(old.textures):
+        return [RECREATE]
+    for a, b in zip(old.items, new.items):
+        if (a.kind, a.id, a.mesh, a.material, a.material_cache) != (b.kind, b.id, b.mesh, b.material, b.material_cache):
+            return [RECREATE]
+        if _bits([a.radius, *a.bbox_min, *a.bbox_max]) != _bits([b.radius, *b.bbox_min, *b.bbox_max]):
+            return [RECREATE]
+    if not all(_same_mesh(a, b) for a, b in zip(old.meshes, new.meshes)):
+        return [RECREATE]
+    if not all(_same_array(a, b) for a, b in zip(old.textures, new.textures)):
+        return [RECREATE]
+    steps = []
+    if len(new.textures) > len(old.textures):
+        steps.append("add_textures")
+    if any(bytes(a.c_struct()) != bytes(b.c_struct()) for a, b in zip(old.materials, new.materials)):
+        steps.append("update_materials")
+    if any(_bits(a.trans) != _bits(b.trans) or _bits(a.trans_inv) != _bits(b.trans_inv) for a, b in zip(old.items, new.items)):
+        steps.append("update_transforms")
+    if any((bool(a.visible), bool(a.flip_normals)) != (bool(b.visible), bool(b.flip_normals)) for a, b in zip(old.items, new.items)):
+        steps.append("update_item_flags")
+    if len(old.lights) != len(new.lights) or any(bytes(a.c_struct()) != bytes(b.c_struct()) for a, b in zip(old.lights, new.lights)):
+        steps.append("update_lights")
+    return steps
+
 
 class Raytracing:
     """Scene + RaytracingConfig, as reference `Raytracing` (src/raytracing.rs:205-224)."""
@@ -54,6 +106,36 @@ class Raytracing:
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
         return (int(r.object_id), float(r.distance)) if r.hit else None
+
+    def apply_scene(self, new_flat: FlatScene) -> list:
+        """The host's restart after a scene edit (Run::restart_rendering, reference src/run.rs:395-420): brings the device scene
+        to `new_flat` by the cheapest correct path (plan_scene_update) and returns the plan it carried out.  In-place steps run in
+        order; if one fails the scene is created anew from `new_flat` and [RECREATE] is returned.  The new handle is created
+        before the old one is released, so a failed re-create leaves the old scene in place (and raises)."""
+        plan = plan_scene_update(self.flat_scene, new_flat)
+        if plan != [RECREATE]:
+            ds = self.device_scene
+            try:
+                for step in plan:
+                    if step == "add_textures":
+                        ds.add_textures(new_flat.textures[len(self.flat_scene.textures):])
+                    elif step == "update_materials":
+                        ds.update_materials(new_flat.materials)
+                    elif step == "update_transforms":
+                        ds.update_transforms(np.stack([np.asarray(it.trans, np.float32) for it in new_flat.items]),
+                                             np.stack([np.asarray(it.trans_inv, np.float32) for it in new_flat.items]))
+                    elif step == "update_item_flags":
+                        ds.update_item_flags([it.visible for it in new_flat.items], [it.flip_normals for it in new_flat.items])
+                    elif step == "update_lights":
+                        ds.update_lights(new_flat.lights)
+            except capi.RustrayHipError:
+                plan = [RECREATE]
+        if plan == [RECREATE]:
+            fresh = capi.DeviceScene(new_flat, self.device_scene.device)
+            self.device_scene.close()
+            self.device_scene = fresh
+        self.flat_scene = new_flat
+        return plan
 
     def close(self):
         self.device_scene.close()

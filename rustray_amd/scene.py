@@ -194,11 +194,11 @@ class Scene:
                 max_angle = _f32(math.radians(_f32(light["max_angle"])))
             lt = {"point": RR_LIGHT_POINT, "directional": RR_LIGHT_DIRECTIONAL, "spot": RR_LIGHT_SPOT}.get(
                 light["light_type"], RR_LIGHT_POINT)
-            self.get_next_id()
+            lid = self.get_next_id()
             self.lights.append(Light(pos=self._xyz(light, "pos", (0.0, 0.0, 0.0)),
                                      dir=self._xyz(light, "dir", (0.0, -1.0, 0.0)),
                                      color=self._rgb(light, "color", (0.0, 0.0, 0.0)),
-                                     intensity=_f32(light["intensity"]), max_angle=max_angle, light_type=lt))
+                                     intensity=_f32(light["intensity"]), max_angle=max_angle, light_type=lt, id=lid))
         for obj in data.get("objects") or []:
             mat_id = self.get_next_id()
             material = Material()
@@ -384,17 +384,17 @@ class Scene:
         double_check: Dict[int, int] = {}   # glTF material identity -> Material id
         for gscene in gltf.load(self._path(path)):
             for l in gscene.lights:
-                self.get_next_id()
+                lid = self.get_next_id()
                 half_pi = _f32(F32(math.pi) / F32(2.0))
                 if l.kind == "point":       # intensity / 10 (src/scene.rs:747)
                     self.lights.append(Light(pos=l.position, dir=(0.0, -1.0, 0.0), color=l.color, intensity=_f32(F32(l.intensity) / F32(10.0)),
-                                             max_angle=half_pi, light_type=RR_LIGHT_POINT))
+                                             max_angle=half_pi, light_type=RR_LIGHT_POINT, id=lid))
                 elif l.kind == "directional":
                     self.lights.append(Light(pos=(0.0, 0.0, 0.0), dir=l.direction, color=l.color, intensity=l.intensity,
-                                             max_angle=half_pi, light_type=RR_LIGHT_DIRECTIONAL))
+                                             max_angle=half_pi, light_type=RR_LIGHT_DIRECTIONAL, id=lid))
                 else:
                     self.lights.append(Light(pos=l.position, dir=l.direction, color=l.color, intensity=l.intensity,
-                                             max_angle=l.outer_cone_angle, light_type=RR_LIGHT_SPOT))
+                                             max_angle=l.outer_cone_angle, light_type=RR_LIGHT_SPOT, id=lid))
             if gscene.cameras:
                 cam = gscene.cameras[0]
                 t = cam.transform
@@ -460,10 +460,27 @@ class Scene:
 
     # ---- defaults (src/scene.rs:1386-1401, :1426-1562) ------------------------------------
     def add_default_light(self) -> None:
-        self.get_next_id()
+        lid = self.get_next_id()
         self.lights.append(Light(pos=(-2.0, 10.0, 5.0), dir=(0.0, -1.0, 0.0), color=(1.0, 1.0, 1.0),
                                  intensity=200.0, max_angle=_f32(F32(math.pi) / F32(2.0)),
-                                 light_type=RR_LIGHT_POINT))
+                                 light_type=RR_LIGHT_POINT, id=lid))
+
+    # ---- GUI deletes (src/scene.rs:1580-1620): the LAST entry with the id goes, later entries move up (Vec::remove) ----
+    def delete_light_by_id(self, id: int) -> None:
+        index = None
+        for i, light in enumerate(self.lights):
+            if light.id == id:
+                index = i
+        if index is not None:
+            del self.lights[index]
+
+    def delete_object_by_id(self, id: int) -> None:
+        index = None
+        for i, item in enumerate(self.items):
+            if item.id == id:
+                index = i
+        if index is not None:
+            del self.items[index]
 
     def _local_bbox(self, it: Shape):
         if it.kind == RR_ITEM_SPHERE:
