@@ -46,6 +46,10 @@ def lib():
         _LIB.rro_scene_create.restype = C.c_void_p
         _LIB.rro_scene_destroy.argtypes = [C.c_void_p]
         _LIB.rro_render_scene.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]
+        _LIB.rro_render_scene_means.restype = C.c_int
+        _LIB.rro_render_scene_means.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int]
+        _LIB.rro_render_means.restype = C.c_int
+        _LIB.rro_render_means.argtypes = [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_int]
         _LIB.rro_wrap.restype = C.c_uint32
         _LIB.rro_wrap.argtypes = [C.c_float, C.c_uint32]
         _LIB.rro_fresnel.restype = C.c_float
@@ -91,10 +95,20 @@ class PreparedScene:
         self.close()
 
 
+MEANS_STRIDE = 10  # oracle.cpp RRO_MEANS_STRIDE: mean r, g, b, depth, normal x, y, z; largest |r|, |g|, |b| of any sample
+
+
 def render(fs_struct, cam: rr_camera, cfg: rr_config, sample_xy=None, window=None,
-           n_threads: int = 1, brute_force: bool = False, want_counters: bool = False):
+           n_threads: int = 1, brute_force: bool = False, want_counters: bool = False,
+           want_means: bool = False, samples_used=None):
     """Render with the CPU restatement.  `fs_struct`: an rr_flat_scene or a PreparedScene.
-    Returns dict(rgba, normal, depth, object_id[, counters])."""
+    Returns dict(rgba, normal, depth, object_id[, counters]).
+
+    want_means: also the float64 means of the samples' own f32 terms, without min(., 1): mean_rgb (h, w, 3),
+    mean_depth (h, w), mean_normal (h, w, 3), max_abs_rgb (h, w, 3), the largest |component| of any sample's
+    colour, and mean_gamma (h, w), cfg.gamma_correction.  Outside `window` the means are 0.
+    samples_used=k (1 <= k <= cfg.samples): samples 0..k-1 of the cfg.samples-sample frame (its sub-sample table
+    and cell size), divided by k: the frame a progressive preview shows after k sample slices."""
     w, h = cam.width, cam.height
     rgba = np.zeros((h, w, 4), np.uint8)
     normal = np.zeros((h, w, 3), np.float32)
@@ -107,10 +121,19 @@ def render(fs_struct, cam: rr_camera, cfg: rr_config, sample_xy=None, window=Non
     if sample_xy is not None:
         sample_xy = np.ascontiguousarray(sample_xy, np.uint16)
         sxy = _p(sample_xy)
+    if samples_used is not None and not 1 <= int(samples_used) <= cfg.samples:
+        raise ValueError(f"samples_used={samples_used} outside 1..{cfg.samples}")
+    k = 0 if samples_used is None else int(samples_used)
+    means = np.zeros((h, w, MEANS_STRIDE), np.float64) if want_means else None
+    mp = _p(means) if want_means else None
     if isinstance(fs_struct, PreparedScene):
-        rc = lib().rro_render_scene(fs_struct._h, C.byref(cam), C.byref(cfg), sxy, C.byref(fr),
+        rc = lib().rro_render_scene_means(fs_struct._h, C.byref(cam), C.byref(cfg), sxy, C.byref(fr),
+                                          C.c_int(x0), C.c_int(y0), C.c_int(x1), C.c_int(y1), C.c_int(n_threads),
+                                          C.byref(cnt) if want_counters else None, mp, C.c_int(k))
+    elif want_means or k:
+        rc = lib().rro_render_means(C.byref(fs_struct), C.byref(cam), C.byref(cfg), sxy, C.byref(fr),
                                     C.c_int(x0), C.c_int(y0), C.c_int(x1), C.c_int(y1), C.c_int(n_threads),
-                                    C.byref(cnt) if want_counters else None)
+                                    C.c_int(1 if brute_force else 0), C.byref(cnt) if want_counters else None, mp, C.c_int(k))
     else:
         rc = lib().rro_render(C.byref(fs_struct), C.byref(cam), C.byref(cfg), sxy, C.byref(fr),
                               C.c_int(x0), C.c_int(y0), C.c_int(x1), C.c_int(y1), C.c_int(n_threads),
@@ -120,6 +143,10 @@ def render(fs_struct, cam: rr_camera, cfg: rr_config, sample_xy=None, window=Non
     out = dict(rgba=rgba, normal=normal, depth=depth, object_id=oid)
     if want_counters:
         out["counters"] = cnt.as_dict()
+    if want_means:
+        out.update(mean_rgb=means[..., 0:3].copy(), mean_depth=means[..., 3].copy(), mean_normal=means[..., 4:7].copy(),
+                   max_abs_rgb=means[..., 7:10].copy(),
+                   mean_gamma=np.full((h, w), bool(cfg.gamma_correction)))  # per pixel, so that windows slice it like the rest
     return out
 
 

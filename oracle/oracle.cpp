@@ -1133,13 +1133,21 @@ static Ray make_primary(const rr_camera& cam, const rr_config& cfg, int x, int y
 
 struct Pixel { uint8_t r, g, b; V3 normal; float depth; uint32_t id; };
 
+// Side output of render_pixel (TEST INFRASTRUCTURE, tests/helpers.py band checks): per pixel, the float64 means of the
+// samples' own f32 colour, depth and normal terms, without the min(., 1), and the largest |component| of any sample's colour.
+enum { RRO_MEAN_R, RRO_MEAN_G, RRO_MEAN_B, RRO_MEAN_DEPTH, RRO_MEAN_NX, RRO_MEAN_NY, RRO_MEAN_NZ,
+       RRO_MAXABS_R, RRO_MAXABS_G, RRO_MAXABS_B, RRO_MEANS_STRIDE };
+
+// n_used: the first n_used samples of the cfg.samples-sample frame (sub-sample table and cell size of the whole frame), the
+// mean taken over those: what a progressive preview after n_used sample slices shows.
 static Pixel render_pixel(const OScene& sc, const rr_camera& cam, const rr_config& cfg,
-                          const uint16_t* sample_xy, uint32_t cell_size, int x, int y) {
+                          const uint16_t* sample_xy, uint32_t cell_size, int x, int y, uint32_t n_used, double* means) {
     V3 color = v3(0, 0, 0);
     float depth = 0.0f;
     V3 normal = v3(0, 0, 0);
     uint32_t object_id = 0;
-    uint32_t n = cfg.samples;
+    uint32_t n = n_used;
+    double m[RRO_MEANS_STRIDE] = {};
     RenderCtx rc;
     rc.sc = &sc; rc.cfg = &cfg;
     rc.rng.seed = cfg.seed;
@@ -1152,6 +1160,18 @@ static Pixel render_pixel(const OScene& sc, const rr_camera& cam, const rr_confi
         depth += res.depth;
         normal = normal + res.normal;
         object_id = res.id;
+        if (means) {
+            m[RRO_MEAN_R] += (double)res.color.x; m[RRO_MEAN_G] += (double)res.color.y; m[RRO_MEAN_B] += (double)res.color.z;
+            m[RRO_MEAN_DEPTH] += (double)res.depth;
+            m[RRO_MEAN_NX] += (double)res.normal.x; m[RRO_MEAN_NY] += (double)res.normal.y; m[RRO_MEAN_NZ] += (double)res.normal.z;
+            m[RRO_MAXABS_R] = std::fmax(m[RRO_MAXABS_R], std::fabs((double)res.color.x)); // fmax: a NaN sample leaves it as it was
+            m[RRO_MAXABS_G] = std::fmax(m[RRO_MAXABS_G], std::fabs((double)res.color.y));
+            m[RRO_MAXABS_B] = std::fmax(m[RRO_MAXABS_B], std::fabs((double)res.color.z));
+        }
+    }
+    if (means) {
+        for (int k = RRO_MEAN_R; k <= RRO_MEAN_NZ; k++) m[k] /= (double)n;
+        std::memcpy(means, m, sizeof m);
     }
     float nf = (float)n;
     color = color / nf;
@@ -1266,30 +1286,47 @@ void* rro_scene_create(const rr_flat_scene* fs, int brute_force) {
 }
 void rro_scene_destroy(void* h) { delete (OScene*)h; }
 
+// means: null, or RRO_MEANS_STRIDE doubles per frame pixel (only the window is written).  samples_used: 0 for all of
+// cfg->samples, else 1..cfg->samples (render_pixel's n_used).
 static int render_prepared(const OScene& sc, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
-                           int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters);
+                           int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters, double* means, int samples_used);
+
+// rro_render_scene / rro_render keep their signatures (callers built against them pass no means); the *_means forms add
+// the float64 side outputs and samples_used.
+int rro_render_scene_means(void* h, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
+                           int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters, double* means, int samples_used) {
+    if (!h || !cam || !cfg || !out || !out->rgba8) return -1;
+    return render_prepared(*(OScene*)h, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, counters, means, samples_used);
+}
 
 int rro_render_scene(void* h, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
                      int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters) {
-    if (!h || !cam || !cfg || !out || !out->rgba8) return -1;
-    return render_prepared(*(OScene*)h, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, counters);
+    return rro_render_scene_means(h, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, counters, nullptr, 0);
 }
 
-int rro_render(const rr_flat_scene* fs, const rr_camera* cam, const rr_config* cfg,
-               const uint16_t* sample_xy, const rr_frame* out,
-               int x0, int y0, int x1, int y1, int n_threads, int brute_force, rro_counters* counters) {
+int rro_render_means(const rr_flat_scene* fs, const rr_camera* cam, const rr_config* cfg,
+                     const uint16_t* sample_xy, const rr_frame* out,
+                     int x0, int y0, int x1, int y1, int n_threads, int brute_force, rro_counters* counters, double* means, int samples_used) {
     if (!fs || !cam || !cfg || !out || !out->rgba8) return -1;
     OScene sc;
     sc.fs = fs;
     sc.brute_force = brute_force != 0;
     sc.prepare();
-    return render_prepared(sc, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, counters);
+    return render_prepared(sc, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, counters, means, samples_used);
+}
+
+int rro_render(const rr_flat_scene* fs, const rr_camera* cam, const rr_config* cfg,
+               const uint16_t* sample_xy, const rr_frame* out,
+               int x0, int y0, int x1, int y1, int n_threads, int brute_force, rro_counters* counters) {
+    return rro_render_means(fs, cam, cfg, sample_xy, out, x0, y0, x1, y1, n_threads, brute_force, counters, nullptr, 0);
 }
 
 static int render_prepared(const OScene& sc, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
-                           int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters) {
+                           int x0, int y0, int x1, int y1, int n_threads, rro_counters* counters, double* means, int samples_used) {
     const rr_flat_scene* fs = sc.fs;
     (void)fs;
+    if (samples_used < 0 || samples_used > (int)cfg->samples) return -2;
+    const uint32_t n_used = samples_used > 0 ? (uint32_t)samples_used : cfg->samples;
     std::vector<uint16_t> table;
     uint32_t cell_size = cell_size_for(cfg->samples);
     if (!sample_xy) {
@@ -1322,8 +1359,8 @@ static int render_prepared(const OScene& sc, const rr_camera* cam, const rr_conf
             const Cell& c = cells[i];
             for (int y = c.y0; y < c.y1; y++)
                 for (int x = c.x0; x < c.x1; x++) {
-                    Pixel p = render_pixel(sc, *cam, *cfg, sample_xy, cell_size, x, y);
                     size_t pi = (size_t)y * cam->width + x;
+                    Pixel p = render_pixel(sc, *cam, *cfg, sample_xy, cell_size, x, y, n_used, means ? means + RRO_MEANS_STRIDE * pi : nullptr);
                     out->rgba8[4 * pi + 0] = p.r; out->rgba8[4 * pi + 1] = p.g;
                     out->rgba8[4 * pi + 2] = p.b; out->rgba8[4 * pi + 3] = 255;
                     if (out->normal) { out->normal[3 * pi] = p.normal.x; out->normal[3 * pi + 1] = p.normal.y; out->normal[3 * pi + 2] = p.normal.z; }

@@ -5,7 +5,7 @@ import pytest
 from rustray_amd.flat import make_config
 from tests.corner_scenes import (INSIDE_SPHERES, alpha_occluder_scene, deep_mesh_scene, equal_toi_scene, inside_spheres_scene,
                                  projective_scene, zero_light_term_scene)
-from tests.helpers import camera_for, compare_frames, load_scene
+from tests.helpers import assert_in_band, camera_for, compare_frames, load_scene
 from tests.test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +16,7 @@ def _check(hip, oracle, fs, w=96, h=96, **cfg):
     c = make_config(**({"samples": 2, "monte_carlo": True, "seed": 3} | cfg))
     with hip.DeviceScene(fs, 0) as ds:
         out = ds.render(cam, c)
-    ref = oracle.render(fs.c_struct(), cam, c, n_threads=8)
+    ref = oracle.render(fs.c_struct(), cam, c, want_means=True, n_threads=8)
     assert_parity(out, ref)
     return out, ref
 
@@ -84,9 +84,10 @@ def test_non_finite_samples_reach_the_pixel_as_in_the_reference(hip, oracle, nam
     cfg = make_config(**fs.meta["kw"])
     with hip.DeviceScene(fs, 0) as ds:
         out = ds.render(cam, cfg)
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8)
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, res
+    assert_in_band(res, name)
     assert int((ref["rgba"][..., :3] == 255).all(axis=-1).sum()) >= 1   # the white pixels are there
 
 
@@ -104,7 +105,7 @@ def test_zero_light_term_still_reaches_the_pixel_through_a_nan_uv_and_only_then(
         with hip.DeviceScene(fs, 0) as ds:
             out = ds.render(cam, cfg)
             st = ds.stats()
-        ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+        ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True)
         assert_parity(out, ref)
         white[degenerate] = int((out["rgba"][..., :3] == 255).all(axis=-1).sum())
         if degenerate:
@@ -149,9 +150,10 @@ def test_depth_of_far_hits_is_merged_per_pixel(hip, oracle):
         assert float(np.nanmax(out["depth"])) > 512.0
         ds.set_profiling(True)
         ds.render(cam_f, cfg); t_far = ds.stats()["ms_shade"]
-    ref = oracle.render(far.c_struct(), cam_f, make_config(samples=64, monte_carlo=True, seed=6, max_recursion=2), n_threads=8)
+    ref = oracle.render(far.c_struct(), cam_f, make_config(samples=64, monte_carlo=True, seed=6, max_recursion=2), want_means=True, n_threads=8)
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["max_depth_rel"] < 1e-4, res
+    assert_in_band(res, "far")
     with hip.DeviceScene(near, 0) as ds:
         ds.set_profiling(True)
         cam_n = camera_for(near, 160, 96).c_struct()

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import make_config
-from tests.helpers import camera_for, compare_frames, load_scene
+from tests.helpers import assert_in_band, camera_for, compare_frames, load_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +22,11 @@ def test_c2_monkey_full_size(hip, oracle):
     assert np.array_equal(a["rgba"], b["rgba"]) and np.array_equal(a["depth"], b["depth"])        # idempotent, bit for bit
     assert st["primary_rays"] == 800 * 600 * 16
     win = (368, 268, 432, 332)                                                                     # 64x64 tile through the oracle
-    ref = oracle.render(fs.c_struct(), cam, cfg, window=win, n_threads=16)
+    ref = oracle.render(fs.c_struct(), cam, cfg, window=win, want_means=True, n_threads=16)
     x0, y0, x1, y1 = win
     r = compare_frames({k: v[y0:y1, x0:x1] for k, v in a.items()}, {k: v[y0:y1, x0:x1] for k, v in ref.items()})
     assert r["n_rgb_over"] == 0 and r["n_id_diff"] == 0, r
+    assert_in_band(r)
 
 
 def test_c4_sponza_syn_full_frame_properties(hip, oracle):
@@ -50,10 +51,11 @@ def test_c4_sponza_syn_full_frame_properties(hip, oracle):
     got = frame.cpu().numpy().reshape(720, 1280, 4)
     assert np.array_equal(got, whole["rgba"])
     win = (608, 400, 672, 432)
-    ref = oracle.render(fs.c_struct(), cam, cfg, window=win, n_threads=16)
+    ref = oracle.render(fs.c_struct(), cam, cfg, window=win, want_means=True, n_threads=16)
     x0, y0, x1, y1 = win
     d = np.abs(whole["rgba"][y0:y1, x0:x1, :3].astype(int) - ref["rgba"][y0:y1, x0:x1, :3].astype(int))
     assert d.max() <= 1
+    assert_in_band(compare_frames({"rgba": whole["rgba"][y0:y1, x0:x1]}, {k: v[y0:y1, x0:x1] for k, v in ref.items()}))
 
 
 # ---------------------------------------------------------------------------
@@ -87,9 +89,10 @@ def _full_size_config(hip, oracle, fs, spp, tile_win, n_ranks=8):
         for k in ("rgba", "depth", "object_id"):
             assert np.array_equal(a[k], m[k]), k
     x0, y0, x1, y1 = tile_win
-    ref = oracle.render(fs.c_struct(), cam, cfg, window=tile_win, n_threads=16)
+    ref = oracle.render(fs.c_struct(), cam, cfg, window=tile_win, want_means=True, n_threads=16)
     r = compare_frames({k: v[y0:y1, x0:x1] for k, v in a.items()}, {k: v[y0:y1, x0:x1] for k, v in ref.items()})
     assert r["n_rgb_over"] == 0 and r["n_id_diff"] == 0 and r["nan_mismatch"] == 0, r
+    assert_in_band(r)
     return st_a
 
 

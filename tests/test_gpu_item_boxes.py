@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import Item, Material, RR_ITEM_SPHERE, make_config
-from tests.helpers import camera_for, compare_frames
+from tests.helpers import assert_in_band, camera_for, compare_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +48,7 @@ def _turned(seed, extra_balls=True):
 def _check(out, ref, what):
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, (what, res)
+    assert_in_band(res, what)
 
 
 @pytest.mark.parametrize("seed", [41, 42])
@@ -59,7 +60,7 @@ def test_turned_instances_against_the_oracle(hip, oracle, seed):
     with hip.DeviceScene(fs, 0) as ds:
         out = ds.render(cam, cfg)
         st = ds.stats()
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8, want_counters=True, brute_force=True)   # every item is a candidate
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True, brute_force=True)   # every item is a candidate
     _check(out, ref, "all-items form")
     c = ref["counters"]
     assert (st["primary_rays"], st["secondary_rays"], st["shaded_hits"]) == (c["rays_primary"], c["rays_secondary"], c["shaded_hits"])
@@ -88,4 +89,4 @@ def test_turned_instances_after_a_transform_update(hip, oracle):
     assert (moved["rgba"] != first["rgba"]).any()
     for k in ("rgba", "depth", "object_id"):
         assert np.array_equal(moved[k], fresh[k]), k
-    _check(moved, oracle.render(a.c_struct(), cam, cfg, n_threads=8, brute_force=True), "after the update")
+    _check(moved, oracle.render(a.c_struct(), cam, cfg, want_means=True, n_threads=8, brute_force=True), "after the update")

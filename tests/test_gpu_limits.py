@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import Light, make_config
-from tests.helpers import camera_for, compare_frames, load_scene
+from tests.helpers import assert_in_band, camera_for, compare_frames, load_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +16,10 @@ def _check(hip, oracle, fs, w, h, cfg, threads=8):
     with hip.DeviceScene(fs, 0) as ds:
         out = ds.render(cam, cfg)
         st = ds.stats()
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=threads, want_counters=True)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=threads, want_counters=True)
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, res
+    assert_in_band(res)
     c = ref["counters"]
     assert st["primary_rays"] == c["rays_primary"] and st["secondary_rays"] == c["rays_secondary"] and st["shaded_hits"] == c["shaded_hits"]
     return out, st
@@ -58,9 +59,10 @@ def test_many_samples_on_a_small_frame(hip, oracle):
         with pytest.raises(hip.RustrayHipError) as e:
             ds.render(cam, make_config(samples=16383))          # beyond the BUILT-IN table's limit (RR_MAX_SAMPLES)
         assert e.value.code == -2
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8)
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, res
+    assert_in_band(res)
 
 
 def test_the_references_own_sample_limit_with_the_callers_table(hip, oracle):
@@ -78,9 +80,10 @@ def test_the_references_own_sample_limit_with_the_callers_table(hip, oracle):
         with pytest.raises(hip.RustrayHipError) as e:
             ds.render(cam, make_config(samples=32767), sample_xy=np.zeros((32767, 2), np.uint16))
         assert e.value.code == -2
-    ref = oracle.render(fs.c_struct(), cam, cfg, sample_xy=table, n_threads=8)
+    ref = oracle.render(fs.c_struct(), cam, cfg, sample_xy=table, want_means=True, n_threads=8)
     res = compare_frames(out, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, res
+    assert_in_band(res)
 
 
 def test_lights_none_many_and_disabled(hip, oracle):

@@ -17,7 +17,7 @@ from rustray_amd import capi
 from rustray_amd.flat import RR_LIGHT_POINT, RR_LIGHT_SPOT, Light, make_config, rr_config, rr_flat_scene, rr_frame, rr_light, rr_texture
 from rustray_amd.renderer import RECREATE, Raytracing
 from rustray_amd.scene import Scene
-from tests.helpers import assert_frames_identical, camera_for, compare_frames
+from tests.helpers import assert_frames_identical, assert_in_band, camera_for, compare_frames
 from tests.test_gpu_scene_edits import EDIT_SCENES, edit_scene, frames_differ
 
 pytestmark = pytest.mark.gpu
@@ -48,9 +48,10 @@ def _check_against_oracle(hip, ds, cur, oracle, cfg, what):
     got = ds.render(cam, cfg)
     st = ds.stats()
     keep = copy.deepcopy(cur)   # c_struct() borrows the copy's arrays: it must outlive the call
-    ref = oracle.render(keep.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+    ref = oracle.render(keep.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True)
     res = compare_frames(got, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, (what, res)
+    assert_in_band(res, what)
     c = ref["counters"]
     assert (st["primary_rays"], st["secondary_rays"], st["shaded_hits"]) == (c["rays_primary"], c["rays_secondary"], c["shaded_hits"]), what
 

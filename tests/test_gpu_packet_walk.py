@@ -169,7 +169,7 @@ def test_padded_frame_equals_unpadded_frame(hip, oracle, base):
             assert [st[k] for k in RAYS] == [st0[k] for k in RAYS], (base, mode, n)
             in_range += in_packet_range(n)
             if n == 64 and mode == modes[0]:
-                o = oracle.render(p.c_struct(), cam, cfg, n_threads=16, want_counters=True, brute_force=True)
+                o = oracle.render(p.c_struct(), cam, cfg, want_means=True, n_threads=16, want_counters=True, brute_force=True)
                 assert_parity(out, o, f"{base} {mode} {n}")
                 c = o["counters"]
                 assert [st[k] for k in RAYS] == [c["rays_primary"], c["rays_secondary"], c["shaded_hits"]], (base, mode, n)
@@ -198,7 +198,7 @@ def test_shadow_packets_under_every_light_kind(hip, oracle):
             out, st = _render(hip, p, cam, cfg)
             assert_frames_identical(out, ref, f"{what} {n}")
             assert st["shadow_rays"] == st0["shadow_rays"] > 0 and [st[k] for k in RAYS] == [st0[k] for k in RAYS], what
-        o = oracle.render(p.c_struct(), cam, cfg, n_threads=16, brute_force=True)
+        o = oracle.render(p.c_struct(), cam, cfg, want_means=True, n_threads=16, brute_force=True)
         assert_parity(out, o, what)
 
 
@@ -423,7 +423,7 @@ def test_candidate_count(hip, oracle):
     cam = camera_for(fs, 96, 64).c_struct()
     cfg = make_config(samples=2, monte_carlo=True, seed=4, max_recursion=3)
     out, _ = _render(hip, fs, cam, cfg)
-    assert_parity(out, oracle.render(fs.c_struct(), cam, cfg, n_threads=16, brute_force=True), "ball field")
+    assert_parity(out, oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=16, brute_force=True), "ball field")
 
 
 def _far(fs, off=1e4, scale=1e3):
@@ -474,7 +474,7 @@ def test_equal_toi_ties_in_the_packet_range(hip, oracle):
         cam = camera_for(fs, 96, 96).c_struct()
         cfg = make_config(samples=2, monte_carlo=True, seed=3)
         out, _ = _render(hip, fs, cam, cfg)
-        assert_parity(out, oracle.render(fs.c_struct(), cam, cfg, n_threads=16), f"thick={thick}")
+        assert_parity(out, oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=16), f"thick={thick}")
         assert set(np.unique(out["object_id"])) - {100 + k for k in range(16)} == want
         rng = np.random.default_rng(1)
         o = np.stack([rng.uniform(-4, 4, 256), np.full(256, 6.0), rng.uniform(-4, 4, 256)], 1).astype(np.float32)
@@ -563,7 +563,7 @@ def test_d10_fixture_matches_the_item_tree_form(hip, oracle):
     cam = camera_for(fs, w, h).c_struct()
     cfg = make_config(**fs.meta["kw"])
     out, st = _render(hip, fs, cam, cfg)
-    tree = oracle.render(fs.c_struct(), cam, cfg, n_threads=16, want_counters=True)
+    tree = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=16, want_counters=True)
     allf = oracle.render(fs.c_struct(), cam, cfg, n_threads=16, want_counters=True, brute_force=True)
     assert np.array_equal(out["rgba"], tree["rgba"]) and np.array_equal(out["object_id"], tree["object_id"])
     assert_parity(out, tree, "item-tree form")

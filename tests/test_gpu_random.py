@@ -91,7 +91,7 @@ def test_random_scene_matches_oracle(hip, oracle, seed):
     with hip.DeviceScene(fs, 0) as ds:
         out = ds.render(cam, cfg)
         st = ds.stats()
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=14, want_counters=True)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=14, want_counters=True)
     assert_parity(out, ref, fs.name)
     c = ref["counters"]
     assert st["primary_rays"] == c["rays_primary"] and st["secondary_rays"] == c["rays_secondary"] and st["shaded_hits"] == c["shaded_hits"]

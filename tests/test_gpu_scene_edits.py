@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import Item, MeshData, make_config
-from tests.helpers import assert_frames_identical, camera_for, compare_frames, item_transforms, load_scene, with_transforms
+from tests.helpers import assert_frames_identical, assert_in_band, camera_for, compare_frames, item_transforms, load_scene, with_transforms
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +33,9 @@ def test_empty_mesh_item_is_legal_and_invisible(hip, oracle):
     with hip.DeviceScene(fs, 0) as ds, hip.DeviceScene(base, 0) as ds0:
         out, ref = ds.render(cam, cfg), ds0.render(cam, cfg)
         _same(out, ref)
-    res = compare_frames(out, oracle.render(fs.c_struct(), cam, cfg, n_threads=4))
+    res = compare_frames(out, oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=4))
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, res
+    assert_in_band(res)
 
 
 def test_scene_without_items_renders_black_and_accepts_updates(hip):
@@ -103,8 +104,9 @@ def test_material_edits_in_place_equal_a_fresh_scene(hip, oracle):
         _same(ds.render(cam, cfg), before)
         with pytest.raises(hip.RustrayHipError):
             ds.update_materials(edited.materials[:-1])
-    res = compare_frames(after, oracle.render(edited.c_struct(), cam, cfg, n_threads=8))
+    res = compare_frames(after, oracle.render(edited.c_struct(), cam, cfg, want_means=True, n_threads=8))
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, res
+    assert_in_band(res)
 
 
 def test_tuning_is_validated(hip):
@@ -298,9 +300,10 @@ def test_material_flag_edits_in_place_equal_a_fresh_scene_and_the_oracle(hip, or
             assert frames_differ(got, prev), f"{case} step {k}: the edit does not change the frame, so it tests nothing"
             with hip.DeviceScene(edited, 0) as fresh:
                 assert_frames_identical(got, fresh.render(cam, cfg), f"{case} step {k}: in place vs a fresh scene")
-            ref = oracle.render(edited.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+            ref = oracle.render(edited.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True)
             res = compare_frames(got, ref)
             assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0, (case, k, res)
+            assert_in_band(res, f"{case} {k}")
             c = ref["counters"]
             assert (st["primary_rays"], st["secondary_rays"], st["shaded_hits"]) == (c["rays_primary"], c["rays_secondary"], c["shaded_hits"]), (case, k)
             prev = got

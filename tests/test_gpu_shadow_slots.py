@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from rustray_amd.flat import make_config
-from tests.helpers import camera_for, compare_frames
+from tests.helpers import assert_in_band, camera_for, compare_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -30,9 +30,10 @@ def test_many_items_several_lights_fixed_shadow_slots(hip, oracle, seed):
         c = ds.render(cam, cfg)
     for k in ("rgba", "depth", "object_id"):
         assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]), k
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True)
     res = compare_frames(a, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, res
+    assert_in_band(res)
     assert st["shadow_rays"] > 0 and st["shadow_rays"] <= ref["counters"]["rays_shadow"]
 
 
@@ -67,9 +68,10 @@ def test_any_number_of_lights(hip, oracle):
             ds.set_tuning(shade_chunk_rays=65536, queue_budget_bytes=1)
             b = ds.render(cam, cfg)
         assert np.array_equal(a["rgba"], b["rgba"])
-        ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8, want_counters=True)
+        ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8, want_counters=True)
         res = compare_frames(a, ref)
         assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, (n_on, res)
+        assert_in_band(res, f"{n_on} lights on")
         assert 0 < st["shadow_rays"] <= ref["counters"]["rays_shadow"] and st["shaded_hits"] == ref["counters"]["shaded_hits"], n_on
 
 
@@ -100,7 +102,8 @@ def test_hundreds_of_unshadowed_lights_do_not_overflow_the_lane_sums(hip, oracle
     with hip.DeviceScene(fs, 0) as ds:
         a = ds.render(cam, cfg)
         assert ds.stats()["shadow_rays"] == 0
-    ref = oracle.render(fs.c_struct(), cam, cfg, n_threads=8)
+    ref = oracle.render(fs.c_struct(), cam, cfg, want_means=True, n_threads=8)
     res = compare_frames(a, ref)
     assert res["n_rgb_over"] == 0 and res["n_id_diff"] == 0 and res["nan_mismatch"] == 0, res
+    assert_in_band(res)
     assert (a["rgba"][..., :3] == 255).mean() > 0.1   # the sums really are large: most lit pixels saturate
