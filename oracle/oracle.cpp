@@ -1472,6 +1472,13 @@ int rro_ray_aabb(const float* mins, const float* maxs, const float* origin, cons
     Ray r{load3(origin), load3(dir)};
     return aabb_cast_local_ray(mins, maxs, r, solid != 0, toi) ? 1 : 0;
 }
+// the reference's candidate test of one item: the ray moved into the item's space with its f32 inverse, against the local box
+// (what a world-space box in front of it must never cull: tests/native/scene_build_test.cpp)
+int rro_item_box_hit(const rr_item* item, const float* origin, const float* dir) {
+    Ray r{load3(origin), load3(dir)};
+    float toi;
+    return aabb_cast_local_ray(item->bbox_min, item->bbox_max, inverse_ray(*item, r), false, &toi) ? 1 : 0;
+}
 int rro_ray_triangle(const float* a, const float* b, const float* c, const float* origin, const float* dir,
                      float* toi, float* normal, int* back) {
     Ray r{load3(origin), load3(dir)};

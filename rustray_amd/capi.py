@@ -40,7 +40,7 @@ def source_id() -> str:
     counter profile (profiles/*_sq_counters.json) to the build a bench run measures."""
     import hashlib
     h = hashlib.sha256()
-    files = [os.path.join(_HERE, "csrc", f) for f in ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h")]
+    files = [os.path.join(_HERE, "csrc", f) for f in ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h")]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rustray_hip.h"))
     for f in files:
         with open(f, "rb") as fh:

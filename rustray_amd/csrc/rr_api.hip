@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <new>
 #include <stdexcept>
 #include <limits>
@@ -54,7 +55,7 @@ static int fail(int code, const char* fmt, ...) noexcept {
 // panic = "abort" (reference Cargo.toml:9-11); a C++ exception that reached one of its frames would be undefined behaviour.
 // Every extern "C" entry point below is a function-try-block that ends in RR_GUARD_END: std::bad_alloc (the std::vectors
 // sized by the caller's scene) becomes RR_ERR_OUT_OF_MEMORY, anything else RR_ERR_DEVICE with what() in rr_last_error().
-// Host worker threads (mesh tree builds, one thread per device in rr_render_multi) run under `Workers`: an exception inside
+// Host worker threads (mesh tree builds, one thread per device in rr_render_multi) run under `Workers` (rr_scene_build.h): an exception inside
 // a worker is carried to the calling thread and rethrown there, a thread that cannot be started is not fatal (the caller
 // does that work itself), and the destructor joins -- no path ends in std::terminate.
 // ---------------------------------------------------------------------------
@@ -65,30 +66,6 @@ static int guard_fail(const char* fn) noexcept {
     catch (...) { return fail(RR_ERR_DEVICE, "%s: unknown exception", fn); }
 }
 #define RR_GUARD_END(fn) catch (...) { return guard_fail(fn); }
-
-struct Workers {
-    std::vector<std::thread> threads;
-    std::atomic_flag taken = ATOMIC_FLAG_INIT;
-    std::exception_ptr first; // written by the one worker that wins `taken`, read after join()
-    Workers() = default;
-    Workers(const Workers&) = delete;
-    Workers& operator=(const Workers&) = delete;
-    ~Workers() { join(); }
-    // runs f() on a new thread; false = no thread could be started (the caller runs f itself)
-    template <class F> bool spawn(F f) {
-        try {
-            threads.emplace_back([this, f]() mutable { run(f); });
-            return true;
-        } catch (...) { return false; }
-    }
-    // f() on the calling thread, under the same net
-    template <class F> void run(F& f) noexcept {
-        try { f(); }
-        catch (...) { if (!taken.test_and_set()) first = std::current_exception(); }
-    }
-    void join() noexcept { for (std::thread& t : threads) if (t.joinable()) t.join(); }
-    void join_and_rethrow() { join(); if (first) std::rethrow_exception(first); }
-};
 
 // Test-only fault injection (tests/test_abi.py, tests/test_gpu_guard.py, tests/test_gpu_scene_edits.py): rr_test_fault("point", kind, skip)
 // arms ONE fault; the (skip + 1)-th crossing of RR_FAULT_POINT("point") on any thread throws std::bad_alloc (kind 1), std::runtime_error (2)
@@ -114,6 +91,7 @@ static void fault_point(const char* name) {
     if (kind == 3) throw 42;
 }
 #define RR_FAULT_POINT(name) fault_point(name)
+#include "rr_scene_build.h" // after `fail` and RR_FAULT_POINT: the scene builder reports and is probed through both
 extern "C" int rr_test_fault(const char* point, int kind, int skip) {
     g_fault_kind.store(0);
     if (!point || kind < 0 || kind > 6 || strlen(point) >= sizeof g_fault_point) return fail(RR_ERR_INVALID_ARGUMENT, "rr_test_fault: bad arguments");
@@ -171,13 +149,18 @@ struct DevBuf {
         if (e == hipSuccess) bytes = n;
         return e;
     }
+    // room for the host's array, never less than min_bytes (an empty array still gives the kernels a pointer), then its bytes; blocking
+    template <class T> hipError_t upload(const std::vector<T>& v, size_t min_bytes) {
+        const hipError_t e = reserve(std::max(v.size() * sizeof(T), min_bytes));
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <class T> T* as() const { return (T*)p; }
 };
 
 enum TimerKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_BINNING }; // what a timed launch ran (resolve_timers)
 struct TimedLaunch { hipEvent_t a, b; TimerKernel kernel; bool level1; }; // level1: the kernel's level-1 build
-struct ItemHost { uint32_t kind; int32_t material, material_cache; bool visible, flip_normals, mesh_has_normals, mesh_degenerate; int32_t mesh; };
 
 struct rr_scene {
     int device = 0;
@@ -211,7 +194,7 @@ struct rr_scene {
     bool broken_geometry = false, broken_materials = false, broken_lights = false, broken_item_flags = false;
     std::vector<DMaterial> h_dmat; // the material records on the device (rr_scene_update_materials puts them back after a failed update)
     std::vector<DLight> h_lights;  // the light records on the device (rr_scene_update_lights puts them back after a failed update)
-    int tlas_depth_limit = RR_TLAS_MAX_DEPTH, blas_depth_limit = RR_BLAS_MAX_DEPTH; // shares of the traversal stack, see rr_scene_create
+    int tlas_depth_limit = RR_TLAS_MAX_DEPTH; // the top level's share of the traversal stack (build_scene_records), for its rebuilds
     // frame state (grown on demand, reused across frames)
     DevBuf hit1;      // hit records of depth level 1 (the primary rays are derived from their index, not stored)
     DevBuf arena[4];  // ray records of the deeper live depth levels, SoA: r0 r1 r2 hit
@@ -390,326 +373,8 @@ extern "C" uint64_t rr_region_pixel_count(uint32_t width, uint32_t height, const
 }
 
 // ---------------------------------------------------------------------------
-// scene validation + upload
+// top level: upload, and the reach it is padded for (the scene's records and trees are built by rr_scene_build.h)
 // ---------------------------------------------------------------------------
-static bool finite16(const float* m) { for (int i = 0; i < 16; i++) if (!std::isfinite(m[i])) return false; return true; }
-
-static int validate_scene(const rr_flat_scene* fs) {
-    if (!fs) return fail(RR_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (fs->abi_version != RR_ABI_VERSION) return fail(RR_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", fs->abi_version, RR_ABI_VERSION);
-    if ((fs->n_items && !fs->items) || (fs->n_meshes && !fs->meshes) || (fs->n_materials && !fs->materials) ||
-        (fs->n_textures && !fs->textures) || (fs->n_lights && !fs->lights))
-        return fail(RR_ERR_INVALID_ARGUMENT, "array pointer is NULL with a non-zero count");
-    if (fs->n_items >= (1u << 27)) return fail(RR_ERR_UNSUPPORTED, "%u items (the shadow-ray record keeps the item index in 27 bits)", fs->n_items);
-    for (uint32_t i = 0; i < fs->n_textures; i++) {
-        const rr_texture& t = fs->textures[i];
-        if ((uint64_t)t.width * t.height > 0 && !t.rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "texture %u has no pixels", i);
-        if (t.width > 32768u || t.height > 32768u) return fail(RR_ERR_UNSUPPORTED, "texture %u is %ux%u", i, t.width, t.height);
-    }
-    for (uint32_t i = 0; i < fs->n_materials; i++)
-        for (int k = 0; k < RR_TEX_COUNT; k++) {
-            int32_t t = fs->materials[i].texture[k];
-            if (t >= (int32_t)fs->n_textures) return fail(RR_ERR_INVALID_ARGUMENT, "material %u texture slot %d = %d out of range", i, k, t);
-        }
-    for (uint32_t i = 0; i < fs->n_meshes; i++) {
-        const rr_mesh& m = fs->meshes[i];
-        if ((m.n_vertices && !m.positions) || (m.n_triangles && !m.indices)) return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: missing positions/indices", i);
-        if ((m.n_uvs && !m.uvs) || (m.n_uv_faces && !m.uv_indices) || (m.n_normals && !m.normals) || (m.n_normal_faces && !m.normal_indices))
-            return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: attribute pointer is NULL with a non-zero count", i);
-        if (m.n_triangles >= (1u << 28)) return fail(RR_ERR_UNSUPPORTED, "mesh %u: %u triangles", i, m.n_triangles);
-        for (size_t k = 0; k < (size_t)m.n_triangles * 3; k++)
-            if (m.indices[k] >= m.n_vertices) return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: vertex index %u out of range", i, m.indices[k]);
-        for (size_t k = 0; k < (size_t)m.n_uv_faces * 3; k++)
-            if (m.uv_indices[k] >= m.n_uvs) return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: uv index %u out of range", i, m.uv_indices[k]);
-        for (size_t k = 0; k < (size_t)m.n_normal_faces * 3; k++)
-            if (m.normal_indices[k] >= m.n_normals) return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: normal index %u out of range", i, m.normal_indices[k]);
-        // Mesh::get_normal indexes normals_indices[face] unchecked (reference src/shape/mesh.rs:216): the reference would panic
-        if (m.n_normals > 0 && m.n_normal_faces > 0 && m.n_normal_faces < m.n_triangles)
-            return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: %u normal faces for %u triangles (the reference panics on this)", i, m.n_normal_faces, m.n_triangles);
-    }
-    for (uint32_t i = 0; i < fs->n_items; i++) {
-        const rr_item& it = fs->items[i];
-        if (it.kind != RR_ITEM_SPHERE && it.kind != RR_ITEM_MESH) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: kind %u", i, it.kind);
-        if (it.material < 0 || it.material >= (int32_t)fs->n_materials || it.material_cache < 0 || it.material_cache >= (int32_t)fs->n_materials)
-            return fail(RR_ERR_INVALID_ARGUMENT, "item %u: material index out of range", i);
-        for (int k = 0; k < RR_TEX_COUNT; k++)
-            if (fs->materials[it.material_cache].texture[k] >= 0)
-                return fail(RR_ERR_INVALID_ARGUMENT, "item %u: material_cache must not carry textures (reference src/shape/mod.rs:769-772)", i);
-        if (it.kind == RR_ITEM_MESH && (it.mesh < 0 || it.mesh >= (int32_t)fs->n_meshes)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: mesh index %d", i, it.mesh);
-        if (!finite16(it.trans) || !finite16(it.trans_inv)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: non-finite transform", i);
-    }
-    for (uint32_t i = 0; i < fs->n_lights; i++)
-        if (fs->lights[i].light_type > RR_LIGHT_SPOT) return fail(RR_ERR_INVALID_ARGUMENT, "light %u: type %u", i, fs->lights[i].light_type);
-    return RR_OK;
-}
-
-// Material (reference src/shape/mod.rs:95-134) -> device record; has_texture = the slot names an image of width > 0
-static DMaterial make_dmaterial(const rr_material& m, const std::vector<uint32_t>& tex_width, const std::vector<DTexture>& dtex) {
-    DMaterial d;
-    memset(&d, 0, sizeof d);
-    for (int k = 0; k < 3; k++) { d.ambient[k] = m.ambient_color[k]; d.base[k] = m.base_color[k]; d.specular[k] = m.specular_color[k]; }
-    d.alpha = m.alpha; d.shininess = m.shininess; d.reflectivity = m.reflectivity; d.refraction_index = m.refraction_index;
-    d.normal_map_strength = m.normal_map_strength; d.shadow_softness = m.shadow_softness; d.roughness = m.roughness;
-    d.cos_shadow_softness = rr_cos(m.shadow_softness * RR_PI_F); d.cos_roughness = rr_cos(m.roughness * RR_PI_F); // jitter()'s z_lo, see DMaterial
-    bool any = false;
-    uint32_t slots = 0u;
-    for (int k = 0; k < RR_TEX_COUNT; k++) {
-        d.tex[k] = m.texture[k];
-        if (m.texture[k] >= 0) { const DTexture& t = dtex[m.texture[k]]; d.texd[k].offset = t.offset; d.texd[k].width = t.width; d.texd[k].height = t.height; }
-        if (m.texture[k] >= 0 && tex_width[m.texture[k]] > 0) { any = true; slots |= RR_MF_TEX_SLOT0 << k; }
-    }
-    d.flags = slots | (m.texture_filtering_nearest ? RR_MF_NEAREST : 0u) | (m.receive_shadow ? RR_MF_RECEIVE_SHADOW : 0u) |
-              (m.monte_carlo ? RR_MF_MONTE_CARLO : 0u) | (any ? RR_MF_ANY_TEX : 0u);
-    return d;
-}
-
-// The flag word of an item: what Raytracing::trace reads of the texture-less material cache (src/raytracing.rs:450-458),
-// intersect_b_box's `solid` (src/shape/mesh.rs:51-59) and the occluder-alpha-map test of the shadow code (:899-912).
-static uint32_t item_flags(const ItemHost& it, const rr_material& cache, const rr_material& full, const std::vector<uint32_t>& tex_width) {
-    uint32_t f = 0;
-    if (it.visible) f |= RR_IF_VISIBLE;
-    if (it.flip_normals) f |= RR_IF_FLIP_NORMALS;
-    if (cache.alpha > 0.0f) f |= RR_IF_CACHE_ALPHA_POS;
-    if (cache.cast_shadow) f |= RR_IF_CACHE_CAST_SHADOW;
-    if (cache.reflection_only) f |= RR_IF_CACHE_REFL_ONLY;
-    if (!(cache.alpha < 1.0f) && cache.backface_cullig) f |= RR_IF_SOLID_BASE; // the cache never has textures
-    if (full.texture[RR_TEX_ALPHA] >= 0 && tex_width[full.texture[RR_TEX_ALPHA]] > 0) f |= RR_IF_OCCLUDER_ALPHA_TEX;
-    if (it.kind == RR_ITEM_SPHERE) f |= RR_IF_SPHERE | RR_IF_UV_MAY_BE_NAN;
-    else {
-        if (cache.smooth_shading && it.mesh_has_normals) f |= RR_IF_SMOOTH;
-        if (it.mesh_degenerate) f |= RR_IF_UV_MAY_BE_NAN;
-    }
-    return f;
-}
-
-// Light (reference src/scene.rs:40-51) -> device record.  Disabled lights keep their slot: the slot is the RNG stream of their shadow jitter.
-static DLight make_dlight(const rr_light& l) {
-    DLight d;
-    memset(&d, 0, sizeof d);
-    for (int k = 0; k < 3; k++) { d.pos[k] = l.pos[k]; d.dir[k] = l.dir[k]; d.color[k] = l.color[k]; }
-    d.intensity = l.intensity; d.max_angle = l.max_angle;
-    d.type = l.light_type | (l.enabled ? 0u : 0x80u);
-    return d;
-}
-
-static void fill_item_matrices(DItem& d, const float* trans, const float* inv) {
-    // rows of the column-major matrices
-    d.inv0 = make_float4(inv[0], inv[4], inv[8], inv[12]);
-    d.inv1 = make_float4(inv[1], inv[5], inv[9], inv[13]);
-    d.inv2 = make_float4(inv[2], inv[6], inv[10], inv[14]);
-    d.inv3 = make_float4(inv[3], inv[7], inv[11], inv[15]);
-    d.tr0 = make_float4(trans[0], trans[4], trans[8], trans[12]);
-    d.tr1 = make_float4(trans[1], trans[5], trans[9], trans[13]);
-    d.tr2 = make_float4(trans[2], trans[6], trans[10], trans[14]);
-}
-
-// ---------------------------------------------------------------------------
-// top level: world boxes over the items
-// ---------------------------------------------------------------------------
-// The reference has no world-space test: a ray is moved into an item's space with the item's f32 inverse matrix and
-// tested there against the local box (Shape::intersect_b_box, src/shape/mod.rs:80-105).  The top-level tree may only
-// skip an item if that local test would fail, so an item's world box is the exact box of its transformed local corners
-// (Bounded::aabb, src/shape/mod.rs:48-78; in double) grown by a bound on how far the f32 local ray can sit from the
-// true one, mapped back to world space.  With M, N the given matrix and inverse, t, t' their translations, u = 2^-24,
-// and origins with |o_c| <= reach_c:  the local ray is  N o + t' + do,  N d + dd  with  |do| <= g (|N| |o| + |t'|),
-// |dd| <= g |N| |d|  (g = 16 u covers the four-term dot products and the local slab test's own rounding), so a point of
-// it maps to the world point  (o + s d) + [E o + e + M do] + s [E d + M dd],  E = M N - I,  e = M t' + t  (N is an f32
-// inverse: E is of the order u cond(M)).  s |d| is at most reach + the box's own extent, which bounds the last term.
-// Far from the origin, or with a badly conditioned transform, this is orders of magnitude more than float spacing
-// (tools/fuzz_parity.py far: a sheared sphere 1e5 away needs 15 units on a 10-unit box); on ordinary scenes it is
-// ~1e-6 of the scene size.  An inverse with a projective bottom row gets an unbounded box (always a candidate).
-//
-// Tighter than the corners, for meshes: a mesh only ever contributes through a triangle its own tree lets the ray reach (a candidate
-// whose box is hit and whose triangles are missed changes nothing: src/raytracing.rs:471-487 looks at `intersect`'s result only),
-// and the walks of rr_kernels.hip test a triangle only under a leaf box that the local ray passes -- boxes of the mesh's own
-// vertices, padded by 4e-6 of their coordinates (rr_bvh.cpp).  So whatever the triangle test then reports, NaN included, it
-// reports for a ray that passes the padded box of the mesh's VERTICES; in world space that is the box of the transformed
-// vertices, which for a rotated item is much smaller than the box of the rotated local box (a unit cube turned by 45 degrees
-// about two axes: 1.7 x per axis).  The world box is the intersection of the two, grown by the leaf padding mapped to world
-// space; the padding of padded_world_box (how far the f32 local ray sits from the true one) applies as before.
-// NOT for balls: ray_ball has no box in front of it, and where its arithmetic overflows (a tiny ball: local coordinates
-// ~1e12) it answers Some(NaN) for ANY ray that passes the local box -- tests/golden/fuzz_568 holds such a scene -- so a ball
-// keeps the box of its local box's corners.  Not for a mesh whose tree is a single leaf either (nothing is culled in front of
-// its triangles).  The extent of the vertices along the transform's rows comes from the device (k_item_spans), where the triangles live.
-struct WorldBox { double lo[3], hi[3]; bool tight[3]; double ext[3]; }; // tight[r]: axis r comes from the vertices; ext: largest |local coordinate| per local axis
-// `span`: the 9 doubles k_item_spans wrote for this item (extent of the mesh's vertices along the transform's rows), or NULL = corners only
-static WorldBox exact_world_box(const DItem& it, const double* span) {
-    WorldBox b;
-    const float4 rows[3] = {it.tr0, it.tr1, it.tr2};
-    for (int r = 0; r < 3; r++) { b.lo[r] = 1e300; b.hi[r] = -1e300; b.tight[r] = false; b.ext[r] = 0.0; }
-    for (int c = 0; c < 8; c++) {
-        const double p[3] = {(c & 1) ? it.bmax[0] : it.bmin[0], (c & 2) ? it.bmax[1] : it.bmin[1], (c & 4) ? it.bmax[2] : it.bmin[2]};
-        for (int r = 0; r < 3; r++) {
-            const double v = (double)rows[r].x * p[0] + (double)rows[r].y * p[1] + (double)rows[r].z * p[2] + (double)rows[r].w;
-            b.lo[r] = std::min(b.lo[r], v); b.hi[r] = std::max(b.hi[r], v);
-        }
-    }
-    if (!(it.flags & RR_IF_SPHERE) && it.root4 >= 0 && span) {
-        bool finite = true;
-        for (int k = 0; k < 9; k++) finite = finite && std::isfinite(span[k]);
-        if (finite) {
-            for (int c = 0; c < 3; c++) b.ext[c] = span[6 + c]; // what the leaf padding is relative to
-            for (int r = 0; r < 3; r++) {
-                const double mx = rows[r].x, my = rows[r].y, mz = rows[r].z;
-                const double leaf_pad = 2.0e-5 * (std::fabs(mx) * b.ext[0] + std::fabs(my) * b.ext[1] + std::fabs(mz) * b.ext[2]) + 1e-30;
-                const double tlo = span[r] + (double)rows[r].w - leaf_pad, thi = span[3 + r] + (double)rows[r].w + leaf_pad;
-                if (std::isfinite(tlo) && std::isfinite(thi) && tlo <= thi && (tlo > b.lo[r] || thi < b.hi[r])) { b.lo[r] = std::max(b.lo[r], tlo); b.hi[r] = std::min(b.hi[r], thi); b.tight[r] = true; }
-            }
-        }
-    }
-    return b;
-}
-static void padded_world_box(const DItem& it, const WorldBox& b, const double reach[3], float* lo, float* hi) {
-    const double M[3][4] = {{it.tr0.x, it.tr0.y, it.tr0.z, it.tr0.w}, {it.tr1.x, it.tr1.y, it.tr1.z, it.tr1.w}, {it.tr2.x, it.tr2.y, it.tr2.z, it.tr2.w}};
-    const double N[3][4] = {{it.inv0.x, it.inv0.y, it.inv0.z, it.inv0.w}, {it.inv1.x, it.inv1.y, it.inv1.z, it.inv1.w}, {it.inv2.x, it.inv2.y, it.inv2.z, it.inv2.w}};
-    const bool affine = it.inv3.x == 0.0f && it.inv3.y == 0.0f && it.inv3.z == 0.0f && it.inv3.w == 1.0f;
-    const double g = 16.0 / 16777216.0;
-    for (int r = 0; r < 3; r++) {
-        double pad = 0.0;
-        for (int c = 0; c < 3; c++) {
-            double e = (r == c) ? -1.0 : 0.0, a = 0.0;
-            for (int k = 0; k < 3; k++) { e += M[r][k] * N[k][c]; a += std::fabs(M[r][k]) * std::fabs(N[k][c]); }
-            const double extent = std::max(std::fabs(b.lo[c]), std::fabs(b.hi[c]));
-            pad += (std::fabs(e) + g * a) * (2.0 * reach[c] + extent);
-        }
-        double et = M[r][3], at = 0.0;
-        for (int k = 0; k < 3; k++) { et += M[r][k] * N[k][3]; at += std::fabs(M[r][k]) * std::fabs(N[k][3]); }
-        pad += std::fabs(et) + g * at;
-        if (b.tight[r]) {
-            // a leaf's slab test lets a ray through whose entry and exit distances differ by up to 8e-6 of themselves (RR_CHILD): planes moved
-            // by that share of the way travelled along a local axis, which is at most the local reach plus the mesh's own extent
-            for (int c = 0; c < 3; c++) {
-                double way = std::fabs(N[c][3]) + b.ext[c];
-                for (int k = 0; k < 3; k++) way += std::fabs(N[c][k]) * 2.0 * reach[k];
-                pad += std::fabs(M[r][c]) * 1.0e-5 * way;
-            }
-        }
-        pad = 2.0 * pad + 1e-6 * std::max(std::fabs(b.lo[r]), std::fabs(b.hi[r])) + 1e-30; // + float rounding of the box and of the walk's plane distances
-        lo[r] = (float)(b.lo[r] - pad); hi[r] = (float)(b.hi[r] + pad);
-        if (!affine || !std::isfinite(lo[r]) || lo[r] < -3.0e38f) lo[r] = -3.0e38f;
-        if (!affine || !std::isfinite(hi[r]) || hi[r] > 3.0e38f) hi[r] = 3.0e38f;
-    }
-}
-
-// Builds the top-level tree over s->h_items for ray origins within +-reach (grown to cover the items themselves: the
-// origins of secondary and shadow rays lie on them).  Writes nothing of the scene: the reach it was built for, the
-// RR_VIEW_NAN_BALLS hint and the item boxes travel in TlasTrees, and upload_tlas keeps them once the device has the trees.
-struct TlasTrees {
-    std::vector<DNode4> corner, surface; int32_t root = (int32_t)0x80000000, root_surface = (int32_t)0x80000000; bool has_surface = false;
-    double reach[3] = {0.0, 0.0, 0.0}; bool nan_balls = false; std::vector<float4> item_boxes;
-};
-static int tlas_tree(const rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4);
-static int build_tlas(const rr_scene* s, const double want_reach[3], TlasTrees* trees) {
-    uint32_t n = (uint32_t)s->h_items.size();
-    *trees = TlasTrees();
-    double* reach_c = trees->reach;
-    for (int c = 0; c < 3; c++) reach_c[c] = want_reach[c];
-    if (n == 0) return RR_OK; // empty scene: every walk ends at once (both roots RR_SENTINEL)
-    // two boxes per item: the box of its local box's corners -- what the tree is built over and what shadow packets are tested against:
-    // the shadow query orders items by the distance at which the LOCAL box is entered, and prunes by it, which only a world box that
-    // contains the local box bounds from below -- and the box of its surface (exact_world_box), which the closest-hit packets use:
-    // there an item matters through its nearest hit alone, and that lies in the tighter box
-    std::vector<WorldBox> exact(n), surf(n);
-    for (uint32_t i = 0; i < n; i++) {
-        exact[i] = exact_world_box(s->h_items[i], nullptr);
-        surf[i] = exact_world_box(s->h_items[i], s->h_spans.size() == 9 * (size_t)n ? &s->h_spans[9 * (size_t)i] : nullptr);
-        for (int c = 0; c < 3; c++) {
-            const double m = std::max(std::fabs(exact[i].lo[c]), std::fabs(exact[i].hi[c])) * 1.001 + 0.01; // + the shadow bias along the normal
-            if (std::isfinite(m)) reach_c[c] = std::max(reach_c[c], m);
-        }
-    }
-    // Can some ball's ray_toi_with_ball overflow (b * b, a * c beyond f32: delta = NaN and the ball answers Some(NaN))?  Judged with six
-    // orders of magnitude to spare on the ray directions; a hint for trace_shadow_blockers only (the closest-hit walks detect the NaN itself).
-    for (uint32_t i = 0; i < n; i++) {
-        const DItem& it = s->h_items[i];
-        if (!(it.flags & RR_IF_SPHERE)) continue;
-        const float4 rows[3] = {it.inv0, it.inv1, it.inv2};
-        double nmax = 0.0, tmax = 0.0;
-        for (int r = 0; r < 3; r++) {
-            nmax = std::max(nmax, std::fabs((double)rows[r].x) + std::fabs((double)rows[r].y) + std::fabs((double)rows[r].z));
-            tmax = std::max(tmax, std::fabs((double)rows[r].w));
-        }
-        const double reach = std::max(reach_c[0], std::max(reach_c[1], reach_c[2]));
-        const double on = nmax * reach + tmax, dn = nmax * 1e6, rad = std::fabs((double)it.radius);
-        const bool affine = it.inv3.x == 0.0f && it.inv3.y == 0.0f && it.inv3.z == 0.0f && it.inv3.w == 1.0f;
-        if (!affine || !(on * dn < 1e18) || !(rad * dn < 1e18) || !(on < 1e18) || !(rad < 1e18)) trees->nan_balls = true;
-    }
-    std::vector<float> lo(3 * (size_t)n), hi(3 * (size_t)n);
-    std::vector<float4>& boxes = trees->item_boxes;
-    boxes.resize(4 * (size_t)n); // [0, 2n): corner boxes (lo, hi); [2n, 4n): surface boxes
-    for (uint32_t i = 0; i < n; i++) {
-        padded_world_box(s->h_items[i], exact[i], reach_c, &lo[3 * (size_t)i], &hi[3 * (size_t)i]);
-        boxes[2 * (size_t)i] = make_float4(lo[3 * (size_t)i], lo[3 * (size_t)i + 1], lo[3 * (size_t)i + 2], 0.0f);
-        boxes[2 * (size_t)i + 1] = make_float4(hi[3 * (size_t)i], hi[3 * (size_t)i + 1], hi[3 * (size_t)i + 2], 0.0f);
-        float tl[3], th[3];
-        padded_world_box(s->h_items[i], surf[i], reach_c, tl, th);
-        boxes[2 * ((size_t)n + i)] = make_float4(tl[0], tl[1], tl[2], 0.0f);
-        boxes[2 * ((size_t)n + i) + 1] = make_float4(th[0], th[1], th[2], 0.0f);
-    }
-    int rc = tlas_tree(s, lo.data(), hi.data(), n, &trees->corner, &trees->root);
-    if (rc != RR_OK) return rc;
-    // The per-ray closest-hit walks get a tree of their own over the SURFACE boxes (the argument above holds for any closest-hit query: an
-    // item matters through its nearest hit alone; until round 4 only the packet form used them): fewer items are set up per ray and fewer
-    // mesh walks entered.  Shadow queries keep the tree over the corner boxes (their order is the local boxes' entry distance).
-    bool differs = false;
-    for (size_t k = 0; k < 2 * (size_t)n && !differs; k++)
-        differs = memcmp(&boxes[k], &boxes[2 * (size_t)n + k], sizeof(float4)) != 0;
-    trees->has_surface = differs;
-    if (differs) {
-        for (uint32_t i = 0; i < n; i++) {
-            const float4 tl = boxes[2 * ((size_t)n + i)], th = boxes[2 * ((size_t)n + i) + 1];
-            lo[3 * (size_t)i] = tl.x; lo[3 * (size_t)i + 1] = tl.y; lo[3 * (size_t)i + 2] = tl.z;
-            hi[3 * (size_t)i] = th.x; hi[3 * (size_t)i + 1] = th.y; hi[3 * (size_t)i + 2] = th.z;
-        }
-        rc = tlas_tree(s, lo.data(), hi.data(), n, &trees->surface, &trees->root_surface);
-        if (rc != RR_OK) return rc;
-    }
-    return RR_OK;
-}
-
-// One top-level tree over the items' boxes lo / hi (n * 3 floats): binned SAH, one item per leaf, collapsed to 4-wide nodes.
-static int tlas_tree(const rr_scene* s, const float* lo, const float* hi, uint32_t n, std::vector<DNode4>* tlas4, int32_t* root4) {
-    tlas4->clear();
-    rr::BvhResult r;
-    if (!rr::build_bvh(lo, hi, n, 1, s->tlas_depth_limit, &r))
-        return fail(RR_ERR_UNSUPPORTED, "internal: top level over %u items does not fit %d levels", n, s->tlas_depth_limit);
-    // leaves must name item indices directly: leaf order is a permutation, so re-code each 1-item leaf
-    for (DNode& nd : r.nodes) {
-        int32_t c[2];
-        memcpy(&c[0], &nd.n3.x, 4); memcpy(&c[1], &nd.n3.y, 4);
-        for (int k = 0; k < 2; k++)
-            if (c[k] < 0) { uint32_t first = RR_LEAF_FIRST(~c[k]); c[k] = ~(int32_t)r.order[first]; }
-        memcpy(&nd.n3.x, &c[0], 4); memcpy(&nd.n3.y, &c[1], 4);
-    }
-    if (r.root < 0) r.root = ~(int32_t)r.order[RR_LEAF_FIRST(~r.root)];
-    // the form the kernels walk: collapsed to 4-wide nodes within the top level's share of the traversal stack
-    int pending = 0;
-    *root4 = rr::collapse_bvh4(r, s->tlas_depth_limit, false, tlas4, &pending);
-    if (pending > s->tlas_depth_limit) return fail(RR_ERR_UNSUPPORTED, "top level: BVH4 stack bound exceeded");
-    // Balls before meshes among the children of a node.  A walk takes the children of a node nearest box first and, at equal entry
-    // distance, in slot order -- and equal is the rule where it matters: a ray that starts inside an environment sphere AND inside an
-    // object's box (every secondary ray of such a scene) enters both at distance 0.  A ball is decided by a dozen instructions and
-    // its toi then bounds the mesh walk that follows (closest_item passes the best hit so far down); the other way round the mesh is
-    // walked without a bound first.  helmet_syn's secondary rays all end on its solid environment sphere at toi 0: with the sphere
-    // in front, the walk of the 80 k-triangle mesh ends at its root.  The candidate SET and the result do not depend on the order.
-    for (DNode4& nd : *tlas4) {
-        int32_t code[4];
-        memcpy(code, &nd.q[6], 16);
-        auto is_ball = [&](int k) { return code[k] < 0 && code[k] != (int32_t)0x80000000 && (s->h_items[RR_LEAF_FIRST((uint32_t)~code[k])].flags & RR_IF_SPHERE) != 0u; };
-        int order[4], m = 0;
-        for (int k = 0; k < 4; k++) if (is_ball(k)) order[m++] = k;
-        if (m == 0) continue;
-        for (int k = 0; k < 4; k++) if (!is_ball(k) && code[k] != (int32_t)0x80000000) order[m++] = k;
-        for (int k = 0; k < 4; k++) if (code[k] == (int32_t)0x80000000) order[m++] = k;
-        DNode4 src = nd;
-        for (int r = 0; r < 7; r++) {
-            const float v[4] = {src.q[r].x, src.q[r].y, src.q[r].z, src.q[r].w};
-            nd.q[r] = make_float4(v[order[0]], v[order[1]], v[order[2]], v[order[3]]);
-        }
-    }
-    return RR_OK;
-}
-
 // The two trees into the scene's node buffer (the corner tree in its first half, the surface tree in the second: tlas_node_capacity
 // nodes each) and the item boxes; then, and only then, the scene keeps what they were built for: the reach, the NaN-ball hint, the host
 // copy of the boxes and the roots in the view.  A failed copy leaves all of that as it was and marks the device trees stale.
@@ -744,8 +409,7 @@ static int ensure_tlas_reach(rr_scene* s, const double need[3]) {
     double want[3];
     for (int c = 0; c < 3; c++) want[c] = 2.0 * need[c]; // build_tlas raises it to the items' own extent
     TlasTrees trees;
-    int rc = build_tlas(s, want, &trees);
-    if (rc != RR_OK) return rc;
+    RR_TRY(build_tlas(s->h_items, s->h_spans, s->tlas_depth_limit, want, &trees));
     RR_FAULT_POINT("tlas_reach.upload");
     HIP_TRY(hipDeviceSynchronize());
     return upload_tlas(s, trees);
@@ -808,59 +472,6 @@ static int derive_from_transforms(rr_scene* s) {
     return RR_OK;
 }
 
-// Per-triangle constants of the shading (DTri::v1.w, v3), with the IEEE binary32 sequence of rr_math.h's cross3 / dot3 / norm3 /
-// normalize3 as k_shade evaluated them per hit (this file is built without contraction and without fast-math on the host side too;
-// sqrtf and the division are correctly rounded on both; tests/test_gpu_math.py compares the two builds bit for bit):
-//   area = norm3(cross3(a - b, a - c))            Mesh::get_normal / get_uv, src/shape/mesh.rs:127-143 (area_weights)
-//   ng   = normalize3(cross3(b - a, c - a))       the triangle's own normal, src/shape/mesh.rs:76-98
-static void tri_shading_constants(const float* a, const float* b, const float* c, float* ng, float* area) {
-    auto cross = [](const float* u, const float* v, float* r) {
-        r[0] = u[1] * v[2] - u[2] * v[1]; r[1] = u[2] * v[0] - u[0] * v[2]; r[2] = u[0] * v[1] - u[1] * v[0];
-    };
-    auto norm = [](const float* u) { return sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]); };
-    const float amb[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]}, amc[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
-    float x[3];
-    cross(amb, amc, x);
-    *area = norm(x);
-    const float bma[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, cma[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    cross(bma, cma, x);
-    const float n = norm(x);
-    ng[0] = x[0] / n; ng[1] = x[1] / n; ng[2] = x[2] / n;
-}
-
-// The binary trees of the meshes are independent: built by a few host threads (a scene of 194 meshes / 559 k triangles:
-// 0.4 s on one core).  The workers pull mesh indices from one counter, so threads that could not be started only mean
-// fewer hands; an exception in any worker (the builder's vectors are sized by the caller's meshes) is rethrown here.
-static void build_mesh_trees(const rr_flat_scene* fs, int depth_limit, std::vector<rr::BvhResult>* built, std::vector<char>* built_ok) {
-    std::atomic<uint32_t> next_mesh{0};
-    auto worker = [&]() {
-        for (;;) {
-            const uint32_t mi = next_mesh.fetch_add(1);
-            if (mi >= fs->n_meshes) break;
-            RR_FAULT_POINT("scene_create.mesh_worker");
-            const rr_mesh& m = fs->meshes[mi];
-            const uint32_t nt = m.n_triangles;
-            std::vector<float> lo(3 * (size_t)nt), hi(3 * (size_t)nt);
-            for (uint32_t f = 0; f < nt; f++)
-                for (int k = 0; k < 3; k++) {
-                    float a = m.positions[3 * (size_t)m.indices[3 * (size_t)f] + k];
-                    float b = m.positions[3 * (size_t)m.indices[3 * (size_t)f + 1] + k];
-                    float c = m.positions[3 * (size_t)m.indices[3 * (size_t)f + 2] + k];
-                    lo[3 * (size_t)f + k] = std::min(a, std::min(b, c));
-                    hi[3 * (size_t)f + k] = std::max(a, std::max(b, c));
-                }
-            (*built_ok)[mi] = rr::build_bvh(lo.data(), hi.data(), nt, RR_MAX_LEAF_TRIS, depth_limit, &(*built)[mi]) ? 1 : 0;
-        }
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint32_t n_threads = std::min<uint32_t>(std::min<uint32_t>(hw ? hw : 4u, 16u), std::max<uint32_t>(fs->n_meshes, 1u));
-    Workers pool;
-    for (uint32_t t = 1; t < n_threads; t++)
-        if (!pool.spawn(worker)) break;
-    pool.run(worker);
-    pool.join_and_rethrow();
-}
-
 // Test-only (tests/test_abi.py; not in the header): the host half of rr_scene_create -- validation and the threaded mesh tree
 // builds -- without a device, so that the no-throw guard and the worker net can be exercised on a CPU-only box.
 extern "C" int rr_test_host_build(const rr_flat_scene* fs, uint64_t* n_nodes_out) try {
@@ -879,11 +490,19 @@ extern "C" int rr_test_host_build(const rr_flat_scene* fs, uint64_t* n_nodes_out
     return RR_OK;
 } RR_GUARD_END("rr_test_host_build")
 
+// the images' texels into the RGBA8 pool, at the offsets their descriptors name (append_texture_layout)
+static int upload_images(uint32_t* pool, const rr_texture* textures, uint32_t n, const DTexture* dtex) {
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t texels = (uint64_t)dtex[i].width * dtex[i].height;
+        if (texels) HIP_TRY(hipMemcpy(pool + dtex[i].offset, textures[i].rgba8, texels * 4, hipMemcpyHostToDevice));
+    }
+    return RR_OK;
+}
+
 extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** out) try {
     if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    int rc = validate_scene(fs);
-    if (rc != RR_OK) return rc;
+    RR_TRY(validate_scene(fs));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RR_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(RR_ERR_INVALID_ARGUMENT, "device %d of %d", device, ndev);
@@ -900,188 +519,28 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     for (int i = 0; i < 256; i++) lut[i] = (float)i / 255.0f;
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_u8_to_f32), lut, sizeof lut));
 
-    // ---- textures: one RGBA8 pool
-    std::vector<DTexture> dtex(fs->n_textures);
-    uint64_t n_texels = 0;
-    for (uint32_t i = 0; i < fs->n_textures; i++) {
-        dtex[i].offset = n_texels; dtex[i].width = fs->textures[i].width; dtex[i].height = fs->textures[i].height;
-        n_texels += (uint64_t)fs->textures[i].width * fs->textures[i].height;
-    }
-    HIP_TRY(s->texels.reserve(std::max<uint64_t>(n_texels, 1) * 4));
-    for (uint32_t i = 0; i < fs->n_textures; i++) {
-        uint64_t n = (uint64_t)dtex[i].width * dtex[i].height;
-        if (n) HIP_TRY(hipMemcpy(s->texels.as<uint32_t>() + dtex[i].offset, fs->textures[i].rgba8, n * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(s->textures.reserve(std::max<size_t>(dtex.size(), 1) * sizeof(DTexture)));
-    if (!dtex.empty()) HIP_TRY(hipMemcpy(s->textures.p, dtex.data(), dtex.size() * sizeof(DTexture), hipMemcpyHostToDevice));
-
-    // ---- materials
-    s->tex_width.resize(fs->n_textures);
-    for (uint32_t i = 0; i < fs->n_textures; i++) s->tex_width[i] = fs->textures[i].width;
-    std::vector<DMaterial> dmat(fs->n_materials);
-    s->h_textures = dtex;
-    for (uint32_t i = 0; i < fs->n_materials; i++) dmat[i] = make_dmaterial(fs->materials[i], s->tex_width, s->h_textures);
-    HIP_TRY(s->materials.reserve(std::max<size_t>(dmat.size(), 1) * sizeof(DMaterial)));
-    if (!dmat.empty()) HIP_TRY(hipMemcpy(s->materials.p, dmat.data(), dmat.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    s->h_dmat.swap(dmat);
-
-    // ---- lights (disabled lights keep their slot: the slot is the RNG stream of their shadow jitter)
-    std::vector<DLight> dl(fs->n_lights);
-    s->n_enabled_lights = 0;
-    for (uint32_t i = 0; i < fs->n_lights; i++) {
-        dl[i] = make_dlight(fs->lights[i]);
-        if (fs->lights[i].enabled) s->n_enabled_lights++;
-    }
-    HIP_TRY(s->lights.reserve(std::max<size_t>(dl.size(), 1) * sizeof(DLight)));
-    if (!dl.empty()) HIP_TRY(hipMemcpy(s->lights.p, dl.data(), dl.size() * sizeof(DLight), hipMemcpyHostToDevice));
-    s->h_lights.swap(dl);
-
-    // ---- shares of the traversal stack (RR_STACK_DEPTH entries per lane): a top level over n items never needs more
-    // than n - 1 pending entries, so a scene of few items leaves more levels to its per-mesh trees (a 320 k-triangle
-    // mesh traces 3 % faster with 30 levels than with 24, and 7 % slower with 20)
-    s->tlas_depth_limit = (int)std::min<uint32_t>(RR_TLAS_MAX_DEPTH, std::max<uint32_t>(1u, fs->n_items > 1 ? fs->n_items - 1 : 1u));
-    // More than 2^RR_TLAS_MAX_DEPTH items (the reference has no limit: `items: Vec<..>`, src/scene.rs:69-83): the top level takes the
-    // levels it needs -- ceil(log2 n): the builder falls back to object-median splits where the budget gets tight -- out of the
-    // per-mesh trees' share, down to 16 levels for those (8 * 2^16 triangles per mesh at worst); RR_MAX_ITEMS = 2^20 is where that ends.
-    if (fs->n_items > (1u << RR_TLAS_MAX_DEPTH)) {
-        if (fs->n_items > RR_MAX_ITEMS) return fail(RR_ERR_UNSUPPORTED, "%u items (RR_MAX_ITEMS = %u)", fs->n_items, RR_MAX_ITEMS);
-        int need = RR_TLAS_MAX_DEPTH;
-        while ((1u << need) < fs->n_items) need++;
-        s->tlas_depth_limit = need;
-    }
-    s->blas_depth_limit = RR_STACK_DEPTH - 3 - s->tlas_depth_limit;
-    // ---- meshes: one BLAS per mesh, shared by every item that names it
-    struct MeshDev { uint32_t tri_base, n_tris; uint32_t node_base4; int32_t root4; bool has_normals, degenerate; };
-    std::vector<MeshDev> md(fs->n_meshes);
-    std::vector<DNode4> all_nodes4;
-    std::vector<DTri> all_tris;
-    std::vector<DTriX> all_trix;
-    std::vector<DTriAttr> all_attrs;
-    std::vector<uint32_t> all_face_slot;
-    // the binary trees of the meshes are independent: built by a few host threads (a scene of 194 meshes / 559 k triangles:
-    // 0.4 s on one core), then collapsed and laid out one after the other
-    std::vector<rr::BvhResult> built(fs->n_meshes);
-    std::vector<char> built_ok(fs->n_meshes, 0);
-    build_mesh_trees(fs, s->blas_depth_limit, &built, &built_ok);
-    for (uint32_t mi = 0; mi < fs->n_meshes; mi++) {
-        const rr_mesh& m = fs->meshes[mi];
-        uint32_t nt = m.n_triangles;
-        if (!built_ok[mi]) return fail(RR_ERR_UNSUPPORTED, "mesh %u: %u triangles need a deeper tree than the %d levels left beside a top level over %u items",
-                                       mi, nt, s->blas_depth_limit, fs->n_items);
-        rr::BvhResult& r = built[mi];
-        md[mi].tri_base = (uint32_t)all_tris.size();
-        md[mi].n_tris = nt;
-        md[mi].has_normals = m.n_normals > 0 && m.n_normal_faces > 0;
-        md[mi].degenerate = false;
-        {
-            int pending = 0;
-            md[mi].node_base4 = (uint32_t)all_nodes4.size();
-            md[mi].root4 = rr::collapse_bvh4(r, s->blas_depth_limit, true, &all_nodes4, &pending);
-            if (pending > s->blas_depth_limit) return fail(RR_ERR_UNSUPPORTED, "mesh %u: BVH4 stack bound exceeded", mi);
-        }
-        size_t fs_base = all_face_slot.size();
-        all_face_slot.resize(fs_base + nt);
-        for (uint32_t slot = 0; slot < nt; slot++) {
-            uint32_t f = r.order[slot];
-            all_face_slot[fs_base + f] = slot;
-            s->h_slot_face.push_back(f);
-            const uint32_t* ix = m.indices + 3 * (size_t)f;
-            const float *a = m.positions + 3 * (size_t)ix[0], *b = m.positions + 3 * (size_t)ix[1], *c = m.positions + 3 * (size_t)ix[2];
-            {   // Mesh::get_uv divides by the triangle's area (src/shape/mesh.rs:127-143): a zero (or non-finite) area makes the uv of ANY point
-                // on that face non-finite.  Judged in double with a generous margin: a false positive only costs shadow rays that a
-                // zero light term would have skipped (k_shade, want_shadow)
-                const double u[3] = {(double)a[0] - b[0], (double)a[1] - b[1], (double)a[2] - b[2]}, v[3] = {(double)a[0] - c[0], (double)a[1] - c[1], (double)a[2] - c[2]};
-                const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
-                const double area2 = cx * cx + cy * cy + cz * cz, scale2 = (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-                if (!(area2 > 1e-10 * scale2) || !(area2 > 1e-24) || !std::isfinite(area2)) md[mi].degenerate = true;
-            }
-            DTri t;
-            float fbits; memcpy(&fbits, &f, 4);
-            float ng[3], area;
-            tri_shading_constants(a, b, c, ng, &area);
-            t.v0 = make_float4(a[0], a[1], a[2], fbits);
-            t.v1 = make_float4(b[0], b[1], b[2], area);
-            t.v2 = make_float4(c[0], c[1], c[2], 0.0f);
-            t.v3 = make_float4(ng[0], ng[1], ng[2], 0.0f);
-            all_tris.push_back(t);
-            {   // the edge vectors parry's test evaluates per ray: ab = b - a, ac = c - a
-                const float ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-                DTriX x;
-                x.t0 = t.v0;
-                x.t1 = make_float4(ab[0], ab[1], ab[2], ac[0]);
-                x.t2 = make_float4(ac[1], ac[2], 0.0f, 0.0f);
-                all_trix.push_back(x);
-            }
-            DTriAttr at;
-            float n[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, uv[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-            if (md[mi].has_normals)
-                for (int v = 0; v < 3; v++)
-                    for (int k = 0; k < 3; k++) n[v][k] = m.normals[3 * (size_t)m.normal_indices[3 * (size_t)f + v] + k];
-            uint32_t flags = 0;
-            if (f < m.n_uv_faces) { // Mesh::get_uv bounds test, reference src/shape/mesh.rs:116
-                flags |= 1u;
-                for (int v = 0; v < 3; v++)
-                    for (int k = 0; k < 2; k++) uv[v][k] = m.uvs[2 * (size_t)m.uv_indices[3 * (size_t)f + v] + k];
-            }
-            float flb; memcpy(&flb, &flags, 4);
-            at.s0 = make_float4(n[0][0], n[0][1], n[0][2], uv[0][0]);
-            at.s1 = make_float4(n[1][0], n[1][1], n[1][2], uv[0][1]);
-            at.s2 = make_float4(n[2][0], n[2][1], n[2][2], uv[1][0]);
-            at.s3 = make_float4(uv[1][1], uv[2][0], uv[2][1], flb);
-            all_attrs.push_back(at);
-        }
-    }
-
-    // ---- items
-    s->h_items.resize(fs->n_items);
-    s->item_host.resize(fs->n_items);
+    // ---- the records, built on the host (rr_scene_build.h), then uploaded; an empty array still gets a buffer
+    SceneRecords r;
+    RR_TRY(build_scene_records(fs, &r));
+    HIP_TRY(s->texels.reserve(std::max<uint64_t>(pool_texels(r.dtex), 1) * 4));
+    RR_TRY(upload_images(s->texels.as<uint32_t>(), fs->textures, fs->n_textures, r.dtex.data()));
+    HIP_TRY(s->textures.upload(r.dtex, sizeof(DTexture)));
+    HIP_TRY(s->materials.upload(r.dmat, sizeof(DMaterial)));
+    HIP_TRY(s->lights.upload(r.dlights, sizeof(DLight)));
+    HIP_TRY(s->nodes4.upload(r.nodes4, 16));
+    HIP_TRY(s->tris.upload(r.tris, 16));
+    HIP_TRY(s->trix.upload(r.trix, 16));
+    HIP_TRY(s->attrs.upload(r.attrs, 16));
+    HIP_TRY(s->face_slot.upload(r.face_slot, 16));
+    HIP_TRY(s->items.upload(r.items, 16));
+    HIP_TRY(s->flat_normals.reserve(std::max<size_t>((size_t)r.n_flat_normals * sizeof(float4), 16)));
+    // the host copies that the scene's edits and queries work from
+    s->tex_width.swap(r.tex_width); s->h_textures.swap(r.dtex); s->h_dmat.swap(r.dmat); s->h_lights.swap(r.dlights);
+    s->h_items.swap(r.items); s->item_host.swap(r.item_host); s->h_slot_face.swap(r.slot_face);
     s->n_materials = fs->n_materials;
-    bool general_w = false;
-    uint64_t n_flat_normals = 0; // entries of DSceneView::flat_normals: two per instanced triangle
-    for (uint32_t i = 0; i < fs->n_items; i++) {
-        const rr_item& it = fs->items[i];
-        const rr_material& cache = fs->materials[it.material_cache];
-        const rr_material& full = fs->materials[it.material];
-        DItem& d = s->h_items[i];
-        memset(&d, 0, sizeof d);
-        fill_item_matrices(d, it.trans, it.trans_inv);
-        if (!(it.trans_inv[3] == 0.0f && it.trans_inv[7] == 0.0f && it.trans_inv[11] == 0.0f && it.trans_inv[15] == 1.0f)) general_w = true;
-        for (int k = 0; k < 3; k++) { d.bmin[k] = it.bbox_min[k]; d.bmax[k] = it.bbox_max[k]; }
-        d.radius = it.radius;
-        d.id = it.id;
-        d.material = it.material;
-        ItemHost& ih = s->item_host[i];
-        ih = ItemHost{it.kind, it.material, it.material_cache, it.visible != 0, it.flip_normals != 0, false, false, it.kind != RR_ITEM_SPHERE ? (int32_t)it.mesh : -1};
-        if (it.kind != RR_ITEM_SPHERE) {
-            const MeshDev& m = md[it.mesh];
-            d.tri_base = m.tri_base; d.n_tris = m.n_tris;
-            d.node_base4 = m.node_base4; d.root4 = m.root4;
-            if (n_flat_normals + 2ull * m.n_tris > 0xffffffffull) return fail(RR_ERR_UNSUPPORTED, "more than 2^31 instanced triangles");
-            d.wn_base = (uint32_t)n_flat_normals; n_flat_normals += 2ull * m.n_tris;
-            ih.mesh_has_normals = m.has_normals; ih.mesh_degenerate = m.degenerate;
-        }
-        const uint32_t f = item_flags(ih, cache, full, s->tex_width);
-        d.flags = f;
-        if (f & RR_IF_OCCLUDER_ALPHA_TEX) s->view.any_alpha_occluder = 1u;
-    }
-
-    auto upload = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        return bytes ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    if (all_nodes4.size() >= (1u << 25)) return fail(RR_ERR_UNSUPPORTED, "%zu BVH4 nodes (nodes are addressed with 32-bit byte offsets)", all_nodes4.size());
-    HIP_TRY(upload(s->nodes4, all_nodes4.data(), all_nodes4.size() * sizeof(DNode4)));
-    HIP_TRY(upload(s->tris, all_tris.data(), all_tris.size() * sizeof(DTri)));
-    if (all_trix.size() >= (1u << 26)) return fail(RR_ERR_UNSUPPORTED, "%zu triangles (addressed with 32-bit byte offsets)", all_trix.size());
-    static_assert(sizeof(DTriX) == 48 && sizeof(DNode4) == 128 && sizeof(DMaterial) == 240, "layouts the kernels address by byte offset");
-    HIP_TRY(upload(s->trix, all_trix.data(), all_trix.size() * sizeof(DTriX)));
-    HIP_TRY(upload(s->attrs, all_attrs.data(), all_attrs.size() * sizeof(DTriAttr)));
-    HIP_TRY(upload(s->face_slot, all_face_slot.data(), all_face_slot.size() * 4));
-    HIP_TRY(upload(s->items, s->h_items.data(), s->h_items.size() * sizeof(DItem)));
-    HIP_TRY(s->flat_normals.reserve(std::max<size_t>((size_t)n_flat_normals * sizeof(float4), 16)));
-    rc = derive_from_transforms(s.get()); // flat world normals; the extent of every item's surface, for the top level below
-    if (rc != RR_OK) return rc;
+    s->n_enabled_lights = r.n_enabled_lights;
+    s->tlas_depth_limit = r.tlas_depth_limit;
+    RR_TRY(derive_from_transforms(s.get())); // flat world normals; the extent of every item's surface, for the top level below
 
     // ---- top level: always present (even for one item), so the kernels have a single traversal path.
     // The reference's choice between "all items" and its scene BVH (src/raytracing.rs:434) only changes the
@@ -1089,16 +548,14 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     {
         TlasTrees trees;
         const double none[3] = {0.0, 0.0, 0.0};
-        rc = build_tlas(s.get(), none, &trees);
-        if (rc != RR_OK) return rc;
+        RR_TRY(build_tlas(s->h_items, s->h_spans, s->tlas_depth_limit, none, &trees));
         for (int c = 0; c < 3; c++) s->tlas_floor[c] = trees.reach[c];
         s->tlas_node_capacity = std::max<uint32_t>((uint32_t)std::max(trees.corner.size(), trees.surface.size()), fs->n_items ? fs->n_items : 1u); // room for rebuilds after transform updates
         HIP_TRY(s->tnodes4.reserve(2 * (size_t)s->tlas_node_capacity * sizeof(DNode4)));
         HIP_TRY(hipMemset(s->tnodes4.p, 0, 2 * (size_t)s->tlas_node_capacity * sizeof(DNode4)));
         HIP_TRY(s->item_boxes.reserve(std::max<size_t>(trees.item_boxes.size() * sizeof(float4), 16)));
         s->view.tnodes4 = s->tnodes4.as<DNode4>();
-        rc = upload_tlas(s.get(), trees);
-        if (rc != RR_OK) return rc;
+        RR_TRY(upload_tlas(s.get(), trees));
     }
 
     DSceneView& v = s->view;
@@ -1109,7 +566,8 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     v.lights = s->lights.as<DLight>();
     v.n_items = fs->n_items; v.n_lights = fs->n_lights; v.n_enabled_lights = s->n_enabled_lights;
     v.item_boxes = s->item_boxes.as<float4>();
-    v.general_w = general_w ? 1u : 0u;
+    v.general_w = r.general_w ? 1u : 0u;
+    v.any_alpha_occluder = r.any_alpha_occluder ? 1u : 0u;
 
     HIP_TRY(s->pool.reserve(POOL_WORDS * 4));
     HIP_TRY(s->counters.reserve(RR_CNT_WORDS * 8));
@@ -1180,8 +638,8 @@ extern "C" int rr_scene_update_transforms(rr_scene* s, const float* trans, const
     bool general_w = false;
     for (uint32_t i = 0; i < n; i++) {
         const float *t = trans + 16 * (size_t)i, *ti = trans_inv + 16 * (size_t)i;
-        if (!finite16(t) || !finite16(ti)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: non-finite transform", i);
-        if (!(ti[3] == 0.0f && ti[7] == 0.0f && ti[11] == 0.0f && ti[15] == 1.0f)) general_w = true;
+        RR_TRY(check_item_transform(i, t, ti));
+        if (!affine_inverse(make_float4(ti[3], ti[7], ti[11], ti[15]))) general_w = true;
     }
     // what the update writes, for the way back
     const std::vector<DItem> items0 = s->h_items;
@@ -1196,7 +654,7 @@ extern "C" int rr_scene_update_transforms(rr_scene* s, const float* trans, const
         s->view.general_w = general_w ? 1u : 0u;
         TlasTrees trees;
         const double none[3] = {0.0, 0.0, 0.0};
-        RR_TRY(build_tlas(s, none, &trees)); // the next frame's camera grows the reach again if it has to
+        RR_TRY(build_tlas(s->h_items, s->h_spans, s->tlas_depth_limit, none, &trees)); // the next frame's camera grows the reach again if it has to
         RR_FAULT_POINT("update_transforms.upload_tlas");
         RR_TRY(upload_tlas(s, trees));
         for (int c = 0; c < 3; c++) s->tlas_floor[c] = s->tlas_reach[c];
@@ -1208,7 +666,7 @@ extern "C" int rr_scene_update_transforms(rr_scene* s, const float* trans, const
         s->view = view0;
         RR_TRY(upload_items_and_derive(s)); // the flat normals and spans of before, bit for bit
         TlasTrees trees;
-        RR_TRY(build_tlas(s, reach0, &trees)); // reach0 already covers the items: the same reach, boxes and trees as before
+        RR_TRY(build_tlas(s->h_items, s->h_spans, s->tlas_depth_limit, reach0, &trees)); // reach0 already covers the items: the same reach, boxes and trees as before
         RR_TRY(upload_tlas(s, trees));
         s->view = view0;
         return RR_OK;
@@ -1216,14 +674,18 @@ extern "C" int rr_scene_update_transforms(rr_scene* s, const float* trans, const
     return all_or_nothing("rr_scene_update_transforms", &s->broken_geometry, apply, restore);
 } RR_GUARD_END("rr_scene_update_transforms")
 
-// The material records and the items' records (their flag words) to the device: the update's way there and its way back.
-static int copy_material_records(rr_scene* s, const std::vector<DMaterial>& dmat, const std::vector<DItem>& items) {
-    HIP_TRY(hipDeviceSynchronize());
-    if (!dmat.empty()) HIP_TRY(hipMemcpy(s->materials.p, dmat.data(), dmat.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    RR_FAULT_POINT("update_materials.device");
-    if (!items.empty()) HIP_TRY(hipMemcpy(s->items.p, items.data(), items.size() * sizeof(DItem), hipMemcpyHostToDevice));
+// Records of an update to buffers that hold them already: the update's way there and its way back.  `point` (a test's fault point) is
+// crossed after the first copy: between the two of a material update, behind the only one of the others.
+struct RecordCopy { void* dst; const void* src; size_t bytes; };
+static int copy_records(const char* point, std::initializer_list<RecordCopy> copies) {
+    HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the records
+    for (const RecordCopy& c : copies) {
+        if (c.bytes) HIP_TRY(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice));
+        if (&c == copies.begin()) RR_FAULT_POINT(point);
+    }
     return RR_OK;
 }
+template <class T> static RecordCopy records_to(const DevBuf& b, const std::vector<T>& v) { return RecordCopy{b.p, v.data(), v.size() * sizeof(T)}; }
 
 // Material edits between frames (GUI sliders: reference src/run.rs:1132-1133 writes through Material::apply_diff,
 // src/shape/mod.rs:182-242): every material record is replaced and the item flag words derived from the material
@@ -1234,13 +696,10 @@ extern "C" int rr_scene_update_materials(rr_scene* s, const rr_material* materia
     RR_TRY(not_in_pass(s, "rr_scene_update_materials"));
     std::lock_guard<std::mutex> lk(s->mu);
     if (n_materials != s->n_materials) return fail(RR_ERR_INVALID_ARGUMENT, "%u materials, the scene was created with %u", n_materials, s->n_materials);
-    for (uint32_t i = 0; i < n_materials; i++)
-        for (int k = 0; k < RR_TEX_COUNT; k++)
-            if (materials[i].texture[k] >= (int32_t)s->tex_width.size()) return fail(RR_ERR_INVALID_ARGUMENT, "material %u texture slot %d = %d out of range", i, k, materials[i].texture[k]);
+    RR_TRY(check_material_textures(materials, n_materials, s->tex_width.size()));
     for (const ItemHost& ih : s->item_host)
-        for (int k = 0; k < RR_TEX_COUNT; k++)
-            if (materials[ih.material_cache].texture[k] >= 0)
-                return fail(RR_ERR_INVALID_ARGUMENT, "material %d is a material cache and must not carry textures (reference src/shape/mod.rs:769-772)", ih.material_cache);
+        if (carries_textures(materials[ih.material_cache]))
+            return fail(RR_ERR_INVALID_ARGUMENT, "material %d is a material cache and must not carry textures (reference src/shape/mod.rs:769-772)", ih.material_cache);
     HIP_TRY(hipSetDevice(s->device));
     std::vector<DMaterial> dmat(n_materials);
     for (uint32_t i = 0; i < n_materials; i++) dmat[i] = make_dmaterial(materials[i], s->tex_width, s->h_textures);
@@ -1251,22 +710,16 @@ extern "C" int rr_scene_update_materials(rr_scene* s, const rr_material* materia
         items[i].flags = item_flags(s->item_host[i], materials[s->item_host[i].material_cache], materials[s->item_host[i].material], s->tex_width);
         if (items[i].flags & RR_IF_OCCLUDER_ALPHA_TEX) any_alpha_occluder = 1u;
     }
-    auto apply = [&]() -> int { return copy_material_records(s, dmat, items); };
-    auto restore = [&]() -> int { return copy_material_records(s, s->h_dmat, s->h_items); }; // the host copies still hold the records of before
+    auto apply = [&]() -> int { return copy_records("update_materials.device", {records_to(s->materials, dmat), records_to(s->items, items)}); };
+    auto restore = [&]() -> int { // the host copies still hold the records of before
+        return copy_records("update_materials.device", {records_to(s->materials, s->h_dmat), records_to(s->items, s->h_items)});
+    };
     RR_TRY(all_or_nothing("rr_scene_update_materials", &s->broken_materials, apply, restore));
     s->h_items.swap(items);
     s->h_dmat.swap(dmat);
     s->view.any_alpha_occluder = any_alpha_occluder;
     return RR_OK;
 } RR_GUARD_END("rr_scene_update_materials")
-
-// The light records to `buf` (the scene's buffer, or a larger one that replaces it): the update's way there and its way back.
-static int copy_light_records(rr_scene* s, DevBuf& buf, const std::vector<DLight>& dl) {
-    HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the records
-    if (!dl.empty()) HIP_TRY(hipMemcpy(buf.p, dl.data(), dl.size() * sizeof(DLight), hipMemcpyHostToDevice));
-    RR_FAULT_POINT("update_lights.device");
-    return RR_OK;
-}
 
 // Light edits between frames (the GUI's light panel: reference src/run.rs:1294-1409 adds, edits and deletes `Scene::lights`): the
 // whole list is replaced; its length may change.  A light's index is the RNG stream of its shadow jitter, so the list is taken in
@@ -1276,23 +729,18 @@ extern "C" int rr_scene_update_lights(rr_scene* s, const rr_light* lights, uint3
     if (!s || (n_lights && !lights)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     RR_TRY(not_in_pass(s, "rr_scene_update_lights"));
     std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < n_lights; i++) // as validate_scene
-        if (lights[i].light_type > RR_LIGHT_SPOT) return fail(RR_ERR_INVALID_ARGUMENT, "light %u: type %u", i, lights[i].light_type);
+    RR_TRY(check_lights(lights, n_lights));
     HIP_TRY(hipSetDevice(s->device));
-    std::vector<DLight> dl(n_lights);
     uint32_t n_enabled = 0;
-    for (uint32_t i = 0; i < n_lights; i++) {
-        dl[i] = make_dlight(lights[i]);
-        if (lights[i].enabled) n_enabled++;
-    }
-    DevBuf grown;
+    std::vector<DLight> dl = make_dlights(lights, n_lights, &n_enabled);
+    DevBuf grown; // a list longer than the scene's buffer holds goes to a new one
     const bool grow = (size_t)n_lights * sizeof(DLight) > s->lights.bytes;
     if (grow) HIP_TRY(grown.reserve((size_t)n_lights * sizeof(DLight)));
-    auto apply = [&]() -> int { return copy_light_records(s, grow ? grown : s->lights, dl); };
-    auto restore = [&]() -> int { return copy_light_records(s, s->lights, s->h_lights); };
+    auto apply = [&]() -> int { return copy_records("update_lights.device", {records_to(grow ? grown : s->lights, dl)}); };
+    auto restore = [&]() -> int { return copy_records("update_lights.device", {records_to(s->lights, s->h_lights)}); };
     RR_TRY(all_or_nothing("rr_scene_update_lights", &s->broken_lights, apply, restore));
     // the device holds the new records: the frame path reads the count, the enabled count (shadow-queue plan, fixed shadow slots) and the pointer together
-    if (grow) s->lights = std::move(grown); // frees the old buffer: nothing reads it since the synchronisation in copy_light_records
+    if (grow) s->lights = std::move(grown); // frees the old buffer: nothing reads it since the synchronisation in copy_records
     s->h_lights.swap(dl);
     s->n_enabled_lights = n_enabled;
     s->view.lights = s->lights.as<DLight>();
@@ -1300,14 +748,6 @@ extern "C" int rr_scene_update_lights(rr_scene* s, const rr_light* lights, uint3
     s->view.n_enabled_lights = n_enabled;
     return RR_OK;
 } RR_GUARD_END("rr_scene_update_lights")
-
-// The items' records (their flag words) to the device: the update's way there and its way back.
-static int copy_item_flag_records(rr_scene* s, const std::vector<DItem>& items) {
-    HIP_TRY(hipDeviceSynchronize());
-    if (!items.empty()) HIP_TRY(hipMemcpy(s->items.p, items.data(), items.size() * sizeof(DItem), hipMemcpyHostToDevice));
-    RR_FAULT_POINT("update_item_flags.device");
-    return RR_OK;
-}
 
 // The GUI's "Visible" and "flip normals" checkboxes (reference src/run.rs:1464-1489, ShapeBasics::visible / flip_normals): only
 // RR_IF_VISIBLE and RR_IF_FLIP_NORMALS of each item's flag word change.  The kernels read both per candidate and per hit
@@ -1323,8 +763,8 @@ extern "C" int rr_scene_update_item_flags(rr_scene* s, const uint8_t* visible, c
     for (uint32_t i = 0; i < n_items; i++)
         items[i].flags = (items[i].flags & ~(uint32_t)(RR_IF_VISIBLE | RR_IF_FLIP_NORMALS)) | (visible[i] ? (uint32_t)RR_IF_VISIBLE : 0u) |
                          (flip_normals[i] ? (uint32_t)RR_IF_FLIP_NORMALS : 0u);
-    auto apply = [&]() -> int { return copy_item_flag_records(s, items); };
-    auto restore = [&]() -> int { return copy_item_flag_records(s, s->h_items); };
+    auto apply = [&]() -> int { return copy_records("update_item_flags.device", {records_to(s->items, items)}); };
+    auto restore = [&]() -> int { return copy_records("update_item_flags.device", {records_to(s->items, s->h_items)}); };
     RR_TRY(all_or_nothing("rr_scene_update_item_flags", &s->broken_item_flags, apply, restore));
     s->h_items.swap(items);
     for (uint32_t i = 0; i < n_items; i++) { s->item_host[i].visible = visible[i] != 0; s->item_host[i].flip_normals = flip_normals[i] != 0; }
@@ -1340,34 +780,19 @@ extern "C" int rr_scene_add_textures(rr_scene* s, const rr_texture* textures, ui
     if (!s || !first_index || (n_textures && !textures)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     RR_TRY(not_in_pass(s, "rr_scene_add_textures"));
     std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < n_textures; i++) { // as validate_scene
-        const rr_texture& t = textures[i];
-        if ((uint64_t)t.width * t.height > 0 && !t.rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "texture %u has no pixels", i);
-        if (t.width > 32768u || t.height > 32768u) return fail(RR_ERR_UNSUPPORTED, "texture %u is %ux%u", i, t.width, t.height);
-    }
+    RR_TRY(check_textures(textures, n_textures));
     const uint32_t first = (uint32_t)s->tex_width.size();
     if (n_textures == 0) { *first_index = first; return RR_OK; }
     HIP_TRY(hipSetDevice(s->device));
     std::vector<DTexture> dtex = s->h_textures;
     std::vector<uint32_t> widths = s->tex_width;
-    const uint64_t old_texels = dtex.empty() ? 0 : dtex.back().offset + (uint64_t)dtex.back().width * dtex.back().height;
-    uint64_t n_texels = old_texels;
-    for (uint32_t i = 0; i < n_textures; i++) {
-        DTexture d;
-        d.offset = n_texels; d.width = textures[i].width; d.height = textures[i].height;
-        dtex.push_back(d);
-        widths.push_back(textures[i].width);
-        n_texels += (uint64_t)textures[i].width * textures[i].height;
-    }
+    const uint64_t old_texels = pool_texels(dtex);
+    append_texture_layout(textures, n_textures, &dtex, &widths);
     DevBuf texels, descs;
-    HIP_TRY(texels.reserve(std::max<uint64_t>(n_texels, 1) * 4));
-    HIP_TRY(descs.reserve(dtex.size() * sizeof(DTexture)));
+    HIP_TRY(texels.reserve(std::max<uint64_t>(pool_texels(dtex), 1) * 4));
     if (old_texels) HIP_TRY(hipMemcpy(texels.p, s->texels.p, old_texels * 4, hipMemcpyDeviceToDevice)); // frames in flight only read the old pool
-    for (uint32_t i = 0; i < n_textures; i++) {
-        const uint64_t n = (uint64_t)textures[i].width * textures[i].height;
-        if (n) HIP_TRY(hipMemcpy(texels.as<uint32_t>() + dtex[first + i].offset, textures[i].rgba8, n * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(descs.p, dtex.data(), dtex.size() * sizeof(DTexture), hipMemcpyHostToDevice));
+    RR_TRY(upload_images(texels.as<uint32_t>(), textures, n_textures, &dtex[first]));
+    HIP_TRY(descs.upload(dtex, sizeof(DTexture)));
     RR_FAULT_POINT("add_textures.device");
     HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the pool that is freed below
     // the pool and the descriptors of the longer list replace the old ones (frees them); material records keep their descriptors
@@ -1984,13 +1409,6 @@ struct GatherMap { DevBuf index, rank, local; };
 using GatherKey = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int>; // width, height, tile_w, tile_h, n_ranks, device
 static std::mutex g_gather_mu;
 static std::map<GatherKey, GatherMap>& g_gather_maps = *new std::map<GatherKey, GatherMap>(); // never destroyed: no hipFree after the HIP runtime's teardown
-static int upload_u32(DevBuf* b, const std::vector<uint32_t>& v) {
-    DevBuf d;
-    HIP_TRY(d.reserve(v.size() * 4));
-    HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    *b = std::move(d);
-    return RR_OK;
-}
 // the map of `key` with `index` (packed = false) or `rank` and `local` (packed = true) on the device; under g_gather_mu
 static int gather_map(const GatherKey& key, bool packed, GatherMap** out) {
     GatherMap& gm = g_gather_maps[key];
@@ -2005,12 +1423,14 @@ static int gather_map(const GatherKey& key, bool packed, GatherMap** out) {
         for (uint32_t p = 0; p < xy.size(); p++) { const size_t o = (size_t)(xy[p] >> 16) * width + (xy[p] & 0xffffu); rank[o] = r; local[o] = p; }
         offset[r] = base; base += (uint32_t)xy.size();
     }
-    if (packed) { // `rank` last: it is what marks the pair as uploaded
-        RR_TRY(upload_u32(&gm.local, local));
-        return upload_u32(&gm.rank, rank);
-    }
-    for (uint32_t o = 0; o < np; o++) local[o] += offset[rank[o]];
-    return upload_u32(&gm.index, local);
+    // a map counts as uploaded once its buffer (of a pair: `rank`) is set: filled aside, moved in when complete
+    DevBuf a, b;
+    if (packed) HIP_TRY(b.upload(rank, 4));
+    else for (uint32_t o = 0; o < np; o++) local[o] += offset[rank[o]];
+    HIP_TRY(a.upload(local, 4));
+    if (packed) { gm.local = std::move(a); gm.rank = std::move(b); }
+    else gm.index = std::move(a);
+    return RR_OK;
 }
 
 extern "C" int rr_deinterleave_device(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n_ranks,

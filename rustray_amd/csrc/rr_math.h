@@ -171,6 +171,9 @@ RR_DEV float rr_atan2(float y, float x) {
 }
 
 // ---- Philox4x32-10: the counter-based generator behind jitter() ----------------------------
+#ifndef __HIPCC__ // a plain host compiler (the native tests of the host-only headers) has no such builtin
+static inline uint32_t __umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+#endif
 RR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                           uint32_t* r0, uint32_t* r1) {
 #pragma unroll

@@ -195,7 +195,10 @@ def test_every_entry_point_is_guarded():
             continue
         assert re.search(r'extern "C" int ' + n + r'\([^{]*\) try \{', src), f"{n} is not a function-try-block"
         assert f'RR_GUARD_END("{n}")' in src, f"{n} has no RR_GUARD_END"
-    assert "std::thread> pool" not in src and "threads.emplace_back(work" not in src   # worker threads only through `Workers`
+    # worker threads only through `Workers`, in this file and in the scene builder it includes (where `Workers` itself lives)
+    src += open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_scene_build.h")).read()
+    assert "std::thread> pool" not in src and "threads.emplace_back(work" not in src
+    assert len(re.findall(r"std::thread\b(?!::hardware_concurrency)", src)) == 2   # Workers' own vector and its join loop
 
 
 def test_guard_from_a_c_host(tmp_path):

@@ -1,6 +1,6 @@
 """The packet form of the top level tests closest-hit packets against the items' SURFACE boxes (the world box of a mesh's
 transformed vertices: much smaller than the box of its turned local box) and shadow packets against the boxes of the local
-boxes' corners, whose entry distances bound the shadow query's order (rr_api.hip build_tlas, exact_world_box).  A scene of turned
+boxes' corners, whose entry distances bound the shadow query's order (rr_scene_build.h build_tlas, exact_world_box).  A scene of turned
 instances, a ball whose arithmetic overflows (ray_ball answers Some(NaN) for every ray through its LOCAL box: it must keep the
 corner box) and a stretched one, against the oracle in both of its candidate forms; then the same after rr_scene_update_transforms."""
 import math

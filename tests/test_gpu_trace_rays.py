@@ -71,7 +71,7 @@ def test_far_from_the_origin_the_top_level_keeps_every_candidate(hip, oracle, na
     """Reduced from tools/fuzz_parity.py `far` mismatches.  The reference has no world-space test: it moves the ray into
     an item's space with the item's f32 inverse matrix and tests there.  1e5 .. 1e8 from the origin, with a sheared
     transform (cond ~ 3000), that local ray sits up to 15 world units from the true one, so world boxes padded by float
-    spacing cull items the reference hits.  The boxes are padded by a derived bound instead (rr_api.hip: padded_world_box),
+    spacing cull items the reference hits.  The boxes are padded by a derived bound instead (rr_scene_build.h: padded_world_box),
     for the camera's distance as well (the top level is rebuilt when a camera moves far outside the scene)."""
     fs = FlatScene.load(os.path.join(GOLDEN, name + ".npz"))
     w, h = fs.meta["wh"]

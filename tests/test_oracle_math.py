@@ -69,7 +69,7 @@ def test_host_build_of_rr_cos_equals_the_oracles(oracle):
 
 
 def test_host_build_of_the_triangle_constants_is_the_ieee_sequence():
-    """DTri::v1.w (area = |cross(a - b, a - c)|) and v3 (normalize(cross(b - a, c - a))) are evaluated on the host (rr_api.hip
+    """DTri::v1.w (area = |cross(a - b, a - c)|) and v3 (normalize(cross(b - a, c - a))) are evaluated on the host (rr_scene_build.h
     tri_shading_constants).  numpy's float32 arithmetic is the same correctly rounded IEEE sequence: bit for bit, NaN for NaN.
     (tests/test_gpu_math.py holds the device build to the host build.)"""
     from rustray_amd import capi

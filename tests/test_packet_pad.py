@@ -45,7 +45,7 @@ def test_decoys_are_inert_in_the_oracle(oracle, base):
 
 
 def test_switch_decoys_set_the_scene_wide_switches():
-    """The three switch items are what the device keys its scene-wide paths on (rr_api.hip: general_w from a non-affine inverse,
+    """The three switch items are what the device keys its scene-wide paths on (rr_scene_build.h: general_w from a non-affine inverse,
     any_alpha_occluder from an alpha map, RR_VIEW_NAN_BALLS from a ball whose arithmetic can overflow)."""
     fs = pad_inert(load_scene("spheres"), 17, "switches")
     new = fs.items[8:]

@@ -34,7 +34,7 @@ def build(name):
     try:
         os.makedirs(os.path.join(d, "rustray_amd", "csrc"))
         os.makedirs(os.path.join(d, "include"))
-        for f in ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h"):
+        for f in ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h"):
             shutil.copy(os.path.join(ROOT, "rustray_amd", "csrc", f), os.path.join(d, "rustray_amd", "csrc", f))
         shutil.copy(os.path.join(ROOT, "include", "rustray_hip.h"), os.path.join(d, "include", "rustray_hip.h"))
         for part in name.split("+"):
