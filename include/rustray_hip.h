@@ -38,7 +38,8 @@ extern "C" {
  * past its structs.  2: rr_frame_stats grew (level-1 timing, binning, multi-GPU exchange), rr_tuning, rr_abi_version.
  * 3: rr_frame_stats carries the level-1 share of the shade and shadow kernels too (one roofline per kernel build in bench.py).
  * rr_scene_update_lights, rr_scene_update_item_flags and rr_scene_add_textures came later without a change of any struct, so the
- * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them). */
+ * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them).
+ * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -360,6 +361,28 @@ int rr_scene_update_item_flags(rr_scene* scene, const uint8_t* visible, const ui
  * rr_scene_update_materials names them.  Adding 0 textures changes nothing.  A failure leaves the scene as it was.  Texture memory
  * never shrinks: images no material names any more stay resident until the scene is destroyed. */
 int rr_scene_add_textures(rr_scene* scene, const rr_texture* textures, uint32_t n_textures, uint32_t* first_index);
+
+/* Append meshes to the scene's mesh list (the GUI's "add ground plane", reference src/scene.rs:1564-1578, brings a mesh the scene
+ * does not hold yet); *first_index receives the index of the first new one.  Meshes are checked as by rr_scene_create and their trees
+ * built for the scene's current share of the traversal stack.  The resident meshes keep their indices and their place; the new
+ * ones take the indices (and layout) a scene created with the longer list gives them.  Nothing is rendered from them until a
+ * following rr_scene_set_items names them.  Adding 0 meshes changes nothing.  A failure leaves the scene as it was.  Meshes are
+ * never removed: a mesh no item names stays resident, on the device and as the scene's host copy of its arrays, until the scene
+ * is destroyed. */
+int rr_scene_add_meshes(rr_scene* scene, const rr_mesh* meshes, uint32_t n_meshes, uint32_t* first_index);
+
+/* Replace the whole item list AND the whole material list, together (items name materials by index): the GUI's object "delete",
+ * "add ground plane" and "add environment sphere" (reference src/scene.rs:1602-1620, :1564-1578).  Any item count from 0 to
+ * RR_MAX_ITEMS, in any order; an item may name any resident mesh (rr_scene_create, rr_scene_add_meshes), a material any resident
+ * texture (rr_scene_create, rr_scene_add_textures); every check and limit of rr_scene_create applies.  Afterwards
+ * rr_scene_update_materials / _transforms / _item_flags expect the new counts.  Resident meshes, their trees and the texture images
+ * stay as they are, and items whose transform, mesh and flags did not change keep what was derived for them, so the cost follows
+ * the edit and not the scene -- with one exception: the per-mesh trees share the traversal stack with the top level, whose share
+ * depends on the item count below 14 and above 4096 items; an edit that changes the share rebuilds every mesh's tree (from the
+ * scene's host copies), and returns RR_ERR_UNSUPPORTED when a mesh no longer fits.  A failure leaves the scene as it was: the new
+ * state is built beside the old one and replaces it last.  A scene that a failed update of another kind left broken (see
+ * rr_scene_update_transforms) refuses this call as it refuses frames. */
+int rr_scene_set_items(rr_scene* scene, const rr_item* items, uint32_t n_items, const rr_material* materials, uint32_t n_materials);
 
 /* Compatibility switches: behaviours of EARLIER reference binaries that the source at HEAD no longer has.  Default 0 = HEAD.
  * RR_COMPAT_OCCLUDER_ALPHA_SHADOWS: a shadow is attenuated by the OCCLUDER's material.alpha, where HEAD takes the

@@ -431,6 +431,15 @@ public:
     int add_textures(const std::vector<rr_texture>& textures, uint32_t* first_index) {
         return check(rr_scene_add_textures(h_, textures.data(), (uint32_t)textures.size(), first_index));
     }
+    // Appends meshes to the mesh list; *first_index: the index of the first (name it in a following set_items).
+    int add_meshes(const std::vector<rr_mesh>& meshes, uint32_t* first_index) {
+        return check(rr_scene_add_meshes(h_, meshes.data(), (uint32_t)meshes.size(), first_index));
+    }
+    // The whole item list and the whole material list the items name, together (the GUI's object "delete", "add ground plane",
+    // "add environment sphere"); an item's `mesh` is an index into the resident meshes.
+    int set_items(const std::vector<rr_item>& items, const std::vector<rr_material>& materials) {
+        return check(rr_scene_set_items(h_, items.data(), (uint32_t)items.size(), materials.data(), (uint32_t)materials.size()));
+    }
 
 private:
     int check(int rc) { if (rc != RR_OK) error_ = rr_last_error(); return rc; }

@@ -12,8 +12,8 @@ import subprocess
 
 import numpy as np
 
-from .flat import (RR_ABI_VERSION, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_light, rr_material, rr_pick_result, rr_region,
-                   rr_texture, rr_tuning)
+from .flat import (RR_ABI_VERSION, FlatScene, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_light, rr_material, rr_pick_result,
+                   rr_region, rr_texture, rr_tuning)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUSTRAY_HIP_LIB") or os.path.join(_HERE, "librustray_hip.so")  # override: developer A/B builds
@@ -21,7 +21,7 @@ _LIB = None
 
 # every symbol include/rustray_hip.h declares (tests/test_abi.py checks the list against the header)
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
-           "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
+           "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
            "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_scene_last_stats", "rr_post_process", "rr_post_process_device"]
 
@@ -97,6 +97,9 @@ def lib():
             L.rr_scene_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
             L.rr_scene_update_item_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             L.rr_scene_add_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        if hasattr(L, "rr_scene_set_items") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_scene_add_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+            L.rr_scene_set_items.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rr_scene_set_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
         L.rr_scene_get_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
         L.rr_post_process.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -257,6 +260,24 @@ class DeviceScene:
         first = C.c_uint32(0)
         _check(lib().rr_scene_add_textures(self._h, arr, len(keep), C.byref(first)))
         return int(first.value)
+
+    def add_meshes(self, meshes) -> int:
+        """rr_scene_add_meshes: appends flat.MeshData meshes to the mesh list; returns the index of the first."""
+        fs = FlatScene()
+        fs.meshes = list(meshes)
+        c = fs.c_struct()                     # (fs keeps the arrays alive during the call)
+        first = C.c_uint32(0)
+        _check(lib().rr_scene_add_meshes(self._h, c.meshes if len(fs.meshes) else None, len(fs.meshes), C.byref(first)))
+        return int(first.value)
+
+    def set_items(self, items, materials):
+        """rr_scene_set_items: the whole item list (flat.Item; `mesh` = an index into the scene's resident meshes) and the whole
+        material list (flat.Material or rr_material) that the items name, together."""
+        fs = FlatScene()
+        fs.items = list(items)
+        c = fs.c_struct()
+        arr = (rr_material * max(len(materials), 1))(*[m.c_struct() if hasattr(m, "c_struct") else m for m in materials])
+        _check(lib().rr_scene_set_items(self._h, c.items if len(fs.items) else None, len(fs.items), arr if len(materials) else None, len(materials)))
 
     def set_tuning(self, **kw):
         """rr_scene_set_tuning: sample_group, queue_budget_bytes, shade_chunk_rays, kernel_timing, multi_force_staged, bin_min_rays (others keep their value)."""

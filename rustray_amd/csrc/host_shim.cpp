@@ -132,6 +132,14 @@ extern "C" int rh_add_textures(void* h, const rr_texture* textures, uint32_t n, 
     return ((RhScene*)h)->scene->add_textures(std::vector<rr_texture>(textures, textures + n), first_index);
 }
 
+extern "C" int rh_add_meshes(void* h, const rr_mesh* meshes, uint32_t n, uint32_t* first_index) {
+    return ((RhScene*)h)->scene->add_meshes(std::vector<rr_mesh>(meshes, meshes + n), first_index);
+}
+
+extern "C" int rh_set_items(void* h, const rr_item* items, uint32_t n_items, const rr_material* materials, uint32_t n_materials) {
+    return ((RhScene*)h)->scene->set_items(std::vector<rr_item>(items, items + n_items), std::vector<rr_material>(materials, materials + n_materials));
+}
+
 // one whole frame (min_passes passes) into the caller's buffers
 extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
                                const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,

@@ -75,7 +75,7 @@ static int guard_fail(const char* fn) noexcept {
 // update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
 // and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload), update_lights.device (after the light
 // records' copy), update_item_flags.device (after the items' copy), add_textures.device (after the grown pool's upload, before it
-// replaces the old one).  Not armed (always, outside the tests): one
+// replaces the old one), add_meshes.device and set_items.device (after the new state's upload, before the commit).  Not armed (always, outside the tests): one
 // acquire load per crossing (it pairs with the release store of rr_test_fault: a thread that sees the kind sees the point's name), and
 // the points sit outside every per-ray and per-triangle loop.
 static std::atomic<int> g_fault_kind{0};
@@ -172,6 +172,13 @@ struct rr_scene {
     std::vector<DItem> h_items;
     std::vector<uint32_t> h_slot_face; // per mesh triangle: leaf-order slot -> original face index (rr_trace_rays reports the reference's face id)
     std::vector<ItemHost> item_host; // what rr_scene_update_materials needs to rebuild the item flag words
+    // the meshes: where each one's records sit in the arenas (what an item takes from the mesh it names, rr_scene_set_items), how many
+    // records the arenas hold (rr_scene_add_meshes appends behind them), the scene's own copy of the caller's arrays (the trees are
+    // rebuilt from it when an edit of the item list changes their share of the traversal stack) and that share
+    std::vector<MeshDev> mesh_table;
+    std::vector<HostMesh> h_meshes;
+    size_t n_nodes4 = 0, n_mesh_tris = 0;
+    int blas_depth_limit = RR_BLAS_MAX_DEPTH;
     // per item: the extent of its surface along the rows of its transform (k_item_spans: minima, maxima, largest |local coordinate|; 9 doubles),
     // read back after every upload of the items' transforms; the top level's surface boxes are derived from it (exact_world_box)
     std::vector<double> h_spans;
@@ -379,20 +386,30 @@ extern "C" uint64_t rr_region_pixel_count(uint32_t width, uint32_t height, const
 // nodes each) and the item boxes; then, and only then, the scene keeps what they were built for: the reach, the NaN-ball hint, the host
 // copy of the boxes and the roots in the view.  A failed copy leaves all of that as it was and marks the device trees stale.
 // Blocking copies.
-static int upload_tlas(rr_scene* s, TlasTrees& t) {
-    if (t.corner.size() > s->tlas_node_capacity || t.surface.size() > s->tlas_node_capacity)
-        return fail(RR_ERR_DEVICE, "top-level rebuild needs %zu / %zu nodes, capacity %u", t.corner.size(), t.surface.size(), s->tlas_node_capacity);
-    s->tlas_stale = true;
-    if (!t.corner.empty()) HIP_TRY(hipMemcpy(s->tnodes4.p, t.corner.data(), t.corner.size() * sizeof(DNode4), hipMemcpyHostToDevice));
-    if (!t.surface.empty()) HIP_TRY(hipMemcpy(s->tnodes4.as<DNode4>() + s->tlas_node_capacity, t.surface.data(), t.surface.size() * sizeof(DNode4), hipMemcpyHostToDevice));
-    if (!t.item_boxes.empty()) HIP_TRY(hipMemcpy(s->item_boxes.p, t.item_boxes.data(), t.item_boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
-    s->tlas_stale = false;
+// copy_tlas / keep_tlas: the two halves, which rr_scene_set_items runs on buffers built beside the scene's and at its commit.
+static int copy_tlas(const TlasTrees& t, DNode4* tnodes4, uint32_t capacity, float4* item_boxes) {
+    if (t.corner.size() > capacity || t.surface.size() > capacity)
+        return fail(RR_ERR_DEVICE, "top-level rebuild needs %zu / %zu nodes, capacity %u", t.corner.size(), t.surface.size(), capacity);
+    if (!t.corner.empty()) HIP_TRY(hipMemcpy(tnodes4, t.corner.data(), t.corner.size() * sizeof(DNode4), hipMemcpyHostToDevice));
+    if (!t.surface.empty()) HIP_TRY(hipMemcpy(tnodes4 + capacity, t.surface.data(), t.surface.size() * sizeof(DNode4), hipMemcpyHostToDevice));
+    if (!t.item_boxes.empty()) HIP_TRY(hipMemcpy(item_boxes, t.item_boxes.data(), t.item_boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    return RR_OK;
+}
+static void keep_tlas(rr_scene* s, TlasTrees& t) noexcept {
     for (int c = 0; c < 3; c++) s->tlas_reach[c] = t.reach[c];
     s->view.compat = t.nan_balls ? (s->view.compat | RR_VIEW_NAN_BALLS) : (s->view.compat & ~RR_VIEW_NAN_BALLS);
     s->h_item_boxes.swap(t.item_boxes);
     s->view.tlas_root4 = t.root;
     s->view.tnodes4c = t.has_surface ? s->tnodes4.as<DNode4>() + s->tlas_node_capacity : s->tnodes4.as<DNode4>();
     s->view.tlas_root4c = t.has_surface ? t.root_surface : t.root;
+}
+static int upload_tlas(rr_scene* s, TlasTrees& t) {
+    if (t.corner.size() > s->tlas_node_capacity || t.surface.size() > s->tlas_node_capacity)
+        return fail(RR_ERR_DEVICE, "top-level rebuild needs %zu / %zu nodes, capacity %u", t.corner.size(), t.surface.size(), s->tlas_node_capacity);
+    s->tlas_stale = true;
+    RR_TRY(copy_tlas(t, s->tnodes4.as<DNode4>(), s->tlas_node_capacity, s->item_boxes.as<float4>()));
+    s->tlas_stale = false;
+    keep_tlas(s, t);
     return RR_OK;
 }
 
@@ -437,16 +454,27 @@ static int ensure_camera_reach(rr_scene* s, const rr_camera* cam, const rr_confi
 // ... and the extent of every item's surface along its transform's rows (k_item_spans -> s->h_spans, for the top level's surface boxes).
 // Everything that depends on the transforms and on the meshes is derived HERE, on the device, where the meshes are resident: the one
 // blocking copy of 72 B per item at the end is the call's only wait.
+static_assert(RR_HOST_ITEM_CHUNK == RR_ITEM_CHUNK, "the host's chunk map is the kernels'");
+// the spans of n items before any chunk is merged into them: what k_item_spans gives a ball or an empty mesh
+static void empty_spans(uint32_t n, std::vector<double>* spans) {
+    spans->resize(9 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++)
+        for (int k = 0; k < 9; k++) (*spans)[9 * (size_t)i + k] = k < 3 ? std::numeric_limits<double>::infinity() : (k < 6 ? -std::numeric_limits<double>::infinity() : 0.0);
+}
+// one chunk's 9 doubles (k_item_spans) into its item's
+static void merge_chunk_span(const double* q, double* d) {
+    for (int k = 0; k < 9; k++) {
+        if (q[k] != q[k]) d[k] = q[k];                       // a NaN chunk poisons the item (the corner box is kept for it)
+        else if (d[k] == d[k]) d[k] = k < 3 ? std::min(d[k], q[k]) : std::max(d[k], q[k]);
+    }
+}
 static int derive_from_transforms(rr_scene* s) {
     const uint32_t n = (uint32_t)s->h_items.size();
     s->h_spans.clear();
     if (n == 0) return RR_OK;
     if (s->h_chunk_item.empty()) { // the chunk map depends on the items' triangle counts only: laid out once
         std::vector<uint2> chunks;
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t nt = (s->h_items[i].flags & RR_IF_SPHERE) ? 0u : s->h_items[i].n_tris;
-            for (uint32_t first = 0; first == 0u || first < nt; first += RR_ITEM_CHUNK) { chunks.push_back(make_uint2(i, first)); s->h_chunk_item.push_back(i); }
-        }
+        item_chunk_map(s->h_items, &chunks, &s->h_chunk_item);
         HIP_TRY(s->item_chunks.reserve(chunks.size() * sizeof(uint2)));
         HIP_TRY(hipMemcpy(s->item_chunks.p, chunks.data(), chunks.size() * sizeof(uint2), hipMemcpyHostToDevice));
         HIP_TRY(s->spans.reserve(9 * sizeof(double) * chunks.size()));
@@ -458,17 +486,8 @@ static int derive_from_transforms(rr_scene* s) {
     HIP_TRY(hipGetLastError());
     std::vector<double> part(9 * nc);
     HIP_TRY(hipMemcpy(part.data(), s->spans.p, 9 * sizeof(double) * nc, hipMemcpyDeviceToHost)); // (waits for both kernels)
-    s->h_spans.resize(9 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++)
-        for (int k = 0; k < 9; k++) s->h_spans[9 * (size_t)i + k] = k < 3 ? std::numeric_limits<double>::infinity() : (k < 6 ? -std::numeric_limits<double>::infinity() : 0.0);
-    for (size_t c = 0; c < nc; c++) {
-        double* d = &s->h_spans[9 * (size_t)s->h_chunk_item[c]];
-        const double* q = &part[9 * c];
-        for (int k = 0; k < 9; k++) {
-            if (q[k] != q[k]) d[k] = q[k];                       // a NaN chunk poisons the item (the corner box is kept for it)
-            else if (d[k] == d[k]) d[k] = k < 3 ? std::min(d[k], q[k]) : std::max(d[k], q[k]);
-        }
-    }
+    empty_spans(n, &s->h_spans);
+    for (size_t c = 0; c < nc; c++) merge_chunk_span(&part[9 * c], &s->h_spans[9 * (size_t)s->h_chunk_item[c]]);
     return RR_OK;
 }
 
@@ -537,6 +556,9 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     // the host copies that the scene's edits and queries work from
     s->tex_width.swap(r.tex_width); s->h_textures.swap(r.dtex); s->h_dmat.swap(r.dmat); s->h_lights.swap(r.dlights);
     s->h_items.swap(r.items); s->item_host.swap(r.item_host); s->h_slot_face.swap(r.slot_face);
+    s->mesh_table.swap(r.meshes); s->n_nodes4 = r.nodes4.size(); s->n_mesh_tris = r.tris.size(); s->blas_depth_limit = r.blas_depth_limit;
+    s->h_meshes.reserve(fs->n_meshes);
+    for (uint32_t i = 0; i < fs->n_meshes; i++) s->h_meshes.emplace_back(fs->meshes[i]);
     s->n_materials = fs->n_materials;
     s->n_enabled_lights = r.n_enabled_lights;
     s->tlas_depth_limit = r.tlas_depth_limit;
@@ -806,6 +828,201 @@ extern "C" int rr_scene_add_textures(rr_scene* s, const rr_texture* textures, ui
     *first_index = first;
     return RR_OK;
 } RR_GUARD_END("rr_scene_add_textures")
+
+// ---------------------------------------------------------------------------
+// structural edits: meshes appended, the item list replaced
+// ---------------------------------------------------------------------------
+// Both build what changes BESIDE what the scene holds -- new device buffers, new host vectors -- and commit by moving buffers, host
+// copies and the view last, after the device has finished every frame in flight.  Nothing the scene renders from is written before
+// the commit and nothing in the commit can fail, so a failure leaves the scene exactly as it was: there is no way back to take and
+// no "broken" state (check_intact has no flag for these).
+
+// The device copies of the mesh arenas: `before` records of the scene's own buffers (device to device), then the host's records.
+struct MeshBuffers { DevBuf nodes4, tris, trix, attrs, face_slot; };
+template <class T> static int grown_copy(DevBuf* dst, const DevBuf& resident, size_t before, const std::vector<T>& more) {
+    HIP_TRY(dst->reserve(std::max<size_t>((before + more.size()) * sizeof(T), 16)));
+    if (before) HIP_TRY(hipMemcpy(dst->p, resident.p, before * sizeof(T), hipMemcpyDeviceToDevice)); // frames in flight only read the resident records
+    if (!more.empty()) HIP_TRY(hipMemcpy(dst->as<T>() + before, more.data(), more.size() * sizeof(T), hipMemcpyHostToDevice));
+    return RR_OK;
+}
+static int upload_mesh_arenas(const rr_scene* s, const MeshArenas& a, MeshBuffers* b) {
+    RR_TRY(grown_copy(&b->nodes4, s->nodes4, a.nodes4_before, a.nodes4));
+    RR_TRY(grown_copy(&b->tris, s->tris, a.tris_before, a.tris));
+    RR_TRY(grown_copy(&b->trix, s->trix, a.tris_before, a.trix));
+    RR_TRY(grown_copy(&b->attrs, s->attrs, a.tris_before, a.attrs));
+    return grown_copy(&b->face_slot, s->face_slot, a.tris_before, a.face_slot);
+}
+// the commit's half for the meshes
+static void keep_mesh_buffers(rr_scene* s, MeshBuffers& b) noexcept {
+    s->nodes4 = std::move(b.nodes4); s->tris = std::move(b.tris); s->trix = std::move(b.trix); s->attrs = std::move(b.attrs); s->face_slot = std::move(b.face_slot);
+    DSceneView& v = s->view;
+    v.nodes4 = s->nodes4.as<DNode4>(); v.tris = s->tris.as<DTri>(); v.trix = s->trix.as<DTriX>(); v.attrs = s->attrs.as<DTriAttr>(); v.face_slot = s->face_slot.as<uint32_t>();
+}
+
+// The GUI's "add ground plane" (reference src/scene.rs:1564-1578 loads a scene file with a mesh the scene does not hold yet): the
+// meshes are appended to the scene's mesh list, in order, and *first_index is the index of the first.  A mesh's records name
+// nothing outside the mesh (rr_scene_build.h: MeshArenas), so the resident meshes keep their records and the new ones get those a
+// scene created with the longer list gives them; their trees are built for the scene's current share of the traversal stack.
+// Nothing is rendered from them until rr_scene_set_items names them.  Mesh memory never shrinks.
+extern "C" int rr_scene_add_meshes(rr_scene* s, const rr_mesh* meshes, uint32_t n_meshes, uint32_t* first_index) try {
+    if (!s || !first_index || (n_meshes && !meshes)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_add_meshes"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    const uint32_t first = (uint32_t)s->mesh_table.size();
+    RR_TRY(check_meshes(meshes, n_meshes, first));
+    if (n_meshes == 0) { *first_index = first; return RR_OK; }
+    if ((uint64_t)first + n_meshes > 0x7fffffffull) return fail(RR_ERR_UNSUPPORTED, "%u + %u meshes (rr_item::mesh is an int32_t)", first, n_meshes);
+    HIP_TRY(hipSetDevice(s->device));
+    MeshArenas a;
+    a.meshes = s->mesh_table;
+    a.tris_before = s->n_mesh_tris; a.nodes4_before = s->n_nodes4;
+    RR_TRY(append_mesh_records(meshes, n_meshes, s->blas_depth_limit, (uint32_t)s->h_items.size(), &a));
+    std::vector<uint32_t> slot_face;
+    slot_face.reserve(s->h_slot_face.size() + a.slot_face.size());
+    slot_face = s->h_slot_face;
+    slot_face.insert(slot_face.end(), a.slot_face.begin(), a.slot_face.end());
+    std::vector<HostMesh> h_meshes;
+    h_meshes.reserve(s->h_meshes.size() + n_meshes);
+    for (uint32_t i = 0; i < n_meshes; i++) h_meshes.emplace_back(meshes[i]);
+    s->h_meshes.reserve(s->h_meshes.size() + n_meshes); // (capacity only: the commit's moves then cannot fail)
+    MeshBuffers b;
+    RR_TRY(upload_mesh_arenas(s, a, &b));
+    RR_FAULT_POINT("add_meshes.device");
+    HIP_TRY(hipDeviceSynchronize()); // no frame enqueued through rr_render_region_device may still read the arenas that are freed below
+    // ---- commit
+    keep_mesh_buffers(s, b);
+    s->n_nodes4 = a.nodes4_before + a.nodes4.size(); s->n_mesh_tris = a.tris_before + a.tris.size();
+    s->mesh_table.swap(a.meshes);
+    s->h_slot_face.swap(slot_face);
+    for (HostMesh& m : h_meshes) s->h_meshes.push_back(std::move(m));
+    *first_index = first;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_add_meshes")
+
+// The GUI's "delete" of an object, "add ground plane" and "add environment sphere" (reference src/scene.rs:1602-1620, :1564-1578):
+// the whole item list and the whole material list are replaced, together -- items name materials by index, and a host that keeps
+// the material caches behind the full materials moves every cache index when one item comes or goes.  Any item count, any order; an
+// item may name any resident mesh, a material any resident texture; the checks and limits are rr_scene_create's.  Afterwards the
+// handle renders, bit for bit, what a handle created from the flat scene (resident meshes and textures, current lights, these items
+// and materials) renders.
+//   Device work follows what changed: an item whose matrices, mesh and flag word are those of an item of the list before keeps that
+// item's surface spans (host copy) and flat world normals (k_world_normals_edit copies its run into the new arena); only the other
+// mesh items are derived.  The top level is rebuilt (host, items only).
+//   The stack share: the top level's share of the traversal stack depends on the item count (stack_shares), and the per-mesh trees
+// are built and collapsed for the rest.  An edit that changes the share rebuilds every mesh's records from the scene's host copies,
+// as a fresh scene builds them (and derives every item: the leaf order changed); a mesh that no longer fits is RR_ERR_UNSUPPORTED.
+extern "C" int rr_scene_set_items(rr_scene* s, const rr_item* items, uint32_t n_items, const rr_material* materials, uint32_t n_materials) try {
+    if (!s || (n_items && !items) || (n_materials && !materials)) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_scene_set_items"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s)); // (a scene that an earlier edit left mixed has no derived data worth keeping)
+    RR_TRY(check_material_textures(materials, n_materials, s->tex_width.size()));
+    int tlas_depth_limit = 0, blas_depth_limit = 0;
+    if (n_items < (1u << 27)) RR_TRY(stack_shares(n_items, &tlas_depth_limit, &blas_depth_limit)); // the count's limits before an item is read
+    RR_TRY(check_items(items, n_items, materials, n_materials, s->mesh_table.size()));
+    HIP_TRY(hipSetDevice(s->device));
+
+    // ---- the meshes, when their share of the stack changes: every record anew
+    const bool rebuild_meshes = blas_depth_limit != s->blas_depth_limit && !s->h_meshes.empty();
+    MeshArenas arenas;
+    MeshBuffers mesh_buffers;
+    if (rebuild_meshes) {
+        std::vector<rr_mesh> views;
+        views.reserve(s->h_meshes.size());
+        for (const HostMesh& m : s->h_meshes) views.push_back(m.view());
+        RR_TRY(append_mesh_records(views.data(), (uint32_t)views.size(), blas_depth_limit, n_items, &arenas));
+        RR_TRY(upload_mesh_arenas(s, arenas, &mesh_buffers));
+    }
+    const std::vector<MeshDev>& mesh_table = rebuild_meshes ? arenas.meshes : s->mesh_table;
+    const DTri* tris = rebuild_meshes ? mesh_buffers.tris.as<DTri>() : s->tris.as<DTri>();
+
+    // ---- item and material records
+    ItemRecords rec;
+    RR_TRY(build_item_records(items, n_items, materials, mesh_table, s->tex_width, &rec));
+    std::vector<DMaterial> dmat(n_materials);
+    for (uint32_t i = 0; i < n_materials; i++) dmat[i] = make_dmaterial(materials[i], s->tex_width, s->h_textures);
+
+    // ---- keep or derive, per chunk of the new chunk map
+    std::vector<uint2> chunks;
+    std::vector<uint32_t> chunk_item;
+    item_chunk_map(rec.items, &chunks, &chunk_item);
+    const size_t nc = chunks.size();
+    if (nc > 0x7fffffffull) return fail(RR_ERR_UNSUPPORTED, "%zu chunks of instanced triangles", nc);
+    std::vector<int32_t> keep_from;
+    const bool old_spans = s->h_spans.size() == 9 * s->h_items.size();
+    const std::vector<DItem> no_items;
+    plan_item_reuse(rebuild_meshes || !old_spans ? no_items : s->h_items, rec.items, &keep_from);
+    std::vector<uint32_t> chunk_src(nc, RR_CHUNK_DERIVE);
+    std::vector<uint2> derive_chunks;
+    std::vector<uint32_t> derive_item;
+    for (size_t c = 0; c < nc; c++) {
+        const uint32_t i = chunk_item[c];
+        if (rec.items[i].flags & RR_IF_SPHERE) continue; // nothing is derived for a ball
+        if (keep_from[i] >= 0) chunk_src[c] = s->h_items[keep_from[i]].wn_base;
+        else { derive_chunks.push_back(chunks[c]); derive_item.push_back(i); }
+    }
+    const size_t nd = derive_chunks.size();
+
+    // ---- the new device state, beside the old
+    DevBuf d_items, d_materials, d_flat_normals, d_item_chunks, d_spans, d_chunk_src, d_derive_chunks, d_tnodes4, d_item_boxes;
+    HIP_TRY(d_items.upload(rec.items, 16));
+    HIP_TRY(d_materials.upload(dmat, sizeof(DMaterial)));
+    HIP_TRY(d_flat_normals.reserve(std::max<size_t>((size_t)rec.n_flat_normals * sizeof(float4), 16)));
+    HIP_TRY(d_item_chunks.upload(chunks, 16));
+    HIP_TRY(d_spans.reserve(std::max<size_t>(9 * sizeof(double) * nc, 16))); // room for every chunk: a transform update derives them all
+    HIP_TRY(d_chunk_src.upload(chunk_src, 16));
+    HIP_TRY(d_derive_chunks.upload(derive_chunks, 16));
+    std::vector<double> spans;
+    empty_spans(n_items, &spans);
+    for (uint32_t i = 0; i < n_items; i++)
+        if (keep_from[i] >= 0) memcpy(&spans[9 * (size_t)i], &s->h_spans[9 * (size_t)keep_from[i]], 9 * sizeof(double));
+    if (nc) hipLaunchKernelGGL(k_world_normals_edit, dim3((uint32_t)nc), dim3(RR_BLOCK), 0, nullptr, d_items.as<DItem>(), d_item_chunks.as<uint2>(), d_chunk_src.as<uint32_t>(),
+                               tris, s->flat_normals.as<float4>(), d_flat_normals.as<float4>());
+    if (nd) hipLaunchKernelGGL(k_item_spans, dim3((uint32_t)nd), dim3(RR_BLOCK), 0, nullptr, d_items.as<DItem>(), d_derive_chunks.as<uint2>(), tris, d_spans.as<double>());
+    HIP_TRY(hipGetLastError());
+    if (nd) {
+        std::vector<double> part(9 * nd);
+        HIP_TRY(hipMemcpy(part.data(), d_spans.p, 9 * sizeof(double) * nd, hipMemcpyDeviceToHost)); // (waits for both kernels)
+        for (size_t c = 0; c < nd; c++) merge_chunk_span(&part[9 * c], &spans[9 * (size_t)derive_item[c]]);
+    }
+
+    // ---- the top level over the new items, as rr_scene_create builds it
+    TlasTrees trees;
+    const double none[3] = {0.0, 0.0, 0.0};
+    RR_TRY(build_tlas(rec.items, spans, tlas_depth_limit, none, &trees));
+    const uint32_t capacity = std::max<uint32_t>((uint32_t)std::max(trees.corner.size(), trees.surface.size()), n_items ? n_items : 1u);
+    HIP_TRY(d_tnodes4.reserve(2 * (size_t)capacity * sizeof(DNode4)));
+    HIP_TRY(hipMemset(d_tnodes4.p, 0, 2 * (size_t)capacity * sizeof(DNode4)));
+    HIP_TRY(d_item_boxes.reserve(std::max<size_t>(trees.item_boxes.size() * sizeof(float4), 16)));
+    RR_TRY(copy_tlas(trees, d_tnodes4.as<DNode4>(), capacity, d_item_boxes.as<float4>()));
+    std::vector<uint32_t> slot_face;
+    if (rebuild_meshes) slot_face = arenas.slot_face;
+    RR_FAULT_POINT("set_items.device");
+    HIP_TRY(hipDeviceSynchronize()); // the kernels above; and no frame enqueued through rr_render_region_device may still read what is freed below
+
+    // ---- commit: buffers, host copies, the view
+    if (rebuild_meshes) {
+        keep_mesh_buffers(s, mesh_buffers);
+        s->mesh_table.swap(arenas.meshes); s->h_slot_face.swap(slot_face);
+        s->n_nodes4 = arenas.nodes4.size(); s->n_mesh_tris = arenas.tris.size();
+    }
+    s->blas_depth_limit = blas_depth_limit; s->tlas_depth_limit = tlas_depth_limit;
+    s->items = std::move(d_items); s->materials = std::move(d_materials); s->flat_normals = std::move(d_flat_normals);
+    s->item_chunks = std::move(d_item_chunks); s->spans = std::move(d_spans); s->tnodes4 = std::move(d_tnodes4); s->item_boxes = std::move(d_item_boxes);
+    s->h_items.swap(rec.items); s->item_host.swap(rec.item_host); s->h_dmat.swap(dmat); s->h_spans.swap(spans); s->h_chunk_item.swap(chunk_item);
+    s->n_materials = n_materials;
+    s->tlas_node_capacity = capacity;
+    DSceneView& v = s->view;
+    v.items = s->items.as<DItem>(); v.materials = s->materials.as<DMaterial>(); v.flat_normals = s->flat_normals.as<float4>();
+    v.tnodes4 = s->tnodes4.as<DNode4>(); v.item_boxes = s->item_boxes.as<float4>();
+    v.n_items = n_items;
+    v.general_w = rec.general_w ? 1u : 0u;
+    v.any_alpha_occluder = rec.any_alpha_occluder ? 1u : 0u;
+    for (int c = 0; c < 3; c++) s->tlas_floor[c] = trees.reach[c];
+    keep_tlas(s, trees);
+    s->tlas_stale = false;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_set_items")
 
 // ---------------------------------------------------------------------------
 // frame

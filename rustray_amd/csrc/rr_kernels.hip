@@ -1996,6 +1996,33 @@ __global__ __launch_bounds__(RR_BLOCK) void k_world_normals(const DItem* __restr
     }
 }
 
+// The flat world normals of an EDITED item list (rr_scene_set_items), into the new arena: one workgroup per chunk of the new chunk
+// map, as k_world_normals.  An item whose matrices, mesh records and flag word are bit for bit those of an item of the list before
+// (rr_scene_build.h: plan_item_reuse) takes that item's normals -- chunk_src[chunk] = the old item's wn_base: the chunk's run of
+// 2 * triangles float4 is copied from `old` at the same offset behind that base -- and every other chunk (RR_CHUNK_DERIVE) evaluates
+// them as k_world_normals does.  The copied bits are those the evaluation gives: it is a pure function of what was compared.
+// The host bounds both runs: a kept item has the triangle count of the old one, whose run lies inside the old arena.
+#define RR_CHUNK_DERIVE 0xffffffffu // never a wn_base: bases are even
+__global__ __launch_bounds__(RR_BLOCK) void k_world_normals_edit(const DItem* __restrict__ items, const uint2* __restrict__ chunks, const uint32_t* __restrict__ chunk_src,
+                                                                 const DTri* __restrict__ tris, const float4* __restrict__ old, float4* __restrict__ out) {
+    const uint2 ch = chunks[blockIdx.x];
+    const DItem& it = items[ch.x];
+    if (it.flags & RR_IF_SPHERE) return;
+    const uint32_t end = min(it.n_tris, ch.y + RR_ITEM_CHUNK);
+    const uint32_t src = chunk_src[blockIdx.x];
+    if (src != RR_CHUNK_DERIVE) {
+        for (uint32_t k = 2u * ch.y + threadIdx.x; k < 2u * end; k += blockDim.x) out[it.wn_base + k] = old[src + k];
+        return;
+    }
+    for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) {
+        const float4 v3 = tris[it.tri_base + slot].v3;
+        const f3 ng = mk3(v3.x, v3.y, v3.z);
+        const f3 p = to_world_normal(it, ng), m = to_world_normal(it, -ng);
+        out[it.wn_base + 2u * slot] = make_float4(p.x, p.y, p.z, 0.0f);
+        out[it.wn_base + 2u * slot + 1u] = make_float4(m.x, m.y, m.z, 0.0f);
+    }
+}
+
 // The extent of every mesh item's SURFACE along the rows of its transform (rr_api.hip: exact_world_box): one workgroup per item over
 // the vertices of the mesh's triangles, which are resident (DTri), in double -- per row r the minimum and maximum of
 // tr_r.x * p.x + tr_r.y * p.y + tr_r.z * p.z, and the largest |coordinate| per local axis.  Products and sums are IEEE binary64

@@ -88,18 +88,11 @@ static int check_item_transform(uint32_t i, const float* trans, const float* tra
     return RR_OK;
 }
 
-static int validate_scene(const rr_flat_scene* fs) {
-    if (!fs) return fail(RR_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (fs->abi_version != RR_ABI_VERSION) return fail(RR_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", fs->abi_version, RR_ABI_VERSION);
-    if ((fs->n_items && !fs->items) || (fs->n_meshes && !fs->meshes) || (fs->n_materials && !fs->materials) ||
-        (fs->n_textures && !fs->textures) || (fs->n_lights && !fs->lights))
-        return fail(RR_ERR_INVALID_ARGUMENT, "array pointer is NULL with a non-zero count");
-    if (fs->n_items >= (1u << 27)) return fail(RR_ERR_UNSUPPORTED, "%u items (the shadow-ray record keeps the item index in 27 bits)", fs->n_items);
-    int rc = check_textures(fs->textures, fs->n_textures);
-    if (rc == RR_OK) rc = check_material_textures(fs->materials, fs->n_materials, fs->n_textures);
-    if (rc != RR_OK) return rc;
-    for (uint32_t i = 0; i < fs->n_meshes; i++) {
-        const rr_mesh& m = fs->meshes[i];
+// the meshes of a scene, or those appended to one (rr_scene_add_meshes: `first` = the index of meshes[0] in the scene's list)
+static int check_meshes(const rr_mesh* meshes, uint32_t n, uint32_t first) {
+    for (uint32_t j = 0; j < n; j++) {
+        const rr_mesh& m = meshes[j];
+        const uint32_t i = first + j;
         if ((m.n_vertices && !m.positions) || (m.n_triangles && !m.indices)) return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: missing positions/indices", i);
         if ((m.n_uvs && !m.uvs) || (m.n_uv_faces && !m.uv_indices) || (m.n_normals && !m.normals) || (m.n_normal_faces && !m.normal_indices))
             return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: attribute pointer is NULL with a non-zero count", i);
@@ -114,17 +107,37 @@ static int validate_scene(const rr_flat_scene* fs) {
         if (m.n_normals > 0 && m.n_normal_faces > 0 && m.n_normal_faces < m.n_triangles)
             return fail(RR_ERR_INVALID_ARGUMENT, "mesh %u: %u normal faces for %u triangles (the reference panics on this)", i, m.n_normal_faces, m.n_triangles);
     }
-    for (uint32_t i = 0; i < fs->n_items; i++) {
-        const rr_item& it = fs->items[i];
+    return RR_OK;
+}
+// an item list against the material list it names and the number of meshes it may name (rr_scene_create, rr_scene_set_items)
+static int check_items(const rr_item* items, uint32_t n_items, const rr_material* materials, uint32_t n_materials, size_t n_meshes) {
+    if (n_items >= (1u << 27)) return fail(RR_ERR_UNSUPPORTED, "%u items (the shadow-ray record keeps the item index in 27 bits)", n_items);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const rr_item& it = items[i];
         if (it.kind != RR_ITEM_SPHERE && it.kind != RR_ITEM_MESH) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: kind %u", i, it.kind);
-        if (it.material < 0 || it.material >= (int32_t)fs->n_materials || it.material_cache < 0 || it.material_cache >= (int32_t)fs->n_materials)
+        if (it.material < 0 || it.material >= (int32_t)n_materials || it.material_cache < 0 || it.material_cache >= (int32_t)n_materials)
             return fail(RR_ERR_INVALID_ARGUMENT, "item %u: material index out of range", i);
-        if (carries_textures(fs->materials[it.material_cache]))
+        if (carries_textures(materials[it.material_cache]))
             return fail(RR_ERR_INVALID_ARGUMENT, "item %u: material_cache must not carry textures (reference src/shape/mod.rs:769-772)", i);
-        if (it.kind == RR_ITEM_MESH && (it.mesh < 0 || it.mesh >= (int32_t)fs->n_meshes)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: mesh index %d", i, it.mesh);
-        rc = check_item_transform(i, it.trans, it.trans_inv);
+        if (it.kind == RR_ITEM_MESH && (it.mesh < 0 || (size_t)it.mesh >= n_meshes)) return fail(RR_ERR_INVALID_ARGUMENT, "item %u: mesh index %d", i, it.mesh);
+        const int rc = check_item_transform(i, it.trans, it.trans_inv);
         if (rc != RR_OK) return rc;
     }
+    return RR_OK;
+}
+
+static int validate_scene(const rr_flat_scene* fs) {
+    if (!fs) return fail(RR_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (fs->abi_version != RR_ABI_VERSION) return fail(RR_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", fs->abi_version, RR_ABI_VERSION);
+    if ((fs->n_items && !fs->items) || (fs->n_meshes && !fs->meshes) || (fs->n_materials && !fs->materials) ||
+        (fs->n_textures && !fs->textures) || (fs->n_lights && !fs->lights))
+        return fail(RR_ERR_INVALID_ARGUMENT, "array pointer is NULL with a non-zero count");
+    if (fs->n_items >= (1u << 27)) return fail(RR_ERR_UNSUPPORTED, "%u items (the shadow-ray record keeps the item index in 27 bits)", fs->n_items);
+    int rc = check_textures(fs->textures, fs->n_textures);
+    if (rc == RR_OK) rc = check_material_textures(fs->materials, fs->n_materials, fs->n_textures);
+    if (rc == RR_OK) rc = check_meshes(fs->meshes, fs->n_meshes, 0);
+    if (rc == RR_OK) rc = check_items(fs->items, fs->n_items, fs->materials, fs->n_materials, fs->n_meshes);
+    if (rc != RR_OK) return rc;
     return check_lights(fs->lights, fs->n_lights);
 }
 
@@ -246,14 +259,14 @@ static void tri_shading_constants(const float* a, const float* b, const float* c
 // The binary trees of the meshes are independent: built by a few host threads (a scene of 194 meshes / 559 k triangles:
 // 0.4 s on one core).  The workers pull mesh indices from one counter, so threads that could not be started only mean
 // fewer hands; an exception in any worker (the builder's vectors are sized by the caller's meshes) is rethrown here.
-static void build_mesh_trees(const rr_flat_scene* fs, int depth_limit, std::vector<rr::BvhResult>* built, std::vector<char>* built_ok) {
+static void build_mesh_trees(const rr_mesh* meshes, uint32_t n_meshes, int depth_limit, std::vector<rr::BvhResult>* built, std::vector<char>* built_ok) {
     std::atomic<uint32_t> next_mesh{0};
     auto worker = [&]() {
         for (;;) {
             const uint32_t mi = next_mesh.fetch_add(1);
-            if (mi >= fs->n_meshes) break;
+            if (mi >= n_meshes) break;
             RR_FAULT_POINT("scene_create.mesh_worker");
-            const rr_mesh& m = fs->meshes[mi];
+            const rr_mesh& m = meshes[mi];
             const uint32_t nt = m.n_triangles;
             std::vector<float> lo(3 * (size_t)nt), hi(3 * (size_t)nt);
             for (uint32_t f = 0; f < nt; f++)
@@ -268,85 +281,107 @@ static void build_mesh_trees(const rr_flat_scene* fs, int depth_limit, std::vect
         }
     };
     const unsigned hw = std::thread::hardware_concurrency();
-    const uint32_t n_threads = std::min<uint32_t>(std::min<uint32_t>(hw ? hw : 4u, 16u), std::max<uint32_t>(fs->n_meshes, 1u));
+    const uint32_t n_threads = std::min<uint32_t>(std::min<uint32_t>(hw ? hw : 4u, 16u), std::max<uint32_t>(n_meshes, 1u));
     Workers pool;
     for (uint32_t t = 1; t < n_threads; t++)
         if (!pool.spawn(worker)) break;
     pool.run(worker);
     pool.join_and_rethrow();
 }
+static void build_mesh_trees(const rr_flat_scene* fs, int depth_limit, std::vector<rr::BvhResult>* built, std::vector<char>* built_ok) {
+    build_mesh_trees(fs->meshes, fs->n_meshes, depth_limit, built, built_ok);
+}
 
-struct SceneRecords {
-    int tlas_depth_limit = RR_TLAS_MAX_DEPTH, blas_depth_limit = RR_BLAS_MAX_DEPTH; // shares of the traversal stack, see build_scene_records
+// ---- shares of the traversal stack (RR_STACK_DEPTH entries per lane): a top level over n items never needs more
+// than n - 1 pending entries, so a scene of few items leaves more levels to its per-mesh trees (a 320 k-triangle
+// mesh traces 3 % faster with 30 levels than with 24, and 7 % slower with 20)
+// More than 2^RR_TLAS_MAX_DEPTH items (the reference has no limit: `items: Vec<..>`, src/scene.rs:69-83): the top level takes the
+// levels it needs -- ceil(log2 n): the builder falls back to object-median splits where the budget gets tight -- out of the
+// per-mesh trees' share, down to 16 levels for those (8 * 2^16 triangles per mesh at worst); RR_MAX_ITEMS = 2^20 is where that ends.
+// The share depends on the item count alone and changes with it only below 14 and above 2^RR_TLAS_MAX_DEPTH items: an edit of the
+// item list (rr_scene_set_items) that changes it rebuilds the per-mesh trees, which are built and collapsed for their share.
+static int stack_shares(uint32_t n_items, int* tlas_depth_limit, int* blas_depth_limit) {
+    *tlas_depth_limit = (int)std::min<uint32_t>(RR_TLAS_MAX_DEPTH, std::max<uint32_t>(1u, n_items > 1 ? n_items - 1 : 1u));
+    if (n_items > (1u << RR_TLAS_MAX_DEPTH)) {
+        if (n_items > RR_MAX_ITEMS) return fail(RR_ERR_UNSUPPORTED, "%u items (RR_MAX_ITEMS = %u)", n_items, RR_MAX_ITEMS);
+        int need = RR_TLAS_MAX_DEPTH;
+        while ((1u << need) < n_items) need++;
+        *tlas_depth_limit = need;
+    }
+    *blas_depth_limit = RR_STACK_DEPTH - 3 - *tlas_depth_limit;
+    return RR_OK;
+}
+
+// What an item takes from the mesh it names: where the mesh's records sit in the arenas, and what its flag word needs.
+struct MeshDev { uint32_t tri_base, n_tris; uint32_t node_base4; int32_t root4; bool has_normals, degenerate; };
+
+// The meshes' records, one mesh after the other.  A mesh's triangle records start at tri_base (all of tris, trix, attrs, face_slot and
+// slot_face) and its nodes at node_base4; everything inside a mesh's records is relative to those two, so appending meshes leaves
+// the records of the meshes before them as they are.  tris_before / nodes4_before: records that precede the vectors' first element
+// (rr_scene_add_meshes builds the records of the new meshes alone, behind those resident on the device).
+struct MeshArenas {
     std::vector<DNode4> nodes4;     // the meshes' trees, one after the other
     std::vector<DTri> tris;         // per mesh triangle, in leaf order: what k_shade reads
     std::vector<DTriX> trix;        // ... what the triangle test reads
     std::vector<DTriAttr> attrs;    // ... its normals and uvs
     std::vector<uint32_t> face_slot, slot_face; // per mesh triangle: original face index -> leaf-order slot, and back
-    std::vector<DItem> items;
-    std::vector<ItemHost> item_host;
-    std::vector<DMaterial> dmat;
-    std::vector<DLight> dlights;
-    uint32_t n_enabled_lights = 0;
-    std::vector<DTexture> dtex;     // where each image sits in the RGBA8 pool
-    std::vector<uint32_t> tex_width;
-    uint64_t n_flat_normals = 0;    // entries of DSceneView::flat_normals: two per instanced triangle
-    bool general_w = false;         // some item's inverse is not affine
-    bool any_alpha_occluder = false;
+    std::vector<MeshDev> meshes;    // per mesh
+    size_t tris_before = 0, nodes4_before = 0;
 };
 
-// The records of a validated scene (validate_scene).
-static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
-    SceneRecords& s = *out;
-    s = SceneRecords();
-    append_texture_layout(fs->textures, fs->n_textures, &s.dtex, &s.tex_width);
-    s.dmat.resize(fs->n_materials);
-    for (uint32_t i = 0; i < fs->n_materials; i++) s.dmat[i] = make_dmaterial(fs->materials[i], s.tex_width, s.dtex);
-    s.dlights = make_dlights(fs->lights, fs->n_lights, &s.n_enabled_lights);
-
-    // ---- shares of the traversal stack (RR_STACK_DEPTH entries per lane): a top level over n items never needs more
-    // than n - 1 pending entries, so a scene of few items leaves more levels to its per-mesh trees (a 320 k-triangle
-    // mesh traces 3 % faster with 30 levels than with 24, and 7 % slower with 20)
-    s.tlas_depth_limit = (int)std::min<uint32_t>(RR_TLAS_MAX_DEPTH, std::max<uint32_t>(1u, fs->n_items > 1 ? fs->n_items - 1 : 1u));
-    // More than 2^RR_TLAS_MAX_DEPTH items (the reference has no limit: `items: Vec<..>`, src/scene.rs:69-83): the top level takes the
-    // levels it needs -- ceil(log2 n): the builder falls back to object-median splits where the budget gets tight -- out of the
-    // per-mesh trees' share, down to 16 levels for those (8 * 2^16 triangles per mesh at worst); RR_MAX_ITEMS = 2^20 is where that ends.
-    if (fs->n_items > (1u << RR_TLAS_MAX_DEPTH)) {
-        if (fs->n_items > RR_MAX_ITEMS) return fail(RR_ERR_UNSUPPORTED, "%u items (RR_MAX_ITEMS = %u)", fs->n_items, RR_MAX_ITEMS);
-        int need = RR_TLAS_MAX_DEPTH;
-        while ((1u << need) < fs->n_items) need++;
-        s.tlas_depth_limit = need;
+// A scene's own copy of a checked mesh (the caller's arrays are only borrowed for the call): what the per-mesh trees are rebuilt
+// from when an edit of the item list changes their share of the traversal stack.
+struct HostMesh {
+    std::vector<float> positions, uvs, normals;
+    std::vector<uint32_t> indices, uv_indices, normal_indices;
+    explicit HostMesh(const rr_mesh& m)
+        : positions(m.positions, m.positions + 3 * (size_t)m.n_vertices), uvs(m.uvs, m.uvs + 2 * (size_t)m.n_uvs), normals(m.normals, m.normals + 3 * (size_t)m.n_normals),
+          indices(m.indices, m.indices + 3 * (size_t)m.n_triangles), uv_indices(m.uv_indices, m.uv_indices + 3 * (size_t)m.n_uv_faces),
+          normal_indices(m.normal_indices, m.normal_indices + 3 * (size_t)m.n_normal_faces) {}
+    rr_mesh view() const {
+        rr_mesh m;
+        memset(&m, 0, sizeof m);
+        m.positions = positions.data(); m.indices = indices.data(); m.uvs = uvs.data(); m.uv_indices = uv_indices.data();
+        m.normals = normals.data(); m.normal_indices = normal_indices.data();
+        m.n_vertices = (uint32_t)(positions.size() / 3); m.n_triangles = (uint32_t)(indices.size() / 3); m.n_uvs = (uint32_t)(uvs.size() / 2);
+        m.n_uv_faces = (uint32_t)(uv_indices.size() / 3); m.n_normals = (uint32_t)(normals.size() / 3); m.n_normal_faces = (uint32_t)(normal_indices.size() / 3);
+        return m;
     }
-    s.blas_depth_limit = RR_STACK_DEPTH - 3 - s.tlas_depth_limit;
-    // ---- meshes: one BLAS per mesh, shared by every item that names it; the binary trees are built by a few threads, then
-    // collapsed and laid out one after the other
-    struct MeshDev { uint32_t tri_base, n_tris; uint32_t node_base4; int32_t root4; bool has_normals, degenerate; };
-    std::vector<MeshDev> md(fs->n_meshes);
-    std::vector<rr::BvhResult> built(fs->n_meshes);
-    std::vector<char> built_ok(fs->n_meshes, 0);
-    build_mesh_trees(fs, s.blas_depth_limit, &built, &built_ok);
-    for (uint32_t mi = 0; mi < fs->n_meshes; mi++) {
-        const rr_mesh& m = fs->meshes[mi];
+};
+
+// Appends the records of `n` checked meshes (check_meshes) to the arenas: one BLAS per mesh, shared by every item that names it;
+// the binary trees are built by a few threads for `blas_depth_limit` levels, then collapsed and laid out one after the other.
+// `n_items`: for the message of a mesh that does not fit.  On failure the arenas are left with a part of the new records.
+static int append_mesh_records(const rr_mesh* meshes, uint32_t n, int blas_depth_limit, uint32_t n_items, MeshArenas* arenas) {
+    MeshArenas& ar = *arenas;
+    const uint32_t first = (uint32_t)ar.meshes.size();
+    std::vector<rr::BvhResult> built(n);
+    std::vector<char> built_ok(n, 0);
+    build_mesh_trees(meshes, n, blas_depth_limit, &built, &built_ok);
+    for (uint32_t k = 0; k < n; k++) {
+        const rr_mesh& m = meshes[k];
+        const uint32_t mi = first + k;
         uint32_t nt = m.n_triangles;
-        if (!built_ok[mi]) return fail(RR_ERR_UNSUPPORTED, "mesh %u: %u triangles need a deeper tree than the %d levels left beside a top level over %u items",
-                                       mi, nt, s.blas_depth_limit, fs->n_items);
-        rr::BvhResult& r = built[mi];
-        md[mi].tri_base = (uint32_t)s.tris.size();
-        md[mi].n_tris = nt;
-        md[mi].has_normals = m.n_normals > 0 && m.n_normal_faces > 0;
-        md[mi].degenerate = false;
+        if (!built_ok[k]) return fail(RR_ERR_UNSUPPORTED, "mesh %u: %u triangles need a deeper tree than the %d levels left beside a top level over %u items",
+                                      mi, nt, blas_depth_limit, n_items);
+        rr::BvhResult& r = built[k];
+        MeshDev md;
+        md.tri_base = (uint32_t)(ar.tris_before + ar.tris.size());
+        md.n_tris = nt;
+        md.has_normals = m.n_normals > 0 && m.n_normal_faces > 0;
+        md.degenerate = false;
         {
             int pending = 0;
-            md[mi].node_base4 = (uint32_t)s.nodes4.size();
-            md[mi].root4 = rr::collapse_bvh4(r, s.blas_depth_limit, true, &s.nodes4, &pending);
-            if (pending > s.blas_depth_limit) return fail(RR_ERR_UNSUPPORTED, "mesh %u: BVH4 stack bound exceeded", mi);
+            md.node_base4 = (uint32_t)(ar.nodes4_before + ar.nodes4.size());
+            md.root4 = rr::collapse_bvh4(r, blas_depth_limit, true, &ar.nodes4, &pending);
+            if (pending > blas_depth_limit) return fail(RR_ERR_UNSUPPORTED, "mesh %u: BVH4 stack bound exceeded", mi);
         }
-        size_t fs_base = s.face_slot.size();
-        s.face_slot.resize(fs_base + nt);
+        size_t fs_base = ar.face_slot.size();
+        ar.face_slot.resize(fs_base + nt);
         for (uint32_t slot = 0; slot < nt; slot++) {
             uint32_t f = r.order[slot];
-            s.face_slot[fs_base + f] = slot;
-            s.slot_face.push_back(f);
+            ar.face_slot[fs_base + f] = slot;
+            ar.slot_face.push_back(f);
             const uint32_t* ix = m.indices + 3 * (size_t)f;
             const float *a = m.positions + 3 * (size_t)ix[0], *b = m.positions + 3 * (size_t)ix[1], *c = m.positions + 3 * (size_t)ix[2];
             {   // Mesh::get_uv divides by the triangle's area (src/shape/mesh.rs:127-143): a zero (or non-finite) area makes the uv of ANY point
@@ -355,7 +390,7 @@ static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
                 const double u[3] = {(double)a[0] - b[0], (double)a[1] - b[1], (double)a[2] - b[2]}, v[3] = {(double)a[0] - c[0], (double)a[1] - c[1], (double)a[2] - c[2]};
                 const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
                 const double area2 = cx * cx + cy * cy + cz * cz, scale2 = (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-                if (!(area2 > 1e-10 * scale2) || !(area2 > 1e-24) || !std::isfinite(area2)) md[mi].degenerate = true;
+                if (!(area2 > 1e-10 * scale2) || !(area2 > 1e-24) || !std::isfinite(area2)) md.degenerate = true;
             }
             DTri t;
             float fbits; memcpy(&fbits, &f, 4);
@@ -365,18 +400,18 @@ static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
             t.v1 = make_float4(b[0], b[1], b[2], area);
             t.v2 = make_float4(c[0], c[1], c[2], 0.0f);
             t.v3 = make_float4(ng[0], ng[1], ng[2], 0.0f);
-            s.tris.push_back(t);
+            ar.tris.push_back(t);
             {   // the edge vectors parry's test evaluates per ray: ab = b - a, ac = c - a
                 const float ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
                 DTriX x;
                 x.t0 = t.v0;
                 x.t1 = make_float4(ab[0], ab[1], ab[2], ac[0]);
                 x.t2 = make_float4(ac[1], ac[2], 0.0f, 0.0f);
-                s.trix.push_back(x);
+                ar.trix.push_back(x);
             }
             DTriAttr at;
             float n[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, uv[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-            if (md[mi].has_normals)
+            if (md.has_normals)
                 for (int v = 0; v < 3; v++)
                     for (int k = 0; k < 3; k++) n[v][k] = m.normals[3 * (size_t)m.normal_indices[3 * (size_t)f + v] + k];
             uint32_t flags = 0;
@@ -390,15 +425,34 @@ static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
             at.s1 = make_float4(n[1][0], n[1][1], n[1][2], uv[0][1]);
             at.s2 = make_float4(n[2][0], n[2][1], n[2][2], uv[1][0]);
             at.s3 = make_float4(uv[1][1], uv[2][0], uv[2][1], flb);
-            s.attrs.push_back(at);
+            ar.attrs.push_back(at);
         }
+        ar.meshes.push_back(md);
     }
+    static_assert(sizeof(DTriX) == 48 && sizeof(DNode4) == 128 && sizeof(DMaterial) == 240, "layouts the kernels address by byte offset");
+    if (ar.nodes4_before + ar.nodes4.size() >= (1u << 25)) return fail(RR_ERR_UNSUPPORTED, "%zu BVH4 nodes (nodes are addressed with 32-bit byte offsets)", ar.nodes4_before + ar.nodes4.size());
+    if (ar.tris_before + ar.trix.size() >= (1u << 26)) return fail(RR_ERR_UNSUPPORTED, "%zu triangles (addressed with 32-bit byte offsets)", ar.tris_before + ar.trix.size());
+    return RR_OK;
+}
 
-    // ---- items
-    s.items.resize(fs->n_items);
-    s.item_host.resize(fs->n_items);
-    for (uint32_t i = 0; i < fs->n_items; i++) {
-        const rr_item& it = fs->items[i];
+// What depends on the item list: the item records in list order, with their share of the flat-normal arena (wn_base, assigned in
+// item order), what their flag words are rebuilt from, and the two hints of the view.
+struct ItemRecords {
+    std::vector<DItem> items;
+    std::vector<ItemHost> item_host;
+    uint64_t n_flat_normals = 0;    // entries of DSceneView::flat_normals: two per instanced triangle
+    bool general_w = false;         // some item's inverse is not affine
+    bool any_alpha_occluder = false;
+};
+// The records of a checked item list (check_items) over the meshes of `mesh_table`, with the materials the items name.
+static int build_item_records(const rr_item* items, uint32_t n_items, const rr_material* materials, const std::vector<MeshDev>& mesh_table,
+                              const std::vector<uint32_t>& tex_width, ItemRecords* out) {
+    ItemRecords& s = *out;
+    s = ItemRecords();
+    s.items.resize(n_items);
+    s.item_host.resize(n_items);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const rr_item& it = items[i];
         DItem& d = s.items[i];
         memset(&d, 0, sizeof d);
         fill_item_matrices(d, it.trans, it.trans_inv);
@@ -410,20 +464,80 @@ static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
         ItemHost& ih = s.item_host[i];
         ih = ItemHost{it.kind, it.material, it.material_cache, it.visible != 0, it.flip_normals != 0, false, false, it.kind != RR_ITEM_SPHERE ? (int32_t)it.mesh : -1};
         if (it.kind != RR_ITEM_SPHERE) {
-            const MeshDev& m = md[it.mesh];
+            const MeshDev& m = mesh_table[it.mesh];
             d.tri_base = m.tri_base; d.n_tris = m.n_tris;
             d.node_base4 = m.node_base4; d.root4 = m.root4;
             if (s.n_flat_normals + 2ull * m.n_tris > 0xffffffffull) return fail(RR_ERR_UNSUPPORTED, "more than 2^31 instanced triangles");
             d.wn_base = (uint32_t)s.n_flat_normals; s.n_flat_normals += 2ull * m.n_tris;
             ih.mesh_has_normals = m.has_normals; ih.mesh_degenerate = m.degenerate;
         }
-        d.flags = item_flags(ih, fs->materials[it.material_cache], fs->materials[it.material], s.tex_width);
+        d.flags = item_flags(ih, materials[it.material_cache], materials[it.material], tex_width);
         if (d.flags & RR_IF_OCCLUDER_ALPHA_TEX) s.any_alpha_occluder = true;
     }
-    static_assert(sizeof(DTriX) == 48 && sizeof(DNode4) == 128 && sizeof(DMaterial) == 240, "layouts the kernels address by byte offset");
-    if (s.nodes4.size() >= (1u << 25)) return fail(RR_ERR_UNSUPPORTED, "%zu BVH4 nodes (nodes are addressed with 32-bit byte offsets)", s.nodes4.size());
-    if (s.trix.size() >= (1u << 26)) return fail(RR_ERR_UNSUPPORTED, "%zu triangles (addressed with 32-bit byte offsets)", s.trix.size());
     return RR_OK;
+}
+
+// Which items of an edited list keep the derived data -- flat world normals, surface spans -- of an item of the list before: those
+// whose matrices, mesh records and flag word are bit for bit what an old item had (both derive from exactly these; the flag word
+// says ball or mesh).  keep_from[i] = the index of such an old item (the first, where several are alike), or -1 = derive anew.
+static void plan_item_reuse(const std::vector<DItem>& old_items, const std::vector<DItem>& new_items, std::vector<int32_t>* keep_from) {
+    struct Key {
+        float4 m[7]; uint32_t tri_base, n_tris, flags, zero;
+        bool operator<(const Key& o) const { return memcmp(this, &o, sizeof(Key)) < 0; }
+    };
+    static_assert(sizeof(Key) == 7 * 16 + 16, "no padding: keys are compared as bytes");
+    auto key_of = [](const DItem& d) {
+        Key k;
+        k.m[0] = d.inv0; k.m[1] = d.inv1; k.m[2] = d.inv2; k.m[3] = d.inv3; k.m[4] = d.tr0; k.m[5] = d.tr1; k.m[6] = d.tr2;
+        k.tri_base = d.tri_base; k.n_tris = d.n_tris; k.flags = d.flags; k.zero = 0u;
+        return k;
+    };
+    std::vector<std::pair<Key, int32_t>> olds(old_items.size());
+    for (size_t i = 0; i < old_items.size(); i++) olds[i] = std::make_pair(key_of(old_items[i]), (int32_t)i);
+    std::sort(olds.begin(), olds.end());
+    keep_from->assign(new_items.size(), -1);
+    for (size_t i = 0; i < new_items.size(); i++) {
+        const Key k = key_of(new_items[i]);
+        auto it = std::lower_bound(olds.begin(), olds.end(), std::make_pair(k, (int32_t)-1));
+        if (it != olds.end() && memcmp(&it->first, &k, sizeof(Key)) == 0) (*keep_from)[i] = it->second;
+    }
+}
+
+// The chunk map of an item list: (item, first triangle) per workgroup of k_world_normals / k_item_spans, RR_HOST_ITEM_CHUNK triangles
+// each; every item has at least one chunk, and the chunks of one item are consecutive.
+#define RR_HOST_ITEM_CHUNK 8192u // = RR_ITEM_CHUNK of rr_kernels.hip (rr_api.hip asserts it)
+static void item_chunk_map(const std::vector<DItem>& items, std::vector<uint2>* chunks, std::vector<uint32_t>* chunk_item) {
+    chunks->clear(); chunk_item->clear();
+    for (uint32_t i = 0; i < (uint32_t)items.size(); i++) {
+        const uint32_t nt = (items[i].flags & RR_IF_SPHERE) ? 0u : items[i].n_tris;
+        for (uint32_t first = 0; first == 0u || first < nt; first += RR_HOST_ITEM_CHUNK) { chunks->push_back(make_uint2(i, first)); chunk_item->push_back(i); }
+    }
+}
+
+struct SceneRecords : MeshArenas, ItemRecords {
+    int tlas_depth_limit = RR_TLAS_MAX_DEPTH, blas_depth_limit = RR_BLAS_MAX_DEPTH; // shares of the traversal stack (stack_shares)
+    std::vector<DMaterial> dmat;
+    std::vector<DLight> dlights;
+    uint32_t n_enabled_lights = 0;
+    std::vector<DTexture> dtex;     // where each image sits in the RGBA8 pool
+    std::vector<uint32_t> tex_width;
+};
+
+// The records of a validated scene (validate_scene).
+static int build_scene_records(const rr_flat_scene* fs, SceneRecords* out) {
+    SceneRecords& s = *out;
+    s = SceneRecords();
+    append_texture_layout(fs->textures, fs->n_textures, &s.dtex, &s.tex_width);
+    s.dmat.resize(fs->n_materials);
+    for (uint32_t i = 0; i < fs->n_materials; i++) s.dmat[i] = make_dmaterial(fs->materials[i], s.tex_width, s.dtex);
+    s.dlights = make_dlights(fs->lights, fs->n_lights, &s.n_enabled_lights);
+    int rc = stack_shares(fs->n_items, &s.tlas_depth_limit, &s.blas_depth_limit);
+    if (rc == RR_OK) rc = append_mesh_records(fs->meshes, fs->n_meshes, s.blas_depth_limit, fs->n_items, &s);
+    if (rc != RR_OK) return rc;
+    ItemRecords ir;
+    rc = build_item_records(fs->items, fs->n_items, fs->materials, s.meshes, s.tex_width, &ir);
+    static_cast<ItemRecords&>(s) = std::move(ir);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------

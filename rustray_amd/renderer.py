@@ -13,6 +13,7 @@ de-interleave kernel.
 """
 from __future__ import annotations
 
+import copy
 import time
 from typing import Optional
 
@@ -24,6 +25,8 @@ from .flat import FlatScene, make_config, rr_config, rr_region
 
 # the in-place steps of Raytracing.apply_scene, in the order they run; RECREATE stands alone
 IN_PLACE_STEPS = ("add_textures", "update_materials", "update_transforms", "update_item_flags", "update_lights")
+# the steps of a structural plan (plan_scene_update(..., structural=True)): the item list, the material list or the mesh list differ
+STRUCTURAL_STEPS = ("add_textures", "add_meshes", "set_items", "update_lights")
 RECREATE = "recreate"
 
 
@@ -42,12 +45,59 @@ def _same_mesh(a, b) -> bool:
     return a is b or all(_same_array(getattr(a, k), getattr(b, k)) for k in ("positions", "indices", "uvs", "uv_indices", "normals", "normal_indices"))
 
 
-def plan_scene_update(old: FlatScene, new: FlatScene) -> list:
+def _resident_mesh_indices(resident, new_meshes):
+    """Where each of `new_meshes` sits in a mesh list that starts as `resident` and gets the unseen ones appended: meshes are
+    recognised by content (_same_mesh).  Returns (index per new mesh, the meshes to append)."""
+    index, appended = [], []
+    pool = list(resident)
+    for m in new_meshes:
+        at = next((k for k, r in enumerate(pool) if _same_mesh(r, m)), None)
+        if at is None:
+            at = len(pool)
+            pool.append(m)
+            appended.append(m)
+        index.append(at)
+    return index, appended
+
+
+def _structural_plan(old: FlatScene, new: FlatScene, resident_meshes) -> list:
+    """The STRUCTURAL_STEPS that bring a handle created from `old` -- whose device holds `resident_meshes`: old.meshes and whatever was
+    appended since -- to `new`; [RECREATE] when a texture image changed or disappeared (the texture list is positional: materials
+    name images by index) or when a mesh of `old` is in `new` no more, changed or dropped: meshes are never removed from a handle, so
+    a host that edits or drops meshes gets their memory back with a new one.  A mesh that `new` still lists and no item names (the
+    mesh of a deleted item, as Scene.flatten() leaves it) is no edit; meshes in another order are only indexed anew."""
+    if len(new.textures) < len(old.textures) or not all(_same_array(a, b) for a, b in zip(old.textures, new.textures)):
+        return [RECREATE]
+    if not all(any(_same_mesh(m, n) for n in new.meshes) for m in old.meshes):
+        return [RECREATE]
+    steps = []
+    if len(new.textures) > len(old.textures):
+        steps.append("add_textures")
+    if _resident_mesh_indices(resident_meshes, new.meshes)[1]:
+        steps.append("add_meshes")
+    steps.append("set_items")
+    if len(old.lights) != len(new.lights) or any(bytes(a.c_struct()) != bytes(b.c_struct()) for a, b in zip(old.lights, new.lights)):
+        steps.append("update_lights")
+    return steps
+
+
+def plan_scene_update(old: FlatScene, new: FlatScene, structural: bool = False, resident_meshes=None) -> list:
     """What turns a handle created from `old` into one that renders what a handle created from `new` renders, at the least cost
     (Run::restart_rendering after a GUI edit, reference src/run.rs:395-420).  Returns [RECREATE] when the item list (count, kind,
     id, mesh or material indices, radius, local box), a mesh, the material count or an existing texture image differs, or the
     texture list got shorter; else the IN_PLACE_STEPS whose part differs, in their order (empty: nothing to do).  Values are
-    compared as the bits that cross the ABI."""
+    compared as the bits that cross the ABI.
+    structural=True: where the default answers [RECREATE] for the item list, the material count or the mesh list (the GUI's object
+    "delete", "add ground plane", "add environment sphere"), the plan is made of STRUCTURAL_STEPS instead (_structural_plan) and
+    [RECREATE] is left for a resident mesh or texture image that changed or disappeared; `resident_meshes` (default: old.meshes) is
+    what the device holds.  When nothing structural differs the plan is the default one."""
+    plan = _plan_in_place(old, new)
+    if structural and plan == [RECREATE]:
+        return _structural_plan(old, new, old.meshes if resident_meshes is None else resident_meshes)
+    return plan
+
+
+def _plan_in_place(old: FlatScene, new: FlatScene) -> list:
     if len(old.items) != len(new.items) or len(old.materials) != len(new.materials) or len(old.meshes) != len(new.meshes):
         return [RECREATE]
     if len(new.textures) < len(old.textures):
@@ -88,6 +138,7 @@ class Raytracing:
                              ("samples", "monte_carlo", "focal_length", "aperture_size", "fog_density",
                               "max_recursion", "gamma_correction")})
         self.device_scene = capi.DeviceScene(flat_scene, device)
+        self.resident_meshes = list(flat_scene.meshes)   # what the device holds: the meshes of creation and those appended since, in order
 
     def apply_config(self, **kw):
         for k, v in kw.items():
@@ -107,18 +158,31 @@ class Raytracing:
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
         return (int(r.object_id), float(r.distance)) if r.hit else None
 
-    def apply_scene(self, new_flat: FlatScene) -> list:
+    def apply_scene(self, new_flat: FlatScene, structural: bool = False) -> list:
         """The host's restart after a scene edit (Run::restart_rendering, reference src/run.rs:395-420): brings the device scene
         to `new_flat` by the cheapest correct path (plan_scene_update) and returns the plan it carried out.  In-place steps run in
         order; if one fails the scene is created anew from `new_flat` and [RECREATE] is returned.  The new handle is created
-        before the old one is released, so a failed re-create leaves the old scene in place (and raises)."""
-        plan = plan_scene_update(self.flat_scene, new_flat)
+        before the old one is released, so a failed re-create leaves the old scene in place (and raises).
+        structural=True: an edit of the item list, the material list or the mesh list keeps the handle too (STRUCTURAL_STEPS):
+        unseen meshes are appended to the resident ones and the items name meshes by their resident index."""
+        resident = self.resident_meshes
+        plan = plan_scene_update(self.flat_scene, new_flat, structural=structural, resident_meshes=resident)
         if plan != [RECREATE]:
             ds = self.device_scene
             try:
                 for step in plan:
                     if step == "add_textures":
                         ds.add_textures(new_flat.textures[len(self.flat_scene.textures):])
+                    elif step == "add_meshes":
+                        ds.add_meshes(_resident_mesh_indices(resident, new_flat.meshes)[1])
+                    elif step == "set_items":
+                        index, appended = _resident_mesh_indices(resident, new_flat.meshes)
+                        items = [copy.copy(it) for it in new_flat.items]
+                        for it in items:
+                            if it.mesh >= 0:
+                                it.mesh = index[it.mesh]
+                        ds.set_items(items, new_flat.materials)
+                        resident = resident + appended
                     elif step == "update_materials":
                         ds.update_materials(new_flat.materials)
                     elif step == "update_transforms":
@@ -134,6 +198,8 @@ class Raytracing:
             fresh = capi.DeviceScene(new_flat, self.device_scene.device)
             self.device_scene.close()
             self.device_scene = fresh
+            resident = list(new_flat.meshes)
+        self.resident_meshes = resident
         self.flat_scene = new_flat
         return plan
 

@@ -482,6 +482,42 @@ class Scene:
         if index is not None:
             del self.items[index]
 
+    # ---- GUI adds (src/scene.rs:1403-1424, :1564-1578; buttons of src/run.rs:1104-1112) ----
+    def find_bottom_y_pos(self) -> float:
+        """Scene::find_bottom_y_pos (src/scene.rs:1403-1424): the lowest y of the eight corners of every item's local box moved
+        through the item's `trans`, in f32 as nalgebra's Matrix4<f32> * Vector4<f32> accumulates it (column by column);
+        f32::MAX for a scene without items."""
+        min_y = F32(np.finfo(np.float32).max)
+        for it in self.items:
+            lo, hi = self._local_bbox(it)
+            row = np.asarray(it.trans, dtype=F32)[1]
+            for cx in (lo[0], hi[0]):
+                for cy in (lo[1], hi[1]):
+                    for cz in (lo[2], hi[2]):
+                        y = F32(F32(F32(F32(row[0] * F32(cx)) + F32(row[1] * F32(cy))) + F32(row[2] * F32(cz))) + row[3])
+                        if y < min_y:           # f32::min: a NaN corner is ignored
+                            min_y = y
+        return float(min_y)
+
+    def get_by_name(self, name: str) -> Optional[Shape]:
+        """Scene::get_by_name_mut (src/scene.rs:1724-1735): the FIRST item of that name."""
+        for it in self.items:
+            if it.name == name:
+                return it
+        return None
+
+    def add_ground_plane(self) -> List[int]:
+        """Scene::add_ground_plane (src/scene.rs:1564-1573): `scene/floor_reflective.json` (relative to `root`), its plane moved
+        to the scene's lowest point -- measured before the plane is loaded.  Returns the ids of the loaded items."""
+        y_pos = self.find_bottom_y_pos()
+        ids = self.load_json("scene/floor_reflective.json")
+        self.get_by_name("floor reflective").apply_transformation((0.0, y_pos, 0.0), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
+        return ids
+
+    def add_environment_sphere(self) -> List[int]:
+        """Scene::add_environment_sphere (src/scene.rs:1575-1578): `scene/environment.json`, relative to `root`."""
+        return self.load_json("scene/environment.json")
+
     def _local_bbox(self, it: Shape):
         if it.kind == RR_ITEM_SPHERE:
             r = it.radius
@@ -569,6 +605,49 @@ class Scene:
                                  bbox_min=lo, bbox_max=hi, visible=it.visible, flip_normals=it.flip_normals,
                                  name=it.name))
         return fs
+
+
+def scene_from_flat(fs: FlatScene, root: str = ".") -> Scene:
+    """A Scene whose items, meshes, textures and lights are those of a flat scene, with one material per full material the items
+    name (the caches are derived anew by flatten()): what the GUI actions of this module -- delete_object_by_id, add_ground_plane,
+    add_environment_sphere -- run on when the host keeps flat scenes.  Ids continue behind the largest id in use."""
+    sc = Scene(root)
+    sc.name = fs.name or "scene"
+    sc.meshes, sc.textures, sc.lights = list(fs.meshes), list(fs.textures), copy.deepcopy(fs.lights)
+    by_flat: Dict[int, int] = {}
+    for it in fs.items:
+        if it.material not in by_flat:
+            by_flat[it.material] = sc.get_next_id()
+            sc.materials[by_flat[it.material]] = copy.deepcopy(fs.materials[it.material])
+            sc.material_tex_paths[by_flat[it.material]] = {}
+        sh = Shape(it.kind, it.name, by_flat[it.material])
+        sh.id, sh.visible, sh.flip_normals, sh.radius = it.id, it.visible, it.flip_normals, it.radius
+        sh.trans = np.asarray(it.trans, dtype=F32).copy()
+        sh.mesh = it.mesh if it.kind == RR_ITEM_MESH else None
+        sc.items.append(sh)
+    sc.item_id = max([sc.item_id] + [it.id for it in fs.items] + [l.id for l in fs.lights])
+    return sc
+
+
+def flat_scene_after_add(fs: FlatScene, action, root: str = ".") -> FlatScene:
+    """`fs` after a GUI "add" action (Scene.add_ground_plane, Scene.add_environment_sphere; `root` holds their scene files): the
+    loaded items are appended with their materials (full, then cache), meshes and images, and everything `fs` held keeps its index
+    -- the flat scene rr_scene_add_textures / rr_scene_add_meshes / rr_scene_set_items bring a handle of `fs` to."""
+    sc = scene_from_flat(fs, root)
+    n_items, n_tex = len(sc.items), len(sc.textures)
+    action(sc)
+    add = sc.flatten()
+    out = copy.deepcopy(fs)
+    out.textures += [t.copy() for t in add.textures[n_tex:]]          # (material texture indices are list positions: unchanged)
+    for it in add.items[n_items:]:
+        it = copy.deepcopy(it)
+        out.materials += [copy.deepcopy(add.materials[it.material]), copy.deepcopy(add.materials[it.material_cache])]
+        it.material, it.material_cache = len(out.materials) - 2, len(out.materials) - 1
+        if it.kind == RR_ITEM_MESH:
+            out.meshes.append(copy.deepcopy(add.meshes[it.mesh]))
+            it.mesh = len(out.meshes) - 1
+        out.items.append(it)
+    return out
 
 
 def load_scene(paths, width: int, height: int, root: str = ".") -> Scene:
