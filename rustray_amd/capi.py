@@ -34,13 +34,19 @@ class RustrayHipError(RuntimeError):
 
 PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
+# THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
+# Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
+# tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
+LIB_SOURCES = ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+               "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
+
 
 def source_id() -> str:
-    """Identity of the kernel sources next to the library (sha256 over csrc/ + the header, 16 hex digits): what ties a committed
+    """Identity of the kernel sources next to the library (sha256 over LIB_SOURCES + the header, 16 hex digits): what ties a committed
     counter profile (profiles/*_sq_counters.json) to the build a bench run measures."""
     import hashlib
     h = hashlib.sha256()
-    files = [os.path.join(_HERE, "csrc", f) for f in ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h")]
+    files = [os.path.join(_HERE, "csrc", f) for f in LIB_SOURCES]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rustray_hip.h"))
     for f in files:
         with open(f, "rb") as fh:

@@ -1111,11 +1111,9 @@ static int copy_outputs(const rr_frame& host, const rr_frame& dev, size_t np, hi
 struct PassHook { rr_pass_fn fn; void* user; uint32_t min_passes; const rr_frame* host; };
 
 // The ONE place that launches the closest-hit kernel: the frame path (run_level), rr_pick and rr_trace_rays all come through here, so a
-// change to the kernel's arguments cannot leave one caller behind.  (Round 3, scratch run r3c50: a variant whose LEVEL-1 build stored
-// the primary rays through q.r0 / q.r1 aborted the process inside rr_pick -- rr_pick built its own argument list with those pointers
-// NULL, which is right for the kernel at HEAD, which never touches them, and was a write to address 16 * i for that variant.)
-// Every pointer the build in question may touch is checked here, on the host, before the launch; level 1 reads no ray records (the
-// rays are derived from their index), so its queue carries the hit records only.
+// change to the kernel's arguments cannot leave one caller behind.  Every pointer the kernel may touch is checked here, on the host,
+// before the launch: a NULL one would be a write to address 16 * i on the device.  Level 1 reads no ray records (the rays are
+// derived from their index), so its queue carries the hit records only and its ray pointers are passed as NULL.
 static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t* count, uint32_t* head, uint64_t n, const DShadeConst* kc,
                                 const uint32_t* slot_xy, const DPrimary& pr, unsigned long long* counters, hipStream_t st) {
     if (!count || !head || !q.hit || !kc || !counters) return fail(RR_ERR_DEVICE, "internal: closest-hit launch with a NULL argument");

@@ -1,0 +1,165 @@
+// rr_surface.h — layer 4 of the device code: what a hit looks like.  Texture sampling (reference src/raytracing.rs:629-675,
+// src/shape/mod.rs:510-629), the material record in registers, uv of spheres and meshes (src/shape/mesh.rs:105-161, :204-259;
+// src/shape/sphere.rs:69-99), the jitter of a direction on the counter-based generator (src/raytracing.rs:565-626) and
+// fresnel (:535-563).
+//
+// Offers: c_u8_to_f32 (filled by rr_api.hip); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
+// area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel.  No macros.
+// Needs: rr_primitives.h (to_local_point), rr_walk.h (rr_global).
+#pragma once
+#include "rr_walk.h"
+
+__constant__ float c_u8_to_f32[256]; // i / 255.0f, exactly as `(p[0] as f32) / 255.0`
+
+// ---------------------------------------------------------------------------
+// textures: reference src/raytracing.rs:629-675, src/shape/mod.rs:510-629
+// ---------------------------------------------------------------------------
+// `lut`: the u8 -> f32 table (c_u8_to_f32, or a workgroup's copy of it in LDS: four dependent reads per texel)
+RR_DEV float4 texel(const DSceneView& sc, const DTexture& t, uint32_t x, uint32_t y, const float* lut = c_u8_to_f32) {
+    uint32_t p = rr_global(sc.texels)[t.offset + (uint64_t)y * t.width + x];
+    return make_float4(lut[p & 255u], lut[(p >> 8) & 255u], lut[(p >> 16) & 255u], lut[p >> 24]);
+}
+RR_DEV uint32_t tex_wrap(float val, uint32_t bound) {
+    int32_t sb = (int32_t)bound;
+    const int32_t x = as_i32(val * (float)bound);
+    // power-of-two sizes: the mask IS the remainder made non-negative (x % sb, plus sb when negative), without the integer division
+    if ((bound & (bound - 1u)) == 0u) return (uint32_t)x & (bound - 1u);
+    int32_t w = x % sb;
+    return (w < 0) ? (uint32_t)(w + sb) : (uint32_t)w;
+}
+RR_DEV float lerp1(float a, float b, float f) { return a + f * (b - a); } // helper::interpolate
+RR_DEV float4 tex_bilinear(const DSceneView& sc, const DTexture& t, float u, float v, const float* lut = c_u8_to_f32) {
+    uint32_t width = t.width, height = t.height;
+    float x = u * (float)width, y = v * (float)height;
+    if (x < 0.0f) x = x + (float)width;
+    if (y < 0.0f) y = y + (float)height;
+    uint32_t x0 = as_u32(floorf(x)), x1 = as_u32(ceilf(x));
+    uint32_t y0 = as_u32(floorf(y)), y1 = as_u32(ceilf(y));
+    if (x0 >= width) x0 = width - 1u;
+    if (y0 >= height) y0 = height - 1u;
+    if (x1 >= width) x1 = width - 1u;
+    if (y1 >= height) y1 = height - 1u;
+    float fx = x - (float)x0, fy = y - (float)y0;
+    float4 p0 = texel(sc, t, x0, y0, lut), p1 = texel(sc, t, x1, y0, lut), p2 = texel(sc, t, x0, y1, lut), p3 = texel(sc, t, x1, y1, lut);
+    float4 a = make_float4(lerp1(p0.x, p1.x, fx), lerp1(p0.y, p1.y, fx), lerp1(p0.z, p1.z, fx), lerp1(p0.w, p1.w, fx));
+    float4 b = make_float4(lerp1(p2.x, p3.x, fx), lerp1(p2.y, p3.y, fx), lerp1(p2.z, p3.z, fx), lerp1(p2.w, p3.w, fx));
+    return make_float4(lerp1(a.x, b.x, fy), lerp1(a.y, b.y, fy), lerp1(a.z, b.z, fy), lerp1(a.w, b.w, fy));
+}
+// The material of a hit, copied into registers once (four 16-B loads + the flag word): the shading code stores to
+// queues and accumulators between its uses, so fields read through the pointer would be re-fetched one dword at a
+// time, each fetch a dependent round trip.  Texture slots are only looked at when the flag word says they are set.
+struct MatR {
+    f3 ambient, base, specular;
+    float alpha, shininess, reflectivity, refraction_index, normal_map_strength, shadow_softness, roughness;
+    float cos_shadow_softness, cos_roughness; // jitter()'s z_lo for the two constant spreads (host-evaluated, DMaterial)
+    uint32_t flags;
+    const DMaterial* p;
+    const float* lut; // u8 -> f32 table of the workgroup (LDS)
+};
+RR_DEV MatR load_material(const DMaterial* p, const float* lut) {
+    const float4* q = (const float4*)p;
+    const float4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[6]; // q[4], q[5]: the texture slots, read when a slot's flag is set
+    MatR m;
+    m.ambient = mk3(a.x, a.y, a.z); m.alpha = a.w;
+    m.base = mk3(b.x, b.y, b.z); m.shininess = b.w;
+    m.specular = mk3(c.x, c.y, c.z); m.reflectivity = c.w;
+    m.refraction_index = d.x; m.normal_map_strength = d.y; m.shadow_softness = d.z; m.roughness = d.w;
+    m.flags = __float_as_uint(e.x); m.cos_shadow_softness = e.y; m.cos_roughness = e.z; m.p = p; m.lut = lut;
+    return m;
+}
+RR_DEV bool tex_color(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, int slot, float4* out) {
+    if (!(m.flags & (RR_MF_TEX_SLOT0 << slot)) || !has_uv) return false; // slot bit = index >= 0 and width > 0
+    DTexture t; // the slot's descriptor sits in the material record itself (DMaterial::texd): one 16-B load at an address known since the material was
+    { const uint4 q = *(const uint4*)&m.p->texd[slot]; t.offset = (uint64_t)q.x | ((uint64_t)q.y << 32); t.width = q.z; t.height = q.w; }
+    if (m.flags & RR_MF_NEAREST) *out = texel(sc, t, tex_wrap(uv.x, t.width), tex_wrap(uv.y, t.height), m.lut);
+    else *out = tex_bilinear(sc, t, uv.x, uv.y, m.lut);
+    return true;
+}
+// get_tex_color: false = None
+RR_DEV bool tex_color(const DSceneView& sc, const DMaterial& m, bool has_uv, f2 uv, int slot, float4* out) {
+    int ti = m.tex[slot];
+    if (ti < 0 || !has_uv) return false;
+    DTexture t; t.offset = m.texd[slot].offset; t.width = m.texd[slot].width; t.height = m.texd[slot].height;
+    if (t.width == 0u) return false;
+    if (m.flags & RR_MF_NEAREST) *out = texel(sc, t, tex_wrap(uv.x, t.width), tex_wrap(uv.y, t.height));
+    else *out = tex_bilinear(sc, t, uv.x, uv.y);
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// uv / normals: reference src/shape/mesh.rs:105-161, :204-259; src/shape/sphere.rs:69-99
+// ---------------------------------------------------------------------------
+RR_DEV void area_weights(f3 a, f3 b, f3 c, f3 p, float* a1, float* a2, float* a3) {
+    f3 f1 = a - p, f2v = b - p, f3v = c - p;
+    float area = norm3(cross3(a - b, a - c));
+    *a1 = norm3(cross3(f2v, f3v)) / area;
+    *a2 = norm3(cross3(f3v, f1)) / area;
+    *a3 = norm3(cross3(f1, f2v)) / area;
+}
+// the same with the triangle's area from the host (DTri::v1.w: the value of the line `area = ...` above, bit for bit)
+RR_DEV void area_weights(f3 a, f3 b, f3 c, f3 p, float area, float* a1, float* a2, float* a3) {
+    f3 f1 = a - p, f2v = b - p, f3v = c - p;
+    *a1 = norm3(cross3(f2v, f3v)) / area;
+    *a2 = norm3(cross3(f3v, f1)) / area;
+    *a3 = norm3(cross3(f1, f2v)) / area;
+}
+RR_DEV f2 sphere_uv(const DItem& it, f3 hit, bool general_w) {
+    f3 p = to_local_point(it, hit, general_w);
+    float theta = rr_atan2(-(p.z - 0.0f), p.x - 0.0f);
+    float u = (theta + RR_PI_F) / (2.0f * RR_PI_F);
+    float phi = rr_acos((-(p.y - 0.0f)) / it.radius);
+    float v = phi / RR_PI_F;
+    f2 r; r.x = u; r.y = -v; return r;
+}
+RR_DEV f2 mesh_uv(const DSceneView& sc, const DItem& it, uint32_t slot, f3 hit, bool general_w) {
+    f2 r; r.x = 0.0f; r.y = 0.0f;
+    const DTriAttr at = rr_global(sc.attrs)[it.tri_base + slot];
+    if (!(__float_as_uint(at.s3.w) & 1u)) return r;
+    f3 p = to_local_point(it, hit, general_w);
+    const DTri tr = rr_global(sc.tris)[it.tri_base + slot];
+    float a1, a2, a3;
+    area_weights(mk3(tr.v0.x, tr.v0.y, tr.v0.z), mk3(tr.v1.x, tr.v1.y, tr.v1.z), mk3(tr.v2.x, tr.v2.y, tr.v2.z), p, &a1, &a2, &a3);
+    float ux = (at.s0.w * a1 + at.s2.w * a2) + at.s3.y * a3;
+    float uy = (at.s1.w * a1 + at.s3.x * a2) + at.s3.z * a3;
+    r.x = ux; r.y = -uy;
+    return r;
+}
+
+// ---------------------------------------------------------------------------
+// jitter (reference src/raytracing.rs:565-626) on the counter-based generator
+// ---------------------------------------------------------------------------
+struct RngKey { uint32_t seed_lo, seed_hi, pixel, sample, node; };
+// z_lo = rr_cos(spread * RR_PI_F): passed in, because for the two spreads that are material constants (shadow_softness, roughness
+// without a map) the host has evaluated it once per material (DMaterial::cos_*) with the same rr_cos
+RR_DEV f3 jitter(f3 dir, float spread, float z_lo, const RngKey& k, uint32_t stream) {
+    if (spread <= 0.0f) return dir;
+    f3 b3 = normalize3(dir);
+    f3 diff = (rr_abs(b3.x) < 0.5f) ? mk3(1.0f, 0.0f, 0.0f) : mk3(0.0f, 1.0f, 0.0f);
+    f3 b1 = normalize3(cross3(b3, diff));
+    f3 b2 = cross3(b1, b3);
+    if (!(z_lo < 1.0f)) return dir;
+    uint32_t r0, r1;
+    philox4x32_10(k.pixel, k.sample, k.node, stream, k.seed_lo, k.seed_hi, &r0, &r1);
+    float z = uniform_f32(r0, z_lo, 1.0f);
+    float r = sqrtf(1.0f - z * z);
+    float theta = uniform_f32(r1, -RR_PI_F, RR_PI_F);
+    float s, c;
+    rr_sincos(theta, &s, &c);
+    float x = r * c, y = r * s;
+    f3 nd = (x * b1 + y * b2) + z * b3;
+    return normalize3(nd);
+}
+
+// fresnel, reference src/raytracing.rs:535-563 (cos_i = |cos_t| as written there)
+RR_DEV float fresnel(f3 incident, f3 normal, float index) {
+    float i_dot_n = dot3(incident, normal);
+    float eta_i = 1.0f, eta_t = index;
+    if (i_dot_n > 0.0f) { eta_i = eta_t; eta_t = 1.0f; }
+    float sin_t = eta_i / eta_t * sqrtf(rs_max(1.0f - i_dot_n * i_dot_n, 0.0f));
+    if (sin_t > 1.0f) return 1.0f;
+    float cos_t = sqrtf(rs_max(1.0f - sin_t * sin_t, 0.0f));
+    float cos_i = rr_abs(cos_t);
+    float r_s = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
+    float r_p = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
+    return (r_s * r_s + r_p * r_p) / 2.0f;
+}

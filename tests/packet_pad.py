@@ -1,6 +1,6 @@
 """Inert decoys: scenes padded with invisible items, so that the same picture is traced by another walk of the top level.
 
-The packet form of the top level (rr_kernels.hip: beam_candidates, trace_closest_packet, trace_shadow_packet) runs in scenes
+The packet form of the top level (rr_trace.h: beam_candidates, trace_closest_packet, trace_shadow_packet) runs in scenes
 with RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS (17 .. 512) items and falls back to the per-ray walk for a packet with more than 64
 candidates.  An invisible item keeps its place in the top-level boxes and in a packet's candidate list: only item_passes
 rejects it, per candidate.  So decoys change which walk runs and how full a packet is, and never what a ray hits.

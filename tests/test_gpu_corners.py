@@ -74,7 +74,7 @@ def test_non_finite_samples_reach_the_pixel_as_in_the_reference(hip, oracle, nam
       fuzz_568:   several such items, semi-transparent and invisible ones, refraction index below 1;
       fuzz_6601:  a normal map gives a sphere a NaN normal, the SHADOW ray starts at NaN: in the reference every candidate
                   sphere then reports Some(NaN), `in_light = toi > len` is false, and the occluder's alpha map sampled at a
-                  NaN uv under the bilinear filter makes the attenuation NaN (rr_kernels.hip: trace_shadow_nonfinite)."""
+                  NaN uv under the bilinear filter makes the attenuation NaN (rr_trace.h: trace_shadow_nonfinite)."""
     from rustray_amd.flat import FlatScene
     import os
     from tests.helpers import GOLDEN

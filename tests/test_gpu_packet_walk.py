@@ -1,4 +1,4 @@
-"""The packet form of the top level (17 .. 512 items: rr_kernels.hip beam_candidates, trace_closest_packet, trace_shadow_packet and
+"""The packet form of the top level (17 .. 512 items: rr_trace.h beam_candidates, trace_closest_packet, trace_shadow_packet and
 the level-1 fixed shadow slots) against the per-ray walk and the oracle, on the cases built to break it.
 
 The lever is tests/packet_pad.py: invisible decoys move a scene into (or out of) the packet range and fill packets past 64

@@ -250,3 +250,52 @@ def test_bench_waits_for_the_other_ranks_by_pid():
     assert not r["ranks_gone"] and r["still_alive"] == [q.pid] and r["waited_s"] < 2.0
     q.kill(); q.wait()
     assert bench.wait_for_ranks_to_leave([], limit_s=1.0)["ranks_gone"]
+
+
+def _included_sources(csrc, roots=("rr_api.hip", "rr_bvh.cpp")):
+    """The files under `csrc` that the library's two translation units are made of: the roots and everything their `#include "..."`
+    lines reach, as names relative to csrc (an include that leaves csrc -- ../../include/rustray_hip.h -- is not followed)."""
+    import re
+    csrc = os.path.realpath(csrc)
+    seen, todo = set(), [os.path.join(csrc, r) for r in roots]
+    while todo:
+        path = os.path.realpath(todo.pop())
+        if path in seen or os.path.dirname(path) != csrc:
+            continue
+        seen.add(path)
+        with open(path) as fh:
+            for m in re.finditer(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M):
+                todo.append(os.path.join(os.path.dirname(path), m.group(1)))
+    return {os.path.basename(p) for p in seen}
+
+
+def _makefile_csrc_prerequisites(makefile, target="../librustray_hip.so"):
+    """The prerequisites of `target` that live in csrc (no directory part), continuation lines joined."""
+    text = open(makefile).read().replace("\\\n", " ")
+    rules = [l for l in text.splitlines() if l.startswith(target + ":")]
+    assert len(rules) == 1, rules
+    return [p for p in rules[0].split(":", 1)[1].split() if "/" not in p]
+
+
+def test_the_library_has_one_list_of_sources(tmp_path):
+    """capi.LIB_SOURCES -- what source_id() hashes, what the developer tools copy and read -- and the csrc prerequisites of the
+    Makefile rule are exactly the files the library is compiled from: rr_bvh.cpp, rr_api.hip and every file its #include lines reach
+    inside csrc.  A header that is included but not listed would let bench.py quote a counter profile for sources it was not
+    collected on, and leave the library stale after an edit."""
+    import shutil
+    from rustray_amd import capi
+    csrc = os.path.join(os.path.dirname(SCENES), "rustray_amd", "csrc")
+    used = _included_sources(csrc)
+    assert {"rr_api.hip", "rr_bvh.cpp", "rr_kernels.hip", "rr_device.h"} <= used   # the walk over the include lines found the tree
+    assert len(set(capi.LIB_SOURCES)) == len(capi.LIB_SOURCES)
+    assert set(capi.LIB_SOURCES) == used
+    prereq = _makefile_csrc_prerequisites(os.path.join(csrc, "Makefile"))
+    assert len(set(prereq)) == len(prereq) and set(prereq) == used
+    # the comparison notices a header that is included and not listed
+    copy = str(tmp_path / "csrc")
+    shutil.copytree(csrc, copy, ignore=shutil.ignore_patterns("*.so", "*.o"))
+    with open(os.path.join(copy, "rr_unlisted.h"), "w") as fh:
+        fh.write("#pragma once\n")
+    with open(os.path.join(copy, "rr_kernels.hip"), "a") as fh:
+        fh.write('\n#include "rr_unlisted.h"\n')
+    assert _included_sources(copy) - set(capi.LIB_SOURCES) == {"rr_unlisted.h"}

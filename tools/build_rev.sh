@@ -4,7 +4,8 @@ set -e
 rev=$1; name=$2; shift 2
 d=$(mktemp -d)
 mkdir -p $d/rustray_amd/csrc $d/include build/variants
-for f in rr_api.hip rr_kernels.hip rr_frame_plan.h rr_scene_build.h rr_bvh.cpp rr_bvh.h rr_device.h rr_math.h; do git show $rev:rustray_amd/csrc/$f > $d/rustray_amd/csrc/$f; done
+# the files of THAT revision (today's names are wrong for an older one)
+for f in $(git ls-tree --name-only $rev rustray_amd/csrc/); do git show $rev:$f > $d/$f; done
 git show $rev:include/rustray_hip.h > $d/include/rustray_hip.h
 (cd $d/rustray_amd/csrc && hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 "$@" -shared -o $OLDPWD/build/variants/lib_$name.so rr_api.hip rr_bvh.cpp)
 rm -rf $d

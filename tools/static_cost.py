@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool: STATIC vector-instruction count per source line of one kernel (hipcc -S -gline-tables-only, .loc directives).
 Straight-line shading code executes once per hit, so for k_shade the static count is close to the dynamic one per path.
-usage: tools/static_cost.py <mangled kernel prefix, e.g. _Z7k_shadeILb1> [top N]"""
+usage: tools/static_cost.py [<mangled kernel prefix, default _Z7k_shadeILb1> [top N]]"""
 import collections
 import os
 import re
@@ -9,9 +9,13 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from rustray_amd.capi import LIB_SOURCES  # noqa: E402
+
 asm = os.path.join(ROOT, "build", "rr_api_g.s")
 csrc = os.path.join(ROOT, "rustray_amd", "csrc")
-if not os.path.exists(asm) or os.path.getmtime(asm) < max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc)):
+os.makedirs(os.path.dirname(asm), exist_ok=True)
+if not os.path.exists(asm) or os.path.getmtime(asm) < max(os.path.getmtime(os.path.join(csrc, f)) for f in LIB_SOURCES):
     subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-Wno-unused-function",
                            "-gline-tables-only", "-S", "--cuda-device-only", "-o", asm, "rr_api.hip"], cwd=csrc, stderr=subprocess.DEVNULL)
 lines = open(asm).read().splitlines()
@@ -20,7 +24,8 @@ for l in lines:
     m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
     if m:
         files[int(m.group(1))] = (m.group(3) or m.group(2)).split("/")[-1]
-prefix = sys.argv[1]
+TOOLCHAIN = "<toolchain headers>"
+prefix = sys.argv[1] if len(sys.argv) > 1 else "_Z7k_shadeILb1"
 top = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 start = [i for i, l in enumerate(lines) if l.startswith(prefix)][0]
 end = [i for i, l in enumerate(lines) if i > start and l.startswith(".Lfunc_end")][0]
@@ -28,7 +33,8 @@ cur, cnt = None, collections.Counter()
 for l in lines[start:end]:
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
     if m:
-        cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+        f = files.get(int(m.group(1)), "?")
+        cur = (f, int(m.group(2))) if f in LIB_SOURCES else (TOOLCHAIN, 0)  # (the compiler's own headers: __ballot, __shfl, ...)
         continue
     t = l.strip()
     if l.startswith("\t") and t and not t.startswith((".", ";")) and t.split()[0].startswith("v_"):
@@ -38,7 +44,7 @@ byfile = collections.Counter()
 for (f, _), c in cnt.items():
     byfile[f] += c
 print(byfile.most_common(6))
-src = {f: open(os.path.join(csrc, f)).read().splitlines() for f in ("rr_kernels.hip", "rr_math.h")}
+src = {f: open(os.path.join(csrc, f)).read().splitlines() for f in LIB_SOURCES if f in byfile}
 for f in src:
     items = sorted(((l, c) for (ff, l), c in cnt.items() if ff == f), key=lambda x: -x[1])[:top]
     for l, c in sorted(items):

@@ -11,10 +11,13 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from rustray_amd.capi import LIB_SOURCES  # noqa: E402
+
 csrc = os.path.join(ROOT, "rustray_amd", "csrc")
 asm = os.path.join(ROOT, "build", "rr_api.s")
 os.makedirs(os.path.dirname(asm), exist_ok=True)
-if not os.path.exists(asm) or os.path.getmtime(asm) < max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc)):
+if not os.path.exists(asm) or os.path.getmtime(asm) < max(os.path.getmtime(os.path.join(csrc, f)) for f in LIB_SOURCES):
     subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-Wno-unused-function",
                            "-S", "--cuda-device-only", "-o", asm, "rr_api.hip"], cwd=csrc, stderr=subprocess.DEVNULL)
 # cycles per instruction per SIMD at 4 waves per SIMD (s_memtime, slowest wave of the workgroup)
