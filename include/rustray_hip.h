@@ -252,7 +252,11 @@ typedef struct rr_pick_result {
 } rr_pick_result;
 
 /* Per-frame work counters: one "ray" = one Raytracing::trace
- * call (reference src/raytracing.rs:429). */
+ * call (reference src/raytracing.rs:429).
+ * The ms_* fields of the kernels are sums of per-launch durations.  Where level 1 runs in stages on two streams
+ * (rr_scene_overlap_stages) its shade and shadow launches run side by side: their durations overlap in time, each is the
+ * launch's time while it shared the device, and their sum may exceed ms_total (first to last event of the frame on the
+ * caller's stream). */
 typedef struct rr_frame_stats {
     uint64_t primary_rays;
     uint64_t secondary_rays; /* reflection + refraction */
@@ -510,6 +514,10 @@ int rr_post_process_device(uint32_t width, uint32_t height, int cavity, int outl
 
 /* Counters and device timings of the most recent frame on this scene. */
 int rr_scene_last_stats(const rr_scene* scene, rr_frame_stats* out);
+
+/* *out = the number of level-1 stages of the most recent frame on this scene whose shade and shadow launches went to two
+ * streams (summed over the frame's batches); 0 = the frame took the serial schedule.  The frame's bits are the same either way. */
+int rr_scene_overlap_stages(const rr_scene* scene, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_scene_last_stats", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class RustrayHipError(RuntimeError):
@@ -311,6 +311,13 @@ class DeviceScene:
         """rr_scene_set_compat: behaviours of earlier reference binaries (1 = shadows attenuated by the occluder's alpha)."""
         lib().rr_scene_set_compat.argtypes = [C.c_void_p, C.c_uint32]
         _check(lib().rr_scene_set_compat(self._h, C.c_uint32(flags)))
+
+    def overlap_stages(self) -> int:
+        """rr_scene_overlap_stages: level-1 stages of the last frame whose shade and shadow launches ran on two streams (0 = serial)."""
+        n = C.c_uint32(0)
+        lib().rr_scene_overlap_stages.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        _check(lib().rr_scene_overlap_stages(self._h, C.byref(n)))
+        return n.value
 
     def stats(self) -> dict:
         st = rr_frame_stats()

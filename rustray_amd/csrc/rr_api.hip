@@ -227,6 +227,11 @@ struct rr_scene {
     std::vector<hipEvent_t> event_pool;
     hipEvent_t frame_a = nullptr, frame_b = nullptr, count_ready = nullptr;
     hipStream_t last_stream = nullptr; // frame state (queues, accumulators) is shared: frames on different streams are serialised
+    // level 1 in stages (run_level1_stages): this handle's second non-blocking stream, created on first use on the handle's device, and per
+    // shadow-queue buffer the event behind its shade launch (first stream) and behind its shadow launch (second stream)
+    hipStream_t overlap_stream = nullptr;
+    hipEvent_t stage_shaded[3] = {nullptr, nullptr, nullptr}, stage_traced[3] = {nullptr, nullptr, nullptr};
+    uint32_t overlap_stages = 0; // level-1 stages of the last frame that ran on the two streams (rr_scene_overlap_stages)
     uint32_t* h_count = nullptr; // pinned: level sizes read back between depth levels
     rr_tuning tuning{};          // rr_scene_set_tuning; all zero = automatic
     std::vector<uint16_t> table_cache; uint16_t table_samples = 0; // built-in sub-sample table of the last sample count
@@ -240,6 +245,9 @@ struct rr_scene {
         if (count_ready) (void)hipEventDestroy(count_ready);
         if (h_count) (void)hipHostFree(h_count);
         if (multi_stream) (void)hipStreamDestroy(multi_stream);
+        for (hipEvent_t e : stage_shaded) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : stage_traced) if (e) (void)hipEventDestroy(e);
+        if (overlap_stream) (void)hipStreamDestroy(overlap_stream);
         for (void* p : multi_stage) if (p) (void)hipHostFree(p);
     }
 };
@@ -1222,6 +1230,12 @@ static int queue_budget(rr_scene* s, uint64_t* budget) {
     return RR_OK;
 }
 
+// how n hits of level 1 are cut into stages for the two-stream path (rr_frame_plan.h; the knobs: rr_kernels.hip)
+static bool level1_stages_wanted(const rr_scene* s) { return RR_L1_OVERLAP >= 2 || (RR_L1_OVERLAP == 1 && s->tuning.shade_chunk_rays != 0); }
+static Level1Stages level1_stages(const rr_scene* s, uint64_t n) {
+    return plan_level1_stages(Level1StageInputs{n, s->n_enabled_lights, s->tuning.shade_chunk_rays, RR_L1_STAGE_RAYS, RR_L1_BUFFERS});
+}
+
 // the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue (grown, never shrunk)
 static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan) {
     uint64_t budget = 0;
@@ -1234,10 +1248,13 @@ static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_
         s->arena_cap = p.M;
     }
     HIP_TRY(s->hit1.reserve(p.B * 16));
-    if (p.sq_need > s->sq_cap) {
-        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(p.sq_need * 16));
-        HIP_TRY(s->sq_valid.reserve((p.sq_need / RR_WAVE + 1) * 8));
-        s->sq_cap = p.sq_need;
+    // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
+    const Level1Stages sp = level1_stages(s, p.B);
+    const uint64_t sq_need = std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull);
+    if (sq_need > s->sq_cap) {
+        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(sq_need * 16));
+        HIP_TRY(s->sq_valid.reserve(std::max<uint64_t>(sq_need / RR_WAVE + 1, sp.valid_need) * 8));
+        s->sq_cap = sq_need;
     }
     return RR_OK;
 }
@@ -1313,6 +1330,92 @@ static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* lev
     return RR_OK;
 }
 
+// ---- level 1 in stages on two streams ---------------------------------------------------------------------------------------------
+// k_shade<true> is bound by instruction issue and k_trace_shadow<true> by memory latency; one after the other, each has the whole
+// GPU in turn.  Here the hits [s0, s1) are cut into stages (rr_frame_plan.h, plan_level1_stages): stage k is shaded on the frame's
+// stream `st` into shadow buffer k % n_buf, and its shadow rays are traced on the handle's second stream behind an event that
+// follows the shade launch, while `st` already shades stage k + 1.  Shade k + n_buf waits for the event behind shadow k, so a
+// buffer is never rewritten while it is read.  `st` may be the legacy null stream and the second stream is non-blocking: all
+// ordering is by these events.  The frame cannot change: the kernels are the serial loop's, every write they share is an integer
+// atomic, and all else goes to the stage's own buffer.  Which frames take this path, and the sizes of the two grids: RR_L1_OVERLAP
+// and the knobs after it (rr_kernels.hip), with what was measured.
+static int ensure_overlap_stream(rr_scene* s) {
+    if (!s->overlap_stream) HIP_TRY(hipStreamCreateWithFlags(&s->overlap_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 3; b++) {
+        if (!s->stage_shaded[b]) HIP_TRY(hipEventCreateWithFlags(&s->stage_shaded[b], hipEventDisableTiming));
+        if (!s->stage_traced[b]) HIP_TRY(hipEventCreateWithFlags(&s->stage_traced[b], hipEventDisableTiming));
+    }
+    return RR_OK;
+}
+
+// enqueues every stage; on any error the caller (run_level1_stages) drains both streams
+static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
+                                 const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+    rr_scene* s = f.s;
+    const hipStream_t st = f.st, st2 = s->overlap_stream;
+    const uint32_t L = s->n_enabled_lights;
+    unsigned long long* counters = s->counters.as<unsigned long long>();
+    if (sp.sq_need > s->sq_cap || sp.valid_need * 8 > s->sq_valid.bytes) return fail(RR_ERR_DEVICE, "internal: shadow queue smaller than its stage buffers");
+    for (uint32_t k = 0; k < sp.n_stages; k++) {
+        if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        const uint64_t c0 = s0 + sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, s1);
+        const uint32_t b = sp.buffer_of(k);
+        const bool first = k == 0, last = k + 1 == sp.n_stages;
+        const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK;
+        const uint32_t sq_chunk_cap = (uint32_t)(groups * RR_BLOCK); // <= sp.stage: L x this many slots fit the buffer
+        const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * L);
+        const DShadowQueue SQ{f.SQ.s0 + sp.ray_offset[b], f.SQ.s1 + sp.ray_offset[b], f.SQ.s2 + sp.ray_offset[b]};
+        unsigned long long* sq_valid = s->sq_valid.as<unsigned long long>() + sp.valid_offset[b];
+        f.pool.align_line();
+        uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
+        uint32_t* shead = f.pool.take(1); // (zeroed on `st` before the event the second stream waits for)
+        if (!sq_counts || !shead) return counters_exhausted();
+        // the first stage's shade and the last stage's shadow run alone: the serial loop's grids.  In between the two launches share the CUs.
+        const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : groups);
+        const uint64_t shadow_wg = last ? (uint64_t)f.shadow_grid : (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
+        if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->stage_traced[b], 0));
+        {
+            ScopedTimer t(s, st, TK_SHADE, true);
+            hipLaunchKernelGGL(k_shade<true>, dim3((uint32_t)std::min<uint64_t>(groups, shade_wg)), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(),
+                               f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+        }
+        HIP_TRY(hipGetLastError());
+        if (spawns && last) { // the next level's size, behind the last shade stage (run_level waits for it)
+            HIP_TRY(hipMemcpyAsync(s->h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(s->count_ready, st));
+        }
+        HIP_TRY(hipEventRecord(s->stage_shaded[b], st));
+        HIP_TRY(hipStreamWaitEvent(st2, s->stage_shaded[b], 0));
+        {
+            ScopedTimer t(s, st2, TK_SHADOW, true);
+            const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
+            const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, shadow_wg);
+            hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st2, s->view, SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->stage_traced[b], st2));
+    }
+    // the second stream joins `st` here: before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
+    HIP_TRY(hipStreamWaitEvent(st, s->stage_traced[sp.buffer_of(sp.n_stages - 1)], 0));
+    return RR_OK;
+}
+
+// THE one way in and out of the staged path: whatever ends it early (cancel flag, HIP error, counter pool exhausted) leaves both streams idle,
+// so the handle stays usable and the next frame cannot race a straggler.
+static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
+                             const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+    rr_scene* s = f.s;
+    RR_TRY(ensure_overlap_stream(s));
+    const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns);
+    if (rc != RR_OK) {
+        (void)hipStreamSynchronize(s->overlap_stream);
+        (void)hipStreamSynchronize(f.st);
+        return rc;
+    }
+    s->overlap_stages += sp.n_stages;
+    return RR_OK;
+}
+
 // One depth level: rays [base, base + n) of the arena, their count also in the device word `count`.
 // The size of the next level is read back once per slice (4 bytes + stream sync), so launches are sized by the
 // rays that exist and empty levels are never launched.
@@ -1340,7 +1443,11 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         uint32_t* child_count = f.pool.take(1);
         if (!child_count) return counters_exhausted();
         const DRayQueue qout = f.queue_at(child_base);
-        for (uint64_t c0 = s0; c0 < s1; c0 += f.plan.chunk) {
+        // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams
+        const bool staged = level1_stages_wanted(s) && d == 1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->view.n_items >= RR_BEAM_MIN_ITEMS &&
+                            s->view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, s1 - s0).overlapped();
+        if (staged) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns));
+        for (uint64_t c0 = s0; c0 < s1 && !staged; c0 += f.plan.chunk) {
             if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
             const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
             const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);
@@ -1448,6 +1555,7 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     resolve_timers(s); // launches of an earlier frame nobody asked about must not leak into this frame's stats
     memset(&s->stats, 0, sizeof s->stats);
     s->stats_final = false;
+    s->overlap_stages = 0;
     if (npix == 0) return RR_OK;
     RR_TRY(ensure_camera_reach(s, cam, cfg)); // the top level's boxes must be padded for this camera's distance from the origin
     DFrame fr = make_frame(cam, cfg);
@@ -1460,8 +1568,8 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
                CounterPool{s, st}, DPrimary{s->sample_xy.as<uint16_t>(), 0ull, 0u, 1u}, cancel,
-               s->n_cus * RR_SHADOW_WAVES, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
-               s->n_cus * 2 * RR_SHADE_WAVES};
+               s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
+               s->n_cus * RR_SHADE_GRID_WG};
     HIP_TRY(hipEventRecord(s->frame_a, st));
     RR_TRY(run_batches(f, fr, out, frame_layout, hook));
     launch_resolve(f, fr, out, frame_layout);
@@ -1525,6 +1633,12 @@ static int collect_stats_locked(rr_scene* s) {
     resolve_timers(s);
     return read_counters(s, &s->stats);
 }
+extern "C" int rr_scene_overlap_stages(const rr_scene* cs, uint32_t* out) try {
+    if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = cs->overlap_stages;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_overlap_stages")
+
 extern "C" int rr_scene_last_stats(const rr_scene* cs, rr_frame_stats* out) try {
     if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (tl_in_pass == cs) { // inside on_pass of this scene: its frame holds s->mu on this thread and the stream is idle -- the passes so far

@@ -85,6 +85,67 @@ inline FramePlan plan_frame(const FramePlanInputs& in) {
     return FramePlan{total_primary, B, G, M, chunk, sq_need};
 }
 
+// ---- level 1 in stages (rr_api.hip run_level, the two-stream path) -------------------------------------------------------
+// Level 1 of a scene with fixed shadow slots may be cut into STAGES of hits: k_shade<true> of stage k + 1 then runs on one
+// stream while k_trace_shadow<true> of stage k runs on a second one.  Stage k writes its shadow rays into buffer
+// k % n_buf of the shadow-queue allocation, so a buffer is rewritten only after the shadow launch that read it.
+// A buffer holds the fixed slots of one whole stage: (enabled light, hit of the stage), with one validity word per 64 slots.
+// With an explicit rr_tuning::shade_chunk_rays a stage is that chunk.  Otherwise the level is cut into the fewest EQUAL
+// stages of at most `auto_stage` hits (a short last stage would shade beside a full stage of shadow rays and then leave
+// them the GPU at the reduced grid).  The buffer layout depends on the largest stage allowed, the lights and n_buf alone,
+// never on the number of hits: the allocation made for one batch of a frame serves every batch and every slice of it.
+struct Level1StageInputs {
+    uint64_t n;                // hits of the level (or of a slice of it): [0, n)
+    uint32_t n_enabled_lights;
+    uint64_t shade_chunk_rays; // rr_tuning::shade_chunk_rays: 0 = automatic
+    uint64_t auto_stage;       // largest stage when automatic (RR_L1_STAGE_RAYS, rr_kernels.hip)
+    uint32_t n_buf;            // shadow-queue buffers: 2 or 3 (RR_L1_BUFFERS)
+};
+
+struct Level1Stages {
+    uint64_t stage;           // hits per stage, a multiple of RR_BLOCK * RR_SQ_SHARDS; the last stage may hold fewer
+    uint64_t stage_cap;       // the largest stage these inputs allow for any n (>= stage): what a buffer is sized for
+    uint32_t n_stages;        // ceil(n / stage); fewer than 2 = the serial loop
+    uint32_t n_buf;           // 2 or 3
+    uint64_t buf_rays;        // capacity of one buffer in shadow rays: lights * stage_cap
+    uint64_t ray_offset[3];   // buffer b starts at this ray of the shadow-queue allocation
+    uint64_t valid_offset[3]; // ... and at this word of sq_valid
+    uint64_t sq_need;         // shadow-queue rays the buffers need together (0 when serial)
+    uint64_t valid_need;      // sq_valid words they need together (0 when serial)
+    bool overlapped() const { return n_stages >= 2; }
+    uint32_t buffer_of(uint32_t k) const { return k % n_buf; }
+    uint64_t begin_of(uint32_t k) const { return (uint64_t)k * stage; }
+};
+
+static const uint64_t RR_STAGE_UNIT = (uint64_t)RR_BLOCK * RR_SQ_SHARDS;
+
+inline Level1Stages plan_level1_stages(const Level1StageInputs& in) {
+    const uint64_t L = std::max<uint32_t>(in.n_enabled_lights, 1u);
+    const uint32_t n_buf = in.n_buf >= 3 ? 3u : 2u;
+    // all buffers together stay within 16 GB of 48-B rays, as plan_frame's chunk does with many lights
+    const uint64_t by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * L * n_buf)) / RR_STAGE_UNIT * RR_STAGE_UNIT);
+    uint64_t stage = in.shade_chunk_rays ? in.shade_chunk_rays : in.auto_stage;
+    stage = std::max<uint64_t>(65536, stage / RR_STAGE_UNIT * RR_STAGE_UNIT); // whole workgroup iterations of every shard
+    stage = std::min<uint64_t>(stage, by_lights);
+    Level1Stages p{};
+    p.stage_cap = stage;
+    if (!in.shade_chunk_rays && in.n > stage) { // automatic: equal stages
+        const uint64_t n_st = (in.n + stage - 1) / stage;
+        stage = std::max<uint64_t>(65536, ((in.n + n_st - 1) / n_st + RR_STAGE_UNIT - 1) / RR_STAGE_UNIT * RR_STAGE_UNIT); // (<= stage_cap, itself whole units)
+    }
+    p.stage = stage;
+    p.n_stages = (uint32_t)((in.n + stage - 1) / stage);
+    p.n_buf = n_buf;
+    p.buf_rays = L * p.stage_cap;
+    for (uint32_t b = 0; b < 3; b++) {
+        p.ray_offset[b] = b < n_buf ? b * p.buf_rays : 0ull;
+        p.valid_offset[b] = b < n_buf ? b * (p.buf_rays / RR_WAVE) : 0ull;
+    }
+    p.sq_need = p.overlapped() ? n_buf * p.buf_rays : 0ull;
+    p.valid_need = p.overlapped() ? n_buf * (p.buf_rays / RR_WAVE) : 0ull;
+    return p;
+}
+
 // The sample group of the batch [first, first + n): G where the batch holds whole groups of whole sample slices, else 1.
 inline uint32_t batch_group(const FramePlan& p, uint32_t npix, uint64_t first, uint64_t n) {
     return (n % ((uint64_t)npix * p.G) == 0 && first % npix == 0) ? p.G : 1u;

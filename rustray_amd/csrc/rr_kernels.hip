@@ -41,6 +41,40 @@
 #ifndef RR_SHADE_WAVES
 #define RR_SHADE_WAVES 4 // waves per SIMD k_shade is built for
 #endif
+// Launch sizes (host side, rr_api.hip): workgroups per CU of a k_shade and of a k_trace_shadow launch that has the GPU to itself.
+#ifndef RR_SHADE_GRID_WG
+#define RR_SHADE_GRID_WG (2 * RR_SHADE_WAVES) // two rounds of resident workgroups
+#endif
+#ifndef RR_SHADOW_GRID_WG
+#define RR_SHADOW_GRID_WG RR_SHADOW_WAVES // exactly the resident workgroups (RR_STACK_DEPTH KB of LDS stack each)
+#endif
+// Level 1 in stages on two streams (rr_api.hip run_level1_stages, rr_frame_plan.h plan_level1_stages): k_shade<true> of stage
+// k + 1 beside k_trace_shadow<true> of stage k.  All numbers: the contract frame (sponza_syn 1280x720 128 spp), serial loop
+// 19.2 ms on the same box (profiles/r05_level1_share_rates.txt, profiles/r05_dropped.txt, profiles/r05_ab_level1_overlap.txt).
+//   0 = never in stages; 1 = only where the caller asks for shade chunks (rr_tuning::shade_chunk_rays != 0: a stage is that
+//   chunk); 2 = also with automatic tuning, in equal stages of at most RR_L1_STAGE_RAYS.
+#ifndef RR_L1_OVERLAP
+#define RR_L1_OVERLAP 2
+#endif
+#ifndef RR_L1_STAGE_RAYS
+#define RR_L1_STAGE_RAYS (20ull << 20) // largest automatic stage: the contract frame in 6 equal stages 18.6 ms; 8 stages 18.6, 5: 18.6, 4: 18.65, 3: 18.7, 2: 19.0;
+#endif                                 // unequal 8 Mi stages (15) 19.7 ms, 16 Mi (8) 18.75 ms, 32 Mi (4) 18.6 ms
+#ifndef RR_L1_BUFFERS
+#define RR_L1_BUFFERS 3 // shadow-queue buffers the stages rotate through (2 or 3): with 2, 16 Mi stages 19.55 ms against 18.75, 32 Mi 19.1 against 18.6
+#endif
+// Workgroups per CU of the two launches while they share the GPU.  4 workgroups of either kernel are resident on a CU, and a
+// split of those 4 (3 + 1 24.2 ms, 2 + 2 21.3 ms, 1 + 3 24.0 ms; 2 + 2 with 3 buffers and 16 Mi stages 19.6 ms) LOSES to the
+// serial loop: a stage's shade and shadow costs differ by up to 4 x with the part of the picture it covers, so one of the two
+// launches always ends early and leaves its slots idle.  Grids of SEVERAL rounds of workgroups share the CUs instead: a
+// workgroup that ends frees its slot for whichever launch has workgroups waiting, no slot is ever idle, and the mix follows
+// the work.  16 + 16: 18.6 ms; 8 + 8 19.2, 12 + 12 18.65, 24 + 24 18.5 - 18.8, 32 + 32 18.75 - 19.2, 64 + 64 25.1 ms; 16 + 8
+// 19.45, 8 + 16 19.2, 24 + 16 19.05, 16 + 24 19.0 ms; 8 + 4 (the grids of the serial loop) 19.65 ms.
+#ifndef RR_L1_SHADE_WG
+#define RR_L1_SHADE_WG 16 // 0 = one workgroup per 256 hits: k_shade then takes 40 ms instead of 6.3 (the dispatcher starts ~11 workgroups per microsecond)
+#endif
+#ifndef RR_L1_SHADOW_WG
+#define RR_L1_SHADOW_WG 16
+#endif
 #ifndef RR_DYN_FETCH
 #define RR_DYN_FETCH 4 // packets per fetch from the shared head on large launches (more costs locality: +4 % at 8, +10 % at 16)
 #endif
