@@ -329,7 +329,7 @@ void rr_scene_destroy(rr_scene* scene);
  * All or nothing, as rr_scene_update_materials: an update that fails (a non-finite matrix anywhere: RR_ERR_INVALID_ARGUMENT;
  * a device or host failure part-way) leaves the scene rendering exactly what it rendered before the call.  Should putting
  * the old scene back fail as well, the scene is marked broken: every frame call (rr_render and its progressive forms,
- * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
+ * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays, rr_trace_shadow_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
  * until an update of the same kind succeeds. */
 int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float* trans_inv);
 
@@ -341,7 +341,7 @@ int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float*
 int rr_scene_update_materials(rr_scene* scene, const rr_material* materials, uint32_t n_materials);
 
 /* The edits below, like the two above, leave the handle rendering bit for bit what a handle freshly created from the edited flat
- * scene renders (every frame call, rr_pick, rr_trace_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
+ * scene renders (every frame call, rr_pick, rr_trace_rays, rr_trace_shadow_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
  * frames still in flight on the device (rr_render_region_device) before it overwrites what they read, and returns
  * RR_ERR_INVALID_ARGUMENT when called from on_pass of the same scene.  Every handle that takes part in a multi-GPU frame must
  * receive the same edits. */
@@ -500,6 +500,30 @@ typedef struct rr_ray_hit {
     float distance;      /* toi */
 } rr_ray_hit;
 int rr_trace_rays(rr_scene* scene, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out);
+
+/* Shadow queries for a batch of caller-supplied rays: the other form of Raytracing::trace, trace(ray, true, true, depth)
+ * (reference src/raytracing.rs:429-490), followed by the light loop's `in_light = toi > len` (:883-892) -- what a frame asks for
+ * every shadow ray, answered by the walk the frames use.  For ray i let r = trace(ray_i, true, true, depth): the first ITEM in
+ * (bbox distance, item index) order that is hit at all (shadow casters only, balls never solid), with that item's nearest hit.
+ *   max_distance == NULL (a directional light):  occluded = r.is_some()
+ *   max_distance[i] = len (a point or spot light at that distance):  occluded = r.is_some() && !(r.toi > len); a NaN toi (a ball
+ *   whose arithmetic overflows, a non-finite ray) therefore counts as occluded, as in the reference.
+ * When occluded, item_index / object_id / face_id / distance are those of r.  When not, the record is {0, 0xffffffff, 0, 0, 0}:
+ * the item of a ray that is lit BECAUSE its first item lies beyond the distance is not reported.
+ * origins / directions: n * 3 floats (host), directions used as given; max_distance: n floats or NULL, each >= 0 (NaN or a
+ * negative value: RR_ERR_INVALID_ARGUMENT, rr_last_error names the first offending index; +inf means "no limit" for that ray);
+ * `depth`: what the candidate filter sees, 1 .. 255, as for rr_trace_rays.  n == 0 returns RR_OK and touches nothing;
+ * n > 0x7fffff00: RR_ERR_UNSUPPORTED.  The attenuation of a shadow (receiver alpha, alpha maps) needs a receiver and stays
+ * inside the frame. */
+typedef struct rr_shadow_hit {
+    uint32_t occluded;   /* 1 = the reference's `!in_light` for this ray and distance */
+    uint32_t item_index; /* the deciding item; 0xffffffff when not occluded */
+    uint32_t object_id;  /* its ShapeBasics::id; 0 when not occluded */
+    uint32_t face_id;    /* as Shape::intersect reports it (triangle index, + n_triangles for back faces; 0 for spheres) */
+    float distance;      /* toi of the deciding item's nearest hit (may be NaN: an overflowing ball); 0 when not occluded */
+} rr_shadow_hit;         /* 20 bytes */
+int rr_trace_shadow_rays(rr_scene* scene, const float* origins, const float* directions, const float* max_distance,
+                         uint32_t n, uint32_t depth, rr_shadow_hit* out);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

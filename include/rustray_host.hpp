@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -464,6 +465,18 @@ public:
         const rr_camera c = camera.c_struct();
         if (rr_pick(scene->handle(), &c, x, y, &r) != RR_OK || !r.hit) return std::nullopt;
         return std::make_pair(r.object_id, r.distance);
+    }
+
+    // Raytracing::trace(ray, true, true, depth) with `in_light = toi > len` (src/raytracing.rs:429-490, :883-892): the occluder of one
+    // shadow ray as (item index, face id, toi), or None when the ray is lit.  max_distance: the distance to a point or spot light;
+    // infinity (the default) = a directional light, no limit.
+    struct ShadowHit { uint32_t item_index, face_id; float toi; };
+    std::optional<ShadowHit> trace_shadow(const Vec3& origin, const Vec3& dir, uint32_t depth,
+                                          float max_distance = std::numeric_limits<float>::infinity()) const {
+        const float o[3] = {origin.x, origin.y, origin.z}, d[3] = {dir.x, dir.y, dir.z};
+        rr_shadow_hit r;
+        if (rr_trace_shadow_rays(scene->handle(), o, d, &max_distance, 1, depth, &r) != RR_OK || !r.occluded) return std::nullopt;
+        return ShadowHit{r.item_index, r.face_id, r.distance};
     }
 
     // The GUI's light and item edits (reference src/run.rs:1294-1409, :1464-1489), applied to the resident scene before the next

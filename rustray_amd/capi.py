@@ -23,7 +23,12 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+
+
+class rr_shadow_hit(C.Structure):
+    """include/rustray_hip.h: one record of rr_trace_shadow_rays."""
+    _fields_ = [("occluded", C.c_uint32), ("item_index", C.c_uint32), ("object_id", C.c_uint32), ("face_id", C.c_uint32), ("distance", C.c_float)]
 
 
 class RustrayHipError(RuntimeError):
@@ -97,6 +102,8 @@ def lib():
                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rr_pick.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_int, C.c_int, C.POINTER(rr_pick_result)]
         L.rr_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        if hasattr(L, "rr_trace_shadow_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
+            L.rr_trace_shadow_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_shadow_hit)]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -303,6 +310,24 @@ class DeviceScene:
         out = np.zeros((n, 5), np.uint32)
         _check(lib().rr_trace_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(depth), out.ctypes.data_as(C.c_void_p)))
         return out[:, 0].astype(bool), out[:, 1].astype(np.int32), out[:, 3].copy(), out[:, 4].copy().view(np.float32)
+
+    def trace_shadow_rays(self, origins, dirs, max_distance=None, depth: int = 2):
+        """rr_trace_shadow_rays: shadow queries of caller-supplied rays, `max_distance` per ray or None for no limit ->
+        (occluded bool, item int32 (-1 when not occluded), face uint32, toi float32) arrays."""
+        o = np.ascontiguousarray(origins, np.float32); d = np.ascontiguousarray(dirs, np.float32)
+        n = len(o)
+        if len(d) != n:
+            raise ValueError(f"{n} origins, {len(d)} directions")
+        lim, lim_p = None, None
+        if max_distance is not None:
+            lim = np.ascontiguousarray(max_distance, np.float32).reshape(-1)
+            if len(lim) != n:
+                raise ValueError(f"{n} rays, {len(lim)} distances")
+            lim_p = lim.ctypes.data_as(C.c_void_p)
+        out = (rr_shadow_hit * max(n, 1))()
+        _check(lib().rr_trace_shadow_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), lim_p, C.c_uint32(n), C.c_uint32(depth), out))
+        a = np.frombuffer(out, np.uint32, 5 * n).reshape(n, 5)
+        return a[:, 0].astype(bool), a[:, 1].astype(np.int32), a[:, 3].copy(), a[:, 4].copy().view(np.float32)
 
     def set_profiling(self, on: bool):
         self.set_tuning(kernel_timing=1 if on else 0)

@@ -140,6 +140,18 @@ extern "C" int rh_set_items(void* h, const rr_item* items, uint32_t n_items, con
     return ((RhScene*)h)->scene->set_items(std::vector<rr_item>(items, items + n_items), std::vector<rr_material>(materials, materials + n_materials));
 }
 
+// Raytracing::trace_shadow for n rays, one call each: out[4 i ..] = (occluded, item index, face id, toi bits); max_distance NULL = the default (no limit)
+extern "C" int rh_trace_shadow(void* h, const float* origins, const float* dirs, const float* max_distance, uint32_t n, uint32_t depth, uint32_t* out) {
+    const Raytracing& rt = *((RhScene*)h)->rt;
+    for (uint32_t i = 0; i < n; i++) {
+        const Vec3 o{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]}, d{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
+        const auto r = max_distance ? rt.trace_shadow(o, d, depth, max_distance[i]) : rt.trace_shadow(o, d, depth);
+        out[4 * i] = r ? 1u : 0u; out[4 * i + 1] = r ? r->item_index : 0xffffffffu; out[4 * i + 2] = r ? r->face_id : 0u; out[4 * i + 3] = 0u;
+        if (r) std::memcpy(&out[4 * i + 3], &r->toi, 4);
+    }
+    return 0;
+}
+
 // one whole frame (min_passes passes) into the caller's buffers
 extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
                                const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,

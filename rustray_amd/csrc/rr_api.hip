@@ -70,7 +70,7 @@ static int guard_fail(const char* fn) noexcept {
 // Test-only fault injection (tests/test_abi.py, tests/test_gpu_guard.py, tests/test_gpu_scene_edits.py): rr_test_fault("point", kind, skip)
 // arms ONE fault; the (skip + 1)-th crossing of RR_FAULT_POINT("point") on any thread throws std::bad_alloc (kind 1), std::runtime_error (2)
 // or an int (3) and disarms.  Kinds 4, 5, 6 throw as 1, 2, 3 and stay armed: every later crossing throws too, until the next call of
-// rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host,
+// rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host, trace_shadow_rays.host,
 // update_transforms.host (before the update writes anything), update_transforms.derive (after the items' upload),
 // update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
 // and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload), update_lights.device (after the light
@@ -1139,6 +1139,18 @@ static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t
     return RR_OK;
 }
 
+// The ONE place that launches the shadow-query kernel (rr_trace_shadow_rays), as launch_trace_closest: every pointer the kernel
+// touches is checked here, on the host.  r0 / r1: n ray records each; out: n result records; head: the zeroed fetch word.
+static int launch_query_shadow(rr_scene* s, const float4* r0, const float4* r1, uint64_t n, uint32_t* head, uint4* out, hipStream_t st) {
+    if (!r0 || !r1 || !head || !out) return fail(RR_ERR_DEVICE, "internal: shadow-query launch with a NULL argument");
+    if (!s->view.items || !s->view.tnodes4 || !s->view.item_boxes) return fail(RR_ERR_DEVICE, "internal: shadow-query launch on a scene without a top level");
+    if (n == 0 || n > 0x7fffff00ull) return fail(RR_ERR_DEVICE, "internal: shadow-query launch of %llu rays", (unsigned long long)n);
+    const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * RR_SHADOW_GRID_WG);
+    hipLaunchKernelGGL(k_query_shadow, dim3(grid), dim3(RR_BLOCK), 0, st, s->view, r0, r1, (uint32_t)n, head, out);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
 // ---- the steps of a frame (render_region_locked)
 
 // the region's accumulator slots on the device (slot -> pixel, slot -> output index), uploaded when the region changes
@@ -2116,6 +2128,61 @@ extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* dir
     }
     return RR_OK;
 } RR_GUARD_END("rr_trace_rays")
+
+// Shadow queries for caller-supplied rays: Raytracing::trace(ray, true, true, depth) and `in_light = toi > len`
+// (reference src/raytracing.rs:429-490, :883-892) through the walk the frames' shadow kernel uses (k_query_shadow).
+extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const float* directions, const float* max_distance,
+                                    uint32_t n, uint32_t depth, rr_shadow_hit* out) try {
+    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
+    if (n == 0) return RR_OK;
+    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
+    if (max_distance)
+        for (uint32_t i = 0; i < n; i++)
+            if (!(max_distance[i] >= 0.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", i, (double)max_distance[i]);
+    RR_TRY(not_in_pass(s, "rr_trace_shadow_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("trace_shadow_rays.host");
+    std::vector<float4> r0(n), r1(n);
+    {
+        double need[3] = {0.0, 0.0, 0.0};
+        for (uint32_t i = 0; i < n; i++)
+            for (int c = 0; c < 3; c++) {
+                const double a = std::fabs((double)origins[3 * (size_t)i + c]) * 1.001;
+                if (std::isfinite(a)) need[c] = std::max(need[c], a);
+            }
+        RR_TRY(ensure_tlas_reach(s, need));
+    }
+    float depth_bits;
+    memcpy(&depth_bits, &depth, 4);
+    for (uint32_t i = 0; i < n; i++) {
+        // no limit (NULL, +inf): what k_shade passes for a directional light
+        const float limit = max_distance ? std::min(max_distance[i], RR_FLT_MAX) : RR_FLT_MAX;
+        r0[i] = make_float4(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], limit);
+        r1[i] = make_float4(directions[3 * (size_t)i], directions[3 * (size_t)i + 1], directions[3 * (size_t)i + 2], depth_bits);
+    }
+    DevBuf b0, b1, bh, bc;
+    HIP_TRY(b0.reserve((size_t)n * 16)); HIP_TRY(b1.reserve((size_t)n * 16)); HIP_TRY(bh.reserve((size_t)n * 16));
+    HIP_TRY(bc.reserve(64)); // [0] the fetch head
+    HIP_TRY(hipMemcpy(b0.p, r0.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b1.p, r1.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(bc.p, 0, 64));
+    RR_TRY(launch_query_shadow(s, b0.as<float4>(), b1.as<float4>(), n, bc.as<uint32_t>(), bh.as<uint4>(), nullptr));
+    std::vector<uint4> hits(n);
+    HIP_TRY(hipMemcpy(hits.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        rr_shadow_hit& h = out[i];
+        memset(&h, 0, sizeof h);
+        h.item_index = 0xffffffffu;
+        if (hits[i].w != 0u && hits[i].y < s->h_items.size()) {
+            h.occluded = 1u; h.item_index = hits[i].y; h.object_id = s->h_items[hits[i].y].id; h.face_id = hits[i].z;
+            memcpy(&h.distance, &hits[i].x, 4);
+        }
+    }
+    return RR_OK;
+} RR_GUARD_END("rr_trace_shadow_rays")
 
 // ---------------------------------------------------------------------------
 // device arithmetic probe (tests/test_device_math.py): runs rr_math.h functions on the GPU

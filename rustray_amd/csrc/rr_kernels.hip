@@ -876,6 +876,56 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
 }
 
 // ---------------------------------------------------------------------------
+// kernel 4b: shadow QUERIES for caller-supplied rays (rr_trace_shadow_rays): Raytracing::trace(ray, true, true, depth) and
+// `in_light = toi > len` (reference src/raytracing.rs:429-490, :883-892), with no receiver and no colour
+// ---------------------------------------------------------------------------
+// Ray i: r0[i] = (origin, limit), r1[i] = (direction, depth as bits).  Packet p = rays 64 p .. 64 p + 63 in the caller's order.
+// The decision is k_trace_shadow's own: trace_shadow_packet where the scene has a packet form and the packet is coherent,
+// trace_shadow_ray otherwise.  out[i] = (toi bits, deciding item, reference face id, occluded) -- (0, 0xffffffff, 0, 0) for a ray
+// that is lit -- written once per ray with one 16-byte vector store.
+__global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_query_shadow(DSceneView sc, const float4* __restrict__ r0, const float4* __restrict__ r1, uint32_t n,
+                                                           uint32_t* head, uint4* __restrict__ out) {
+    __shared__ int s_stack[RR_STACK_DEPTH * RR_BLOCK];
+    RR_UTIL_KIND(2u)
+    const uint32_t n_packets = (n + RR_WAVE - 1) / RR_WAVE;
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1);
+    // the packet stream of k_trace_shadow's dense queue: half dealt round-robin without an atomic, half pulled from the shared head
+    const uint32_t n_waves = gridDim.x * (RR_BLOCK / RR_WAVE);
+    uint32_t blk = blockIdx.x;
+    if ((gridDim.x & 7u) == 0u) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const uint32_t wave_id = blk * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE;
+    const uint32_t rounds = (uint32_t)(((unsigned long long)n_packets * RR_SHADOW_STATIC_NUM / RR_SHADOW_STATIC_DEN) / n_waves);
+    const uint32_t n_static = rounds * n_waves;
+    uint32_t round = 0, dyn_next = 0, dyn_left = 0;
+    const uint32_t dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
+    for (;;) {
+        uint32_t p;
+        if (round < rounds) { p = round * n_waves + wave_id; round++; }
+        else {
+            if (dyn_left == 0u) {
+                uint32_t f = 0;
+                if (lane == 0) f = atomicAdd(head, dyn_k);
+                dyn_next = n_static + __shfl(f, 0); dyn_left = dyn_k;
+            }
+            p = dyn_next++; dyn_left--;
+        }
+        if (p >= n_packets) break; // wave-uniform
+        const uint32_t i = p * RR_WAVE + lane;
+        const bool live = i < n;
+        // lanes past the end repeat the packet's first ray (the packet form runs with all lanes) and write nothing
+        const uint32_t j = live ? i : p * RR_WAVE;
+        const float4 s0 = r0[j], s1 = r1[j];
+        const f3 o = mk3(s0.x, s0.y, s0.z), d = mk3(s1.x, s1.y, s1.z);
+        const uint32_t depth = __float_as_uint(s1.w);
+        ShadowSel sel;
+        if (!trace_shadow_packet(sc, o, d, depth, s0.w, s_stack, &sel)) trace_shadow_ray(sc, o, d, depth, s0.w, s_stack, &sel);
+        const bool occluded = sel.found && sel.within;
+        if (occluded) shadow_deciding_hit(sc, o, d, s_stack, &sel);
+        if (live) out[i] = occluded ? make_uint4(__float_as_uint(sel.t), (uint32_t)sel.item, sel.face, 1u) : make_uint4(0u, 0xffffffffu, 0u, 0u);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // ray binning between depth levels (counting sort of a level's rays by origin cell x direction octant)
 //
 // OFF by default (rr_tuning::bin_min_rays).  A deeper level's rays can be re-ordered before they are traced so that a

@@ -4,7 +4,7 @@
 // arithmetic does with non-finite rays and NaN hits.
 //
 // Offers: Closest, ray_nonfinite, trace_closest_ray, trace_closest_packet, trace_closest_nonfinite, trace_closest_ordered;
-// ShadowSel, trace_shadow_ray, trace_shadow_packet (trace_shadow_nonfinite through trace_shadow_ray).  The per-item functions
+// ShadowSel, trace_shadow_ray, trace_shadow_packet (trace_shadow_nonfinite through trace_shadow_ray), shadow_deciding_hit.  The per-item functions
 // (aabb_cast2, item_passes, closest_item*, shadow_item, shadow_blocker_item, trace_shadow_blockers) and the packet top level
 // (wave_min_f32 / wave_max_f32 / wave_min_u32, beam_axis, beam_candidates, beam_next) are this layer's own.
 // No macro leaves this file: RR_TOI_SLACK and RR_SHADOW_BOUND are its own, and the node step of rr_walk.h, whose last user
@@ -349,6 +349,21 @@ RR_DEV void shadow_item(const DSceneView& sc, int idx, f3 o, f3 d, uint32_t dept
         }
     }
     if (any) { sel->found = true; sel->key = key; sel->item = idx; sel->within = within; sel->t = t; sel->face = face; }
+}
+
+// What a shadow QUERY reports beyond the decision (k_query_shadow): the deciding item's nearest hit, as the reference's
+// Shape::intersect returns it for the item its loop stopped at.  shadow_item knows it for balls and for alpha-mapped occluders;
+// any other mesh was walked for ANY hit (blas_any), so that one item is walked once more for its nearest one: toi, and the
+// reference's face id as shadow_item forms it.  For an occluded ray only (sel->found && sel->within); a NaN ball (a blocker of
+// trace_shadow_blockers, a non-finite ray) is a ball and keeps t = NaN, face = 0.
+RR_DEV void shadow_deciding_hit(const DSceneView& sc, f3 o, f3 d, int* s_stack, ShadowSel* sel) {
+    const DItem& it = rr_global(sc.items)[sel->item];
+    const uint32_t flags = it.flags;
+    if ((flags & (RR_IF_SPHERE | RR_IF_OCCLUDER_ALPHA_TEX)) != 0u || it.n_tris == 0u) return;
+    const LRay lr = inverse_ray(it, o, d, sc.general_w != 0u);
+    TriBest tb;
+    blas_closest<false>(sc, it, lr, RR_FLT_MAX, s_stack, 0, &tb);
+    if (tb.found) { sel->t = tb.t; sel->face = tb.face + ((tb.side & 2u) ? it.n_tris : 0u); }
 }
 
 // Second pass of a shadow query: is there an item whose box starts BEYOND the light (skipped above), ordered before

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool: rr_trace_rays against the oracle's Raytracing::trace on random rays into random scenes, a third of them
 with special values in some components (NaN, infinite origin components, +-0, denormals): found / item / face id / toi must agree bit
-for bit (a NaN toi as NaN).  usage (on the GPU box): python tools/fuzz_rays.py [scenes] [first seed] [far]"""
+for bit (a NaN toi as NaN).  usage (on the GPU box): python tools/fuzz_rays.py [scenes] [first seed] [far] [--shadow]
+--shadow: rr_trace_shadow_rays instead, with a random non-negative limit per ray (a tenth of them +inf), against the oracle's
+trace(ray, true, true, depth): occluded = found and not toi > limit, and an occluded ray's item / face id / toi are the oracle's."""
 import sys, time
 sys.path.insert(0, '.')
 import torch  # noqa
@@ -10,6 +12,9 @@ from oracle import binding as ob
 from rustray_amd import capi
 from tools.fuzz_parity import rich_scene, far_and_scaled
 
+SHADOW = "--shadow" in sys.argv
+if SHADOW:
+    sys.argv.remove("--shadow")
 n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 first = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 FAR = len(sys.argv) > 3 and sys.argv[3] == "far"   # the scenes moved far from the origin and scaled (fuzz_parity's far mode)
@@ -38,9 +43,21 @@ for seed in range(first, first + n_scenes):
             if rng.random() < 0.5: o[i, int(rng.integers(0, 3))] = SPECIAL_O[int(rng.integers(0, len(SPECIAL_O)))]
             else: d[i, int(rng.integers(0, 3))] = SPECIAL_D[int(rng.integers(0, len(SPECIAL_D)))]
     depth = int(rng.integers(1, 3))
-    with capi.DeviceScene(fs, 0) as ds:
-        g = ds.trace_rays(o, d, depth)
-    r = ob.trace_rays(fs.c_struct(), o, d, depth, brute_force=True)   # (the all-items form: DESIGN D10)
+    if SHADOW:
+        # limits around the distances that occur (0 .. a few scene sizes, log-uniform), exact zero and +inf among them
+        lim = (np.exp(rng.uniform(np.log(1e-3), np.log(30.0), n)) * scale).astype(np.float32)
+        lim[rng.random(n) < 0.1] = np.inf
+        lim[rng.random(n) < 0.05] = 0.0
+        with capi.DeviceScene(fs, 0) as ds:
+            g = ds.trace_shadow_rays(o, d, lim, depth)
+        f, it, fc, t = ob.trace_rays(fs.c_struct(), o, d, depth, for_shadow=True, brute_force=True)
+        with np.errstate(invalid="ignore"):
+            f = f & ~(t > lim)
+        r = (f, np.where(f, it, -1), fc, t)
+    else:
+        with capi.DeviceScene(fs, 0) as ds:
+            g = ds.trace_rays(o, d, depth)
+        r = ob.trace_rays(fs.c_struct(), o, d, depth, brute_force=True)   # (the all-items form: DESIGN D10)
     both = g[0] & r[0]
     same_toi = (g[3].view(np.uint32) == r[3].view(np.uint32)) | (np.isnan(g[3]) & np.isnan(r[3]))
     diff = (g[0] != r[0]) | (both & ((g[1] != r[1]) | (g[2] != r[2]) | ~same_toi))

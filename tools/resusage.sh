@@ -17,6 +17,6 @@ import subprocess
 for n, r in rows.items():
     try: d = subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.split('(')[0].replace('void ', '')
     except Exception: d = n
-    if not d.startswith('k_trace') and not d.startswith('k_shade') and '-a' not in sys.argv: continue
+    if not d.startswith(('k_trace', 'k_shade', 'k_query')) and '-a' not in sys.argv: continue
     print(f\"{d:28s} sgpr {r.get('TotalSGPRs','?'):>4s} vgpr {r.get('VGPRs','?'):>4s} agpr {r.get('AGPRs','?'):>3s} sspill {r.get('SGPRs Spill','?'):>4s} vspill {r.get('VGPRs Spill','?'):>3s} scratch {r.get('ScratchSize [bytes/lane]','?'):>4s} occ {r.get('Occupancy [waves/SIMD]','?'):>2s} lds {r.get('LDS Size [bytes/block]','?')}\")
 "
