@@ -39,7 +39,8 @@ extern "C" {
  * 3: rr_frame_stats carries the level-1 share of the shade and shadow kernels too (one roofline per kernel build in bench.py).
  * rr_scene_update_lights, rr_scene_update_item_flags and rr_scene_add_textures came later without a change of any struct, so the
  * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them).
- * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well. */
+ * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well.
+ * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own). */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -329,7 +330,7 @@ void rr_scene_destroy(rr_scene* scene);
  * All or nothing, as rr_scene_update_materials: an update that fails (a non-finite matrix anywhere: RR_ERR_INVALID_ARGUMENT;
  * a device or host failure part-way) leaves the scene rendering exactly what it rendered before the call.  Should putting
  * the old scene back fail as well, the scene is marked broken: every frame call (rr_render and its progressive forms,
- * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays, rr_trace_shadow_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
+ * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
  * until an update of the same kind succeeds. */
 int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float* trans_inv);
 
@@ -341,7 +342,7 @@ int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float*
 int rr_scene_update_materials(rr_scene* scene, const rr_material* materials, uint32_t n_materials);
 
 /* The edits below, like the two above, leave the handle rendering bit for bit what a handle freshly created from the edited flat
- * scene renders (every frame call, rr_pick, rr_trace_rays, rr_trace_shadow_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
+ * scene renders (every frame call, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
  * frames still in flight on the device (rr_render_region_device) before it overwrites what they read, and returns
  * RR_ERR_INVALID_ARGUMENT when called from on_pass of the same scene.  Every handle that takes part in a multi-GPU frame must
  * receive the same edits. */
@@ -524,6 +525,40 @@ typedef struct rr_shadow_hit {
 } rr_shadow_hit;         /* 20 bytes */
 int rr_trace_shadow_rays(rr_scene* scene, const float* origins, const float* directions, const float* max_distance,
                          uint32_t n, uint32_t depth, rr_shadow_hit* out);
+
+/* Radiance queries for caller-supplied rays: Raytracing::get_color_depth_normal_id(scene, ray, 1) (reference
+ * src/raytracing.rs:720-998), the function `render` calls per sample -- for any camera the host can write down: a panorama, an
+ * orthographic view, light probes, lightmap texels, its own lens model.  The call is a frame without the pinhole / DOF camera.
+ *   Grouping: ray j * rays_per_result + k is sample k of result j; out[j] is the mean over result j's rays.  The direction is
+ *   normalised on entry, as the reference does (:723); recursion, lights, shadows, fog, textures and the candidate filter of
+ *   depth 1 are exactly a frame's.
+ *   Config: seed, monte_carlo, max_recursion (at most RR_MAX_RECURSION, else RR_ERR_UNSUPPORTED), fog_density and fog_color are
+ *   used.  samples (replaced by rays_per_result), focal_length and aperture_size (the caller made the rays) and gamma_correction
+ *   (the output is linear) are ignored.
+ *   RNG: the generator behind `jitter` is keyed (seed, pixel, sample, path node, stream); here pixel = stream_ids ? stream_ids[j] : j
+ *   and sample = k.  Rays of frame pixel y * width + x given with that id draw what the frame draws for that pixel.
+ *   Outputs: what a frame resolves for a pixel whose samples are these rays, BEFORE its min(., 1): color[c] = (float)(fixed-point
+ *   sum * 2^-24) / (float)rays_per_result, NaN or +-inf where a ray's term was (as the reference's f32 sum); depth, normal and
+ *   object_id exactly a frame's.  A ray that misses contributes colour 0, depth 0, normal 0, id 0.
+ *   Limits: rays_per_result 1 .. RR_MAX_SAMPLES_WITH_TABLE (0: RR_ERR_INVALID_ARGUMENT, more: RR_ERR_UNSUPPORTED); n_results == 0
+ *   returns RR_OK and touches nothing; n_results > 0x7fffff00: RR_ERR_UNSUPPORTED.  The total ray count may exceed 2^32: the
+ *   call works in batches sized by rr_tuning::queue_budget_bytes.  Device memory: 64 B per result for the call's accumulators
+ *   (RR_ERR_OUT_OF_MEMORY when they do not fit; the handle stays usable).
+ *   Non-finite rays are accepted and answered as a frame answers them.  cancel: polled between device launches; a cancelled call
+ *   returns RR_ERR_CANCELLED and the contents of `out` are then unspecified.
+ * A frame call: it takes the scene's lock, returns RR_ERR_INVALID_ARGUMENT from on_pass of the same scene and RR_ERR_DEVICE on a
+ * broken scene, and rr_scene_last_stats afterwards reports its counters (primary_rays = the number of rays).
+ * origins / directions: n_results * rays_per_result * 3 floats (host); stream_ids: n_results ids, or NULL (result j uses j).
+ * Device-buffer and stream forms are out of scope. */
+typedef struct rr_radiance {
+    float color[3];     /* mean over the result's rays of get_color_depth_normal_id(..).0: LINEAR, no min(., 1), no gamma */
+    float depth;        /* mean of .1 */
+    float normal[3];    /* the mean of .2, normalised (NaN when every ray missed: 0/0, as a frame's pixel) */
+    uint32_t object_id; /* .3 as a frame reports it for a pixel whose samples are these rays */
+} rr_radiance;          /* 32 bytes */
+int rr_shade_rays(rr_scene* scene, const rr_config* config, const float* origins, const float* directions,
+                  uint32_t n_results, uint32_t rays_per_result, const uint32_t* stream_ids,
+                  rr_radiance* out, const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

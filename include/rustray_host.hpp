@@ -479,6 +479,25 @@ public:
         return ShadowHit{r.item_index, r.face_id, r.distance};
     }
 
+    // Raytracing::get_color_depth_normal_id(scene, ray, 1) (src/raytracing.rs:720-998) for a span of rays of the host's own, with this
+    // handle's config (seed, monte_carlo, max_recursion, fog): (colour, depth, normal, object id) per ray when rays_per_result is 1,
+    // or the mean over every rays_per_result consecutive rays.  The colour is LINEAR (no min(., 1), no gamma).  An empty vector =
+    // refused or failed (rr_last_error() says why).  stream_ids: the RNG pixel id per result, or nullptr = the result's index.
+    struct Ray { Vec3 origin, dir; };
+    std::vector<rr_radiance> shade_rays(const Ray* rays, size_t n_rays, uint32_t rays_per_result = 1, const uint32_t* stream_ids = nullptr) const {
+        std::vector<rr_radiance> out;
+        if (rays_per_result == 0 || n_rays == 0 || n_rays % rays_per_result != 0 || n_rays / rays_per_result > 0x7fffff00u) return out;
+        std::vector<float> o(3 * n_rays), d(3 * n_rays);
+        for (size_t i = 0; i < n_rays; i++) {
+            o[3 * i] = rays[i].origin.x; o[3 * i + 1] = rays[i].origin.y; o[3 * i + 2] = rays[i].origin.z;
+            d[3 * i] = rays[i].dir.x; d[3 * i + 1] = rays[i].dir.y; d[3 * i + 2] = rays[i].dir.z;
+        }
+        const rr_config c = config.c_struct();
+        out.resize(n_rays / rays_per_result);
+        if (rr_shade_rays(scene->handle(), &c, o.data(), d.data(), (uint32_t)out.size(), rays_per_result, stream_ids, out.data(), nullptr) != RR_OK) out.clear();
+        return out;
+    }
+
     // The GUI's light and item edits (reference src/run.rs:1294-1409, :1464-1489), applied to the resident scene before the next
     // RendererManager::restart: `lights` is the edited Scene::lights, the flags are ShapeBasics::visible / flip_normals per item.
     // false = refused or failed (scene->error() says why); the scene then renders what it rendered before.

@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 
 from .flat import (RR_ABI_VERSION, FlatScene, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_light, rr_material, rr_pick_result,
-                   rr_region, rr_texture, rr_tuning)
+                   rr_radiance, rr_region, rr_texture, rr_tuning)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUSTRAY_HIP_LIB") or os.path.join(_HERE, "librustray_hip.so")  # override: developer A/B builds
@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -104,6 +104,8 @@ def lib():
         L.rr_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         if hasattr(L, "rr_trace_shadow_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
             L.rr_trace_shadow_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_shadow_hit)]
+        if hasattr(L, "rr_shade_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
+            L.rr_shade_rays.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -328,6 +330,29 @@ class DeviceScene:
         _check(lib().rr_trace_shadow_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), lim_p, C.c_uint32(n), C.c_uint32(depth), out))
         a = np.frombuffer(out, np.uint32, 5 * n).reshape(n, 5)
         return a[:, 0].astype(bool), a[:, 1].astype(np.int32), a[:, 3].copy(), a[:, 4].copy().view(np.float32)
+
+    def shade_rays(self, origins, dirs, cfg: rr_config, rays_per_result: int = 1, stream_ids=None, cancel=None):
+        """rr_shade_rays: get_color_depth_normal_id(scene, ray, 1) of caller-supplied rays, averaged over each result's
+        `rays_per_result` consecutive rays -> dict(color (n, 3) float32 LINEAR, depth (n,), normal (n, 3), object_id (n,) uint32).
+        stream_ids: the RNG pixel id of every result (default: its index); cancel: a ctypes c_int polled between launches."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if len(d) != len(o):
+            raise ValueError(f"{len(o)} origins, {len(d)} directions")
+        rpr = int(rays_per_result)
+        if rpr < 1 or len(o) % rpr:
+            raise ValueError(f"{len(o)} rays are not whole results of {rpr} rays")
+        n = len(o) // rpr
+        ids, ids_p = None, None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError(f"{n} results, {len(ids)} stream ids")
+            ids_p = ids.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        _check(lib().rr_shade_rays(self._h, C.byref(cfg), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(rpr), ids_p,
+                                   out.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
 
     def set_profiling(self, on: bool):
         self.set_tuning(kernel_timing=1 if on else 0)

@@ -152,6 +152,22 @@ extern "C" int rh_trace_shadow(void* h, const float* origins, const float* dirs,
     return 0;
 }
 
+// Raytracing::shade_rays over n_rays rays with the given config: out = n_rays / rays_per_result records of 8 words (rr_radiance)
+extern "C" int rh_shade_rays(void* h, const rr_config* cfg, const float* origins, const float* dirs, uint32_t n_rays, uint32_t rays_per_result,
+                             const uint32_t* stream_ids, rr_radiance* out) {
+    Raytracing& rt = *((RhScene*)h)->rt;
+    rt.config = RaytracingConfig();
+    rt.config.apply(from_c(cfg));
+    rt.config.seed = cfg->seed;
+    std::vector<Raytracing::Ray> rays(n_rays);
+    for (uint32_t i = 0; i < n_rays; i++)
+        rays[i] = Raytracing::Ray{Vec3{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]}, Vec3{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]}};
+    const std::vector<rr_radiance> r = rt.shade_rays(rays.data(), rays.size(), rays_per_result, stream_ids);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    return 0;
+}
+
 // one whole frame (min_passes passes) into the caller's buffers
 extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
                                const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,

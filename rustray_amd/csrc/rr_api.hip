@@ -17,6 +17,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,7 +71,7 @@ static int guard_fail(const char* fn) noexcept {
 // Test-only fault injection (tests/test_abi.py, tests/test_gpu_guard.py, tests/test_gpu_scene_edits.py): rr_test_fault("point", kind, skip)
 // arms ONE fault; the (skip + 1)-th crossing of RR_FAULT_POINT("point") on any thread throws std::bad_alloc (kind 1), std::runtime_error (2)
 // or an int (3) and disarms.  Kinds 4, 5, 6 throw as 1, 2, 3 and stay armed: every later crossing throws too, until the next call of
-// rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host, trace_shadow_rays.host,
+// rr_test_fault (a failed update whose rollback crosses the same point fails as well).  Points: scene_create.host, scene_create.mesh_worker, render_multi.worker, trace_rays.host, trace_shadow_rays.host, shade_rays.host,
 // update_transforms.host (before the update writes anything), update_transforms.derive (after the items' upload),
 // update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
 // and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload), update_lights.device (after the light
@@ -1215,7 +1216,7 @@ static int upload_sample_table(rr_scene* s, uint16_t samples, const uint16_t* sa
 }
 
 // zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all
-static int reset_accumulators(rr_scene* s, uint32_t npix, const rr_frame* out, hipStream_t st, DAccum* acc) {
+static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool want_depth, bool want_id, hipStream_t st, DAccum* acc) {
     HIP_TRY(s->acc_rgb.reserve((size_t)npix * 24));
     HIP_TRY(s->acc_normal.reserve((size_t)npix * 24));
     HIP_TRY(s->acc_depth.reserve((size_t)npix * 8));
@@ -1227,8 +1228,8 @@ static int reset_accumulators(rr_scene* s, uint32_t npix, const rr_frame* out, h
     HIP_TRY(hipMemsetAsync(s->acc_depth.p, 0, (size_t)npix * 8, st));
     HIP_TRY(hipMemsetAsync(s->acc_id.p, 0, (size_t)npix * 4, st));
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, RR_CNT_WORDS * 8, st));
-    *acc = DAccum{s->acc_rgb.as<long long>(), out->normal ? s->acc_normal.as<long long>() : nullptr, out->depth ? s->acc_depth.as<long long>() : nullptr,
-                  out->object_id ? s->acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->acc_flags.as<uint32_t>()};
+    *acc = DAccum{s->acc_rgb.as<long long>(), want_normal ? s->acc_normal.as<long long>() : nullptr, want_depth ? s->acc_depth.as<long long>() : nullptr,
+                  want_id ? s->acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->acc_flags.as<uint32_t>()};
     return RR_OK;
 }
 
@@ -1312,6 +1313,8 @@ struct FrameRun {
     DPrimary pr; // the batch being traced: depth level 1
     const volatile int* cancel;
     int shadow_grid, shade_grid_max;
+    const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, or the stream ids of rr_shade_rays
+    bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->arena[0].as<float4>() + base, s->arena[1].as<float4>() + base, s->arena[2].as<uint2>() + base, s->arena[3].as<uint4>() + base};
     }
@@ -1432,21 +1435,25 @@ static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueu
 // The size of the next level is read back once per slice (4 bytes + stream sync), so launches are sized by the
 // rays that exist and empty levels are never launched.
 // depth level 1 = the batch's primary rays [pr.first, pr.first + pr.n): only hit records (hit1); its children start the arena
+// SEEDED (rr_shade_rays): depth level 1 is n ray records at the front of the arena like any deeper level -- arena hit records, the
+// <false> builds of the three kernels (a path is a root where its record says depth 1 and carries the id bit), children behind
+// the level, the dense shadow queue, no stages.
 static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_t* count) {
     rr_scene* s = f.s;
     const hipStream_t st = f.st;
     const uint32_t L = s->n_enabled_lights;
     unsigned long long* counters = s->counters.as<unsigned long long>();
+    const bool l1 = d == 1 && !f.seeded; // the level-1 builds: rays derived from their index
     DRayQueue qin = f.queue_at(base);
-    if (d == 1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->hit1.as<uint4>(); }
+    if (l1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->hit1.as<uint4>(); }
     {
         uint32_t* head = f.pool.take(1);
         if (!head) return counters_exhausted();
-        ScopedTimer t(s, st, TK_CLOSEST, d == 1);
-        RR_TRY(launch_trace_closest(s, d == 1, qin, count, head, n, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, counters, st));
+        ScopedTimer t(s, st, TK_CLOSEST, l1);
+        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->shade_const.as<DShadeConst>(), f.slot_xy, f.pr, counters, st));
     }
     const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
-    const uint64_t M = f.plan.M, child_base = d == 1 ? 0 : base + n;
+    const uint64_t M = f.plan.M, child_base = l1 ? 0 : base + n;
     const uint64_t slice = level_slice(M, child_base, n, d, f.R);
     if (slice == 0) return fail(RR_ERR_OUT_OF_MEMORY, "ray arena of %llu rays is too small for depth level %u", (unsigned long long)M, d);
     if (slice < n) s->stats.sliced_levels++;
@@ -1456,7 +1463,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         if (!child_count) return counters_exhausted();
         const DRayQueue qout = f.queue_at(child_base);
         // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams
-        const bool staged = level1_stages_wanted(s) && d == 1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->view.n_items >= RR_BEAM_MIN_ITEMS &&
+        const bool staged = level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->view.n_items >= RR_BEAM_MIN_ITEMS &&
                             s->view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, s1 - s0).overlapped();
         if (staged) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns));
         for (uint64_t c0 = s0; c0 < s1 && !staged; c0 += f.plan.chunk) {
@@ -1467,7 +1474,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
             // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
             // take the dense queue of the deeper levels, which has no such limit
-            const bool sq_fixed = d == 1 && s->view.n_items >= RR_BEAM_MIN_ITEMS && s->view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
+            const bool sq_fixed = l1 && s->view.n_items >= RR_BEAM_MIN_ITEMS && s->view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
             const uint32_t sq_chunk_cap = sq_fixed ? (uint32_t)(((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK) * RR_BLOCK) : 0u;
             unsigned long long* sq_valid = s->sq_valid.as<unsigned long long>();
             // deeper levels: shadow sub-queues, a shard gets the packets with (packet % RR_SQ_SHARDS == shard), L rays per hit at most
@@ -1478,10 +1485,10 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             uint32_t* shead = f.pool.take(1);
             if (!sq_counts || !shead) return counters_exhausted();
             {
-                ScopedTimer t(s, st, TK_SHADE, d == 1);
-                if (d == 1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, qin, count,
+                ScopedTimer t(s, st, TK_SHADE, l1);
+                if (l1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
                                                (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
-                else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), s->region_xy.as<uint32_t>(), f.pr, qin, count,
+                else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
                                         (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
             }
             // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
@@ -1575,13 +1582,14 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     RR_TRY(upload_shade_const(s, fr, st));
     RR_TRY(upload_sample_table(s, cfg->samples, sample_xy, st));
     DAccum acc;
-    RR_TRY(reset_accumulators(s, npix, out, st, &acc));
+    RR_TRY(reset_accumulators(s, npix, out->normal != nullptr, out->depth != nullptr, out->object_id != nullptr, st, &acc));
     FramePlan plan;
     RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
                CounterPool{s, st}, DPrimary{s->sample_xy.as<uint16_t>(), 0ull, 0u, 1u}, cancel,
                s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                s->n_cus * RR_SHADE_GRID_WG};
+    f.slot_xy = s->region_xy.as<uint32_t>();
     HIP_TRY(hipEventRecord(s->frame_a, st));
     RR_TRY(run_batches(f, fr, out, frame_layout, hook));
     launch_resolve(f, fr, out, frame_layout);
@@ -2183,6 +2191,139 @@ extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const flo
     }
     return RR_OK;
 } RR_GUARD_END("rr_trace_shadow_rays")
+
+// ---------------------------------------------------------------------------
+// radiance queries: Raytracing::get_color_depth_normal_id(scene, ray, 1) (reference src/raytracing.rs:720-998) for caller-supplied
+// rays -- what `render` calls per sample, without its pinhole / DOF camera.  The caller's rays are seeded as depth level 1 of the
+// frame's own level walk (k_seed_rays, run_level's seeded form), batch by batch (rr_frame_plan.h plan_ray_batches), into one
+// accumulator slot per result; k_resolve_rays returns what k_resolve computes before its clamp.
+// Per-frame state of the handle this call shares with rr_render, and why the next frame does not see it: the shade constants, the
+// accumulators and the counter pool are rewritten by every frame; the arena and the shadow queue only grow (a frame takes what it
+// needs from the front); the slot -> pixel map is this call's own buffer (FrameRun::slot_xy), so the cached region map, the
+// sub-sample table and arena_factor are not touched at all.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(rr_radiance) == 32 && offsetof(rr_radiance, depth) == 12 && offsetof(rr_radiance, normal) == 16 && offsetof(rr_radiance, object_id) == 28,
+              "k_resolve_rays writes rr_radiance as two float4");
+static const uint32_t RESOLVE_RAYS_CHUNK = 1u << 22; // results per k_resolve_rays launch and read-back (128 MB of staging at most)
+
+// the batches of one call, in order; whatever ends them early leaves the stream idle (shade_rays_locked)
+static int run_ray_batches(FrameRun& f, const float* origins, const float* directions, uint32_t rays_per_result, float* d_origins, float* d_dirs) {
+    rr_scene* s = f.s;
+    const uint64_t B = f.plan.B, n_rays = f.plan.total_primary;
+    for (uint64_t first = 0; first < n_rays; first += B) {
+        if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rays - first);
+        RR_TRY(f.pool.start_batch());
+        uint32_t* level1_count = f.pool.take(1);
+        if (!level1_count) return counters_exhausted();
+        // (stream-ordered: the copies wait for the kernels of the batch before, which read the same staging buffers)
+        HIP_TRY(hipMemcpyAsync(d_origins, origins + 3ull * first, 12ull * nb, hipMemcpyHostToDevice, f.st));
+        HIP_TRY(hipMemcpyAsync(d_dirs, directions + 3ull * first, 12ull * nb, hipMemcpyHostToDevice, f.st));
+        hipLaunchKernelGGL(k_seed_rays, dim3((nb + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, d_origins, d_dirs, (unsigned long long)first, nb, rays_per_result,
+                           f.queue_at(0), level1_count, s->counters.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        s->stats.batches++;
+        RR_TRY(run_level(f, 1, 0, nb, level1_count));
+        HIP_TRY(hipGetLastError());
+        if (f.cancel && first + B < n_rays) HIP_TRY(hipStreamSynchronize(f.st)); // only a caller that can cancel needs the host to keep pace
+    }
+    return RR_OK;
+}
+
+static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                             const uint32_t* stream_ids, rr_radiance* out, const volatile int* cancel) {
+    const hipStream_t st = nullptr;
+    if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
+    resolve_timers(s);
+    memset(&s->stats, 0, sizeof s->stats);
+    s->stats_final = false;
+    s->overlap_stages = 0;
+    const uint64_t n_rays = (uint64_t)n_results * rays_per_result;
+    {
+        double need[3] = {0.0, 0.0, 0.0};
+        for (uint64_t i = 0; i < n_rays; i++)
+            for (int c = 0; c < 3; c++) {
+                const double a = std::fabs((double)origins[3 * i + c]) * 1.001;
+                if (std::isfinite(a)) need[c] = std::max(need[c], a);
+            }
+        RR_TRY(ensure_tlas_reach(s, need));
+    }
+    // the frame constants k_shade reads: `samples` decides which ray of a result carries its object id; a width of 65536 makes
+    // k_shade's RNG pixel (xy >> 16) * width + (xy & 0xffff) the 32-bit id itself
+    DFrame fr;
+    memset(&fr, 0, sizeof fr);
+    fr.width = 65536u; fr.height = 65536u; fr.samples = rays_per_result; fr.cell_size = 1u;
+    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u;
+    fr.fog_density = cfg->fog_density;
+    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
+    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
+    fr.n_region_pixels = n_results;
+    RR_TRY(upload_shade_const(s, fr, st));
+    DevBuf d_ids, d_origins, d_dirs, d_out;
+    HIP_TRY(d_ids.reserve((size_t)n_results * 4));
+    if (stream_ids) HIP_TRY(hipMemcpy(d_ids.p, stream_ids, (size_t)n_results * 4, hipMemcpyHostToDevice));
+    else {
+        std::vector<uint32_t> iota(std::min<uint32_t>(n_results, 1u << 20));
+        for (uint32_t j0 = 0; j0 < n_results; j0 += (uint32_t)iota.size()) {
+            const uint32_t n = std::min<uint32_t>((uint32_t)iota.size(), n_results - j0);
+            for (uint32_t j = 0; j < n; j++) iota[j] = j0 + j;
+            HIP_TRY(hipMemcpy(d_ids.as<uint32_t>() + j0, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        }
+    }
+    DAccum acc;
+    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->n_enabled_lights, s->tuning.shade_chunk_rays);
+    if (plan.M > s->arena_cap) {
+        const size_t elem[4] = {16, 16, 8, 16};
+        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(plan.M * elem[k]));
+        s->arena_cap = plan.M;
+    }
+    if (plan.sq_need > s->sq_cap) { // (sq_valid as plan_queues sizes it: a frame's stage buffers need one word per 64 rays of the queue)
+        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(plan.sq_need * 16));
+        HIP_TRY(s->sq_valid.reserve((plan.sq_need / RR_WAVE + 1) * 8));
+        s->sq_cap = plan.sq_need;
+    }
+    HIP_TRY(d_origins.reserve(12ull * plan.B));
+    HIP_TRY(d_dirs.reserve(12ull * plan.B));
+    HIP_TRY(d_out.reserve(32ull * std::min<uint32_t>(n_results, RESOLVE_RAYS_CHUNK)));
+    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
+               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
+    f.slot_xy = d_ids.as<uint32_t>();
+    f.seeded = true;
+    HIP_TRY(hipEventRecord(s->frame_a, st));
+    int rc = run_ray_batches(f, origins, directions, rays_per_result, d_origins.as<float>(), d_dirs.as<float>());
+    for (uint32_t r0 = 0; r0 < n_results && rc == RR_OK; r0 += RESOLVE_RAYS_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(RESOLVE_RAYS_CHUNK, n_results - r0);
+        hipLaunchKernelGGL(k_resolve_rays, dim3((n + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, acc, r0, n, rays_per_result, d_out.as<float4>());
+        const hipError_t e = hipMemcpyAsync(out + r0, d_out.p, 32ull * n, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = fail(RR_ERR_DEVICE, "rr_shade_rays: %s", hipGetErrorString(e));
+    }
+    (void)hipEventRecord(s->frame_b, st);
+    const hipError_t e = hipStreamSynchronize(st); // before this call's buffers go: nothing of it is left in flight, whatever ended it
+    if (rc != RR_OK) return rc;
+    HIP_TRY(e);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_shade_rays(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                             const uint32_t* stream_ids, rr_radiance* out, const volatile int* cancel) try {
+    if (!s || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (rays_per_result == 0) return fail(RR_ERR_INVALID_ARGUMENT, "rays_per_result must be >= 1");
+    if (rays_per_result > RR_MAX_SAMPLES_WITH_TABLE) return fail(RR_ERR_UNSUPPORTED, "rays_per_result %u > %u", rays_per_result, RR_MAX_SAMPLES_WITH_TABLE);
+    if (cfg->max_recursion > RR_MAX_RECURSION) return fail(RR_ERR_UNSUPPORTED, "max_recursion %u > %u", cfg->max_recursion, RR_MAX_RECURSION);
+    if (n_results == 0) return RR_OK;
+    if (n_results > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u results in one call", n_results);
+    if (!origins || !directions || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(not_in_pass(s, "rr_shade_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("shade_rays.host");
+    return shade_rays_locked(s, cfg, origins, directions, n_results, rays_per_result, stream_ids, out, cancel);
+} RR_GUARD_END("rr_shade_rays")
 
 // ---------------------------------------------------------------------------
 // device arithmetic probe (tests/test_device_math.py): runs rr_math.h functions on the GPU

@@ -85,6 +85,28 @@ inline FramePlan plan_frame(const FramePlanInputs& in) {
     return FramePlan{total_primary, B, G, M, chunk, sq_need};
 }
 
+// ---- caller-supplied rays (rr_api.hip rr_shade_rays) ----------------------------------------------------------------------
+// The rays of such a call are depth level 1 as RECORDS: a batch of B rays sits at the front of the arena (56 B each, where a
+// frame keeps 16-B hit records only), its children behind it.  2 arena rays per ray for the children, as plan_frame allows per
+// primary ray, plus the slack every spawning level needs to make progress; level_slice covers a scene that branches more.
+// B <= RR_LEVEL_MAX / 3, so that the children's room stays inside 32-bit ray indices; at least 4096 rays, as plan_frame.
+// The batches are equal: batch k = rays [k * B, min((k + 1) * B, n_rays)), a result's rays cut anywhere (the accumulators are
+// integers and live across the batches).  Returned as a FramePlan (total_primary = n_rays, G = 1): the level walk reads it.
+inline FramePlan plan_ray_batches(uint64_t n_rays, uint32_t max_recursion, uint64_t budget, uint32_t n_enabled_lights, uint64_t shade_chunk_rays) {
+    const uint32_t L = n_enabled_lights;
+    const uint64_t slack = 2ull * RR_BLOCK * (max_recursion + 1);
+    const uint64_t per_ray = 3ull * 56ull;
+    uint64_t B = std::max<uint64_t>(budget > 56ull * slack ? (budget - 56ull * slack) / per_ray : 0ull, 4096);
+    B = std::min<uint64_t>(B, std::min<uint64_t>(std::max<uint64_t>(n_rays, 1), (RR_LEVEL_MAX - slack) / 3));
+    { const uint64_t nb = (std::max<uint64_t>(n_rays, 1) + B - 1) / B; B = (std::max<uint64_t>(n_rays, 1) + nb - 1) / nb; }
+    const uint64_t M = 3 * B + slack;
+    const uint64_t chunk_by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(L, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
+    const uint64_t chunk = std::min<uint64_t>(shade_chunk_rays ? std::max<uint64_t>(65536, shade_chunk_rays) : (64ull << 20), chunk_by_lights);
+    // every level takes the dense sharded shadow queue (no fixed slots: the rays of a packet need not belong together)
+    const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, M) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(L, 1u));
+    return FramePlan{n_rays, B, 1u, M, chunk, sq_need};
+}
+
 // ---- level 1 in stages (rr_api.hip run_level, the two-stream path) -------------------------------------------------------
 // Level 1 of a scene with fixed shadow slots may be cut into STAGES of hits: k_shade<true> of stage k + 1 then runs on one
 // stream while k_trace_shadow<true> of stage k runs on a second one.  Stage k writes its shadow rays into buffer

@@ -1082,6 +1082,59 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t*
 }
 
 // ---------------------------------------------------------------------------
+// kernels 5b, 5c: caller-supplied rays as depth level 1 (rr_shade_rays): get_color_depth_normal_id(scene, ray, 1) per ray
+// ---------------------------------------------------------------------------
+// One batch of the caller's rays -> level-1 RECORDS at the front of the ray arena, the fields k_shade<true> builds for a root:
+// throughput 1, depth 1, id carrier, path node 1.  Record i is the caller's ray first + i = sample (first + i) % rays_per_result of
+// result (first + i) / rays_per_result, whose accumulator slot is the result's index: the samples of a result sit in neighbouring
+// lanes and accum_merged merges their adds.  origins / dirs: the batch's 3 n floats each.  The direction is normalised as
+// primary_ray does it (get_color_depth_normal_id, :723).  Thread 0 publishes the level's size and counts the rays.
+__global__ __launch_bounds__(RR_BLOCK) void k_seed_rays(const float* __restrict__ origins, const float* __restrict__ dirs, unsigned long long first, uint32_t n,
+                                                        uint32_t rays_per_result, DRayQueue q, uint32_t* __restrict__ q_count, unsigned long long* counters) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0u) { *q_count = n; atomicAdd(&counters[RR_CNT_PRIMARY], (unsigned long long)n); }
+    if (i >= n) return;
+    const unsigned long long g = first + i;
+    const uint32_t slot = (uint32_t)(g / rays_per_result), sample = (uint32_t)(g % rays_per_result);
+    const f3 d = normalize3(mk3(dirs[3ull * i], dirs[3ull * i + 1], dirs[3ull * i + 2]));
+    q.r0[i] = make_float4(origins[3ull * i], origins[3ull * i + 1], origins[3ull * i + 2], 1.0f);
+    q.r1[i] = make_float4(d.x, d.y, d.z, __uint_as_float(slot));
+    q.r2[i] = make_uint2(sample | (1u << 16) | (1u << 24), 1u);
+}
+
+// What k_resolve computes BEFORE its clamp, per accumulator slot [first, first + n): two float4 per result =
+// (colour rgb, depth), (normal xyz, bits(object id)) -- rr_radiance.  Every expression is k_resolve's own.
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t first, uint32_t n, uint32_t samples, float4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = first + i;
+    const double inv_fix = 1.0 / 16777216.0;
+    const float ns = (float)samples;
+    const uint32_t nf = acc.flags[p];
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float sum = (float)((double)acc.rgb[(unsigned long long)k * acc.n + p] * inv_fix);
+        const bool pinf = (nf >> (3 + k)) & 1u, ninf = (nf >> (6 + k)) & 1u;
+        if (((nf >> k) & 1u) || (pinf && ninf)) sum = __builtin_nanf("");
+        else if (pinf) sum = __builtin_inff();
+        else if (ninf) sum = -__builtin_inff();
+        c[k] = sum / ns;
+    }
+    f3 nn = mk3((float)((double)acc.normal[p] * inv_fix) / ns, (float)((double)acc.normal[acc.n + p] * inv_fix) / ns,
+                (float)((double)acc.normal[2ull * acc.n + p] * inv_fix) / ns);
+    if (nf & (RR_NF_NORMAL_NAN * 7u)) {
+        if (nf & RR_NF_NORMAL_NAN) nn.x = __builtin_nanf("");
+        if (nf & (RR_NF_NORMAL_NAN << 1)) nn.y = __builtin_nanf("");
+        if (nf & (RR_NF_NORMAL_NAN << 2)) nn.z = __builtin_nanf("");
+    }
+    nn = normalize3(nn); // 0/0 = NaN when every ray missed, as a frame's pixel
+    const float depth = (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)acc.depth[p] * (1.0 / 65536.0)) / ns;
+    out[2ull * i] = make_float4(c[0], c[1], c[2], depth);
+    out[2ull * i + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
+}
+
+// ---------------------------------------------------------------------------
 // kernel 6: gather compact per-rank buffers into frame order (multi-GPU epilogue)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(RR_BLOCK) void k_gather_frame(const uint32_t* __restrict__ src_index, uint32_t n_pixels,

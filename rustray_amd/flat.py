@@ -106,6 +106,11 @@ class rr_pick_result(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("object_id", C.c_uint32), ("item_index", C.c_uint32), ("distance", C.c_float)]
 
 
+class rr_radiance(C.Structure):
+    """include/rustray_hip.h: one record of rr_shade_rays (linear floats)."""
+    _fields_ = [("color", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("object_id", C.c_uint32)]
+
+
 class rr_frame_stats(C.Structure):
     _fields_ = [
         ("primary_rays", C.c_uint64), ("secondary_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
