@@ -40,7 +40,8 @@ extern "C" {
  * rr_scene_update_lights, rr_scene_update_item_flags and rr_scene_add_textures came later without a change of any struct, so the
  * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them).
  * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well.
- * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own). */
+ * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own), and after them the
+ * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -549,7 +550,7 @@ int rr_trace_shadow_rays(rr_scene* scene, const float* origins, const float* dir
  * A frame call: it takes the scene's lock, returns RR_ERR_INVALID_ARGUMENT from on_pass of the same scene and RR_ERR_DEVICE on a
  * broken scene, and rr_scene_last_stats afterwards reports its counters (primary_rays = the number of rays).
  * origins / directions: n_results * rays_per_result * 3 floats (host); stream_ids: n_results ids, or NULL (result j uses j).
- * Device-buffer and stream forms are out of scope. */
+ * The device-buffer, stream-ordered form is rr_shade_rays_device below. */
 typedef struct rr_radiance {
     float color[3];     /* mean over the result's rays of get_color_depth_normal_id(..).0: LINEAR, no min(., 1), no gamma */
     float depth;        /* mean of .1 */
@@ -559,6 +560,41 @@ typedef struct rr_radiance {
 int rr_shade_rays(rr_scene* scene, const rr_config* config, const float* origins, const float* directions,
                   uint32_t n_results, uint32_t rays_per_result, const uint32_t* stream_ids,
                   rr_radiance* out, const volatile int* cancel);
+
+/* The three ray queries on DEVICE buffers, in stream order: for rays that were produced on the GPU (a torch op, an earlier query's
+ * hits, a lens model run as a kernel) and answers that are consumed there.  Every buffer is memory the scene's device can address
+ * -- device memory of that device, of another device this library has enabled peer access to, pinned or managed memory -- in the
+ * layout of the host form: n * 3 floats, n floats, n records of 20 / 20 / 32 bytes; every pointer 4-byte aligned, out_dev of
+ * rr_shade_rays_device 16-byte aligned.  Each pointer is classified (hipPointerGetAttributes) before anything is enqueued: pageable
+ * host memory, or another device's memory without peer access, is RR_ERR_INVALID_ARGUMENT with the argument's name in rr_last_error,
+ * never a launch.
+ *   Results: once `hip_stream` is synchronised, out_dev holds byte for byte what the host form writes into `out` for the same inputs
+ *   on the same handle state (NaN bit patterns, the not-hit and not-occluded records and the reference's face ids included).
+ *   Limits and argument checks are the host forms': n == 0 returns RR_OK and touches nothing, n > 0x7fffff00 is RR_ERR_UNSUPPORTED,
+ *   depth 1 .. 255, rays_per_result, max_recursion; a NaN or negative max_distance_dev[i] is RR_ERR_INVALID_ARGUMENT naming the
+ *   first such i, and nothing is written to out_dev.
+ *   Stream: work is enqueued on `hip_stream` (a hipStream_t, NULL = the default stream).  The inputs are read in stream order -- the
+ *   caller need not synchronise after producing them on that stream -- and the call returns once its last launch is enqueued; the
+ *   caller synchronises before it reads out_dev on the host.  The call WAITS inside for what it must learn from the device before it
+ *   can enqueue the walk: once, for 16 bytes -- the largest finite |origin| per axis, for which the top level must be padded (found
+ *   on the device, in float; the host forms scan the origins on the host), and the first bad max_distance.  rr_shade_rays_device
+ *   waits in addition where rr_shade_rays does: for its frame constants and for the size of every depth level.
+ *   Scene state: a frame call like the host forms -- the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene,
+ *   RR_ERR_DEVICE on a broken scene.  The handle's query buffers are shared, so a call on another stream than the handle's last
+ *   call first waits for that stream, as rr_render_region_device does.  A scene edit or rr_scene_destroy waits for queries in
+ *   flight; rr_scene_last_stats after rr_shade_rays_device behaves as after rr_render_region_device (it waits for the stream).
+ *   Memory: nothing is allocated per call.  What the launches read after the call has returned belongs to the handle, grows on
+ *   demand and is freed by rr_scene_destroy: 56 B per ray of the largest closest-hit or shadow query so far (the packed records and
+ *   the walk's raw hits), 4 B per result of the largest radiance query without stream ids, plus what rr_shade_rays keeps (64 B per
+ *   result, the ray arena).  A growth that fails is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.
+ *   cancel (rr_shade_rays_device): as rr_shade_rays; a call that is cancelled or fails part-way leaves the stream idle. */
+int rr_trace_rays_device(rr_scene* scene, const float* origins_dev, const float* directions_dev, uint32_t n, uint32_t depth,
+                         rr_ray_hit* out_dev, void* hip_stream);
+int rr_trace_shadow_rays_device(rr_scene* scene, const float* origins_dev, const float* directions_dev, const float* max_distance_dev /* or NULL */,
+                                uint32_t n, uint32_t depth, rr_shadow_hit* out_dev, void* hip_stream);
+int rr_shade_rays_device(rr_scene* scene, const rr_config* config, const float* origins_dev, const float* directions_dev,
+                         uint32_t n_results, uint32_t rays_per_result, const uint32_t* stream_ids_dev /* or NULL */,
+                         rr_radiance* out_dev, void* hip_stream, const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

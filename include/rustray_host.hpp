@@ -498,6 +498,24 @@ public:
         return out;
     }
 
+    // The three ray queries on DEVICE buffers, in stream order (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device):
+    // the pointers name memory the scene's device can address, in the layouts of the C ABI (3 floats per origin and direction, 20-byte
+    // hit records, 32-byte radiance records); `hip_stream` is a hipStream_t (nullptr = the default stream).  The work is enqueued and
+    // the call returns: synchronise the stream before reading the results on the host.  Each returns the rr_status (rr_last_error()
+    // says why it is not RR_OK).  shade_device uses this handle's config, as shade_rays does.
+    int trace_device(const float* origins_dev, const float* dirs_dev, uint32_t n, uint32_t depth, rr_ray_hit* out_dev, void* hip_stream) const {
+        return rr_trace_rays_device(scene->handle(), origins_dev, dirs_dev, n, depth, out_dev, hip_stream);
+    }
+    int trace_shadow_device(const float* origins_dev, const float* dirs_dev, const float* max_distance_dev, uint32_t n, uint32_t depth,
+                            rr_shadow_hit* out_dev, void* hip_stream) const {
+        return rr_trace_shadow_rays_device(scene->handle(), origins_dev, dirs_dev, max_distance_dev, n, depth, out_dev, hip_stream);
+    }
+    int shade_device(const float* origins_dev, const float* dirs_dev, uint32_t n_results, uint32_t rays_per_result, const uint32_t* stream_ids_dev,
+                     rr_radiance* out_dev, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_config c = config.c_struct();
+        return rr_shade_rays_device(scene->handle(), &c, origins_dev, dirs_dev, n_results, rays_per_result, stream_ids_dev, out_dev, hip_stream, cancel);
+    }
+
     // The GUI's light and item edits (reference src/run.rs:1294-1409, :1464-1489), applied to the resident scene before the next
     // RendererManager::restart: `lights` is the edited Scene::lights, the flags are ShapeBasics::visible / flip_normals per item.
     // false = refused or failed (scene->error() says why); the scene then renders what it rendered before.

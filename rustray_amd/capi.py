@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -42,7 +42,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_kernels.hip", "rr_frame_plan.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -106,6 +106,11 @@ def lib():
             L.rr_trace_shadow_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_shadow_hit)]
         if hasattr(L, "rr_shade_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
             L.rr_shade_rays.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_shade_rays_device") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rr_trace_shadow_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rr_shade_rays_device.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -353,6 +358,25 @@ class DeviceScene:
                                    out.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
         out = out[:n]
         return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+
+    # -- the ray queries on device buffers, in stream order ---------------------------
+    def trace_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
+        """rr_trace_rays_device: raw device pointers (ints) of n * 3 float32 origins and directions and of n 20-byte rr_ray_hit records;
+        enqueued on `stream_ptr` (a hipStream_t as int, None = the default stream).  Synchronise before reading the records on the host."""
+        _check(lib().rr_trace_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr),
+                                          C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def trace_shadow_rays_device(self, origins_ptr, dirs_ptr, max_distance_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
+        """rr_trace_shadow_rays_device: as trace_rays_device, with n float32 limits (None = no limit) and n 20-byte rr_shadow_hit records."""
+        _check(lib().rr_trace_shadow_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(max_distance_ptr) if max_distance_ptr else None,
+                                                 C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr), C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def shade_rays_device(self, cfg: rr_config, origins_ptr, dirs_ptr, n_results: int, rays_per_result: int, stream_ids_ptr, out_ptr, stream_ptr=None, cancel=None):
+        """rr_shade_rays_device: n_results * rays_per_result rays, n_results uint32 stream ids (None = the result's index) and n_results
+        32-byte rr_radiance records (16-byte aligned), all raw device pointers; enqueued on `stream_ptr`."""
+        _check(lib().rr_shade_rays_device(self._h, C.byref(cfg), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n_results), C.c_uint32(rays_per_result),
+                                          C.c_void_p(stream_ids_ptr) if stream_ids_ptr else None, C.c_void_p(out_ptr),
+                                          C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
 
     def set_profiling(self, on: bool):
         self.set_tuning(kernel_timing=1 if on else 0)

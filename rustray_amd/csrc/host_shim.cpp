@@ -168,6 +168,25 @@ extern "C" int rh_shade_rays(void* h, const rr_config* cfg, const float* origins
     return 0;
 }
 
+// Raytracing::trace_device / trace_shadow_device / shade_device: the device-buffer ray queries, enqueued on `stream` (a hipStream_t)
+extern "C" int rh_trace_device(void* h, const float* origins_dev, const float* dirs_dev, uint32_t n, uint32_t depth, rr_ray_hit* out_dev, void* stream) {
+    return ((RhScene*)h)->rt->trace_device(origins_dev, dirs_dev, n, depth, out_dev, stream);
+}
+
+extern "C" int rh_trace_shadow_device(void* h, const float* origins_dev, const float* dirs_dev, const float* max_distance_dev, uint32_t n, uint32_t depth,
+                                      rr_shadow_hit* out_dev, void* stream) {
+    return ((RhScene*)h)->rt->trace_shadow_device(origins_dev, dirs_dev, max_distance_dev, n, depth, out_dev, stream);
+}
+
+extern "C" int rh_shade_device(void* h, const rr_config* cfg, const float* origins_dev, const float* dirs_dev, uint32_t n_results, uint32_t rays_per_result,
+                               const uint32_t* stream_ids_dev, rr_radiance* out_dev, void* stream) {
+    Raytracing& rt = *((RhScene*)h)->rt;
+    rt.config = RaytracingConfig();
+    rt.config.apply(from_c(cfg));
+    rt.config.seed = cfg->seed;
+    return rt.shade_device(origins_dev, dirs_dev, n_results, rays_per_result, stream_ids_dev, out_dev, stream);
+}
+
 // one whole frame (min_passes passes) into the caller's buffers
 extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
                                const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,

@@ -9,6 +9,7 @@
 #include "rr_bvh.h"
 #include "rr_device.h"
 #include "rr_frame_plan.h"
+#include "rr_query_pointers.h"
 
 #include <hip/hip_runtime.h>
 
@@ -214,6 +215,11 @@ struct rr_scene {
     DevBuf region_xy, trace_order, sample_xy, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
     std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
     DevBuf tmp_out[4];
+    // device-buffer ray queries (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device): what their launches read and write
+    // after the call has returned belongs to the handle, grows on demand and is never shrunk.  query_rec: the packed records r0, r1, r2 and
+    // the walks' raw hits (16 + 16 + 8 + 16 = 56 B per ray of the largest closest-hit or shadow query; a shadow query uses 48 of them);
+    // query_words: QW_* below; query_ids: the stream ids 0 .. n - 1 of a radiance query without the caller's (4 B per result)
+    DevBuf query_rec[4], query_words, query_ids;
     DevBuf multi_part[4], multi_cat[4]; // rr_render_multi: this device's compact buffers; on device slot 0 the concatenation of all
     hipStream_t multi_stream = nullptr; // rr_render_multi: this handle's own non-blocking stream (created on first use)
     void* multi_stage[4] = {nullptr, nullptr, nullptr, nullptr}; size_t multi_stage_bytes[4] = {0, 0, 0, 0}; // pinned staging, devices without peer access
@@ -2324,6 +2330,262 @@ extern "C" int rr_shade_rays(rr_scene* s, const rr_config* cfg, const float* ori
     RR_FAULT_POINT("shade_rays.host");
     return shade_rays_locked(s, cfg, origins, directions, n_results, rays_per_result, stream_ids, out, cancel);
 } RR_GUARD_END("rr_shade_rays")
+
+// ---------------------------------------------------------------------------
+// device-buffer, stream-ordered forms of the three ray queries: rays that were produced on the device are traced where they are and
+// the answers are consumed in stream order.  The streaming kernels of rr_kernels.hip (5d .. 5g) stand where the host forms loop on
+// the host; the walks, their launch sites and the level walk of rr_shade_rays are the host forms' own.
+// Each call waits ONCE for the device, for the 16 bytes of query_words[QW_REACH]: the largest finite |origin| per axis (the top
+// level must be padded for it BEFORE the walk is enqueued: ensure_tlas_reach, the same * 1.001 in double as the host forms) and the
+// first bad max_distance.  rr_shade_rays_device additionally waits where rr_shade_rays' level walk does (the level sizes).
+// Everything the launches touch after the call has returned is the caller's or the handle's (rr_scene::query_*, the arena): a scene
+// edit waits for the device before it overwrites what they read, and rr_scene_destroy before it frees.
+// ---------------------------------------------------------------------------
+enum : size_t { QW_COUNT = 0, QW_HEAD = 4, QW_REACH = 64, QW_COUNTERS = 128, QW_CONST = 256 }; // byte offsets into rr_scene::query_words
+
+// `p` (argument `arg` of `fn`) must be memory the scene's device can address: decided by query_pointer_ok (rr_query_pointers.h)
+static int check_query_pointer(const rr_scene* s, const void* p, const char* fn, const char* arg) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    QueryMemKind kind = RR_QMEM_UNREGISTERED;
+    int owner = -1;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) (void)hipGetLastError(); // a pointer the runtime has never seen
+    else {
+        switch (at.type) {
+        case hipMemoryTypeHost: kind = RR_QMEM_HOST; break;
+        case hipMemoryTypeDevice: kind = RR_QMEM_DEVICE; owner = at.device; break;
+        case hipMemoryTypeManaged: case hipMemoryTypeUnified: kind = RR_QMEM_MANAGED; break;
+        case hipMemoryTypeArray: kind = RR_QMEM_ARRAY; break;
+        default: kind = RR_QMEM_UNREGISTERED; break;
+        }
+    }
+    bool peer = false;
+    if (kind == RR_QMEM_DEVICE && owner != s->device) { // only what this library has enabled itself (rr_render_multi) counts
+        std::lock_guard<std::mutex> lk(g_peer_mu);
+        const auto it = g_peer_state.find({s->device, owner});
+        peer = it != g_peer_state.end() && it->second;
+    }
+    if (!query_pointer_ok(kind, owner, s->device, peer))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s is %s%s the scene's device %d cannot address", fn, arg, query_mem_kind_name(kind),
+                    kind == RR_QMEM_DEVICE ? " of another device without peer access, which" : ", which", s->device);
+    return RR_OK;
+}
+
+// the handle's record buffers for n rays (grow-only; a failed growth leaves an empty buffer that the next call allocates anew)
+static int reserve_query_records(rr_scene* s, uint32_t n, bool shadow) {
+    const size_t elem[4] = {16, 16, 8, 16};
+    for (int k = 0; k < 4; k++)
+        if (!(shadow && k == 2)) HIP_TRY(s->query_rec[k].reserve((size_t)n * elem[k]));
+    HIP_TRY(s->query_words.reserve(QW_CONST + sizeof(DShadeConst)));
+    return RR_OK;
+}
+
+static int take_stream(rr_scene* s, hipStream_t st) { // the handle's query buffers are shared: queries on different streams are serialised, as frames are
+    if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
+    return RR_OK;
+}
+
+// the reach words, preset; the caller enqueues the kernel that merges into them and then calls await_reach
+static int preset_reach(rr_scene* s, hipStream_t st) {
+    char* w = s->query_words.as<char>();
+    HIP_TRY(hipMemsetAsync(w, 0, QW_CONST, st));
+    HIP_TRY(hipMemsetAsync(w + QW_REACH + 12, 0xff, 4, st));
+    return RR_OK;
+}
+// THE wait of a device-buffer query: reads the reach words back (pinned, s->h_count[4 .. 7]) and pads the top level as the host forms do.
+// *first_bad = the first index with a bad limit, or 0xffffffff.
+static int await_reach(rr_scene* s, hipStream_t st, uint32_t* first_bad) {
+    uint32_t* h = s->h_count + 4;
+    HIP_TRY(hipMemcpyAsync(h, s->query_words.as<char>() + QW_REACH, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *first_bad = h[3];
+    if (h[3] != 0xffffffffu) return RR_OK; // the caller refuses: nothing is rebuilt for a call that does nothing
+    double need[3];
+    for (int c = 0; c < 3; c++) {
+        float a;
+        memcpy(&a, &h[c], 4);
+        need[c] = (double)a * 1.001;
+    }
+    return ensure_tlas_reach(s, need);
+}
+
+static int query_grid(const rr_scene* s, uint64_t n) { return (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u); }
+
+extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out,
+                                    void* hip_stream) try {
+    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
+    if (n == 0) return RR_OK;
+    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
+    if (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)out) & 3u) return fail(RR_ERR_INVALID_ARGUMENT, "rr_trace_rays_device: a buffer is not 4-byte aligned");
+    RR_TRY(not_in_pass(s, "rr_trace_rays_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("trace_rays_device.host");
+    RR_TRY(check_query_pointer(s, origins, "rr_trace_rays_device", "origins_dev"));
+    RR_TRY(check_query_pointer(s, directions, "rr_trace_rays_device", "directions_dev"));
+    RR_TRY(check_query_pointer(s, out, "rr_trace_rays_device", "out_dev"));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(take_stream(s, st));
+    RR_TRY(reserve_query_records(s, n, false));
+    char* w = s->query_words.as<char>();
+    DRayQueue q{s->query_rec[0].as<float4>(), s->query_rec[1].as<float4>(), s->query_rec[2].as<uint2>(), s->query_rec[3].as<uint4>()};
+    RR_TRY(preset_reach(s, st));
+    hipLaunchKernelGGL(k_pack_rays<false>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, origins, directions, (const float*)nullptr, n, depth, q.r0, q.r1, q.r2,
+                       (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_REACH));
+    HIP_TRY(hipGetLastError());
+    uint32_t first_bad = 0;
+    RR_TRY(await_reach(s, st, &first_bad));
+    DPrimary pr{nullptr, 0ull, 0u, 1u};
+    // (the <false> build reads neither the frame constants nor the work counters; both pointers name the handle's words all the same)
+    RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), nullptr, pr,
+                                (unsigned long long*)(w + QW_COUNTERS), st));
+    hipLaunchKernelGGL(k_unpack_hits<false>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+} RR_GUARD_END("rr_trace_rays_device")
+
+extern "C" int rr_trace_shadow_rays_device(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth,
+                                           rr_shadow_hit* out, void* hip_stream) try {
+    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
+    if (n == 0) return RR_OK;
+    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
+    if (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)max_distance | (uintptr_t)out) & 3u)
+        return fail(RR_ERR_INVALID_ARGUMENT, "rr_trace_shadow_rays_device: a buffer is not 4-byte aligned");
+    RR_TRY(not_in_pass(s, "rr_trace_shadow_rays_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("trace_shadow_rays_device.host");
+    RR_TRY(check_query_pointer(s, origins, "rr_trace_shadow_rays_device", "origins_dev"));
+    RR_TRY(check_query_pointer(s, directions, "rr_trace_shadow_rays_device", "directions_dev"));
+    if (max_distance) RR_TRY(check_query_pointer(s, max_distance, "rr_trace_shadow_rays_device", "max_distance_dev"));
+    RR_TRY(check_query_pointer(s, out, "rr_trace_shadow_rays_device", "out_dev"));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(take_stream(s, st));
+    RR_TRY(reserve_query_records(s, n, true));
+    char* w = s->query_words.as<char>();
+    float4 *r0 = s->query_rec[0].as<float4>(), *r1 = s->query_rec[1].as<float4>();
+    uint4* raw = s->query_rec[3].as<uint4>();
+    RR_TRY(preset_reach(s, st));
+    hipLaunchKernelGGL(k_pack_rays<true>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, origins, directions, max_distance, n, depth, r0, r1, (uint2*)nullptr,
+                       (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_REACH));
+    HIP_TRY(hipGetLastError());
+    uint32_t first_bad = 0;
+    RR_TRY(await_reach(s, st, &first_bad));
+    if (first_bad != 0xffffffffu) { // (the stream is idle: the value for the message comes with one more small copy)
+        float v = 0.0f;
+        HIP_TRY(hipMemcpy(&v, max_distance + first_bad, 4, hipMemcpyDefault));
+        return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", first_bad, (double)v);
+    }
+    RR_TRY(launch_query_shadow(s, r0, r1, n, (uint32_t*)(w + QW_HEAD), raw, st));
+    hipLaunchKernelGGL(k_unpack_hits<true>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, raw, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+} RR_GUARD_END("rr_trace_shadow_rays_device")
+
+// rr_shade_rays on the caller's device buffers: k_seed_rays reads them batch by batch where they are, the stream ids are used in
+// place (or written by k_iota into the handle's buffer) and k_resolve_rays writes straight into out_dev.  The handle's state is
+// treated as shade_rays_locked treats it; nothing of the call is freed behind launches in flight, because nothing is the call's own.
+static int shade_rays_device_locked(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                                    const uint32_t* stream_ids, rr_radiance* out, hipStream_t st, const volatile int* cancel) {
+    RR_TRY(take_stream(s, st));
+    resolve_timers(s);
+    memset(&s->stats, 0, sizeof s->stats);
+    s->stats_final = false;
+    s->overlap_stages = 0;
+    const uint64_t n_rays = (uint64_t)n_results * rays_per_result;
+    HIP_TRY(s->query_words.reserve(QW_CONST + sizeof(DShadeConst)));
+    if (!stream_ids) HIP_TRY(s->query_ids.reserve((size_t)n_results * 4));
+    RR_TRY(preset_reach(s, st));
+    hipLaunchKernelGGL(k_ray_reach, dim3(query_grid(s, 3ull * n_rays)), dim3(RR_BLOCK), 0, st, origins, (unsigned long long)(3ull * n_rays),
+                       (uint32_t*)(s->query_words.as<char>() + QW_REACH));
+    HIP_TRY(hipGetLastError());
+    uint32_t first_bad = 0;
+    RR_TRY(await_reach(s, st, &first_bad));
+    DFrame fr; // as shade_rays_locked
+    memset(&fr, 0, sizeof fr);
+    fr.width = 65536u; fr.height = 65536u; fr.samples = rays_per_result; fr.cell_size = 1u;
+    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u;
+    fr.fog_density = cfg->fog_density;
+    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
+    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
+    fr.n_region_pixels = n_results;
+    RR_TRY(upload_shade_const(s, fr, st));
+    if (!stream_ids) {
+        hipLaunchKernelGGL(k_iota, dim3((n_results + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, s->query_ids.as<uint32_t>(), n_results);
+        HIP_TRY(hipGetLastError());
+        stream_ids = s->query_ids.as<uint32_t>();
+    }
+    DAccum acc;
+    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->n_enabled_lights, s->tuning.shade_chunk_rays);
+    if (plan.M > s->arena_cap) {
+        const size_t elem[4] = {16, 16, 8, 16};
+        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(plan.M * elem[k]));
+        s->arena_cap = plan.M;
+    }
+    if (plan.sq_need > s->sq_cap) {
+        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(plan.sq_need * 16));
+        HIP_TRY(s->sq_valid.reserve((plan.sq_need / RR_WAVE + 1) * 8));
+        s->sq_cap = plan.sq_need;
+    }
+    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
+               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
+    f.slot_xy = stream_ids;
+    f.seeded = true;
+    HIP_TRY(hipEventRecord(s->frame_a, st));
+    int rc = RR_OK;
+    const uint64_t B = plan.B;
+    for (uint64_t first = 0; first < n_rays && rc == RR_OK; first += B) { // run_ray_batches without its staging copies
+        if (cancel && *cancel) { rc = fail(RR_ERR_CANCELLED, "cancelled"); break; }
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rays - first);
+        rc = f.pool.start_batch();
+        if (rc != RR_OK) break;
+        uint32_t* level1_count = f.pool.take(1);
+        if (!level1_count) { rc = counters_exhausted(); break; }
+        hipLaunchKernelGGL(k_seed_rays, dim3((nb + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, origins + 3ull * first, directions + 3ull * first,
+                           (unsigned long long)first, nb, rays_per_result, f.queue_at(0), level1_count, s->counters.as<unsigned long long>());
+        s->stats.batches++;
+        rc = run_level(f, 1, 0, nb, level1_count);
+        if (rc == RR_OK && cancel && first + B < n_rays && hipStreamSynchronize(st) != hipSuccess) rc = fail(RR_ERR_DEVICE, "rr_shade_rays_device: the stream failed");
+    }
+    for (uint32_t r0 = 0; r0 < n_results && rc == RR_OK; r0 += RESOLVE_RAYS_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(RESOLVE_RAYS_CHUNK, n_results - r0);
+        hipLaunchKernelGGL(k_resolve_rays, dim3((n + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, acc, r0, n, rays_per_result, (float4*)out + 2ull * r0);
+    }
+    (void)hipEventRecord(s->frame_b, st);
+    if (rc != RR_OK) { (void)hipStreamSynchronize(st); return rc; } // a call that ends early leaves the stream idle, as the host form does
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                                    const uint32_t* stream_ids, rr_radiance* out, void* hip_stream, const volatile int* cancel) try {
+    if (!s || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (rays_per_result == 0) return fail(RR_ERR_INVALID_ARGUMENT, "rays_per_result must be >= 1");
+    if (rays_per_result > RR_MAX_SAMPLES_WITH_TABLE) return fail(RR_ERR_UNSUPPORTED, "rays_per_result %u > %u", rays_per_result, RR_MAX_SAMPLES_WITH_TABLE);
+    if (cfg->max_recursion > RR_MAX_RECURSION) return fail(RR_ERR_UNSUPPORTED, "max_recursion %u > %u", cfg->max_recursion, RR_MAX_RECURSION);
+    if (n_results == 0) return RR_OK;
+    if (n_results > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u results in one call", n_results);
+    if (!origins || !directions || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if ((((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)stream_ids) & 3u) || ((uintptr_t)out & 15u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: the ray buffers must be 4-byte aligned and out_dev 16-byte aligned");
+    RR_TRY(not_in_pass(s, "rr_shade_rays_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("shade_rays_device.host");
+    RR_TRY(check_query_pointer(s, origins, "rr_shade_rays_device", "origins_dev"));
+    RR_TRY(check_query_pointer(s, directions, "rr_shade_rays_device", "directions_dev"));
+    if (stream_ids) RR_TRY(check_query_pointer(s, stream_ids, "rr_shade_rays_device", "stream_ids_dev"));
+    RR_TRY(check_query_pointer(s, out, "rr_shade_rays_device", "out_dev"));
+    return shade_rays_device_locked(s, cfg, origins, directions, n_results, rays_per_result, stream_ids, out, (hipStream_t)hip_stream, cancel);
+} RR_GUARD_END("rr_shade_rays_device")
 
 // ---------------------------------------------------------------------------
 // device arithmetic probe (tests/test_device_math.py): runs rr_math.h functions on the GPU

@@ -1135,6 +1135,135 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t 
 }
 
 // ---------------------------------------------------------------------------
+// kernels 5d .. 5g: the streaming passes around the walks of the DEVICE-BUFFER ray queries (rr_trace_rays_device,
+// rr_trace_shadow_rays_device, rr_shade_rays_device): the caller's 12-byte and 20-byte records are not a power of two, so a
+// workgroup moves its 256 rays' 768 or 1280 consecutive dwords with lane-strided dword accesses (every wave instruction covers 64
+// consecutive dwords = two 128-B lines) and turns them into per-ray records through LDS, where a stride of 3 or 5 dwords meets
+// every bank once.  Ray i of the caller's order stays record i: packet p of the walks is rays 64 p .. 64 p + 63.
+// ---------------------------------------------------------------------------
+// reach[0 .. 2]: the largest finite |origin| per axis as float bits (non-negative floats order as their bits: atomicMax);
+// reach[3]: the first index whose limit is NaN or negative (atomicMin; 0xffffffff = none).  One atomic per wave and word, and none
+// for a wave that has nothing to report.  The host presets the words (0, 0, 0, 0xffffffff).
+RR_DEV void reach_merge(uint32_t* __restrict__ reach, float ax, float ay, float az, uint32_t bad, uint32_t lane) {
+#pragma unroll
+    for (int off = RR_WAVE / 2; off > 0; off >>= 1) {
+        ax = fmaxf(ax, __shfl_xor(ax, off)); ay = fmaxf(ay, __shfl_xor(ay, off)); az = fmaxf(az, __shfl_xor(az, off));
+        bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
+    }
+    if (lane == 0u) {
+        if (ax > 0.0f) atomicMax(&reach[0], __float_as_uint(ax));
+        if (ay > 0.0f) atomicMax(&reach[1], __float_as_uint(ay));
+        if (az > 0.0f) atomicMax(&reach[2], __float_as_uint(az));
+        if (bad != 0xffffffffu) atomicMin(&reach[3], bad);
+    }
+}
+RR_DEV float finite_abs(float v) { const float a = fabsf(v); return a <= RR_FLT_MAX ? a : 0.0f; } // NaN and inf: ignored (0)
+
+// 5d: the caller's rays -> the records the walks read, and what the host must learn before it may enqueue the walk.
+//   SHADOW: r0[i] = (origin, min(limit, FLT_MAX)), r1[i] = (direction, bits(depth));  limits == NULL: no limit
+//   else:   r0[i] = (origin, 1), r1[i] = (direction, 0), r2[i] = (depth << 16, 1); thread 0 publishes the level's size in *q_count
+template <bool SHADOW>
+__global__ __launch_bounds__(RR_BLOCK) void k_pack_rays(const float* __restrict__ origins, const float* __restrict__ dirs, const float* __restrict__ limits,
+                                                        uint32_t n, uint32_t depth, float4* __restrict__ r0, float4* __restrict__ r1, uint2* __restrict__ r2,
+                                                        uint32_t* __restrict__ q_count, uint32_t* __restrict__ reach) {
+    __shared__ float s_o[3 * RR_BLOCK], s_d[3 * RR_BLOCK];
+    const uint32_t tid = threadIdx.x, lane = tid & (RR_WAVE - 1);
+    if (!SHADOW && blockIdx.x == 0 && tid == 0) *q_count = n;
+    const unsigned long long n_words = 3ull * n;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    uint32_t bad = 0xffffffffu;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * RR_BLOCK; base < n; base += (unsigned long long)gridDim.x * RR_BLOCK) { // block-uniform
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const uint32_t w = k * RR_BLOCK + tid;
+            const unsigned long long g = 3ull * base + w;
+            if (g < n_words) { s_o[w] = origins[g]; s_d[w] = dirs[g]; }
+        }
+        __syncthreads();
+        const unsigned long long i = base + tid;
+        if (i < n) {
+            const float ox = s_o[3 * tid], oy = s_o[3 * tid + 1], oz = s_o[3 * tid + 2];
+            const float dx = s_d[3 * tid], dy = s_d[3 * tid + 1], dz = s_d[3 * tid + 2];
+            ax = fmaxf(ax, finite_abs(ox)); ay = fmaxf(ay, finite_abs(oy)); az = fmaxf(az, finite_abs(oz));
+            if (SHADOW) {
+                float limit = RR_FLT_MAX;
+                if (limits) {
+                    const float l = limits[i];
+                    if (!(l >= 0.0f)) bad = min(bad, (uint32_t)i);
+                    limit = fminf(l, RR_FLT_MAX);
+                }
+                r0[i] = make_float4(ox, oy, oz, limit);
+                r1[i] = make_float4(dx, dy, dz, __uint_as_float(depth));
+            } else {
+                r0[i] = make_float4(ox, oy, oz, 1.0f);
+                r1[i] = make_float4(dx, dy, dz, 0.0f);
+                r2[i] = make_uint2(depth << 16, 1u);
+            }
+        }
+        __syncthreads(); // the next round overwrites the staging
+    }
+    reach_merge(reach, ax, ay, az, bad, lane);
+}
+
+// 5e: the reach alone, for rays that k_seed_rays reads where they are (rr_shade_rays_device): n_words = 3 x rays, which may pass 2^32
+__global__ __launch_bounds__(RR_BLOCK) void k_ray_reach(const float* __restrict__ origins, unsigned long long n_words, uint32_t* __restrict__ reach) {
+    float a[3] = {0.0f, 0.0f, 0.0f};
+    const unsigned long long stride = (unsigned long long)gridDim.x * RR_BLOCK;
+    unsigned long long g = (unsigned long long)blockIdx.x * RR_BLOCK + threadIdx.x;
+    uint32_t c = (uint32_t)(g % 3ull);
+    const uint32_t dc = (uint32_t)(stride % 3ull);
+    for (; g < n_words; g += stride) {
+        const float v = finite_abs(origins[g]);
+        a[0] = fmaxf(a[0], c == 0u ? v : 0.0f); a[1] = fmaxf(a[1], c == 1u ? v : 0.0f); a[2] = fmaxf(a[2], c == 2u ? v : 0.0f);
+        c += dc; if (c >= 3u) c -= 3u;
+    }
+    reach_merge(reach, a[0], a[1], a[2], 0xffffffffu, threadIdx.x & (RR_WAVE - 1));
+}
+
+// 5f: the walks' raw 16-byte hit records -> the 20-byte records of the ABI, as rr_trace_rays / rr_trace_shadow_rays build them on the host.
+//   closest (k_trace_closest): (bits(toi), item or -1, leaf-order slot | side bits, 0) -> rr_ray_hit {hit, item, id, face, toi}; the reference's
+//     face id is the triangle record's original face index (DTriX::t0.w) + n_tris for a back face, 0 for a ball
+//   SHADOW (k_query_shadow): (bits(toi), item, reference face id, occluded) -> rr_shadow_hit {occluded, item, id, face, toi}
+template <bool SHADOW>
+__global__ __launch_bounds__(RR_BLOCK) void k_unpack_hits(const uint4* __restrict__ hits, uint32_t n, const DItem* __restrict__ items, uint32_t n_items,
+                                                          const DTriX* __restrict__ trix, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_w[5 * RR_BLOCK];
+    const uint32_t tid = threadIdx.x;
+    const unsigned long long n_words = 5ull * n;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * RR_BLOCK; base < n; base += (unsigned long long)gridDim.x * RR_BLOCK) { // block-uniform
+        const unsigned long long i = base + tid;
+        if (i < n) {
+            const uint4 h = hits[i];
+            uint32_t w0 = 0u, w1 = 0xffffffffu, w2 = 0u, w3 = 0u, w4 = 0u;
+            if (SHADOW ? (h.w != 0u && h.y < n_items) : ((int32_t)h.y >= 0 && h.y < n_items)) {
+                const DItem* it = &items[h.y];
+                w0 = 1u; w1 = h.y; w2 = it->id; w4 = h.x;
+                if (SHADOW) w3 = h.z;
+                else if (!(it->flags & RR_IF_SPHERE)) {
+                    const uint32_t slot = h.z & 0x3fffffffu, back = h.z >> 31;
+                    w3 = __float_as_uint(trix[(unsigned long long)it->tri_base + slot].t0.w) + (back ? it->n_tris : 0u);
+                }
+            }
+            s_w[5 * tid] = w0; s_w[5 * tid + 1] = w1; s_w[5 * tid + 2] = w2; s_w[5 * tid + 3] = w3; s_w[5 * tid + 4] = w4;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const uint32_t w = k * RR_BLOCK + tid;
+            const unsigned long long g = 5ull * base + w;
+            if (g < n_words) out[g] = s_w[w];
+        }
+        __syncthreads();
+    }
+}
+
+// 5g: stream ids 0 .. n - 1 (rr_shade_rays_device without the caller's)
+__global__ __launch_bounds__(RR_BLOCK) void k_iota(uint32_t* __restrict__ ids, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ids[i] = i;
+}
+
+// ---------------------------------------------------------------------------
 // kernel 6: gather compact per-rank buffers into frame order (multi-GPU epilogue)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(RR_BLOCK) void k_gather_frame(const uint32_t* __restrict__ src_index, uint32_t n_pixels,

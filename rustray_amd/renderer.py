@@ -497,3 +497,99 @@ def render_region_torch(device_scene: capi.DeviceScene, cam, cfg, tf: TiledFrame
         ptrs = [parts["rgba"].data_ptr(), parts["normal"].data_ptr(), parts["depth"].data_ptr(), parts["object_id"].data_ptr()]
     device_scene.render_region_device(cam, cfg, tf.region(), ptrs, torch.cuda.current_stream(dev).cuda_stream, sample_xy)
     return parts
+
+
+# ---------------------------------------------------------------------------
+# the ray queries on torch tensors: rays produced on the GPU are traced where they are, on torch's current stream
+# ---------------------------------------------------------------------------
+def _ray_tensor(device_scene: capi.DeviceScene, t, name: str, shape_tail=(3,), dtype=None):
+    """`t` as the library reads it: a contiguous CUDA tensor of `dtype` (float32) and shape (n, *shape_tail) on the scene's device; raises otherwise."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a torch tensor is required, got {type(t).__name__}")
+    if not t.is_cuda or (t.device.index or 0) != device_scene.device:
+        raise ValueError(f"{name}: the tensor is on {t.device}, the scene on cuda:{device_scene.device}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: dtype {t.dtype}, {dtype} is required")
+    if t.dim() != 1 + len(shape_tail) or tuple(t.shape[1:]) != tuple(shape_tail):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, (n, {', '.join(map(str, shape_tail))}) is required" if shape_tail else f"{name}: shape {tuple(t.shape)}, (n,) is required")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor must be contiguous")
+    return t
+
+
+def _hit_views(rec, first: str) -> dict:
+    """An (n, 5) int32 tensor of 20-byte hit records and its named column views (no copy): `first` (hit / occluded), item_index,
+    object_id, face_id as int32 and distance viewed as float32."""
+    import torch
+    return {"records": rec, first: rec[:, 0], "item_index": rec[:, 1], "object_id": rec[:, 2], "face_id": rec[:, 3],
+            "distance": rec.view(torch.float32)[:, 4]}
+
+
+def trace_rays_torch(device_scene: capi.DeviceScene, origins, directions, depth: int = 2) -> dict:
+    """rr_trace_rays_device on torch's current stream of the scene's device: `origins` / `directions` are contiguous float32 CUDA tensors
+    of shape (n, 3) on that device (anything else raises).  Returns torch tensors, without a host copy and without a synchronisation
+    of the results: dict(records (n, 5) int32, hit, item_index (-1 = nothing hit), object_id, face_id, distance (float32 view))."""
+    import torch
+    o = _ray_tensor(device_scene, origins, "origins")
+    d = _ray_tensor(device_scene, directions, "directions")
+    if d.shape[0] != o.shape[0]:
+        raise ValueError(f"{o.shape[0]} origins, {d.shape[0]} directions")
+    dev = torch.device("cuda", device_scene.device)
+    n = int(o.shape[0])
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        if n:
+            device_scene.trace_rays_device(o.data_ptr(), d.data_ptr(), n, depth, rec.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return _hit_views(rec, "hit")
+
+
+def trace_shadow_rays_torch(device_scene: capi.DeviceScene, origins, directions, max_distance=None, depth: int = 2) -> dict:
+    """rr_trace_shadow_rays_device on torch's current stream: as trace_rays_torch, with `max_distance` a contiguous float32 CUDA tensor of
+    shape (n,) or None (no limit).  Returns dict(records (n, 5) int32, occluded, item_index (-1 = lit), object_id, face_id, distance)."""
+    import torch
+    o = _ray_tensor(device_scene, origins, "origins")
+    d = _ray_tensor(device_scene, directions, "directions")
+    if d.shape[0] != o.shape[0]:
+        raise ValueError(f"{o.shape[0]} origins, {d.shape[0]} directions")
+    lim = None
+    if max_distance is not None:
+        lim = _ray_tensor(device_scene, max_distance, "max_distance", shape_tail=())
+        if lim.shape[0] != o.shape[0]:
+            raise ValueError(f"{o.shape[0]} rays, {lim.shape[0]} distances")
+    dev = torch.device("cuda", device_scene.device)
+    n = int(o.shape[0])
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        if n:
+            device_scene.trace_shadow_rays_device(o.data_ptr(), d.data_ptr(), lim.data_ptr() if lim is not None else None, n, depth, rec.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+    return _hit_views(rec, "occluded")
+
+
+def shade_rays_torch(device_scene: capi.DeviceScene, origins, directions, cfg: rr_config, rays_per_result: int = 1, stream_ids=None) -> dict:
+    """rr_shade_rays_device on torch's current stream: `origins` / `directions` hold n_results * rays_per_result rays as contiguous float32
+    CUDA tensors of shape (n, 3), `stream_ids` n_results ids as a contiguous int32 CUDA tensor (the 32 bits are the id) or None.  Returns
+    dict(records (n_results, 8) float32, color (n_results, 3) LINEAR, depth, normal (n_results, 3), object_id (int32 view)), views of `records`."""
+    import torch
+    o = _ray_tensor(device_scene, origins, "origins")
+    d = _ray_tensor(device_scene, directions, "directions")
+    if d.shape[0] != o.shape[0]:
+        raise ValueError(f"{o.shape[0]} origins, {d.shape[0]} directions")
+    rpr = int(rays_per_result)
+    if rpr < 1 or o.shape[0] % rpr:
+        raise ValueError(f"{o.shape[0]} rays are not whole results of {rpr} rays")
+    n = int(o.shape[0]) // rpr
+    ids = None
+    if stream_ids is not None:
+        ids = _ray_tensor(device_scene, stream_ids, "stream_ids", shape_tail=(), dtype=torch.int32)
+        if ids.shape[0] != n:
+            raise ValueError(f"{n} results, {ids.shape[0]} stream ids")
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n:
+            device_scene.shade_rays_device(cfg, o.data_ptr(), d.data_ptr(), n, rpr, ids.data_ptr() if ids is not None else None, rec.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7]}
