@@ -493,7 +493,11 @@ int rr_pick(rr_scene* scene, const rr_camera* camera, int x, int y, rr_pick_resu
  * (reference src/raytracing.rs:429-490) for each of them, the generalisation of rr_pick (which is one such query for
  * a pixel-centre ray).  origins / directions: n * 3 floats (host); directions are used as given (trace does not
  * normalise).  `depth` is the recursion depth the candidate filter sees: reflection-only items are candidates for
- * depth > 1 only (:454).  out[i].item_index = 0xffffffff when nothing is hit. */
+ * depth > 1 only (:454).  out[i].item_index = 0xffffffff when nothing is hit.
+ * Memory: this call and rr_trace_shadow_rays are rr_trace_rays_device / rr_trace_shadow_rays_device (below) behind a staging copy.
+ * For the duration of the call they hold the caller's arrays and the answers on the device (12 + 12 + 20 B per ray, 4 more with
+ * limits); the packed records and raw hits are the handle's, as for the device forms: 56 B per ray (48 for a shadow query) of the
+ * largest such query so far, kept until rr_scene_destroy. */
 typedef struct rr_ray_hit {
     uint32_t hit;        /* 0 = None */
     uint32_t item_index;
@@ -577,16 +581,18 @@ int rr_shade_rays(rr_scene* scene, const rr_config* config, const float* origins
  *   caller need not synchronise after producing them on that stream -- and the call returns once its last launch is enqueued; the
  *   caller synchronises before it reads out_dev on the host.  The call WAITS inside for what it must learn from the device before it
  *   can enqueue the walk: once, for 16 bytes -- the largest finite |origin| per axis, for which the top level must be padded (found
- *   on the device, in float; the host forms scan the origins on the host), and the first bad max_distance.  rr_shade_rays_device
+ *   on the device, in float; rr_shade_rays scans its host origins on the host), and the first bad max_distance.  rr_shade_rays_device
  *   waits in addition where rr_shade_rays does: for its frame constants and for the size of every depth level.
  *   Scene state: a frame call like the host forms -- the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene,
  *   RR_ERR_DEVICE on a broken scene.  The handle's query buffers are shared, so a call on another stream than the handle's last
  *   call first waits for that stream, as rr_render_region_device does.  A scene edit or rr_scene_destroy waits for queries in
  *   flight; rr_scene_last_stats after rr_shade_rays_device behaves as after rr_render_region_device (it waits for the stream).
  *   Memory: nothing is allocated per call.  What the launches read after the call has returned belongs to the handle, grows on
- *   demand and is freed by rr_scene_destroy: 56 B per ray of the largest closest-hit or shadow query so far (the packed records and
- *   the walk's raw hits), 4 B per result of the largest radiance query without stream ids, plus what rr_shade_rays keeps (64 B per
- *   result, the ray arena).  A growth that fails is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.
+ *   demand and is freed by rr_scene_destroy: 56 B per ray of the largest closest-hit or shadow query so far, host or device form
+ *   (the packed records and the walk's raw hits), 4 B per result of the largest rr_shade_rays_device without stream ids, plus what
+ *   rr_shade_rays keeps (64 B per result, the ray arena).  A growth that fails is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.
+ *   The host forms are these calls behind a staging copy: the caller's arrays in buffers of the call, the null stream, and the
+ *   copy of the answers into `out`.
  *   cancel (rr_shade_rays_device): as rr_shade_rays; a call that is cancelled or fails part-way leaves the stream idle. */
 int rr_trace_rays_device(rr_scene* scene, const float* origins_dev, const float* directions_dev, uint32_t n, uint32_t depth,
                          rr_ray_hit* out_dev, void* hip_stream);

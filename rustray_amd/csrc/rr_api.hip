@@ -172,7 +172,6 @@ struct rr_scene {
     DevBuf items, nodes4, tnodes4, tris, trix, attrs, face_slot, materials, textures, texels, lights, flat_normals;
     DSceneView view{};
     std::vector<DItem> h_items;
-    std::vector<uint32_t> h_slot_face; // per mesh triangle: leaf-order slot -> original face index (rr_trace_rays reports the reference's face id)
     std::vector<ItemHost> item_host; // what rr_scene_update_materials needs to rebuild the item flag words
     // the meshes: where each one's records sit in the arenas (what an item takes from the mesh it names, rr_scene_set_items), how many
     // records the arenas hold (rr_scene_add_meshes appends behind them), the scene's own copy of the caller's arrays (the trees are
@@ -215,10 +214,10 @@ struct rr_scene {
     DevBuf region_xy, trace_order, sample_xy, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
     std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
     DevBuf tmp_out[4];
-    // device-buffer ray queries (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device): what their launches read and write
-    // after the call has returned belongs to the handle, grows on demand and is never shrunk.  query_rec: the packed records r0, r1, r2 and
-    // the walks' raw hits (16 + 16 + 8 + 16 = 56 B per ray of the largest closest-hit or shadow query; a shadow query uses 48 of them);
-    // query_words: QW_* below; query_ids: the stream ids 0 .. n - 1 of a radiance query without the caller's (4 B per result)
+    // ray queries (the host forms are the device forms behind a staging copy): what the launches of a device form read and write after the
+    // call has returned belongs to the handle, grows on demand and is never shrunk.  query_rec: the packed records r0, r1, r2 and the walks'
+    // raw hits (16 + 16 + 8 + 16 = 56 B per ray of the largest closest-hit or shadow query, host or device form; a shadow query uses 48 of
+    // them); query_words: QW_* below; query_ids: the stream ids 0 .. n - 1 of rr_shade_rays_device without the caller's (4 B per result)
     DevBuf query_rec[4], query_words, query_ids;
     DevBuf multi_part[4], multi_cat[4]; // rr_render_multi: this device's compact buffers; on device slot 0 the concatenation of all
     hipStream_t multi_stream = nullptr; // rr_render_multi: this handle's own non-blocking stream (created on first use)
@@ -570,7 +569,7 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     HIP_TRY(s->flat_normals.reserve(std::max<size_t>((size_t)r.n_flat_normals * sizeof(float4), 16)));
     // the host copies that the scene's edits and queries work from
     s->tex_width.swap(r.tex_width); s->h_textures.swap(r.dtex); s->h_dmat.swap(r.dmat); s->h_lights.swap(r.dlights);
-    s->h_items.swap(r.items); s->item_host.swap(r.item_host); s->h_slot_face.swap(r.slot_face);
+    s->h_items.swap(r.items); s->item_host.swap(r.item_host);
     s->mesh_table.swap(r.meshes); s->n_nodes4 = r.nodes4.size(); s->n_mesh_tris = r.tris.size(); s->blas_depth_limit = r.blas_depth_limit;
     s->h_meshes.reserve(fs->n_meshes);
     for (uint32_t i = 0; i < fs->n_meshes; i++) s->h_meshes.emplace_back(fs->meshes[i]);
@@ -892,10 +891,6 @@ extern "C" int rr_scene_add_meshes(rr_scene* s, const rr_mesh* meshes, uint32_t 
     a.meshes = s->mesh_table;
     a.tris_before = s->n_mesh_tris; a.nodes4_before = s->n_nodes4;
     RR_TRY(append_mesh_records(meshes, n_meshes, s->blas_depth_limit, (uint32_t)s->h_items.size(), &a));
-    std::vector<uint32_t> slot_face;
-    slot_face.reserve(s->h_slot_face.size() + a.slot_face.size());
-    slot_face = s->h_slot_face;
-    slot_face.insert(slot_face.end(), a.slot_face.begin(), a.slot_face.end());
     std::vector<HostMesh> h_meshes;
     h_meshes.reserve(s->h_meshes.size() + n_meshes);
     for (uint32_t i = 0; i < n_meshes; i++) h_meshes.emplace_back(meshes[i]);
@@ -908,7 +903,6 @@ extern "C" int rr_scene_add_meshes(rr_scene* s, const rr_mesh* meshes, uint32_t 
     keep_mesh_buffers(s, b);
     s->n_nodes4 = a.nodes4_before + a.nodes4.size(); s->n_mesh_tris = a.tris_before + a.tris.size();
     s->mesh_table.swap(a.meshes);
-    s->h_slot_face.swap(slot_face);
     for (HostMesh& m : h_meshes) s->h_meshes.push_back(std::move(m));
     *first_index = first;
     return RR_OK;
@@ -1010,15 +1004,13 @@ extern "C" int rr_scene_set_items(rr_scene* s, const rr_item* items, uint32_t n_
     HIP_TRY(hipMemset(d_tnodes4.p, 0, 2 * (size_t)capacity * sizeof(DNode4)));
     HIP_TRY(d_item_boxes.reserve(std::max<size_t>(trees.item_boxes.size() * sizeof(float4), 16)));
     RR_TRY(copy_tlas(trees, d_tnodes4.as<DNode4>(), capacity, d_item_boxes.as<float4>()));
-    std::vector<uint32_t> slot_face;
-    if (rebuild_meshes) slot_face = arenas.slot_face;
     RR_FAULT_POINT("set_items.device");
     HIP_TRY(hipDeviceSynchronize()); // the kernels above; and no frame enqueued through rr_render_region_device may still read what is freed below
 
     // ---- commit: buffers, host copies, the view
     if (rebuild_meshes) {
         keep_mesh_buffers(s, mesh_buffers);
-        s->mesh_table.swap(arenas.meshes); s->h_slot_face.swap(slot_face);
+        s->mesh_table.swap(arenas.meshes);
         s->n_nodes4 = arenas.nodes4.size(); s->n_mesh_tris = arenas.tris.size();
     }
     s->blas_depth_limit = blas_depth_limit; s->tlas_depth_limit = tlas_depth_limit;
@@ -1255,27 +1247,31 @@ static Level1Stages level1_stages(const rr_scene* s, uint64_t n) {
     return plan_level1_stages(Level1StageInputs{n, s->n_enabled_lights, s->tuning.shade_chunk_rays, RR_L1_STAGE_RAYS, RR_L1_BUFFERS});
 }
 
-// the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue (grown, never shrunk)
+// the ray arena for M rays and the shadow queue for sq_need rays, with at least valid_need words of lane masks (grown, never shrunk)
+static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t valid_need) {
+    const size_t elem[4] = {16, 16, 8, 16};
+    if (M > s->arena_cap) {
+        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(M * elem[k]));
+        s->arena_cap = M;
+    }
+    if (sq_need > s->sq_cap) { // (one word of sq_valid per 64 rays of the queue)
+        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(sq_need * 16));
+        HIP_TRY(s->sq_valid.reserve(std::max<uint64_t>(sq_need / RR_WAVE + 1, valid_need) * 8));
+        s->sq_cap = sq_need;
+    }
+    return RR_OK;
+}
+
+// the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue
 static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan) {
     uint64_t budget = 0;
     RR_TRY(queue_budget(s, &budget));
     const FramePlan& p = *plan = plan_frame(FramePlanInputs{npix, cfg->samples, cfg->max_recursion, budget, s->tuning.sample_group, min_passes,
                                                             s->arena_factor, s->n_enabled_lights, s->tuning.shade_chunk_rays});
-    const size_t elem[4] = {16, 16, 8, 16};
-    if (p.M > s->arena_cap) {
-        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(p.M * elem[k]));
-        s->arena_cap = p.M;
-    }
     HIP_TRY(s->hit1.reserve(p.B * 16));
     // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
     const Level1Stages sp = level1_stages(s, p.B);
-    const uint64_t sq_need = std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull);
-    if (sq_need > s->sq_cap) {
-        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(sq_need * 16));
-        HIP_TRY(s->sq_valid.reserve(std::max<uint64_t>(sq_need / RR_WAVE + 1, sp.valid_need) * 8));
-        s->sq_cap = sq_need;
-    }
-    return RR_OK;
+    return grow_ray_queues(s, p.M, std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need);
 }
 
 // Per-batch counters (level sizes, fetch heads, shadow shard counts) come out of zeroed segments of POOL_WORDS words.  A segment
@@ -2077,271 +2073,21 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
 } RR_GUARD_END("rr_pick")
 
 // ---------------------------------------------------------------------------
-// ray queries: Raytracing::trace for caller-supplied rays (the closest-hit kernel of the deeper levels on a queue that
-// the host fills), rr_pick generalised
-// ---------------------------------------------------------------------------
-extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out) try {
-    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
-    if (n == 0) return RR_OK;
-    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
-    RR_TRY(not_in_pass(s, "rr_trace_rays"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_FAULT_POINT("trace_rays.host");
-    std::vector<float4> r0(n), r1(n);
-    std::vector<uint2> r2(n);
-    {
-        double need[3] = {0.0, 0.0, 0.0};
-        for (uint32_t i = 0; i < n; i++)
-            for (int c = 0; c < 3; c++) {
-                const double a = std::fabs((double)origins[3 * (size_t)i + c]) * 1.001;
-                if (std::isfinite(a)) need[c] = std::max(need[c], a);
-            }
-        RR_TRY(ensure_tlas_reach(s, need));
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        r0[i] = make_float4(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], 1.0f);
-        r1[i] = make_float4(directions[3 * (size_t)i], directions[3 * (size_t)i + 1], directions[3 * (size_t)i + 2], 0.0f);
-        r2[i] = make_uint2(depth << 16, 1u);
-    }
-    DevBuf b0, b1, b2, bh, bc;
-    HIP_TRY(b0.reserve((size_t)n * 16)); HIP_TRY(b1.reserve((size_t)n * 16)); HIP_TRY(b2.reserve((size_t)n * 8)); HIP_TRY(bh.reserve((size_t)n * 16));
-    HIP_TRY(bc.reserve(256 + sizeof(DShadeConst))); // [0] the level's size, [4] the fetch head, [128] work counters, [256] scene view + (empty) frame constants
-    HIP_TRY(hipMemcpy(b0.p, r0.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b1.p, r1.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b2.p, r2.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    uint32_t words[64] = {n, 0u};
-    HIP_TRY(hipMemcpy(bc.p, words, sizeof words, hipMemcpyHostToDevice));
-    DRayQueue q{b0.as<float4>(), b1.as<float4>(), b2.as<uint2>(), bh.as<uint4>()};
-    {
-        DShadeConst hc;
-        memset(&hc, 0, sizeof hc);
-        hc.sc = s->view;
-        HIP_TRY(hipMemcpy(bc.as<char>() + 256, &hc, sizeof hc, hipMemcpyHostToDevice));
-    }
-    DPrimary pr{nullptr, 0ull, 0u, 1u};
-    RR_TRY(launch_trace_closest(s, false, q, bc.as<uint32_t>(), bc.as<uint32_t>() + 1, n, (const DShadeConst*)(bc.as<char>() + 256), nullptr, pr,
-                                (unsigned long long*)(bc.as<char>() + 128), nullptr));
-    std::vector<uint4> hits(n);
-    HIP_TRY(hipMemcpy(hits.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) {
-        rr_ray_hit& h = out[i];
-        memset(&h, 0, sizeof h);
-        h.item_index = 0xffffffffu;
-        if ((int32_t)hits[i].y >= 0) {
-            const DItem& it = s->h_items[hits[i].y];
-            h.hit = 1u; h.item_index = hits[i].y; h.object_id = it.id;
-            memcpy(&h.distance, &hits[i].x, 4);
-            if (!(it.flags & RR_IF_SPHERE)) { // leaf-order slot + side bits -> the reference's face id
-                const uint32_t slot = hits[i].z & 0x3fffffffu, back = hits[i].z >> 31;
-                h.face_id = s->h_slot_face[it.tri_base + slot] + (back ? it.n_tris : 0u);
-            }
-        }
-    }
-    return RR_OK;
-} RR_GUARD_END("rr_trace_rays")
-
-// Shadow queries for caller-supplied rays: Raytracing::trace(ray, true, true, depth) and `in_light = toi > len`
-// (reference src/raytracing.rs:429-490, :883-892) through the walk the frames' shadow kernel uses (k_query_shadow).
-extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const float* directions, const float* max_distance,
-                                    uint32_t n, uint32_t depth, rr_shadow_hit* out) try {
-    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
-    if (n == 0) return RR_OK;
-    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
-    if (max_distance)
-        for (uint32_t i = 0; i < n; i++)
-            if (!(max_distance[i] >= 0.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", i, (double)max_distance[i]);
-    RR_TRY(not_in_pass(s, "rr_trace_shadow_rays"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_FAULT_POINT("trace_shadow_rays.host");
-    std::vector<float4> r0(n), r1(n);
-    {
-        double need[3] = {0.0, 0.0, 0.0};
-        for (uint32_t i = 0; i < n; i++)
-            for (int c = 0; c < 3; c++) {
-                const double a = std::fabs((double)origins[3 * (size_t)i + c]) * 1.001;
-                if (std::isfinite(a)) need[c] = std::max(need[c], a);
-            }
-        RR_TRY(ensure_tlas_reach(s, need));
-    }
-    float depth_bits;
-    memcpy(&depth_bits, &depth, 4);
-    for (uint32_t i = 0; i < n; i++) {
-        // no limit (NULL, +inf): what k_shade passes for a directional light
-        const float limit = max_distance ? std::min(max_distance[i], RR_FLT_MAX) : RR_FLT_MAX;
-        r0[i] = make_float4(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], limit);
-        r1[i] = make_float4(directions[3 * (size_t)i], directions[3 * (size_t)i + 1], directions[3 * (size_t)i + 2], depth_bits);
-    }
-    DevBuf b0, b1, bh, bc;
-    HIP_TRY(b0.reserve((size_t)n * 16)); HIP_TRY(b1.reserve((size_t)n * 16)); HIP_TRY(bh.reserve((size_t)n * 16));
-    HIP_TRY(bc.reserve(64)); // [0] the fetch head
-    HIP_TRY(hipMemcpy(b0.p, r0.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b1.p, r1.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(bc.p, 0, 64));
-    RR_TRY(launch_query_shadow(s, b0.as<float4>(), b1.as<float4>(), n, bc.as<uint32_t>(), bh.as<uint4>(), nullptr));
-    std::vector<uint4> hits(n);
-    HIP_TRY(hipMemcpy(hits.data(), bh.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) {
-        rr_shadow_hit& h = out[i];
-        memset(&h, 0, sizeof h);
-        h.item_index = 0xffffffffu;
-        if (hits[i].w != 0u && hits[i].y < s->h_items.size()) {
-            h.occluded = 1u; h.item_index = hits[i].y; h.object_id = s->h_items[hits[i].y].id; h.face_id = hits[i].z;
-            memcpy(&h.distance, &hits[i].x, 4);
-        }
-    }
-    return RR_OK;
-} RR_GUARD_END("rr_trace_shadow_rays")
-
-// ---------------------------------------------------------------------------
-// radiance queries: Raytracing::get_color_depth_normal_id(scene, ray, 1) (reference src/raytracing.rs:720-998) for caller-supplied
-// rays -- what `render` calls per sample, without its pinhole / DOF camera.  The caller's rays are seeded as depth level 1 of the
-// frame's own level walk (k_seed_rays, run_level's seeded form), batch by batch (rr_frame_plan.h plan_ray_batches), into one
-// accumulator slot per result; k_resolve_rays returns what k_resolve computes before its clamp.
-// Per-frame state of the handle this call shares with rr_render, and why the next frame does not see it: the shade constants, the
-// accumulators and the counter pool are rewritten by every frame; the arena and the shadow queue only grow (a frame takes what it
-// needs from the front); the slot -> pixel map is this call's own buffer (FrameRun::slot_xy), so the cached region map, the
-// sub-sample table and arena_factor are not touched at all.
-// ---------------------------------------------------------------------------
-static_assert(sizeof(rr_radiance) == 32 && offsetof(rr_radiance, depth) == 12 && offsetof(rr_radiance, normal) == 16 && offsetof(rr_radiance, object_id) == 28,
-              "k_resolve_rays writes rr_radiance as two float4");
-static const uint32_t RESOLVE_RAYS_CHUNK = 1u << 22; // results per k_resolve_rays launch and read-back (128 MB of staging at most)
-
-// the batches of one call, in order; whatever ends them early leaves the stream idle (shade_rays_locked)
-static int run_ray_batches(FrameRun& f, const float* origins, const float* directions, uint32_t rays_per_result, float* d_origins, float* d_dirs) {
-    rr_scene* s = f.s;
-    const uint64_t B = f.plan.B, n_rays = f.plan.total_primary;
-    for (uint64_t first = 0; first < n_rays; first += B) {
-        if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rays - first);
-        RR_TRY(f.pool.start_batch());
-        uint32_t* level1_count = f.pool.take(1);
-        if (!level1_count) return counters_exhausted();
-        // (stream-ordered: the copies wait for the kernels of the batch before, which read the same staging buffers)
-        HIP_TRY(hipMemcpyAsync(d_origins, origins + 3ull * first, 12ull * nb, hipMemcpyHostToDevice, f.st));
-        HIP_TRY(hipMemcpyAsync(d_dirs, directions + 3ull * first, 12ull * nb, hipMemcpyHostToDevice, f.st));
-        hipLaunchKernelGGL(k_seed_rays, dim3((nb + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, d_origins, d_dirs, (unsigned long long)first, nb, rays_per_result,
-                           f.queue_at(0), level1_count, s->counters.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        s->stats.batches++;
-        RR_TRY(run_level(f, 1, 0, nb, level1_count));
-        HIP_TRY(hipGetLastError());
-        if (f.cancel && first + B < n_rays) HIP_TRY(hipStreamSynchronize(f.st)); // only a caller that can cancel needs the host to keep pace
-    }
-    return RR_OK;
-}
-
-static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
-                             const uint32_t* stream_ids, rr_radiance* out, const volatile int* cancel) {
-    const hipStream_t st = nullptr;
-    if (st != s->last_stream) { HIP_TRY(hipStreamSynchronize(s->last_stream)); s->last_stream = st; }
-    resolve_timers(s);
-    memset(&s->stats, 0, sizeof s->stats);
-    s->stats_final = false;
-    s->overlap_stages = 0;
-    const uint64_t n_rays = (uint64_t)n_results * rays_per_result;
-    {
-        double need[3] = {0.0, 0.0, 0.0};
-        for (uint64_t i = 0; i < n_rays; i++)
-            for (int c = 0; c < 3; c++) {
-                const double a = std::fabs((double)origins[3 * i + c]) * 1.001;
-                if (std::isfinite(a)) need[c] = std::max(need[c], a);
-            }
-        RR_TRY(ensure_tlas_reach(s, need));
-    }
-    // the frame constants k_shade reads: `samples` decides which ray of a result carries its object id; a width of 65536 makes
-    // k_shade's RNG pixel (xy >> 16) * width + (xy & 0xffff) the 32-bit id itself
-    DFrame fr;
-    memset(&fr, 0, sizeof fr);
-    fr.width = 65536u; fr.height = 65536u; fr.samples = rays_per_result; fr.cell_size = 1u;
-    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u;
-    fr.fog_density = cfg->fog_density;
-    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
-    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
-    fr.n_region_pixels = n_results;
-    RR_TRY(upload_shade_const(s, fr, st));
-    DevBuf d_ids, d_origins, d_dirs, d_out;
-    HIP_TRY(d_ids.reserve((size_t)n_results * 4));
-    if (stream_ids) HIP_TRY(hipMemcpy(d_ids.p, stream_ids, (size_t)n_results * 4, hipMemcpyHostToDevice));
-    else {
-        std::vector<uint32_t> iota(std::min<uint32_t>(n_results, 1u << 20));
-        for (uint32_t j0 = 0; j0 < n_results; j0 += (uint32_t)iota.size()) {
-            const uint32_t n = std::min<uint32_t>((uint32_t)iota.size(), n_results - j0);
-            for (uint32_t j = 0; j < n; j++) iota[j] = j0 + j;
-            HIP_TRY(hipMemcpy(d_ids.as<uint32_t>() + j0, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        }
-    }
-    DAccum acc;
-    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
-    uint64_t budget = 0;
-    RR_TRY(queue_budget(s, &budget));
-    const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->n_enabled_lights, s->tuning.shade_chunk_rays);
-    if (plan.M > s->arena_cap) {
-        const size_t elem[4] = {16, 16, 8, 16};
-        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(plan.M * elem[k]));
-        s->arena_cap = plan.M;
-    }
-    if (plan.sq_need > s->sq_cap) { // (sq_valid as plan_queues sizes it: a frame's stage buffers need one word per 64 rays of the queue)
-        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(plan.sq_need * 16));
-        HIP_TRY(s->sq_valid.reserve((plan.sq_need / RR_WAVE + 1) * 8));
-        s->sq_cap = plan.sq_need;
-    }
-    HIP_TRY(d_origins.reserve(12ull * plan.B));
-    HIP_TRY(d_dirs.reserve(12ull * plan.B));
-    HIP_TRY(d_out.reserve(32ull * std::min<uint32_t>(n_results, RESOLVE_RAYS_CHUNK)));
-    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = d_ids.as<uint32_t>();
-    f.seeded = true;
-    HIP_TRY(hipEventRecord(s->frame_a, st));
-    int rc = run_ray_batches(f, origins, directions, rays_per_result, d_origins.as<float>(), d_dirs.as<float>());
-    for (uint32_t r0 = 0; r0 < n_results && rc == RR_OK; r0 += RESOLVE_RAYS_CHUNK) {
-        const uint32_t n = std::min<uint32_t>(RESOLVE_RAYS_CHUNK, n_results - r0);
-        hipLaunchKernelGGL(k_resolve_rays, dim3((n + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, acc, r0, n, rays_per_result, d_out.as<float4>());
-        const hipError_t e = hipMemcpyAsync(out + r0, d_out.p, 32ull * n, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) rc = fail(RR_ERR_DEVICE, "rr_shade_rays: %s", hipGetErrorString(e));
-    }
-    (void)hipEventRecord(s->frame_b, st);
-    const hipError_t e = hipStreamSynchronize(st); // before this call's buffers go: nothing of it is left in flight, whatever ended it
-    if (rc != RR_OK) return rc;
-    HIP_TRY(e);
-    HIP_TRY(hipGetLastError());
-    return RR_OK;
-}
-
-extern "C" int rr_shade_rays(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
-                             const uint32_t* stream_ids, rr_radiance* out, const volatile int* cancel) try {
-    if (!s || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (rays_per_result == 0) return fail(RR_ERR_INVALID_ARGUMENT, "rays_per_result must be >= 1");
-    if (rays_per_result > RR_MAX_SAMPLES_WITH_TABLE) return fail(RR_ERR_UNSUPPORTED, "rays_per_result %u > %u", rays_per_result, RR_MAX_SAMPLES_WITH_TABLE);
-    if (cfg->max_recursion > RR_MAX_RECURSION) return fail(RR_ERR_UNSUPPORTED, "max_recursion %u > %u", cfg->max_recursion, RR_MAX_RECURSION);
-    if (n_results == 0) return RR_OK;
-    if (n_results > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u results in one call", n_results);
-    if (!origins || !directions || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    RR_TRY(not_in_pass(s, "rr_shade_rays"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_FAULT_POINT("shade_rays.host");
-    return shade_rays_locked(s, cfg, origins, directions, n_results, rays_per_result, stream_ids, out, cancel);
-} RR_GUARD_END("rr_shade_rays")
-
-// ---------------------------------------------------------------------------
-// device-buffer, stream-ordered forms of the three ray queries: rays that were produced on the device are traced where they are and
-// the answers are consumed in stream order.  The streaming kernels of rr_kernels.hip (5d .. 5g) stand where the host forms loop on
-// the host; the walks, their launch sites and the level walk of rr_shade_rays are the host forms' own.
-// Each call waits ONCE for the device, for the 16 bytes of query_words[QW_REACH]: the largest finite |origin| per axis (the top
-// level must be padded for it BEFORE the walk is enqueued: ensure_tlas_reach, the same * 1.001 in double as the host forms) and the
-// first bad max_distance.  rr_shade_rays_device additionally waits where rr_shade_rays' level walk does (the level sizes).
-// Everything the launches touch after the call has returned is the caller's or the handle's (rr_scene::query_*, the arena): a scene
-// edit waits for the device before it overwrites what they read, and rr_scene_destroy before it frees.
+// ray queries: Raytracing::trace for caller-supplied rays (rr_pick generalised), closest-hit and shadow form, and
+// Raytracing::get_color_depth_normal_id for them (rr_shade_rays).  Each query has ONE body, which works on buffers the scene's
+// device can address and on a stream: the *_device entry points check the caller's pointers and run it in place; the host entry
+// points are the device forms behind a staging copy -- the caller's arrays go into buffers of the call as they are, the body runs
+// on the null stream, and the copy of the answers into `out` is the synchronisation.
+// The streaming kernels of rr_kernels.hip (5d .. 5g) turn the caller's 12-byte rays into the walks' records and the walks' raw
+// hits into the 20-byte records of the ABI; the walks and their launch sites are the frames' own.
+// A closest-hit or shadow query waits ONCE for the device, for the 16 bytes of query_words[QW_REACH]: the largest finite |origin|
+// per axis (the top level must be padded for it BEFORE the walk is enqueued: ensure_tlas_reach, * 1.001 in double) and the first
+// bad max_distance.  A radiance query additionally waits where a frame's level walk does (the level sizes).
+// Everything the launches of a device form touch after the call has returned is the caller's or the handle's (rr_scene::query_*,
+// the arena): a scene edit waits for the device before it overwrites what they read, and rr_scene_destroy before it frees.
 // ---------------------------------------------------------------------------
 enum : size_t { QW_COUNT = 0, QW_HEAD = 4, QW_REACH = 64, QW_COUNTERS = 128, QW_CONST = 256 }; // byte offsets into rr_scene::query_words
+static_assert(sizeof(rr_ray_hit) == 20 && sizeof(rr_shadow_hit) == 20, "k_unpack_hits writes five words per ray");
 
 // `p` (argument `arg` of `fn`) must be memory the scene's device can address: decided by query_pointer_ok (rr_query_pointers.h)
 static int check_query_pointer(const rr_scene* s, const void* p, const char* fn, const char* arg) {
@@ -2392,7 +2138,7 @@ static int preset_reach(rr_scene* s, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(w + QW_REACH + 12, 0xff, 4, st));
     return RR_OK;
 }
-// THE wait of a device-buffer query: reads the reach words back (pinned, s->h_count[4 .. 7]) and pads the top level as the host forms do.
+// THE wait of a query on device buffers: reads the reach words back (pinned, s->h_count[4 .. 7]) and pads the top level for them.
 // *first_bad = the first index with a bad limit, or 0xffffffff.
 static int await_reach(rr_scene* s, hipStream_t st, uint32_t* first_bad) {
     uint32_t* h = s->h_count + 4;
@@ -2411,13 +2157,106 @@ static int await_reach(rr_scene* s, hipStream_t st, uint32_t* first_bad) {
 
 static int query_grid(const rr_scene* s, uint64_t n) { return (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u); }
 
-extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out,
-                                    void* hip_stream) try {
+// a host array of the caller's in a device buffer of the call (blocking)
+static int stage_in(DevBuf* b, const void* src, size_t bytes) {
+    HIP_TRY(b->reserve(bytes));
+    HIP_TRY(hipMemcpy(b->p, src, bytes, hipMemcpyHostToDevice));
+    return RR_OK;
+}
+
+// ---- closest-hit and shadow queries
+// Shadow queries: Raytracing::trace(ray, true, true, depth) and `in_light = toi > len` (reference src/raytracing.rs:429-490,
+// :883-892) through the walk the frames' shadow kernel uses (k_query_shadow); closest-hit queries: the closest-hit kernel of the
+// deeper levels on a queue that k_pack_rays fills.
+
+// The argument checks of the four entry points, in the order the tests pin; `device`: the alignment rule of the device forms.
+// n == 0 passes: the caller returns RR_OK before it touches anything.
+static int check_trace_args(const char* fn, bool device, const rr_scene* s, const float* origins, const float* directions, const float* max_distance,
+                            uint32_t n, uint32_t depth, const void* out) {
     if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
     if (n == 0) return RR_OK;
     if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
-    if (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)out) & 3u) return fail(RR_ERR_INVALID_ARGUMENT, "rr_trace_rays_device: a buffer is not 4-byte aligned");
+    if (device && (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)max_distance | (uintptr_t)out) & 3u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: a buffer is not 4-byte aligned", fn);
+    return RR_OK;
+}
+
+// One query on device buffers, in stream order (the caller holds the lock): SHADOW = limits (or NULL) and the shadow walk into
+// rr_shadow_hit records, else the closest-hit walk into rr_ray_hit records.  The only wait is await_reach.
+template <bool SHADOW>
+static int trace_rays_locked(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth, void* out,
+                             hipStream_t st) {
+    RR_TRY(take_stream(s, st));
+    RR_TRY(reserve_query_records(s, n, SHADOW));
+    char* w = s->query_words.as<char>();
+    const DRayQueue q{s->query_rec[0].as<float4>(), s->query_rec[1].as<float4>(), SHADOW ? nullptr : s->query_rec[2].as<uint2>(), s->query_rec[3].as<uint4>()};
+    RR_TRY(preset_reach(s, st));
+    hipLaunchKernelGGL(k_pack_rays<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, origins, directions, max_distance, n, depth, q.r0, q.r1, q.r2,
+                       (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_REACH));
+    HIP_TRY(hipGetLastError());
+    uint32_t first_bad = 0;
+    RR_TRY(await_reach(s, st, &first_bad));
+    if (SHADOW && first_bad != 0xffffffffu) { // (the stream is idle: the value for the message comes with one more small copy)
+        float v = 0.0f;
+        HIP_TRY(hipMemcpy(&v, max_distance + first_bad, 4, hipMemcpyDefault));
+        return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", first_bad, (double)v);
+    }
+    if (SHADOW) RR_TRY(launch_query_shadow(s, q.r0, q.r1, n, (uint32_t*)(w + QW_HEAD), q.hit, st));
+    else { // (the <false> build reads neither the frame constants nor the work counters; both pointers name the handle's words all the same)
+        const DPrimary pr{nullptr, 0ull, 0u, 1u};
+        RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), nullptr, pr,
+                                    (unsigned long long*)(w + QW_COUNTERS), st));
+    }
+    hipLaunchKernelGGL(k_unpack_hits<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+// The host form: the caller's arrays as they are (12 + 12 B per ray, 4 B of limit) and the 20-byte answers in buffers of the call,
+// freed on return (hipFree waits for what a failed call left in flight); trace_rays_locked on the null stream between them.
+template <bool SHADOW>
+static int trace_rays_staged(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth, void* out) {
+    DevBuf d_origins, d_dirs, d_limits, d_out;
+    RR_TRY(stage_in(&d_origins, origins, 12ull * n));
+    RR_TRY(stage_in(&d_dirs, directions, 12ull * n));
+    if (max_distance) RR_TRY(stage_in(&d_limits, max_distance, 4ull * n));
+    HIP_TRY(d_out.reserve(20ull * n));
+    RR_TRY(trace_rays_locked<SHADOW>(s, d_origins.as<float>(), d_dirs.as<float>(), d_limits.as<float>(), n, depth, d_out.p, nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.p, 20ull * n, hipMemcpyDeviceToHost)); // waits for the launches: `out` is written by a finished query only
+    return RR_OK;
+}
+
+extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out) try {
+    RR_TRY(check_trace_args("rr_trace_rays", false, s, origins, directions, nullptr, n, depth, out));
+    if (n == 0) return RR_OK;
+    RR_TRY(not_in_pass(s, "rr_trace_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("trace_rays.host");
+    return trace_rays_staged<false>(s, origins, directions, nullptr, n, depth, out);
+} RR_GUARD_END("rr_trace_rays")
+
+extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const float* directions, const float* max_distance,
+                                    uint32_t n, uint32_t depth, rr_shadow_hit* out) try {
+    RR_TRY(check_trace_args("rr_trace_shadow_rays", false, s, origins, directions, max_distance, n, depth, out));
+    if (n == 0) return RR_OK;
+    if (max_distance) // (the body refuses the same limits; here the refusal costs no upload)
+        for (uint32_t i = 0; i < n; i++)
+            if (!(max_distance[i] >= 0.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", i, (double)max_distance[i]);
+    RR_TRY(not_in_pass(s, "rr_trace_shadow_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("trace_shadow_rays.host");
+    return trace_rays_staged<true>(s, origins, directions, max_distance, n, depth, out);
+} RR_GUARD_END("rr_trace_shadow_rays")
+
+extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out,
+                                    void* hip_stream) try {
+    RR_TRY(check_trace_args("rr_trace_rays_device", true, s, origins, directions, nullptr, n, depth, out));
+    if (n == 0) return RR_OK;
     RR_TRY(not_in_pass(s, "rr_trace_rays_device"));
     std::lock_guard<std::mutex> lk(s->mu);
     RR_TRY(check_intact(s));
@@ -2426,34 +2265,13 @@ extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const flo
     RR_TRY(check_query_pointer(s, origins, "rr_trace_rays_device", "origins_dev"));
     RR_TRY(check_query_pointer(s, directions, "rr_trace_rays_device", "directions_dev"));
     RR_TRY(check_query_pointer(s, out, "rr_trace_rays_device", "out_dev"));
-    const hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(take_stream(s, st));
-    RR_TRY(reserve_query_records(s, n, false));
-    char* w = s->query_words.as<char>();
-    DRayQueue q{s->query_rec[0].as<float4>(), s->query_rec[1].as<float4>(), s->query_rec[2].as<uint2>(), s->query_rec[3].as<uint4>()};
-    RR_TRY(preset_reach(s, st));
-    hipLaunchKernelGGL(k_pack_rays<false>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, origins, directions, (const float*)nullptr, n, depth, q.r0, q.r1, q.r2,
-                       (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_REACH));
-    HIP_TRY(hipGetLastError());
-    uint32_t first_bad = 0;
-    RR_TRY(await_reach(s, st, &first_bad));
-    DPrimary pr{nullptr, 0ull, 0u, 1u};
-    // (the <false> build reads neither the frame constants nor the work counters; both pointers name the handle's words all the same)
-    RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), nullptr, pr,
-                                (unsigned long long*)(w + QW_COUNTERS), st));
-    hipLaunchKernelGGL(k_unpack_hits<false>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
-    HIP_TRY(hipGetLastError());
-    return RR_OK;
+    return trace_rays_locked<false>(s, origins, directions, nullptr, n, depth, out, (hipStream_t)hip_stream);
 } RR_GUARD_END("rr_trace_rays_device")
 
 extern "C" int rr_trace_shadow_rays_device(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth,
                                            rr_shadow_hit* out, void* hip_stream) try {
-    if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
+    RR_TRY(check_trace_args("rr_trace_shadow_rays_device", true, s, origins, directions, max_distance, n, depth, out));
     if (n == 0) return RR_OK;
-    if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
-    if (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)max_distance | (uintptr_t)out) & 3u)
-        return fail(RR_ERR_INVALID_ARGUMENT, "rr_trace_shadow_rays_device: a buffer is not 4-byte aligned");
     RR_TRY(not_in_pass(s, "rr_trace_shadow_rays_device"));
     std::lock_guard<std::mutex> lk(s->mu);
     RR_TRY(check_intact(s));
@@ -2463,109 +2281,29 @@ extern "C" int rr_trace_shadow_rays_device(rr_scene* s, const float* origins, co
     RR_TRY(check_query_pointer(s, directions, "rr_trace_shadow_rays_device", "directions_dev"));
     if (max_distance) RR_TRY(check_query_pointer(s, max_distance, "rr_trace_shadow_rays_device", "max_distance_dev"));
     RR_TRY(check_query_pointer(s, out, "rr_trace_shadow_rays_device", "out_dev"));
-    const hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(take_stream(s, st));
-    RR_TRY(reserve_query_records(s, n, true));
-    char* w = s->query_words.as<char>();
-    float4 *r0 = s->query_rec[0].as<float4>(), *r1 = s->query_rec[1].as<float4>();
-    uint4* raw = s->query_rec[3].as<uint4>();
-    RR_TRY(preset_reach(s, st));
-    hipLaunchKernelGGL(k_pack_rays<true>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, origins, directions, max_distance, n, depth, r0, r1, (uint2*)nullptr,
-                       (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_REACH));
-    HIP_TRY(hipGetLastError());
-    uint32_t first_bad = 0;
-    RR_TRY(await_reach(s, st, &first_bad));
-    if (first_bad != 0xffffffffu) { // (the stream is idle: the value for the message comes with one more small copy)
-        float v = 0.0f;
-        HIP_TRY(hipMemcpy(&v, max_distance + first_bad, 4, hipMemcpyDefault));
-        return fail(RR_ERR_INVALID_ARGUMENT, "max_distance[%u] = %g (a distance >= 0, or +inf for no limit)", first_bad, (double)v);
-    }
-    RR_TRY(launch_query_shadow(s, r0, r1, n, (uint32_t*)(w + QW_HEAD), raw, st));
-    hipLaunchKernelGGL(k_unpack_hits<true>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, raw, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
-    HIP_TRY(hipGetLastError());
-    return RR_OK;
+    return trace_rays_locked<true>(s, origins, directions, max_distance, n, depth, out, (hipStream_t)hip_stream);
 } RR_GUARD_END("rr_trace_shadow_rays_device")
 
-// rr_shade_rays on the caller's device buffers: k_seed_rays reads them batch by batch where they are, the stream ids are used in
-// place (or written by k_iota into the handle's buffer) and k_resolve_rays writes straight into out_dev.  The handle's state is
-// treated as shade_rays_locked treats it; nothing of the call is freed behind launches in flight, because nothing is the call's own.
-static int shade_rays_device_locked(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
-                                    const uint32_t* stream_ids, rr_radiance* out, hipStream_t st, const volatile int* cancel) {
-    RR_TRY(take_stream(s, st));
-    resolve_timers(s);
-    memset(&s->stats, 0, sizeof s->stats);
-    s->stats_final = false;
-    s->overlap_stages = 0;
-    const uint64_t n_rays = (uint64_t)n_results * rays_per_result;
-    HIP_TRY(s->query_words.reserve(QW_CONST + sizeof(DShadeConst)));
-    if (!stream_ids) HIP_TRY(s->query_ids.reserve((size_t)n_results * 4));
-    RR_TRY(preset_reach(s, st));
-    hipLaunchKernelGGL(k_ray_reach, dim3(query_grid(s, 3ull * n_rays)), dim3(RR_BLOCK), 0, st, origins, (unsigned long long)(3ull * n_rays),
-                       (uint32_t*)(s->query_words.as<char>() + QW_REACH));
-    HIP_TRY(hipGetLastError());
-    uint32_t first_bad = 0;
-    RR_TRY(await_reach(s, st, &first_bad));
-    DFrame fr; // as shade_rays_locked
-    memset(&fr, 0, sizeof fr);
-    fr.width = 65536u; fr.height = 65536u; fr.samples = rays_per_result; fr.cell_size = 1u;
-    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u;
-    fr.fog_density = cfg->fog_density;
-    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
-    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
-    fr.n_region_pixels = n_results;
-    RR_TRY(upload_shade_const(s, fr, st));
-    if (!stream_ids) {
-        hipLaunchKernelGGL(k_iota, dim3((n_results + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, s->query_ids.as<uint32_t>(), n_results);
-        HIP_TRY(hipGetLastError());
-        stream_ids = s->query_ids.as<uint32_t>();
-    }
-    DAccum acc;
-    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
-    uint64_t budget = 0;
-    RR_TRY(queue_budget(s, &budget));
-    const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->n_enabled_lights, s->tuning.shade_chunk_rays);
-    if (plan.M > s->arena_cap) {
-        const size_t elem[4] = {16, 16, 8, 16};
-        for (int k = 0; k < 4; k++) HIP_TRY(s->arena[k].reserve(plan.M * elem[k]));
-        s->arena_cap = plan.M;
-    }
-    if (plan.sq_need > s->sq_cap) {
-        for (int k = 0; k < 3; k++) HIP_TRY(s->sq[k].reserve(plan.sq_need * 16));
-        HIP_TRY(s->sq_valid.reserve((plan.sq_need / RR_WAVE + 1) * 8));
-        s->sq_cap = plan.sq_need;
-    }
-    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = stream_ids;
-    f.seeded = true;
-    HIP_TRY(hipEventRecord(s->frame_a, st));
-    int rc = RR_OK;
-    const uint64_t B = plan.B;
-    for (uint64_t first = 0; first < n_rays && rc == RR_OK; first += B) { // run_ray_batches without its staging copies
-        if (cancel && *cancel) { rc = fail(RR_ERR_CANCELLED, "cancelled"); break; }
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rays - first);
-        rc = f.pool.start_batch();
-        if (rc != RR_OK) break;
-        uint32_t* level1_count = f.pool.take(1);
-        if (!level1_count) { rc = counters_exhausted(); break; }
-        hipLaunchKernelGGL(k_seed_rays, dim3((nb + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, origins + 3ull * first, directions + 3ull * first,
-                           (unsigned long long)first, nb, rays_per_result, f.queue_at(0), level1_count, s->counters.as<unsigned long long>());
-        s->stats.batches++;
-        rc = run_level(f, 1, 0, nb, level1_count);
-        if (rc == RR_OK && cancel && first + B < n_rays && hipStreamSynchronize(st) != hipSuccess) rc = fail(RR_ERR_DEVICE, "rr_shade_rays_device: the stream failed");
-    }
-    for (uint32_t r0 = 0; r0 < n_results && rc == RR_OK; r0 += RESOLVE_RAYS_CHUNK) {
-        const uint32_t n = std::min<uint32_t>(RESOLVE_RAYS_CHUNK, n_results - r0);
-        hipLaunchKernelGGL(k_resolve_rays, dim3((n + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, acc, r0, n, rays_per_result, (float4*)out + 2ull * r0);
-    }
-    (void)hipEventRecord(s->frame_b, st);
-    if (rc != RR_OK) { (void)hipStreamSynchronize(st); return rc; } // a call that ends early leaves the stream idle, as the host form does
-    HIP_TRY(hipGetLastError());
-    return RR_OK;
-}
+// ---- radiance queries: Raytracing::get_color_depth_normal_id(scene, ray, 1) (reference src/raytracing.rs:720-998) for caller-supplied
+// rays -- what `render` calls per sample, without its pinhole / DOF camera.  The caller's rays are seeded as depth level 1 of the
+// frame's own level walk (k_seed_rays, run_level's seeded form), batch by batch (rr_frame_plan.h plan_ray_batches), into one
+// accumulator slot per result; k_resolve_rays returns what k_resolve computes before its clamp.
+// Per-frame state of the handle this call shares with rr_render, and why the next frame does not see it: the shade constants, the
+// accumulators and the counter pool are rewritten by every frame; the arena and the shadow queue only grow (a frame takes what it
+// needs from the front); the slot -> pixel map is this call's own buffer (FrameRun::slot_xy), so the cached region map, the
+// sub-sample table and arena_factor are not touched at all.
+static_assert(sizeof(rr_radiance) == 32 && offsetof(rr_radiance, depth) == 12 && offsetof(rr_radiance, normal) == 16 && offsetof(rr_radiance, object_id) == 28,
+              "k_resolve_rays writes rr_radiance as two float4");
+static const uint32_t RESOLVE_RAYS_CHUNK = 1u << 22; // results per k_resolve_rays launch and, in the host form, read-back (128 MB of staging at most)
 
-extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
-                                    const uint32_t* stream_ids, rr_radiance* out, void* hip_stream, const volatile int* cancel) try {
+// Where the rays, the stream ids (or NULL) and the results of one radiance query live: `host` = the caller's host arrays, which
+// shade_rays_locked stages batch by batch and chunk by chunk; else buffers the scene's device can address, used where they are.
+struct RayIo { const float* origins; const float* directions; const uint32_t* stream_ids; rr_radiance* out; bool host; };
+
+// The argument checks of the two entry points, in the order the tests pin; `device`: the alignment rule of the device form.
+// n_results == 0 passes: the caller returns RR_OK before it touches anything.
+static int check_shade_args(const char* fn, bool device, const rr_scene* s, const rr_config* cfg, const float* origins, const float* directions,
+                            const uint32_t* stream_ids, const rr_radiance* out, uint32_t n_results, uint32_t rays_per_result) {
     if (!s || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (rays_per_result == 0) return fail(RR_ERR_INVALID_ARGUMENT, "rays_per_result must be >= 1");
     if (rays_per_result > RR_MAX_SAMPLES_WITH_TABLE) return fail(RR_ERR_UNSUPPORTED, "rays_per_result %u > %u", rays_per_result, RR_MAX_SAMPLES_WITH_TABLE);
@@ -2573,8 +2311,148 @@ extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const flo
     if (n_results == 0) return RR_OK;
     if (n_results > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u results in one call", n_results);
     if (!origins || !directions || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if ((((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)stream_ids) & 3u) || ((uintptr_t)out & 15u))
-        return fail(RR_ERR_INVALID_ARGUMENT, "rr_shade_rays_device: the ray buffers must be 4-byte aligned and out_dev 16-byte aligned");
+    if (device && ((((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)stream_ids) & 3u) || ((uintptr_t)out & 15u)))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: the ray buffers must be 4-byte aligned and out_dev 16-byte aligned", fn);
+    return RR_OK;
+}
+
+// the top level padded for host origins (n_words = 3 x rays): what k_ray_reach and await_reach do for rays on the device
+static int ensure_host_ray_reach(rr_scene* s, const float* origins, uint64_t n_words) {
+    double need[3] = {0.0, 0.0, 0.0};
+    for (uint64_t g = 0; g < n_words; g++) {
+        const double a = std::fabs((double)origins[g]) * 1.001;
+        if (std::isfinite(a)) need[g % 3] = std::max(need[g % 3], a);
+    }
+    return ensure_tlas_reach(s, need);
+}
+
+// the frame constants k_shade reads: `samples` decides which ray of a result carries its object id; a width of 65536 makes
+// k_shade's RNG pixel (xy >> 16) * width + (xy & 0xffff) the 32-bit id itself
+static DFrame make_ray_frame(const rr_config* cfg, uint32_t rays_per_result, uint32_t n_results) {
+    DFrame fr;
+    memset(&fr, 0, sizeof fr);
+    fr.width = 65536u; fr.height = 65536u; fr.samples = rays_per_result; fr.cell_size = 1u;
+    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u;
+    fr.fog_density = cfg->fog_density;
+    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
+    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
+    fr.n_region_pixels = n_results;
+    return fr;
+}
+
+// the batches of one call, in order; d_origins / d_dirs: the host form's staging for one batch (plan.B rays)
+static int run_ray_batches(FrameRun& f, const RayIo& io, uint32_t rays_per_result, float* d_origins, float* d_dirs) {
+    rr_scene* s = f.s;
+    const uint64_t B = f.plan.B, n_rays = f.plan.total_primary;
+    for (uint64_t first = 0; first < n_rays; first += B) {
+        if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rays - first);
+        RR_TRY(f.pool.start_batch());
+        uint32_t* level1_count = f.pool.take(1);
+        if (!level1_count) return counters_exhausted();
+        const float *origins = io.origins + 3ull * first, *dirs = io.directions + 3ull * first;
+        if (io.host) { // (stream-ordered: the copies wait for the kernels of the batch before, which read the same staging buffers)
+            HIP_TRY(hipMemcpyAsync(d_origins, origins, 12ull * nb, hipMemcpyHostToDevice, f.st));
+            HIP_TRY(hipMemcpyAsync(d_dirs, dirs, 12ull * nb, hipMemcpyHostToDevice, f.st));
+            origins = d_origins; dirs = d_dirs;
+        }
+        hipLaunchKernelGGL(k_seed_rays, dim3((nb + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, origins, dirs, (unsigned long long)first, nb, rays_per_result,
+                           f.queue_at(0), level1_count, s->counters.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        s->stats.batches++;
+        RR_TRY(run_level(f, 1, 0, nb, level1_count));
+        HIP_TRY(hipGetLastError());
+        if (f.cancel && first + B < n_rays) { // only a caller that can cancel needs the host to keep pace
+            if (io.host) HIP_TRY(hipStreamSynchronize(f.st));
+            else if (hipStreamSynchronize(f.st) != hipSuccess) return fail(RR_ERR_DEVICE, "rr_shade_rays_device: the stream failed");
+        }
+    }
+    return RR_OK;
+}
+
+// One radiance query (the caller holds the lock).  Host rays: staging of the call, bounded by plan.B rays and RESOLVE_RAYS_CHUNK
+// results, and the stream is idle when the call returns, whatever ended it (the staging goes, `out` is the caller's to read).
+// Device rays: nothing is the call's own, so nothing is freed behind launches in flight, and only a call that ends early waits.
+static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const RayIo& io, uint32_t n_results, uint32_t rays_per_result, hipStream_t st,
+                             const volatile int* cancel) {
+    RR_TRY(take_stream(s, st));
+    resolve_timers(s);
+    memset(&s->stats, 0, sizeof s->stats);
+    s->stats_final = false;
+    s->overlap_stages = 0;
+    const uint64_t n_rays = (uint64_t)n_results * rays_per_result;
+    if (io.host) RR_TRY(ensure_host_ray_reach(s, io.origins, 3ull * n_rays));
+    else {
+        HIP_TRY(s->query_words.reserve(QW_CONST + sizeof(DShadeConst)));
+        RR_TRY(preset_reach(s, st));
+        hipLaunchKernelGGL(k_ray_reach, dim3(query_grid(s, 3ull * n_rays)), dim3(RR_BLOCK), 0, st, io.origins, (unsigned long long)(3ull * n_rays),
+                           (uint32_t*)(s->query_words.as<char>() + QW_REACH));
+        HIP_TRY(hipGetLastError());
+        uint32_t first_bad = 0;
+        RR_TRY(await_reach(s, st, &first_bad));
+    }
+    RR_TRY(upload_shade_const(s, make_ray_frame(cfg, rays_per_result, n_results), st));
+    DevBuf d_ids, d_origins, d_dirs, d_out; // the host form's staging
+    const uint32_t* ids = io.stream_ids;
+    if (io.host || !ids) { // the caller's host ids uploaded, or 0 .. n - 1: into the call's buffer (host form) or the handle's
+        DevBuf& b = io.host ? d_ids : s->query_ids;
+        HIP_TRY(b.reserve((size_t)n_results * 4));
+        if (ids) HIP_TRY(hipMemcpy(b.p, ids, (size_t)n_results * 4, hipMemcpyHostToDevice));
+        else {
+            hipLaunchKernelGGL(k_iota, dim3((n_results + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, b.as<uint32_t>(), n_results);
+            HIP_TRY(hipGetLastError());
+        }
+        ids = b.as<uint32_t>();
+    }
+    DAccum acc;
+    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->n_enabled_lights, s->tuning.shade_chunk_rays);
+    RR_TRY(grow_ray_queues(s, plan.M, plan.sq_need, 0));
+    if (io.host) {
+        HIP_TRY(d_origins.reserve(12ull * plan.B));
+        HIP_TRY(d_dirs.reserve(12ull * plan.B));
+        HIP_TRY(d_out.reserve(32ull * std::min<uint32_t>(n_results, RESOLVE_RAYS_CHUNK)));
+    }
+    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
+               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
+    f.slot_xy = ids;
+    f.seeded = true;
+    HIP_TRY(hipEventRecord(s->frame_a, st));
+    int rc = run_ray_batches(f, io, rays_per_result, d_origins.as<float>(), d_dirs.as<float>());
+    for (uint32_t r0 = 0; r0 < n_results && rc == RR_OK; r0 += RESOLVE_RAYS_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(RESOLVE_RAYS_CHUNK, n_results - r0);
+        hipLaunchKernelGGL(k_resolve_rays, dim3((n + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, st, acc, r0, n, rays_per_result,
+                           io.host ? d_out.as<float4>() : (float4*)(io.out + r0));
+        if (!io.host) continue;
+        const hipError_t e = hipMemcpyAsync(io.out + r0, d_out.p, 32ull * n, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = fail(RR_ERR_DEVICE, "rr_shade_rays: %s", hipGetErrorString(e));
+    }
+    (void)hipEventRecord(s->frame_b, st);
+    const hipError_t e = (io.host || rc != RR_OK) ? hipStreamSynchronize(st) : hipSuccess;
+    if (rc != RR_OK) return rc;
+    HIP_TRY(e);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_shade_rays(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                             const uint32_t* stream_ids, rr_radiance* out, const volatile int* cancel) try {
+    RR_TRY(check_shade_args("rr_shade_rays", false, s, cfg, origins, directions, stream_ids, out, n_results, rays_per_result));
+    if (n_results == 0) return RR_OK;
+    RR_TRY(not_in_pass(s, "rr_shade_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("shade_rays.host");
+    return shade_rays_locked(s, cfg, RayIo{origins, directions, stream_ids, out, true}, n_results, rays_per_result, nullptr, cancel);
+} RR_GUARD_END("rr_shade_rays")
+
+extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const float* origins, const float* directions, uint32_t n_results, uint32_t rays_per_result,
+                                    const uint32_t* stream_ids, rr_radiance* out, void* hip_stream, const volatile int* cancel) try {
+    RR_TRY(check_shade_args("rr_shade_rays_device", true, s, cfg, origins, directions, stream_ids, out, n_results, rays_per_result));
+    if (n_results == 0) return RR_OK;
     RR_TRY(not_in_pass(s, "rr_shade_rays_device"));
     std::lock_guard<std::mutex> lk(s->mu);
     RR_TRY(check_intact(s));
@@ -2584,7 +2462,7 @@ extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const flo
     RR_TRY(check_query_pointer(s, directions, "rr_shade_rays_device", "directions_dev"));
     if (stream_ids) RR_TRY(check_query_pointer(s, stream_ids, "rr_shade_rays_device", "stream_ids_dev"));
     RR_TRY(check_query_pointer(s, out, "rr_shade_rays_device", "out_dev"));
-    return shade_rays_device_locked(s, cfg, origins, directions, n_results, rays_per_result, stream_ids, out, (hipStream_t)hip_stream, cancel);
+    return shade_rays_locked(s, cfg, RayIo{origins, directions, stream_ids, out, false}, n_results, rays_per_result, (hipStream_t)hip_stream, cancel);
 } RR_GUARD_END("rr_shade_rays_device")
 
 // ---------------------------------------------------------------------------

@@ -315,8 +315,8 @@ static int stack_shares(uint32_t n_items, int* tlas_depth_limit, int* blas_depth
 // What an item takes from the mesh it names: where the mesh's records sit in the arenas, and what its flag word needs.
 struct MeshDev { uint32_t tri_base, n_tris; uint32_t node_base4; int32_t root4; bool has_normals, degenerate; };
 
-// The meshes' records, one mesh after the other.  A mesh's triangle records start at tri_base (all of tris, trix, attrs, face_slot and
-// slot_face) and its nodes at node_base4; everything inside a mesh's records is relative to those two, so appending meshes leaves
+// The meshes' records, one mesh after the other.  A mesh's triangle records start at tri_base (all of tris, trix, attrs and
+// face_slot) and its nodes at node_base4; everything inside a mesh's records is relative to those two, so appending meshes leaves
 // the records of the meshes before them as they are.  tris_before / nodes4_before: records that precede the vectors' first element
 // (rr_scene_add_meshes builds the records of the new meshes alone, behind those resident on the device).
 struct MeshArenas {
@@ -324,7 +324,7 @@ struct MeshArenas {
     std::vector<DTri> tris;         // per mesh triangle, in leaf order: what k_shade reads
     std::vector<DTriX> trix;        // ... what the triangle test reads
     std::vector<DTriAttr> attrs;    // ... its normals and uvs
-    std::vector<uint32_t> face_slot, slot_face; // per mesh triangle: original face index -> leaf-order slot, and back
+    std::vector<uint32_t> face_slot; // per mesh triangle: original face index -> leaf-order slot (the way back: the bits of DTri::v0.w)
     std::vector<MeshDev> meshes;    // per mesh
     size_t tris_before = 0, nodes4_before = 0;
 };
@@ -381,7 +381,6 @@ static int append_mesh_records(const rr_mesh* meshes, uint32_t n, int blas_depth
         for (uint32_t slot = 0; slot < nt; slot++) {
             uint32_t f = r.order[slot];
             ar.face_slot[fs_base + f] = slot;
-            ar.slot_face.push_back(f);
             const uint32_t* ix = m.indices + 3 * (size_t)f;
             const float *a = m.positions + 3 * (size_t)ix[0], *b = m.positions + 3 * (size_t)ix[1], *c = m.positions + 3 * (size_t)ix[2];
             {   // Mesh::get_uv divides by the triangle's area (src/shape/mesh.rs:127-143): a zero (or non-finite) area makes the uv of ANY point

@@ -347,7 +347,7 @@ static int test_scene_records() {
     CHECK(validate_scene(&fs) == RR_OK && build_scene_records(&fs, &r) == RR_OK);
     size_t n_tris = 0;
     for (const rr_mesh& m : s.meshes) n_tris += m.n_triangles;
-    CHECK(r.tris.size() == n_tris && r.trix.size() == n_tris && r.attrs.size() == n_tris && r.face_slot.size() == n_tris && r.slot_face.size() == n_tris);
+    CHECK(r.tris.size() == n_tris && r.trix.size() == n_tris && r.attrs.size() == n_tris && r.face_slot.size() == n_tris);
     CHECK(r.items.size() == 6 && r.item_host.size() == 6 && r.dmat.size() == 2 && r.dtex.size() == 2 && r.tlas_depth_limit == 5 && r.blas_depth_limit == RR_STACK_DEPTH - 8);
     std::vector<std::pair<uint32_t, uint32_t>> normals; // [first, end) of every mesh item's flat world normals
     for (size_t i = 0; i < r.items.size(); i++) {
@@ -360,12 +360,11 @@ static int test_scene_records() {
         const rr_mesh& m = s.meshes[s.items[i].mesh];
         CHECK(it.n_tris == m.n_triangles && (size_t)it.tri_base + it.n_tris <= n_tris && (it.root4 >= 0) == (i != 5));
         for (uint32_t slot = 0; slot < it.n_tris; slot++) { // inverse permutations of the mesh's faces
-            const uint32_t f = r.slot_face[it.tri_base + slot];
-            CHECK(f < it.n_tris && r.face_slot[it.tri_base + f] == slot);
             const DTri& t = r.tris[it.tri_base + slot];
             const DTriX& x = r.trix[it.tri_base + slot];
-            uint32_t fbits; memcpy(&fbits, &t.v0.w, 4);
-            CHECK(fbits == f && same_bits(x.t0, t.v0));
+            uint32_t f; memcpy(&f, &t.v0.w, 4); // the slot's face: the bits of v0.w
+            CHECK(f < it.n_tris && r.face_slot[it.tri_base + f] == slot);
+            CHECK(same_bits(x.t0, t.v0));
             CHECK(same_bits(x.t1, make_float4(t.v1.x - t.v0.x, t.v1.y - t.v0.y, t.v1.z - t.v0.z, t.v2.x - t.v0.x)));
             CHECK(same_bits(x.t2, make_float4(t.v2.y - t.v0.y, t.v2.z - t.v0.z, 0.0f, 0.0f)));
             for (int k = 0; k < 3; k++) CHECK(t.v0.x == m.positions[3 * m.indices[3 * f]] && (&t.v1.x)[k] == m.positions[3 * m.indices[3 * f + 1] + k]);
@@ -438,7 +437,7 @@ static void print_digests(const char* name, const SceneRecords& r, const TlasTre
     std::printf("%s: %zu items %zu triangles limits %d/%d flat normals %llu switches %d%d lights on %u roots %d %d surface %d nan_balls %d\n", name, r.items.size(), r.tris.size(),
                 r.tlas_depth_limit, r.blas_depth_limit, (unsigned long long)r.n_flat_normals, (int)r.general_w, (int)r.any_alpha_occluder, r.n_enabled_lights, t.root, t.root_surface,
                 (int)t.has_surface, (int)t.nan_balls);
-    std::printf("  nodes4 %016llx tris %016llx trix %016llx attrs %016llx face_slot %016llx slot_face %016llx\n", fnv(r.nodes4), fnv(r.tris), fnv(r.trix), fnv(r.attrs), fnv(r.face_slot), fnv(r.slot_face));
+    std::printf("  nodes4 %016llx tris %016llx trix %016llx attrs %016llx face_slot %016llx\n", fnv(r.nodes4), fnv(r.tris), fnv(r.trix), fnv(r.attrs), fnv(r.face_slot));
     std::printf("  items %016llx item_host %016llx dmat %016llx dlights %016llx dtex %016llx tex_width %016llx\n", fnv(r.items), fnv(r.item_host), fnv(r.dmat), fnv(r.dlights), fnv(r.dtex), fnv(r.tex_width));
     std::printf("  tlas corner %016llx surface %016llx item_boxes %016llx reach %016llx\n", fnv(t.corner), fnv(t.surface), fnv(t.item_boxes), fnv(std::vector<double>(t.reach, t.reach + 3)));
 }

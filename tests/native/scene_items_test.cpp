@@ -128,7 +128,7 @@ static bool same_table(const std::vector<MeshDev>& a, const std::vector<MeshDev>
 }
 static bool same_arenas(const MeshArenas& a, const MeshArenas& b) {
     return same_bytes(a.nodes4, b.nodes4) && same_bytes(a.tris, b.tris) && same_bytes(a.trix, b.trix) && same_bytes(a.attrs, b.attrs) &&
-           same_bytes(a.face_slot, b.face_slot) && same_bytes(a.slot_face, b.slot_face) && same_table(a.meshes, b.meshes);
+           same_bytes(a.face_slot, b.face_slot) && same_table(a.meshes, b.meshes);
 }
 static bool same_host(const std::vector<ItemHost>& a, const std::vector<ItemHost>& b) {
     if (a.size() != b.size()) return false;
@@ -147,7 +147,7 @@ static int test_split_append(Scene s, const char* what) {
     rr_flat_scene fs = s.flat();
     SceneRecords whole;
     CHECK(validate_scene(&fs) == RR_OK && build_scene_records(&fs, &whole) == RR_OK);
-    CHECK(whole.meshes.size() == fs.n_meshes && whole.tris.size() == whole.trix.size() && whole.tris.size() == whole.slot_face.size());
+    CHECK(whole.meshes.size() == fs.n_meshes && whole.tris.size() == whole.trix.size() && whole.tris.size() == whole.face_slot.size());
     for (uint32_t k = 0; k <= fs.n_meshes; k++) {
         MeshArenas a; // in place: the first k, then the rest
         CHECK(append_mesh_records(fs.meshes, k, whole.blas_depth_limit, fs.n_items, &a) == RR_OK);
@@ -160,7 +160,7 @@ static int test_split_append(Scene s, const char* what) {
         CHECK(append_mesh_records(fs.meshes + k, fs.n_meshes - k, whole.blas_depth_limit, fs.n_items, &b) == RR_OK);
         CHECK(same_table(b.meshes, whole.meshes));
         CHECK(same_tail(whole.nodes4, nodes_k, b.nodes4) && same_tail(whole.tris, tris_k, b.tris) && same_tail(whole.trix, tris_k, b.trix) &&
-              same_tail(whole.attrs, tris_k, b.attrs) && same_tail(whole.face_slot, tris_k, b.face_slot) && same_tail(whole.slot_face, tris_k, b.slot_face));
+              same_tail(whole.attrs, tris_k, b.attrs) && same_tail(whole.face_slot, tris_k, b.face_slot));
         // the scene's own copies of the caller's arrays give the same records (what a changed stack share rebuilds from)
         std::vector<HostMesh> copies;
         std::vector<rr_mesh> views;

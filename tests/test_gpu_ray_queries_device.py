@@ -1,6 +1,7 @@
 """The device-buffer, stream-ordered forms of the three ray queries (rr_trace_rays_device, rr_trace_shadow_rays_device,
 rr_shade_rays_device) against their host forms: once the stream is synchronised, out_dev holds byte for byte what the host form
-writes for the same inputs on the same handle state.
+writes for the same inputs on the same handle state.  The host forms are the device forms behind a staging copy, so what the two
+share (the streaming kernels around the walks) is judged from outside too: test_host_forms_against_the_oracle.
 
 Two scenes: spheres_room as it is (14 items: every ray walks the top level) and padded to 40 items with the scene-wide switches
 (tests/packet_pad.py: the packet form of the top level, the dividing inverse, the alpha-occluder switch, an overflowing ball), the
@@ -22,7 +23,9 @@ from tests.packet_pad import pad_inert
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (1, 63, 64, 65, 256, 257, 70001)   # the packet (64), workgroup (256) and grid-stride edges of the streaming kernels
+# the packet (64) and workgroup (256) edges of the streaming kernels, and 274 workgroups of ONE round each: their grid is capped at 8
+# workgroups per CU, so only a size past multi_processor_count * 8 * 256 makes the grid-stride loop go round again (_second_round_size)
+SIZES = (1, 63, 64, 65, 256, 257, 70001)
 N_MAX = SIZES[-1]
 SENTINEL = 0x5a5a5a5a
 COUNTERS = ("primary_rays", "secondary_rays", "shadow_rays", "shaded_hits")
@@ -233,6 +236,79 @@ def test_straight_against_the_oracle(hip, oracle, form):
             assert len(bad) == 0, f"{form}: {len(bad)} shadow records differ from the oracle's, first {int(bad[0])}"
             occ = g[:, 0] == 1
             assert occ.any() and np.array_equal(g[occ, 2], ids[g[occ, 1]])   # the occluders' object ids came with them
+
+
+# ---- 1b: the host forms against the oracle -----------------------------------------------------------------------------------------
+def _second_round_size():
+    """Rays that make the grid-stride loop of k_pack_rays / k_unpack_hits take a second round (524 545 on an MI355X)."""
+    return torch.cuda.get_device_properties(0).multi_processor_count * 8 * 256 + 257
+
+
+@functools.lru_cache(maxsize=None)
+def _logged(oracle, shadow: bool):
+    """((depth, calls), (depth, calls)): the logged closest-hit or shadow calls of depth 1 and of the depth past 1 that has most of
+    them (past 1 the candidate filter admits the reflection-only items), in call order, with the oracle's own answers (a query
+    takes one depth for all its rays).  All finite."""
+    log = _log(oracle)
+    m = log["for_shadow"] if shadow else ~log["for_shadow"]
+    per_depth = np.bincount(log["depth"][m].astype(np.int64))
+    out = []
+    for depth in (1, 2 + int(per_depth[2:].argmax())):
+        idx = np.flatnonzero(m & (log["depth"] == depth))
+        calls = {k: log[k][idx] for k in ("origin", "dir", "found", "item", "face", "toi")}
+        assert len(idx) > 100 and np.isfinite(calls["origin"]).all() and np.isfinite(calls["dir"]).all()
+        assert calls["found"].any()
+        out.append((depth, calls))
+    return tuple(out)
+
+
+def _tiled(calls, n):
+    """The logged calls tiled to n rays: the oracle's answers tile with them."""
+    idx = np.resize(np.arange(len(calls["toi"])), n)
+    return {k: np.ascontiguousarray(v[idx]) for k, v in calls.items()}
+
+
+def _closest_equals_the_oracle(got, ref, ids, what):
+    f = ref["found"]
+    assert got.shape == (len(f), 5), what
+    assert np.array_equal(got[:, 0], f.astype(np.uint32)), (what, "found")
+    assert np.array_equal(got[f, 1].view(np.int32), ref["item"][f]) and np.array_equal(got[f, 3], ref["face"][f]), (what, "item / face")
+    assert np.array_equal(got[f, 4], ref["toi"][f].view(np.uint32)) and np.array_equal(got[f, 2], ids[got[f, 1]]), (what, "toi / object id")
+    assert np.array_equal(got[~f], np.broadcast_to(np.asarray([0, 0xffffffff, 0, 0, 0], np.uint32), got[~f].shape)), (what, "the not-hit record")
+
+
+def _shadow_equals_the_oracle(got, ref, lim, ids, what):
+    assert got.shape == (len(ref["found"]), 5), what
+    rec = (got[:, 0].astype(bool), got[:, 1].copy().view(np.int32), got[:, 3].copy(), got[:, 4].copy().view(np.float32))
+    bad = cases.mismatches(rec, ref, lim)
+    assert len(bad) == 0, f"{what}: {len(bad)} of {len(got)} shadow records differ from the oracle's, first {int(bad[0])}"
+    occ = got[:, 0] == 1
+    assert (got[:, 0] <= 1).all() and np.array_equal(got[occ, 2], ids[got[occ, 1]]) and (got[~occ, 2] == 0).all(), (what, "object ids")
+
+
+@pytest.mark.parametrize("form", ["per_ray_14", "packet_40"])
+def test_host_forms_against_the_oracle(hip, oracle, form):
+    """The HOST closest-hit and shadow forms against the oracle's own logged answers, bit for bit, every ray compared: the host
+    forms run through the device forms' streaming kernels, so the identity tests above no longer judge those from outside.  Sizes:
+    the packet and workgroup edges, each at depth 1 and at a deeper one, and at depth 1 one that takes the kernels' grid-stride loop
+    into its second round; there the two device forms are held to the same answers."""
+    fs = _scene(form)                                   # (the decoys of packet_40 are invisible: the oracle's answers are the unpadded scene's)
+    ids = np.asarray([it.id for it in fs.items], np.uint32)
+    big = _second_round_size()
+    with hip.DeviceScene(fs, 0) as ds:
+        for (c_depth, closest), (s_depth, shadow) in zip(_logged(oracle, False), _logged(oracle, True)):
+            for n in (1, 63, 64, 65, 256, 257) + ((big,) if c_depth == 1 else ()):
+                ref = _tiled(closest, n)
+                what = f"{form} closest depth {c_depth} n {n}"
+                _closest_equals_the_oracle(host_trace(hip, ds, ref["origin"], ref["dir"], c_depth), ref, ids, "host " + what)
+                if n == big:
+                    _closest_equals_the_oracle(dev_trace(ds, ref["origin"], ref["dir"], c_depth), ref, ids, "device " + what)
+                ref = _tiled(shadow, n)
+                what = f"{form} shadow depth {s_depth} n {n}"
+                for lim in (None, _light_distances(fs, ref["origin"])):
+                    _shadow_equals_the_oracle(host_shadow(hip, ds, ref["origin"], ref["dir"], lim, s_depth), ref, lim, ids, "host " + what)
+                    if n == big:
+                        _shadow_equals_the_oracle(dev_shadow(ds, ref["origin"], ref["dir"], lim, s_depth), ref, lim, ids, "device " + what)
 
 
 # ---- 2: radiance -------------------------------------------------------------------------------------------------------------------
