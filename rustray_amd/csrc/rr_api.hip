@@ -9,6 +9,7 @@
 #include "rr_bvh.h"
 #include "rr_device.h"
 #include "rr_frame_plan.h"
+#include "rr_primary_setup.h"
 #include "rr_query_pointers.h"
 
 #include <hip/hip_runtime.h>
@@ -211,7 +212,11 @@ struct rr_scene {
     DevBuf sq[3];
     size_t sq_cap = 0;
     DevBuf acc_rgb, acc_normal, acc_depth, acc_id, acc_flags, shade_const;
-    DevBuf region_xy, trace_order, sample_xy, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
+    DevBuf region_xy, trace_order, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
+    // what primary_ray reads (rr_primary_setup.h): slot_c, the screen point of each slot's pixel centre, lives and dies with region_xy;
+    // sample_tr, the screen offset of each sample, is uploaded when the sub-sample table or one of the frame constants in tr_key changes
+    DevBuf slot_c, sample_tr;
+    std::vector<uint16_t> tr_table; PrimarySampleKey tr_key{}; bool tr_valid = false;
     std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
     DevBuf tmp_out[4];
     // ray queries (the host forms are the device forms behind a staging copy): what the launches of a device form read and write after the
@@ -1122,17 +1127,17 @@ struct PassHook { rr_pass_fn fn; void* user; uint32_t min_passes; const rr_frame
 // before the launch: a NULL one would be a write to address 16 * i on the device.  Level 1 reads no ray records (the rays are
 // derived from their index), so its queue carries the hit records only and its ray pointers are passed as NULL.
 static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t* count, uint32_t* head, uint64_t n, const DShadeConst* kc,
-                                const uint32_t* slot_xy, const DPrimary& pr, unsigned long long* counters, hipStream_t st) {
+                                const DPrimary& pr, unsigned long long* counters, hipStream_t st) {
     if (!count || !head || !q.hit || !kc || !counters) return fail(RR_ERR_DEVICE, "internal: closest-hit launch with a NULL argument");
-    if (primary && (!slot_xy || !pr.sample_xy || pr.n != n)) return fail(RR_ERR_DEVICE, "internal: level-1 closest-hit launch without its ray table");
+    if (primary && (!pr.sample_tr || pr.n != n)) return fail(RR_ERR_DEVICE, "internal: level-1 closest-hit launch without its ray table");
     if (!primary && (!q.r0 || !q.r1 || !q.r2)) return fail(RR_ERR_DEVICE, "internal: closest-hit launch without ray records");
     if (n == 0 || n > 0x7fffff00ull) return fail(RR_ERR_DEVICE, "internal: closest-hit launch of %llu rays", (unsigned long long)n);
     const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * RR_CLOSEST_WAVES);
     if (primary) {
         q.r0 = nullptr; q.r1 = nullptr; q.r2 = nullptr;
-        hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->view, q, count, head, kc, slot_xy, pr, counters);
+        hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->view, q, count, head, kc, pr, counters);
     } else {
-        hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->view, q, count, head, kc, slot_xy, pr, counters);
+        hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->view, q, count, head, kc, pr, counters);
     }
     HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -1159,12 +1164,16 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
     fill_region(W, H, rg, &s->h_region_xy, &order);
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(s->region_xy.reserve(std::max<size_t>(s->h_region_xy.size(), 1) * 4));
+    HIP_TRY(s->slot_c.reserve(std::max<size_t>(s->h_region_xy.size(), 1) * 8));
     HIP_TRY(s->trace_order.reserve(std::max<size_t>(order.size(), 1) * 4));
     if (!s->h_region_xy.empty()) {
         // slot_xy[j] = pixel of accumulator slot j; slot_out[j] = its index in the compact output order
         std::vector<uint32_t> slot_xy(order.size());
         for (size_t j = 0; j < order.size(); j++) slot_xy[j] = s->h_region_xy[order[j]];
         HIP_TRY(hipMemcpy(s->region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice));
+        std::vector<float> slot_c(slot_xy.size() * 2); // the pixel centres on the screen, as primary_ray adds the sample's offset to them
+        primary_slot_centres(slot_xy.data(), slot_xy.size(), W, H, slot_c.data());
+        HIP_TRY(hipMemcpy(s->slot_c.p, slot_c.data(), slot_c.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
     }
     s->region_cached = rg; s->region_w = W; s->region_h = H;
@@ -1187,29 +1196,42 @@ static DFrame make_frame(const rr_camera* cam, const rr_config* cfg) {
 }
 
 // the shade kernel's constants (scene view + frame), read from device memory
-static int upload_shade_const(rr_scene* s, const DFrame& fr, hipStream_t st) {
+static int upload_shade_const(rr_scene* s, const DFrame& fr, const PrimaryFrame& ps, hipStream_t st) {
     DShadeConst hc;
-    hc.sc = s->view; hc.fr = fr;
+    hc.sc = s->view; hc.fr = fr; hc.ps = ps;
     HIP_TRY(s->shade_const.reserve(sizeof hc));
     HIP_TRY(hipMemcpyAsync(s->shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st)); // `hc` is a stack local
     return RR_OK;
 }
 
-static int upload_sample_table(rr_scene* s, uint16_t samples, const uint16_t* sample_xy, hipStream_t st) {
+// sample_tr on the device: the screen offset of every sample of this frame (primary_sample_offsets), uploaded only when the
+// sub-sample table or a frame constant it depends on differs from what the buffer holds
+static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sample_xy, hipStream_t st) {
+    const uint32_t samples = fr.samples;
     if (!sample_xy) { // the built-in table depends on the sample count only: built once per count, not once per frame
         if (s->table_samples != samples) {
             s->table_samples = 0; // the cache names a sample count only once its table is complete
             try { s->table_cache.resize((size_t)samples * 2); }
             catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sub-sample table"); }
-            RR_TRY(rr_sample_table(samples, s->table_cache.data(), nullptr));
-            s->table_samples = samples;
+            RR_TRY(rr_sample_table((uint16_t)samples, s->table_cache.data(), nullptr));
+            s->table_samples = (uint16_t)samples;
         }
         sample_xy = s->table_cache.data();
     }
-    HIP_TRY(s->sample_xy.reserve((size_t)samples * 4));
-    HIP_TRY(hipMemcpyAsync(s->sample_xy.p, sample_xy, (size_t)samples * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st)); // the caller's table may be a temporary
+    const PrimarySampleKey key{fr.width, fr.height, fr.cell_size, fr.dof, samples, fr.aperture_size};
+    if (s->tr_valid && same_key(s->tr_key, key) && s->tr_table.size() == (size_t)samples * 2 &&
+        memcmp(s->tr_table.data(), sample_xy, (size_t)samples * 4) == 0) return RR_OK;
+    s->tr_valid = false;
+    std::vector<float> tr;
+    try { s->tr_table.assign(sample_xy, sample_xy + (size_t)samples * 2); tr.resize((size_t)samples * 2); }
+    catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sample offsets"); }
+    primary_sample_offsets(sample_xy, key, tr.data());
+    HIP_TRY(hipStreamSynchronize(st)); // an earlier frame on this stream may still read the buffer
+    HIP_TRY(s->sample_tr.reserve((size_t)samples * 8));
+    HIP_TRY(hipMemcpyAsync(s->sample_tr.p, tr.data(), (size_t)samples * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // `tr` is a local
+    s->tr_key = key; s->tr_valid = true;
     return RR_OK;
 }
 
@@ -1452,7 +1474,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         uint32_t* head = f.pool.take(1);
         if (!head) return counters_exhausted();
         ScopedTimer t(s, st, TK_CLOSEST, l1);
-        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->shade_const.as<DShadeConst>(), f.slot_xy, f.pr, counters, st));
+        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->shade_const.as<DShadeConst>(), f.pr, counters, st));
     }
     const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
     const uint64_t M = f.plan.M, child_base = l1 ? 0 : base + n;
@@ -1543,8 +1565,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool 
         RR_TRY(f.pool.start_batch());
         uint32_t* level1_count = f.pool.take(1);
         // The batch covers primary indices [first, first + n_batch): index i -> sample i / npix, pixel i % npix.
-        f.pr.first = first; f.pr.n = n_batch;
-        f.pr.group = batch_group(f.plan, npix, first, n_batch);
+        f.pr.at = primary_launch(first, npix, batch_group(f.plan, npix, first, n_batch)); f.pr.n = n_batch;
         s->stats.batches++;
         RR_TRY(run_level(f, 1, 0, n_batch, level1_count));
         HIP_TRY(hipGetLastError());
@@ -1581,14 +1602,14 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     RR_TRY(ensure_camera_reach(s, cam, cfg)); // the top level's boxes must be padded for this camera's distance from the origin
     DFrame fr = make_frame(cam, cfg);
     fr.n_region_pixels = npix;
-    RR_TRY(upload_shade_const(s, fr, st));
-    RR_TRY(upload_sample_table(s, cfg->samples, sample_xy, st));
+    RR_TRY(upload_sample_table(s, fr, sample_xy, st));
     DAccum acc;
     RR_TRY(reset_accumulators(s, npix, out->normal != nullptr, out->depth != nullptr, out->object_id != nullptr, st, &acc));
     FramePlan plan;
     RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
+    RR_TRY(upload_shade_const(s, fr, primary_frame(s->slot_c.as<float>(), npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{s->sample_xy.as<uint16_t>(), 0ull, 0u, 1u}, cancel,
+               CounterPool{s, st}, DPrimary{s->sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u}, cancel,
                s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                s->n_cus * RR_SHADE_GRID_WG};
     f.slot_xy = s->region_xy.as<uint32_t>();
@@ -2050,17 +2071,21 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
     fr.samples = 1; fr.cell_size = 1; fr.n_region_pixels = 1;
     DevBuf scratch;
     HIP_TRY(scratch.reserve(256 + sizeof(DShadeConst)));
-    // layout: [0] region_xy, [4] sample_xy (2 x u16), [64] hit, [96] count, [100] head, [128] counters, [256] scene view + frame constants
+    // layout: [0] slot_c (the pixel's centre), [8] sample_tr (the one sample's offset), [64] hit, [96] count, [100] head, [128] counters, [256] scene view + frame constants
     char* b = scratch.as<char>();
-    uint32_t h_xy = (uint32_t)x | ((uint32_t)y << 16);
+    const uint32_t h_xy = (uint32_t)x | ((uint32_t)y << 16);
+    const uint16_t h_sample[2] = {0, 0};
+    float h_tables[4]; // the one-entry tables of a frame of one pixel and one sample: the launch takes the frames' code path
+    primary_slot_centres(&h_xy, 1, fr.width, fr.height, h_tables);
+    primary_sample_offsets(h_sample, PrimarySampleKey{fr.width, fr.height, fr.cell_size, fr.dof, fr.samples, fr.aperture_size}, h_tables + 2);
     HIP_TRY(hipMemset(b, 0, 256));
-    HIP_TRY(hipMemcpy(b, &h_xy, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b, h_tables, sizeof h_tables, hipMemcpyHostToDevice));
     DRayQueue q{nullptr, nullptr, nullptr, (uint4*)(b + 64)};
-    DPrimary pr{(const uint16_t*)(b + 4), 0ull, 1u, 1u};
+    DPrimary pr{(const float*)(b + 8), primary_launch(0, 1u, 1u), 1u};
     DShadeConst hc;
-    hc.sc = s->view; hc.fr = fr;
+    hc.sc = s->view; hc.fr = fr; hc.ps = primary_frame((const float*)b, 1u, 1u);
     HIP_TRY(hipMemcpy(b + 256, &hc, sizeof hc, hipMemcpyHostToDevice));
-    RR_TRY(launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), (const uint32_t*)b, pr, (unsigned long long*)(b + 128), nullptr));
+    RR_TRY(launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), pr, (unsigned long long*)(b + 128), nullptr));
     uint32_t hit[4];
     HIP_TRY(hipMemcpy(hit, b + 64, 16, hipMemcpyDeviceToHost));
     scratch.release();
@@ -2204,8 +2229,8 @@ static int trace_rays_locked(rr_scene* s, const float* origins, const float* dir
     }
     if (SHADOW) RR_TRY(launch_query_shadow(s, q.r0, q.r1, n, (uint32_t*)(w + QW_HEAD), q.hit, st));
     else { // (the <false> build reads neither the frame constants nor the work counters; both pointers name the handle's words all the same)
-        const DPrimary pr{nullptr, 0ull, 0u, 1u};
-        RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), nullptr, pr,
+        const DPrimary pr{nullptr, PrimaryLaunch{0u, 0u, 0u, 6u}, 0u};
+        RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), pr,
                                     (unsigned long long*)(w + QW_COUNTERS), st));
     }
     hipLaunchKernelGGL(k_unpack_hits<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
@@ -2391,7 +2416,7 @@ static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const RayIo& io,
         uint32_t first_bad = 0;
         RR_TRY(await_reach(s, st, &first_bad));
     }
-    RR_TRY(upload_shade_const(s, make_ray_frame(cfg, rays_per_result, n_results), st));
+    RR_TRY(upload_shade_const(s, make_ray_frame(cfg, rays_per_result, n_results), PrimaryFrame{}, st)); // (level 1 is ray records here: nothing is derived)
     DevBuf d_ids, d_origins, d_dirs, d_out; // the host form's staging
     const uint32_t* ids = io.stream_ids;
     if (io.host || !ids) { // the caller's host ids uploaded, or 0 .. n - 1: into the call's buffer (host form) or the handle's
@@ -2416,7 +2441,7 @@ static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const RayIo& io,
         HIP_TRY(d_out.reserve(32ull * std::min<uint32_t>(n_results, RESOLVE_RAYS_CHUNK)));
     }
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->sq[0].as<float4>(), s->sq[1].as<float4>(), s->sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{nullptr, 0ull, 0u, 1u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
+               CounterPool{s, st}, DPrimary{nullptr, PrimaryLaunch{0u, 0u, 0u, 6u}, 0u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
     f.slot_xy = ids;
     f.seeded = true;
     HIP_TRY(hipEventRecord(s->frame_a, st));

@@ -21,6 +21,7 @@
 // shared head; the queue length is read on the device.
 #include "rr_device.h"
 #include "rr_math.h"
+#include "rr_primary_setup.h"
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -122,47 +123,22 @@ RR_DEV float4 mat4_mul(const float* m, float x, float y, float z, float w) {
 // instead of reading ray records that a ray-generation kernel wrote (round 1: k_raygen wrote 40 B per primary ray,
 // 4.7 GB per sponza_syn frame, that the trace kernel read straight back and the shade kernel read a third time).
 // Both kernels run the same instruction sequence on the same inputs, so they see the same ray, bit for bit.
+// What the derivation does not owe to the ray is set up on the host (rr_primary_setup.h): the screen point of a pixel's
+// centre per accumulator slot, the sub-sample's offset per sample, and the constants of the index arithmetic.
 struct DPrimary {
-    const uint16_t* sample_xy;   // the sub-sample table, samples x (x_i, y_i)
-    unsigned long long first;    // first primary index of the batch (sample-major over the region: sample = index / n_pix)
-    uint32_t n;                  // primary rays in the batch
-    uint32_t group;              // samples of one pixel per 64-ray packet (1 = one sample of 64 pixels)
+    const float* sample_tr; // (x_trans, y_trans) per sample: primary_sample_offsets
+    PrimaryLaunch at;       // where the batch starts and how its packets are grouped
+    uint32_t n;             // primary rays in the batch
 };
-RR_DEV void primary_ray(const DFrame& fr, const uint32_t* __restrict__ slot_xy, const DPrimary& pr, uint32_t i,
+RR_DEV void primary_ray(const DFrame& fr, const PrimaryFrame& pf, const DPrimary& pr, uint32_t i,
                         f3* origin_out, f3* dir_out, uint32_t* pix_out, uint32_t* sample_out) {
-    const uint16_t* __restrict__ sample_xy = pr.sample_xy;
-    const unsigned long long first = pr.first;
-    const uint32_t group = pr.group;
     uint32_t pix, s; // accumulator slot (slots enumerate 8x8 blocks of the region's tiles) and sample
-    if (group <= 1u) {
-        const unsigned long long gi = first + i; // sample-major index over the region: sample = gi / n_pix
-        pix = (uint32_t)(gi % fr.n_region_pixels);
-        s = (uint32_t)(gi / fr.n_region_pixels);
-    } else {
-        // a 64-ray packet = 64/group neighbouring pixels x `group` samples of each (the host guarantees whole groups)
-        const uint32_t ppp = RR_WAVE / group;                       // pixels per packet
-        const uint32_t packets_per_group = fr.n_region_pixels / ppp;
-        const uint32_t pkt = i / RR_WAVE, lane = i % RR_WAVE;
-        // the samples of one pixel sit in neighbouring lanes, so that their accumulator adds can be merged (accum_merged)
-        pix = (pkt % packets_per_group) * ppp + lane / group;
-        s = (uint32_t)(first / fr.n_region_pixels) + (pkt / packets_per_group) * group + lane % group;
-    }
-    uint32_t xy = slot_xy[pix];
-    float x_f = (float)(xy & 0xffffu), y_f = (float)(xy >> 16);
-    float w = (float)fr.width, h = (float)fr.height;
-    float x_step = 2.0f / w, y_step = 2.0f / h;
-    float x_i = (float)sample_xy[2u * s], y_i = (float)sample_xy[2u * s + 1u];
-    float inv_cell = 1.0f / (float)fr.cell_size;
-    float x_trans = x_step * x_i * inv_cell;
-    float y_trans = y_step * y_i * inv_cell;
-    if (fr.dof && fr.samples > 1u) { x_trans -= x_step / 2.0f; y_trans -= y_step / 2.0f; }
+    primary_index(pf, pr.at, i, &pix, &s);
+    const float2 c = rr_global(reinterpret_cast<const float2*>(pf.slot_c))[pix]; // (a pointer read from a device record: rr_global)
+    const float2 tr = reinterpret_cast<const float2*>(pr.sample_tr)[s];
+    const float cx = c.x, cy = c.y, x_trans = tr.x, y_trans = tr.y;
     f3 origin, dir;
     if (fr.dof) {
-        float aperture_scale = (float)fr.width / 800.0f;
-        x_trans *= fr.aperture_size * aperture_scale;
-        y_trans *= fr.aperture_size * aperture_scale;
-        float cx = ((x_f + 0.5f) / w) * 2.0f - 1.0f;
-        float cy = 1.0f - ((y_f + 0.5f) / h) * 2.0f;
         float4 cpp = mat4_mul(fr.proj_inv, cx, cy, -1.0f, 1.0f);
         f3 rd = mk3(cpp.x - 0.0f, cpp.y - 0.0f, cpp.z - 0.0f);
         float4 eye = mat4_mul(fr.view_inv, 0.0f, 0.0f, 0.0f, 1.0f);
@@ -172,15 +148,15 @@ RR_DEV void primary_ray(const DFrame& fr, const uint32_t* __restrict__ slot_xy, 
         float dist = norm3(rd);
         float f = 1.0f / (dist / (dist + fr.focal_length));
         f3 p = mk3(eye.x + f * dvn.x, eye.y + f * dvn.y, eye.z + f * dvn.z);
-        float sx = (((x_f + 0.5f) / w) * 2.0f - 1.0f) + x_trans;
-        float sy = (1.0f - ((y_f + 0.5f) / h) * 2.0f) + y_trans;
+        float sx = cx + x_trans;
+        float sy = cy + y_trans;
         float4 pp = mat4_mul(fr.proj_inv, sx, sy, -1.0f, 1.0f);
         float4 ro = mat4_mul(fr.view_inv, pp.x, pp.y, pp.z, 1.0f);
         origin = mk3(ro.x, ro.y, ro.z);
         dir = mk3(p.x - ro.x, p.y - ro.y, p.z - ro.z);
     } else {
-        float sx = (((x_f + 0.5f) / w) * 2.0f - 1.0f) + x_trans;
-        float sy = (1.0f - ((y_f + 0.5f) / h) * 2.0f) + y_trans;
+        float sx = cx + x_trans;
+        float sy = cy + y_trans;
         float4 pp = mat4_mul(fr.proj_inv, sx, sy, -1.0f, 1.0f);
         float4 o = mat4_mul(fr.view_inv, pp.x, pp.y, pp.z, 1.0f);
         float4 d = mat4_mul(fr.view_inv, pp.x - 0.0f, pp.y - 0.0f, pp.z - 0.0f, 0.0f);
@@ -198,13 +174,13 @@ RR_DEV void primary_ray(const DFrame& fr, const uint32_t* __restrict__ slot_xy, 
 // in SGPRs across the kernel's loop and 117 of them were spilled into VGPR lanes; read through a pointer, only what is
 // in use is kept (k_shade -4 %).  The trace kernels keep their by-value arguments: their walks use the same few fields
 // in every step, and re-reading those costs more than the spills did (closest-hit +4 %, shadow +10 %, measured).
-struct DShadeConst { DSceneView sc; DFrame fr; };
+struct DShadeConst { DSceneView sc; DFrame fr; PrimaryFrame ps; };
 
 // PRIMARY: depth level 1.  The rays are derived from their index (primary_ray), only the 16-B hit record is written;
 // block 0 publishes the level's size for the shade kernel and counts the rays.
 template <bool PRIMARY>
 __global__ __launch_bounds__(RR_BLOCK, RR_CLOSEST_WAVES) void k_trace_closest(DSceneView sc, DRayQueue q, uint32_t* __restrict__ q_count,
-                                                            uint32_t* head, const DShadeConst* __restrict__ kc, const uint32_t* __restrict__ slot_xy, DPrimary pr,
+                                                            uint32_t* head, const DShadeConst* __restrict__ kc, DPrimary pr,
                                                             unsigned long long* counters) {
     __shared__ int s_stack[RR_STACK_DEPTH * RR_BLOCK];
     RR_UTIL_KIND(PRIMARY ? 0u : 1u)
@@ -250,7 +226,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_CLOSEST_WAVES) void k_trace_closest(DS
         const uint32_t ii = min(i, n - 1u); // the lanes past the end of the last packet repeat its last ray, so that the packet form below runs with all lanes
         f3 ro, rd; uint32_t depth;
         if constexpr (PRIMARY) { // the frame constants are read once per packet (not worth 49 SGPRs across the walks); kc is NULL in the <false> build's launches
-            uint32_t pix_, smp_; primary_ray(kc->fr, slot_xy, pr, ii, &ro, &rd, &pix_, &smp_); depth = 1u;
+            uint32_t pix_, smp_; primary_ray(kc->fr, kc->ps, pr, ii, &ro, &rd, &pix_, &smp_); depth = 1u;
         } else {
             const float4 r0 = q.r0[ii], r1 = q.r1[ii];
             ro = mk3(r0.x, r0.y, r0.z); rd = mk3(r1.x, r1.y, r1.z);
@@ -352,7 +328,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         float4 r0, r1; uint2 r2;
         if (PRIMARY) { // the root node of a path: throughput 1, depth 1, carries the object id, path node 1
             f3 po, pd; uint32_t ppix, psmp;
-            primary_ray(fr, slot_xy, pr, i, &po, &pd, &ppix, &psmp);
+            primary_ray(fr, kc->ps, pr, i, &po, &pd, &ppix, &psmp);
             r0 = make_float4(po.x, po.y, po.z, 1.0f);
             r1 = make_float4(pd.x, pd.y, pd.z, __uint_as_float(ppix));
             r2 = make_uint2(psmp | (1u << 16) | (1u << 24), 1u);
