@@ -41,7 +41,8 @@ extern "C" {
  * version stayed 3: a version-3 library may lack these three symbols (look them up, e.g. with dlsym, before relying on them).
  * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well.
  * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own), and after them the
- * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device. */
+ * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device.
+ * rr_surface_rays and rr_surface_rays_device (with rr_surface_hit, a struct of its own) came after those, in the same way. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -601,6 +602,48 @@ int rr_trace_shadow_rays_device(rr_scene* scene, const float* origins_dev, const
 int rr_shade_rays_device(rr_scene* scene, const rr_config* config, const float* origins_dev, const float* directions_dev,
                          uint32_t n_results, uint32_t rays_per_result, const uint32_t* stream_ids_dev /* or NULL */,
                          rr_radiance* out_dev, void* hip_stream, const volatile int* cancel);
+
+/* Surface queries for a batch of caller-supplied rays: what lies between rr_trace_rays (which item and face, how far) and
+ * rr_shade_rays (the finished colour) -- the hit point, the normals, the uv and the material as the reference evaluates it there.
+ * For a baker, a G-buffer, the albedo and normal guides of a denoiser, a host that applies its own BRDF.
+ * Ray i is Raytracing::trace(ray_i, false, false, depth) (reference src/raytracing.rs:429-490) followed by the surface part of
+ * get_color_depth_normal_id for that hit (:747-811, :928-933, :985-991): lights, recursion, fog and the generator are left out, so
+ * the query is deterministic and takes no config.  Directions are used as given, as in rr_trace_rays (neither trace nor the hit
+ * point normalises).  A miss is {0, 0xffffffff, 0, 0} followed by 112 zero bytes.
+ * origins / directions: n * 3 floats (host); `depth`: what the candidate filter sees, 1 .. 255 (1 = a frame's primary ray).  Limits
+ * and argument checks are rr_trace_rays': n == 0 returns RR_OK and touches nothing, n > 0x7fffff00 is RR_ERR_UNSUPPORTED.
+ * Non-finite rays are accepted and answered as a frame answers them.  A frame call: the scene's lock, RR_ERR_INVALID_ARGUMENT from
+ * on_pass of the same scene, RR_ERR_DEVICE on a broken scene; nothing of a frame's state (accumulators, counters, rr_scene_last_stats)
+ * is touched.
+ * rr_surface_rays_device: the same on DEVICE buffers in stream order, under every rule of rr_trace_rays_device above -- pointers
+ * classified before any launch, origins_dev / directions_dev 4-byte aligned, out_dev 16-byte aligned (RR_ERR_INVALID_ARGUMENT naming
+ * the argument, never a launch), one wait inside for the 16 bytes of the origins' reach, the handle's query buffers (56 B per ray
+ * of the largest query so far) shared with the other queries.  Once `hip_stream` is synchronised out_dev holds byte for byte what
+ * the host form writes.  The host form is the device form behind a staging copy (12 + 12 + 128 B per ray for the call). */
+typedef struct rr_surface_hit {       /* 128 bytes, eight 16-byte rows */
+    uint32_t hit;                     /* 0 = None; this row is exactly rr_ray_hit's four words for the ray */
+    uint32_t item_index;
+    uint32_t object_id;
+    uint32_t face_id;
+    float position[3];                /* origin + direction * toi, in f32 (:747) */
+    float distance;                   /* toi */
+    float normal[3];                  /* Shape::intersect's world normal = what a frame sums into its normal buffer: smooth interpolation,
+                                         back face and flip_normals applied */
+    int32_t material;                 /* the item's `material` index */
+    float shading_normal[3];          /* after normal mapping (:757-784), BEFORE the roughness jitter; = normal without a normal map */
+    uint32_t has_uv;                  /* material.has_any_texture() (:751) */
+    float base_color[4];              /* get_item_color(Base), rgba (:677-712) */
+    float ambient_color[3];           /* get_item_color(Ambient).xyz */
+    float alpha;                      /* material.alpha * base_color.w, * the alpha texel's .x with an alpha map (:806-811) */
+    float specular_color[3];          /* get_item_color(Specular).xyz */
+    float reflectivity;               /* material.reflectivity, or the reflectivity map's .x (:928-933) */
+    float uv[2];                      /* get_uv as the frame uses it; (0, 0) when !has_uv */
+    float roughness;                  /* material.roughness, or (1/PI/2) * texel.x with a roughness map (:790-795), whatever monte_carlo says */
+    float ambient_occlusion;          /* the AO texel's .x; 1 without an AO map (:985-991) */
+} rr_surface_hit;
+int rr_surface_rays(rr_scene* scene, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_surface_hit* out);
+int rr_surface_rays_device(rr_scene* scene, const float* origins_dev, const float* directions_dev, uint32_t n, uint32_t depth,
+                           rr_surface_hit* out_dev, void* hip_stream);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -498,6 +498,27 @@ public:
         return out;
     }
 
+    // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
+    // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
+    // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a
+    // frame's primary ray.  One record per ray (hit == 0: nothing hit); an empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_surface_hit> surface(const Ray* rays, size_t n_rays, uint32_t depth = 1) const {
+        std::vector<rr_surface_hit> out;
+        if (n_rays == 0 || n_rays > 0x7fffff00u) return out;
+        std::vector<float> o(3 * n_rays), d(3 * n_rays);
+        for (size_t i = 0; i < n_rays; i++) {
+            o[3 * i] = rays[i].origin.x; o[3 * i + 1] = rays[i].origin.y; o[3 * i + 2] = rays[i].origin.z;
+            d[3 * i] = rays[i].dir.x; d[3 * i + 1] = rays[i].dir.y; d[3 * i + 2] = rays[i].dir.z;
+        }
+        out.resize(n_rays);
+        if (rr_surface_rays(scene->handle(), o.data(), d.data(), (uint32_t)n_rays, depth, out.data()) != RR_OK) out.clear();
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_surface_rays_device): as trace_device below, with 128-byte records, 16-byte aligned
+    int surface_device(const float* origins_dev, const float* dirs_dev, uint32_t n, uint32_t depth, rr_surface_hit* out_dev, void* hip_stream) const {
+        return rr_surface_rays_device(scene->handle(), origins_dev, dirs_dev, n, depth, out_dev, hip_stream);
+    }
+
     // The three ray queries on DEVICE buffers, in stream order (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device):
     // the pointers name memory the scene's device can address, in the layouts of the C ABI (3 floats per origin and direction, 20-byte
     // hit records, 32-byte radiance records); `hip_stream` is a hipStream_t (nullptr = the default stream).  The work is enqueued and

@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 
 from .flat import (RR_ABI_VERSION, FlatScene, rr_camera, rr_config, rr_flat_scene, rr_frame, rr_frame_stats, rr_light, rr_material, rr_pick_result,
-                   rr_radiance, rr_region, rr_texture, rr_tuning)
+                   rr_radiance, rr_region, rr_surface_hit, rr_texture, rr_tuning, SURFACE_HIT_DTYPE)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUSTRAY_HIP_LIB") or os.path.join(_HERE, "librustray_hip.so")  # override: developer A/B builds
@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -111,6 +111,9 @@ def lib():
             L.rr_trace_shadow_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rr_shade_rays_device.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_surface_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_surface_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.rr_surface_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -359,7 +362,23 @@ class DeviceScene:
         out = out[:n]
         return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
 
+    def surface_rays(self, origins, dirs, depth: int = 1):
+        """rr_surface_rays: position, normals, uv and material of the closest hits of caller-supplied rays (depth 1 = a frame's primary
+        ray) -> a structured array of n rr_surface_hit records (flat.SURFACE_HIT_DTYPE)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if len(d) != len(o):
+            raise ValueError(f"{len(o)} origins, {len(d)} directions")
+        n = len(o)
+        out = np.zeros(max(n, 1), SURFACE_HIT_DTYPE)
+        _check(lib().rr_surface_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(depth), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
     # -- the ray queries on device buffers, in stream order ---------------------------
+    def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
+        """rr_surface_rays_device: as trace_rays_device, with n 128-byte rr_surface_hit records (16-byte aligned)."""
+        _check(lib().rr_surface_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr),
+                                            C.c_void_p(stream_ptr) if stream_ptr else None))
+
     def trace_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
         """rr_trace_rays_device: raw device pointers (ints) of n * 3 float32 origins and directions and of n 20-byte rr_ray_hit records;
         enqueued on `stream_ptr` (a hipStream_t as int, None = the default stream).  Synchronise before reading the records on the host."""

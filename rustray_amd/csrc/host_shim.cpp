@@ -187,6 +187,22 @@ extern "C" int rh_shade_device(void* h, const rr_config* cfg, const float* origi
     return rt.shade_device(origins_dev, dirs_dev, n_results, rays_per_result, stream_ids_dev, out_dev, stream);
 }
 
+// Raytracing::surface over n rays: out = n records of 128 bytes (rr_surface_hit); Raytracing::surface_device: the same on device buffers
+extern "C" int rh_surface_rays(void* h, const float* origins, const float* dirs, uint32_t n, uint32_t depth, rr_surface_hit* out) {
+    const Raytracing& rt = *((RhScene*)h)->rt;
+    std::vector<Raytracing::Ray> rays(n);
+    for (uint32_t i = 0; i < n; i++)
+        rays[i] = Raytracing::Ray{Vec3{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]}, Vec3{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]}};
+    const std::vector<rr_surface_hit> r = rt.surface(rays.data(), rays.size(), depth);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_surface_hit));
+    return 0;
+}
+
+extern "C" int rh_surface_rays_device(void* h, const float* origins_dev, const float* dirs_dev, uint32_t n, uint32_t depth, rr_surface_hit* out_dev, void* stream) {
+    return ((RhScene*)h)->rt->surface_device(origins_dev, dirs_dev, n, depth, out_dev, stream);
+}
+
 // one whole frame (min_passes passes) into the caller's buffers
 extern "C" int rh_scene_render(void* hv, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar,
                                const rr_config* cfg, uint32_t w, uint32_t h, uint32_t min_passes,

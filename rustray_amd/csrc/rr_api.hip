@@ -2113,6 +2113,9 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
 // ---------------------------------------------------------------------------
 enum : size_t { QW_COUNT = 0, QW_HEAD = 4, QW_REACH = 64, QW_COUNTERS = 128, QW_CONST = 256 }; // byte offsets into rr_scene::query_words
 static_assert(sizeof(rr_ray_hit) == 20 && sizeof(rr_shadow_hit) == 20, "k_unpack_hits writes five words per ray");
+static_assert(sizeof(rr_surface_hit) == 128 && offsetof(rr_surface_hit, position) == 16 && offsetof(rr_surface_hit, normal) == 32 &&
+              offsetof(rr_surface_hit, shading_normal) == 48 && offsetof(rr_surface_hit, base_color) == 64 && offsetof(rr_surface_hit, ambient_color) == 80 &&
+              offsetof(rr_surface_hit, specular_color) == 96 && offsetof(rr_surface_hit, uv) == 112, "k_surface_hits writes rr_surface_hit as eight 16-byte rows");
 
 // `p` (argument `arg` of `fn`) must be memory the scene's device can address: decided by query_pointer_ok (rr_query_pointers.h)
 static int check_query_pointer(const rr_scene* s, const void* p, const char* fn, const char* arg) {
@@ -2197,21 +2200,27 @@ static int stage_in(DevBuf* b, const void* src, size_t bytes) {
 // The argument checks of the four entry points, in the order the tests pin; `device`: the alignment rule of the device forms.
 // n == 0 passes: the caller returns RR_OK before it touches anything.
 static int check_trace_args(const char* fn, bool device, const rr_scene* s, const float* origins, const float* directions, const float* max_distance,
-                            uint32_t n, uint32_t depth, const void* out) {
+                            uint32_t n, uint32_t depth, const void* out, uintptr_t out_align = 4u) {
     if (!s || (n && (!origins || !directions || !out))) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (depth == 0 || depth > 255u) return fail(RR_ERR_INVALID_ARGUMENT, "depth %u (1 .. 255)", depth);
     if (n == 0) return RR_OK;
     if (n > 0x7fffff00u) return fail(RR_ERR_UNSUPPORTED, "%u rays in one call", n);
     if (device && (((uintptr_t)origins | (uintptr_t)directions | (uintptr_t)max_distance | (uintptr_t)out) & 3u))
         return fail(RR_ERR_INVALID_ARGUMENT, "%s: a buffer is not 4-byte aligned", fn);
+    if (device && ((uintptr_t)out & (out_align - 1u))) return fail(RR_ERR_INVALID_ARGUMENT, "%s: out_dev is not %u-byte aligned", fn, (unsigned)out_align);
     return RR_OK;
 }
 
-// One query on device buffers, in stream order (the caller holds the lock): SHADOW = limits (or NULL) and the shadow walk into
-// rr_shadow_hit records, else the closest-hit walk into rr_ray_hit records.  The only wait is await_reach.
-template <bool SHADOW>
+// One query on device buffers, in stream order (the caller holds the lock): Q_SHADOW = limits (or NULL) and the shadow walk into
+// rr_shadow_hit records, else the closest-hit walk, whose raw hits end as rr_ray_hit records (Q_CLOSEST) or, with the packed rays
+// they answer, as rr_surface_hit records (Q_SURFACE).  The only wait is await_reach.
+enum QueryKind { Q_CLOSEST, Q_SHADOW, Q_SURFACE };
+template <QueryKind KIND> struct QueryRecord { static const size_t bytes = 20; };
+template <> struct QueryRecord<Q_SURFACE> { static const size_t bytes = sizeof(rr_surface_hit); };
+template <QueryKind KIND>
 static int trace_rays_locked(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth, void* out,
                              hipStream_t st) {
+    constexpr bool SHADOW = KIND == Q_SHADOW;
     RR_TRY(take_stream(s, st));
     RR_TRY(reserve_query_records(s, n, SHADOW));
     char* w = s->query_words.as<char>();
@@ -2233,22 +2242,24 @@ static int trace_rays_locked(rr_scene* s, const float* origins, const float* dir
         RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), pr,
                                     (unsigned long long*)(w + QW_COUNTERS), st));
     }
-    hipLaunchKernelGGL(k_unpack_hits<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
+    if (KIND == Q_SURFACE) hipLaunchKernelGGL(k_surface_hits, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, s->view, q.r0, q.r1, q.hit, n, (uint4*)out);
+    else hipLaunchKernelGGL(k_unpack_hits<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->view.items, s->view.n_items, s->view.trix, (uint32_t*)out);
     HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 
-// The host form: the caller's arrays as they are (12 + 12 B per ray, 4 B of limit) and the 20-byte answers in buffers of the call,
-// freed on return (hipFree waits for what a failed call left in flight); trace_rays_locked on the null stream between them.
-template <bool SHADOW>
+// The host form: the caller's arrays as they are (12 + 12 B per ray, 4 B of limit) and the 20-byte (128-byte) answers in buffers of the
+// call, freed on return (hipFree waits for what a failed call left in flight); trace_rays_locked on the null stream between them.
+template <QueryKind KIND>
 static int trace_rays_staged(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth, void* out) {
     DevBuf d_origins, d_dirs, d_limits, d_out;
     RR_TRY(stage_in(&d_origins, origins, 12ull * n));
     RR_TRY(stage_in(&d_dirs, directions, 12ull * n));
     if (max_distance) RR_TRY(stage_in(&d_limits, max_distance, 4ull * n));
-    HIP_TRY(d_out.reserve(20ull * n));
-    RR_TRY(trace_rays_locked<SHADOW>(s, d_origins.as<float>(), d_dirs.as<float>(), d_limits.as<float>(), n, depth, d_out.p, nullptr));
-    HIP_TRY(hipMemcpy(out, d_out.p, 20ull * n, hipMemcpyDeviceToHost)); // waits for the launches: `out` is written by a finished query only
+    const size_t out_bytes = QueryRecord<KIND>::bytes * n;
+    HIP_TRY(d_out.reserve(out_bytes));
+    RR_TRY(trace_rays_locked<KIND>(s, d_origins.as<float>(), d_dirs.as<float>(), d_limits.as<float>(), n, depth, d_out.p, nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost)); // waits for the launches: `out` is written by a finished query only
     return RR_OK;
 }
 
@@ -2260,7 +2271,7 @@ extern "C" int rr_trace_rays(rr_scene* s, const float* origins, const float* dir
     RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_FAULT_POINT("trace_rays.host");
-    return trace_rays_staged<false>(s, origins, directions, nullptr, n, depth, out);
+    return trace_rays_staged<Q_CLOSEST>(s, origins, directions, nullptr, n, depth, out);
 } RR_GUARD_END("rr_trace_rays")
 
 extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const float* directions, const float* max_distance,
@@ -2275,7 +2286,7 @@ extern "C" int rr_trace_shadow_rays(rr_scene* s, const float* origins, const flo
     RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_FAULT_POINT("trace_shadow_rays.host");
-    return trace_rays_staged<true>(s, origins, directions, max_distance, n, depth, out);
+    return trace_rays_staged<Q_SHADOW>(s, origins, directions, max_distance, n, depth, out);
 } RR_GUARD_END("rr_trace_shadow_rays")
 
 extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_ray_hit* out,
@@ -2290,7 +2301,7 @@ extern "C" int rr_trace_rays_device(rr_scene* s, const float* origins, const flo
     RR_TRY(check_query_pointer(s, origins, "rr_trace_rays_device", "origins_dev"));
     RR_TRY(check_query_pointer(s, directions, "rr_trace_rays_device", "directions_dev"));
     RR_TRY(check_query_pointer(s, out, "rr_trace_rays_device", "out_dev"));
-    return trace_rays_locked<false>(s, origins, directions, nullptr, n, depth, out, (hipStream_t)hip_stream);
+    return trace_rays_locked<Q_CLOSEST>(s, origins, directions, nullptr, n, depth, out, (hipStream_t)hip_stream);
 } RR_GUARD_END("rr_trace_rays_device")
 
 extern "C" int rr_trace_shadow_rays_device(rr_scene* s, const float* origins, const float* directions, const float* max_distance, uint32_t n, uint32_t depth,
@@ -2306,8 +2317,36 @@ extern "C" int rr_trace_shadow_rays_device(rr_scene* s, const float* origins, co
     RR_TRY(check_query_pointer(s, directions, "rr_trace_shadow_rays_device", "directions_dev"));
     if (max_distance) RR_TRY(check_query_pointer(s, max_distance, "rr_trace_shadow_rays_device", "max_distance_dev"));
     RR_TRY(check_query_pointer(s, out, "rr_trace_shadow_rays_device", "out_dev"));
-    return trace_rays_locked<true>(s, origins, directions, max_distance, n, depth, out, (hipStream_t)hip_stream);
+    return trace_rays_locked<Q_SHADOW>(s, origins, directions, max_distance, n, depth, out, (hipStream_t)hip_stream);
 } RR_GUARD_END("rr_trace_shadow_rays_device")
+
+// ---- surface queries: the closest-hit query with its third ending (k_surface_hits): what get_color_depth_normal_id evaluates at the
+// hit before its light loop.  No config, no generator, nothing of a frame's state is touched.
+extern "C" int rr_surface_rays(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_surface_hit* out) try {
+    RR_TRY(check_trace_args("rr_surface_rays", false, s, origins, directions, nullptr, n, depth, out));
+    if (n == 0) return RR_OK;
+    RR_TRY(not_in_pass(s, "rr_surface_rays"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("surface_rays.host");
+    return trace_rays_staged<Q_SURFACE>(s, origins, directions, nullptr, n, depth, out);
+} RR_GUARD_END("rr_surface_rays")
+
+extern "C" int rr_surface_rays_device(rr_scene* s, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_surface_hit* out,
+                                      void* hip_stream) try {
+    RR_TRY(check_trace_args("rr_surface_rays_device", true, s, origins, directions, nullptr, n, depth, out, 16u));
+    if (n == 0) return RR_OK;
+    RR_TRY(not_in_pass(s, "rr_surface_rays_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_FAULT_POINT("surface_rays_device.host");
+    RR_TRY(check_query_pointer(s, origins, "rr_surface_rays_device", "origins_dev"));
+    RR_TRY(check_query_pointer(s, directions, "rr_surface_rays_device", "directions_dev"));
+    RR_TRY(check_query_pointer(s, out, "rr_surface_rays_device", "out_dev"));
+    return trace_rays_locked<Q_SURFACE>(s, origins, directions, nullptr, n, depth, out, (hipStream_t)hip_stream);
+} RR_GUARD_END("rr_surface_rays_device")
 
 // ---- radiance queries: Raytracing::get_color_depth_normal_id(scene, ray, 1) (reference src/raytracing.rs:720-998) for caller-supplied
 // rays -- what `render` calls per sample, without its pinhole / DOF camera.  The caller's rays are seeded as depth level 1 of the

@@ -257,14 +257,6 @@ RR_DEV uint32_t wave_alloc(uint32_t* counter, bool want, uint32_t lane) {
     return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
-// get_item_color, reference src/raytracing.rs:677-712
-RR_DEV float4 item_color(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, f3 rgb, int slot) {
-    float4 c = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-    float4 t;
-    if (tex_color(sc, m, has_uv, uv, slot, &t)) { c.x *= t.x; c.y *= t.y; c.z *= t.z; c.w *= t.w; }
-    return c;
-}
-
 // ---------------------------------------------------------------------------
 // kernel 3: shade one depth level (reference src/raytracing.rs:734-995)
 // ---------------------------------------------------------------------------
@@ -1111,8 +1103,8 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t 
 }
 
 // ---------------------------------------------------------------------------
-// kernels 5d .. 5g: the streaming passes around the walks of the DEVICE-BUFFER ray queries (rr_trace_rays_device,
-// rr_trace_shadow_rays_device, rr_shade_rays_device): the caller's 12-byte and 20-byte records are not a power of two, so a
+// kernels 5d .. 5h: the streaming passes around the walks of the DEVICE-BUFFER ray queries (rr_trace_rays_device,
+// rr_trace_shadow_rays_device, rr_shade_rays_device, rr_surface_rays_device): the caller's 12-byte and 20-byte records are not a power of two, so a
 // workgroup moves its 256 rays' 768 or 1280 consecutive dwords with lane-strided dword accesses (every wave instruction covers 64
 // consecutive dwords = two 128-B lines) and turns them into per-ray records through LDS, where a stride of 3 or 5 dwords meets
 // every bank once.  Ray i of the caller's order stays record i: packet p of the walks is rays 64 p .. 64 p + 63.
@@ -1230,6 +1222,63 @@ __global__ __launch_bounds__(RR_BLOCK) void k_unpack_hits(const uint4* __restric
             if (g < n_words) out[g] = s_w[w];
         }
         __syncthreads();
+    }
+}
+
+// 5h: the walks' raw closest hits and the packed rays they answer -> the 128-byte records of rr_surface_rays: rr_ray_hit's four words,
+// then surface_at (rr_surface.h) as eight 16-byte rows.  One ray per lane, grid-stride over groups of 256 rays like 5f; the gathers of
+// surface_at are divergent by nature, the stores are not: a lane puts its eight rows into the workgroup's LDS image (32 KB, the 256
+// records in output order) and the workgroup then moves the image out 16 bytes per lane, every wave instruction covering 1 KB of
+// consecutive bytes -- never eight lane-strided stores of 64 lines with 16 bytes each.  Inside the image row r of ray t sits in
+// 16-byte unit 8 t + (r ^ (t & 7)): the eight lanes a ds_write_b128 serves together then meet every bank once (unswizzled, all eight
+// would share four banks), and so do the lanes of the ds_read_b128 on the way out, which read 8 consecutive units of one ray.
+//   r0[i] = (origin, .), r1[i] = (direction, .): k_pack_rays' records; hits[i]: k_trace_closest's
+//   a miss, or an item index out of range: {0, 0xffffffff, 0, 0} and 112 zero bytes
+__global__ __launch_bounds__(RR_BLOCK) void k_surface_hits(DSceneView sc, const float4* __restrict__ r0, const float4* __restrict__ r1, const uint4* __restrict__ hits,
+                                                           uint32_t n, uint4* __restrict__ out) {
+    __shared__ uint4 s_rows[8 * RR_BLOCK];
+    __shared__ float s_lut[256]; // the u8 -> f32 table next to the lanes, as in k_shade
+    const uint32_t tid = threadIdx.x;
+    s_lut[tid] = c_u8_to_f32[tid];
+    __syncthreads();
+    const unsigned long long n_rows = 8ull * n;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * RR_BLOCK; base < n; base += (unsigned long long)gridDim.x * RR_BLOCK) { // block-uniform
+        const unsigned long long i = base + tid;
+        if (i < n) {
+            const uint4 h = hits[i];
+            uint4 row[8];
+            row[0] = make_uint4(0u, 0xffffffffu, 0u, 0u);
+#pragma unroll
+            for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
+            if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
+                const DItem& it = rr_global(sc.items)[h.y];
+                uint32_t face = 0u; // the reference's face id, as k_unpack_hits reports it
+                if (!(it.flags & RR_IF_SPHERE))
+                    face = __float_as_uint(rr_global(sc.trix)[(unsigned long long)it.tri_base + (h.z & 0x3fffffffu)].t0.w) + ((h.z >> 31) ? it.n_tris : 0u);
+                const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
+                const float4 a = r0[i], b = r1[i];
+                const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);
+                row[0] = make_uint4(1u, h.y, it.id, face);
+                row[1] = make_uint4(__float_as_uint(s.position.x), __float_as_uint(s.position.y), __float_as_uint(s.position.z), h.x);
+                row[2] = make_uint4(__float_as_uint(s.normal.x), __float_as_uint(s.normal.y), __float_as_uint(s.normal.z), (uint32_t)it.material);
+                row[3] = make_uint4(__float_as_uint(s.shading_normal.x), __float_as_uint(s.shading_normal.y), __float_as_uint(s.shading_normal.z), s.has_uv ? 1u : 0u);
+                row[4] = make_uint4(__float_as_uint(s.base_color.x), __float_as_uint(s.base_color.y), __float_as_uint(s.base_color.z), __float_as_uint(s.base_color.w));
+                row[5] = make_uint4(__float_as_uint(s.ambient_color.x), __float_as_uint(s.ambient_color.y), __float_as_uint(s.ambient_color.z), __float_as_uint(s.alpha));
+                row[6] = make_uint4(__float_as_uint(s.specular_color.x), __float_as_uint(s.specular_color.y), __float_as_uint(s.specular_color.z), __float_as_uint(s.reflectivity));
+                row[7] = make_uint4(__float_as_uint(s.uv.x), __float_as_uint(s.uv.y), __float_as_uint(s.roughness), __float_as_uint(s.ambient_occlusion));
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; k++) s_rows[8u * tid + (k ^ (tid & 7u))] = row[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) {
+            const uint32_t u = k * RR_BLOCK + tid;      // unit of the output image: row u % 8 of ray u / 8
+            const uint32_t t = u >> 3;
+            const unsigned long long g = 8ull * base + u;
+            if (g < n_rows) out[g] = s_rows[8u * t + ((u & 7u) ^ (t & 7u))];
+        }
+        __syncthreads(); // the next round overwrites the image
     }
 }
 

@@ -4,10 +4,11 @@
 // fresnel (:535-563).
 //
 // Offers: c_u8_to_f32 (filled by rr_api.hip); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
-// area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel.  No macros.
-// Needs: rr_primitives.h (to_local_point), rr_walk.h (rr_global).
+// item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; SurfaceAt, surface_at.  No macros.
+// Needs: rr_primitives.h (to_local_point, inverse_ray, ray_ball, to_world_normal), rr_walk.h (rr_global), rr_trace.h (ray_nonfinite).
 #pragma once
 #include "rr_walk.h"
+#include "rr_trace.h"
 
 __constant__ float c_u8_to_f32[256]; // i / 255.0f, exactly as `(p[0] as f32) / 255.0`
 
@@ -86,6 +87,14 @@ RR_DEV bool tex_color(const DSceneView& sc, const DMaterial& m, bool has_uv, f2 
     return true;
 }
 
+// get_item_color, reference src/raytracing.rs:677-712
+RR_DEV float4 item_color(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, f3 rgb, int slot) {
+    float4 c = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
+    float4 t;
+    if (tex_color(sc, m, has_uv, uv, slot, &t)) { c.x *= t.x; c.y *= t.y; c.z *= t.z; c.w *= t.w; }
+    return c;
+}
+
 // ---------------------------------------------------------------------------
 // uv / normals: reference src/shape/mesh.rs:105-161, :204-259; src/shape/sphere.rs:69-99
 // ---------------------------------------------------------------------------
@@ -162,4 +171,104 @@ RR_DEV float fresnel(f3 incident, f3 normal, float index) {
     float r_s = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
     float r_p = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
     return (r_s * r_s + r_p * r_p) / 2.0f;
+}
+
+// ---------------------------------------------------------------------------
+// the surface of a closest hit (rr_surface_rays): what get_color_depth_normal_id evaluates between `trace` and the light loop
+// (reference src/raytracing.rs:747-811, :928-933, :985-991), without lights, recursion, fog and the generator
+// ---------------------------------------------------------------------------
+// k_shade evaluates the same values inline, for its own use; this restates them, operation for operation and in k_shade's order,
+// for callers that want the values themselves.  `hit_z`: the walks' face word (leaf-order slot | negated << 30 | back << 31).
+struct SurfaceAt {
+    f3 position, normal, shading_normal; // origin + direction * toi; Shape::intersect's world normal; after normal mapping, before any jitter
+    f2 uv; bool has_uv;                  // get_uv where the material has any texture, else (0, 0) and false
+    float4 base_color, ambient_color, specular_color; // get_item_color
+    float alpha, reflectivity, roughness, ambient_occlusion;
+};
+RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m, f3 ro, f3 rd, float hit_dist, uint32_t hit_z) {
+    SurfaceAt s;
+    const bool gw = sc.general_w != 0u;
+    const uint32_t it_flags = it.flags, it_tri_base = it.tri_base;
+    const f3 hit_point = ro + (rd * hit_dist);
+    const uint32_t slot = hit_z & 0x3fffffffu;
+    const bool back = (hit_z >> 31) != 0u, neg = ((hit_z >> 30) & 1u) != 0u;
+    s.position = hit_point;
+
+    // ---- world normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65)
+    f3 normal;
+    DTriAttr at; float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f; bool have_weights = false;
+    at.s0 = at.s1 = at.s2 = at.s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (it_flags & RR_IF_SPHERE) {
+        LRay lr = inverse_ray(it, ro, rd, gw || ray_nonfinite(ro, rd)); // (see to_local_point)
+        float t2 = 0.0f; bool inside = false;
+        ray_ball(it.radius, lr, (it_flags & RR_IF_SOLID_BASE) != 0u, &t2, &inside);
+        f3 nl = normalize3(lr.o + lr.d * t2);
+        normal = to_world_normal(it, inside ? -nl : nl);
+    } else {
+        const DTri* trp = &rr_global(sc.tris)[it_tri_base + slot];
+        // the area weights of the hit point serve the interpolated normal AND the uv (src/shape/mesh.rs:105-161, :204-259)
+        if ((it_flags & RR_IF_SMOOTH) || (m.flags & RR_MF_ANY_TEX)) {
+            const float4 v0 = trp->v0, v1 = trp->v1, v2 = trp->v2;
+            at = rr_global(sc.attrs)[it_tri_base + slot];
+            const f3 p = to_local_point(it, hit_point, gw);
+            area_weights(mk3(v0.x, v0.y, v0.z), mk3(v1.x, v1.y, v1.z), mk3(v2.x, v2.y, v2.z), p, v1.w, &a1, &a2, &a3); // v1.w: the triangle's area (host)
+            have_weights = true;
+        }
+        if (it_flags & RR_IF_SMOOTH) {
+            f3 p1 = mk3(at.s0.x, at.s0.y, at.s0.z) * a1, p2 = mk3(at.s1.x, at.s1.y, at.s1.z) * a2, p3 = mk3(at.s2.x, at.s2.y, at.s2.z) * a3;
+            normal = to_world_normal(it, mk3(p1.x + p2.x + p3.x, p1.y + p2.y + p3.y, p1.z + p2.z + p3.z));
+            if (back) normal = -normal;
+        } else {
+            // to_world_normal(it, neg ? -ng : ng) with ng = DTri::v3, evaluated once per instanced triangle by k_world_normals
+            const float4 wn = rr_global(sc.flat_normals)[it.wn_base + 2u * slot + (neg ? 1u : 0u)];
+            normal = mk3(wn.x, wn.y, wn.z);
+        }
+        if (it_flags & RR_IF_FLIP_NORMALS) normal = -normal;
+    }
+    s.normal = normal;
+    // ---- uv (:749-754)
+    bool has_uv = false; f2 uv; uv.x = 0.0f; uv.y = 0.0f;
+    if (m.flags & RR_MF_ANY_TEX) {
+        if (it_flags & RR_IF_SPHERE) uv = sphere_uv(it, hit_point, gw);
+        else if (have_weights && (__float_as_uint(at.s3.w) & 1u)) { // Mesh::get_uv with the weights from above
+            uv.x = (at.s0.w * a1 + at.s2.w * a2) + at.s3.y * a3;
+            uv.y = -((at.s1.w * a1 + at.s3.x * a2) + at.s3.z * a3);
+        }
+        has_uv = true;
+    }
+    s.uv = uv; s.has_uv = has_uv;
+    f3 surface_normal = normal;
+    float4 tc;
+    // ---- normal mapping (:757-784)
+    if (tex_color(sc, m, has_uv, uv, 3, &tc)) {
+        f3 tangent = cross3(normal, mk3(0.0f, 1.0f, 0.0f));
+        if (norm3(tangent) <= 0.0001f) tangent = cross3(normal, mk3(0.0f, 0.0f, 1.0f));
+        tangent = normalize3(tangent);
+        f3 bitangent = normalize3(cross3(normal, tangent));
+        f3 nm = mk3((tc.x * 2.0f) - 1.0f, (tc.y * 2.0f) - 1.0f, (tc.z * 2.0f) - 1.0f);
+        nm.x *= m.normal_map_strength; nm.y *= m.normal_map_strength;
+        nm = normalize3(nm);
+        f3 t;
+        t.x = (tangent.x * nm.x + bitangent.x * nm.y) + normal.x * nm.z;
+        t.y = (tangent.y * nm.x + bitangent.y * nm.y) + normal.y * nm.z;
+        t.z = (tangent.z * nm.x + bitangent.z * nm.y) + normal.z * nm.z;
+        surface_normal = normalize3(t);
+    }
+    s.shading_normal = surface_normal;
+    // ---- roughness (:787-798): the spread the jitter would take, whether or not monte_carlo asks for one
+    s.roughness = m.roughness;
+    if (tex_color(sc, m, has_uv, uv, 5, &tc)) s.roughness = (1.0f / RR_PI_F / 2.0f) * tc.x;
+    // ---- colours and alpha (:801-811)
+    s.ambient_color = item_color(sc, m, has_uv, uv, m.ambient, 1);
+    s.base_color = item_color(sc, m, has_uv, uv, m.base, 0);
+    s.specular_color = item_color(sc, m, has_uv, uv, m.specular, 2);
+    float alpha = m.alpha * s.base_color.w;
+    if (tex_color(sc, m, has_uv, uv, 4, &tc)) alpha *= tc.x;
+    s.alpha = alpha;
+    // ---- reflectivity (:928-933) and ambient occlusion (:985-991)
+    s.reflectivity = m.reflectivity;
+    if (tex_color(sc, m, has_uv, uv, 7, &tc)) s.reflectivity = tc.x;
+    s.ambient_occlusion = 1.0f;
+    if (tex_color(sc, m, has_uv, uv, 6, &tc)) s.ambient_occlusion = tc.x;
+    return s;
 }

@@ -111,6 +111,29 @@ class rr_radiance(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("object_id", C.c_uint32)]
 
 
+class rr_surface_hit(C.Structure):
+    """include/rustray_hip.h: one record of rr_surface_rays (128 bytes, eight 16-byte rows)."""
+    _fields_ = [("hit", C.c_uint32), ("item_index", C.c_uint32), ("object_id", C.c_uint32), ("face_id", C.c_uint32),
+                ("position", C.c_float * 3), ("distance", C.c_float),
+                ("normal", C.c_float * 3), ("material", C.c_int32),
+                ("shading_normal", C.c_float * 3), ("has_uv", C.c_uint32),
+                ("base_color", C.c_float * 4),
+                ("ambient_color", C.c_float * 3), ("alpha", C.c_float),
+                ("specular_color", C.c_float * 3), ("reflectivity", C.c_float),
+                ("uv", C.c_float * 2), ("roughness", C.c_float), ("ambient_occlusion", C.c_float)]
+
+
+# the same record as a numpy structured dtype (rr_surface_rays returns an array of it)
+SURFACE_HIT_DTYPE = np.dtype([("hit", np.uint32), ("item_index", np.uint32), ("object_id", np.uint32), ("face_id", np.uint32),
+                              ("position", np.float32, (3,)), ("distance", np.float32),
+                              ("normal", np.float32, (3,)), ("material", np.int32),
+                              ("shading_normal", np.float32, (3,)), ("has_uv", np.uint32),
+                              ("base_color", np.float32, (4,)),
+                              ("ambient_color", np.float32, (3,)), ("alpha", np.float32),
+                              ("specular_color", np.float32, (3,)), ("reflectivity", np.float32),
+                              ("uv", np.float32, (2,)), ("roughness", np.float32), ("ambient_occlusion", np.float32)])
+
+
 class rr_frame_stats(C.Structure):
     _fields_ = [
         ("primary_rays", C.c_uint64), ("secondary_rays", C.c_uint64), ("shadow_rays", C.c_uint64),

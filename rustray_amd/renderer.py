@@ -545,6 +545,31 @@ def trace_rays_torch(device_scene: capi.DeviceScene, origins, directions, depth:
     return _hit_views(rec, "hit")
 
 
+def surface_rays_torch(device_scene: capi.DeviceScene, origins, directions, depth: int = 1) -> dict:
+    """rr_surface_rays_device on torch's current stream: as trace_rays_torch (depth 1 = a frame's primary ray).  Returns torch tensors,
+    without a host copy and without a synchronisation of the results: dict(records (n, 32) float32 = n rr_surface_hit records, and
+    views of it named as the struct's fields: hit, item_index, object_id, face_id, material, has_uv as int32 views; position, normal,
+    shading_normal, ambient_color, specular_color (n, 3), base_color (n, 4), uv (n, 2), distance, alpha, reflectivity, roughness,
+    ambient_occlusion (n,))."""
+    import torch
+    o = _ray_tensor(device_scene, origins, "origins")
+    d = _ray_tensor(device_scene, directions, "directions")
+    if d.shape[0] != o.shape[0]:
+        raise ValueError(f"{o.shape[0]} origins, {d.shape[0]} directions")
+    dev = torch.device("cuda", device_scene.device)
+    n = int(o.shape[0])
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 32), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        if n:
+            device_scene.surface_rays_device(o.data_ptr(), d.data_ptr(), n, depth, rec.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    i = rec.view(torch.int32)
+    return {"records": rec, "hit": i[:, 0], "item_index": i[:, 1], "object_id": i[:, 2], "face_id": i[:, 3],
+            "position": rec[:, 4:7], "distance": rec[:, 7], "normal": rec[:, 8:11], "material": i[:, 11],
+            "shading_normal": rec[:, 12:15], "has_uv": i[:, 15], "base_color": rec[:, 16:20],
+            "ambient_color": rec[:, 20:23], "alpha": rec[:, 23], "specular_color": rec[:, 24:27], "reflectivity": rec[:, 27],
+            "uv": rec[:, 28:30], "roughness": rec[:, 30], "ambient_occlusion": rec[:, 31]}
+
+
 def trace_shadow_rays_torch(device_scene: capi.DeviceScene, origins, directions, max_distance=None, depth: int = 2) -> dict:
     """rr_trace_shadow_rays_device on torch's current stream: as trace_rays_torch, with `max_distance` a contiguous float32 CUDA tensor of
     shape (n,) or None (no limit).  Returns dict(records (n, 5) int32, occluded, item_index (-1 = lit), object_id, face_id, distance)."""
