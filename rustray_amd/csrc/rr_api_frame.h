@@ -1,0 +1,744 @@
+// rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
+// Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
+//         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
+//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; render_region_locked; rr_render_region_device,
+//         rr_render, rr_render_progressive, rr_render_progressive_tiles; rr_scene_last_stats, rr_scene_overlap_stages;
+//         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
+// Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
+//         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h,
+//         rr_primary_setup.h, the frame kernels of rr_kernels.hip.
+
+// ---------------------------------------------------------------------------
+// frame
+// ---------------------------------------------------------------------------
+static int check_frame_args(const rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy) {
+    if (!s || !cam || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (cfg->samples == 0) return fail(RR_ERR_INVALID_ARGUMENT, "samples must be >= 1");
+    // with the caller's table the reference's own u16 limit applies; the built-in table stops where its shuffle stays affordable
+    if (cfg->samples > (sample_xy ? RR_MAX_SAMPLES_WITH_TABLE : RR_MAX_SAMPLES))
+        return fail(RR_ERR_UNSUPPORTED, "samples %u > %u%s", (unsigned)cfg->samples, sample_xy ? RR_MAX_SAMPLES_WITH_TABLE : RR_MAX_SAMPLES,
+                    sample_xy ? "" : " (the built-in sub-sample table; pass sample_xy for up to 32766)");
+    if (cfg->max_recursion > RR_MAX_RECURSION) return fail(RR_ERR_UNSUPPORTED, "max_recursion %u > %u", cfg->max_recursion, RR_MAX_RECURSION);
+    if (cam->width == 0 || cam->height == 0 || cam->width > 65535u || cam->height > 65535u) return fail(RR_ERR_INVALID_ARGUMENT, "bad frame size %ux%u", cam->width, cam->height);
+    if (!finite16(cam->projection_inverse) || !finite16(cam->view_inverse)) return fail(RR_ERR_INVALID_ARGUMENT, "non-finite camera matrix");
+    return RR_OK;
+}
+
+static hipEvent_t take_event(rr_scene* s) {
+    if (!s->timing.event_pool.empty()) { hipEvent_t e = s->timing.event_pool.back(); s->timing.event_pool.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+struct ScopedTimer {
+    rr_scene* s; hipStream_t st; TimerKernel kernel; bool level1; hipEvent_t a = nullptr, b = nullptr;
+    ScopedTimer(rr_scene* s_, hipStream_t st_, TimerKernel kernel_, bool level1_) : s(s_), st(st_), kernel(kernel_), level1(level1_) {
+        if (s->timing.profiling) { a = take_event(s); b = take_event(s); (void)hipEventRecord(a, st); }
+    }
+    ~ScopedTimer() { if (s->timing.profiling) { (void)hipEventRecord(b, st); s->timing.timed.push_back(TimedLaunch{a, b, kernel, level1}); } }
+};
+
+// the rr_frame_stats fields of each TimerKernel: every launch, and the launches of its level-1 build (binning: time only)
+static const struct {
+    double rr_frame_stats::*ms; uint64_t rr_frame_stats::*launches;
+    double rr_frame_stats::*ms_level1; uint64_t rr_frame_stats::*launches_level1;
+} k_timer_fields[] = {
+    {&rr_frame_stats::ms_trace_closest, &rr_frame_stats::launches_trace_closest, &rr_frame_stats::ms_trace_closest_level1, &rr_frame_stats::launches_trace_closest_level1},
+    {&rr_frame_stats::ms_trace_shadow, &rr_frame_stats::launches_trace_shadow, &rr_frame_stats::ms_trace_shadow_level1, &rr_frame_stats::launches_trace_shadow_level1},
+    {&rr_frame_stats::ms_shade, &rr_frame_stats::launches_shade, &rr_frame_stats::ms_shade_level1, &rr_frame_stats::launches_shade_level1},
+    {&rr_frame_stats::ms_binning, nullptr, nullptr, nullptr},
+};
+
+static void resolve_timers(rr_scene* s) {
+    for (auto& t : s->timing.timed) {
+        float ms = 0.0f;
+        if (hipEventSynchronize(t.b) == hipSuccess && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
+            const auto& f = k_timer_fields[t.kernel];
+            s->timing.stats.*f.ms += ms;
+            if (f.launches) s->timing.stats.*f.launches += 1;
+            if (t.level1) { s->timing.stats.*f.ms_level1 += ms; s->timing.stats.*f.launches_level1 += 1; }
+        }
+        s->timing.event_pool.push_back(t.a); s->timing.event_pool.push_back(t.b);
+    }
+    s->timing.timed.clear();
+}
+
+// ---- the output buffers of a frame, in rr_frame order, and their bytes per pixel: rgba8, normal (3 x f32), depth, object_id
+static const size_t OUT_ELEM[4] = {4, 12, 4, 4};
+static void* out_buffer(const rr_frame& f, int k) {
+    void* const b[4] = {f.rgba8, f.normal, f.depth, f.object_id};
+    return b[k];
+}
+// The device frame behind a frame for the host: s->frame.tmp_out[k] of np pixels for every buffer `host` asks for, zeroed on request.
+static int stage_outputs(rr_scene* s, const rr_frame& host, size_t np, bool zero, rr_frame* dev) {
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++) {
+        if (!out_buffer(host, k)) continue;
+        HIP_TRY(s->frame.tmp_out[k].reserve(np * OUT_ELEM[k]));
+        p[k] = s->frame.tmp_out[k].p;
+        if (zero) HIP_TRY(hipMemsetAsync(p[k], 0, np * OUT_ELEM[k], nullptr));
+    }
+    *dev = rr_frame{(uint8_t*)p[0], (float*)p[1], (float*)p[2], (uint32_t*)p[3]};
+    return RR_OK;
+}
+// dev -> host for every buffer both have (np pixels each), on stream st; returns when they are on the host
+static int copy_outputs(const rr_frame& host, const rr_frame& dev, size_t np, hipStream_t st) {
+    for (int k = 0; k < 4; k++)
+        if (out_buffer(host, k) && out_buffer(dev, k))
+            HIP_TRY(hipMemcpyAsync(out_buffer(host, k), out_buffer(dev, k), np * OUT_ELEM[k], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RR_OK;
+}
+
+// Progressive preview (rr_render_progressive): after every device batch that ends on a whole slice of samples the
+// accumulators are resolved over the samples finished so far and handed to the caller (the device frame -> `host`).
+struct PassHook { rr_pass_fn fn; void* user; uint32_t min_passes; const rr_frame* host; };
+
+// The ONE place that launches the closest-hit kernel: the frame path (run_level), rr_pick and rr_trace_rays all come through here, so a
+// change to the kernel's arguments cannot leave one caller behind.  Every pointer the kernel may touch is checked here, on the host,
+// before the launch: a NULL one would be a write to address 16 * i on the device.  Level 1 reads no ray records (the rays are
+// derived from their index), so its queue carries the hit records only and its ray pointers are passed as NULL.
+static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t* count, uint32_t* head, uint64_t n, const DShadeConst* kc,
+                                const DPrimary& pr, unsigned long long* counters, hipStream_t st) {
+    if (!count || !head || !q.hit || !kc || !counters) return fail(RR_ERR_DEVICE, "internal: closest-hit launch with a NULL argument");
+    if (primary && (!pr.sample_tr || pr.n != n)) return fail(RR_ERR_DEVICE, "internal: level-1 closest-hit launch without its ray table");
+    if (!primary && (!q.r0 || !q.r1 || !q.r2)) return fail(RR_ERR_DEVICE, "internal: closest-hit launch without ray records");
+    if (n == 0 || n > 0x7fffff00ull) return fail(RR_ERR_DEVICE, "internal: closest-hit launch of %llu rays", (unsigned long long)n);
+    const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * RR_CLOSEST_WAVES);
+    if (primary) {
+        q.r0 = nullptr; q.r1 = nullptr; q.r2 = nullptr;
+        hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters);
+    } else {
+        hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters);
+    }
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+
+// ---- the steps of a frame (render_region_locked)
+
+// the region's accumulator slots on the device (slot -> pixel, slot -> output index), uploaded when the region changes
+static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_region& rg, hipStream_t st) {
+    if (memcmp(&s->frame.region_cached, &rg, sizeof rg) == 0 && s->frame.region_w == W && s->frame.region_h == H) return RR_OK;
+    std::vector<uint32_t> order;
+    fill_region(W, H, rg, &s->frame.h_region_xy, &order);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(s->frame.region_xy.reserve(std::max<size_t>(s->frame.h_region_xy.size(), 1) * 4));
+    HIP_TRY(s->frame.slot_c.reserve(std::max<size_t>(s->frame.h_region_xy.size(), 1) * 8));
+    HIP_TRY(s->frame.trace_order.reserve(std::max<size_t>(order.size(), 1) * 4));
+    if (!s->frame.h_region_xy.empty()) {
+        // slot_xy[j] = pixel of accumulator slot j; slot_out[j] = its index in the compact output order
+        std::vector<uint32_t> slot_xy(order.size());
+        for (size_t j = 0; j < order.size(); j++) slot_xy[j] = s->frame.h_region_xy[order[j]];
+        HIP_TRY(hipMemcpy(s->frame.region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice));
+        std::vector<float> slot_c(slot_xy.size() * 2); // the pixel centres on the screen, as primary_ray adds the sample's offset to them
+        primary_slot_centres(slot_xy.data(), slot_xy.size(), W, H, slot_c.data());
+        HIP_TRY(hipMemcpy(s->frame.slot_c.p, slot_c.data(), slot_c.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->frame.trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+    }
+    s->frame.region_cached = rg; s->frame.region_w = W; s->frame.region_h = H;
+    return RR_OK;
+}
+
+// the frame constants of a camera and config (n_region_pixels is the caller's)
+static DFrame make_frame(const rr_camera* cam, const rr_config* cfg) {
+    DFrame fr;
+    memset(&fr, 0, sizeof fr);
+    memcpy(fr.proj_inv, cam->projection_inverse, 64);
+    memcpy(fr.view_inv, cam->view_inverse, 64);
+    fr.width = cam->width; fr.height = cam->height; fr.samples = cfg->samples; fr.cell_size = cell_size_of(cfg->samples);
+    fr.max_recursion = cfg->max_recursion; fr.monte_carlo = cfg->monte_carlo ? 1u : 0u; fr.gamma = cfg->gamma_correction ? 1u : 0u;
+    fr.dof = (cfg->aperture_size > 1.0f && cfg->focal_length > 1.0f) ? 1u : 0u;
+    fr.focal_length = cfg->focal_length; fr.aperture_size = cfg->aperture_size; fr.fog_density = cfg->fog_density;
+    for (int k = 0; k < 3; k++) fr.fog_color[k] = cfg->fog_color[k];
+    fr.seed_lo = (uint32_t)cfg->seed; fr.seed_hi = (uint32_t)(cfg->seed >> 32);
+    return fr;
+}
+
+// the shade kernel's constants (scene view + frame), read from device memory
+static int upload_shade_const(rr_scene* s, const DFrame& fr, const PrimaryFrame& ps, hipStream_t st) {
+    DShadeConst hc;
+    hc.sc = s->data.view; hc.fr = fr; hc.ps = ps;
+    HIP_TRY(s->frame.shade_const.reserve(sizeof hc));
+    HIP_TRY(hipMemcpyAsync(s->frame.shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // `hc` is a stack local
+    return RR_OK;
+}
+
+// sample_tr on the device: the screen offset of every sample of this frame (primary_sample_offsets), uploaded only when the
+// sub-sample table or a frame constant it depends on differs from what the buffer holds
+static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sample_xy, hipStream_t st) {
+    const uint32_t samples = fr.samples;
+    if (!sample_xy) { // the built-in table depends on the sample count only: built once per count, not once per frame
+        if (s->frame.table_samples != samples) {
+            s->frame.table_samples = 0; // the cache names a sample count only once its table is complete
+            try { s->frame.table_cache.resize((size_t)samples * 2); }
+            catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sub-sample table"); }
+            RR_TRY(rr_sample_table((uint16_t)samples, s->frame.table_cache.data(), nullptr));
+            s->frame.table_samples = (uint16_t)samples;
+        }
+        sample_xy = s->frame.table_cache.data();
+    }
+    const PrimarySampleKey key{fr.width, fr.height, fr.cell_size, fr.dof, samples, fr.aperture_size};
+    if (s->frame.tr_valid && same_key(s->frame.tr_key, key) && s->frame.tr_table.size() == (size_t)samples * 2 &&
+        memcmp(s->frame.tr_table.data(), sample_xy, (size_t)samples * 4) == 0) return RR_OK;
+    s->frame.tr_valid = false;
+    std::vector<float> tr;
+    try { s->frame.tr_table.assign(sample_xy, sample_xy + (size_t)samples * 2); tr.resize((size_t)samples * 2); }
+    catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sample offsets"); }
+    primary_sample_offsets(sample_xy, key, tr.data());
+    HIP_TRY(hipStreamSynchronize(st)); // an earlier frame on this stream may still read the buffer
+    HIP_TRY(s->frame.sample_tr.reserve((size_t)samples * 8));
+    HIP_TRY(hipMemcpyAsync(s->frame.sample_tr.p, tr.data(), (size_t)samples * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // `tr` is a local
+    s->frame.tr_key = key; s->frame.tr_valid = true;
+    return RR_OK;
+}
+
+// zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all
+static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool want_depth, bool want_id, hipStream_t st, DAccum* acc) {
+    HIP_TRY(s->frame.acc_rgb.reserve((size_t)npix * 24));
+    HIP_TRY(s->frame.acc_normal.reserve((size_t)npix * 24));
+    HIP_TRY(s->frame.acc_depth.reserve((size_t)npix * 8));
+    HIP_TRY(s->frame.acc_id.reserve((size_t)npix * 4));
+    HIP_TRY(s->frame.acc_flags.reserve((size_t)npix * 4));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_flags.p, 0, (size_t)npix * 4, st));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_rgb.p, 0, (size_t)npix * 24, st));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_normal.p, 0, (size_t)npix * 24, st));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_depth.p, 0, (size_t)npix * 8, st));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_id.p, 0, (size_t)npix * 4, st));
+    HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
+    *acc = DAccum{s->frame.acc_rgb.as<long long>(), want_normal ? s->frame.acc_normal.as<long long>() : nullptr, want_depth ? s->frame.acc_depth.as<long long>() : nullptr,
+                  want_id ? s->frame.acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
+    return RR_OK;
+}
+
+// Ray memory (rr_frame_plan.h): a quarter of what is free on the device, at most 64 GB (MI355X has 288 GB of HBM3E),
+// unless rr_tuning::queue_budget_bytes says otherwise.  Memory already held by this scene's arena counts as free.
+static int queue_budget(rr_scene* s, uint64_t* budget) {
+    if (s->tuning.queue_budget_bytes) { *budget = s->tuning.queue_budget_bytes; return RR_OK; }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    *budget = std::min<uint64_t>((free_b + 56ull * s->frame.arena_cap + s->frame.hit1.bytes) / 4, 64ull << 30);
+    return RR_OK;
+}
+
+// how n hits of level 1 are cut into stages for the two-stream path (rr_frame_plan.h; the knobs: rr_kernels.hip)
+static bool level1_stages_wanted(const rr_scene* s) { return RR_L1_OVERLAP >= 2 || (RR_L1_OVERLAP == 1 && s->tuning.shade_chunk_rays != 0); }
+static Level1Stages level1_stages(const rr_scene* s, uint64_t n) {
+    return plan_level1_stages(Level1StageInputs{n, s->data.n_enabled_lights, s->tuning.shade_chunk_rays, RR_L1_STAGE_RAYS, RR_L1_BUFFERS});
+}
+
+// the ray arena for M rays and the shadow queue for sq_need rays, with at least valid_need words of lane masks (grown, never shrunk)
+static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t valid_need) {
+    if (M > s->frame.arena_cap) {
+        for (int k = 0; k < 4; k++) HIP_TRY(s->frame.arena[k].reserve(M * RAY_RECORD_BYTES[k]));
+        s->frame.arena_cap = M;
+    }
+    if (sq_need > s->frame.sq_cap) { // (one word of sq_valid per 64 rays of the queue)
+        for (int k = 0; k < 3; k++) HIP_TRY(s->frame.sq[k].reserve(sq_need * 16));
+        HIP_TRY(s->frame.sq_valid.reserve(std::max<uint64_t>(sq_need / RR_WAVE + 1, valid_need) * 8));
+        s->frame.sq_cap = sq_need;
+    }
+    return RR_OK;
+}
+
+// the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue
+static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan) {
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan& p = *plan = plan_frame(FramePlanInputs{npix, cfg->samples, cfg->max_recursion, budget, s->tuning.sample_group, min_passes,
+                                                            s->frame.arena_factor, s->data.n_enabled_lights, s->tuning.shade_chunk_rays});
+    HIP_TRY(s->frame.hit1.reserve(p.B * 16));
+    // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
+    const Level1Stages sp = level1_stages(s, p.B);
+    return grow_ray_queues(s, p.M, std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need);
+}
+
+// Per-batch counters (level sizes, fetch heads, shadow shard counts) come out of zeroed segments of POOL_WORDS words.  A segment
+// is never recycled inside a batch (launches still in flight and the levels above in the recursion hold pointers into it); a
+// batch with more launches than one segment serves (a deeply branching scene in a very small ray arena) gets another one.
+struct CounterPool {
+    rr_scene* s; hipStream_t st;
+    uint32_t* pool = nullptr;
+    uint32_t next_word = 0;
+    size_t pool_segment = 0; // 0 = s->frame.pool, k = s->frame.pool_more[k - 1]
+    int start_batch() {
+        pool = s->frame.pool.as<uint32_t>(); pool_segment = 0;
+        HIP_TRY(hipMemsetAsync(pool, 0, POOL_WORDS * 4, st));
+        next_word = 0;
+        return RR_OK;
+    }
+    // n zeroed words; nullptr = no memory for another segment
+    uint32_t* take(uint32_t n) {
+        if (next_word + n > POOL_WORDS) {
+            if (pool_segment == s->frame.pool_more.size()) {
+                if (s->frame.pool_more.size() >= 255) return nullptr; // 4 GB of counters: something else is wrong
+                s->frame.pool_more.emplace_back();
+                if (s->frame.pool_more.back().reserve(POOL_WORDS * 4) != hipSuccess) { s->frame.pool_more.pop_back(); return nullptr; }
+            }
+            pool = s->frame.pool_more[pool_segment++].as<uint32_t>();
+            if (hipMemsetAsync(pool, 0, POOL_WORDS * 4, st) != hipSuccess) return nullptr;
+            next_word = 0;
+        }
+        uint32_t* p = pool + next_word; next_word += n; return p;
+    }
+    void align_line() { next_word = (next_word + 31u) & ~31u; } // the next words start on a 128-B line
+};
+static int counters_exhausted() { return fail(RR_ERR_UNSUPPORTED, "out of memory for the per-launch counters of a batch"); }
+
+// what the depth levels of a frame share
+struct FrameRun {
+    rr_scene* s; hipStream_t st;
+    FramePlan plan; uint32_t R;
+    DShadowQueue SQ; DAccum acc;
+    CounterPool pool;
+    DPrimary pr; // the batch being traced: depth level 1
+    const volatile int* cancel;
+    int shadow_grid, shade_grid_max;
+    const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, or the stream ids of rr_shade_rays
+    bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
+    DRayQueue queue_at(uint64_t base) const {
+        return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
+    }
+};
+
+// On request (rr_tuning::bin_min_rays) a deeper level of m rays at child_base is traced in bins of (origin cell, direction octant)
+// when the sorted copy fits behind the unsorted one (rr_kernels.hip: ray binning; off by default, it does not pay).
+// *level_base = child_base + m (the sorted copy) when the level was binned.
+static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* level_base) {
+    rr_scene* s = f.s;
+    const uint64_t bin_min = s->tuning.bin_min_rays;
+    if (bin_min == 0 || m < bin_min || f.plan.M - child_base < 3 * m + 2ull * RR_BLOCK * (f.R + 1)) return RR_OK;
+    f.pool.align_line();
+    int* bounds = (int*)f.pool.take(8);
+    uint32_t* hist = f.pool.take(RR_BIN_COUNT);
+    if (!bounds || !hist) return RR_OK;
+    const int init[8] = {0x7f7fffff, 0x7f7fffff, 0x7f7fffff, (int)0x80800000, (int)0x80800000, (int)0x80800000, 0, 0}; // ordered(+FLT_MAX) x3, ordered(-FLT_MAX) x3
+    HIP_TRY(hipMemcpyAsync(bounds, init, sizeof init, hipMemcpyHostToDevice, f.st));
+    const DRayQueue qsrc = f.queue_at(child_base), qdst = f.queue_at(child_base + m);
+    const int g = (int)std::min<uint64_t>((m + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8);
+    ScopedTimer t(s, f.st, TK_BINNING, false);
+    hipLaunchKernelGGL(k_bin_bounds, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds);
+    hipLaunchKernelGGL(k_bin_count, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds, hist);
+    hipLaunchKernelGGL(k_bin_prefix, dim3(1), dim3(1024), 0, f.st, hist);
+    hipLaunchKernelGGL(k_bin_scatter, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, qdst, (uint32_t)m, hist);
+    *level_base = child_base + m;
+    s->timing.stats.binned_rays += m;
+    return RR_OK;
+}
+
+// ---- level 1 in stages on two streams ---------------------------------------------------------------------------------------------
+// k_shade<true> is bound by instruction issue and k_trace_shadow<true> by memory latency; one after the other, each has the whole
+// GPU in turn.  Here the hits [s0, s1) are cut into stages (rr_frame_plan.h, plan_level1_stages): stage k is shaded on the frame's
+// stream `st` into shadow buffer k % n_buf, and its shadow rays are traced on the handle's second stream behind an event that
+// follows the shade launch, while `st` already shades stage k + 1.  Shade k + n_buf waits for the event behind shadow k, so a
+// buffer is never rewritten while it is read.  `st` may be the legacy null stream and the second stream is non-blocking: all
+// ordering is by these events.  The frame cannot change: the kernels are the serial loop's, every write they share is an integer
+// atomic, and all else goes to the stage's own buffer.  Which frames take this path, and the sizes of the two grids: RR_L1_OVERLAP
+// and the knobs after it (rr_kernels.hip), with what was measured.
+static int ensure_overlap_stream(rr_scene* s) {
+    if (!s->frame.overlap_stream) HIP_TRY(hipStreamCreateWithFlags(&s->frame.overlap_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 3; b++) {
+        if (!s->frame.stage_shaded[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_shaded[b], hipEventDisableTiming));
+        if (!s->frame.stage_traced[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_traced[b], hipEventDisableTiming));
+    }
+    return RR_OK;
+}
+
+// enqueues every stage; on any error the caller (run_level1_stages) drains both streams
+static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
+                                 const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+    rr_scene* s = f.s;
+    const hipStream_t st = f.st, st2 = s->frame.overlap_stream;
+    const uint32_t L = s->data.n_enabled_lights;
+    unsigned long long* counters = s->frame.counters.as<unsigned long long>();
+    if (sp.sq_need > s->frame.sq_cap || sp.valid_need * 8 > s->frame.sq_valid.bytes) return fail(RR_ERR_DEVICE, "internal: shadow queue smaller than its stage buffers");
+    for (uint32_t k = 0; k < sp.n_stages; k++) {
+        if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        const uint64_t c0 = s0 + sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, s1);
+        const uint32_t b = sp.buffer_of(k);
+        const bool first = k == 0, last = k + 1 == sp.n_stages;
+        const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK;
+        const uint32_t sq_chunk_cap = (uint32_t)(groups * RR_BLOCK); // <= sp.stage: L x this many slots fit the buffer
+        const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * L);
+        const DShadowQueue SQ{f.SQ.s0 + sp.ray_offset[b], f.SQ.s1 + sp.ray_offset[b], f.SQ.s2 + sp.ray_offset[b]};
+        unsigned long long* sq_valid = s->frame.sq_valid.as<unsigned long long>() + sp.valid_offset[b];
+        f.pool.align_line();
+        uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
+        uint32_t* shead = f.pool.take(1); // (zeroed on `st` before the event the second stream waits for)
+        if (!sq_counts || !shead) return counters_exhausted();
+        // the first stage's shade and the last stage's shadow run alone: the serial loop's grids.  In between the two launches share the CUs.
+        const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : groups);
+        const uint64_t shadow_wg = last ? (uint64_t)f.shadow_grid : (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
+        if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[b], 0));
+        {
+            ScopedTimer t(s, st, TK_SHADE, true);
+            hipLaunchKernelGGL(k_shade<true>, dim3((uint32_t)std::min<uint64_t>(groups, shade_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), s->frame.region_xy.as<uint32_t>(),
+                               f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+        }
+        HIP_TRY(hipGetLastError());
+        if (spawns && last) { // the next level's size, behind the last shade stage (run_level waits for it)
+            HIP_TRY(hipMemcpyAsync(s->frame.h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(s->frame.count_ready, st));
+        }
+        HIP_TRY(hipEventRecord(s->frame.stage_shaded[b], st));
+        HIP_TRY(hipStreamWaitEvent(st2, s->frame.stage_shaded[b], 0));
+        {
+            ScopedTimer t(s, st2, TK_SHADOW, true);
+            const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
+            const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, shadow_wg);
+            hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st2, s->data.view, SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->frame.stage_traced[b], st2));
+    }
+    // the second stream joins `st` here: before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
+    HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[sp.buffer_of(sp.n_stages - 1)], 0));
+    return RR_OK;
+}
+
+// THE one way in and out of the staged path: whatever ends it early (cancel flag, HIP error, counter pool exhausted) leaves both streams idle,
+// so the handle stays usable and the next frame cannot race a straggler.
+static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
+                             const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+    rr_scene* s = f.s;
+    RR_TRY(ensure_overlap_stream(s));
+    const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns);
+    if (rc != RR_OK) {
+        (void)hipStreamSynchronize(s->frame.overlap_stream);
+        (void)hipStreamSynchronize(f.st);
+        return rc;
+    }
+    s->frame.overlap_stages += sp.n_stages;
+    return RR_OK;
+}
+
+// One depth level: rays [base, base + n) of the arena, their count also in the device word `count`.
+// The size of the next level is read back once per slice (4 bytes + stream sync), so launches are sized by the
+// rays that exist and empty levels are never launched.
+// depth level 1 = the batch's primary rays [pr.first, pr.first + pr.n): only hit records (hit1); its children start the arena
+// SEEDED (rr_shade_rays): depth level 1 is n ray records at the front of the arena like any deeper level -- arena hit records, the
+// <false> builds of the three kernels (a path is a root where its record says depth 1 and carries the id bit), children behind
+// the level, the dense shadow queue, no stages.
+static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_t* count) {
+    rr_scene* s = f.s;
+    const hipStream_t st = f.st;
+    const uint32_t L = s->data.n_enabled_lights;
+    unsigned long long* counters = s->frame.counters.as<unsigned long long>();
+    const bool l1 = d == 1 && !f.seeded; // the level-1 builds: rays derived from their index
+    DRayQueue qin = f.queue_at(base);
+    if (l1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->frame.hit1.as<uint4>(); }
+    {
+        uint32_t* head = f.pool.take(1);
+        if (!head) return counters_exhausted();
+        ScopedTimer t(s, st, TK_CLOSEST, l1);
+        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st));
+    }
+    const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
+    const uint64_t M = f.plan.M, child_base = l1 ? 0 : base + n;
+    const uint64_t slice = level_slice(M, child_base, n, d, f.R);
+    if (slice == 0) return fail(RR_ERR_OUT_OF_MEMORY, "ray arena of %llu rays is too small for depth level %u", (unsigned long long)M, d);
+    if (slice < n) s->timing.stats.sliced_levels++;
+    for (uint64_t s0 = 0; s0 < n; s0 += slice) {
+        const uint64_t s1 = std::min<uint64_t>(s0 + slice, n);
+        uint32_t* child_count = f.pool.take(1);
+        if (!child_count) return counters_exhausted();
+        const DRayQueue qout = f.queue_at(child_base);
+        // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams
+        const bool staged = level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
+                            s->data.view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, s1 - s0).overlapped();
+        if (staged) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns));
+        for (uint64_t c0 = s0; c0 < s1 && !staged; c0 += f.plan.chunk) {
+            if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+            const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
+            const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);
+            // level 1: shadow slots of this chunk = L x (the chunk padded to whole workgroup iterations), one validity word per 64
+            // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
+            // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
+            // take the dense queue of the deeper levels, which has no such limit
+            const bool sq_fixed = l1 && s->data.view.n_items >= RR_BEAM_MIN_ITEMS && s->data.view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
+            const uint32_t sq_chunk_cap = sq_fixed ? (uint32_t)(((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK) * RR_BLOCK) : 0u;
+            unsigned long long* sq_valid = s->frame.sq_valid.as<unsigned long long>();
+            // deeper levels: shadow sub-queues, a shard gets the packets with (packet % RR_SQ_SHARDS == shard), L rays per hit at most
+            const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK; // 256-ray groups, dealt round-robin to the shards
+            const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * std::max(L, 1u));
+            f.pool.align_line(); // the append counters start on a 128-B line
+            uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
+            uint32_t* shead = f.pool.take(1);
+            if (!sq_counts || !shead) return counters_exhausted();
+            {
+                ScopedTimer t(s, st, TK_SHADE, l1);
+                if (l1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
+                                               (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+                else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
+                                        (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
+            }
+            // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
+            // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
+            // rays are still being traced, instead of leaving the device idle for a host round trip per level.
+            if (spawns && c1 == s1) {
+                HIP_TRY(hipMemcpyAsync(s->frame.h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(s->frame.count_ready, st));
+            }
+            if (L) {
+                ScopedTimer t(s, st, TK_SHADOW, sq_fixed); // (by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
+                if (sq_fixed) {
+                    const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
+                    const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
+                    hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->data.view, f.SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
+                } else {
+                    const uint64_t sq_ub = (c1 - c0) * L;
+                    const int sgrid = (int)std::min<uint64_t>((sq_ub + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
+                    hipLaunchKernelGGL(k_trace_shadow<false>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->data.view, f.SQ, sq_counts, segcap, sq_valid, 0u, shead, f.acc);
+                }
+            }
+        }
+        if (!spawns) continue;
+        HIP_TRY(hipEventSynchronize(s->frame.count_ready));
+        const uint64_t m = *s->frame.h_count;
+        if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
+        if (m == 0) continue;
+        uint64_t level_base = child_base;
+        RR_TRY(bin_level(f, child_base, m, &level_base));
+        RR_TRY(run_level(f, d + 1, level_base, m, child_count));
+    }
+    return RR_OK;
+}
+
+static void launch_resolve(const FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout) {
+    const uint32_t npix = fr.n_region_pixels;
+    hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(),
+                       f.acc, out->rgba8, out->normal, out->depth, out->object_id, frame_layout ? 1u : 0u);
+}
+
+// The frame's batches of primary rays, in order.  After a batch that ends on a whole slice of samples the pass hook
+// (if any) gets the frame resolved over the samples finished so far.
+static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout, const PassHook* hook) {
+    rr_scene* s = f.s;
+    const uint32_t npix = fr.n_region_pixels;
+    const uint64_t B = f.plan.B, total_primary = f.plan.total_primary;
+    for (uint64_t first = 0; first < total_primary; first += B) {
+        if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+        const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
+        RR_TRY(f.pool.start_batch());
+        uint32_t* level1_count = f.pool.take(1);
+        // The batch covers primary indices [first, first + n_batch): index i -> sample i / npix, pixel i % npix.
+        f.pr.at = primary_launch(first, npix, batch_group(f.plan, npix, first, n_batch)); f.pr.n = n_batch;
+        s->timing.stats.batches++;
+        RR_TRY(run_level(f, 1, 0, n_batch, level1_count));
+        HIP_TRY(hipGetLastError());
+        // batches are stream-ordered; only a caller that can cancel needs the host to keep pace with the device
+        if (f.cancel && first + B < total_primary) HIP_TRY(hipStreamSynchronize(f.st));
+        const uint64_t done = first + n_batch;
+        if (hook && hook->fn && done < total_primary && done % npix == 0) {
+            DFrame pf = fr;
+            pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
+            launch_resolve(f, pf, out, frame_layout);
+            RR_TRY(copy_outputs(*hook->host, *out, (size_t)fr.width * fr.height, f.st));
+            InPass in_pass(s);
+            if (hook->fn(hook->user, done, total_primary) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
+        }
+    }
+    return RR_OK;
+}
+
+// The handle's frame and query buffers are shared: frames and queries on different streams are serialised.
+static int take_stream(rr_scene* s, hipStream_t st) {
+    if (st != s->frame.last_stream) { HIP_TRY(hipStreamSynchronize(s->frame.last_stream)); s->frame.last_stream = st; }
+    return RR_OK;
+}
+// a frame's (or a radiance query's) statistics start from nothing
+static void begin_frame_stats(rr_scene* s) {
+    resolve_timers(s); // launches of an earlier frame nobody asked about must not leak into this frame's stats
+    memset(&s->timing.stats, 0, sizeof s->timing.stats);
+    s->timing.stats_final = false;
+    s->frame.overlap_stages = 0;
+}
+
+static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                                const rr_region* rg, const rr_frame* out, bool frame_layout, hipStream_t st, const volatile int* cancel,
+                                const PassHook* hook = nullptr) {
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_TRY(take_stream(s, st));
+    const uint32_t W = cam->width, H = cam->height;
+    if ((uint64_t)W * H > (1ull << 30)) return fail(RR_ERR_UNSUPPORTED, "frame of %ux%u pixels", W, H);
+    RR_TRY(update_region_map(s, W, H, *rg, st));
+    const uint32_t npix = (uint32_t)s->frame.h_region_xy.size();
+    begin_frame_stats(s);
+    if (npix == 0) return RR_OK;
+    RR_TRY(ensure_camera_reach(s, cam, cfg)); // the top level's boxes must be padded for this camera's distance from the origin
+    DFrame fr = make_frame(cam, cfg);
+    fr.n_region_pixels = npix;
+    RR_TRY(upload_sample_table(s, fr, sample_xy, st));
+    DAccum acc;
+    RR_TRY(reset_accumulators(s, npix, out->normal != nullptr, out->depth != nullptr, out->object_id != nullptr, st, &acc));
+    FramePlan plan;
+    RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
+    RR_TRY(upload_shade_const(s, fr, primary_frame(s->frame.slot_c.as<float>(), npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
+    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
+               CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u}, cancel,
+               s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
+               s->n_cus * RR_SHADE_GRID_WG};
+    f.slot_xy = s->frame.region_xy.as<uint32_t>();
+    HIP_TRY(hipEventRecord(s->timing.frame_a, st));
+    RR_TRY(run_batches(f, fr, out, frame_layout, hook));
+    launch_resolve(f, fr, out, frame_layout);
+    HIP_TRY(hipEventRecord(s->timing.frame_b, st));
+    HIP_TRY(hipGetLastError());
+    // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)
+    if (s->timing.stats.sliced_levels > 0 && s->frame.arena_factor < 128) s->frame.arena_factor *= 2;
+    return RR_OK;
+}
+
+extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                                       const rr_region* rg, const rr_frame* out, void* hip_stream, const volatile int* cancel) try {
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
+    RR_TRY(check_region(cam->width, cam->height, rg));
+    if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, "rr_render_region_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    return render_region_locked(s, cam, cfg, sample_xy, rg, out, false, (hipStream_t)hip_stream, cancel);
+} RR_GUARD_END("rr_render_region_device")
+
+static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
+                          const volatile int* cancel, rr_pass_fn fn, void* user, uint32_t min_passes) {
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
+    if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, fn ? "rr_render_progressive" : "rr_render"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t np = (size_t)cam->width * cam->height;
+    rr_frame dev{};
+    RR_TRY(stage_outputs(s, *out, np, false, &dev));
+    rr_region whole{8, 8, 1, 0}; // 8x8 tiles: one wave = one tile of primary rays
+    PassHook hook{fn, user, min_passes, out};
+    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &whole, &dev, true, nullptr, cancel, fn ? &hook : nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_outputs(*out, dev, np, nullptr);
+}
+
+extern "C" int rr_render(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
+                         const volatile int* cancel) try {
+    return render_to_host(s, cam, cfg, sample_xy, out, cancel, nullptr, nullptr, 0);
+} RR_GUARD_END("rr_render")
+
+extern "C" int rr_render_progressive(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
+                                     uint32_t min_passes, rr_pass_fn on_pass, void* user, const volatile int* cancel) try {
+    if (!on_pass) return fail(RR_ERR_INVALID_ARGUMENT, "on_pass is required (use rr_render for a one-shot frame)");
+    return render_to_host(s, cam, cfg, sample_xy, out, cancel, on_pass, user, min_passes);
+} RR_GUARD_END("rr_render_progressive")
+
+// the device's work counters of the frame (or pass) that ran last, or of the batches so far inside on_pass
+static int read_counters(const rr_scene* s, rr_frame_stats* st) {
+    unsigned long long c[RR_CNT_WORDS];
+    HIP_TRY(hipMemcpy(c, s->frame.counters.p, sizeof c, hipMemcpyDeviceToHost));
+    st->primary_rays = c[RR_CNT_PRIMARY]; st->secondary_rays = c[RR_CNT_SECONDARY];
+    st->shadow_rays = c[RR_CNT_SHADOW]; st->shaded_hits = c[RR_CNT_SHADED];
+    return RR_OK;
+}
+// the device counters and launch timers of the frame (or pass) that ran last, into s->timing.stats
+static int collect_stats_locked(rr_scene* s) {
+    float ms = 0.0f;
+    if (hipEventSynchronize(s->timing.frame_b) == hipSuccess && hipEventElapsedTime(&ms, s->timing.frame_a, s->timing.frame_b) == hipSuccess) s->timing.stats.ms_total = ms;
+    resolve_timers(s);
+    return read_counters(s, &s->timing.stats);
+}
+extern "C" int rr_scene_overlap_stages(const rr_scene* cs, uint32_t* out) try {
+    if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = cs->frame.overlap_stages;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_overlap_stages")
+
+extern "C" int rr_scene_last_stats(const rr_scene* cs, rr_frame_stats* out) try {
+    if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (tl_in_pass == cs) { // inside on_pass of this scene: its frame holds s->mu on this thread and the stream is idle -- the passes so far
+        rr_frame_stats st = cs->timing.stats;
+        if (!cs->timing.stats_final) RR_TRY(read_counters(cs, &st));
+        *out = st;
+        return RR_OK;
+    }
+    rr_scene* s = const_cast<rr_scene*>(cs);
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->timing.stats_final) { const int rc = collect_stats_locked(s); if (rc != RR_OK) return rc; }
+    *out = s->timing.stats;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_last_stats")
+
+// The frame filled in TILE BY TILE, every pixel final when it appears: what the reference's GUI shows (shuffled 2x2 cells, each rendered with all of
+// its samples: src/renderer.rs:125-172, drained by Run::apply_pixels, src/run.rs:506-545).  Pass k of n_passes renders the 32x8-pixel tiles with
+// tile_index % n_passes == k -- an interleaved subset, like the shuffled cell list -- straight into their places in the frame.
+extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
+                                           uint32_t n_passes, rr_pass_fn on_pass, void* user, const volatile int* cancel) try {
+    if (!on_pass) return fail(RR_ERR_INVALID_ARGUMENT, "on_pass is required (use rr_render for a one-shot frame)");
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
+    if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
+    RR_TRY(not_in_pass(s, "rr_render_progressive_tiles"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t W = cam->width, H = cam->height, TW = 32, TH = 8;
+    const size_t np = (size_t)W * H;
+    for (int k = 0; k < 4; k++) // pixels not rendered yet are zero, also when the frame stops before its first pass
+        if (out_buffer(*out, k)) memset(out_buffer(*out, k), 0, np * OUT_ELEM[k]);
+    rr_frame dev{};
+    RR_TRY(stage_outputs(s, *out, np, true, &dev));
+    const uint32_t n_tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+    const uint32_t P = std::max(1u, std::min(n_passes ? n_passes : 16u, n_tiles));
+    rr_frame_stats sum{};
+    uint64_t done = 0;
+    for (uint32_t k = 0; k < P; k++) {
+        if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        const rr_region rg{TW, TH, P, k};
+        RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, true, nullptr, cancel));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        RR_TRY(collect_stats_locked(s));
+        {   // the frame's statistics are the sums over its passes
+            const rr_frame_stats& a = s->timing.stats;
+            sum.primary_rays += a.primary_rays; sum.secondary_rays += a.secondary_rays; sum.shadow_rays += a.shadow_rays; sum.shaded_hits += a.shaded_hits;
+            sum.ms_total += a.ms_total; sum.ms_trace_closest += a.ms_trace_closest; sum.ms_trace_shadow += a.ms_trace_shadow; sum.ms_shade += a.ms_shade;
+            sum.launches_trace_closest += a.launches_trace_closest; sum.launches_trace_shadow += a.launches_trace_shadow; sum.launches_shade += a.launches_shade;
+            sum.batches += a.batches; sum.sliced_levels += a.sliced_levels; sum.binned_rays += a.binned_rays; sum.ms_binning += a.ms_binning;
+            sum.ms_trace_closest_level1 += a.ms_trace_closest_level1; sum.launches_trace_closest_level1 += a.launches_trace_closest_level1;
+            sum.ms_shade_level1 += a.ms_shade_level1; sum.launches_shade_level1 += a.launches_shade_level1;
+            sum.ms_trace_shadow_level1 += a.ms_trace_shadow_level1; sum.launches_trace_shadow_level1 += a.launches_trace_shadow_level1;
+        }
+        RR_TRY(copy_outputs(*out, dev, np, nullptr));
+        done += rr_region_pixel_count(W, H, &rg);
+        s->timing.stats = sum; s->timing.stats_final = true;
+        if (k + 1 < P) {
+            InPass in_pass(s);
+            if (on_pass(user, done * cfg->samples, (uint64_t)np * cfg->samples) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
+        }
+    }
+    return RR_OK;
+} RR_GUARD_END("rr_render_progressive_tiles")
+
+extern "C" int rr_scene_set_compat(rr_scene* s, uint32_t flags) try {
+    if (!s) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (flags & ~RR_COMPAT_OCCLUDER_ALPHA_SHADOWS) return fail(RR_ERR_INVALID_ARGUMENT, "unknown compatibility flags 0x%x", flags);
+    RR_TRY(not_in_pass(s, "rr_scene_set_compat"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->data.view.compat = (s->data.view.compat & RR_VIEW_NAN_BALLS) | flags; // the scene view is passed to the kernels by value with every launch
+    return RR_OK;
+} RR_GUARD_END("rr_scene_set_compat")
+
+extern "C" int rr_scene_set_tuning(rr_scene* s, const rr_tuning* t) try {
+    if (!s || !t) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (t->struct_size != sizeof(rr_tuning)) return fail(RR_ERR_INVALID_ARGUMENT, "rr_tuning::struct_size %u, library expects %zu", t->struct_size, sizeof(rr_tuning));
+    if (t->sample_group > 64u || (t->sample_group & (t->sample_group - 1u))) return fail(RR_ERR_INVALID_ARGUMENT, "sample_group %u is not 0 or a power of two <= 64", t->sample_group);
+    RR_TRY(not_in_pass(s, "rr_scene_set_tuning"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->tuning = *t;
+    s->timing.profiling = t->kernel_timing != 0;
+    return RR_OK;
+} RR_GUARD_END("rr_scene_set_tuning")
+extern "C" int rr_scene_get_tuning(const rr_scene* s, rr_tuning* t) try {
+    if (!s || !t) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *t = s->tuning;
+    t->struct_size = (uint32_t)sizeof(rr_tuning);
+    return RR_OK;
+} RR_GUARD_END("rr_scene_get_tuning")
+

@@ -1,0 +1,169 @@
+// rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, MultiState, FrameTiming
+//         and rr_scene, which holds one of each; check_intact.
+// Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
+// A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
+
+enum TimerKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_BINNING }; // what a timed launch ran (resolve_timers)
+struct TimedLaunch { hipEvent_t a, b; TimerKernel kernel; bool level1; }; // level1: the kernel's level-1 build
+
+static const uint32_t POOL_WORDS = 1u << 22; // per-batch counters (level sizes, fetch heads, shadow shard counts): 16 MB, zeroed per batch
+// bytes per ray of the four record arrays r0, r1, r2, hit (DRayQueue): the frames' arena and the queries' records
+static const size_t RAY_RECORD_BYTES[4] = {16, 16, 8, 16};
+
+// ---- scene data: what the kernels read through the view, and the host copies the edits and queries work from.  Written by rr_api_scene.h.
+struct SceneData {
+    DevBuf items, nodes4, tnodes4, tris, trix, attrs, face_slot, materials, textures, texels, lights, flat_normals;
+    DSceneView view{}; // its pointers and counts are set by point_view (rr_api_scene.h) after every move of a buffer above, and nowhere else
+    std::vector<DItem> h_items;
+    std::vector<ItemHost> item_host; // what rr_scene_update_materials needs to rebuild the item flag words
+    // the meshes: where each one's records sit in the arenas (what an item takes from the mesh it names, rr_scene_set_items), how many
+    // records the arenas hold (rr_scene_add_meshes appends behind them), the scene's own copy of the caller's arrays (the trees are
+    // rebuilt from it when an edit of the item list changes their share of the traversal stack) and that share
+    std::vector<MeshDev> mesh_table;
+    std::vector<HostMesh> h_meshes;
+    size_t n_nodes4 = 0, n_mesh_tris = 0;
+    int blas_depth_limit = RR_BLAS_MAX_DEPTH;
+    // per item: the extent of its surface along the rows of its transform (k_item_spans: minima, maxima, largest |local coordinate|; 9 doubles),
+    // read back after every upload of the items' transforms; the top level's surface boxes are derived from it (exact_world_box)
+    std::vector<double> h_spans;
+    DevBuf spans, item_chunks;              // item_chunks: (item, first triangle) per workgroup of k_world_normals / k_item_spans (RR_ITEM_CHUNK triangles each)
+    std::vector<uint32_t> h_chunk_item;     // the item of every chunk (chunks of one item are consecutive)
+    std::vector<uint32_t> tex_width;
+    std::vector<DTexture> h_textures; // descriptors of the uploaded images (copied into the material records, make_dmaterial)
+    uint32_t n_materials = 0;
+    uint32_t n_enabled_lights = 0;
+    DevBuf item_boxes; // the top level's padded world boxes per item on the device (view.item_boxes); the trees themselves: tnodes4
+    std::vector<DMaterial> h_dmat; // the material records on the device (rr_scene_update_materials puts them back after a failed update)
+    std::vector<DLight> h_lights;  // the light records on the device (rr_scene_update_lights puts them back after a failed update)
+};
+
+// ---- the top level's host state (its device records are SceneData::tnodes4 and item_boxes).  Written by rr_api_scene.h.
+struct TopLevel {
+    uint32_t node_capacity = 0; // nodes per tree in SceneData::tnodes4: the corner tree in its first half, the surface tree in the second
+    bool has_surface = false;   // the closest-hit walks take the surface tree (point_view: view.tnodes4c)
+    std::vector<float4> h_item_boxes; // padded world boxes per item (lo, hi), built by build_tlas, kept by upload_tlas
+    double reach[3] = {0.0, 0.0, 0.0}; // the top level's boxes are padded for ray origins within +-reach (build_tlas)
+    double floor[3] = {0.0, 0.0, 0.0}; // ... and never for less than this: the items' own extent
+    bool stale = false; // a top-level upload failed part-way: the device trees match no reach, the next frame rebuilds them
+    int depth_limit = RR_TLAS_MAX_DEPTH; // the top level's share of the traversal stack (build_scene_records), for its rebuilds
+};
+
+// ---- frame state (grown on demand, reused across frames).  Written by rr_api_frame.h; the ray queries (rr_api_query.h) borrow h_count and
+// last_stream, and rr_shade_rays the arena, the shadow queue, the accumulators and the counter pool (why that is safe: next to its body).
+struct FrameState {
+    DevBuf hit1;      // hit records of depth level 1 (the primary rays are derived from their index, not stored)
+    DevBuf arena[4];  // ray records of the deeper live depth levels, SoA: r0 r1 r2 hit (RAY_RECORD_BYTES each)
+    size_t arena_cap = 0; // rays
+    uint32_t arena_factor = 2; // arena rays per primary ray of a batch; doubled after a frame that had to slice levels
+    DevBuf sq[3];
+    size_t sq_cap = 0;
+    DevBuf sq_valid; // one 64-bit word per (enabled light, 64 shadow slots): which lanes hold a ray
+    DevBuf acc_rgb, acc_normal, acc_depth, acc_id, acc_flags, shade_const;
+    DevBuf region_xy, trace_order, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
+    // what primary_ray reads (rr_primary_setup.h): slot_c, the screen point of each slot's pixel centre, lives and dies with region_xy;
+    // sample_tr, the screen offset of each sample, is uploaded when the sub-sample table or one of the frame constants in tr_key changes
+    DevBuf slot_c, sample_tr;
+    std::vector<uint16_t> tr_table; PrimarySampleKey tr_key{}; bool tr_valid = false;
+    std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
+    DevBuf tmp_out[4];
+    std::vector<uint32_t> h_region_xy;
+    rr_region region_cached{0, 0, 0, 0};
+    uint32_t region_w = 0, region_h = 0;
+    hipEvent_t count_ready = nullptr;
+    hipStream_t last_stream = nullptr; // frame state (queues, accumulators) is shared: frames on different streams are serialised
+    // level 1 in stages (run_level1_stages): this handle's second non-blocking stream, created on first use on the handle's device, and per
+    // shadow-queue buffer the event behind its shade launch (first stream) and behind its shadow launch (second stream)
+    hipStream_t overlap_stream = nullptr;
+    hipEvent_t stage_shaded[3] = {nullptr, nullptr, nullptr}, stage_traced[3] = {nullptr, nullptr, nullptr};
+    uint32_t overlap_stages = 0; // level-1 stages of the last frame that ran on the two streams (rr_scene_overlap_stages)
+    uint32_t* h_count = nullptr; // pinned: level sizes read back between depth levels
+    std::vector<uint16_t> table_cache; uint16_t table_samples = 0; // built-in sub-sample table of the last sample count
+    // what every frame needs from the start (rr_scene_create, on the scene's device)
+    int init() {
+        HIP_TRY(pool.reserve(POOL_WORDS * 4));
+        HIP_TRY(counters.reserve(RR_CNT_WORDS * 8));
+        HIP_TRY(hipEventCreateWithFlags(&count_ready, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc((void**)&h_count, 64, hipHostMallocDefault));
+        return RR_OK;
+    }
+    ~FrameState() {
+        if (count_ready) (void)hipEventDestroy(count_ready);
+        if (h_count) (void)hipHostFree(h_count);
+        for (hipEvent_t e : stage_shaded) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : stage_traced) if (e) (void)hipEventDestroy(e);
+        if (overlap_stream) (void)hipStreamDestroy(overlap_stream);
+    }
+};
+
+// ---- ray queries (the host forms are the device forms behind a staging copy): what the launches of a device form read and write after the
+// call has returned belongs to the handle, grows on demand and is never shrunk.  rec: the packed records r0, r1, r2 and the walks'
+// raw hits (RAY_RECORD_BYTES: 16 + 16 + 8 + 16 = 56 B per ray of the largest closest-hit or shadow query, host or device form; a shadow
+// query uses 48 of them); words: QW_* (rr_api_query.h); ids: the stream ids 0 .. n - 1 of rr_shade_rays_device without the caller's
+// (4 B per result).  Written by rr_api_query.h.
+struct QueryState {
+    DevBuf rec[4], words, ids;
+};
+
+// ---- rr_render_multi (rr_api_multi.h)
+struct MultiState {
+    DevBuf part[4], cat[4]; // this device's compact buffers; on device slot 0 the concatenation of all
+    hipStream_t stream = nullptr; // this handle's own non-blocking stream (created on first use)
+    void* stage[4] = {nullptr, nullptr, nullptr, nullptr}; size_t stage_bytes[4] = {0, 0, 0, 0}; // pinned staging, devices without peer access
+    ~MultiState() {
+        if (stream) (void)hipStreamDestroy(stream);
+        for (void* p : stage) if (p) (void)hipHostFree(p);
+    }
+};
+
+// ---- what a frame cost: written by rr_api_frame.h; rr_render_multi adds its multi_* fields and rr_shade_rays counts its batches in `stats`
+struct FrameTiming {
+    rr_frame_stats stats{};
+    bool stats_final = false; // stats already holds the sums over the passes of rr_render_progressive_tiles (nothing to collect from the device)
+    bool profiling = false;
+    std::vector<TimedLaunch> timed;
+    std::vector<hipEvent_t> event_pool;
+    hipEvent_t frame_a = nullptr, frame_b = nullptr;
+    int init() {
+        HIP_TRY(hipEventCreate(&frame_a));
+        HIP_TRY(hipEventCreate(&frame_b));
+        return RR_OK;
+    }
+    ~FrameTiming() {
+        for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+        for (auto& t : timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+        if (frame_a) (void)hipEventDestroy(frame_a);
+        if (frame_b) (void)hipEventDestroy(frame_b);
+    }
+};
+
+struct rr_scene {
+    int device = 0;
+    int n_cus = 256;
+    std::mutex mu;
+    rr_tuning tuning{}; // rr_scene_set_tuning; all zero = automatic
+    // An update that failed and could not be rolled back either (all_or_nothing): the device holds a mix of two scenes, and every
+    // frame call refuses until an update of that kind succeeds.  geometry: items, flat normals, top level; materials: materials, item flags.
+    // lights: the light records; item_flags: the items' records after a failed rr_scene_update_item_flags.
+    bool broken_geometry = false, broken_materials = false, broken_lights = false, broken_item_flags = false;
+    // one part per layer; each is written by its layer's file only (the exceptions are named at the part) and releases what it owns
+    SceneData data;
+    TopLevel tlas;
+    FrameState frame;
+    QueryState query;
+    MultiState multi;
+    FrameTiming timing;
+    // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's
+    // device.  A destructor's body runs before its class's members are destroyed, whatever their order of declaration: the
+    // hipSetDevice here precedes every one of them, and `device` is a plain int that stays readable throughout.
+    ~rr_scene() { (void)hipSetDevice(device); }
+};
+
+// every frame call on a scene: a scene that a failed update left mixed is not rendered
+static int check_intact(const rr_scene* s) {
+    if (s->broken_geometry || s->broken_materials || s->broken_lights || s->broken_item_flags)
+        return fail(RR_ERR_DEVICE, "the scene is broken: a failed %s update could not be rolled back (update again, or create the scene anew)",
+                    s->broken_geometry ? "transform" : s->broken_materials ? "material" : s->broken_lights ? "light" : "item flag");
+    return RR_OK;
+}
+

@@ -1,5 +1,5 @@
 // rr_device.h — HBM-resident data layout of a scene and of the ray queues.
-// Shared by the host uploader (rr_api.cpp / rr_bvh.cpp) and the kernels.
+// Shared by the host uploader (rr_api.hip and its layer files, rr_bvh.cpp) and the kernels.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -47,7 +47,7 @@ struct DNode4 { float4 q[8]; };
 //   v0 = (a.xyz, bits(original face index)), v1 = (b.xyz, area), v2 = (c.xyz, 0), v3 = (flat normal.xyz, 0)
 // area = |cross(a - b, a - c)| (Mesh::get_normal / get_uv divide their weights by it, src/shape/mesh.rs:127-143) and the flat normal
 // normalize(cross(b - a, c - a)) (parry's triangle normal, mesh.rs:76-98) are the same IEEE values for every hit of the triangle:
-// the host evaluates them once, with the sequence k_shade used per hit (rr_api.hip tri_shading_constants; a flat, untextured hit
+// the host evaluates them once, with the sequence k_shade used per hit (rr_scene_build.h tri_shading_constants; a flat, untextured hit
 // then reads v3 alone).
 struct DTri { float4 v0, v1, v2, v3; };
 
@@ -142,10 +142,10 @@ struct DSceneView {
     uint32_t n_enabled_lights; // any number; level 1 uses fixed shadow slots for up to RR_FIXED_SLOT_LIGHTS of them
     const DNode4* tnodes4;  // the top level over item world boxes, same form (one item per leaf)
     int32_t tlas_root4;      // node index, a leaf code (one item), or RR_SENTINEL (empty scene)
-    const DNode4* tnodes4c;  // the top level of the per-ray CLOSEST-HIT walks: over the items' surface boxes where those are tighter (rr_api.hip build_tlas),
+    const DNode4* tnodes4c;  // the top level of the per-ray CLOSEST-HIT walks: over the items' surface boxes where those are tighter (rr_scene_build.h build_tlas; which one: rr_api_scene.h point_view),
     int32_t tlas_root4c;     // else the same tree as tnodes4 / tlas_root4 (which shadow queries always take)
     const float4* item_boxes; // padded world boxes per item for the packet form of the top level: [2 i] = lo, [2 i + 1] = hi of the item's corner box (the boxes of
-                              // the tree; trace_shadow_packet), [2 (n_items + i)], [.. + 1] of its surface box (trace_closest_packet); rr_api.hip build_tlas
+                              // the tree; trace_shadow_packet), [2 (n_items + i)], [.. + 1] of its surface box (trace_closest_packet); rr_scene_build.h build_tlas
     uint32_t any_alpha_occluder; // some item's material has an alpha map: the shadow attenuation of a receiver whose uv may be NaN can be NaN (k_shade, want_shadow)
     uint32_t general_w;      // some trans_inv has a w row other than (0,0,0,1)
     uint32_t compat;         // RR_COMPAT_* (rr_scene_set_compat): behaviours of earlier reference binaries; 0 = the source at HEAD.

@@ -1,5 +1,5 @@
 // rr_frame_plan.h — how a frame is cut into device batches and how its ray memory is sized: plain host arithmetic,
-// no HIP calls (rr_api.hip render_region_locked runs it; tests/native/frame_plan_test.cpp checks it on the CPU).
+// no HIP calls (rr_api_frame.h render_region_locked runs it; tests/native/frame_plan_test.cpp checks it on the CPU).
 //
 // All live depth levels of a batch sit in ONE arena of ray records (56 B each), level d + 1 stacked behind level d.
 // A level of n rays spawns at most 2 n children; if they fit behind it the level is shaded in one go, otherwise in
@@ -17,7 +17,7 @@ struct FramePlanInputs {
     uint32_t npix;             // accumulator slots of the region (>= 1)
     uint32_t samples;          // per pixel (>= 1)
     uint32_t max_recursion;    // R
-    uint64_t queue_budget;     // bytes for level 1's hit records and the arena (rr_api.hip queue_budget)
+    uint64_t queue_budget;     // bytes for level 1's hit records and the arena (rr_api_frame.h queue_budget)
     uint32_t sample_group;     // rr_tuning::sample_group: 0 = automatic
     uint32_t min_passes;       // progressive passes asked for; 0 without a pass hook
     uint32_t arena_factor;     // arena rays per primary ray after a frame that had to slice levels
@@ -85,7 +85,7 @@ inline FramePlan plan_frame(const FramePlanInputs& in) {
     return FramePlan{total_primary, B, G, M, chunk, sq_need};
 }
 
-// ---- caller-supplied rays (rr_api.hip rr_shade_rays) ----------------------------------------------------------------------
+// ---- caller-supplied rays (rr_api_query.h rr_shade_rays) ----------------------------------------------------------------------
 // The rays of such a call are depth level 1 as RECORDS: a batch of B rays sits at the front of the arena (56 B each, where a
 // frame keeps 16-B hit records only), its children behind it.  2 arena rays per ray for the children, as plan_frame allows per
 // primary ray, plus the slack every spawning level needs to make progress; level_slice covers a scene that branches more.
@@ -107,7 +107,7 @@ inline FramePlan plan_ray_batches(uint64_t n_rays, uint32_t max_recursion, uint6
     return FramePlan{n_rays, B, 1u, M, chunk, sq_need};
 }
 
-// ---- level 1 in stages (rr_api.hip run_level, the two-stream path) -------------------------------------------------------
+// ---- level 1 in stages (rr_api_frame.h run_level, the two-stream path) -------------------------------------------------------
 // Level 1 of a scene with fixed shadow slots may be cut into STAGES of hits: k_shade<true> of stage k + 1 then runs on one
 // stream while k_trace_shadow<true> of stage k runs on a second one.  Stage k writes its shadow rays into buffer
 // k % n_buf of the shadow-queue allocation, so a buffer is rewritten only after the shadow launch that read it.

@@ -42,14 +42,14 @@
 #ifndef RR_SHADE_WAVES
 #define RR_SHADE_WAVES 4 // waves per SIMD k_shade is built for
 #endif
-// Launch sizes (host side, rr_api.hip): workgroups per CU of a k_shade and of a k_trace_shadow launch that has the GPU to itself.
+// Launch sizes (host side, rr_api_frame.h): workgroups per CU of a k_shade and of a k_trace_shadow launch that has the GPU to itself.
 #ifndef RR_SHADE_GRID_WG
 #define RR_SHADE_GRID_WG (2 * RR_SHADE_WAVES) // two rounds of resident workgroups
 #endif
 #ifndef RR_SHADOW_GRID_WG
 #define RR_SHADOW_GRID_WG RR_SHADOW_WAVES // exactly the resident workgroups (RR_STACK_DEPTH KB of LDS stack each)
 #endif
-// Level 1 in stages on two streams (rr_api.hip run_level1_stages, rr_frame_plan.h plan_level1_stages): k_shade<true> of stage
+// Level 1 in stages on two streams (rr_api_frame.h run_level1_stages, rr_frame_plan.h plan_level1_stages): k_shade<true> of stage
 // k + 1 beside k_trace_shadow<true> of stage k.  All numbers: the contract frame (sponza_syn 1280x720 128 spp), serial loop
 // 19.2 ms on the same box (profiles/r05_level1_share_rates.txt, profiles/r05_dropped.txt, profiles/r05_ab_level1_overlap.txt).
 //   0 = never in stages; 1 = only where the caller asks for shade chunks (rr_tuning::shade_chunk_rays != 0: a stage is that
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_world_normals_edit(const DItem* __
     }
 }
 
-// The extent of every mesh item's SURFACE along the rows of its transform (rr_api.hip: exact_world_box): one workgroup per item over
+// The extent of every mesh item's SURFACE along the rows of its transform (rr_scene_build.h: exact_world_box): one workgroup per item over
 // the vertices of the mesh's triangles, which are resident (DTri), in double -- per row r the minimum and maximum of
 // tr_r.x * p.x + tr_r.y * p.y + tr_r.z * p.z, and the largest |coordinate| per local axis.  Products and sums are IEEE binary64
 // without contraction and minimum / maximum are exact, so the host evaluation this replaces (one thread, every vertex of every
@@ -1371,7 +1371,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_post_process(uint32_t width, uint3
 // ---------------------------------------------------------------------------
 // kernel 8: device self-test of the arithmetic contract (tests/test_device_math.py)
 // op: 0 sincos -> (sin, cos); 1 acos; 2 atan2(a, b); 3 a / b; 4 sqrt(a); 5 jitter(dir = (a, b, c)); 7 cos(a * pi) as jitter() needs it
-// (op 6 is the HOST build of the same rr_cos, rr_api.hip)
+// (op 6 is the HOST build of the same rr_cos, rr_api_probe.h rr_math_probe)
 // ---------------------------------------------------------------------------
 __global__ void k_math_probe(int op, const float* a, const float* b, const float* c, int n, float* out0, float* out1, float* out2,
                              uint32_t seed_lo, uint32_t seed_hi) {

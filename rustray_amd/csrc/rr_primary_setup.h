@@ -1,6 +1,6 @@
 // rr_primary_setup.h — what the derivation of a primary ray (rr_kernels.hip primary_ray) does NOT owe to the ray: the parts
 // that are constant for the frame, the sample, the pixel or the launch, evaluated once on the host.  Plain host arithmetic,
-// no HIP calls (rr_api.hip builds the tables and records; tests/native/primary_setup_test.cpp checks them on the CPU against
+// no HIP calls (rr_api_frame.h builds the tables and records; tests/native/primary_setup_test.cpp checks them on the CPU against
 // the per-ray formula they replace).  The kernels read the records declared here and evaluate rr_div_* on the device.
 //
 // Every float below is the IEEE binary32 expression the per-ray code evaluated, in its order, and must be compiled without

@@ -1,5 +1,5 @@
 // rr_query_pointers.h — may the kernels of a scene's device read or write a buffer the caller handed to a device-buffer ray query
-// (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device)?  Plain host logic, no HIP calls: rr_api.hip classifies the
+// (rr_trace_rays_device, rr_trace_shadow_rays_device, rr_shade_rays_device)?  Plain host logic, no HIP calls: rr_api_query.h classifies the
 // pointer (hipPointerGetAttributes) and looks up the peer state, this header decides; tests/native/query_pointer_test.cpp checks the
 // whole table on the CPU.  A pointer that fails here never reaches a launch: the call returns RR_ERR_INVALID_ARGUMENT naming the argument.
 #pragma once

@@ -1,9 +1,9 @@
 // rr_scene_build.h — everything a scene's device records are made of before the first upload: the checks of the caller's arrays,
 // the record makers, the per-mesh trees and the top level over the items' world boxes.  Plain host arithmetic, no HIP runtime
-// calls (rr_api.hip uploads what this builds; tests/native/scene_build_test.cpp checks it on the CPU).
+// calls (rr_api_scene.h uploads what this builds; tests/native/scene_build_test.cpp checks it on the CPU).
 //
 // Errors go through the library's one channel: `fail` sets the calling thread's rr_last_error text and returns the code.  It is
-// defined by whoever includes this file (rr_api.hip; the native test).  RR_FAULT_POINT is rr_api.hip's test-only fault hook.
+// defined by whoever includes this file (rr_api_base.h; the native test).  RR_FAULT_POINT is rr_api_base.h's test-only fault hook.
 #pragma once
 #include "../../include/rustray_hip.h"
 #include "rr_bvh.h"
@@ -504,7 +504,7 @@ static void plan_item_reuse(const std::vector<DItem>& old_items, const std::vect
 
 // The chunk map of an item list: (item, first triangle) per workgroup of k_world_normals / k_item_spans, RR_HOST_ITEM_CHUNK triangles
 // each; every item has at least one chunk, and the chunks of one item are consecutive.
-#define RR_HOST_ITEM_CHUNK 8192u // = RR_ITEM_CHUNK of rr_kernels.hip (rr_api.hip asserts it)
+#define RR_HOST_ITEM_CHUNK 8192u // = RR_ITEM_CHUNK of rr_kernels.hip (rr_api_scene.h asserts it)
 static void item_chunk_map(const std::vector<DItem>& items, std::vector<uint2>* chunks, std::vector<uint32_t>* chunk_item) {
     chunks->clear(); chunk_item->clear();
     for (uint32_t i = 0; i < (uint32_t)items.size(); i++) {
@@ -673,7 +673,7 @@ static int tlas_tree(const std::vector<DItem>& items, int depth_limit, const flo
 // Builds the top-level trees over `items` for ray origins within +-want_reach (grown to cover the items themselves: the
 // origins of secondary and shadow rays lie on them).  `spans`: 9 doubles per item (exact_world_box), or empty = corner boxes only.
 // Writes nothing of a scene: the reach it was built for, the RR_VIEW_NAN_BALLS hint and the item boxes travel in TlasTrees, and
-// rr_api.hip's upload_tlas keeps them once the device has the trees.
+// rr_api_scene.h's upload_tlas keeps them once the device has the trees.
 struct TlasTrees {
     std::vector<DNode4> corner, surface; int32_t root = (int32_t)0x80000000, root_surface = (int32_t)0x80000000; bool has_surface = false;
     double reach[3] = {0.0, 0.0, 0.0}; bool nan_balls = false; std::vector<float4> item_boxes;

@@ -3,7 +3,7 @@
 // src/shape/sphere.rs:69-99), the jitter of a direction on the counter-based generator (src/raytracing.rs:565-626) and
 // fresnel (:535-563).
 //
-// Offers: c_u8_to_f32 (filled by rr_api.hip); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
+// Offers: c_u8_to_f32 (filled by rr_api_scene.h rr_scene_create); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
 // item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; SurfaceAt, surface_at.  No macros.
 // Needs: rr_primitives.h (to_local_point, inverse_ray, ray_ball, to_world_normal), rr_walk.h (rr_global), rr_trace.h (ray_nonfinite).
 #pragma once

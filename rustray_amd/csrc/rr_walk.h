@@ -3,7 +3,7 @@
 // (reference src/shape/mesh.rs:67) over parry's Qbvh; the box tests here are conservative filters, the hits are rr_primitives.h's.
 //
 // Offers: rr_global; Slab4, make_slab, make_slab4; TriBest, blas_closest<SCALAR_LEAVES>, blas_any, blas_closest_packet;
-// the instrumentation hooks RR_UTIL / RR_UTIL_KIND (empty unless -DRR_EXP_UTIL; g_util is read by rr_api.hip: rr_exp_util);
+// the instrumentation hooks RR_UTIL / RR_UTIL_KIND (empty unless -DRR_EXP_UTIL; g_util is read by rr_api_probe.h: rr_exp_util);
 // and, for the top-level walks of rr_trace.h, the step itself as macros: RR_NODE4_STEP, RR_NODE4_STEP_PLAIN, RR_NODE4_STEP_ANY
 // with STK and RR_SENTINEL.  A step macro expands where it is USED, so everything it is made of (RR_NODE4_FORM, RR_NODE4_ROWS_*,
 // RR_NODE4_TESTS, RR_NODE4_SINGLE_HIT, RR_NODE4_DESCEND_*, RR_ROW, RR_CHILD, RR_CSWAP, RR_UTIL_UNI, RR_UTIL_ONE, RR_UTIL_NODE_SLOT)

@@ -13,6 +13,29 @@ SCENES = os.path.join(ROOT, "scenes")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
+def host_api_source() -> str:
+    """The text of the library's host side: rustray_amd/csrc/rr_api.hip and every project header under csrc that its `#include "..."`
+    lines reach, each once, in include order -- without rr_kernels.hip and the headers the kernels are made of (what rr_kernels.hip
+    includes itself).  The tests that read the source text read it through here, so a layer file cannot drop out of their sight."""
+    import re
+    csrc = os.path.join(ROOT, "rustray_amd", "csrc")
+
+    def walk(name, seen, texts):
+        if name in seen or os.path.dirname(name) or not os.path.exists(os.path.join(csrc, name)):
+            return   # seen already, or outside csrc (../../include/rustray_hip.h)
+        seen.add(name)
+        with open(os.path.join(csrc, name)) as fh:
+            text = fh.read()
+        texts.append(text)
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', text, re.M):
+            walk(inc, seen, texts)
+
+    kernel_side, host = set(), []
+    walk("rr_kernels.hip", kernel_side, [])
+    walk("rr_api.hip", set(kernel_side), host)
+    return "\n".join(host)
+
+
 def load_scene(name: str) -> FlatScene:
     return FlatScene.load(os.path.join(SCENES, name + ".npz"))
 

@@ -9,7 +9,7 @@ import pytest
 
 from rustray_amd import capi
 from rustray_amd.flat import FlatScene, Item, Material, RR_ITEM_SPHERE, rr_flat_scene
-from tests.helpers import ROOT, load_scene
+from tests.helpers import ROOT, host_api_source, load_scene
 
 
 def declared_functions():
@@ -184,19 +184,19 @@ def test_exceptions_do_not_cross_the_abi():
 
 
 def test_every_entry_point_is_guarded():
-    """Every `extern "C" int rr_*` definition in rr_api.hip is a function-try-block closed by RR_GUARD_END (the no-throw promise of
-    include/rustray_hip.h:21-23 is structural, not case by case)."""
-    src = open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_api.hip")).read()
+    """Every `extern "C" int rr_*` definition in rr_api.hip and its layer files is a function-try-block closed by RR_GUARD_END (the
+    no-throw promise of include/rustray_hip.h:21-23 is structural, not case by case)."""
+    src = host_api_source()
     names = re.findall(r'extern "C" int (rr_[a-z_]+)\(', src)
-    assert len(names) >= 20
+    assert len(names) == 38 and len(set(names)) == 38   # every one of them: a layer file that drops out of the walk is missed here
     exempt = {"rr_test_fault", "rr_exp_util"}   # noexcept by construction (atomics and a strcpy) / developer build only
     for n in names:
         if n in exempt:
             continue
         assert re.search(r'extern "C" int ' + n + r'\([^{]*\) try \{', src), f"{n} is not a function-try-block"
         assert f'RR_GUARD_END("{n}")' in src, f"{n} has no RR_GUARD_END"
-    # worker threads only through `Workers`, in this file and in the scene builder it includes (where `Workers` itself lives)
-    src += open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_scene_build.h")).read()
+    # worker threads only through `Workers`, in these files and in the scene builder they include (where `Workers` itself lives)
+    assert "struct Workers {" in src
     assert "std::thread> pool" not in src and "threads.emplace_back(work" not in src
     assert len(re.findall(r"std::thread\b(?!::hardware_concurrency)", src)) == 2   # Workers' own vector and its join loop
 

@@ -1,4 +1,4 @@
-"""Level 1 in stages on two streams (rr_api.hip run_level1_stages): k_shade<true> of stage k + 1 beside k_trace_shadow<true> of
+"""Level 1 in stages on two streams (rr_api_frame.h run_level1_stages): k_shade<true> of stage k + 1 beside k_trace_shadow<true> of
 stage k, the stages rotating through 2 or 3 shadow-queue buffers.  The schedule may not change one bit of a frame: 152 x 120 at
 16 spp = 291 840 primary rays = 5 stages of 65 536 (the last one partial, the buffers wrapped) against the one-stage frame of the
 default tuning, which is itself held to the oracle's band; repeated frames on one handle, one enabled light (the buffer stride

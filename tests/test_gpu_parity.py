@@ -150,7 +150,7 @@ def test_batching_and_chunking_do_not_change_a_single_bit(hip):
 
 def test_branching_scene_in_a_small_ray_arena_is_sliced_depth_first(hip):
     """Every hit on glass spawns two children; with a ray arena of a few thousand rays the deeper levels do not fit
-    behind their parents at once, so levels are shaded in slices whose subtrees finish first (rr_api.hip run_level).
+    behind their parents at once, so levels are shaded in slices whose subtrees finish first (rr_api_frame.h run_level).
     Same bits as the unconstrained frame."""
     from rustray_amd.flat import FlatScene, Item, Light, Material
     from rustray_amd.scene import Scene

@@ -67,7 +67,7 @@ def test_sample_table_golden(oracle):
 
 
 def test_product_sample_table_matches_oracle(oracle):
-    # the product's own ChaCha12 / shuffle (rustray_amd/csrc/rr_api.hip) against the oracle's, no GPU needed
+    # the product's own ChaCha12 / shuffle (rustray_amd/csrc/rr_sample_table.h) against the oracle's, no GPU needed
     from rustray_amd import capi
     for samples in (1, 2, 3, 16, 64, 128, 512):
         a, ca = capi.sample_table(samples)

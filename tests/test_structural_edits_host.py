@@ -15,7 +15,7 @@ from rustray_amd import capi
 from rustray_amd.flat import RR_ITEM_MESH, RR_ITEM_SPHERE, TEX_NAMES
 from rustray_amd.renderer import IN_PLACE_STEPS, RECREATE, STRUCTURAL_STEPS, Raytracing, _resident_mesh_indices, plan_scene_update
 from rustray_amd.scene import Scene, scene_from_flat
-from tests.helpers import GOLDEN, ROOT, load_scene
+from tests.helpers import GOLDEN, ROOT, host_api_source, load_scene
 
 FIXTURE = os.path.join(GOLDEN, "add_objects")
 
@@ -252,8 +252,7 @@ def test_both_symbols_are_exported_and_refuse_null():
 
 
 def test_both_definitions_are_guarded_and_commit_last():
-    with open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_api.hip")) as f:
-        src = f.read()
+    src = host_api_source()
     for name, point in (("rr_scene_add_meshes", "add_meshes.device"), ("rr_scene_set_items", "set_items.device")):
         m = re.search(r'extern "C" int ' + name + r"\([^)]*\) try \{(.*?)\} RR_GUARD_END\(\"" + name + r"\"\)", src, re.S)
         assert m, f"{name} is not a function-try-block closed by RR_GUARD_END"
@@ -262,7 +261,7 @@ def test_both_definitions_are_guarded_and_commit_last():
         # nothing of the scene is written before the fault point and the wait for frames in flight; no "broken" flag is involved
         head, tail = body.split(f'RR_FAULT_POINT("{point}")')
         assert "hipDeviceSynchronize()" in tail.split("commit")[0]
-        assert not re.search(r"\bs->(?!mu\b)\w+(\.\w+)*\s*(=[^=]|\.swap|\.push_back)", head.replace("s->h_meshes.reserve", "")), name
+        assert not re.search(r"\bs->(?!mu\b)\w+(\.\w+)*\s*(=[^=]|\.swap|\.push_back)", head.replace("s->data.h_meshes.reserve", "")), name
         assert "broken_" not in body and "all_or_nothing" not in body
     m = re.search(r"static int check_intact\(const rr_scene\* s\) \{(.*?)\n\}", src, re.S)
     assert sorted(set(re.findall(r"broken_\w+", m.group(1)))) == ["broken_geometry", "broken_item_flags", "broken_lights", "broken_materials"]
