@@ -172,6 +172,7 @@ struct DFrame {
 //   r1 = (dir.xyz (normalised), bits(accumulator slot of the pixel))
 //   r2 = (sample | depth << 16 | idcarrier << 24, path node index)
 //   hit = (bits(toi), item index or -1, face id (+ n_tris for back faces), 0)
+// (the record of a path's root is written by root_record, rr_kernels.hip)
 struct DRayQueue {
     float4* r0;
     float4* r1;

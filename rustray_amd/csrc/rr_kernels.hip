@@ -79,7 +79,7 @@
 #ifndef RR_DYN_FETCH
 #define RR_DYN_FETCH 4 // packets per fetch from the shared head on large launches (more costs locality: +4 % at 8, +10 % at 16)
 #endif
-// Share of a launch's packets that is dealt to the waves round-robin, without an atomic (see k_trace_closest).
+// Share of a launch's packets that is dealt to the waves round-robin, without an atomic (see PacketStream).
 #ifndef RR_STATIC_NUM
 #define RR_STATIC_NUM 1
 #define RR_STATIC_DEN 2
@@ -167,6 +167,57 @@ RR_DEV void primary_ray(const DFrame& fr, const PrimaryFrame& pf, const DPrimary
     *origin_out = origin; *dir_out = dir; *pix_out = pix; *sample_out = s;
 }
 
+// The ray record (DRayQueue: r0, r1, r2) of the ROOT of a path -- a primary ray of a frame (k_shade<true>) or a caller's ray as depth
+// level 1 (k_seed_rays): throughput 1, depth 1, carries the object id, path node 1.  `pix`: the accumulator slot.
+RR_DEV void root_record(f3 origin, f3 dir, uint32_t pix, uint32_t sample, float4* r0, float4* r1, uint2* r2) {
+    *r0 = make_float4(origin.x, origin.y, origin.z, 1.0f);
+    *r1 = make_float4(dir.x, dir.y, dir.z, __uint_as_float(pix));
+    *r2 = make_uint2(sample | (1u << 16) | (1u << 24), 1u);
+}
+
+// ---------------------------------------------------------------------------
+// the packet stream of the walk kernels (k_trace_closest, k_trace_shadow, k_query_shadow): which 64-ray packet a wave takes next
+// ---------------------------------------------------------------------------
+// Work distribution.  Locality decides here: the waves that run side by side must walk neighbouring
+// packets (runs of consecutive packets per wave cost 1.8x, measured), and one head word sustains only ~90
+// fetches per microsecond.  So num / den of the packets (the static share: RR_STATIC_*, RR_SHADOW_*STATIC_*) are dealt
+// round-robin with no atomic at all, and the rest is pulled a few packets at a time from the shared head word to absorb
+// expensive packets.  Blocks b and b + 8 share an XCD (and its L2): when the grid is a multiple of 8 the blocks of one XCD
+// take one contiguous run of packets per round instead of every eighth group.
+struct PacketStream {
+    uint32_t n_packets, n_waves, wave_id, rounds, n_static, round, dyn_next, dyn_left, dyn_k;
+    uint32_t* head;
+    static RR_DEV uint32_t waves() { return gridDim.x * (RR_BLOCK / RR_WAVE); } // of the launch
+    // num / den: the static share; head: the launch's head word (the host zeroes it), counted in packets behind the static ones
+    RR_DEV PacketStream(uint32_t n_packets_, uint32_t num, uint32_t den, uint32_t* head_) : n_packets(n_packets_), head(head_) {
+        n_waves = waves();
+        uint32_t blk = blockIdx.x;
+        if ((gridDim.x & 7u) == 0u) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+        wave_id = blk * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE;
+        rounds = (uint32_t)(((unsigned long long)n_packets * num / den) / n_waves);
+        n_static = rounds * n_waves;
+        round = 0; dyn_next = 0; dyn_left = 0;
+        // packets per fetch of the dynamic part: RR_DYN_FETCH on large launches (more costs locality: +4 % at 8, +10 % at 16), fewer when
+        // the launch has only a few packets per wave
+        dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
+    }
+    // false: the stream has ended for this wave (wave-uniform)
+    RR_DEV bool next(uint32_t* pkt) {
+        uint32_t p;
+        if (round < rounds) { p = round * n_waves + wave_id; round++; }
+        else {
+            if (dyn_left == 0u) { // several packets per atomic: the head word sustains only ~90 fetches per microsecond
+                uint32_t f = 0;
+                if ((threadIdx.x & (RR_WAVE - 1)) == 0) f = atomicAdd(head, dyn_k);
+                dyn_next = n_static + __shfl(f, 0); dyn_left = dyn_k;
+            }
+            p = dyn_next++; dyn_left--;
+        }
+        *pkt = p;
+        return p < n_packets;
+    }
+};
+
 // ---------------------------------------------------------------------------
 // kernel 2: closest hit for a queue of rays
 // ---------------------------------------------------------------------------
@@ -190,38 +241,12 @@ __global__ __launch_bounds__(RR_BLOCK, RR_CLOSEST_WAVES) void k_trace_closest(DS
         if (blockIdx.x == 0 && threadIdx.x == 0) { *q_count = n; atomicAdd(&counters[RR_CNT_PRIMARY], (unsigned long long)n); }
     } else n = *q_count;
     const uint32_t lane = threadIdx.x & (RR_WAVE - 1);
-    // Work distribution.  Locality decides here: the waves that run side by side must walk neighbouring
-    // packets (runs of consecutive packets per wave cost 1.8x, measured), and one head word sustains only ~90
-    // fetches per microsecond.  So RR_STATIC_NUM/RR_STATIC_DEN of the packets are dealt round-robin with no atomic
-    // at all, and the rest is pulled a few packets at a time from the shared head to absorb expensive packets.
-    // Blocks b and b + 8 share an XCD (and its L2): when the grid is a multiple of 8 the blocks of one XCD take one
-    // contiguous run of packets per round instead of every eighth group.
-    const uint32_t n_waves = gridDim.x * (RR_BLOCK / RR_WAVE);
-    uint32_t blk = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t wave_id = blk * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE;
     const uint32_t n_packets = (n + RR_WAVE - 1) / RR_WAVE;
     // (a launch with few packets per wave -- one rank's share of a frame tiled over 4 or 8 GPUs -- deals three quarters statically:
     // closest-hit 2.36 -> 2.29 ms on a quarter of the contract frame, 1.36 -> 1.32 ms on an eighth; the whole frame loses 5 % to it)
-    const bool small_launch = n_packets < 160u * n_waves;
-    const uint32_t rounds = (uint32_t)(((unsigned long long)n_packets * (small_launch ? 3u : (uint32_t)RR_STATIC_NUM) / (small_launch ? 4u : (uint32_t)RR_STATIC_DEN)) / n_waves);
-    const uint32_t n_static = rounds * n_waves;
-    uint32_t round = 0, dyn_next = 0, dyn_left = 0;
-    // packets per fetch of the dynamic part: RR_DYN_FETCH on large launches (more costs locality: +4 % at 8, +10 % at 16), fewer when
-    // the launch has only a few packets per wave
-    const uint32_t dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
-    for (;;) {
-        uint32_t pkt;
-        if (round < rounds) { pkt = round * n_waves + wave_id; round++; }
-        else {
-            if (dyn_left == 0u) { // several packets per atomic: the head word sustains only ~90 fetches per microsecond
-                uint32_t f = 0;
-                if (lane == 0) f = atomicAdd(head, dyn_k);
-                dyn_next = n_static + __shfl(f, 0); dyn_left = dyn_k;
-            }
-            pkt = dyn_next++; dyn_left--;
-        }
-        if (pkt >= n_packets) break; // wave-uniform
+    const bool small_launch = n_packets < 160u * PacketStream::waves();
+    PacketStream stream(n_packets, small_launch ? 3u : (uint32_t)RR_STATIC_NUM, small_launch ? 4u : (uint32_t)RR_STATIC_DEN, head);
+    for (uint32_t pkt; stream.next(&pkt);) {
         const uint32_t i = pkt * RR_WAVE + lane;
         const uint32_t ii = min(i, n - 1u); // the lanes past the end of the last packet repeat its last ray, so that the packet form below runs with all lanes
         f3 ro, rd; uint32_t depth;
@@ -318,12 +343,10 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         if (active) {
         n_shaded++;
         float4 r0, r1; uint2 r2;
-        if (PRIMARY) { // the root node of a path: throughput 1, depth 1, carries the object id, path node 1
+        if (PRIMARY) { // the root node of a path
             f3 po, pd; uint32_t ppix, psmp;
             primary_ray(fr, kc->ps, pr, i, &po, &pd, &ppix, &psmp);
-            r0 = make_float4(po.x, po.y, po.z, 1.0f);
-            r1 = make_float4(pd.x, pd.y, pd.z, __uint_as_float(ppix));
-            r2 = make_uint2(psmp | (1u << 16) | (1u << 24), 1u);
+            root_record(po, pd, ppix, psmp, &r0, &r1, &r2);
         } else { r0 = qin.r0[i]; r1 = qin.r1[i]; r2 = qin.r2[i]; }
         const uint32_t pix = __float_as_uint(r1.w);
         pix_of_nf = pix;
@@ -332,46 +355,15 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         const bool idc = ((meta >> 24) & 1u) != 0u;
         const float thr = r0.w;
         const DItem& it = rr_global(sc.items)[item_idx];
-        const uint32_t it_flags = it.flags, it_tri_base = it.tri_base, it_id = it.id; // register copies (see MatR)
+        const uint32_t it_flags = it.flags, it_id = it.id; // register copies (see MatR)
         const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
         const f3 ro = mk3(r0.x, r0.y, r0.z), rd = mk3(r1.x, r1.y, r1.z);
         const float hit_dist = __uint_as_float(hit.x);
         const f3 hit_point = ro + (rd * hit_dist);
-        const uint32_t slot = hit.z & 0x3fffffffu;
-        const bool back = (hit.z >> 31) != 0u, neg = ((hit.z >> 30) & 1u) != 0u;
 
         // ---- world normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65)
-        f3 normal;
-        DTriAttr at; float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f; bool have_weights = false;
-        at.s0 = at.s1 = at.s2 = at.s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (it_flags & RR_IF_SPHERE) {
-            LRay lr = inverse_ray(it, ro, rd, gw || ray_nonfinite(ro, rd)); // (see to_local_point)
-            float t2 = 0.0f; bool inside = false;
-            ray_ball(it.radius, lr, (it_flags & RR_IF_SOLID_BASE) != 0u, &t2, &inside);
-            f3 nl = normalize3(lr.o + lr.d * t2);
-            normal = to_world_normal(it, inside ? -nl : nl);
-        } else {
-            const DTri* trp = &rr_global(sc.tris)[it_tri_base + slot];
-            // the area weights of the hit point serve the interpolated normal AND the uv (Mesh::get_normal and
-            // Mesh::get_uv compute the same three numbers from the same inputs, src/shape/mesh.rs:105-161, :204-259)
-            if ((it_flags & RR_IF_SMOOTH) || (m.flags & RR_MF_ANY_TEX)) {
-                const float4 v0 = trp->v0, v1 = trp->v1, v2 = trp->v2;
-                at = rr_global(sc.attrs)[it_tri_base + slot];
-                const f3 p = to_local_point(it, hit_point, gw);
-                area_weights(mk3(v0.x, v0.y, v0.z), mk3(v1.x, v1.y, v1.z), mk3(v2.x, v2.y, v2.z), p, v1.w, &a1, &a2, &a3); // v1.w: the triangle's area (host)
-                have_weights = true;
-            }
-            if (it_flags & RR_IF_SMOOTH) {
-                f3 p1 = mk3(at.s0.x, at.s0.y, at.s0.z) * a1, p2 = mk3(at.s1.x, at.s1.y, at.s1.z) * a2, p3 = mk3(at.s2.x, at.s2.y, at.s2.z) * a3;
-                normal = to_world_normal(it, mk3(p1.x + p2.x + p3.x, p1.y + p2.y + p3.y, p1.z + p2.z + p3.z));
-                if (back) normal = -normal;
-            } else {
-                // to_world_normal(it, neg ? -ng : ng) with ng = DTri::v3, evaluated once per instanced triangle by k_world_normals
-                const float4 wn = rr_global(sc.flat_normals)[it.wn_base + 2u * slot + (neg ? 1u : 0u)];
-                normal = mk3(wn.x, wn.y, wn.z);
-            }
-            if (it_flags & RR_IF_FLIP_NORMALS) normal = -normal;
-        }
+        HitWeights hw;
+        const f3 normal = hit_normal(sc, it, it_flags, m, ro, rd, hit_point, hit.z, gw, &hw);
         // ---- aux outputs of the root node (:742-744, :400-402): summed per pixel below, with the wave's other root hits
         if (depth == 1u) {
             aux_pix = pix;
@@ -390,32 +382,10 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             }
         }
         // ---- uv (:749-754)
-        bool has_uv = false; f2 uv; uv.x = 0.0f; uv.y = 0.0f;
-        if (m.flags & RR_MF_ANY_TEX) {
-            if (it_flags & RR_IF_SPHERE) uv = sphere_uv(it, hit_point, gw);
-            else if (have_weights && (__float_as_uint(at.s3.w) & 1u)) { // Mesh::get_uv with the weights from above
-                uv.x = (at.s0.w * a1 + at.s2.w * a2) + at.s3.y * a3;
-                uv.y = -((at.s1.w * a1 + at.s3.x * a2) + at.s3.z * a3);
-            }
-            has_uv = true;
-        }
-        f3 surface_normal = normal;
-        float4 tc;
+        f2 uv;
+        const bool has_uv = hit_uv(it, it_flags, m, hit_point, gw, hw, &uv);
         // ---- normal mapping (:757-784)
-        if (tex_color(sc, m, has_uv, uv, 3, &tc)) {
-            f3 tangent = cross3(normal, mk3(0.0f, 1.0f, 0.0f));
-            if (norm3(tangent) <= 0.0001f) tangent = cross3(normal, mk3(0.0f, 0.0f, 1.0f));
-            tangent = normalize3(tangent);
-            f3 bitangent = normalize3(cross3(normal, tangent));
-            f3 nm = mk3((tc.x * 2.0f) - 1.0f, (tc.y * 2.0f) - 1.0f, (tc.z * 2.0f) - 1.0f);
-            nm.x *= m.normal_map_strength; nm.y *= m.normal_map_strength;
-            nm = normalize3(nm);
-            f3 t;
-            t.x = (tangent.x * nm.x + bitangent.x * nm.y) + normal.x * nm.z;
-            t.y = (tangent.y * nm.x + bitangent.y * nm.y) + normal.y * nm.z;
-            t.z = (tangent.z * nm.x + bitangent.z * nm.y) + normal.z * nm.z;
-            surface_normal = normalize3(t);
-        }
+        f3 surface_normal = mapped_normal(sc, m, has_uv, uv, normal);
         // the generator is keyed on the FRAME pixel (y * width + x), never on the accumulator slot
         const uint32_t xy = slot_xy[pix];
         RngKey rk; rk.seed_lo = fr.seed_lo; rk.seed_hi = fr.seed_hi;
@@ -423,23 +393,18 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         const bool mc = fr.monte_carlo != 0u && (m.flags & RR_MF_MONTE_CARLO) != 0u;
         // ---- roughness (:787-798)
         {
-            bool has_rtc = tex_color(sc, m, has_uv, uv, 5, &tc);
-            if (mc && (m.roughness > 0.0f || has_rtc)) {
-                float roughness = m.roughness, z_lo = m.cos_roughness;
-                if (has_rtc) { roughness = (1.0f / RR_PI_F / 2.0f) * tc.x; z_lo = rr_cos(roughness * RR_PI_F); }
-                surface_normal = jitter(surface_normal, roughness, z_lo, rk, 0u);
-            }
+            float roughness;
+            const bool has_rtc = roughness_spread(sc, m, has_uv, uv, &roughness);
+            if (mc && (m.roughness > 0.0f || has_rtc))
+                surface_normal = jitter(surface_normal, roughness, has_rtc ? rr_cos(roughness * RR_PI_F) : m.cos_roughness, rk, 0u);
         }
         // ---- colours and alpha (:801-811)
-        const float4 ambient_color = item_color(sc, m, has_uv, uv, m.ambient, 1);
-        const float4 base_color = item_color(sc, m, has_uv, uv, m.base, 0);
-        const float4 specular_color = item_color(sc, m, has_uv, uv, m.specular, 2);
-        float alpha = m.alpha * base_color.w;
-        if (tex_color(sc, m, has_uv, uv, 4, &tc)) alpha *= tc.x;
+        const HitColors col = hit_colors(sc, m, has_uv, uv);
+        const float4 ambient_color = col.ambient, base_color = col.base, specular_color = col.specular;
+        const float alpha = col.alpha;
 
         // ---- everything after the light loop that does not depend on it (:922-991)
-        float reflectivity = m.reflectivity;
-        if (tex_color(sc, m, has_uv, uv, 7, &tc)) reflectivity = tc.x;
+        const float reflectivity = hit_reflectivity(sc, m, has_uv, uv);
         const bool may_recurse = depth <= fr.max_recursion;
         spawn_refl = reflectivity > 0.0f && may_recurse;
         f3 refr_o = mk3(0.0f, 0.0f, 0.0f), refr_d = mk3(0.0f, 0.0f, 0.0f);
@@ -463,8 +428,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             a_mul = alpha;
         }
         const float fog_amount = rs_min(fr.fog_density * hit_dist, 1.0f);
-        float ao = 1.0f;
-        if (tex_color(sc, m, has_uv, uv, 6, &tc)) ao = tc.x;
+        const float ao = hit_ambient_occlusion(sc, m, has_uv, uv);
         const float g = (1.0f - fog_amount) * ao;
         const float w_light = thr * ((1.0f - reflectivity) * a_mul * g);
         const float w_refl = thr * (reflectivity * a_mul * g);
@@ -636,18 +600,20 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
 // One workgroup per CHUNK of an item's triangles (`chunks`: (item, first triangle) per workgroup, RR_ITEM_CHUNK triangles each, laid out by
 // rr_scene_create: a mesh of a million triangles is 123 workgroups, not one).
 #define RR_ITEM_CHUNK 8192u
+// Triangle `slot` of mesh item `it`: both signs of its flat normal through the item's transform
+RR_DEV void flat_world_normals(const DItem& it, uint32_t slot, const DTri* tris, float4* out) {
+    const float4 v3 = tris[it.tri_base + slot].v3;
+    const f3 ng = mk3(v3.x, v3.y, v3.z);
+    const f3 p = to_world_normal(it, ng), m = to_world_normal(it, -ng);
+    out[it.wn_base + 2u * slot] = make_float4(p.x, p.y, p.z, 0.0f);
+    out[it.wn_base + 2u * slot + 1u] = make_float4(m.x, m.y, m.z, 0.0f);
+}
 __global__ __launch_bounds__(RR_BLOCK) void k_world_normals(const DItem* __restrict__ items, const uint2* __restrict__ chunks, const DTri* __restrict__ tris, float4* __restrict__ out) {
     const uint2 ch = chunks[blockIdx.x];
     const DItem& it = items[ch.x];
     if (it.flags & RR_IF_SPHERE) return;
     const uint32_t end = min(it.n_tris, ch.y + RR_ITEM_CHUNK);
-    for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) {
-        const float4 v3 = tris[it.tri_base + slot].v3;
-        const f3 ng = mk3(v3.x, v3.y, v3.z);
-        const f3 p = to_world_normal(it, ng), m = to_world_normal(it, -ng);
-        out[it.wn_base + 2u * slot] = make_float4(p.x, p.y, p.z, 0.0f);
-        out[it.wn_base + 2u * slot + 1u] = make_float4(m.x, m.y, m.z, 0.0f);
-    }
+    for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) flat_world_normals(it, slot, tris, out);
 }
 
 // The flat world normals of an EDITED item list (rr_scene_set_items), into the new arena: one workgroup per chunk of the new chunk
@@ -668,13 +634,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_world_normals_edit(const DItem* __
         for (uint32_t k = 2u * ch.y + threadIdx.x; k < 2u * end; k += blockDim.x) out[it.wn_base + k] = old[src + k];
         return;
     }
-    for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) {
-        const float4 v3 = tris[it.tri_base + slot].v3;
-        const f3 ng = mk3(v3.x, v3.y, v3.z);
-        const f3 p = to_world_normal(it, ng), m = to_world_normal(it, -ng);
-        out[it.wn_base + 2u * slot] = make_float4(p.x, p.y, p.z, 0.0f);
-        out[it.wn_base + 2u * slot + 1u] = make_float4(m.x, m.y, m.z, 0.0f);
-    }
+    for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) flat_world_normals(it, slot, tris, out);
 }
 
 // The extent of every mesh item's SURFACE along the rows of its transform (rr_scene_build.h: exact_world_box): one workgroup per item over
@@ -762,31 +722,9 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
     const uint32_t n_packets = FIXED ? n_fixed_packets : (n + RR_WAVE - 1) / RR_WAVE;
     const uint32_t lane = threadIdx.x & (RR_WAVE - 1);
     const bool gw = sc.general_w != 0u;
-    // same packet stream as k_trace_closest: most packets dealt round-robin without an atomic (blocks of one XCD
-    // take one contiguous run per round), the tail pulled dyn_k packets per atomic to absorb the expensive ones
-    const uint32_t n_waves = gridDim.x * (RR_BLOCK / RR_WAVE);
-    uint32_t blk = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t wave_id = blk * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE;
     // (level 1's aligned packets cost much the same and are mostly dealt statically; the dense queue of the deeper levels keeps half dynamic)
-    const uint32_t rounds = (uint32_t)(((unsigned long long)n_packets * (FIXED ? RR_SHADOW_FIXED_STATIC_NUM : RR_SHADOW_STATIC_NUM) / (FIXED ? RR_SHADOW_FIXED_STATIC_DEN : RR_SHADOW_STATIC_DEN)) / n_waves);
-    const uint32_t n_static = rounds * n_waves;
-    uint32_t round = 0, dyn_next = 0, dyn_left = 0;
-    // packets per fetch of the dynamic part: RR_DYN_FETCH on large launches (more costs locality: +4 % at 8, +10 % at 16), fewer when
-    // the launch has only a few packets per wave
-    const uint32_t dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
-    for (;;) {
-        uint32_t p;
-        if (round < rounds) { p = round * n_waves + wave_id; round++; }
-        else {
-            if (dyn_left == 0u) {
-                uint32_t f = 0;
-                if (lane == 0) f = atomicAdd(head, dyn_k);
-                dyn_next = n_static + __shfl(f, 0); dyn_left = dyn_k;
-            }
-            p = dyn_next++; dyn_left--;
-        }
-        if (p >= n_packets) break;
+    PacketStream stream(n_packets, FIXED ? RR_SHADOW_FIXED_STATIC_NUM : RR_SHADOW_STATIC_NUM, FIXED ? RR_SHADOW_FIXED_STATIC_DEN : RR_SHADOW_STATIC_DEN, head);
+    for (uint32_t p; stream.next(&p);) {
         unsigned long long valid;
         if (FIXED) valid = sq_valid[p]; // (the same word in every lane)
         else { const uint32_t left = n - p * RR_WAVE; valid = left >= RR_WAVE ? ~0ull : (1ull << left) - 1ull; }
@@ -857,27 +795,8 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_query_shadow(DSce
     RR_UTIL_KIND(2u)
     const uint32_t n_packets = (n + RR_WAVE - 1) / RR_WAVE;
     const uint32_t lane = threadIdx.x & (RR_WAVE - 1);
-    // the packet stream of k_trace_shadow's dense queue: half dealt round-robin without an atomic, half pulled from the shared head
-    const uint32_t n_waves = gridDim.x * (RR_BLOCK / RR_WAVE);
-    uint32_t blk = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t wave_id = blk * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE;
-    const uint32_t rounds = (uint32_t)(((unsigned long long)n_packets * RR_SHADOW_STATIC_NUM / RR_SHADOW_STATIC_DEN) / n_waves);
-    const uint32_t n_static = rounds * n_waves;
-    uint32_t round = 0, dyn_next = 0, dyn_left = 0;
-    const uint32_t dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
-    for (;;) {
-        uint32_t p;
-        if (round < rounds) { p = round * n_waves + wave_id; round++; }
-        else {
-            if (dyn_left == 0u) {
-                uint32_t f = 0;
-                if (lane == 0) f = atomicAdd(head, dyn_k);
-                dyn_next = n_static + __shfl(f, 0); dyn_left = dyn_k;
-            }
-            p = dyn_next++; dyn_left--;
-        }
-        if (p >= n_packets) break; // wave-uniform
+    PacketStream stream(n_packets, RR_SHADOW_STATIC_NUM, RR_SHADOW_STATIC_DEN, head); // the static share of k_trace_shadow's dense queue
+    for (uint32_t p; stream.next(&p);) {
         const uint32_t i = p * RR_WAVE + lane;
         const bool live = i < n;
         // lanes past the end repeat the packet's first ray (the packet form runs with all lanes) and write nothing
@@ -1011,21 +930,11 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t*
     uint32_t o;
     if (frame_layout) { uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
     else o = slot_out[p]; // position in the region's compact output order
-    const double inv_fix = 1.0 / 16777216.0;
     const float n = (float)fr.samples;
     const uint32_t nf = acc.flags[p];
     float c[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float sum = (float)((double)acc.rgb[(unsigned long long)k * acc.n + p] * inv_fix);
-        // what the reference's f32 sum would hold if a sample was not finite: NaN (also +inf + -inf) or +-inf
-        const bool pinf = (nf >> (3 + k)) & 1u, ninf = (nf >> (6 + k)) & 1u;
-        if (((nf >> k) & 1u) || (pinf && ninf)) sum = __builtin_nanf("");
-        else if (pinf) sum = __builtin_inff();
-        else if (ninf) sum = -__builtin_inff();
-        float v = sum / n;
-        c[k] = rs_min(v, 1.0f); // f32::min: NaN.min(1.0) = 1.0
-    }
+    for (int k = 0; k < 3; k++) c[k] = rs_min(resolve_color(acc, p, nf, k, n), 1.0f); // f32::min: NaN.min(1.0) = 1.0
     uint32_t r, g, b;
     if (fr.gamma) {
         const float ig = 1.0f / 2.2f;
@@ -1035,28 +944,21 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t*
     }
     ((uint32_t*)rgba8)[o] = r | (g << 8) | (b << 16) | (255u << 24);
     if (normal && acc.normal) {
-        f3 nn = mk3((float)((double)acc.normal[p] * inv_fix) / n, (float)((double)acc.normal[acc.n + p] * inv_fix) / n,
-                    (float)((double)acc.normal[2ull * acc.n + p] * inv_fix) / n);
-        if (nf & (RR_NF_NORMAL_NAN * 7u)) { // a NaN sample normal poisons its component, and through the norm all three
-            if (nf & RR_NF_NORMAL_NAN) nn.x = __builtin_nanf("");
-            if (nf & (RR_NF_NORMAL_NAN << 1)) nn.y = __builtin_nanf("");
-            if (nf & (RR_NF_NORMAL_NAN << 2)) nn.z = __builtin_nanf("");
-        }
-        nn = normalize3(nn); // 0/0 = NaN on all-miss pixels, as in the reference (:426)
+        const f3 nn = resolve_normal(acc, p, nf, n);
         normal[3ull * o] = nn.x; normal[3ull * o + 1] = nn.y; normal[3ull * o + 2] = nn.z;
     }
-    if (depth && acc.depth) depth[o] = (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)acc.depth[p] * (1.0 / 65536.0)) / n;
+    if (depth && acc.depth) depth[o] = resolve_depth(acc, p, nf, n);
     if (object_id && acc.object_id) object_id[o] = acc.object_id[p];
 }
 
 // ---------------------------------------------------------------------------
 // kernels 5b, 5c: caller-supplied rays as depth level 1 (rr_shade_rays): get_color_depth_normal_id(scene, ray, 1) per ray
 // ---------------------------------------------------------------------------
-// One batch of the caller's rays -> level-1 RECORDS at the front of the ray arena, the fields k_shade<true> builds for a root:
-// throughput 1, depth 1, id carrier, path node 1.  Record i is the caller's ray first + i = sample (first + i) % rays_per_result of
-// result (first + i) / rays_per_result, whose accumulator slot is the result's index: the samples of a result sit in neighbouring
-// lanes and accum_merged merges their adds.  origins / dirs: the batch's 3 n floats each.  The direction is normalised as
-// primary_ray does it (get_color_depth_normal_id, :723).  Thread 0 publishes the level's size and counts the rays.
+// One batch of the caller's rays -> level-1 RECORDS at the front of the ray arena: root_record, as for a frame's primary ray.
+// Record i is the caller's ray first + i = sample (first + i) % rays_per_result of result (first + i) / rays_per_result, whose
+// accumulator slot is the result's index: the samples of a result sit in neighbouring lanes and accum_merged merges their adds.
+// origins / dirs: the batch's 3 n floats each.  The direction is normalised as primary_ray does it (get_color_depth_normal_id, :723).
+// Thread 0 publishes the level's size and counts the rays.
 __global__ __launch_bounds__(RR_BLOCK) void k_seed_rays(const float* __restrict__ origins, const float* __restrict__ dirs, unsigned long long first, uint32_t n,
                                                         uint32_t rays_per_result, DRayQueue q, uint32_t* __restrict__ q_count, unsigned long long* counters) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1065,39 +967,22 @@ __global__ __launch_bounds__(RR_BLOCK) void k_seed_rays(const float* __restrict_
     const unsigned long long g = first + i;
     const uint32_t slot = (uint32_t)(g / rays_per_result), sample = (uint32_t)(g % rays_per_result);
     const f3 d = normalize3(mk3(dirs[3ull * i], dirs[3ull * i + 1], dirs[3ull * i + 2]));
-    q.r0[i] = make_float4(origins[3ull * i], origins[3ull * i + 1], origins[3ull * i + 2], 1.0f);
-    q.r1[i] = make_float4(d.x, d.y, d.z, __uint_as_float(slot));
-    q.r2[i] = make_uint2(sample | (1u << 16) | (1u << 24), 1u);
+    root_record(mk3(origins[3ull * i], origins[3ull * i + 1], origins[3ull * i + 2]), d, slot, sample, &q.r0[i], &q.r1[i], &q.r2[i]);
 }
 
 // What k_resolve computes BEFORE its clamp, per accumulator slot [first, first + n): two float4 per result =
-// (colour rgb, depth), (normal xyz, bits(object id)) -- rr_radiance.  Every expression is k_resolve's own.
+// (colour rgb, depth), (normal xyz, bits(object id)) -- rr_radiance: resolve_color / resolve_normal / resolve_depth (rr_accumulate.h).
 __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t first, uint32_t n, uint32_t samples, float4* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t p = first + i;
-    const double inv_fix = 1.0 / 16777216.0;
     const float ns = (float)samples;
     const uint32_t nf = acc.flags[p];
     float c[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float sum = (float)((double)acc.rgb[(unsigned long long)k * acc.n + p] * inv_fix);
-        const bool pinf = (nf >> (3 + k)) & 1u, ninf = (nf >> (6 + k)) & 1u;
-        if (((nf >> k) & 1u) || (pinf && ninf)) sum = __builtin_nanf("");
-        else if (pinf) sum = __builtin_inff();
-        else if (ninf) sum = -__builtin_inff();
-        c[k] = sum / ns;
-    }
-    f3 nn = mk3((float)((double)acc.normal[p] * inv_fix) / ns, (float)((double)acc.normal[acc.n + p] * inv_fix) / ns,
-                (float)((double)acc.normal[2ull * acc.n + p] * inv_fix) / ns);
-    if (nf & (RR_NF_NORMAL_NAN * 7u)) {
-        if (nf & RR_NF_NORMAL_NAN) nn.x = __builtin_nanf("");
-        if (nf & (RR_NF_NORMAL_NAN << 1)) nn.y = __builtin_nanf("");
-        if (nf & (RR_NF_NORMAL_NAN << 2)) nn.z = __builtin_nanf("");
-    }
-    nn = normalize3(nn); // 0/0 = NaN when every ray missed, as a frame's pixel
-    const float depth = (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)acc.depth[p] * (1.0 / 65536.0)) / ns;
+    for (int k = 0; k < 3; k++) c[k] = resolve_color(acc, p, nf, k, ns);
+    const f3 nn = resolve_normal(acc, p, nf, ns);
+    const float depth = resolve_depth(acc, p, nf, ns);
     out[2ull * i] = make_float4(c[0], c[1], c[2], depth);
     out[2ull * i + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
 }
@@ -1189,8 +1074,8 @@ __global__ __launch_bounds__(RR_BLOCK) void k_ray_reach(const float* __restrict_
 }
 
 // 5f: the walks' raw 16-byte hit records -> the 20-byte records of the ABI, as rr_trace_rays / rr_trace_shadow_rays build them on the host.
-//   closest (k_trace_closest): (bits(toi), item or -1, leaf-order slot | side bits, 0) -> rr_ray_hit {hit, item, id, face, toi}; the reference's
-//     face id is the triangle record's original face index (DTriX::t0.w) + n_tris for a back face, 0 for a ball
+//   closest (k_trace_closest): (bits(toi), item or -1, leaf-order slot | side bits, 0) -> rr_ray_hit {hit, item, id, face, toi}; face:
+//     reference_face_id (rr_trace.h)
 //   SHADOW (k_query_shadow): (bits(toi), item, reference face id, occluded) -> rr_shadow_hit {occluded, item, id, face, toi}
 template <bool SHADOW>
 __global__ __launch_bounds__(RR_BLOCK) void k_unpack_hits(const uint4* __restrict__ hits, uint32_t n, const DItem* __restrict__ items, uint32_t n_items,
@@ -1207,10 +1092,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_unpack_hits(const uint4* __restric
                 const DItem* it = &items[h.y];
                 w0 = 1u; w1 = h.y; w2 = it->id; w4 = h.x;
                 if (SHADOW) w3 = h.z;
-                else if (!(it->flags & RR_IF_SPHERE)) {
-                    const uint32_t slot = h.z & 0x3fffffffu, back = h.z >> 31;
-                    w3 = __float_as_uint(trix[(unsigned long long)it->tri_base + slot].t0.w) + (back ? it->n_tris : 0u);
-                }
+                else w3 = reference_face_id(it, trix, h.z);
             }
             s_w[5 * tid] = w0; s_w[5 * tid + 1] = w1; s_w[5 * tid + 2] = w2; s_w[5 * tid + 3] = w3; s_w[5 * tid + 4] = w4;
         }
@@ -1252,9 +1134,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_hits(DSceneView sc, const 
             for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
             if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
                 const DItem& it = rr_global(sc.items)[h.y];
-                uint32_t face = 0u; // the reference's face id, as k_unpack_hits reports it
-                if (!(it.flags & RR_IF_SPHERE))
-                    face = __float_as_uint(rr_global(sc.trix)[(unsigned long long)it.tri_base + (h.z & 0x3fffffffu)].t0.w) + ((h.z >> 31) ? it.n_tris : 0u);
+                const uint32_t face = reference_face_id(&it, rr_global(sc.trix), h.z);
                 const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
                 const float4 a = r0[i], b = r1[i];
                 const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);

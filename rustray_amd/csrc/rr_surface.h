@@ -4,7 +4,8 @@
 // fresnel (:535-563).
 //
 // Offers: c_u8_to_f32 (filled by rr_api_scene.h rr_scene_create); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
-// item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; SurfaceAt, surface_at.  No macros.
+// item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; the steps of a hit's surface (HitWeights, hit_normal, hit_uv,
+// mapped_normal, roughness_spread, hit_colors, hit_reflectivity, hit_ambient_occlusion) and their composition (SurfaceAt, surface_at).  No macros.
 // Needs: rr_primitives.h (to_local_point, inverse_ray, ray_ball, to_world_normal), rr_walk.h (rr_global), rr_trace.h (ray_nonfinite).
 #pragma once
 #include "rr_walk.h"
@@ -174,27 +175,20 @@ RR_DEV float fresnel(f3 incident, f3 normal, float index) {
 }
 
 // ---------------------------------------------------------------------------
-// the surface of a closest hit (rr_surface_rays): what get_color_depth_normal_id evaluates between `trace` and the light loop
-// (reference src/raytracing.rs:747-811, :928-933, :985-991), without lights, recursion, fog and the generator
+// the surface of a closest hit: what get_color_depth_normal_id evaluates between `trace` and the light loop (reference
+// src/raytracing.rs:747-811, :928-933, :985-991), in the reference's steps.  k_shade calls the steps where it needs their values,
+// between its own sums, jitter and recursion; surface_at (rr_surface_rays) is their composition for callers that want the values.
 // ---------------------------------------------------------------------------
-// k_shade evaluates the same values inline, for its own use; this restates them, operation for operation and in k_shade's order,
-// for callers that want the values themselves.  `hit_z`: the walks' face word (leaf-order slot | negated << 30 | back << 31).
-struct SurfaceAt {
-    f3 position, normal, shading_normal; // origin + direction * toi; Shape::intersect's world normal; after normal mapping, before any jitter
-    f2 uv; bool has_uv;                  // get_uv where the material has any texture, else (0, 0) and false
-    float4 base_color, ambient_color, specular_color; // get_item_color
-    float alpha, reflectivity, roughness, ambient_occlusion;
-};
-RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m, f3 ro, f3 rd, float hit_dist, uint32_t hit_z) {
-    SurfaceAt s;
-    const bool gw = sc.general_w != 0u;
-    const uint32_t it_flags = it.flags, it_tri_base = it.tri_base;
-    const f3 hit_point = ro + (rd * hit_dist);
+// The area weights of a mesh hit and its triangle's attributes: they serve the interpolated normal AND the uv (Mesh::get_normal and
+// Mesh::get_uv compute the same three numbers from the same inputs, src/shape/mesh.rs:105-161, :204-259)
+struct HitWeights { DTriAttr at; float a1, a2, a3; bool have; };
+
+// World normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65).  `it_flags`: the caller's register copy of it.flags (see MatR);
+// `hit_z`: the walks' face word (leaf-order slot | negated << 30 | back << 31); `gw`: DSceneView::general_w.
+RR_DEV f3 hit_normal(const DSceneView& sc, const DItem& it, uint32_t it_flags, const MatR& m, f3 ro, f3 rd, f3 hit_point, uint32_t hit_z, bool gw, HitWeights* w) {
+    const uint32_t it_tri_base = it.tri_base;
     const uint32_t slot = hit_z & 0x3fffffffu;
     const bool back = (hit_z >> 31) != 0u, neg = ((hit_z >> 30) & 1u) != 0u;
-    s.position = hit_point;
-
-    // ---- world normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65)
     f3 normal;
     DTriAttr at; float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f; bool have_weights = false;
     at.s0 = at.s1 = at.s2 = at.s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -206,7 +200,6 @@ RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m
         normal = to_world_normal(it, inside ? -nl : nl);
     } else {
         const DTri* trp = &rr_global(sc.tris)[it_tri_base + slot];
-        // the area weights of the hit point serve the interpolated normal AND the uv (src/shape/mesh.rs:105-161, :204-259)
         if ((it_flags & RR_IF_SMOOTH) || (m.flags & RR_MF_ANY_TEX)) {
             const float4 v0 = trp->v0, v1 = trp->v1, v2 = trp->v2;
             at = rr_global(sc.attrs)[it_tri_base + slot];
@@ -225,21 +218,27 @@ RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m
         }
         if (it_flags & RR_IF_FLIP_NORMALS) normal = -normal;
     }
-    s.normal = normal;
-    // ---- uv (:749-754)
+    w->at = at; w->a1 = a1; w->a2 = a2; w->a3 = a3; w->have = have_weights;
+    return normal;
+}
+// uv (:749-754): get_uv where the material has any texture (the return value), else (0, 0)
+RR_DEV bool hit_uv(const DItem& it, uint32_t it_flags, const MatR& m, f3 hit_point, bool gw, const HitWeights& w, f2* uv_out) {
     bool has_uv = false; f2 uv; uv.x = 0.0f; uv.y = 0.0f;
     if (m.flags & RR_MF_ANY_TEX) {
         if (it_flags & RR_IF_SPHERE) uv = sphere_uv(it, hit_point, gw);
-        else if (have_weights && (__float_as_uint(at.s3.w) & 1u)) { // Mesh::get_uv with the weights from above
-            uv.x = (at.s0.w * a1 + at.s2.w * a2) + at.s3.y * a3;
-            uv.y = -((at.s1.w * a1 + at.s3.x * a2) + at.s3.z * a3);
+        else if (w.have && (__float_as_uint(w.at.s3.w) & 1u)) { // Mesh::get_uv with the weights of hit_normal
+            uv.x = (w.at.s0.w * w.a1 + w.at.s2.w * w.a2) + w.at.s3.y * w.a3;
+            uv.y = -((w.at.s1.w * w.a1 + w.at.s3.x * w.a2) + w.at.s3.z * w.a3);
         }
         has_uv = true;
     }
-    s.uv = uv; s.has_uv = has_uv;
+    *uv_out = uv;
+    return has_uv;
+}
+// normal mapping (:757-784): `normal` where the material has no normal map
+RR_DEV f3 mapped_normal(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, f3 normal) {
     f3 surface_normal = normal;
     float4 tc;
-    // ---- normal mapping (:757-784)
     if (tex_color(sc, m, has_uv, uv, 3, &tc)) {
         f3 tangent = cross3(normal, mk3(0.0f, 1.0f, 0.0f));
         if (norm3(tangent) <= 0.0001f) tangent = cross3(normal, mk3(0.0f, 0.0f, 1.0f));
@@ -254,21 +253,62 @@ RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m
         t.z = (tangent.z * nm.x + bitangent.z * nm.y) + normal.z * nm.z;
         surface_normal = normalize3(t);
     }
-    s.shading_normal = surface_normal;
-    // ---- roughness (:787-798): the spread the jitter would take, whether or not monte_carlo asks for one
-    s.roughness = m.roughness;
-    if (tex_color(sc, m, has_uv, uv, 5, &tc)) s.roughness = (1.0f / RR_PI_F / 2.0f) * tc.x;
-    // ---- colours and alpha (:801-811)
-    s.ambient_color = item_color(sc, m, has_uv, uv, m.ambient, 1);
-    s.base_color = item_color(sc, m, has_uv, uv, m.base, 0);
-    s.specular_color = item_color(sc, m, has_uv, uv, m.specular, 2);
-    float alpha = m.alpha * s.base_color.w;
-    if (tex_color(sc, m, has_uv, uv, 4, &tc)) alpha *= tc.x;
-    s.alpha = alpha;
-    // ---- reflectivity (:928-933) and ambient occlusion (:985-991)
-    s.reflectivity = m.reflectivity;
-    if (tex_color(sc, m, has_uv, uv, 7, &tc)) s.reflectivity = tc.x;
-    s.ambient_occlusion = 1.0f;
-    if (tex_color(sc, m, has_uv, uv, 6, &tc)) s.ambient_occlusion = tc.x;
+    return surface_normal;
+}
+// roughness (:787-798): the spread a jitter of the normal takes -- the material's, or its roughness map's texel (the return value says which)
+RR_DEV bool roughness_spread(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, float* roughness) {
+    float4 tc;
+    const bool has_rtc = tex_color(sc, m, has_uv, uv, 5, &tc);
+    *roughness = m.roughness;
+    if (has_rtc) *roughness = (1.0f / RR_PI_F / 2.0f) * tc.x;
+    return has_rtc;
+}
+// colours (get_item_color) and alpha (:801-811), returned as one value: through four pointers k_shade spills VGPRs at its 128
+struct HitColors { float4 ambient, base, specular; float alpha; };
+RR_DEV HitColors hit_colors(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv) {
+    HitColors c;
+    c.ambient = item_color(sc, m, has_uv, uv, m.ambient, 1);
+    c.base = item_color(sc, m, has_uv, uv, m.base, 0);
+    c.specular = item_color(sc, m, has_uv, uv, m.specular, 2);
+    c.alpha = m.alpha * c.base.w;
+    float4 tc;
+    if (tex_color(sc, m, has_uv, uv, 4, &tc)) c.alpha *= tc.x;
+    return c;
+}
+// reflectivity (:928-933)
+RR_DEV float hit_reflectivity(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv) {
+    float reflectivity = m.reflectivity;
+    float4 tc;
+    if (tex_color(sc, m, has_uv, uv, 7, &tc)) reflectivity = tc.x;
+    return reflectivity;
+}
+// ambient occlusion (:985-991)
+RR_DEV float hit_ambient_occlusion(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv) {
+    float ao = 1.0f;
+    float4 tc;
+    if (tex_color(sc, m, has_uv, uv, 6, &tc)) ao = tc.x;
+    return ao;
+}
+
+struct SurfaceAt {
+    f3 position, normal, shading_normal; // origin + direction * toi; Shape::intersect's world normal; after normal mapping, before any jitter
+    f2 uv; bool has_uv;                  // get_uv where the material has any texture, else (0, 0) and false
+    float4 base_color, ambient_color, specular_color; // get_item_color
+    float alpha, reflectivity, roughness, ambient_occlusion; // roughness: the spread, whether or not monte_carlo asks for a jitter
+};
+RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m, f3 ro, f3 rd, float hit_dist, uint32_t hit_z) {
+    SurfaceAt s;
+    const bool gw = sc.general_w != 0u;
+    const uint32_t it_flags = it.flags;
+    HitWeights w;
+    s.position = ro + (rd * hit_dist);
+    s.normal = hit_normal(sc, it, it_flags, m, ro, rd, s.position, hit_z, gw, &w);
+    s.has_uv = hit_uv(it, it_flags, m, s.position, gw, w, &s.uv);
+    s.shading_normal = mapped_normal(sc, m, s.has_uv, s.uv, s.normal);
+    roughness_spread(sc, m, s.has_uv, s.uv, &s.roughness);
+    const HitColors c = hit_colors(sc, m, s.has_uv, s.uv);
+    s.ambient_color = c.ambient; s.base_color = c.base; s.specular_color = c.specular; s.alpha = c.alpha;
+    s.reflectivity = hit_reflectivity(sc, m, s.has_uv, s.uv);
+    s.ambient_occlusion = hit_ambient_occlusion(sc, m, s.has_uv, s.uv);
     return s;
 }

@@ -3,7 +3,7 @@
 // closest-hit rays and for shadow rays (first item hit in bbox-distance order, :483-486), including what the reference's
 // arithmetic does with non-finite rays and NaN hits.
 //
-// Offers: Closest, ray_nonfinite, trace_closest_ray, trace_closest_packet, trace_closest_nonfinite, trace_closest_ordered;
+// Offers: Closest, reference_face_id, ray_nonfinite, trace_closest_ray, trace_closest_packet, trace_closest_nonfinite, trace_closest_ordered;
 // ShadowSel, trace_shadow_ray, trace_shadow_packet (trace_shadow_nonfinite through trace_shadow_ray), shadow_deciding_hit.  The per-item functions
 // (aabb_cast2, item_passes, closest_item*, shadow_item, shadow_blocker_item, trace_shadow_blockers) and the packet top level
 // (wave_min_f32 / wave_max_f32 / wave_min_u32, beam_axis, beam_candidates, beam_next) are this layer's own.
@@ -60,6 +60,13 @@ RR_DEV bool item_passes(uint32_t flags, bool for_shadow, uint32_t depth) {
 }
 
 struct Closest { float t; int item; uint32_t face; float key; bool found; bool nan_seen; }; // nan_seen: a ball answered Some(NaN) (trace_closest_ordered)
+
+// The reference's face id of a raw closest hit on item `it` (`face`: Closest::face = leaf-order slot | negated << 30 | back << 31): the
+// triangle record's original face index (DTriX::t0.w), plus n_tris for a back face; 0 for a ball.
+RR_DEV uint32_t reference_face_id(const DItem* it, const DTriX* trix, uint32_t face) {
+    if (it->flags & RR_IF_SPHERE) return 0u;
+    return __float_as_uint(trix[(unsigned long long)it->tri_base + (face & 0x3fffffffu)].t0.w) + ((face >> 31) ? it->n_tris : 0u);
+}
 
 // The reference sorts candidates by bbox distance (stable) and keeps strictly
 // smaller toi, so among equal toi the smaller (bbox distance, item index) wins.

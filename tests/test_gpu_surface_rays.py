@@ -406,3 +406,56 @@ def test_non_finite_rays_are_answered(hip, oracle):
     with hip.DeviceScene(c["fs"], 0) as ds:
         got = ds.surface_rays(o, d, 1)
     assert np.array_equal(_bytes(got[4:]), _bytes(c["got"][4:n]))
+
+
+# ---- 13: frame and queries answer from the same code ----------------------------------------------------------------------------------
+def _mesh_and_ball():
+    """One textured mesh (a checkered floor, bilinear) and one ball over it, under a point light (tests/corner_scenes.py's parts)."""
+    from rustray_amd.flat import FlatScene, Item, Light, Material
+    from tests import corner_scenes as cs
+    fs = FlatScene()
+    base = np.full((8, 8, 4), 255, np.uint8); base[::2, ::2, :3] = 60
+    fs.textures = [base]
+    fs.meshes = [cs._quad(0.0, 4.0)]
+    fm = Material(base_color=(0.9, 0.8, 0.7), ambient_color=(0.1, 0.1, 0.1)); fm.texture[BASE] = 0
+    cs._mesh_item(fs, 0, fm, 3, "floor")
+    mi, ci = cs._mat(fs, Material(base_color=(0.2, 0.7, 0.3), ambient_color=(0.05, 0.1, 0.05)))
+    t = cs.EYE.copy(); t[:3, 3] = (0.5, 1.0, -0.5); ti = cs.EYE.copy(); ti[:3, 3] = (-0.5, -1.0, 0.5)
+    fs.items.append(Item(kind=0, id=6, material=mi, material_cache=ci, radius=1.0, trans=t, trans_inv=ti, bbox_min=(-1.0,) * 3, bbox_max=(1.0,) * 3, name="ball"))
+    fs.lights = [Light(pos=(2.0, 7.0, 3.0), intensity=70.0)]
+    cs._cam(fs, eye=(0.0, 3.0, 6.0), direction=(0.0, -0.35, -1.0))
+    return fs
+
+
+def test_a_frame_and_the_queries_of_its_primary_rays_agree(hip, oracle):
+    """A 16 x 8 frame at 1 sample, max_recursion 0, no fog, and its 128 primary rays rebuilt on the host: the frame's kernels and the
+    queries' evaluate a hit's surface, resolve a slot and seed a root record through the same functions (rr_surface.h's steps,
+    rr_accumulate.h's resolve_*, root_record), so the frame IS the queries' answer -- object id and hit mask, colour bytes, and the
+    depth as the accumulator holds it: round(distance * RR_DEPTH_SCALE) / RR_DEPTH_SCALE with RR_DEPTH_SCALE = 65536 (rr_device.h; one
+    sample, and every distance here is far below the 512 units a 32-bit lane sum takes).  Every pixel is in every comparison."""
+    from tests.helpers import as_u8
+    w, h = 16, 8
+    n = w * h
+    fs = _mesh_and_ball()
+    cam = camera_for(fs, w, h).c_struct()
+    cfg = _cfg()
+    table, _ = oracle.sample_table(1)
+    o, d = primaries(oracle, cam, cfg, table)
+    assert len(o) == n
+    with hip.DeviceScene(fs, 0) as ds:
+        frame = ds.render(cam, cfg, sample_xy=table, aux=True)
+        surf = ds.surface_rays(o, _f32_normalised(d), 1)
+        shade = ds.shade_rays(o, d, cfg, 1)
+    hit = surf["hit"] == 1
+    assert {3, 6} <= set(surf["object_id"][hit].tolist()) and (~hit).any()   # the mesh, the ball and the background are all in the picture
+    assert np.array_equal(surf["object_id"], frame["object_id"].reshape(n))
+    assert np.array_equal(hit, frame["depth"].reshape(n) > 0)
+    c = np.fmin(shade["color"].astype(np.float32), np.float32(1.0)) * np.float32(255.0)   # f32::min: NaN.min(1.0) = 1.0
+    assert c.dtype == np.float32 and c.shape == (n, 3)
+    assert np.array_equal(as_u8(c).astype(np.uint8), frame["rgba"].reshape(n, 4)[:, :3])
+    assert (frame["rgba"].reshape(n, 4)[hit, :3] != 0).any()
+    x = surf["distance"] * np.float32(65536.0)
+    assert x.dtype == np.float32 and float(np.abs(x).max()) < 2.0 ** 25
+    want = (np.rint(x).astype(np.float64) / 65536.0).astype(np.float32)   # v_rndne: to nearest, ties to even, as numpy's rint
+    assert np.array_equal(_bits(frame["depth"].reshape(n)), _bits(want))
+    assert np.array_equal(_bits(shade["depth"]), _bits(want))

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Developer tool: host wall time per call of the three ray queries in their host form (rr_trace_rays, rr_trace_shadow_rays,
-rr_shade_rays: host arrays in, host arrays out) and in their device-buffer form (rr_trace_rays_device, rr_trace_shadow_rays_device,
-rr_shade_rays_device: inputs and outputs resident on the GPU as torch tensors, the call followed by one synchronisation), on ONE
+"""Developer tool: host wall time per call of the four ray queries in their host form (rr_trace_rays, rr_trace_shadow_rays,
+rr_shade_rays, rr_surface_rays: host arrays in, host arrays out) and in their device-buffer form (rr_trace_rays_device,
+rr_trace_shadow_rays_device, rr_shade_rays_device, rr_surface_rays_device: inputs and outputs resident on the GPU as torch tensors,
+the call followed by one synchronisation), on ONE
 handle of scenes/spheres_room and about 1 Mi rays generated once: the primary rays of a 1024 x 1024 pinhole camera at the scene's
-eye, the shadow rays from their hit points to the first point light (limit: the light's distance), and the primaries again as
-radiance rays (one per result, max_recursion 3).  Median and minimum of 7 calls each, after one untimed call of each form.
+eye, the shadow rays from their hit points to the first point light (limit: the light's distance), the primaries again as
+radiance rays (one per result, max_recursion 3) and as surface rays.  Median and minimum of 7 calls each, after one untimed call of each form.
 usage: python tools/query_probe.py [side]      (default: 1024, i.e. 1 048 576 rays)"""
 import ctypes as C
 import os
@@ -56,6 +57,7 @@ def main():
         dev = {k: torch.from_numpy(v).cuda() for k, v in dict(o=o, d=d, so=so, sd=sd, lim=lim).items()}
         out5 = torch.empty((n, 5), dtype=torch.int32, device="cuda")
         out8 = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+        out32 = torch.empty((n, 32), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
 
         def dev_closest():
@@ -70,9 +72,13 @@ def main():
             ds.shade_rays_device(cfg, dev["o"].data_ptr(), dev["d"].data_ptr(), n, 1, None, out8.data_ptr())
             torch.cuda.synchronize()
 
+        def dev_surface():
+            ds.surface_rays_device(dev["o"].data_ptr(), dev["d"].data_ptr(), n, 1, out32.data_ptr())
+            torch.cuda.synchronize()
+
         # the host forms through the C ABI itself, into arrays that exist: no binding work inside the clock
         L, vp = capi.lib(), C.c_void_p
-        h5, h8 = np.zeros((n, 5), np.uint32), np.zeros((n, 8), np.float32)
+        h5, h8, h32 = np.zeros((n, 5), np.uint32), np.zeros((n, 8), np.float32), np.zeros((n, 32), np.float32)
 
         def host_closest():
             capi._check(L.rr_trace_rays(ds._h, vp(o.ctypes.data), vp(d.ctypes.data), n, 1, vp(h5.ctypes.data)))
@@ -84,9 +90,13 @@ def main():
         def host_shade():
             capi._check(L.rr_shade_rays(ds._h, C.byref(cfg), vp(o.ctypes.data), vp(d.ctypes.data), n, 1, None, vp(h8.ctypes.data), None))
 
+        def host_surface():
+            capi._check(L.rr_surface_rays(ds._h, vp(o.ctypes.data), vp(d.ctypes.data), n, 1, vp(h32.ctypes.data)))
+
         rows = (("closest hit", host_closest, dev_closest),
                 ("shadow, limit = the light's distance", host_shadow, dev_shadow),
-                ("radiance, max_recursion 3", host_shade, dev_shade))
+                ("radiance, max_recursion 3", host_shade, dev_shade),
+                ("surface of the closest hit", host_surface, dev_surface))
         print(f"spheres_room, {len(fs.items)} items, {n} rays per call, median (min) of {REPS} calls, host wall time including the final synchronisation")
         for name, host_fn, dev_fn in rows:
             (hm, hl), (dm, dl) = timed(host_fn), timed(dev_fn)
