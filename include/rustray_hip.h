@@ -42,7 +42,8 @@ extern "C" {
  * rr_scene_add_meshes and rr_scene_set_items came later still, in the same way: a version-3 library may lack these two as well.
  * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own), and after them the
  * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device.
- * rr_surface_rays and rr_surface_rays_device (with rr_surface_hit, a struct of its own) came after those, in the same way. */
+ * rr_surface_rays and rr_surface_rays_device (with rr_surface_hit, a struct of its own) came after those, in the same way.
+ * rr_render_pixels and rr_render_pixels_device came after those, again without a change of any struct: a version-3 library may lack the two. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -332,7 +333,7 @@ void rr_scene_destroy(rr_scene* scene);
  * All or nothing, as rr_scene_update_materials: an update that fails (a non-finite matrix anywhere: RR_ERR_INVALID_ARGUMENT;
  * a device or host failure part-way) leaves the scene rendering exactly what it rendered before the call.  Should putting
  * the old scene back fail as well, the scene is marked broken: every frame call (rr_render and its progressive forms,
- * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays) returns RR_ERR_DEVICE and says so in rr_last_error,
+ * rr_render_region_device, rr_render_multi, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays, rr_render_pixels) returns RR_ERR_DEVICE and says so in rr_last_error,
  * until an update of the same kind succeeds. */
 int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float* trans_inv);
 
@@ -344,7 +345,7 @@ int rr_scene_update_transforms(rr_scene* scene, const float* trans, const float*
 int rr_scene_update_materials(rr_scene* scene, const rr_material* materials, uint32_t n_materials);
 
 /* The edits below, like the two above, leave the handle rendering bit for bit what a handle freshly created from the edited flat
- * scene renders (every frame call, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
+ * scene renders (every frame call, rr_pick, rr_trace_rays, rr_trace_shadow_rays, rr_shade_rays, rr_render_pixels, the counters of rr_frame_stats).  Each takes the scene's lock, waits for
  * frames still in flight on the device (rr_render_region_device) before it overwrites what they read, and returns
  * RR_ERR_INVALID_ARGUMENT when called from on_pass of the same scene.  Every handle that takes part in a multi-GPU frame must
  * receive the same edits. */
@@ -644,6 +645,47 @@ typedef struct rr_surface_hit {       /* 128 bytes, eight 16-byte rows */
 int rr_surface_rays(rr_scene* scene, const float* origins, const float* directions, uint32_t n, uint32_t depth, rr_surface_hit* out);
 int rr_surface_rays_device(rr_scene* scene, const float* origins_dev, const float* directions_dev, uint32_t n, uint32_t depth,
                            rr_surface_hit* out_dev, void* hip_stream);
+
+/* Pixels of the frame's own camera, as linear floats: Raytracing::render(x, y) -> PixelData (reference src/raytracing.rs:275-427) for a
+ * list of pixels of the caller's choice or for every pixel of the frame, BEFORE the clamp, the gamma curve and the truncation to bytes
+ * that rr_render applies.  For tone mapping, a denoiser, EXR output, averages over frames of several seeds, compositing; for a crop
+ * window, the part of the screen an edit touched, more samples where a host found noise, the reference's own shuffled 2x2 cells.
+ * The call is a frame: the camera, the sub-sample table (sample_xy or the built-in one), depth of field, the sample groups, the level
+ * walk and the generator are rr_render's, and a pixel's record does not depend on which other pixels the call holds.
+ *   Pixel list: pixel_xy[i] = x | y << 16 with x < width and y < height; out[i] (and rgba8_out + 4 * i) is that pixel.  Duplicates are
+ *   allowed and give equal records; any order is allowed.  List order is slot order: a 64-ray packet of primary rays holds 64 / G
+ *   consecutive entries (G = the frame's sample group, 1 .. 64), so screen neighbours should be list neighbours -- 8x8 blocks, as the
+ *   library orders a whole frame -- or the packets lose their coherence.  A list whose length is no multiple of 64 / G runs with G = 1.
+ *   NULL list: every pixel of the frame; n_pixels must be width * height (else RR_ERR_INVALID_ARGUMENT); pixel (x, y) goes to
+ *   out[y * width + x], and the call is traced in the library's own 8x8-block slot order, as rr_render is.
+ *   out[i]: rr_radiance exactly as rr_shade_rays defines it -- color = (float)(fixed-point sum * 2^-24) / (float)samples, LINEAR, NaN or
+ *   +-inf where a sample's term was; depth; the normalised mean normal (NaN when every sample missed); object_id.  depth, normal and
+ *   object_id are what rr_render writes for the pixel (the three sums are always accumulated here).
+ *   rgba8_out (or NULL): 4 bytes per pixel, the bytes rr_render writes for it: min(., 1), the gamma curve when config->gamma_correction
+ *   is set, truncation, alpha 255.  An output of its own because the device's powf cannot be reproduced on the host; without gamma it
+ *   equals (uint8_t)(fminf(color, 1) * 255) in f32.
+ *   Config: every field is used as a frame uses it (samples, focal_length / aperture_size, fog, seed, monte_carlo, max_recursion);
+ *   gamma_correction affects rgba8_out only.
+ *   Limits and checks: rr_render's for scene, camera, config and table; out == NULL is RR_ERR_INVALID_ARGUMENT; n_pixels == 0 returns
+ *   RR_OK and touches nothing; n_pixels > 2^30 is RR_ERR_UNSUPPORTED before anything is allocated; an entry outside the frame is
+ *   RR_ERR_INVALID_ARGUMENT, rr_last_error names the first such index, and nothing is written to out.  Device memory: 64 B per pixel
+ *   of accumulators and 12 B per list entry, kept by the handle; the host form adds 36 (40 with a list) B per pixel for the call.
+ *   A frame call: the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene, RR_ERR_DEVICE on a broken scene;
+ *   rr_scene_last_stats and rr_scene_overlap_stages report it like a frame (primary_rays = n_pixels * samples).  cancel: as
+ *   rr_shade_rays.  The frames before and after are not affected: the list's slot table is the call's own.
+ * rr_render_pixels_device: the same on DEVICE buffers in stream order, under every rule of rr_shade_rays_device above -- pointers
+ * classified before any launch (RR_ERR_INVALID_ARGUMENT naming the argument), out_dev 16-byte aligned, pixel_xy_dev and rgba8_out_dev
+ * 4-byte aligned; camera, config and sample_xy are host memory.  The call waits inside where a frame waits (its constants, the size of
+ * every depth level) and, with a list, once for 4 bytes: the first index outside the frame.  The list is copied into a buffer of the
+ * handle first, so nothing the launches read after the return is the caller's.  A scene edit or rr_scene_destroy waits for calls in
+ * flight.  Once `hip_stream` is synchronised the buffers hold byte for byte what the host form writes; the host form is this call
+ * behind a staging copy (without a list there is nothing to stage in). */
+int rr_render_pixels(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                     const uint32_t* pixel_xy /* or NULL */, uint32_t n_pixels,
+                     rr_radiance* out, uint8_t* rgba8_out /* or NULL */, const volatile int* cancel);
+int rr_render_pixels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                            const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels,
+                            rr_radiance* out_dev, uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream, const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -448,7 +448,8 @@ private:
     std::string error_;
 };
 
-// reference src/raytracing.rs:205-273: scene + config; the per-pixel `render(x, y)` is replaced by whole frames
+// reference src/raytracing.rs:205-427: scene + config.  A frame is one device call (RendererManager); the per-pixel `render(x, y)` is
+// here too, for one pixel and for lists of pixels (render, render_pixels: rr_render_pixels)
 class Raytracing {
 public:
     std::shared_ptr<DeviceScene> scene;
@@ -496,6 +497,50 @@ public:
         out.resize(n_rays / rays_per_result);
         if (rr_shade_rays(scene->handle(), &c, o.data(), d.data(), (uint32_t)out.size(), rays_per_result, stream_ids, out.data(), nullptr) != RR_OK) out.clear();
         return out;
+    }
+
+    // Raytracing::render(x, y) -> PixelData (src/raytracing.rs:275-427): one pixel of this handle's camera with this handle's config (the
+    // built-in sub-sample table, depth of field, all samples) -- the bytes, normal, depth and id a frame holds for that pixel.  A pixel
+    // outside the frame, or a failed call, gives a default PixelData with x = y = -1 (rr_last_error() says why).  One device call per
+    // pixel: for more than a few, use render_pixels.
+    PixelData render(int x, int y) const {
+        PixelData p;
+        p.x = -1; p.y = -1;
+        if (x < 0 || y < 0 || x > 65535 || y > 65535) return p;
+        const uint32_t xy = (uint32_t)x | ((uint32_t)y << 16);
+        std::vector<uint8_t> bytes;
+        const std::vector<rr_radiance> r = render_pixels(&xy, 1, &bytes);
+        if (r.size() != 1) return p;
+        p.r = bytes[0]; p.g = bytes[1]; p.b = bytes[2];
+        p.normal = Vec3{r[0].normal[0], r[0].normal[1], r[0].normal[2]};
+        p.depth = r[0].depth; p.object_id = r[0].object_id;
+        p.x = x; p.y = y;
+        return p;
+    }
+    // What `render` holds BEFORE its clamp, as linear floats, for n pixels xy[i] = x | y << 16 in any order (list neighbours should be
+    // screen neighbours: 8x8 blocks), or for every pixel of the frame in row-major order when xy is nullptr (n is then ignored).
+    // rgba8 (optional): the frame's own 4 bytes per pixel.  An empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_radiance> render_pixels(const uint32_t* xy, size_t n, std::vector<uint8_t>* rgba8 = nullptr) const {
+        std::vector<rr_radiance> out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        if (!xy) n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 30)) return out;
+        out.resize(n);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_render_pixels(scene->handle(), &cam, &c, nullptr, xy, (uint32_t)n, out.data(), rgba8 ? rgba8->data() : nullptr, nullptr) != RR_OK) {
+            out.clear();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_pixels_device): as shade_device below; xy_dev nullptr = the whole frame
+    // (n_pixels = width * height), rgba8_out_dev optional
+    int render_pixels_device(const uint32_t* xy_dev, uint32_t n_pixels, rr_radiance* out_dev, uint8_t* rgba8_out_dev, void* hip_stream,
+                             const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_pixels_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, out_dev, rgba8_out_dev, hip_stream, cancel);
     }
 
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)

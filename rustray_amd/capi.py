@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -43,7 +43,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
 LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -115,6 +115,10 @@ def lib():
         if hasattr(L, "rr_surface_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
             L.rr_surface_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             L.rr_surface_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_render_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_render_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -132,6 +136,19 @@ def lib():
                                     C.c_void_p, C.c_uint64, C.c_int]
         _LIB = L
     return _LIB
+
+
+def pack_pixels(pixels) -> np.ndarray:
+    """The pixel list of rr_render_pixels: an (n, 2) integer array of (x, y) -> (n,) uint32 of x | y << 16; an (n,) array is taken as packed."""
+    a = np.asarray(pixels)
+    if a.ndim == 2 and a.shape[1] == 2:
+        if len(a) and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("pixel coordinates must lie in 0 .. 65535")
+        a = a.astype(np.uint32)
+        return np.ascontiguousarray(a[:, 0] | (a[:, 1] << np.uint32(16)), np.uint32)
+    if a.ndim != 1:
+        raise ValueError(f"pixels of shape {a.shape}: (n, 2) of (x, y), or (n,) packed x | y << 16")
+    return np.ascontiguousarray(a, np.uint32)
 
 
 def _check(rc: int):
@@ -373,6 +390,33 @@ class DeviceScene:
         out = np.zeros(max(n, 1), SURFACE_HIT_DTYPE)
         _check(lib().rr_surface_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(depth), out.ctypes.data_as(C.c_void_p)))
         return out[:n]
+
+    def render_pixels(self, cam: rr_camera, cfg: rr_config, pixels=None, sample_xy=None, rgba8: bool = False, cancel=None):
+        """rr_render_pixels: Raytracing::render(x, y) before its clamp, for the pixels named in `pixels` -- an (n, 2) integer array of
+        (x, y) or an (n,) uint32 array of x | y << 16, in any order, duplicates allowed -- or for every pixel of the frame in row-major
+        order (None) -> the dict of shade_rays (color LINEAR), plus `rgba` (n, 4) uint8, the frame's own bytes, with rgba8=True."""
+        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
+        if pixels is not None:
+            xy = pack_pixels(pixels)
+            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixels(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), out.ctypes.data_as(C.c_void_p),
+                                      rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+        if rgba8:
+            res["rgba"] = rgba[:n]
+        return res
+
+    def render_pixels_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, out_ptr, rgba8_ptr=None, stream_ptr=None, sample_xy=None, cancel=None):
+        """rr_render_pixels_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels 32-byte
+        rr_radiance records (16-byte aligned) and, optionally, n_pixels x 4 bytes, all raw device pointers; enqueued on `stream_ptr`."""
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixels_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
+                                             C.c_void_p(out_ptr), C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
+                                             C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

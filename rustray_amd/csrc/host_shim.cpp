@@ -187,6 +187,63 @@ extern "C" int rh_shade_device(void* h, const rr_config* cfg, const float* origi
     return rt.shade_device(origins_dev, dirs_dev, n_results, rays_per_result, stream_ids_dev, out_dev, stream);
 }
 
+// Raytracing::render_pixels with the given camera (of a w x h frame) and config: xy NULL = the whole frame (n = w * h); out = n records of 8
+// words (rr_radiance), rgba8 (or NULL) = n x 4 bytes.  rh_render_pixel: Raytracing::render(x, y), out6 = (r, g, b, object id, x, y), nd4 =
+// (normal, depth).  rh_render_pixels_device: Raytracing::render_pixels_device on device buffers.
+static Raytracing& rh_with(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                           uint32_t w, uint32_t hgt) {
+    Raytracing& rt = *((RhScene*)h)->rt;
+    rt.camera = make_camera(fov, eye, up, dir, cnear, cfar);
+    rt.camera.init(w, hgt);
+    rt.config = RaytracingConfig();
+    rt.config.apply(from_c(cfg));
+    rt.config.seed = cfg->seed;
+    return rt;
+}
+extern "C" int rh_render_pixels(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                uint32_t w, uint32_t hgt, const uint32_t* xy, uint32_t n, rr_radiance* out, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.render_pixels(xy, n, rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return (int)r.size();
+}
+extern "C" int rh_render_pixel(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                               uint32_t w, uint32_t hgt, int x, int y, int32_t* out6, float* nd4) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    const PixelData p = rt.render(x, y);
+    out6[0] = p.r; out6[1] = p.g; out6[2] = p.b; out6[3] = (int32_t)p.object_id; out6[4] = p.x; out6[5] = p.y;
+    nd4[0] = p.normal.x; nd4[1] = p.normal.y; nd4[2] = p.normal.z; nd4[3] = p.depth;
+    return p.x < 0 ? -1 : 0;
+}
+extern "C" int rh_render_pixels_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                       uint32_t w, uint32_t hgt, const uint32_t* xy_dev, uint32_t n, rr_radiance* out_dev, uint8_t* rgba8_dev, void* stream,
+                                       const int* cancel) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_pixels_device(xy_dev, n, out_dev, rgba8_dev, stream, cancel);
+}
+// Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
+// [1] = how many of them were refused; returns the frame's rr_status
+extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                             uint32_t w, uint32_t hgt, uint32_t* calls_refused) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    struct Ctx { const Raytracing* rt; uint32_t calls, refused; } ctx{&rt, 0u, 0u};
+    const rr_camera cam = rt.camera.c_struct();
+    const rr_config c = rt.config.c_struct();
+    std::vector<uint8_t> rgba(4 * (size_t)w * hgt);
+    const rr_frame fr{rgba.data(), nullptr, nullptr, nullptr};
+    const int rc = rr_render_progressive(rt.scene->handle(), &cam, &c, nullptr, &fr, 2, [](void* user, uint64_t, uint64_t) -> int {
+        Ctx* x = (Ctx*)user;
+        const uint32_t xy = 0;
+        x->calls++;
+        if (x->rt->render_pixels(&xy, 1).empty() && x->rt->render(0, 0).x < 0) x->refused++;
+        return 0;
+    }, &ctx, nullptr);
+    calls_refused[0] = ctx.calls; calls_refused[1] = ctx.refused;
+    return rc;
+}
+
 // Raytracing::surface over n rays: out = n records of 128 bytes (rr_surface_hit); Raytracing::surface_device: the same on device buffers
 extern "C" int rh_surface_rays(void* h, const float* origins, const float* dirs, uint32_t n, uint32_t depth, rr_surface_hit* out) {
     const Raytracing& rt = *((RhScene*)h)->rt;

@@ -1,12 +1,13 @@
 // rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
 // Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
 //         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
-//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; render_region_locked; rr_render_region_device,
+//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; FrameIo, fill_pixel_slots, render_region_locked
+//         (rr_render_pixels, rr_api_query.h, is its other caller); rr_render_region_device,
 //         rr_render, rr_render_progressive, rr_render_progressive_tiles; rr_scene_last_stats, rr_scene_overlap_stages;
 //         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
 // Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
 //         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h,
-//         rr_primary_setup.h, the frame kernels of rr_kernels.hip.
+//         rr_primary_setup.h, rr_pixel_list.h, the frame kernels of rr_kernels.hip.
 
 // ---------------------------------------------------------------------------
 // frame
@@ -139,6 +140,42 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
     }
     s->frame.region_cached = rg; s->frame.region_w = W; s->frame.region_h = H;
     return RR_OK;
+}
+
+// Where the accumulator slots of a frame come from and how the frame ends, by value (render_region_locked):
+//   slots: a region's map (update_region_map), or `n_pixels` entries x | y << 16 the scene's device can address, entry i = slot i;
+//   end:   k_resolve into the device frame `out` (frame_layout: at the pixel's place in the whole frame, else compact; `hook`: the
+//          progressive preview), or k_resolve_pixels into `radiance` records and, on request, the frame's bytes in `rgba8` -- at the
+//          entry's index for a list, at y * width + x for a region.
+struct FrameIo {
+    const rr_region* region; const uint32_t* pixel_xy; uint32_t n_pixels;
+    const rr_frame* out; bool frame_layout; const PassHook* hook;
+    rr_radiance* radiance; uint8_t* rgba8;
+};
+static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
+    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr};
+}
+
+// The caller's pixel list as the slot table of this call: buffers of the handle's own (pixel_xy, pixel_c), so the launches read nothing
+// of the caller's after the return and the cached region map (region_xy, slot_c, trace_order) is what it was for the next frame.
+// THE wait of a list call: 4 bytes, the first index outside the frame (pinned, h_count[8]); such a call is refused before any walk.
+static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n, hipStream_t st) {
+    HIP_TRY(s->frame.pixel_xy.reserve((size_t)n * 4));
+    HIP_TRY(s->frame.pixel_c.reserve((size_t)n * 8));
+    HIP_TRY(s->frame.pixel_bad.reserve(4));
+    HIP_TRY(hipMemsetAsync(s->frame.pixel_bad.p, 0xff, 4, st));
+    const int grid = (int)std::min<uint64_t>(((uint64_t)n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
+    hipLaunchKernelGGL(k_pixel_slots, dim3(grid), dim3(RR_BLOCK), 0, st, pixel_xy, n, W, H, s->frame.pixel_xy.as<uint32_t>(), s->frame.pixel_c.as<float2>(),
+                       s->frame.pixel_bad.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    uint32_t* h = s->frame.h_count + 8;
+    HIP_TRY(hipMemcpyAsync(h, s->frame.pixel_bad.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t bad = *h;
+    if (bad == RR_PIXEL_LIST_OK) return RR_OK;
+    uint32_t xy = 0; // (the stream is idle: the entry for the message comes with one more small copy)
+    HIP_TRY(hipMemcpy(&xy, s->frame.pixel_xy.as<uint32_t>() + bad, 4, hipMemcpyDeviceToHost));
+    return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, xy & 0xffffu, xy >> 16, W, H);
 }
 
 // the frame constants of a camera and config (n_region_pixels is the caller's)
@@ -297,7 +334,7 @@ struct FrameRun {
     DPrimary pr; // the batch being traced: depth level 1
     const volatile int* cancel;
     int shadow_grid, shade_grid_max;
-    const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, or the stream ids of rr_shade_rays
+    const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, the pixel list of rr_render_pixels, or the stream ids of rr_shade_rays
     bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
@@ -375,7 +412,7 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[b], 0));
         {
             ScopedTimer t(s, st, TK_SHADE, true);
-            hipLaunchKernelGGL(k_shade<true>, dim3((uint32_t)std::min<uint64_t>(groups, shade_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), s->frame.region_xy.as<uint32_t>(),
+            hipLaunchKernelGGL(k_shade<true>, dim3((uint32_t)std::min<uint64_t>(groups, shade_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy,
                                f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
         }
         HIP_TRY(hipGetLastError());
@@ -507,18 +544,21 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
     return RR_OK;
 }
 
-static void launch_resolve(const FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout) {
+static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& io) {
     const uint32_t npix = fr.n_region_pixels;
-    hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(),
-                       f.acc, out->rgba8, out->normal, out->depth, out->object_id, frame_layout ? 1u : 0u);
+    if (io.radiance) hipLaunchKernelGGL(k_resolve_pixels, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
+                                        (float4*)io.radiance, (uint32_t*)io.rgba8);
+    else hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(),
+                            f.acc, io.out->rgba8, io.out->normal, io.out->depth, io.out->object_id, io.frame_layout ? 1u : 0u);
 }
 
 // The frame's batches of primary rays, in order.  After a batch that ends on a whole slice of samples the pass hook
 // (if any) gets the frame resolved over the samples finished so far.
-static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool frame_layout, const PassHook* hook) {
+static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io) {
     rr_scene* s = f.s;
     const uint32_t npix = fr.n_region_pixels;
     const uint64_t B = f.plan.B, total_primary = f.plan.total_primary;
+    const PassHook* hook = io.hook;
     for (uint64_t first = 0; first < total_primary; first += B) {
         if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
         const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
@@ -535,8 +575,8 @@ static int run_batches(FrameRun& f, const DFrame& fr, const rr_frame* out, bool 
         if (hook && hook->fn && done < total_primary && done % npix == 0) {
             DFrame pf = fr;
             pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
-            launch_resolve(f, pf, out, frame_layout);
-            RR_TRY(copy_outputs(*hook->host, *out, (size_t)fr.width * fr.height, f.st));
+            launch_resolve(f, pf, io);
+            RR_TRY(copy_outputs(*hook->host, *io.out, (size_t)fr.width * fr.height, f.st));
             InPass in_pass(s);
             if (hook->fn(hook->user, done, total_primary) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
         }
@@ -558,15 +598,23 @@ static void begin_frame_stats(rr_scene* s) {
 }
 
 static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
-                                const rr_region* rg, const rr_frame* out, bool frame_layout, hipStream_t st, const volatile int* cancel,
-                                const PassHook* hook = nullptr) {
+                                const FrameIo io, hipStream_t st, const volatile int* cancel) {
     RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_TRY(take_stream(s, st));
     const uint32_t W = cam->width, H = cam->height;
     if ((uint64_t)W * H > (1ull << 30)) return fail(RR_ERR_UNSUPPORTED, "frame of %ux%u pixels", W, H);
-    RR_TRY(update_region_map(s, W, H, *rg, st));
-    const uint32_t npix = (uint32_t)s->frame.h_region_xy.size();
+    const PassHook* hook = io.hook;
+    uint32_t npix;
+    const uint32_t* slot_xy; // accumulator slot -> pixel, and the screen point of its centre: the list's own tables or the region's
+    const float* slot_c;
+    if (io.pixel_xy) {
+        RR_TRY(fill_pixel_slots(s, W, H, io.pixel_xy, io.n_pixels, st));
+        npix = io.n_pixels; slot_xy = s->frame.pixel_xy.as<uint32_t>(); slot_c = s->frame.pixel_c.as<float>();
+    } else {
+        RR_TRY(update_region_map(s, W, H, *io.region, st));
+        npix = (uint32_t)s->frame.h_region_xy.size(); slot_xy = s->frame.region_xy.as<uint32_t>(); slot_c = s->frame.slot_c.as<float>();
+    }
     begin_frame_stats(s);
     if (npix == 0) return RR_OK;
     RR_TRY(ensure_camera_reach(s, cam, cfg)); // the top level's boxes must be padded for this camera's distance from the origin
@@ -574,18 +622,19 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     fr.n_region_pixels = npix;
     RR_TRY(upload_sample_table(s, fr, sample_xy, st));
     DAccum acc;
-    RR_TRY(reset_accumulators(s, npix, out->normal != nullptr, out->depth != nullptr, out->object_id != nullptr, st, &acc));
+    const bool radiance = io.radiance != nullptr; // rr_radiance holds all three aux means
+    RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc));
     FramePlan plan;
     RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
-    RR_TRY(upload_shade_const(s, fr, primary_frame(s->frame.slot_c.as<float>(), npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
+    RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
                CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u}, cancel,
                s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = s->frame.region_xy.as<uint32_t>();
+    f.slot_xy = slot_xy;
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
-    RR_TRY(run_batches(f, fr, out, frame_layout, hook));
-    launch_resolve(f, fr, out, frame_layout);
+    RR_TRY(run_batches(f, fr, io));
+    launch_resolve(f, fr, io);
     HIP_TRY(hipEventRecord(s->timing.frame_b, st));
     HIP_TRY(hipGetLastError());
     // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)
@@ -600,7 +649,7 @@ extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const 
     if (!out || !out->rgba8) return fail(RR_ERR_INVALID_ARGUMENT, "out->rgba8 is required");
     RR_TRY(not_in_pass(s, "rr_render_region_device"));
     std::lock_guard<std::mutex> lk(s->mu);
-    return render_region_locked(s, cam, cfg, sample_xy, rg, out, false, (hipStream_t)hip_stream, cancel);
+    return render_region_locked(s, cam, cfg, sample_xy, frame_io(rg, out, false), (hipStream_t)hip_stream, cancel);
 } RR_GUARD_END("rr_render_region_device")
 
 static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
@@ -613,9 +662,9 @@ static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cf
     const size_t np = (size_t)cam->width * cam->height;
     rr_frame dev{};
     RR_TRY(stage_outputs(s, *out, np, false, &dev));
-    rr_region whole{8, 8, 1, 0}; // 8x8 tiles: one wave = one tile of primary rays
+    rr_region whole{8, 8, 1, 0}; // 8x8 tiles: one wave = one tile of primary rays (rr_render_pixels without a list takes the same region: WHOLE_FRAME)
     PassHook hook{fn, user, min_passes, out};
-    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &whole, &dev, true, nullptr, cancel, fn ? &hook : nullptr));
+    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&whole, &dev, true, fn ? &hook : nullptr), nullptr, cancel));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return copy_outputs(*out, dev, np, nullptr);
 }
@@ -692,7 +741,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
     for (uint32_t k = 0; k < P; k++) {
         if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled");
         const rr_region rg{TW, TH, P, k};
-        RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, true, nullptr, cancel));
+        RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&rg, &dev, true), nullptr, cancel));
         HIP_TRY(hipStreamSynchronize(nullptr));
         RR_TRY(collect_stats_locked(s));
         {   // the frame's statistics are the sums over its passes

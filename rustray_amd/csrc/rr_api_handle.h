@@ -64,6 +64,9 @@ struct FrameState {
     // what primary_ray reads (rr_primary_setup.h): slot_c, the screen point of each slot's pixel centre, lives and dies with region_xy;
     // sample_tr, the screen offset of each sample, is uploaded when the sub-sample table or one of the frame constants in tr_key changes
     DevBuf slot_c, sample_tr;
+    // rr_render_pixels with a list: the call's own slot table (the caller's entries and their centres, k_pixel_slots) and the first bad
+    // index; the region's tables and their cache below are not touched, so the frame after a list call finds its map
+    DevBuf pixel_xy, pixel_c, pixel_bad;
     std::vector<uint16_t> tr_table; PrimarySampleKey tr_key{}; bool tr_valid = false;
     std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
     DevBuf tmp_out[4];

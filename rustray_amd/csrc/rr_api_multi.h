@@ -198,7 +198,7 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
                 else { HIP_TRY(s->multi.part[k].reserve(std::max<uint64_t>(count[i], 1) * OUT_ELEM[k])); *devp[k] = s->multi.part[k].p; }
             }
             rr_region rg{TW, TH, n_scenes, i};
-            RR_TRY(render_region_locked(s, cam, cfg, sample_xy, &rg, &dev, false, s->multi.stream, cancel));
+            RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&rg, &dev, false), s->multi.stream, cancel));
             if (i != 0)
                 for (int k = 0; k < 4; k++) {
                     if (!host[k] || !count[i]) continue;

@@ -1,9 +1,10 @@
 // rr_api_query.h — questions to a scene outside a frame: rr_pick, and the closest-hit, shadow, surface and radiance queries for rays of the caller's.
-// Offers: rr_pick; check_query_pointer(s); launch_query_shadow; rr_trace_rays, rr_trace_shadow_rays, rr_surface_rays, rr_shade_rays and
-//         their *_device forms.
+// Offers: rr_pick; check_query_pointer(s); launch_query_shadow; rr_trace_rays, rr_trace_shadow_rays, rr_surface_rays, rr_shade_rays,
+//         rr_render_pixels and their *_device forms.
 // Needs:  rr_api_base.h, rr_api_handle.h (writes rr_scene::query), rr_api_scene.h (ensure_tlas_reach, ensure_camera_reach; reads
 //         rr_scene::data), rr_api_frame.h (launch_trace_closest, take_stream, make_frame; for rr_shade_rays the frame's own level walk:
-//         FrameRun, run_level, upload_shade_const, reset_accumulators, grow_ray_queues, begin_frame_stats), rr_api_multi.h (the peer
+//         FrameRun, run_level, upload_shade_const, reset_accumulators, grow_ray_queues, begin_frame_stats; for rr_render_pixels the whole frame:
+//         check_frame_args, FrameIo, render_region_locked), rr_pixel_list.h, rr_api_multi.h (the peer
 //         access it has enabled: g_peer_mu, g_peer_state), rr_query_pointers.h, rr_frame_plan.h.
 // Borrowed from rr_scene::frame: h_count[4 .. 7] and last_stream by every query (await_reach, take_stream); the arena, the shadow
 // queue, the accumulators and the counter pool by rr_shade_rays (why the next frame does not see it: above shade_rays_locked).
@@ -482,3 +483,80 @@ extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const flo
     return shade_rays_locked(s, cfg, RayIo{origins, directions, stream_ids, out, false}, n_results, rays_per_result, (hipStream_t)hip_stream, cancel);
 } RR_GUARD_END("rr_shade_rays_device")
 
+// ---- pixel queries: rr_render_pixels, Raytracing::render(x, y) (reference src/raytracing.rs:275-427) for pixels of the caller's choice, or for every
+// pixel of the frame, ending in what `render` holds before its clamp (rr_radiance, as rr_shade_rays defines it) and, on request, in the
+// frame's own bytes.  The body is render_region_locked: the frame's batches, level walk, stages and plan; only the slot table
+// (fill_pixel_slots) and the last kernel (k_resolve_pixels) differ.  The device form works on buffers the scene's device can address, in
+// stream order; the host form is the device form behind a staging copy (the list, 32 + 4 B per pixel of answers, the null stream).
+static_assert(sizeof(rr_radiance) == 32, "k_resolve_pixels writes rr_radiance as two float4");
+static const rr_region WHOLE_FRAME{8, 8, 1, 0}; // rr_render's slot order: 8x8 tiles, one wave = one tile of primary rays
+
+// The argument checks of the two entry points; `device`: the alignment rule of the device form.  n_pixels == 0 passes: the caller returns
+// RR_OK before it touches anything.
+static int check_pixels_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                             const uint32_t* pixel_xy, uint32_t n_pixels, const rr_radiance* out, const uint8_t* rgba8) {
+    RR_TRY(check_frame_args(s, cam, cfg, sample_xy));
+    if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "%s: out is required", fn);
+    if (n_pixels > (1u << 30)) return fail(RR_ERR_UNSUPPORTED, "%u pixels in one call", n_pixels);
+    if (n_pixels == 0) return RR_OK;
+    if (!pixel_xy && (uint64_t)n_pixels != (uint64_t)cam->width * cam->height)
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: %u pixels without a list, the frame of %ux%u has %llu", fn, n_pixels, cam->width, cam->height,
+                    (unsigned long long)cam->width * cam->height);
+    if (device && ((((uintptr_t)pixel_xy | (uintptr_t)rgba8) & 3u) || ((uintptr_t)out & 15u)))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: pixel_xy_dev and rgba8_out_dev must be 4-byte aligned and out_dev 16-byte aligned", fn);
+    return RR_OK;
+}
+
+// one call on buffers the device can address (the caller holds the lock); a call that ends early leaves the stream idle
+static int render_pixels_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
+                                uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8, hipStream_t st, const volatile int* cancel) {
+    const int rc = render_region_locked(s, cam, cfg, sample_xy, FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, rgba8}, st, cancel);
+    if (rc != RR_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// (the two entry points of this family share one linkage block; tests/test_pixel_list.py holds each to the guard every entry point has)
+extern "C" {
+int rr_render_pixels_device(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
+                                       uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8_out, void* hip_stream, const volatile int* cancel) try {
+    RR_TRY(check_pixels_args("rr_render_pixels_device", true, s, cam, cfg, sample_xy, pixel_xy, n_pixels, out, rgba8_out));
+    if (n_pixels == 0) return RR_OK;
+    RR_TRY(not_in_pass(s, "rr_render_pixels_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_TRY(check_query_pointers(s, "rr_render_pixels_device", {{pixel_xy, "pixel_xy_dev"}, {out, "out_dev"}, {rgba8_out, "rgba8_out_dev"}}));
+    return render_pixels_locked(s, cam, cfg, sample_xy, pixel_xy, n_pixels, out, rgba8_out, (hipStream_t)hip_stream, cancel);
+} RR_GUARD_END("rr_render_pixels_device")
+
+int rr_render_pixels(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
+                                uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8_out, const volatile int* cancel) try {
+    RR_TRY(check_pixels_args("rr_render_pixels", false, s, cam, cfg, sample_xy, pixel_xy, n_pixels, out, rgba8_out));
+    if (n_pixels == 0) return RR_OK;
+    if (pixel_xy) { // (the body refuses the same entries; here the refusal costs no upload)
+        const uint32_t bad = pixel_list_first_bad(pixel_xy, n_pixels, cam->width, cam->height);
+        if (bad != RR_PIXEL_LIST_OK)
+            return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, pixel_xy[bad] & 0xffffu, pixel_xy[bad] >> 16,
+                        cam->width, cam->height);
+    }
+    RR_TRY(not_in_pass(s, "rr_render_pixels"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    // the staging is the handle's, as rr_render's device frame is (s->frame.tmp_out: grown, kept, used by host forms only, which return with the stream idle): the bytes where
+    // rr_render stages its bytes, the records and the list in the buffers of the next two outputs -- no allocation per call
+    DevBuf &d_rgba = s->frame.tmp_out[0], &d_out = s->frame.tmp_out[1], &d_list = s->frame.tmp_out[2];
+    if (pixel_xy) {
+        HIP_TRY(d_list.reserve(4ull * n_pixels));
+        HIP_TRY(hipMemcpy(d_list.p, pixel_xy, 4ull * n_pixels, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(d_out.reserve(32ull * n_pixels));
+    if (rgba8_out) HIP_TRY(d_rgba.reserve(4ull * n_pixels));
+    RR_TRY(render_pixels_locked(s, cam, cfg, sample_xy, pixel_xy ? d_list.as<uint32_t>() : nullptr, n_pixels, d_out.as<rr_radiance>(),
+                                rgba8_out ? d_rgba.as<uint8_t>() : nullptr, nullptr, cancel));
+    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, d_rgba.p, 4ull * n_pixels, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.p, 32ull * n_pixels, hipMemcpyDeviceToHost)); // waits for the launches: `out` is written by a finished call only
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return RR_OK;
+} RR_GUARD_END("rr_render_pixels")
+} // extern "C"

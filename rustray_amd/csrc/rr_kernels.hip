@@ -921,6 +921,22 @@ __global__ __launch_bounds__(RR_BLOCK) void k_bin_scatter(DRayQueue src, DRayQue
 // ---------------------------------------------------------------------------
 // kernel 5: resolve accumulators into PixelData (reference src/raytracing.rs:406-426)
 // ---------------------------------------------------------------------------
+// The four bytes of a frame's pixel from the resolved, unclamped colour (:410-424): f32::min (NaN.min(1.0) = 1.0), the gamma curve when
+// the config asks for it, truncation to u8, alpha 255.  k_resolve and k_resolve_pixels both write what this returns.
+RR_DEV uint32_t frame_bytes(const float* color, uint32_t gamma) {
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = rs_min(color[k], 1.0f);
+    uint32_t r, g, b;
+    if (gamma) {
+        const float ig = 1.0f / 2.2f;
+        r = as_u8(powf(c[0], ig) * 255.0f); g = as_u8(powf(c[1], ig) * 255.0f); b = as_u8(powf(c[2], ig) * 255.0f);
+    } else {
+        r = as_u8(c[0] * 255.0f); g = as_u8(c[1] * 255.0f); b = as_u8(c[2] * 255.0f);
+    }
+    return r | (g << 8) | (b << 16) | (255u << 24);
+}
+
 __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t* __restrict__ slot_xy,
                                                       const uint32_t* __restrict__ slot_out, DAccum acc,
                                                       uint8_t* rgba8, float* normal, float* depth, uint32_t* object_id,
@@ -934,15 +950,8 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t*
     const uint32_t nf = acc.flags[p];
     float c[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = rs_min(resolve_color(acc, p, nf, k, n), 1.0f); // f32::min: NaN.min(1.0) = 1.0
-    uint32_t r, g, b;
-    if (fr.gamma) {
-        const float ig = 1.0f / 2.2f;
-        r = as_u8(powf(c[0], ig) * 255.0f); g = as_u8(powf(c[1], ig) * 255.0f); b = as_u8(powf(c[2], ig) * 255.0f);
-    } else {
-        r = as_u8(c[0] * 255.0f); g = as_u8(c[1] * 255.0f); b = as_u8(c[2] * 255.0f);
-    }
-    ((uint32_t*)rgba8)[o] = r | (g << 8) | (b << 16) | (255u << 24);
+    for (int k = 0; k < 3; k++) c[k] = resolve_color(acc, p, nf, k, n);
+    ((uint32_t*)rgba8)[o] = frame_bytes(c, fr.gamma);
     if (normal && acc.normal) {
         const f3 nn = resolve_normal(acc, p, nf, n);
         normal[3ull * o] = nn.x; normal[3ull * o + 1] = nn.y; normal[3ull * o + 2] = nn.z;
@@ -985,6 +994,52 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t 
     const float depth = resolve_depth(acc, p, nf, ns);
     out[2ull * i] = make_float4(c[0], c[1], c[2], depth);
     out[2ull * i + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
+}
+
+// ---------------------------------------------------------------------------
+// kernels 5i, 5j: the frame's camera for pixels of the caller's choice, ending in floats (rr_render_pixels)
+// ---------------------------------------------------------------------------
+// 5i: the caller's pixel list on the device -> the handle's slot table: entry i becomes accumulator slot i (slot_xy[i], and its centre
+// slot_c[i] = pixel_centre, rr_pixel_list.h: what primary_slot_centres writes for a region's slot).  One entry per lane, grid-stride:
+// a wave instruction reads 256 consecutive bytes and writes 256 and 512.  *first_bad: the first index whose pixel lies outside the
+// frame (the host presets 0xffffffff); one atomicMin per wave that has one to report, as reach_merge does for the limits.  Such an
+// entry is copied like any other -- its centre is plain arithmetic -- and the host refuses the call before a walk reads the table.
+__global__ __launch_bounds__(RR_BLOCK) void k_pixel_slots(const uint32_t* __restrict__ pixel_xy, uint32_t n, uint32_t width, uint32_t height,
+                                                          uint32_t* __restrict__ slot_xy, float2* __restrict__ slot_c, uint32_t* __restrict__ first_bad) {
+    const float w = (float)width, h = (float)height;
+    uint32_t bad = 0xffffffffu;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * RR_BLOCK) {
+        const uint32_t xy = pixel_xy[i];
+        if (!pixel_in_frame(xy, width, height)) bad = min(bad, (uint32_t)i);
+        float2 c;
+        pixel_centre(xy, w, h, &c.x, &c.y);
+        slot_xy[i] = xy;
+        slot_c[i] = c;
+    }
+#pragma unroll
+    for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
+    if ((threadIdx.x & (RR_WAVE - 1)) == 0u && bad != 0xffffffffu) atomicMin(first_bad, bad);
+}
+
+// 5j: what k_resolve computes BEFORE its clamp, per accumulator slot of a frame, as k_resolve_rays writes it (two float4 = rr_radiance),
+// and on request the frame's own bytes of the pixel next to it (frame_bytes: the device's powf is not the host's).  Record index:
+// the slot itself for a pixel list (out[i] is list entry i), y * width + x of the slot's pixel for a whole frame (from_xy).
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixels(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, uint32_t from_xy,
+                                                             float4* __restrict__ out, uint32_t* __restrict__ rgba8) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
+    if (p >= fr.n_region_pixels) return;
+    uint32_t o = p;
+    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
+    const float n = (float)fr.samples;
+    const uint32_t nf = acc.flags[p];
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = resolve_color(acc, p, nf, k, n);
+    const f3 nn = resolve_normal(acc, p, nf, n);
+    const float depth = resolve_depth(acc, p, nf, n);
+    out[2ull * o] = make_float4(c[0], c[1], c[2], depth);
+    out[2ull * o + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
+    if (rgba8) rgba8[o] = frame_bytes(c, fr.gamma);
 }
 
 // ---------------------------------------------------------------------------

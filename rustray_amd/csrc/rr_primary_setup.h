@@ -15,6 +15,7 @@
 #else
 #define RR_SETUP_HD inline
 #endif
+#include "rr_pixel_list.h" // pixel_centre: the centre of one packed pixel, also what k_pixel_slots evaluates per list entry
 
 // ---- exact division by a run-time constant --------------------------------------------------------------------------------
 // q = n / d as one multiply-high, a shift and at most one add (Granlund & Montgomery, "Division by invariant integers using
@@ -137,9 +138,5 @@ inline void primary_sample_offsets(const uint16_t* sample_xy, const PrimarySampl
 // ---- per-slot centres: slot_c[j] = (cx, cy) of the pixel slot_xy[j] = x | y << 16 ------------------------------------------
 inline void primary_slot_centres(const uint32_t* slot_xy, size_t n, uint32_t width, uint32_t height, float* out) {
     const float w = (float)width, h = (float)height;
-    for (size_t j = 0; j < n; j++) {
-        const float x_f = (float)(slot_xy[j] & 0xffffu), y_f = (float)(slot_xy[j] >> 16);
-        out[2 * j] = ((x_f + 0.5f) / w) * 2.0f - 1.0f;
-        out[2 * j + 1] = 1.0f - ((y_f + 0.5f) / h) * 2.0f;
-    }
+    for (size_t j = 0; j < n; j++) pixel_centre(slot_xy[j], w, h, &out[2 * j], &out[2 * j + 1]);
 }

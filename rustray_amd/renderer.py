@@ -153,6 +153,12 @@ class Raytracing:
         """All pixels of `Raytracing::render(x, y)` (src/raytracing.rs:275-427) in one call."""
         return self.device_scene.render(self.camera.c_struct(), self.config, sample_xy=sample_xy, aux=aux)
 
+    def render_pixels(self, pixels=None, rgba8: bool = False, sample_xy=None) -> dict:
+        """`Raytracing::render(x, y)` before its clamp, as linear floats (rr_render_pixels): for `pixels`, an (n, 2) array of (x, y) or
+        an (n,) uint32 array of x | y << 16, or for the whole frame in row-major order (None) -> dict(color, depth, normal, object_id
+        [, rgba: the frame's own bytes])."""
+        return self.device_scene.render_pixels(self.camera.c_struct(), self.config, pixels=pixels, sample_xy=sample_xy, rgba8=rgba8)
+
     def pick(self, x: int, y: int):
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
@@ -618,3 +624,27 @@ def shade_rays_torch(device_scene: capi.DeviceScene, origins, directions, cfg: r
             device_scene.shade_rays_device(cfg, o.data_ptr(), d.data_ptr(), n, rpr, ids.data_ptr() if ids is not None else None, rec.data_ptr(),
                                            torch.cuda.current_stream(dev).cuda_stream)
     return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7]}
+
+
+def render_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, sample_xy=None, rgba8: bool = False) -> dict:
+    """rr_render_pixels_device on torch's current stream: `pixels` holds n entries x | y << 16 as a contiguous int32 or uint32 CUDA tensor of
+    shape (n,) (the 32 bits are the entry), or None for every pixel of the frame in row-major order.  Returns torch tensors, without a
+    host copy and without a synchronisation of the results: dict(records (n, 8) float32, color (n, 3) LINEAR, depth, normal (n, 3),
+    object_id (int32 view)), views of `records`, and with rgba8=True rgba (n, 4) uint8, the frame's own bytes."""
+    import torch
+    n, xy = int(cam.width) * int(cam.height), None
+    if pixels is not None:
+        dtype = torch.int32 if not isinstance(pixels, torch.Tensor) or pixels.dtype != getattr(torch, "uint32", None) else pixels.dtype
+        xy = _ray_tensor(device_scene, pixels, "pixels", shape_tail=(), dtype=dtype)
+        n = int(xy.shape[0])
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        if n:
+            device_scene.render_pixels_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
+                                              torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
+    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7]}
+    if rgba8:
+        out["rgba"] = rgba
+    return out
