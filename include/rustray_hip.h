@@ -43,7 +43,8 @@ extern "C" {
  * So did rr_trace_shadow_rays and rr_shade_rays (with rr_shadow_hit and rr_radiance, structs of their own), and after them the
  * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device.
  * rr_surface_rays and rr_surface_rays_device (with rr_surface_hit, a struct of its own) came after those, in the same way.
- * rr_render_pixels and rr_render_pixels_device came after those, again without a change of any struct: a version-3 library may lack the two. */
+ * rr_render_pixels and rr_render_pixels_device came after those, again without a change of any struct: a version-3 library may lack the two.
+ * rr_render_pixel_parts and rr_render_pixel_parts_device came after those in the same way: a version-3 library may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -686,6 +687,44 @@ int rr_render_pixels(rr_scene* scene, const rr_camera* camera, const rr_config* 
 int rr_render_pixels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
                             const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels,
                             rr_radiance* out_dev, uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream, const volatile int* cancel);
+
+/* A pixel's samples as K interleaved means next to its full record: what a host needs to FIND noise (the half-buffer error estimate
+ * |A - B| / 2 at K = 2), to reject fireflies (median of means), or to see every single sample of a pixel (K = samples <= 64).  The rays
+ * are exactly those of rr_render_pixels for the same arguments; only where their terms are summed differs.
+ *   Subsets: with S = config->samples and K = n_parts, part h of a pixel is the samples {s : s mod K == h} of the frame's S samples.
+ *   s is the frame's sample index: the row of the sub-sample table, the `sample` key of the generator, the index the object-id rule
+ *   looks at.  Nothing about a sample changes because it is in a part.
+ *   parts_out[i * K + h]: an rr_radiance over the part's S / K samples -- color[c] = (float)(fixed-point sum of the part's terms * 2^-24)
+ *   / (float)(S / K), NaN or +-inf where a term of THAT part was; depth and normal resolved the same way over the part's samples (the
+ *   normal normalised, NaN when every sample of the part missed); object_id is the pixel's id, out[i].object_id, in every part.
+ *   out[i]: byte for byte the record rr_render_pixels writes for that pixel under the same handle state, camera, config and table.  It
+ *   is formed from the sum of the parts' integer sums and the OR of their flags; integer adds commute, so this is exact.  Required, as
+ *   parts_out is (NULL: RR_ERR_INVALID_ARGUMENT).
+ *   n_parts: a power of two from 2 to 64 that divides samples; anything else is RR_ERR_INVALID_ARGUMENT and rr_last_error says which
+ *   rule failed.  n_pixels * n_parts > 2^30 is RR_ERR_UNSUPPORTED before anything is allocated.
+ *   Everything else is rr_render_pixels': the list form and the NULL list for the whole frame (n_pixels == width * height; pixel (x, y)
+ *   at out[y * width + x] and parts_out[(y * width + x) * K + h]); duplicates and any order; an entry outside the frame refused naming
+ *   its index with nothing written; n_pixels == 0 returns RR_OK and touches nothing; a frame call (the scene's lock, refused from
+ *   on_pass, RR_ERR_DEVICE on a broken scene); rr_scene_last_stats gives primary_rays = n_pixels * samples and all four work counters
+ *   equal those of rr_render_pixels for the same pixels; cancel; the frames before and after are not affected.
+ *   Device memory: 64 * K B per pixel of accumulators and 12 * K B per list entry (a whole frame counts as a list here), kept by the
+ *   handle; the host form adds 32 + 32 * K (with a list 36 + 32 * K) B per pixel, kept by the handle as well.
+ *   Sample groups: the call runs as n_pixels * K accumulator slots of S / K samples each, the K slots of an entry side by side.  A
+ *   64-ray packet holds 64 / G consecutive slots, so G is the largest power of two that divides S / K (at most 64) for which
+ *   n_pixels * K is a multiple of 64 / G; where there is none the call runs with G = 1.  K = S leaves one sample per slot: G = 1.  A
+ *   list padded to a multiple of 64 entries keeps its group for every K.
+ * rr_render_pixel_parts_device: the same on DEVICE buffers in stream order, under every rule of rr_render_pixels_device: pointers
+ * classified before any launch, out_dev and parts_out_dev 16-byte aligned, pixel_xy_dev 4-byte aligned, the list copied into a buffer
+ * of the handle, the call waits where a frame waits and once for the 4 bytes of the list check.  Once `hip_stream` is synchronised
+ * the buffers hold byte for byte what the host form writes; the host form is this call behind a staging copy.
+ * There is no byte output: bytes are rr_render_pixels' business. */
+int rr_render_pixel_parts(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                          const uint32_t* pixel_xy /* or NULL */, uint32_t n_pixels, uint32_t n_parts,
+                          rr_radiance* out /* n_pixels */, rr_radiance* parts_out /* n_pixels * n_parts */, const volatile int* cancel);
+int rr_render_pixel_parts_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                                 const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels, uint32_t n_parts,
+                                 rr_radiance* out_dev /* n_pixels */, rr_radiance* parts_out_dev /* n_pixels * n_parts */, void* hip_stream,
+                                 const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

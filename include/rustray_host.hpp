@@ -543,6 +543,33 @@ public:
         return rr_render_pixels_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, out_dev, rgba8_out_dev, hip_stream, cancel);
     }
 
+    // render_pixels, and per pixel the means over its n_parts interleaved sample subsets (rr_render_pixel_parts): part h of a pixel is
+    // the samples s of config.samples with s % n_parts == h.  n_parts: a power of two from 2 to 64 that divides config.samples.  Returns
+    // the full records (byte for byte render_pixels') and fills parts[i * n_parts + h].  Both empty = refused or failed (rr_last_error()
+    // says why).  At n_parts = 2, |A - B| / 2 of a pixel's two part colours estimates the error of its mean.
+    std::vector<rr_radiance> render_pixel_parts(const uint32_t* xy, size_t n, uint32_t n_parts, std::vector<rr_radiance>* parts) const {
+        std::vector<rr_radiance> out;
+        if (parts) parts->clear();
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        if (!xy) n = (size_t)cam.width * cam.height;
+        if (!parts || n == 0 || n_parts == 0 || n_parts > 64 || n * n_parts > ((size_t)1 << 30)) return out;
+        out.resize(n);
+        parts->resize(n * n_parts);
+        if (rr_render_pixel_parts(scene->handle(), &cam, &c, nullptr, xy, (uint32_t)n, n_parts, out.data(), parts->data(), nullptr) != RR_OK) {
+            out.clear();
+            parts->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_pixel_parts_device): xy_dev nullptr = the whole frame (n_pixels = width * height)
+    int render_pixel_parts_device(const uint32_t* xy_dev, uint32_t n_pixels, uint32_t n_parts, rr_radiance* out_dev, rr_radiance* parts_out_dev,
+                                  void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_pixel_parts_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, n_parts, out_dev, parts_out_dev, hip_stream, cancel);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -42,7 +42,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -119,6 +119,11 @@ def lib():
             L.rr_render_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rr_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_render_pixel_parts") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_render_pixel_parts.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+            L.rr_render_pixel_parts_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -417,6 +422,36 @@ class DeviceScene:
         _check(lib().rr_render_pixels_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
                                              C.c_void_p(out_ptr), C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
                                              C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+
+    def render_pixel_parts(self, cam: rr_camera, cfg: rr_config, pixels=None, n_parts: int = 2, sample_xy=None, cancel=None):
+        """rr_render_pixel_parts: the pixels of render_pixels (a list, or None for the whole frame in row-major order) and, per pixel, the
+        means over its n_parts interleaved sample subsets (part h = the samples s with s % n_parts == h) -> the dict of render_pixels
+        plus parts = dict(color (n, K, 3) LINEAR, depth (n, K), normal (n, K, 3))."""
+        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
+        if pixels is not None:
+            xy = pack_pixels(pixels)
+            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        K = int(n_parts)
+        if K < 0 or K > 0xffffffff:
+            raise ValueError(f"n_parts {n_parts}")
+        out = np.zeros((max(n, 1), 8), np.float32)
+        parts = np.zeros((max(n, 1), max(min(K, 64), 1), 8), np.float32)
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_parts(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(K), out.ctypes.data_as(C.c_void_p),
+                                           parts.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
+        out, parts = out[:n], parts[:n]
+        return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
+                    parts=dict(color=parts[:, :, 0:3].copy(), depth=parts[:, :, 3].copy(), normal=parts[:, :, 4:7].copy(),
+                               object_id=parts[:, :, 7].copy().view(np.uint32)))
+
+    def render_pixel_parts_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, n_parts: int, out_ptr, parts_ptr, stream_ptr=None,
+                                  sample_xy=None, cancel=None):
+        """rr_render_pixel_parts_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels and
+        n_pixels * n_parts 32-byte rr_radiance records (both 16-byte aligned), all raw device pointers; enqueued on `stream_ptr`."""
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_parts_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
+                                                  C.c_uint32(n_parts), C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(parts_ptr) if parts_ptr else None,
+                                                  C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

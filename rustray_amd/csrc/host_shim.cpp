@@ -223,6 +223,23 @@ extern "C" int rh_render_pixels_device(void* h, float fov, const float* eye, con
                                        const int* cancel) {
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_pixels_device(xy_dev, n, out_dev, rgba8_dev, stream, cancel);
 }
+// Raytracing::render_pixel_parts: as rh_render_pixels, with parts = n * n_parts records; returns n, or -1 when the call was refused.
+// rh_render_pixel_parts_device: Raytracing::render_pixel_parts_device on device buffers, the rr_status as it is.
+extern "C" int rh_render_pixel_parts(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                     uint32_t w, uint32_t hgt, const uint32_t* xy, uint32_t n, uint32_t n_parts, rr_radiance* out, rr_radiance* parts) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> p;
+    const std::vector<rr_radiance> r = rt.render_pixel_parts(xy, n, n_parts, &p);
+    if (r.empty() || p.size() != r.size() * n_parts) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    std::memcpy(parts, p.data(), p.size() * sizeof(rr_radiance));
+    return (int)r.size();
+}
+extern "C" int rh_render_pixel_parts_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                            uint32_t w, uint32_t hgt, const uint32_t* xy_dev, uint32_t n, uint32_t n_parts, rr_radiance* out_dev,
+                                            rr_radiance* parts_dev, void* stream, const int* cancel) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_pixel_parts_device(xy_dev, n, n_parts, out_dev, parts_dev, stream, cancel);
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -2,7 +2,7 @@
 // over samples (src/raytracing.rs:400-417).  Integer adds commute, so the frame does not depend on the order of anything.
 //
 // Offers: to_fix, fix_add, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged (the last three must be
-// called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth.  wave_merge_runs /
+// called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms).  wave_merge_runs /
 // wave_merge_runs32 / fits25i are this layer's own, and so are its DPP macros (RR_DPP_*, RR_SEG_STEP, RR_SEG_STEP32),
 // un-defined at the end.
 // Needs: rr_device.h (DAccum, RR_NF_*), rr_math.h.
@@ -146,8 +146,9 @@ RR_DEV void accum_depth_wide_merged(const DAccum& acc, uint32_t pix, long long d
 // `nf`: the slot's acc.flags word; `n`: the number of samples as a float
 // ---------------------------------------------------------------------------
 RR_DEV float from_fix(long long sum) { return (float)((double)sum * (1.0 / 16777216.0)); } // RR_FIX_SCALE
-RR_DEV float resolve_color(const DAccum& acc, uint32_t p, uint32_t nf, int k, float n) { // channel k
-    float sum = from_fix(acc.rgb[(unsigned long long)k * acc.n + p]);
+// (the *_sum forms take the slot's integer sums themselves: k_resolve_pixel_parts resolves sums it formed across lanes)
+RR_DEV float resolve_color_sum(long long fix, uint32_t nf, int k, float n) { // channel k
+    float sum = from_fix(fix);
     // what the reference's f32 sum would hold if a sample was not finite: NaN (also +inf + -inf) or +-inf
     const bool pinf = (nf >> (3 + k)) & 1u, ninf = (nf >> (6 + k)) & 1u;
     if (((nf >> k) & 1u) || (pinf && ninf)) sum = __builtin_nanf("");
@@ -155,8 +156,11 @@ RR_DEV float resolve_color(const DAccum& acc, uint32_t p, uint32_t nf, int k, fl
     else if (ninf) sum = -__builtin_inff();
     return sum / n;
 }
-RR_DEV f3 resolve_normal(const DAccum& acc, uint32_t p, uint32_t nf, float n) {
-    f3 nn = mk3(from_fix(acc.normal[p]) / n, from_fix(acc.normal[acc.n + p]) / n, from_fix(acc.normal[2ull * acc.n + p]) / n);
+RR_DEV float resolve_color(const DAccum& acc, uint32_t p, uint32_t nf, int k, float n) { // channel k
+    return resolve_color_sum(acc.rgb[(unsigned long long)k * acc.n + p], nf, k, n);
+}
+RR_DEV f3 resolve_normal_sum(long long fx, long long fy, long long fz, uint32_t nf, float n) {
+    f3 nn = mk3(from_fix(fx) / n, from_fix(fy) / n, from_fix(fz) / n);
     if (nf & (RR_NF_NORMAL_NAN * 7u)) { // a NaN sample normal poisons its component, and through the norm all three
         if (nf & RR_NF_NORMAL_NAN) nn.x = __builtin_nanf("");
         if (nf & (RR_NF_NORMAL_NAN << 1)) nn.y = __builtin_nanf("");
@@ -164,9 +168,13 @@ RR_DEV f3 resolve_normal(const DAccum& acc, uint32_t p, uint32_t nf, float n) {
     }
     return normalize3(nn); // 0/0 = NaN where every ray missed, as in the reference (:426)
 }
-RR_DEV float resolve_depth(const DAccum& acc, uint32_t p, uint32_t nf, float n) {
-    return (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)acc.depth[p] * (1.0 / 65536.0)) / n; // RR_DEPTH_SCALE
+RR_DEV f3 resolve_normal(const DAccum& acc, uint32_t p, uint32_t nf, float n) {
+    return resolve_normal_sum(acc.normal[p], acc.normal[acc.n + p], acc.normal[2ull * acc.n + p], nf, n);
 }
+RR_DEV float resolve_depth_sum(long long fix, uint32_t nf, float n) {
+    return (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)fix * (1.0 / 65536.0)) / n; // RR_DEPTH_SCALE
+}
+RR_DEV float resolve_depth(const DAccum& acc, uint32_t p, uint32_t nf, float n) { return resolve_depth_sum(acc.depth[p], nf, n); }
 
 #undef RR_DPP_SHR
 #undef RR_DPP_SHL

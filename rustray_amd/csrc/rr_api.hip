@@ -49,4 +49,5 @@
 #include "rr_api_multi.h"    // one frame on several devices; the gather maps
 #include "rr_api_post.h"     // post-processing
 #include "rr_api_query.h"    // rr_pick; closest-hit, shadow, surface and radiance queries
+#include "rr_api_parts.h"    // rr_render_pixel_parts: a pixel's samples as K interleaved means
 #include "rr_api_probe.h"    // device arithmetic probe, developer counters

@@ -151,21 +151,26 @@ struct FrameIo {
     const rr_region* region; const uint32_t* pixel_xy; uint32_t n_pixels;
     const rr_frame* out; bool frame_layout; const PassHook* hook;
     rr_radiance* radiance; uint8_t* rgba8;
+    // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i, ending in
+    // k_resolve_pixel_parts: `parts` gets the K part records of every pixel, `radiance` the pixel's full record
+    uint32_t lg_parts; rr_radiance* parts;
 };
 static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
-    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr};
+    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr, 0u, nullptr};
 }
 
 // The caller's pixel list as the slot table of this call: buffers of the handle's own (pixel_xy, pixel_c), so the launches read nothing
 // of the caller's after the return and the cached region map (region_xy, slot_c, trace_order) is what it was for the next frame.
 // THE wait of a list call: 4 bytes, the first index outside the frame (pinned, h_count[8]); such a call is refused before any walk.
-static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n, hipStream_t st) {
+// With parts every entry becomes 2^lg_parts slots (k_pixel_slots); `pixel_xy` may then be the region's own map (the whole frame in parts).
+static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n_entries, uint32_t lg_parts, hipStream_t st) {
+    const uint64_t n = (uint64_t)n_entries << lg_parts; // slots
     HIP_TRY(s->frame.pixel_xy.reserve((size_t)n * 4));
     HIP_TRY(s->frame.pixel_c.reserve((size_t)n * 8));
     HIP_TRY(s->frame.pixel_bad.reserve(4));
     HIP_TRY(hipMemsetAsync(s->frame.pixel_bad.p, 0xff, 4, st));
-    const int grid = (int)std::min<uint64_t>(((uint64_t)n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
-    hipLaunchKernelGGL(k_pixel_slots, dim3(grid), dim3(RR_BLOCK), 0, st, pixel_xy, n, W, H, s->frame.pixel_xy.as<uint32_t>(), s->frame.pixel_c.as<float2>(),
+    const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
+    hipLaunchKernelGGL(k_pixel_slots, dim3(grid), dim3(RR_BLOCK), 0, st, pixel_xy, n_entries, lg_parts, W, H, s->frame.pixel_xy.as<uint32_t>(), s->frame.pixel_c.as<float2>(),
                        s->frame.pixel_bad.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     uint32_t* h = s->frame.h_count + 8;
@@ -174,7 +179,7 @@ static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t*
     const uint32_t bad = *h;
     if (bad == RR_PIXEL_LIST_OK) return RR_OK;
     uint32_t xy = 0; // (the stream is idle: the entry for the message comes with one more small copy)
-    HIP_TRY(hipMemcpy(&xy, s->frame.pixel_xy.as<uint32_t>() + bad, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&xy, s->frame.pixel_xy.as<uint32_t>() + ((size_t)bad << lg_parts), 4, hipMemcpyDeviceToHost));
     return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, xy & 0xffffu, xy >> 16, W, H);
 }
 
@@ -546,7 +551,9 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
 
 static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& io) {
     const uint32_t npix = fr.n_region_pixels;
-    if (io.radiance) hipLaunchKernelGGL(k_resolve_pixels, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
+    if (io.parts) hipLaunchKernelGGL(k_resolve_pixel_parts, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, io.pixel_xy ? 0u : 1u,
+                                     (float4*)io.radiance, (float4*)io.parts);
+    else if (io.radiance) hipLaunchKernelGGL(k_resolve_pixels, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
                                         (float4*)io.radiance, (uint32_t*)io.rgba8);
     else hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(),
                             f.acc, io.out->rgba8, io.out->normal, io.out->depth, io.out->object_id, io.frame_layout ? 1u : 0u);
@@ -609,11 +616,15 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     const uint32_t* slot_xy; // accumulator slot -> pixel, and the screen point of its centre: the list's own tables or the region's
     const float* slot_c;
     if (io.pixel_xy) {
-        RR_TRY(fill_pixel_slots(s, W, H, io.pixel_xy, io.n_pixels, st));
-        npix = io.n_pixels; slot_xy = s->frame.pixel_xy.as<uint32_t>(); slot_c = s->frame.pixel_c.as<float>();
+        RR_TRY(fill_pixel_slots(s, W, H, io.pixel_xy, io.n_pixels, io.lg_parts, st));
+        npix = io.n_pixels << io.lg_parts; slot_xy = s->frame.pixel_xy.as<uint32_t>(); slot_c = s->frame.pixel_c.as<float>();
     } else {
         RR_TRY(update_region_map(s, W, H, *io.region, st));
         npix = (uint32_t)s->frame.h_region_xy.size(); slot_xy = s->frame.region_xy.as<uint32_t>(); slot_c = s->frame.slot_c.as<float>();
+        if (io.lg_parts && npix) { // the region's slots, in their order, as the entries of a list: K slots each, in the list's own tables
+            RR_TRY(fill_pixel_slots(s, W, H, slot_xy, npix, io.lg_parts, st));
+            npix <<= io.lg_parts; slot_xy = s->frame.pixel_xy.as<uint32_t>(); slot_c = s->frame.pixel_c.as<float>();
+        }
     }
     begin_frame_stats(s);
     if (npix == 0) return RR_OK;
@@ -625,10 +636,12 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     const bool radiance = io.radiance != nullptr; // rr_radiance holds all three aux means
     RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc));
     FramePlan plan;
-    RR_TRY(plan_queues(s, npix, cfg, hook ? hook->min_passes : 0u, &plan));
+    rr_config plan_cfg = *cfg; // with parts the plan sees K x the slots and 1 / K of the samples; the frame constants keep the frame's S
+    plan_cfg.samples = (decltype(plan_cfg.samples))(cfg->samples >> io.lg_parts);
+    RR_TRY(plan_queues(s, npix, &plan_cfg, hook ? hook->min_passes : 0u, &plan));
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u}, cancel,
+               CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, cancel,
                s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                s->n_cus * RR_SHADE_GRID_WG};
     f.slot_xy = slot_xy;

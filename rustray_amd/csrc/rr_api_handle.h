@@ -70,6 +70,7 @@ struct FrameState {
     std::vector<uint16_t> tr_table; PrimarySampleKey tr_key{}; bool tr_valid = false;
     std::vector<DevBuf> pool_more; // further segments of per-batch counters, for batches with very many launches (kept for the next frame)
     DevBuf tmp_out[4];
+    DevBuf tmp_parts; // rr_render_pixel_parts, host form: the part records on the device (32 B per pixel and part)
     std::vector<uint32_t> h_region_xy;
     rr_region region_cached{0, 0, 0, 0};
     uint32_t region_w = 0, region_h = 0;

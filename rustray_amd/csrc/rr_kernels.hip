@@ -129,11 +129,12 @@ struct DPrimary {
     const float* sample_tr; // (x_trans, y_trans) per sample: primary_sample_offsets
     PrimaryLaunch at;       // where the batch starts and how its packets are grouped
     uint32_t n;             // primary rays in the batch
+    uint32_t lg_parts;      // log2 of the accumulator slots per pixel: 0 but for rr_render_pixel_parts (primary_part_sample)
 };
 RR_DEV void primary_ray(const DFrame& fr, const PrimaryFrame& pf, const DPrimary& pr, uint32_t i,
                         f3* origin_out, f3* dir_out, uint32_t* pix_out, uint32_t* sample_out) {
     uint32_t pix, s; // accumulator slot (slots enumerate 8x8 blocks of the region's tiles) and sample
-    primary_index(pf, pr.at, i, &pix, &s);
+    primary_index(pf, pr.at, pr.lg_parts, i, &pix, &s);
     const float2 c = rr_global(reinterpret_cast<const float2*>(pf.slot_c))[pix]; // (a pointer read from a device record: rr_global)
     const float2 tr = reinterpret_cast<const float2*>(pr.sample_tr)[s];
     const float cx = c.x, cy = c.y, x_trans = tr.x, y_trans = tr.y;
@@ -1004,17 +1005,21 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t 
 // a wave instruction reads 256 consecutive bytes and writes 256 and 512.  *first_bad: the first index whose pixel lies outside the
 // frame (the host presets 0xffffffff); one atomicMin per wave that has one to report, as reach_merge does for the limits.  Such an
 // entry is copied like any other -- its centre is plain arithmetic -- and the host refuses the call before a walk reads the table.
-__global__ __launch_bounds__(RR_BLOCK) void k_pixel_slots(const uint32_t* __restrict__ pixel_xy, uint32_t n, uint32_t width, uint32_t height,
+// With parts (rr_render_pixel_parts, lg_parts > 0) entry i becomes the K = 2^lg_parts slots i * K .. i * K + K - 1, all with the entry's pixel
+// and centre: K neighbouring lanes read one word and every store stays as wide as it was.
+__global__ __launch_bounds__(RR_BLOCK) void k_pixel_slots(const uint32_t* __restrict__ pixel_xy, uint32_t n, uint32_t lg_parts, uint32_t width, uint32_t height,
                                                           uint32_t* __restrict__ slot_xy, float2* __restrict__ slot_c, uint32_t* __restrict__ first_bad) {
     const float w = (float)width, h = (float)height;
+    const unsigned long long n_slots = (unsigned long long)n << lg_parts; // <= 2^30 (the host)
     uint32_t bad = 0xffffffffu;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * RR_BLOCK) {
+    for (unsigned long long j = (unsigned long long)blockIdx.x * RR_BLOCK + threadIdx.x; j < n_slots; j += (unsigned long long)gridDim.x * RR_BLOCK) {
+        const uint32_t i = (uint32_t)(j >> lg_parts);
         const uint32_t xy = pixel_xy[i];
-        if (!pixel_in_frame(xy, width, height)) bad = min(bad, (uint32_t)i);
+        if (!pixel_in_frame(xy, width, height)) bad = min(bad, i);
         float2 c;
         pixel_centre(xy, w, h, &c.x, &c.y);
-        slot_xy[i] = xy;
-        slot_c[i] = c;
+        slot_xy[j] = xy;
+        slot_c[j] = c;
     }
 #pragma unroll
     for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
@@ -1040,6 +1045,60 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixels(DFrame fr, const ui
     out[2ull * o] = make_float4(c[0], c[1], c[2], depth);
     out[2ull * o + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
     if (rgba8) rgba8[o] = frame_bytes(c, fr.gamma);
+}
+
+// 5k: the K = 2^lg_parts slots of a pixel (rr_render_pixel_parts; slot i * K + h = part h of entry i) -> K part records and the pixel's full record.
+// One lane per slot: a lane resolves its own part over the part's S / K samples (loads of consecutive lanes are consecutive, 8 B per
+// accumulator word; so are the 32-B stores of a list, and those of a whole frame in runs of 8 pixels x K parts, a row of an 8x8 block).  The K lanes of a pixel are an aligned power-of-two group inside the wave (K <= 64 and the
+// block starts on a multiple of 64), so log2 K butterfly steps of __shfl_xor leave in every lane of the group the group's integer sums and
+// the OR of its flags; the group's first lane resolves them over all S samples through the functions k_resolve_pixels uses -- integer
+// adds commute, so these are the sums one slot would have held and the record has k_resolve_pixels' bytes.  The object id sits in the
+// slot that received sample S - 1, the group's last (K divides S); every record of the pixel carries it.  Lanes behind the last slot
+// belong to groups that lie behind it as a whole: they take part in the shuffles with zeros and store nothing.
+// Record index o of the pixel: the entry itself for a list, y * width + x for a whole frame (from_xy), as k_resolve_pixels; part h goes to o * K + h.
+RR_DEV long long shfl_xor_ll(long long v, int mask) {
+    const int lo = __shfl_xor((int)(uint32_t)(unsigned long long)v, mask), hi = __shfl_xor((int)(uint32_t)((unsigned long long)v >> 32), mask);
+    return (long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_parts(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, uint32_t lg_parts, uint32_t from_xy,
+                                                                  float4* __restrict__ out, float4* __restrict__ parts) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
+    const bool live = p < fr.n_region_pixels;                 // (n_region_pixels: the slots, n_pixels * K)
+    const uint32_t K = 1u << lg_parts;
+    long long w[7] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll}; // rgb, normal, depth
+    uint32_t nf = 0u, id = 0u;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { w[k] = acc.rgb[(unsigned long long)k * acc.n + p]; w[3 + k] = acc.normal[(unsigned long long)k * acc.n + p]; }
+        w[6] = acc.depth[p];
+        nf = acc.flags[p];
+        id = acc.object_id[p];
+    }
+    const float n_part = (float)(fr.samples >> lg_parts);
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n_part);
+    const f3 nn = resolve_normal_sum(w[3], w[4], w[5], nf, n_part);
+    const float depth = resolve_depth_sum(w[6], nf, n_part);
+    for (uint32_t off = 1u; off < K; off <<= 1) { // (wave-uniform trip count)
+#pragma unroll
+        for (int k = 0; k < 7; k++) w[k] += shfl_xor_ll(w[k], (int)off);
+        nf |= (uint32_t)__shfl_xor((int)nf, (int)off);
+    }
+    id = (uint32_t)__shfl((int)id, (int)((threadIdx.x & (RR_WAVE - 1)) | (K - 1u))); // the group's last slot holds sample S - 1
+    if (!live) return;
+    uint32_t o = p >> lg_parts; // the pixel's record index; its parts follow each other at o * K
+    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
+    const unsigned long long q = ((unsigned long long)o << lg_parts) + (p & (K - 1u));
+    parts[2ull * q] = make_float4(c[0], c[1], c[2], depth);
+    parts[2ull * q + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(id));
+    if ((p & (K - 1u)) != 0u) return;
+    const float n = (float)fr.samples;
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n);
+    const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
+    out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
+    out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
 }
 
 // ---------------------------------------------------------------------------

@@ -106,6 +106,19 @@ RR_SETUP_HD void primary_index(const PrimaryFrame& pf, const PrimaryLaunch& pl, 
     }
 }
 
+// ---- interleaved parts (rr_render_pixel_parts): K = 2^lg_parts accumulator slots per pixel ----------------------------------
+// Slot i * K + h is part h of list entry i and receives the frame samples {s : s mod K == h}.  The batch plan and the index
+// arithmetic above see K * n slots of S / K samples each; the k-th sample of a slot is frame sample k * K + (slot mod K), and
+// that is the sample everything behind the index means (the row of sample_tr, the generator's key, the object-id rule).
+// lg_parts == 0 is the identity: the frame without parts.
+RR_SETUP_HD uint32_t primary_part_sample(uint32_t slot, uint32_t k, uint32_t lg_parts) {
+    return (k << lg_parts) | (slot & ((1u << lg_parts) - 1u));
+}
+RR_SETUP_HD void primary_index(const PrimaryFrame& pf, const PrimaryLaunch& pl, uint32_t lg_parts, uint32_t i, uint32_t* pix, uint32_t* sample) {
+    primary_index(pf, pl, i, pix, sample);
+    *sample = primary_part_sample(*pix, *sample, lg_parts);
+}
+
 // ---- per-sample offsets: sample_tr[s] = (x_trans, y_trans) -----------------------------------------------------------------
 // What the table depends on besides the sub-sample table itself.
 struct PrimarySampleKey {

@@ -159,6 +159,38 @@ class Raytracing:
         [, rgba: the frame's own bytes])."""
         return self.device_scene.render_pixels(self.camera.c_struct(), self.config, pixels=pixels, sample_xy=sample_xy, rgba8=rgba8)
 
+    def render_pixel_parts(self, pixels=None, n_parts: int = 2, sample_xy=None) -> dict:
+        """render_pixels, and per pixel the means over its n_parts interleaved sample subsets (rr_render_pixel_parts): the dict of
+        render_pixels plus parts = dict(color (n, K, 3), depth (n, K), normal (n, K, 3), object_id (n, K))."""
+        return self.device_scene.render_pixel_parts(self.camera.c_struct(), self.config, pixels=pixels, n_parts=n_parts, sample_xy=sample_xy)
+
+    def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
+        """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
+        base frame's error (adaptive.half_error of the two interleaved halves, one rr_render_pixel_parts call) exceeds `threshold`
+        (one rr_render_pixels call for adaptive.refine_list).  Returns the frame in row-major order: dict(color (n, 3) LINEAR, depth,
+        normal, object_id, samples: the count each pixel was rendered at, error: the estimate).  Every pixel is, bit for bit, the
+        rr_render_pixels pixel at the sample count `samples` names."""
+        from . import adaptive
+        cam = self.camera.c_struct()
+        w, h = int(cam.width), int(cam.height)
+        cfg = rr_config.from_buffer_copy(self.config)
+        cfg.samples = base_samples
+        base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=sample_xy_base)
+        error = adaptive.half_error(base["parts"]["color"])
+        xy, count = adaptive.refine_list(error, threshold, w, h)
+        res = {k: base[k].copy() for k in ("color", "depth", "normal", "object_id")}
+        samples = np.full(w * h, base_samples, np.uint32)
+        if count:
+            cfg.samples = max_samples
+            fine = self.device_scene.render_pixels(cam, cfg, pixels=xy, sample_xy=sample_xy_max)
+            at = (xy[:count] >> np.uint32(16)).astype(np.int64) * w + (xy[:count] & np.uint32(0xffff)).astype(np.int64)
+            for k in res:
+                res[k][at] = fine[k][:count]
+            samples[at] = max_samples
+        res["samples"] = samples
+        res["error"] = error
+        return res
+
     def pick(self, x: int, y: int):
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
@@ -648,3 +680,25 @@ def render_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pix
     if rgba8:
         out["rgba"] = rgba
     return out
+
+
+def render_pixel_parts_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, n_parts: int = 2, sample_xy=None) -> dict:
+    """rr_render_pixel_parts_device on torch's current stream: `pixels` as render_pixels_torch takes them.  Returns torch tensors, without a
+    host copy and without a synchronisation of the results: the dict of render_pixels_torch (records (n, 8) float32 and its views) plus
+    part_records (n, K, 8) float32 and parts = dict(color (n, K, 3) LINEAR, depth (n, K), normal (n, K, 3), object_id (int32 view)), views of it."""
+    import torch
+    n, xy = int(cam.width) * int(cam.height), None
+    if pixels is not None:
+        dtype = torch.int32 if not isinstance(pixels, torch.Tensor) or pixels.dtype != getattr(torch, "uint32", None) else pixels.dtype
+        xy = _ray_tensor(device_scene, pixels, "pixels", shape_tail=(), dtype=dtype)
+        n = int(xy.shape[0])
+    K = int(n_parts)
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        prec = torch.empty((n, max(min(K, 64), 1), 8), dtype=torch.float32, device=dev)
+        if n:
+            device_scene.render_pixel_parts_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, K, rec.data_ptr(), prec.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
+    return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "part_records": prec,
+            "parts": {"color": prec[:, :, 0:3], "depth": prec[:, :, 3], "normal": prec[:, :, 4:7], "object_id": prec.view(torch.int32)[:, :, 7]}}
