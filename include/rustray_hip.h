@@ -44,7 +44,9 @@ extern "C" {
  * device-buffer forms of the three ray queries: rr_trace_rays_device, rr_trace_shadow_rays_device and rr_shade_rays_device.
  * rr_surface_rays and rr_surface_rays_device (with rr_surface_hit, a struct of its own) came after those, in the same way.
  * rr_render_pixels and rr_render_pixels_device came after those, again without a change of any struct: a version-3 library may lack the two.
- * rr_render_pixel_parts and rr_render_pixel_parts_device came after those in the same way: a version-3 library may lack these two as well. */
+ * rr_render_pixel_parts and rr_render_pixel_parts_device came after those in the same way: a version-3 library may lack these two as well.
+ * rr_refine_list_capacity, rr_refine_list_device, rr_render_adaptive and rr_render_adaptive_device came after those, again without a change
+ * of any struct: a version-3 library may lack these four as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -277,7 +279,7 @@ typedef struct rr_frame_stats {
     uint64_t batches;       /* device batches of primary samples the frame was cut into */
     uint64_t sliced_levels; /* depth levels whose children did not fit behind them in the ray arena at once */
     uint64_t binned_rays;   /* secondary rays that were re-ordered by (origin cell, direction octant) before being traced */
-    double ms_binning;      /* device time of that re-ordering (kernel_timing) */
+    double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive, also of the launches that make its list */
     double ms_trace_closest_level1;          /* the part of ms_trace_closest spent on depth level 1 (the primary rays) */
     uint64_t launches_trace_closest_level1;
     /* rr_render_multi only (on scenes[0]; zero after any other frame): how the per-device buffers reached scenes[0]'s device */
@@ -725,6 +727,66 @@ int rr_render_pixel_parts_device(rr_scene* scene, const rr_camera* camera, const
                                  const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels, uint32_t n_parts,
                                  rr_radiance* out_dev /* n_pixels */, rr_radiance* parts_out_dev /* n_pixels * n_parts */, void* hip_stream,
                                  const volatile int* cancel);
+
+/* Adaptive sampling on the device: find the noisy pixels of a frame and spend more samples on them, without a trip through the host.
+ * The estimate is the half-buffer one: with A and B the LINEAR colours of the two halves of a pixel (rr_render_pixel_parts at K = 2),
+ *   error = max over r, g, b of |min(A, 1) - min(B, 1)| / 2, and 0 where any of the six floats is NaN or infinite
+ * (more samples cannot cure a non-finite term); every step is exact in binary32, so a host that computes it itself gets the same bits.
+ *
+ * rr_refine_list_device: the pixels of a width x height frame whose error exceeds `threshold`, as a list rr_render_pixels_device takes.
+ *   parts_dev: width * height * 2 records, the whole-frame layout of rr_render_pixel_parts at K = 2 (part h of pixel (x, y) at
+ *   (y * width + x) * 2 + h), 16-byte aligned.  error_out_dev (or NULL): width * height floats, the error at y * width + x.
+ *   list_out_dev: rr_refine_list_capacity(width, height) entries x | y << 16 (width * height rounded up to a multiple of 64).  The list
+ *   is ordered as the library orders a whole frame -- 8x8 blocks row-major, row-major inside a block -- so that screen neighbours are
+ *   list neighbours, and is padded with copies of its last entry to a multiple of 64 entries (the call that renders it keeps its sample
+ *   group; duplicates give equal records).  *count_out (HOST) = the entries before the pad; an empty list has no pad.  Entries behind
+ *   the padded length are not written.  A pixel is taken when error > threshold: a negative threshold takes every pixel.
+ *   The call follows the rules of the device ray queries: every pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming
+ *   the argument), error_out_dev and list_out_dev 4-byte aligned, work enqueued on `hip_stream` in stream order (the parts may have been
+ *   produced on that stream without a synchronisation), the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene.  It
+ *   WAITS inside once, for the 4 bytes of the count.  Nothing of a frame's state or statistics is touched.
+ *   Refusals: width or height 0 or above 65535, a NaN threshold, a NULL parts_dev, list_out_dev or count_out: RR_ERR_INVALID_ARGUMENT;
+ *   width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ *   Memory: 12 B per 8x8 block of the largest frame so far, kept by the handle until rr_scene_destroy.
+ *
+ * rr_render_adaptive: a frame at two sample counts.  Under ONE hold of the scene's lock (no edit can land between the estimate and the
+ * refinement), on one stream: the whole frame in two parts at base_samples, the list above, the padded list through the body of
+ * rr_render_pixels at max_samples, and the refined records scattered over the base frame.
+ *   out[y * width + x]: byte for byte the record rr_render_pixels writes for that pixel at the sample count samples_out names there,
+ *   base_samples or max_samples, under the table given for that count (sample_xy_base, sample_xy_max; NULL = the built-in one).
+ *   rgba8_out (or NULL): the bytes rr_render_pixels writes for that pixel at that count.  samples_out (or NULL): the count per pixel.
+ *   error_out (or NULL): the error of the BASE frame's halves, as above.  *n_refined_out (or NULL, HOST): the pixels refined, the list's
+ *   count before the pad.
+ *   Config: samples is ignored; every other field is used as a frame uses it; gamma_correction affects rgba8_out only.
+ *   Checks: base_samples even and at least 2 (the two halves must be equal), both counts under rr_render's rule for their table, a
+ *   NaN threshold and out == NULL: RR_ERR_INVALID_ARGUMENT; width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ *   A frame call: the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene, RR_ERR_DEVICE on a broken scene; cancel as
+ *   rr_render_pixels (RR_ERR_CANCELLED, `out` unspecified, the stream left idle); the frames before and after are not affected.
+ *   rr_scene_last_stats reports the SUMS over the two passes, as rr_render_progressive_tiles sums its passes: primary_rays = width *
+ *   height * base_samples + padded count * max_samples; with rr_tuning::kernel_timing, ms_binning holds the device time of the three
+ *   launches that make the list (an order-preserving compaction is a re-ordering too).  The call waits inside where its two passes
+ *   wait, and once for the 4 bytes of the count; with count 0 the fine pass and the scatter are skipped.
+ *   Device memory kept by the handle: per pixel 64 B of part records, 4 B of list, and rr_render_pixel_parts' own at K = 2 (128 B of
+ *   accumulators, 24 B of slot table); per entry of the largest padded list 32 B of fine records and rr_render_pixels' own (64 + 12 B);
+ *   12 B per 8x8 block.  The host form adds 32 B per pixel, and 4, 2 and 4 B for the outputs it is asked for.
+ * rr_render_adaptive_device: the same on DEVICE buffers in stream order, under every rule of rr_render_pixels_device: pointers classified
+ * before any launch, out_dev 16-byte aligned, rgba8_out_dev and error_out_dev 4-byte aligned, samples_out_dev 2-byte aligned.  Once
+ * `hip_stream` is synchronised the buffers hold byte for byte what the host form writes; the host form is this call behind a staging copy. */
+uint64_t rr_refine_list_capacity(uint32_t width, uint32_t height);
+int rr_refine_list_device(rr_scene* scene, uint32_t width, uint32_t height, const rr_radiance* parts_dev /* width * height * 2 */,
+                          float threshold, float* error_out_dev /* width * height, or NULL */,
+                          uint32_t* list_out_dev /* rr_refine_list_capacity entries */, uint32_t* count_out /* HOST */, void* hip_stream);
+int rr_render_adaptive(rr_scene* scene, const rr_camera* camera, const rr_config* config,
+                       uint16_t base_samples, uint16_t max_samples, float threshold,
+                       const uint16_t* sample_xy_base /* or NULL */, const uint16_t* sample_xy_max /* or NULL */,
+                       rr_radiance* out /* width * height */, uint8_t* rgba8_out /* or NULL */, uint16_t* samples_out /* or NULL */,
+                       float* error_out /* or NULL */, uint32_t* n_refined_out /* or NULL, HOST */, const volatile int* cancel);
+int rr_render_adaptive_device(rr_scene* scene, const rr_camera* camera, const rr_config* config,
+                              uint16_t base_samples, uint16_t max_samples, float threshold,
+                              const uint16_t* sample_xy_base /* or NULL */, const uint16_t* sample_xy_max /* or NULL */,
+                              rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */, uint16_t* samples_out_dev /* or NULL */,
+                              float* error_out_dev /* or NULL */, uint32_t* n_refined_out /* or NULL, HOST */, void* hip_stream,
+                              const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -570,6 +570,40 @@ public:
         return rr_render_pixel_parts_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, n_parts, out_dev, parts_out_dev, hip_stream, cancel);
     }
 
+    // A frame at two sample counts (rr_render_adaptive): every pixel at base_samples (even, at least 2), and at max_samples where the
+    // half-buffer error of the base frame -- max over channels of |min(A, 1) - min(B, 1)| / 2 of the pixel's two halves -- exceeds
+    // `threshold`; estimate, list, fine pass and scatter run on the device under one hold of the scene's lock.  config.samples is ignored.
+    // Returns the records in row-major order, each byte for byte render_pixels' at the count `samples` names there; samples, error, rgba8
+    // and n_refined are optional.  An empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_radiance> render_adaptive(uint16_t base_samples, uint16_t max_samples, float threshold, std::vector<uint16_t>* samples = nullptr,
+                                             std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr, uint32_t* n_refined = nullptr) const {
+        std::vector<rr_radiance> out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        const size_t n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (samples) samples->assign(n, 0);
+        if (error) error->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_render_adaptive(scene->handle(), &cam, &c, base_samples, max_samples, threshold, nullptr, nullptr, out.data(), rgba8 ? rgba8->data() : nullptr,
+                               samples ? samples->data() : nullptr, error ? error->data() : nullptr, n_refined, nullptr) != RR_OK) {
+            out.clear();
+            if (samples) samples->clear();
+            if (error) error->clear();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_adaptive_device): out_dev holds width * height records; the other buffers are optional
+    int render_adaptive_device(uint16_t base_samples, uint16_t max_samples, float threshold, rr_radiance* out_dev, uint8_t* rgba8_out_dev, uint16_t* samples_out_dev,
+                               float* error_out_dev, uint32_t* n_refined, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_adaptive_device(scene->handle(), &cam, &c, base_samples, max_samples, threshold, nullptr, nullptr, out_dev, rgba8_out_dev, samples_out_dev,
+                                         error_out_dev, n_refined, hip_stream, cancel);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -42,8 +42,8 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_probe.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -124,6 +124,14 @@ def lib():
                                                 C.c_void_p, C.c_void_p]
             L.rr_render_pixel_parts_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_render_adaptive") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
+            L.rr_refine_list_capacity.restype = C.c_uint64
+            L.rr_refine_list_capacity.argtypes = [C.c_uint32, C.c_uint32]
+            L.rr_refine_list_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+            L.rr_render_adaptive.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+            L.rr_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -171,6 +179,11 @@ def sample_table(samples: int):
     cs = C.c_uint32(0)
     _check(lib().rr_sample_table(C.c_uint16(samples), xy.ctypes.data_as(C.c_void_p), C.byref(cs)))
     return xy[:samples], int(cs.value)
+
+
+def refine_list_capacity(width: int, height: int) -> int:
+    """rr_refine_list_capacity: entries a refinement list of a width x height frame may need (every pixel, padded to a multiple of 64)."""
+    return int(lib().rr_refine_list_capacity(C.c_uint32(width), C.c_uint32(height)))
 
 
 def region_pixel_count(width: int, height: int, tile_w: int, tile_h: int, n_ranks: int, rank: int) -> int:
@@ -452,6 +465,55 @@ class DeviceScene:
         _check(lib().rr_render_pixel_parts_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
                                                   C.c_uint32(n_parts), C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(parts_ptr) if parts_ptr else None,
                                                   C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+
+    # -- adaptive sampling on the device ----------------------------------------------
+    def refine_list_device(self, width: int, height: int, parts_ptr, threshold: float, error_ptr, list_ptr, stream_ptr=None) -> int:
+        """rr_refine_list_device: adaptive.refine_list(adaptive.half_error(parts), threshold, width, height) on the device.  parts_ptr: the
+        width * height * 2 part records of a whole frame at n_parts = 2 (16-byte aligned); error_ptr: width * height float32 or None; list_ptr:
+        refine_list_capacity(width, height) uint32, of which the padded list is written; raw device pointers, enqueued on `stream_ptr`.  Returns
+        the number of entries before the pad (the call waits for it)."""
+        count = C.c_uint32(0)
+        _check(lib().rr_refine_list_device(self._h, C.c_uint32(width), C.c_uint32(height), C.c_void_p(parts_ptr) if parts_ptr else None, C.c_float(threshold),
+                                           C.c_void_p(error_ptr) if error_ptr else None, C.c_void_p(list_ptr) if list_ptr else None, C.byref(count),
+                                           C.c_void_p(stream_ptr) if stream_ptr else None))
+        return int(count.value)
+
+    def render_adaptive(self, cam: rr_camera, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None,
+                        rgba8: bool = False, cancel=None) -> dict:
+        """rr_render_adaptive: every pixel at `base_samples`, and at `max_samples` where the half-buffer error of the base frame exceeds
+        `threshold` -- estimate, list, fine pass and scatter in one call on the device.  Returns the dict of Raytracing.render_adaptive in
+        row-major order (color (n, 3) LINEAR, depth, normal, object_id, samples uint32, error) plus n_refined, and `rgba` (n, 4) uint8, the
+        frame's own bytes, with rgba8=True.  cfg.samples is ignored."""
+        n = int(cam.width) * int(cam.height)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        samples = np.zeros(max(n, 1), np.uint16)
+        error = np.zeros(max(n, 1), np.float32)
+        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        keep_b, pb = _sxy(sample_xy_base)
+        keep_m, pm = _sxy(sample_xy_max)
+        count = C.c_uint32(0)
+        _check(lib().rr_render_adaptive(self._h, C.byref(cam), C.byref(cfg), C.c_uint16(base_samples), C.c_uint16(max_samples), C.c_float(threshold), pb, pm,
+                                        out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
+                                        error.ctypes.data_as(C.c_void_p), C.byref(count), C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
+                   samples=samples[:n].astype(np.uint32), error=error[:n], n_refined=int(count.value))
+        if rgba8:
+            res["rgba"] = rgba[:n]
+        return res
+
+    def render_adaptive_device(self, cam: rr_camera, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None,
+                               error_ptr=None, stream_ptr=None, sample_xy_base=None, sample_xy_max=None, cancel=None) -> int:
+        """rr_render_adaptive_device: width * height 32-byte rr_radiance records (16-byte aligned) and, optionally, as many x 4 bytes, uint16
+        sample counts and float32 errors, all raw device pointers; enqueued on `stream_ptr`.  Returns the number of refined pixels."""
+        keep_b, pb = _sxy(sample_xy_base)
+        keep_m, pm = _sxy(sample_xy_max)
+        count = C.c_uint32(0)
+        _check(lib().rr_render_adaptive_device(self._h, C.byref(cam), C.byref(cfg), C.c_uint16(base_samples), C.c_uint16(max_samples), C.c_float(threshold), pb, pm,
+                                               C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
+                                               C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None, C.byref(count),
+                                               C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+        return int(count.value)
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

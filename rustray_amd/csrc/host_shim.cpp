@@ -240,6 +240,29 @@ extern "C" int rh_render_pixel_parts_device(void* h, float fov, const float* eye
                                             rr_radiance* parts_dev, void* stream, const int* cancel) {
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_pixel_parts_device(xy_dev, n, n_parts, out_dev, parts_dev, stream, cancel);
 }
+// Raytracing::render_adaptive: out = w * h records, samples = w * h uint16, error = w * h floats, rgba8 = w * h x 4 bytes (each of the three
+// or NULL); returns the number of refined pixels, or -1 when the call was refused.  rh_render_adaptive_device: Raytracing::render_adaptive_device
+// on device buffers, the rr_status as it is.
+extern "C" int rh_render_adaptive(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                  uint32_t w, uint32_t hgt, uint16_t base_samples, uint16_t max_samples, float threshold, rr_radiance* out, uint16_t* samples,
+                                  float* error, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<uint16_t> sm; std::vector<float> er; std::vector<uint8_t> bytes;
+    uint32_t n_refined = 0;
+    const std::vector<rr_radiance> r = rt.render_adaptive(base_samples, max_samples, threshold, samples ? &sm : nullptr, error ? &er : nullptr, rgba8 ? &bytes : nullptr, &n_refined);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (samples) std::memcpy(samples, sm.data(), sm.size() * 2);
+    if (error) std::memcpy(error, er.data(), er.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return (int)n_refined;
+}
+extern "C" int rh_render_adaptive_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                         uint32_t w, uint32_t hgt, uint16_t base_samples, uint16_t max_samples, float threshold, rr_radiance* out_dev, uint8_t* rgba8_dev,
+                                         uint16_t* samples_dev, float* error_dev, uint32_t* n_refined, void* stream, const int* cancel) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_adaptive_device(base_samples, max_samples, threshold, out_dev, rgba8_dev, samples_dev, error_dev,
+                                                                                          n_refined, stream, cancel);
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -3,7 +3,7 @@
 //         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
 //         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; FrameIo, fill_pixel_slots, render_region_locked
 //         (rr_render_pixels, rr_api_query.h, is its other caller); rr_render_region_device,
-//         rr_render, rr_render_progressive, rr_render_progressive_tiles; rr_scene_last_stats, rr_scene_overlap_stages;
+//         rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
 //         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
 // Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
 //         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h,
@@ -600,7 +600,7 @@ static int take_stream(rr_scene* s, hipStream_t st) {
 static void begin_frame_stats(rr_scene* s) {
     resolve_timers(s); // launches of an earlier frame nobody asked about must not leak into this frame's stats
     memset(&s->timing.stats, 0, sizeof s->timing.stats);
-    s->timing.stats_final = false;
+    s->timing.stats_final = false; s->timing.has_carry = false;
     s->frame.overlap_stages = 0;
 }
 
@@ -701,12 +701,29 @@ static int read_counters(const rr_scene* s, rr_frame_stats* st) {
     st->shadow_rays = c[RR_CNT_SHADOW]; st->shaded_hits = c[RR_CNT_SHADED];
     return RR_OK;
 }
-// the device counters and launch timers of the frame (or pass) that ran last, into s->timing.stats
+// sum += a, field by field: the statistics of a frame made of several passes (rr_render_progressive_tiles, rr_render_adaptive)
+static void add_pass_stats(rr_frame_stats* sum_, const rr_frame_stats& a) {
+    rr_frame_stats& sum = *sum_;
+    sum.primary_rays += a.primary_rays; sum.secondary_rays += a.secondary_rays; sum.shadow_rays += a.shadow_rays; sum.shaded_hits += a.shaded_hits;
+    sum.ms_total += a.ms_total; sum.ms_trace_closest += a.ms_trace_closest; sum.ms_trace_shadow += a.ms_trace_shadow; sum.ms_shade += a.ms_shade;
+    sum.launches_trace_closest += a.launches_trace_closest; sum.launches_trace_shadow += a.launches_trace_shadow; sum.launches_shade += a.launches_shade;
+    sum.batches += a.batches; sum.sliced_levels += a.sliced_levels; sum.binned_rays += a.binned_rays; sum.ms_binning += a.ms_binning;
+    sum.ms_trace_closest_level1 += a.ms_trace_closest_level1; sum.launches_trace_closest_level1 += a.launches_trace_closest_level1;
+    sum.ms_shade_level1 += a.ms_shade_level1; sum.launches_shade_level1 += a.launches_shade_level1;
+    sum.ms_trace_shadow_level1 += a.ms_trace_shadow_level1; sum.launches_trace_shadow_level1 += a.launches_trace_shadow_level1;
+}
+// the device counters and launch timers of the frame (or pass) that ran last, into s->timing.stats; behind the fine pass of
+// rr_render_adaptive the base pass it carries is added, once, and the sums are final
 static int collect_stats_locked(rr_scene* s) {
     float ms = 0.0f;
     if (hipEventSynchronize(s->timing.frame_b) == hipSuccess && hipEventElapsedTime(&ms, s->timing.frame_a, s->timing.frame_b) == hipSuccess) s->timing.stats.ms_total = ms;
     resolve_timers(s);
-    return read_counters(s, &s->timing.stats);
+    RR_TRY(read_counters(s, &s->timing.stats));
+    if (s->timing.has_carry) {
+        add_pass_stats(&s->timing.stats, s->timing.carry);
+        s->timing.has_carry = false; s->timing.stats_final = true;
+    }
+    return RR_OK;
 }
 extern "C" int rr_scene_overlap_stages(const rr_scene* cs, uint32_t* out) try {
     if (!cs || !out) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -757,16 +774,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
         RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&rg, &dev, true), nullptr, cancel));
         HIP_TRY(hipStreamSynchronize(nullptr));
         RR_TRY(collect_stats_locked(s));
-        {   // the frame's statistics are the sums over its passes
-            const rr_frame_stats& a = s->timing.stats;
-            sum.primary_rays += a.primary_rays; sum.secondary_rays += a.secondary_rays; sum.shadow_rays += a.shadow_rays; sum.shaded_hits += a.shaded_hits;
-            sum.ms_total += a.ms_total; sum.ms_trace_closest += a.ms_trace_closest; sum.ms_trace_shadow += a.ms_trace_shadow; sum.ms_shade += a.ms_shade;
-            sum.launches_trace_closest += a.launches_trace_closest; sum.launches_trace_shadow += a.launches_trace_shadow; sum.launches_shade += a.launches_shade;
-            sum.batches += a.batches; sum.sliced_levels += a.sliced_levels; sum.binned_rays += a.binned_rays; sum.ms_binning += a.ms_binning;
-            sum.ms_trace_closest_level1 += a.ms_trace_closest_level1; sum.launches_trace_closest_level1 += a.launches_trace_closest_level1;
-            sum.ms_shade_level1 += a.ms_shade_level1; sum.launches_shade_level1 += a.launches_shade_level1;
-            sum.ms_trace_shadow_level1 += a.ms_trace_shadow_level1; sum.launches_trace_shadow_level1 += a.launches_trace_shadow_level1;
-        }
+        add_pass_stats(&sum, s->timing.stats); // the frame's statistics are the sums over its passes
         RR_TRY(copy_outputs(*out, dev, np, nullptr));
         done += rr_region_pixel_count(W, H, &rg);
         s->timing.stats = sum; s->timing.stats_final = true;

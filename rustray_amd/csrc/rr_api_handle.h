@@ -1,5 +1,5 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
-// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, MultiState, FrameTiming
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, MultiState, FrameTiming
 //         and rr_scene, which holds one of each; check_intact.
 // Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
@@ -109,6 +109,14 @@ struct QueryState {
     DevBuf rec[4], words, ids;
 };
 
+// ---- rr_refine_list_device and rr_render_adaptive (rr_api_adaptive.h): grown on demand, never shrunk.  scratch: per 8x8 block of the largest
+// frame so far its 64-bit refine mask, then its count (after k_refine_scan: its offset), then one word, the list's length (12 B per
+// block + 4).  The fused call keeps in addition the base frame's two part records per pixel (64 B), its list (4 B per pixel, padded)
+// and the fine records of the largest padded list so far (32 B per entry).  Written by rr_api_adaptive.h.
+struct AdaptiveState {
+    DevBuf scratch, parts, list, fine;
+};
+
 // ---- rr_render_multi (rr_api_multi.h)
 struct MultiState {
     DevBuf part[4], cat[4]; // this device's compact buffers; on device slot 0 the concatenation of all
@@ -124,6 +132,10 @@ struct MultiState {
 struct FrameTiming {
     rr_frame_stats stats{};
     bool stats_final = false; // stats already holds the sums over the passes of rr_render_progressive_tiles (nothing to collect from the device)
+    // rr_render_adaptive: what its base pass cost, collected while the call waited for the list's length; added ONCE to what the device
+    // reports for the fine pass when somebody asks (collect_stats_locked), so the call itself need not wait for its last launch
+    rr_frame_stats carry{};
+    bool has_carry = false;
     bool profiling = false;
     std::vector<TimedLaunch> timed;
     std::vector<hipEvent_t> event_pool;
@@ -155,6 +167,7 @@ struct rr_scene {
     TopLevel tlas;
     FrameState frame;
     QueryState query;
+    AdaptiveState adaptive;
     MultiState multi;
     FrameTiming timing;
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's

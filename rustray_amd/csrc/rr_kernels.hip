@@ -22,6 +22,7 @@
 #include "rr_device.h"
 #include "rr_math.h"
 #include "rr_primary_setup.h"
+#include "rr_adaptive.h" // half_error and the 8x8-block order of a refinement list (kernels 5l .. 5p)
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -1099,6 +1100,108 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_parts(DFrame fr, con
     const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
     out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
     out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
+}
+
+// ---------------------------------------------------------------------------
+// kernels 5l .. 5p: find the noisy pixels of a frame and refine them on the device (rr_refine_list_device, rr_render_adaptive)
+// ---------------------------------------------------------------------------
+// The list of adaptive.refine_list (rustray_amd/adaptive.py) as an order-preserving stream compaction in three launches, and the two
+// passes that put a refined frame together.  The frame's 8x8 blocks, row-major, ARE the list's order (rr_adaptive.h), and on wave64 one
+// wave is one block: lane l is the block's pixel l, __ballot of the lanes' flags is the block's 64-bit refine mask, and a set lane's
+// place inside its block is the number of set bits below it.  No kernel waits for another workgroup: the scan between the two wave
+// kernels is a launch of its own.
+//
+// 5l: parts = the K = 2 part records of the whole frame (k_resolve_pixel_parts, from_xy: two float4 per part at (y * width + x) * 2 + h).
+// A lane loads the colour float4 of its pixel's two halves (the 8 lanes of a block row: 512 consecutive bytes), error_out (or NULL) gets
+// half_error at y * width + x, and lane 0 stores the block's mask and its popcount.  Lanes outside the frame load nothing and flag nothing.
+__global__ __launch_bounds__(RR_BLOCK) void k_refine_masks(const float4* __restrict__ parts, uint32_t width, uint32_t height, uint32_t n_blocks, float threshold,
+                                                           float* __restrict__ error_out, unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE);
+    for (uint32_t b = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; b < n_blocks; b += waves) { // (wave-uniform)
+        uint32_t xy = 0u;
+        const bool present = refine_position_pixel(((unsigned long long)b << 6) | lane, width, height, &xy);
+        bool flag = false;
+        if (present) {
+            const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
+            const float4 a = parts[4ull * o], c = parts[4ull * o + 2];
+            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
+            const float e = half_error(ca, cb);
+            if (error_out) error_out[o] = e;
+            flag = e > threshold;
+        }
+        const unsigned long long mask = __ballot(flag);
+        if (lane == 0u) { masks[b] = mask; counts[b] = (uint32_t)__popcll(mask); }
+    }
+}
+
+// 5m: the exclusive prefix of the n block counts, in place, and their sum in *total.  ONE workgroup of 1024 threads walks the array in
+// steps of 1024 with a carry (14 400 blocks at 1280x720: 15 steps): a shuffle scan inside each wave, the 16 wave sums through LDS.
+__global__ __launch_bounds__(1024) void k_refine_scan(uint32_t* __restrict__ counts, uint32_t n, uint32_t* __restrict__ total) {
+    __shared__ uint32_t s_wave[1024 / RR_WAVE];
+    const uint32_t t = threadIdx.x, lane = t & (RR_WAVE - 1), wv = t / RR_WAVE;
+    uint32_t carry = 0u;
+    for (uint32_t base = 0u; base < n; base += 1024u) { // (uniform over the workgroup)
+        const uint32_t i = base + t;
+        const uint32_t v = i < n ? counts[i] : 0u;
+        uint32_t incl = v;
+#pragma unroll
+        for (int off = 1; off < RR_WAVE; off <<= 1) {
+            const uint32_t u = (uint32_t)__shfl_up((int)incl, off);
+            if (lane >= (uint32_t)off) incl += u;
+        }
+        if (lane == RR_WAVE - 1) s_wave[wv] = incl;
+        __syncthreads();
+        uint32_t before = 0u, all = 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 1024 / RR_WAVE; k++) { const uint32_t w = s_wave[k]; before += k < wv ? w : 0u; all += w; }
+        if (i < n) counts[i] = carry + before + incl - v;
+        carry += all;
+        __syncthreads(); // s_wave is written again in the next step
+    }
+    if (t == 0u) *total = carry;
+}
+
+// 5n: one wave per block again; it reads the block's mask and offset only.  A lane whose bit is set writes its pixel x | y << 16 at
+// offset + (set bits below the lane).  The wave that holds the list's last entry -- the last block with any bit set: its offset plus its
+// popcount is the total -- also writes the pad: copies of that entry up to the next multiple of 64 (fewer than 64: one per lane).
+__global__ __launch_bounds__(RR_BLOCK) void k_refine_scatter(const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ total,
+                                                             uint32_t width, uint32_t height, uint32_t n_blocks, uint32_t* __restrict__ list) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE);
+    const uint32_t count = *total;
+    for (uint32_t b = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; b < n_blocks; b += waves) { // (wave-uniform)
+        const unsigned long long mask = masks[b];
+        if (mask == 0ull) continue;
+        const uint32_t off = offsets[b];
+        uint32_t xy = 0u;
+        (void)refine_position_pixel(((unsigned long long)b << 6) | lane, width, height, &xy); // (a set bit is a pixel of the frame: k_refine_masks)
+        if ((mask >> lane) & 1ull) list[off + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = xy;
+        if (off + (uint32_t)__popcll(mask) != count) continue;
+        const uint32_t last = (uint32_t)__shfl((int)xy, 63 - __clzll((long long)mask)); // the highest set lane's pixel
+        if (count + lane < refine_padded(count)) list[count + lane] = last;
+    }
+}
+
+// 5o: fine record i (two float4) -> out at the pixel of list entry i, for the `count` entries before the pad; samples_out (or NULL) names
+// the sample count there.  The entries before the pad are distinct pixels of the frame (k_refine_scatter).
+__global__ __launch_bounds__(RR_BLOCK) void k_scatter_records(const uint32_t* __restrict__ list, const uint32_t* __restrict__ count, const float4* __restrict__ fine, uint32_t width,
+                                                              uint16_t max_samples, float4* __restrict__ out, uint16_t* __restrict__ samples_out) {
+    const uint32_t n = *count;
+    for (uint32_t i = blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += gridDim.x * RR_BLOCK) {
+        const uint32_t xy = list[i];
+        const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
+        out[2ull * o] = fine[2ull * i];
+        out[2ull * o + 1] = fine[2ull * i + 1];
+        if (samples_out) samples_out[o] = max_samples;
+    }
+}
+
+// 5p: the frame's own bytes of n finished records: frame_bytes on the record's colour, the function and the floats of k_resolve_pixels
+__global__ __launch_bounds__(RR_BLOCK) void k_record_bytes(const float4* __restrict__ out, uint32_t n, uint32_t gamma, uint32_t* __restrict__ rgba8) {
+    for (uint32_t o = blockIdx.x * RR_BLOCK + threadIdx.x; o < n; o += gridDim.x * RR_BLOCK) {
+        const float4 r = out[2ull * o];
+        const float c[3] = {r.x, r.y, r.z};
+        rgba8[o] = frame_bytes(c, gamma);
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -191,6 +191,13 @@ class Raytracing:
         res["error"] = error
         return res
 
+    def render_adaptive_on_device(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None, rgba8: bool = False) -> dict:
+        """render_adaptive as ONE library call (rr_render_adaptive): the estimate, the list, the fine pass and the scatter run on the device
+        under one hold of the scene's lock.  Returns what render_adaptive returns, field for field and bit for bit, plus n_refined, and
+        `rgba`, the frame's own bytes, with rgba8=True."""
+        return self.device_scene.render_adaptive(self.camera.c_struct(), self.config, base_samples, max_samples, threshold, sample_xy_base=sample_xy_base,
+                                                 sample_xy_max=sample_xy_max, rgba8=rgba8)
+
     def pick(self, x: int, y: int):
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
@@ -702,3 +709,30 @@ def render_pixel_parts_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config
                                                    torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
     return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "part_records": prec,
             "parts": {"color": prec[:, :, 0:3], "depth": prec[:, :, 3], "normal": prec[:, :, 4:7], "object_id": prec.view(torch.int32)[:, :, 7]}}
+
+
+def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None,
+                          sample_xy_max=None, rgba8: bool = False, samples: bool = True, error: bool = True) -> dict:
+    """rr_render_adaptive_device on torch's current stream: the frame at `base_samples`, and at `max_samples` where the half-buffer error
+    of the base frame exceeds `threshold`.  Returns torch tensors in row-major order, without a host copy of the results: the dict of
+    render_pixels_torch (records (n, 8) float32 and its views), n_refined (an int: the call waits for it), and on request samples (n,)
+    int16 (the sample count per pixel), error (n,) float32 and rgba (n, 4) uint8."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
+        err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
+        count = device_scene.render_adaptive_device(cam, cfg, base_samples, max_samples, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
+                                                    smp.data_ptr() if samples else None, err.data_ptr() if error else None,
+                                                    torch.cuda.current_stream(dev).cuda_stream, sample_xy_base=sample_xy_base, sample_xy_max=sample_xy_max)
+    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "n_refined": count}
+    if rgba8:
+        out["rgba"] = rgba
+    if samples:
+        out["samples"] = smp
+    if error:
+        out["error"] = err
+    return out

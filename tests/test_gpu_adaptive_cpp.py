@@ -1,0 +1,84 @@
+"""Raytracing::render_adaptive and render_adaptive_device of include/rustray_host.hpp, driven through host_shim.cpp: the frame at two sample
+counts equals what the ctypes binding gives, and a refusal of rr_render_adaptive comes back through the C++ layer."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from rustray_amd import capi
+from rustray_amd.flat import make_config, rr_config, rr_flat_scene
+from tests.helpers import camera_for, load_scene
+from tests.test_cpp_host import _cam_args
+
+pytestmark = pytest.mark.gpu
+
+SHIM = os.path.join(os.path.dirname(capi.LIB_PATH), "librustray_host_shim.so")
+W, H = 50, 38
+N = W * H
+BASE, TOP, THRESHOLD = 6, 16, 0.1
+
+
+def _shim():
+    assert os.path.exists(SHIM), f"{SHIM} is missing: run `make -C rustray_amd/csrc`"
+    L = C.CDLL(SHIM)
+    F3 = C.c_float * 3
+    camera = [C.c_float, F3, F3, F3, C.c_float, C.c_float, C.POINTER(rr_config), C.c_uint32, C.c_uint32]
+    L.rh_scene_create.restype = C.c_void_p
+    L.rh_scene_create.argtypes = [C.POINTER(rr_flat_scene), C.c_int]
+    L.rh_scene_destroy.argtypes = [C.c_void_p]
+    L.rh_render_adaptive.argtypes = [C.c_void_p] + camera + [C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rh_render_adaptive_device.argtypes = [C.c_void_p] + camera + [C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                  C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+    return L
+
+
+def _equal(rec, samples, error, rgba, want):
+    assert np.array_equal(rec[:, 0:3], want["color"].view(np.uint32)) and np.array_equal(rec[:, 3], want["depth"].view(np.uint32))
+    assert np.array_equal(rec[:, 4:7], want["normal"].view(np.uint32)) and np.array_equal(rec[:, 7], want["object_id"])
+    assert np.array_equal(samples.astype(np.uint32), want["samples"]) and np.array_equal(error.view(np.uint32), want["error"].view(np.uint32))
+    assert np.array_equal(rgba.reshape(N, 4), want["rgba"])
+
+
+def test_render_adaptive_through_the_cpp_host_layer(hip):
+    import torch
+    fs = load_scene("spheres_room")
+    camera = camera_for(fs, W, H)
+    cam = camera.c_struct()
+    cfg = make_config(samples=6, monte_carlo=True, seed=3, max_recursion=4)
+    with hip.DeviceScene(fs, 0) as ds:             # (the C++ layer uses the library's built-in sub-sample tables)
+        want = ds.render_adaptive(cam, cfg, BASE, TOP, THRESHOLD, rgba8=True)
+    assert 0 < want["n_refined"] < N
+    L = _shim()
+    cs = fs.c_struct()
+    h = L.rh_scene_create(C.byref(cs), 0)
+    assert h
+    args = _cam_args(camera) + (C.byref(cfg), W, H)
+    try:
+        rec, samples, error, rgba = np.zeros((N, 8), np.uint32), np.zeros(N, np.uint16), np.zeros(N, np.float32), np.zeros(4 * N, np.uint8)
+        assert L.rh_render_adaptive(h, *args, BASE, TOP, THRESHOLD, rec.ctypes.data, samples.ctypes.data, error.ctypes.data, rgba.ctypes.data) == want["n_refined"]
+        _equal(rec, samples, error, rgba, want)
+        rec2 = np.zeros((N, 8), np.uint32)
+        assert L.rh_render_adaptive(h, *args, BASE, TOP, THRESHOLD, rec2.ctypes.data, None, None, None) == want["n_refined"]
+        assert np.array_equal(rec2, rec)
+        assert L.rh_render_adaptive(h, *args, 7, TOP, THRESHOLD, rec2.ctypes.data, None, None, None) == -1      # an odd base count
+        assert L.rh_render_adaptive(h, *args, BASE, TOP, float("nan"), rec2.ctypes.data, None, None, None) == -1
+        # the device form
+        out = torch.zeros((N, 8), dtype=torch.int32, device="cuda")
+        t_rgba = torch.zeros((N, 4), dtype=torch.uint8, device="cuda")
+        t_samples = torch.zeros((N,), dtype=torch.int16, device="cuda")
+        t_error = torch.zeros((N,), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        count = C.c_uint32(0)
+
+        def dev(base, cancel=None):
+            return L.rh_render_adaptive_device(h, *args, base, TOP, THRESHOLD, out.data_ptr(), t_rgba.data_ptr(), t_samples.data_ptr(), t_error.data_ptr(),
+                                               C.byref(count), None, cancel)
+        assert dev(7) == -1
+        flag = C.c_int(1)
+        assert dev(BASE, C.byref(flag)) == -6
+        assert dev(BASE) == 0 and count.value == want["n_refined"]
+        torch.cuda.synchronize()
+        _equal(out.cpu().numpy().view(np.uint32), t_samples.cpu().numpy().view(np.uint16), t_error.cpu().numpy(), t_rgba.cpu().numpy(), want)
+    finally:
+        L.rh_scene_destroy(h)
