@@ -46,7 +46,9 @@ extern "C" {
  * rr_render_pixels and rr_render_pixels_device came after those, again without a change of any struct: a version-3 library may lack the two.
  * rr_render_pixel_parts and rr_render_pixel_parts_device came after those in the same way: a version-3 library may lack these two as well.
  * rr_refine_list_capacity, rr_refine_list_device, rr_render_adaptive and rr_render_adaptive_device came after those, again without a change
- * of any struct: a version-3 library may lack these four as well. */
+ * of any struct: a version-3 library may lack these four as well.
+ * rr_refine_sublist_device, rr_render_adaptive_levels and rr_render_adaptive_levels_device came after those in the same way: a version-3
+ * library may lack these three as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -279,7 +281,7 @@ typedef struct rr_frame_stats {
     uint64_t batches;       /* device batches of primary samples the frame was cut into */
     uint64_t sliced_levels; /* depth levels whose children did not fit behind them in the ray arena at once */
     uint64_t binned_rays;   /* secondary rays that were re-ordered by (origin cell, direction octant) before being traced */
-    double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive, also of the launches that make its list */
+    double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive and rr_render_adaptive_levels, also of the launches that make their lists */
     double ms_trace_closest_level1;          /* the part of ms_trace_closest spent on depth level 1 (the primary rays) */
     uint64_t launches_trace_closest_level1;
     /* rr_render_multi only (on scenes[0]; zero after any other frame): how the per-device buffers reached scenes[0]'s device */
@@ -787,6 +789,72 @@ int rr_render_adaptive_device(rr_scene* scene, const rr_camera* camera, const rr
                               rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */, uint16_t* samples_out_dev /* or NULL */,
                               float* error_out_dev /* or NULL */, uint32_t* n_refined_out /* or NULL, HOST */, void* hip_stream,
                               const volatile int* cancel);
+
+/* Refinement level by level.  rr_render_adaptive knows two sample counts; most pixels that fail the threshold at the lower one pass it
+ * long before the upper one.  Here a pixel climbs a ladder of counts and stops at the first whose halves agree.
+ *
+ * rr_refine_sublist_device: the list of a list.  Entry i of list_dev is x | y << 16 and its two halves lie at parts_dev[2 i] and
+ * parts_dev[2 i + 1], the layout rr_render_pixel_parts writes for a list at K = 2.
+ *   error_out_dev (or NULL): `count` floats, the error of entry i at i (the estimate above, the same bits as on the host).
+ *   list_out_dev: the entries with error > threshold in the order they had (a sub-sequence of a block-ordered list is block-ordered),
+ *   padded with copies of its last entry to a multiple of 64; room for `count` rounded up to a multiple of 64 entries.  *count_out
+ *   (HOST) = the entries before the pad.  An empty result has no pad and writes nothing to the list; words behind the padded length
+ *   are not written.
+ *   Only the first `count` entries and their halves are looked at: the caller's own pad is never taken.  Duplicates are entries like
+ *   any other.  The coordinates are not interpreted: there is no frame size.
+ *   The call follows rr_refine_list_device: every pointer classified before any launch (RR_ERR_INVALID_ARGUMENT naming the argument),
+ *   parts_dev 16-byte aligned, the others 4-byte aligned, work enqueued on `hip_stream` in stream order, the scene's lock,
+ *   RR_ERR_INVALID_ARGUMENT from on_pass of the same scene, ONE wait inside for the 4 bytes of the count, nothing of a frame's state
+ *   or statistics touched.
+ *   Refusals: a NULL scene or count_out, a NaN threshold, and with count > 0 a NULL list_dev, parts_dev or list_out_dev, a misaligned
+ *   pointer, or list_out_dev (padded) overlapping list_dev: RR_ERR_INVALID_ARGUMENT; count > 2^29: RR_ERR_UNSUPPORTED.  count == 0:
+ *   RR_OK with *count_out = 0; nothing is launched and no other pointer is looked at.
+ *   Memory: 12 B per 64 entries of the longest list so far, kept by the handle until rr_scene_destroy (the buffer rr_refine_list_device grows).
+ *
+ * rr_render_adaptive_levels: a frame at n_levels sample counts, 2 <= n_levels <= RR_MAX_ADAPTIVE_LEVELS.  Under ONE hold of the scene's
+ * lock, on one stream: the whole frame in two parts at level_samples[0] and its list, as rr_render_adaptive; then for l = 1, 2, ...
+ * while the list is not empty, the padded list in two parts at level_samples[l], its records scattered over the frame, and the
+ * sublist above as the next level's list.  Every pixel ends below the threshold or at the top count.
+ *   sample_xy_levels: NULL, or n_levels pointers, each the table of its level or NULL for the built-in one.
+ *   out[y * width + x]: byte for byte the record rr_render_pixels writes for that pixel at the count samples_out names there, under the
+ *   table of that level.  rgba8_out (or NULL): its bytes at that count.  samples_out (or NULL): the count of the last level that
+ *   rendered the pixel.
+ *   error_out (or NULL): the error of the pixel's halves AT THAT COUNT, the residual error.  This differs by design from
+ *   rr_render_adaptive, whose error_out is the base frame's: there a refined pixel keeps the error that had it refined.
+ *   level_pixels_out (or NULL, HOST, n_levels words): the pixels rendered at each level before the pad; [0] = width * height; levels
+ *   never reached are 0.
+ *   Config: samples is ignored; every other field is used as a frame uses it; gamma_correction affects rgba8_out only.
+ *   Checks: n_levels out of range, a count that is odd or below 2 (the two halves must be equal), a count not above the one before
+ *   it (the message names the level and the rule), a NaN threshold, out == NULL: RR_ERR_INVALID_ARGUMENT; every count under rr_render's
+ *   rule for its table; width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ *   A frame call: the scene's lock, RR_ERR_INVALID_ARGUMENT from on_pass of the same scene, RR_ERR_DEVICE on a broken scene; cancel is
+ *   polled inside the passes and between levels (RR_ERR_CANCELLED, `out` unspecified, the stream left idle); the frames before and
+ *   after are not affected.
+ *   rr_scene_last_stats reports the SUMS over all passes: primary_rays = the sum over the levels reached of padded list length x the
+ *   level's count (level 0: width * height); with rr_tuning::kernel_timing, ms_binning holds the device time of every list's launches.
+ *   The call waits inside where its passes wait, and once per level but the last for the 4 bytes of a count.
+ *   Device memory kept by the handle: what rr_render_adaptive keeps (per pixel 64 B of part records, rounded up to 64 pixels, 4 B of
+ *   list and rr_render_pixel_parts' own at K = 2; 12 B per 8x8 block), per entry of the largest padded list 32 B of records, 4 B of
+ *   the second list and rr_render_pixel_parts' own at K = 2 (128 B of accumulators, 24 B of slot table).  The host form adds 32 B per
+ *   pixel, and 4, 2 and 4 B for the outputs it is asked for.
+ * rr_render_adaptive_levels_device: the same on DEVICE buffers in stream order, under every rule of rr_render_adaptive_device.  Once
+ * `hip_stream` is synchronised the buffers hold byte for byte what the host form writes; the host form is this call behind a staging copy. */
+#define RR_MAX_ADAPTIVE_LEVELS 8u
+int rr_refine_sublist_device(rr_scene* scene, const uint32_t* list_dev, uint32_t count, const rr_radiance* parts_dev /* count * 2 */,
+                             float threshold, float* error_out_dev /* count, or NULL */,
+                             uint32_t* list_out_dev /* count rounded up to 64 entries */, uint32_t* count_out /* HOST */, void* hip_stream);
+int rr_render_adaptive_levels(rr_scene* scene, const rr_camera* camera, const rr_config* config,
+                              const uint16_t* level_samples, uint32_t n_levels, float threshold,
+                              const uint16_t* const* sample_xy_levels /* NULL, or n_levels pointers each a table or NULL */,
+                              rr_radiance* out /* width * height */, uint8_t* rgba8_out /* or NULL */, uint16_t* samples_out /* or NULL */,
+                              float* error_out /* or NULL */, uint32_t* level_pixels_out /* n_levels, HOST, or NULL */,
+                              const volatile int* cancel);
+int rr_render_adaptive_levels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config,
+                                     const uint16_t* level_samples, uint32_t n_levels, float threshold,
+                                     const uint16_t* const* sample_xy_levels /* NULL, or n_levels pointers each a table or NULL */,
+                                     rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */,
+                                     uint16_t* samples_out_dev /* or NULL */, float* error_out_dev /* or NULL */,
+                                     uint32_t* level_pixels_out /* n_levels, HOST, or NULL */, void* hip_stream, const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

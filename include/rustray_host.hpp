@@ -604,6 +604,46 @@ public:
                                          error_out_dev, n_refined, hip_stream, cancel);
     }
 
+    // A frame at a ladder of sample counts (rr_render_adaptive_levels): every pixel at levels[0], and level after level the pixels whose
+    // half-buffer error still exceeds `threshold` at the next count (2 to RR_MAX_ADAPTIVE_LEVELS counts, even and strictly increasing),
+    // on the device under one hold of the scene's lock.  config.samples is ignored.  Returns the records in row-major order, each byte
+    // for byte render_pixels' at the count `samples` names there; `error` is the RESIDUAL error, of the pixel's halves at that count;
+    // level_pixels gets the pixels rendered at each level.  samples, error, rgba8 and level_pixels are optional.  An empty vector =
+    // refused or failed (rr_last_error() says why).
+    std::vector<rr_radiance> render_adaptive_levels(const std::vector<uint16_t>& levels, float threshold, std::vector<uint16_t>* samples = nullptr,
+                                                    std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
+                                                    std::vector<uint32_t>* level_pixels = nullptr) const {
+        std::vector<rr_radiance> out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        const size_t n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (samples) samples->assign(n, 0);
+        if (error) error->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        std::vector<uint32_t> lp(levels.size() > RR_MAX_ADAPTIVE_LEVELS ? levels.size() : RR_MAX_ADAPTIVE_LEVELS, 0u);
+        if (rr_render_adaptive_levels(scene->handle(), &cam, &c, levels.data(), (uint32_t)levels.size(), threshold, nullptr, out.data(), rgba8 ? rgba8->data() : nullptr,
+                                      samples ? samples->data() : nullptr, error ? error->data() : nullptr, lp.data(), nullptr) != RR_OK) {
+            out.clear();
+            if (samples) samples->clear();
+            if (error) error->clear();
+            if (rgba8) rgba8->clear();
+            lp.clear();
+        } else lp.resize(levels.size());
+        if (level_pixels) *level_pixels = lp;
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_adaptive_levels_device): out_dev holds width * height records, level_pixels (HOST, or
+    // NULL) n_levels words; the other buffers are optional
+    int render_adaptive_levels_device(const uint16_t* levels, uint32_t n_levels, float threshold, rr_radiance* out_dev, uint8_t* rgba8_out_dev, uint16_t* samples_out_dev,
+                                      float* error_out_dev, uint32_t* level_pixels, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_adaptive_levels_device(scene->handle(), &cam, &c, levels, n_levels, threshold, nullptr, out_dev, rgba8_out_dev, samples_out_dev, error_out_dev,
+                                                level_pixels, hip_stream, cancel);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -35,3 +35,21 @@ def refine_list(error, threshold: float, width: int, height: int):
     if count % 64:
         xy = np.concatenate([xy, np.full(64 - count % 64, xy[-1], np.uint32)])
     return np.ascontiguousarray(xy, np.uint32), count
+
+
+def refine_sublist(error, threshold: float, list_xy, count: int):
+    """The list of a list: error (>= count,) the error of entry i of `list_xy` (packed x | y << 16) -> (pixel list, count): the entries
+    among the first `count` with error > threshold, in the order they had -- a sub-sequence of a block-ordered list is block-ordered --
+    padded to a multiple of 64 entries by repeating its last one, as refine_list pads; an empty result has no pad.  What lies at
+    `count` and beyond, the list's own pad, is never taken; duplicates are entries like any other; the coordinates are not interpreted.
+    An entry whose error equals the threshold is not taken."""
+    count = int(count)
+    xy = np.asarray(list_xy, np.uint32).reshape(-1)
+    e = np.asarray(error).reshape(-1)
+    if count < 0 or count > len(xy) or count > len(e):
+        raise ValueError(f"count {count} with {len(xy)} entries and {len(e)} errors")
+    out = xy[:count][e[:count].astype(np.float32) > np.float32(threshold)]   # (NaN > threshold is False; the threshold as the library takes it, in binary32)
+    taken = int(len(out))
+    if taken % 64:
+        out = np.concatenate([out, np.full(64 - taken % 64, out[-1], np.uint32)])
+    return np.ascontiguousarray(out, np.uint32), taken

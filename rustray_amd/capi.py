@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -42,7 +42,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -132,6 +132,12 @@ def lib():
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
             L.rr_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_render_adaptive_levels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_refine_sublist_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+            L.rr_render_adaptive_levels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_adaptive_levels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -196,6 +202,22 @@ def _sxy(sample_xy):
         return None, None
     a = np.ascontiguousarray(sample_xy, np.uint16)
     return a, a.ctypes.data_as(C.c_void_p)
+
+
+def _levels(levels, sample_xy_levels):
+    """The sample counts of rr_render_adaptive_levels as a uint16 array, and its table pointers: (counts, what must stay alive, the
+    array of n_levels pointers or None).  Values a uint16 cannot hold are refused here: the library would see other numbers."""
+    lv = [int(v) for v in levels]
+    if any(v < 0 or v > 0xffff for v in lv):
+        raise ValueError(f"levels {lv}: sample counts are uint16")
+    counts = np.ascontiguousarray(lv, np.uint16)
+    if sample_xy_levels is None:
+        return counts, None, None
+    if len(sample_xy_levels) != len(lv):
+        raise ValueError(f"{len(sample_xy_levels)} tables for {len(lv)} levels")
+    keep = [_sxy(t)[0] for t in sample_xy_levels]
+    ptrs = (C.c_void_p * max(len(lv), 1))(*[k.ctypes.data if k is not None else None for k in keep])
+    return counts, (keep, ptrs), C.cast(ptrs, C.c_void_p)
 
 
 class DeviceScene:
@@ -514,6 +536,54 @@ class DeviceScene:
                                                C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None, C.byref(count),
                                                C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
         return int(count.value)
+
+    # -- refinement level by level -----------------------------------------------------
+    def refine_sublist_device(self, list_ptr, count: int, parts_ptr, threshold: float, error_ptr, list_out_ptr, stream_ptr=None) -> int:
+        """rr_refine_sublist_device: adaptive.refine_sublist(adaptive.half_error(parts), threshold, list, count) on the device.  list_ptr:
+        `count` uint32 entries; parts_ptr: their count * 2 part records at n_parts = 2 (16-byte aligned); error_ptr: count float32 or None;
+        list_out_ptr: count rounded up to a multiple of 64 uint32, of which the padded result is written; raw device pointers, enqueued
+        on `stream_ptr`.  Returns the number of entries before the pad (the call waits for it)."""
+        taken = C.c_uint32(0)
+        _check(lib().rr_refine_sublist_device(self._h, C.c_void_p(list_ptr) if list_ptr else None, C.c_uint32(count), C.c_void_p(parts_ptr) if parts_ptr else None,
+                                              C.c_float(threshold), C.c_void_p(error_ptr) if error_ptr else None, C.c_void_p(list_out_ptr) if list_out_ptr else None,
+                                              C.byref(taken), C.c_void_p(stream_ptr) if stream_ptr else None))
+        return int(taken.value)
+
+    def render_adaptive_levels(self, cam: rr_camera, cfg: rr_config, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False, cancel=None) -> dict:
+        """rr_render_adaptive_levels: every pixel at levels[0], and level after level the pixels whose half-buffer error still exceeds
+        `threshold` at the next count (even, strictly increasing, 2 to 8 of them) -- one call on the device.  sample_xy_levels: None, or
+        one table or None per level.  Returns the dict of Raytracing.render_adaptive_levels in row-major order (color (n, 3) LINEAR,
+        depth, normal, object_id, samples uint32, error: the RESIDUAL error at the pixel's own count, level_pixels), and `rgba` (n, 4)
+        uint8, the frame's own bytes, with rgba8=True.  cfg.samples is ignored."""
+        n = int(cam.width) * int(cam.height)
+        lv, keep, tables = _levels(levels, sample_xy_levels)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        samples = np.zeros(max(n, 1), np.uint16)
+        error = np.zeros(max(n, 1), np.float32)
+        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
+        _check(lib().rr_render_adaptive_levels(self._h, C.byref(cam), C.byref(cfg), lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold), tables,
+                                               out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
+                                               error.ctypes.data_as(C.c_void_p), level_pixels.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
+                   samples=samples[:n].astype(np.uint32), error=error[:n], level_pixels=[int(v) for v in level_pixels[:len(lv)]])
+        if rgba8:
+            res["rgba"] = rgba[:n]
+        return res
+
+    def render_adaptive_levels_device(self, cam: rr_camera, cfg: rr_config, levels, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None, error_ptr=None,
+                                      stream_ptr=None, sample_xy_levels=None, cancel=None) -> list:
+        """rr_render_adaptive_levels_device: width * height 32-byte rr_radiance records (16-byte aligned) and, optionally, as many x 4 bytes,
+        uint16 sample counts and float32 errors, all raw device pointers; enqueued on `stream_ptr`.  Returns level_pixels, a list of ints."""
+        lv, keep, tables = _levels(levels, sample_xy_levels)
+        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
+        _check(lib().rr_render_adaptive_levels_device(self._h, C.byref(cam), C.byref(cfg), lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold), tables,
+                                                      C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
+                                                      C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None,
+                                                      level_pixels.ctypes.data_as(C.c_void_p), C.c_void_p(stream_ptr) if stream_ptr else None,
+                                                      C.byref(cancel) if cancel is not None else None))
+        return [int(v) for v in level_pixels[:len(lv)]]
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

@@ -1,8 +1,9 @@
 // rr_adaptive.h — the arithmetic of adaptive sampling that host and device share: the half-buffer error estimate of one pixel
-// (rustray_amd/adaptive.py: half_error) and the order in which a frame's pixels enter a refinement list (refine_list: 8x8 blocks
-// row-major, row-major inside a block).  Plain host logic, no HIP calls and no include of its own: k_refine_masks and k_refine_scatter
-// (rr_kernels.hip) apply these functions per lane, rr_api_adaptive.h sizes its buffers with them, and
-// tests/native/adaptive_order_test.cpp checks all of it on the CPU.
+// (rustray_amd/adaptive.py: half_error), the order in which a frame's pixels enter a refinement list (refine_list: 8x8 blocks
+// row-major, row-major inside a block), and where the entries of a list go in the list made from it (refine_sublist).  Plain host
+// logic, no HIP calls and no include of its own: k_refine_masks, k_refine_scatter, k_sublist_masks and k_sublist_scatter
+// (rr_kernels.hip) apply these functions per lane, rr_api_adaptive.h and rr_api_levels.h size their buffers with them, and
+// tests/native/adaptive_order_test.cpp and adaptive_sublist_test.cpp check all of it on the CPU.
 //
 // half_error is exact in binary32 step by step (a compare, a subtraction whose rounding is the IEEE one, a sign clear, a halving, a
 // maximum) and must be compiled without contraction (-ffp-contract=off, as the library is): host, device and numpy give the same bits.
@@ -55,3 +56,35 @@ RR_SETUP_HD unsigned long long refine_pixel_position(unsigned int x, unsigned in
 RR_SETUP_HD unsigned int refine_padded(unsigned int count) { return (count + 63u) & ~63u; }
 // entries a list of a width x height frame may need: every pixel, padded
 RR_SETUP_HD unsigned long long refine_capacity(unsigned int width, unsigned int height) { return ((unsigned long long)width * height + 63ull) & ~63ull; }
+
+// ---- the list of a list (adaptive.refine_sublist): entries 64 w .. 64 w + 63 of a list of `count` entries are wave w's, lane l holding
+// entry 64 w + l; the entries with error > threshold keep their order.  A wave's 64-bit mask has bit l set where lane l's entry is taken.
+RR_SETUP_HD unsigned int sublist_waves(unsigned int count) { return (count + 63u) >> 6; } // count <= 2^29
+// the entry of lane `lane` of wave `wave`; false = the lane lies behind the list (the caller's own pad is never looked at)
+RR_SETUP_HD bool sublist_lane_entry(unsigned int wave, unsigned int lane, unsigned int count, unsigned int* entry) {
+    const unsigned int i = (wave << 6) | lane;
+    if (i >= count) return false;
+    *entry = i;
+    return true;
+}
+// set bits of `mask` below bit `lane`: the place of a taken entry among its wave's (on the device: the two mbcnt instructions)
+RR_SETUP_HD unsigned int refine_mask_rank(unsigned long long mask, unsigned int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane; // (the hardware counts below the executing lane, which is `lane`)
+    return __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
+#else
+    return (unsigned int)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+#endif
+}
+// the wave whose taken entries end the output (offset: taken entries of the waves before it; total: all taken) writes the pad
+RR_SETUP_HD bool sublist_wave_is_last(unsigned long long mask, unsigned int offset, unsigned int total) {
+    return mask != 0ull && offset + (unsigned int)__builtin_popcountll(mask) == total;
+}
+// the lane of that wave whose entry is the output's last one
+RR_SETUP_HD unsigned int sublist_last_lane(unsigned long long mask) { return 63u - (unsigned int)__builtin_clzll(mask); } // mask != 0
+// lane `lane` of that wave writes one word of the pad at *at; false = the pad ends before this lane (fewer than 64 words: one per lane)
+RR_SETUP_HD bool sublist_pad_word(unsigned int total, unsigned int lane, unsigned int* at) {
+    if (total + lane >= refine_padded(total)) return false;
+    *at = total + lane;
+    return true;
+}

@@ -701,7 +701,7 @@ static int read_counters(const rr_scene* s, rr_frame_stats* st) {
     st->shadow_rays = c[RR_CNT_SHADOW]; st->shaded_hits = c[RR_CNT_SHADED];
     return RR_OK;
 }
-// sum += a, field by field: the statistics of a frame made of several passes (rr_render_progressive_tiles, rr_render_adaptive)
+// sum += a, field by field: the statistics of a frame made of several passes (rr_render_progressive_tiles, rr_render_adaptive, rr_render_adaptive_levels)
 static void add_pass_stats(rr_frame_stats* sum_, const rr_frame_stats& a) {
     rr_frame_stats& sum = *sum_;
     sum.primary_rays += a.primary_rays; sum.secondary_rays += a.secondary_rays; sum.shadow_rays += a.shadow_rays; sum.shaded_hits += a.shaded_hits;

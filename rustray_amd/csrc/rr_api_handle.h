@@ -113,8 +113,11 @@ struct QueryState {
 // frame so far its 64-bit refine mask, then its count (after k_refine_scan: its offset), then one word, the list's length (12 B per
 // block + 4).  The fused call keeps in addition the base frame's two part records per pixel (64 B), its list (4 B per pixel, padded)
 // and the fine records of the largest padded list so far (32 B per entry).  Written by rr_api_adaptive.h.
+// rr_refine_sublist_device and rr_render_adaptive_levels (rr_api_levels.h) use the same buffers -- scratch: 12 B per 64 entries of the list + 4;
+// parts: the frame's part records and then every list's (64 B per pixel, rounded up to 64 pixels) -- and a second list buffer for the
+// list made from a list (list2: 4 B per entry of the largest padded list so far).  Written by rr_api_levels.h as well.
 struct AdaptiveState {
-    DevBuf scratch, parts, list, fine;
+    DevBuf scratch, parts, list, fine, list2;
 };
 
 // ---- rr_render_multi (rr_api_multi.h)
@@ -133,7 +136,8 @@ struct FrameTiming {
     rr_frame_stats stats{};
     bool stats_final = false; // stats already holds the sums over the passes of rr_render_progressive_tiles (nothing to collect from the device)
     // rr_render_adaptive: what its base pass cost, collected while the call waited for the list's length; added ONCE to what the device
-    // reports for the fine pass when somebody asks (collect_stats_locked), so the call itself need not wait for its last launch
+    // reports for the fine pass when somebody asks (collect_stats_locked), so the call itself need not wait for its last launch.
+    // rr_render_adaptive_levels: the sums over every pass but its last, in the same way
     rr_frame_stats carry{};
     bool has_carry = false;
     bool profiling = false;

@@ -1205,6 +1205,77 @@ __global__ __launch_bounds__(RR_BLOCK) void k_record_bytes(const float4* __restr
 }
 
 // ---------------------------------------------------------------------------
+// kernels 5q .. 5s: the list of a list, and a level of a frame refined level by level (rr_refine_sublist_device, rr_render_adaptive_levels)
+// ---------------------------------------------------------------------------
+// adaptive.refine_sublist as the compaction above, over the entries of a LIST instead of the blocks of a frame: one wave per 64
+// consecutive entries, k_refine_scan between the two wave kernels as it is, no kernel waiting for another workgroup.  The entries'
+// coordinates are not interpreted: there is no frame here.
+//
+// 5q: parts = the K = 2 part records of the list (k_resolve_pixel_parts on a list: two float4 per part, entry i's halves at 2 i and 2 i + 1).
+// Lane l of wave w loads the colour float4 of the two halves of entry 64 w + l (64 consecutive bytes per lane, 4 KB per wave), error_out
+// (or NULL) gets half_error at the entry's index, and lane 0 stores the wave's mask and its popcount.  Lanes behind `count` load nothing
+// and flag nothing: what lies there -- the caller's own pad -- is never looked at.
+__global__ __launch_bounds__(RR_BLOCK) void k_sublist_masks(const float4* __restrict__ parts, uint32_t count, float threshold, float* __restrict__ error_out,
+                                                            unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        uint32_t i = 0u;
+        bool flag = false;
+        if (sublist_lane_entry(w, lane, count, &i)) {
+            const float4 a = parts[4ull * i], c = parts[4ull * i + 2];
+            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
+            const float e = half_error(ca, cb);
+            if (error_out) error_out[i] = e;
+            flag = e > threshold;
+        }
+        const unsigned long long mask = __ballot(flag);
+        if (lane == 0u) { masks[w] = mask; counts[w] = (uint32_t)__popcll(mask); }
+    }
+}
+
+// 5r: one wave per 64 entries again.  A lane whose bit is set writes its entry list[64 w + l] at offset + (set bits below the lane); the
+// wave that holds the last taken entry also writes the pad, copies of that entry up to the next multiple of 64.  list_out does not
+// overlap list (the host refuses it): a wave may write where another has yet to read.
+__global__ __launch_bounds__(RR_BLOCK) void k_sublist_scatter(const uint32_t* __restrict__ list, uint32_t count, const unsigned long long* __restrict__ masks,
+                                                              const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ total, uint32_t* __restrict__ list_out) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
+    const uint32_t taken = *total;
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        const unsigned long long mask = masks[w];
+        if (mask == 0ull) continue;
+        const uint32_t off = offsets[w];
+        uint32_t i = 0u, xy = 0u;
+        if (sublist_lane_entry(w, lane, count, &i)) xy = list[i];
+        if ((mask >> lane) & 1ull) list_out[off + refine_mask_rank(mask, lane)] = xy; // (a set bit is an entry before `count`: k_sublist_masks)
+        if (!sublist_wave_is_last(mask, off, taken)) continue;
+        const uint32_t last = (uint32_t)__shfl((int)xy, (int)sublist_last_lane(mask));
+        uint32_t at = 0u;
+        if (sublist_pad_word(taken, lane, &at)) list_out[at] = last;
+    }
+}
+
+// 5s: a level's records over the frame, in the manner of k_scatter_records: full record i (two float4) -> out at the pixel of list entry
+// i, for the n entries before the pad; samples_out (or NULL) gets the level's count there and error_out (or NULL) half_error of the
+// entry's two halves at this count, the bits k_sublist_masks computes from the same floats.  The entries before the pad are distinct
+// pixels of the frame: a sub-sequence of k_refine_scatter's list.
+__global__ __launch_bounds__(RR_BLOCK) void k_scatter_level(const uint32_t* __restrict__ list, uint32_t n, const float4* __restrict__ fine, const float4* __restrict__ parts,
+                                                            uint32_t width, uint16_t samples, float4* __restrict__ out, uint16_t* __restrict__ samples_out,
+                                                            float* __restrict__ error_out) {
+    for (uint32_t i = blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += gridDim.x * RR_BLOCK) {
+        const uint32_t xy = list[i];
+        const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
+        out[2ull * o] = fine[2ull * i];
+        out[2ull * o + 1] = fine[2ull * i + 1];
+        if (samples_out) samples_out[o] = samples;
+        if (error_out) {
+            const float4 a = parts[4ull * i], c = parts[4ull * i + 2];
+            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
+            error_out[o] = half_error(ca, cb);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // kernels 5d .. 5h: the streaming passes around the walks of the DEVICE-BUFFER ray queries (rr_trace_rays_device,
 // rr_trace_shadow_rays_device, rr_shade_rays_device, rr_surface_rays_device): the caller's 12-byte and 20-byte records are not a power of two, so a
 // workgroup moves its 256 rays' 768 or 1280 consecutive dwords with lane-strided dword accesses (every wave instruction covers 64

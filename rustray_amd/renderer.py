@@ -198,6 +198,52 @@ class Raytracing:
         return self.device_scene.render_adaptive(self.camera.c_struct(), self.config, base_samples, max_samples, threshold, sample_xy_base=sample_xy_base,
                                                  sample_xy_max=sample_xy_max, rgba8=rgba8)
 
+    def render_adaptive_levels(self, levels, threshold: float, sample_xy_levels=None) -> dict:
+        """A ladder of sample counts in one frame, as a HOST LOOP over library calls: every pixel at levels[0] in two halves (one
+        rr_render_pixel_parts call), and level after level the pixels whose half-buffer error (adaptive.half_error) still exceeds
+        `threshold`, again in two halves at the next count (one rr_render_pixel_parts call per list: adaptive.refine_list, then
+        adaptive.refine_sublist), until the list is empty or the top count is reached.  Returns the frame in row-major order:
+        dict(color (n, 3) LINEAR, depth, normal, object_id, samples: the count of the last level that rendered the pixel, error: the
+        estimate at THAT count -- the residual error --, level_pixels: the pixels of each level before the pad, padded: each level's
+        list length with it).  Every pixel is, bit for bit, the rr_render_pixels pixel at the count `samples` names."""
+        from . import adaptive
+        levels = [int(v) for v in levels]
+        tables = list(sample_xy_levels) if sample_xy_levels is not None else [None] * len(levels)
+        cam = self.camera.c_struct()
+        w, h = int(cam.width), int(cam.height)
+        cfg = rr_config.from_buffer_copy(self.config)
+        cfg.samples = levels[0]
+        base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=tables[0])
+        res = {k: base[k].copy() for k in ("color", "depth", "normal", "object_id")}
+        error = adaptive.half_error(base["parts"]["color"])
+        samples = np.full(w * h, levels[0], np.uint32)
+        level_pixels, padded = [w * h] + [0] * (len(levels) - 1), [w * h] + [0] * (len(levels) - 1)
+        xy, count = adaptive.refine_list(error, threshold, w, h)
+        for l in range(1, len(levels)):
+            if not count:
+                break
+            cfg.samples = levels[l]
+            fine = self.device_scene.render_pixel_parts(cam, cfg, pixels=xy, n_parts=2, sample_xy=tables[l])
+            level_pixels[l], padded[l] = count, len(xy)
+            at = (xy[:count] >> np.uint32(16)).astype(np.int64) * w + (xy[:count] & np.uint32(0xffff)).astype(np.int64)
+            for k in res:
+                res[k][at] = fine[k][:count]
+            samples[at] = levels[l]
+            e = adaptive.half_error(fine["parts"]["color"])
+            error[at] = e[:count]
+            xy, count = adaptive.refine_sublist(e, threshold, xy, count)
+        res["samples"] = samples
+        res["error"] = error
+        res["level_pixels"] = level_pixels
+        res["padded"] = padded
+        return res
+
+    def render_adaptive_levels_on_device(self, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False) -> dict:
+        """render_adaptive_levels as ONE library call (rr_render_adaptive_levels): every pass, list and scatter runs on the device under one
+        hold of the scene's lock.  Returns what render_adaptive_levels returns, field for field and bit for bit (without `padded`), and
+        `rgba`, the frame's own bytes, with rgba8=True."""
+        return self.device_scene.render_adaptive_levels(self.camera.c_struct(), self.config, levels, threshold, sample_xy_levels=sample_xy_levels, rgba8=rgba8)
+
     def pick(self, x: int, y: int):
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
@@ -729,6 +775,34 @@ def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, b
                                                     smp.data_ptr() if samples else None, err.data_ptr() if error else None,
                                                     torch.cuda.current_stream(dev).cuda_stream, sample_xy_base=sample_xy_base, sample_xy_max=sample_xy_max)
     out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "n_refined": count}
+    if rgba8:
+        out["rgba"] = rgba
+    if samples:
+        out["samples"] = smp
+    if error:
+        out["error"] = err
+    return out
+
+
+def render_adaptive_levels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False,
+                                 samples: bool = True, error: bool = True) -> dict:
+    """rr_render_adaptive_levels_device on torch's current stream: the frame at levels[0], and level after level the pixels whose
+    half-buffer error still exceeds `threshold` at the next count.  Returns torch tensors in row-major order, without a host copy of the
+    results: the dict of render_pixels_torch (records (n, 8) float32 and its views), level_pixels (a list of ints: the call waits for
+    them), and on request samples (n,) int16 (the count of the last level that rendered the pixel), error (n,) float32 (the residual
+    error, at that count) and rgba (n, 4) uint8."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
+        err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
+        level_pixels = device_scene.render_adaptive_levels_device(cam, cfg, levels, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
+                                                                  smp.data_ptr() if samples else None, err.data_ptr() if error else None,
+                                                                  torch.cuda.current_stream(dev).cuda_stream, sample_xy_levels=sample_xy_levels)
+    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "level_pixels": level_pixels}
     if rgba8:
         out["rgba"] = rgba
     if samples:
