@@ -48,7 +48,9 @@ extern "C" {
  * rr_refine_list_capacity, rr_refine_list_device, rr_render_adaptive and rr_render_adaptive_device came after those, again without a change
  * of any struct: a version-3 library may lack these four as well.
  * rr_refine_sublist_device, rr_render_adaptive_levels and rr_render_adaptive_levels_device came after those in the same way: a version-3
- * library may lack these three as well. */
+ * library may lack these three as well.
+ * rr_render_pixel_prefix, rr_render_pixel_prefix_device, rr_render_adaptive_prefix and rr_render_adaptive_prefix_device came after those in
+ * the same way: a version-3 library may lack these four as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -281,7 +283,7 @@ typedef struct rr_frame_stats {
     uint64_t batches;       /* device batches of primary samples the frame was cut into */
     uint64_t sliced_levels; /* depth levels whose children did not fit behind them in the ray arena at once */
     uint64_t binned_rays;   /* secondary rays that were re-ordered by (origin cell, direction octant) before being traced */
-    double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive and rr_render_adaptive_levels, also of the launches that make their lists */
+    double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive, rr_render_adaptive_levels and rr_render_adaptive_prefix, also of the launches that make their lists */
     double ms_trace_closest_level1;          /* the part of ms_trace_closest spent on depth level 1 (the primary rays) */
     uint64_t launches_trace_closest_level1;
     /* rr_render_multi only (on scenes[0]; zero after any other frame): how the per-device buffers reached scenes[0]'s device */
@@ -852,6 +854,70 @@ int rr_render_adaptive_levels(rr_scene* scene, const rr_camera* camera, const rr
 int rr_render_adaptive_levels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config,
                                      const uint16_t* level_samples, uint32_t n_levels, float threshold,
                                      const uint16_t* const* sample_xy_levels /* NULL, or n_levels pointers each a table or NULL */,
+                                     rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */,
+                                     uint16_t* samples_out_dev /* or NULL */, float* error_out_dev /* or NULL */,
+                                     uint32_t* level_pixels_out /* n_levels, HOST, or NULL */, void* hip_stream, const volatile int* cancel);
+
+/* Refinement that keeps its samples.  A level of rr_render_adaptive_levels is a frame of its own: its table and its cell size are those
+ * of its count, so a pixel that climbs 16 -> 32 -> 64 -> 128 is traced from scratch four times.  Here every level is a PREFIX of one
+ * frame of config->samples samples, and a pixel that climbs is only given the samples it does not have yet.
+ *
+ * rr_render_pixel_prefix: rr_render_pixels over samples 0 .. samples_used - 1 of the frame of config->samples samples.  Everything is
+ * that frame's: its table (sample_xy, or the built-in one for config->samples), its cell size, its depth-of-field offsets, its
+ * generator keys; only the sums are divided by samples_used.  This is the estimator a progressive preview shows after samples_used
+ * slices, at a count of the caller's choice and as records.
+ *   out[i]: the record over those samples; object_id is the id of sample samples_used - 1, the last one taken.
+ *   halves_out (or NULL): n_pixels * 2 records in the layout of rr_render_pixel_parts at K = 2; half h is the samples
+ *   {s < samples_used : s mod 2 == h}, resolved over samples_used / 2.  With it samples_used must be even: the two halves of a pixel
+ *   must be equal (RR_ERR_INVALID_ARGUMENT), and n_pixels * 2 > 2^30 is RR_ERR_UNSUPPORTED.
+ *   rgba8_out (or NULL): the frame's bytes of `out`, as rr_render_pixels writes them.
+ *   samples_used == config->samples: out and rgba8_out are byte for byte what rr_render_pixels writes, halves_out byte for byte what
+ *   rr_render_pixel_parts writes at K = 2.  samples_used == 0 or above config->samples: RR_ERR_INVALID_ARGUMENT.
+ *   Every other check, limit, list rule, lock rule, cancel behaviour and memory note is rr_render_pixels' (without halves_out) or
+ *   rr_render_pixel_parts' at K = 2 (with it).  rr_scene_last_stats reports primary_rays = n_pixels * samples_used.
+ *   Sample groups: the plan groups the samples_used / K samples of a slot, not the frame's; a count that no group divides runs with
+ *   G = 1.  The bits do not depend on G.
+ * rr_render_pixel_prefix_device: the same on DEVICE buffers in stream order, under every rule of rr_render_pixels_device; out_dev and
+ * halves_out_dev 16-byte aligned, pixel_xy_dev and rgba8_out_dev 4-byte aligned.
+ *
+ * rr_render_adaptive_prefix: a frame at the n_levels prefixes prefix_samples[0] < ... < prefix_samples[n_levels - 1] == config->samples
+ * of ONE frame (sample_xy: ONE table of config->samples entries, or NULL), 2 <= n_levels <= RR_MAX_ADAPTIVE_LEVELS.  Under one hold of
+ * the scene's lock, on one stream: the whole frame in two halves over samples [0, P0) and its list, made with the estimate and in the
+ * order of rr_refine_list_device; then for l = 1, 2, ... while the list is not empty: ONLY samples [P(l-1), Pl) of the listed pixels,
+ * added to the fixed-point sums those pixels already have (integer adds: the sums are those of a pixel traced from sample 0 in one
+ * go), the records at Pl written over the frame, and the sublist for the next level.  The sums stay on the device between levels.
+ *   out[y * width + x]: byte for byte what rr_render_pixel_prefix writes for that pixel at the samples_used that samples_out names
+ *   there.  rgba8_out (or NULL): its bytes at that count.  samples_out (or NULL): the last prefix the pixel reached.  error_out (or
+ *   NULL): the residual error of its halves at that count, as rr_render_adaptive_levels reports it.  level_pixels_out (or NULL, HOST,
+ *   n_levels words): as rr_render_adaptive_levels.
+ *   Config: samples IS used here: it is the frame every prefix is taken from, and the last prefix.
+ *   Checks: n_levels out of range, a prefix that is odd or below 2, a prefix not above the one before it, a last prefix other than
+ *   config->samples (the message names the level and the rule), a NaN threshold, out == NULL: RR_ERR_INVALID_ARGUMENT; config->samples
+ *   under rr_render's rule for its table; width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ *   A frame call, cancel, and the frames before and after: as rr_render_adaptive_levels.
+ *   rr_scene_last_stats reports the sums over all passes: primary_rays = width * height * P0 + the sum over the levels reached of
+ *   padded list length x (Pl - P(l-1)); with rr_tuning::kernel_timing, ms_binning holds the device time of the launches that make
+ *   the lists and move the sums.  The call waits inside where its passes wait and once per level but the last for the 4 bytes of a
+ *   count; a level's pass does not wait for a list check, the list being the library's own.
+ *   Device memory kept by the handle: rr_render_pixel_parts' own at K = 2 for the frame (128 B of accumulators and 24 B of slot table
+ *   per pixel), and per entry of the first padded list two sets of accumulators (128 B each), two lists (4 B each), 24 B of slot table;
+ *   12 B per 64 pixels.  The host form adds 32 B per pixel, and 4, 2 and 4 B for the outputs it is asked for.
+ * rr_render_adaptive_prefix_device: the same on DEVICE buffers in stream order, under every rule of rr_render_adaptive_levels_device. */
+int rr_render_pixel_prefix(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                           const uint32_t* pixel_xy /* or NULL */, uint32_t n_pixels, uint32_t samples_used,
+                           rr_radiance* out /* n_pixels */, rr_radiance* halves_out /* n_pixels * 2, or NULL */,
+                           uint8_t* rgba8_out /* or NULL */, const volatile int* cancel);
+int rr_render_pixel_prefix_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy,
+                                  const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels, uint32_t samples_used,
+                                  rr_radiance* out_dev /* n_pixels */, rr_radiance* halves_out_dev /* n_pixels * 2, or NULL */,
+                                  uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream, const volatile int* cancel);
+int rr_render_adaptive_prefix(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* ONE table, or NULL */,
+                              const uint16_t* prefix_samples, uint32_t n_levels, float threshold,
+                              rr_radiance* out /* width * height */, uint8_t* rgba8_out /* or NULL */, uint16_t* samples_out /* or NULL */,
+                              float* error_out /* or NULL */, uint32_t* level_pixels_out /* n_levels, HOST, or NULL */,
+                              const volatile int* cancel);
+int rr_render_adaptive_prefix_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* ONE table, or NULL */,
+                                     const uint16_t* prefix_samples, uint32_t n_levels, float threshold,
                                      rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */,
                                      uint16_t* samples_out_dev /* or NULL */, float* error_out_dev /* or NULL */,
                                      uint32_t* level_pixels_out /* n_levels, HOST, or NULL */, void* hip_stream, const volatile int* cancel);

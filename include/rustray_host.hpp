@@ -644,6 +644,75 @@ public:
                                                 level_pixels, hip_stream, cancel);
     }
 
+    // render_pixels over the first samples_used samples of the frame of config.samples samples (rr_render_pixel_prefix): that frame's table,
+    // cell size and generator keys, the sums divided by samples_used.  halves (or nullptr; samples_used must then be even) gets the two
+    // interleaved halves of those samples, halves[i * 2 + h]; rgba8 (or nullptr) the frame's bytes.  An empty vector = refused or failed.
+    std::vector<rr_radiance> render_pixel_prefix(const uint32_t* xy, size_t n, uint32_t samples_used, std::vector<rr_radiance>* halves = nullptr,
+                                                 std::vector<uint8_t>* rgba8 = nullptr) const {
+        std::vector<rr_radiance> out;
+        if (halves) halves->clear();
+        if (rgba8) rgba8->clear();
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        if (!xy) n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (halves) halves->resize(2 * n);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_render_pixel_prefix(scene->handle(), &cam, &c, nullptr, xy, (uint32_t)n, samples_used, out.data(), halves ? halves->data() : nullptr,
+                                   rgba8 ? rgba8->data() : nullptr, nullptr) != RR_OK) {
+            out.clear();
+            if (halves) halves->clear();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_pixel_prefix_device): xy_dev nullptr = the whole frame (n_pixels = width * height)
+    int render_pixel_prefix_device(const uint32_t* xy_dev, uint32_t n_pixels, uint32_t samples_used, rr_radiance* out_dev, rr_radiance* halves_out_dev,
+                                   uint8_t* rgba8_out_dev, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_pixel_prefix_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, samples_used, out_dev, halves_out_dev, rgba8_out_dev, hip_stream, cancel);
+    }
+
+    // A frame at a ladder of PREFIXES of one frame of config.samples samples (rr_render_adaptive_prefix): every pixel over its first
+    // prefixes[0] samples, and level after level only the samples up to the next prefix for the pixels whose half-buffer error still
+    // exceeds `threshold`, added to the sums those pixels keep on the device.  2 to RR_MAX_ADAPTIVE_LEVELS prefixes, even and strictly
+    // increasing, the last one config.samples.  Returns the records in row-major order, each byte for byte render_pixel_prefix's at the
+    // count `samples` names there; the optional outputs are those of render_adaptive_levels.  An empty vector = refused or failed.
+    std::vector<rr_radiance> render_adaptive_prefix(const std::vector<uint16_t>& prefixes, float threshold, std::vector<uint16_t>* samples = nullptr,
+                                                    std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
+                                                    std::vector<uint32_t>* level_pixels = nullptr) const {
+        std::vector<rr_radiance> out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        const size_t n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (samples) samples->assign(n, 0);
+        if (error) error->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        std::vector<uint32_t> lp(prefixes.size() > RR_MAX_ADAPTIVE_LEVELS ? prefixes.size() : RR_MAX_ADAPTIVE_LEVELS, 0u);
+        if (rr_render_adaptive_prefix(scene->handle(), &cam, &c, nullptr, prefixes.data(), (uint32_t)prefixes.size(), threshold, out.data(), rgba8 ? rgba8->data() : nullptr,
+                                      samples ? samples->data() : nullptr, error ? error->data() : nullptr, lp.data(), nullptr) != RR_OK) {
+            out.clear();
+            if (samples) samples->clear();
+            if (error) error->clear();
+            if (rgba8) rgba8->clear();
+            lp.clear();
+        } else lp.resize(prefixes.size());
+        if (level_pixels) *level_pixels = lp;
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_adaptive_prefix_device): the buffers of render_adaptive_levels_device
+    int render_adaptive_prefix_device(const uint16_t* prefixes, uint32_t n_levels, float threshold, rr_radiance* out_dev, uint8_t* rgba8_out_dev, uint16_t* samples_out_dev,
+                                      float* error_out_dev, uint32_t* level_pixels, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_adaptive_prefix_device(scene->handle(), &cam, &c, nullptr, prefixes, n_levels, threshold, out_dev, rgba8_out_dev, samples_out_dev, error_out_dev,
+                                                level_pixels, hip_stream, cancel);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -42,7 +42,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -137,6 +137,15 @@ def lib():
             L.rr_render_adaptive_levels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rr_render_adaptive_levels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_render_adaptive_prefix") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
+            L.rr_render_pixel_prefix.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_pixel_prefix_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_adaptive_prefix.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_adaptive_prefix_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -579,6 +588,83 @@ class DeviceScene:
         lv, keep, tables = _levels(levels, sample_xy_levels)
         level_pixels = np.zeros(max(len(lv), 1), np.uint32)
         _check(lib().rr_render_adaptive_levels_device(self._h, C.byref(cam), C.byref(cfg), lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold), tables,
+                                                      C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
+                                                      C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None,
+                                                      level_pixels.ctypes.data_as(C.c_void_p), C.c_void_p(stream_ptr) if stream_ptr else None,
+                                                      C.byref(cancel) if cancel is not None else None))
+        return [int(v) for v in level_pixels[:len(lv)]]
+
+    # -- refinement that keeps its samples ---------------------------------------------
+    def render_pixel_prefix(self, cam: rr_camera, cfg: rr_config, pixels=None, samples_used: int = 1, halves: bool = False, sample_xy=None, rgba8: bool = False,
+                            cancel=None):
+        """rr_render_pixel_prefix: render_pixels over samples 0 .. samples_used - 1 of the frame of cfg.samples samples (its table, its cell
+        size, its generator keys), the sums divided by samples_used -> the dict of render_pixels; with halves=True (samples_used even) plus
+        parts = the dict render_pixel_parts gives at n_parts = 2: half h = the samples s < samples_used with s % 2 == h."""
+        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
+        if pixels is not None:
+            xy = pack_pixels(pixels)
+            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        k = int(samples_used)
+        if k < 0 or k > 0xffffffff:
+            raise ValueError(f"samples_used {samples_used}")
+        out = np.zeros((max(n, 1), 8), np.float32)
+        parts = np.zeros((max(n, 1), 2, 8), np.float32) if halves else None
+        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_prefix(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(k), out.ctypes.data_as(C.c_void_p),
+                                            parts.ctypes.data_as(C.c_void_p) if halves else None, rgba.ctypes.data_as(C.c_void_p) if rgba8 else None,
+                                            C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+        if halves:
+            parts = parts[:n]
+            res["parts"] = dict(color=parts[:, :, 0:3].copy(), depth=parts[:, :, 3].copy(), normal=parts[:, :, 4:7].copy(),
+                                object_id=parts[:, :, 7].copy().view(np.uint32))
+        if rgba8:
+            res["rgba"] = rgba[:n]
+        return res
+
+    def render_pixel_prefix_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, samples_used: int, out_ptr, halves_ptr=None, rgba8_ptr=None,
+                                   stream_ptr=None, sample_xy=None, cancel=None):
+        """rr_render_pixel_prefix_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels
+        and, optionally, n_pixels * 2 32-byte rr_radiance records (16-byte aligned) and n_pixels x 4 bytes, all raw device pointers; enqueued
+        on `stream_ptr`."""
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
+                                                   C.c_uint32(samples_used), C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(halves_ptr) if halves_ptr else None,
+                                                   C.c_void_p(rgba8_ptr) if rgba8_ptr else None, C.c_void_p(stream_ptr) if stream_ptr else None,
+                                                   C.byref(cancel) if cancel is not None else None))
+
+    def render_adaptive_prefix(self, cam: rr_camera, cfg: rr_config, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False, cancel=None) -> dict:
+        """rr_render_adaptive_prefix: every pixel over the first prefix_samples[0] samples of the frame of cfg.samples samples, and level
+        after level ONLY the samples up to the next prefix (even, strictly increasing, 2 to 8 of them, the last one cfg.samples) for the
+        pixels whose half-buffer error still exceeds `threshold`, added to the sums those pixels have -- one call on the device.  sample_xy:
+        ONE table of cfg.samples entries or None.  Returns the dict of render_adaptive_levels."""
+        n = int(cam.width) * int(cam.height)
+        lv, _, _ = _levels(prefix_samples, None)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        samples = np.zeros(max(n, 1), np.uint16)
+        error = np.zeros(max(n, 1), np.float32)
+        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_adaptive_prefix(self._h, C.byref(cam), C.byref(cfg), p, lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold),
+                                               out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
+                                               error.ctypes.data_as(C.c_void_p), level_pixels.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
+        out = out[:n]
+        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
+                   samples=samples[:n].astype(np.uint32), error=error[:n], level_pixels=[int(v) for v in level_pixels[:len(lv)]])
+        if rgba8:
+            res["rgba"] = rgba[:n]
+        return res
+
+    def render_adaptive_prefix_device(self, cam: rr_camera, cfg: rr_config, prefix_samples, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None, error_ptr=None,
+                                      stream_ptr=None, sample_xy=None, cancel=None) -> list:
+        """rr_render_adaptive_prefix_device: the buffers of render_adaptive_levels_device.  Returns level_pixels, a list of ints."""
+        lv, _, _ = _levels(prefix_samples, None)
+        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_adaptive_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold),
                                                       C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
                                                       C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None,
                                                       level_pixels.ctypes.data_as(C.c_void_p), C.c_void_p(stream_ptr) if stream_ptr else None,

@@ -286,6 +286,40 @@ extern "C" int rh_render_adaptive_levels_device(void* h, float fov, const float*
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_adaptive_levels_device(levels, n_levels, threshold, out_dev, rgba8_dev, samples_dev, error_dev,
                                                                                                  level_pixels, stream, cancel);
 }
+// Raytracing::render_pixel_prefix: as rh_render_pixels, with halves = n * 2 records (or NULL); returns n, or -1 when the call was refused.
+// rh_render_adaptive_prefix and its device form: as rh_render_adaptive_levels, on the prefixes of the frame of cfg->samples samples.
+extern "C" int rh_render_pixel_prefix(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                      uint32_t w, uint32_t hgt, const uint32_t* xy, uint32_t n, uint32_t samples_used, rr_radiance* out, rr_radiance* halves, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> p; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.render_pixel_prefix(xy, n, samples_used, halves ? &p : nullptr, rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (halves) std::memcpy(halves, p.data(), p.size() * sizeof(rr_radiance));
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return (int)r.size();
+}
+extern "C" int rh_render_adaptive_prefix(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                         uint32_t w, uint32_t hgt, const uint16_t* prefixes, uint32_t n_levels, float threshold, rr_radiance* out, uint16_t* samples,
+                                         float* error, uint8_t* rgba8, uint32_t* level_pixels) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<uint16_t> sm; std::vector<float> er; std::vector<uint8_t> bytes; std::vector<uint32_t> lp;
+    const std::vector<rr_radiance> r = rt.render_adaptive_prefix(std::vector<uint16_t>(prefixes, prefixes + n_levels), threshold, samples ? &sm : nullptr, error ? &er : nullptr,
+                                                                 rgba8 ? &bytes : nullptr, &lp);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (samples) std::memcpy(samples, sm.data(), sm.size() * 2);
+    if (error) std::memcpy(error, er.data(), er.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    if (level_pixels) std::memcpy(level_pixels, lp.data(), lp.size() * 4);
+    return 0;
+}
+extern "C" int rh_render_adaptive_prefix_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                                uint32_t w, uint32_t hgt, const uint16_t* prefixes, uint32_t n_levels, float threshold, rr_radiance* out_dev,
+                                                uint8_t* rgba8_dev, uint16_t* samples_dev, float* error_dev, uint32_t* level_pixels, void* stream, const int* cancel) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_adaptive_prefix_device(prefixes, n_levels, threshold, out_dev, rgba8_dev, samples_dev, error_dev,
+                                                                                                 level_pixels, stream, cancel);
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -3,7 +3,9 @@
 // row-major, row-major inside a block), and where the entries of a list go in the list made from it (refine_sublist).  Plain host
 // logic, no HIP calls and no include of its own: k_refine_masks, k_refine_scatter, k_sublist_masks and k_sublist_scatter
 // (rr_kernels.hip) apply these functions per lane, rr_api_adaptive.h and rr_api_levels.h size their buffers with them, and
-// tests/native/adaptive_order_test.cpp and adaptive_sublist_test.cpp check all of it on the CPU.
+// tests/native/adaptive_order_test.cpp and adaptive_sublist_test.cpp check all of it on the CPU.  Last: where the accumulators of a
+// list's entries lie and where a compaction moves them (rr_render_adaptive_prefix: k_prefix_masks, k_prefix_compact, rr_api_prefix.h;
+// tests/native/adaptive_prefix_test.cpp).
 //
 // half_error is exact in binary32 step by step (a compare, a subtraction whose rounding is the IEEE one, a sign clear, a halving, a
 // maximum) and must be compiled without contraction (-ffp-contract=off, as the library is): host, device and numpy give the same bits.
@@ -86,5 +88,33 @@ RR_SETUP_HD unsigned int sublist_last_lane(unsigned long long mask) { return 63u
 RR_SETUP_HD bool sublist_pad_word(unsigned int total, unsigned int lane, unsigned int* at) {
     if (total + lane >= refine_padded(total)) return false;
     *at = total + lane;
+    return true;
+}
+
+// ---- resident accumulators (rr_render_adaptive_prefix): the pixels of a list keep their integer sums from level to level.  A SET holds
+// the two halves of every entry of a padded list in list order: entry i owns slots 2 i (samples s with s mod 2 == 0) and 2 i + 1, which
+// are the slots rr_render_pixel_parts gives it at K = 2.  With n slots a set is seven planes of n 8-byte words (colour r g b, normal
+// x y z, depth), then n 4-byte object ids, then n 4-byte flag words: 64 n bytes, and with n a multiple of 128 every plane starts on a
+// 16-byte boundary, so the two slots of an entry are one 16-byte access per plane (8 bytes for ids and flags).
+RR_SETUP_HD unsigned long long prefix_set_slots(unsigned int entries) { return 2ull * refine_padded(entries); } // n of the set of a list of `entries`
+RR_SETUP_HD unsigned long long prefix_set_bytes(unsigned long long n) { return 64ull * n; }
+enum { PREFIX_PLANES = 7 }; // 8-byte planes of a set
+RR_SETUP_HD unsigned long long prefix_plane_offset(unsigned int plane, unsigned long long n) { return 8ull * plane * n; } // bytes; plane < PREFIX_PLANES
+RR_SETUP_HD unsigned long long prefix_id_offset(unsigned long long n) { return 56ull * n; }
+RR_SETUP_HD unsigned long long prefix_flags_offset(unsigned long long n) { return 60ull * n; }
+// the first of the two slots of entry i (the other one follows it)
+RR_SETUP_HD unsigned long long prefix_entry_slot(unsigned int entry) { return 2ull * entry; }
+// Compaction of a set into the set of the list made from its list (sublist_* above give the wave, the lane's entry and the last wave):
+// the entry of lane `lane` of a wave with `mask`, `offset` taken entries before the wave; false = the lane's entry is not taken
+RR_SETUP_HD bool prefix_survivor_entry(unsigned long long mask, unsigned int offset, unsigned int lane, unsigned int* entry_out) {
+    if (!((mask >> lane) & 1ull)) return false;
+    *entry_out = offset + refine_mask_rank(mask, lane);
+    return true;
+}
+// The last wave's pad: lane `lane` copies the source entry *src (the wave's last taken one) to entry *dst of the new list and set;
+// false = the pad ends before this lane.  A pad entry is a duplicate like any other: traced, accumulated and never looked at.
+RR_SETUP_HD bool prefix_pad_entry(unsigned int wave, unsigned long long mask, unsigned int total, unsigned int lane, unsigned int* src, unsigned int* dst) {
+    if (!sublist_pad_word(total, lane, dst)) return false;
+    *src = (wave << 6) | sublist_last_lane(mask);
     return true;
 }

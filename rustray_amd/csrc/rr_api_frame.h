@@ -154,16 +154,25 @@ struct FrameIo {
     // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i, ending in
     // k_resolve_pixel_parts: `parts` gets the K part records of every pixel, `radiance` the pixel's full record
     uint32_t lg_parts; rr_radiance* parts;
+    // rr_render_pixel_prefix and rr_render_adaptive_prefix (rr_api_prefix.h): the samples [samples_from, samples_used) of the frame of
+    // config->samples samples, both multiples of K; samples_used == 0 = all of them.  The table, the cell size and the generator's keys
+    // stay the whole frame's; the object-id rule and the resolve take samples_used as the frame's count.
+    uint32_t samples_used, samples_from;
+    // ... its level passes: `resident` = accumulators that already hold the samples before samples_from (not cleared, n = the call's slots);
+    // own_list = the list is the library's own, made from pixels it has checked (no wait for a first bad entry); no_resolve = the caller
+    // reads the accumulators itself
+    const DAccum* resident; bool own_list, no_resolve;
 };
 static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
-    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr, 0u, nullptr};
+    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr, 0u, nullptr, 0u, 0u, nullptr, false, false};
 }
 
 // The caller's pixel list as the slot table of this call: buffers of the handle's own (pixel_xy, pixel_c), so the launches read nothing
 // of the caller's after the return and the cached region map (region_xy, slot_c, trace_order) is what it was for the next frame.
 // THE wait of a list call: 4 bytes, the first index outside the frame (pinned, h_count[8]); such a call is refused before any walk.
 // With parts every entry becomes 2^lg_parts slots (k_pixel_slots); `pixel_xy` may then be the region's own map (the whole frame in parts).
-static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n_entries, uint32_t lg_parts, hipStream_t st) {
+// trusted: a list the library made itself from pixels of the frame; nothing is read back and the call does not wait.
+static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n_entries, uint32_t lg_parts, hipStream_t st, bool trusted = false) {
     const uint64_t n = (uint64_t)n_entries << lg_parts; // slots
     HIP_TRY(s->frame.pixel_xy.reserve((size_t)n * 4));
     HIP_TRY(s->frame.pixel_c.reserve((size_t)n * 8));
@@ -173,6 +182,7 @@ static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t*
     hipLaunchKernelGGL(k_pixel_slots, dim3(grid), dim3(RR_BLOCK), 0, st, pixel_xy, n_entries, lg_parts, W, H, s->frame.pixel_xy.as<uint32_t>(), s->frame.pixel_c.as<float2>(),
                        s->frame.pixel_bad.as<uint32_t>());
     HIP_TRY(hipGetLastError());
+    if (trusted) return RR_OK;
     uint32_t* h = s->frame.h_count + 8;
     HIP_TRY(hipMemcpyAsync(h, s->frame.pixel_bad.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -238,8 +248,16 @@ static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sa
     return RR_OK;
 }
 
-// zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all
-static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool want_depth, bool want_id, hipStream_t st, DAccum* acc) {
+// zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all.
+// resident: the set to go on with instead, as it is (every plane present, n == npix); the work counters are zeroed all the same.
+static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool want_depth, bool want_id, hipStream_t st, DAccum* acc, const DAccum* resident = nullptr) {
+    if (resident) {
+        if (resident->n != npix || !resident->rgb || !resident->normal || !resident->depth || !resident->object_id || !resident->flags)
+            return fail(RR_ERR_DEVICE, "internal: resident accumulators of %llu slots for a pass of %u", resident->n, npix);
+        HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
+        *acc = *resident;
+        return RR_OK;
+    }
     HIP_TRY(s->frame.acc_rgb.reserve((size_t)npix * 24));
     HIP_TRY(s->frame.acc_normal.reserve((size_t)npix * 24));
     HIP_TRY(s->frame.acc_depth.reserve((size_t)npix * 8));
@@ -560,13 +578,14 @@ static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& i
 }
 
 // The frame's batches of primary rays, in order.  After a batch that ends on a whole slice of samples the pass hook
-// (if any) gets the frame resolved over the samples finished so far.
-static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io) {
+// (if any) gets the frame resolved over the samples finished so far.  first0: the primary index the batches start at, a whole number
+// of sample slices (a pass that goes on where resident accumulators stopped); the plan's total_primary indices follow it.
+static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_t first0 = 0) {
     rr_scene* s = f.s;
     const uint32_t npix = fr.n_region_pixels;
-    const uint64_t B = f.plan.B, total_primary = f.plan.total_primary;
+    const uint64_t B = f.plan.B, total_primary = first0 + f.plan.total_primary;
     const PassHook* hook = io.hook;
-    for (uint64_t first = 0; first < total_primary; first += B) {
+    for (uint64_t first = first0; first < total_primary; first += B) {
         if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
         const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
         RR_TRY(f.pool.start_batch());
@@ -616,7 +635,7 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     const uint32_t* slot_xy; // accumulator slot -> pixel, and the screen point of its centre: the list's own tables or the region's
     const float* slot_c;
     if (io.pixel_xy) {
-        RR_TRY(fill_pixel_slots(s, W, H, io.pixel_xy, io.n_pixels, io.lg_parts, st));
+        RR_TRY(fill_pixel_slots(s, W, H, io.pixel_xy, io.n_pixels, io.lg_parts, st, io.own_list));
         npix = io.n_pixels << io.lg_parts; slot_xy = s->frame.pixel_xy.as<uint32_t>(); slot_c = s->frame.pixel_c.as<float>();
     } else {
         RR_TRY(update_region_map(s, W, H, *io.region, st));
@@ -632,12 +651,17 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     DFrame fr = make_frame(cam, cfg);
     fr.n_region_pixels = npix;
     RR_TRY(upload_sample_table(s, fr, sample_xy, st));
+    // a prefix: samples [samples_from, used) of the frame.  The table above and the cell size are the whole frame's; from here on the frame's
+    // count is `used` (k_shade: the id is that of sample used - 1, as the oracle's samples_used has it; the resolve divides by it)
+    const uint32_t used = io.samples_used ? io.samples_used : cfg->samples;
+    fr.samples = used;
     DAccum acc;
     const bool radiance = io.radiance != nullptr; // rr_radiance holds all three aux means
-    RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc));
+    RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc,
+                              io.resident));
     FramePlan plan;
     rr_config plan_cfg = *cfg; // with parts the plan sees K x the slots and 1 / K of the samples; the frame constants keep the frame's S
-    plan_cfg.samples = (decltype(plan_cfg.samples))(cfg->samples >> io.lg_parts);
+    plan_cfg.samples = (decltype(plan_cfg.samples))((used - io.samples_from) >> io.lg_parts); // (a sample group must divide THIS range: plan_frame)
     RR_TRY(plan_queues(s, npix, &plan_cfg, hook ? hook->min_passes : 0u, &plan));
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
@@ -646,8 +670,8 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
                s->n_cus * RR_SHADE_GRID_WG};
     f.slot_xy = slot_xy;
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
-    RR_TRY(run_batches(f, fr, io));
-    launch_resolve(f, fr, io);
+    RR_TRY(run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix));
+    if (!io.no_resolve) launch_resolve(f, fr, io);
     HIP_TRY(hipEventRecord(s->timing.frame_b, st));
     HIP_TRY(hipGetLastError());
     // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)

@@ -116,8 +116,10 @@ struct QueryState {
 // rr_refine_sublist_device and rr_render_adaptive_levels (rr_api_levels.h) use the same buffers -- scratch: 12 B per 64 entries of the list + 4;
 // parts: the frame's part records and then every list's (64 B per pixel, rounded up to 64 pixels) -- and a second list buffer for the
 // list made from a list (list2: 4 B per entry of the largest padded list so far).  Written by rr_api_levels.h as well.
+// rr_render_adaptive_prefix (rr_api_prefix.h) uses scratch, list and list2 in the same way and keeps two sets of resident accumulators
+// (acc_set: 64 B per slot, two slots per entry of the first padded list; rr_adaptive.h has the layout), written in turn level by level.
 struct AdaptiveState {
-    DevBuf scratch, parts, list, fine, list2;
+    DevBuf scratch, parts, list, fine, list2, acc_set[2];
 };
 
 // ---- rr_render_multi (rr_api_multi.h)

@@ -30,7 +30,7 @@ static int check_parts_args(const char* fn, bool device, const rr_scene* s, cons
 static int render_pixel_parts_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
                                      uint32_t n_pixels, uint32_t lg_parts, rr_radiance* out, rr_radiance* parts_out, hipStream_t st, const volatile int* cancel) {
     const int rc = render_region_locked(s, cam, cfg, sample_xy,
-                                        FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, nullptr, lg_parts, parts_out}, st, cancel);
+                                        FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, nullptr, lg_parts, parts_out, 0u, 0u, nullptr, false, false}, st, cancel);
     if (rc != RR_OK) (void)hipStreamSynchronize(st);
     return rc;
 }

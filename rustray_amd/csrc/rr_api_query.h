@@ -510,7 +510,7 @@ static int check_pixels_args(const char* fn, bool device, const rr_scene* s, con
 // one call on buffers the device can address (the caller holds the lock); a call that ends early leaves the stream idle
 static int render_pixels_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
                                 uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8, hipStream_t st, const volatile int* cancel) {
-    const int rc = render_region_locked(s, cam, cfg, sample_xy, FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, rgba8, 0u, nullptr}, st, cancel);
+    const int rc = render_region_locked(s, cam, cfg, sample_xy, FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, rgba8, 0u, nullptr, 0u, 0u, nullptr, false, false}, st, cancel);
     if (rc != RR_OK) (void)hipStreamSynchronize(st);
     return rc;
 }

@@ -1276,6 +1276,119 @@ __global__ __launch_bounds__(RR_BLOCK) void k_scatter_level(const uint32_t* __re
 }
 
 // ---------------------------------------------------------------------------
+// kernels 5t, 5u: a level of a frame whose refined pixels KEEP their samples (rr_render_adaptive_prefix)
+// ---------------------------------------------------------------------------
+// The accumulators of a level stay on the device from level to level: entry i of the level's list owns slots 2 i and 2 i + 1 of `acc`
+// (rr_adaptive.h: the halves s mod 2 of rr_render_pixel_parts at K = 2), and the next level adds only the samples the entry does not have
+// yet.  So nothing here reads a float that another kernel wrote: the records, the error and the refine mask of an entry all come from its
+// integer sums in one pass, where k_resolve_pixel_parts, k_scatter_level and k_sublist_masks hand two part records per entry through HBM.
+// One wave per 64 consecutive entries, k_refine_scan between the two wave kernels as it is, no kernel waiting for another workgroup.
+// Level 0 is the whole frame in the region's slot order, which IS the list order of a frame (8x8 blocks row-major, row-major inside);
+// there the pixel of entry i is the slot table's word 2 i (xy_stride 2: k_pixel_slots wrote every entry twice), for a list it is list[i]
+// (xy_stride 1).  No block shape is assumed: a partial block's pixels are wherever the table says.
+//
+// the two slots of an entry: one 16-byte access per 8-byte plane, one 8-byte access for the ids and the flags
+struct PrefixEntry { long long w[2][PREFIX_PLANES]; uint32_t id[2], nf[2]; };
+RR_DEV void prefix_load_entry(const DAccum& acc, uint32_t i, PrefixEntry* e) {
+    const unsigned long long p = prefix_entry_slot(i);
+#pragma unroll
+    for (int k = 0; k < PREFIX_PLANES; k++) {
+        const long long* plane = k < 3 ? acc.rgb + (unsigned long long)k * acc.n : k < 6 ? acc.normal + (unsigned long long)(k - 3) * acc.n : acc.depth;
+        const longlong2 v = *(const longlong2*)(plane + p);
+        e->w[0][k] = v.x; e->w[1][k] = v.y;
+    }
+    const uint2 id = *(const uint2*)(acc.object_id + p), nf = *(const uint2*)(acc.flags + p);
+    e->id[0] = id.x; e->id[1] = id.y; e->nf[0] = nf.x; e->nf[1] = nf.y;
+}
+// The ids are NOT carried: a level's pass writes the id of its last sample where that sample's path ends in a hit, and a pixel whose
+// last sample hits nothing reports 0, as a frame rendered from cleared accumulators does.
+RR_DEV void prefix_store_entry(const DAccum& acc, uint32_t j, const PrefixEntry& e) {
+    const unsigned long long p = prefix_entry_slot(j);
+#pragma unroll
+    for (int k = 0; k < PREFIX_PLANES; k++) {
+        long long* plane = k < 3 ? acc.rgb + (unsigned long long)k * acc.n : k < 6 ? acc.normal + (unsigned long long)(k - 3) * acc.n : acc.depth;
+        longlong2 v; v.x = e.w[0][k]; v.y = e.w[1][k];
+        *(longlong2*)(plane + p) = v;
+    }
+    *(uint2*)(acc.object_id + p) = make_uint2(0u, 0u);
+    *(uint2*)(acc.flags + p) = make_uint2(e.nf[0], e.nf[1]);
+}
+
+// 5t: lane l of wave w resolves entry 64 w + l at `samples` samples: its halves over samples / 2 and its full record over `samples`,
+// through the functions k_resolve_pixel_parts uses on the same integers (the sum of the two slots and the OR of their flags are what one
+// slot would have held; the id lies in the slot of the last sample, the odd one).  The record goes to out at the entry's pixel, with
+// samples_out and error_out (either may be NULL) beside it as k_scatter_level writes them, and lane 0 stores the wave's mask of
+// half_error > threshold and its popcount.  Lanes behind `count` load nothing and flag nothing: the pad is never looked at, so every
+// pixel is written once.
+__global__ __launch_bounds__(RR_BLOCK) void k_prefix_masks(DAccum acc, const uint32_t* __restrict__ xy_table, uint32_t xy_stride, uint32_t count, uint32_t samples,
+                                                           float threshold, uint32_t width, float4* __restrict__ out, uint16_t* __restrict__ samples_out,
+                                                           float* __restrict__ error_out, unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
+    const float n_half = (float)(samples >> 1), n_full = (float)samples;
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        uint32_t i = 0u;
+        bool flag = false;
+        if (sublist_lane_entry(w, lane, count, &i)) {
+            PrefixEntry e;
+            prefix_load_entry(acc, i, &e);
+            float ca[3], cb[3], c[3];
+            const uint32_t nf = e.nf[0] | e.nf[1];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                ca[k] = resolve_color_sum(e.w[0][k], e.nf[0], k, n_half);
+                cb[k] = resolve_color_sum(e.w[1][k], e.nf[1], k, n_half);
+                c[k] = resolve_color_sum(e.w[0][k] + e.w[1][k], nf, k, n_full);
+            }
+            const f3 nn = resolve_normal_sum(e.w[0][3] + e.w[1][3], e.w[0][4] + e.w[1][4], e.w[0][5] + e.w[1][5], nf, n_full);
+            const float depth = resolve_depth_sum(e.w[0][6] + e.w[1][6], nf, n_full);
+            const uint32_t xy = xy_table[(unsigned long long)i * xy_stride];
+            const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
+            out[2ull * o] = make_float4(c[0], c[1], c[2], depth);
+            out[2ull * o + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(e.id[1]));
+            const float err = half_error(ca, cb);
+            if (samples_out) samples_out[o] = (uint16_t)samples;
+            if (error_out) error_out[o] = err;
+            flag = err > threshold;
+        }
+        const unsigned long long mask = __ballot(flag);
+        if (lane == 0u) { masks[w] = mask; counts[w] = (uint32_t)__popcll(mask); }
+    }
+}
+
+// 5u: one wave per 64 entries again.  A lane whose bit is set moves its entry to place offset + (set bits below the lane) of the next
+// level: the pixel into list_out, the two slots of every plane and the flags into `dst`, the set of the next list (dst.n = twice its
+// padded length, which the host knows: it has waited for *total).  The wave that holds the last taken entry also writes the pad: every
+// pad lane copies that entry once more, from `src`, up to the next multiple of 64.  `dst` and list_out overlap nothing that is read here.
+__global__ __launch_bounds__(RR_BLOCK) void k_prefix_compact(DAccum src, const uint32_t* __restrict__ xy_table, uint32_t xy_stride, uint32_t count,
+                                                             const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ offsets,
+                                                             const uint32_t* __restrict__ total, uint32_t* __restrict__ list_out, DAccum dst) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
+    const uint32_t taken = *total;
+    if (prefix_set_slots(taken) != dst.n) return; // (the host sized `dst` by this very word)
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        const unsigned long long mask = masks[w];
+        if (mask == 0ull) continue;
+        const uint32_t off = offsets[w];
+        uint32_t j = 0u;
+        if (prefix_survivor_entry(mask, off, lane, &j)) { // (a set bit is an entry before `count`: k_prefix_masks)
+            const uint32_t i = (w << 6) | lane;
+            PrefixEntry e;
+            prefix_load_entry(src, i, &e);
+            list_out[j] = xy_table[(unsigned long long)i * xy_stride];
+            prefix_store_entry(dst, j, e);
+        }
+        if (!sublist_wave_is_last(mask, off, taken)) continue;
+        uint32_t i = 0u;
+        if (prefix_pad_entry(w, mask, taken, lane, &i, &j)) {
+            PrefixEntry e;
+            prefix_load_entry(src, i, &e);
+            list_out[j] = xy_table[(unsigned long long)i * xy_stride];
+            prefix_store_entry(dst, j, e);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // kernels 5d .. 5h: the streaming passes around the walks of the DEVICE-BUFFER ray queries (rr_trace_rays_device,
 // rr_trace_shadow_rays_device, rr_shade_rays_device, rr_surface_rays_device): the caller's 12-byte and 20-byte records are not a power of two, so a
 // workgroup moves its 256 rays' 768 or 1280 consecutive dwords with lane-strided dword accesses (every wave instruction covers 64

@@ -244,6 +244,56 @@ class Raytracing:
         `rgba`, the frame's own bytes, with rgba8=True."""
         return self.device_scene.render_adaptive_levels(self.camera.c_struct(), self.config, levels, threshold, sample_xy_levels=sample_xy_levels, rgba8=rgba8)
 
+    def render_pixel_prefix(self, samples_used: int, pixels=None, halves: bool = False, rgba8: bool = False, sample_xy=None) -> dict:
+        """render_pixels over the first `samples_used` samples of the frame of config.samples samples (rr_render_pixel_prefix): that
+        frame's table, cell size and generator keys, the sums divided by samples_used; with halves=True plus `parts`, the two
+        interleaved halves of those samples as render_pixel_parts gives them at n_parts = 2."""
+        return self.device_scene.render_pixel_prefix(self.camera.c_struct(), self.config, pixels=pixels, samples_used=samples_used, halves=halves,
+                                                     sample_xy=sample_xy, rgba8=rgba8)
+
+    def render_adaptive_prefix(self, prefix_samples, threshold: float, sample_xy=None) -> dict:
+        """A ladder of PREFIXES of one frame of config.samples samples (the last prefix), as a HOST LOOP over library calls that renders
+        each prefix from scratch: every pixel over the first prefix_samples[0] samples in two halves (one rr_render_pixel_prefix call),
+        and level after level the pixels whose half-buffer error (adaptive.half_error) still exceeds `threshold`, over the next
+        prefix (adaptive.refine_list, then adaptive.refine_sublist), until the list is empty or the whole frame is reached.  Returns
+        the dict of render_adaptive_levels.  Every pixel is, bit for bit, the rr_render_pixel_prefix pixel at the count `samples`
+        names.  This is the yardstick of render_adaptive_prefix_on_device, which traces every sample once."""
+        from . import adaptive
+        prefixes = [int(v) for v in prefix_samples]
+        cam = self.camera.c_struct()
+        w, h = int(cam.width), int(cam.height)
+        if not prefixes or prefixes[-1] != int(self.config.samples):
+            raise ValueError(f"prefix_samples {prefixes}: the last prefix must be config.samples = {int(self.config.samples)}")
+        base = self.device_scene.render_pixel_prefix(cam, self.config, samples_used=prefixes[0], halves=True, sample_xy=sample_xy)
+        res = {k: base[k].copy() for k in ("color", "depth", "normal", "object_id")}
+        error = adaptive.half_error(base["parts"]["color"])
+        samples = np.full(w * h, prefixes[0], np.uint32)
+        level_pixels, padded = [w * h] + [0] * (len(prefixes) - 1), [w * h] + [0] * (len(prefixes) - 1)
+        xy, count = adaptive.refine_list(error, threshold, w, h)
+        for l in range(1, len(prefixes)):
+            if not count:
+                break
+            fine = self.device_scene.render_pixel_prefix(cam, self.config, pixels=xy, samples_used=prefixes[l], halves=True, sample_xy=sample_xy)
+            level_pixels[l], padded[l] = count, len(xy)
+            at = (xy[:count] >> np.uint32(16)).astype(np.int64) * w + (xy[:count] & np.uint32(0xffff)).astype(np.int64)
+            for k in res:
+                res[k][at] = fine[k][:count]
+            samples[at] = prefixes[l]
+            e = adaptive.half_error(fine["parts"]["color"])
+            error[at] = e[:count]
+            xy, count = adaptive.refine_sublist(e, threshold, xy, count)
+        res["samples"] = samples
+        res["error"] = error
+        res["level_pixels"] = level_pixels
+        res["padded"] = padded
+        return res
+
+    def render_adaptive_prefix_on_device(self, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False) -> dict:
+        """render_adaptive_prefix as ONE library call (rr_render_adaptive_prefix): the sums of a listed pixel stay on the device and every
+        level adds only the samples the pixel does not have yet.  Returns what render_adaptive_prefix returns, field for field and bit
+        for bit (without `padded`), and `rgba`, the frame's own bytes, with rgba8=True."""
+        return self.device_scene.render_adaptive_prefix(self.camera.c_struct(), self.config, prefix_samples, threshold, sample_xy=sample_xy, rgba8=rgba8)
+
     def pick(self, x: int, y: int):
         """Raytracing::pick (src/raytracing.rs:237-273): Some((id, distance)) or None."""
         r = self.device_scene.pick(self.camera.c_struct(), x, y)
@@ -802,6 +852,32 @@ def render_adaptive_levels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_co
         level_pixels = device_scene.render_adaptive_levels_device(cam, cfg, levels, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
                                                                   smp.data_ptr() if samples else None, err.data_ptr() if error else None,
                                                                   torch.cuda.current_stream(dev).cuda_stream, sample_xy_levels=sample_xy_levels)
+    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "level_pixels": level_pixels}
+    if rgba8:
+        out["rgba"] = rgba
+    if samples:
+        out["samples"] = smp
+    if error:
+        out["error"] = err
+    return out
+
+
+def render_adaptive_prefix_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False,
+                                 samples: bool = True, error: bool = True) -> dict:
+    """rr_render_adaptive_prefix_device on torch's current stream: the frame over its first prefix_samples[0] samples, and level after
+    level only the samples up to the next prefix for the pixels whose half-buffer error still exceeds `threshold`.  Returns what
+    render_adaptive_levels_torch returns."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
+        err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
+        level_pixels = device_scene.render_adaptive_prefix_device(cam, cfg, prefix_samples, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
+                                                                  smp.data_ptr() if samples else None, err.data_ptr() if error else None,
+                                                                  torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
     out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "level_pixels": level_pixels}
     if rgba8:
         out["rgba"] = rgba

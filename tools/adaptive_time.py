@@ -16,7 +16,14 @@ the one process (a drift of the clocks or of the machine's load meets all of the
 Per arm: wall ms (median and range), primary_rays, the pixels of each level and the pixels left above the threshold at their final
 count; then, with kernel_timing and again alternating, the device ms of the passes and of the list launches of the two fused arms.
 
-usage: adaptive_time.py [scene [width height base_samples max_samples]] [--levels S0,S1,...] [--threshold T] [--limit SECONDS]"""
+With --prefix the ladder is taken as PREFIXES of one frame of its top count, and refinement that keeps its samples is compared with the
+two calls above.  Three arms, alternating in the same way:
+  two-level     Raytracing.render_adaptive_on_device(first, last): rr_render_adaptive
+  levels        Raytracing.render_adaptive_levels_on_device(ladder): rr_render_adaptive_levels, every level a frame of its own
+  prefix        Raytracing.render_adaptive_prefix_on_device(ladder): rr_render_adaptive_prefix, every level the samples a pixel lacks
+Per arm the same figures.  The arms estimate on different samples, so their lists differ: compare rays and time at the pixels left.
+
+usage: adaptive_time.py [scene [width height base_samples max_samples]] [--levels S0,S1,...] [--prefix P0,P1,...] [--threshold T] [--limit SECONDS]"""
 import os
 import signal
 import sys
@@ -117,6 +124,51 @@ def levels_arms(rt, ds, scene, w, h, levels, threshold):
     ds.set_profiling(False)
 
 
+def prefix_arms(rt, ds, scene, w, h, ladder, threshold):
+    """The --prefix comparison: the two-level call, the level-by-level call and the call that keeps its samples, alternating."""
+    n, base, top = w * h, ladder[0], ladder[-1]
+    rt.config = _with(rt.config, top)        # the frame every prefix is taken from (the other two arms ignore config.samples)
+    arms = {"two-level": lambda: rt.render_adaptive_on_device(base, top, threshold),
+            "levels": lambda: rt.render_adaptive_levels_on_device(ladder, threshold),
+            "prefix": lambda: rt.render_adaptive_prefix_on_device(ladder, threshold)}
+    print(f"{scene} {w}x{h}, ladder {list(ladder)}, threshold {threshold:.6g}; {WARMUP} warm-up rounds, median of {FRAMES} (range), the arms alternating")
+    keep, wall, rays = {}, {tag: [] for tag in arms}, {}
+    for r in range(WARMUP + FRAMES):
+        for tag, call in arms.items():
+            t0 = time.perf_counter(); keep[tag] = call(); ms = (time.perf_counter() - t0) * 1e3
+            if r >= WARMUP:
+                wall[tag].append(ms)
+            rays[tag] = ds.stats()["primary_rays"]
+    px = keep["prefix"]
+    padded = [n] + [(c + 63) // 64 * 64 for c in px["level_pixels"][1:]]
+    assert rays["prefix"] == n * base + sum(p * (ladder[l] - ladder[l - 1]) for l, p in enumerate(padded) if l), (rays["prefix"], padded)
+    scratch = sum(p * s for p, s in zip(padded, ladder))
+    two_residual = rt.render_adaptive_levels_on_device((base, top), threshold)      # the two-level frame with the error of its refined pixels at `top`
+    left = {"two-level": int((two_residual["error"] > np.float32(threshold)).sum())}
+    pixels = {"two-level": [n, int(keep["two-level"]["n_refined"])]}
+    for tag in ("levels", "prefix"):
+        left[tag] = int((keep[tag]["error"] > np.float32(threshold)).sum()); pixels[tag] = keep[tag]["level_pixels"]
+    med = {}
+    for tag in arms:
+        med[tag], lo, hi = _median(wall[tag])
+        print(f"{tag:13s} wall {med[tag]:8.3f} ms ({lo:8.3f} .. {hi:8.3f})  primary_rays {rays[tag]:>11d}  level_pixels {pixels[tag]}  left above the threshold {left[tag]}")
+    print(f"prefix: its own lists rendered from scratch would cost {scratch} primary rays ({rays['prefix'] / scratch:.3f} kept)")
+    print(f"prefix / levels: rays {rays['prefix'] / rays['levels']:.3f}, wall {med['prefix'] / med['levels']:.3f};  prefix / two-level: rays {rays['prefix'] / rays['two-level']:.3f}, "
+          f"wall {med['prefix'] / med['two-level']:.3f}")
+    ds.set_profiling(True)
+    dev = {tag: ([], []) for tag in arms}
+    for r in range(WARMUP + FRAMES):
+        for tag in dev:
+            arms[tag]()
+            st = ds.stats()
+            if r >= WARMUP:
+                dev[tag][0].append(st["ms_total"]); dev[tag][1].append(st["ms_binning"])
+    for tag, (passes, lists) in dev.items():
+        (p, plo, phi), (l, llo, lhi) = _median(passes), _median(lists)
+        print(f"{tag:13s} kernel_timing: passes {p:8.3f} ms ({plo:.3f} .. {phi:.3f}), list launches {l * 1e3:7.1f} us ({llo * 1e3:.1f} .. {lhi * 1e3:.1f})")
+    ds.set_profiling(False)
+
+
 def _with(config, samples):
     c = rr_config.from_buffer_copy(config)
     c.samples = samples
@@ -127,12 +179,13 @@ def main():
     argv = list(sys.argv[1:])
     limit = _option(argv, "--limit", 300, int)
     levels = _option(argv, "--levels", None, lambda t: tuple(int(v) for v in t.split(",")))
+    prefix = _option(argv, "--prefix", None, lambda t: tuple(int(v) for v in t.split(",")))
     fixed_threshold = _option(argv, "--threshold", None, float)
     signal.alarm(limit)      # the probe's own time limit: SIGALRM ends the process
     scene = argv[0] if argv else "sponza_syn"
     w, h, base, top = (int(a) for a in argv[1:5]) if len(argv) > 4 else (1280, 720, 16, 128)
-    if levels:
-        base, top = levels[0], levels[-1]
+    if levels or prefix:
+        base, top = (levels or prefix)[0], (levels or prefix)[-1]
     fs, camera, cfg = bench.build_workload(scene, w, h, base, 1)
     rt = Raytracing(fs, camera, 0)
     try:
@@ -141,6 +194,9 @@ def main():
         first = ds.render_pixel_parts(camera.c_struct(), cfg, None, n_parts=2)
         err = adaptive.half_error(first["parts"]["color"])
         threshold = fixed_threshold if fixed_threshold is not None else float(np.quantile(err, 1.0 - FRACTION))
+        if prefix:
+            prefix_arms(rt, ds, scene, w, h, prefix, threshold)
+            return
         if levels:
             levels_arms(rt, ds, scene, w, h, levels, threshold)
             return
