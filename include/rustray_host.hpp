@@ -577,23 +577,9 @@ public:
     // and n_refined are optional.  An empty vector = refused or failed (rr_last_error() says why).
     std::vector<rr_radiance> render_adaptive(uint16_t base_samples, uint16_t max_samples, float threshold, std::vector<uint16_t>* samples = nullptr,
                                              std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr, uint32_t* n_refined = nullptr) const {
-        std::vector<rr_radiance> out;
-        const rr_camera cam = camera.c_struct();
-        const rr_config c = config.c_struct();
-        const size_t n = (size_t)cam.width * cam.height;
-        if (n == 0 || n > ((size_t)1 << 29)) return out;
-        out.resize(n);
-        if (samples) samples->assign(n, 0);
-        if (error) error->assign(n, 0.0f);
-        if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_render_adaptive(scene->handle(), &cam, &c, base_samples, max_samples, threshold, nullptr, nullptr, out.data(), rgba8 ? rgba8->data() : nullptr,
-                               samples ? samples->data() : nullptr, error ? error->data() : nullptr, n_refined, nullptr) != RR_OK) {
-            out.clear();
-            if (samples) samples->clear();
-            if (error) error->clear();
-            if (rgba8) rgba8->clear();
-        }
-        return out;
+        return fused_call(samples, error, rgba8, nullptr, 0, [&](const rr_camera* cam, const rr_config* c, rr_radiance* o, uint8_t* b, uint16_t* sm, float* e, uint32_t*) {
+            return rr_render_adaptive(scene->handle(), cam, c, base_samples, max_samples, threshold, nullptr, nullptr, o, b, sm, e, n_refined, nullptr);
+        });
     }
     // the same on DEVICE buffers, in stream order (rr_render_adaptive_device): out_dev holds width * height records; the other buffers are optional
     int render_adaptive_device(uint16_t base_samples, uint16_t max_samples, float threshold, rr_radiance* out_dev, uint8_t* rgba8_out_dev, uint16_t* samples_out_dev,
@@ -613,26 +599,9 @@ public:
     std::vector<rr_radiance> render_adaptive_levels(const std::vector<uint16_t>& levels, float threshold, std::vector<uint16_t>* samples = nullptr,
                                                     std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
                                                     std::vector<uint32_t>* level_pixels = nullptr) const {
-        std::vector<rr_radiance> out;
-        const rr_camera cam = camera.c_struct();
-        const rr_config c = config.c_struct();
-        const size_t n = (size_t)cam.width * cam.height;
-        if (n == 0 || n > ((size_t)1 << 29)) return out;
-        out.resize(n);
-        if (samples) samples->assign(n, 0);
-        if (error) error->assign(n, 0.0f);
-        if (rgba8) rgba8->assign(4 * n, 0);
-        std::vector<uint32_t> lp(levels.size() > RR_MAX_ADAPTIVE_LEVELS ? levels.size() : RR_MAX_ADAPTIVE_LEVELS, 0u);
-        if (rr_render_adaptive_levels(scene->handle(), &cam, &c, levels.data(), (uint32_t)levels.size(), threshold, nullptr, out.data(), rgba8 ? rgba8->data() : nullptr,
-                                      samples ? samples->data() : nullptr, error ? error->data() : nullptr, lp.data(), nullptr) != RR_OK) {
-            out.clear();
-            if (samples) samples->clear();
-            if (error) error->clear();
-            if (rgba8) rgba8->clear();
-            lp.clear();
-        } else lp.resize(levels.size());
-        if (level_pixels) *level_pixels = lp;
-        return out;
+        return fused_call(samples, error, rgba8, level_pixels, levels.size(), [&](const rr_camera* cam, const rr_config* c, rr_radiance* o, uint8_t* b, uint16_t* sm, float* e, uint32_t* lp) {
+            return rr_render_adaptive_levels(scene->handle(), cam, c, levels.data(), (uint32_t)levels.size(), threshold, nullptr, o, b, sm, e, lp, nullptr);
+        });
     }
     // the same on DEVICE buffers, in stream order (rr_render_adaptive_levels_device): out_dev holds width * height records, level_pixels (HOST, or
     // NULL) n_levels words; the other buffers are optional
@@ -683,26 +652,9 @@ public:
     std::vector<rr_radiance> render_adaptive_prefix(const std::vector<uint16_t>& prefixes, float threshold, std::vector<uint16_t>* samples = nullptr,
                                                     std::vector<float>* error = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
                                                     std::vector<uint32_t>* level_pixels = nullptr) const {
-        std::vector<rr_radiance> out;
-        const rr_camera cam = camera.c_struct();
-        const rr_config c = config.c_struct();
-        const size_t n = (size_t)cam.width * cam.height;
-        if (n == 0 || n > ((size_t)1 << 29)) return out;
-        out.resize(n);
-        if (samples) samples->assign(n, 0);
-        if (error) error->assign(n, 0.0f);
-        if (rgba8) rgba8->assign(4 * n, 0);
-        std::vector<uint32_t> lp(prefixes.size() > RR_MAX_ADAPTIVE_LEVELS ? prefixes.size() : RR_MAX_ADAPTIVE_LEVELS, 0u);
-        if (rr_render_adaptive_prefix(scene->handle(), &cam, &c, nullptr, prefixes.data(), (uint32_t)prefixes.size(), threshold, out.data(), rgba8 ? rgba8->data() : nullptr,
-                                      samples ? samples->data() : nullptr, error ? error->data() : nullptr, lp.data(), nullptr) != RR_OK) {
-            out.clear();
-            if (samples) samples->clear();
-            if (error) error->clear();
-            if (rgba8) rgba8->clear();
-            lp.clear();
-        } else lp.resize(prefixes.size());
-        if (level_pixels) *level_pixels = lp;
-        return out;
+        return fused_call(samples, error, rgba8, level_pixels, prefixes.size(), [&](const rr_camera* cam, const rr_config* c, rr_radiance* o, uint8_t* b, uint16_t* sm, float* e, uint32_t* lp) {
+            return rr_render_adaptive_prefix(scene->handle(), cam, c, nullptr, prefixes.data(), (uint32_t)prefixes.size(), threshold, o, b, sm, e, lp, nullptr);
+        });
     }
     // the same on DEVICE buffers, in stream order (rr_render_adaptive_prefix_device): the buffers of render_adaptive_levels_device
     int render_adaptive_prefix_device(const uint16_t* prefixes, uint32_t n_levels, float threshold, rr_radiance* out_dev, uint8_t* rgba8_out_dev, uint16_t* samples_out_dev,
@@ -758,6 +710,34 @@ public:
     bool update_lights(const std::vector<rr_light>& lights) { return scene->update_lights(lights) == RR_OK; }
     bool update_item_flags(const std::vector<uint8_t>& visible, const std::vector<uint8_t>& flip_normals) {
         return scene->update_item_flags(visible, flip_normals) == RR_OK;
+    }
+
+private:
+    // The host form of a fused call (render_adaptive, render_adaptive_levels, render_adaptive_prefix): the frame's vectors sized and zeroed,
+    // call(cam, config, out, rgba8, samples, error, level words) made, and every vector cleared if it fails.  level_pixels (or nullptr)
+    // gets the first n_levels of the level words.
+    template <class Call>
+    std::vector<rr_radiance> fused_call(std::vector<uint16_t>* samples, std::vector<float>* error, std::vector<uint8_t>* rgba8, std::vector<uint32_t>* level_pixels,
+                                        size_t n_levels, Call call) const {
+        std::vector<rr_radiance> out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        const size_t n = (size_t)cam.width * cam.height;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (samples) samples->assign(n, 0);
+        if (error) error->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        std::vector<uint32_t> lp(n_levels > RR_MAX_ADAPTIVE_LEVELS ? n_levels : RR_MAX_ADAPTIVE_LEVELS, 0u);
+        if (call(&cam, &c, out.data(), rgba8 ? rgba8->data() : nullptr, samples ? samples->data() : nullptr, error ? error->data() : nullptr, lp.data()) != RR_OK) {
+            out.clear();
+            if (samples) samples->clear();
+            if (error) error->clear();
+            if (rgba8) rgba8->clear();
+            lp.clear();
+        } else lp.resize(n_levels);
+        if (level_pixels) *level_pixels = lp;
+        return out;
     }
 };
 

@@ -229,6 +229,58 @@ def _levels(levels, sample_xy_levels):
     return counts, (keep, ptrs), C.cast(ptrs, C.c_void_p)
 
 
+def _ptr(p):
+    """A raw pointer (an int) as a ctypes argument; None or 0 is NULL."""
+    return C.c_void_p(p) if p else None
+
+
+def _flag(cancel):
+    """The optional cancel flag, a ctypes c_int, as a ctypes argument."""
+    return C.byref(cancel) if cancel is not None else None
+
+
+def _data(a):
+    """A host array's memory as a ctypes argument; None is NULL."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _pixel_list(cam, pixels):
+    """What a list call works on: (n, the packed list -- it must stay alive during the call --, its pointer); None is the whole frame."""
+    if pixels is None:
+        return int(cam.width) * int(cam.height), None, None
+    xy = pack_pixels(pixels)
+    return len(xy), xy, xy.ctypes.data_as(C.c_void_p)
+
+
+def _records(a):
+    """(..., 8) float32 rr_radiance records as the dict of shade_rays: copies, one array per field."""
+    return dict(color=a[..., 0:3].copy(), depth=a[..., 3].copy(), normal=a[..., 4:7].copy(), object_id=a[..., 7].copy().view(np.uint32))
+
+
+class _FusedOutputs:
+    """The host outputs of a fused adaptive call over the frame of `cam`: records, sample counts, errors, on request the bytes, and
+    n_counts uint32 words (n_refined, or level_pixels)."""
+
+    def __init__(self, cam, rgba8: bool, n_counts: int):
+        self.n = n = int(cam.width) * int(cam.height)
+        self.out = np.zeros((max(n, 1), 8), np.float32)
+        self.samples = np.zeros(max(n, 1), np.uint16)
+        self.error = np.zeros(max(n, 1), np.float32)
+        self.rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        self.counts = np.zeros(max(n_counts, 1), np.uint32)
+
+    def args(self):
+        """out, rgba8_out, samples_out, error_out and the counts, in the order every fused entry point takes them"""
+        return _data(self.out), _data(self.rgba), _data(self.samples), _data(self.error), self.counts.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def result(self, **counts) -> dict:
+        n = self.n
+        res = dict(_records(self.out[:n]), samples=self.samples[:n].astype(np.uint32), error=self.error[:n], **counts)
+        if self.rgba is not None:
+            res["rgba"] = self.rgba[:n]
+        return res
+
+
 class DeviceScene:
     """Owns one `rr_scene*` (scene uploaded to one GPU, acceleration structures built)."""
 
@@ -304,10 +356,10 @@ class DeviceScene:
     # -- one rank's region into device (torch) tensors ----------------------------
     def render_region_device(self, cam, cfg, region: rr_region, out_ptrs, stream_ptr=None, sample_xy=None):
         """out_ptrs: (rgba8, normal, depth, object_id) device pointers (ints, None allowed for aux)."""
-        fr = rr_frame(*[C.c_void_p(p) if p else None for p in out_ptrs])
+        fr = rr_frame(*[_ptr(p) for p in out_ptrs])
         keep, p = _sxy(sample_xy)
         _check(lib().rr_render_region_device(self._h, C.byref(cam), C.byref(cfg), p, C.byref(region), C.byref(fr),
-                                             C.c_void_p(stream_ptr) if stream_ptr else None, None))
+                                             _ptr(stream_ptr), None))
 
     def update_transforms(self, trans: np.ndarray, trans_inv: np.ndarray):
         """trans / trans_inv: (n_items, 4, 4) in math layout."""
@@ -425,9 +477,8 @@ class DeviceScene:
             ids_p = ids.ctypes.data_as(C.c_void_p)
         out = np.zeros((max(n, 1), 8), np.float32)
         _check(lib().rr_shade_rays(self._h, C.byref(cfg), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(rpr), ids_p,
-                                   out.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+                                   out.ctypes.data_as(C.c_void_p), _flag(cancel)))
+        return _records(out[:n])
 
     def surface_rays(self, origins, dirs, depth: int = 1):
         """rr_surface_rays: position, normals, uv and material of the closest hits of caller-supplied rays (depth 1 = a frame's primary
@@ -444,17 +495,12 @@ class DeviceScene:
         """rr_render_pixels: Raytracing::render(x, y) before its clamp, for the pixels named in `pixels` -- an (n, 2) integer array of
         (x, y) or an (n,) uint32 array of x | y << 16, in any order, duplicates allowed -- or for every pixel of the frame in row-major
         order (None) -> the dict of shade_rays (color LINEAR), plus `rgba` (n, 4) uint8, the frame's own bytes, with rgba8=True."""
-        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
-        if pixels is not None:
-            xy = pack_pixels(pixels)
-            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        n, xy, xy_p = _pixel_list(cam, pixels)
         out = np.zeros((max(n, 1), 8), np.float32)
         rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixels(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), out.ctypes.data_as(C.c_void_p),
-                                      rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+        _check(lib().rr_render_pixels(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), _data(out), _data(rgba), _flag(cancel)))
+        res = _records(out[:n])
         if rgba8:
             res["rgba"] = rgba[:n]
         return res
@@ -463,39 +509,30 @@ class DeviceScene:
         """rr_render_pixels_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels 32-byte
         rr_radiance records (16-byte aligned) and, optionally, n_pixels x 4 bytes, all raw device pointers; enqueued on `stream_ptr`."""
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixels_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
-                                             C.c_void_p(out_ptr), C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
-                                             C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+        _check(lib().rr_render_pixels_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), _ptr(out_ptr), _ptr(rgba8_ptr),
+                                             _ptr(stream_ptr), _flag(cancel)))
 
     def render_pixel_parts(self, cam: rr_camera, cfg: rr_config, pixels=None, n_parts: int = 2, sample_xy=None, cancel=None):
         """rr_render_pixel_parts: the pixels of render_pixels (a list, or None for the whole frame in row-major order) and, per pixel, the
         means over its n_parts interleaved sample subsets (part h = the samples s with s % n_parts == h) -> the dict of render_pixels
         plus parts = dict(color (n, K, 3) LINEAR, depth (n, K), normal (n, K, 3))."""
-        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
-        if pixels is not None:
-            xy = pack_pixels(pixels)
-            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        n, xy, xy_p = _pixel_list(cam, pixels)
         K = int(n_parts)
         if K < 0 or K > 0xffffffff:
             raise ValueError(f"n_parts {n_parts}")
         out = np.zeros((max(n, 1), 8), np.float32)
         parts = np.zeros((max(n, 1), max(min(K, 64), 1), 8), np.float32)
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixel_parts(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(K), out.ctypes.data_as(C.c_void_p),
-                                           parts.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
-        out, parts = out[:n], parts[:n]
-        return dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
-                    parts=dict(color=parts[:, :, 0:3].copy(), depth=parts[:, :, 3].copy(), normal=parts[:, :, 4:7].copy(),
-                               object_id=parts[:, :, 7].copy().view(np.uint32)))
+        _check(lib().rr_render_pixel_parts(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(K), _data(out), _data(parts), _flag(cancel)))
+        return dict(_records(out[:n]), parts=_records(parts[:n]))
 
     def render_pixel_parts_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, n_parts: int, out_ptr, parts_ptr, stream_ptr=None,
                                   sample_xy=None, cancel=None):
         """rr_render_pixel_parts_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels and
         n_pixels * n_parts 32-byte rr_radiance records (both 16-byte aligned), all raw device pointers; enqueued on `stream_ptr`."""
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixel_parts_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
-                                                  C.c_uint32(n_parts), C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(parts_ptr) if parts_ptr else None,
-                                                  C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+        _check(lib().rr_render_pixel_parts_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), C.c_uint32(n_parts), _ptr(out_ptr),
+                                                  _ptr(parts_ptr), _ptr(stream_ptr), _flag(cancel)))
 
     # -- adaptive sampling on the device ----------------------------------------------
     def refine_list_device(self, width: int, height: int, parts_ptr, threshold: float, error_ptr, list_ptr, stream_ptr=None) -> int:
@@ -504,9 +541,8 @@ class DeviceScene:
         refine_list_capacity(width, height) uint32, of which the padded list is written; raw device pointers, enqueued on `stream_ptr`.  Returns
         the number of entries before the pad (the call waits for it)."""
         count = C.c_uint32(0)
-        _check(lib().rr_refine_list_device(self._h, C.c_uint32(width), C.c_uint32(height), C.c_void_p(parts_ptr) if parts_ptr else None, C.c_float(threshold),
-                                           C.c_void_p(error_ptr) if error_ptr else None, C.c_void_p(list_ptr) if list_ptr else None, C.byref(count),
-                                           C.c_void_p(stream_ptr) if stream_ptr else None))
+        _check(lib().rr_refine_list_device(self._h, C.c_uint32(width), C.c_uint32(height), _ptr(parts_ptr), C.c_float(threshold), _ptr(error_ptr), _ptr(list_ptr),
+                                           C.byref(count), _ptr(stream_ptr)))
         return int(count.value)
 
     def render_adaptive(self, cam: rr_camera, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None,
@@ -515,23 +551,12 @@ class DeviceScene:
         `threshold` -- estimate, list, fine pass and scatter in one call on the device.  Returns the dict of Raytracing.render_adaptive in
         row-major order (color (n, 3) LINEAR, depth, normal, object_id, samples uint32, error) plus n_refined, and `rgba` (n, 4) uint8, the
         frame's own bytes, with rgba8=True.  cfg.samples is ignored."""
-        n = int(cam.width) * int(cam.height)
-        out = np.zeros((max(n, 1), 8), np.float32)
-        samples = np.zeros(max(n, 1), np.uint16)
-        error = np.zeros(max(n, 1), np.float32)
-        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
+        f = _FusedOutputs(cam, rgba8, 1)
         keep_b, pb = _sxy(sample_xy_base)
         keep_m, pm = _sxy(sample_xy_max)
-        count = C.c_uint32(0)
         _check(lib().rr_render_adaptive(self._h, C.byref(cam), C.byref(cfg), C.c_uint16(base_samples), C.c_uint16(max_samples), C.c_float(threshold), pb, pm,
-                                        out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
-                                        error.ctypes.data_as(C.c_void_p), C.byref(count), C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
-                   samples=samples[:n].astype(np.uint32), error=error[:n], n_refined=int(count.value))
-        if rgba8:
-            res["rgba"] = rgba[:n]
-        return res
+                                        *f.args(), _flag(cancel)))
+        return f.result(n_refined=int(f.counts[0]))
 
     def render_adaptive_device(self, cam: rr_camera, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None,
                                error_ptr=None, stream_ptr=None, sample_xy_base=None, sample_xy_max=None, cancel=None) -> int:
@@ -541,9 +566,7 @@ class DeviceScene:
         keep_m, pm = _sxy(sample_xy_max)
         count = C.c_uint32(0)
         _check(lib().rr_render_adaptive_device(self._h, C.byref(cam), C.byref(cfg), C.c_uint16(base_samples), C.c_uint16(max_samples), C.c_float(threshold), pb, pm,
-                                               C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
-                                               C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None, C.byref(count),
-                                               C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+                                               _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(samples_ptr), _ptr(error_ptr), C.byref(count), _ptr(stream_ptr), _flag(cancel)))
         return int(count.value)
 
     # -- refinement level by level -----------------------------------------------------
@@ -553,9 +576,8 @@ class DeviceScene:
         list_out_ptr: count rounded up to a multiple of 64 uint32, of which the padded result is written; raw device pointers, enqueued
         on `stream_ptr`.  Returns the number of entries before the pad (the call waits for it)."""
         taken = C.c_uint32(0)
-        _check(lib().rr_refine_sublist_device(self._h, C.c_void_p(list_ptr) if list_ptr else None, C.c_uint32(count), C.c_void_p(parts_ptr) if parts_ptr else None,
-                                              C.c_float(threshold), C.c_void_p(error_ptr) if error_ptr else None, C.c_void_p(list_out_ptr) if list_out_ptr else None,
-                                              C.byref(taken), C.c_void_p(stream_ptr) if stream_ptr else None))
+        _check(lib().rr_refine_sublist_device(self._h, _ptr(list_ptr), C.c_uint32(count), _ptr(parts_ptr), C.c_float(threshold), _ptr(error_ptr), _ptr(list_out_ptr),
+                                              C.byref(taken), _ptr(stream_ptr)))
         return int(taken.value)
 
     def render_adaptive_levels(self, cam: rr_camera, cfg: rr_config, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False, cancel=None) -> dict:
@@ -564,22 +586,11 @@ class DeviceScene:
         one table or None per level.  Returns the dict of Raytracing.render_adaptive_levels in row-major order (color (n, 3) LINEAR,
         depth, normal, object_id, samples uint32, error: the RESIDUAL error at the pixel's own count, level_pixels), and `rgba` (n, 4)
         uint8, the frame's own bytes, with rgba8=True.  cfg.samples is ignored."""
-        n = int(cam.width) * int(cam.height)
         lv, keep, tables = _levels(levels, sample_xy_levels)
-        out = np.zeros((max(n, 1), 8), np.float32)
-        samples = np.zeros(max(n, 1), np.uint16)
-        error = np.zeros(max(n, 1), np.float32)
-        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
-        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
-        _check(lib().rr_render_adaptive_levels(self._h, C.byref(cam), C.byref(cfg), lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold), tables,
-                                               out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
-                                               error.ctypes.data_as(C.c_void_p), level_pixels.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
-                   samples=samples[:n].astype(np.uint32), error=error[:n], level_pixels=[int(v) for v in level_pixels[:len(lv)]])
-        if rgba8:
-            res["rgba"] = rgba[:n]
-        return res
+        f = _FusedOutputs(cam, rgba8, len(lv))
+        _check(lib().rr_render_adaptive_levels(self._h, C.byref(cam), C.byref(cfg), _data(lv), C.c_uint32(len(lv)), C.c_float(threshold), tables, *f.args(),
+                                               _flag(cancel)))
+        return f.result(level_pixels=[int(v) for v in f.counts[:len(lv)]])
 
     def render_adaptive_levels_device(self, cam: rr_camera, cfg: rr_config, levels, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None, error_ptr=None,
                                       stream_ptr=None, sample_xy_levels=None, cancel=None) -> list:
@@ -587,11 +598,8 @@ class DeviceScene:
         uint16 sample counts and float32 errors, all raw device pointers; enqueued on `stream_ptr`.  Returns level_pixels, a list of ints."""
         lv, keep, tables = _levels(levels, sample_xy_levels)
         level_pixels = np.zeros(max(len(lv), 1), np.uint32)
-        _check(lib().rr_render_adaptive_levels_device(self._h, C.byref(cam), C.byref(cfg), lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold), tables,
-                                                      C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
-                                                      C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None,
-                                                      level_pixels.ctypes.data_as(C.c_void_p), C.c_void_p(stream_ptr) if stream_ptr else None,
-                                                      C.byref(cancel) if cancel is not None else None))
+        _check(lib().rr_render_adaptive_levels_device(self._h, C.byref(cam), C.byref(cfg), _data(lv), C.c_uint32(len(lv)), C.c_float(threshold), tables, _ptr(out_ptr),
+                                                      _ptr(rgba8_ptr), _ptr(samples_ptr), _ptr(error_ptr), _data(level_pixels), _ptr(stream_ptr), _flag(cancel)))
         return [int(v) for v in level_pixels[:len(lv)]]
 
     # -- refinement that keeps its samples ---------------------------------------------
@@ -600,10 +608,7 @@ class DeviceScene:
         """rr_render_pixel_prefix: render_pixels over samples 0 .. samples_used - 1 of the frame of cfg.samples samples (its table, its cell
         size, its generator keys), the sums divided by samples_used -> the dict of render_pixels; with halves=True (samples_used even) plus
         parts = the dict render_pixel_parts gives at n_parts = 2: half h = the samples s < samples_used with s % 2 == h."""
-        n, xy, xy_p = int(cam.width) * int(cam.height), None, None
-        if pixels is not None:
-            xy = pack_pixels(pixels)
-            n, xy_p = len(xy), xy.ctypes.data_as(C.c_void_p)
+        n, xy, xy_p = _pixel_list(cam, pixels)
         k = int(samples_used)
         if k < 0 or k > 0xffffffff:
             raise ValueError(f"samples_used {samples_used}")
@@ -611,15 +616,11 @@ class DeviceScene:
         parts = np.zeros((max(n, 1), 2, 8), np.float32) if halves else None
         rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixel_prefix(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(k), out.ctypes.data_as(C.c_void_p),
-                                            parts.ctypes.data_as(C.c_void_p) if halves else None, rgba.ctypes.data_as(C.c_void_p) if rgba8 else None,
-                                            C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32))
+        _check(lib().rr_render_pixel_prefix(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), C.c_uint32(k), _data(out), _data(parts), _data(rgba),
+                                            _flag(cancel)))
+        res = _records(out[:n])
         if halves:
-            parts = parts[:n]
-            res["parts"] = dict(color=parts[:, :, 0:3].copy(), depth=parts[:, :, 3].copy(), normal=parts[:, :, 4:7].copy(),
-                                object_id=parts[:, :, 7].copy().view(np.uint32))
+            res["parts"] = _records(parts[:n])
         if rgba8:
             res["rgba"] = rgba[:n]
         return res
@@ -630,33 +631,19 @@ class DeviceScene:
         and, optionally, n_pixels * 2 32-byte rr_radiance records (16-byte aligned) and n_pixels x 4 bytes, all raw device pointers; enqueued
         on `stream_ptr`."""
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_pixel_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, C.c_void_p(pixel_xy_ptr) if pixel_xy_ptr else None, C.c_uint32(n_pixels),
-                                                   C.c_uint32(samples_used), C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(halves_ptr) if halves_ptr else None,
-                                                   C.c_void_p(rgba8_ptr) if rgba8_ptr else None, C.c_void_p(stream_ptr) if stream_ptr else None,
-                                                   C.byref(cancel) if cancel is not None else None))
+        _check(lib().rr_render_pixel_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), C.c_uint32(samples_used),
+                                                   _ptr(out_ptr), _ptr(halves_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr), _flag(cancel)))
 
     def render_adaptive_prefix(self, cam: rr_camera, cfg: rr_config, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False, cancel=None) -> dict:
         """rr_render_adaptive_prefix: every pixel over the first prefix_samples[0] samples of the frame of cfg.samples samples, and level
         after level ONLY the samples up to the next prefix (even, strictly increasing, 2 to 8 of them, the last one cfg.samples) for the
         pixels whose half-buffer error still exceeds `threshold`, added to the sums those pixels have -- one call on the device.  sample_xy:
         ONE table of cfg.samples entries or None.  Returns the dict of render_adaptive_levels."""
-        n = int(cam.width) * int(cam.height)
         lv, _, _ = _levels(prefix_samples, None)
-        out = np.zeros((max(n, 1), 8), np.float32)
-        samples = np.zeros(max(n, 1), np.uint16)
-        error = np.zeros(max(n, 1), np.float32)
-        rgba = np.zeros((max(n, 1), 4), np.uint8) if rgba8 else None
-        level_pixels = np.zeros(max(len(lv), 1), np.uint32)
+        f = _FusedOutputs(cam, rgba8, len(lv))
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_adaptive_prefix(self._h, C.byref(cam), C.byref(cfg), p, lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold),
-                                               out.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba8 else None, samples.ctypes.data_as(C.c_void_p),
-                                               error.ctypes.data_as(C.c_void_p), level_pixels.ctypes.data_as(C.c_void_p), C.byref(cancel) if cancel is not None else None))
-        out = out[:n]
-        res = dict(color=out[:, 0:3].copy(), depth=out[:, 3].copy(), normal=out[:, 4:7].copy(), object_id=out[:, 7].copy().view(np.uint32),
-                   samples=samples[:n].astype(np.uint32), error=error[:n], level_pixels=[int(v) for v in level_pixels[:len(lv)]])
-        if rgba8:
-            res["rgba"] = rgba[:n]
-        return res
+        _check(lib().rr_render_adaptive_prefix(self._h, C.byref(cam), C.byref(cfg), p, _data(lv), C.c_uint32(len(lv)), C.c_float(threshold), *f.args(), _flag(cancel)))
+        return f.result(level_pixels=[int(v) for v in f.counts[:len(lv)]])
 
     def render_adaptive_prefix_device(self, cam: rr_camera, cfg: rr_config, prefix_samples, threshold: float, out_ptr, rgba8_ptr=None, samples_ptr=None, error_ptr=None,
                                       stream_ptr=None, sample_xy=None, cancel=None) -> list:
@@ -664,36 +651,33 @@ class DeviceScene:
         lv, _, _ = _levels(prefix_samples, None)
         level_pixels = np.zeros(max(len(lv), 1), np.uint32)
         keep, p = _sxy(sample_xy)
-        _check(lib().rr_render_adaptive_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, lv.ctypes.data_as(C.c_void_p), C.c_uint32(len(lv)), C.c_float(threshold),
-                                                      C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(rgba8_ptr) if rgba8_ptr else None,
-                                                      C.c_void_p(samples_ptr) if samples_ptr else None, C.c_void_p(error_ptr) if error_ptr else None,
-                                                      level_pixels.ctypes.data_as(C.c_void_p), C.c_void_p(stream_ptr) if stream_ptr else None,
-                                                      C.byref(cancel) if cancel is not None else None))
+        _check(lib().rr_render_adaptive_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, _data(lv), C.c_uint32(len(lv)), C.c_float(threshold), _ptr(out_ptr),
+                                                      _ptr(rgba8_ptr), _ptr(samples_ptr), _ptr(error_ptr), _data(level_pixels), _ptr(stream_ptr), _flag(cancel)))
         return [int(v) for v in level_pixels[:len(lv)]]
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
         """rr_surface_rays_device: as trace_rays_device, with n 128-byte rr_surface_hit records (16-byte aligned)."""
         _check(lib().rr_surface_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr),
-                                            C.c_void_p(stream_ptr) if stream_ptr else None))
+                                            _ptr(stream_ptr)))
 
     def trace_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
         """rr_trace_rays_device: raw device pointers (ints) of n * 3 float32 origins and directions and of n 20-byte rr_ray_hit records;
         enqueued on `stream_ptr` (a hipStream_t as int, None = the default stream).  Synchronise before reading the records on the host."""
         _check(lib().rr_trace_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr),
-                                          C.c_void_p(stream_ptr) if stream_ptr else None))
+                                          _ptr(stream_ptr)))
 
     def trace_shadow_rays_device(self, origins_ptr, dirs_ptr, max_distance_ptr, n: int, depth: int, out_ptr, stream_ptr=None):
         """rr_trace_shadow_rays_device: as trace_rays_device, with n float32 limits (None = no limit) and n 20-byte rr_shadow_hit records."""
-        _check(lib().rr_trace_shadow_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(max_distance_ptr) if max_distance_ptr else None,
-                                                 C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr), C.c_void_p(stream_ptr) if stream_ptr else None))
+        _check(lib().rr_trace_shadow_rays_device(self._h, C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), _ptr(max_distance_ptr),
+                                                 C.c_uint32(n), C.c_uint32(depth), C.c_void_p(out_ptr), _ptr(stream_ptr)))
 
     def shade_rays_device(self, cfg: rr_config, origins_ptr, dirs_ptr, n_results: int, rays_per_result: int, stream_ids_ptr, out_ptr, stream_ptr=None, cancel=None):
         """rr_shade_rays_device: n_results * rays_per_result rays, n_results uint32 stream ids (None = the result's index) and n_results
         32-byte rr_radiance records (16-byte aligned), all raw device pointers; enqueued on `stream_ptr`."""
         _check(lib().rr_shade_rays_device(self._h, C.byref(cfg), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_uint32(n_results), C.c_uint32(rays_per_result),
-                                          C.c_void_p(stream_ids_ptr) if stream_ids_ptr else None, C.c_void_p(out_ptr),
-                                          C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(cancel) if cancel is not None else None))
+                                          _ptr(stream_ids_ptr), C.c_void_p(out_ptr),
+                                          _ptr(stream_ptr), _flag(cancel)))
 
     def set_profiling(self, on: bool):
         self.set_tuning(kernel_timing=1 if on else 0)
@@ -735,7 +719,7 @@ def render_multi(device_scenes, cam: rr_camera, cfg: rr_config, sample_xy=None, 
 
 def deinterleave_device(width, height, tile_w, tile_h, n_ranks, elem_bytes, src_ptr, dst_ptr, device, stream_ptr=None):
     _check(lib().rr_deinterleave_device(width, height, tile_w, tile_h, n_ranks, elem_bytes, C.c_void_p(src_ptr),
-                                        C.c_void_p(dst_ptr), device, C.c_void_p(stream_ptr) if stream_ptr else None))
+                                        C.c_void_p(dst_ptr), device, _ptr(stream_ptr)))
 
 
 def deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, packs_ptr, pack_stride, section_offset, elem_bytes, dst_ptrs, device, stream_ptr=None):
@@ -748,7 +732,7 @@ def deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, packs_ptr
     L.rr_deinterleave_packed_device.argtypes = [C.c_uint32] * 5 + [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                                 C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
     _check(L.rr_deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, C.c_void_p(packs_ptr), C.c_uint64(pack_stride), so, eb, dp,
-                                           device, C.c_void_p(stream_ptr) if stream_ptr else None))
+                                           device, _ptr(stream_ptr)))
 
 
 def post_process(rgba: np.ndarray, normal, object_id, cavity: bool, outline: bool, device: int = 0) -> np.ndarray:
@@ -766,9 +750,9 @@ def post_process(rgba: np.ndarray, normal, object_id, cavity: bool, outline: boo
 
 
 def post_process_device(w, h, cavity, outline, rgba_ptr, normal_ptr, id_ptr, out_ptr, device=0, stream_ptr=None):
-    _check(lib().rr_post_process_device(w, h, int(cavity), int(outline), C.c_void_p(rgba_ptr), C.c_void_p(normal_ptr) if normal_ptr else None,
-                                        C.c_void_p(id_ptr) if id_ptr else None, C.c_void_p(out_ptr), device,
-                                        C.c_void_p(stream_ptr) if stream_ptr else None))
+    _check(lib().rr_post_process_device(w, h, int(cavity), int(outline), C.c_void_p(rgba_ptr), _ptr(normal_ptr),
+                                        _ptr(id_ptr), C.c_void_p(out_ptr), device,
+                                        _ptr(stream_ptr)))
 
 
 def math_probe(op: int, a, b=None, c=None, seed: int = 0, device: int = 0):

@@ -118,3 +118,19 @@ RR_SETUP_HD bool prefix_pad_entry(unsigned int wave, unsigned long long mask, un
     *src = (wave << 6) | sublist_last_lane(mask);
     return true;
 }
+
+// ---- the ladder of a call that refines level by level (rr_render_adaptive_levels: level_samples; rr_render_adaptive_prefix:
+// prefix_samples), host only: 2 .. max_levels counts, every one even and at least 2 (the two halves of a pixel must be equal), strictly
+// increasing.  The first fault in the order the calls report them, and in *at the entry it was found at (LADDER_ENTRY, LADDER_ORDER:
+// entry *at is not above entry *at - 1); nothing of `ladder` is read where n_levels is refused.
+enum LadderFault { LADDER_OK, LADDER_LEVELS, LADDER_NULL, LADDER_ENTRY, LADDER_ORDER };
+inline LadderFault ladder_fault(const unsigned short* ladder, unsigned int n_levels, unsigned int max_levels, unsigned int* at) {
+    if (n_levels < 2u || n_levels > max_levels) return LADDER_LEVELS;
+    if (!ladder) return LADDER_NULL;
+    for (unsigned int l = 0; l < n_levels; l++) {
+        *at = l;
+        if (ladder[l] < 2u || (ladder[l] & 1u)) return LADDER_ENTRY;
+        if (l && ladder[l] <= ladder[l - 1]) return LADDER_ORDER;
+    }
+    return LADDER_OK;
+}

@@ -1,9 +1,10 @@
 // rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
 // Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
 //         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
-//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; FrameIo, fill_pixel_slots, render_region_locked
-//         (rr_render_pixels, rr_api_query.h, is its other caller); rr_render_region_device,
-//         rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
+//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
+//         WHOLE_FRAME, IdleOnExit, fill_pixel_slots, render_region_locked (the pixel queries and the adaptive calls are its other callers);
+//         rr_render_region_device, rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, PassSums,
+//         collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
 //         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
 // Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
 //         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h,
@@ -147,29 +148,50 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
 //   end:   k_resolve into the device frame `out` (frame_layout: at the pixel's place in the whole frame, else compact; `hook`: the
 //          progressive preview), or k_resolve_pixels into `radiance` records and, on request, the frame's bytes in `rgba8` -- at the
 //          entry's index for a list, at y * width + x for a region.
+// Built by name: a maker below, then assignments of the fields that differ; every field left alone is null / 0 / false.
 struct FrameIo {
-    const rr_region* region; const uint32_t* pixel_xy; uint32_t n_pixels;
-    const rr_frame* out; bool frame_layout; const PassHook* hook;
-    rr_radiance* radiance; uint8_t* rgba8;
+    const rr_region* region = nullptr; const uint32_t* pixel_xy = nullptr; uint32_t n_pixels = 0u;
+    const rr_frame* out = nullptr; bool frame_layout = false; const PassHook* hook = nullptr;
+    rr_radiance* radiance = nullptr; uint8_t* rgba8 = nullptr;
     // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i, ending in
     // k_resolve_pixel_parts: `parts` gets the K part records of every pixel, `radiance` the pixel's full record
-    uint32_t lg_parts; rr_radiance* parts;
+    uint32_t lg_parts = 0u; rr_radiance* parts = nullptr;
     // rr_render_pixel_prefix and rr_render_adaptive_prefix (rr_api_prefix.h): the samples [samples_from, samples_used) of the frame of
     // config->samples samples, both multiples of K; samples_used == 0 = all of them.  The table, the cell size and the generator's keys
     // stay the whole frame's; the object-id rule and the resolve take samples_used as the frame's count.
-    uint32_t samples_used, samples_from;
+    uint32_t samples_used = 0u, samples_from = 0u;
     // ... its level passes: `resident` = accumulators that already hold the samples before samples_from (not cleared, n = the call's slots);
     // own_list = the list is the library's own, made from pixels it has checked (no wait for a first bad entry); no_resolve = the caller
     // reads the accumulators itself
-    const DAccum* resident; bool own_list, no_resolve;
+    const DAccum* resident = nullptr; bool own_list = false, no_resolve = false;
 };
 static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
-    return FrameIo{rg, nullptr, 0u, out, frame_layout, hook, nullptr, nullptr, 0u, nullptr, 0u, 0u, nullptr, false, false};
+    FrameIo io;
+    io.region = rg; io.out = out; io.frame_layout = frame_layout; io.hook = hook;
+    return io;
 }
+static const rr_region WHOLE_FRAME{8, 8, 1, 0}; // rr_render's slot order: 8x8 tiles, one wave = one tile of primary rays
+// records (and, on request, the frame's bytes) of a list's pixels, or of the whole frame where there is no list
+static FrameIo pixels_io(const uint32_t* pixel_xy, uint32_t n_pixels, rr_radiance* radiance, uint8_t* rgba8) {
+    FrameIo io;
+    io.region = pixel_xy ? nullptr : &WHOLE_FRAME; io.pixel_xy = pixel_xy; io.n_pixels = n_pixels; io.radiance = radiance; io.rgba8 = rgba8;
+    return io;
+}
+
+// "A call that ends early leaves the stream idle", by construction: armed at the top of a *_locked body, it waits for the stream on every
+// way out but `return idle.done(RR_OK)` -- a refusal, a failed launch or reservation, the cancel flag, whatever was launched before it.
+struct IdleOnExit {
+    hipStream_t st; bool armed = true;
+    explicit IdleOnExit(hipStream_t st_) : st(st_) {}
+    ~IdleOnExit() { if (armed) (void)hipStreamSynchronize(st); }
+    int done(int rc) { armed = rc != RR_OK; return rc; }
+    IdleOnExit(const IdleOnExit&) = delete;
+    IdleOnExit& operator=(const IdleOnExit&) = delete;
+};
 
 // The caller's pixel list as the slot table of this call: buffers of the handle's own (pixel_xy, pixel_c), so the launches read nothing
 // of the caller's after the return and the cached region map (region_xy, slot_c, trace_order) is what it was for the next frame.
-// THE wait of a list call: 4 bytes, the first index outside the frame (pinned, h_count[8]); such a call is refused before any walk.
+// THE wait of a list call: 4 bytes, the first index outside the frame (pinned, h_count[HC_PIXEL_BAD]); such a call is refused before any walk.
 // With parts every entry becomes 2^lg_parts slots (k_pixel_slots); `pixel_xy` may then be the region's own map (the whole frame in parts).
 // trusted: a list the library made itself from pixels of the frame; nothing is read back and the call does not wait.
 static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t* pixel_xy, uint32_t n_entries, uint32_t lg_parts, hipStream_t st, bool trusted = false) {
@@ -183,7 +205,7 @@ static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t*
                        s->frame.pixel_bad.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     if (trusted) return RR_OK;
-    uint32_t* h = s->frame.h_count + 8;
+    uint32_t* h = s->frame.h_count + HC_PIXEL_BAD;
     HIP_TRY(hipMemcpyAsync(h, s->frame.pixel_bad.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t bad = *h;
@@ -440,7 +462,7 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         }
         HIP_TRY(hipGetLastError());
         if (spawns && last) { // the next level's size, behind the last shade stage (run_level waits for it)
-            HIP_TRY(hipMemcpyAsync(s->frame.h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(s->frame.count_ready, st));
         }
         HIP_TRY(hipEventRecord(s->frame.stage_shaded[b], st));
@@ -539,7 +561,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
             // rays are still being traced, instead of leaving the device idle for a host round trip per level.
             if (spawns && c1 == s1) {
-                HIP_TRY(hipMemcpyAsync(s->frame.h_count, child_count, 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipEventRecord(s->frame.count_ready, st));
             }
             if (L) {
@@ -557,7 +579,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         }
         if (!spawns) continue;
         HIP_TRY(hipEventSynchronize(s->frame.count_ready));
-        const uint64_t m = *s->frame.h_count;
+        const uint64_t m = s->frame.h_count[HC_LEVEL];
         if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
         if (m == 0) continue;
         uint64_t level_base = child_base;
@@ -699,9 +721,8 @@ static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cf
     const size_t np = (size_t)cam->width * cam->height;
     rr_frame dev{};
     RR_TRY(stage_outputs(s, *out, np, false, &dev));
-    rr_region whole{8, 8, 1, 0}; // 8x8 tiles: one wave = one tile of primary rays (rr_render_pixels without a list takes the same region: WHOLE_FRAME)
     PassHook hook{fn, user, min_passes, out};
-    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&whole, &dev, true, fn ? &hook : nullptr), nullptr, cancel));
+    RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&WHOLE_FRAME, &dev, true, fn ? &hook : nullptr), nullptr, cancel));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return copy_outputs(*out, dev, np, nullptr);
 }
@@ -736,8 +757,17 @@ static void add_pass_stats(rr_frame_stats* sum_, const rr_frame_stats& a) {
     sum.ms_shade_level1 += a.ms_shade_level1; sum.launches_shade_level1 += a.launches_shade_level1;
     sum.ms_trace_shadow_level1 += a.ms_trace_shadow_level1; sum.launches_trace_shadow_level1 += a.launches_trace_shadow_level1;
 }
-// the device counters and launch timers of the frame (or pass) that ran last, into s->timing.stats; behind the fine pass of
-// rr_render_adaptive the base pass it carries is added, once, and the sums are final
+// The statistics of a call made of several passes are the sums over them.  add: the pass that was just collected (collect_stats_locked, the
+// stream idle).  carry: the last pass is still in flight -- the device reports it when somebody asks and the sums so far are added to it,
+// once (FrameTiming::carry), so the call need not wait for its last launch.  close: unless carried, no pass is in flight and the sums are final.
+struct PassSums {
+    rr_scene* s; rr_frame_stats sum{}; bool carried = false;
+    void add() { add_pass_stats(&sum, s->timing.stats); }
+    void carry() { s->timing.carry = sum; s->timing.has_carry = true; carried = true; }
+    void close() { if (!carried) { s->timing.stats = sum; s->timing.has_carry = false; s->timing.stats_final = true; } }
+};
+// the device counters and launch timers of the frame (or pass) that ran last, into s->timing.stats; behind a pass that carries the sums
+// of the passes before it (PassSums::carry) these are added, once, and the sums are final
 static int collect_stats_locked(rr_scene* s) {
     float ms = 0.0f;
     if (hipEventSynchronize(s->timing.frame_b) == hipSuccess && hipEventElapsedTime(&ms, s->timing.frame_a, s->timing.frame_b) == hipSuccess) s->timing.stats.ms_total = ms;
@@ -790,7 +820,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
     RR_TRY(stage_outputs(s, *out, np, true, &dev));
     const uint32_t n_tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
     const uint32_t P = std::max(1u, std::min(n_passes ? n_passes : 16u, n_tiles));
-    rr_frame_stats sum{};
+    PassSums sums{s};
     uint64_t done = 0;
     for (uint32_t k = 0; k < P; k++) {
         if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled");
@@ -798,10 +828,10 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
         RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&rg, &dev, true), nullptr, cancel));
         HIP_TRY(hipStreamSynchronize(nullptr));
         RR_TRY(collect_stats_locked(s));
-        add_pass_stats(&sum, s->timing.stats); // the frame's statistics are the sums over its passes
+        sums.add(); // the frame's statistics are the sums over its passes
         RR_TRY(copy_outputs(*out, dev, np, nullptr));
         done += rr_region_pixel_count(W, H, &rg);
-        s->timing.stats = sum; s->timing.stats_final = true;
+        sums.close();
         if (k + 1 < P) {
             InPass in_pass(s);
             if (on_pass(user, done * cfg->samples, (uint64_t)np * cfg->samples) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");

@@ -1,6 +1,6 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
 // Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, MultiState, FrameTiming
-//         and rr_scene, which holds one of each; check_intact.
+//         and rr_scene, which holds one of each; HC_* (the words of FrameState::h_count); check_intact.
 // Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
 
@@ -49,6 +49,15 @@ struct TopLevel {
     int depth_limit = RR_TLAS_MAX_DEPTH; // the top level's share of the traversal stack (build_scene_records), for its rebuilds
 };
 
+// the words of FrameState::h_count.  HC_LIST_COUNT serves every list (rr_api_adaptive.h, rr_api_levels.h, rr_api_prefix.h): the calls are
+// serialised by the scene's lock and each reads its count behind its own wait
+enum : uint32_t {
+    HC_LEVEL = 0,      // the next depth level's size (run_level)
+    HC_REACH = 4,      // 4 words: the reach of a query's rays (await_reach, rr_api_query.h)
+    HC_PIXEL_BAD = 8,  // the first entry of a pixel list outside the frame (fill_pixel_slots)
+    HC_LIST_COUNT = 9, // the length of a refinement list (await_list_count, rr_api_adaptive.h)
+};
+
 // ---- frame state (grown on demand, reused across frames).  Written by rr_api_frame.h; the ray queries (rr_api_query.h) borrow h_count and
 // last_stream, and rr_shade_rays the arena, the shadow queue, the accumulators and the counter pool (why that is safe: next to its body).
 struct FrameState {
@@ -81,7 +90,7 @@ struct FrameState {
     hipStream_t overlap_stream = nullptr;
     hipEvent_t stage_shaded[3] = {nullptr, nullptr, nullptr}, stage_traced[3] = {nullptr, nullptr, nullptr};
     uint32_t overlap_stages = 0; // level-1 stages of the last frame that ran on the two streams (rr_scene_overlap_stages)
-    uint32_t* h_count = nullptr; // pinned: level sizes read back between depth levels
+    uint32_t* h_count = nullptr; // pinned, 16 words, by HC_*: what the host waits for (every wait reads its word before the next one is issued)
     std::vector<uint16_t> table_cache; uint16_t table_samples = 0; // built-in sub-sample table of the last sample count
     // what every frame needs from the start (rr_scene_create, on the scene's device)
     int init() {

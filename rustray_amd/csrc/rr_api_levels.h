@@ -1,39 +1,34 @@
 // rr_api_levels.h — refine the noisy pixels of a frame level by level, on the device: the list made from a list (adaptive.refine_sublist
 // of rustray_amd/adaptive.py) and a frame at up to RR_MAX_ADAPTIVE_LEVELS sample counts as ONE call under one hold of the scene's lock.
 // Offers: rr_refine_sublist_device, rr_render_adaptive_levels, rr_render_adaptive_levels_device.
-// Needs:  rr_api_adaptive.h (refine_list_locked, check_refine_frame), rr_api_parts.h (render_pixel_parts_locked: the whole frame and every
-//         list in two parts), rr_api_query.h (check_query_pointers), rr_api_frame.h (check_frame_args, take_stream, ScopedTimer, add_pass_stats,
-//         collect_stats_locked), rr_adaptive.h, kernels 5m, 5p and 5q .. 5s of rr_kernels.hip.
+//         For rr_api_prefix.h: check_ladder.
+// Needs:  rr_api_adaptive.h (refine_list_locked, list_scratch, await_list_count; FusedOut, check_fused_outputs, device_fused_call,
+//         host_fused_call, finish_fused), rr_api_parts.h (render_pixel_parts_locked: the whole frame and every list in two parts),
+//         rr_api_query.h (check_query_pointers), rr_api_frame.h (check_frame_args, take_stream, ScopedTimer, IdleOnExit, PassSums,
+//         collect_stats_locked), rr_adaptive.h (ladder_fault), kernels 5m, 5p and 5q .. 5s of rr_kernels.hip.
 //
 // The sublist is three launches (k_sublist_masks, k_refine_scan, k_sublist_scatter) and one wait, for the 4 bytes of its length.  The
 // fused call is: the frame in parts at level_samples[0] (records straight into `out`) and its list as rr_render_adaptive makes it; then
 // per level, while the list is not empty, the padded list in parts at the level's count, k_scatter_level, and -- unless the level is
-// the last -- the sublist for the next one; k_record_bytes at the end.  The host form is the device form behind a staging copy in
-// buffers of the handle.
+// the last -- the sublist for the next one; k_record_bytes at the end.  The host form is the device form behind the staging copy of
+// every fused call (host_fused_call, rr_api_adaptive.h).
 
 // The sublist of `count` > 0 entries on stream st, into list_out (refine_padded(count) entries) and *count_out (host); the caller holds the
-// lock and has taken the stream.  THE wait of the call: 4 bytes (pinned, h_count[10]).  With kernel_timing the three launches are timed as
-// one re-ordering (rr_frame_stats::ms_binning).  Scratch: per 64 entries a mask and a count, then the total (12 B per wave + 4).
+// lock and has taken the stream.  With kernel_timing the three launches are timed as one re-ordering (rr_frame_stats::ms_binning).
+// Scratch: per 64 entries a mask and a count, then the total (list_scratch over the list's waves).
 static int refine_sublist_locked(rr_scene* s, const uint32_t* list, uint32_t count, const rr_radiance* parts, float threshold, float* error_out,
                                  uint32_t* list_out, uint32_t* count_out, hipStream_t st) {
     const uint32_t nw = sublist_waves(count);
-    HIP_TRY(s->adaptive.scratch.reserve(12ull * nw + 4u));
-    unsigned long long* masks = s->adaptive.scratch.as<unsigned long long>();
-    uint32_t* counts = (uint32_t*)(masks + nw);
-    uint32_t* total = counts + nw;
-    const int grid = (int)std::min<uint64_t>((nw + RR_BLOCK / RR_WAVE - 1) / (RR_BLOCK / RR_WAVE), (uint64_t)s->n_cus * 8u);
+    ListScratch ls;
+    RR_TRY(list_scratch(s, nw, &ls));
     {
         ScopedTimer t(s, st, TK_BINNING, false);
-        hipLaunchKernelGGL(k_sublist_masks, dim3(grid), dim3(RR_BLOCK), 0, st, (const float4*)parts, count, threshold, error_out, masks, counts);
-        hipLaunchKernelGGL(k_refine_scan, dim3(1), dim3(1024), 0, st, counts, nw, total);
-        hipLaunchKernelGGL(k_sublist_scatter, dim3(grid), dim3(RR_BLOCK), 0, st, list, count, masks, counts, total, list_out);
+        hipLaunchKernelGGL(k_sublist_masks, dim3(ls.grid), dim3(RR_BLOCK), 0, st, (const float4*)parts, count, threshold, error_out, ls.masks, ls.counts);
+        hipLaunchKernelGGL(k_refine_scan, dim3(1), dim3(1024), 0, st, ls.counts, nw, ls.total);
+        hipLaunchKernelGGL(k_sublist_scatter, dim3(ls.grid), dim3(RR_BLOCK), 0, st, list, count, ls.masks, ls.counts, ls.total, list_out);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t* h = s->frame.h_count + 10;
-    HIP_TRY(hipMemcpyAsync(h, total, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *count_out = *h;
-    return RR_OK;
+    return await_list_count(s, ls.total, st, count_out);
 }
 
 // (C linkage: the entry points of this layer are declared in include/rustray_hip.h, inside its extern "C" block, and a definition keeps the
@@ -58,46 +53,50 @@ int rr_refine_sublist_device(rr_scene* s, const uint32_t* list, uint32_t count, 
                                 {{list, "list_dev"}, {parts, "parts_dev"}, {error_out, "error_out_dev"}, {list_out, "list_out_dev"}}));
     const hipStream_t st = (hipStream_t)hip_stream;
     RR_TRY(take_stream(s, st));
+    IdleOnExit idle(st);
     const bool profiling = s->timing.profiling; // nothing of a frame's stats is touched: the launches are not timed here
     s->timing.profiling = false;
     const int rc = refine_sublist_locked(s, list, count, parts, threshold, error_out, list_out, count_out, st);
     s->timing.profiling = profiling;
-    if (rc != RR_OK) (void)hipStreamSynchronize(st);
-    return rc;
+    return idle.done(rc);
 } RR_GUARD_END("rr_refine_sublist_device")
 
-// what both forms check before the scene is looked at; `device`: the alignment rule of the device form
-static int check_levels_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* level_samples, uint32_t n_levels,
-                             float threshold, const uint16_t* const* tables, const rr_radiance* out, const uint8_t* rgba8, const uint16_t* samples_out,
-                             const float* error_out) {
-    if (!s || !cam || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_levels < 2u || n_levels > RR_MAX_ADAPTIVE_LEVELS)
-        return fail(RR_ERR_INVALID_ARGUMENT, "%s: n_levels %u must be from 2 to %u", fn, n_levels, RR_MAX_ADAPTIVE_LEVELS);
-    if (!level_samples) return fail(RR_ERR_INVALID_ARGUMENT, "%s: level_samples is NULL", fn);
-    rr_config c = *cfg; // (config->samples is ignored)
-    for (uint32_t l = 0; l < n_levels; l++) {
-        const unsigned S = level_samples[l];
-        if (S < 2u || (S & 1u))
-            return fail(RR_ERR_INVALID_ARGUMENT, "%s: level_samples[%u] = %u must be even and at least 2: the two halves of a pixel must be equal", fn, l, S);
-        if (l && S <= level_samples[l - 1])
-            return fail(RR_ERR_INVALID_ARGUMENT, "%s: level_samples[%u] = %u is not above level_samples[%u] = %u: the counts must increase strictly", fn, l, S, l - 1,
-                        (unsigned)level_samples[l - 1]);
-        c.samples = level_samples[l];
-        RR_TRY(check_frame_args(s, cam, &c, tables ? tables[l] : nullptr));
-    }
-    RR_TRY(check_refine_frame(fn, cam->width, cam->height, threshold));
-    if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "%s: out is required", fn);
-    if (device && (((uintptr_t)out & 15u) || ((uintptr_t)samples_out & 1u) || (((uintptr_t)rgba8 | (uintptr_t)error_out) & 3u)))
-        return fail(RR_ERR_INVALID_ARGUMENT, "%s: out_dev must be 16-byte aligned, rgba8_out_dev and error_out_dev 4-byte aligned and samples_out_dev 2-byte aligned", fn);
+// THE ladder rule of the calls that refine level by level (rr_adaptive.h: ladder_fault), as their refusals: `array` is the ladder's name
+// (level_samples, prefix_samples) and `noun` what its entries are (counts, prefixes).  Faults are reported in the ladder's order:
+// per_level(l) -- this call's own check of level l, or nothing -- runs for the levels before the first entry that breaks the rule.
+template <class PerLevel>
+static int check_ladder(const char* fn, const char* array, const char* noun, const uint16_t* ladder, uint32_t n_levels, PerLevel per_level) {
+    unsigned int at = 0;
+    const LadderFault f = ladder_fault(ladder, n_levels, RR_MAX_ADAPTIVE_LEVELS, &at);
+    if (f == LADDER_LEVELS) return fail(RR_ERR_INVALID_ARGUMENT, "%s: n_levels %u must be from 2 to %u", fn, n_levels, RR_MAX_ADAPTIVE_LEVELS);
+    if (f == LADDER_NULL) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s is NULL", fn, array);
+    for (uint32_t l = 0; l < (f == LADDER_OK ? n_levels : at); l++) RR_TRY(per_level(l));
+    if (f == LADDER_ENTRY)
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s[%u] = %u must be even and at least 2: the two halves of a pixel must be equal", fn, array, at, (unsigned)ladder[at]);
+    if (f == LADDER_ORDER)
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s[%u] = %u is not above %s[%u] = %u: the %s must increase strictly", fn, array, at, (unsigned)ladder[at], array, at - 1,
+                    (unsigned)ladder[at - 1], noun);
     return RR_OK;
 }
 
+// what both forms check before the scene is looked at
+static int check_levels_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* level_samples, uint32_t n_levels,
+                             float threshold, const uint16_t* const* tables, const FusedOut& o) {
+    if (!s || !cam || !cfg) return fail(RR_ERR_INVALID_ARGUMENT, "NULL argument");
+    RR_TRY(check_ladder(fn, "level_samples", "counts", level_samples, n_levels, [&](uint32_t l) {
+        rr_config c = *cfg; // (config->samples is ignored)
+        c.samples = level_samples[l];
+        return check_frame_args(s, cam, &c, tables ? tables[l] : nullptr);
+    }));
+    return check_fused_outputs(fn, device, cam, threshold, o);
+}
+
 // One call on buffers the device can address (the caller holds the lock); a call that ends early leaves the stream idle.  The stream is
-// idle behind every list's wait: there the finished passes' statistics are collected into `sum`.  The last level has no list behind it,
-// so its pass is reported by the device when somebody asks, with `sum` carried (FrameTiming::carry); the call returns without that wait.
+// idle behind every list's wait: there the finished passes' statistics are collected (PassSums).  The last level has no list behind it,
+// so its pass is reported by the device when somebody asks, with the sums carried; the call returns without that wait.
 static int render_adaptive_levels_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* level_samples, uint32_t n_levels, float threshold,
-                                         const uint16_t* const* tables, rr_radiance* out, uint8_t* rgba8, uint16_t* samples_out, float* error_out,
-                                         uint32_t* level_pixels_out, hipStream_t st, const volatile int* cancel) {
+                                         const uint16_t* const* tables, const FusedOut& o, hipStream_t st, const volatile int* cancel) {
+    IdleOnExit idle(st);
     const uint32_t W = cam->width, H = cam->height, N = W * H;
     const uint64_t cap = refine_capacity(W, H);
     HIP_TRY(s->adaptive.parts.reserve(64ull * cap)); // the frame's part records; then those of every list, none longer than `cap`
@@ -107,18 +106,16 @@ static int render_adaptive_levels_locked(rr_scene* s, const rr_camera* cam, cons
     uint32_t level_pixels[RR_MAX_ADAPTIVE_LEVELS] = {N, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     rr_config c = *cfg;
     c.samples = level_samples[0];
-    RR_TRY(render_pixel_parts_locked(s, cam, &c, tables ? tables[0] : nullptr, nullptr, N, 1u, out, parts, st, cancel));
+    RR_TRY(render_pixel_parts_locked(s, cam, &c, tables ? tables[0] : nullptr, nullptr, N, 1u, o.out, parts, st, cancel));
     uint32_t count = 0;
-    int rc = RR_OK;
-    if (samples_out && hipMemsetD16Async((hipDeviceptr_t)samples_out, level_samples[0], N, st) != hipSuccess) rc = fail(RR_ERR_DEVICE, "hipMemsetD16Async(samples_out) failed");
-    if (rc == RR_OK) rc = refine_list_locked(s, W, H, parts, threshold, error_out, lists[0], &count, st);
-    if (rc == RR_OK) rc = collect_stats_locked(s); // the stream is idle: what the pass cost, and the list's launches with it
-    if (rc != RR_OK) { (void)hipStreamSynchronize(st); return rc; }
-    rr_frame_stats sum = s->timing.stats;
-    bool carried = false; // the last pass is still in flight and `sum` is its carry
+    if (o.samples && hipMemsetD16Async((hipDeviceptr_t)o.samples, level_samples[0], N, st) != hipSuccess) return fail(RR_ERR_DEVICE, "hipMemsetD16Async(samples_out) failed");
+    RR_TRY(refine_list_locked(s, W, H, parts, threshold, o.error, lists[0], &count, st));
+    RR_TRY(collect_stats_locked(s)); // the stream is idle: what the pass cost, and the list's launches with it
+    PassSums sums{s};
+    sums.add();
     uint32_t cur = 0;
     for (uint32_t l = 1; l < n_levels && count; l++) {
-        if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled"); // (between levels the stream is idle)
+        if (cancel && *cancel) return fail(RR_ERR_CANCELLED, "cancelled");
         const uint32_t padded = refine_padded(count);
         HIP_TRY(s->adaptive.fine.reserve(32ull * padded));
         float4* fine = s->adaptive.fine.as<float4>();
@@ -126,72 +123,41 @@ static int render_adaptive_levels_locked(rr_scene* s, const rr_camera* cam, cons
         RR_TRY(render_pixel_parts_locked(s, cam, &c, tables ? tables[l] : nullptr, lists[cur], padded, 1u, (rr_radiance*)fine, parts, st, cancel));
         level_pixels[l] = count;
         const int grid = (int)std::min<uint64_t>((count + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
-        hipLaunchKernelGGL(k_scatter_level, dim3(grid), dim3(RR_BLOCK), 0, st, lists[cur], count, fine, (const float4*)parts, W, level_samples[l], (float4*)out, samples_out,
-                           error_out);
+        hipLaunchKernelGGL(k_scatter_level, dim3(grid), dim3(RR_BLOCK), 0, st, lists[cur], count, fine, (const float4*)parts, W, level_samples[l], (float4*)o.out, o.samples,
+                           o.error);
         if (l + 1 == n_levels) {
-            s->timing.carry = sum; s->timing.has_carry = true; // rr_scene_last_stats: the sums over all passes
-            carried = true;
+            sums.carry(); // rr_scene_last_stats: the sums over all passes
             break;
         }
         if (!lists[1]) { // the second list buffer: no list made from a list is longer than the first one made
             HIP_TRY(s->adaptive.list2.reserve(4ull * padded));
             lists[1] = s->adaptive.list2.as<uint32_t>();
         }
-        rc = refine_sublist_locked(s, lists[cur], count, parts, threshold, nullptr, lists[cur ^ 1u], &count, st);
-        if (rc == RR_OK) rc = collect_stats_locked(s);
-        if (rc != RR_OK) { (void)hipStreamSynchronize(st); return rc; }
-        add_pass_stats(&sum, s->timing.stats);
+        RR_TRY(refine_sublist_locked(s, lists[cur], count, parts, threshold, nullptr, lists[cur ^ 1u], &count, st));
+        RR_TRY(collect_stats_locked(s));
+        sums.add();
         cur ^= 1u;
     }
-    if (!carried) { s->timing.stats = sum; s->timing.has_carry = false; s->timing.stats_final = true; }
-    if (rgba8) {
-        const int grid = (int)std::min<uint64_t>((N + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
-        hipLaunchKernelGGL(k_record_bytes, dim3(grid), dim3(RR_BLOCK), 0, st, (const float4*)out, N, cfg->gamma_correction ? 1u : 0u, (uint32_t*)rgba8);
-    }
-    if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(st); return fail(RR_ERR_DEVICE, "rr_render_adaptive_levels: a launch failed"); }
-    if (level_pixels_out) memcpy(level_pixels_out, level_pixels, 4ull * n_levels);
-    return RR_OK;
+    sums.close();
+    return idle.done(finish_fused(s, "rr_render_adaptive_levels", cfg, N, o, level_pixels, n_levels, st));
 }
 
 int rr_render_adaptive_levels_device(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* level_samples, uint32_t n_levels, float threshold,
                                      const uint16_t* const* sample_xy_levels, rr_radiance* out, uint8_t* rgba8_out, uint16_t* samples_out, float* error_out,
                                      uint32_t* level_pixels_out, void* hip_stream, const volatile int* cancel) try {
-    RR_TRY(check_levels_args("rr_render_adaptive_levels_device", true, s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, out, rgba8_out, samples_out,
-                             error_out));
-    RR_TRY(not_in_pass(s, "rr_render_adaptive_levels_device"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, "rr_render_adaptive_levels_device",
-                                {{out, "out_dev"}, {rgba8_out, "rgba8_out_dev"}, {samples_out, "samples_out_dev"}, {error_out, "error_out_dev"}}));
-    return render_adaptive_levels_locked(s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, out, rgba8_out, samples_out, error_out, level_pixels_out,
-                                         (hipStream_t)hip_stream, cancel);
+    const FusedOut o{out, rgba8_out, samples_out, error_out, level_pixels_out};
+    RR_TRY(check_levels_args("rr_render_adaptive_levels_device", true, s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, o));
+    return device_fused_call(s, "rr_render_adaptive_levels_device", o, [&](const FusedOut& d) {
+        return render_adaptive_levels_locked(s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, d, (hipStream_t)hip_stream, cancel);
+    });
 } RR_GUARD_END("rr_render_adaptive_levels_device")
 
 int rr_render_adaptive_levels(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* level_samples, uint32_t n_levels, float threshold,
                               const uint16_t* const* sample_xy_levels, rr_radiance* out, uint8_t* rgba8_out, uint16_t* samples_out, float* error_out,
                               uint32_t* level_pixels_out, const volatile int* cancel) try {
-    RR_TRY(check_levels_args("rr_render_adaptive_levels", false, s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, out, rgba8_out, samples_out, error_out));
-    RR_TRY(not_in_pass(s, "rr_render_adaptive_levels"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    // the staging is the handle's, where rr_render_adaptive stages its own (s->frame.tmp_out: grown, kept, used by host forms only)
-    const size_t n = (size_t)cam->width * cam->height;
-    DevBuf &d_rgba = s->frame.tmp_out[0], &d_out = s->frame.tmp_out[1], &d_samples = s->frame.tmp_out[2], &d_error = s->frame.tmp_out[3];
-    HIP_TRY(d_out.reserve(32ull * n));
-    if (rgba8_out) HIP_TRY(d_rgba.reserve(4ull * n));
-    if (samples_out) HIP_TRY(d_samples.reserve(2ull * n));
-    if (error_out) HIP_TRY(d_error.reserve(4ull * n));
-    uint32_t level_pixels[RR_MAX_ADAPTIVE_LEVELS] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // (the caller's words are written by a finished call only)
-    RR_TRY(render_adaptive_levels_locked(s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, d_out.as<rr_radiance>(),
-                                         rgba8_out ? d_rgba.as<uint8_t>() : nullptr, samples_out ? d_samples.as<uint16_t>() : nullptr,
-                                         error_out ? d_error.as<float>() : nullptr, level_pixels, nullptr, cancel));
-    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, d_rgba.p, 4ull * n, hipMemcpyDeviceToHost, nullptr));
-    if (samples_out) HIP_TRY(hipMemcpyAsync(samples_out, d_samples.p, 2ull * n, hipMemcpyDeviceToHost, nullptr));
-    if (error_out) HIP_TRY(hipMemcpyAsync(error_out, d_error.p, 4ull * n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(out, d_out.p, 32ull * n, hipMemcpyDeviceToHost)); // waits for the launches: the outputs are written by a finished call only
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if (level_pixels_out) memcpy(level_pixels_out, level_pixels, 4ull * n_levels);
-    return RR_OK;
+    const FusedOut o{out, rgba8_out, samples_out, error_out, level_pixels_out};
+    RR_TRY(check_levels_args("rr_render_adaptive_levels", false, s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, o));
+    return host_fused_call(s, "rr_render_adaptive_levels", cam, o, n_levels, [&](const FusedOut& d) {
+        return render_adaptive_levels_locked(s, cam, cfg, level_samples, n_levels, threshold, sample_xy_levels, d, nullptr, cancel);
+    });
 } RR_GUARD_END("rr_render_adaptive_levels")

@@ -1,12 +1,12 @@
 // rr_api_parts.h — rr_render_pixel_parts and its device form: the samples of a pixel as K interleaved means (part h = the frame samples
 // s with s mod K == h) next to the pixel's full record, from the rays rr_render_pixels traces.
 // Offers: rr_render_pixel_parts, rr_render_pixel_parts_device.
-// Needs:  rr_api_frame.h (FrameIo, render_region_locked: K slots per pixel, k_pixel_slots and k_resolve_pixel_parts at its two ends),
-//         rr_api_query.h (check_pixels_args, WHOLE_FRAME, check_query_pointers), rr_pixel_list.h.
+// Needs:  rr_api_frame.h (FrameIo, pixels_io, IdleOnExit, render_region_locked: K slots per pixel, k_pixel_slots and k_resolve_pixel_parts at
+//         its two ends), rr_api_query.h (check_pixels_args, host_list_call, check_query_pointers).
 //
 // The body is the frame's: batches, level walk, stages and plan, over n_pixels * K accumulator slots of samples / K samples each.  The
-// device form works on buffers the scene's device can address, in stream order; the host form is the device form behind a staging
-// copy in buffers of the handle (the records where rr_render_pixels stages its own, the part records in a buffer of this layer's).
+// device form works on buffers the scene's device can address, in stream order; the host form is the device form behind the staging
+// copy of every list call (host_list_call, rr_api_query.h).
 
 // n_parts as log2, or why it is refused.  `out`, `parts_out`: both required; `device`: the alignment rule of the device form.
 static int check_parts_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
@@ -29,10 +29,10 @@ static int check_parts_args(const char* fn, bool device, const rr_scene* s, cons
 // one call on buffers the device can address (the caller holds the lock); a call that ends early leaves the stream idle
 static int render_pixel_parts_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
                                      uint32_t n_pixels, uint32_t lg_parts, rr_radiance* out, rr_radiance* parts_out, hipStream_t st, const volatile int* cancel) {
-    const int rc = render_region_locked(s, cam, cfg, sample_xy,
-                                        FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, nullptr, lg_parts, parts_out, 0u, 0u, nullptr, false, false}, st, cancel);
-    if (rc != RR_OK) (void)hipStreamSynchronize(st);
-    return rc;
+    IdleOnExit idle(st);
+    FrameIo io = pixels_io(pixel_xy, n_pixels, out, nullptr);
+    io.lg_parts = lg_parts; io.parts = parts_out;
+    return idle.done(render_region_locked(s, cam, cfg, sample_xy, io, st, cancel));
 }
 
 // (C linkage: both are declared in include/rustray_hip.h, inside its extern "C" block, and a definition keeps the linkage of its declaration;
@@ -56,29 +56,8 @@ int rr_render_pixel_parts(rr_scene* s, const rr_camera* cam, const rr_config* cf
     uint32_t lg_parts = 0;
     RR_TRY(check_parts_args("rr_render_pixel_parts", false, s, cam, cfg, sample_xy, pixel_xy, n_pixels, n_parts, out, parts_out, &lg_parts));
     if (n_pixels == 0) return RR_OK;
-    if (pixel_xy) { // (the body refuses the same entries; here the refusal costs no upload)
-        const uint32_t bad = pixel_list_first_bad(pixel_xy, n_pixels, cam->width, cam->height);
-        if (bad != RR_PIXEL_LIST_OK)
-            return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, pixel_xy[bad] & 0xffffu, pixel_xy[bad] >> 16,
-                        cam->width, cam->height);
-    }
-    RR_TRY(not_in_pass(s, "rr_render_pixel_parts"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    // the staging is the handle's (grown, kept, used by host forms only, which return with the stream idle): no allocation per call
-    DevBuf &d_out = s->frame.tmp_out[1], &d_list = s->frame.tmp_out[2], &d_parts = s->frame.tmp_parts;
-    const size_t parts_bytes = 32ull * n_pixels * n_parts;
-    if (pixel_xy) {
-        HIP_TRY(d_list.reserve(4ull * n_pixels));
-        HIP_TRY(hipMemcpy(d_list.p, pixel_xy, 4ull * n_pixels, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(d_out.reserve(32ull * n_pixels));
-    HIP_TRY(d_parts.reserve(parts_bytes));
-    RR_TRY(render_pixel_parts_locked(s, cam, cfg, sample_xy, pixel_xy ? d_list.as<uint32_t>() : nullptr, n_pixels, lg_parts, d_out.as<rr_radiance>(),
-                                     d_parts.as<rr_radiance>(), nullptr, cancel));
-    HIP_TRY(hipMemcpyAsync(parts_out, d_parts.p, parts_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(out, d_out.p, 32ull * n_pixels, hipMemcpyDeviceToHost)); // waits for the launches: the outputs are written by a finished call only
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return RR_OK;
+    return host_list_call(s, "rr_render_pixel_parts", cam, pixel_xy, n_pixels, n_parts, out, parts_out, nullptr,
+                          [&](const uint32_t* d_list, rr_radiance* d_out, rr_radiance* d_parts, uint8_t*) {
+                              return render_pixel_parts_locked(s, cam, cfg, sample_xy, d_list, n_pixels, lg_parts, d_out, d_parts, nullptr, cancel);
+                          });
 } RR_GUARD_END("rr_render_pixel_parts")

@@ -1,12 +1,13 @@
 // rr_api_query.h — questions to a scene outside a frame: rr_pick, and the closest-hit, shadow, surface and radiance queries for rays of the caller's.
 // Offers: rr_pick; check_query_pointer(s); launch_query_shadow; rr_trace_rays, rr_trace_shadow_rays, rr_surface_rays, rr_shade_rays,
-//         rr_render_pixels and their *_device forms.
+//         rr_render_pixels and their *_device forms; for the list calls of the layers behind it: check_pixels_args, host_list_call,
+//         render_pixels_locked.
 // Needs:  rr_api_base.h, rr_api_handle.h (writes rr_scene::query), rr_api_scene.h (ensure_tlas_reach, ensure_camera_reach; reads
 //         rr_scene::data), rr_api_frame.h (launch_trace_closest, take_stream, make_frame; for rr_shade_rays the frame's own level walk:
 //         FrameRun, run_level, upload_shade_const, reset_accumulators, grow_ray_queues, begin_frame_stats; for rr_render_pixels the whole frame:
-//         check_frame_args, FrameIo, render_region_locked), rr_pixel_list.h, rr_api_multi.h (the peer
+//         check_frame_args, pixels_io, IdleOnExit, render_region_locked), rr_pixel_list.h, rr_api_multi.h (the peer
 //         access it has enabled: g_peer_mu, g_peer_state), rr_query_pointers.h, rr_frame_plan.h.
-// Borrowed from rr_scene::frame: h_count[4 .. 7] and last_stream by every query (await_reach, take_stream); the arena, the shadow
+// Borrowed from rr_scene::frame: h_count[HC_REACH ..] and last_stream by every query (await_reach, take_stream); the arena, the shadow
 // queue, the accumulators and the counter pool by rr_shade_rays (why the next frame does not see it: above shade_rays_locked).
 
 // ---------------------------------------------------------------------------
@@ -133,10 +134,10 @@ static int preset_reach(rr_scene* s, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(w + QW_REACH + 12, 0xff, 4, st));
     return RR_OK;
 }
-// THE wait of a query on device buffers: reads the reach words back (pinned, s->frame.h_count[4 .. 7]) and pads the top level for them.
+// THE wait of a query on device buffers: reads the reach words back (pinned, s->frame.h_count[HC_REACH ..]) and pads the top level for them.
 // *first_bad = the first index with a bad limit, or 0xffffffff.
 static int await_reach(rr_scene* s, hipStream_t st, uint32_t* first_bad) {
-    uint32_t* h = s->frame.h_count + 4;
+    uint32_t* h = s->frame.h_count + HC_REACH;
     HIP_TRY(hipMemcpyAsync(h, s->query.words.as<char>() + QW_REACH, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *first_bad = h[3];
@@ -489,7 +490,6 @@ extern "C" int rr_shade_rays_device(rr_scene* s, const rr_config* cfg, const flo
 // (fill_pixel_slots) and the last kernel (k_resolve_pixels) differ.  The device form works on buffers the scene's device can address, in
 // stream order; the host form is the device form behind a staging copy (the list, 32 + 4 B per pixel of answers, the null stream).
 static_assert(sizeof(rr_radiance) == 32, "k_resolve_pixels writes rr_radiance as two float4");
-static const rr_region WHOLE_FRAME{8, 8, 1, 0}; // rr_render's slot order: 8x8 tiles, one wave = one tile of primary rays
 
 // The argument checks of the two entry points; `device`: the alignment rule of the device form.  n_pixels == 0 passes: the caller returns
 // RR_OK before it touches anything.
@@ -507,12 +507,48 @@ static int check_pixels_args(const char* fn, bool device, const rr_scene* s, con
     return RR_OK;
 }
 
+// THE host form of a list call (rr_render_pixels, rr_render_pixel_parts, rr_render_pixel_prefix), its arguments checked and n_pixels > 0:
+// the device form behind a staging copy.  The list is checked here (the body refuses the same entries; here the refusal costs no
+// upload), the scene is locked, and `body(list, out, parts, rgba8)` runs on the null stream on buffers of the handle -- s->frame.tmp_out
+// (grown, kept, used by host forms only, which return with the stream idle): the bytes where rr_render stages its bytes, the records and
+// the list in the buffers of the next two outputs, the part records (parts_per_pixel of them, where parts_out is given) in tmp_parts; no
+// allocation per call.  The caller's outputs are written by a finished call only: `out` is copied last and waits for the launches.
+template <class Body>
+static int host_list_call(rr_scene* s, const char* fn, const rr_camera* cam, const uint32_t* pixel_xy, uint32_t n_pixels, uint32_t parts_per_pixel,
+                          rr_radiance* out, rr_radiance* parts_out, uint8_t* rgba8_out, Body body) {
+    if (pixel_xy) {
+        const uint32_t bad = pixel_list_first_bad(pixel_xy, n_pixels, cam->width, cam->height);
+        if (bad != RR_PIXEL_LIST_OK)
+            return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, pixel_xy[bad] & 0xffffu, pixel_xy[bad] >> 16,
+                        cam->width, cam->height);
+    }
+    RR_TRY(not_in_pass(s, fn));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf &d_rgba = s->frame.tmp_out[0], &d_out = s->frame.tmp_out[1], &d_list = s->frame.tmp_out[2], &d_parts = s->frame.tmp_parts;
+    const size_t parts_bytes = 32ull * n_pixels * parts_per_pixel;
+    if (pixel_xy) {
+        HIP_TRY(d_list.reserve(4ull * n_pixels));
+        HIP_TRY(hipMemcpy(d_list.p, pixel_xy, 4ull * n_pixels, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(d_out.reserve(32ull * n_pixels));
+    if (parts_out) HIP_TRY(d_parts.reserve(parts_bytes));
+    if (rgba8_out) HIP_TRY(d_rgba.reserve(4ull * n_pixels));
+    RR_TRY(body(pixel_xy ? d_list.as<uint32_t>() : nullptr, d_out.as<rr_radiance>(), parts_out ? d_parts.as<rr_radiance>() : nullptr,
+                rgba8_out ? d_rgba.as<uint8_t>() : nullptr));
+    if (parts_out) HIP_TRY(hipMemcpyAsync(parts_out, d_parts.p, parts_bytes, hipMemcpyDeviceToHost, nullptr));
+    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, d_rgba.p, 4ull * n_pixels, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.p, 32ull * n_pixels, hipMemcpyDeviceToHost));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return RR_OK;
+}
+
 // one call on buffers the device can address (the caller holds the lock); a call that ends early leaves the stream idle
 static int render_pixels_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy,
                                 uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8, hipStream_t st, const volatile int* cancel) {
-    const int rc = render_region_locked(s, cam, cfg, sample_xy, FrameIo{pixel_xy ? nullptr : &WHOLE_FRAME, pixel_xy, n_pixels, nullptr, false, nullptr, out, rgba8, 0u, nullptr, 0u, 0u, nullptr, false, false}, st, cancel);
-    if (rc != RR_OK) (void)hipStreamSynchronize(st);
-    return rc;
+    IdleOnExit idle(st);
+    return idle.done(render_region_locked(s, cam, cfg, sample_xy, pixels_io(pixel_xy, n_pixels, out, rgba8), st, cancel));
 }
 
 // (the two entry points of this family share one linkage block; tests/test_pixel_list.py holds each to the guard every entry point has)
@@ -533,30 +569,9 @@ int rr_render_pixels(rr_scene* s, const rr_camera* cam, const rr_config* cfg, co
                                 uint32_t n_pixels, rr_radiance* out, uint8_t* rgba8_out, const volatile int* cancel) try {
     RR_TRY(check_pixels_args("rr_render_pixels", false, s, cam, cfg, sample_xy, pixel_xy, n_pixels, out, rgba8_out));
     if (n_pixels == 0) return RR_OK;
-    if (pixel_xy) { // (the body refuses the same entries; here the refusal costs no upload)
-        const uint32_t bad = pixel_list_first_bad(pixel_xy, n_pixels, cam->width, cam->height);
-        if (bad != RR_PIXEL_LIST_OK)
-            return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, pixel_xy[bad] & 0xffffu, pixel_xy[bad] >> 16,
-                        cam->width, cam->height);
-    }
-    RR_TRY(not_in_pass(s, "rr_render_pixels"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    // the staging is the handle's, as rr_render's device frame is (s->frame.tmp_out: grown, kept, used by host forms only, which return with the stream idle): the bytes where
-    // rr_render stages its bytes, the records and the list in the buffers of the next two outputs -- no allocation per call
-    DevBuf &d_rgba = s->frame.tmp_out[0], &d_out = s->frame.tmp_out[1], &d_list = s->frame.tmp_out[2];
-    if (pixel_xy) {
-        HIP_TRY(d_list.reserve(4ull * n_pixels));
-        HIP_TRY(hipMemcpy(d_list.p, pixel_xy, 4ull * n_pixels, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(d_out.reserve(32ull * n_pixels));
-    if (rgba8_out) HIP_TRY(d_rgba.reserve(4ull * n_pixels));
-    RR_TRY(render_pixels_locked(s, cam, cfg, sample_xy, pixel_xy ? d_list.as<uint32_t>() : nullptr, n_pixels, d_out.as<rr_radiance>(),
-                                rgba8_out ? d_rgba.as<uint8_t>() : nullptr, nullptr, cancel));
-    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, d_rgba.p, 4ull * n_pixels, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(out, d_out.p, 32ull * n_pixels, hipMemcpyDeviceToHost)); // waits for the launches: `out` is written by a finished call only
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return RR_OK;
+    return host_list_call(s, "rr_render_pixels", cam, pixel_xy, n_pixels, 0u, out, nullptr, rgba8_out,
+                          [&](const uint32_t* d_list, rr_radiance* d_out, rr_radiance*, uint8_t* d_rgba) {
+                              return render_pixels_locked(s, cam, cfg, sample_xy, d_list, n_pixels, d_out, d_rgba, nullptr, cancel);
+                          });
 } RR_GUARD_END("rr_render_pixels")
 } // extern "C"

@@ -198,37 +198,28 @@ class Raytracing:
         return self.device_scene.render_adaptive(self.camera.c_struct(), self.config, base_samples, max_samples, threshold, sample_xy_base=sample_xy_base,
                                                  sample_xy_max=sample_xy_max, rgba8=rgba8)
 
-    def render_adaptive_levels(self, levels, threshold: float, sample_xy_levels=None) -> dict:
-        """A ladder of sample counts in one frame, as a HOST LOOP over library calls: every pixel at levels[0] in two halves (one
-        rr_render_pixel_parts call), and level after level the pixels whose half-buffer error (adaptive.half_error) still exceeds
-        `threshold`, again in two halves at the next count (one rr_render_pixel_parts call per list: adaptive.refine_list, then
-        adaptive.refine_sublist), until the list is empty or the top count is reached.  Returns the frame in row-major order:
-        dict(color (n, 3) LINEAR, depth, normal, object_id, samples: the count of the last level that rendered the pixel, error: the
-        estimate at THAT count -- the residual error --, level_pixels: the pixels of each level before the pad, padded: each level's
-        list length with it).  Every pixel is, bit for bit, the rr_render_pixels pixel at the count `samples` names."""
+    def _render_ladder(self, counts, threshold: float, render_level) -> dict:
+        """The host loop behind render_adaptive_levels and render_adaptive_prefix: render_level(l, pixels) renders level l of the ladder
+        `counts` in two halves, for the whole frame (pixels None, level 0) or for a padded list, and returns the dict of
+        render_pixel_parts.  The lists are adaptive.refine_list, then adaptive.refine_sublist, until one is empty or the top is reached."""
         from . import adaptive
-        levels = [int(v) for v in levels]
-        tables = list(sample_xy_levels) if sample_xy_levels is not None else [None] * len(levels)
         cam = self.camera.c_struct()
         w, h = int(cam.width), int(cam.height)
-        cfg = rr_config.from_buffer_copy(self.config)
-        cfg.samples = levels[0]
-        base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=tables[0])
+        base = render_level(0, None)
         res = {k: base[k].copy() for k in ("color", "depth", "normal", "object_id")}
         error = adaptive.half_error(base["parts"]["color"])
-        samples = np.full(w * h, levels[0], np.uint32)
-        level_pixels, padded = [w * h] + [0] * (len(levels) - 1), [w * h] + [0] * (len(levels) - 1)
+        samples = np.full(w * h, counts[0], np.uint32)
+        level_pixels, padded = [w * h] + [0] * (len(counts) - 1), [w * h] + [0] * (len(counts) - 1)
         xy, count = adaptive.refine_list(error, threshold, w, h)
-        for l in range(1, len(levels)):
+        for l in range(1, len(counts)):
             if not count:
                 break
-            cfg.samples = levels[l]
-            fine = self.device_scene.render_pixel_parts(cam, cfg, pixels=xy, n_parts=2, sample_xy=tables[l])
+            fine = render_level(l, xy)
             level_pixels[l], padded[l] = count, len(xy)
             at = (xy[:count] >> np.uint32(16)).astype(np.int64) * w + (xy[:count] & np.uint32(0xffff)).astype(np.int64)
             for k in res:
                 res[k][at] = fine[k][:count]
-            samples[at] = levels[l]
+            samples[at] = counts[l]
             e = adaptive.half_error(fine["parts"]["color"])
             error[at] = e[:count]
             xy, count = adaptive.refine_sublist(e, threshold, xy, count)
@@ -237,6 +228,24 @@ class Raytracing:
         res["level_pixels"] = level_pixels
         res["padded"] = padded
         return res
+
+    def render_adaptive_levels(self, levels, threshold: float, sample_xy_levels=None) -> dict:
+        """A ladder of sample counts in one frame, as a HOST LOOP over library calls: every pixel at levels[0] in two halves (one
+        rr_render_pixel_parts call), and level after level the pixels whose half-buffer error (adaptive.half_error) still exceeds
+        `threshold`, again in two halves at the next count (one rr_render_pixel_parts call per list: adaptive.refine_list, then
+        adaptive.refine_sublist), until the list is empty or the top count is reached.  Returns the frame in row-major order:
+        dict(color (n, 3) LINEAR, depth, normal, object_id, samples: the count of the last level that rendered the pixel, error: the
+        estimate at THAT count -- the residual error --, level_pixels: the pixels of each level before the pad, padded: each level's
+        list length with it).  Every pixel is, bit for bit, the rr_render_pixels pixel at the count `samples` names."""
+        levels = [int(v) for v in levels]
+        tables = list(sample_xy_levels) if sample_xy_levels is not None else [None] * len(levels)
+        cam = self.camera.c_struct()
+        cfg = rr_config.from_buffer_copy(self.config)
+
+        def render_level(l, pixels):
+            cfg.samples = levels[l]
+            return self.device_scene.render_pixel_parts(cam, cfg, pixels=pixels, n_parts=2, sample_xy=tables[l])
+        return self._render_ladder(levels, threshold, render_level)
 
     def render_adaptive_levels_on_device(self, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False) -> dict:
         """render_adaptive_levels as ONE library call (rr_render_adaptive_levels): every pass, list and scatter runs on the device under one
@@ -258,35 +267,12 @@ class Raytracing:
         prefix (adaptive.refine_list, then adaptive.refine_sublist), until the list is empty or the whole frame is reached.  Returns
         the dict of render_adaptive_levels.  Every pixel is, bit for bit, the rr_render_pixel_prefix pixel at the count `samples`
         names.  This is the yardstick of render_adaptive_prefix_on_device, which traces every sample once."""
-        from . import adaptive
         prefixes = [int(v) for v in prefix_samples]
         cam = self.camera.c_struct()
-        w, h = int(cam.width), int(cam.height)
         if not prefixes or prefixes[-1] != int(self.config.samples):
             raise ValueError(f"prefix_samples {prefixes}: the last prefix must be config.samples = {int(self.config.samples)}")
-        base = self.device_scene.render_pixel_prefix(cam, self.config, samples_used=prefixes[0], halves=True, sample_xy=sample_xy)
-        res = {k: base[k].copy() for k in ("color", "depth", "normal", "object_id")}
-        error = adaptive.half_error(base["parts"]["color"])
-        samples = np.full(w * h, prefixes[0], np.uint32)
-        level_pixels, padded = [w * h] + [0] * (len(prefixes) - 1), [w * h] + [0] * (len(prefixes) - 1)
-        xy, count = adaptive.refine_list(error, threshold, w, h)
-        for l in range(1, len(prefixes)):
-            if not count:
-                break
-            fine = self.device_scene.render_pixel_prefix(cam, self.config, pixels=xy, samples_used=prefixes[l], halves=True, sample_xy=sample_xy)
-            level_pixels[l], padded[l] = count, len(xy)
-            at = (xy[:count] >> np.uint32(16)).astype(np.int64) * w + (xy[:count] & np.uint32(0xffff)).astype(np.int64)
-            for k in res:
-                res[k][at] = fine[k][:count]
-            samples[at] = prefixes[l]
-            e = adaptive.half_error(fine["parts"]["color"])
-            error[at] = e[:count]
-            xy, count = adaptive.refine_sublist(e, threshold, xy, count)
-        res["samples"] = samples
-        res["error"] = error
-        res["level_pixels"] = level_pixels
-        res["padded"] = padded
-        return res
+        return self._render_ladder(prefixes, threshold, lambda l, pixels: self.device_scene.render_pixel_prefix(
+            cam, self.config, pixels=pixels, samples_used=prefixes[l], halves=True, sample_xy=sample_xy))
 
     def render_adaptive_prefix_on_device(self, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False) -> dict:
         """render_adaptive_prefix as ONE library call (rr_render_adaptive_prefix): the sums of a listed pixel stay on the device and every
@@ -758,7 +744,7 @@ def shade_rays_torch(device_scene: capi.DeviceScene, origins, directions, cfg: r
         if n:
             device_scene.shade_rays_device(cfg, o.data_ptr(), d.data_ptr(), n, rpr, ids.data_ptr() if ids is not None else None, rec.data_ptr(),
                                            torch.cuda.current_stream(dev).cuda_stream)
-    return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7]}
+    return _record_views(rec)
 
 
 def render_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, sample_xy=None, rgba8: bool = False) -> dict:
@@ -779,7 +765,7 @@ def render_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pix
         if n:
             device_scene.render_pixels_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
                                               torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
-    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7]}
+    out = _record_views(rec)
     if rgba8:
         out["rgba"] = rgba
     return out
@@ -803,16 +789,19 @@ def render_pixel_parts_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config
         if n:
             device_scene.render_pixel_parts_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, K, rec.data_ptr(), prec.data_ptr(),
                                                    torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
-    return {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "part_records": prec,
-            "parts": {"color": prec[:, :, 0:3], "depth": prec[:, :, 3], "normal": prec[:, :, 4:7], "object_id": prec.view(torch.int32)[:, :, 7]}}
+    parts = _record_views(prec)
+    return dict(_record_views(rec), part_records=parts.pop("records"), parts=parts)
 
 
-def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None,
-                          sample_xy_max=None, rgba8: bool = False, samples: bool = True, error: bool = True) -> dict:
-    """rr_render_adaptive_device on torch's current stream: the frame at `base_samples`, and at `max_samples` where the half-buffer error
-    of the base frame exceeds `threshold`.  Returns torch tensors in row-major order, without a host copy of the results: the dict of
-    render_pixels_torch (records (n, 8) float32 and its views), n_refined (an int: the call waits for it), and on request samples (n,)
-    int16 (the sample count per pixel), error (n,) float32 and rgba (n, 4) uint8."""
+def _record_views(rec) -> dict:
+    """`records`, (..., 8) float32 rr_radiance on the device, and the views of its fields"""
+    import torch
+    return {"records": rec, "color": rec[..., 0:3], "depth": rec[..., 3], "normal": rec[..., 4:7], "object_id": rec.view(torch.int32)[..., 7]}
+
+
+def _fused_torch(device_scene: capi.DeviceScene, cam, rgba8: bool, samples: bool, error: bool, counts_key: str, call) -> dict:
+    """The body of the three fused calls on torch's current stream: the outputs as torch tensors, `call(out, rgba8, samples, error, stream)`
+    on their raw pointers (None where one is not asked for), and the dict they return; what `call` returns goes under `counts_key`."""
     import torch
     n = int(cam.width) * int(cam.height)
     dev = torch.device("cuda", device_scene.device)
@@ -821,10 +810,9 @@ def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, b
         rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
         smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
         err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
-        count = device_scene.render_adaptive_device(cam, cfg, base_samples, max_samples, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
-                                                    smp.data_ptr() if samples else None, err.data_ptr() if error else None,
-                                                    torch.cuda.current_stream(dev).cuda_stream, sample_xy_base=sample_xy_base, sample_xy_max=sample_xy_max)
-    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "n_refined": count}
+        counts = call(rec.data_ptr(), rgba.data_ptr() if rgba8 else None, smp.data_ptr() if samples else None, err.data_ptr() if error else None,
+                      torch.cuda.current_stream(dev).cuda_stream)
+    out = dict(_record_views(rec), **{counts_key: counts})
     if rgba8:
         out["rgba"] = rgba
     if samples:
@@ -832,6 +820,16 @@ def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, b
     if error:
         out["error"] = err
     return out
+
+
+def render_adaptive_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None,
+                          sample_xy_max=None, rgba8: bool = False, samples: bool = True, error: bool = True) -> dict:
+    """rr_render_adaptive_device on torch's current stream: the frame at `base_samples`, and at `max_samples` where the half-buffer error
+    of the base frame exceeds `threshold`.  Returns torch tensors in row-major order, without a host copy of the results: the dict of
+    render_pixels_torch (records (n, 8) float32 and its views), n_refined (an int: the call waits for it), and on request samples (n,)
+    int16 (the sample count per pixel), error (n,) float32 and rgba (n, 4) uint8."""
+    return _fused_torch(device_scene, cam, rgba8, samples, error, "n_refined", lambda out, rgba, smp, err, stream: device_scene.render_adaptive_device(
+        cam, cfg, base_samples, max_samples, threshold, out, rgba, smp, err, stream, sample_xy_base=sample_xy_base, sample_xy_max=sample_xy_max))
 
 
 def render_adaptive_levels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, levels, threshold: float, sample_xy_levels=None, rgba8: bool = False,
@@ -841,25 +839,8 @@ def render_adaptive_levels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_co
     results: the dict of render_pixels_torch (records (n, 8) float32 and its views), level_pixels (a list of ints: the call waits for
     them), and on request samples (n,) int16 (the count of the last level that rendered the pixel), error (n,) float32 (the residual
     error, at that count) and rgba (n, 4) uint8."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    dev = torch.device("cuda", device_scene.device)
-    with torch.cuda.device(dev):
-        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
-        err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
-        level_pixels = device_scene.render_adaptive_levels_device(cam, cfg, levels, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
-                                                                  smp.data_ptr() if samples else None, err.data_ptr() if error else None,
-                                                                  torch.cuda.current_stream(dev).cuda_stream, sample_xy_levels=sample_xy_levels)
-    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "level_pixels": level_pixels}
-    if rgba8:
-        out["rgba"] = rgba
-    if samples:
-        out["samples"] = smp
-    if error:
-        out["error"] = err
-    return out
+    return _fused_torch(device_scene, cam, rgba8, samples, error, "level_pixels", lambda out, rgba, smp, err, stream: device_scene.render_adaptive_levels_device(
+        cam, cfg, levels, threshold, out, rgba, smp, err, stream, sample_xy_levels=sample_xy_levels))
 
 
 def render_adaptive_prefix_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, prefix_samples, threshold: float, sample_xy=None, rgba8: bool = False,
@@ -867,22 +848,5 @@ def render_adaptive_prefix_torch(device_scene: capi.DeviceScene, cam, cfg: rr_co
     """rr_render_adaptive_prefix_device on torch's current stream: the frame over its first prefix_samples[0] samples, and level after
     level only the samples up to the next prefix for the pixels whose half-buffer error still exceeds `threshold`.  Returns what
     render_adaptive_levels_torch returns."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    dev = torch.device("cuda", device_scene.device)
-    with torch.cuda.device(dev):
-        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        smp = torch.empty((n,), dtype=torch.int16, device=dev) if samples else None
-        err = torch.empty((n,), dtype=torch.float32, device=dev) if error else None
-        level_pixels = device_scene.render_adaptive_prefix_device(cam, cfg, prefix_samples, threshold, rec.data_ptr(), rgba.data_ptr() if rgba8 else None,
-                                                                  smp.data_ptr() if samples else None, err.data_ptr() if error else None,
-                                                                  torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
-    out = {"records": rec, "color": rec[:, 0:3], "depth": rec[:, 3], "normal": rec[:, 4:7], "object_id": rec.view(torch.int32)[:, 7], "level_pixels": level_pixels}
-    if rgba8:
-        out["rgba"] = rgba
-    if samples:
-        out["samples"] = smp
-    if error:
-        out["error"] = err
-    return out
+    return _fused_torch(device_scene, cam, rgba8, samples, error, "level_pixels", lambda out, rgba, smp, err, stream: device_scene.render_adaptive_prefix_device(
+        cam, cfg, prefix_samples, threshold, out, rgba, smp, err, stream, sample_xy=sample_xy))

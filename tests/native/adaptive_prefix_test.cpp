@@ -3,7 +3,8 @@
 // accumulators is laid out in a byte buffer with guard words through the shared offset functions, every word of every entry tagged with
 // (entry, half, plane); a compaction is replayed on the CPU, wave by wave and lane by lane, into a second set and a second list, both with
 // guards, and compared with a plain loop: the survivors in their order, two slots each, every plane, the flags, the pad as copies of the
-// last survivor up to a multiple of 64, nothing written twice and nothing written behind.
+// last survivor up to a multiple of 64, nothing written twice and nothing written behind.  Last: the ladder rule of the calls that refine
+// level by level (ladder_fault), every fault at every position.
 #include "../../rustray_amd/csrc/rr_adaptive.h"
 
 #include <cstdint>
@@ -127,7 +128,47 @@ static int test_compaction(uint32_t count, int pattern) {
     return 0;
 }
 
+// the ladder rule: 2 .. 8 counts, each even and at least 2, strictly increasing; the first fault and its entry.  The ladders live in
+// vectors of exactly n_levels entries, so a read behind the ladder is the sanitizer's to find.
+static int test_ladders() {
+    const unsigned short good[9] = {2, 4, 6, 8, 10, 12, 14, 16, 18};
+    const unsigned int UNSET = 0xdeadbeefu;
+    for (unsigned int n : {0u, 1u, 2u, 8u, 9u}) {
+        const std::vector<unsigned short> v(good, good + n);
+        unsigned int at = UNSET;
+        const LadderFault f = ladder_fault(v.data(), n, 8u, &at);
+        CHECK(f == ((n == 2u || n == 8u) ? LADDER_OK : LADDER_LEVELS));
+        if (f == LADDER_LEVELS) CHECK(at == UNSET);
+        at = UNSET;
+        CHECK(ladder_fault(nullptr, n, 8u, &at) == ((n == 2u || n == 8u) ? LADDER_NULL : LADDER_LEVELS) && at == UNSET); // the count is judged first
+    }
+    for (unsigned int n : {2u, 3u, 8u})
+        for (unsigned int k = 0; k < n; k++) {
+            unsigned int at = UNSET;
+            std::vector<unsigned short> v(good, good + n);
+            v[k] = (unsigned short)(good[k] + 1u); // an odd entry (above its neighbour below: the fault is the entry's own)
+            CHECK(ladder_fault(v.data(), n, 8u, &at) == LADDER_ENTRY && at == k);
+            v[k] = 0; // an entry of 0: below 2 before it is "not above" anything
+            CHECK(ladder_fault(v.data(), n, 8u, &at) == LADDER_ENTRY && at == k);
+            v[k] = 1;
+            CHECK(ladder_fault(v.data(), n, 8u, &at) == LADDER_ENTRY && at == k);
+            if (k == 0) continue;
+            v[k] = good[k - 1]; // equal neighbours
+            CHECK(ladder_fault(v.data(), n, 8u, &at) == LADDER_ORDER && at == k);
+            v[k] = (unsigned short)(good[k - 1] - 2u); // decreasing (2 -> 0 is an entry fault, covered above)
+            CHECK(ladder_fault(v.data(), n, 8u, &at) == (v[k] ? LADDER_ORDER : LADDER_ENTRY) && at == k);
+        }
+    // the first fault wins: an odd entry at 1 before equal neighbours at 3; a valid ladder of 8 with large steps
+    const unsigned short two_faults[4] = {6, 15, 30, 30}, wide[8] = {2, 6, 14, 30, 62, 126, 254, 65534};
+    unsigned int at = UNSET;
+    CHECK(ladder_fault(two_faults, 4u, 8u, &at) == LADDER_ENTRY && at == 1u);
+    CHECK(ladder_fault(wide, 8u, 8u, &at) == LADDER_OK);
+    CHECK(ladder_fault(wide, 8u, 7u, &at) == LADDER_LEVELS); // (the limit is the caller's)
+    return 0;
+}
+
 int main() {
+    if (test_ladders()) return 1;
     const uint32_t counts[] = {1, 63, 64, 65, 4097};
     for (uint32_t count : counts) {
         if (test_layout(count)) return 1;
