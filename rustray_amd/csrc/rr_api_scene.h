@@ -38,7 +38,7 @@ static uint32_t tlas_capacity(const TlasTrees& t, uint32_t n_items) {
 static int reserve_tlas(DevBuf* tnodes4, DevBuf* item_boxes, const TlasTrees& t, uint32_t capacity) {
     HIP_TRY(tnodes4->reserve(2 * (size_t)capacity * sizeof(DNode4)));
     HIP_TRY(hipMemset(tnodes4->p, 0, 2 * (size_t)capacity * sizeof(DNode4)));
-    HIP_TRY(item_boxes->reserve(std::max<size_t>(t.item_boxes.size() * sizeof(float4), 16)));
+    HIP_TRY(item_boxes->reserve(std::max<size_t>((t.item_boxes.size() + t.item_groups.size()) * sizeof(float4), 16))); // (both sizes follow from n_items alone)
     return RR_OK;
 }
 // THE refusal of trees that do not fit a node buffer of `capacity` nodes per tree
@@ -57,6 +57,7 @@ static int copy_tlas(const TlasTrees& t, DNode4* tnodes4, uint32_t capacity, flo
     if (!t.corner.empty()) HIP_TRY(hipMemcpy(tnodes4, t.corner.data(), t.corner.size() * sizeof(DNode4), hipMemcpyHostToDevice));
     if (!t.surface.empty()) HIP_TRY(hipMemcpy(tnodes4 + capacity, t.surface.data(), t.surface.size() * sizeof(DNode4), hipMemcpyHostToDevice));
     if (!t.item_boxes.empty()) HIP_TRY(hipMemcpy(item_boxes, t.item_boxes.data(), t.item_boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if (!t.item_groups.empty()) HIP_TRY(hipMemcpy(item_boxes + t.item_boxes.size(), t.item_groups.data(), t.item_groups.size() * sizeof(float4), hipMemcpyHostToDevice));
     return RR_OK;
 }
 static void keep_tlas(rr_scene* s, TlasTrees& t) noexcept {

@@ -145,7 +145,8 @@ struct DSceneView {
     const DNode4* tnodes4c;  // the top level of the per-ray CLOSEST-HIT walks: over the items' surface boxes where those are tighter (rr_scene_build.h build_tlas; which one: rr_api_scene.h point_view),
     int32_t tlas_root4c;     // else the same tree as tnodes4 / tlas_root4 (which shadow queries always take)
     const float4* item_boxes; // padded world boxes per item for the packet form of the top level: [2 i] = lo, [2 i + 1] = hi of the item's corner box (the boxes of
-                              // the tree; trace_shadow_packet), [2 (n_items + i)], [.. + 1] of its surface box (trace_closest_packet); rr_scene_build.h build_tlas
+                              // the tree; trace_shadow_packet), [2 (n_items + i)], [.. + 1] of its surface box (trace_closest_packet); rr_scene_build.h build_tlas.
+                              // Behind these 4 n_items entries, in scenes of 65 .. 512 items: the group records of the two-level search (rr_beam.h)
     uint32_t any_alpha_occluder; // some item's material has an alpha map: the shadow attenuation of a receiver whose uv may be NaN can be NaN (k_shade, want_shadow)
     uint32_t general_w;      // some trans_inv has a w row other than (0,0,0,1)
     uint32_t compat;         // RR_COMPAT_* (rr_scene_set_compat): behaviours of earlier reference binaries; 0 = the source at HEAD.

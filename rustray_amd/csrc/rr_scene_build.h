@@ -6,6 +6,7 @@
 // defined by whoever includes this file (rr_api_base.h; the native test).  RR_FAULT_POINT is rr_api_base.h's test-only fault hook.
 #pragma once
 #include "../../include/rustray_hip.h"
+#include "rr_beam.h"
 #include "rr_bvh.h"
 #include "rr_device.h"
 #include "rr_math.h"
@@ -670,13 +671,73 @@ static int tlas_tree(const std::vector<DItem>& items, int depth_limit, const flo
     return RR_OK;
 }
 
+// The group records of the packet top level (rr_beam.h has the layout and the rule; rr_trace.h beam_candidates reads them).
+// `boxes`: the 4 n float4 of build_tlas (corner boxes, then surface boxes).  Items are sorted by the Morton code of their corner
+// box's centre (30 bits over the extent of the finite centres; ties and non-finite centres by item index) and cut into runs of
+// 1 << RR_BEAM_GROUP_SHIFT: one membership for both box sets.  A group's box is the float min / max of its members' boxes, so it
+// contains them bound by bound; a member bound that is not finite opens that side of the group (-inf / +inf): an infinite
+// bound has to, and a NaN bound never constrains the member's own test (fmaxf / fminf drop it), so it must not constrain the
+// group's either.  Deterministic: `records` depends on `boxes` alone.  Empty outside 65 .. 512 items.
+static void build_item_groups(const std::vector<float4>& boxes, uint32_t n, std::vector<float4>* records) {
+    records->clear();
+    if (!beam_grouped(n) || boxes.size() != 4 * (size_t)n) return;
+    double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    std::vector<double> centre(3 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        const float l[3] = {boxes[2 * (size_t)i].x, boxes[2 * (size_t)i].y, boxes[2 * (size_t)i].z}, h[3] = {boxes[2 * (size_t)i + 1].x, boxes[2 * (size_t)i + 1].y, boxes[2 * (size_t)i + 1].z};
+        for (int c = 0; c < 3; c++) {
+            const double m = 0.5 * ((double)l[c] + (double)h[c]);
+            centre[3 * (size_t)i + c] = m;
+            if (std::isfinite(m)) { clo[c] = std::min(clo[c], m); chi[c] = std::max(chi[c], m); }
+        }
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> order(n); // (Morton code, item)
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t code = 0;
+        for (int c = 0; c < 3; c++) {
+            const double m = centre[3 * (size_t)i + c], w = chi[c] - clo[c];
+            uint32_t q = 0;
+            if (std::isfinite(m) && w > 0.0 && std::isfinite(w)) q = (uint32_t)std::min(1023.0, std::max(0.0, (m - clo[c]) / w * 1024.0));
+            for (int b = 0; b < 10; b++) code |= ((q >> b) & 1u) << (3 * b + c);
+        }
+        order[i] = {code, i};
+    }
+    std::sort(order.begin(), order.end());
+    const uint32_t shift = RR_BEAM_GROUP_SHIFT, g = beam_group_count(n);
+    records->resize(beam_group_records(n));
+    const float inf = INFINITY;
+    for (uint32_t set = 0; set < 2; set++) {
+        const float4* src = boxes.data() + 2 * (size_t)n * set;
+        float4* members = records->data() + 2 * (size_t)n * set;
+        float4* groups = records->data() + 4 * (size_t)n + 2 * (size_t)g * set;
+        for (uint32_t k = 0; k < g; k++) { groups[2 * k] = make_float4(inf, inf, inf, 0.0f); groups[2 * k + 1] = make_float4(-inf, -inf, -inf, 0.0f); }
+        for (uint32_t slot = 0; slot < n; slot++) {
+            const uint32_t item = order[slot].second;
+            float4 lo = src[2 * (size_t)item], hi = src[2 * (size_t)item + 1];
+            memcpy(&lo.w, &item, 4);
+            hi.w = 0.0f;
+            members[2 * (size_t)slot] = lo; members[2 * (size_t)slot + 1] = hi;
+            float4& glo = groups[2 * (slot >> shift)];
+            float4& ghi = groups[2 * (slot >> shift) + 1];
+            const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+            float* gl[3] = {&glo.x, &glo.y, &glo.z};
+            float* gh[3] = {&ghi.x, &ghi.y, &ghi.z};
+            for (int c = 0; c < 3; c++) {
+                *gl[c] = std::isfinite(l[c]) ? std::min(*gl[c], l[c]) : -inf;
+                *gh[c] = std::isfinite(h[c]) ? std::max(*gh[c], h[c]) : inf;
+            }
+        }
+    }
+}
+
 // Builds the top-level trees over `items` for ray origins within +-want_reach (grown to cover the items themselves: the
 // origins of secondary and shadow rays lie on them).  `spans`: 9 doubles per item (exact_world_box), or empty = corner boxes only.
 // Writes nothing of a scene: the reach it was built for, the RR_VIEW_NAN_BALLS hint and the item boxes travel in TlasTrees, and
-// rr_api_scene.h's upload_tlas keeps them once the device has the trees.
+// rr_api_scene.h's upload_tlas keeps them once the device has the trees.  `item_groups` (build_item_groups) follows `item_boxes` in the
+// device buffer; it is a vector of its own because the scene keeps the boxes on the host and has no use for the groups there.
 struct TlasTrees {
     std::vector<DNode4> corner, surface; int32_t root = (int32_t)0x80000000, root_surface = (int32_t)0x80000000; bool has_surface = false;
-    double reach[3] = {0.0, 0.0, 0.0}; bool nan_balls = false; std::vector<float4> item_boxes;
+    double reach[3] = {0.0, 0.0, 0.0}; bool nan_balls = false; std::vector<float4> item_boxes, item_groups;
 };
 static int build_tlas(const std::vector<DItem>& items, const std::vector<double>& spans, int depth_limit, const double want_reach[3], TlasTrees* trees) {
     uint32_t n = (uint32_t)items.size();
@@ -724,6 +785,7 @@ static int build_tlas(const std::vector<DItem>& items, const std::vector<double>
         boxes[2 * ((size_t)n + i)] = make_float4(tl[0], tl[1], tl[2], 0.0f);
         boxes[2 * ((size_t)n + i) + 1] = make_float4(th[0], th[1], th[2], 0.0f);
     }
+    build_item_groups(boxes, n, &trees->item_groups);
     int rc = tlas_tree(items, depth_limit, lo.data(), hi.data(), n, &trees->corner, &trees->root);
     if (rc != RR_OK) return rc;
     // The per-ray closest-hit walks get a tree of their own over the SURFACE boxes (the argument above holds for any closest-hit query: an

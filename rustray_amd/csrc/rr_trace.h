@@ -6,11 +6,12 @@
 // Offers: Closest, reference_face_id, ray_nonfinite, trace_closest_ray, trace_closest_packet, trace_closest_nonfinite, trace_closest_ordered;
 // ShadowSel, trace_shadow_ray, trace_shadow_packet (trace_shadow_nonfinite through trace_shadow_ray), shadow_deciding_hit.  The per-item functions
 // (aabb_cast2, item_passes, closest_item*, shadow_item, shadow_blocker_item, trace_shadow_blockers) and the packet top level
-// (wave_min_f32 / wave_max_f32 / wave_min_u32, beam_axis, beam_candidates, beam_next) are this layer's own.
+// (the wave_min_* / wave_max_* reductions, beam_candidates, beam_next; the box test itself is rr_beam.h's, shared with the host) are this layer's own.
 // No macro leaves this file: RR_TOI_SLACK and RR_SHADOW_BOUND are its own, and the node step of rr_walk.h, whose last user
 // is here, is un-defined at the end with STK and RR_SENTINEL.  RR_UTIL / RR_UTIL_KIND stay for the kernels.
-// Needs: rr_walk.h.
+// Needs: rr_walk.h, rr_beam.h.
 #pragma once
+#include "rr_beam.h"
 #include "rr_walk.h"
 
 // An item's REPORTED toi can lie in front of its box.  ray_toi_with_ball takes the root of b^2 - a c, which cancels
@@ -19,7 +20,7 @@
 // front of its box, by a ray that misses it: tools/fuzz_rays.py far, seed 419).  Wherever the top level prunes by distance
 // -- against the best hit, or against the light -- the bound is therefore taken 1e-3 wider than the box distance says
 // (and kept finite: the unused child slots of a node are boxes at infinity, which only a finite bound rejects).
-#define RR_TOI_SLACK 1.001f
+#define RR_TOI_SLACK RR_BEAM_TOI_SLACK
 
 // ---------------------------------------------------------------------------
 // Raytracing::trace (reference src/raytracing.rs:429-490) per item
@@ -217,81 +218,122 @@ RR_DEV void trace_closest_ordered(const DSceneView& sc, f3 o, f3 d, uint32_t dep
 // tested exactly in its own space, and the winner is a minimum that does not depend on the order.  A packet whose 64
 // rays share their direction signs (64 samples of one pixel do) therefore does not walk the top-level tree 64 times:
 // the wave bounds its rays by an interval ray (component ranges of origin and reciprocal direction), tests the items'
-// world boxes against it with one ITEM per lane, and all lanes then visit the few candidates together, nearest box
+// world boxes against it with one ITEM per lane (above 64 items: one group of 8 items per lane first), and all lanes then visit the few candidates together, nearest box
 // first, until the next box starts behind every lane's best hit.  On the contract frame the per-ray walk spent a third
 // of the kernel's vector instructions in the top level (7.8 node steps per ray over 194 items).
 // All 64 lanes must be active.  Returns false (nothing touched) when the packet is not coherent, the scene has more
 // items than a few passes cover, or more than 64 items survive: the caller walks the tree per ray instead.
 // ---------------------------------------------------------------------------
-RR_DEV float wave_min_f32(float v) {
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false)));  // quad_perm [1,0,3,2]
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false)));  // quad_perm [2,3,0,1]
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false))); // row_half_mirror
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false))); // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fminf(fminf(r0, r1), fminf(r2, r3));
-}
-RR_DEV float wave_max_f32(float v) { return -wave_min_f32(-v); }
-RR_DEV uint32_t wave_min_u32(uint32_t v) {
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(r0, r1), min(r2, r3));
-}
-// one axis of the interval-ray slab test: lower bound of the entry distance and upper bound of the exit distance over
-// all rays with origin in [olo, ohi] and |1/d| in [alo, ahi], direction sign `neg` (wave-uniform)
-RR_DEV void beam_axis(bool neg, float blo, float bhi, float olo, float ohi, float alo, float ahi, float* tn, float* tf) {
-    const float un = neg ? olo - bhi : blo - ohi; // smallest signed distance to the near plane
-    const float wf = neg ? ohi - blo : bhi - olo; // largest signed distance to the far plane
-    *tn = un * (un >= 0.0f ? alo : ahi);
-    *tf = wf * (wf >= 0.0f ? ahi : alo);
-}
+// Exact wave reductions on INTEGERS: six DPP steps, each one instruction, leave the result in lane 63.  Within a row of 16:
+// quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror (every lane reads a lane of the wave: bound_ctrl changes nothing and
+// lets the compiler fold the move into the min / max); then row_bcast:15 carries a row's result into the next row (rows 1 and 3
+// take it, the others keep theirs) and row_bcast:31 that of the first half into rows 2 and 3.  All 64 lanes must be active.
+// (The float forms cost twice as much: fminf of a value that comes out of a lane move is preceded by an instruction that quiets
+// a signalling NaN, and the move is not folded.)
+#define RR_WAVE_REDUCE(T, OP, IDENTITY)                                                                            \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));                /* quad_perm [1,0,3,2] */ \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));                /* quad_perm [2,3,0,1] */ \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true));               /* row_half_mirror */     \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true));               /* row_mirror */          \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp((int)(IDENTITY), (int)v, 0x142, 0xa, 0xf, false)); /* row_bcast:15 */        \
+    v = OP(v, (T)__builtin_amdgcn_update_dpp((int)(IDENTITY), (int)v, 0x143, 0xc, 0xf, false)); /* row_bcast:31 */        \
+    return (T)__builtin_amdgcn_readlane((int)v, 63);
+RR_DEV uint32_t wave_min_u32(uint32_t v) { RR_WAVE_REDUCE(uint32_t, min, 0xffffffffu) }
+RR_DEV uint32_t wave_max_u32(uint32_t v) { RR_WAVE_REDUCE(uint32_t, max, 0u) }
+RR_DEV int wave_min_i32(int v) { RR_WAVE_REDUCE(int, min, 0x7fffffff) }
+RR_DEV int wave_max_i32(int v) { RR_WAVE_REDUCE(int, max, (int)0x80000000u) }
+#undef RR_WAVE_REDUCE
+// Floats through them.  The bits of a float that is not NaN, with the low 31 flipped when the sign is set, order as signed
+// integers exactly as the floats do (-0 below +0, as v_min_f32 / v_max_f32 have it); the map is its own inverse, and the
+// minimum and maximum of a set do not depend on the order of combination.  No lane may hold a NaN.
+RR_DEV int float_order(int bits) { return bits ^ (int)((uint32_t)(bits >> 31) >> 1); }
+RR_DEV float wave_min_f32(float v) { return __int_as_float(float_order(wave_min_i32(float_order(__float_as_int(v))))); }
+RR_DEV float wave_max_f32(float v) { return __int_as_float(float_order(wave_max_i32(float_order(__float_as_int(v))))); }
+// the same for floats >= +0, whose bits order as unsigned integers
+RR_DEV float wave_min_pos_f32(float v) { return __uint_as_float(wave_min_u32(__float_as_uint(v))); }
+RR_DEV float wave_max_pos_f32(float v) { return __uint_as_float(wave_max_u32(__float_as_uint(v))); }
+// how many lanes below this one a ballot names (two instructions, and no lane mask to keep in registers)
+RR_DEV uint32_t lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 // The candidate list of a packet: lane l of the wave holds candidate l as (sort key, item); the key keeps the upper bits
 // of the distance at which the item's box can first be entered by any ray of the packet (a lower bound) and the lane in
 // its low six bits, 0xffffffff = none.  `far`: (wave-uniform) boxes that start beyond it are of no interest.
-// `boxes`: sc.item_boxes (the items' corner boxes: shadow packets, whose order and bounds are the LOCAL boxes' entry distances, which only a world box
-// around the local box bounds from below) or sc.item_boxes + 2 * n_items (their surface boxes: closest-hit packets; rr_scene_build.h build_tlas).
+// `set`: 0 = the items' corner boxes (shadow packets, whose order and bounds are the LOCAL boxes' entry distances, which only a world box
+// around the local box bounds from below), 1 = their surface boxes (closest-hit packets); rr_scene_build.h build_tlas, sc.item_boxes.
 // (A shadow packet that also dropped the items whose surface box none of its rays reaches gained nothing: 6.00 -> 6.02 ms.)
-RR_DEV bool beam_candidates(const DSceneView& sc, const float4* __restrict__ boxes, f3 o, f3 d, float far, int* s_stack, uint32_t* sk_out, int* item_out, uint32_t min_items = RR_BEAM_MIN_ITEMS) {
+//
+// Above 64 items the search has two levels (rr_beam.h has the records, rr_scene_build.h build_item_groups makes them): one GROUP box per
+// lane first, then the members of the surviving groups, one per lane, each against its OWN box.  Why no ray's result can change:
+// (a) The candidate set is the same set.  A group box contains its members' boxes bound by bound, and every step of the test is
+//     monotone in the box bounds: un and wf (a float difference), their products with a non-negative factor chosen by their
+//     sign, fmaxf / fminf, the constant factors.  So a group's key is at most each member's and its tf at least each member's: a
+//     rejected group has only rejected members.  What would break the chain is a NaN on one side only: a member bound that is
+//     not finite opens that side of the group box (build_item_groups), and the groups are searched only while every lower
+//     reciprocal bound is positive (beam_ray_takes_groups; else inf * 0 could make a member's axis NaN, which fminf / fmaxf drop,
+//     while the group's stays a number), the flat pass otherwise.  A group test that is NaN all the same passes (beam_group_passes).
+// (b) The list ORDER changes -- among equal truncated keys it followed the item index and now follows the group order -- and
+//     nothing depends on it: the closest-hit winner is a minimum over (t, key, idx) (closest_item_packet), the shadow
+//     selection a minimum over (key, idx) (shadow_item), and the `break` conditions of the two packet loops read the key only.
+// A member's key is that of the flat pass bit for bit: the same test on the same box.
+RR_DEV float4 box_row(const float4* boxes, uint32_t byte_off) { return *(const float4*)((const char*)boxes + byte_off); }
+RR_DEV bool beam_candidates(const DSceneView& sc, uint32_t set, f3 o, f3 d, float far, int* s_stack, uint32_t* sk_out, int* item_out, uint32_t min_items = RR_BEAM_MIN_ITEMS) {
     const uint32_t n_items = sc.n_items;
     if (n_items > RR_BEAM_MAX_ITEMS || n_items < min_items) return false;
     // coherent: finite rays, no zero direction component, one sign per axis
     const bool bad = ray_nonfinite(o, d) || !(fabsf(d.x) > 1e-30f) || !(fabsf(d.y) > 1e-30f) || !(fabsf(d.z) > 1e-30f);
     const unsigned long long nx_ = __ballot(d.x < 0.0f), ny_ = __ballot(d.y < 0.0f), nz_ = __ballot(d.z < 0.0f);
     if (__ballot(bad) != 0ull || (nx_ != 0ull && ~nx_ != 0ull) || (ny_ != 0ull && ~ny_ != 0ull) || (nz_ != 0ull && ~nz_ != 0ull)) return false;
-    const bool negx = nx_ != 0ull, negy = ny_ != 0ull, negz = nz_ != 0ull;
     const float ax = fabsf(__builtin_amdgcn_rcpf(d.x)), ay = fabsf(__builtin_amdgcn_rcpf(d.y)), az = fabsf(__builtin_amdgcn_rcpf(d.z));
-    const float oxl = wave_min_f32(o.x), oxh = wave_max_f32(o.x), oyl = wave_min_f32(o.y), oyh = wave_max_f32(o.y), ozl = wave_min_f32(o.z), ozh = wave_max_f32(o.z);
-    const float axl = wave_min_f32(ax) * 0.99999f, axh = wave_max_f32(ax) * 1.00001f;
-    const float ayl = wave_min_f32(ay) * 0.99999f, ayh = wave_max_f32(ay) * 1.00001f;
-    const float azl = wave_min_f32(az) * 0.99999f, azh = wave_max_f32(az) * 1.00001f;
+    BeamRay br;
+    br.negx = nx_ != 0ull; br.negy = ny_ != 0ull; br.negz = nz_ != 0ull;
+    br.oxl = wave_min_f32(o.x); br.oxh = wave_max_f32(o.x); br.oyl = wave_min_f32(o.y); br.oyh = wave_max_f32(o.y); br.ozl = wave_min_f32(o.z); br.ozh = wave_max_f32(o.z);
+    br.axl = wave_min_pos_f32(ax) * 0.99999f; br.axh = wave_max_pos_f32(ax) * 1.00001f;
+    br.ayl = wave_min_pos_f32(ay) * 0.99999f; br.ayh = wave_max_pos_f32(ay) * 1.00001f;
+    br.azl = wave_min_pos_f32(az) * 0.99999f; br.azh = wave_max_pos_f32(az) * 1.00001f;
     const uint32_t lane = threadIdx.x & (RR_WAVE - 1), wave_col = threadIdx.x & ~(RR_WAVE - 1u);
-    // the items' boxes against the interval ray, one item per lane; survivors appended to a list in the wave's own
-    // columns of two stack rows (nothing is on the stack yet)
-    uint32_t total = 0;
-    for (uint32_t base = 0; base < n_items; base += RR_WAVE) {
-        const uint32_t j = base + lane;
-        bool cand = false; float key = 0.0f;
-        if (j < n_items) {
-            const float4 lo = boxes[2u * j], hi = boxes[2u * j + 1u];
-            float tnx, tfx, tny, tfy, tnz, tfz;
-            beam_axis(negx, lo.x, hi.x, oxl, oxh, axl, axh, &tnx, &tfx);
-            beam_axis(negy, lo.y, hi.y, oyl, oyh, ayl, ayh, &tny, &tfy);
-            beam_axis(negz, lo.z, hi.z, ozl, ozh, azl, azh, &tnz, &tfz);
-            const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, 0.0f));
-            const float tf = fminf(fminf(tfx, tfy), tfz);
-            key = tn * (1.0f / RR_TOI_SLACK) * 0.99999f; // a lower bound on any toi the item can report
-            cand = key <= tf * 1.00001f && key <= far;
+    // The boxes against the interval ray, one per lane; survivors appended to a list in the wave's own columns of two stack rows
+    // (nothing is on the stack yet).  Up to 64 items the slots of a pass are the items themselves.  Above, the first pass has the
+    // groups for its slots and leaves the survivors, in order, in a third stack row; the slots of the passes after it are their
+    // members: slot s is member s & 7 of survivor s >> 3.  One loop, so that there is one copy of the test.
+    // (Everything is addressed from sc.item_boxes by a 32-bit offset that changes inside the loop: a pointer per record kind, or a
+    // lane's address of its group, does not change from packet to packet and would be kept in registers across the whole walk.)
+    const float4* __restrict__ boxes = sc.item_boxes;
+    const bool grouped = n_items > RR_WAVE && beam_ray_takes_groups(br); // (wave-uniform)
+    bool groups_now = grouped;
+    uint32_t n_slots = grouped ? beam_group_count(n_items) : n_items;
+    uint32_t first = grouped ? 8u * n_items + 2u * n_slots * set : 2u * n_items * set;
+    uint32_t total = 0, base = 0;
+    while (base < n_slots) {
+        uint32_t slot = base + lane, j = slot;
+        bool in = slot < n_slots;
+        if (grouped && !groups_now) { // (the last group may be short: its missing members are no candidates)
+            slot = in ? ((uint32_t)s_stack[3 * RR_BLOCK + wave_col + (slot >> RR_BEAM_GROUP_SHIFT)] << RR_BEAM_GROUP_SHIFT) + (slot & ((1u << RR_BEAM_GROUP_SHIFT) - 1u)) : n_items;
+            in = slot < n_items;
+        }
+        bool cand = false, through = false; float key = 0.0f;
+        if (in) {
+            const uint32_t at = (first + 2u * slot) << 4;
+            const float4 lo = box_row(boxes, at), hi = box_row(boxes, at + 16u);
+            float tf;
+            beam_box_test(br, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, &key, &tf); // key: a lower bound on any toi the item can report
+            cand = beam_item_passes(key, tf, far);
+            through = beam_group_passes(key, tf, far);
+            if (grouped) j = __float_as_uint(lo.w);
+        }
+        if (groups_now) {
+            const unsigned long long gm = __ballot(through);
+            if (through) s_stack[3 * RR_BLOCK + wave_col + lanes_below(gm)] = (int)slot;
+            __builtin_amdgcn_wave_barrier();
+            groups_now = false;
+            n_slots = (uint32_t)__popcll(gm) << RR_BEAM_GROUP_SHIFT;
+            first = 4u * n_items + 2u * n_items * set;
+            continue; // (base stays 0: there are at most 64 groups)
         }
         const unsigned long long m = __ballot(cand);
-        const uint32_t pos = total + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t pos = total + lanes_below(m);
         total += (uint32_t)__popcll(m);
         if (total > RR_WAVE) return false; // (wave-uniform) more candidates than lanes: not a packet worth treating as one
         if (cand) { s_stack[1 * RR_BLOCK + wave_col + pos] = __float_as_int(key); s_stack[2 * RR_BLOCK + wave_col + pos] = (int)j; }
+        base += RR_WAVE;
     }
     __builtin_amdgcn_wave_barrier();
     uint32_t sk = 0xffffffffu; int item = 0;
@@ -312,7 +354,7 @@ RR_DEV bool beam_next(uint32_t& sk, int item, float* key, int* idx) {
 }
 RR_DEV bool trace_closest_packet(const DSceneView& sc, f3 o, f3 d, uint32_t depth, int* s_stack, Closest* best) {
     uint32_t sk; int item;
-    if (!beam_candidates(sc, sc.item_boxes + 2u * sc.n_items, o, d, RR_FLT_MAX, s_stack, &sk, &item, RR_BEAM_MIN_ITEMS_CLOSEST)) return false;
+    if (!beam_candidates(sc, 1u, o, d, RR_FLT_MAX, s_stack, &sk, &item, RR_BEAM_MIN_ITEMS_CLOSEST)) return false;
     best->found = false; best->nan_seen = false; best->t = RR_FLT_MAX; best->item = -1; best->face = 0u; best->key = 0.0f;
     float key; int idx;
     while (beam_next(sk, item, &key, &idx)) {
@@ -469,7 +511,7 @@ RR_DEV void trace_shadow_ray(const DSceneView& sc, f3 o, f3 d, uint32_t depth, f
 // next box starts beyond every lane's bound (the light, or the key of the occluder selected so far).
 RR_DEV bool trace_shadow_packet(const DSceneView& sc, f3 o, f3 d, uint32_t depth, float limit, int* s_stack, ShadowSel* sel) {
     uint32_t sk; int item;
-    if (!beam_candidates(sc, sc.item_boxes, o, d, wave_max_f32(limit == limit ? limit : 0.0f), s_stack, &sk, &item)) return false;
+    if (!beam_candidates(sc, 0u, o, d, wave_max_f32(limit == limit ? limit : 0.0f), s_stack, &sk, &item)) return false;
     sel->found = false; sel->within = false; sel->key = 0.0f; sel->item = -1; sel->t = 0.0f; sel->face = 0u;
     float key; int idx;
     while (beam_next(sk, item, &key, &idx)) {
