@@ -50,7 +50,9 @@ extern "C" {
  * rr_refine_sublist_device, rr_render_adaptive_levels and rr_render_adaptive_levels_device came after those in the same way: a version-3
  * library may lack these three as well.
  * rr_render_pixel_prefix, rr_render_pixel_prefix_device, rr_render_adaptive_prefix and rr_render_adaptive_prefix_device came after those in
- * the same way: a version-3 library may lack these four as well. */
+ * the same way: a version-3 library may lack these four as well.
+ * rr_denoise_default_params, rr_denoise_records and rr_denoise_records_device (with rr_denoise_params, a struct of its own) came after
+ * those, again without a change of any existing struct: a version-3 library may lack these three as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -921,6 +923,74 @@ int rr_render_adaptive_prefix_device(rr_scene* scene, const rr_camera* camera, c
                                      rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */,
                                      uint16_t* samples_out_dev /* or NULL */, float* error_out_dev /* or NULL */,
                                      uint32_t* level_pixels_out /* n_levels, HOST, or NULL */, void* hip_stream, const volatile int* cancel);
+
+/* A denoiser for the records the calls above produce: an edge-avoiding a-trous wavelet filter (5x5 B3 spline, step 1, 2, 4, ... per pass)
+ * over a whole frame of rr_radiance records, on the device.  It is guided by the records' own object id, normal and depth; when the two
+ * halves of every pixel are given (rr_render_pixel_parts at K = 2, rr_render_pixel_prefix with halves_out) also by the luminance variance
+ * estimated from them, which costs no ray; with an albedo (rr_surface_rays_device over the pixel-centre rays: base_color) it runs on
+ * albedo-demodulated colour.  Without halves the filter is geometry-only: it does not cross an id, normal or depth edge, but blurs
+ * texture and shading inside a surface.
+ * As for the half-buffer error above, EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE: no transcendentals (the weights are
+ * rational functions), no contraction, division and sqrt correctly rounded.  A host that follows this text gets the same bits
+ * (rustray_amd/denoise.py: atrous_denoise does, in numpy).
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  lum(c) = (0.2126f*r + 0.7152f*g) + 0.0722f*b;  EPS = 2^-20.
+ *   Prepare, per pixel p.  fin_p: the three colour floats of records[p] are finite.  valid_p: depth and the three normal floats are.
+ *   With albedo, channel k of a colour is demodulated as c_k / a_k when 2^-10 < a_k <= FLT_MAX, otherwise left as it is; the same rule
+ *   is applied to both halves, and undone by * a_k at the end.  Variance, with halves: where fin_p holds and all six half colours (as
+ *   given) are finite, d = (lum(A) - lum(B)) * 0.5f on the demodulated halves and v_p = d*d, otherwise v_p = 0; then a 3x3 prefilter
+ *   over the taps q inside the frame with fin_q, row-major (dy outer), weights g = {1/2, 1/4}[|dx|] * {1/2, 1/4}[|dy|], both sums
+ *   starting at 0: var_p = (sum g*v_q) / (sum g).  Without halves, and where !fin_p, var_p = 0.
+ *   Pass i, step s = 2^i, for every p with fin_p.  Three sums start at 0; dy = -2..2 (outer), dx = -2..2 (inner), q = p + s*(dx, dy).
+ *   A tap is skipped when q lies outside the frame, !fin_q, id_q != id_p, or valid_q != valid_p.  Otherwise, in this order:
+ *     1. w = K[|dx|] * K[|dy|], K = {3/8, 1/4, 1/16}.
+ *     2. If valid_p: cs = dot(n_p, n_q); cs = cs > 0 ? cs : 0; normal_power_log2 times cs = cs*cs; w = w * cs; and unless dx = dy = 0:
+ *        t = |z_p - z_q| / ((sigma_depth * |z_p|) * (float)(s * max(|dx|, |dy|)) + EPS), w = w / (1.0f + t*t).
+ *     3. With halves: t = |lum(c_p) - lum(c_q)| / (sigma_luminance * sqrtf(var_p) + EPS), w = w / (1.0f + t*t); c and var are the
+ *        pass's input.
+ *     4. sum_c[k] += w * c_q[k]; sum_v += (w*w) * var_q; sum_w += w.
+ *   Then c'_p = sum_c / sum_w and var'_p = sum_v / (sum_w * sum_w).  A pixel with !fin_p keeps its colour bits and var 0 through every
+ *   pass and is never a tap.
+ *   Finish.  The colour is remodulated.  out[p].color is the result, for !fin_p the input's bits; out[p].depth, normal and object_id
+ *   are the input's bits.  rgba8_out (or NULL): the bytes rr_render_pixels writes for the record out[p], with params->gamma_correction
+ *   as rr_config's.  variance_out (or NULL): the last var.
+ * rr_denoise_params: struct_size = sizeof(rr_denoise_params); iterations 1 .. RR_MAX_DENOISE_ITERATIONS (pass i uses step 2^i);
+ * normal_power_log2 0 .. 7; sigma_depth and sigma_luminance finite and above 0 (sigma_luminance is used only with halves).
+ * rr_denoise_default_params writes 5 iterations, power 5, sigma_depth 0.05, sigma_luminance 4, no gamma; it never touches a device.
+ * rr_denoise_records_device: records_dev width * height records (pixel (x, y) at y * width + x), halves_dev width * height * 2 records
+ * in the K = 2 layout or NULL, albedo_dev width * height * 3 floats or NULL, out_dev width * height records.  The scene handle serves
+ * for its device, its lock and the buffers it keeps, as for rr_refine_list_device: every pointer is classified before any launch
+ * (RR_ERR_INVALID_ARGUMENT naming the argument); records_dev, halves_dev and out_dev 16-byte aligned, the others 4-byte aligned; work is
+ * enqueued on `hip_stream` in stream order (the inputs may have been produced on that stream without a synchronisation); the scene's
+ * lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene.  Nothing of a frame's state or statistics is touched, and the call does
+ * not wait inside; a scene edit or rr_scene_destroy waits for a call in flight.
+ *   out_dev == records_dev (in place) is allowed.  Every other overlap between an output and an input, or between two outputs, is
+ *   RR_ERR_INVALID_ARGUMENT.
+ *   Refusals: a NULL scene, params, records or out; width or height 0 or above 65535; a struct_size other than
+ *   sizeof(rr_denoise_params); iterations or power out of range; a sigma that is NaN, infinite or <= 0: RR_ERR_INVALID_ARGUMENT.
+ *   width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ *   Memory kept by the handle until rr_scene_destroy: 56 B per pixel of the largest frame so far (two working colours of 16 B, the
+ *   packed guide of 16 + 8 B).  A growth that fails is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.
+ * rr_denoise_records: the same on HOST pointers, the device form on the null stream behind a staging copy (32 + 32 B per pixel, and
+ * 64, 12, 4 and 4 B for halves, albedo, rgba8_out and variance_out where given, kept by the handle as well); it returns with `out` written. */
+#define RR_MAX_DENOISE_ITERATIONS 6u
+typedef struct rr_denoise_params {
+    uint32_t struct_size;        /* sizeof(rr_denoise_params) */
+    uint32_t iterations;         /* 1 .. RR_MAX_DENOISE_ITERATIONS; pass i uses step 2^i */
+    uint32_t normal_power_log2;  /* 0 .. 7: the normal weight is max(0, n_p . n_q) squared this many times */
+    float    sigma_depth;        /* > 0, finite */
+    float    sigma_luminance;    /* > 0, finite; used only with halves */
+    uint32_t gamma_correction;   /* rgba8_out only, as rr_config's */
+} rr_denoise_params;
+int rr_denoise_default_params(rr_denoise_params* out);
+int rr_denoise_records_device(rr_scene* scene, uint32_t width, uint32_t height, const rr_denoise_params* params,
+                              const rr_radiance* records_dev /* width * height */, const rr_radiance* halves_dev /* width * height * 2, or NULL */,
+                              const float* albedo_dev /* width * height * 3, or NULL */,
+                              rr_radiance* out_dev /* width * height */, uint8_t* rgba8_out_dev /* or NULL */, float* variance_out_dev /* width * height, or NULL */,
+                              void* hip_stream);
+int rr_denoise_records(rr_scene* scene, uint32_t width, uint32_t height, const rr_denoise_params* params,
+                       const rr_radiance* records /* width * height */, const rr_radiance* halves /* width * height * 2, or NULL */,
+                       const float* albedo /* width * height * 3, or NULL */,
+                       rr_radiance* out /* width * height */, uint8_t* rgba8_out /* or NULL */, float* variance_out /* width * height, or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -665,6 +665,41 @@ public:
                                                 level_pixels, hip_stream, cancel);
     }
 
+    // The a-trous filter over a frame of this camera's size (rr_denoise_records): `records` width * height records in row-major order,
+    // `halves` twice as many in the layout of render_pixel_parts at n_parts = 2 or nullptr (geometry only), `albedo` width * height * 3
+    // floats or nullptr; `params` nullptr = rr_denoise_default_params.  Returns the filtered records (depth, normal and id are the
+    // input's bits); variance (or nullptr) gets the last variance, rgba8 (or nullptr) the frame's bytes of the filtered records.  An
+    // empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_radiance> denoise(const rr_radiance* records, const rr_radiance* halves, const float* albedo, const rr_denoise_params* params = nullptr,
+                                     std::vector<float>* variance = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+        std::vector<rr_radiance> out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_denoise_params prm;
+        if (params) prm = *params;
+        else if (rr_denoise_default_params(&prm) != RR_OK) return out;
+        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (variance) variance->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_denoise_records(scene->handle(), camera.width, camera.height, &prm, records, halves, albedo, out.data(), rgba8 ? rgba8->data() : nullptr,
+                               variance ? variance->data() : nullptr) != RR_OK) {
+            out.clear();
+            if (variance) variance->clear();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // The whole frame in two halves (render_pixel_parts at n_parts = 2; config.samples even) followed by the filter guided by their
+    // variance.  noisy (or nullptr) gets the records before the filter.  An empty vector = refused or failed.
+    std::vector<rr_radiance> render_denoised(const rr_denoise_params* params = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
+                                             std::vector<rr_radiance>* noisy = nullptr) const {
+        std::vector<rr_radiance> halves;
+        const std::vector<rr_radiance> records = render_pixel_parts(nullptr, 0, 2, &halves);
+        if (records.empty()) return records;
+        if (noisy) *noisy = records;
+        return denoise(records.data(), halves.data(), nullptr, params, nullptr, rgba8);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -23,12 +23,18 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
     """include/rustray_hip.h: one record of rr_trace_shadow_rays."""
     _fields_ = [("occluded", C.c_uint32), ("item_index", C.c_uint32), ("object_id", C.c_uint32), ("face_id", C.c_uint32), ("distance", C.c_float)]
+
+
+class rr_denoise_params(C.Structure):
+    """include/rustray_hip.h: the parameters of rr_denoise_records."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_depth", C.c_float),
+                ("sigma_luminance", C.c_float), ("gamma_correction", C.c_uint32)]
 
 
 class RustrayHipError(RuntimeError):
@@ -42,8 +48,8 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_probe.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -147,6 +153,14 @@ def lib():
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rr_render_adaptive_prefix_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_denoise_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_denoise_default_params.argtypes = [C.POINTER(rr_denoise_params)]
+            L.rr_denoise_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+            L.rr_denoise_records_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_test_denoise_forms.argtypes = [C.c_uint32]
+            L.rr_test_denoise_forms.restype = None
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -199,6 +213,41 @@ def sample_table(samples: int):
 def refine_list_capacity(width: int, height: int) -> int:
     """rr_refine_list_capacity: entries a refinement list of a width x height frame may need (every pixel, padded to a multiple of 64)."""
     return int(lib().rr_refine_list_capacity(C.c_uint32(width), C.c_uint32(height)))
+
+
+def denoise_default_params() -> rr_denoise_params:
+    """rr_denoise_default_params: 5 iterations, power 5, sigma_depth 0.05, sigma_luminance 4, no gamma (never touches a device)."""
+    p = rr_denoise_params()
+    _check(lib().rr_denoise_default_params(C.byref(p)))
+    return p
+
+
+def denoise_params(params=None) -> rr_denoise_params:
+    """A denoise.DenoiseParams (or None: the library's defaults) as the C struct; a C struct is passed through."""
+    if isinstance(params, rr_denoise_params):
+        return params
+    p = denoise_default_params()
+    if params is not None:
+        p.iterations, p.normal_power_log2 = int(params.iterations), int(params.normal_power_log2)
+        p.sigma_depth, p.sigma_luminance = float(params.sigma_depth), float(params.sigma_luminance)
+        p.gamma_correction = 1 if params.gamma_correction else 0
+    return p
+
+
+# the forms a pass of rr_denoise_records can run in (rustray_amd/csrc/rr_denoise.h)
+DENOISE_FORM_AUTO, DENOISE_FORM_GATHER, DENOISE_FORM_TILE, DENOISE_FORM_LATTICE = 0, 1, 2, 3
+
+
+def denoise_forms(forms=None):
+    """The tuning hook of rr_denoise_records, process-wide: forms[i] is the form of pass i (DENOISE_FORM_*; a form that does not exist
+    at that pass's step leaves it automatic); None = every pass automatic, the shipped choice.  The bits do not depend on it: for the
+    tests that say so and for tools/denoise_time.py."""
+    word = 0
+    for i, f in enumerate(forms or ()):
+        if not 0 <= int(f) <= 3 or i >= 6:
+            raise ValueError(f"forms {forms}")
+        word |= int(f) << (4 * i)
+    lib().rr_test_denoise_forms(C.c_uint32(word))
 
 
 def region_pixel_count(width: int, height: int, tile_w: int, tile_h: int, n_ranks: int, rank: int) -> int:
@@ -654,6 +703,38 @@ class DeviceScene:
         _check(lib().rr_render_adaptive_prefix_device(self._h, C.byref(cam), C.byref(cfg), p, _data(lv), C.c_uint32(len(lv)), C.c_float(threshold), _ptr(out_ptr),
                                                       _ptr(rgba8_ptr), _ptr(samples_ptr), _ptr(error_ptr), _data(level_pixels), _ptr(stream_ptr), _flag(cancel)))
         return [int(v) for v in level_pixels[:len(lv)]]
+
+    # -- the a-trous filter over a frame of records ------------------------------------
+    def denoise_records(self, width: int, height: int, records, halves=None, albedo=None, params=None, rgba8: bool = False, variance: bool = True,
+                        in_place: bool = False) -> dict:
+        """rr_denoise_records: denoise.atrous_denoise on the device, host arrays in and out.  records: (n, 8) float32 rr_radiance records of
+        the whole frame in row-major order; halves: (n, 2, 8) or None; albedo: (n, 3) or None; params: a denoise.DenoiseParams or None.
+        Returns dict(records (n, 8) float32, and on request variance (n,) float32 and rgba (n, 4) uint8); in_place filters a copy of
+        `records` in place (out == records)."""
+        n = int(width) * int(height)
+        rec = np.array(records, np.float32, order="C").reshape(n, 8) if in_place else np.ascontiguousarray(records, np.float32).reshape(n, 8)
+        hv = None if halves is None else np.ascontiguousarray(halves, np.float32).reshape(n, 2, 8)
+        al = None if albedo is None else np.ascontiguousarray(albedo, np.float32).reshape(n, 3)
+        out = rec if in_place else np.zeros((n, 8), np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        var = np.zeros(n, np.float32) if variance else None
+        p = denoise_params(params)
+        _check(lib().rr_denoise_records(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _data(rec), _data(hv), _data(al), _data(out), _data(rgba), _data(var)))
+        res = dict(records=out)
+        if variance:
+            res["variance"] = var
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def denoise_records_device(self, width: int, height: int, records_ptr, halves_ptr, albedo_ptr, out_ptr, rgba8_ptr=None, variance_ptr=None, params=None,
+                               stream_ptr=None):
+        """rr_denoise_records_device: width * height 32-byte records in and out (16-byte aligned; out_ptr may be records_ptr), optionally
+        twice as many half records, width * height * 3 float32 of albedo, width * height x 4 bytes and as many float32 of variance, all raw
+        device pointers; enqueued on `stream_ptr`, not waited for."""
+        p = denoise_params(params)
+        _check(lib().rr_denoise_records_device(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(albedo_ptr),
+                                               _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(variance_ptr), _ptr(stream_ptr)))
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

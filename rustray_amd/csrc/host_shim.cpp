@@ -320,6 +320,32 @@ extern "C" int rh_render_adaptive_prefix_device(void* h, float fov, const float*
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).render_adaptive_prefix_device(prefixes, n_levels, threshold, out_dev, rgba8_dev, samples_dev, error_dev,
                                                                                                  level_pixels, stream, cancel);
 }
+// Raytracing::denoise: records = w * h, halves = w * h * 2 or NULL, albedo = w * h * 3 or NULL, params or NULL for the defaults; out = w * h
+// records, variance = w * h floats or NULL, rgba8 = w * h x 4 bytes or NULL; returns 0, or -1 when the call was refused.
+// rh_render_denoised: Raytracing::render_denoised; noisy = w * h records or NULL.
+extern "C" int rh_denoise(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                          uint32_t w, uint32_t hgt, const rr_radiance* records, const rr_radiance* halves, const float* albedo, const rr_denoise_params* params,
+                          rr_radiance* out, float* variance, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<float> var; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.denoise(records, halves, albedo, params, variance ? &var : nullptr, rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (variance) std::memcpy(variance, var.data(), var.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
+extern "C" int rh_render_denoised(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                  uint32_t w, uint32_t hgt, const rr_denoise_params* params, rr_radiance* out, uint8_t* rgba8, rr_radiance* noisy) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<uint8_t> bytes; std::vector<rr_radiance> raw;
+    const std::vector<rr_radiance> r = rt.render_denoised(params, rgba8 ? &bytes : nullptr, noisy ? &raw : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
+    return 0;
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -1,0 +1,165 @@
+// rr_api_denoise.h — the variance-guided a-trous filter over a frame of records, on the device: what a host does with the records,
+// the halves and the albedo the other calls give it, without a trip through host memory.
+// Offers: rr_denoise_default_params, rr_denoise_records_device, rr_denoise_records; rr_test_denoise_forms (the tuning hook of the tests
+//         and of tools/denoise_time.py).
+// Needs:  rr_api_query.h (check_query_pointers), rr_api_frame.h (take_stream, IdleOnExit), rr_api_adaptive.h (launch_record_bytes),
+//         rr_denoise.h, kernels 7a .. 7d of rr_kernels.hip.
+//
+// The call is k_denoise_prepare, one pass launch per iteration (step 1, 2, 4, ...), k_denoise_finish and, for the bytes, k_record_bytes:
+// all on the caller's stream, none of them waited for.  The working data are the handle's (DenoiseState): two working colours of 16 B,
+// the guide of 16 + 8 B: 56 B per pixel of the largest frame so far.  The host form is the device form behind a staging copy.
+
+// ---- which form of the pass kernel runs a step.  Measured at 1280x720 (profiles/r10_denoise_time.txt; the forms that lost:
+// profiles/r10_dropped.txt): steps 1 and 2 through an LDS tile of the frame, steps 4 and 8 as one dense tile per residue class of the
+// step's sub-lattice, step 16 gathered from global memory; step 32 was not measured and is gathered like step 16.  The bits are the
+// same in every form (tests/test_gpu_denoise.py).
+static int denoise_auto_form(int step) { return step <= 2 ? DN_FORM_TILE : step <= 8 ? DN_FORM_LATTICE : DN_FORM_GATHER; }
+
+// The tuning hook: four bits per pass, pass i in bits 4 i .. 4 i + 3: DN_FORM_AUTO (0), DN_FORM_GATHER, DN_FORM_TILE, DN_FORM_LATTICE.  A
+// form that does not exist at a pass's step (rr_denoise.h: denoise_form_available) leaves that pass automatic.  Process-wide, read
+// once per call; 0 (always, outside the tests and the timing tool) = automatic.
+static std::atomic<uint32_t> g_denoise_forms{0u};
+extern "C" void rr_test_denoise_forms(uint32_t forms) { g_denoise_forms.store(forms); }
+static int denoise_form(uint32_t forms, uint32_t pass_index, int step) {
+    const int forced = (int)((forms >> (4u * pass_index)) & 15u);
+    return forced != DN_FORM_AUTO && denoise_form_available(forced, step) ? forced : denoise_auto_form(step);
+}
+
+int rr_denoise_default_params(rr_denoise_params* out) try {
+    if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "rr_denoise_default_params: out is NULL");
+    out->struct_size = (uint32_t)sizeof(rr_denoise_params);
+    out->iterations = 5u;
+    out->normal_power_log2 = 5u;
+    out->sigma_depth = 0.05f;
+    out->sigma_luminance = 4.0f;
+    out->gamma_correction = 0u;
+    return RR_OK;
+} RR_GUARD_END("rr_denoise_default_params")
+
+struct DenoiseIo {
+    const rr_radiance* records; const rr_radiance* halves; const float* albedo;
+    rr_radiance* out; uint8_t* rgba8; float* variance;
+};
+
+// what both forms check before the scene is looked at; `device`: the alignment rule of the device form
+static int check_denoise_args(const char* fn, bool device, const rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const DenoiseIo& io) {
+    if (!s) return fail(RR_ERR_INVALID_ARGUMENT, "%s: scene is NULL", fn);
+    if (!prm) return fail(RR_ERR_INVALID_ARGUMENT, "%s: params is NULL", fn);
+    if (!io.records) return fail(RR_ERR_INVALID_ARGUMENT, "%s: records is NULL", fn);
+    if (!io.out) return fail(RR_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: bad frame size %ux%u", fn, width, height);
+    if (prm->struct_size != sizeof(rr_denoise_params))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: params->struct_size %u, expected %u", fn, prm->struct_size, (unsigned)sizeof(rr_denoise_params));
+    if (prm->iterations == 0 || prm->iterations > RR_MAX_DENOISE_ITERATIONS)
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: iterations %u (1 .. %u)", fn, prm->iterations, RR_MAX_DENOISE_ITERATIONS);
+    if (prm->normal_power_log2 > 7u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: normal_power_log2 %u (0 .. 7)", fn, prm->normal_power_log2);
+    if (!(prm->sigma_depth > 0.0f) || !denoise_is_finite(prm->sigma_depth)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: sigma_depth must be finite and above 0", fn);
+    if (!(prm->sigma_luminance > 0.0f) || !denoise_is_finite(prm->sigma_luminance))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: sigma_luminance must be finite and above 0", fn);
+    if ((uint64_t)width * height * 2u > (1ull << 30))
+        return fail(RR_ERR_UNSUPPORTED, "%s: %ux%u pixels x 2 halves are more than 2^30 records", fn, width, height);
+    if (device && (((uintptr_t)io.records | (uintptr_t)io.halves | (uintptr_t)io.out) & 15u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: records_dev, halves_dev and out_dev must be 16-byte aligned", fn);
+    if (device && (((uintptr_t)io.albedo | (uintptr_t)io.rgba8 | (uintptr_t)io.variance) & 3u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: albedo_dev, rgba8_out_dev and variance_out_dev must be 4-byte aligned", fn);
+    // overlaps: an output with an input or with another output; out == records exactly is the in-place call
+    const uint64_t n = (uint64_t)width * height;
+    struct Range { const void* p; uint64_t bytes; const char* name; };
+    const Range in[3] = {{io.records, 32u * n, "records"}, {io.halves, 64u * n, "halves"}, {io.albedo, 12u * n, "albedo"}};
+    const Range outs[3] = {{io.out, 32u * n, "out"}, {io.rgba8, 4u * n, "rgba8_out"}, {io.variance, 4u * n, "variance_out"}};
+    auto overlap = [](const Range& a, const Range& b) {
+        return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < (uintptr_t)a.p + a.bytes;
+    };
+    for (int o = 0; o < 3; o++) {
+        for (int i = 0; i < 3; i++)
+            if (overlap(outs[o], in[i]) && !(o == 0 && i == 0 && io.out == io.records))
+                return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s (only out == records, in place, is allowed)", fn, outs[o].name, in[i].name);
+        for (int o2 = o + 1; o2 < 3; o2++)
+            if (overlap(outs[o], outs[o2])) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, outs[o].name, outs[o2].name);
+    }
+    return RR_OK;
+}
+
+// the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
+static int denoise_locked(rr_scene* s, uint32_t W, uint32_t H, const rr_denoise_params* prm, const DenoiseIo& io, hipStream_t st) {
+    const uint64_t N = (uint64_t)W * H;
+    DenoiseState& d = s->denoise;
+    HIP_TRY(d.work[0].reserve(16ull * N));
+    HIP_TRY(d.work[1].reserve(16ull * N));
+    HIP_TRY(d.guide.reserve(16ull * N));
+    HIP_TRY(d.meta.reserve(8ull * N));
+    float4* work[2] = {d.work[0].as<float4>(), d.work[1].as<float4>()};
+    const dim3 grid((W + DN_TILE_W - 1) / DN_TILE_W, (H + DN_TILE_H - 1) / DN_TILE_H), block(RR_BLOCK);
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, st, (const float4*)io.records, (const float4*)io.halves, io.albedo, W, H, work[0], d.guide.as<float4>(),
+                       d.meta.as<uint2>());
+    const uint32_t forms = g_denoise_forms.load();
+    int cur = 0;
+    for (uint32_t i = 0; i < prm->iterations; i++, cur ^= 1) {
+        DnPass pass{prm->sigma_depth, prm->sigma_luminance, prm->normal_power_log2, io.halves ? 1u : 0u, 1 << i};
+        const int form = denoise_form(forms, i, pass.step);
+        if (form == DN_FORM_GATHER) {
+            hipLaunchKernelGGL(k_denoise_pass_gather, grid, block, 0, st, work[cur], d.guide.as<float4>(), d.meta.as<uint2>(), W, H, pass, work[cur ^ 1]);
+        } else {
+            const int L = form == DN_FORM_LATTICE ? pass.step : 1, halo = 2 * (pass.step / L);
+            // the largest residue class has ceil(W / L) x ceil(H / L) lattice points; workgroups of smaller classes beyond theirs return at once
+            const uint32_t wl = (W + L - 1) / L, hl = (H + L - 1) / L;
+            const dim3 tgrid((wl + DN_TILE_W - 1) / DN_TILE_W, (hl + DN_TILE_H - 1) / DN_TILE_H, (uint32_t)(L * L));
+            hipLaunchKernelGGL(k_denoise_pass_tile, tgrid, block, (size_t)(40ull * denoise_tile_entries(halo)), st, work[cur], d.guide.as<float4>(), d.meta.as<uint2>(), W, H,
+                               pass, L, work[cur ^ 1]);
+        }
+    }
+    hipLaunchKernelGGL(k_denoise_finish, grid, block, 0, st, (const float4*)io.records, io.albedo, work[cur], d.meta.as<uint2>(), W, H, (float4*)io.out, io.variance);
+    if (io.rgba8) {
+        rr_config cfg{};
+        cfg.gamma_correction = prm->gamma_correction ? 1 : 0;
+        launch_record_bytes(s, &cfg, io.out, (uint32_t)N, io.rgba8, st);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(RR_ERR_DEVICE, "rr_denoise_records: a launch failed");
+    return RR_OK;
+}
+
+int rr_denoise_records_device(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                              const float* albedo, rr_radiance* out, uint8_t* rgba8_out, float* variance_out, void* hip_stream) try {
+    const DenoiseIo io{records, halves, albedo, out, rgba8_out, variance_out};
+    RR_TRY(check_denoise_args("rr_denoise_records_device", true, s, width, height, prm, io));
+    RR_TRY(not_in_pass(s, "rr_denoise_records_device"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    RR_TRY(check_query_pointers(s, "rr_denoise_records_device", {{records, "records_dev"}, {halves, "halves_dev"}, {albedo, "albedo_dev"}, {out, "out_dev"},
+                                                                  {rgba8_out, "rgba8_out_dev"}, {variance_out, "variance_out_dev"}}));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(take_stream(s, st));
+    IdleOnExit idle(st);
+    return idle.done(denoise_locked(s, width, height, prm, io, st));
+} RR_GUARD_END("rr_denoise_records_device")
+
+int rr_denoise_records(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                       const float* albedo, rr_radiance* out, uint8_t* rgba8_out, float* variance_out) try {
+    const DenoiseIo host{records, halves, albedo, out, rgba8_out, variance_out};
+    RR_TRY(check_denoise_args("rr_denoise_records", false, s, width, height, prm, host));
+    RR_TRY(not_in_pass(s, "rr_denoise_records"));
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    RR_TRY(take_stream(s, nullptr));
+    IdleOnExit idle(nullptr);
+    // the staging is the handle's (DenoiseState::stage: grown, kept, used by the host form only, which returns with the stream idle)
+    const size_t n = (size_t)width * height;
+    DevBuf* g = s->denoise.stage;
+    HIP_TRY(g[0].reserve(32 * n));
+    HIP_TRY(g[3].reserve(32 * n));
+    if (halves) HIP_TRY(g[1].reserve(64 * n));
+    if (albedo) HIP_TRY(g[2].reserve(12 * n));
+    if (rgba8_out) HIP_TRY(g[4].reserve(4 * n));
+    if (variance_out) HIP_TRY(g[5].reserve(4 * n));
+    HIP_TRY(hipMemcpyAsync(g[0].p, records, 32 * n, hipMemcpyHostToDevice, nullptr));
+    if (halves) HIP_TRY(hipMemcpyAsync(g[1].p, halves, 64 * n, hipMemcpyHostToDevice, nullptr));
+    if (albedo) HIP_TRY(hipMemcpyAsync(g[2].p, albedo, 12 * n, hipMemcpyHostToDevice, nullptr));
+    const DenoiseIo dev{g[0].as<rr_radiance>(), halves ? g[1].as<rr_radiance>() : nullptr, albedo ? g[2].as<float>() : nullptr, g[3].as<rr_radiance>(),
+                        rgba8_out ? g[4].as<uint8_t>() : nullptr, variance_out ? g[5].as<float>() : nullptr};
+    RR_TRY(denoise_locked(s, width, height, prm, dev, nullptr));
+    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, g[4].p, 4 * n, hipMemcpyDeviceToHost, nullptr));
+    if (variance_out) HIP_TRY(hipMemcpyAsync(variance_out, g[5].p, 4 * n, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpy(out, g[3].p, 32 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return idle.done(RR_OK);
+} RR_GUARD_END("rr_denoise_records")

@@ -1,5 +1,5 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
-// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, MultiState, FrameTiming
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, MultiState, FrameTiming
 //         and rr_scene, which holds one of each; HC_* (the words of FrameState::h_count); check_intact.
 // Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
@@ -131,6 +131,14 @@ struct AdaptiveState {
     DevBuf scratch, parts, list, fine, list2, acc_set[2];
 };
 
+// ---- rr_denoise_records (rr_api_denoise.h): grown on demand, never shrunk.  work: the working colour (r, g, b, var), ping-pong, 16 B per
+// pixel each; guide: normal and depth, 16 B; meta: object id and flags, 8 B -- 56 B per pixel of the largest frame so far.  stage: the
+// host form's copies of records, halves, albedo, out, rgba8_out and variance_out (32 + 64 + 12 + 32 + 4 + 4 B per pixel, each only where
+// the call has it).  Written by rr_api_denoise.h.
+struct DenoiseState {
+    DevBuf work[2], guide, meta, stage[6];
+};
+
 // ---- rr_render_multi (rr_api_multi.h)
 struct MultiState {
     DevBuf part[4], cat[4]; // this device's compact buffers; on device slot 0 the concatenation of all
@@ -183,6 +191,7 @@ struct rr_scene {
     FrameState frame;
     QueryState query;
     AdaptiveState adaptive;
+    DenoiseState denoise;
     MultiState multi;
     FrameTiming timing;
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's

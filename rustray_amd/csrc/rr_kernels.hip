@@ -23,6 +23,7 @@
 #include "rr_math.h"
 #include "rr_primary_setup.h"
 #include "rr_adaptive.h" // half_error and the 8x8-block order of a refinement list (kernels 5l .. 5p)
+#include "rr_denoise.h"  // the arithmetic of the a-trous filter (kernels 7a .. 7d)
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -1647,6 +1648,171 @@ __global__ __launch_bounds__(RR_BLOCK) void k_post_process(uint32_t width, uint3
     g = (g < 0.0f) ? 0.0f : ((g > 255.0f) ? 255.0f : g);
     b = (b < 0.0f) ? 0.0f : ((b > 255.0f) ? 255.0f : b);
     rgba_out[i] = as_u8(r) | (as_u8(g) << 8) | (as_u8(b) << 16) | (255u << 24);
+}
+
+// ---------------------------------------------------------------------------
+// kernels 7a .. 7d: the variance-guided a-trous filter over a frame of records (rr_denoise_records; rr_denoise.h has the arithmetic, in
+// the order the header states; rustray_amd/denoise.py is the yardstick)
+// ---------------------------------------------------------------------------
+// Every kernel here works a 32x8 tile of pixels per workgroup, one pixel per lane, a tile row per half wave.  Working data are the
+// handle's: the working colour as ping-pong float4 (r, g, b, var), the guide packed once as float4 (normal, depth) and uint2 (id, flags).
+// A lane whose pixel lies outside the frame does nothing after the last barrier of its kernel.
+//
+// 7a: prepare.  Per pixel: the flags, the guide, the (demodulated) colour, and with halves the variance: the seeds of the tile and a
+// halo of one pixel go through LDS (34 x 10 floats; a seed is >= 0, -1 marks "no tap": outside the frame or colour not finite), then the
+// 3x3 prefilter.  halves: the K = 2 layout (part h of pixel o: two float4 at 4 o + 2 h); albedo: 3 floats per pixel; either may be NULL.
+RR_DEV uint32_t denoise_record_flags(const float4 r0, const float4 r1) {
+    const float c[3] = {r0.x, r0.y, r0.z}, n[3] = {r1.x, r1.y, r1.z};
+    return denoise_flags(c, r0.w, n);
+}
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_prepare(const float4* __restrict__ records, const float4* __restrict__ halves, const float* __restrict__ albedo,
+                                                              uint32_t width, uint32_t height, float4* __restrict__ work, float4* __restrict__ guide,
+                                                              uint2* __restrict__ meta) {
+    __shared__ float s_v[(DN_TILE_H + 2) * (DN_TILE_W + 2)];
+    const int x0 = (int)blockIdx.x * DN_TILE_W, y0 = (int)blockIdx.y * DN_TILE_H;
+    if (halves) {
+        for (int e = (int)threadIdx.x; e < (DN_TILE_H + 2) * (DN_TILE_W + 2); e += RR_BLOCK) {
+            const int qx = x0 - 1 + e % (DN_TILE_W + 2), qy = y0 - 1 + e / (DN_TILE_W + 2);
+            float v = -1.0f;
+            if (qx >= 0 && qy >= 0 && qx < (int)width && qy < (int)height) {
+                const unsigned long long o = (unsigned long long)qy * width + (unsigned int)qx;
+                const float4 r0 = records[2ull * o];
+                const float c[3] = {r0.x, r0.y, r0.z};
+                if (denoise_is_finite(c[0]) && denoise_is_finite(c[1]) && denoise_is_finite(c[2])) {
+                    const float4 ha = halves[4ull * o], hb = halves[4ull * o + 2];
+                    const float a[3] = {ha.x, ha.y, ha.z}, b[3] = {hb.x, hb.y, hb.z};
+                    v = denoise_variance_seed(true, a, b, albedo ? albedo + 3ull * o : nullptr);
+                }
+            }
+            s_v[e] = v;
+        }
+        __syncthreads();
+    }
+    const int tx = (int)threadIdx.x & (DN_TILE_W - 1), ty = (int)threadIdx.x / DN_TILE_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= (int)width || y >= (int)height) return;
+    const unsigned long long o = (unsigned long long)y * width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    const uint32_t flags = denoise_record_flags(r0, r1);
+    float c[3] = {r0.x, r0.y, r0.z}, var = 0.0f;
+    if (flags & DN_FIN) {
+        if (albedo)
+            for (int k = 0; k < 3; k++) c[k] = denoise_demodulate(c[k], albedo[3ull * o + k]);
+        if (halves)
+            var = denoise_prefilter([&](int dx, int dy, float* v) {
+                *v = s_v[(ty + 1 + dy) * (DN_TILE_W + 2) + tx + 1 + dx];
+                return *v >= 0.0f;
+            });
+    }
+    work[o] = make_float4(c[0], c[1], c[2], var);
+    guide[o] = make_float4(r1.x, r1.y, r1.z, r0.w);
+    meta[o] = make_uint2(__float_as_uint(r1.w), flags);
+}
+
+RR_DEV DnTap denoise_make_tap(const float4 w, const float4 g, const uint2 m) {
+    DnTap t;
+    t.c[0] = w.x; t.c[1] = w.y; t.c[2] = w.z; t.var = w.w;
+    t.n[0] = g.x; t.n[1] = g.y; t.n[2] = g.z; t.z = g.w;
+    t.id = m.x; t.flags = m.y;
+    return t;
+}
+
+// 7b: one pass, every tap gathered straight from global memory (the form of the large steps: the taps of a lane's neighbours are the
+// neighbours of its taps, so each of the 25 loads of a wave is two runs of 512 contiguous bytes).  A tap's id and flags are read first;
+// its colour and guide only where it is taken.
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_pass_gather(const float4* __restrict__ in, const float4* __restrict__ guide, const uint2* __restrict__ meta,
+                                                                  uint32_t width, uint32_t height, DnPass pass, float4* __restrict__ out) {
+    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
+    if (x >= (int)width || y >= (int)height) return;
+    const unsigned long long o = (unsigned long long)y * width + (unsigned int)x;
+    const float4 w_p = in[o];
+    const uint2 m_p = meta[o];
+    if (!(m_p.y & DN_FIN)) { out[o] = w_p; return; }
+    const DnTap p = denoise_make_tap(w_p, guide[o], m_p);
+    float c[3], var;
+    denoise_pixel_pass(pass, p, [&](int dx, int dy, DnTap* q) {
+        const int qx = x + dx * pass.step, qy = y + dy * pass.step;
+        if (qx < 0 || qy < 0 || qx >= (int)width || qy >= (int)height) return false;
+        const unsigned long long oq = (unsigned long long)qy * width + (unsigned int)qx;
+        const uint2 m_q = meta[oq];
+        q->id = m_q.x; q->flags = m_q.y;
+        if (!denoise_tap_taken(p, *q)) return false;
+        *q = denoise_make_tap(in[oq], guide[oq], m_q);
+        return true;
+    }, c, &var);
+    out[o] = make_float4(c[0], c[1], c[2], var);
+}
+
+// 7c: one pass through LDS.  The kernel works on the sub-lattice of period L of the frame -- the pixels (rx + L i, ry + L j) of residue
+// class blockIdx.z = ry * L + rx -- on which the pass is a filter of step u = step / L: a 32x8 tile of lattice points plus a halo of
+// h = 2 u points is staged in LDS (working colour, guide, id and flags; 40 B per point), and the 25 taps of every lane are LDS reads.
+//   L = 1, u = step: the frame itself, for the small steps (h = 2, 4, 8);
+//   L = step, u = 1: one dense 36 x 12 tile per residue class, for the large steps, whose halo in the frame would outgrow the tile.
+// LDS: float4 arrays in row-major tile order; a wave reads two tile rows, 32 consecutive 16-byte slots each, and the four 16-lane groups
+// of a ds_read_b128 each stay inside one row: 16 distinct slots of one 256-byte bank row whatever the tile's pitch, so the reads are
+// conflict-free without padding (as are the staging writes, whose lanes walk the tile linearly).  Dynamic LDS: 40 B x (32 + 2h)(8 + 2h).
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_pass_tile(const float4* __restrict__ in, const float4* __restrict__ guide, const uint2* __restrict__ meta,
+                                                                uint32_t width, uint32_t height, DnPass pass, int lattice, float4* __restrict__ out) {
+    extern __shared__ float4 s_dn[];
+    const int L = lattice, u = pass.step / L, h = 2 * u;
+    const int rx = (int)blockIdx.z % L, ry = (int)blockIdx.z / L;
+    if (rx >= (int)width || ry >= (int)height) return; // (uniform over the workgroup, as the next one: before any barrier)
+    const int wl = ((int)width - rx + L - 1) / L, hl = ((int)height - ry + L - 1) / L; // lattice points of this class
+    const int i0 = (int)blockIdx.x * DN_TILE_W, j0 = (int)blockIdx.y * DN_TILE_H;
+    if (i0 >= wl || j0 >= hl) return;
+    const int tw = DN_TILE_W + 2 * h, th = DN_TILE_H + 2 * h, n_e = tw * th;
+    float4* s_work = s_dn;
+    float4* s_guide = s_dn + n_e;
+    uint2* s_meta = (uint2*)(s_dn + 2 * n_e);
+    for (int e = (int)threadIdx.x; e < n_e; e += RR_BLOCK) {
+        const int i = i0 - h + e % tw, j = j0 - h + e / tw;
+        float4 w = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = w;
+        uint2 m = make_uint2(0u, DN_ABSENT);
+        if (i >= 0 && j >= 0 && i < wl && j < hl) {
+            const unsigned long long oq = (unsigned long long)(ry + L * j) * width + (unsigned int)(rx + L * i);
+            w = in[oq]; g = guide[oq]; m = meta[oq];
+        }
+        s_work[e] = w; s_guide[e] = g; s_meta[e] = m;
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x & (DN_TILE_W - 1), ty = (int)threadIdx.x / DN_TILE_W;
+    if (i0 + tx >= wl || j0 + ty >= hl) return;
+    const unsigned long long o = (unsigned long long)(ry + L * (j0 + ty)) * width + (unsigned int)(rx + L * (i0 + tx));
+    const int e_p = (ty + h) * tw + tx + h;
+    const uint2 m_p = s_meta[e_p];
+    if (!(m_p.y & DN_FIN)) { out[o] = s_work[e_p]; return; }
+    const DnTap p = denoise_make_tap(s_work[e_p], s_guide[e_p], m_p);
+    float c[3], var;
+    denoise_pixel_pass(pass, p, [&](int dx, int dy, DnTap* q) {
+        const int e = e_p + dy * u * tw + dx * u;
+        const uint2 m_q = s_meta[e];
+        q->id = m_q.x; q->flags = m_q.y;
+        if (!denoise_tap_taken(p, *q)) return false; // (DN_ABSENT: no pixel there)
+        *q = denoise_make_tap(s_work[e], s_guide[e], m_q);
+        return true;
+    }, c, &var);
+    out[o] = make_float4(c[0], c[1], c[2], var);
+}
+
+// 7d: finish.  out = the record with the filtered colour, remodulated (a pixel whose colour is not finite keeps its bits: the working
+// colour was never touched, but it is the INPUT's bits that are written); depth, normal and id are the input's bits; variance_out
+// (or NULL) gets the last variance.  out may be `records` itself: a lane reads and writes its own pixel only.
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_finish(const float4* records, const float* __restrict__ albedo, const float4* __restrict__ work,
+                                                             const uint2* __restrict__ meta, uint32_t width, uint32_t height, float4* out,
+                                                             float* __restrict__ variance_out) {
+    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
+    if (x >= (int)width || y >= (int)height) return;
+    const unsigned long long o = (unsigned long long)y * width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1], w = work[o];
+    float c[3] = {r0.x, r0.y, r0.z};
+    if (meta[o].y & DN_FIN) {
+        c[0] = w.x; c[1] = w.y; c[2] = w.z;
+        if (albedo)
+            for (int k = 0; k < 3; k++) c[k] = denoise_remodulate(c[k], albedo[3ull * o + k]);
+    }
+    out[2ull * o] = make_float4(c[0], c[1], c[2], r0.w);
+    out[2ull * o + 1] = r1;
+    if (variance_out) variance_out[o] = w.w;
 }
 
 // ---------------------------------------------------------------------------

@@ -30,6 +30,17 @@ STRUCTURAL_STEPS = ("add_textures", "add_meshes", "set_items", "update_lights")
 RECREATE = "recreate"
 
 
+def _pack_records(fields: dict) -> np.ndarray:
+    """The dict of render_pixels (color (..., 3), depth (...), normal (..., 3), object_id (...) uint32) as (..., 8) float32 rr_radiance records."""
+    color = np.asarray(fields["color"], np.float32)
+    rec = np.zeros(color.shape[:-1] + (8,), np.float32)
+    rec[..., 0:3] = color
+    rec[..., 3] = fields["depth"]
+    rec[..., 4:7] = fields["normal"]
+    rec[..., 7] = np.asarray(fields["object_id"], np.uint32).view(np.float32)
+    return rec
+
+
 def _bits(a, dtype=np.float32) -> bytes:
     return np.ascontiguousarray(np.asarray(a, dtype)).tobytes()
 
@@ -163,6 +174,29 @@ class Raytracing:
         """render_pixels, and per pixel the means over its n_parts interleaved sample subsets (rr_render_pixel_parts): the dict of
         render_pixels plus parts = dict(color (n, K, 3), depth (n, K), normal (n, K, 3), object_id (n, K))."""
         return self.device_scene.render_pixel_parts(self.camera.c_struct(), self.config, pixels=pixels, n_parts=n_parts, sample_xy=sample_xy)
+
+    def denoise(self, records, halves=None, albedo=None, params=None, rgba8: bool = False) -> dict:
+        """rr_denoise_records over a frame of this camera: `records` (n, 8) float32 rr_radiance records in row-major order (what
+        render_pixels gives, as records), `halves` (n, 2, 8) or None (render_pixel_parts at n_parts = 2), `albedo` (n, 3) or None, `params`
+        a denoise.DenoiseParams or None for the defaults.  Returns dict(records (n, 8), variance (n,), color, depth, normal, object_id:
+        copies of the filtered records' fields [, rgba: the frame's bytes of the filtered records]).  The result is, bit for bit,
+        denoise.atrous_denoise of the same arrays."""
+        cam = self.camera.c_struct()
+        res = self.device_scene.denoise_records(int(cam.width), int(cam.height), records, halves, albedo, params, rgba8=rgba8)
+        return dict(res, **capi._records(res["records"]))
+
+    def render_denoised(self, samples: Optional[int] = None, params=None, sample_xy=None, rgba8: bool = False) -> dict:
+        """The whole frame at `samples` (default: the config's; even) in two halves, followed by the filter guided by their variance: one
+        rr_render_pixel_parts call at n_parts = 2 and one rr_denoise_records call.  Returns the dict of denoise() plus `noisy`, the
+        records before the filter.  render_denoised_torch is the same on the device, with no host trip."""
+        cam = self.camera.c_struct()
+        cfg = rr_config.from_buffer_copy(self.config)
+        if samples is not None:
+            cfg.samples = samples
+        base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=sample_xy)
+        records = _pack_records(base)
+        halves = _pack_records(base["parts"])
+        return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -850,3 +884,45 @@ def render_adaptive_prefix_torch(device_scene: capi.DeviceScene, cam, cfg: rr_co
     render_adaptive_levels_torch returns."""
     return _fused_torch(device_scene, cam, rgba8, samples, error, "level_pixels", lambda out, rgba, smp, err, stream: device_scene.render_adaptive_prefix_device(
         cam, cfg, prefix_samples, threshold, out, rgba, smp, err, stream, sample_xy=sample_xy))
+
+
+# ---------------------------------------------------------------------------
+# the a-trous filter on torch tensors: records rendered on the GPU are filtered where they are, on torch's current stream
+# ---------------------------------------------------------------------------
+def denoise_torch(device_scene: capi.DeviceScene, width: int, height: int, records, halves=None, albedo=None, params=None, rgba8: bool = False,
+                  variance: bool = True, in_place: bool = False) -> dict:
+    """rr_denoise_records_device on torch's current stream of the scene's device: `records` (n, 8), `halves` (n, 2, 8) or None and `albedo`
+    (n, 3) or None are contiguous float32 CUDA tensors on that device, n = width * height (anything else raises).  Returns torch tensors,
+    without a host copy and without a synchronisation: dict(records (n, 8) float32 and its views color, depth, normal, object_id; on
+    request variance (n,) float32 and rgba (n, 4) uint8).  in_place: the filtered records are written over `records`."""
+    import torch
+    n = int(width) * int(height)
+    rec = _ray_tensor(device_scene, records, "records", shape_tail=(8,))
+    hv = _ray_tensor(device_scene, halves, "halves", shape_tail=(2, 8)) if halves is not None else None
+    al = _ray_tensor(device_scene, albedo, "albedo", shape_tail=(3,)) if albedo is not None else None
+    for t, name in ((rec, "records"), (hv, "halves"), (al, "albedo")):
+        if t is not None and int(t.shape[0]) != n:
+            raise ValueError(f"{name}: {int(t.shape[0])} entries for a frame of {width}x{height}")
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        out = rec if in_place else torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        var = torch.empty((n,), dtype=torch.float32, device=dev) if variance else None
+        device_scene.denoise_records_device(width, height, rec.data_ptr(), hv.data_ptr() if hv is not None else None, al.data_ptr() if al is not None else None,
+                                            out.data_ptr(), rgba.data_ptr() if rgba8 else None, var.data_ptr() if variance else None, params,
+                                            torch.cuda.current_stream(dev).cuda_stream)
+    res = _record_views(out)
+    if variance:
+        res["variance"] = var
+    if rgba8:
+        res["rgba"] = rgba
+    return res
+
+
+def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, params=None, sample_xy=None, rgba8: bool = False) -> dict:
+    """Raytracing.render_denoised on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples even) and
+    rr_denoise_records_device on the same stream, the second reading what the first wrote without a synchronisation.  Returns the dict of
+    denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the tensors the filter read."""
+    base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
+    res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], None, params, rgba8=rgba8)
+    return dict(res, noisy=base["records"], halves=base["part_records"])

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""Developer probe: what rr_denoise_records_device costs, launch by launch, and which form of the pass kernel each step should run in.
+
+One frame (spheres_room, 1280 x 720, 8 samples in two halves by default) is rendered on one handle, on the device, and stays there;
+the filter then runs on it with halves, 5 iterations, in one process.  Every figure is device time between two HIP events around CALLS
+back-to-back calls on one stream, divided by CALLS; the arms ALTERNATE round by round (a drift of the clocks or of the machine's load
+meets all of them alike), WARMUP rounds and then the median of ROUNDS timed rounds with their range.
+
+  whole call        5 iterations, every pass in its shipped form
+  k iterations      k = 1 .. 5, shipped forms: T(k) - T(k - 1) is pass k - 1 (step 2^(k-1)); T(1) is prepare + pass 0 + finish + bytes
+  pass i as form f  iterations = i + 1 with pass i forced to gather / tile / lattice (the passes before it shipped): minus T(i) it is
+                    that pass in that form -- the A/B of the forms, per step
+next to two yardsticks: the compulsory traffic of a pass (working colour, guide and flags read once: 16 + 16 + 8 B, 16 B written per
+pixel) at the HBM rate the machine reaches with a float4 copy (6.29 TB/s), and the device time of the frame being filtered (the two
+halves at 8 samples per pixel) on the same handle.
+
+With --sweep (no GPU): the four defaults on the CPU quality frame of tests/denoise_cases.py through the numpy yardstick -- RMSE against
+the truth for a grid around rr_denoise_default_params.
+
+usage: denoise_time.py [scene [width height samples]] [--out FILE] [--sweep]"""
+import itertools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WARMUP, ROUNDS, CALLS = 2, 9, 20
+HBM_BYTES_PER_S = 6.29e12        # float4 copy, measured
+PASS_BYTES_PER_PIXEL = 16 + 16 + 8 + 16
+FORM_NAMES = {1: "gather", 2: "tile", 3: "lattice"}
+
+
+def _median(runs):
+    runs = sorted(runs)
+    return runs[len(runs) // 2], runs[0], runs[-1]
+
+
+def sweep(emit):
+    from rustray_amd.denoise import DenoiseParams, atrous_denoise
+    from tests.denoise_cases import quality_frame
+    truth, records, halves = quality_frame()
+    rmse = lambda rec: float(np.sqrt(np.mean((rec[:, 0:3].astype(np.float64) - truth) ** 2)))
+    emit(f"sweep of the defaults, 64x48 quality frame (halves = truth + N(0, 0.1)): raw RMSE {rmse(records):.4f}")
+    rows = []
+    for it, power, sd, sl in itertools.product((3, 4, 5, 6), (3, 5, 7), (0.02, 0.05, 0.2), (1.0, 2.0, 4.0, 8.0)):
+        prm = DenoiseParams(iterations=it, normal_power_log2=power, sigma_depth=sd, sigma_luminance=sl)
+        rows.append((rmse(atrous_denoise(records, halves, None, 64, 48, prm)["records"]), it, power, sd, sl))
+    rows.sort()
+    default = [r for r in rows if r[1:] == (5, 5, 0.05, 4.0)][0]
+    emit(f"  defaults (5 iterations, power 5, sigma_depth 0.05, sigma_luminance 4): RMSE {default[0]:.4f}, rank {rows.index(default) + 1} of {len(rows)}")
+    for r in rows[:8]:
+        emit(f"  RMSE {r[0]:.4f}  iterations {r[1]}  power {r[2]}  sigma_depth {r[3]}  sigma_luminance {r[4]}")
+    emit(f"  worst: RMSE {rows[-1][0]:.4f}  iterations {rows[-1][1]}  power {rows[-1][2]}  sigma_depth {rows[-1][3]}  sigma_luminance {rows[-1][4]}")
+
+
+def main(argv):
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    out_path = None
+    if "--out" in argv:
+        i = argv.index("--out")
+        out_path = argv[i + 1]
+        del argv[i:i + 2]
+    if "--sweep" in argv:
+        sweep(emit)
+    else:
+        measure(argv, emit)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "a") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+def measure(argv, emit):
+    import torch
+    from rustray_amd import capi, renderer
+    from rustray_amd.denoise import DenoiseParams
+    from rustray_amd.flat import make_config
+    from tests.helpers import camera_for, load_scene
+    scene = argv[1] if len(argv) > 1 else "spheres_room"
+    w, h, samples = (int(argv[2]), int(argv[3]), int(argv[4])) if len(argv) > 4 else (1280, 720, 8)
+    if capi.device_count() < 1:
+        raise SystemExit("denoise_time.py needs a GPU: no HIP device visible")
+    fs = load_scene(scene)
+    cam = camera_for(fs, w, h).c_struct()
+    cfg = make_config(samples=samples, monte_carlo=True, seed=1, max_recursion=4)
+    n = w * h
+    with capi.DeviceScene(fs, 0) as ds:
+        def timed(fn, calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b) / calls
+
+        frame = renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2)
+        torch.cuda.synchronize()
+        rec, halves = frame["records"], frame["part_records"]
+        out = torch.empty_like(rec)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def call(iterations, forms=None):
+            prm = capi.denoise_params(DenoiseParams(iterations=iterations))
+
+            def run():
+                capi.denoise_forms(forms)
+                ds.denoise_records_device(w, h, rec.data_ptr(), halves.data_ptr(), None, out.data_ptr(), rgba.data_ptr(), None, prm, stream)
+            return run
+
+        arms = {("auto", k): call(k) for k in range(1, 6)}
+        for i in range(5):
+            for f in (1, 2, 3):
+                if (f == 2 and 2 * (1 << i) > 8) or (f == 3 and i == 0):
+                    continue
+                arms[("pass", i, f)] = call(i + 1, [0] * i + [f])
+        runs = {k: [] for k in arms}
+        frame_runs = []
+        try:
+            for r in range(WARMUP + ROUNDS):
+                for k, fn in arms.items():
+                    t = timed(fn, CALLS)
+                    if r >= WARMUP:
+                        runs[k].append(t)
+                t = timed(lambda: renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2), 1)
+                if r >= WARMUP:
+                    frame_runs.append(t)
+        finally:
+            capi.denoise_forms(None)
+        torch.cuda.synchronize()
+
+    med = {k: _median(v) for k, v in runs.items()}
+    floor_ms = n * PASS_BYTES_PER_PIXEL / HBM_BYTES_PER_S * 1e3
+    emit(f"rr_denoise_records_device, {scene} {w}x{h}, {samples} samples in two halves, with halves, rgba8_out; device ms per call, median of {ROUNDS} rounds of {CALLS} calls [min .. max]")
+    emit(f"  the frame being filtered (rr_render_pixel_parts_device, n_parts = 2): {_median(frame_runs)[0]:.3f} ms [{_median(frame_runs)[1]:.3f} .. {_median(frame_runs)[2]:.3f}]")
+    emit(f"  compulsory traffic of one pass: {PASS_BYTES_PER_PIXEL} B per pixel = {n * PASS_BYTES_PER_PIXEL / 1e6:.1f} MB, {floor_ms * 1e3:.1f} us at {HBM_BYTES_PER_S / 1e12:.2f} TB/s")
+    m, lo, hi = med[("auto", 5)]
+    emit(f"  whole call, 5 iterations, shipped forms: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
+    m1 = med[("auto", 1)][0]
+    emit(f"  1 iteration (prepare + pass 0 + finish + bytes): {m1:.4f} ms")
+    for k in range(2, 6):
+        d = med[("auto", k)][0] - med[("auto", k - 1)][0]
+        emit(f"  pass {k - 1} (step {1 << (k - 1)}), shipped form, T({k}) - T({k - 1}): {d * 1e3:.1f} us = {floor_ms / d:.2f} of the traffic floor's rate")
+    emit("  the forms per pass (pass 0: the whole 1-iteration call; later passes: minus the shipped call of the passes before):")
+    for i in range(5):
+        base = med[("auto", i)][0] if i else 0.0
+        row = []
+        for f in (1, 2, 3):
+            if ("pass", i, f) in med:
+                m, lo, hi = med[("pass", i, f)]
+                row.append(f"{FORM_NAMES[f]} {(m - base) * 1e3:.1f} us [{(lo - base) * 1e3:.1f} .. {(hi - base) * 1e3:.1f}]")
+        emit(f"    pass {i} (step {1 << i}): " + ", ".join(row))
+
+
+if __name__ == "__main__":
+    main(list(sys.argv))
