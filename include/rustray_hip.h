@@ -948,8 +948,26 @@ int rr_render_adaptive_prefix_device(rr_scene* scene, const rr_camera* camera, c
  *     3. With halves: t = |lum(c_p) - lum(c_q)| / (sigma_luminance * sqrtf(var_p) + EPS), w = w / (1.0f + t*t); c and var are the
  *        pass's input.
  *     4. sum_c[k] += w * c_q[k]; sum_v += (w*w) * var_q; sum_w += w.
- *   Then c'_p = sum_c / sum_w and var'_p = sum_v / (sum_w * sum_w).  A pixel with !fin_p keeps its colour bits and var 0 through every
- *   pass and is never a tap.
+ *   Then, if 0 < sum_w <= FLT_MAX: c'_p = sum_c / sum_w and var'_p = sum_v / (sum_w * sum_w).  Otherwise (sum_w is 0, inf or NaN: a
+ *   weightless pixel) c'_p = c_p and var'_p = var_p: the pixel keeps the colour and variance of the pass's input for this pass.  A
+ *   pixel with !fin_p keeps its colour bits and var 0 through every pass and is never a tap.
+ *   Normals are expected to be of unit length or non-finite, as the records of this library are.  Any finite normal is accepted: a
+ *   zero normal, or a short one at a high power (length 0.5 at normal_power_log2 7: 0.25^128 underflows), makes the centre tap's own cs
+ *   and with it sum_w 0, a huge one makes a dot product overflow and sum_w inf or NaN; such a pixel is weightless in that pass, keeps
+ *   its colour by the rule above and remains a tap of its neighbours with that finite colour.
+ *   Finite working colours stay finite through the passes: a pass forms a weighted mean with weights of one sign, which cannot
+ *   overflow.  What a finite input can still produce that is not finite:
+ *     - a +inf variance, where a squared luminance difference (colours above 2^64 or so) overflows;
+ *     - an inf colour at the finish, where the remodulation c * a_k by an albedo above 1 overflows;
+ *     - an inf working colour at the start, where the demodulation c_k / a_k of a colour above 2^117 by an albedo below 1 overflows:
+ *       fin is judged on the input, so that inf is a tap of its id region and makes infs and NaNs there; where both halves overflow
+ *       as well, the seed (lum(A) - lum(B)) is inf - inf = NaN and still a tap of the prefilter, a NaN variance for the 3x3 pixels
+ *       around it.  All of it follows from the text above and is the same on every implementation, but keep c_k / a_k finite;
+ *     - a NaN variance: (w*w) * var_q is 0 * inf where a weight's square underflows at a tap whose variance is +inf, and
+ *       sum_v / (sum_w * sum_w) is 0 / 0 where sum_w * sum_w underflows (normals of length 0.5 at normal_power_log2 6).  A pixel whose
+ *       variance is NaN has NaN weights with halves, is weightless and keeps its colour: the colours stay finite.
+ *   NaNs that the arithmetic generates, as opposed to the NaNs of the input that pass through with their bits, have unspecified sign
+ *   and payload: only "is a NaN" is the same on every implementation.
  *   Finish.  The colour is remodulated.  out[p].color is the result, for !fin_p the input's bits; out[p].depth, normal and object_id
  *   are the input's bits.  rgba8_out (or NULL): the bytes rr_render_pixels writes for the record out[p], with params->gamma_correction
  *   as rr_config's.  variance_out (or NULL): the last var.

@@ -125,8 +125,11 @@ RR_SETUP_HD void denoise_pixel_pass(const DnPass& pass, const DnTap& p, Fetch fe
             sum_v += (w * w) * q.var;
             sum_w += w;
         }
-    for (int k = 0; k < 3; k++) out_c[k] = sum_c[k] / sum_w;
-    *out_var = sum_v / (sum_w * sum_w);
+    // a weightless pixel keeps its colour and variance for this pass: sum_w is 0 when the centre's own cs is (a zero normal, a short one
+    // at a high power), inf or NaN when a dot product of huge normals overflows; false for NaN
+    const bool ok = sum_w > 0.0f && sum_w <= DN_FLT_MAX;
+    for (int k = 0; k < 3; k++) out_c[k] = ok ? sum_c[k] / sum_w : p.c[k];
+    *out_var = ok ? sum_v / (sum_w * sum_w) : p.var;
 }
 
 // ---- where the passes run (host only): the three forms a pass kernel has, and what a forced choice comes to at a step

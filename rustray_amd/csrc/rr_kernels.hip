@@ -1659,7 +1659,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_post_process(uint32_t width, uint3
 // A lane whose pixel lies outside the frame does nothing after the last barrier of its kernel.
 //
 // 7a: prepare.  Per pixel: the flags, the guide, the (demodulated) colour, and with halves the variance: the seeds of the tile and a
-// halo of one pixel go through LDS (34 x 10 floats; a seed is >= 0, -1 marks "no tap": outside the frame or colour not finite), then the
+// halo of one pixel go through LDS (34 x 10 floats; a seed is >= 0 or NaN, -1 marks "no tap": outside the frame or colour not finite), then the
 // 3x3 prefilter.  halves: the K = 2 layout (part h of pixel o: two float4 at 4 o + 2 h); albedo: 3 floats per pixel; either may be NULL.
 RR_DEV uint32_t denoise_record_flags(const float4 r0, const float4 r1) {
     const float c[3] = {r0.x, r0.y, r0.z}, n[3] = {r1.x, r1.y, r1.z};
@@ -1701,7 +1701,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_denoise_prepare(const float4* __re
         if (halves)
             var = denoise_prefilter([&](int dx, int dy, float* v) {
                 *v = s_v[(ty + 1 + dy) * (DN_TILE_W + 2) + tx + 1 + dx];
-                return *v >= 0.0f;
+                return !(*v < 0.0f); // (a seed may be NaN -- halves that both overflow at demodulation -- and is a tap all the same)
             });
     }
     work[o] = make_float4(c[0], c[1], c[2], var);

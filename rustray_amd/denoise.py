@@ -63,6 +63,12 @@ def _window(n, d):
     return slice(lo, hi), slice(lo + d, hi + d)
 
 
+def _pass_ok(fin, sum_w):
+    """Where a pass divides: fin_p and sum_w in (0, FLT_MAX].  A weightless pixel (sum_w 0, inf or NaN: a zero or short normal, a dot
+    product that overflows) keeps its colour and variance of the pass's input for this pass."""
+    return fin & (sum_w > 0) & (sum_w <= FLT_MAX)
+
+
 def atrous_denoise(records, halves, albedo, width: int, height: int, params: DenoiseParams | None = None) -> dict:
     """records: (width * height, 8) float32 rr_radiance records in row-major order (column 7 holds the object id's bits); halves:
     (width * height, 2, 8) in the layout of render_pixel_parts at n_parts = 2, or None; albedo: (width * height, 3) or None.
@@ -137,8 +143,9 @@ def atrous_denoise(records, halves, albedo, width: int, height: int, params: Den
                     np.add(sum_v[P], (w * w) * var[Q], out=sum_v[P], where=taken)
                     np.add(sum_w[P], w, out=sum_w[P], where=taken)
             c_next, var_next = c.copy(), var.copy()
-            np.divide(sum_c, sum_w[..., None], out=c_next, where=fin[..., None])
-            np.divide(sum_v, sum_w * sum_w, out=var_next, where=fin)
+            ok = _pass_ok(fin, sum_w)
+            np.divide(sum_c, sum_w[..., None], out=c_next, where=ok[..., None])
+            np.divide(sum_v, sum_w * sum_w, out=var_next, where=ok)
             c, var = c_next, var_next
 
         # ---- finish

@@ -13,7 +13,7 @@ import pytest
 
 from rustray_amd import denoise
 from rustray_amd.denoise import DenoiseParams, atrous_denoise
-from tests.denoise_cases import F, random_frame
+from tests.denoise_cases import F, differing_words, random_frame
 from tests.helpers import camera_for
 from tests.test_gpu_pixel_parts import SENTINEL, _cfg
 from tests.test_gpu_shade_rays import _scene
@@ -40,12 +40,13 @@ def small_scene(hip):
         yield ds
 
 
-def _device_call(ds, W, H, use_halves, use_albedo, prm, in_place=False, rgba8=True, variance=True, stream=None, produce=False):
-    """One rr_denoise_records_device call on random_frame(W, H) with sentinels behind every output -> (records, variance, rgba) as numpy
-    words.  produce: the inputs are made by copy kernels on `stream` and the call follows them without a synchronisation."""
+def _device_call(ds, W, H, use_halves, use_albedo, prm, in_place=False, rgba8=True, variance=True, stream=None, produce=False, frame=None):
+    """One rr_denoise_records_device call on random_frame(W, H), or on `frame` = (records, halves, albedo) of that size, with sentinels
+    behind every output -> (records, variance, rgba) as numpy words.  produce: the inputs are made by copy kernels on `stream` and the
+    call follows them without a synchronisation."""
     import torch
     n = W * H
-    records, halves, albedo = random_frame(W, H)
+    records, halves, albedo = frame if frame is not None else random_frame(W, H)
     ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(0)
     with ctx:
         src = [torch.from_numpy(a.copy()).cuda() for a in (records, halves, albedo)]
@@ -84,9 +85,23 @@ def _device_call(ds, W, H, use_halves, use_albedo, prm, in_place=False, rgba8=Tr
     return o[:n], v[:n], r[:n].view(np.uint8).reshape(n, 4)
 
 
-def _check(got, want, what, rgba8=True, variance=True):
+def _check(got, want, what, rgba8=True, variance=True, nan_equal=False):
+    """nan_equal: a word that is a NaN on both sides counts as equal whatever its other bits (a NaN the arithmetic generated has no
+    specified sign or payload), and the bytes of a pixel with such a word are not compared.  "variance": in the variance words only,
+    the records strict."""
     rec, var, rgba = got
     w = want["records"].view(np.uint32)
+    if nan_equal:
+        d_rec, n_rec = differing_words(rec, w)
+        d_var, n_var = differing_words(var, want["variance"]) if variance else (0, 0)
+        print(f"{what}: {n_rec} record and {n_var} variance words are NaNs of other bits on both sides")
+        assert d_rec == 0, f"{what}: {d_rec} of {w.size} record words differ"
+        assert d_var == 0, f"{what}: {d_var} variance words differ"
+        assert n_rec == 0 or nan_equal != "variance", f"{what}: {n_rec} record words are NaNs of other bits"
+        if rgba8:
+            same = (rec == w).all(1)
+            assert np.array_equal(rgba[same], want["rgba"][same]), f"{what}: {int((rgba[same] != want['rgba'][same]).sum())} bytes differ"
+        return
     assert np.array_equal(rec, w), f"{what}: {int((rec != w).sum())} of {w.size} record words differ (first pixel {int(np.argwhere((rec != w).any(1))[0][0])})"
     if variance:
         assert np.array_equal(var, want["variance"].view(np.uint32)), f"{what}: {int((var != want['variance'].view(np.uint32)).sum())} variance words differ"
