@@ -52,7 +52,9 @@ extern "C" {
  * rr_render_pixel_prefix, rr_render_pixel_prefix_device, rr_render_adaptive_prefix and rr_render_adaptive_prefix_device came after those in
  * the same way: a version-3 library may lack these four as well.
  * rr_denoise_default_params, rr_denoise_records and rr_denoise_records_device (with rr_denoise_params, a struct of its own) came after
- * those, again without a change of any existing struct: a version-3 library may lack these three as well. */
+ * those, again without a change of any existing struct: a version-3 library may lack these three as well.
+ * rr_accumulate_default_params, rr_accumulate_records and rr_accumulate_records_device (with rr_accumulate_params, a struct of its own)
+ * came after those in the same way: a version-3 library may lack these three as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1009,6 +1011,92 @@ int rr_denoise_records(rr_scene* scene, uint32_t width, uint32_t height, const r
                        const rr_radiance* records /* width * height */, const rr_radiance* halves /* width * height * 2, or NULL */,
                        const float* albedo /* width * height * 3, or NULL */,
                        rr_radiance* out /* width * height */, uint8_t* rgba8_out /* or NULL */, float* variance_out /* width * height, or NULL */);
+
+/* Temporal accumulation, the step a real-time denoiser takes before its spatial filter: the previous call's result is reprojected into
+ * the current frame and the current records are blended into it, on the device.  Frame after frame of a few samples then converge
+ * where nothing moved, and a pixel whose surface was not visible before starts anew.  With halves, each half accumulates its own
+ * half-history with the same taps and weights: the two stay independent estimators, their difference remains the variance guide of
+ * the accumulated mean, and rr_denoise_records takes out / halves_out as they are.
+ * EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE, as for rr_denoise_records: no transcendentals, no contraction, division and
+ * sqrt correctly rounded (rustray_amd/temporal.py: accumulate_records follows this text in numpy and gives the same bits).
+ *   W, H = camera->width, height; n = W * H; pixel (x, y) is p = y * W + x.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;
+ *   row(M, r, v) = ((M[r]*v.x + M[4+r]*v.y) + M[8+r]*v.z) + M[12+r]*v.w for a column-major matrix; EPS = 2^-20.
+ *   Per pixel p, with fin_p and valid_p of records[p] as rr_denoise_records defines them:
+ *   1. No history: if history is NULL (the first frame), !fin_p or !valid_p (a miss has a NaN normal; a constant background has no noise
+ *      to average), or where a later step says so: out[p], halves_out[2p] and halves_out[2p + 1] are the bits of records[p], halves[2p]
+ *      and halves[2p + 1]; length_out[p] = 1 if fin_p, else 0.
+ *   2. World point.  cx = (((float)x + 0.5f) / (float)W) * 2.0f - 1.0f, cy = 1.0f - (((float)y + 0.5f) / (float)H) * 2.0f.
+ *      pp_r = row(projection_inverse, r, (cx, cy, -1, 1)), o_r = row(view_inverse, r, (pp, 1)), d_r = row(view_inverse, r, (pp, 0)), r = 0..2;
+ *      len = sqrtf(dot(d, d)); world_r = o_r + (d_r / len) * depth_p; with motion, prev_r = world_r + motion[3p + r], else prev = world.
+ *      (The ray of a frame without depth of field through the pixel's centre; its bits need not be the frame kernels'.)
+ *   3. Reprojection.  clip_r = row(prev_world_to_clip, r, (prev, 1)) for r = 0, 1, 3.  No history unless clip.w > EPS.
+ *      fx = ((clip.x / clip.w) * 0.5f + 0.5f) * (float)W - 0.5f;  fy = (0.5f - (clip.y / clip.w) * 0.5f) * (float)H - 0.5f.
+ *      No history if fx or fy is not finite, or unless -1 < fx < W and -1 < fy < H (no tap would lie inside the frame).
+ *      e = prev - prev_eye, dist = sqrtf(dot(e, e)), z_exp = dist - dist / clip.w: the depth the previous frame recorded for that point.
+ *      A record's depth is measured from its ray's origin, which lies on the plane one unit ahead of the eye, not from the eye; of the
+ *      distance to the eye the part before that plane is dist / clip.w, clip.w of a perspective projection (last row 0 0 -1 0 times the
+ *      view) being the distance ahead of the eye.  prev_world_to_clip must be of that kind.
+ *   4. Taps.  rx = rintf(fx), ry = rintf(fy) (ties to even).  If |fx - rx| <= snap and |fy - ry| <= snap: the one tap (rx, ry) with weight
+ *      1, so that a static camera neither blurs nor drifts.  Otherwise x0 = floorf(fx), y0 = floorf(fy), tx = fx - x0, ty = fy - y0 and
+ *      the four taps k = 0..3 in this order: (x0 + (k & 1), y0 + (k >> 1)) with weight (k & 1 ? tx : 1.0f - tx) * (k >> 1 ? ty : 1.0f - ty).
+ *   5. A tap q is taken when it lies inside the frame; history[q].object_id == object_id_p; the three floats of history[q].normal are
+ *      finite and dot(n_p, n_q) >= normal_min; the three floats of history[q].color and history[q].depth are finite and
+ *      |z_exp - depth_q| <= sigma_depth * z_exp + EPS; history_length[q] > 0; and, with halves, the six colour floats of
+ *      history_halves[2q] and [2q + 1] are finite.
+ *   6. Blend.  Starting from 0, in tap order over the taken taps: sum_w += w; sum_l += w * history_length[q]; per channel and layer
+ *      sum_c += w * c_q.  No history unless sum_w >= 2^-6.  Otherwise h = sum_c / sum_w per channel and layer, len = sum_l / sum_w,
+ *      N = len + 1.0f; if not N < max_history then N = max_history; a = 1.0f / N;  out.color = h + a * (cur - h) per channel, each half
+ *      with its own half-history; a current half whose colour is not finite keeps its bits.  length_out[p] = N.  Depth, normal and
+ *      object_id of every output record are the bits of the current record of that layer.
+ *   rgba8_out (or NULL): the bytes rr_render_pixels writes for the record out[p], with params->gamma_correction as rr_config's.
+ * rr_accumulate_params: struct_size = sizeof(rr_accumulate_params); prev_world_to_clip: the previous frame's projection x view,
+ * column-major (the host has both matrices; rr_camera holds only inverses) and prev_eye, its eye; max_history 1 .. 65536 caps the
+ * length, so the blend factor never falls below 1 / max_history; normal_min in [-1, 1]; sigma_depth finite and above 0; snap in [0, 0.5).
+ * rr_accumulate_default_params writes max_history 32, normal_min 0.9, sigma_depth 0.05, snap 1/64, no gamma, the identity matrix and
+ * an eye of 0; it never touches a device.
+ * rr_accumulate_records_device: records_dev n records, halves_dev 2n records in the K = 2 layout of rr_render_pixel_parts or NULL;
+ * history_dev n records, the previous call's out; history_halves_dev 2n records, the previous call's halves_out; history_length_dev n
+ * floats, the previous call's length_out (0: the pixel has no history); motion_dev 3n floats or NULL (nothing moved): the world-space
+ * displacement per pixel, the surface point pixel p shows now lay at world_p + motion_p in the previous frame.  history_dev == NULL
+ * together with history_length_dev == NULL (and history_halves_dev == NULL) is the first frame; one of the two without the other is
+ * RR_ERR_INVALID_ARGUMENT.  With history, history_halves_dev is required exactly when halves_dev is given; halves_out_dev is required
+ * exactly when halves_dev is given; out_dev and length_out_dev are required.
+ *   The call follows rr_denoise_records_device: every pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming the
+ *   argument); the record pointers 16-byte aligned, the others 4-byte aligned; one launch (and one for the bytes) enqueued on `hip_stream`
+ *   in stream order, not waited for; the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene; nothing of a frame's state
+ *   or statistics is touched; a scene edit or rr_scene_destroy waits for a call in flight.  The call keeps no device memory.
+ *   out_dev == records_dev and halves_out_dev == halves_dev (in place on the current frame) are allowed: those are read at p only.  Every
+ *   other overlap between an output and an input, or between two outputs, is RR_ERR_INVALID_ARGUMENT: history is gathered, so it can
+ *   never be written by the call.  Callers ping-pong two sets of buffers.
+ *   Refusals: a NULL scene, camera, params, records, out or length_out; width or height 0 or above 65535; a struct_size other than
+ *   sizeof(rr_accumulate_params); max_history, normal_min, sigma_depth or snap out of range or NaN; the pairing rules above:
+ *   RR_ERR_INVALID_ARGUMENT.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ * rr_accumulate_records: the same on HOST pointers, the device form on the null stream behind staging copies the handle keeps until
+ * rr_scene_destroy (per pixel 32 B each for records, history and out, 64 B each for halves, history_halves and halves_out, 4 B each for
+ * history_length, length_out and rgba8_out, 12 B for motion, each only where the call has it); it returns with the outputs written. */
+typedef struct rr_accumulate_params {
+    uint32_t struct_size;            /* sizeof(rr_accumulate_params) */
+    float    prev_world_to_clip[16]; /* the previous frame's projection x view, column-major */
+    float    prev_eye[3];
+    float    max_history;            /* 1 .. 65536 */
+    float    normal_min;             /* -1 .. 1 */
+    float    sigma_depth;            /* > 0, finite */
+    float    snap;                   /* 0 <= snap < 0.5, in pixels */
+    uint32_t gamma_correction;       /* rgba8_out only, as rr_config's */
+} rr_accumulate_params;
+int rr_accumulate_default_params(rr_accumulate_params* out);
+int rr_accumulate_records_device(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                                 const rr_radiance* records_dev /* n */, const rr_radiance* halves_dev /* 2n, or NULL */,
+                                 const rr_radiance* history_dev /* n, or NULL */, const rr_radiance* history_halves_dev /* 2n, or NULL */,
+                                 const float* history_length_dev /* n, or NULL */, const float* motion_dev /* 3n, or NULL */,
+                                 rr_radiance* out_dev /* n */, rr_radiance* halves_out_dev /* 2n, or NULL */, float* length_out_dev /* n */,
+                                 uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream);
+int rr_accumulate_records(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                          const rr_radiance* records /* n */, const rr_radiance* halves /* 2n, or NULL */,
+                          const rr_radiance* history /* n, or NULL */, const rr_radiance* history_halves /* 2n, or NULL */,
+                          const float* history_length /* n, or NULL */, const float* motion /* 3n, or NULL */,
+                          rr_radiance* out /* n */, rr_radiance* halves_out /* 2n, or NULL */, float* length_out /* n */,
+                          uint8_t* rgba8_out /* or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

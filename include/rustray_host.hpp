@@ -175,6 +175,17 @@ public:
         for (int i = 0; i < 16; i++) { c.projection_inverse[i] = (float)projection_inverse[i]; c.view_inverse[i] = (float)view_inverse[i]; }
         return c;
     }
+    // projection x view, column-major, and the eye: what the NEXT frame's rr_accumulate_params takes as prev_world_to_clip and prev_eye
+    // (Raytracing::accumulate).  The product is formed in double and rounded once.
+    void world_to_clip(float* m16, float* eye3) const {
+        for (int c = 0; c < 4; c++)
+            for (int r = 0; r < 4; r++) {
+                double s = 0.0;
+                for (int k = 0; k < 4; k++) s += projection[k * 4 + r] * view[c * 4 + k];
+                m16[c * 4 + r] = (float)s;
+            }
+        for (int r = 0; r < 3; r++) eye3[r] = (float)view_inverse[12 + r];
+    }
 
 private:
     static double& at(double* m, int r, int c) { return m[c * 4 + r]; }
@@ -698,6 +709,49 @@ public:
         if (records.empty()) return records;
         if (noisy) *noisy = records;
         return denoise(records.data(), halves.data(), nullptr, params, nullptr, rgba8);
+    }
+
+    // What accumulate() returns and takes back as the history of the next call: the accumulated records, halves and lengths.
+    struct History {
+        std::vector<rr_radiance> records, halves; // width * height, and twice as many in the K = 2 layout (empty: no halves)
+        std::vector<float> length;                // width * height (0: the pixel has no history)
+        bool empty() const { return records.empty(); }
+    };
+    // Temporal accumulation over a frame of this camera (rr_accumulate_records): `records` width * height records in row-major order,
+    // `halves` twice as many or nullptr; `history` what the previous call returned (nullptr or empty: the first frame; with halves it
+    // must hold halves as well); `params` carries the PREVIOUS frame's view (prev_world_to_clip, prev_eye: Camera::world_to_clip() and
+    // eye_pos of the camera that frame was rendered with) and nullptr = rr_accumulate_default_params; `motion` width * height * 3 floats
+    // or nullptr.  rgba8 (or nullptr) gets the frame's bytes of the accumulated records.  An empty History = refused or failed
+    // (rr_last_error() says why).
+    History accumulate(const rr_radiance* records, const rr_radiance* halves, const History* history, const rr_accumulate_params* params = nullptr,
+                       const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+        History out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_accumulate_params prm;
+        if (params) prm = *params;
+        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
+        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
+        const bool first = !history || history->empty();
+        const rr_camera cam = camera.c_struct();
+        out.records.resize(n);
+        out.length.assign(n, 0.0f);
+        if (halves) out.halves.resize(2 * n);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_accumulate_records(scene->handle(), &cam, &prm, records, halves, first ? nullptr : history->records.data(),
+                                  first || history->halves.empty() ? nullptr : history->halves.data(), first ? nullptr : history->length.data(), motion,
+                                  out.records.data(), halves ? out.halves.data() : nullptr, out.length.data(), rgba8 ? rgba8->data() : nullptr) != RR_OK) {
+            out = History();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_accumulate_records_device): not waited for
+    int accumulate_device(const rr_accumulate_params& params, const rr_radiance* records_dev, const rr_radiance* halves_dev, const rr_radiance* history_dev,
+                          const rr_radiance* history_halves_dev, const float* history_length_dev, const float* motion_dev, rr_radiance* out_dev,
+                          rr_radiance* halves_out_dev, float* length_out_dev, uint8_t* rgba8_out_dev, void* hip_stream) const {
+        const rr_camera cam = camera.c_struct();
+        return rr_accumulate_records_device(scene->handle(), &cam, &params, records_dev, halves_dev, history_dev, history_halves_dev, history_length_dev, motion_dev,
+                                            out_dev, halves_out_dev, length_out_dev, rgba8_out_dev, hip_stream);
     }
 
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)

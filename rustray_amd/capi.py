@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -37,6 +37,12 @@ class rr_denoise_params(C.Structure):
                 ("sigma_luminance", C.c_float), ("gamma_correction", C.c_uint32)]
 
 
+class rr_accumulate_params(C.Structure):
+    """include/rustray_hip.h: the parameters of rr_accumulate_records."""
+    _fields_ = [("struct_size", C.c_uint32), ("prev_world_to_clip", C.c_float * 16), ("prev_eye", C.c_float * 3), ("max_history", C.c_float),
+                ("normal_min", C.c_float), ("sigma_depth", C.c_float), ("snap", C.c_float), ("gamma_correction", C.c_uint32)]
+
+
 class RustrayHipError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rustray_hip error {code}: {msg}")
@@ -48,8 +54,8 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_probe.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -161,6 +167,10 @@ def lib():
                                                     C.c_void_p, C.c_void_p, C.c_void_p]
             L.rr_test_denoise_forms.argtypes = [C.c_uint32]
             L.rr_test_denoise_forms.restype = None
+        if hasattr(L, "rr_accumulate_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_accumulate_default_params.argtypes = [C.POINTER(rr_accumulate_params)]
+            L.rr_accumulate_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 10
+            L.rr_accumulate_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 11
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -230,6 +240,28 @@ def denoise_params(params=None) -> rr_denoise_params:
     if params is not None:
         p.iterations, p.normal_power_log2 = int(params.iterations), int(params.normal_power_log2)
         p.sigma_depth, p.sigma_luminance = float(params.sigma_depth), float(params.sigma_luminance)
+        p.gamma_correction = 1 if params.gamma_correction else 0
+    return p
+
+
+def accumulate_default_params() -> rr_accumulate_params:
+    """rr_accumulate_default_params: max_history 32, normal_min 0.9, sigma_depth 0.05, snap 1/64, no gamma, the identity as the previous
+    view and an eye of 0 (never touches a device)."""
+    p = rr_accumulate_params()
+    _check(lib().rr_accumulate_default_params(C.byref(p)))
+    return p
+
+
+def accumulate_params(params=None) -> rr_accumulate_params:
+    """A temporal.AccumulateParams (or None: the library's defaults) as the C struct; a C struct is passed through."""
+    if isinstance(params, rr_accumulate_params):
+        return params
+    p = accumulate_default_params()
+    if params is not None:
+        p.prev_world_to_clip[:] = np.asarray(params.prev_world_to_clip, np.float32).T.reshape(16).tolist()   # column-major
+        p.prev_eye[:] = np.asarray(params.prev_eye, np.float32).reshape(3).tolist()
+        p.max_history, p.normal_min = float(params.max_history), float(params.normal_min)
+        p.sigma_depth, p.snap = float(params.sigma_depth), float(params.snap)
         p.gamma_correction = 1 if params.gamma_correction else 0
     return p
 
@@ -735,6 +767,42 @@ class DeviceScene:
         p = denoise_params(params)
         _check(lib().rr_denoise_records_device(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(albedo_ptr),
                                                _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(variance_ptr), _ptr(stream_ptr)))
+
+    # -- temporal reprojection of a frame of records -----------------------------------
+    def accumulate_records(self, cam: rr_camera, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
+                           rgba8: bool = False, in_place: bool = False) -> dict:
+        """rr_accumulate_records: temporal.accumulate_records on the device, host arrays in and out.  records (n, 8) float32 rr_radiance
+        records of the whole frame of `cam` in row-major order; halves (n, 2, 8) or None; history (n, 8), history_halves (n, 2, 8) and
+        history_length (n,): the previous call's records, halves and length, or None on the first frame; motion (n, 3) or None; params: a
+        temporal.AccumulateParams or None.  Returns dict(records (n, 8), length (n,), halves (n, 2, 8) or None [, rgba (n, 4) uint8]);
+        in_place accumulates into copies of `records` and `halves` (out == records, halves_out == halves)."""
+        n = int(cam.width) * int(cam.height)
+        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
+        rec = np.array(records, np.float32, order="C").reshape(n, 8) if in_place else arr(records, (n, 8))
+        hv = None if halves is None else (np.array(halves, np.float32, order="C").reshape(n, 2, 8) if in_place else arr(halves, (n, 2, 8)))
+        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
+        out = rec if in_place else np.zeros((n, 8), np.float32)
+        out_h = None if hv is None else (hv if in_place else np.zeros((n, 2, 8), np.float32))
+        length = np.zeros(n, np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        p = accumulate_params(params)
+        _check(lib().rr_accumulate_records(self._h, C.byref(cam), C.byref(p), _data(rec), _data(hv), _data(hist), _data(hist_h), _data(hist_l), _data(mv),
+                                           _data(out), _data(out_h), _data(length), _data(rgba)))
+        res = dict(records=out, length=length, halves=out_h)
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def accumulate_records_device(self, cam: rr_camera, records_ptr, halves_ptr, history_ptr, history_halves_ptr, history_length_ptr, motion_ptr, out_ptr,
+                                  halves_out_ptr, length_out_ptr, rgba8_ptr=None, params=None, stream_ptr=None):
+        """rr_accumulate_records_device: width * height 32-byte records in, as history and out (16-byte aligned; out_ptr may be records_ptr
+        and halves_out_ptr halves_ptr), optionally twice as many half records each, width * height float32 of length in and out,
+        width * height * 3 float32 of motion and width * height x 4 bytes, all raw device pointers (None where the call has none);
+        enqueued on `stream_ptr`, not waited for."""
+        p = accumulate_params(params)
+        _check(lib().rr_accumulate_records_device(self._h, C.byref(cam), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
+                                                  _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr), _ptr(halves_out_ptr),
+                                                  _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

@@ -346,6 +346,39 @@ extern "C" int rh_render_denoised(void* h, float fov, const float* eye, const fl
     if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
     return 0;
 }
+// Raytracing::accumulate: records = w * h, halves = w * h * 2 or NULL, history / history_halves / history_length = the previous call's
+// out / halves_out / length_out or all NULL (the first frame), params or NULL for the defaults, motion = w * h * 3 floats or NULL; out,
+// halves_out (with halves), length_out, rgba8 or NULL; returns 0, or -1 when the call was refused.
+// rh_accumulate_records_device: Raytracing::accumulate_device on device pointers and a stream; returns its rr_status.
+extern "C" int rh_accumulate_records(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                     uint32_t w, uint32_t hgt, const rr_radiance* records, const rr_radiance* halves, const rr_radiance* history,
+                                     const rr_radiance* history_halves, const float* history_length, const rr_accumulate_params* params, const float* motion,
+                                     rr_radiance* out, rr_radiance* halves_out, float* length_out, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    const size_t n = (size_t)w * hgt;
+    Raytracing::History hist;
+    if (history) {
+        hist.records.assign(history, history + n);
+        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
+        if (history_length) hist.length.assign(history_length, history_length + n);
+    }
+    std::vector<uint8_t> bytes;
+    const Raytracing::History r = rt.accumulate(records, halves, history ? &hist : nullptr, params, motion, rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
+    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
+    std::memcpy(length_out, r.length.data(), n * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
+extern "C" int rh_accumulate_records_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                            uint32_t w, uint32_t hgt, const rr_accumulate_params* params, const rr_radiance* records_dev, const rr_radiance* halves_dev,
+                                            const rr_radiance* history_dev, const rr_radiance* history_halves_dev, const float* history_length_dev,
+                                            const float* motion_dev, rr_radiance* out_dev, rr_radiance* halves_out_dev, float* length_out_dev, uint8_t* rgba8_dev,
+                                            void* stream) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).accumulate_device(*params, records_dev, halves_dev, history_dev, history_halves_dev, history_length_dev,
+                                                                                     motion_dev, out_dev, halves_out_dev, length_out_dev, rgba8_dev, stream);
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -1,5 +1,5 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
-// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, MultiState, FrameTiming
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, TemporalState, MultiState, FrameTiming
 //         and rr_scene, which holds one of each; HC_* (the words of FrameState::h_count); check_intact.
 // Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
@@ -139,6 +139,13 @@ struct DenoiseState {
     DevBuf work[2], guide, meta, stage[6];
 };
 
+// ---- rr_accumulate_records (rr_api_temporal.h): the call itself keeps nothing.  stage: the host form's copies of records, halves, history,
+// history_halves, history_length, motion, out, halves_out, length_out and rgba8_out (32 + 64 + 32 + 64 + 4 + 12 + 32 + 64 + 4 + 4 B per
+// pixel, each only where the call has it), grown on demand, never shrunk.  Written by rr_api_temporal.h.
+struct TemporalState {
+    DevBuf stage[10];
+};
+
 // ---- rr_render_multi (rr_api_multi.h)
 struct MultiState {
     DevBuf part[4], cat[4]; // this device's compact buffers; on device slot 0 the concatenation of all
@@ -192,6 +199,7 @@ struct rr_scene {
     QueryState query;
     AdaptiveState adaptive;
     DenoiseState denoise;
+    TemporalState temporal;
     MultiState multi;
     FrameTiming timing;
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's

@@ -24,6 +24,7 @@
 #include "rr_primary_setup.h"
 #include "rr_adaptive.h" // half_error and the 8x8-block order of a refinement list (kernels 5l .. 5p)
 #include "rr_denoise.h"  // the arithmetic of the a-trous filter (kernels 7a .. 7d)
+#include "rr_temporal.h" // the arithmetic of the temporal reprojection (kernel 7e)
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -1813,6 +1814,66 @@ __global__ __launch_bounds__(RR_BLOCK) void k_denoise_finish(const float4* recor
     out[2ull * o] = make_float4(c[0], c[1], c[2], r0.w);
     out[2ull * o + 1] = r1;
     if (variance_out) variance_out[o] = w.w;
+}
+
+// 7e: temporal reprojection (rr_accumulate_records; rr_temporal.h has the arithmetic, in the order the header states;
+// rustray_amd/temporal.py is the yardstick).  One pixel per lane, 32x8 tiles as 7a .. 7d, so that the 2x2 taps of neighbouring lanes fall
+// into the same 128-byte lines; no LDS: the shifts are sub-tile and the taps hit in cache.  A record is two 16-byte loads and two 16-byte
+// stores.  Of a tap the guide row (normal, id) is read and tested first, then the colour row (colour, depth), then the length, and only then
+// the colour rows of its two half-histories.  The camera, the previous view and the scalars are the kernel argument f.  HALVES: the
+// one-layer call carries no registers for three layers.  history == NULL: the first frame, every pixel takes the no-history path.
+// out may be `records` and halves_out `halves`: a lane reads those at its own pixel only, before it writes.
+struct TpHistory {
+    const float4* __restrict__ history;
+    const float4* __restrict__ history_halves;
+    const float* __restrict__ history_length;
+    RR_DEV float length(unsigned long long q) const { return history_length[q]; }
+    RR_DEV void guide(unsigned long long q, float* n, unsigned int* id) const {
+        const float4 r1 = history[2ull * q + 1];
+        n[0] = r1.x; n[1] = r1.y; n[2] = r1.z; *id = __float_as_uint(r1.w);
+    }
+    RR_DEV void colour(unsigned long long q, float* c, float* z) const {
+        const float4 r0 = history[2ull * q];
+        c[0] = r0.x; c[1] = r0.y; c[2] = r0.z; *z = r0.w;
+    }
+    RR_DEV void half(unsigned long long q, int h, float* c) const {
+        const float4 r0 = history_halves[4ull * q + 2ull * (unsigned int)h];
+        c[0] = r0.x; c[1] = r0.y; c[2] = r0.z;
+    }
+};
+template <bool HALVES>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
+                                                                 const float4* __restrict__ history_halves, const float* __restrict__ history_length,
+                                                                 const float* __restrict__ motion, float4* out, float4* halves_out, float* __restrict__ length_out) {
+    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
+    if (x >= f.width || y >= f.height) return;
+    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    float4 a0, a1, b0, b1;
+    if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
+    const uint32_t flags = denoise_record_flags(r0, r1);
+    TpMix m;
+    bool kept = false;
+    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
+        const float n_p[3] = {r1.x, r1.y, r1.z};
+        const TpHistory hist{history, history_halves, history_length};
+        kept = temporal_history<HALVES>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr, hist, &m);
+    }
+    float4 c0 = r0;
+    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
+    out[2ull * o] = c0;
+    out[2ull * o + 1] = r1;
+    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
+    if (HALVES) {
+        // a current half whose colour is not finite keeps its bits (the pixel's own colour is finite here)
+        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
+            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
+        }
+        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
+            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
+        }
+        halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -198,6 +198,22 @@ class Raytracing:
         halves = _pack_records(base["parts"])
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
+    def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
+                        motion=None, sample_xy=None, rgba8: bool = False) -> dict:
+        """One frame of a frame-after-frame loop at `samples` (default: the config's; even) and `seed` (default: the config's): the frame
+        in two halves, blended into the history `state` carries from the previous call (rr_accumulate_records, reprojected through the
+        camera of that call), then the filter guided by the accumulated halves.  render_temporal_torch on this scene and camera: three
+        calls on one stream, no host trip; the result holds torch tensors.  Move self.camera (or the scene) between calls; give `motion`
+        (n, 3) for what moved in the world (temporal.item_motion)."""
+        from .temporal import previous_view
+        cfg = rr_config.from_buffer_copy(self.config)
+        if samples is not None:
+            cfg.samples = samples
+        if seed is not None:
+            cfg.seed = seed
+        return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
+                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera))
+
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
         base frame's error (adaptive.half_error of the two interleaved halves, one rr_render_pixel_parts call) exceeds `threshold`
@@ -926,3 +942,105 @@ def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, p
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], None, params, rgba8=rgba8)
     return dict(res, noisy=base["records"], halves=base["part_records"])
+
+
+# ---------------------------------------------------------------------------
+# temporal reprojection on torch tensors: the history lives on the device from frame to frame
+# ---------------------------------------------------------------------------
+class TemporalState:
+    """What a frame-after-frame loop carries from one rr_accumulate_records call to the next: two sets of device tensors (records (n, 8),
+    halves (n, 2, 8), length (n,)) used in turn -- the call gathers from one set and writes the other --, which of them holds the history,
+    and the view (world_to_clip, eye) the history was rendered from.  reset() forgets the history: the next frame is a first frame."""
+
+    def __init__(self):
+        self.sets = [None, None]
+        self.current = None      # index of the set that holds the history, or None
+        self.view = None
+        self.frames = 0
+
+    def reset(self):
+        self.current, self.view, self.frames = None, None, 0
+
+    def history(self):
+        return self.sets[self.current] if self.current is not None else None
+
+    def target(self, n: int, halves: bool, device) -> dict:
+        """The set the next call writes: the one that does not hold the history, (re)allocated when the frame's size changed."""
+        import torch
+        k = 0 if self.current is None else self.current ^ 1
+        t = self.sets[k]
+        if t is None or int(t["records"].shape[0]) != n or t["records"].device != device or (t["halves"] is not None) != halves:
+            t = dict(records=torch.empty((n, 8), dtype=torch.float32, device=device),
+                     halves=torch.empty((n, 2, 8), dtype=torch.float32, device=device) if halves else None,
+                     length=torch.empty((n,), dtype=torch.float32, device=device))
+            self.sets[k] = t
+        return t
+
+    def advance(self, written: dict, view):
+        self.current = next(k for k, t in enumerate(self.sets) if t is written)
+        self.view, self.frames = view, self.frames + 1
+
+
+def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
+                     rgba8: bool = False, in_place: bool = False, out: Optional[dict] = None) -> dict:
+    """rr_accumulate_records_device on torch's current stream of the scene's device: `records` (n, 8), `halves` (n, 2, 8) or None, `history`
+    (n, 8), `history_halves` (n, 2, 8) and `history_length` (n,) (all None: the first frame) and `motion` (n, 3) or None are contiguous
+    float32 CUDA tensors on that device, n = cam.width * cam.height (anything else raises); params: a temporal.AccumulateParams.  Returns
+    torch tensors, without a host copy and without a synchronisation: dict(records (n, 8) and its views, halves (n, 2, 8) or None, length
+    (n,) [, rgba (n, 4) uint8]).  in_place: written over `records` and `halves`; out: dict(records, halves, length) of tensors to write."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    tensors = dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)), history_halves=(history_halves, (2, 8)),
+                   history_length=(history_length, ()), motion=(motion, (3,)))
+    t = {}
+    for name, (value, tail) in tensors.items():
+        t[name] = _ray_tensor(device_scene, value, name, shape_tail=tail) if value is not None else None
+        if t[name] is not None and int(t[name].shape[0]) != n:
+            raise ValueError(f"{name}: {int(t[name].shape[0])} entries for a frame of {int(cam.width)}x{int(cam.height)}")
+    dev = torch.device("cuda", device_scene.device)
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    with torch.cuda.device(dev):
+        if in_place:
+            res, res_h = t["records"], t["halves"]
+        elif out is not None:
+            res, res_h = out["records"], out["halves"] if t["halves"] is not None else None
+        else:
+            res = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+            res_h = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if t["halves"] is not None else None
+        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        device_scene.accumulate_records_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["history"]), ptr(t["history_halves"]), ptr(t["history_length"]),
+                                               ptr(t["motion"]), ptr(res), ptr(res_h), ptr(length), ptr(rgba), params, torch.cuda.current_stream(dev).cuda_stream)
+    result = dict(_record_views(res), halves=res_h, length=length)
+    if rgba8:
+        result["rgba"] = rgba
+    return result
+
+
+def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
+                          sample_xy=None, rgba8: bool = False, view=None) -> dict:
+    """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
+    even), rr_accumulate_records_device against the history in `state`, rr_denoise_records_device with the accumulated halves -- three
+    calls on torch's current stream, each reading what the one before wrote without a synchronisation.  params: a
+    temporal.AccumulateParams whose scalars are used (its previous view is replaced by the state's); view: (world_to_clip, eye) of `cam`
+    for the NEXT call (default: temporal.previous_view(cam), the float64 inverse of its inverses).  Returns the dict of denoise_torch plus
+    noisy (n, 8) and halves (n, 2, 8), the frame's own records, accumulated (n, 8), accumulated_halves (n, 2, 8) and length (n,): what the
+    filter read, which `state` now holds as the history."""
+    import dataclasses
+    import torch
+    from .temporal import AccumulateParams, previous_view
+    base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
+    n = int(cam.width) * int(cam.height)
+    hist = state.history()
+    if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None):
+        state.reset()
+        hist = None
+    prm = dataclasses.replace(params) if params is not None else AccumulateParams()
+    if hist is not None:
+        prm.prev_world_to_clip, prm.prev_eye = state.view
+    target = state.target(n, True, torch.device("cuda", device_scene.device))
+    acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
+                           hist["length"] if hist else None, motion, prm, out=target)
+    res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], None, denoise_params, rgba8=rgba8)
+    state.advance(target, view if view is not None else previous_view(cam))
+    return dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"])

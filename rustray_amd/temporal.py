@@ -1,0 +1,196 @@
+"""The temporal reprojection of rr_accumulate_records in numpy float32: the yardstick the device kernel and the host loop over
+rustray_amd/csrc/rr_temporal.h are held to, bit for bit.
+
+Every step is exact in binary32 in the order include/rustray_hip.h states: float32 products and sums one at a time (numpy does not
+contract), one correctly rounded division or square root at a time, no transcendentals.  The up to four taps of a pixel are four
+whole-frame gathers here; a tap that is skipped adds nothing (np.add(..., where=taken)), so the sums are those of the per-pixel loop.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+
+F = np.float32
+EPS = F(2.0 ** -20)
+MIN_WEIGHT = F(2.0 ** -6)
+
+
+@dataclass
+class AccumulateParams:
+    """rr_accumulate_params without its struct_size; the defaults are rr_accumulate_default_params'.  prev_world_to_clip is the 4x4
+    matrix as written on paper (row r, column c), the C struct holds it column-major."""
+    prev_world_to_clip: np.ndarray = field(default_factory=lambda: np.eye(4, dtype=F))
+    prev_eye: np.ndarray = field(default_factory=lambda: np.zeros(3, F))
+    max_history: float = 32.0
+    normal_min: float = 0.9
+    sigma_depth: float = 0.05
+    snap: float = 1.0 / 64.0
+    gamma_correction: bool = False
+
+    def check(self):
+        if np.asarray(self.prev_world_to_clip).shape != (4, 4) or np.asarray(self.prev_eye).shape != (3,):
+            raise ValueError("prev_world_to_clip is 4x4, prev_eye has 3 floats")
+        if not 1.0 <= float(F(self.max_history)) <= 65536.0:
+            raise ValueError(f"max_history {self.max_history} (1 .. 65536)")
+        if not -1.0 <= float(F(self.normal_min)) <= 1.0:
+            raise ValueError(f"normal_min {self.normal_min} (-1 .. 1)")
+        if not (float(F(self.sigma_depth)) > 0.0 and np.isfinite(F(self.sigma_depth))):
+            raise ValueError("sigma_depth must be finite and above 0")
+        if not 0.0 <= float(F(self.snap)) < 0.5:
+            raise ValueError(f"snap {self.snap} (0 <= snap < 0.5)")
+
+
+def previous_view(camera):
+    """(world_to_clip (4, 4) float32, eye (3,) float32) of a camera.Camera: what the NEXT frame's AccumulateParams take as
+    prev_world_to_clip and prev_eye.  The product is formed in float64 and rounded once.  An rr_camera, which holds only the
+    inverses, is inverted in float64."""
+    if hasattr(camera, "projection"):
+        m = np.asarray(camera.projection, np.float64) @ np.asarray(camera.view, np.float64)
+        return m.astype(F), np.asarray(camera.view_inverse, np.float64)[:3, 3].astype(F)
+    pi = np.array(camera.projection_inverse[:], np.float64).reshape(4, 4).T
+    vi = np.array(camera.view_inverse[:], np.float64).reshape(4, 4).T
+    return (np.linalg.inv(pi) @ np.linalg.inv(vi)).astype(F), vi[:3, 3].astype(F)
+
+
+def _camera_matrices(cam):
+    """The two inverses of a camera.Camera or an rr_camera, column-major float32 (16,), and (width, height)."""
+    if hasattr(cam, "c_struct"):
+        cam = cam.c_struct()
+    return np.array(cam.projection_inverse[:], F), np.array(cam.view_inverse[:], F), int(cam.width), int(cam.height)
+
+
+def _row(m, r, x, y, z, w):
+    return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def world_positions(records, cam) -> np.ndarray:
+    """(n, 3) float32: world_p = o + d * depth_p of every record of a whole frame of `cam`, o and d the pinhole ray through the pixel's
+    centre, in the header's arithmetic (step 2)."""
+    pi, vi, W, H = _camera_matrices(cam)
+    rec = np.ascontiguousarray(records, F).reshape(H * W, 8)
+    y, x = np.mgrid[0:H, 0:W]
+    x_f, y_f = x.reshape(-1).astype(F), y.reshape(-1).astype(F)
+    one, zero = F(1), F(0)
+    with np.errstate(all="ignore"):
+        cx = ((x_f + F(0.5)) / F(W)) * F(2) - one
+        cy = one - ((y_f + F(0.5)) / F(H)) * F(2)
+        pp = [_row(pi, r, cx, cy, F(-1), one) for r in range(3)]
+        o = [_row(vi, r, pp[0], pp[1], pp[2], one) for r in range(3)]
+        d = np.stack([_row(vi, r, pp[0], pp[1], pp[2], zero) for r in range(3)], axis=-1)
+        length = np.sqrt(_dot(d, d))
+        return np.stack([o[r] + (d[..., r] / length) * rec[:, 3] for r in range(3)], axis=-1).astype(F)
+
+
+def item_motion(world, object_id, item_ids, prev_trans, cur_trans_inv) -> np.ndarray:
+    """The `motion` of rigidly moving items: for every pixel whose object id is item_ids[i], prev_trans[i] @ cur_trans_inv[i] @ world_p
+    - world_p (the point in the item's own space, placed where the item stood one rr_scene_update_transforms step ago); 0 elsewhere.
+    world (n, 3), object_id (n,), item_ids (k,), prev_trans and cur_trans_inv (k, 4, 4) as written on paper.  float64 inside, rounded once."""
+    world = np.asarray(world, np.float64)
+    ids = np.asarray(object_id).astype(np.int64)
+    out = np.zeros((len(world), 3), F)
+    for ident, a, b in zip(np.asarray(item_ids).astype(np.int64), np.asarray(prev_trans, np.float64), np.asarray(cur_trans_inv, np.float64)):
+        at = np.flatnonzero((ids == ident) & np.isfinite(world).all(-1))
+        if len(at):
+            p = np.concatenate([world[at], np.ones((len(at), 1))], axis=1) @ (a @ b).T
+            out[at] = (p[:, :3] - world[at]).astype(F)
+    return out
+
+
+def accumulate_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None) -> dict:
+    """records (n, 8) float32 rr_radiance records of the whole frame of `cam` (a camera.Camera or an rr_camera) in row-major order;
+    halves (n, 2, 8) or None; history (n, 8), history_halves (n, 2, 8) and history_length (n,): the previous call's records, halves and
+    length, or all None on the first frame; motion (n, 3) or None.  Returns dict(records (n, 8), length (n,), halves (n, 2, 8) or None,
+    taps: dict(x, y (n, 4) int, weight (n, 4) float32, taken (n, 4) bool, reprojected (n,) bool: the pixel reached step 4) -- where each
+    pixel's history came from)."""
+    prm = params or AccumulateParams()
+    prm.check()
+    pi, vi, W, H = _camera_matrices(cam)
+    n = W * H
+    rec = np.ascontiguousarray(records, F).reshape(n, 8)
+    hv = None if halves is None else np.ascontiguousarray(halves, F).reshape(n, 2, 8)
+    if (history is None) != (history_length is None):
+        raise ValueError("history and history_length come together")
+    if history is not None and (history_halves is None) != (hv is None) or history is None and history_halves is not None:
+        raise ValueError("history_halves is required exactly when history and halves are given")
+    m = np.asarray(prm.prev_world_to_clip, F).T.reshape(16)   # column-major, as the C struct
+    eye = np.asarray(prm.prev_eye, F)
+    max_history, normal_min, sigma_depth, snap = F(prm.max_history), F(prm.normal_min), F(prm.sigma_depth), F(prm.snap)
+    one, half = F(1), F(0.5)
+
+    out = rec.copy()
+    out_h = None if hv is None else hv.copy()
+    taps = dict(x=np.zeros((n, 4), np.int64), y=np.zeros((n, 4), np.int64), weight=np.zeros((n, 4), F), taken=np.zeros((n, 4), bool),
+                reprojected=np.zeros(n, bool))
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(rec[:, 0:3]).all(-1)
+        valid = np.isfinite(rec[:, 3]) & np.isfinite(rec[:, 4:7]).all(-1)
+        length = np.where(fin, one, F(0)).astype(F)
+        if history is None:
+            return dict(records=out, length=length, halves=out_h, taps=taps)
+        hist = np.ascontiguousarray(history, F).reshape(n, 8)
+        hist_h = None if hv is None else np.ascontiguousarray(history_halves, F).reshape(n, 2, 8)
+        hist_len = np.ascontiguousarray(history_length, F).reshape(n)
+
+        prev = world_positions(rec, cam)
+        if motion is not None:
+            prev = prev + np.ascontiguousarray(motion, F).reshape(n, 3)
+        px, py, pz = prev[:, 0], prev[:, 1], prev[:, 2]
+        cx, cy, cw = _row(m, 0, px, py, pz, one), _row(m, 1, px, py, pz, one), _row(m, 3, px, py, pz, one)
+        alive = fin & valid & (cw > EPS)
+        fx = ((cx / cw) * half + half) * F(W) - half
+        fy = (half - (cy / cw) * half) * F(H) - half
+        alive &= np.isfinite(fx) & np.isfinite(fy)
+        alive &= (fx > F(-1)) & (fx < F(W)) & (fy > F(-1)) & (fy < F(H))
+        e = prev - eye
+        dist = np.sqrt(_dot(e, e))
+        z_exp = dist - dist / cw
+
+        fx, fy = np.where(alive, fx, F(0)), np.where(alive, fy, F(0))   # (so that the integer conversions below are defined)
+        rx, ry = np.rint(fx), np.rint(fy)
+        snapped = (np.abs(fx - rx) <= snap) & (np.abs(fy - ry) <= snap)
+        x0f, y0f = np.floor(fx), np.floor(fy)
+        tx, ty = np.where(snapped, F(0), fx - x0f), np.where(snapped, F(0), fy - y0f)
+        x0 = np.where(snapped, rx, x0f).astype(np.int64)
+        y0 = np.where(snapped, ry, y0f).astype(np.int64)
+        n_taps = np.where(snapped, 1, 4)
+
+        ids_p, n_p = rec[:, 7].view(np.uint32), rec[:, 4:7]
+        layers = [hist[:, 0:3]] + ([] if hv is None else [hist_h[:, 0, 0:3], hist_h[:, 1, 0:3]])
+        sum_c = [np.zeros((n, 3), F) for _ in layers]
+        sum_w, sum_l = np.zeros(n, F), np.zeros(n, F)
+        for k in range(4):
+            qx, qy = x0 + (k & 1), y0 + (k >> 1)
+            inside = (qx >= 0) & (qy >= 0) & (qx < W) & (qy < H)
+            q = np.where(inside, qy * W + qx, 0)
+            taken = alive & (k < n_taps) & inside
+            n_q = hist[q, 4:7]
+            taken &= (hist[q, 7].view(np.uint32) == ids_p) & np.isfinite(n_q).all(-1) & (_dot(n_p, n_q) >= normal_min)
+            taken &= np.isfinite(hist[q, 0:3]).all(-1) & np.isfinite(hist[q, 3]) & (np.abs(z_exp - hist[q, 3]) <= sigma_depth * z_exp + EPS)
+            taken &= hist_len[q] > 0
+            if hv is not None:
+                taken &= np.isfinite(hist_h[q, 0, 0:3]).all(-1) & np.isfinite(hist_h[q, 1, 0:3]).all(-1)
+            w = ((tx if k & 1 else one - tx) * (ty if k >> 1 else one - ty)).astype(F)
+            for s, layer in zip(sum_c, layers):
+                np.add(s, w[:, None] * layer[q], out=s, where=taken[:, None])
+            np.add(sum_l, w * hist_len[q], out=sum_l, where=taken)
+            np.add(sum_w, w, out=sum_w, where=taken)
+            taps["x"][:, k], taps["y"][:, k], taps["weight"][:, k], taps["taken"][:, k] = qx, qy, w, taken
+        kept = alive & (sum_w >= MIN_WEIGHT)
+        taps["taken"] &= kept[:, None]
+        taps["reprojected"] = alive
+        n1 = sum_l / sum_w + one
+        N = np.where(n1 < max_history, n1, max_history).astype(F)
+        a = one / N
+        currents = [rec[:, 0:3]] + ([] if hv is None else [hv[:, 0, 0:3], hv[:, 1, 0:3]])
+        targets = [out[:, 0:3]] + ([] if hv is None else [out_h[:, 0, 0:3], out_h[:, 1, 0:3]])
+        for s, cur, dst in zip(sum_c, currents, targets):
+            h = s / sum_w[:, None]
+            blended = h + a[:, None] * (cur - h)
+            dst[...] = np.where((kept & np.isfinite(cur).all(-1))[:, None], blended, cur)
+        length = np.where(kept, N, length).astype(F)
+    return dict(records=out, length=length, halves=out_h, taps=taps)
