@@ -78,7 +78,7 @@ enum : uint32_t {
                                     // from its surface), a mesh with a zero-area triangle (area weights 0/0).  k_shade, want_shadow.
 };
 
-// 208 B instance record.  Rows of the column-major matrices, so that
+// 176 B instance record.  Rows of the column-major matrices, so that
 // row4(inv0, x, y, z, w) is exactly nalgebra's (M * v).x.
 struct DItem {
     float4 inv0, inv1, inv2, inv3; // trans_inv rows (inv3 = w row)

@@ -3,7 +3,7 @@
 // them (ShapeBasics::get_inverse_ray, src/shape/mod.rs:755-761).  These decide every hit; all layers above only choose
 // which of them to run.
 //
-// Offers: LRay, inverse_ray, to_local_point, to_world_normal, aabb_cast, ray_triangle, ray_ball.  No macros.
+// Offers: LRay, ItemRec, item_rec_uniform, inverse_ray, to_local_point, to_world_normal, aabb_cast, ray_triangle, ray_ball.  No macros.
 // Needs: rr_device.h (DItem), rr_math.h.
 #pragma once
 #include "rr_device.h"
@@ -14,8 +14,48 @@
 // ---------------------------------------------------------------------------
 struct LRay { f3 o, d; };
 
-// ShapeBasics::get_inverse_ray, reference src/shape/mod.rs:755-761
-RR_DEV LRay inverse_ray(const DItem& it, f3 o, f3 d, bool general_w) {
+// What a walk needs from an item, in registers (the way MatR is for materials, rr_surface.h): the inverse rows, the local box
+// with the radius and the flags in its w lanes, and the 16-byte group that names the mesh's tree.  Fields read through a
+// `const DItem&` are fetched where they are used, behind the early exits of the box test: one dependent round trip per group,
+// eight or nine per candidate.  The field names are DItem's, so the tests below take either: the per-ray walks, whose item
+// differs from lane to lane, keep reading DItem where they use it (the same groups loaded together per lane cost the deeper
+// levels' kernels scratch and did not pay on the contract frame: profiles/r13_dropped.txt).
+struct ItemRec {
+    float4 inv0, inv1, inv2, inv3; // (inv3 is loaded under general_w only, and read under it only)
+    float bmin[3]; float radius;
+    float bmax[3]; uint32_t flags;
+    uint32_t tri_base, n_tris, node_base4; int32_t root4;
+};
+static_assert(offsetof(DItem, inv0) == 0 && offsetof(DItem, inv1) == 16 && offsetof(DItem, inv2) == 32 && offsetof(DItem, inv3) == 48, "ItemRec: inverse rows");
+static_assert(offsetof(DItem, bmin) == 112 && offsetof(DItem, radius) == 124 && offsetof(DItem, bmax) == 128 && offsetof(DItem, flags) == 140, "ItemRec: box rows");
+static_assert(offsetof(DItem, tri_base) == 160 && offsetof(DItem, n_tris) == 164 && offsetof(DItem, node_base4) == 168 && offsetof(DItem, root4) == 172, "ItemRec: tree group");
+static_assert(sizeof(DItem) == 176, "ItemRec: record size (every group is 16-byte aligned)");
+typedef float rr_f4v __attribute__((ext_vector_type(4)));
+// The record of a WAVE-UNIFORM item (every lane of a packet visits the same candidate): through the constant address space,
+// like the node rows of a uniform step (rr_walk.h node_row_uniform) -- the groups are issued together and waited for once,
+// and arrive in scalar registers.  The items array is written by no trace kernel; edits happen between launches.
+// (The empty asm statement reads the groups where they are loaded.  Without it the compiler sinks each load to its first use,
+// behind the branches of the box test, where every group is a round trip of its own again: three waits in the shadow kernel.)
+RR_DEV ItemRec item_rec_uniform(const DItem* items, int idx, bool general_w) {
+    const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)(uintptr_t)items
+                                                      + (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(idx) * sizeof(DItem);
+#define RR_ITEM_ROW(off) (*(const __attribute__((address_space(4))) rr_f4v*)(p + (off)))
+    const rr_f4v i0 = RR_ITEM_ROW(0), i1 = RR_ITEM_ROW(16), i2 = RR_ITEM_ROW(32), lo = RR_ITEM_ROW(112), hi = RR_ITEM_ROW(128), g = RR_ITEM_ROW(160);
+    rr_f4v i3 = {0.0f, 0.0f, 0.0f, 1.0f};
+    if (general_w) i3 = RR_ITEM_ROW(48);
+#undef RR_ITEM_ROW
+    asm volatile("" :: "s"(i0), "s"(i1), "s"(i2), "s"(lo), "s"(hi), "s"(g));
+    ItemRec r;
+    r.inv0 = make_float4(i0.x, i0.y, i0.z, i0.w); r.inv1 = make_float4(i1.x, i1.y, i1.z, i1.w); r.inv2 = make_float4(i2.x, i2.y, i2.z, i2.w);
+    r.inv3 = make_float4(i3.x, i3.y, i3.z, i3.w);
+    r.bmin[0] = lo.x; r.bmin[1] = lo.y; r.bmin[2] = lo.z; r.radius = lo.w;
+    r.bmax[0] = hi.x; r.bmax[1] = hi.y; r.bmax[2] = hi.z; r.flags = __float_as_uint(hi.w);
+    r.tri_base = __float_as_uint(g.x); r.n_tris = __float_as_uint(g.y); r.node_base4 = __float_as_uint(g.z); r.root4 = __float_as_int(g.w);
+    return r;
+}
+
+// ShapeBasics::get_inverse_ray, reference src/shape/mod.rs:755-761.  Item: DItem or ItemRec.
+template <class Item> RR_DEV LRay inverse_ray(const Item& it, f3 o, f3 d, bool general_w) {
     LRay r;
     float ox = row4(it.inv0, o.x, o.y, o.z, 1.0f);
     float oy = row4(it.inv1, o.x, o.y, o.z, 1.0f);

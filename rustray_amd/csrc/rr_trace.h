@@ -71,10 +71,10 @@ RR_DEV uint32_t reference_face_id(const DItem* it, const DTriX* trix, uint32_t f
 
 // The reference sorts candidates by bbox distance (stable) and keeps strictly
 // smaller toi, so among equal toi the smaller (bbox distance, item index) wins.
-RR_DEV void closest_item(const DSceneView& sc, int idx, f3 o, f3 d, uint32_t depth,
+// `it`: item idx -- its DItem, or its ItemRec where all lanes visit the same item (item_rec_uniform).
+template <class Item> RR_DEV void closest_item(const DSceneView& sc, int idx, const Item& it, f3 o, f3 d, uint32_t depth,
                          int* s_stack, int sp_base, Closest* best) {
     RR_UTIL(1)
-    const DItem& it = rr_global(sc.items)[idx];
     uint32_t flags = it.flags;
     if (!item_passes(flags, false, depth)) return;
     LRay lr = inverse_ray(it, o, d, sc.general_w != 0u);
@@ -104,9 +104,9 @@ RR_DEV void closest_item(const DSceneView& sc, int idx, f3 o, f3 d, uint32_t dep
 // closest_item for a candidate that ALL lanes of a packet visit together (trace_closest_packet): a mesh is walked once per wave
 // (blas_closest_packet), with the lanes whose exact box test passed taking part.  Same result as closest_item, lane by lane.
 RR_DEV void closest_item_packet(const DSceneView& sc, int idx, f3 o, f3 d, uint32_t depth, int* s_stack, Closest* best) {
-    const DItem& it = rr_global(sc.items)[idx];
+    const ItemRec it = item_rec_uniform(sc.items, idx, sc.general_w != 0u); // (wave-uniform: one item, fetched once for the wave)
     const uint32_t flags = it.flags;
-    if (flags & RR_IF_SPHERE) { closest_item(sc, idx, o, d, depth, s_stack, 0, best); return; } // (wave-uniform: one item)
+    if (flags & RR_IF_SPHERE) { closest_item(sc, idx, it, o, d, depth, s_stack, 0, best); return; }
     RR_UTIL(1)
     bool in = item_passes(flags, false, depth) && it.n_tris != 0u;
     const LRay lr = inverse_ray(it, o, d, sc.general_w != 0u);
@@ -141,7 +141,8 @@ RR_DEV void trace_closest_ray(const DSceneView& sc, f3 o, f3 d, uint32_t depth, 
     for (;;) {
         while (cur >= 0) { RR_NODE4_STEP(sc.tnodes4c, ws, fminf(best->t * RR_TOI_SLACK, RR_FLT_MAX)) }
         if (cur == RR_SENTINEL) break;
-        closest_item(sc, (int)RR_LEAF_FIRST((uint32_t)~cur), o, d, depth, s_stack, sp, best); // one item per top-level leaf
+        const int idx = (int)RR_LEAF_FIRST((uint32_t)~cur); // one item per top-level leaf
+        closest_item(sc, idx, rr_global(sc.items)[idx], o, d, depth, s_stack, sp, best);
         sp--; cur = STK(sp);
     }
 }
@@ -369,10 +370,10 @@ RR_DEV bool trace_closest_packet(const DSceneView& sc, f3 o, f3 d, uint32_t dept
 // (reference src/raytracing.rs:483-486), not at the nearest hit.
 struct ShadowSel { float key; int item; bool found; bool within; float t; uint32_t face; };
 
-RR_DEV void shadow_item(const DSceneView& sc, int idx, f3 o, f3 d, uint32_t depth, float limit,
+// `it`: item idx, as for closest_item.
+template <class Item> RR_DEV void shadow_item(const DSceneView& sc, int idx, const Item& it, f3 o, f3 d, uint32_t depth, float limit,
                         int* s_stack, int sp_base, ShadowSel* sel) {
     RR_UTIL(1)
-    const DItem& it = rr_global(sc.items)[idx];
     uint32_t flags = it.flags;
     if (!item_passes(flags, true, depth)) return;
     LRay lr = inverse_ray(it, o, d, sc.general_w != 0u);
@@ -499,7 +500,8 @@ RR_DEV void trace_shadow_ray(const DSceneView& sc, f3 o, f3 d, uint32_t depth, f
     for (;;) {
         while (cur >= 0) { RR_NODE4_STEP_PLAIN(sc.tnodes4, ws, RR_SHADOW_BOUND) }
         if (cur == RR_SENTINEL) break;
-        shadow_item(sc, (int)RR_LEAF_FIRST((uint32_t)~cur), o, d, depth, limit, s_stack, sp, sel);
+        const int idx = (int)RR_LEAF_FIRST((uint32_t)~cur);
+        shadow_item(sc, idx, rr_global(sc.items)[idx], o, d, depth, limit, s_stack, sp, sel);
         sp--; cur = STK(sp);
     }
     // The occluder found has a hit within the light distance.  Only if its sort key lies beyond the light (its box
@@ -516,7 +518,8 @@ RR_DEV bool trace_shadow_packet(const DSceneView& sc, f3 o, f3 d, uint32_t depth
     float key; int idx;
     while (beam_next(sk, item, &key, &idx)) {
         if (__ballot(key <= RR_SHADOW_BOUND) == 0ull) break; // (a NaN light distance compares false: that lane wants nothing, as in the per-ray walk)
-        shadow_item(sc, idx, o, d, depth, limit, s_stack, 0, sel); // (wave-uniform: one item; every lane walks it by itself)
+        // (wave-uniform: one item, its record fetched once for the wave; every lane walks it by itself)
+        shadow_item(sc, idx, item_rec_uniform(sc.items, idx, sc.general_w != 0u), o, d, depth, limit, s_stack, 0, sel);
     }
     if (sel->found && sel->within && sel->key > limit) trace_shadow_blockers(sc, o, d, depth, limit, sel, s_stack);
     return true;

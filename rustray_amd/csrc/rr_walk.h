@@ -102,7 +102,6 @@ RR_DEV float4 node_row(const DNode4* nodes, uint32_t byte_off) { return *(const 
 // the same row at a wave-uniform offset, through the constant address space: one s_load_dwordx4 for the wave, the row
 // arrives in scalar registers and feeds the packed subtracts directly.  (A vector load costs the L1 pipeline a quad of
 // lanes per cycle whether or not the 64 addresses are equal: 16 cycles per row, and the walks are bound by exactly that.)
-typedef float rr_f4v __attribute__((ext_vector_type(4)));
 RR_DEV float4 node_row_uniform(const DNode4* nodes, uint32_t byte_off) {
     const rr_f4v v = *(const __attribute__((address_space(4))) rr_f4v*)((const __attribute__((address_space(4))) char*)(uintptr_t)nodes + byte_off);
     return make_float4(v.x, v.y, v.z, v.w);
@@ -257,8 +256,9 @@ struct TriBest { float t; uint32_t slot; uint32_t face; uint32_t side; bool foun
     }
 
 // SCALAR_LEAVES: the closest-hit kernels' form (see RR_LEAF_CLOSEST); the shadow kernel, at its register limit, keeps the plain loop.
-template <bool SCALAR_LEAVES>
-RR_DEV void blas_closest(const DSceneView& sc, const DItem& it, const LRay& ray, float gbound,
+// Item (here and below): ItemRec, the register copy of the walks of rr_trace.h, or DItem itself (its rare passes over all items).
+template <bool SCALAR_LEAVES, class Item>
+RR_DEV void blas_closest(const DSceneView& sc, const Item& it, const LRay& ray, float gbound,
                          int* s_stack, int sp_base, TriBest* out) {
     TriBest best; best.found = false; best.t = RR_FLT_MAX; best.slot = 0; best.face = 0xffffffffu; best.side = 0u;
     const Slab4 sr = make_slab4(make_slab(ray.o, ray.d), it.node_base4);
@@ -288,7 +288,8 @@ RR_DEV void blas_closest(const DSceneView& sc, const DItem& it, const LRay& ray,
 
 // Shadow query of one mesh: is there ANY hit, and is there one with toi <= limit?
 // Stops at the first hit within the limit.
-RR_DEV void blas_any(const DSceneView& sc, const DItem& it, const LRay& ray, float limit,
+template <class Item>
+RR_DEV void blas_any(const DSceneView& sc, const Item& it, const LRay& ray, float limit,
                      int* s_stack, int sp_base, bool* found_any, bool* found_within) {
     bool any = false, within = false;
     const Slab4 sr = make_slab4(make_slab(ray.o, ray.d), it.node_base4);
@@ -413,7 +414,8 @@ RR_DEV void blas_any(const DSceneView& sc, const DItem& it, const LRay& ray, flo
                                     ka = s_ ? kb : ka; ca = s_ ? cb : ca; kb = tk_; cb = tc_; }
 
 // returns false (nothing done) when the lanes do not share their direction signs in the mesh's space: the caller walks per lane
-RR_DEV bool blas_closest_packet(const DSceneView& sc, const DItem& it, const LRay& ray, bool in, float gbound,
+template <class Item>
+RR_DEV bool blas_closest_packet(const DSceneView& sc, const Item& it, const LRay& ray, bool in, float gbound,
                                 int* s_stack, int sp_base, TriBest* out) {
     const Slab4 sr = make_slab4(make_slab(ray.o, ray.d), it.node_base4);
     if (!sr.uni) return false;
