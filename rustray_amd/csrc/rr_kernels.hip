@@ -359,15 +359,28 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         const bool idc = ((meta >> 24) & 1u) != 0u;
         const float thr = r0.w;
         const DItem& it = rr_global(sc.items)[item_idx];
-        const uint32_t it_flags = it.flags, it_id = it.id; // register copies (see MatR)
-        const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
+        // The item's words and the material, in registers (HitItem, MatR).  A level-1 packet is 64 samples of one pixel: as a rule every hit of
+        // it is on ONE item, and then the wave asks for both records once, through the scalar cache -- two dependent requests of a few groups each
+        // instead of hit -> item -> material per lane.  Lanes that missed are outside this region and never supply the index.  Packets at an
+        // item's edge, of several pixels (sample_group < 64) and all deeper levels load per lane.  One shading body follows either loader.
+        HitItem hi; MatR m;
+        bool one_item = false;
+        if constexpr (PRIMARY) one_item = __ballot(item_idx != __builtin_amdgcn_readfirstlane(item_idx)) == 0ull;
+        if (one_item) {
+            hi = load_hit_item_uniform(sc.items, item_idx);
+            m = load_material_uniform(sc.materials, hi.material, s_lut);
+        } else {
+            hi = load_hit_item(it);
+            m = load_material(&rr_global(sc.materials)[hi.material], s_lut);
+        }
+        const uint32_t it_flags = hi.flags, it_id = hi.id;
         const f3 ro = mk3(r0.x, r0.y, r0.z), rd = mk3(r1.x, r1.y, r1.z);
         const float hit_dist = __uint_as_float(hit.x);
         const f3 hit_point = ro + (rd * hit_dist);
 
         // ---- world normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65)
         HitWeights hw;
-        const f3 normal = hit_normal(sc, it, it_flags, m, ro, rd, hit_point, hit.z, gw, &hw);
+        const f3 normal = hit_normal(sc, it, hi, m, ro, rd, hit_point, hit.z, gw, &hw);
         // ---- aux outputs of the root node (:742-744, :400-402): summed per pixel below, with the wave's other root hits
         if (depth == 1u) {
             aux_pix = pix;

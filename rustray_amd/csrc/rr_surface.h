@@ -3,9 +3,10 @@
 // src/shape/sphere.rs:69-99), the jitter of a direction on the counter-based generator (src/raytracing.rs:565-626) and
 // fresnel (:535-563).
 //
-// Offers: c_u8_to_f32 (filled by rr_api_scene.h rr_scene_create); texel, tex_wrap, tex_bilinear, MatR, load_material, tex_color (both forms);
-// item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; the steps of a hit's surface (HitWeights, hit_normal, hit_uv,
-// mapped_normal, roughness_spread, hit_colors, hit_reflectivity, hit_ambient_occlusion) and their composition (SurfaceAt, surface_at).  No macros.
+// Offers: c_u8_to_f32 (filled by rr_api_scene.h rr_scene_create); texel, tex_wrap, tex_bilinear, MatR, load_material, uniform_row, load_material_uniform,
+// tex_color (both forms); item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; HitItem, load_hit_item,
+// load_hit_item_uniform; the steps of a hit's surface (HitWeights, hit_normal, hit_uv, mapped_normal, roughness_spread, hit_colors,
+// hit_reflectivity, hit_ambient_occlusion) and their composition (SurfaceAt, surface_at).  No macros.
 // Needs: rr_primitives.h (to_local_point, inverse_ray, ray_ball, to_world_normal), rr_walk.h (rr_global), rr_trace.h (ray_nonfinite).
 #pragma once
 #include "rr_walk.h"
@@ -56,22 +57,47 @@ struct MatR {
     float cos_shadow_softness, cos_roughness; // jitter()'s z_lo for the two constant spreads (host-evaluated, DMaterial)
     uint32_t flags;
     const DMaterial* p;
+    const DMaterial* up; // the same record where every lane of the wave shades this material (load_material_uniform: a scalar), else NULL
     const float* lut; // u8 -> f32 table of the workgroup (LDS)
 };
-RR_DEV MatR load_material(const DMaterial* p, const float* lut) {
-    const float4* q = (const float4*)p;
-    const float4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[6]; // q[4], q[5]: the texture slots, read when a slot's flag is set
+static_assert(offsetof(DMaterial, ambient) == 0 && offsetof(DMaterial, alpha) == 12 && offsetof(DMaterial, base) == 16 && offsetof(DMaterial, specular) == 32
+              && offsetof(DMaterial, refraction_index) == 48 && offsetof(DMaterial, roughness) == 60, "MatR: colour and scalar groups");
+static_assert(offsetof(DMaterial, tex) == 64 && offsetof(DMaterial, flags) == 96 && offsetof(DMaterial, cos_shadow_softness) == 100 && offsetof(DMaterial, cos_roughness) == 104
+              && offsetof(DMaterial, texd) == 112 && sizeof(DMaterial) == 240, "MatR: flag group, texture descriptors, record size");
+template <class F4> RR_DEV MatR material_regs(F4 a, F4 b, F4 c, F4 d, F4 e, const DMaterial* p, const DMaterial* up, const float* lut) {
     MatR m;
     m.ambient = mk3(a.x, a.y, a.z); m.alpha = a.w;
     m.base = mk3(b.x, b.y, b.z); m.shininess = b.w;
     m.specular = mk3(c.x, c.y, c.z); m.reflectivity = c.w;
     m.refraction_index = d.x; m.normal_map_strength = d.y; m.shadow_softness = d.z; m.roughness = d.w;
-    m.flags = __float_as_uint(e.x); m.cos_shadow_softness = e.y; m.cos_roughness = e.z; m.p = p; m.lut = lut;
+    m.flags = __float_as_uint(e.x); m.cos_shadow_softness = e.y; m.cos_roughness = e.z; m.p = p; m.up = up; m.lut = lut;
     return m;
+}
+RR_DEV MatR load_material(const DMaterial* p, const float* lut) {
+    const float4* q = (const float4*)p;
+    const float4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[6]; // q[4], q[5]: the texture slots, read when a slot's flag is set
+    return material_regs(a, b, c, d, e, p, nullptr, lut);
+}
+// 16 bytes of a record at a WAVE-UNIFORM address, through the constant address space: a scalar request, the value arrives in SGPRs
+RR_DEV rr_f4v uniform_row(const void* record, uint32_t byte_off) {
+    return *(const __attribute__((address_space(4))) rr_f4v*)((const __attribute__((address_space(4))) char*)(uintptr_t)record + byte_off);
+}
+// The material of a WAVE-UNIFORM hit (`material`: a scalar, HitItem::material of load_hit_item_uniform): the same five groups through the
+// constant address space, issued together and waited for once (item_rec_uniform, rr_primitives.h, has the story of the empty asm
+// statement).  Materials are written by no kernel; edits happen between launches.
+RR_DEV MatR load_material_uniform(const DMaterial* materials, int material, const float* lut) {
+    const DMaterial* up = materials + material;
+    const rr_f4v a = uniform_row(up, 0u), b = uniform_row(up, 16u), c = uniform_row(up, 32u), d = uniform_row(up, 48u), e = uniform_row(up, 96u);
+    asm volatile("" :: "s"(a), "s"(b), "s"(c), "s"(d), "s"(e));
+    return material_regs(a, b, c, d, e, up, up, lut);
 }
 RR_DEV bool tex_color(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, int slot, float4* out) {
     if (!(m.flags & (RR_MF_TEX_SLOT0 << slot)) || !has_uv) return false; // slot bit = index >= 0 and width > 0
     DTexture t; // the slot's descriptor sits in the material record itself (DMaterial::texd): one 16-B load at an address known since the material was
+    if (m.up) { // (a scalar test: one request for the wave, and the texel addresses below are formed from scalars)
+        const rr_f4v q = uniform_row(m.up, (uint32_t)offsetof(DMaterial, texd) + 16u * (uint32_t)slot);
+        t.offset = (uint64_t)__float_as_uint(q.x) | ((uint64_t)__float_as_uint(q.y) << 32); t.width = __float_as_uint(q.z); t.height = __float_as_uint(q.w);
+    } else
     { const uint4 q = *(const uint4*)&m.p->texd[slot]; t.offset = (uint64_t)q.x | ((uint64_t)q.y << 32); t.width = q.z; t.height = q.w; }
     if (m.flags & RR_MF_NEAREST) *out = texel(sc, t, tex_wrap(uv.x, t.width), tex_wrap(uv.y, t.height), m.lut);
     else *out = tex_bilinear(sc, t, uv.x, uv.y, m.lut);
@@ -179,14 +205,32 @@ RR_DEV float fresnel(f3 incident, f3 normal, float index) {
 // src/raytracing.rs:747-811, :928-933, :985-991), in the reference's steps.  k_shade calls the steps where it needs their values,
 // between its own sums, jitter and recursion; surface_at (rr_surface_rays) is their composition for callers that want the values.
 // ---------------------------------------------------------------------------
+// The words of a hit's item that every hit reads, in registers (see MatR); the matrix rows and the radius, which smooth, textured and
+// sphere hits alone read, stay behind `const DItem&`.
+struct HitItem { uint32_t flags, id, wn_base, tri_base; int32_t material; };
+static_assert(offsetof(DItem, id) == 144 && offsetof(DItem, material) == 148 && offsetof(DItem, wn_base) == 152, "HitItem: id group");
+RR_DEV HitItem load_hit_item(const DItem& it) {
+    HitItem h; h.flags = it.flags; h.id = it.id; h.wn_base = it.wn_base; h.tri_base = it.tri_base; h.material = it.material;
+    return h;
+}
+// The same of a WAVE-UNIFORM item (`idx`: the same in every active lane, at least one of them): the flag word, the id group and the tree
+// group's first word through the constant address space, issued together and waited for once, as item_rec_uniform does for the walks.
+RR_DEV HitItem load_hit_item_uniform(const DItem* items, int idx) {
+    const DItem* it = items + (uint32_t)__builtin_amdgcn_readfirstlane(idx);
+    const rr_f4v box = uniform_row(it, 128u), g = uniform_row(it, 144u), tree = uniform_row(it, 160u); // (flags: the box row's w lane, as in ItemRec)
+    asm volatile("" :: "s"(box), "s"(g), "s"(tree));
+    HitItem h; h.flags = __float_as_uint(box.w); h.id = __float_as_uint(g.x); h.material = __float_as_int(g.y); h.wn_base = __float_as_uint(g.z); h.tri_base = __float_as_uint(tree.x);
+    return h;
+}
+
 // The area weights of a mesh hit and its triangle's attributes: they serve the interpolated normal AND the uv (Mesh::get_normal and
 // Mesh::get_uv compute the same three numbers from the same inputs, src/shape/mesh.rs:105-161, :204-259)
 struct HitWeights { DTriAttr at; float a1, a2, a3; bool have; };
 
-// World normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65).  `it_flags`: the caller's register copy of it.flags (see MatR);
+// World normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65).  `hi`: the caller's register copies of the item's words (HitItem);
 // `hit_z`: the walks' face word (leaf-order slot | negated << 30 | back << 31); `gw`: DSceneView::general_w.
-RR_DEV f3 hit_normal(const DSceneView& sc, const DItem& it, uint32_t it_flags, const MatR& m, f3 ro, f3 rd, f3 hit_point, uint32_t hit_z, bool gw, HitWeights* w) {
-    const uint32_t it_tri_base = it.tri_base;
+RR_DEV f3 hit_normal(const DSceneView& sc, const DItem& it, const HitItem& hi, const MatR& m, f3 ro, f3 rd, f3 hit_point, uint32_t hit_z, bool gw, HitWeights* w) {
+    const uint32_t it_flags = hi.flags, it_tri_base = hi.tri_base;
     const uint32_t slot = hit_z & 0x3fffffffu;
     const bool back = (hit_z >> 31) != 0u, neg = ((hit_z >> 30) & 1u) != 0u;
     f3 normal;
@@ -213,7 +257,7 @@ RR_DEV f3 hit_normal(const DSceneView& sc, const DItem& it, uint32_t it_flags, c
             if (back) normal = -normal;
         } else {
             // to_world_normal(it, neg ? -ng : ng) with ng = DTri::v3, evaluated once per instanced triangle by k_world_normals
-            const float4 wn = rr_global(sc.flat_normals)[it.wn_base + 2u * slot + (neg ? 1u : 0u)];
+            const float4 wn = rr_global(sc.flat_normals)[hi.wn_base + 2u * slot + (neg ? 1u : 0u)];
             normal = mk3(wn.x, wn.y, wn.z);
         }
         if (it_flags & RR_IF_FLIP_NORMALS) normal = -normal;
@@ -299,10 +343,11 @@ struct SurfaceAt {
 RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m, f3 ro, f3 rd, float hit_dist, uint32_t hit_z) {
     SurfaceAt s;
     const bool gw = sc.general_w != 0u;
-    const uint32_t it_flags = it.flags;
+    const HitItem hi = load_hit_item(it);
+    const uint32_t it_flags = hi.flags;
     HitWeights w;
     s.position = ro + (rd * hit_dist);
-    s.normal = hit_normal(sc, it, it_flags, m, ro, rd, s.position, hit_z, gw, &w);
+    s.normal = hit_normal(sc, it, hi, m, ro, rd, s.position, hit_z, gw, &w);
     s.has_uv = hit_uv(it, it_flags, m, s.position, gw, w, &s.uv);
     s.shading_normal = mapped_normal(sc, m, s.has_uv, s.uv, s.normal);
     roughness_spread(sc, m, s.has_uv, s.uv, &s.roughness);
