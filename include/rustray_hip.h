@@ -268,10 +268,13 @@ typedef struct rr_pick_result {
 
 /* Per-frame work counters: one "ray" = one Raytracing::trace
  * call (reference src/raytracing.rs:429).
- * The ms_* fields of the kernels are sums of per-launch durations.  Where level 1 runs in stages on two streams
- * (rr_scene_overlap_stages) its shade and shadow launches run side by side: their durations overlap in time, each is the
+ * The ms_* fields of the kernels are sums of per-launch durations.  Where level 1 runs in stages (rr_scene_overlap_stages)
+ * its shade and shadow launches run side by side on two streams: their durations overlap in time, each is the
  * launch's time while it shared the device, and their sum may exceed ms_total (first to last event of the frame on the
- * caller's stream). */
+ * caller's stream).  Where such a level is one slice of the ray arena, its closest hits are traced stage by stage as well, on a
+ * third stream beside the other two: launches_trace_closest_level1 then counts one launch per stage (not one per batch), and
+ * ms_trace_closest_level1 -- with it ms_trace_closest -- is a sum of durations that overlap the shade and shadow launches' in
+ * the same way. */
 typedef struct rr_frame_stats {
     uint64_t primary_rays;
     uint64_t secondary_rays; /* reflection + refraction */
@@ -288,7 +291,7 @@ typedef struct rr_frame_stats {
     uint64_t sliced_levels; /* depth levels whose children did not fit behind them in the ray arena at once */
     uint64_t binned_rays;   /* secondary rays that were re-ordered by (origin cell, direction octant) before being traced */
     double ms_binning;      /* device time of that re-ordering (kernel_timing); after rr_render_adaptive, rr_render_adaptive_levels and rr_render_adaptive_prefix, also of the launches that make their lists */
-    double ms_trace_closest_level1;          /* the part of ms_trace_closest spent on depth level 1 (the primary rays) */
+    double ms_trace_closest_level1;          /* the part of ms_trace_closest spent on depth level 1 (the primary rays); in stages: see above */
     uint64_t launches_trace_closest_level1;
     /* rr_render_multi only (on scenes[0]; zero after any other frame): how the per-device buffers reached scenes[0]'s device */
     uint32_t multi_devices;       /* handles that took part */

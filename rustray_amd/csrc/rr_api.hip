@@ -45,7 +45,7 @@
 #include "rr_sample_table.h" // the reference's sub-sample table; regions of a frame (no HIP call)
 #include "rr_api_handle.h"   // rr_scene in its parts, one per layer below
 #include "rr_api_scene.h"    // scene creation, the view, the top level and its reach, in-place and structural edits
-#include "rr_api_frame.h"    // the frame driver: level walk, two-stream level 1, stats, tuning
+#include "rr_api_frame.h"    // the frame driver: level walk, level 1 in stages, stats, tuning
 #include "rr_api_multi.h"    // one frame on several devices; the gather maps
 #include "rr_api_post.h"     // post-processing
 #include "rr_api_query.h"    // rr_pick; closest-hit, shadow, surface and radiance queries

@@ -1,7 +1,7 @@
 // rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
 // Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
 //         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
-//         run_level (with level 1 in stages on two streams); take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
+//         run_level (with level 1 in stages on three streams); take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
 //         WHOLE_FRAME, IdleOnExit, fill_pixel_slots, render_region_locked (the pixel queries and the adaptive calls are its other callers);
 //         rr_render_region_device, rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, PassSums,
 //         collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
@@ -100,18 +100,24 @@ struct PassHook { rr_pass_fn fn; void* user; uint32_t min_passes; const rr_frame
 // change to the kernel's arguments cannot leave one caller behind.  Every pointer the kernel may touch is checked here, on the host,
 // before the launch: a NULL one would be a write to address 16 * i on the device.  Level 1 reads no ray records (the rays are
 // derived from their index), so its queue carries the hit records only and its ray pointers are passed as NULL.
+// The launch walks the packets [p0, p0 + np) of the level's n rays with `head` as its own head word (0, RR_ALL_PACKETS: the whole level) on at
+// most wg_per_cu workgroups per CU: RR_CLOSEST_WAVES, the resident ones, for a launch that has the GPU to itself.
 static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t* count, uint32_t* head, uint64_t n, const DShadeConst* kc,
-                                const DPrimary& pr, unsigned long long* counters, hipStream_t st) {
+                                const DPrimary& pr, unsigned long long* counters, hipStream_t st, uint32_t p0, uint32_t np,
+                                uint32_t wg_per_cu = RR_CLOSEST_WAVES) {
     if (!count || !head || !q.hit || !kc || !counters) return fail(RR_ERR_DEVICE, "internal: closest-hit launch with a NULL argument");
     if (primary && (!pr.sample_tr || pr.n != n)) return fail(RR_ERR_DEVICE, "internal: level-1 closest-hit launch without its ray table");
     if (!primary && (!q.r0 || !q.r1 || !q.r2)) return fail(RR_ERR_DEVICE, "internal: closest-hit launch without ray records");
     if (n == 0 || n > 0x7fffff00ull) return fail(RR_ERR_DEVICE, "internal: closest-hit launch of %llu rays", (unsigned long long)n);
-    const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * RR_CLOSEST_WAVES);
+    const uint64_t level_packets = (n + RR_WAVE - 1) / RR_WAVE;
+    if (np == 0 || p0 >= level_packets || wg_per_cu == 0) return fail(RR_ERR_DEVICE, "internal: closest-hit launch of packets %u + %u of %llu", p0, np, (unsigned long long)level_packets);
+    const uint64_t packets = std::min<uint64_t>(np, level_packets - p0); // a hit record is written only for a ray below n, whatever the range
+    const int grid = (int)std::min<uint64_t>((packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * wg_per_cu);
     if (primary) {
         q.r0 = nullptr; q.r1 = nullptr; q.r2 = nullptr;
-        hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters);
+        hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters, p0, np);
     } else {
-        hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters);
+        hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters, p0, np);
     }
     HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -411,32 +417,49 @@ static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* lev
     return RR_OK;
 }
 
-// ---- level 1 in stages on two streams ---------------------------------------------------------------------------------------------
+// ---- level 1 in stages on three streams -------------------------------------------------------------------------------------------
 // k_shade<true> is bound by instruction issue and k_trace_shadow<true> by memory latency; one after the other, each has the whole
 // GPU in turn.  Here the hits [s0, s1) are cut into stages (rr_frame_plan.h, plan_level1_stages): stage k is shaded on the frame's
 // stream `st` into shadow buffer k % n_buf, and its shadow rays are traced on the handle's second stream behind an event that
 // follows the shade launch, while `st` already shades stage k + 1.  Shade k + n_buf waits for the event behind shadow k, so a
 // buffer is never rewritten while it is read.  `st` may be the legacy null stream and the second stream is non-blocking: all
 // ordering is by these events.  The frame cannot change: the kernels are the serial loop's, every write they share is an integer
-// atomic, and all else goes to the stage's own buffer.  Which frames take this path, and the sizes of the two grids: RR_L1_OVERLAP
+// atomic, and all else goes to the stage's own buffer.  Which frames take this path, and the sizes of the grids: RR_L1_OVERLAP
 // and the knobs after it (rr_kernels.hip), with what was measured.
+// Where the stages cover the whole level (trace_closest: one slice), its closest hits are traced stage by stage as well, on the handle's third
+// stream: k_trace_closest<true> over the packets of stage k (launch_trace_closest with a range; a stage is whole packets), each launch with
+// its own head word.  The stream forks from `st` where the path begins -- behind the frame's uploads and memsets, the zeroing of the counter
+// pool and the previous batch's last shade launch, which reads hit1 -- and nothing else orders its launches: hit1 covers the level, so they
+// run ahead as far as the CUs allow.  Shade k waits for the event behind closest-hit launch k; the wait of the last stage joins the stream into `st`.
 static int ensure_overlap_stream(rr_scene* s) {
     if (!s->frame.overlap_stream) HIP_TRY(hipStreamCreateWithFlags(&s->frame.overlap_stream, hipStreamNonBlocking));
+    if (!s->frame.closest_stream) HIP_TRY(hipStreamCreateWithFlags(&s->frame.closest_stream, hipStreamNonBlocking));
+    if (!s->frame.stage_fork) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_fork, hipEventDisableTiming));
     for (int b = 0; b < 3; b++) {
         if (!s->frame.stage_shaded[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_shaded[b], hipEventDisableTiming));
         if (!s->frame.stage_traced[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_traced[b], hipEventDisableTiming));
+        if (!s->frame.stage_closest[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_closest[b], hipEventDisableTiming));
     }
     return RR_OK;
 }
 
-// enqueues every stage; on any error the caller (run_level1_stages) drains both streams
-static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
-                                 const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+// enqueues every stage; on any error the caller (run_level1_stages) drains all three streams
+static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, uint32_t* count, uint64_t s0, uint64_t s1,
+                                 const DRayQueue& qout, uint32_t* child_count, bool spawns, bool trace_closest) {
     rr_scene* s = f.s;
-    const hipStream_t st = f.st, st2 = s->frame.overlap_stream;
+    const hipStream_t st = f.st, st2 = s->frame.overlap_stream, st3 = s->frame.closest_stream;
     const uint32_t L = s->data.n_enabled_lights;
     unsigned long long* counters = s->frame.counters.as<unsigned long long>();
     if (sp.sq_need > s->frame.sq_cap || sp.valid_need * 8 > s->frame.sq_valid.bytes) return fail(RR_ERR_DEVICE, "internal: shadow queue smaller than its stage buffers");
+    uint32_t* closest_heads = nullptr; // one per closest-hit launch, RR_SQ_STRIDE words apart, zeroed on `st` before the fork
+    if (trace_closest) {
+        if (s0 != 0 || s1 != f.pr.n || sp.stage % RR_WAVE != 0) return fail(RR_ERR_DEVICE, "internal: closest-hit stages over a part of level 1");
+        f.pool.align_line();
+        closest_heads = f.pool.take(sp.n_stages * RR_SQ_STRIDE);
+        if (!closest_heads) return counters_exhausted();
+        HIP_TRY(hipEventRecord(s->frame.stage_fork, st));
+        HIP_TRY(hipStreamWaitEvent(st3, s->frame.stage_fork, 0));
+    }
     for (uint32_t k = 0; k < sp.n_stages; k++) {
         if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
         const uint64_t c0 = s0 + sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, s1);
@@ -454,6 +477,15 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         // the first stage's shade and the last stage's shadow run alone: the serial loop's grids.  In between the two launches share the CUs.
         const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : groups);
         const uint64_t shadow_wg = last ? (uint64_t)f.shadow_grid : (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
+        if (trace_closest) { // the host is stages ahead of the device: launch k is enqueued long before launch k - 1 ends
+            {
+                ScopedTimer t(s, st3, TK_CLOSEST, true);
+                RR_TRY(launch_trace_closest(s, true, qin, count, closest_heads + (size_t)k * RR_SQ_STRIDE, f.pr.n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st3,
+                                            (uint32_t)(c0 / RR_WAVE), (uint32_t)(sp.stage / RR_WAVE), first ? RR_L1_CLOSEST_FIRST_WG : RR_L1_CLOSEST_WG));
+            }
+            HIP_TRY(hipEventRecord(s->frame.stage_closest[k % 3u], st3));
+            HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_closest[k % 3u], 0));
+        }
         if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[b], 0));
         {
             ScopedTimer t(s, st, TK_SHADE, true);
@@ -481,14 +513,15 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
     return RR_OK;
 }
 
-// THE one way in and out of the staged path: whatever ends it early (cancel flag, HIP error, counter pool exhausted) leaves both streams idle,
-// so the handle stays usable and the next frame cannot race a straggler.
-static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, const uint32_t* count, uint64_t s0, uint64_t s1,
-                             const DRayQueue& qout, uint32_t* child_count, bool spawns) {
+// THE one way in and out of the staged path: whatever ends it early (cancel flag, HIP error, counter pool exhausted) leaves all three streams
+// idle, so the handle stays usable and the next frame cannot race a straggler.
+static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, uint32_t* count, uint64_t s0, uint64_t s1,
+                             const DRayQueue& qout, uint32_t* child_count, bool spawns, bool trace_closest) {
     rr_scene* s = f.s;
     RR_TRY(ensure_overlap_stream(s));
-    const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns);
+    const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns, trace_closest);
     if (rc != RR_OK) {
+        (void)hipStreamSynchronize(s->frame.closest_stream);
         (void)hipStreamSynchronize(s->frame.overlap_stream);
         (void)hipStreamSynchronize(f.st);
         return rc;
@@ -512,15 +545,22 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
     const bool l1 = d == 1 && !f.seeded; // the level-1 builds: rays derived from their index
     DRayQueue qin = f.queue_at(base);
     if (l1) { qin.r0 = nullptr; qin.r1 = nullptr; qin.r2 = nullptr; qin.hit = s->frame.hit1.as<uint4>(); }
-    {
-        uint32_t* head = f.pool.take(1);
-        if (!head) return counters_exhausted();
-        ScopedTimer t(s, st, TK_CLOSEST, l1);
-        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st));
-    }
     const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
     const uint64_t M = f.plan.M, child_base = l1 ? 0 : base + n;
     const uint64_t slice = level_slice(M, child_base, n, d, f.R);
+    // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams (per slice of the level)
+    const auto staged = [&](uint64_t hits) {
+        return level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
+               s->data.view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, hits).overlapped();
+    };
+    // ... and where the level is ONE slice, its closest hits stage by stage on a third stream; every other level in one launch, here
+    const bool closest_staged = slice == n && staged(n);
+    if (!closest_staged) {
+        uint32_t* head = f.pool.take(1);
+        if (!head) return counters_exhausted();
+        ScopedTimer t(s, st, TK_CLOSEST, l1);
+        RR_TRY(launch_trace_closest(s, l1, qin, count, head, n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st, 0u, RR_ALL_PACKETS));
+    }
     if (slice == 0) return fail(RR_ERR_OUT_OF_MEMORY, "ray arena of %llu rays is too small for depth level %u", (unsigned long long)M, d);
     if (slice < n) s->timing.stats.sliced_levels++;
     for (uint64_t s0 = 0; s0 < n; s0 += slice) {
@@ -528,11 +568,9 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         uint32_t* child_count = f.pool.take(1);
         if (!child_count) return counters_exhausted();
         const DRayQueue qout = f.queue_at(child_base);
-        // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams
-        const bool staged = level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
-                            s->data.view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, s1 - s0).overlapped();
-        if (staged) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns));
-        for (uint64_t c0 = s0; c0 < s1 && !staged; c0 += f.plan.chunk) {
+        const bool in_stages = staged(s1 - s0);
+        if (in_stages) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns, closest_staged));
+        for (uint64_t c0 = s0; c0 < s1 && !in_stages; c0 += f.plan.chunk) {
             if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
             const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
             const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);

@@ -89,6 +89,10 @@ struct FrameState {
     // shadow-queue buffer the event behind its shade launch (first stream) and behind its shadow launch (second stream)
     hipStream_t overlap_stream = nullptr;
     hipEvent_t stage_shaded[3] = {nullptr, nullptr, nullptr}, stage_traced[3] = {nullptr, nullptr, nullptr};
+    // ... and the third one, which traces the closest hits of stage k + 1, k + 2, ... while stage k is shaded: it forks from the frame's stream
+    // behind stage_fork, and stage_closest[k % 3] follows the closest-hit launch of stage k
+    hipStream_t closest_stream = nullptr;
+    hipEvent_t stage_fork = nullptr, stage_closest[3] = {nullptr, nullptr, nullptr};
     uint32_t overlap_stages = 0; // level-1 stages of the last frame that ran on the two streams (rr_scene_overlap_stages)
     uint32_t* h_count = nullptr; // pinned, 16 words, by HC_*: what the host waits for (every wait reads its word before the next one is issued)
     std::vector<uint16_t> table_cache; uint16_t table_samples = 0; // built-in sub-sample table of the last sample count
@@ -105,7 +109,10 @@ struct FrameState {
         if (h_count) (void)hipHostFree(h_count);
         for (hipEvent_t e : stage_shaded) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : stage_traced) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : stage_closest) if (e) (void)hipEventDestroy(e);
+        if (stage_fork) (void)hipEventDestroy(stage_fork);
         if (overlap_stream) (void)hipStreamDestroy(overlap_stream);
+        if (closest_stream) (void)hipStreamDestroy(closest_stream);
     }
 };
 

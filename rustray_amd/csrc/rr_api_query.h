@@ -40,7 +40,7 @@ extern "C" int rr_pick(rr_scene* s, const rr_camera* cam, int x, int y, rr_pick_
     DShadeConst hc;
     hc.sc = s->data.view; hc.fr = fr; hc.ps = primary_frame((const float*)b, 1u, 1u);
     HIP_TRY(hipMemcpy(b + 256, &hc, sizeof hc, hipMemcpyHostToDevice));
-    RR_TRY(launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), pr, (unsigned long long*)(b + 128), nullptr));
+    RR_TRY(launch_trace_closest(s, true, q, (uint32_t*)(b + 96), (uint32_t*)(b + 100), 1, (const DShadeConst*)(b + 256), pr, (unsigned long long*)(b + 128), nullptr, 0u, RR_ALL_PACKETS));
     uint32_t hit[4];
     HIP_TRY(hipMemcpy(hit, b + 64, 16, hipMemcpyDeviceToHost));
     scratch.release();
@@ -208,7 +208,7 @@ static int trace_rays_locked(rr_scene* s, const float* origins, const float* dir
     else { // (the <false> build reads neither the frame constants nor the work counters; both pointers name the handle's words all the same)
         const DPrimary pr{nullptr, PrimaryLaunch{0u, 0u, 0u, 6u}, 0u};
         RR_TRY(launch_trace_closest(s, false, q, (uint32_t*)(w + QW_COUNT), (uint32_t*)(w + QW_HEAD), n, (const DShadeConst*)(w + QW_CONST), pr,
-                                    (unsigned long long*)(w + QW_COUNTERS), st));
+                                    (unsigned long long*)(w + QW_COUNTERS), st, 0u, RR_ALL_PACKETS));
     }
     if (KIND == Q_SURFACE) hipLaunchKernelGGL(k_surface_hits, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, s->data.view, q.r0, q.r1, q.hit, n, (uint4*)out);
     else hipLaunchKernelGGL(k_unpack_hits<SHADOW>, dim3(query_grid(s, n)), dim3(RR_BLOCK), 0, st, q.hit, n, s->data.view.items, s->data.view.n_items, s->data.view.trix, (uint32_t*)out);

@@ -52,9 +52,11 @@
 #ifndef RR_SHADOW_GRID_WG
 #define RR_SHADOW_GRID_WG RR_SHADOW_WAVES // exactly the resident workgroups (RR_STACK_DEPTH KB of LDS stack each)
 #endif
-// Level 1 in stages on two streams (rr_api_frame.h run_level1_stages, rr_frame_plan.h plan_level1_stages): k_shade<true> of stage
-// k + 1 beside k_trace_shadow<true> of stage k.  All numbers: the contract frame (sponza_syn 1280x720 128 spp), serial loop
-// 19.2 ms on the same box (profiles/r05_level1_share_rates.txt, profiles/r05_dropped.txt, profiles/r05_ab_level1_overlap.txt).
+// Level 1 in stages on three streams (rr_api_frame.h run_level1_stages, rr_frame_plan.h plan_level1_stages): k_shade<true> of stage
+// k + 1 beside k_trace_shadow<true> of stage k and, where the level is one slice, beside k_trace_closest<true> over the packets of stage
+// k + 2 (round 15: before, one closest-hit launch traced the whole level alone, a third of the level-1 work at rate 1.0).  The numbers of
+// the first two knob blocks: the contract frame (sponza_syn 1280x720 128 spp) in round 5, serial loop 19.2 ms on the same box
+// (profiles/r05_level1_share_rates.txt, profiles/r05_dropped.txt, profiles/r05_ab_level1_overlap.txt).
 //   0 = never in stages; 1 = only where the caller asks for shade chunks (rr_tuning::shade_chunk_rays != 0: a stage is that
 //   chunk); 2 = also with automatic tuning, in equal stages of at most RR_L1_STAGE_RAYS.
 #ifndef RR_L1_OVERLAP
@@ -78,6 +80,17 @@
 #endif
 #ifndef RR_L1_SHADOW_WG
 #define RR_L1_SHADOW_WG 16
+#endif
+// ... and of the closest-hit launches of the stages, which share the CUs with both (round 15, parent 17.07 - 17.10 ms on the same box;
+// profiles/r15_ab_closest_stages.txt, profiles/r15_dropped.txt): 24: 16.78 - 16.84 ms; 4 (exactly the resident workgroups: a slot is never
+// handed over) 17.02 - 17.05, 8: 16.88 - 16.89, 16: 16.98 - 17.00, 20: 16.84 - 16.94, 32: 17.02 - 17.06, 48: 19.6 - 19.8.  With the closest-hit
+// launches at 24, shade and shadow at 12 + 12: 16.98 - 17.01, 24 + 24: 17.29; 4 stages instead of 6: 16.74 - 16.78 (no better), 5: 17.2,
+// 8: 17.2 - 17.3, 12: 19.1 - 19.2.  The launch of stage 0 runs alone: the grid of the serial loop, 16.66 - 16.74 against 16.78 - 16.81 at 24.
+#ifndef RR_L1_CLOSEST_WG
+#define RR_L1_CLOSEST_WG 24
+#endif
+#ifndef RR_L1_CLOSEST_FIRST_WG
+#define RR_L1_CLOSEST_FIRST_WG RR_CLOSEST_WAVES // stage 0 (8: 16.71 - 16.76)
 #endif
 #ifndef RR_DYN_FETCH
 #define RR_DYN_FETCH 4 // packets per fetch from the shared head on large launches (more costs locality: +4 % at 8, +10 % at 16)
@@ -205,6 +218,8 @@ struct PacketStream {
         // the launch has only a few packets per wave
         dyn_k = n_packets >= 8u * n_waves ? (uint32_t)RR_DYN_FETCH : (n_packets >= 2u * n_waves ? 2u : 1u);
     }
+    // the stream hands out p0 + its packets from here on: once, before the first next() (nothing of p0 stays live in the walk)
+    RR_DEV void start_at(uint32_t p0) { wave_id += p0; n_static += p0; n_packets += p0; }
     // false: the stream has ended for this wave (wave-uniform)
     RR_DEV bool next(uint32_t* pkt) {
         uint32_t p;
@@ -233,24 +248,31 @@ struct DShadeConst { DSceneView sc; DFrame fr; PrimaryFrame ps; };
 
 // PRIMARY: depth level 1.  The rays are derived from their index (primary_ray), only the 16-B hit record is written;
 // block 0 publishes the level's size for the shade kernel and counts the rays.
+// A launch walks the packets [p0, p0 + np) of the level, as far as the level has them (RR_ALL_PACKETS from 0: the whole level).  A ray
+// and its hit record depend on the ray's index alone, so the launches of a level cut into ranges write what one launch would: level 1
+// in stages (rr_api_frame.h) traces stage k + 1 while stage k is shaded.  Every launch publishes the LEVEL's size and counts its own rays;
+// its packet stream (static share, small_launch) is dealt over its own packets, and the head word is its own.
+#define RR_ALL_PACKETS 0xffffffffu
 template <bool PRIMARY>
 __global__ __launch_bounds__(RR_BLOCK, RR_CLOSEST_WAVES) void k_trace_closest(DSceneView sc, DRayQueue q, uint32_t* __restrict__ q_count,
                                                             uint32_t* head, const DShadeConst* __restrict__ kc, DPrimary pr,
-                                                            unsigned long long* counters) {
+                                                            unsigned long long* counters, uint32_t p0, uint32_t np) {
     __shared__ int s_stack[RR_STACK_DEPTH * RR_BLOCK];
     RR_UTIL_KIND(PRIMARY ? 0u : 1u)
-    uint32_t n;
-    if (PRIMARY) {
-        n = pr.n;
-        if (blockIdx.x == 0 && threadIdx.x == 0) { *q_count = n; atomicAdd(&counters[RR_CNT_PRIMARY], (unsigned long long)n); }
-    } else n = *q_count;
+    const uint32_t n = PRIMARY ? pr.n : *q_count;
+    const uint32_t level_packets = (n + RR_WAVE - 1) / RR_WAVE;
+    const uint32_t n_packets = p0 < level_packets ? min(np, level_packets - p0) : 0u; // of this launch
+    if (PRIMARY && blockIdx.x == 0 && threadIdx.x == 0) {
+        *q_count = n;
+        atomicAdd(&counters[RR_CNT_PRIMARY], (unsigned long long)(min(n, (p0 + n_packets) * RR_WAVE) - min(n, p0 * RR_WAVE)));
+    }
     const uint32_t lane = threadIdx.x & (RR_WAVE - 1);
-    const uint32_t n_packets = (n + RR_WAVE - 1) / RR_WAVE;
     // (a launch with few packets per wave -- one rank's share of a frame tiled over 4 or 8 GPUs -- deals three quarters statically:
     // closest-hit 2.36 -> 2.29 ms on a quarter of the contract frame, 1.36 -> 1.32 ms on an eighth; the whole frame loses 5 % to it)
     const bool small_launch = n_packets < 160u * PacketStream::waves();
     PacketStream stream(n_packets, small_launch ? 3u : (uint32_t)RR_STATIC_NUM, small_launch ? 4u : (uint32_t)RR_STATIC_DEN, head);
-    for (uint32_t pkt; stream.next(&pkt);) {
+    stream.start_at(p0);
+    for (uint32_t pkt; stream.next(&pkt);) { // a packet of the LEVEL
         const uint32_t i = pkt * RR_WAVE + lane;
         const uint32_t ii = min(i, n - 1u); // the lanes past the end of the last packet repeat its last ray, so that the packet form below runs with all lanes
         f3 ro, rd; uint32_t depth;

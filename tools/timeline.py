@@ -31,20 +31,23 @@ else:
     f = max(glob.glob(os.path.join(sys.argv[2], "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)
     rows = [r for r in csv.DictReader(open(f))]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    # the last frame = from the last k_trace_closest<true> launch to the k_resolve after it
+    # the last frame = from its first k_trace_closest<true> launch (level 1 in stages has one per stage) to its k_resolve
     names = [r["Kernel_Name"] for r in rows]
-    first = max(i for i, nm in enumerate(names) if "k_trace_closest<true>" in nm)
-    last = next(i for i in range(first, len(rows)) if "k_resolve" in names[i])
-    # include the memsets before the level-1 launch (same frame): walk back while the gap is small
+    resolves = [i for i, nm in enumerate(names) if "k_resolve" in nm]
+    last = resolves[-1]
+    first = min(i for i in range(resolves[-2] + 1 if len(resolves) > 1 else 0, last) if "k_trace_closest<true>" in names[i])
     t0 = int(rows[first]["Start_Timestamp"])
     prev_end = t0
-    busy = 0
-    print(f"{'kernel':44s} {'start us':>9s} {'dur us':>8s} {'gap us':>7s}")
+    busy = covered = 0
+    print(f"{'kernel':44s} {'queue':>5s} {'start us':>9s} {'end us':>9s} {'dur us':>8s} {'gap us':>7s}")
     for r in rows[first:last + 1]:
         s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
         nm = r["Kernel_Name"].split("(")[0].replace("void ", "")
-        print(f"{nm[:44]:44s} {(s - t0) / 1e3:9.1f} {(e - s) / 1e3:8.1f} {(s - prev_end) / 1e3:7.1f}")
+        # gap: the device idle before this launch (launches of the staged level 1 overlap: negative = it started beside another)
+        print(f"{nm[:44]:44s} {r.get('Queue_Id', '?'):>5s} {(s - t0) / 1e3:9.1f} {(e - t0) / 1e3:9.1f} {(e - s) / 1e3:8.1f} {(s - prev_end) / 1e3:7.1f}")
         busy += e - s
-        prev_end = e
+        covered += max(0, e - max(s, prev_end))
+        prev_end = max(prev_end, e)
     total = prev_end - t0
-    print(f"frame (level-1 launch to resolve): {total / 1e3:.1f} us, kernels busy {busy / 1e3:.1f} us, gaps {(total - busy) / 1e3:.1f} us, {last - first + 1} dispatches")
+    print(f"frame (level-1 launch to resolve): {total / 1e3:.1f} us, sum of kernel durations {busy / 1e3:.1f} us, no kernel running {(total - covered) / 1e3:.1f} us, "
+          f"{last - first + 1} dispatches")
