@@ -54,7 +54,9 @@ extern "C" {
  * rr_denoise_default_params, rr_denoise_records and rr_denoise_records_device (with rr_denoise_params, a struct of its own) came after
  * those, again without a change of any existing struct: a version-3 library may lack these three as well.
  * rr_accumulate_default_params, rr_accumulate_records and rr_accumulate_records_device (with rr_accumulate_params, a struct of its own)
- * came after those in the same way: a version-3 library may lack these three as well. */
+ * came after those in the same way: a version-3 library may lack these three as well.
+ * rr_motion_records and rr_motion_records_device came after those, without a struct of their own: a version-3 library may lack these two
+ * as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1100,6 +1102,46 @@ int rr_accumulate_records(rr_scene* scene, const rr_camera* camera, const rr_acc
                           const float* history_length /* n, or NULL */, const float* motion /* 3n, or NULL */,
                           rr_radiance* out /* n */, rr_radiance* halves_out /* 2n, or NULL */, float* length_out /* n */,
                           uint8_t* rgba8_out /* or NULL */);
+
+/* The motion of moved items per pixel: what rr_accumulate_records takes as motion when items moved between the frame the history was
+ * rendered from and the current one (rr_scene_update_transforms, rr_scene_set_items), computed on the device from the records it holds.
+ * A call names n_moved items by index; for each, prev_trans + 16 k is the item's `trans` in the frame of the history, column-major.
+ * inv_i is the item's trans_inv as the handle holds it now -- the one the current frame was traced with, from rr_scene_create, the
+ * last rr_scene_update_transforms or rr_scene_set_items -- and id_i its object_id (ShapeBasics::id).
+ * EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE, as for rr_accumulate_records, whose row and dot these are
+ * (rustray_amd/temporal.py: motion_records follows this text in numpy and gives the same bits).
+ *   Per pixel p of the camera->width x camera->height frame:
+ *   1. world_p: step 2 of rr_accumulate_records, for every pixel whatever its record holds (a NaN it generates has no specified sign or
+ *      payload).  world_out[3p ..] (or NULL) gets it.
+ *   2. motion_p = (0, 0, 0) unless valid_p holds (depth and the three floats of the normal are finite, as rr_denoise_records defines it)
+ *      and records[p].object_id equals some id_i.  A miss has a NaN normal, so an item of id 0 does not drag the background.
+ *   3. Otherwise local_r = row(inv_i, r, (world_p, 1)), prev_r = row(prev_trans_i, r, (local, 1)), m_r = prev_r - world_p[r], r = 0..2;
+ *      if any m_r is not finite all three are 0.  motion_out[3p + r] = m_r.
+ *   The object id is the key, because a record holds no item index.  Two LISTED items with the same id: RR_ERR_INVALID_ARGUMENT naming
+ *   both entries.  THE CALLER'S CONTRACT: an unlisted item that shares a listed item's id moves with it (the reference hands out unique ids).
+ * rr_motion_records_device: records_dev n records (n = width * height), motion_out_dev 3n floats, world_out_dev 3n floats or NULL.  The
+ *   rules are rr_accumulate_records_device's: every device pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming the
+ *   argument); records_dev 16-byte aligned, the outputs 4-byte aligned; no overlap between an output and the input or between the two
+ *   outputs; the work (one copy of the table and one launch; with n_moved == 0 and no world_out one fill) is enqueued on `hip_stream` in
+ *   stream order and not waited for, and the records may come from that stream unsynchronised; the scene's lock;
+ *   RR_ERR_INVALID_ARGUMENT from on_pass of the same scene; RR_ERR_DEVICE on a scene that a failed update left broken; nothing of a
+ *   frame's state or statistics is touched; a scene edit or rr_scene_destroy waits for a call in flight.
+ *   item_index and prev_trans are HOST arrays, read before the call returns.  The table made from them (112 B per entry, sorted by id)
+ *   goes into a buffer of the handle, sized for the largest list so far and kept until rr_scene_destroy, through one of four pinned
+ *   copies of the same size, used in turn; a failed growth is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.  That buffer is
+ *   shared: a call on a different stream from the handle's last call first waits for that stream, as the query buffers do; a call on
+ *   the same stream waits only until the table copy of the fourth call before it has run.
+ *   Refusals: a NULL scene, camera, records or motion output; width or height 0 or above 65535; n_moved > the scene's item count; with
+ *   n_moved > 0 a NULL item_index or prev_trans; an item_index[k] >= the item count; a prev_trans that is not finite (naming the entry);
+ *   two listed items of one id: RR_ERR_INVALID_ARGUMENT, nothing launched.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED.
+ * rr_motion_records: the same on HOST pointers, the device form on the null stream behind staging copies the handle keeps until
+ * rr_scene_destroy (32 B per pixel for the records, 12 B for motion_out and 12 B for world_out where given); it returns with the
+ * outputs written. */
+int rr_motion_records_device(rr_scene* scene, const rr_camera* camera, const uint32_t* item_index /* HOST, n_moved */,
+                             const float* prev_trans /* HOST, n_moved * 16 */, uint32_t n_moved, const rr_radiance* records_dev /* n */,
+                             float* motion_out_dev /* 3n */, float* world_out_dev /* 3n, or NULL */, void* hip_stream);
+int rr_motion_records(rr_scene* scene, const rr_camera* camera, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved,
+                      const rr_radiance* records /* n */, float* motion_out /* 3n */, float* world_out /* 3n, or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

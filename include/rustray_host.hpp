@@ -754,6 +754,33 @@ public:
                                             out_dev, halves_out_dev, length_out_dev, rgba8_out_dev, hip_stream);
     }
 
+    // What motion() returns: width * height * 3 floats of motion, and of world points where asked for.
+    struct Motion {
+        std::vector<float> motion, world;
+        bool empty() const { return motion.empty(); }
+    };
+    // The motion of moved items per pixel of a frame of this camera (rr_motion_records), what accumulate() takes as `motion` when items
+    // moved since the history was rendered: `records` width * height records of the current frame; item_index[k] names a moved item and
+    // prev_trans + 16 k is its `trans` in the frame of the history, column-major (what rr_scene_update_transforms was given then).
+    // An empty Motion = refused or failed (rr_last_error() says why).
+    Motion motion(const rr_radiance* records, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved, bool want_world = false) const {
+        Motion out;
+        const size_t n = (size_t)camera.width * camera.height;
+        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
+        const rr_camera cam = camera.c_struct();
+        out.motion.assign(3 * n, 0.0f);
+        if (want_world) out.world.assign(3 * n, 0.0f);
+        if (rr_motion_records(scene->handle(), &cam, item_index, prev_trans, n_moved, records, out.motion.data(), want_world ? out.world.data() : nullptr) != RR_OK)
+            out = Motion();
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_motion_records_device): not waited for; item_index and prev_trans are host arrays
+    int motion_device(const uint32_t* item_index, const float* prev_trans, uint32_t n_moved, const rr_radiance* records_dev, float* motion_out_dev,
+                      float* world_out_dev, void* hip_stream) const {
+        const rr_camera cam = camera.c_struct();
+        return rr_motion_records_device(scene->handle(), &cam, item_index, prev_trans, n_moved, records_dev, motion_out_dev, world_out_dev, hip_stream);
+    }
+
     // The surface of the closest hits of a span of rays of the host's own (rr_surface_rays): Raytracing::trace(ray, false, false, depth)
     // and, at the hit, what get_color_depth_normal_id evaluates before its light loop (src/raytracing.rs:747-811, :928-933, :985-991) --
     // hit point, normals, uv, the three colours, alpha, reflectivity, roughness, ambient occlusion.  No config is used.  depth 1 = a

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -54,8 +54,8 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_probe.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_motion.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -171,6 +171,9 @@ def lib():
             L.rr_accumulate_default_params.argtypes = [C.POINTER(rr_accumulate_params)]
             L.rr_accumulate_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 10
             L.rr_accumulate_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 11
+        if hasattr(L, "rr_motion_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_motion_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_motion_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -803,6 +806,41 @@ class DeviceScene:
         _check(lib().rr_accumulate_records_device(self._h, C.byref(cam), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
                                                   _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr), _ptr(halves_out_ptr),
                                                   _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
+
+    # -- the motion of moved items per pixel -------------------------------------------
+    @staticmethod
+    def _moved(item_index, prev_trans):
+        """The host arrays of rr_motion_records: item indices (k,) uint32 and their previous transforms (k, 4, 4) in math layout ->
+        (k, uint32 array or None, column-major float32 array or None)."""
+        idx = np.ascontiguousarray(np.asarray(item_index if item_index is not None else [], np.int64).reshape(-1))
+        if len(idx) and (idx.min() < 0 or idx.max() > 0xffffffff):
+            raise ValueError("item indices must lie in 0 .. 2^32 - 1")
+        idx = idx.astype(np.uint32)
+        t = np.asarray(prev_trans if prev_trans is not None else np.zeros((0, 4, 4)), np.float32).reshape(-1, 4, 4)
+        if len(t) != len(idx):
+            raise ValueError(f"{len(idx)} moved items with {len(t)} previous transforms")
+        t = np.ascontiguousarray(np.transpose(t, (0, 2, 1)))
+        return len(idx), (idx if len(idx) else None), (t if len(idx) else None)
+
+    def motion_records(self, cam: rr_camera, item_index, prev_trans, records, world: bool = False):
+        """rr_motion_records: temporal.motion_records on the device, host arrays in and out.  item_index (k,) names the moved items,
+        prev_trans (k, 4, 4) is each one's `trans` in the frame the history was rendered from (math layout); records (n, 8) float32 of the
+        whole frame of `cam`.  Returns (motion (n, 3) float32, world (n, 3) float32 or None)."""
+        n = int(cam.width) * int(cam.height)
+        rec = np.ascontiguousarray(records, np.float32).reshape(n, 8)
+        k, idx, t = self._moved(item_index, prev_trans)
+        motion = np.zeros((n, 3), np.float32)
+        wout = np.zeros((n, 3), np.float32) if world else None
+        _check(lib().rr_motion_records(self._h, C.byref(cam), _data(idx), _data(t), C.c_uint32(k), _data(rec), _data(motion), _data(wout)))
+        return motion, wout
+
+    def motion_records_device(self, cam: rr_camera, item_index, prev_trans, records_ptr, motion_ptr, world_ptr=None, stream_ptr=None):
+        """rr_motion_records_device: item_index and prev_trans as motion_records takes them (host arrays, read before the call returns);
+        width * height 32-byte records in (16-byte aligned), width * height * 3 float32 of motion and optionally as many of world out,
+        all raw device pointers; enqueued on `stream_ptr`, not waited for."""
+        k, idx, t = self._moved(item_index, prev_trans)
+        _check(lib().rr_motion_records_device(self._h, C.byref(cam), _data(idx), _data(t), C.c_uint32(k), _ptr(records_ptr), _ptr(motion_ptr), _ptr(world_ptr),
+                                              _ptr(stream_ptr)))
 
     # -- the ray queries on device buffers, in stream order ---------------------------
     def surface_rays_device(self, origins_ptr, dirs_ptr, n: int, depth: int, out_ptr, stream_ptr=None):

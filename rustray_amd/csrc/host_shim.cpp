@@ -379,6 +379,24 @@ extern "C" int rh_accumulate_records_device(void* h, float fov, const float* eye
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).accumulate_device(*params, records_dev, halves_dev, history_dev, history_halves_dev, history_length_dev,
                                                                                      motion_dev, out_dev, halves_out_dev, length_out_dev, rgba8_dev, stream);
 }
+// Raytracing::motion: records = w * h, item_index = n_moved indices, prev_trans = n_moved * 16 floats (column-major); motion_out = w * h * 3
+// floats, world_out the same or NULL; returns 0, or -1 when the call was refused.
+// rh_motion_records_device: Raytracing::motion_device on device pointers and a stream; returns its rr_status.
+extern "C" int rh_motion_records(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                 uint32_t w, uint32_t hgt, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved, const rr_radiance* records,
+                                 float* motion_out, float* world_out) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    const Raytracing::Motion r = rt.motion(records, item_index, prev_trans, n_moved, world_out != nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(motion_out, r.motion.data(), r.motion.size() * 4);
+    if (world_out) std::memcpy(world_out, r.world.data(), r.world.size() * 4);
+    return 0;
+}
+extern "C" int rh_motion_records_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                        uint32_t w, uint32_t hgt, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved,
+                                        const rr_radiance* records_dev, float* motion_out_dev, float* world_out_dev, void* stream) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).motion_device(item_index, prev_trans, n_moved, records_dev, motion_out_dev, world_out_dev, stream);
+}
 // Raytracing::render_pixels called from on_pass of a progressive frame of the same scene: calls_refused[0] = the calls made there,
 // [1] = how many of them were refused; returns the frame's rr_status
 extern "C" int rh_render_pixels_from_on_pass(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,

@@ -1,7 +1,7 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
-// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, TemporalState, MultiState, FrameTiming
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, TemporalState, MotionState, MultiState, FrameTiming
 //         and rr_scene, which holds one of each; HC_* (the words of FrameState::h_count); check_intact.
-// Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h.
+// Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h, rr_motion.h (MoEntry).
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
 
 enum TimerKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_BINNING }; // what a timed launch ran (resolve_timers)
@@ -153,6 +153,26 @@ struct TemporalState {
     DevBuf stage[10];
 };
 
+// ---- rr_motion_records (rr_api_motion.h): grown on demand, never shrunk.  table: the call's table on the device, 112 B per entry of the
+// largest list so far; slot: the same in pinned memory, what the copy on the caller's stream reads after the call has returned, four of
+// them used in turn, each with the event behind its last copy (pending: there is one) -- a call waits for the copy of the fourth call
+// before it, which reads the slot it is about to write, and for nothing else.  stage: the host form's copies of records, motion_out and
+// world_out (32 + 12 + 12 B per pixel, the last only where the call has it).  Written by rr_api_motion.h.
+struct MotionSlot {
+    MoEntry* h_table = nullptr; size_t entries = 0;
+    hipEvent_t copied = nullptr; bool pending = false;
+};
+struct MotionState {
+    DevBuf table, stage[3];
+    MotionSlot slot[4]; uint32_t next = 0;
+    ~MotionState() {
+        for (MotionSlot& m : slot) {
+            if (m.copied) (void)hipEventDestroy(m.copied);
+            if (m.h_table) (void)hipHostFree(m.h_table);
+        }
+    }
+};
+
 // ---- rr_render_multi (rr_api_multi.h)
 struct MultiState {
     DevBuf part[4], cat[4]; // this device's compact buffers; on device slot 0 the concatenation of all
@@ -207,6 +227,7 @@ struct rr_scene {
     AdaptiveState adaptive;
     DenoiseState denoise;
     TemporalState temporal;
+    MotionState motion;
     MultiState multi;
     FrameTiming timing;
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's

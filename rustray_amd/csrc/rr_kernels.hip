@@ -25,6 +25,7 @@
 #include "rr_adaptive.h" // half_error and the 8x8-block order of a refinement list (kernels 5l .. 5p)
 #include "rr_denoise.h"  // the arithmetic of the a-trous filter (kernels 7a .. 7d)
 #include "rr_temporal.h" // the arithmetic of the temporal reprojection (kernel 7e)
+#include "rr_motion.h"   // the per-pixel motion of moved items and the call's table (kernel 7f)
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -1909,6 +1910,24 @@ __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_records(const TpFrame f
         }
         halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
     }
+}
+
+// 7f: the motion of moved items per pixel (rr_motion_records; rr_motion.h has the arithmetic, rustray_amd/temporal.py: motion_records is
+// the yardstick).  One pixel per lane, 32x8 tiles as 7a .. 7e; a record is two 16-byte loads, the answer three dword stores (six with
+// world_out); no LDS.  The table is sorted by id: a lane whose record is valid looks its id up by binary search and reads the 24 floats
+// of its entry.  The camera is the kernel argument f (of TpFrame only the two inverses and the frame's size are set).  n_moved == 0: the
+// table is never read (the call with world_out and nothing moved).
+__global__ __launch_bounds__(RR_BLOCK) void k_motion_records(const TpFrame f, const float4* __restrict__ records, const MoEntry* __restrict__ table,
+                                                             uint32_t n_moved, float* __restrict__ motion_out, float* __restrict__ world_out) {
+    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
+    if (x >= f.width || y >= f.height) return;
+    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    const float n_p[3] = {r1.x, r1.y, r1.z};
+    float world[3], m[3];
+    motion_pixel(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), table, n_moved, world, m);
+    motion_out[3ull * o] = m[0]; motion_out[3ull * o + 1] = m[1]; motion_out[3ull * o + 2] = m[2];
+    if (world_out) { world_out[3ull * o] = world[0]; world_out[3ull * o + 1] = world[1]; world_out[3ull * o + 2] = world[2]; }
 }
 
 // ---------------------------------------------------------------------------

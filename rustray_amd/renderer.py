@@ -199,20 +199,33 @@ class Raytracing:
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
     def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
-                        motion=None, sample_xy=None, rgba8: bool = False) -> dict:
+                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False) -> dict:
         """One frame of a frame-after-frame loop at `samples` (default: the config's; even) and `seed` (default: the config's): the frame
         in two halves, blended into the history `state` carries from the previous call (rr_accumulate_records, reprojected through the
         camera of that call), then the filter guided by the accumulated halves.  render_temporal_torch on this scene and camera: three
         calls on one stream, no host trip; the result holds torch tensors.  Move self.camera (or the scene) between calls; give `motion`
-        (n, 3) for what moved in the world (temporal.item_motion)."""
+        (n, 3) for what moved in the world, or track_items=True: the state notes `trans` of every item of self.flat_scene at each call,
+        the next call lists the items whose 16 floats differ bitwise, and rr_motion_records makes their motion on the device (a fourth
+        call on the same stream); a change of the item count or of any item's id resets the state, and so does a history from a call
+        without track_items."""
         from .temporal import previous_view
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
             cfg.samples = samples
         if seed is not None:
             cfg.seed = seed
+        moved = None
+        if track_items:
+            if motion is not None:
+                raise ValueError("give track_items=True (the motion is made on the device) or `motion`, not both")
+            items = self.flat_scene.items
+            moved = state.track([it.id for it in items], np.stack([np.asarray(it.trans, np.float32) for it in items]) if items else np.zeros((0, 4, 4), np.float32))
+            if moved is None:
+                moved = (np.zeros(0, np.uint32), np.zeros((0, 4, 4), np.float32))
+        else:
+            state.items = None
         return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera))
+                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -957,9 +970,27 @@ class TemporalState:
         self.current = None      # index of the set that holds the history, or None
         self.view = None
         self.frames = 0
+        self.items = None        # (ids (k,) uint32, trans (k, 4, 4) float32) of the items the history was rendered with (track)
 
     def reset(self):
-        self.current, self.view, self.frames = None, None, 0
+        self.current, self.view, self.frames, self.items = None, None, 0, None
+
+    def track(self, ids, trans):
+        """Takes note of the items the frame about to be rendered is traced with -- object ids (k,) and `trans` (k, 4, 4) in math
+        layout -- and returns what rr_motion_records needs against the history: (item_index (m,) uint32, prev_trans (m, 4, 4)) of the
+        items whose 16 floats differ bitwise from the ones noted at the call before; None when there is no history.  A change of
+        the item count or of any item's id resets the state first; so does a history whose items were not noted (a frame rendered
+        without tracking): nobody knows what moved since, and the frame starts anew rather than treat every item as static."""
+        ids = np.array(ids, np.uint32).reshape(-1)
+        trans = np.array(trans, np.float32).reshape(len(ids), 4, 4)
+        if (self.items is None and self.current is not None) or (self.items is not None and not np.array_equal(self.items[0], ids)):
+            self.reset()
+        moved = None
+        if self.items is not None and self.current is not None:
+            changed = np.flatnonzero((self.items[1].view(np.uint32) != trans.view(np.uint32)).reshape(len(ids), 16).any(1))
+            moved = (changed.astype(np.uint32), self.items[1][changed])
+        self.items = (ids, trans)
+        return moved
 
     def history(self):
         return self.sets[self.current] if self.current is not None else None
@@ -1017,30 +1048,59 @@ def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, 
     return result
 
 
+def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_trans, world: bool = False) -> dict:
+    """rr_motion_records_device on torch's current stream of the scene's device: `records` (n, 8) is a contiguous float32 CUDA tensor on
+    that device, n = cam.width * cam.height (anything else raises); item_index (k,) and prev_trans (k, 4, 4, math layout) are host arrays:
+    the moved items and their `trans` in the frame the history was rendered from.  Returns torch tensors, without a host copy and without
+    a synchronisation: dict(motion (n, 3), world (n, 3) or None) -- motion is what accumulate_torch takes."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    rec = _ray_tensor(device_scene, records, "records", shape_tail=(8,))
+    if int(rec.shape[0]) != n:
+        raise ValueError(f"records: {int(rec.shape[0])} entries for a frame of {int(cam.width)}x{int(cam.height)}")
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        motion = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        wout = torch.empty((n, 3), dtype=torch.float32, device=dev) if world else None
+        device_scene.motion_records_device(cam, item_index, prev_trans, rec.data_ptr(), motion.data_ptr(), wout.data_ptr() if world else None,
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    return dict(motion=motion, world=wout)
+
+
 def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
-                          sample_xy=None, rgba8: bool = False, view=None) -> dict:
+                          sample_xy=None, rgba8: bool = False, view=None, moved=None) -> dict:
     """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
     even), rr_accumulate_records_device against the history in `state`, rr_denoise_records_device with the accumulated halves -- three
     calls on torch's current stream, each reading what the one before wrote without a synchronisation.  params: a
     temporal.AccumulateParams whose scalars are used (its previous view is replaced by the state's); view: (world_to_clip, eye) of `cam`
-    for the NEXT call (default: temporal.previous_view(cam), the float64 inverse of its inverses).  Returns the dict of denoise_torch plus
-    noisy (n, 8) and halves (n, 2, 8), the frame's own records, accumulated (n, 8), accumulated_halves (n, 2, 8) and length (n,): what the
-    filter read, which `state` now holds as the history."""
+    for the NEXT call (default: temporal.previous_view(cam), the float64 inverse of its inverses).  moved: (item_index (k,), prev_trans
+    (k, 4, 4)) of the items that moved since the history was rendered and their `trans` then -- with a history and k > 0
+    rr_motion_records_device makes the motion on the same stream, the second of four calls; together with `motion` it is a ValueError.
+    Returns the dict of denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the frame's own records, accumulated (n, 8),
+    accumulated_halves (n, 2, 8) and length (n,): what the filter read, which `state` now holds as the history; and motion (n, 3) or None:
+    what the accumulation read."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
+    if moved is not None and motion is not None:
+        raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
     n = int(cam.width) * int(cam.height)
     hist = state.history()
     if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None):
+        items = state.items
         state.reset()
+        state.items = items      # (the items noted for this frame are those of the history it becomes)
         hist = None
     prm = dataclasses.replace(params) if params is not None else AccumulateParams()
     if hist is not None:
         prm.prev_world_to_clip, prm.prev_eye = state.view
     target = state.target(n, True, torch.device("cuda", device_scene.device))
+    if moved is not None and hist is not None and len(moved[0]):
+        motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
     acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
                            hist["length"] if hist else None, motion, prm, out=target)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], None, denoise_params, rgba8=rgba8)
     state.advance(target, view if view is not None else previous_view(cam))
-    return dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"])
+    return dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"],
+                motion=motion)

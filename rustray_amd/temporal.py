@@ -101,6 +101,39 @@ def item_motion(world, object_id, item_ids, prev_trans, cur_trans_inv) -> np.nda
     return out
 
 
+def motion_records(records, cam, item_ids, prev_trans, cur_trans_inv):
+    """rr_motion_records in numpy float32, the yardstick the kernel k_motion_records and the host loop over rustray_amd/csrc/rr_motion.h
+    equal bit for bit: records (n, 8) of the whole frame of `cam`; item_ids (k,) the object ids of the moved items (no two alike),
+    prev_trans (k, 4, 4) their `trans` in the frame of the history and cur_trans_inv (k, 4, 4) their `trans_inv` in the current one,
+    as written on paper.  -> (motion (n, 3), world (n, 3)): world is world_positions(records, cam); motion is 0 unless the record is
+    valid (depth and normal finite) and its object id is listed, and then row(prev_trans, r, (row(trans_inv, ., (world, 1)), 1)) -
+    world_r, all three 0 if one of them is not finite."""
+    world = world_positions(records, cam)
+    n = len(world)
+    rec = np.ascontiguousarray(records, F).reshape(n, 8)
+    ids = np.asarray(item_ids).astype(np.uint32).reshape(-1)
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError("two moved items have the same object id")
+    prev = np.asarray(prev_trans, F).reshape(len(ids), 4, 4)
+    inv = np.asarray(cur_trans_inv, F).reshape(len(ids), 4, 4)
+    valid = np.isfinite(rec[:, 3]) & np.isfinite(rec[:, 4:7]).all(-1)
+    ids_p = rec[:, 7].view(np.uint32)
+    motion = np.zeros((n, 3), F)
+    one = F(1)
+    with np.errstate(all="ignore"):
+        for ident, a, b in zip(ids, prev, inv):
+            at = np.flatnonzero(valid & (ids_p == ident))
+            if not len(at):
+                continue
+            w = world[at]
+            a_cm, b_cm = a.T.reshape(16), b.T.reshape(16)      # column-major, as the C arrays
+            local = [_row(b_cm, r, w[:, 0], w[:, 1], w[:, 2], one) for r in range(3)]
+            m = np.stack([_row(a_cm, r, local[0], local[1], local[2], one) - w[:, r] for r in range(3)], axis=-1).astype(F)
+            m[~np.isfinite(m).all(-1)] = F(0)
+            motion[at] = m
+    return motion, world
+
+
 def accumulate_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None) -> dict:
     """records (n, 8) float32 rr_radiance records of the whole frame of `cam` (a camera.Camera or an rr_camera) in row-major order;
     halves (n, 2, 8) or None; history (n, 8), history_halves (n, 2, 8) and history_length (n,): the previous call's records, halves and

@@ -14,7 +14,11 @@ next to the compulsory traffic of a call (with halves per pixel 96 B of records 
 the HBM rate the machine reaches with a float4 copy (6.29 TB/s), and rr_denoise_records_device (5 iterations, with halves) in the same
 rounds.
 
-usage: temporal_time.py [scene [width height samples]] [--out FILE]"""
+--motion: rr_motion_records_device in the same rounds, on the same records -- every item of the scene listed as moved (each one's
+previous transform shifted by 0.05), or one item, with and without world_out -- next to ITS compulsory traffic: 32 B of records read
+and 12 B of motion written per pixel, 12 more with world_out.  The yardstick is the static-view accumulation with halves of the same run.
+
+usage: temporal_time.py [scene [width height samples]] [--motion] [--out FILE]"""
 import math
 import os
 import sys
@@ -51,6 +55,9 @@ def main(argv):
         i = argv.index("--out")
         out_path = argv[i + 1]
         del argv[i:i + 2]
+    with_motion = "--motion" in argv
+    if with_motion:
+        argv.remove("--motion")
     scene = argv[1] if len(argv) > 1 else "spheres_room"
     w, h, samples = (int(argv[2]), int(argv[3]), int(argv[4])) if len(argv) > 4 else (1280, 720, 4)
     if capi.device_count() < 1:
@@ -93,6 +100,17 @@ def main(argv):
         arms = {(hv, view): call(hv, view) for hv in (True, False) for view in ("static", "moved")}
         arms[(True, "first frame")] = call(True, "static", first=True)
         arms["denoise"] = lambda: ds.denoise_records_device(w, h, rec.data_ptr(), halves.data_ptr(), None, out.data_ptr(), rgba.data_ptr(), None, dprm, stream)
+        if with_motion:
+            from tests.helpers import item_transforms
+            prev_trans = item_transforms(fs, dx=0.05)[0]
+            motion, world = torch.empty((n, 3), dtype=torch.float32, device="cuda"), torch.empty((n, 3), dtype=torch.float32, device="cuda")
+            index = np.arange(len(fs.items), dtype=np.uint32)
+
+            def motion_call(k, with_world):
+                return lambda: ds.motion_records_device(cam, index[:k], prev_trans[:k], rec.data_ptr(), motion.data_ptr(), world.data_ptr() if with_world else None, stream)
+            for k in (len(fs.items), 1):
+                for with_world in (False, True):
+                    arms[("motion", k, with_world)] = motion_call(k, with_world)
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
@@ -110,6 +128,13 @@ def main(argv):
         m, lo, hi = _median(v)
         if k == "denoise":
             emit(f"  rr_denoise_records_device, 5 iterations, with halves, rgba8_out, same rounds: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
+            continue
+        if k[0] == "motion":
+            per_pixel = 44 + (12 if k[2] else 0)
+            floor_ms = n * per_pixel / HBM_BYTES_PER_S * 1e3
+            base = _median(runs[(True, "static")])[0]
+            emit(f"  rr_motion_records_device, {k[1]} of {len(fs.items)} items moved, {'with' if k[2] else 'without'} world_out: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the "
+                 f"rate of its compulsory traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / base:.2f} x the static accumulation with halves")
             continue
         hv, view = k
         per_pixel = BYTES_PER_PIXEL[hv] - (100 if view == "first frame" else 0)      # (no history is read)
