@@ -56,7 +56,8 @@ extern "C" {
  * rr_accumulate_default_params, rr_accumulate_records and rr_accumulate_records_device (with rr_accumulate_params, a struct of its own)
  * came after those in the same way: a version-3 library may lack these three as well.
  * rr_motion_records and rr_motion_records_device came after those, without a struct of their own: a version-3 library may lack these two
- * as well. */
+ * as well.
+ * rr_surface_pixels and rr_surface_pixels_device came after those in the same way: a version-3 library may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -934,7 +935,7 @@ int rr_render_adaptive_prefix_device(rr_scene* scene, const rr_camera* camera, c
 /* A denoiser for the records the calls above produce: an edge-avoiding a-trous wavelet filter (5x5 B3 spline, step 1, 2, 4, ... per pass)
  * over a whole frame of rr_radiance records, on the device.  It is guided by the records' own object id, normal and depth; when the two
  * halves of every pixel are given (rr_render_pixel_parts at K = 2, rr_render_pixel_prefix with halves_out) also by the luminance variance
- * estimated from them, which costs no ray; with an albedo (rr_surface_rays_device over the pixel-centre rays: base_color) it runs on
+ * estimated from them, which costs no ray; with an albedo (rr_surface_pixels_device for the frame's camera: albedo_out) it runs on
  * albedo-demodulated colour.  Without halves the filter is geometry-only: it does not cross an id, normal or depth edge, but blurs
  * texture and shading inside a surface.
  * As for the half-buffer error above, EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE: no transcendentals (the weights are
@@ -1142,6 +1143,56 @@ int rr_motion_records_device(rr_scene* scene, const rr_camera* camera, const uin
                              float* motion_out_dev /* 3n */, float* world_out_dev /* 3n, or NULL */, void* hip_stream);
 int rr_motion_records(rr_scene* scene, const rr_camera* camera, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved,
                       const rr_radiance* records /* n */, float* motion_out /* 3n */, float* world_out /* 3n, or NULL */);
+
+/* The camera's surface per pixel: rr_surface_rays for the pinhole ray through the centre of each pixel, made on the device from the
+ * camera -- the G-buffer of the frame, and the albedo rr_denoise_records takes.  As rr_render_pixels is the frame's camera per pixel for
+ * radiance, this is the frame's camera per pixel for the surface.  There is no rr_config: no depth of field, no sub-sample table, no
+ * generator; the call is deterministic, as rr_surface_rays is.
+ * THE RAY OF A PIXEL.  The ray of pixel (x, y) of the camera->width x camera->height frame (w, h as floats) passes through the pixel's
+ *   centre, the screen point rr_render_pixels gives it: cx = ((x + 0.5f) / w) * 2 - 1, cy = 1 - ((y + 0.5f) / h) * 2.  With
+ *   row(m, r, v) = ((m[r]*v.x + m[4+r]*v.y) + m[8+r]*v.z) + m[12+r]*v.w over a column-major matrix:
+ *     pp_r = row(projection_inverse, r, (cx, cy, -1, 1)),  origin_r = row(view_inverse, r, (pp, 1)),  u_r = row(view_inverse, r, (pp, 0)),
+ *     direction_r = u_r / sqrtf((u.x*u.x + u.y*u.y) + u.z*u.z),  r = 0 .. 2.
+ *   EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE, without contraction: these are bit for bit the o and d of step 2 of
+ *   rr_accumulate_records (one function serves both), and rustray_amd/pixel_rays.py: pixel_rays follows this text in numpy and gives the
+ *   same bits.
+ *   out[i] (or NULL): byte for byte the record rr_surface_rays writes for that ray at depth 1 under the same handle state; for a miss
+ *   {0, 0xffffffff, 0, 0} and 112 zero bytes.  position is origin + direction * distance, which makes it bit for bit the world point
+ *   step 2 of rr_accumulate_records forms from a record whose depth is `distance`.
+ *   albedo_out[3i .. 3i + 2] (or NULL): the bits of out[i].base_color[0 .. 2]; three zeros for a miss (the denoiser leaves a channel
+ *   whose albedo is 0 alone).  This is the array rr_denoise_records(_device) takes as `albedo`.  It is the albedo of the FIRST hit of
+ *   the pixel's centre: not seen through a mirror or glass, not averaged over the frame's sub-samples.
+ *   At least one of the two outputs is required: both NULL is RR_ERR_INVALID_ARGUMENT.
+ *   The list form and the NULL list are rr_render_pixels': pixel_xy NULL needs n_pixels == width * height, and pixel (x, y) goes to index
+ *   y * width + x; else entry i = x | y << 16 answers index i, duplicates and any order allowed, and an entry outside the frame is
+ *   RR_ERR_INVALID_ARGUMENT naming its index, with nothing written.  n_pixels == 0 returns RR_OK and touches nothing;
+ *   n_pixels > 0x7fffff00: RR_ERR_UNSUPPORTED.  The camera checks are rr_render_pixels' (width or height 0 or above 65535, a matrix that
+ *   is not finite: RR_ERR_INVALID_ARGUMENT).  The checks come in this order: a NULL scene or camera; both outputs NULL; the camera; the
+ *   pixel limit; n_pixels == 0 (RR_OK); n_pixels against the frame without a list; (device form) alignment, then overlap; the scene; the
+ *   pointers; the list.
+ *   It is a frame call in the sense of rr_surface_rays: the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene;
+ *   RR_ERR_DEVICE on a scene that a failed update left broken; nothing of a frame's accumulators, counters or rr_scene_last_stats is
+ *   touched, and the frames before and after are bit-identical.
+ * rr_surface_pixels_device: pixel_xy_dev n_pixels entries or NULL, out_dev n_pixels records or NULL, albedo_out_dev 3 * n_pixels floats
+ *   or NULL, all memory the scene's device can address: every pointer is classified before any launch, as rr_trace_rays_device does it
+ *   (RR_ERR_INVALID_ARGUMENT naming the argument).  out_dev 16-byte aligned, albedo_out_dev and pixel_xy_dev 4-byte aligned; any overlap
+ *   of the two outputs with each other or with the list is refused.  The work is enqueued on `hip_stream` in stream order, and the list
+ *   may come from that stream unsynchronised.  The rays' origins are a function of the camera alone, so the reach the top level must be
+ *   padded for is known on the host before the first launch (each origin component is affine in (cx, cy): its largest magnitude lies at
+ *   one of the four corner pixels, evaluated in double with the margin 1.001 and the binary32 rounding added).  THE WHOLE-FRAME FORM
+ *   THEREFORE WAITS FOR NOTHING: it enqueues and returns.  (Two exceptions, both one-time: a camera farther from the scene than any
+ *   call before rebuilds the top level, which waits for the device; a frame larger than any query before grows the working memory.)
+ *   The list form waits once for 4 bytes, the first index outside the frame, as rr_render_pixels_device does.  A call that ends early
+ *   leaves the stream idle.  Working memory: the handle's query buffers, shared with the ray queries and kept until rr_scene_destroy
+ *   (56 B per pixel of the largest query so far, 4 B more for the whole-frame form); a call on a different stream from the handle's last
+ *   call first waits for that stream.  A scene edit or rr_scene_destroy waits for a call in flight.
+ * rr_surface_pixels: the same on HOST pointers, the device form on the null stream behind staging copies in buffers of the call (4 B of
+ *   list, 128 B and 12 B of answers per pixel, each only where the call has it), freed on return; the list is checked before anything
+ *   is uploaded, and the call returns with the outputs written. */
+int rr_surface_pixels(rr_scene* scene, const rr_camera* camera, const uint32_t* pixel_xy /* n_pixels, or NULL */, uint32_t n_pixels,
+                      rr_surface_hit* out /* n_pixels, or NULL */, float* albedo_out /* n_pixels * 3, or NULL */);
+int rr_surface_pixels_device(rr_scene* scene, const rr_camera* camera, const uint32_t* pixel_xy_dev /* n_pixels, or NULL */, uint32_t n_pixels,
+                             rr_surface_hit* out_dev /* n_pixels, or NULL */, float* albedo_out_dev /* n_pixels * 3, or NULL */, void* hip_stream);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

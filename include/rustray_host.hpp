@@ -702,13 +702,53 @@ public:
     }
     // The whole frame in two halves (render_pixel_parts at n_parts = 2; config.samples even) followed by the filter guided by their
     // variance.  noisy (or nullptr) gets the records before the filter.  An empty vector = refused or failed.
+    // with_albedo: one rr_surface_pixels call between the two makes this camera's albedo() and the filter runs on albedo-demodulated colour.
     std::vector<rr_radiance> render_denoised(const rr_denoise_params* params = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
-                                             std::vector<rr_radiance>* noisy = nullptr) const {
+                                             std::vector<rr_radiance>* noisy = nullptr, bool with_albedo = false) const {
         std::vector<rr_radiance> halves;
         const std::vector<rr_radiance> records = render_pixel_parts(nullptr, 0, 2, &halves);
         if (records.empty()) return records;
         if (noisy) *noisy = records;
-        return denoise(records.data(), halves.data(), nullptr, params, nullptr, rgba8);
+        std::vector<float> guide;
+        if (with_albedo) {
+            guide = albedo();
+            if (guide.empty()) return std::vector<rr_radiance>();
+        }
+        return denoise(records.data(), halves.data(), with_albedo ? guide.data() : nullptr, params, nullptr, rgba8);
+    }
+
+    // The G-buffer of this camera (rr_surface_pixels): the rr_surface_hit record of the pinhole ray through the centre of each pixel --
+    // xy[i] = x | y << 16, n_pixels entries, or xy nullptr for the whole frame in row-major order -- byte for byte what surface() gives
+    // for that ray at depth 1.  albedo_out (or nullptr) gets 3 floats per pixel, the records' base_color and 0 for a miss: what
+    // denoise() takes as `albedo`.  An empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_surface_hit> surface_pixels(const uint32_t* xy = nullptr, size_t n_pixels = 0, std::vector<float>* albedo_out = nullptr) const {
+        std::vector<rr_surface_hit> out;
+        const size_t n = xy ? n_pixels : (size_t)camera.width * camera.height;
+        if (n == 0 || n > 0x7fffff00u) return out;
+        const rr_camera cam = camera.c_struct();
+        out.resize(n);
+        if (albedo_out) albedo_out->assign(3 * n, 0.0f);
+        if (rr_surface_pixels(scene->handle(), &cam, xy, (uint32_t)n, out.data(), albedo_out ? albedo_out->data() : nullptr) != RR_OK) {
+            out.clear();
+            if (albedo_out) albedo_out->clear();
+        }
+        return out;
+    }
+    // the albedo of the whole frame alone: width * height * 3 floats in row-major order; empty = refused or failed
+    std::vector<float> albedo() const {
+        std::vector<float> out;
+        const size_t n = (size_t)camera.width * camera.height;
+        if (n == 0 || n > 0x7fffff00u) return out;
+        const rr_camera cam = camera.c_struct();
+        out.assign(3 * n, 0.0f);
+        if (rr_surface_pixels(scene->handle(), &cam, nullptr, (uint32_t)n, nullptr, out.data()) != RR_OK) out.clear();
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_surface_pixels_device): xy_dev nullptr = the whole frame (n_pixels = width * height),
+    // which is enqueued and not waited for; out_dev or albedo_out_dev may be nullptr, not both
+    int surface_pixels_device(const uint32_t* xy_dev, uint32_t n_pixels, rr_surface_hit* out_dev, float* albedo_out_dev, void* hip_stream) const {
+        const rr_camera cam = camera.c_struct();
+        return rr_surface_pixels_device(scene->handle(), &cam, xy_dev, n_pixels, out_dev, albedo_out_dev, hip_stream);
     }
 
     // What accumulate() returns and takes back as the history of the next call: the accumulated records, halves and lengths.

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -54,7 +54,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_motion.h", "rr_query_pointers.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -174,6 +174,9 @@ def lib():
         if hasattr(L, "rr_motion_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
             L.rr_motion_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rr_motion_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_surface_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_surface_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rr_surface_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -574,6 +577,27 @@ class DeviceScene:
         out = np.zeros(max(n, 1), SURFACE_HIT_DTYPE)
         _check(lib().rr_surface_rays(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(depth), out.ctypes.data_as(C.c_void_p)))
         return out[:n]
+
+    def surface_pixels(self, cam: rr_camera, pixels=None, records: bool = True, albedo: bool = True):
+        """rr_surface_pixels: rr_surface_rays for the pixel-centre rays of `cam` (pixel_rays.pixel_rays), made on the device, for the pixels
+        named in `pixels` (as render_pixels takes them) or for every pixel of the frame in row-major order (None).  Returns the structured
+        array of n rr_surface_hit records (flat.SURFACE_HIT_DTYPE), the (n, 3) float32 albedo rr_denoise_records takes (the records'
+        base_color, 0 for a miss), or with both the tuple (records, albedo)."""
+        if not records and not albedo:
+            raise ValueError("surface_pixels: neither records nor albedo")
+        n, xy, xy_p = _pixel_list(cam, pixels)
+        out = np.zeros(max(n, 1), SURFACE_HIT_DTYPE) if records else None
+        alb = np.zeros((max(n, 1), 3), np.float32) if albedo else None
+        _check(lib().rr_surface_pixels(self._h, C.byref(cam), xy_p, C.c_uint32(n), _data(out), _data(alb)))
+        if records and albedo:
+            return out[:n], alb[:n]
+        return out[:n] if records else alb[:n]
+
+    def surface_pixels_device(self, cam: rr_camera, pixel_xy_ptr, n: int, out_ptr, albedo_ptr, stream_ptr=None):
+        """rr_surface_pixels_device: n uint32 entries x | y << 16 (None = the whole frame, n = width * height), n 128-byte rr_surface_hit
+        records (16-byte aligned, or None) and n x 3 float32 of albedo (or None), all raw device pointers; enqueued on `stream_ptr`.  The
+        whole-frame form is not waited for."""
+        _check(lib().rr_surface_pixels_device(self._h, C.byref(cam), _ptr(pixel_xy_ptr), C.c_uint32(n), _ptr(out_ptr), _ptr(albedo_ptr), _ptr(stream_ptr)))
 
     def render_pixels(self, cam: rr_camera, cfg: rr_config, pixels=None, sample_xy=None, rgba8: bool = False, cancel=None):
         """rr_render_pixels: Raytracing::render(x, y) before its clamp, for the pixels named in `pixels` -- an (n, 2) integer array of

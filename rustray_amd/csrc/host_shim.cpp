@@ -346,6 +346,38 @@ extern "C" int rh_render_denoised(void* h, float fov, const float* eye, const fl
     if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
     return 0;
 }
+// rh_render_denoised_albedo: Raytracing::render_denoised with its albedo argument; albedo_out = w * h * 3 floats of Raytracing::albedo or NULL
+extern "C" int rh_render_denoised_albedo(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                         uint32_t w, uint32_t hgt, const rr_denoise_params* params, int with_albedo, rr_radiance* out, rr_radiance* noisy, float* albedo_out) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> raw;
+    const std::vector<rr_radiance> r = rt.render_denoised(params, nullptr, noisy ? &raw : nullptr, with_albedo != 0);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
+    if (albedo_out) {
+        const std::vector<float> a = rt.albedo();
+        if (a.empty()) return -1;
+        std::memcpy(albedo_out, a.data(), a.size() * 4);
+    }
+    return 0;
+}
+// Raytracing::surface_pixels: xy = n entries or NULL (the whole frame, n = w * h); out = n records, albedo_out = n * 3 floats or NULL;
+// returns 0, or -1 when the call was refused.  rh_surface_pixels_device: Raytracing::surface_pixels_device; returns its rr_status.
+extern "C" int rh_surface_pixels(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                 uint32_t w, uint32_t hgt, const uint32_t* xy, uint32_t n, rr_surface_hit* out, float* albedo_out) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<float> a;
+    const std::vector<rr_surface_hit> r = rt.surface_pixels(xy, n, albedo_out ? &a : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_surface_hit));
+    if (albedo_out) std::memcpy(albedo_out, a.data(), a.size() * 4);
+    return 0;
+}
+extern "C" int rh_surface_pixels_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                        uint32_t w, uint32_t hgt, const uint32_t* xy_dev, uint32_t n, rr_surface_hit* out_dev, float* albedo_out_dev, void* stream) {
+    return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).surface_pixels_device(xy_dev, n, out_dev, albedo_out_dev, stream);
+}
 // Raytracing::accumulate: records = w * h, halves = w * h * 2 or NULL, history / history_halves / history_length = the previous call's
 // out / halves_out / length_out or all NULL (the first frame), params or NULL for the defaults, motion = w * h * 3 floats or NULL; out,
 // halves_out (with halves), length_out, rgba8 or NULL; returns 0, or -1 when the call was refused.

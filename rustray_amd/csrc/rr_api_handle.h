@@ -120,7 +120,8 @@ struct FrameState {
 // call has returned belongs to the handle, grows on demand and is never shrunk.  rec: the packed records r0, r1, r2 and the walks'
 // raw hits (RAY_RECORD_BYTES: 16 + 16 + 8 + 16 = 56 B per ray of the largest closest-hit or shadow query, host or device form; a shadow
 // query uses 48 of them); words: QW_* (rr_api_query.h); ids: the stream ids 0 .. n - 1 of rr_shade_rays_device without the caller's
-// (4 B per result).  Written by rr_api_query.h.
+// (4 B per result), or the slot -> output index map of a whole-frame rr_surface_pixels (4 B per pixel).  Written by rr_api_query.h and
+// rr_api_surface_pixels.h.
 struct QueryState {
     DevBuf rec[4], words, ids;
 };

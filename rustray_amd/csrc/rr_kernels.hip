@@ -1601,6 +1601,120 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_hits(DSceneView sc, const 
     }
 }
 
+// ---------------------------------------------------------------------------
+// kernels 5v, 5w: the camera's surface per pixel (rr_surface_pixels): the rays of 5d made on the device from the camera, the
+// closest-hit walk on them unchanged, and the ending of 5h with a target per record
+// ---------------------------------------------------------------------------
+// the camera's two inverses, a kernel argument: 32 floats in SGPRs, as TpFrame in kernels 7e and 7f
+struct PixelCam { float proj_inv[16], view_inv[16]; };
+
+// 5v: the records k_pack_rays<false> would have written for the pinhole rays through pixel centres (pixel_ray, rr_pixel_list.h) at depth 1:
+// r0[i] = (origin, 1), r1[i] = (direction, 0), r2[i] = (1 << 16, 1), *q_count = n.  Ray i is the ray of list entry i (pixel_xy, n entries;
+// *first_bad: the first index whose pixel lies outside the frame, one atomicMin per wave that has one to report, the host presets
+// 0xffffffff and refuses the call before a walk -- the ray of such an entry is plain arithmetic) or, without a list, of slot i of the whole
+// frame in the frame's own slot order (pixel_of_block_slot, n = width * height: a wave's 64 rays are one 8x8 block of the screen), and then
+// target[i] = y * width + x: where the ending puts its record.  One ray per lane, grid-stride; every store of a wave is consecutive.
+__global__ __launch_bounds__(RR_BLOCK) void k_pixel_rays(const PixelCam cam, uint32_t width, uint32_t height, const uint32_t* __restrict__ pixel_xy, uint32_t n,
+                                                         float4* __restrict__ r0, float4* __restrict__ r1, uint2* __restrict__ r2, uint32_t* __restrict__ q_count,
+                                                         uint32_t* __restrict__ target, uint32_t* __restrict__ first_bad) {
+    const float w = (float)width, h = (float)height;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *q_count = n;
+    uint32_t bad = 0xffffffffu;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * RR_BLOCK + threadIdx.x; j < n; j += (unsigned long long)gridDim.x * RR_BLOCK) {
+        const uint32_t i = (uint32_t)j;
+        uint32_t xy;
+        if (pixel_xy) {
+            xy = pixel_xy[i];
+            if (!pixel_in_frame(xy, width, height)) bad = min(bad, i);
+        } else {
+            xy = pixel_of_block_slot(i, width, height);
+            target[i] = (xy >> 16) * width + (xy & 0xffffu);
+        }
+        float o[3], d[3];
+        pixel_ray(cam.proj_inv, cam.view_inv, xy, w, h, o, d);
+        r0[i] = make_float4(o[0], o[1], o[2], 1.0f);
+        r1[i] = make_float4(d[0], d[1], d[2], 0.0f);
+        r2[i] = make_uint2(1u << 16, 1u);
+    }
+    if (pixel_xy) { // (kernel-uniform)
+#pragma unroll
+        for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
+        if ((threadIdx.x & (RR_WAVE - 1)) == 0u && bad != 0xffffffffu) atomicMin(first_bad, bad);
+    }
+}
+
+// 5w: the ending of 5h for these rays.  Ray i answers record target[i] (target == NULL: record i): with RECORDS its rr_surface_hit goes to
+// out[target[i]], with ALBEDO the bits of its base_color[0 .. 2] to albedo[3 target[i] ..] -- three zeros for a miss.  The evaluation is
+// k_surface_hits': surface_at in full in every build, so the albedo has the record's bits by construction (in the albedo-only build the
+// compiler drops what nothing stores: the normal map, the roughness, the other colours).  Records leave through the LDS image and swizzle of
+// 5h: the eight lanes that hold the eight 16-byte units of one record store its whole 128-byte line at the record's own address, so a wave
+// store instruction covers eight whole lines wherever the targets lie.  The albedo leaves lane-strided through a 3 KB image as 5f's words
+// do: consecutive dwords for a list, runs of 24 dwords (a row of an 8x8 block) for a whole frame.
+//   a miss, or an item index out of range: {0, 0xffffffff, 0, 0} and 112 zero bytes; albedo 0, 0, 0
+template <bool RECORDS, bool ALBEDO>
+__global__ __launch_bounds__(RR_BLOCK) void k_surface_pixels(DSceneView sc, const float4* __restrict__ r0, const float4* __restrict__ r1, const uint4* __restrict__ hits,
+                                                             uint32_t n, const uint32_t* __restrict__ target, uint4* __restrict__ out, uint32_t* __restrict__ albedo) {
+    __shared__ uint4 s_rows[RECORDS ? 8 * RR_BLOCK : 1];
+    __shared__ uint32_t s_albedo[ALBEDO ? 3 * RR_BLOCK : 1];
+    __shared__ uint32_t s_target[RR_BLOCK];
+    __shared__ float s_lut[256]; // the u8 -> f32 table next to the lanes, as in k_shade
+    const uint32_t tid = threadIdx.x;
+    s_lut[tid] = c_u8_to_f32[tid];
+    __syncthreads();
+    for (unsigned long long base = (unsigned long long)blockIdx.x * RR_BLOCK; base < n; base += (unsigned long long)gridDim.x * RR_BLOCK) { // block-uniform
+        const unsigned long long i = base + tid;
+        const uint32_t in_round = (uint32_t)(n - base < RR_BLOCK ? n - base : RR_BLOCK); // rays of this round
+        if (i < n) {
+            const uint4 h = hits[i];
+            uint4 row[8];
+            row[0] = make_uint4(0u, 0xffffffffu, 0u, 0u);
+#pragma unroll
+            for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
+            if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
+                const DItem& it = rr_global(sc.items)[h.y];
+                const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
+                const float4 a = r0[i], b = r1[i];
+                const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);
+                row[4] = make_uint4(__float_as_uint(s.base_color.x), __float_as_uint(s.base_color.y), __float_as_uint(s.base_color.z), __float_as_uint(s.base_color.w));
+                if (RECORDS) {
+                    const uint32_t face = reference_face_id(&it, rr_global(sc.trix), h.z);
+                    row[0] = make_uint4(1u, h.y, it.id, face);
+                    row[1] = make_uint4(__float_as_uint(s.position.x), __float_as_uint(s.position.y), __float_as_uint(s.position.z), h.x);
+                    row[2] = make_uint4(__float_as_uint(s.normal.x), __float_as_uint(s.normal.y), __float_as_uint(s.normal.z), (uint32_t)it.material);
+                    row[3] = make_uint4(__float_as_uint(s.shading_normal.x), __float_as_uint(s.shading_normal.y), __float_as_uint(s.shading_normal.z), s.has_uv ? 1u : 0u);
+                    row[5] = make_uint4(__float_as_uint(s.ambient_color.x), __float_as_uint(s.ambient_color.y), __float_as_uint(s.ambient_color.z), __float_as_uint(s.alpha));
+                    row[6] = make_uint4(__float_as_uint(s.specular_color.x), __float_as_uint(s.specular_color.y), __float_as_uint(s.specular_color.z), __float_as_uint(s.reflectivity));
+                    row[7] = make_uint4(__float_as_uint(s.uv.x), __float_as_uint(s.uv.y), __float_as_uint(s.roughness), __float_as_uint(s.ambient_occlusion));
+                }
+            }
+            if (RECORDS) {
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; k++) s_rows[8u * tid + (k ^ (tid & 7u))] = row[k];
+            }
+            if (ALBEDO) { s_albedo[3u * tid] = row[4].x; s_albedo[3u * tid + 1u] = row[4].y; s_albedo[3u * tid + 2u] = row[4].z; }
+            s_target[tid] = target ? target[i] : (uint32_t)i;
+        }
+        __syncthreads();
+        if (RECORDS) {
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; k++) {
+                const uint32_t u = k * RR_BLOCK + tid; // unit of the image: row u % 8 of ray u / 8 of this round
+                const uint32_t t = u >> 3;
+                if (t < in_round) out[8ull * s_target[t] + (u & 7u)] = s_rows[8u * t + ((u & 7u) ^ (t & 7u))];
+            }
+        }
+        if (ALBEDO) {
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; k++) {
+                const uint32_t word = k * RR_BLOCK + tid; // word of the image: channel word % 3 of ray word / 3 of this round
+                const uint32_t t = word / 3u;
+                if (t < in_round) albedo[3ull * s_target[t] + (word - 3u * t)] = s_albedo[word];
+            }
+        }
+        __syncthreads(); // the next round overwrites the images
+    }
+}
+
 // 5g: stream ids 0 .. n - 1 (rr_shade_rays_device without the caller's)
 __global__ __launch_bounds__(RR_BLOCK) void k_iota(uint32_t* __restrict__ ids, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

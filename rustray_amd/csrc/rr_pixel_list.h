@@ -3,9 +3,15 @@
 // with it before anything is uploaded, k_pixel_slots (rr_kernels.hip) applies the same two functions per lane to a list on the device,
 // and primary_slot_centres (rr_primary_setup.h) forms a region's centres through pixel_centre, so a pixel has ONE centre whichever way
 // it became a slot; tests/native/pixel_list_test.cpp checks all of it on the CPU.
+// Then the pinhole ray through that centre, the one expression of it that host and device share (pixel_ray: rr_surface_pixels' k_pixel_rays,
+// and temporal_world of rr_temporal.h for rr_accumulate_records and rr_motion_records; the numpy yardstick is rustray_amd/pixel_rays.py),
+// the whole frame's own slot order in closed form (pixel_of_block_slot) and, host only, a bound on the origins of a whole frame of such rays
+// from the camera alone (pixel_ray_reach: what ensure_tlas_reach needs before the walk of rr_surface_pixels is enqueued);
+// tests/native/pixel_rays_test.cpp runs these as a host program.
 //
 // pixel_centre is the IEEE binary32 expression of the reference's `render` (src/raytracing.rs:319-331), in its order, and must be
-// compiled without contraction (-ffp-contract=off, as the library is): host and device then give the same bits.
+// compiled without contraction (-ffp-contract=off, as the library is): host and device then give the same bits.  So is pixel_ray: every
+// step exact in binary32 in the order written (products, sums, one correctly rounded division or square root at a time).
 #pragma once
 
 #ifndef RR_SETUP_HD // (rr_primary_setup.h defines the same)
@@ -32,4 +38,70 @@ RR_SETUP_HD void pixel_centre(unsigned int xy, float w, float h, float* cx, floa
     const float x_f = (float)(xy & 0xffffu), y_f = (float)(xy >> 16);
     *cx = ((x_f + 0.5f) / w) * 2.0f - 1.0f;
     *cy = 1.0f - ((y_f + 0.5f) / h) * 2.0f;
+}
+
+// row r of a column-major 4x4 matrix times (x, y, z, w)
+RR_SETUP_HD float temporal_row(const float* m, int r, float x, float y, float z, float w) { return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w; }
+RR_SETUP_HD float temporal_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// The ray of pixel xy = x | y << 16 of a frame of w x h pixels (the sizes as floats): o = view_inv * (proj_inv * (cx, cy, -1, 1)).xyz1 with
+// (cx, cy) = pixel_centre, d = the same product with w = 0, divided by its length.  proj_inv, view_inv: rr_camera's, column-major.
+// A NaN or an infinity in a matrix passes through; nothing traps.
+RR_SETUP_HD void pixel_ray(const float* proj_inv, const float* view_inv, unsigned int xy, float w, float h, float* o, float* d) {
+    float cx, cy;
+    pixel_centre(xy, w, h, &cx, &cy);
+    float pp[3], u[3];
+    for (int r = 0; r < 3; r++) pp[r] = temporal_row(proj_inv, r, cx, cy, -1.0f, 1.0f);
+    for (int r = 0; r < 3; r++) {
+        o[r] = temporal_row(view_inv, r, pp[0], pp[1], pp[2], 1.0f);
+        u[r] = temporal_row(view_inv, r, pp[0], pp[1], pp[2], 0.0f);
+    }
+    const float len = __builtin_sqrtf(temporal_dot(u, u));
+    for (int r = 0; r < 3; r++) d[r] = u[r] / len;
+}
+
+// The pixel (x | y << 16) of slot j < width * height of a whole frame in the frame's own slot order (fill_region for rr_render's 8x8 tiles:
+// the blocks row-major, row-major inside a block, a block at the right or lower border clipped to the frame and holding no empty
+// position), so that the 64 rays of a wave are screen neighbours.  Every row of blocks above the last is whole (8 * width pixels).
+RR_SETUP_HD unsigned int pixel_of_block_slot(unsigned int j, unsigned int width, unsigned int height) {
+    const unsigned int by = j / (8u * width), in_row = j - by * 8u * width;
+    const unsigned int bh = height - 8u * by < 8u ? height - 8u * by : 8u;
+    const unsigned int bx = in_row / (8u * bh), in_block = in_row - bx * 8u * bh;
+    const unsigned int bw = width - 8u * bx < 8u ? width - 8u * bx : 8u;
+    const unsigned int y = in_block / bw, x = in_block - y * bw;
+    return (8u * bx + x) | ((8u * by + y) << 16);
+}
+
+// reach[c] >= |o[c]| of every finite origin that pixel_ray gives for a pixel of the width x height frame.  Each component of o is affine in
+// (cx, cy), so the exact value is largest in magnitude at one of the four corner pixels: those are evaluated in double from the binary32
+// centres, with the margin 1.001 that await_reach applies to origins read back from the device.  The binary32 evaluation differs from the
+// exact one by its rounding: eight roundings lie between a matrix entry and a component (four per row, two rows), each at most
+// 2^-24 of the sum of the terms' magnitudes, which |cx|, |cy| <= 1 bound from the matrices alone; 16 x 2^-24 of that sum is added.
+// A bound that is not finite (a camera the entry points refuse) is returned as it is.
+inline void pixel_ray_reach(const float* proj_inv, const float* view_inv, unsigned int width, unsigned int height, double* reach) {
+    const float w = (float)width, h = (float)height;
+    const unsigned int corner[4] = {0u, width - 1u, (height - 1u) << 16, (width - 1u) | ((height - 1u) << 16)};
+    double mag[3]; // sum of the magnitudes of pp[k]'s terms
+    for (int k = 0; k < 3; k++) {
+        mag[k] = 0.0;
+        for (int j = 0; j < 4; j++) mag[k] += __builtin_fabs((double)proj_inv[4 * j + k]);
+    }
+    for (int c = 0; c < 3; c++) {
+        double exact = 0.0, terms = __builtin_fabs((double)view_inv[12 + c]);
+        for (int k = 0; k < 3; k++) terms += __builtin_fabs((double)view_inv[4 * k + c]) * mag[k];
+        for (int q = 0; q < 4; q++) {
+            float cx, cy;
+            pixel_centre(corner[q], w, h, &cx, &cy);
+            const double v[4] = {(double)cx, (double)cy, -1.0, 1.0};
+            double o = (double)view_inv[12 + c];
+            for (int k = 0; k < 3; k++) {
+                double pp = 0.0;
+                for (int j = 0; j < 4; j++) pp += (double)proj_inv[4 * j + k] * v[j];
+                o += (double)view_inv[4 * k + c] * pp;
+            }
+            const double a = __builtin_fabs(o);
+            if (!(a <= exact)) exact = a; // (a NaN is kept)
+        }
+        reach[c] = exact * 1.001 + terms * (16.0 / 16777216.0);
+    }
 }

@@ -9,7 +9,7 @@
 // are no transcendentals.
 #pragma once
 #include "rr_denoise.h"    // denoise_is_finite, denoise_flags (DN_FIN, DN_VALID), DN_EPS, DN_TILE_W, DN_TILE_H
-#include "rr_pixel_list.h" // pixel_centre
+#include "rr_pixel_list.h" // pixel_ray (and pixel_centre behind it), temporal_row, temporal_dot
 
 #define TP_MIN_WEIGHT 0.015625f // 2^-6: a pixel whose taken taps weigh less has no history
 
@@ -34,22 +34,11 @@ struct TpMix {
     float length, a;          // N = min(len + 1, max_history) and 1 / N
 };
 
-// row r of a column-major 4x4 matrix times (x, y, z, w)
-RR_SETUP_HD float temporal_row(const float* m, int r, float x, float y, float z, float w) { return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w; }
-RR_SETUP_HD float temporal_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
 // world = o + d * depth: o and d are the pinhole ray through the centre of pixel (x, y), d normalised
 RR_SETUP_HD void temporal_world(const TpFrame& f, unsigned int x, unsigned int y, float depth, float* world) {
-    float cx, cy;
-    pixel_centre(x | (y << 16), f.w, f.h, &cx, &cy);
-    float pp[3], o[3], d[3];
-    for (int r = 0; r < 3; r++) pp[r] = temporal_row(f.proj_inv, r, cx, cy, -1.0f, 1.0f);
-    for (int r = 0; r < 3; r++) {
-        o[r] = temporal_row(f.view_inv, r, pp[0], pp[1], pp[2], 1.0f);
-        d[r] = temporal_row(f.view_inv, r, pp[0], pp[1], pp[2], 0.0f);
-    }
-    const float len = __builtin_sqrtf(temporal_dot(d, d));
-    for (int r = 0; r < 3; r++) world[r] = o[r] + (d[r] / len) * depth;
+    float o[3], d[3];
+    pixel_ray(f.proj_inv, f.view_inv, x | (y << 16), f.w, f.h, o, d);
+    for (int r = 0; r < 3; r++) world[r] = o[r] + d[r] * depth;
 }
 
 // Where `prev`, a world point of the previous frame, lay on that frame's screen (in pixels: the centre of pixel (i, j) is (i, j)) and the

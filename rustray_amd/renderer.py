@@ -185,10 +185,21 @@ class Raytracing:
         res = self.device_scene.denoise_records(int(cam.width), int(cam.height), records, halves, albedo, params, rgba8=rgba8)
         return dict(res, **capi._records(res["records"]))
 
-    def render_denoised(self, samples: Optional[int] = None, params=None, sample_xy=None, rgba8: bool = False) -> dict:
+    def surface_pixels(self, pixels=None):
+        """The G-buffer of this camera (rr_surface_pixels): the rr_surface_hit record of the pixel-centre ray of every pixel of `pixels`
+        (as render_pixels takes them) or of the whole frame in row-major order (None) -> a structured array (flat.SURFACE_HIT_DTYPE)."""
+        return self.device_scene.surface_pixels(self.camera.c_struct(), pixels=pixels, records=True, albedo=False)
+
+    def albedo(self) -> np.ndarray:
+        """The albedo of the whole frame of this camera, (n, 3) float32 in row-major order: what denoise() takes as `albedo` (the
+        base_color of surface_pixels(), 0 where the pixel's centre ray hits nothing)."""
+        return self.device_scene.surface_pixels(self.camera.c_struct(), records=False, albedo=True)
+
+    def render_denoised(self, samples: Optional[int] = None, params=None, sample_xy=None, rgba8: bool = False, albedo: bool = False) -> dict:
         """The whole frame at `samples` (default: the config's; even) in two halves, followed by the filter guided by their variance: one
-        rr_render_pixel_parts call at n_parts = 2 and one rr_denoise_records call.  Returns the dict of denoise() plus `noisy`, the
-        records before the filter.  render_denoised_torch is the same on the device, with no host trip."""
+        rr_render_pixel_parts call at n_parts = 2 and one rr_denoise_records call.  albedo=True: one rr_surface_pixels call between them
+        makes this camera's albedo and the filter runs on albedo-demodulated colour; the result then holds it as `albedo`.  Returns the
+        dict of denoise() plus `noisy`, the records before the filter.  render_denoised_torch is the same on the device, with no host trip."""
         cam = self.camera.c_struct()
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
@@ -196,10 +207,13 @@ class Raytracing:
         base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=sample_xy)
         records = _pack_records(base)
         halves = _pack_records(base["parts"])
+        if albedo:
+            guide = self.device_scene.surface_pixels(cam, records=False, albedo=True)
+            return dict(self.denoise(records, halves, guide, params, rgba8=rgba8), noisy=records, albedo=guide)
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
     def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
-                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False) -> dict:
+                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo: bool = False) -> dict:
         """One frame of a frame-after-frame loop at `samples` (default: the config's; even) and `seed` (default: the config's): the frame
         in two halves, blended into the history `state` carries from the previous call (rr_accumulate_records, reprojected through the
         camera of that call), then the filter guided by the accumulated halves.  render_temporal_torch on this scene and camera: three
@@ -207,7 +221,8 @@ class Raytracing:
         (n, 3) for what moved in the world, or track_items=True: the state notes `trans` of every item of self.flat_scene at each call,
         the next call lists the items whose 16 floats differ bitwise, and rr_motion_records makes their motion on the device (a fourth
         call on the same stream); a change of the item count or of any item's id resets the state, and so does a history from a call
-        without track_items."""
+        without track_items.  albedo=True: one more call on the same stream (rr_surface_pixels_device) makes this camera's albedo for the
+        filter; the accumulation is not changed, it blends un-demodulated colour."""
         from .temporal import previous_view
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
@@ -225,7 +240,7 @@ class Raytracing:
         else:
             state.items = None
         return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
+                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo)
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -752,12 +767,44 @@ def surface_rays_torch(device_scene: capi.DeviceScene, origins, directions, dept
         rec = torch.empty((n, 32), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
         if n:
             device_scene.surface_rays_device(o.data_ptr(), d.data_ptr(), n, depth, rec.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return _surface_views(rec)
+
+
+def _surface_views(rec) -> dict:
+    """`records`, (n, 32) float32 = n rr_surface_hit records on the device, and the views of its fields"""
+    import torch
     i = rec.view(torch.int32)
     return {"records": rec, "hit": i[:, 0], "item_index": i[:, 1], "object_id": i[:, 2], "face_id": i[:, 3],
             "position": rec[:, 4:7], "distance": rec[:, 7], "normal": rec[:, 8:11], "material": i[:, 11],
             "shading_normal": rec[:, 12:15], "has_uv": i[:, 15], "base_color": rec[:, 16:20],
             "ambient_color": rec[:, 20:23], "alpha": rec[:, 23], "specular_color": rec[:, 24:27], "reflectivity": rec[:, 27],
             "uv": rec[:, 28:30], "roughness": rec[:, 30], "ambient_occlusion": rec[:, 31]}
+
+
+def surface_pixels_torch(device_scene: capi.DeviceScene, cam, pixels=None, records: bool = True, albedo: bool = True) -> dict:
+    """rr_surface_pixels_device on torch's current stream: the G-buffer of `cam`'s pixel-centre rays and the albedo denoise_torch takes.
+    `pixels` as render_pixels_torch takes them, or None for every pixel of the frame in row-major order -- that form is only enqueued: no
+    host copy, no synchronisation.  Returns torch tensors: with records=True the dict of surface_rays_torch (records (n, 32) float32 and
+    the views of its fields), with albedo=True `albedo` (n, 3) float32 (the records' base_color, 0 for a miss)."""
+    import torch
+    if not records and not albedo:
+        raise ValueError("surface_pixels_torch: neither records nor albedo")
+    n, xy = int(cam.width) * int(cam.height), None
+    if pixels is not None:
+        dtype = torch.int32 if not isinstance(pixels, torch.Tensor) or pixels.dtype != getattr(torch, "uint32", None) else pixels.dtype
+        xy = _ray_tensor(device_scene, pixels, "pixels", shape_tail=(), dtype=dtype)
+        n = int(xy.shape[0])
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 32), dtype=torch.float32, device=dev) if records else None   # (torch allocations are at least 512-byte aligned)
+        alb = torch.empty((n, 3), dtype=torch.float32, device=dev) if albedo else None
+        if n:
+            device_scene.surface_pixels_device(cam, xy.data_ptr() if xy is not None else None, n, rec.data_ptr() if records else None,
+                                               alb.data_ptr() if albedo else None, torch.cuda.current_stream(dev).cuda_stream)
+    out = _surface_views(rec) if records else {}
+    if albedo:
+        out["albedo"] = alb
+    return out
 
 
 def trace_shadow_rays_torch(device_scene: capi.DeviceScene, origins, directions, max_distance=None, depth: int = 2) -> dict:
@@ -948,13 +995,19 @@ def denoise_torch(device_scene: capi.DeviceScene, width: int, height: int, recor
     return res
 
 
-def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, params=None, sample_xy=None, rgba8: bool = False) -> dict:
+def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, params=None, sample_xy=None, rgba8: bool = False, albedo: bool = False) -> dict:
     """Raytracing.render_denoised on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples even) and
-    rr_denoise_records_device on the same stream, the second reading what the first wrote without a synchronisation.  Returns the dict of
-    denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the tensors the filter read."""
+    rr_denoise_records_device on the same stream, the second reading what the first wrote without a synchronisation.  albedo=True:
+    rr_surface_pixels_device between the two, on the same stream, makes the camera's albedo for the filter (three calls, still no host
+    trip).  Returns the dict of denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the tensors the filter read, and with albedo=True
+    albedo (n, 3)."""
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
-    res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], None, params, rgba8=rgba8)
-    return dict(res, noisy=base["records"], halves=base["part_records"])
+    guide = surface_pixels_torch(device_scene, cam, None, records=False, albedo=True)["albedo"] if albedo else None
+    res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], guide, params, rgba8=rgba8)
+    res = dict(res, noisy=base["records"], halves=base["part_records"])
+    if albedo:
+        res["albedo"] = guide
+    return res
 
 
 # ---------------------------------------------------------------------------
@@ -1068,7 +1121,7 @@ def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_
 
 
 def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
-                          sample_xy=None, rgba8: bool = False, view=None, moved=None) -> dict:
+                          sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo: bool = False) -> dict:
     """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
     even), rr_accumulate_records_device against the history in `state`, rr_denoise_records_device with the accumulated halves -- three
     calls on torch's current stream, each reading what the one before wrote without a synchronisation.  params: a
@@ -1078,7 +1131,8 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     rr_motion_records_device makes the motion on the same stream, the second of four calls; together with `motion` it is a ValueError.
     Returns the dict of denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the frame's own records, accumulated (n, 8),
     accumulated_halves (n, 2, 8) and length (n,): what the filter read, which `state` now holds as the history; and motion (n, 3) or None:
-    what the accumulation read."""
+    what the accumulation read.  albedo=True: rr_surface_pixels_device on the same stream, one call more, makes the albedo of `cam` for the
+    filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
@@ -1100,7 +1154,11 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
         motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
     acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
                            hist["length"] if hist else None, motion, prm, out=target)
-    res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], None, denoise_params, rgba8=rgba8)
+    guide = surface_pixels_torch(device_scene, cam, None, records=False, albedo=True)["albedo"] if albedo else None
+    res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], guide, denoise_params, rgba8=rgba8)
     state.advance(target, view if view is not None else previous_view(cam))
-    return dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"],
-                motion=motion)
+    res = dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"],
+               motion=motion)
+    if albedo:
+        res["albedo"] = guide
+    return res

@@ -11,6 +11,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .pixel_rays import pixel_rays
+
 F = np.float32
 EPS = F(2.0 ** -20)
 MIN_WEIGHT = F(2.0 ** -6)
@@ -71,19 +73,11 @@ def _dot(a, b):
 def world_positions(records, cam) -> np.ndarray:
     """(n, 3) float32: world_p = o + d * depth_p of every record of a whole frame of `cam`, o and d the pinhole ray through the pixel's
     centre, in the header's arithmetic (step 2)."""
-    pi, vi, W, H = _camera_matrices(cam)
+    _, _, W, H = _camera_matrices(cam)
     rec = np.ascontiguousarray(records, F).reshape(H * W, 8)
-    y, x = np.mgrid[0:H, 0:W]
-    x_f, y_f = x.reshape(-1).astype(F), y.reshape(-1).astype(F)
-    one, zero = F(1), F(0)
+    o, d = pixel_rays(cam)
     with np.errstate(all="ignore"):
-        cx = ((x_f + F(0.5)) / F(W)) * F(2) - one
-        cy = one - ((y_f + F(0.5)) / F(H)) * F(2)
-        pp = [_row(pi, r, cx, cy, F(-1), one) for r in range(3)]
-        o = [_row(vi, r, pp[0], pp[1], pp[2], one) for r in range(3)]
-        d = np.stack([_row(vi, r, pp[0], pp[1], pp[2], zero) for r in range(3)], axis=-1)
-        length = np.sqrt(_dot(d, d))
-        return np.stack([o[r] + (d[..., r] / length) * rec[:, 3] for r in range(3)], axis=-1).astype(F)
+        return (o + d * rec[:, 3:4]).astype(F)
 
 
 def item_motion(world, object_id, item_ids, prev_trans, cur_trans_inv) -> np.ndarray:

@@ -17,7 +17,15 @@ halves at 8 samples per pixel) on the same handle.
 With --sweep (no GPU): the four defaults on the CPU quality frame of tests/denoise_cases.py through the numpy yardstick -- RMSE against
 the truth for a grid around rr_denoise_default_params.
 
-usage: denoise_time.py [scene [width height samples]] [--out FILE] [--sweep]"""
+With --albedo: what the albedo guide costs next to the filter and the frame, same protocol (one process, one handle, arms alternating,
+device events around CALLS back-to-back calls, WARMUP rounds, the median of ROUNDS):
+  (a) rr_surface_pixels_device, albedo only      (b) the same with records
+  (c) the path it replaces: host-made pixel-centre rays already resident on the device + rr_surface_rays_device + a torch gather of base_color
+  (d) rr_denoise_records_device (5 iterations, halves, that albedo)      (e) the 4-sample rr_render_pixel_parts_device frame
+next to the compulsory traffic of (a) per pixel (the walk's records: 16 + 16 + 8 B written and read, 16 B of hit written and read, the
+4 B slot map written and read, 12 B of albedo written) at the float4-copy rate.  Scene `sponza_syn` is the benchmark's stand-in.
+
+usage: denoise_time.py [scene [width height samples]] [--out FILE] [--sweep | --albedo]"""
 import itertools
 import os
 import sys
@@ -69,6 +77,9 @@ def main(argv):
         del argv[i:i + 2]
     if "--sweep" in argv:
         sweep(emit)
+    elif "--albedo" in argv:
+        argv.remove("--albedo")
+        measure_albedo(argv, emit)
     else:
         measure(argv, emit)
     if out_path:
@@ -158,6 +169,78 @@ def measure(argv, emit):
                 m, lo, hi = med[("pass", i, f)]
                 row.append(f"{FORM_NAMES[f]} {(m - base) * 1e3:.1f} us [{(lo - base) * 1e3:.1f} .. {(hi - base) * 1e3:.1f}]")
         emit(f"    pass {i} (step {1 << i}): " + ", ".join(row))
+
+
+ALBEDO_BYTES_PER_PIXEL = 2 * (16 + 16 + 8) + 2 * 16 + 2 * 4 + 12
+
+
+def measure_albedo(argv, emit):
+    import torch
+    from rustray_amd import capi, renderer, synthetic
+    from rustray_amd.denoise import DenoiseParams
+    from rustray_amd.flat import make_config
+    from rustray_amd.pixel_rays import pixel_rays
+    from tests.helpers import camera_for, load_scene
+    scene = argv[1] if len(argv) > 1 else "spheres_room"
+    w, h = (int(argv[2]), int(argv[3])) if len(argv) > 3 else (1280, 720)
+    if capi.device_count() < 1:
+        raise SystemExit("denoise_time.py needs a GPU: no HIP device visible")
+    fs = synthetic.sponza_syn() if scene == "sponza_syn" else load_scene(scene)
+    cam = camera_for(fs, w, h).c_struct()
+    cfg = make_config(samples=4, monte_carlo=True, seed=1, max_recursion=4)
+    n = w * h
+    with capi.DeviceScene(fs, 0) as ds:
+        def timed(fn, calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b) / calls
+
+        stream = torch.cuda.current_stream().cuda_stream
+        o, d = (torch.from_numpy(a).cuda() for a in pixel_rays(cam))
+        frame = renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2)
+        rec, halves = frame["records"], frame["part_records"]
+        albedo = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        surf = torch.empty((n, 32), dtype=torch.float32, device="cuda")
+        out = torch.empty_like(rec)
+        prm = capi.denoise_params(DenoiseParams(iterations=5))
+        torch.cuda.synchronize()
+
+        def replaced():
+            ds.surface_rays_device(o.data_ptr(), d.data_ptr(), n, 1, surf.data_ptr(), stream)
+            return surf[:, 16:19].contiguous()
+
+        arms = {
+            "a": lambda: ds.surface_pixels_device(cam, None, n, None, albedo.data_ptr(), stream),
+            "b": lambda: ds.surface_pixels_device(cam, None, n, surf.data_ptr(), albedo.data_ptr(), stream),
+            "c": replaced,
+            "d": lambda: ds.denoise_records_device(w, h, rec.data_ptr(), halves.data_ptr(), albedo.data_ptr(), out.data_ptr(), None, None, prm, stream),
+            "e": lambda: renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2),
+        }
+        runs = {k: [] for k in arms}
+        for r in range(WARMUP + ROUNDS):
+            for k, fn in arms.items():
+                t = timed(fn, 1 if k == "e" else CALLS)
+                if r >= WARMUP:
+                    runs[k].append(t)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(replaced().view(torch.int32), albedo.view(torch.int32)))
+    med = {k: _median(v) for k, v in runs.items()}
+    floor_ms = n * ALBEDO_BYTES_PER_PIXEL / HBM_BYTES_PER_S * 1e3
+    names = {"a": "(a) rr_surface_pixels_device, albedo only", "b": "(b) rr_surface_pixels_device, records and albedo",
+             "c": "(c) resident rays + rr_surface_rays_device + torch gather of base_color", "d": "(d) rr_denoise_records_device, 5 iterations, halves, albedo",
+             "e": "(e) rr_render_pixel_parts_device, 4 samples in two halves"}
+    emit(f"the albedo guide, {scene} {w}x{h}; device ms per call, median of {ROUNDS} rounds of {CALLS} calls (e: 1 call) [min .. max]; (c)'s albedo equals (a)'s bit for bit: {same}")
+    for k in "abcde":
+        m, lo, hi = med[k]
+        emit(f"  {names[k]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
+    a, c = med["a"], med["c"]
+    emit(f"  (a) / (c) = {a[0] / c[0]:.3f}; (c)'s own spread {c[1]:.4f} .. {c[2]:.4f}; (a) / (d) = {a[0] / med['d'][0]:.3f}; (a) / (e) = {a[0] / med['e'][0]:.3f}")
+    emit(f"  compulsory traffic of (a): {ALBEDO_BYTES_PER_PIXEL} B per pixel = {n * ALBEDO_BYTES_PER_PIXEL / 1e6:.1f} MB, {floor_ms * 1e3:.1f} us at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: "
+         f"(a) reaches {floor_ms / a[0]:.3f} of that rate (the walk between the two streaming kernels reads the scene, not the frame)")
 
 
 if __name__ == "__main__":
