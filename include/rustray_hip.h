@@ -997,7 +997,9 @@ int rr_render_adaptive_prefix_device(rr_scene* scene, const rr_camera* camera, c
  *   Memory kept by the handle until rr_scene_destroy: 56 B per pixel of the largest frame so far (two working colours of 16 B, the
  *   packed guide of 16 + 8 B).  A growth that fails is RR_ERR_OUT_OF_MEMORY and leaves the handle usable.
  * rr_denoise_records: the same on HOST pointers, the device form on the null stream behind a staging copy (32 + 32 B per pixel, and
- * 64, 12, 4 and 4 B for halves, albedo, rgba8_out and variance_out where given, kept by the handle as well); it returns with `out` written. */
+ * 64, 12, 4 and 4 B for halves, albedo, rgba8_out and variance_out where given, in the pool of staging buffers the handle keeps for this
+ * call, rr_accumulate_records and rr_motion_records together: per argument position the largest any of them has needed); it returns
+ * with `out` written. */
 #define RR_MAX_DENOISE_ITERATIONS 6u
 typedef struct rr_denoise_params {
     uint32_t struct_size;        /* sizeof(rr_denoise_params) */
@@ -1077,8 +1079,8 @@ int rr_denoise_records(rr_scene* scene, uint32_t width, uint32_t height, const r
  *   Refusals: a NULL scene, camera, params, records, out or length_out; width or height 0 or above 65535; a struct_size other than
  *   sizeof(rr_accumulate_params); max_history, normal_min, sigma_depth or snap out of range or NaN; the pairing rules above:
  *   RR_ERR_INVALID_ARGUMENT.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
- * rr_accumulate_records: the same on HOST pointers, the device form on the null stream behind staging copies the handle keeps until
- * rr_scene_destroy (per pixel 32 B each for records, history and out, 64 B each for halves, history_halves and halves_out, 4 B each for
+ * rr_accumulate_records: the same on HOST pointers, the device form on the null stream behind staging copies in the pool the handle keeps
+ * until rr_scene_destroy, shared with rr_denoise_records (per pixel 32 B each for records, history and out, 64 B each for halves, history_halves and halves_out, 4 B each for
  * history_length, length_out and rgba8_out, 12 B for motion, each only where the call has it); it returns with the outputs written. */
 typedef struct rr_accumulate_params {
     uint32_t struct_size;            /* sizeof(rr_accumulate_params) */
@@ -1135,8 +1137,8 @@ int rr_accumulate_records(rr_scene* scene, const rr_camera* camera, const rr_acc
  *   Refusals: a NULL scene, camera, records or motion output; width or height 0 or above 65535; n_moved > the scene's item count; with
  *   n_moved > 0 a NULL item_index or prev_trans; an item_index[k] >= the item count; a prev_trans that is not finite (naming the entry);
  *   two listed items of one id: RR_ERR_INVALID_ARGUMENT, nothing launched.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED.
- * rr_motion_records: the same on HOST pointers, the device form on the null stream behind staging copies the handle keeps until
- * rr_scene_destroy (32 B per pixel for the records, 12 B for motion_out and 12 B for world_out where given); it returns with the
+ * rr_motion_records: the same on HOST pointers, the device form on the null stream behind staging copies in the pool the handle keeps
+ * until rr_scene_destroy, shared with rr_denoise_records (32 B per pixel for the records, 12 B for motion_out and 12 B for world_out where given); it returns with the
  * outputs written. */
 int rr_motion_records_device(rr_scene* scene, const rr_camera* camera, const uint32_t* item_index /* HOST, n_moved */,
                              const float* prev_trans /* HOST, n_moved * 16 */, uint32_t n_moved, const rr_radiance* records_dev /* n */,

@@ -14,6 +14,7 @@
 #include "rr_frame_plan.h"
 #include "rr_primary_setup.h"
 #include "rr_query_pointers.h"
+#include "rr_arg_ranges.h"
 
 #include <hip/hip_runtime.h>
 

@@ -2,12 +2,13 @@
 // the halves and the albedo the other calls give it, without a trip through host memory.
 // Offers: rr_denoise_default_params, rr_denoise_records_device, rr_denoise_records; rr_test_denoise_forms (the tuning hook of the tests
 //         and of tools/denoise_time.py).
-// Needs:  rr_api_query.h (check_query_pointers), rr_api_frame.h (take_stream, IdleOnExit), rr_api_adaptive.h (launch_record_bytes),
-//         rr_denoise.h, kernels 7a .. 7d of rr_kernels.hip.
+// Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_denoise.h,
+//         kernels 7a .. 7d of rr_kernels.hip.
 //
 // The call is k_denoise_prepare, one pass launch per iteration (step 1, 2, 4, ...), k_denoise_finish and, for the bytes, k_record_bytes:
 // all on the caller's stream, none of them waited for.  The working data are the handle's (DenoiseState): two working colours of 16 B,
-// the guide of 16 + 8 B: 56 B per pixel of the largest frame so far.  The host form is the device form behind a staging copy.
+// the guide of 16 + 8 B: 56 B per pixel of the largest frame so far.  The host form is the device form behind the staging of every
+// record call (staged_host_call, in the handle's pool).
 
 // ---- which form of the pass kernel runs a step.  Measured at 1280x720 (profiles/r10_denoise_time.txt; the forms that lost:
 // profiles/r10_dropped.txt): steps 1 and 2 through an LDS tile of the frame, steps 4 and 8 as one dense tile per residue class of the
@@ -64,20 +65,9 @@ static int check_denoise_args(const char* fn, bool device, const rr_scene* s, ui
         return fail(RR_ERR_INVALID_ARGUMENT, "%s: albedo_dev, rgba8_out_dev and variance_out_dev must be 4-byte aligned", fn);
     // overlaps: an output with an input or with another output; out == records exactly is the in-place call
     const uint64_t n = (uint64_t)width * height;
-    struct Range { const void* p; uint64_t bytes; const char* name; };
-    const Range in[3] = {{io.records, 32u * n, "records"}, {io.halves, 64u * n, "halves"}, {io.albedo, 12u * n, "albedo"}};
-    const Range outs[3] = {{io.out, 32u * n, "out"}, {io.rgba8, 4u * n, "rgba8_out"}, {io.variance, 4u * n, "variance_out"}};
-    auto overlap = [](const Range& a, const Range& b) {
-        return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < (uintptr_t)a.p + a.bytes;
-    };
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 3; i++)
-            if (overlap(outs[o], in[i]) && !(o == 0 && i == 0 && io.out == io.records))
-                return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s (only out == records, in place, is allowed)", fn, outs[o].name, in[i].name);
-        for (int o2 = o + 1; o2 < 3; o2++)
-            if (overlap(outs[o], outs[o2])) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, outs[o].name, outs[o2].name);
-    }
-    return RR_OK;
+    const ArgRange t[6] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {io.albedo, 12u * n, "albedo", false, -1},
+                           {io.out, 32u * n, "out", true, 0}, {io.rgba8, 4u * n, "rgba8_out", true, -1}, {io.variance, 4u * n, "variance_out", true, -1}};
+    return check_arg_ranges(fn, t, 6, false, " (only out == records, in place, is allowed)");
 }
 
 // the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
@@ -120,46 +110,25 @@ static int denoise_locked(rr_scene* s, uint32_t W, uint32_t H, const rr_denoise_
 
 int rr_denoise_records_device(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
                               const float* albedo, rr_radiance* out, uint8_t* rgba8_out, float* variance_out, void* hip_stream) try {
+    const char* fn = "rr_denoise_records_device";
     const DenoiseIo io{records, halves, albedo, out, rgba8_out, variance_out};
-    RR_TRY(check_denoise_args("rr_denoise_records_device", true, s, width, height, prm, io));
-    RR_TRY(not_in_pass(s, "rr_denoise_records_device"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, "rr_denoise_records_device", {{records, "records_dev"}, {halves, "halves_dev"}, {albedo, "albedo_dev"}, {out, "out_dev"},
-                                                                  {rgba8_out, "rgba8_out_dev"}, {variance_out, "variance_out_dev"}}));
+    RR_TRY(check_denoise_args(fn, true, s, width, height, prm, io));
     const hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(take_stream(s, st));
-    IdleOnExit idle(st);
-    return idle.done(denoise_locked(s, width, height, prm, io, st));
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {albedo, "albedo_dev"}, {out, "out_dev"}, {rgba8_out, "rgba8_out_dev"},
+                                      {variance_out, "variance_out_dev"}}, st, [&] { return denoise_locked(s, width, height, prm, io, st); });
 } RR_GUARD_END("rr_denoise_records_device")
 
 int rr_denoise_records(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
                        const float* albedo, rr_radiance* out, uint8_t* rgba8_out, float* variance_out) try {
-    const DenoiseIo host{records, halves, albedo, out, rgba8_out, variance_out};
-    RR_TRY(check_denoise_args("rr_denoise_records", false, s, width, height, prm, host));
-    RR_TRY(not_in_pass(s, "rr_denoise_records"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(take_stream(s, nullptr));
-    IdleOnExit idle(nullptr);
-    // the staging is the handle's (DenoiseState::stage: grown, kept, used by the host form only, which returns with the stream idle)
+    const char* fn = "rr_denoise_records";
+    RR_TRY(check_denoise_args(fn, false, s, width, height, prm, DenoiseIo{records, halves, albedo, out, rgba8_out, variance_out}));
     const size_t n = (size_t)width * height;
-    DevBuf* g = s->denoise.stage;
-    HIP_TRY(g[0].reserve(32 * n));
-    HIP_TRY(g[3].reserve(32 * n));
-    if (halves) HIP_TRY(g[1].reserve(64 * n));
-    if (albedo) HIP_TRY(g[2].reserve(12 * n));
-    if (rgba8_out) HIP_TRY(g[4].reserve(4 * n));
-    if (variance_out) HIP_TRY(g[5].reserve(4 * n));
-    HIP_TRY(hipMemcpyAsync(g[0].p, records, 32 * n, hipMemcpyHostToDevice, nullptr));
-    if (halves) HIP_TRY(hipMemcpyAsync(g[1].p, halves, 64 * n, hipMemcpyHostToDevice, nullptr));
-    if (albedo) HIP_TRY(hipMemcpyAsync(g[2].p, albedo, 12 * n, hipMemcpyHostToDevice, nullptr));
-    const DenoiseIo dev{g[0].as<rr_radiance>(), halves ? g[1].as<rr_radiance>() : nullptr, albedo ? g[2].as<float>() : nullptr, g[3].as<rr_radiance>(),
-                        rgba8_out ? g[4].as<uint8_t>() : nullptr, variance_out ? g[5].as<float>() : nullptr};
-    RR_TRY(denoise_locked(s, width, height, prm, dev, nullptr));
-    if (rgba8_out) HIP_TRY(hipMemcpyAsync(rgba8_out, g[4].p, 4 * n, hipMemcpyDeviceToHost, nullptr));
-    if (variance_out) HIP_TRY(hipMemcpyAsync(variance_out, g[5].p, 4 * n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(out, g[3].p, 32 * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return idle.done(RR_OK);
+    const StageArg args[6] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(albedo, 12 * n),
+                              stage_output(out, 32 * n), stage_output(rgba8_out, 4 * n), stage_output(variance_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const DenoiseIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const float*)d[2], (rr_radiance*)d[3], (uint8_t*)d[4], (float*)d[5]};
+            return denoise_locked(s, width, height, prm, dev, nullptr);
+        });
+    });
 } RR_GUARD_END("rr_denoise_records")

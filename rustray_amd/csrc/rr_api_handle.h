@@ -1,5 +1,5 @@
 // rr_api_handle.h — the scene handle of the C ABI (rr_scene), in named parts: one per host layer of rr_api.hip.
-// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, TemporalState, MotionState, MultiState, FrameTiming
+// Offers: TimerKernel, TimedLaunch; POOL_WORDS; RAY_RECORD_BYTES; SceneData, TopLevel, FrameState, QueryState, AdaptiveState, DenoiseState, MotionState, RecordStage, MultiState, FrameTiming
 //         and rr_scene, which holds one of each; HC_* (the words of FrameState::h_count); check_intact.
 // Needs:  rr_api_base.h (fail, HIP_TRY, DevBuf), rr_scene_build.h (ItemHost, MeshDev, HostMesh), rr_device.h, rr_primary_setup.h, rr_motion.h (MoEntry).
 // A layer that reads or borrows another layer's part says so in the spelling of the access (s->frame.h_count in a query).
@@ -140,31 +140,22 @@ struct AdaptiveState {
 };
 
 // ---- rr_denoise_records (rr_api_denoise.h): grown on demand, never shrunk.  work: the working colour (r, g, b, var), ping-pong, 16 B per
-// pixel each; guide: normal and depth, 16 B; meta: object id and flags, 8 B -- 56 B per pixel of the largest frame so far.  stage: the
-// host form's copies of records, halves, albedo, out, rgba8_out and variance_out (32 + 64 + 12 + 32 + 4 + 4 B per pixel, each only where
-// the call has it).  Written by rr_api_denoise.h.
+// pixel each; guide: normal and depth, 16 B; meta: object id and flags, 8 B -- 56 B per pixel of the largest frame so far.  Written by
+// rr_api_denoise.h.  (rr_accumulate_records, rr_api_temporal.h, keeps nothing.)
 struct DenoiseState {
-    DevBuf work[2], guide, meta, stage[6];
-};
-
-// ---- rr_accumulate_records (rr_api_temporal.h): the call itself keeps nothing.  stage: the host form's copies of records, halves, history,
-// history_halves, history_length, motion, out, halves_out, length_out and rgba8_out (32 + 64 + 32 + 64 + 4 + 12 + 32 + 64 + 4 + 4 B per
-// pixel, each only where the call has it), grown on demand, never shrunk.  Written by rr_api_temporal.h.
-struct TemporalState {
-    DevBuf stage[10];
+    DevBuf work[2], guide, meta;
 };
 
 // ---- rr_motion_records (rr_api_motion.h): grown on demand, never shrunk.  table: the call's table on the device, 112 B per entry of the
 // largest list so far; slot: the same in pinned memory, what the copy on the caller's stream reads after the call has returned, four of
 // them used in turn, each with the event behind its last copy (pending: there is one) -- a call waits for the copy of the fourth call
-// before it, which reads the slot it is about to write, and for nothing else.  stage: the host form's copies of records, motion_out and
-// world_out (32 + 12 + 12 B per pixel, the last only where the call has it).  Written by rr_api_motion.h.
+// before it, which reads the slot it is about to write, and for nothing else.  Written by rr_api_motion.h.
 struct MotionSlot {
     MoEntry* h_table = nullptr; size_t entries = 0;
     hipEvent_t copied = nullptr; bool pending = false;
 };
 struct MotionState {
-    DevBuf table, stage[3];
+    DevBuf table;
     MotionSlot slot[4]; uint32_t next = 0;
     ~MotionState() {
         for (MotionSlot& m : slot) {
@@ -172,6 +163,15 @@ struct MotionState {
             if (m.h_table) (void)hipHostFree(m.h_table);
         }
     }
+};
+
+// ---- the host forms of rr_denoise_records, rr_accumulate_records and rr_motion_records: the device's copies of the caller's arrays, argument
+// k of a call in buf[k] (the most arguments: the ten of rr_accumulate_records), each only where the call has it; grown on demand, never
+// shrunk, so a slot holds the largest argument any of the three calls has put there.  One pool serves the three: a host form holds the
+// scene's lock and returns with the null stream idle, on its failing paths as well (IdleOnExit), so no call finds another's copies in
+// use.  Written by staged_host_call (rr_api_query.h).
+struct RecordStage {
+    DevBuf buf[10];
 };
 
 // ---- rr_render_multi (rr_api_multi.h)
@@ -227,8 +227,8 @@ struct rr_scene {
     QueryState query;
     AdaptiveState adaptive;
     DenoiseState denoise;
-    TemporalState temporal;
     MotionState motion;
+    RecordStage record_stage;
     MultiState multi;
     FrameTiming timing;
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's

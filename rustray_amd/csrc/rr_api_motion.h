@@ -1,13 +1,13 @@
 // rr_api_motion.h — the per-pixel motion of moved items on the device: what rr_accumulate_records takes as motion_dev when items moved
 // between two frames, from the records the device already holds.
 // Offers: rr_motion_records_device, rr_motion_records.
-// Needs:  rr_api_query.h (check_query_pointers), rr_api_frame.h (take_stream, IdleOnExit), rr_api_handle.h (MotionState, check_intact),
+// Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_temporal.h (tp_frame), rr_api_handle.h (MotionState),
 //         rr_motion.h (motion_build_table), kernel 7f of rr_kernels.hip.
 //
 // The call is ONE copy of the table (from one of the handle's pinned copies) and ONE launch of k_motion_records on the caller's stream, not waited
 // for; with nothing moved and no world_out it is one hipMemsetAsync.  The caller's host arrays are read before the call returns: the
 // table is built on the host from them and from the handle's item records (SceneData::h_items: the trans_inv and id the current frame
-// was traced with).  The host form is the device form behind staging copies (MotionState::stage).
+// was traced with).  The host form is the device form behind the staging of every record call (staged_host_call, in the handle's pool).
 
 struct MotionIo {
     const rr_radiance* records; float* motion; float* world;
@@ -29,13 +29,8 @@ static int check_motion_args(const char* fn, bool device, const rr_scene* s, con
     if (device && ((uintptr_t)io.records & 15u)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: records_dev must be 16-byte aligned", fn);
     if (device && (((uintptr_t)io.motion | (uintptr_t)io.world) & 3u)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: motion_out_dev and world_out_dev must be 4-byte aligned", fn);
     const uint64_t n = (uint64_t)width * height;
-    struct Range { const void* p; uint64_t bytes; const char* name; };
-    const Range r[3] = {{io.records, 32u * n, "records"}, {io.motion, 12u * n, "motion_out"}, {io.world, 12u * n, "world_out"}};
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
-            if (r[a].p && r[b].p && (uintptr_t)r[a].p < (uintptr_t)r[b].p + r[b].bytes && (uintptr_t)r[b].p < (uintptr_t)r[a].p + r[a].bytes)
-                return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, r[b].name, r[a].name);
-    return RR_OK;
+    const ArgRange t[3] = {{io.records, 32u * n, "records", false, -1}, {io.motion, 12u * n, "motion_out", true, -1}, {io.world, 12u * n, "world_out", true, -1}};
+    return check_arg_ranges(fn, t, 3, true, "");
 }
 
 // The table of this call, built on the host from the caller's arrays and the handle's item records: every refusal that concerns the list
@@ -83,13 +78,8 @@ static int motion_locked(rr_scene* s, const char* fn, const rr_camera* cam, cons
         return RR_OK;
     }
     if (n_moved) RR_TRY(upload_motion_table(s, table, st));
-    TpFrame f{};
-    memcpy(f.proj_inv, cam->projection_inverse, sizeof f.proj_inv);
-    memcpy(f.view_inv, cam->view_inverse, sizeof f.view_inv);
-    f.w = (float)W; f.h = (float)H;
-    f.width = (int)W; f.height = (int)H;
     const dim3 grid((W + DN_TILE_W - 1) / DN_TILE_W, (H + DN_TILE_H - 1) / DN_TILE_H), block(RR_BLOCK);
-    hipLaunchKernelGGL(k_motion_records, grid, block, 0, st, f, (const float4*)io.records, n_moved ? s->motion.table.as<MoEntry>() : (const MoEntry*)nullptr, n_moved,
+    hipLaunchKernelGGL(k_motion_records, grid, block, 0, st, tp_frame(cam), (const float4*)io.records, n_moved ? s->motion.table.as<MoEntry>() : (const MoEntry*)nullptr, n_moved,
                        io.motion, io.world);
     if (hipGetLastError() != hipSuccess) return fail(RR_ERR_DEVICE, "%s: a launch failed", fn);
     return RR_OK;
@@ -100,43 +90,23 @@ int rr_motion_records_device(rr_scene* s, const rr_camera* camera, const uint32_
     const char* fn = "rr_motion_records_device";
     const MotionIo io{records, motion_out, world_out};
     RR_TRY(check_motion_args(fn, true, s, camera, item_index, prev_trans, n_moved, io));
-    RR_TRY(not_in_pass(s, fn));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, fn, {{records, "records_dev"}, {motion_out, "motion_out_dev"}, {world_out, "world_out_dev"}}));
-    std::vector<MoEntry> table;
-    RR_TRY(build_motion_table(s, fn, item_index, prev_trans, n_moved, &table));
     const hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(take_stream(s, st));
-    IdleOnExit idle(st);
-    return idle.done(motion_locked(s, fn, camera, table, io, st));
+    std::vector<MoEntry> table;
+    return record_call(s, fn, true, {{records, "records_dev"}, {motion_out, "motion_out_dev"}, {world_out, "world_out_dev"}}, st,
+                       [&] { return build_motion_table(s, fn, item_index, prev_trans, n_moved, &table); },
+                       [&] { return motion_locked(s, fn, camera, table, io, st); });
 } RR_GUARD_END("rr_motion_records_device")
 
 int rr_motion_records(rr_scene* s, const rr_camera* camera, const uint32_t* item_index, const float* prev_trans, uint32_t n_moved, const rr_radiance* records,
                       float* motion_out, float* world_out) try {
     const char* fn = "rr_motion_records";
     RR_TRY(check_motion_args(fn, false, s, camera, item_index, prev_trans, n_moved, MotionIo{records, motion_out, world_out}));
-    RR_TRY(not_in_pass(s, fn));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<MoEntry> table;
-    RR_TRY(build_motion_table(s, fn, item_index, prev_trans, n_moved, &table));
-    RR_TRY(take_stream(s, nullptr));
-    IdleOnExit idle(nullptr);
-    // the staging is the handle's (MotionState::stage: grown, kept, used by the host form only, which returns with the stream idle):
-    // 0 records 32 B, 1 motion_out 12, 2 world_out 12 per pixel, the last only where the call has it
     const size_t n = (size_t)camera->width * camera->height;
-    DevBuf* g = s->motion.stage;
-    HIP_TRY(g[0].reserve(32 * n));
-    HIP_TRY(g[1].reserve(12 * n));
-    if (world_out) HIP_TRY(g[2].reserve(12 * n));
-    HIP_TRY(hipMemcpyAsync(g[0].p, records, 32 * n, hipMemcpyHostToDevice, nullptr));
-    const MotionIo dev{g[0].as<rr_radiance>(), g[1].as<float>(), world_out ? g[2].as<float>() : nullptr};
-    RR_TRY(motion_locked(s, fn, camera, table, dev, nullptr));
-    HIP_TRY(hipMemcpyAsync(motion_out, g[1].p, 12 * n, hipMemcpyDeviceToHost, nullptr));
-    if (world_out) HIP_TRY(hipMemcpyAsync(world_out, g[2].p, 12 * n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return idle.done(RR_OK);
+    const StageArg args[3] = {stage_input(records, 32 * n), stage_output(motion_out, 12 * n), stage_output(world_out, 12 * n)};
+    std::vector<MoEntry> table;
+    return record_call(s, fn, true, {}, nullptr, [&] { return build_motion_table(s, fn, item_index, prev_trans, n_moved, &table); }, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            return motion_locked(s, fn, camera, table, MotionIo{(const rr_radiance*)d[0], (float*)d[1], (float*)d[2]}, nullptr);
+        });
+    });
 } RR_GUARD_END("rr_motion_records")

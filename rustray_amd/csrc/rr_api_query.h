@@ -1,8 +1,9 @@
 // rr_api_query.h — questions to a scene outside a frame: rr_pick, and the closest-hit, shadow, surface and radiance queries for rays of the caller's.
 // Offers: rr_pick; check_query_pointer(s); launch_query_shadow; rr_trace_rays, rr_trace_shadow_rays, rr_surface_rays, rr_shade_rays,
 //         rr_render_pixels and their *_device forms; for the list calls of the layers behind it: check_pixels_args, host_list_call,
-//         render_pixels_locked.
-// Needs:  rr_api_base.h, rr_api_handle.h (writes rr_scene::query), rr_api_scene.h (ensure_tlas_reach, ensure_camera_reach; reads
+//         render_pixels_locked; for the record calls (rr_api_denoise.h, rr_api_temporal.h, rr_api_motion.h, rr_api_surface_pixels.h):
+//         check_arg_ranges, record_call, StageArg, stage_input, stage_output, staged_host_call (writes rr_scene::record_stage).
+// Needs:  rr_arg_ranges.h, rr_api_base.h, rr_api_handle.h (writes rr_scene::query), rr_api_scene.h (ensure_tlas_reach, ensure_camera_reach; reads
 //         rr_scene::data), rr_api_frame.h (launch_trace_closest, take_stream, make_frame; for rr_shade_rays the frame's own level walk:
 //         FrameRun, run_level, upload_shade_const, reset_accumulators, grow_ray_queues, begin_frame_stats; for rr_render_pixels the whole frame:
 //         check_frame_args, pixels_io, IdleOnExit, render_region_locked), rr_pixel_list.h, rr_api_multi.h (the peer
@@ -107,6 +108,17 @@ static int check_query_pointers(const rr_scene* s, const char* fn, std::initiali
     return RR_OK;
 }
 
+// The buffers of one call as a table (rr_arg_ranges.h has the rule): the first forbidden overlap, worded.  An output over an input is
+// "<output> overlaps <input>" and `in_place_tail`; two outputs are "<earlier> overlaps <later>", or with `later_first` the other way
+// round -- the two wordings the tests of the record calls pin.
+static int check_arg_ranges(const char* fn, const ArgRange* t, int n, bool later_first, const char* in_place_tail) {
+    const ArgConflict c = arg_ranges_first_conflict(t, n);
+    if (c.a < 0) return RR_OK;
+    if (c.a == c.b) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s ends beyond the address space", fn, t[c.a].name);
+    if (!t[c.b].is_output) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s%s", fn, t[c.a].name, t[c.b].name, in_place_tail);
+    return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, t[later_first ? c.b : c.a].name, t[later_first ? c.a : c.b].name);
+}
+
 // The ONE place that launches the shadow-query kernel (rr_trace_shadow_rays), as launch_trace_closest (rr_api_frame.h): every pointer the kernel
 // touches is checked here, on the host.  r0 / r1: n ray records each; out: n result records; head: the zeroed fetch word.
 static int launch_query_shadow(rr_scene* s, const float4* r0, const float4* r1, uint64_t n, uint32_t* head, uint4* out, hipStream_t st) {
@@ -158,6 +170,50 @@ static int stage_in(DevBuf* b, const void* src, size_t bytes) {
     HIP_TRY(b->reserve(bytes));
     HIP_TRY(hipMemcpy(b->p, src, bytes, hipMemcpyHostToDevice));
     return RR_OK;
+}
+
+// THE staging of a host form whose arguments are whole arrays (rr_denoise_records, rr_accumulate_records, rr_motion_records): argument k
+// in pool[k], reserved only where the caller gave it; the inputs go up on the null stream, `body(dev)` runs on the device's copies
+// (dev[k] NULL where host was), the outputs come back behind it and ONE wait ends the call: the caller's outputs are written by a
+// finished call only.  The pool is the handle's (rr_scene::record_stage) or, for answers too large to stay resident, the call's own.
+struct StageArg { void* host; size_t bytes; bool is_output; };
+static StageArg stage_input(const void* host, size_t bytes) { return StageArg{const_cast<void*>(host), bytes, false}; } // (only read)
+static StageArg stage_output(void* host, size_t bytes) { return StageArg{host, bytes, true}; }
+template <int N, class Body>
+static int staged_host_call(DevBuf* pool, const StageArg (&args)[N], Body body) {
+    void* dev[N];
+    for (int k = 0; k < N; k++) {
+        if (args[k].host) HIP_TRY(pool[k].reserve(args[k].bytes));
+        dev[k] = args[k].host ? pool[k].p : nullptr;
+    }
+    for (int k = 0; k < N; k++)
+        if (args[k].host && !args[k].is_output) HIP_TRY(hipMemcpyAsync(dev[k], args[k].host, args[k].bytes, hipMemcpyHostToDevice, nullptr));
+    RR_TRY(body(dev));
+    for (int k = 0; k < N; k++)
+        if (args[k].host && args[k].is_output) HIP_TRY(hipMemcpyAsync(args[k].host, dev[k], args[k].bytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return RR_OK;
+}
+
+// THE entry of a record call, its arguments checked: `body()` under the scene's lock on stream st, which a call that ends early leaves
+// idle.  `intact`: the call reads the scene (a call that only filters records works on a broken one too).  `pointers`: the caller's
+// buffers of a device form; a host form has none and runs on the null stream.  `prepare()` is what the call refuses from the scene's
+// host state, before it waits for another stream or enqueues anything.
+template <class Prepare, class Body>
+static int record_call(rr_scene* s, const char* fn, bool intact, std::initializer_list<QueryPointer> pointers, hipStream_t st, Prepare prepare, Body body) {
+    RR_TRY(not_in_pass(s, fn));
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (intact) RR_TRY(check_intact(s));
+    HIP_TRY(hipSetDevice(s->device));
+    RR_TRY(check_query_pointers(s, fn, pointers));
+    RR_TRY(prepare());
+    RR_TRY(take_stream(s, st));
+    IdleOnExit idle(st);
+    return idle.done(body());
+}
+template <class Body>
+static int record_call(rr_scene* s, const char* fn, bool intact, std::initializer_list<QueryPointer> pointers, hipStream_t st, Body body) {
+    return record_call(s, fn, intact, pointers, st, [] { return (int)RR_OK; }, body);
 }
 
 // ---- closest-hit and shadow queries

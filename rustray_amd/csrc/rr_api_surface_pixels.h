@@ -1,7 +1,7 @@
 // rr_api_surface_pixels.h — the camera's surface per pixel: the G-buffer of the pixel-centre rays and the albedo rr_denoise_records takes.
 // Offers: rr_surface_pixels_device, rr_surface_pixels.
-// Needs:  rr_api_query.h (check_query_pointers, reserve_query_records, preset_reach, query_grid, stage_in, QW_*; writes rr_scene::query),
-//         rr_api_frame.h (launch_trace_closest, take_stream, IdleOnExit), rr_api_scene.h (ensure_tlas_reach), rr_api_handle.h (check_intact),
+// Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call, reserve_query_records, preset_reach, query_grid, QW_*; writes
+//         rr_scene::query), rr_api_frame.h (launch_trace_closest, take_stream), rr_api_scene.h (ensure_tlas_reach),
 //         rr_pixel_list.h (pixel_ray_reach, pixel_list_first_bad), kernels 5v and 5w of rr_kernels.hip.
 // Borrowed from rr_scene::frame: h_count[HC_REACH + 3] (the list form's one wait) and last_stream (take_stream).
 //
@@ -30,13 +30,9 @@ static int check_surface_pixels_args(const char* fn, bool device, const rr_scene
     if ((uintptr_t)io.out & 15u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: out_dev is not 16-byte aligned", fn);
     if ((uintptr_t)io.albedo & 3u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: albedo_out_dev is not 4-byte aligned", fn);
     if ((uintptr_t)io.pixel_xy & 3u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: pixel_xy_dev is not 4-byte aligned", fn);
-    struct Range { const void* p; uint64_t bytes; const char* name; };
-    const Range r[3] = {{io.pixel_xy, 4ull * n_pixels, "pixel_xy_dev"}, {io.out, 128ull * n_pixels, "out_dev"}, {io.albedo, 12ull * n_pixels, "albedo_out_dev"}};
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
-            if (r[a].p && r[b].p && (uintptr_t)r[a].p < (uintptr_t)r[b].p + r[b].bytes && (uintptr_t)r[b].p < (uintptr_t)r[a].p + r[a].bytes)
-                return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, r[b].name, r[a].name);
-    return RR_OK;
+    const ArgRange t[3] = {{io.pixel_xy, 4ull * n_pixels, "pixel_xy_dev", false, -1}, {io.out, 128ull * n_pixels, "out_dev", true, -1},
+                           {io.albedo, 12ull * n_pixels, "albedo_out_dev", true, -1}};
+    return check_arg_ranges(fn, t, 3, true, "");
 }
 
 // One call on buffers the scene's device can address, in stream order (the caller holds the lock).  `trusted`: the list was checked on
@@ -89,19 +85,14 @@ int rr_surface_pixels_device(rr_scene* s, const rr_camera* camera, const uint32_
     const SurfacePixelsIo io{pixel_xy, out, albedo_out};
     RR_TRY(check_surface_pixels_args(fn, true, s, camera, n_pixels, io));
     if (n_pixels == 0) return RR_OK;
-    RR_TRY(not_in_pass(s, fn));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, fn, {{pixel_xy, "pixel_xy_dev"}, {out, "out_dev"}, {albedo_out, "albedo_out_dev"}}));
     const hipStream_t st = (hipStream_t)hip_stream;
-    IdleOnExit idle(st);
-    return idle.done(surface_pixels_locked(s, camera, io, n_pixels, st, false));
+    return record_call(s, fn, true, {{pixel_xy, "pixel_xy_dev"}, {out, "out_dev"}, {albedo_out, "albedo_out_dev"}}, st,
+                       [&] { return surface_pixels_locked(s, camera, io, n_pixels, st, false); });
 } RR_GUARD_END("rr_surface_pixels_device")
 
-// The host form: the device form behind staging copies in buffers of the call, freed on return (hipFree waits for what a failed call left in
-// flight), on the null stream.  The list is checked here, before anything is uploaded; the caller's outputs are written by a finished
-// call only.
+// The host form: the device form behind the staging of every record call, in buffers of the call's own, freed on return (128 B per pixel
+// of answers are not kept resident), on the null stream.  The list is checked here, before anything is uploaded; the caller's outputs
+// are written by a finished call only.
 int rr_surface_pixels(rr_scene* s, const rr_camera* camera, const uint32_t* pixel_xy, uint32_t n_pixels, rr_surface_hit* out, float* albedo_out) try {
     const char* fn = "rr_surface_pixels";
     RR_TRY(check_surface_pixels_args(fn, false, s, camera, n_pixels, SurfacePixelsIo{pixel_xy, out, albedo_out}));
@@ -112,17 +103,11 @@ int rr_surface_pixels(rr_scene* s, const rr_camera* camera, const uint32_t* pixe
             return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, pixel_xy[bad] & 0xffffu, pixel_xy[bad] >> 16,
                         camera->width, camera->height);
     }
-    RR_TRY(not_in_pass(s, fn));
-    std::lock_guard<std::mutex> lk(s->mu);
-    RR_TRY(check_intact(s));
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf d_list, d_out, d_albedo;
-    if (pixel_xy) RR_TRY(stage_in(&d_list, pixel_xy, 4ull * n_pixels));
-    if (out) HIP_TRY(d_out.reserve(128ull * n_pixels));
-    if (albedo_out) HIP_TRY(d_albedo.reserve(12ull * n_pixels));
-    RR_TRY(surface_pixels_locked(s, camera, SurfacePixelsIo{d_list.as<uint32_t>(), d_out.as<rr_surface_hit>(), d_albedo.as<float>()}, n_pixels, nullptr, true));
-    if (out) HIP_TRY(hipMemcpyAsync(out, d_out.p, 128ull * n_pixels, hipMemcpyDeviceToHost, nullptr));
-    if (albedo_out) HIP_TRY(hipMemcpyAsync(albedo_out, d_albedo.p, 12ull * n_pixels, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return RR_OK;
+    const StageArg args[3] = {stage_input(pixel_xy, 4ull * n_pixels), stage_output(out, 128ull * n_pixels), stage_output(albedo_out, 12ull * n_pixels)};
+    return record_call(s, fn, true, {}, nullptr, [&] {
+        DevBuf own[3];
+        return staged_host_call(own, args, [&](void* const* d) {
+            return surface_pixels_locked(s, camera, SurfacePixelsIo{(const uint32_t*)d[0], (rr_surface_hit*)d[1], (float*)d[2]}, n_pixels, nullptr, true);
+        });
+    });
 } RR_GUARD_END("rr_surface_pixels")

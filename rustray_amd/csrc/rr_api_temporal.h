@@ -1,11 +1,12 @@
 // rr_api_temporal.h — temporal reprojection of a frame of records on the device: the previous call's result is gathered into the
 // current frame and the current records are blended into it, the step before rr_denoise_records in a frame-after-frame loop.
-// Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records.
-// Needs:  rr_api_query.h (check_query_pointers), rr_api_frame.h (take_stream, IdleOnExit), rr_api_adaptive.h (launch_record_bytes),
-//         rr_temporal.h, kernel 7e of rr_kernels.hip.
+// Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records; tp_frame (for rr_api_motion.h).
+// Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_temporal.h,
+//         kernel 7e of rr_kernels.hip.
 //
 // The call is ONE launch of k_accumulate_records (with or without halves) and, for the bytes, k_record_bytes, on the caller's stream,
-// not waited for.  It keeps no working data.  The host form is the device form behind staging copies (TemporalState::stage).
+// not waited for.  It keeps no working data.  The host form is the device form behind the staging of every record call
+// (staged_host_call, in the handle's pool).
 
 int rr_accumulate_default_params(rr_accumulate_params* out) try {
     if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "rr_accumulate_default_params: out is NULL");
@@ -55,37 +56,31 @@ static int check_accumulate_args(const char* fn, bool device, const rr_scene* s,
         return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_length_dev, motion_dev, length_out_dev and rgba8_out_dev must be 4-byte aligned", fn);
     // overlaps: an output with an input or with another output; out == records and halves_out == halves exactly are the in-place call
     const uint64_t n = (uint64_t)width * height;
-    struct Range { const void* p; uint64_t bytes; const char* name; };
-    const Range in[6] = {{io.records, 32u * n, "records"}, {io.halves, 64u * n, "halves"}, {io.history, 32u * n, "history"},
-                         {io.history_halves, 64u * n, "history_halves"}, {io.history_length, 4u * n, "history_length"}, {io.motion, 12u * n, "motion"}};
-    const Range outs[4] = {{io.out, 32u * n, "out"}, {io.halves_out, 64u * n, "halves_out"}, {io.length_out, 4u * n, "length_out"}, {io.rgba8, 4u * n, "rgba8_out"}};
-    auto overlap = [](const Range& a, const Range& b) {
-        return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < (uintptr_t)a.p + a.bytes;
-    };
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < 6; i++) {
-            const bool in_place = (o == 0 && i == 0 && io.out == io.records) || (o == 1 && i == 1 && io.halves_out == io.halves);
-            if (overlap(outs[o], in[i]) && !in_place)
-                return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s (only out == records and halves_out == halves, in place, are allowed)", fn, outs[o].name,
-                            in[i].name);
-        }
-        for (int o2 = o + 1; o2 < 4; o2++)
-            if (overlap(outs[o], outs[o2])) return fail(RR_ERR_INVALID_ARGUMENT, "%s: %s overlaps %s", fn, outs[o].name, outs[o2].name);
-    }
-    return RR_OK;
+    const ArgRange t[10] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {io.history, 32u * n, "history", false, -1},
+                            {io.history_halves, 64u * n, "history_halves", false, -1}, {io.history_length, 4u * n, "history_length", false, -1},
+                            {io.motion, 12u * n, "motion", false, -1}, {io.out, 32u * n, "out", true, 0}, {io.halves_out, 64u * n, "halves_out", true, 1},
+                            {io.length_out, 4u * n, "length_out", true, -1}, {io.rgba8, 4u * n, "rgba8_out", true, -1}};
+    return check_arg_ranges(fn, t, 10, false, " (only out == records and halves_out == halves, in place, are allowed)");
+}
+
+// the camera and the frame size as the frame constants of the kernels that turn a record's depth into a world position (k_accumulate_records,
+// k_motion_records); what else a kernel reads of them is its caller's to fill
+static TpFrame tp_frame(const rr_camera* cam) {
+    TpFrame f{};
+    memcpy(f.proj_inv, cam->projection_inverse, sizeof f.proj_inv);
+    memcpy(f.view_inv, cam->view_inverse, sizeof f.view_inv);
+    f.w = (float)cam->width; f.h = (float)cam->height;
+    f.width = (int)cam->width; f.height = (int)cam->height;
+    return f;
 }
 
 // the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
 static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io, hipStream_t st) {
     const uint32_t W = cam->width, H = cam->height;
-    TpFrame f{};
-    memcpy(f.proj_inv, cam->projection_inverse, sizeof f.proj_inv);
-    memcpy(f.view_inv, cam->view_inverse, sizeof f.view_inv);
+    TpFrame f = tp_frame(cam);
     memcpy(f.prev_clip, prm->prev_world_to_clip, sizeof f.prev_clip);
     memcpy(f.prev_eye, prm->prev_eye, sizeof f.prev_eye);
-    f.w = (float)W; f.h = (float)H;
     f.max_history = prm->max_history; f.normal_min = prm->normal_min; f.sigma_depth = prm->sigma_depth; f.snap = prm->snap;
-    f.width = (int)W; f.height = (int)H;
     const dim3 grid((W + DN_TILE_W - 1) / DN_TILE_W, (H + DN_TILE_H - 1) / DN_TILE_H), block(RR_BLOCK);
     if (io.halves)
         hipLaunchKernelGGL(k_accumulate_records<true>, grid, block, 0, st, f, (const float4*)io.records, (const float4*)io.halves, (const float4*)io.history,
@@ -105,49 +100,29 @@ static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumul
 int rr_accumulate_records_device(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_radiance* records, const rr_radiance* halves,
                                  const rr_radiance* history, const rr_radiance* history_halves, const float* history_length, const float* motion,
                                  rr_radiance* out, rr_radiance* halves_out, float* length_out, uint8_t* rgba8_out, void* hip_stream) try {
+    const char* fn = "rr_accumulate_records_device";
     const AccumulateIo io{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out};
-    RR_TRY(check_accumulate_args("rr_accumulate_records_device", true, s, camera, prm, io));
-    RR_TRY(not_in_pass(s, "rr_accumulate_records_device"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, "rr_accumulate_records_device", {{records, "records_dev"}, {halves, "halves_dev"}, {history, "history_dev"},
-                                                                     {history_halves, "history_halves_dev"}, {history_length, "history_length_dev"},
-                                                                     {motion, "motion_dev"}, {out, "out_dev"}, {halves_out, "halves_out_dev"},
-                                                                     {length_out, "length_out_dev"}, {rgba8_out, "rgba8_out_dev"}}));
+    RR_TRY(check_accumulate_args(fn, true, s, camera, prm, io));
     const hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(take_stream(s, st));
-    IdleOnExit idle(st);
-    return idle.done(accumulate_locked(s, camera, prm, io, st));
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {history, "history_dev"}, {history_halves, "history_halves_dev"},
+                                      {history_length, "history_length_dev"}, {motion, "motion_dev"}, {out, "out_dev"}, {halves_out, "halves_out_dev"},
+                                      {length_out, "length_out_dev"}, {rgba8_out, "rgba8_out_dev"}}, st, [&] { return accumulate_locked(s, camera, prm, io, st); });
 } RR_GUARD_END("rr_accumulate_records_device")
 
 int rr_accumulate_records(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_radiance* records, const rr_radiance* halves,
                           const rr_radiance* history, const rr_radiance* history_halves, const float* history_length, const float* motion, rr_radiance* out,
                           rr_radiance* halves_out, float* length_out, uint8_t* rgba8_out) try {
-    const AccumulateIo host{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out};
-    RR_TRY(check_accumulate_args("rr_accumulate_records", false, s, camera, prm, host));
-    RR_TRY(not_in_pass(s, "rr_accumulate_records"));
-    std::lock_guard<std::mutex> lk(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(take_stream(s, nullptr));
-    IdleOnExit idle(nullptr);
-    // the staging is the handle's (TemporalState::stage: grown, kept, used by the host form only, which returns with the stream idle):
-    // 0 records 32 B, 1 halves 64, 2 history 32, 3 history_halves 64, 4 history_length 4, 5 motion 12, 6 out 32, 7 halves_out 64,
-    // 8 length_out 4, 9 rgba8_out 4 per pixel, each only where the call has it
+    const char* fn = "rr_accumulate_records";
+    RR_TRY(check_accumulate_args(fn, false, s, camera, prm, AccumulateIo{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out}));
     const size_t n = (size_t)camera->width * camera->height;
-    DevBuf* g = s->temporal.stage;
-    const void* src[6] = {records, halves, history, history_halves, history_length, motion};
-    void* dst[4] = {out, halves_out, length_out, rgba8_out};
-    const size_t per_pixel[10] = {32, 64, 32, 64, 4, 12, 32, 64, 4, 4};
-    for (int k = 0; k < 10; k++)
-        if (k < 6 ? src[k] != nullptr : dst[k - 6] != nullptr) HIP_TRY(g[k].reserve(per_pixel[k] * n));
-    for (int k = 0; k < 6; k++)
-        if (src[k]) HIP_TRY(hipMemcpyAsync(g[k].p, src[k], per_pixel[k] * n, hipMemcpyHostToDevice, nullptr));
-    const AccumulateIo dev{g[0].as<rr_radiance>(), halves ? g[1].as<rr_radiance>() : nullptr, history ? g[2].as<rr_radiance>() : nullptr,
-                           history_halves ? g[3].as<rr_radiance>() : nullptr, history_length ? g[4].as<float>() : nullptr, motion ? g[5].as<float>() : nullptr,
-                           g[6].as<rr_radiance>(), halves_out ? g[7].as<rr_radiance>() : nullptr, g[8].as<float>(), rgba8_out ? g[9].as<uint8_t>() : nullptr};
-    RR_TRY(accumulate_locked(s, camera, prm, dev, nullptr));
-    for (int k = 6; k < 10; k++)
-        if (dst[k - 6]) HIP_TRY(hipMemcpyAsync(dst[k - 6], g[k].p, per_pixel[k] * n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return idle.done(RR_OK);
+    const StageArg args[10] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(history, 32 * n), stage_input(history_halves, 64 * n),
+                               stage_input(history_length, 4 * n), stage_input(motion, 12 * n), stage_output(out, 32 * n), stage_output(halves_out, 64 * n),
+                               stage_output(length_out, 4 * n), stage_output(rgba8_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const AccumulateIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const rr_radiance*)d[2], (const rr_radiance*)d[3], (const float*)d[4],
+                                   (const float*)d[5], (rr_radiance*)d[6], (rr_radiance*)d[7], (float*)d[8], (uint8_t*)d[9]};
+            return accumulate_locked(s, camera, prm, dev, nullptr);
+        });
+    });
 } RR_GUARD_END("rr_accumulate_records")

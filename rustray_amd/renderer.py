@@ -724,6 +724,18 @@ def _ray_tensor(device_scene: capi.DeviceScene, t, name: str, shape_tail=(3,), d
     return t
 
 
+def _frame_tensors(device_scene: capi.DeviceScene, width: int, height: int, tensors: dict, required=()) -> dict:
+    """{name: (tensor or None, shape_tail)} as {name: what _ray_tensor makes of it, or None where the caller left it out and it is not
+    `required`}: every tensor holds the width * height entries of the frame; raises otherwise."""
+    n = int(width) * int(height)
+    checked = {}
+    for name, (value, tail) in tensors.items():
+        checked[name] = t = _ray_tensor(device_scene, value, name, shape_tail=tail) if value is not None or name in required else None
+        if t is not None and int(t.shape[0]) != n:
+            raise ValueError(f"{name}: {int(t.shape[0])} entries for a frame of {int(width)}x{int(height)}")
+    return checked
+
+
 def _hit_views(rec, first: str) -> dict:
     """An (n, 5) int32 tensor of 20-byte hit records and its named column views (no copy): `first` (hit / occluded), item_index,
     object_id, face_id as int32 and distance viewed as float32."""
@@ -973,12 +985,9 @@ def denoise_torch(device_scene: capi.DeviceScene, width: int, height: int, recor
     request variance (n,) float32 and rgba (n, 4) uint8).  in_place: the filtered records are written over `records`."""
     import torch
     n = int(width) * int(height)
-    rec = _ray_tensor(device_scene, records, "records", shape_tail=(8,))
-    hv = _ray_tensor(device_scene, halves, "halves", shape_tail=(2, 8)) if halves is not None else None
-    al = _ray_tensor(device_scene, albedo, "albedo", shape_tail=(3,)) if albedo is not None else None
-    for t, name in ((rec, "records"), (hv, "halves"), (al, "albedo")):
-        if t is not None and int(t.shape[0]) != n:
-            raise ValueError(f"{name}: {int(t.shape[0])} entries for a frame of {width}x{height}")
+    t = _frame_tensors(device_scene, width, height, dict(records=(records, (8,)), halves=(halves, (2, 8)), albedo=(albedo, (3,))),
+                       required=("records",))
+    rec, hv, al = t["records"], t["halves"], t["albedo"]
     dev = torch.device("cuda", device_scene.device)
     with torch.cuda.device(dev):
         out = rec if in_place else torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
@@ -1074,13 +1083,9 @@ def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, 
     (n,) [, rgba (n, 4) uint8]).  in_place: written over `records` and `halves`; out: dict(records, halves, length) of tensors to write."""
     import torch
     n = int(cam.width) * int(cam.height)
-    tensors = dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)), history_halves=(history_halves, (2, 8)),
-                   history_length=(history_length, ()), motion=(motion, (3,)))
-    t = {}
-    for name, (value, tail) in tensors.items():
-        t[name] = _ray_tensor(device_scene, value, name, shape_tail=tail) if value is not None else None
-        if t[name] is not None and int(t[name].shape[0]) != n:
-            raise ValueError(f"{name}: {int(t[name].shape[0])} entries for a frame of {int(cam.width)}x{int(cam.height)}")
+    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)),
+                                                                  history_halves=(history_halves, (2, 8)), history_length=(history_length, ()),
+                                                                  motion=(motion, (3,))))
     dev = torch.device("cuda", device_scene.device)
     ptr = lambda x: x.data_ptr() if x is not None else None
     with torch.cuda.device(dev):
@@ -1108,9 +1113,7 @@ def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_
     a synchronisation: dict(motion (n, 3), world (n, 3) or None) -- motion is what accumulate_torch takes."""
     import torch
     n = int(cam.width) * int(cam.height)
-    rec = _ray_tensor(device_scene, records, "records", shape_tail=(8,))
-    if int(rec.shape[0]) != n:
-        raise ValueError(f"records: {int(rec.shape[0])} entries for a frame of {int(cam.width)}x{int(cam.height)}")
+    rec = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,))), required=("records",))["records"]
     dev = torch.device("cuda", device_scene.device)
     with torch.cuda.device(dev):
         motion = torch.empty((n, 3), dtype=torch.float32, device=dev)

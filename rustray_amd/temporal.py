@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .pixel_rays import pixel_rays
+from .pixel_rays import camera_matrices, dot, pixel_rays, row
 
 F = np.float32
 EPS = F(2.0 ** -20)
@@ -55,25 +55,10 @@ def previous_view(camera):
     return (np.linalg.inv(pi) @ np.linalg.inv(vi)).astype(F), vi[:3, 3].astype(F)
 
 
-def _camera_matrices(cam):
-    """The two inverses of a camera.Camera or an rr_camera, column-major float32 (16,), and (width, height)."""
-    if hasattr(cam, "c_struct"):
-        cam = cam.c_struct()
-    return np.array(cam.projection_inverse[:], F), np.array(cam.view_inverse[:], F), int(cam.width), int(cam.height)
-
-
-def _row(m, r, x, y, z, w):
-    return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w
-
-
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
 def world_positions(records, cam) -> np.ndarray:
     """(n, 3) float32: world_p = o + d * depth_p of every record of a whole frame of `cam`, o and d the pinhole ray through the pixel's
     centre, in the header's arithmetic (step 2)."""
-    _, _, W, H = _camera_matrices(cam)
+    _, _, W, H = camera_matrices(cam)
     rec = np.ascontiguousarray(records, F).reshape(H * W, 8)
     o, d = pixel_rays(cam)
     with np.errstate(all="ignore"):
@@ -121,8 +106,8 @@ def motion_records(records, cam, item_ids, prev_trans, cur_trans_inv):
                 continue
             w = world[at]
             a_cm, b_cm = a.T.reshape(16), b.T.reshape(16)      # column-major, as the C arrays
-            local = [_row(b_cm, r, w[:, 0], w[:, 1], w[:, 2], one) for r in range(3)]
-            m = np.stack([_row(a_cm, r, local[0], local[1], local[2], one) - w[:, r] for r in range(3)], axis=-1).astype(F)
+            local = [row(b_cm, r, w[:, 0], w[:, 1], w[:, 2], one) for r in range(3)]
+            m = np.stack([row(a_cm, r, local[0], local[1], local[2], one) - w[:, r] for r in range(3)], axis=-1).astype(F)
             m[~np.isfinite(m).all(-1)] = F(0)
             motion[at] = m
     return motion, world
@@ -136,7 +121,7 @@ def accumulate_records(records, halves, history, history_halves, history_length,
     pixel's history came from)."""
     prm = params or AccumulateParams()
     prm.check()
-    pi, vi, W, H = _camera_matrices(cam)
+    pi, vi, W, H = camera_matrices(cam)
     n = W * H
     rec = np.ascontiguousarray(records, F).reshape(n, 8)
     hv = None if halves is None else np.ascontiguousarray(halves, F).reshape(n, 2, 8)
@@ -167,14 +152,14 @@ def accumulate_records(records, halves, history, history_halves, history_length,
         if motion is not None:
             prev = prev + np.ascontiguousarray(motion, F).reshape(n, 3)
         px, py, pz = prev[:, 0], prev[:, 1], prev[:, 2]
-        cx, cy, cw = _row(m, 0, px, py, pz, one), _row(m, 1, px, py, pz, one), _row(m, 3, px, py, pz, one)
+        cx, cy, cw = row(m, 0, px, py, pz, one), row(m, 1, px, py, pz, one), row(m, 3, px, py, pz, one)
         alive = fin & valid & (cw > EPS)
         fx = ((cx / cw) * half + half) * F(W) - half
         fy = (half - (cy / cw) * half) * F(H) - half
         alive &= np.isfinite(fx) & np.isfinite(fy)
         alive &= (fx > F(-1)) & (fx < F(W)) & (fy > F(-1)) & (fy < F(H))
         e = prev - eye
-        dist = np.sqrt(_dot(e, e))
+        dist = np.sqrt(dot(e, e))
         z_exp = dist - dist / cw
 
         fx, fy = np.where(alive, fx, F(0)), np.where(alive, fy, F(0))   # (so that the integer conversions below are defined)
@@ -196,7 +181,7 @@ def accumulate_records(records, halves, history, history_halves, history_length,
             q = np.where(inside, qy * W + qx, 0)
             taken = alive & (k < n_taps) & inside
             n_q = hist[q, 4:7]
-            taken &= (hist[q, 7].view(np.uint32) == ids_p) & np.isfinite(n_q).all(-1) & (_dot(n_p, n_q) >= normal_min)
+            taken &= (hist[q, 7].view(np.uint32) == ids_p) & np.isfinite(n_q).all(-1) & (dot(n_p, n_q) >= normal_min)
             taken &= np.isfinite(hist[q, 0:3]).all(-1) & np.isfinite(hist[q, 3]) & (np.abs(z_exp - hist[q, 3]) <= sigma_depth * z_exp + EPS)
             taken &= hist_len[q] > 0
             if hv is not None:
