@@ -57,7 +57,8 @@ extern "C" {
  * came after those in the same way: a version-3 library may lack these three as well.
  * rr_motion_records and rr_motion_records_device came after those, without a struct of their own: a version-3 library may lack these two
  * as well.
- * rr_surface_pixels and rr_surface_pixels_device came after those in the same way: a version-3 library may lack these two as well. */
+ * rr_surface_pixels and rr_surface_pixels_device came after those in the same way: a version-3 library may lack these two as well.
+ * rr_albedo_pixels and rr_albedo_pixels_device came after those in the same way: a version-3 library may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1195,6 +1196,51 @@ int rr_surface_pixels(rr_scene* scene, const rr_camera* camera, const uint32_t* 
                       rr_surface_hit* out /* n_pixels, or NULL */, float* albedo_out /* n_pixels * 3, or NULL */);
 int rr_surface_pixels_device(rr_scene* scene, const rr_camera* camera, const uint32_t* pixel_xy_dev /* n_pixels, or NULL */, uint32_t n_pixels,
                              rr_surface_hit* out_dev /* n_pixels, or NULL */, float* albedo_out_dev /* n_pixels * 3, or NULL */, void* hip_stream);
+
+/* The frame's albedo per pixel: the mean, over the S = config->samples primary rays rr_render_pixels traces for the pixel, of the base
+ * colour at each ray's first hit -- the albedo the pixel's colour was actually modulated by.  rr_surface_pixels gives the one colour
+ * under the pixel's centre; a pixel on a texture edge, a silhouette or out of focus holds a mix, and rr_denoise_records divides by the
+ * wrong value there.  This is the array to pass as its `albedo` instead.
+ * RAYS.  Ray (p, s) is the primary ray rr_render_pixels derives for list entry (or pixel) p and frame sample s: the same slot tables, the
+ *   same sub-sample table (sample_xy, or the built-in one when NULL) with the cell size of config->samples, the same depth-of-field
+ *   branch (focal_length and aperture_size both above 1).  Of the config, samples, focal_length and aperture_size are used; the whole
+ *   config is checked as every frame call checks it, then seed, monte_carlo, max_recursion, the fog and gamma_correction are ignored.
+ *   Nothing is drawn from the generator: the call is deterministic.
+ * TERM.  a(p, s) = base_color[0 .. 2] of the rr_surface_hit rr_surface_rays writes for that (normalised) ray at depth 1 under the same
+ *   handle state -- the same evaluation in full, so the bits are the record's; (0, 0, 0) for a miss, as a miss adds 0 to the pixel's colour.
+ * SUM.  Exactly rr_radiance.color's: every term is clamped to +-32768, scaled by 2^24 and rounded to nearest-even by itself, the terms are
+ *   added as integers, and albedo_out[3p + c] = (float)(sum * 2^-24) / (float)S.  A NaN term adds 0 and makes the channel NaN, a +inf
+ *   (-inf) term makes it +inf (-inf), both in one pixel and channel make it NaN -- as a frame's colour.  Integer adds commute: the
+ *   result does not depend on batching, sample groups, chunks or rr_tuning.  rustray_amd/albedo.py: mean_albedo follows this text in numpy.
+ * LIST AND WHOLE FRAME are rr_render_pixels': pixel_xy NULL needs n_pixels == width * height and pixel (x, y) goes to index y * width + x;
+ *   else entry i = x | y << 16 answers index i, duplicates and any order allowed, a length that is no multiple of 64 / G runs with G = 1,
+ *   and an entry outside the frame is RR_ERR_INVALID_ARGUMENT naming its index, with nothing written.  n_pixels == 0 returns RR_OK and
+ *   touches nothing; n_pixels > 2^30 is RR_ERR_UNSUPPORTED before anything is allocated; albedo_out == NULL is RR_ERR_INVALID_ARGUMENT.
+ *   The checks come in this order: scene, camera, config and table as rr_render checks them; albedo_out; the pixel limit; n_pixels == 0
+ *   (RR_OK); n_pixels against the frame without a list; (device form) alignment, then overlap; (host form) the list; the scene; the
+ *   pointers; (device form) the list.
+ * A FRAME CALL in the sense of rr_render_pixels: the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene; RR_ERR_DEVICE
+ *   on a scene that a failed update left broken; rr_scene_last_stats afterwards reports primary_rays = n_pixels * samples and zero
+ *   secondary_rays, shadow_rays and shaded_hits.  cancel: as rr_shade_rays.  The frames before and after are bit-identical: the list's
+ *   slot table is the call's own, and the accumulators are cleared by every frame.
+ * rr_albedo_pixels_device: pixel_xy_dev n_pixels entries or NULL and albedo_out_dev 3 * n_pixels floats, memory the scene's device can
+ *   address, under every rule of rr_render_pixels_device: pointers classified before any launch (RR_ERR_INVALID_ARGUMENT naming the
+ *   argument), both 4-byte aligned, an overlap of the two refused; camera, config and sample_xy are host memory.  The work is enqueued on
+ *   `hip_stream` in stream order and the list may come from that stream unsynchronised: it is copied into the handle's buffer first, so
+ *   nothing the launches read after the return is the caller's.  The call waits where a frame waits for its constants and, with a list,
+ *   once for 4 bytes: the first index outside the frame.  It never waits for the size of a level, because nothing spawns.  A call that
+ *   ends early leaves the stream idle.  Device memory, kept by the handle until rr_scene_destroy and shared with the frames: 28 B per
+ *   pixel of accumulators (the colour planes and the flags), 16 B of hit records per primary ray of a batch, 12 B per list entry; no ray
+ *   arena and no shadow queue is sized for the call.
+ * rr_albedo_pixels: the same on HOST pointers, the device form on the null stream behind staging copies in buffers of the call (4 B of
+ *   list and 12 B of answer per pixel), freed on return; the list is checked before anything is uploaded, and the call returns with the
+ *   output written. */
+int rr_albedo_pixels(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* or NULL */,
+                     const uint32_t* pixel_xy /* or NULL */, uint32_t n_pixels,
+                     float* albedo_out /* n_pixels * 3 */, const volatile int* cancel);
+int rr_albedo_pixels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* or NULL */,
+                            const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels,
+                            float* albedo_out_dev /* n_pixels * 3 */, void* hip_stream, const volatile int* cancel);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

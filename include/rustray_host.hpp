@@ -716,6 +716,40 @@ public:
         }
         return denoise(records.data(), halves.data(), with_albedo ? guide.data() : nullptr, params, nullptr, rgba8);
     }
+    // The same with the albedo guide named: NONE and CENTRE are with_albedo = false and true above, bit for bit; MEAN takes mean_albedo(),
+    // one rr_albedo_pixels call with this frame's config in place of the rr_surface_pixels call.
+    enum class AlbedoGuide { NONE, CENTRE, MEAN };
+    std::vector<rr_radiance> render_denoised(AlbedoGuide guide_kind, const rr_denoise_params* params = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
+                                             std::vector<rr_radiance>* noisy = nullptr) const {
+        if (guide_kind != AlbedoGuide::MEAN) return render_denoised(params, rgba8, noisy, guide_kind == AlbedoGuide::CENTRE);
+        std::vector<rr_radiance> halves;
+        const std::vector<rr_radiance> records = render_pixel_parts(nullptr, 0, 2, &halves);
+        if (records.empty()) return records;
+        if (noisy) *noisy = records;
+        const std::vector<float> guide = mean_albedo();
+        if (guide.empty()) return std::vector<rr_radiance>();
+        return denoise(records.data(), halves.data(), guide.data(), params, nullptr, rgba8);
+    }
+
+    // The albedo of the whole frame as the frame of config.samples samples sees it (rr_albedo_pixels): width * height * 3 floats in
+    // row-major order, per pixel the mean over the frame's primary rays of the base colour at each ray's first hit -- at an edge pixel the
+    // mix its colour was modulated by, where albedo() holds the colour under the pixel's centre.  empty = refused or failed.
+    std::vector<float> mean_albedo() const {
+        std::vector<float> out;
+        const size_t n = (size_t)camera.width * camera.height;
+        if (n == 0 || n > ((size_t)1 << 30)) return out;
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        out.assign(3 * n, 0.0f);
+        if (rr_albedo_pixels(scene->handle(), &cam, &c, nullptr, nullptr, (uint32_t)n, out.data(), nullptr) != RR_OK) out.clear();
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_albedo_pixels_device): xy_dev nullptr = the whole frame (n_pixels = width * height)
+    int mean_albedo_device(const uint32_t* xy_dev, uint32_t n_pixels, float* albedo_out_dev, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_albedo_pixels_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, albedo_out_dev, hip_stream, cancel);
+    }
 
     // The G-buffer of this camera (rr_surface_pixels): the rr_surface_hit record of the pinhole ray through the centre of each pixel --
     // xy[i] = x | y << 16, n_pixels entries, or xy nullptr for the whole frame in row-major order -- byte for byte what surface() gives

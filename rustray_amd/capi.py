@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -54,7 +54,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -177,6 +177,10 @@ def lib():
         if hasattr(L, "rr_surface_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
             L.rr_surface_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rr_surface_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rr_albedo_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            L.rr_albedo_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rr_albedo_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -598,6 +602,23 @@ class DeviceScene:
         records (16-byte aligned, or None) and n x 3 float32 of albedo (or None), all raw device pointers; enqueued on `stream_ptr`.  The
         whole-frame form is not waited for."""
         _check(lib().rr_surface_pixels_device(self._h, C.byref(cam), _ptr(pixel_xy_ptr), C.c_uint32(n), _ptr(out_ptr), _ptr(albedo_ptr), _ptr(stream_ptr)))
+
+    def albedo_pixels(self, cam: rr_camera, cfg: rr_config, pixels=None, sample_xy=None, cancel=None):
+        """rr_albedo_pixels: the frame's albedo per pixel -- the mean over the cfg.samples primary rays render_pixels traces for the pixel of
+        the base colour at each ray's first hit (albedo.mean_albedo states the sum), for the pixels named in `pixels` (as render_pixels takes
+        them) or for every pixel of the frame in row-major order (None) -> (n, 3) float32, the array rr_denoise_records takes as `albedo`."""
+        n, xy, xy_p = _pixel_list(cam, pixels)
+        alb = np.zeros((max(n, 1), 3), np.float32)
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_albedo_pixels(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), _data(alb), _flag(cancel)))
+        return alb[:n]
+
+    def albedo_pixels_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, albedo_ptr, stream_ptr=None, sample_xy=None, cancel=None):
+        """rr_albedo_pixels_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height) and n_pixels x 3
+        float32 of albedo, raw device pointers, both 4-byte aligned; enqueued on `stream_ptr`."""
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_albedo_pixels_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), _ptr(albedo_ptr),
+                                             _ptr(stream_ptr), _flag(cancel)))
 
     def render_pixels(self, cam: rr_camera, cfg: rr_config, pixels=None, sample_xy=None, rgba8: bool = False, cancel=None):
         """rr_render_pixels: Raytracing::render(x, y) before its clamp, for the pixels named in `pixels` -- an (n, 2) integer array of

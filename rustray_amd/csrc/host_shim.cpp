@@ -378,6 +378,23 @@ extern "C" int rh_surface_pixels_device(void* h, float fov, const float* eye, co
                                         uint32_t w, uint32_t hgt, const uint32_t* xy_dev, uint32_t n, rr_surface_hit* out_dev, float* albedo_out_dev, void* stream) {
     return rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt).surface_pixels_device(xy_dev, n, out_dev, albedo_out_dev, stream);
 }
+// rh_render_denoised_mean_albedo: Raytracing::render_denoised(AlbedoGuide::MEAN); out = w * h records, noisy = the same or NULL,
+// albedo_out = w * h * 3 floats of Raytracing::mean_albedo or NULL; returns 0, or -1 when a call was refused.
+extern "C" int rh_render_denoised_mean_albedo(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                              uint32_t w, uint32_t hgt, const rr_denoise_params* params, rr_radiance* out, rr_radiance* noisy, float* albedo_out) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> raw;
+    const std::vector<rr_radiance> r = rt.render_denoised(Raytracing::AlbedoGuide::MEAN, params, nullptr, noisy ? &raw : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
+    if (albedo_out) {
+        const std::vector<float> a = rt.mean_albedo();
+        if (a.empty()) return -1;
+        std::memcpy(albedo_out, a.data(), a.size() * 4);
+    }
+    return 0;
+}
 // Raytracing::accumulate: records = w * h, halves = w * h * 2 or NULL, history / history_halves / history_length = the previous call's
 // out / halves_out / length_out or all NULL (the first frame), params or NULL for the defaults, motion = w * h * 3 floats or NULL; out,
 // halves_out (with halves), length_out, rgba8 or NULL; returns 0, or -1 when the call was refused.

@@ -1,7 +1,8 @@
 // rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
 // Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
 //         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
-//         run_level (with level 1 in stages on three streams); take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
+//         run_level (with level 1 in stages on three streams; with FrameIo::albedo level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h);
+//         take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
 //         WHOLE_FRAME, IdleOnExit, fill_pixel_slots, render_region_locked (the pixel queries and the adaptive calls are its other callers);
 //         rr_render_region_device, rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, PassSums,
 //         collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
@@ -170,6 +171,10 @@ struct FrameIo {
     // own_list = the list is the library's own, made from pixels it has checked (no wait for a first bad entry); no_resolve = the caller
     // reads the accumulators itself
     const DAccum* resident = nullptr; bool own_list = false, no_resolve = false;
+    // rr_albedo_pixels (rr_api_albedo_pixels.h): level 1 ends in k_albedo_level1 instead of the shade and shadow kernels, nothing spawns, only
+    // the colour planes are accumulated, and k_resolve_albedo writes three floats per pixel here -- at the entry's index for a list, at
+    // y * width + x for a region
+    float* albedo = nullptr;
 };
 static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
     FrameIo io;
@@ -301,6 +306,16 @@ static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool
                   want_id ? s->frame.acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
     return RR_OK;
 }
+// the same for a call that sums colours only (rr_albedo_pixels): the colour planes and the flags, zeroed; no aux plane is reserved or touched
+static int reset_colour_accumulators(rr_scene* s, uint32_t npix, hipStream_t st, DAccum* acc) {
+    HIP_TRY(s->frame.acc_rgb.reserve((size_t)npix * 24));
+    HIP_TRY(s->frame.acc_flags.reserve((size_t)npix * 4));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_flags.p, 0, (size_t)npix * 4, st));
+    HIP_TRY(hipMemsetAsync(s->frame.acc_rgb.p, 0, (size_t)npix * 24, st));
+    HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
+    *acc = DAccum{s->frame.acc_rgb.as<long long>(), nullptr, nullptr, nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
+    return RR_OK;
+}
 
 // Ray memory (rr_frame_plan.h): a quarter of what is free on the device, at most 64 GB (MI355X has 288 GB of HBM3E),
 // unless rr_tuning::queue_budget_bytes says otherwise.  Memory already held by this scene's arena counts as free.
@@ -333,12 +348,14 @@ static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t v
 }
 
 // the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue
-static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan) {
+// (hits_only: a call whose level 1 spawns nothing and asks no light -- rr_albedo_pixels -- needs the hit records alone: no arena, no shadow queue)
+static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan, bool hits_only = false) {
     uint64_t budget = 0;
     RR_TRY(queue_budget(s, &budget));
     const FramePlan& p = *plan = plan_frame(FramePlanInputs{npix, cfg->samples, cfg->max_recursion, budget, s->tuning.sample_group, min_passes,
                                                             s->frame.arena_factor, s->data.n_enabled_lights, s->tuning.shade_chunk_rays});
     HIP_TRY(s->frame.hit1.reserve(p.B * 16));
+    if (hits_only) return RR_OK;
     // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
     const Level1Stages sp = level1_stages(s, p.B);
     return grow_ray_queues(s, p.M, std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need);
@@ -387,6 +404,7 @@ struct FrameRun {
     int shadow_grid, shade_grid_max;
     const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, the pixel list of rr_render_pixels, or the stream ids of rr_shade_rays
     bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
+    bool albedo_only = false;          // rr_albedo_pixels: level 1 ends in k_albedo_level1 (R = 0: the level spawns nothing; never in stages)
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
     }
@@ -550,7 +568,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
     const uint64_t slice = level_slice(M, child_base, n, d, f.R);
     // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams (per slice of the level)
     const auto staged = [&](uint64_t hits) {
-        return level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
+        return !f.albedo_only && level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
                s->data.view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, hits).overlapped();
     };
     // ... and where the level is ONE slice, its closest hits stage by stage on a third stream; every other level in one launch, here
@@ -574,6 +592,12 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
             const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
             const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);
+            if (f.albedo_only) { // the ending of level 1 of rr_albedo_pixels: no shadow slots, no children, no counters of its own
+                if (!l1 || spawns || !f.acc.rgb || !f.acc.flags) return fail(RR_ERR_DEVICE, "internal: albedo launch outside a level 1 that ends its paths");
+                ScopedTimer t(s, st, TK_SHADE, true);
+                hipLaunchKernelGGL(k_albedo_level1, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.pr, qin.hit, count, (uint32_t)c0, (uint32_t)c1, f.acc);
+                continue;
+            }
             // level 1: shadow slots of this chunk = L x (the chunk padded to whole workgroup iterations), one validity word per 64
             // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
             // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
@@ -629,7 +653,9 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
 
 static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& io) {
     const uint32_t npix = fr.n_region_pixels;
-    if (io.parts) hipLaunchKernelGGL(k_resolve_pixel_parts, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, io.pixel_xy ? 0u : 1u,
+    if (io.albedo) hipLaunchKernelGGL(k_resolve_albedo, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
+                                      (uint32_t*)io.albedo);
+    else if (io.parts) hipLaunchKernelGGL(k_resolve_pixel_parts, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, io.pixel_xy ? 0u : 1u,
                                      (float4*)io.radiance, (float4*)io.parts);
     else if (io.radiance) hipLaunchKernelGGL(k_resolve_pixels, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
                                         (float4*)io.radiance, (uint32_t*)io.rgba8);
@@ -717,18 +743,21 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     fr.samples = used;
     DAccum acc;
     const bool radiance = io.radiance != nullptr; // rr_radiance holds all three aux means
-    RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc,
-                              io.resident));
+    const bool albedo_only = io.albedo != nullptr; // rr_albedo_pixels: colour sums alone, level 1 alone
+    if (albedo_only) RR_TRY(reset_colour_accumulators(s, npix, st, &acc));
+    else RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc,
+                                   io.resident));
     FramePlan plan;
     rr_config plan_cfg = *cfg; // with parts the plan sees K x the slots and 1 / K of the samples; the frame constants keep the frame's S
     plan_cfg.samples = (decltype(plan_cfg.samples))((used - io.samples_from) >> io.lg_parts); // (a sample group must divide THIS range: plan_frame)
-    RR_TRY(plan_queues(s, npix, &plan_cfg, hook ? hook->min_passes : 0u, &plan));
+    if (albedo_only) plan_cfg.max_recursion = 0u;
+    RR_TRY(plan_queues(s, npix, &plan_cfg, hook ? hook->min_passes : 0u, &plan, albedo_only));
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
-    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
+    FrameRun f{s, st, plan, albedo_only ? 0u : cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
                CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, cancel,
                s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = slot_xy;
+    f.slot_xy = slot_xy; f.albedo_only = albedo_only;
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
     RR_TRY(run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix));
     if (!io.no_resolve) launch_resolve(f, fr, io);

@@ -1715,6 +1715,78 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_pixels(DSceneView sc, cons
     }
 }
 
+// ---------------------------------------------------------------------------
+// kernels 5x, 5y: the frame's albedo per pixel (rr_albedo_pixels): the base colour at the first hit of every primary ray of the frame,
+// summed per pixel in the frame's own accumulators
+// ---------------------------------------------------------------------------
+// 5x: the ending of depth level 1 for this call, where k_shade<true> stands in a frame.  Hit i of [chunk_begin, min(*count, chunk_end)) is
+// the hit record k_trace_closest<true> wrote for primary index i of the batch; the ray is derived again (primary_ray: the inputs and the
+// instruction sequence of the closest-hit kernel, so the same bits), the evaluation is k_surface_pixels' -- item and material per lane,
+// surface_at in full, of which only base_color.xyz is used (the compiler drops the normal map, the roughness and the other colours) -- and
+// the term goes the way every colour term of a frame goes: fix_add at scale 2^24 with the colour clamp (to_fix for a term beyond 2^25),
+// the non-finite flags, accum_merged.  The samples of a pixel sit in neighbouring lanes, so the segmented merge applies unchanged.
+// All 64 lanes of every wave reach accum_merged (the loop bound is block-uniform): lanes past the end, misses and item indices out of
+// range pass pix = 0xffffffff.  No children, no shadow slots, no counters: RR_CNT_PRIMARY is the closest-hit kernel's.
+__global__ __launch_bounds__(RR_BLOCK) void k_albedo_level1(const DShadeConst* __restrict__ kc, DPrimary pr, const uint4* __restrict__ hit1,
+                                                            const uint32_t* __restrict__ count, uint32_t chunk_begin, uint32_t chunk_end, DAccum acc) {
+    const DSceneView& sc = kc->sc;
+    const DFrame& fr = kc->fr;
+    const uint32_t n = min(*count, chunk_end);
+    __shared__ float s_lut[256]; // the u8 -> f32 table next to the lanes, as in k_shade
+    s_lut[threadIdx.x] = c_u8_to_f32[threadIdx.x];
+    __syncthreads();
+    for (uint32_t base = chunk_begin + blockIdx.x * RR_BLOCK; base < n; base += gridDim.x * RR_BLOCK) { // block-uniform
+        const uint32_t i = base + threadIdx.x;
+        uint32_t sum_pix = 0xffffffffu;
+        int sum_r = 0, sum_g = 0, sum_b = 0;
+        if (i < n) {
+            const uint4 h = hit1[i];
+            if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
+                f3 ro, rd; uint32_t pix, smp;
+                primary_ray(fr, kc->ps, pr, i, &ro, &rd, &pix, &smp);
+                const DItem& it = rr_global(sc.items)[h.y];
+                const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
+                const SurfaceAt s = surface_at(sc, it, m, ro, rd, __uint_as_float(h.x), h.z);
+                const float ar = s.base_color.x, ag = s.base_color.y, ab = s.base_color.z;
+                sum_pix = pix;
+                const uint32_t nf = nonfinite_flags(ar, ag, ab);
+                fix_add(sum_r, ar, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb, pix); fix_add(sum_g, ag, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + acc.n, pix);
+                fix_add(sum_b, ab, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + 2ull * acc.n, pix);
+                if (nf) atomicOr(&acc.flags[pix], nf); // rare: a non-finite base colour
+            }
+        }
+        accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
+    }
+}
+
+// 5y: the colour sums of every accumulator slot -> three floats per pixel through resolve_color, what k_resolve_pixels puts into
+// rr_radiance.color.  Index o of slot p: the slot itself for a pixel list, y * width + x of the slot's pixel for a whole frame (from_xy),
+// as k_resolve_pixels.  The floats leave through a 3 KB image as the albedo of k_surface_pixels does: consecutive dwords for a list, runs
+// of 24 dwords (a row of an 8x8 block) for a whole frame.  One workgroup per 256 slots.
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_albedo(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, uint32_t from_xy, uint32_t* __restrict__ albedo) {
+    __shared__ uint32_t s_albedo[3 * RR_BLOCK];
+    __shared__ uint32_t s_target[RR_BLOCK];
+    const uint32_t tid = threadIdx.x, base = blockIdx.x * RR_BLOCK, npix = fr.n_region_pixels;
+    const uint32_t p = base + tid; // accumulator slot
+    const uint32_t in_round = base < npix ? min(npix - base, (uint32_t)RR_BLOCK) : 0u; // slots of this workgroup
+    if (p < npix) {
+        uint32_t o = p;
+        if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
+        const float n = (float)fr.samples;
+        const uint32_t nf = acc.flags[p];
+#pragma unroll
+        for (int k = 0; k < 3; k++) s_albedo[3u * tid + k] = __float_as_uint(resolve_color(acc, p, nf, k, n));
+        s_target[tid] = o;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        const uint32_t word = k * RR_BLOCK + tid; // word of the image: channel word % 3 of slot word / 3 of this workgroup
+        const uint32_t t = word / 3u;
+        if (t < in_round) albedo[3ull * s_target[t] + (word - 3u * t)] = s_albedo[word];
+    }
+}
+
 // 5g: stream ids 0 .. n - 1 (rr_shade_rays_device without the caller's)
 __global__ __launch_bounds__(RR_BLOCK) void k_iota(uint32_t* __restrict__ ids, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

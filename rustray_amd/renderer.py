@@ -195,25 +195,47 @@ class Raytracing:
         base_color of surface_pixels(), 0 where the pixel's centre ray hits nothing)."""
         return self.device_scene.surface_pixels(self.camera.c_struct(), records=False, albedo=True)
 
-    def render_denoised(self, samples: Optional[int] = None, params=None, sample_xy=None, rgba8: bool = False, albedo: bool = False) -> dict:
+    def mean_albedo(self, samples: Optional[int] = None, sample_xy=None) -> np.ndarray:
+        """The albedo of the whole frame of this camera as the frame at `samples` (default: the config's) sees it, (n, 3) float32 in
+        row-major order (rr_albedo_pixels): per pixel the mean over the frame's primary rays -- its sub-sample table, its depth of field --
+        of the base colour at each ray's first hit.  What denoise() should take as `albedo` for a frame of that many samples: a pixel on a
+        texture edge or a silhouette holds the mix its colour was modulated by, where albedo() holds the colour under its centre."""
+        cfg = rr_config.from_buffer_copy(self.config)
+        if samples is not None:
+            cfg.samples = samples
+        return self.device_scene.albedo_pixels(self.camera.c_struct(), cfg, sample_xy=sample_xy)
+
+    def mean_albedo_torch(self, samples: Optional[int] = None, sample_xy=None):
+        """mean_albedo on torch's current stream, without a host trip (rr_albedo_pixels_device): an (n, 3) float32 CUDA tensor."""
+        cfg = rr_config.from_buffer_copy(self.config)
+        if samples is not None:
+            cfg.samples = samples
+        return albedo_pixels_torch(self.device_scene, self.camera.c_struct(), cfg, None, sample_xy=sample_xy)
+
+    def render_denoised(self, samples: Optional[int] = None, params=None, sample_xy=None, rgba8: bool = False, albedo=False) -> dict:
         """The whole frame at `samples` (default: the config's; even) in two halves, followed by the filter guided by their variance: one
         rr_render_pixel_parts call at n_parts = 2 and one rr_denoise_records call.  albedo=True: one rr_surface_pixels call between them
-        makes this camera's albedo and the filter runs on albedo-demodulated colour; the result then holds it as `albedo`.  Returns the
+        makes this camera's albedo and the filter runs on albedo-demodulated colour; the result then holds it as `albedo`.  albedo="mean":
+        one rr_albedo_pixels call with the frame's config and table stands in its place (mean_albedo).  Returns the
         dict of denoise() plus `noisy`, the records before the filter.  render_denoised_torch is the same on the device, with no host trip."""
         cam = self.camera.c_struct()
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
             cfg.samples = samples
+        _check_albedo_mode(albedo)
         base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=sample_xy)
         records = _pack_records(base)
         halves = _pack_records(base["parts"])
         if albedo:
-            guide = self.device_scene.surface_pixels(cam, records=False, albedo=True)
+            if _mean_mode(albedo):
+                guide = self.device_scene.albedo_pixels(cam, cfg, sample_xy=sample_xy)
+            else:
+                guide = self.device_scene.surface_pixels(cam, records=False, albedo=True)
             return dict(self.denoise(records, halves, guide, params, rgba8=rgba8), noisy=records, albedo=guide)
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
     def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
-                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo: bool = False) -> dict:
+                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo=False) -> dict:
         """One frame of a frame-after-frame loop at `samples` (default: the config's; even) and `seed` (default: the config's): the frame
         in two halves, blended into the history `state` carries from the previous call (rr_accumulate_records, reprojected through the
         camera of that call), then the filter guided by the accumulated halves.  render_temporal_torch on this scene and camera: three
@@ -222,7 +244,8 @@ class Raytracing:
         the next call lists the items whose 16 floats differ bitwise, and rr_motion_records makes their motion on the device (a fourth
         call on the same stream); a change of the item count or of any item's id resets the state, and so does a history from a call
         without track_items.  albedo=True: one more call on the same stream (rr_surface_pixels_device) makes this camera's albedo for the
-        filter; the accumulation is not changed, it blends un-demodulated colour."""
+        filter; the accumulation is not changed, it blends un-demodulated colour.  albedo="mean": rr_albedo_pixels_device with the frame's
+        config and table in its place."""
         from .temporal import previous_view
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
@@ -819,6 +842,35 @@ def surface_pixels_torch(device_scene: capi.DeviceScene, cam, pixels=None, recor
     return out
 
 
+def _check_albedo_mode(albedo) -> None:
+    """The `albedo` argument of the pipelines: False, True (the pixel-centre albedo, rr_surface_pixels) or "mean" (rr_albedo_pixels)."""
+    if isinstance(albedo, str) and albedo != "mean":
+        raise ValueError(f'albedo must be False, True or "mean", not {albedo!r}')
+
+
+def _mean_mode(albedo) -> bool:
+    return isinstance(albedo, str) and albedo == "mean"
+
+
+def albedo_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, sample_xy=None):
+    """rr_albedo_pixels_device on torch's current stream: the albedo of `cam`'s pixels as the frame of `cfg` sees them (the mean over the
+    frame's primary rays of the base colour at each first hit).  `pixels` as render_pixels_torch takes them, or None for every pixel of the
+    frame in row-major order.  Returns an (n, 3) float32 CUDA tensor, what denoise_torch takes as `albedo`; no host copy of the result."""
+    import torch
+    n, xy = int(cam.width) * int(cam.height), None
+    if pixels is not None:
+        dtype = torch.int32 if not isinstance(pixels, torch.Tensor) or pixels.dtype != getattr(torch, "uint32", None) else pixels.dtype
+        xy = _ray_tensor(device_scene, pixels, "pixels", shape_tail=(), dtype=dtype)
+        n = int(xy.shape[0])
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        alb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if n:
+            device_scene.albedo_pixels_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, alb.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream, sample_xy=sample_xy)
+    return alb
+
+
 def trace_shadow_rays_torch(device_scene: capi.DeviceScene, origins, directions, max_distance=None, depth: int = 2) -> dict:
     """rr_trace_shadow_rays_device on torch's current stream: as trace_rays_torch, with `max_distance` a contiguous float32 CUDA tensor of
     shape (n,) or None (no limit).  Returns dict(records (n, 5) int32, occluded, item_index (-1 = lit), object_id, face_id, distance)."""
@@ -1004,14 +1056,25 @@ def denoise_torch(device_scene: capi.DeviceScene, width: int, height: int, recor
     return res
 
 
-def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, params=None, sample_xy=None, rgba8: bool = False, albedo: bool = False) -> dict:
+def _albedo_guide_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, sample_xy, albedo):
+    """The albedo guide of a device pipeline on torch's current stream: None, the pixel-centre albedo (True) or the frame's mean ("mean")."""
+    _check_albedo_mode(albedo)
+    if not albedo:
+        return None
+    if _mean_mode(albedo):
+        return albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
+    return surface_pixels_torch(device_scene, cam, None, records=False, albedo=True)["albedo"]
+
+
+def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, params=None, sample_xy=None, rgba8: bool = False, albedo=False) -> dict:
     """Raytracing.render_denoised on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples even) and
     rr_denoise_records_device on the same stream, the second reading what the first wrote without a synchronisation.  albedo=True:
     rr_surface_pixels_device between the two, on the same stream, makes the camera's albedo for the filter (three calls, still no host
-    trip).  Returns the dict of denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the tensors the filter read, and with albedo=True
-    albedo (n, 3)."""
+    trip); albedo="mean": rr_albedo_pixels_device with the frame's config and table in its place.  Returns the dict of denoise_torch plus
+    noisy (n, 8) and halves (n, 2, 8), the tensors the filter read, and with an albedo albedo (n, 3)."""
+    _check_albedo_mode(albedo)
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
-    guide = surface_pixels_torch(device_scene, cam, None, records=False, albedo=True)["albedo"] if albedo else None
+    guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], guide, params, rgba8=rgba8)
     res = dict(res, noisy=base["records"], halves=base["part_records"])
     if albedo:
@@ -1124,7 +1187,7 @@ def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_
 
 
 def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
-                          sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo: bool = False) -> dict:
+                          sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo=False) -> dict:
     """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
     even), rr_accumulate_records_device against the history in `state`, rr_denoise_records_device with the accumulated halves -- three
     calls on torch's current stream, each reading what the one before wrote without a synchronisation.  params: a
@@ -1135,7 +1198,8 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     Returns the dict of denoise_torch plus noisy (n, 8) and halves (n, 2, 8), the frame's own records, accumulated (n, 8),
     accumulated_halves (n, 2, 8) and length (n,): what the filter read, which `state` now holds as the history; and motion (n, 3) or None:
     what the accumulation read.  albedo=True: rr_surface_pixels_device on the same stream, one call more, makes the albedo of `cam` for the
-    filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it."""
+    filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it.  albedo="mean":
+    rr_albedo_pixels_device with the frame's config and table in its place."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
@@ -1157,7 +1221,7 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
         motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
     acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
                            hist["length"] if hist else None, motion, prm, out=target)
-    guide = surface_pixels_torch(device_scene, cam, None, records=False, albedo=True)["albedo"] if albedo else None
+    guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], guide, denoise_params, rgba8=rgba8)
     state.advance(target, view if view is not None else previous_view(cam))
     res = dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"],

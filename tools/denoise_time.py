@@ -21,7 +21,8 @@ With --albedo: what the albedo guide costs next to the filter and the frame, sam
 device events around CALLS back-to-back calls, WARMUP rounds, the median of ROUNDS):
   (a) rr_surface_pixels_device, albedo only      (b) the same with records
   (c) the path it replaces: host-made pixel-centre rays already resident on the device + rr_surface_rays_device + a torch gather of base_color
-  (d) rr_denoise_records_device (5 iterations, halves, that albedo)      (e) the 4-sample rr_render_pixel_parts_device frame
+  (d) rr_denoise_records_device (5 iterations, halves, that albedo)      (e) the 4-sample rr_render_pixel_parts_device frame, and the 8-sample one
+  (f) rr_albedo_pixels_device, the frame's mean albedo, at 4 and at 8 samples: a strict subset of (e)'s level-1 work at the same count
 next to the compulsory traffic of (a) per pixel (the walk's records: 16 + 16 + 8 B written and read, 16 B of hit written and read, the
 4 B slot map written and read, 12 B of albedo written) at the float4-copy rate.  Scene `sponza_syn` is the benchmark's stand-in.
 
@@ -204,6 +205,8 @@ def measure_albedo(argv, emit):
         frame = renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2)
         rec, halves = frame["records"], frame["part_records"]
         albedo = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        mean = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        cfg8 = make_config(samples=8, monte_carlo=True, seed=1, max_recursion=4)
         surf = torch.empty((n, 32), dtype=torch.float32, device="cuda")
         out = torch.empty_like(rec)
         prm = capi.denoise_params(DenoiseParams(iterations=5))
@@ -219,11 +222,14 @@ def measure_albedo(argv, emit):
             "c": replaced,
             "d": lambda: ds.denoise_records_device(w, h, rec.data_ptr(), halves.data_ptr(), albedo.data_ptr(), out.data_ptr(), None, None, prm, stream),
             "e": lambda: renderer.render_pixel_parts_torch(ds, cam, cfg, None, 2),
+            "e8": lambda: renderer.render_pixel_parts_torch(ds, cam, cfg8, None, 2),
+            "f4": lambda: ds.albedo_pixels_device(cam, cfg, None, n, mean.data_ptr(), stream),
+            "f8": lambda: ds.albedo_pixels_device(cam, cfg8, None, n, mean.data_ptr(), stream),
         }
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
-                t = timed(fn, 1 if k == "e" else CALLS)
+                t = timed(fn, 1 if k in ("e", "e8") else CALLS)
                 if r >= WARMUP:
                     runs[k].append(t)
         torch.cuda.synchronize()
@@ -232,11 +238,15 @@ def measure_albedo(argv, emit):
     floor_ms = n * ALBEDO_BYTES_PER_PIXEL / HBM_BYTES_PER_S * 1e3
     names = {"a": "(a) rr_surface_pixels_device, albedo only", "b": "(b) rr_surface_pixels_device, records and albedo",
              "c": "(c) resident rays + rr_surface_rays_device + torch gather of base_color", "d": "(d) rr_denoise_records_device, 5 iterations, halves, albedo",
-             "e": "(e) rr_render_pixel_parts_device, 4 samples in two halves"}
+             "e": "(e) rr_render_pixel_parts_device, 4 samples in two halves", "e8": "(e) the same at 8 samples",
+             "f4": "(f) rr_albedo_pixels_device, the frame's mean albedo, 4 samples", "f8": "(f) the same at 8 samples"}
     emit(f"the albedo guide, {scene} {w}x{h}; device ms per call, median of {ROUNDS} rounds of {CALLS} calls (e: 1 call) [min .. max]; (c)'s albedo equals (a)'s bit for bit: {same}")
-    for k in "abcde":
+    for k in ("a", "b", "c", "d", "e", "e8", "f4", "f8"):
         m, lo, hi = med[k]
         emit(f"  {names[k]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
+    for f, e, s in (("f4", "e", 4), ("f8", "e8", 8)):
+        below = med[f][2] < med[e][1]   # outside the two arms' ranges
+        emit(f"  (f) / (e) at {s} samples = {med[f][0] / med[e][0]:.3f}; (f)'s largest below (e)'s smallest: {below}; (f) / (a) = {med[f][0] / med['a'][0]:.2f}")
     a, c = med["a"], med["c"]
     emit(f"  (a) / (c) = {a[0] / c[0]:.3f}; (c)'s own spread {c[1]:.4f} .. {c[2]:.4f}; (a) / (d) = {a[0] / med['d'][0]:.3f}; (a) / (e) = {a[0] / med['e'][0]:.3f}")
     emit(f"  compulsory traffic of (a): {ALBEDO_BYTES_PER_PIXEL} B per pixel = {n * ALBEDO_BYTES_PER_PIXEL / 1e6:.1f} MB, {floor_ms * 1e3:.1f} us at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: "
