@@ -1,7 +1,7 @@
 // rr_api_albedo_pixels.h — the frame's albedo per pixel: the mean, over the primary rays rr_render_pixels traces for the pixel, of the base
 // colour at each ray's first hit -- the albedo a pixel's colour was actually modulated by, what rr_denoise_records takes at an edge pixel.
 // Offers: rr_albedo_pixels_device, rr_albedo_pixels.
-// Needs:  rr_api_frame.h (check_frame_args, FrameIo::albedo, pixels_io, render_region_locked: level 1 alone, ending in k_albedo_level1 and
+// Needs:  rr_api_frame.h (check_frame_args, FrameEnd::ALBEDO, pixels_io, render_region_locked: level 1 alone, ending in k_albedo_level1 and
 //         k_resolve_albedo, kernels 5x and 5y of rr_kernels.hip), rr_api_query.h (check_arg_ranges, record_call, staged_host_call, StageArg),
 //         rr_pixel_list.h (pixel_list_first_bad).
 //
@@ -33,7 +33,7 @@ static int check_albedo_pixels_args(const char* fn, bool device, const rr_scene*
 static int albedo_pixels_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const uint32_t* pixel_xy, uint32_t n,
                                 float* albedo, hipStream_t st, bool trusted, const volatile int* cancel) {
     FrameIo io = pixels_io(pixel_xy, n, nullptr, nullptr);
-    io.albedo = albedo; io.own_list = trusted;
+    io.end = FrameEnd::ALBEDO; io.albedo = albedo; io.own_list = trusted;
     return render_region_locked(s, cam, cfg, sample_xy, io, st, cancel);
 }
 

@@ -1,14 +1,17 @@
 // rr_api_frame.h — one frame on one device: the batches of primary rays, the level walk behind them, what the frame cost.
 // Offers: check_frame_args; ScopedTimer, resolve_timers; OUT_ELEM, out_buffer, stage_outputs, copy_outputs; PassHook;
-//         launch_trace_closest; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun,
-//         run_level (with level 1 in stages on three streams; with FrameIo::albedo level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h);
-//         take_stream, begin_frame_stats; FrameIo and its makers frame_io and pixels_io,
+//         launch_trace_closest; FrameEnd, FrameIo and its makers frame_io and pixels_io, frame_end_plan (what an ending implies),
+//         ALL_PLANES; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun and its maker
+//         make_frame_run; launch_shade and launch_shadow (THE launch sites of k_shade and k_trace_shadow), read_back_level_size;
+//         run_level (with level 1 in stages on three streams; with FrameEnd::ALBEDO level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h);
+//         take_stream, begin_frame_stats;
 //         WHOLE_FRAME, IdleOnExit, fill_pixel_slots, render_region_locked (the pixel queries and the adaptive calls are its other callers);
 //         rr_render_region_device, rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, PassSums,
 //         collect_stats_locked, rr_scene_last_stats, rr_scene_overlap_stages;
 //         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
 // Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
-//         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h,
+//         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h (plan_frame,
+//         plan_level1_stages, plan_shade_chunk, level_slice, batch_group),
 //         rr_primary_setup.h, rr_pixel_list.h, the frame kernels of rr_kernels.hip.
 
 // ---------------------------------------------------------------------------
@@ -150,31 +153,33 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
     return RR_OK;
 }
 
+// How a frame ends, by name.  What an ending implies is stated once, in frame_end_plan; its last kernel is launch_resolve's.
+enum class FrameEnd {
+    REGION_BYTES, // k_resolve into the device frame `out` (frame_layout: at the pixel's place in the whole frame, else compact; `hook`: the progressive preview)
+    RECORDS,      // k_resolve_pixels into `radiance` records and, on request, the frame's bytes in `rgba8`
+    RECORD_PARTS, // k_resolve_pixel_parts (rr_api_parts.h): `parts` gets the K part records of every pixel, `radiance` the pixel's full record
+    ALBEDO,       // rr_albedo_pixels (rr_api_albedo_pixels.h): level 1 ends in k_albedo_level1 instead of the shade and shadow kernels, nothing spawns,
+                  // only the colour planes are accumulated, and k_resolve_albedo writes three floats per pixel to `albedo`
+    NONE,         // no resolve: the caller reads the accumulators itself (every plane: rr_api_prefix.h)
+};
 // Where the accumulator slots of a frame come from and how the frame ends, by value (render_region_locked):
 //   slots: a region's map (update_region_map), or `n_pixels` entries x | y << 16 the scene's device can address, entry i = slot i;
-//   end:   k_resolve into the device frame `out` (frame_layout: at the pixel's place in the whole frame, else compact; `hook`: the
-//          progressive preview), or k_resolve_pixels into `radiance` records and, on request, the frame's bytes in `rgba8` -- at the
-//          entry's index for a list, at y * width + x for a region.
+//   end:   `end` and the outputs it names; what is per pixel goes to the entry's index for a list, to y * width + x for a region.
 // Built by name: a maker below, then assignments of the fields that differ; every field left alone is null / 0 / false.
 struct FrameIo {
     const rr_region* region = nullptr; const uint32_t* pixel_xy = nullptr; uint32_t n_pixels = 0u;
+    FrameEnd end = FrameEnd::REGION_BYTES;
     const rr_frame* out = nullptr; bool frame_layout = false; const PassHook* hook = nullptr;
-    rr_radiance* radiance = nullptr; uint8_t* rgba8 = nullptr;
-    // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i, ending in
-    // k_resolve_pixel_parts: `parts` gets the K part records of every pixel, `radiance` the pixel's full record
+    rr_radiance* radiance = nullptr; uint8_t* rgba8 = nullptr; float* albedo = nullptr;
+    // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i
     uint32_t lg_parts = 0u; rr_radiance* parts = nullptr;
     // rr_render_pixel_prefix and rr_render_adaptive_prefix (rr_api_prefix.h): the samples [samples_from, samples_used) of the frame of
     // config->samples samples, both multiples of K; samples_used == 0 = all of them.  The table, the cell size and the generator's keys
     // stay the whole frame's; the object-id rule and the resolve take samples_used as the frame's count.
     uint32_t samples_used = 0u, samples_from = 0u;
     // ... its level passes: `resident` = accumulators that already hold the samples before samples_from (not cleared, n = the call's slots);
-    // own_list = the list is the library's own, made from pixels it has checked (no wait for a first bad entry); no_resolve = the caller
-    // reads the accumulators itself
-    const DAccum* resident = nullptr; bool own_list = false, no_resolve = false;
-    // rr_albedo_pixels (rr_api_albedo_pixels.h): level 1 ends in k_albedo_level1 instead of the shade and shadow kernels, nothing spawns, only
-    // the colour planes are accumulated, and k_resolve_albedo writes three floats per pixel here -- at the entry's index for a list, at
-    // y * width + x for a region
-    float* albedo = nullptr;
+    // own_list = the list is the library's own, made from pixels it has checked (no wait for a first bad entry)
+    const DAccum* resident = nullptr; bool own_list = false;
 };
 static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_layout, const PassHook* hook = nullptr) {
     FrameIo io;
@@ -182,11 +187,23 @@ static FrameIo frame_io(const rr_region* rg, const rr_frame* out, bool frame_lay
     return io;
 }
 static const rr_region WHOLE_FRAME{8, 8, 1, 0}; // rr_render's slot order: 8x8 tiles, one wave = one tile of primary rays
-// records (and, on request, the frame's bytes) of a list's pixels, or of the whole frame where there is no list
+// records (and, on request, the frame's bytes) of a list's pixels, or of the whole frame where there is no list; a caller with another
+// ending names it and its output afterwards
 static FrameIo pixels_io(const uint32_t* pixel_xy, uint32_t n_pixels, rr_radiance* radiance, uint8_t* rgba8) {
     FrameIo io;
-    io.region = pixel_xy ? nullptr : &WHOLE_FRAME; io.pixel_xy = pixel_xy; io.n_pixels = n_pixels; io.radiance = radiance; io.rgba8 = rgba8;
+    io.region = pixel_xy ? nullptr : &WHOLE_FRAME; io.pixel_xy = pixel_xy; io.n_pixels = n_pixels; io.end = FrameEnd::RECORDS; io.radiance = radiance; io.rgba8 = rgba8;
     return io;
+}
+
+// What an ending implies, stated once: the accumulator planes (aux: the three aux planes are reserved and zeroed; normal, depth, id:
+// handed to the kernels -- an aux output nobody asked for is not accumulated at all) and whether level 1 ends every path (no arena, no
+// shadow queue, R = 0).  Records hold all three aux means.
+struct FrameEndPlan { bool aux, normal, depth, id, level1_only; };
+static const FrameEndPlan ALL_PLANES{true, true, true, true, false}; // (also what rr_shade_rays, which resolves its own way, accumulates)
+static FrameEndPlan frame_end_plan(const FrameIo& io) {
+    if (io.end == FrameEnd::ALBEDO) return FrameEndPlan{false, false, false, false, true};
+    if (io.end == FrameEnd::REGION_BYTES) return FrameEndPlan{true, io.out->normal != nullptr, io.out->depth != nullptr, io.out->object_id != nullptr, false};
+    return ALL_PLANES;
 }
 
 // "A call that ends early leaves the stream idle", by construction: armed at the top of a *_locked body, it waits for the stream on every
@@ -281,9 +298,10 @@ static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sa
     return RR_OK;
 }
 
-// zeroed accumulators (and work counters) for npix slots; aux outputs the caller did not ask for are not accumulated at all.
+// zeroed accumulators (and work counters) for npix slots: the planes `want` names (a call that sums colours only reserves and touches no
+// aux plane; an aux plane that is reserved is zeroed whether or not the kernels are handed it).
 // resident: the set to go on with instead, as it is (every plane present, n == npix); the work counters are zeroed all the same.
-static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool want_depth, bool want_id, hipStream_t st, DAccum* acc, const DAccum* resident = nullptr) {
+static int reset_accumulators(rr_scene* s, uint32_t npix, const FrameEndPlan& want, hipStream_t st, DAccum* acc, const DAccum* resident = nullptr) {
     if (resident) {
         if (resident->n != npix || !resident->rgb || !resident->normal || !resident->depth || !resident->object_id || !resident->flags)
             return fail(RR_ERR_DEVICE, "internal: resident accumulators of %llu slots for a pass of %u", resident->n, npix);
@@ -291,29 +309,15 @@ static int reset_accumulators(rr_scene* s, uint32_t npix, bool want_normal, bool
         *acc = *resident;
         return RR_OK;
     }
-    HIP_TRY(s->frame.acc_rgb.reserve((size_t)npix * 24));
-    HIP_TRY(s->frame.acc_normal.reserve((size_t)npix * 24));
-    HIP_TRY(s->frame.acc_depth.reserve((size_t)npix * 8));
-    HIP_TRY(s->frame.acc_id.reserve((size_t)npix * 4));
-    HIP_TRY(s->frame.acc_flags.reserve((size_t)npix * 4));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_flags.p, 0, (size_t)npix * 4, st));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_rgb.p, 0, (size_t)npix * 24, st));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_normal.p, 0, (size_t)npix * 24, st));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_depth.p, 0, (size_t)npix * 8, st));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_id.p, 0, (size_t)npix * 4, st));
+    // (flags, colour, normal, depth, id, counters: the order the memsets have always been enqueued in)
+    DevBuf* const plane[5] = {&s->frame.acc_flags, &s->frame.acc_rgb, &s->frame.acc_normal, &s->frame.acc_depth, &s->frame.acc_id};
+    const size_t bytes[5] = {4, 24, 24, 8, 4};
+    const int n_planes = want.aux ? 5 : 2;
+    for (int k = 0; k < n_planes; k++) HIP_TRY(plane[k]->reserve((size_t)npix * bytes[k]));
+    for (int k = 0; k < n_planes; k++) HIP_TRY(hipMemsetAsync(plane[k]->p, 0, (size_t)npix * bytes[k], st));
     HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
-    *acc = DAccum{s->frame.acc_rgb.as<long long>(), want_normal ? s->frame.acc_normal.as<long long>() : nullptr, want_depth ? s->frame.acc_depth.as<long long>() : nullptr,
-                  want_id ? s->frame.acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
-    return RR_OK;
-}
-// the same for a call that sums colours only (rr_albedo_pixels): the colour planes and the flags, zeroed; no aux plane is reserved or touched
-static int reset_colour_accumulators(rr_scene* s, uint32_t npix, hipStream_t st, DAccum* acc) {
-    HIP_TRY(s->frame.acc_rgb.reserve((size_t)npix * 24));
-    HIP_TRY(s->frame.acc_flags.reserve((size_t)npix * 4));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_flags.p, 0, (size_t)npix * 4, st));
-    HIP_TRY(hipMemsetAsync(s->frame.acc_rgb.p, 0, (size_t)npix * 24, st));
-    HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
-    *acc = DAccum{s->frame.acc_rgb.as<long long>(), nullptr, nullptr, nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
+    *acc = DAccum{s->frame.acc_rgb.as<long long>(), want.normal ? s->frame.acc_normal.as<long long>() : nullptr, want.depth ? s->frame.acc_depth.as<long long>() : nullptr,
+                  want.id ? s->frame.acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
     return RR_OK;
 }
 
@@ -345,20 +349,6 @@ static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t v
         s->frame.sq_cap = sq_need;
     }
     return RR_OK;
-}
-
-// the frame's plan (rr_frame_plan.h), and its ray arena, level-1 hit records and shadow queue
-// (hits_only: a call whose level 1 spawns nothing and asks no light -- rr_albedo_pixels -- needs the hit records alone: no arena, no shadow queue)
-static int plan_queues(rr_scene* s, uint32_t npix, const rr_config* cfg, uint32_t min_passes, FramePlan* plan, bool hits_only = false) {
-    uint64_t budget = 0;
-    RR_TRY(queue_budget(s, &budget));
-    const FramePlan& p = *plan = plan_frame(FramePlanInputs{npix, cfg->samples, cfg->max_recursion, budget, s->tuning.sample_group, min_passes,
-                                                            s->frame.arena_factor, s->data.n_enabled_lights, s->tuning.shade_chunk_rays});
-    HIP_TRY(s->frame.hit1.reserve(p.B * 16));
-    if (hits_only) return RR_OK;
-    // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
-    const Level1Stages sp = level1_stages(s, p.B);
-    return grow_ray_queues(s, p.M, std::max<uint64_t>(p.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need);
 }
 
 // Per-batch counters (level sizes, fetch heads, shadow shard counts) come out of zeroed segments of POOL_WORDS words.  A segment
@@ -404,11 +394,72 @@ struct FrameRun {
     int shadow_grid, shade_grid_max;
     const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, the pixel list of rr_render_pixels, or the stream ids of rr_shade_rays
     bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
-    bool albedo_only = false;          // rr_albedo_pixels: level 1 ends in k_albedo_level1 (R = 0: the level spawns nothing; never in stages)
+    bool level1_only = false;          // FrameEnd::ALBEDO: level 1 ends in k_albedo_level1 (R = 0: the level spawns nothing; never in stages)
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
     }
 };
+// THE maker (render_region_locked, rr_shade_rays): the handle's shadow queue and the launch sizes of a kernel that has the GPU to itself
+static FrameRun make_frame_run(rr_scene* s, hipStream_t st, const FramePlan& plan, uint32_t R, bool level1_only, const DAccum& acc, const DPrimary& pr,
+                               const uint32_t* slot_xy, const volatile int* cancel) {
+    return FrameRun{s, st, plan, R, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc, CounterPool{s, st}, pr, cancel,
+                    s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
+                    s->n_cus * RR_SHADE_GRID_WG, slot_xy, false, level1_only};
+}
+
+// Where the shadow rays of one shade chunk go: the queue and its validity words (the handle's, from `ray_offset` / `valid_offset` on: a
+// stage's buffer) and, from the batch's pool, the chunk's own append counters (on a 128-B line) and the shadow launch's head word.
+// counts or head NULL = the pool has no memory for another segment: launch_shade refuses the chunk.
+struct ChunkShadow { DShadowQueue SQ; unsigned long long* valid; uint32_t* counts; uint32_t* head; };
+static ChunkShadow take_chunk_shadow(FrameRun& f, uint64_t ray_offset, uint64_t valid_offset) {
+    f.pool.align_line();
+    return ChunkShadow{DShadowQueue{f.SQ.s0 + ray_offset, f.SQ.s1 + ray_offset, f.SQ.s2 + ray_offset}, f.s->frame.sq_valid.as<unsigned long long>() + valid_offset,
+                       f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE), f.pool.take(1)}; // (a braced list is evaluated in order: the counters, then the head word)
+}
+
+// The ONE place that launches the shade kernel, and the one that launches the shadow kernel behind it: the serial loop of run_level and the
+// staged path come through here with the chunk's geometry (rr_frame_plan.h plan_shade_chunk) and its queue, so the two launches of a chunk
+// cannot disagree about where the shadow rays are.  As in launch_trace_closest, every pointer the build in question dereferences is checked
+// on the host, and so is that the geometry fits the kernels' 32-bit arguments.  max_wg: the caller's cap on the grid.
+// (A template's builds are emitted in the order they are first named.  This line names the four in the order the code object has always
+// held them, level 1's pair before the deeper levels', so the library's device assembly stays byte for byte what it was and a diff of it
+// remains a usable check of a change to the host code.)
+[[maybe_unused]] static const void* const k_chunk_kernel_order[4] = {(const void*)k_shade<true>, (const void*)k_trace_shadow<true>, (const void*)k_shade<false>,
+                                                                     (const void*)k_trace_shadow<false>};
+// level1 = the <true> build (rays derived from their index: no ray records, and only it may have fixed shadow slots); the hits [c0, c1) of
+// qin, children to qout
+static int launch_shade(FrameRun& f, bool level1, const DRayQueue& qin, const uint32_t* count, uint64_t c0, uint64_t c1, const DRayQueue& qout, uint32_t* child_count,
+                        const ShadeChunk& g, const ChunkShadow& q, uint64_t max_wg, hipStream_t st) {
+    rr_scene* s = f.s;
+    if (!q.counts || !q.head) return counters_exhausted();
+    if (!qin.hit || !count || !child_count || !f.acc.rgb || !f.acc.flags || !s->frame.shade_const.p || (!level1 && (!qin.r0 || !qin.r1 || !qin.r2)) ||
+        (s->data.n_enabled_lights > 0 && (!q.SQ.s0 || !q.SQ.s1 || !q.SQ.s2)) || (g.fixed && (!level1 || !q.valid)) || c1 <= c0 || c1 > 0xffffffffull ||
+        g.segcap > 0xffffffffull || g.sq_cap > 0xffffffffull || max_wg == 0)
+        return fail(RR_ERR_DEVICE, "internal: shade launch of hits %llu .. %llu with a NULL or out-of-range argument", (unsigned long long)c0, (unsigned long long)c1);
+    ScopedTimer t(s, st, TK_SHADE, level1);
+    hipLaunchKernelGGL((level1 ? k_shade<true> : k_shade<false>), dim3((uint32_t)std::min<uint64_t>(g.groups, max_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(),
+                       f.slot_xy, f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, q.SQ, q.counts, (uint32_t)g.segcap, q.valid, (uint32_t)g.sq_cap, f.acc,
+                       s->frame.counters.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+// (the timer's level-1 flag is by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
+static int launch_shadow(FrameRun& f, const ShadeChunk& g, const ChunkShadow& q, uint64_t max_wg, hipStream_t st) {
+    if (!q.counts || !q.head || !f.acc.rgb || !f.acc.flags || !q.SQ.s0 || !q.SQ.s1 || !q.SQ.s2 || (g.fixed && !q.valid) || g.segcap > 0xffffffffull ||
+        g.sq_packets > 0xffffffffull || g.shadow_wg == 0 || max_wg == 0)
+        return fail(RR_ERR_DEVICE, "internal: shadow launch of %llu workgroups with a NULL or out-of-range argument", (unsigned long long)g.shadow_wg);
+    ScopedTimer t(f.s, st, TK_SHADOW, g.fixed);
+    hipLaunchKernelGGL((g.fixed ? k_trace_shadow<true> : k_trace_shadow<false>), dim3((uint32_t)std::min<uint64_t>(g.shadow_wg, max_wg)), dim3(RR_BLOCK), 0, st, f.s->data.view, q.SQ,
+                       q.counts, (uint32_t)g.segcap, q.valid, (uint32_t)g.sq_packets, q.head, f.acc);
+    HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+// The size of the next level, final once the last shade launch of a slice has run, on its way to the host (run_level waits for count_ready)
+static int read_back_level_size(FrameRun& f, const uint32_t* child_count) {
+    HIP_TRY(hipMemcpyAsync(f.s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, f.st));
+    HIP_TRY(hipEventRecord(f.s->frame.count_ready, f.st));
+    return RR_OK;
+}
 
 // On request (rr_tuning::bin_min_rays) a deeper level of m rays at child_base is traced in bins of (origin cell, direction octant)
 // when the sorted copy fits behind the unsorted one (rr_kernels.hip: ray binning; off by default, it does not pay).
@@ -466,7 +517,6 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
                                  const DRayQueue& qout, uint32_t* child_count, bool spawns, bool trace_closest) {
     rr_scene* s = f.s;
     const hipStream_t st = f.st, st2 = s->frame.overlap_stream, st3 = s->frame.closest_stream;
-    const uint32_t L = s->data.n_enabled_lights;
     unsigned long long* counters = s->frame.counters.as<unsigned long long>();
     if (sp.sq_need > s->frame.sq_cap || sp.valid_need * 8 > s->frame.sq_valid.bytes) return fail(RR_ERR_DEVICE, "internal: shadow queue smaller than its stage buffers");
     uint32_t* closest_heads = nullptr; // one per closest-hit launch, RR_SQ_STRIDE words apart, zeroed on `st` before the fork
@@ -483,17 +533,10 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         const uint64_t c0 = s0 + sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, s1);
         const uint32_t b = sp.buffer_of(k);
         const bool first = k == 0, last = k + 1 == sp.n_stages;
-        const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK;
-        const uint32_t sq_chunk_cap = (uint32_t)(groups * RR_BLOCK); // <= sp.stage: L x this many slots fit the buffer
-        const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * L);
-        const DShadowQueue SQ{f.SQ.s0 + sp.ray_offset[b], f.SQ.s1 + sp.ray_offset[b], f.SQ.s2 + sp.ray_offset[b]};
-        unsigned long long* sq_valid = s->frame.sq_valid.as<unsigned long long>() + sp.valid_offset[b];
-        f.pool.align_line();
-        uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
-        uint32_t* shead = f.pool.take(1); // (zeroed on `st` before the event the second stream waits for)
-        if (!sq_counts || !shead) return counters_exhausted();
+        const ShadeChunk g = plan_shade_chunk(c0, c1, s->data.n_enabled_lights, true); // (sq_cap <= sp.stage: lights x this many slots fit the buffer)
+        const ChunkShadow q = take_chunk_shadow(f, sp.ray_offset[b], sp.valid_offset[b]); // (its head word is zeroed on `st` before the event the second stream waits for)
         // the first stage's shade and the last stage's shadow run alone: the serial loop's grids.  In between the two launches share the CUs.
-        const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : groups);
+        const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : g.groups);
         const uint64_t shadow_wg = last ? (uint64_t)f.shadow_grid : (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
         if (trace_closest) { // the host is stages ahead of the device: launch k is enqueued long before launch k - 1 ends
             {
@@ -505,25 +548,11 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
             HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_closest[k % 3u], 0));
         }
         if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[b], 0));
-        {
-            ScopedTimer t(s, st, TK_SHADE, true);
-            hipLaunchKernelGGL(k_shade<true>, dim3((uint32_t)std::min<uint64_t>(groups, shade_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy,
-                               f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
-        }
-        HIP_TRY(hipGetLastError());
-        if (spawns && last) { // the next level's size, behind the last shade stage (run_level waits for it)
-            HIP_TRY(hipMemcpyAsync(s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(s->frame.count_ready, st));
-        }
+        RR_TRY(launch_shade(f, true, qin, count, c0, c1, qout, child_count, g, q, shade_wg, st));
+        if (spawns && last) RR_TRY(read_back_level_size(f, child_count)); // behind the last shade stage
         HIP_TRY(hipEventRecord(s->frame.stage_shaded[b], st));
         HIP_TRY(hipStreamWaitEvent(st2, s->frame.stage_shaded[b], 0));
-        {
-            ScopedTimer t(s, st2, TK_SHADOW, true);
-            const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
-            const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, shadow_wg);
-            hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st2, s->data.view, SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
-        }
-        HIP_TRY(hipGetLastError());
+        RR_TRY(launch_shadow(f, g, q, shadow_wg, st2));
         HIP_TRY(hipEventRecord(s->frame.stage_traced[b], st2));
     }
     // the second stream joins `st` here: before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
@@ -566,11 +595,12 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
     const bool spawns = d <= f.R; // the deepest level spawns nothing (k_shade: depth <= max_recursion)
     const uint64_t M = f.plan.M, child_base = l1 ? 0 : base + n;
     const uint64_t slice = level_slice(M, child_base, n, d, f.R);
-    // level 1 with fixed shadow slots and at least two stages: shade and shadow launches side by side on two streams (per slice of the level)
-    const auto staged = [&](uint64_t hits) {
-        return !f.albedo_only && level1_stages_wanted(s) && l1 && L >= 1 && L <= RR_FIXED_SLOT_LIGHTS && s->data.view.n_items >= RR_BEAM_MIN_ITEMS &&
-               s->data.view.n_items <= RR_BEAM_MAX_ITEMS && level1_stages(s, hits).overlapped();
-    };
+    // level 1 keeps fixed shadow slots per chunk (rr_frame_plan.h plan_shade_chunk), only where the shadow kernel's packet form applies
+    // (rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS) and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per
+    // light and lane for the validity words; more lights take the dense queue of the deeper levels, which has no such limit
+    const bool sq_fixed = l1 && s->data.view.n_items >= RR_BEAM_MIN_ITEMS && s->data.view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
+    // ... and with at least one light and two stages: shade and shadow launches side by side on two streams (per slice of the level)
+    const auto staged = [&](uint64_t hits) { return !f.level1_only && level1_stages_wanted(s) && sq_fixed && L >= 1 && level1_stages(s, hits).overlapped(); };
     // ... and where the level is ONE slice, its closest hits stage by stage on a third stream; every other level in one launch, here
     const bool closest_staged = slice == n && staged(n);
     if (!closest_staged) {
@@ -591,53 +621,21 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         for (uint64_t c0 = s0; c0 < s1 && !in_stages; c0 += f.plan.chunk) {
             if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
             const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
-            const int grid = (int)std::min<uint64_t>((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shade_grid_max);
-            if (f.albedo_only) { // the ending of level 1 of rr_albedo_pixels: no shadow slots, no children, no counters of its own
+            const ShadeChunk g = plan_shade_chunk(c0, c1, L, sq_fixed);
+            if (f.level1_only) { // the ending of level 1 of rr_albedo_pixels: no shadow slots, no children, no counters of its own
                 if (!l1 || spawns || !f.acc.rgb || !f.acc.flags) return fail(RR_ERR_DEVICE, "internal: albedo launch outside a level 1 that ends its paths");
                 ScopedTimer t(s, st, TK_SHADE, true);
-                hipLaunchKernelGGL(k_albedo_level1, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.pr, qin.hit, count, (uint32_t)c0, (uint32_t)c1, f.acc);
+                hipLaunchKernelGGL(k_albedo_level1, dim3((uint32_t)std::min<uint64_t>(g.groups, (uint64_t)f.shade_grid_max)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(),
+                                   f.pr, qin.hit, count, (uint32_t)c0, (uint32_t)c1, f.acc);
                 continue;
             }
-            // level 1: shadow slots of this chunk = L x (the chunk padded to whole workgroup iterations), one validity word per 64
-            // (only where the shadow kernel's packet form applies: rr_kernels.hip, RR_BEAM_MIN_ITEMS .. RR_BEAM_MAX_ITEMS)
-            // and up to RR_FIXED_SLOT_LIGHTS enabled lights: k_shade keeps one bit per light and lane for the validity words; more lights
-            // take the dense queue of the deeper levels, which has no such limit
-            const bool sq_fixed = l1 && s->data.view.n_items >= RR_BEAM_MIN_ITEMS && s->data.view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
-            const uint32_t sq_chunk_cap = sq_fixed ? (uint32_t)(((c1 - c0 + RR_BLOCK - 1) / RR_BLOCK) * RR_BLOCK) : 0u;
-            unsigned long long* sq_valid = s->frame.sq_valid.as<unsigned long long>();
-            // deeper levels: shadow sub-queues, a shard gets the packets with (packet % RR_SQ_SHARDS == shard), L rays per hit at most
-            const uint64_t groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK; // 256-ray groups, dealt round-robin to the shards
-            const uint32_t segcap = (uint32_t)(((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * std::max(L, 1u));
-            f.pool.align_line(); // the append counters start on a 128-B line
-            uint32_t* sq_counts = f.pool.take(RR_SQ_SHARDS * RR_SQ_STRIDE);
-            uint32_t* shead = f.pool.take(1);
-            if (!sq_counts || !shead) return counters_exhausted();
-            {
-                ScopedTimer t(s, st, TK_SHADE, l1);
-                if (l1) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
-                                               (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
-                else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count,
-                                        (uint32_t)c0, (uint32_t)c1, qout, child_count, f.SQ, sq_counts, segcap, sq_valid, sq_chunk_cap, f.acc, counters);
-            }
+            const ChunkShadow q = take_chunk_shadow(f, 0, 0);
+            RR_TRY(launch_shade(f, l1, qin, count, c0, c1, qout, child_count, g, q, (uint64_t)f.shade_grid_max, st));
             // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
             // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
             // rays are still being traced, instead of leaving the device idle for a host round trip per level.
-            if (spawns && c1 == s1) {
-                HIP_TRY(hipMemcpyAsync(s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(s->frame.count_ready, st));
-            }
-            if (L) {
-                ScopedTimer t(s, st, TK_SHADOW, sq_fixed); // (by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
-                if (sq_fixed) {
-                    const uint32_t sq_packets = (sq_chunk_cap / RR_WAVE) * L;
-                    const int sgrid = (int)std::min<uint64_t>(((uint64_t)sq_packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
-                    hipLaunchKernelGGL(k_trace_shadow<true>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->data.view, f.SQ, sq_counts, segcap, sq_valid, sq_packets, shead, f.acc);
-                } else {
-                    const uint64_t sq_ub = (c1 - c0) * L;
-                    const int sgrid = (int)std::min<uint64_t>((sq_ub + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)f.shadow_grid);
-                    hipLaunchKernelGGL(k_trace_shadow<false>, dim3(sgrid), dim3(RR_BLOCK), 0, st, s->data.view, f.SQ, sq_counts, segcap, sq_valid, 0u, shead, f.acc);
-                }
-            }
+            if (spawns && c1 == s1) RR_TRY(read_back_level_size(f, child_count));
+            if (L) RR_TRY(launch_shadow(f, g, q, (uint64_t)f.shadow_grid, st));
         }
         if (!spawns) continue;
         HIP_TRY(hipEventSynchronize(s->frame.count_ready));
@@ -652,15 +650,18 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
 }
 
 static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& io) {
-    const uint32_t npix = fr.n_region_pixels;
-    if (io.albedo) hipLaunchKernelGGL(k_resolve_albedo, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
-                                      (uint32_t*)io.albedo);
-    else if (io.parts) hipLaunchKernelGGL(k_resolve_pixel_parts, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, io.pixel_xy ? 0u : 1u,
-                                     (float4*)io.radiance, (float4*)io.parts);
-    else if (io.radiance) hipLaunchKernelGGL(k_resolve_pixels, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.slot_xy, f.acc, io.pixel_xy ? 0u : 1u,
-                                        (float4*)io.radiance, (uint32_t*)io.rgba8);
-    else hipLaunchKernelGGL(k_resolve, dim3((npix + RR_BLOCK - 1) / RR_BLOCK), dim3(RR_BLOCK), 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(),
-                            f.acc, io.out->rgba8, io.out->normal, io.out->depth, io.out->object_id, io.frame_layout ? 1u : 0u);
+    const dim3 grid((fr.n_region_pixels + RR_BLOCK - 1) / RR_BLOCK), block(RR_BLOCK);
+    const uint32_t by_pixel = io.pixel_xy ? 0u : 1u; // a region's answers go to y * width + x, a list's to the entry's index
+    switch (io.end) {
+    case FrameEnd::NONE: break;
+    case FrameEnd::ALBEDO: hipLaunchKernelGGL(k_resolve_albedo, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (uint32_t*)io.albedo); break;
+    case FrameEnd::RECORD_PARTS: hipLaunchKernelGGL(k_resolve_pixel_parts, grid, block, 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, by_pixel, (float4*)io.radiance, (float4*)io.parts); break;
+    case FrameEnd::RECORDS: hipLaunchKernelGGL(k_resolve_pixels, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (float4*)io.radiance, (uint32_t*)io.rgba8); break;
+    case FrameEnd::REGION_BYTES:
+        hipLaunchKernelGGL(k_resolve, grid, block, 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(), f.acc, io.out->rgba8, io.out->normal,
+                           io.out->depth, io.out->object_id, io.frame_layout ? 1u : 0u);
+        break;
+    }
 }
 
 // The frame's batches of primary rays, in order.  After a batch that ends on a whole slice of samples the pass hook
@@ -716,7 +717,6 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     RR_TRY(take_stream(s, st));
     const uint32_t W = cam->width, H = cam->height;
     if ((uint64_t)W * H > (1ull << 30)) return fail(RR_ERR_UNSUPPORTED, "frame of %ux%u pixels", W, H);
-    const PassHook* hook = io.hook;
     uint32_t npix;
     const uint32_t* slot_xy; // accumulator slot -> pixel, and the screen point of its centre: the list's own tables or the region's
     const float* slot_c;
@@ -741,26 +741,26 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     // count is `used` (k_shade: the id is that of sample used - 1, as the oracle's samples_used has it; the resolve divides by it)
     const uint32_t used = io.samples_used ? io.samples_used : cfg->samples;
     fr.samples = used;
+    const FrameEndPlan end = frame_end_plan(io);
+    const uint32_t R = end.level1_only ? 0u : cfg->max_recursion;
     DAccum acc;
-    const bool radiance = io.radiance != nullptr; // rr_radiance holds all three aux means
-    const bool albedo_only = io.albedo != nullptr; // rr_albedo_pixels: colour sums alone, level 1 alone
-    if (albedo_only) RR_TRY(reset_colour_accumulators(s, npix, st, &acc));
-    else RR_TRY(reset_accumulators(s, npix, radiance || io.out->normal != nullptr, radiance || io.out->depth != nullptr, radiance || io.out->object_id != nullptr, st, &acc,
-                                   io.resident));
-    FramePlan plan;
-    rr_config plan_cfg = *cfg; // with parts the plan sees K x the slots and 1 / K of the samples; the frame constants keep the frame's S
-    plan_cfg.samples = (decltype(plan_cfg.samples))((used - io.samples_from) >> io.lg_parts); // (a sample group must divide THIS range: plan_frame)
-    if (albedo_only) plan_cfg.max_recursion = 0u;
-    RR_TRY(plan_queues(s, npix, &plan_cfg, hook ? hook->min_passes : 0u, &plan, albedo_only));
+    RR_TRY(reset_accumulators(s, npix, end, st, &acc, io.resident));
+    // The frame's plan (rr_frame_plan.h), and its level-1 hit records, ray arena and shadow queue.  With parts the plan sees K x the slots
+    // and 1 / K of the samples (a sample group must divide THIS range: plan_frame); the frame constants keep the frame's S.
+    uint64_t budget = 0;
+    RR_TRY(queue_budget(s, &budget));
+    const FramePlan plan = plan_frame(FramePlanInputs{npix, (used - io.samples_from) >> io.lg_parts, R, budget, s->tuning.sample_group, io.hook ? io.hook->min_passes : 0u,
+                                                      s->frame.arena_factor, s->data.n_enabled_lights, s->tuning.shade_chunk_rays});
+    HIP_TRY(s->frame.hit1.reserve(plan.B * 16));
+    if (!end.level1_only) { // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
+        const Level1Stages sp = level1_stages(s, plan.B);
+        RR_TRY(grow_ray_queues(s, plan.M, std::max<uint64_t>(plan.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need));
+    }
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
-    FrameRun f{s, st, plan, albedo_only ? 0u : cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, cancel,
-               s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
-               s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = slot_xy; f.albedo_only = albedo_only;
+    FrameRun f = make_frame_run(s, st, plan, R, end.level1_only, acc, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, slot_xy, cancel);
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
     RR_TRY(run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix));
-    if (!io.no_resolve) launch_resolve(f, fr, io);
+    launch_resolve(f, fr, io);
     HIP_TRY(hipEventRecord(s->timing.frame_b, st));
     HIP_TRY(hipGetLastError());
     // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)

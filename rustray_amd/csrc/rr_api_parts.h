@@ -31,7 +31,7 @@ static int render_pixel_parts_locked(rr_scene* s, const rr_camera* cam, const rr
                                      uint32_t n_pixels, uint32_t lg_parts, rr_radiance* out, rr_radiance* parts_out, hipStream_t st, const volatile int* cancel) {
     IdleOnExit idle(st);
     FrameIo io = pixels_io(pixel_xy, n_pixels, out, nullptr);
-    io.lg_parts = lg_parts; io.parts = parts_out;
+    io.end = FrameEnd::RECORD_PARTS; io.lg_parts = lg_parts; io.parts = parts_out;
     return idle.done(render_region_locked(s, cam, cfg, sample_xy, io, st, cancel));
 }
 

@@ -1,7 +1,7 @@
 // rr_api_prefix.h — the first samples of a frame as records, and a frame refined level by level whose pixels KEEP their samples: every
 // level is a prefix of ONE frame of config->samples samples, and a pixel that climbs is given only the samples it does not have yet.
 // Offers: rr_render_pixel_prefix, rr_render_pixel_prefix_device, rr_render_adaptive_prefix, rr_render_adaptive_prefix_device.
-// Needs:  rr_api_frame.h (FrameIo: samples_used, samples_from, resident, own_list, no_resolve; pixels_io, render_region_locked, ScopedTimer,
+// Needs:  rr_api_frame.h (FrameIo: samples_used, samples_from, resident, own_list, FrameEnd::NONE and RECORD_PARTS; pixels_io, render_region_locked, ScopedTimer,
 //         IdleOnExit, PassSums, collect_stats_locked), rr_api_query.h (check_pixels_args, host_list_call, check_query_pointers),
 //         rr_api_adaptive.h (list_scratch, await_list_count; FusedOut, check_fused_outputs, device_fused_call, host_fused_call,
 //         launch_record_bytes, finish_fused), rr_api_levels.h (check_ladder), rr_adaptive.h (the sets of resident accumulators), kernels 5m,
@@ -34,7 +34,8 @@ static int render_pixel_prefix_locked(rr_scene* s, const rr_camera* cam, const r
     IdleOnExit idle(st);
     // (k_resolve_pixel_parts has no byte output: with halves the bytes come from the finished records, as rr_render_adaptive makes its own)
     FrameIo io = pixels_io(pixel_xy, n_pixels, out, halves ? nullptr : rgba8);
-    io.lg_parts = halves ? 1u : 0u; io.parts = halves; io.samples_used = samples_used;
+    if (halves) { io.end = FrameEnd::RECORD_PARTS; io.lg_parts = 1u; io.parts = halves; }
+    io.samples_used = samples_used;
     RR_TRY(render_region_locked(s, cam, cfg, sample_xy, io, st, cancel));
     if (halves && rgba8) {
         launch_record_bytes(s, cfg, out, n_pixels, rgba8, st);
@@ -98,8 +99,8 @@ static int render_adaptive_prefix_locked(rr_scene* s, const rr_camera* cam, cons
     const uint32_t W = cam->width, H = cam->height, N = W * H;
     uint32_t level_pixels[RR_MAX_ADAPTIVE_LEVELS] = {N, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     // every level's pass: two halves per entry, its samples added to accumulators nobody resolves but k_prefix_masks
-    FrameIo io = pixels_io(nullptr, N, o.out, nullptr);
-    io.lg_parts = 1u; io.no_resolve = true;
+    FrameIo io = pixels_io(nullptr, N, nullptr, nullptr);
+    io.end = FrameEnd::NONE; io.lg_parts = 1u;
     // level 0: the whole frame over [0, P0); its sums stay in the frame's own accumulators, in the region's slot order
     io.samples_used = prefix_samples[0];
     RR_TRY(render_region_locked(s, cam, cfg, sample_xy, io, st, cancel));

@@ -5,7 +5,7 @@
 //         check_arg_ranges, record_call, StageArg, stage_input, stage_output, staged_host_call (writes rr_scene::record_stage).
 // Needs:  rr_arg_ranges.h, rr_api_base.h, rr_api_handle.h (writes rr_scene::query), rr_api_scene.h (ensure_tlas_reach, ensure_camera_reach; reads
 //         rr_scene::data), rr_api_frame.h (launch_trace_closest, take_stream, make_frame; for rr_shade_rays the frame's own level walk:
-//         FrameRun, run_level, upload_shade_const, reset_accumulators, grow_ray_queues, begin_frame_stats; for rr_render_pixels the whole frame:
+//         make_frame_run, run_level, upload_shade_const, reset_accumulators, ALL_PLANES, grow_ray_queues, begin_frame_stats; for rr_render_pixels the whole frame:
 //         check_frame_args, pixels_io, IdleOnExit, render_region_locked), rr_pixel_list.h, rr_api_multi.h (the peer
 //         access it has enabled: g_peer_mu, g_peer_state), rr_query_pointers.h, rr_frame_plan.h.
 // Borrowed from rr_scene::frame: h_count[HC_REACH ..] and last_stream by every query (await_reach, take_stream); the arena, the shadow
@@ -483,7 +483,7 @@ static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const RayIo& io,
         ids = b.as<uint32_t>();
     }
     DAccum acc;
-    RR_TRY(reset_accumulators(s, n_results, true, true, true, st, &acc));
+    RR_TRY(reset_accumulators(s, n_results, ALL_PLANES, st, &acc));
     uint64_t budget = 0;
     RR_TRY(queue_budget(s, &budget));
     const FramePlan plan = plan_ray_batches(n_rays, cfg->max_recursion, budget, s->data.n_enabled_lights, s->tuning.shade_chunk_rays);
@@ -493,9 +493,7 @@ static int shade_rays_locked(rr_scene* s, const rr_config* cfg, const RayIo& io,
         HIP_TRY(d_dirs.reserve(12ull * plan.B));
         HIP_TRY(d_out.reserve(32ull * std::min<uint32_t>(n_results, RESOLVE_RAYS_CHUNK)));
     }
-    FrameRun f{s, st, plan, cfg->max_recursion, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc,
-               CounterPool{s, st}, DPrimary{nullptr, PrimaryLaunch{0u, 0u, 0u, 6u}, 0u}, cancel, s->n_cus * RR_SHADOW_GRID_WG, s->n_cus * RR_SHADE_GRID_WG};
-    f.slot_xy = ids;
+    FrameRun f = make_frame_run(s, st, plan, cfg->max_recursion, false, acc, DPrimary{nullptr, PrimaryLaunch{0u, 0u, 0u, 6u}, 0u}, ids, cancel);
     f.seeded = true;
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
     int rc = run_ray_batches(f, io, rays_per_result, d_origins.as<float>(), d_dirs.as<float>());

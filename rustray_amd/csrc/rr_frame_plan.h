@@ -1,5 +1,7 @@
 // rr_frame_plan.h — how a frame is cut into device batches and how its ray memory is sized: plain host arithmetic,
-// no HIP calls (rr_api_frame.h render_region_locked runs it; tests/native/frame_plan_test.cpp checks it on the CPU).
+// no HIP calls.  rr_api_frame.h runs it: render_region_locked (plan_frame), run_level (level_slice, plan_level1_stages and, for the
+// serial loop and the staged path alike, plan_shade_chunk); rr_api_query.h rr_shade_rays (plan_ray_batches).
+// tests/native/frame_plan_test.cpp and level1_stages_test.cpp check it on the CPU.
 //
 // All live depth levels of a batch sit in ONE arena of ray records (56 B each), level d + 1 stacked behind level d.
 // A level of n rays spawns at most 2 n children; if they fit behind it the level is shaded in one go, otherwise in
@@ -35,6 +37,14 @@ struct FramePlan {
 };
 
 static const uint64_t RR_LEVEL_MAX = 0x7fffff00ull; // ray indices are 32-bit
+
+// Rays per shade launch: rr_tuning::shade_chunk_rays, at least 65536 (0 = 64 Mi).  The shadow queue holds one 48-B ray per hit of the
+// chunk and ENABLED light: with many lights the chunk shrinks so that the queue stays within 16 GB -- the reference has no limit on
+// lights, src/raytracing.rs:814.
+inline uint64_t shade_chunk(uint32_t n_enabled_lights, uint64_t shade_chunk_rays) {
+    const uint64_t by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(n_enabled_lights, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
+    return std::min<uint64_t>(shade_chunk_rays ? std::max<uint64_t>(65536, shade_chunk_rays) : (64ull << 20), by_lights);
+}
 
 inline FramePlan plan_frame(const FramePlanInputs& in) {
     const uint32_t npix = in.npix, R = in.max_recursion, L = in.n_enabled_lights;
@@ -75,10 +85,7 @@ inline FramePlan plan_frame(const FramePlanInputs& in) {
     const uint64_t roomy = std::min<uint64_t>(7 * B, (16ull << 30) / 56ull);
     const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(2 * B, roomy), (uint64_t)in.arena_factor * B);
     const uint64_t M = std::min<uint64_t>(std::min<uint64_t>(want, std::max<uint64_t>(2 * B, after_hits)) + 2ull * RR_BLOCK * (R + 1), RR_LEVEL_MAX);
-    // (the shadow queue holds one 48-B ray per hit of the chunk and ENABLED light: with many lights the chunk shrinks so that
-    // the queue stays within 16 GB -- the reference has no limit on lights, src/raytracing.rs:814)
-    const uint64_t chunk_by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(L, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
-    const uint64_t chunk = std::min<uint64_t>(in.shade_chunk_rays ? std::max<uint64_t>(65536, in.shade_chunk_rays) : (64ull << 20), chunk_by_lights);
+    const uint64_t chunk = shade_chunk(L, in.shade_chunk_rays);
     // level 1: fixed shadow slots, (enabled light, hit of the chunk), the chunk padded to whole workgroup iterations;
     // deeper levels: the dense sharded queue (a shard's static share of the chunk, one slack group per shard)
     const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, std::max<uint64_t>(M, B)) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(L, 1u));
@@ -93,17 +100,15 @@ inline FramePlan plan_frame(const FramePlanInputs& in) {
 // The batches are equal: batch k = rays [k * B, min((k + 1) * B, n_rays)), a result's rays cut anywhere (the accumulators are
 // integers and live across the batches).  Returned as a FramePlan (total_primary = n_rays, G = 1): the level walk reads it.
 inline FramePlan plan_ray_batches(uint64_t n_rays, uint32_t max_recursion, uint64_t budget, uint32_t n_enabled_lights, uint64_t shade_chunk_rays) {
-    const uint32_t L = n_enabled_lights;
     const uint64_t slack = 2ull * RR_BLOCK * (max_recursion + 1);
     const uint64_t per_ray = 3ull * 56ull;
     uint64_t B = std::max<uint64_t>(budget > 56ull * slack ? (budget - 56ull * slack) / per_ray : 0ull, 4096);
     B = std::min<uint64_t>(B, std::min<uint64_t>(std::max<uint64_t>(n_rays, 1), (RR_LEVEL_MAX - slack) / 3));
     { const uint64_t nb = (std::max<uint64_t>(n_rays, 1) + B - 1) / B; B = (std::max<uint64_t>(n_rays, 1) + nb - 1) / nb; }
     const uint64_t M = 3 * B + slack;
-    const uint64_t chunk_by_lights = std::max<uint64_t>(65536, ((16ull << 30) / (48ull * std::max<uint32_t>(L, 1u))) / (RR_BLOCK * RR_SQ_SHARDS) * (RR_BLOCK * RR_SQ_SHARDS));
-    const uint64_t chunk = std::min<uint64_t>(shade_chunk_rays ? std::max<uint64_t>(65536, shade_chunk_rays) : (64ull << 20), chunk_by_lights);
+    const uint64_t chunk = shade_chunk(n_enabled_lights, shade_chunk_rays);
     // every level takes the dense sharded shadow queue (no fixed slots: the rays of a packet need not belong together)
-    const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, M) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(L, 1u));
+    const uint64_t sq_need = std::max<uint64_t>(1, (std::min<uint64_t>(chunk, M) + RR_BLOCK * RR_SQ_SHARDS) * std::max<uint32_t>(n_enabled_lights, 1u));
     return FramePlan{n_rays, B, 1u, M, chunk, sq_need};
 }
 
@@ -166,6 +171,28 @@ inline Level1Stages plan_level1_stages(const Level1StageInputs& in) {
     p.sq_need = p.overlapped() ? n_buf * p.buf_rays : 0ull;
     p.valid_need = p.overlapped() ? n_buf * (p.buf_rays / RR_WAVE) : 0ull;
     return p;
+}
+
+// ---- the shadow queue of one shade chunk (rr_api_frame.h: the serial loop of run_level and every stage of the staged path) ------
+// Where k_shade writes the shadow rays of the hits [c0, c1) and how far k_trace_shadow reads: both launches of a chunk take these
+// numbers, and nothing else computes them.  Level 1 with fixed slots: slot (light, hit of the chunk), the chunk padded to whole
+// workgroup iterations, one validity word per 64 slots, walked as packets.  Otherwise the dense queue: a shard gets the 256-ray groups
+// with (group % RR_SQ_SHARDS == shard), at most `lights` rays per hit.  64-bit, so that the launch sites can refuse what the kernels'
+// 32-bit arguments cannot hold; what the allocations of plan_frame and plan_level1_stages must cover: tests/native/frame_plan_test.cpp.
+struct ShadeChunk {
+    bool fixed;
+    uint64_t groups;     // 256-ray groups of the chunk: k_shade's workgroup iterations, dealt round-robin to the shards
+    uint64_t sq_cap, sq_packets; // fixed slots per light (0 when dense), and the 64-slot packets of all lights together
+    uint64_t segcap;     // rays a shard of the dense queue holds at most
+    uint64_t shadow_wg;  // workgroups with one thread per shadow ray there can be, before the caller's cap
+};
+
+inline ShadeChunk plan_shade_chunk(uint64_t c0, uint64_t c1, uint32_t n_enabled_lights, bool fixed) {
+    const uint64_t L = n_enabled_lights, groups = (c1 - c0 + RR_BLOCK - 1) / RR_BLOCK;
+    const uint64_t sq_cap = fixed ? groups * RR_BLOCK : 0ull, sq_packets = (sq_cap / RR_WAVE) * L;
+    const uint64_t segcap = ((groups + RR_SQ_SHARDS - 1) / RR_SQ_SHARDS) * RR_BLOCK * std::max<uint64_t>(L, 1);
+    const uint64_t shadow_rays = fixed ? sq_packets * RR_WAVE : (c1 - c0) * L; // the most there can be
+    return ShadeChunk{fixed, groups, sq_cap, sq_packets, segcap, (shadow_rays + RR_BLOCK - 1) / RR_BLOCK};
 }
 
 // The sample group of the batch [first, first + n): G where the batch holds whole groups of whole sample slices, else 1.

@@ -61,7 +61,77 @@ static int check_level_slice(uint64_t M, uint64_t child_base, uint64_t n, uint32
     return 0;
 }
 
+// The shadow-queue geometry of one shade chunk of `len` rays (plan_shade_chunk: what k_shade writes by and k_trace_shadow reads by) against
+// the allocations the plans ask for: the frame's queue p.sq_need with its sq_need / 64 + 1 validity words (rr_api_frame.h grow_ray_queues)
+// and, for a chunk that is a stage of level 1, a stage buffer.  `checked` counts the cases.
+static int check_shade_chunk(const FramePlanInputs& in, const FramePlan& p, uint64_t len, uint64_t* checked) {
+    const uint32_t L = in.n_enabled_lights;
+    for (const bool fixed : {false, true}) {
+        const uint64_t c0 = 12345 * RR_BLOCK; // (a chunk anywhere in its level: only the length counts)
+        const ShadeChunk g = plan_shade_chunk(c0, c0 + len, L, fixed);
+        CHECK(g.fixed == fixed && g.groups == (len + RR_BLOCK - 1) / RR_BLOCK && g.groups * RR_BLOCK >= len);
+        CHECK(g.sq_cap == (fixed ? g.groups * RR_BLOCK : 0) && g.sq_packets * RR_WAVE == L * g.sq_cap);
+        CHECK(g.shadow_wg * RR_BLOCK >= (fixed ? L * g.sq_cap : len * L) && g.shadow_wg <= (fixed ? L * g.sq_cap : len * L) / RR_BLOCK + 1);
+        CHECK(g.segcap <= 0xffffffffull && L * g.sq_cap <= 0xffffffffull); // the kernels' arguments and slot indices are 32-bit
+        CHECK(RR_SQ_SHARDS * g.segcap <= p.sq_need);                       // every shard's share of the dense queue lies inside it
+        CHECK(RR_SQ_SHARDS * g.segcap >= len * std::max(L, 1u));           // ... and the shards together hold every ray the chunk can write
+        if (len % ((uint64_t)RR_BLOCK * RR_SQ_SHARDS) == 0) CHECK(RR_SQ_SHARDS * g.segcap == len * std::max(L, 1u)); // whole rounds: equal shares
+        if (fixed && L >= 1 && L <= 32 && len <= p.B) {                    // level 1 with fixed slots (RR_FIXED_SLOT_LIGHTS, rr_kernels.hip)
+            CHECK(L * g.sq_cap <= p.sq_need);
+            CHECK(g.sq_packets <= p.sq_need / RR_WAVE + 1);
+        }
+    }
+    ++*checked;
+    return 0;
+}
+
+// ... and every stage of level 1 in stages (plan_level1_stages, as rr_api_frame.h asks for it: the batch's B hits): L x sq_cap slots fit a buffer
+static int check_stage_chunks(const FramePlanInputs& in, const FramePlan& p) {
+    const uint32_t L = in.n_enabled_lights;
+    if (L < 1 || L > 32) return 0;
+    for (const uint32_t n_buf : {2u, 3u}) {
+        const Level1Stages sp = plan_level1_stages({p.B, L, in.shade_chunk_rays, 20ull << 20, n_buf});
+        for (uint32_t k = 0; k < sp.n_stages; k++) {
+            const uint64_t c0 = sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, p.B);
+            const ShadeChunk g = plan_shade_chunk(c0, c1, L, true);
+            CHECK(L * g.sq_cap <= sp.buf_rays && g.sq_packets <= sp.buf_rays / RR_WAVE && g.segcap <= 0xffffffffull);
+            if (k > 2 && k + 3 < sp.n_stages) k = sp.n_stages - 3; // (the middle of a long level is all alike)
+        }
+    }
+    return 0;
+}
+
 int main() {
+    // the geometry of a shade chunk by hand: 257 rays are 2 groups, so 512 fixed slots per light; a shard holds ceil(2 / 32) groups x 3 lights
+    {
+        const ShadeChunk g = plan_shade_chunk(1000, 1257, 3, true), d = plan_shade_chunk(1000, 1257, 3, false), none = plan_shade_chunk(0, 65536, 0, true);
+        CHECK(g.groups == 2 && g.sq_cap == 512 && g.segcap == 768 && g.sq_packets == 24 && g.shadow_wg == 6);
+        CHECK(d.groups == 2 && d.sq_cap == 0 && d.segcap == 768 && d.sq_packets == 0 && d.shadow_wg == 4); // 771 rays at most: 4 workgroups
+        CHECK(none.groups == 256 && none.sq_cap == 65536 && none.segcap == 2048 && none.sq_packets == 0 && none.shadow_wg == 0); // no light: nothing to trace
+        CHECK(shade_chunk(1, 0) == 64ull << 20 && shade_chunk(1, 1) == 65536 && shade_chunk(1, 100000) == 100000 && shade_chunk(40, 0) == 8945664);
+    }
+    // ... and over a sweep of frames, against what their plans allocate
+    {
+        uint64_t checked = 0;
+        for (uint32_t npix : {1u, 64u, 9216u, 18240u, 921600u})
+            for (uint32_t spp : {1u, 2u, 8u, 16u, 128u})
+                for (uint32_t L : {0u, 1u, 2u, 32u, 33u, 300u})
+                    for (uint64_t chunk_rays : {0ull, 1ull, 65536ull, 100000ull, 1ull << 22})
+                        for (uint64_t budget : {150000ull * 128, 1ull << 30, 1ull << 36})
+                            for (uint32_t R : {0u, 4u, 15u}) {
+                                const FramePlanInputs in{npix, spp, R, budget, 0, 0, 2, L, chunk_rays};
+                                const FramePlan p = plan_frame(in);
+                                const uint64_t longest = std::min<uint64_t>(p.chunk, std::max<uint64_t>(p.M, p.B)); // no level holds more rays
+                                for (uint64_t len : {(uint64_t)1, (uint64_t)255, (uint64_t)256, (uint64_t)257, (uint64_t)8191, (uint64_t)8193, longest})
+                                    if (len <= longest && check_shade_chunk(in, p, len, &checked)) {
+                                        std::printf("  npix %u spp %u lights %u chunk %llu budget %llu R %u len %llu\n", npix, spp, L, (unsigned long long)chunk_rays,
+                                                    (unsigned long long)budget, R, (unsigned long long)len);
+                                        return 1;
+                                    }
+                                if (check_stage_chunks(in, p)) return 1;
+                            }
+        CHECK(checked == 44190); // (the sweep ran: 47 250 combinations, less the lengths no level of their frame can hold)
+    }
     for (const Case& c : k_cases) {
         const FramePlan p = plan_frame(c.in);
         if (p.B != c.B || p.G != c.G || p.M != c.M || p.chunk != c.chunk || p.sq_need != c.sq_need) {

@@ -45,8 +45,8 @@ static int check_invariants(const Level1StageInputs& in) {
         CHECK(p.begin_of(k) == at);
         const uint64_t end = std::min<uint64_t>(at + p.stage, in.n);
         CHECK(end > at && end - at <= p.stage);
-        const uint64_t padded = (end - at + RR_BLOCK - 1) / RR_BLOCK * RR_BLOCK; // the slots per light k_shade is given (sq_cap)
-        CHECK(L * padded <= p.buf_rays && L * (padded / RR_WAVE) <= p.buf_rays / RR_WAVE);
+        const ShadeChunk g = plan_shade_chunk(at, end, (uint32_t)L, true); // what k_shade and k_trace_shadow are given for the stage
+        CHECK(g.sq_cap >= end - at && L * g.sq_cap <= p.buf_rays && g.sq_packets == L * (g.sq_cap / RR_WAVE) && g.sq_packets <= p.buf_rays / RR_WAVE);
         CHECK(p.buffer_of(k) == k % p.n_buf);
         at = end;
         if (k > 4 && k + 4 < p.n_stages) { k = p.n_stages - 4; at = p.begin_of(k + 1); } // (the middle of a long level is all alike)

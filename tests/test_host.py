@@ -291,6 +291,14 @@ def test_the_library_has_one_list_of_sources(tmp_path):
     assert set(capi.LIB_SOURCES) == used
     prereq = _makefile_csrc_prerequisites(os.path.join(csrc, "Makefile"))
     assert len(set(prereq)) == len(prereq) and set(prereq) == used
+    # ... and in these files the two kernels of a shade chunk have ONE launch site each (rr_api_frame.h launch_shade, launch_shadow): the
+    # serial loop and the staged path cannot pass them different arguments
+    import re
+    code = "".join(re.sub(r"//[^\n]*", "", open(os.path.join(csrc, name)).read()) for name in sorted(used))
+    launched = re.findall(r"hipLaunchKernelGGL\s*\(([^,]*),", code)   # the first argument of every launch: the kernel
+    assert len(launched) > 20   # (the pattern found the launches)
+    for kernel in ("k_shade", "k_trace_shadow"):
+        assert sum(1 for k in launched if re.search(r"\b%s\b" % kernel, k)) == 1, kernel
     # the comparison notices a header that is included and not listed
     copy = str(tmp_path / "csrc")
     shutil.copytree(csrc, copy, ignore=shutil.ignore_patterns("*.so", "*.o"))
