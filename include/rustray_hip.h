@@ -58,7 +58,9 @@ extern "C" {
  * rr_motion_records and rr_motion_records_device came after those, without a struct of their own: a version-3 library may lack these two
  * as well.
  * rr_surface_pixels and rr_surface_pixels_device came after those in the same way: a version-3 library may lack these two as well.
- * rr_albedo_pixels and rr_albedo_pixels_device came after those in the same way: a version-3 library may lack these two as well. */
+ * rr_albedo_pixels and rr_albedo_pixels_device came after those in the same way: a version-3 library may lack these two as well.
+ * rr_render_pixel_split, rr_render_pixel_split_device, rr_denoise_split_records and rr_denoise_split_records_device came after those in the
+ * same way: a version-3 library may lack these four as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1241,6 +1243,65 @@ int rr_albedo_pixels(rr_scene* scene, const rr_camera* camera, const rr_config* 
 int rr_albedo_pixels_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* or NULL */,
                             const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels,
                             float* albedo_out_dev /* n_pixels * 3 */, void* hip_stream, const volatile int* cancel);
+
+/* A frame's records and, as a sum of its own, the DIRECT DIFFUSE light of its primary hits: the part of a pixel's colour that the base
+ * colour of the surface under it modulates.  What is left, out.color - diffuse, is "rest": ambient and fog, highlights, and everything
+ * behind mirrors and glass.  rr_denoise_split_records takes the pair; the diffuse pass is also what a compositor relights.
+ * RECORDS.  out and halves_out are, bit for bit, what rr_render_pixel_parts writes at n_parts = 2 for the same arguments (out and parts_out);
+ *   with halves_out == NULL, out is what rr_render_pixels writes.  The list and whole-frame rules are rr_render_pixels'.
+ * TERM.  For every hit of depth 1 (a primary ray's own hit) and every enabled light, with the names of the shading step,
+ *   d[c] = ((light.color[c] * (base_color[c] * dot_light)) * intensity) * w_light, in exactly this order of binary32 operations: the light's
+ *   term of the frame with the specular product left out.  It is multiplied by the shadow factor the light's shadow ray gets for the whole
+ *   term (1 for a receiver that takes no shadows, and no term where the whole term is exactly 0).  A miss adds 0; hits of depth 2 and
+ *   deeper add nothing.
+ * SUM.  Exactly rr_radiance.color's: every term clamped to +-32768, scaled by 2^24 and rounded to nearest-even by itself, added as an
+ *   integer; diffuse_out[3p + c] = (float)(sum * 2^-24) / (float)S, and diffuse_halves_out[3 (2p + h) + c] the same over the half's S / 2
+ *   samples (half h = the samples s with s mod 2 == h).  Integer adds commute: the result does not depend on batching, chunks or rr_tuning.
+ *   A channel whose record colour is not finite (NaN, +-inf) holds the record's value in diffuse_out too; no second set of flags is kept.
+ * ARGUMENTS.  out and diffuse_out are required; halves_out and diffuse_halves_out are given together or not at all, and with them
+ *   config->samples must be even (RR_ERR_INVALID_ARGUMENT, the message of rr_render_pixel_parts).  n_pixels == 0 returns RR_OK and touches
+ *   nothing; n_pixels (x 2 with halves) above 2^30 is RR_ERR_UNSUPPORTED.
+ * A FRAME CALL in the sense of rr_render_pixels: the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene; cancel as
+ *   rr_render_pixel_parts; rr_scene_last_stats reports the counters rr_render_pixel_parts reports for the same frame; the frames before
+ *   and after are bit-identical.  Level 1 of the call runs its shade and shadow launches one after the other on the call's stream.
+ * rr_render_pixel_split_device: buffers the scene's device can address, in stream order, under every rule of rr_render_pixels_device:
+ *   pointers classified before any launch, out_dev and halves_out_dev 16-byte aligned, the others 4-byte aligned, overlaps refused; the
+ *   list may come from the stream unsynchronised.  A call that ends early leaves the stream idle.  Device memory kept by the handle until
+ *   rr_scene_destroy, beyond rr_render_pixel_parts' own: 24 B per accumulator slot and 16 B per ray of the shadow queue.
+ * rr_render_pixel_split: the same on HOST pointers, the device form on the null stream behind staging copies in buffers of the call, freed on
+ *   return; the list is checked before anything is uploaded, and the call returns with the outputs written. */
+int rr_render_pixel_split(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* or NULL */,
+                          const uint32_t* pixel_xy /* or NULL */, uint32_t n_pixels,
+                          rr_radiance* out /* n_pixels */, rr_radiance* halves_out /* n_pixels * 2, or NULL */,
+                          float* diffuse_out /* n_pixels * 3 */, float* diffuse_halves_out /* n_pixels * 2 * 3; NULL exactly when halves_out is */,
+                          const volatile int* cancel);
+int rr_render_pixel_split_device(rr_scene* scene, const rr_camera* camera, const rr_config* config, const uint16_t* sample_xy /* or NULL */,
+                                 const uint32_t* pixel_xy_dev /* or NULL */, uint32_t n_pixels,
+                                 rr_radiance* out_dev /* n_pixels */, rr_radiance* halves_out_dev /* n_pixels * 2, or NULL */,
+                                 float* diffuse_out_dev /* n_pixels * 3 */,
+                                 float* diffuse_halves_out_dev /* n_pixels * 2 * 3; NULL exactly when halves_out_dev is */,
+                                 void* hip_stream, const volatile int* cancel);
+
+/* rr_denoise_records with the albedo applied to the direct diffuse part of the colour alone.  Two record sets share depth, normal and id
+ * with `records`: REST, whose colour is records.color - diffuse (one binary32 subtraction per channel), and DIRECT, whose colour is diffuse;
+ * halves and diffuse_halves (given together or not at all) are split the same way.  out.color = F(rest, rest halves, no albedo).color +
+ * F(direct, direct halves, albedo).color, one binary32 add per channel, with F the filter of rr_denoise_records under `params`, every
+ * step exact in binary32 as stated there; a pixel whose record colour is not finite keeps the record's colour.  Depth, normal and id
+ * are the record's bits.  rgba8_out (or NULL) gets the bytes of out as rr_denoise_records writes them; no variance is offered.
+ * rustray_amd/denoise.py: atrous_denoise_split follows this text in numpy, and the result equals it bit for bit.
+ * Arguments, refusals, alignment, the in-place rule (out == records) and the stream order are rr_denoise_records(_device)'s; diffuse is
+ * width * height * 3 floats and required, diffuse_halves width * height * 2 * 3 floats, both 4-byte aligned in the device form, neither
+ * overlapping an output.  Device memory kept by the handle until rr_scene_destroy, beyond rr_denoise_records' own: 64 B per pixel, and
+ * 128 B more with halves. */
+int rr_denoise_split_records_device(rr_scene* scene, uint32_t width, uint32_t height, const rr_denoise_params* params,
+                                    const rr_radiance* records_dev, const rr_radiance* halves_dev /* or NULL */,
+                                    const float* diffuse_dev, const float* diffuse_halves_dev /* NULL exactly when halves_dev is */,
+                                    const float* albedo_dev /* or NULL */, rr_radiance* out_dev, uint8_t* rgba8_out_dev /* or NULL */,
+                                    void* hip_stream);
+int rr_denoise_split_records(rr_scene* scene, uint32_t width, uint32_t height, const rr_denoise_params* params,
+                             const rr_radiance* records, const rr_radiance* halves /* or NULL */,
+                             const float* diffuse, const float* diffuse_halves /* NULL exactly when halves is */,
+                             const float* albedo /* or NULL */, rr_radiance* out, uint8_t* rgba8_out /* or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -581,6 +581,40 @@ public:
         return rr_render_pixel_parts_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, n_parts, out_dev, parts_out_dev, hip_stream, cancel);
     }
 
+    // render_pixel_parts at n_parts = 2 and, as a sum of its own, the frame's direct diffuse light of the primary hits (rr_render_pixel_split):
+    // returns the full records and fills halves[i * 2 + h], diffuse[i * 3 + c] and diffuse_halves[(i * 2 + h) * 3 + c].  halves and
+    // diffuse_halves are both given or both nullptr (then the records are render_pixels' and config.samples may be odd).  All empty =
+    // refused or failed (rr_last_error() says why).  color - diffuse is everything the base colour does not modulate.
+    std::vector<rr_radiance> render_pixel_split(const uint32_t* xy, size_t n, std::vector<rr_radiance>* halves, std::vector<float>* diffuse,
+                                                std::vector<float>* diffuse_halves) const {
+        std::vector<rr_radiance> out;
+        if (halves) halves->clear();
+        if (diffuse) diffuse->clear();
+        if (diffuse_halves) diffuse_halves->clear();
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        if (!xy) n = (size_t)cam.width * cam.height;
+        if (!diffuse || (halves == nullptr) != (diffuse_halves == nullptr) || n == 0 || n * 2 > ((size_t)1 << 30)) return out;
+        out.resize(n);
+        diffuse->assign(3 * n, 0.0f);
+        if (halves) { halves->resize(2 * n); diffuse_halves->assign(6 * n, 0.0f); }
+        if (rr_render_pixel_split(scene->handle(), &cam, &c, nullptr, xy, (uint32_t)n, out.data(), halves ? halves->data() : nullptr, diffuse->data(),
+                                  halves ? diffuse_halves->data() : nullptr, nullptr) != RR_OK) {
+            out.clear();
+            diffuse->clear();
+            if (halves) { halves->clear(); diffuse_halves->clear(); }
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_render_pixel_split_device): xy_dev nullptr = the whole frame (n_pixels = width * height)
+    int render_pixel_split_device(const uint32_t* xy_dev, uint32_t n_pixels, rr_radiance* out_dev, rr_radiance* halves_out_dev, float* diffuse_out_dev,
+                                  float* diffuse_halves_out_dev, void* hip_stream, const volatile int* cancel = nullptr) const {
+        const rr_camera cam = camera.c_struct();
+        const rr_config c = config.c_struct();
+        return rr_render_pixel_split_device(scene->handle(), &cam, &c, nullptr, xy_dev, n_pixels, out_dev, halves_out_dev, diffuse_out_dev, diffuse_halves_out_dev,
+                                            hip_stream, cancel);
+    }
+
     // A frame at two sample counts (rr_render_adaptive): every pixel at base_samples (even, at least 2), and at max_samples where the
     // half-buffer error of the base frame -- max over channels of |min(A, 1) - min(B, 1)| / 2 of the pixel's two halves -- exceeds
     // `threshold`; estimate, list, fine pass and scatter run on the device under one hold of the scene's lock.  config.samples is ignored.
@@ -717,10 +751,31 @@ public:
         return denoise(records.data(), halves.data(), with_albedo ? guide.data() : nullptr, params, nullptr, rgba8);
     }
     // The same with the albedo guide named: NONE and CENTRE are with_albedo = false and true above, bit for bit; MEAN takes mean_albedo(),
-    // one rr_albedo_pixels call with this frame's config in place of the rr_surface_pixels call.
-    enum class AlbedoGuide { NONE, CENTRE, MEAN };
+    // one rr_albedo_pixels call with this frame's config in place of the rr_surface_pixels call.  DIFFUSE: the frame comes from
+    // render_pixel_split, the albedo is mean_albedo(), and rr_denoise_split_records demodulates the direct diffuse part of the colour alone.
+    enum class AlbedoGuide { NONE, CENTRE, MEAN, DIFFUSE };
     std::vector<rr_radiance> render_denoised(AlbedoGuide guide_kind, const rr_denoise_params* params = nullptr, std::vector<uint8_t>* rgba8 = nullptr,
                                              std::vector<rr_radiance>* noisy = nullptr) const {
+        if (guide_kind == AlbedoGuide::DIFFUSE) {
+            std::vector<rr_radiance> halves, out;
+            std::vector<float> diffuse, diffuse_halves;
+            const std::vector<rr_radiance> records = render_pixel_split(nullptr, 0, &halves, &diffuse, &diffuse_halves);
+            if (records.empty()) return records;
+            if (noisy) *noisy = records;
+            const std::vector<float> guide = mean_albedo();
+            rr_denoise_params prm;
+            if (params) prm = *params;
+            else if (rr_denoise_default_params(&prm) != RR_OK) return out;
+            if (guide.empty()) return out;
+            out.resize(records.size());
+            if (rgba8) rgba8->assign(4 * records.size(), 0);
+            if (rr_denoise_split_records(scene->handle(), camera.width, camera.height, &prm, records.data(), halves.data(), diffuse.data(), diffuse_halves.data(),
+                                         guide.data(), out.data(), rgba8 ? rgba8->data() : nullptr) != RR_OK) {
+                out.clear();
+                if (rgba8) rgba8->clear();
+            }
+            return out;
+        }
         if (guide_kind != AlbedoGuide::MEAN) return render_denoised(params, rgba8, noisy, guide_kind == AlbedoGuide::CENTRE);
         std::vector<rr_radiance> halves;
         const std::vector<rr_radiance> records = render_pixel_parts(nullptr, 0, 2, &halves);

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -54,7 +54,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -181,6 +181,13 @@ def lib():
             L.rr_albedo_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rr_albedo_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
+        if hasattr(L, "rr_render_pixel_split") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
+            L.rr_render_pixel_split.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_render_pixel_split_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rr_denoise_split_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params)] + [C.c_void_p] * 7
+            L.rr_denoise_split_records_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params)] + [C.c_void_p] * 8
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -663,6 +670,31 @@ class DeviceScene:
         _check(lib().rr_render_pixel_parts_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), C.c_uint32(n_parts), _ptr(out_ptr),
                                                   _ptr(parts_ptr), _ptr(stream_ptr), _flag(cancel)))
 
+    def render_pixel_split(self, cam: rr_camera, cfg: rr_config, pixels=None, halves: bool = True, sample_xy=None, cancel=None):
+        """rr_render_pixel_split: the dict of render_pixel_parts at n_parts = 2 (without `parts` when halves=False: the dict of render_pixels)
+        plus diffuse (n, 3) float32, the direct diffuse light of the primary hits summed on its own, and with halves diffuse_halves (n, 2, 3)."""
+        n, xy, xy_p = _pixel_list(cam, pixels)
+        out = np.zeros((max(n, 1), 8), np.float32)
+        parts = np.zeros((max(n, 1), 2, 8), np.float32) if halves else None
+        dif = np.zeros((max(n, 1), 3), np.float32)
+        dif_h = np.zeros((max(n, 1), 2, 3), np.float32) if halves else None
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_split(self._h, C.byref(cam), C.byref(cfg), p, xy_p, C.c_uint32(n), _data(out), _data(parts), _data(dif), _data(dif_h), _flag(cancel)))
+        res = dict(_records(out[:n]), diffuse=dif[:n])
+        if halves:
+            res["parts"] = _records(parts[:n])
+            res["diffuse_halves"] = dif_h[:n]
+        return res
+
+    def render_pixel_split_device(self, cam: rr_camera, cfg: rr_config, pixel_xy_ptr, n_pixels: int, out_ptr, halves_ptr, diffuse_ptr, diffuse_halves_ptr,
+                                  stream_ptr=None, sample_xy=None, cancel=None):
+        """rr_render_pixel_split_device: n_pixels uint32 entries x | y << 16 (None = the whole frame, n_pixels = width * height), n_pixels and
+        (or None) n_pixels * 2 32-byte rr_radiance records (16-byte aligned), n_pixels x 3 and (None exactly when halves_ptr is) n_pixels x 2 x 3
+        float32, all raw device pointers; enqueued on `stream_ptr`."""
+        keep, p = _sxy(sample_xy)
+        _check(lib().rr_render_pixel_split_device(self._h, C.byref(cam), C.byref(cfg), p, _ptr(pixel_xy_ptr), C.c_uint32(n_pixels), _ptr(out_ptr), _ptr(halves_ptr),
+                                                  _ptr(diffuse_ptr), _ptr(diffuse_halves_ptr), _ptr(stream_ptr), _flag(cancel)))
+
     # -- adaptive sampling on the device ----------------------------------------------
     def refine_list_device(self, width: int, height: int, parts_ptr, threshold: float, error_ptr, list_ptr, stream_ptr=None) -> int:
         """rr_refine_list_device: adaptive.refine_list(adaptive.half_error(parts), threshold, width, height) on the device.  parts_ptr: the
@@ -815,6 +847,36 @@ class DeviceScene:
         p = denoise_params(params)
         _check(lib().rr_denoise_records_device(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(albedo_ptr),
                                                _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(variance_ptr), _ptr(stream_ptr)))
+
+    def denoise_split(self, width: int, height: int, records, diffuse, halves=None, diffuse_halves=None, albedo=None, params=None, rgba8: bool = False,
+                      in_place: bool = False) -> dict:
+        """rr_denoise_split_records: denoise.atrous_denoise_split on the device, host arrays in and out.  records, halves, albedo and params
+        as denoise_records takes them; diffuse: (n, 3) float32, diffuse_halves: (n, 2, 3) or None (exactly when halves is).  Returns
+        dict(records (n, 8) float32, and on request rgba (n, 4) uint8)."""
+        n = int(width) * int(height)
+        rec = np.array(records, np.float32, order="C").reshape(n, 8) if in_place else np.ascontiguousarray(records, np.float32).reshape(n, 8)
+        hv = None if halves is None else np.ascontiguousarray(halves, np.float32).reshape(n, 2, 8)
+        df = None if diffuse is None else np.ascontiguousarray(diffuse, np.float32).reshape(n, 3)
+        dh = None if diffuse_halves is None else np.ascontiguousarray(diffuse_halves, np.float32).reshape(n, 2, 3)
+        al = None if albedo is None else np.ascontiguousarray(albedo, np.float32).reshape(n, 3)
+        out = rec if in_place else np.zeros((n, 8), np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        p = denoise_params(params)
+        _check(lib().rr_denoise_split_records(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _data(rec), _data(hv), _data(df), _data(dh), _data(al),
+                                              _data(out), _data(rgba)))
+        res = dict(records=out)
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def denoise_split_device(self, width: int, height: int, records_ptr, halves_ptr, diffuse_ptr, diffuse_halves_ptr, albedo_ptr, out_ptr, rgba8_ptr=None, params=None,
+                             stream_ptr=None):
+        """rr_denoise_split_records_device: the buffers of denoise_records_device without the variance, plus width * height x 3 float32 of
+        diffuse and (None exactly when halves_ptr is) width * height x 2 x 3 of its halves, all raw device pointers; enqueued on `stream_ptr`,
+        not waited for."""
+        p = denoise_params(params)
+        _check(lib().rr_denoise_split_records_device(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(diffuse_ptr),
+                                                     _ptr(diffuse_halves_ptr), _ptr(albedo_ptr), _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
 
     # -- temporal reprojection of a frame of records -----------------------------------
     def accumulate_records(self, cam: rr_camera, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,

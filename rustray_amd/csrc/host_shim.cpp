@@ -395,6 +395,34 @@ extern "C" int rh_render_denoised_mean_albedo(void* h, float fov, const float* e
     }
     return 0;
 }
+// rh_render_pixel_split: Raytracing::render_pixel_split; xy = n entries or NULL (the whole frame, n = w * h); out = n records, diffuse = n * 3
+// floats, halves = n * 2 records and diffuse_halves = n * 2 * 3 floats or both NULL; returns the number of records, or -1 when refused.
+extern "C" int rh_render_pixel_split(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                     uint32_t w, uint32_t hgt, const uint32_t* xy, uint32_t n, rr_radiance* out, rr_radiance* halves, float* diffuse,
+                                     float* diffuse_halves) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> hv;
+    std::vector<float> d, dh;
+    const std::vector<rr_radiance> r = rt.render_pixel_split(xy, n, halves ? &hv : nullptr, &d, diffuse_halves ? &dh : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    std::memcpy(diffuse, d.data(), d.size() * 4);
+    if (halves) std::memcpy(halves, hv.data(), hv.size() * sizeof(rr_radiance));
+    if (diffuse_halves) std::memcpy(diffuse_halves, dh.data(), dh.size() * 4);
+    return (int)r.size();
+}
+// rh_render_denoised_diffuse: Raytracing::render_denoised(AlbedoGuide::DIFFUSE); out = w * h records, noisy = the same or NULL; returns 0, or
+// -1 when a call was refused.
+extern "C" int rh_render_denoised_diffuse(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                          uint32_t w, uint32_t hgt, const rr_denoise_params* params, rr_radiance* out, rr_radiance* noisy) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> raw;
+    const std::vector<rr_radiance> r = rt.render_denoised(Raytracing::AlbedoGuide::DIFFUSE, params, nullptr, noisy ? &raw : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
+    return 0;
+}
 // Raytracing::accumulate: records = w * h, halves = w * h * 2 or NULL, history / history_halves / history_length = the previous call's
 // out / halves_out / length_out or all NULL (the first frame), params or NULL for the defaults, motion = w * h * 3 floats or NULL; out,
 // halves_out (with halves), length_out, rgba8 or NULL; returns 0, or -1 when the call was refused.

@@ -1,7 +1,8 @@
 // rr_api_denoise.h — the variance-guided a-trous filter over a frame of records, on the device: what a host does with the records,
 // the halves and the albedo the other calls give it, without a trip through host memory.
 // Offers: rr_denoise_default_params, rr_denoise_records_device, rr_denoise_records; rr_test_denoise_forms (the tuning hook of the tests
-//         and of tools/denoise_time.py).
+//         and of tools/denoise_time.py); rr_denoise_split_records_device, rr_denoise_split_records (the filter with the albedo applied to
+//         the direct diffuse part of the colour alone: two runs of the launches above between two streaming kernels).
 // Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_denoise.h,
 //         kernels 7a .. 7d of rr_kernels.hip.
 //
@@ -132,3 +133,85 @@ int rr_denoise_records(rr_scene* s, uint32_t width, uint32_t height, const rr_de
         });
     });
 } RR_GUARD_END("rr_denoise_records")
+
+// ---- rr_denoise_split_records: colour = rest + direct diffuse (rr_render_pixel_split); the filter runs on `rest` without an albedo and on the
+// direct part with it, and the two results are added.  k_denoise_split_sets makes the two record sets (and their halves) in the handle's
+// scratch (DenoiseState::split, 192 B per pixel with halves), denoise_locked runs on each in place, k_denoise_split_sum adds.
+struct DenoiseSplitIo {
+    const rr_radiance* records; const rr_radiance* halves; const float* diffuse; const float* diffuse_halves; const float* albedo;
+    rr_radiance* out; uint8_t* rgba8;
+};
+
+static int check_denoise_split_args(const char* fn, bool device, const rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm,
+                                    const DenoiseSplitIo& io) {
+    RR_TRY(check_denoise_args(fn, device, s, width, height, prm, DenoiseIo{io.records, io.halves, io.albedo, io.out, io.rgba8, nullptr}));
+    if (!io.diffuse) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse is NULL", fn);
+    if ((io.halves != nullptr) != (io.diffuse_halves != nullptr))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: halves and diffuse_halves are given together or not at all", fn);
+    if (device && (((uintptr_t)io.diffuse | (uintptr_t)io.diffuse_halves) & 3u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_dev and diffuse_halves_dev must be 4-byte aligned", fn);
+    const uint64_t n = (uint64_t)width * height;
+    const ArgRange t[4] = {{io.diffuse, 12u * n, "diffuse", false, -1}, {io.diffuse_halves, 24u * n, "diffuse_halves", false, -1},
+                           {io.out, 32u * n, "out", true, -1}, {io.rgba8, 4u * n, "rgba8_out", true, -1}};
+    return check_arg_ranges(fn, t, 4, false, "");
+}
+
+static int denoise_split_locked(rr_scene* s, uint32_t W, uint32_t H, const rr_denoise_params* prm, const DenoiseSplitIo& io, hipStream_t st) {
+    const uint64_t N = (uint64_t)W * H;
+    DenoiseState& d = s->denoise;
+    HIP_TRY(d.split[0].reserve(32ull * N));
+    HIP_TRY(d.split[1].reserve(32ull * N));
+    if (io.halves) {
+        HIP_TRY(d.split[2].reserve(64ull * N));
+        HIP_TRY(d.split[3].reserve(64ull * N));
+    }
+    rr_radiance* const rest = d.split[0].as<rr_radiance>();
+    rr_radiance* const direct = d.split[1].as<rr_radiance>();
+    rr_radiance* const rest_h = io.halves ? d.split[2].as<rr_radiance>() : nullptr;
+    rr_radiance* const direct_h = io.halves ? d.split[3].as<rr_radiance>() : nullptr;
+    const int grid = (int)std::min<uint64_t>((N + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
+    hipLaunchKernelGGL(k_denoise_split_sets, dim3(grid), dim3(RR_BLOCK), 0, st, (const float4*)io.records, (const float4*)io.halves, io.diffuse, io.diffuse_halves, (uint32_t)N,
+                       (float4*)rest, (float4*)direct, (float4*)rest_h, (float4*)direct_h);
+    // the filter's own launches, twice, each in place on its set; neither writes bytes
+    rr_denoise_params plain = *prm;
+    plain.gamma_correction = 0u;
+    RR_TRY(denoise_locked(s, W, H, &plain, DenoiseIo{rest, rest_h, nullptr, rest, nullptr, nullptr}, st));
+    RR_TRY(denoise_locked(s, W, H, &plain, DenoiseIo{direct, direct_h, io.albedo, direct, nullptr, nullptr}, st));
+    hipLaunchKernelGGL(k_denoise_split_sum, dim3(grid), dim3(RR_BLOCK), 0, st, (const float4*)io.records, (const float4*)rest, (const float4*)direct, (uint32_t)N, (float4*)io.out);
+    if (io.rgba8) {
+        rr_config cfg{};
+        cfg.gamma_correction = prm->gamma_correction ? 1 : 0;
+        launch_record_bytes(s, &cfg, io.out, (uint32_t)N, io.rgba8, st);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(RR_ERR_DEVICE, "rr_denoise_split_records: a launch failed");
+    return RR_OK;
+}
+
+// (defined under the C linkage of their declarations in include/rustray_hip.h)
+int rr_denoise_split_records_device(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                                    const float* diffuse, const float* diffuse_halves, const float* albedo, rr_radiance* out, uint8_t* rgba8_out,
+                                    void* hip_stream) try {
+    const char* fn = "rr_denoise_split_records_device";
+    const DenoiseSplitIo io{records, halves, diffuse, diffuse_halves, albedo, out, rgba8_out};
+    RR_TRY(check_denoise_split_args(fn, true, s, width, height, prm, io));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {diffuse, "diffuse_dev"}, {diffuse_halves, "diffuse_halves_dev"},
+                                      {albedo, "albedo_dev"}, {out, "out_dev"}, {rgba8_out, "rgba8_out_dev"}}, st,
+                       [&] { return denoise_split_locked(s, width, height, prm, io, st); });
+} RR_GUARD_END("rr_denoise_split_records_device")
+
+int rr_denoise_split_records(rr_scene* s, uint32_t width, uint32_t height, const rr_denoise_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                             const float* diffuse, const float* diffuse_halves, const float* albedo, rr_radiance* out, uint8_t* rgba8_out) try {
+    const char* fn = "rr_denoise_split_records";
+    RR_TRY(check_denoise_split_args(fn, false, s, width, height, prm, DenoiseSplitIo{records, halves, diffuse, diffuse_halves, albedo, out, rgba8_out}));
+    const size_t n = (size_t)width * height;
+    const StageArg args[7] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(diffuse, 12 * n), stage_input(diffuse_halves, 24 * n),
+                              stage_input(albedo, 12 * n), stage_output(out, 32 * n), stage_output(rgba8_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const DenoiseSplitIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const float*)d[2], (const float*)d[3], (const float*)d[4], (rr_radiance*)d[5],
+                                     (uint8_t*)d[6]};
+            return denoise_split_locked(s, width, height, prm, dev, nullptr);
+        });
+    });
+} RR_GUARD_END("rr_denoise_split_records")

@@ -3,7 +3,8 @@
 //         launch_trace_closest; FrameEnd, FrameIo and its makers frame_io and pixels_io, frame_end_plan (what an ending implies),
 //         ALL_PLANES; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun and its maker
 //         make_frame_run; launch_shade and launch_shadow (THE launch sites of k_shade and k_trace_shadow), read_back_level_size;
-//         run_level (with level 1 in stages on three streams; with FrameEnd::ALBEDO level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h);
+//         run_level (with level 1 in stages on three streams; with FrameEnd::ALBEDO level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h;
+//         with FrameEnd::RECORD_SPLIT level 1 runs the SPLIT builds of the two kernels, serially: rr_api_pixel_split.h); pick_build;
 //         take_stream, begin_frame_stats;
 //         WHOLE_FRAME, IdleOnExit, fill_pixel_slots, render_region_locked (the pixel queries and the adaptive calls are its other callers);
 //         rr_render_region_device, rr_render, rr_render_progressive, rr_render_progressive_tiles; add_pass_stats, PassSums,
@@ -160,6 +161,9 @@ enum class FrameEnd {
     RECORD_PARTS, // k_resolve_pixel_parts (rr_api_parts.h): `parts` gets the K part records of every pixel, `radiance` the pixel's full record
     ALBEDO,       // rr_albedo_pixels (rr_api_albedo_pixels.h): level 1 ends in k_albedo_level1 instead of the shade and shadow kernels, nothing spawns,
                   // only the colour planes are accumulated, and k_resolve_albedo writes three floats per pixel to `albedo`
+    RECORD_SPLIT, // rr_render_pixel_split (rr_api_pixel_split.h): level 1 runs the SPLIT builds of k_shade and k_trace_shadow, which sum the direct
+                  // diffuse light of the primary hits in three planes of their own; k_resolve_pixel_split writes RECORD_PARTS' outputs (`parts` only
+                  // with lg_parts > 0) and the planes as floats to `diffuse` and `diffuse_parts`
     NONE,         // no resolve: the caller reads the accumulators itself (every plane: rr_api_prefix.h)
 };
 // Where the accumulator slots of a frame come from and how the frame ends, by value (render_region_locked):
@@ -171,6 +175,7 @@ struct FrameIo {
     FrameEnd end = FrameEnd::REGION_BYTES;
     const rr_frame* out = nullptr; bool frame_layout = false; const PassHook* hook = nullptr;
     rr_radiance* radiance = nullptr; uint8_t* rgba8 = nullptr; float* albedo = nullptr;
+    float* diffuse = nullptr; float* diffuse_parts = nullptr; // RECORD_SPLIT: 3 floats per pixel, and per part where lg_parts > 0
     // rr_render_pixel_parts (rr_api_parts.h): 2^lg_parts accumulator slots per pixel, slot i * K + h = part h of entry i
     uint32_t lg_parts = 0u; rr_radiance* parts = nullptr;
     // rr_render_pixel_prefix and rr_render_adaptive_prefix (rr_api_prefix.h): the samples [samples_from, samples_used) of the frame of
@@ -198,11 +203,13 @@ static FrameIo pixels_io(const uint32_t* pixel_xy, uint32_t n_pixels, rr_radianc
 // What an ending implies, stated once: the accumulator planes (aux: the three aux planes are reserved and zeroed; normal, depth, id:
 // handed to the kernels -- an aux output nobody asked for is not accumulated at all) and whether level 1 ends every path (no arena, no
 // shadow queue, R = 0).  Records hold all three aux means.
-struct FrameEndPlan { bool aux, normal, depth, id, level1_only; };
-static const FrameEndPlan ALL_PLANES{true, true, true, true, false}; // (also what rr_shade_rays, which resolves its own way, accumulates)
+// split: three diffuse planes and the fourth shadow-queue array are reserved, and level 1 runs the SPLIT builds, serially.
+struct FrameEndPlan { bool aux, normal, depth, id, level1_only, split; };
+static const FrameEndPlan ALL_PLANES{true, true, true, true, false, false}; // (also what rr_shade_rays, which resolves its own way, accumulates)
 static FrameEndPlan frame_end_plan(const FrameIo& io) {
-    if (io.end == FrameEnd::ALBEDO) return FrameEndPlan{false, false, false, false, true};
-    if (io.end == FrameEnd::REGION_BYTES) return FrameEndPlan{true, io.out->normal != nullptr, io.out->depth != nullptr, io.out->object_id != nullptr, false};
+    if (io.end == FrameEnd::ALBEDO) return FrameEndPlan{false, false, false, false, true, false};
+    if (io.end == FrameEnd::REGION_BYTES) return FrameEndPlan{true, io.out->normal != nullptr, io.out->depth != nullptr, io.out->object_id != nullptr, false, false};
+    if (io.end == FrameEnd::RECORD_SPLIT) return FrameEndPlan{true, true, true, true, false, true};
     return ALL_PLANES;
 }
 
@@ -301,7 +308,15 @@ static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sa
 // zeroed accumulators (and work counters) for npix slots: the planes `want` names (a call that sums colours only reserves and touches no
 // aux plane; an aux plane that is reserved is zeroed whether or not the kernels are handed it).
 // resident: the set to go on with instead, as it is (every plane present, n == npix); the work counters are zeroed all the same.
-static int reset_accumulators(rr_scene* s, uint32_t npix, const FrameEndPlan& want, hipStream_t st, DAccum* acc, const DAccum* resident = nullptr) {
+// want.split: the three diffuse planes of rr_render_pixel_split as well, to *diffuse (never with resident accumulators).
+static int reset_accumulators(rr_scene* s, uint32_t npix, const FrameEndPlan& want, hipStream_t st, DAccum* acc, const DAccum* resident = nullptr,
+                              long long** diffuse = nullptr) {
+    if (want.split) {
+        if (resident || !diffuse) return fail(RR_ERR_DEVICE, "internal: a split frame on resident accumulators");
+        HIP_TRY(s->frame.acc_diffuse.reserve((size_t)npix * 24));
+        HIP_TRY(hipMemsetAsync(s->frame.acc_diffuse.p, 0, (size_t)npix * 24, st));
+        *diffuse = s->frame.acc_diffuse.as<long long>();
+    }
     if (resident) {
         if (resident->n != npix || !resident->rgb || !resident->normal || !resident->depth || !resident->object_id || !resident->flags)
             return fail(RR_ERR_DEVICE, "internal: resident accumulators of %llu slots for a pass of %u", resident->n, npix);
@@ -338,7 +353,9 @@ static Level1Stages level1_stages(const rr_scene* s, uint64_t n) {
 }
 
 // the ray arena for M rays and the shadow queue for sq_need rays, with at least valid_need words of lane masks (grown, never shrunk)
-static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t valid_need) {
+// split: the fourth queue array of rr_render_pixel_split as well (16 B per ray; no other frame reserves it)
+static int grow_ray_queues(rr_scene* s, uint64_t M, uint64_t sq_need, uint64_t valid_need, bool split = false) {
+    if (split) HIP_TRY(s->frame.sq3.reserve(std::max<uint64_t>(sq_need, s->frame.sq_cap) * 16)); // (as many rays as sq[2] holds after this call)
     if (M > s->frame.arena_cap) {
         for (int k = 0; k < 4; k++) HIP_TRY(s->frame.arena[k].reserve(M * RAY_RECORD_BYTES[k]));
         s->frame.arena_cap = M;
@@ -395,6 +412,8 @@ struct FrameRun {
     const uint32_t* slot_xy = nullptr; // accumulator slot -> RNG pixel as (x | y << 16): the region's map, the pixel list of rr_render_pixels, or the stream ids of rr_shade_rays
     bool seeded = false;               // rr_shade_rays: depth level 1 is ray RECORDS at the front of the arena (k_seed_rays), not derived from its index
     bool level1_only = false;          // FrameEnd::ALBEDO: level 1 ends in k_albedo_level1 (R = 0: the level spawns nothing; never in stages)
+    // FrameEnd::RECORD_SPLIT: the diffuse planes (3 x acc.n words) and the fourth shadow-queue array; level 1 runs the SPLIT builds, never in stages
+    long long* diffuse = nullptr; float4* sq_s3 = nullptr;
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
     }
@@ -424,6 +443,11 @@ static ChunkShadow take_chunk_shadow(FrameRun& f, uint64_t ray_offset, uint64_t 
 // (A template's builds are emitted in the order they are first named.  This line names the four in the order the code object has always
 // held them, level 1's pair before the deeper levels', so the library's device assembly stays byte for byte what it was and a diff of it
 // remains a usable check of a change to the host code.)
+// `first` where FIRST, else `other`: the kernel of a launch whose SPLIT build is another function type than the builds it stands beside
+template <bool FIRST, class A, class B> static auto pick_build(A first, B other) {
+    if constexpr (FIRST) return first;
+    else return other;
+}
 [[maybe_unused]] static const void* const k_chunk_kernel_order[4] = {(const void*)k_shade<true>, (const void*)k_trace_shadow<true>, (const void*)k_shade<false>,
                                                                      (const void*)k_trace_shadow<false>};
 // level1 = the <true> build (rays derived from their index: no ray records, and only it may have fixed shadow slots); the hits [c0, c1) of
@@ -436,21 +460,40 @@ static int launch_shade(FrameRun& f, bool level1, const DRayQueue& qin, const ui
         (s->data.n_enabled_lights > 0 && (!q.SQ.s0 || !q.SQ.s1 || !q.SQ.s2)) || (g.fixed && (!level1 || !q.valid)) || c1 <= c0 || c1 > 0xffffffffull ||
         g.segcap > 0xffffffffull || g.sq_cap > 0xffffffffull || max_wg == 0)
         return fail(RR_ERR_DEVICE, "internal: shade launch of hits %llu .. %llu with a NULL or out-of-range argument", (unsigned long long)c0, (unsigned long long)c1);
+    // a split frame's level 1 (serial loop only: the queue starts at the handle's, where sq_s3 starts too); its deeper levels add nothing to the planes
+    const bool split = level1 && f.diffuse != nullptr;
+    if (split && ((s->data.n_enabled_lights > 0 && !f.sq_s3) || q.SQ.s0 != f.SQ.s0))
+        return fail(RR_ERR_DEVICE, "internal: split shade launch without its queue array, or in a stage buffer");
     ScopedTimer t(s, st, TK_SHADE, level1);
-    hipLaunchKernelGGL((level1 ? k_shade<true> : k_shade<false>), dim3((uint32_t)std::min<uint64_t>(g.groups, max_wg)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(),
-                       f.slot_xy, f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, q.SQ, q.counts, (uint32_t)g.segcap, q.valid, (uint32_t)g.sq_cap, f.acc,
-                       s->frame.counters.as<unsigned long long>());
+    // ONE launch for every build: `extra` is empty, or the two pointers only the SPLIT build takes behind the arguments all builds share
+    const auto launch = [&](auto... extra) {
+        constexpr bool SP = sizeof...(extra) != 0;
+        hipLaunchKernelGGL((pick_build<SP>(k_shade<true, SP, decltype(extra)...>, level1 ? k_shade<true> : k_shade<false>)), dim3((uint32_t)std::min<uint64_t>(g.groups, max_wg)),
+                           dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(), f.slot_xy, f.pr, qin, count, (uint32_t)c0, (uint32_t)c1, qout, child_count, q.SQ, q.counts,
+                           (uint32_t)g.segcap, q.valid, (uint32_t)g.sq_cap, f.acc, s->frame.counters.as<unsigned long long>(), extra...);
+    };
+    if (split) launch(f.diffuse, f.sq_s3);
+    else launch();
     HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 // (the timer's level-1 flag is by kernel BUILD: level 1 of a scene without fixed shadow slots runs k_trace_shadow<false>)
-static int launch_shadow(FrameRun& f, const ShadeChunk& g, const ChunkShadow& q, uint64_t max_wg, hipStream_t st) {
+// split: the launch behind k_shade<true, true> (level 1 of a split frame)
+static int launch_shadow(FrameRun& f, const ShadeChunk& g, const ChunkShadow& q, uint64_t max_wg, hipStream_t st, bool split = false) {
+    if (split && (!f.diffuse || !f.sq_s3 || q.SQ.s0 != f.SQ.s0)) return fail(RR_ERR_DEVICE, "internal: split shadow launch without its planes or queue array");
     if (!q.counts || !q.head || !f.acc.rgb || !f.acc.flags || !q.SQ.s0 || !q.SQ.s1 || !q.SQ.s2 || (g.fixed && !q.valid) || g.segcap > 0xffffffffull ||
         g.sq_packets > 0xffffffffull || g.shadow_wg == 0 || max_wg == 0)
         return fail(RR_ERR_DEVICE, "internal: shadow launch of %llu workgroups with a NULL or out-of-range argument", (unsigned long long)g.shadow_wg);
     ScopedTimer t(f.s, st, TK_SHADOW, g.fixed);
-    hipLaunchKernelGGL((g.fixed ? k_trace_shadow<true> : k_trace_shadow<false>), dim3((uint32_t)std::min<uint64_t>(g.shadow_wg, max_wg)), dim3(RR_BLOCK), 0, st, f.s->data.view, q.SQ,
-                       q.counts, (uint32_t)g.segcap, q.valid, (uint32_t)g.sq_packets, q.head, f.acc);
+    const auto launch = [&](auto... extra) { // (as in launch_shade: empty, or the SPLIT builds' two pointers)
+        constexpr bool SP = sizeof...(extra) != 0;
+        hipLaunchKernelGGL((pick_build<SP>(g.fixed ? k_trace_shadow<true, SP, decltype(extra)...> : k_trace_shadow<false, SP, decltype(extra)...>,
+                                           g.fixed ? k_trace_shadow<true> : k_trace_shadow<false>)),
+                           dim3((uint32_t)std::min<uint64_t>(g.shadow_wg, max_wg)), dim3(RR_BLOCK), 0, st, f.s->data.view, q.SQ, q.counts, (uint32_t)g.segcap, q.valid,
+                           (uint32_t)g.sq_packets, q.head, f.acc, extra...);
+    };
+    if (split) launch(f.diffuse, (const float4*)f.sq_s3);
+    else launch();
     HIP_TRY(hipGetLastError());
     return RR_OK;
 }
@@ -600,7 +643,8 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
     // light and lane for the validity words; more lights take the dense queue of the deeper levels, which has no such limit
     const bool sq_fixed = l1 && s->data.view.n_items >= RR_BEAM_MIN_ITEMS && s->data.view.n_items <= RR_BEAM_MAX_ITEMS && L <= RR_FIXED_SLOT_LIGHTS;
     // ... and with at least one light and two stages: shade and shadow launches side by side on two streams (per slice of the level)
-    const auto staged = [&](uint64_t hits) { return !f.level1_only && level1_stages_wanted(s) && sq_fixed && L >= 1 && level1_stages(s, hits).overlapped(); };
+    // (a split frame leaves the staged schedule out and runs the serial loop: integer adds commute, so its bits do not depend on the schedule)
+    const auto staged = [&](uint64_t hits) { return !f.level1_only && !f.diffuse && level1_stages_wanted(s) && sq_fixed && L >= 1 && level1_stages(s, hits).overlapped(); };
     // ... and where the level is ONE slice, its closest hits stage by stage on a third stream; every other level in one launch, here
     const bool closest_staged = slice == n && staged(n);
     if (!closest_staged) {
@@ -635,7 +679,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             // BEFORE that chunk's shadow kernel, so the host learns it (and enqueues the next level) while the shadow
             // rays are still being traced, instead of leaving the device idle for a host round trip per level.
             if (spawns && c1 == s1) RR_TRY(read_back_level_size(f, child_count));
-            if (L) RR_TRY(launch_shadow(f, g, q, (uint64_t)f.shadow_grid, st));
+            if (L) RR_TRY(launch_shadow(f, g, q, (uint64_t)f.shadow_grid, st, l1 && f.diffuse != nullptr));
         }
         if (!spawns) continue;
         HIP_TRY(hipEventSynchronize(s->frame.count_ready));
@@ -656,6 +700,10 @@ static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& i
     case FrameEnd::NONE: break;
     case FrameEnd::ALBEDO: hipLaunchKernelGGL(k_resolve_albedo, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (uint32_t*)io.albedo); break;
     case FrameEnd::RECORD_PARTS: hipLaunchKernelGGL(k_resolve_pixel_parts, grid, block, 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, by_pixel, (float4*)io.radiance, (float4*)io.parts); break;
+    case FrameEnd::RECORD_SPLIT:
+        hipLaunchKernelGGL(k_resolve_pixel_split, grid, block, 0, f.st, fr, f.slot_xy, f.acc, (const long long*)f.diffuse, io.lg_parts, by_pixel, (float4*)io.radiance,
+                           (float4*)io.parts, io.diffuse, io.diffuse_parts);
+        break;
     case FrameEnd::RECORDS: hipLaunchKernelGGL(k_resolve_pixels, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (float4*)io.radiance, (uint32_t*)io.rgba8); break;
     case FrameEnd::REGION_BYTES:
         hipLaunchKernelGGL(k_resolve, grid, block, 0, f.st, fr, f.s->frame.region_xy.as<uint32_t>(), f.s->frame.trace_order.as<uint32_t>(), f.acc, io.out->rgba8, io.out->normal,
@@ -744,7 +792,8 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     const FrameEndPlan end = frame_end_plan(io);
     const uint32_t R = end.level1_only ? 0u : cfg->max_recursion;
     DAccum acc;
-    RR_TRY(reset_accumulators(s, npix, end, st, &acc, io.resident));
+    long long* diffuse = nullptr; // (a split frame's planes)
+    RR_TRY(reset_accumulators(s, npix, end, st, &acc, io.resident, &diffuse));
     // The frame's plan (rr_frame_plan.h), and its level-1 hit records, ray arena and shadow queue.  With parts the plan sees K x the slots
     // and 1 / K of the samples (a sample group must divide THIS range: plan_frame); the frame constants keep the frame's S.
     uint64_t budget = 0;
@@ -754,10 +803,11 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     HIP_TRY(s->frame.hit1.reserve(plan.B * 16));
     if (!end.level1_only) { // the shadow queue serves the serial loop and, where level 1 runs in stages, the stage buffers (their layout is the same for every batch)
         const Level1Stages sp = level1_stages(s, plan.B);
-        RR_TRY(grow_ray_queues(s, plan.M, std::max<uint64_t>(plan.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need));
+        RR_TRY(grow_ray_queues(s, plan.M, std::max<uint64_t>(plan.sq_need, level1_stages_wanted(s) ? sp.sq_need : 0ull), sp.valid_need, end.split));
     }
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f = make_frame_run(s, st, plan, R, end.level1_only, acc, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, slot_xy, cancel);
+    if (end.split) { f.diffuse = diffuse; f.sq_s3 = s->frame.sq3.as<float4>(); }
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
     RR_TRY(run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix));
     launch_resolve(f, fr, io);

@@ -67,6 +67,8 @@ struct FrameState {
     uint32_t arena_factor = 2; // arena rays per primary ray of a batch; doubled after a frame that had to slice levels
     DevBuf sq[3];
     size_t sq_cap = 0;
+    DevBuf sq3;         // rr_render_pixel_split: the diffuse part of every shadow ray's term, 16 B per ray of the queue; reserved by such a frame only
+    DevBuf acc_diffuse; // ... and its three diffuse planes, 24 B per slot
     DevBuf sq_valid; // one 64-bit word per (enabled light, 64 shadow slots): which lanes hold a ray
     DevBuf acc_rgb, acc_normal, acc_depth, acc_id, acc_flags, shade_const;
     DevBuf region_xy, trace_order, pool, counters; // region_xy: pixel of each accumulator slot; trace_order: its output index
@@ -144,6 +146,7 @@ struct AdaptiveState {
 // rr_api_denoise.h.  (rr_accumulate_records, rr_api_temporal.h, keeps nothing.)
 struct DenoiseState {
     DevBuf work[2], guide, meta;
+    DevBuf split[4]; // rr_denoise_split_records: the rest and direct record sets (32 B per pixel each) and their halves (64 B each)
 };
 
 // ---- rr_motion_records (rr_api_motion.h): grown on demand, never shrunk.  table: the call's table on the device, 112 B per entry of the

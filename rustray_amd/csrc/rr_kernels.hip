@@ -312,13 +312,27 @@ RR_DEV uint32_t wave_alloc(uint32_t* counter, bool want, uint32_t lane) {
 // ---------------------------------------------------------------------------
 // kernel 3: shade one depth level (reference src/raytracing.rs:734-995)
 // ---------------------------------------------------------------------------
-template <bool PRIMARY>
+// SPLIT (rr_render_pixel_split, level 1 only): next to every light term of a depth-1 hit its DIFFUSE part -- the same product with the
+// specular summand left out -- goes to three planes of its own (`diffuse`, laid out as acc.rgb: channel k at diffuse + k * acc.n) through
+// the same fix_add / accum_merged, and for a receiver that takes shadows into a fourth queue array (sq_s3, next to sq.s2) that
+// k_trace_shadow<*, true> scales by the ray's factor.  The two pointers are the arguments `split` of the SPLIT builds ALONE (long long*
+// diffuse, float4* sq_s3): the other builds take no argument more than they took, so their kernel-argument segment and with it their code
+// are what they were.
+RR_DEV long long* split_planes() { return nullptr; }
+template <class Q> RR_DEV long long* split_planes(long long* planes, Q*) { return planes; }
+RR_DEV float4* split_queue() { return nullptr; }
+template <class Q> RR_DEV Q* split_queue(long long*, Q* queue) { return queue; }
+template <bool PRIMARY, bool SPLIT = false, class... Split>
 __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShadeConst* __restrict__ kc, const uint32_t* __restrict__ slot_xy, DPrimary pr,
                                                     DRayQueue qin, const uint32_t* __restrict__ qin_count,
                                                     uint32_t chunk_begin, uint32_t chunk_end,
                                                     DRayQueue qout, uint32_t* qout_count,
                                                     DShadowQueue sq, uint32_t* sq_counts, uint32_t sq_segcap, unsigned long long* __restrict__ sq_valid, uint32_t sq_cap,
-                                                    DAccum acc, unsigned long long* counters) {
+                                                    DAccum acc, unsigned long long* counters, Split... split) {
+    static_assert(sizeof...(Split) == (SPLIT ? 2 : 0), "the SPLIT builds take (long long* diffuse, float4* sq_s3), the others nothing");
+    DAccum dacc = acc; // SPLIT: the diffuse planes behind the colour planes' own interface (fix_add, accum_merged)
+    [[maybe_unused]] float4* const sq_s3 = split_queue(split...);
+    if constexpr (SPLIT) dacc.rgb = split_planes(split...);
     // The scene view and the frame constants (90 dwords) are read from a small device record where they are needed
     // instead of arriving as kernel arguments: as arguments they were all live in SGPRs across the whole loop and the
     // kernel spilled 117 of them into VGPR lanes.
@@ -361,6 +375,8 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         uint32_t* const sq_count = sq_counts + shard * RR_SQ_STRIDE;
         const uint32_t sq_base = shard * sq_segcap;
         int sum_r = 0, sum_g = 0, sum_b = 0; // this hit's direct adds (32-bit fixed point, fix_add), merged with its neighbours' at the end
+        [[maybe_unused]] int dif_r = 0, dif_g = 0, dif_b = 0; // SPLIT: the same for the diffuse parts of a depth-1 hit's unshadowed light terms
+        [[maybe_unused]] uint32_t dif_pix = 0xffffffffu;
         // children of this hit (emitted after the hit is shaded, by all waves of the workgroup together)
         bool spawn_refl = false, spawn_refr = false;
         float4 c1_r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1_r1 = c1_r0, c2_r0 = c1_r0, c2_r1 = c1_r0;
@@ -528,6 +544,14 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             const float cg = ((L.color[1] * (specular_color.y * light_power + base_color.y * dot_light)) * intensity) * w_light;
             const float cb = ((L.color[2] * (specular_color.z * light_power + base_color.z * dot_light)) * intensity) * w_light;
             const bool nonzero = (cr != 0.0f) || (cg != 0.0f) || (cb != 0.0f);
+            [[maybe_unused]] float dr = 0.0f, dg = 0.0f, db = 0.0f; // SPLIT: the term without its specular summand, for the hits of depth 1
+            if constexpr (SPLIT) {
+                if (depth == 1u) {
+                    dr = ((L.color[0] * (base_color.x * dot_light)) * intensity) * w_light;
+                    dg = ((L.color[1] * (base_color.y * dot_light)) * intensity) * w_light;
+                    db = ((L.color[2] * (base_color.z * dot_light)) * intensity) * w_light;
+                }
+            }
             // A light term that is exactly zero stays zero whatever the shadow query says, so its ray is not traced -- unless
             // an occluder with an alpha map exists AND this receiver's uv can be non-finite: the reference samples that map at the
             // RECEIVER's uv of the OCCLUDER's hit point (:905), which for a sphere receiver is acos of a value beyond 1 = NaN (for
@@ -539,6 +563,13 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
                 nf |= nonfinite_flags(cr, cg, cb);
                 fix_add(sum_r, cr, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb, pix); fix_add(sum_g, cg, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + acc.n, pix);
                 fix_add(sum_b, cb, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + 2ull * acc.n, pix);
+                if constexpr (SPLIT) {
+                    if (depth == 1u) {
+                        dif_pix = pix;
+                        fix_add(dif_r, dr, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb, pix); fix_add(dif_g, dg, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + dacc.n, pix);
+                        fix_add(dif_b, db, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + 2ull * dacc.n, pix);
+                    }
+                }
             }
             // Hundreds of unshadowed lights: the 32-bit sums are flushed every 32 enabled lights, whether or not THIS light added a term
             // (inside the branch above a light 31 or 63 with a zero term skipped its flush, and 96 terms can pass 2^31).
@@ -547,6 +578,12 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
                 if (sum_g) atomicAdd((unsigned long long*)acc.rgb + acc.n + pix, (unsigned long long)(long long)sum_g);
                 if (sum_b) atomicAdd((unsigned long long*)acc.rgb + 2ull * acc.n + pix, (unsigned long long)(long long)sum_b);
                 sum_r = sum_g = sum_b = 0;
+                if constexpr (SPLIT) {
+                    if (dif_r) atomicAdd((unsigned long long*)dacc.rgb + pix, (unsigned long long)(long long)dif_r);
+                    if (dif_g) atomicAdd((unsigned long long*)dacc.rgb + dacc.n + pix, (unsigned long long)(long long)dif_g);
+                    if (dif_b) atomicAdd((unsigned long long*)dacc.rgb + 2ull * dacc.n + pix, (unsigned long long)(long long)dif_b);
+                    dif_r = dif_g = dif_b = 0;
+                }
             }
             const uint32_t si = sq_fixed ? lk * sq_cap + sq_slot : sq_base + wave_alloc(sq_count, want_shadow, lane);
             if (want_shadow) {
@@ -557,6 +594,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
                 sq.s0[si] = make_float4(so.x, so.y, so.z, limit);
                 sq.s1[si] = make_float4(sd.x, sd.y, sd.z, __uint_as_float((uint32_t)item_idx | (depth << 27)));
                 sq.s2[si] = make_float4(cr, cg, cb, __uint_as_float(pix));
+                if constexpr (SPLIT) sq_s3[si] = make_float4(dr, dg, db, 0.0f); // (zeros for a hit that is not of depth 1)
                 n_shadow++;
             }
         }
@@ -589,6 +627,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         }
         if (nf) atomicOr(&acc.flags[pix_of_nf], nf); // rare: a non-finite term
         accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
+        if constexpr (SPLIT) accum_merged(dacc, dif_pix, dif_r, dif_g, dif_b);
         if ((acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull) {
             if (__ballot(aux_d == RR_DEPTH_WIDE) != 0ull) { // hits beyond 512 units: their depth terms in 64 bits, merged per pixel
                 long long wide = 0ll;
@@ -740,10 +779,16 @@ __global__ __launch_bounds__(RR_BLOCK) void k_item_spans(const DItem* __restrict
 // FIXED (level 1): packet p = the shadow rays of hit packet (p % packets per light) towards enabled light (p / packets per
 // light), slots p * 64 .. p * 64 + 63, lanes by sq_valid[p]; n_packets given.  Otherwise the dense sharded queue of the
 // deeper levels (k_shade), n_packets from the shard counts.
-template <bool FIXED>
+// SPLIT (rr_render_pixel_split, level 1): sq_s3[i] is the diffuse part of ray i's term (k_shade<true, true>); it is scaled by the ray's
+// factor and summed in the planes `diffuse` as the term itself is in acc.rgb, in the same packet pass.
+template <bool FIXED, bool SPLIT = false, class... Split>
 __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSceneView sc, DShadowQueue sq, const uint32_t* __restrict__ sq_counts, uint32_t sq_segcap,
                                                            const unsigned long long* __restrict__ sq_valid, uint32_t n_fixed_packets,
-                                                           uint32_t* head, DAccum acc) {
+                                                           uint32_t* head, DAccum acc, Split... split) {
+    static_assert(sizeof...(Split) == (SPLIT ? 2 : 0), "the SPLIT builds take (long long* diffuse, const float4* sq_s3), the others nothing");
+    DAccum dacc = acc;
+    [[maybe_unused]] const float4* const sq_s3 = split_queue(split...);
+    if constexpr (SPLIT) dacc.rgb = split_planes(split...);
     __shared__ int s_stack[RR_STACK_DEPTH * RR_BLOCK];
     __shared__ uint32_t s_prefix[RR_SQ_SHARDS + 1];
     RR_UTIL_KIND(2u)
@@ -771,6 +816,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
         if (valid == 0ull) continue;
         {
         int sum_r = 0, sum_g = 0, sum_b = 0;
+        [[maybe_unused]] int dif_r = 0, dif_g = 0, dif_b = 0;
         uint32_t sum_pix = 0xffffffffu;
         const bool live = ((valid >> lane) & 1ull) != 0ull;
         {
@@ -784,6 +830,8 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
             }
             const float4 s0 = sq.s0[i];
             const float4 s1 = sq.s1[i], s2 = sq.s2[i];
+            [[maybe_unused]] float4 s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if constexpr (SPLIT) s3 = sq_s3[i];
             const uint32_t rcv_item = __float_as_uint(s1.w) & 0x07ffffffu, rcv_depth = __float_as_uint(s1.w) >> 27;
             const f3 o = mk3(s0.x, s0.y, s0.z), d = mk3(s1.x, s1.y, s1.z);
             ShadowSel sel;
@@ -814,9 +862,14 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
             fix_add(sum_r, vr_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb, sum_pix); fix_add(sum_g, vg_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + acc.n, sum_pix);
             fix_add(sum_b, vb_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + 2ull * acc.n, sum_pix);
             if (nf) atomicOr(&acc.flags[sum_pix], nf);
+            if constexpr (SPLIT) {
+                fix_add(dif_r, s3.x * factor, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb, sum_pix); fix_add(dif_g, s3.y * factor, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + dacc.n, sum_pix);
+                fix_add(dif_b, s3.z * factor, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + 2ull * dacc.n, sum_pix);
+            }
             }
         }
         accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
+        if constexpr (SPLIT) accum_merged(dacc, sum_pix, dif_r, dif_g, dif_b);
         }
     }
 }
@@ -1135,6 +1188,60 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_parts(DFrame fr, con
     const float n = (float)fr.samples;
 #pragma unroll
     for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n);
+    const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
+    out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
+    out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
+}
+
+// 5k': the end of rr_render_pixel_split: records and part records exactly as 5k writes them (the same loads, shuffles and resolve functions),
+// and next to them the diffuse planes (`diffuse`: three planes of acc.n words, laid out as acc.rgb) resolved the same way, as floats:
+// dif_out[3 o + c] over all S samples, dif_parts[3 (o K + h) + c] over the part's S / K.  The flags are the colour's: a channel whose record
+// colour is not finite holds the record's value here too.  lg_parts == 0 (no halves wanted): one slot per pixel, `parts` and `dif_parts`
+// are NULL and not written, and the record has k_resolve_pixels' bytes.
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_split(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, const long long* __restrict__ diffuse,
+                                                                  uint32_t lg_parts, uint32_t from_xy, float4* __restrict__ out, float4* __restrict__ parts,
+                                                                  float* __restrict__ dif_out, float* __restrict__ dif_parts) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
+    const bool live = p < fr.n_region_pixels;                 // (n_region_pixels: the slots, n_pixels * K)
+    const uint32_t K = 1u << lg_parts;
+    long long w[10] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll}; // rgb, normal, depth, diffuse rgb
+    uint32_t nf = 0u, id = 0u;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            w[k] = acc.rgb[(unsigned long long)k * acc.n + p]; w[3 + k] = acc.normal[(unsigned long long)k * acc.n + p];
+            w[7 + k] = diffuse[(unsigned long long)k * acc.n + p];
+        }
+        w[6] = acc.depth[p];
+        nf = acc.flags[p];
+        id = acc.object_id[p];
+    }
+    const float n_part = (float)(fr.samples >> lg_parts);
+    float c[3], dc[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { c[k] = resolve_color_sum(w[k], nf, k, n_part); dc[k] = resolve_color_sum(w[7 + k], nf, k, n_part); }
+    const f3 nn = resolve_normal_sum(w[3], w[4], w[5], nf, n_part);
+    const float depth = resolve_depth_sum(w[6], nf, n_part);
+    for (uint32_t off = 1u; off < K; off <<= 1) { // (wave-uniform trip count)
+#pragma unroll
+        for (int k = 0; k < 10; k++) w[k] += shfl_xor_ll(w[k], (int)off);
+        nf |= (uint32_t)__shfl_xor((int)nf, (int)off);
+    }
+    id = (uint32_t)__shfl((int)id, (int)((threadIdx.x & (RR_WAVE - 1)) | (K - 1u))); // the group's last slot holds sample S - 1
+    if (!live) return;
+    uint32_t o = p >> lg_parts; // the pixel's record index; its parts follow each other at o * K
+    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
+    if (parts) {
+        const unsigned long long q = ((unsigned long long)o << lg_parts) + (p & (K - 1u));
+        parts[2ull * q] = make_float4(c[0], c[1], c[2], depth);
+        parts[2ull * q + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(id));
+#pragma unroll
+        for (int k = 0; k < 3; k++) dif_parts[3ull * q + k] = dc[k];
+    }
+    if ((p & (K - 1u)) != 0u) return;
+    const float n = (float)fr.samples;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { c[k] = resolve_color_sum(w[k], nf, k, n); dif_out[3ull * o + k] = resolve_color_sum(w[7 + k], nf, k, n); }
     const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
     out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
     out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
@@ -2036,6 +2143,49 @@ __global__ __launch_bounds__(RR_BLOCK) void k_denoise_finish(const float4* recor
     out[2ull * o] = make_float4(c[0], c[1], c[2], r0.w);
     out[2ull * o + 1] = r1;
     if (variance_out) variance_out[o] = w.w;
+}
+
+// 7d', 7d'': the two streaming ends of rr_denoise_split_records (rustray_amd/denoise.py: atrous_denoise_split), one pixel per lane, grid-stride.
+// 7d': the two record sets the filter runs on.  Both share depth, normal and id with `records`; `rest` holds colour - diffuse (one binary32
+// subtraction per channel), `direct` holds diffuse.  halves / dif_halves (both or neither) are split the same way, part q = 2 o + h.
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_split_sets(const float4* __restrict__ records, const float4* __restrict__ halves, const float* __restrict__ diffuse,
+                                                                 const float* __restrict__ dif_halves, uint32_t n, float4* __restrict__ rest, float4* __restrict__ direct,
+                                                                 float4* __restrict__ rest_halves, float4* __restrict__ direct_halves) {
+    for (uint32_t o = blockIdx.x * RR_BLOCK + threadIdx.x; o < n; o += gridDim.x * RR_BLOCK) {
+        const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+        const float d0 = diffuse[3ull * o], d1 = diffuse[3ull * o + 1], d2 = diffuse[3ull * o + 2];
+        rest[2ull * o] = make_float4(r0.x - d0, r0.y - d1, r0.z - d2, r0.w);
+        rest[2ull * o + 1] = r1;
+        direct[2ull * o] = make_float4(d0, d1, d2, r0.w);
+        direct[2ull * o + 1] = r1;
+        if (halves) {
+#pragma unroll
+            for (uint32_t h = 0; h < 2u; h++) {
+                const unsigned long long q = 2ull * o + h;
+                const float4 h0 = halves[2ull * q], h1 = halves[2ull * q + 1];
+                const float e0 = dif_halves[3ull * q], e1 = dif_halves[3ull * q + 1], e2 = dif_halves[3ull * q + 2];
+                rest_halves[2ull * q] = make_float4(h0.x - e0, h0.y - e1, h0.z - e2, h0.w);
+                rest_halves[2ull * q + 1] = h1;
+                direct_halves[2ull * q] = make_float4(e0, e1, e2, h0.w);
+                direct_halves[2ull * q + 1] = h1;
+            }
+        }
+    }
+}
+// 7d'': out = the record with the sum of the two filtered colours, one binary32 add per channel; a pixel whose record colour is not finite
+// keeps the record's colour.  out may be `records` itself: a lane reads and writes its own pixel only.
+__global__ __launch_bounds__(RR_BLOCK) void k_denoise_split_sum(const float4* records, const float4* __restrict__ rest, const float4* __restrict__ direct, uint32_t n,
+                                                                float4* out) {
+    for (uint32_t o = blockIdx.x * RR_BLOCK + threadIdx.x; o < n; o += gridDim.x * RR_BLOCK) {
+        const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+        float4 c = r0;
+        if (denoise_is_finite(r0.x) && denoise_is_finite(r0.y) && denoise_is_finite(r0.z)) {
+            const float4 a = rest[2ull * o], b = direct[2ull * o];
+            c.x = a.x + b.x; c.y = a.y + b.y; c.z = a.z + b.z;
+        }
+        out[2ull * o] = c;
+        out[2ull * o + 1] = r1;
+    }
 }
 
 // 7e: temporal reprojection (rr_accumulate_records; rr_temporal.h has the arithmetic, in the order the header states;

@@ -157,6 +157,37 @@ def atrous_denoise(records, halves, albedo, width: int, height: int, params: Den
     return dict(records=out.reshape(H * W, 8), variance=var.reshape(H * W).copy())
 
 
+def atrous_denoise_split(records, halves, diffuse, diffuse_halves, albedo, width: int, height: int, params: DenoiseParams | None = None) -> dict:
+    """The filter of rr_denoise_split_records: the albedo is applied to the direct diffuse part of the colour alone.  records, halves, albedo
+    as atrous_denoise takes them; diffuse: (width * height, 3) float32 (render_pixel_split), diffuse_halves: (width * height, 2, 3) or None,
+    exactly when halves is.  Two record sets share depth, normal and id with `records`: `rest` with the colour records.color - diffuse (one
+    binary32 subtraction) and `direct` with the colour diffuse; the halves are split the same way.  The colour returned is
+    atrous_denoise(rest, rest halves, None).color + atrous_denoise(direct, direct halves, albedo).color, one binary32 add; a pixel whose
+    record colour is not finite keeps the record's colour.  Returns dict(records (n, 8) float32)."""
+    n = int(width) * int(height)
+    rec = np.ascontiguousarray(records, F).reshape(n, 8)
+    dif = np.ascontiguousarray(diffuse, F).reshape(n, 3)
+    if (halves is None) != (diffuse_halves is None):
+        raise ValueError("halves and diffuse_halves are given together or not at all")
+    with np.errstate(all="ignore"):
+        rest, direct = rec.copy(), rec.copy()
+        rest[:, 0:3] = rec[:, 0:3] - dif
+        direct[:, 0:3] = dif
+        rest_h = direct_h = None
+        if halves is not None:
+            hv = np.ascontiguousarray(halves, F).reshape(n, 2, 8)
+            dh = np.ascontiguousarray(diffuse_halves, F).reshape(n, 2, 3)
+            rest_h, direct_h = hv.copy(), hv.copy()
+            rest_h[:, :, 0:3] = hv[:, :, 0:3] - dh
+            direct_h[:, :, 0:3] = dh
+        a = atrous_denoise(rest, rest_h, None, width, height, params)["records"]
+        b = atrous_denoise(direct, direct_h, albedo, width, height, params)["records"]
+        out = rec.copy()
+        fin = np.isfinite(rec[:, 0:3]).all(-1)
+        out[:, 0:3] = np.where(fin[:, None], a[:, 0:3] + b[:, 0:3], rec[:, 0:3])
+    return dict(records=out)
+
+
 def frame_bytes_linear(color) -> np.ndarray:
     """The frame's bytes of (n, 3) linear colours without the gamma curve: (uint8)(fminf(c, 1) * 255) in float32, alpha 255 (what
     rr_render_pixels documents for gamma_correction = 0; NaN -> 0 as the device's conversion gives it)."""

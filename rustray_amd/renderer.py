@@ -175,6 +175,20 @@ class Raytracing:
         render_pixels plus parts = dict(color (n, K, 3), depth (n, K), normal (n, K, 3), object_id (n, K))."""
         return self.device_scene.render_pixel_parts(self.camera.c_struct(), self.config, pixels=pixels, n_parts=n_parts, sample_xy=sample_xy)
 
+    def render_pixel_split(self, pixels=None, halves: bool = True, sample_xy=None) -> dict:
+        """render_pixel_parts at n_parts = 2 (render_pixels with halves=False) and, as a sum of its own, the frame's direct diffuse light of the
+        primary hits (rr_render_pixel_split): the dict of render_pixel_parts plus diffuse (n, 3) and, with halves, diffuse_halves (n, 2, 3).
+        color - diffuse is everything else: ambient and fog, highlights, what mirrors and glass show."""
+        return self.device_scene.render_pixel_split(self.camera.c_struct(), self.config, pixels=pixels, halves=halves, sample_xy=sample_xy)
+
+    def denoise_split(self, records, diffuse, halves=None, diffuse_halves=None, albedo=None, params=None, rgba8: bool = False) -> dict:
+        """rr_denoise_split_records over a frame of this camera: denoise() with the albedo applied to `diffuse` (n, 3), the direct diffuse part
+        of the colour (render_pixel_split), alone; `diffuse_halves` (n, 2, 3) exactly when `halves` is given.  Returns dict(records (n, 8),
+        color, depth, normal, object_id [, rgba]).  The result is, bit for bit, denoise.atrous_denoise_split of the same arrays."""
+        cam = self.camera.c_struct()
+        res = self.device_scene.denoise_split(int(cam.width), int(cam.height), records, diffuse, halves, diffuse_halves, albedo, params, rgba8=rgba8)
+        return dict(res, **capi._records(res["records"]))
+
     def denoise(self, records, halves=None, albedo=None, params=None, rgba8: bool = False) -> dict:
         """rr_denoise_records over a frame of this camera: `records` (n, 8) float32 rr_radiance records in row-major order (what
         render_pixels gives, as records), `halves` (n, 2, 8) or None (render_pixel_parts at n_parts = 2), `albedo` (n, 3) or None, `params`
@@ -216,13 +230,21 @@ class Raytracing:
         """The whole frame at `samples` (default: the config's; even) in two halves, followed by the filter guided by their variance: one
         rr_render_pixel_parts call at n_parts = 2 and one rr_denoise_records call.  albedo=True: one rr_surface_pixels call between them
         makes this camera's albedo and the filter runs on albedo-demodulated colour; the result then holds it as `albedo`.  albedo="mean":
-        one rr_albedo_pixels call with the frame's config and table stands in its place (mean_albedo).  Returns the
+        one rr_albedo_pixels call with the frame's config and table stands in its place (mean_albedo).  albedo="diffuse": the frame comes
+        from rr_render_pixel_split, the albedo is the mean one, and rr_denoise_split_records demodulates the direct diffuse part of the colour
+        alone; the result then holds `diffuse` and `diffuse_halves` too, and no variance.  Returns the
         dict of denoise() plus `noisy`, the records before the filter.  render_denoised_torch is the same on the device, with no host trip."""
         cam = self.camera.c_struct()
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
             cfg.samples = samples
         _check_albedo_mode(albedo)
+        if _diffuse_mode(albedo):
+            base = self.device_scene.render_pixel_split(cam, cfg, sample_xy=sample_xy)
+            records, halves = _pack_records(base), _pack_records(base["parts"])
+            guide = self.device_scene.albedo_pixels(cam, cfg, sample_xy=sample_xy)
+            res = self.denoise_split(records, base["diffuse"], halves, base["diffuse_halves"], guide, params, rgba8=rgba8)
+            return dict(res, noisy=records, albedo=guide, diffuse=base["diffuse"], diffuse_halves=base["diffuse_halves"])
         base = self.device_scene.render_pixel_parts(cam, cfg, n_parts=2, sample_xy=sample_xy)
         records = _pack_records(base)
         halves = _pack_records(base["parts"])
@@ -245,8 +267,9 @@ class Raytracing:
         call on the same stream); a change of the item count or of any item's id resets the state, and so does a history from a call
         without track_items.  albedo=True: one more call on the same stream (rr_surface_pixels_device) makes this camera's albedo for the
         filter; the accumulation is not changed, it blends un-demodulated colour.  albedo="mean": rr_albedo_pixels_device with the frame's
-        config and table in its place."""
+        config and table in its place.  albedo="diffuse" raises ValueError: no diffuse part is accumulated over time."""
         from .temporal import previous_view
+        _check_albedo_mode(albedo, temporal=True)
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
             cfg.samples = samples
@@ -842,14 +865,22 @@ def surface_pixels_torch(device_scene: capi.DeviceScene, cam, pixels=None, recor
     return out
 
 
-def _check_albedo_mode(albedo) -> None:
-    """The `albedo` argument of the pipelines: False, True (the pixel-centre albedo, rr_surface_pixels) or "mean" (rr_albedo_pixels)."""
-    if isinstance(albedo, str) and albedo != "mean":
-        raise ValueError(f'albedo must be False, True or "mean", not {albedo!r}')
+def _check_albedo_mode(albedo, temporal: bool = False) -> None:
+    """The `albedo` argument of the pipelines: False, True (the pixel-centre albedo, rr_surface_pixels), "mean" (rr_albedo_pixels) or, in the
+    single-frame pipelines only, "diffuse" (the mean albedo applied to the direct diffuse part alone: rr_render_pixel_split and
+    rr_denoise_split_records)."""
+    if isinstance(albedo, str) and albedo not in ("mean", "diffuse"):
+        raise ValueError(f'albedo must be False, True, "mean" or "diffuse", not {albedo!r}')
+    if temporal and _diffuse_mode(albedo):
+        raise ValueError('albedo="diffuse" is for the single-frame pipelines: the temporal ones accumulate no diffuse part')
 
 
 def _mean_mode(albedo) -> bool:
     return isinstance(albedo, str) and albedo == "mean"
+
+
+def _diffuse_mode(albedo) -> bool:
+    return isinstance(albedo, str) and albedo == "diffuse"
 
 
 def albedo_pixels_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, sample_xy=None):
@@ -967,6 +998,33 @@ def render_pixel_parts_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config
     return dict(_record_views(rec), part_records=parts.pop("records"), parts=parts)
 
 
+def render_pixel_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, pixels=None, halves: bool = True, sample_xy=None) -> dict:
+    """rr_render_pixel_split_device on torch's current stream: `pixels` as render_pixels_torch takes them.  Returns torch tensors, without a host
+    copy and without a synchronisation of the results: the dict of render_pixel_parts_torch at n_parts = 2 (that of render_pixels_torch with
+    halves=False) plus diffuse (n, 3) float32 and, with halves, diffuse_halves (n, 2, 3)."""
+    import torch
+    n, xy = int(cam.width) * int(cam.height), None
+    if pixels is not None:
+        dtype = torch.int32 if not isinstance(pixels, torch.Tensor) or pixels.dtype != getattr(torch, "uint32", None) else pixels.dtype
+        xy = _ray_tensor(device_scene, pixels, "pixels", shape_tail=(), dtype=dtype)
+        n = int(xy.shape[0])
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        rec = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        prec = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if halves else None
+        dif = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        dif_h = torch.empty((n, 2, 3), dtype=torch.float32, device=dev) if halves else None
+        if n:
+            device_scene.render_pixel_split_device(cam, cfg, xy.data_ptr() if xy is not None else None, n, rec.data_ptr(), prec.data_ptr() if halves else None,
+                                                   dif.data_ptr(), dif_h.data_ptr() if halves else None, torch.cuda.current_stream(dev).cuda_stream,
+                                                   sample_xy=sample_xy)
+    out = dict(_record_views(rec), diffuse=dif)
+    if halves:
+        parts = _record_views(prec)
+        out.update(part_records=parts.pop("records"), parts=parts, diffuse_halves=dif_h)
+    return out
+
+
 def _record_views(rec) -> dict:
     """`records`, (..., 8) float32 rr_radiance on the device, and the views of its fields"""
     import torch
@@ -1056,6 +1114,28 @@ def denoise_torch(device_scene: capi.DeviceScene, width: int, height: int, recor
     return res
 
 
+def denoise_split_torch(device_scene: capi.DeviceScene, width: int, height: int, records, diffuse, halves=None, diffuse_halves=None, albedo=None, params=None,
+                        rgba8: bool = False, in_place: bool = False) -> dict:
+    """rr_denoise_split_records_device on torch's current stream of the scene's device: the tensors of denoise_torch plus `diffuse` (n, 3) and
+    `diffuse_halves` (n, 2, 3) or None (exactly when `halves` is).  Returns torch tensors, without a host copy and without a synchronisation:
+    dict(records (n, 8) float32 and its views; on request rgba (n, 4) uint8)."""
+    import torch
+    n = int(width) * int(height)
+    t = _frame_tensors(device_scene, width, height, dict(records=(records, (8,)), halves=(halves, (2, 8)), albedo=(albedo, (3,)), diffuse=(diffuse, (3,)),
+                                                         diffuse_halves=(diffuse_halves, (2, 3))), required=("records", "diffuse"))
+    ptr = lambda k: t[k].data_ptr() if t[k] is not None else None
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        out = t["records"] if in_place else torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        device_scene.denoise_split_device(width, height, ptr("records"), ptr("halves"), ptr("diffuse"), ptr("diffuse_halves"), ptr("albedo"), out.data_ptr(),
+                                          rgba.data_ptr() if rgba8 else None, params, torch.cuda.current_stream(dev).cuda_stream)
+    res = _record_views(out)
+    if rgba8:
+        res["rgba"] = rgba
+    return res
+
+
 def _albedo_guide_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, sample_xy, albedo):
     """The albedo guide of a device pipeline on torch's current stream: None, the pixel-centre albedo (True) or the frame's mean ("mean")."""
     _check_albedo_mode(albedo)
@@ -1071,8 +1151,16 @@ def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, p
     rr_denoise_records_device on the same stream, the second reading what the first wrote without a synchronisation.  albedo=True:
     rr_surface_pixels_device between the two, on the same stream, makes the camera's albedo for the filter (three calls, still no host
     trip); albedo="mean": rr_albedo_pixels_device with the frame's config and table in its place.  Returns the dict of denoise_torch plus
-    noisy (n, 8) and halves (n, 2, 8), the tensors the filter read, and with an albedo albedo (n, 3)."""
+    noisy (n, 8) and halves (n, 2, 8), the tensors the filter read, and with an albedo albedo (n, 3).  albedo="diffuse": three calls on the
+    stream, rr_render_pixel_split_device, rr_albedo_pixels_device (the mean albedo) and rr_denoise_split_records_device, which demodulates the
+    direct diffuse part of the colour alone; the result then holds diffuse (n, 3) and diffuse_halves (n, 2, 3) too, and no variance."""
     _check_albedo_mode(albedo)
+    if _diffuse_mode(albedo):
+        base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)
+        guide = albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
+        res = denoise_split_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["diffuse"], base["part_records"], base["diffuse_halves"], guide,
+                                  params, rgba8=rgba8)
+        return dict(res, noisy=base["records"], halves=base["part_records"], albedo=guide, diffuse=base["diffuse"], diffuse_halves=base["diffuse_halves"])
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
     guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), base["records"], base["part_records"], guide, params, rgba8=rgba8)
@@ -1199,10 +1287,12 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     accumulated_halves (n, 2, 8) and length (n,): what the filter read, which `state` now holds as the history; and motion (n, 3) or None:
     what the accumulation read.  albedo=True: rr_surface_pixels_device on the same stream, one call more, makes the albedo of `cam` for the
     filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it.  albedo="mean":
-    rr_albedo_pixels_device with the frame's config and table in its place."""
+    rr_albedo_pixels_device with the frame's config and table in its place.  albedo="diffuse" raises ValueError: no diffuse part is
+    accumulated over time."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
+    _check_albedo_mode(albedo, temporal=True)
     if moved is not None and motion is not None:
         raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)

@@ -23,6 +23,8 @@ device events around CALLS back-to-back calls, WARMUP rounds, the median of ROUN
   (c) the path it replaces: host-made pixel-centre rays already resident on the device + rr_surface_rays_device + a torch gather of base_color
   (d) rr_denoise_records_device (5 iterations, halves, that albedo)      (e) the 4-sample rr_render_pixel_parts_device frame, and the 8-sample one
   (f) rr_albedo_pixels_device, the frame's mean albedo, at 4 and at 8 samples: a strict subset of (e)'s level-1 work at the same count
+  (g) rr_render_pixel_split_device at 4 and at 8 samples: (e)'s frame plus the direct diffuse sum; the bar is (g) < 2 x (e), rendering twice
+  (h) rr_denoise_split_records_device (5 iterations, halves, that albedo): (d)'s launches twice between two streaming kernels
 next to the compulsory traffic of (a) per pixel (the walk's records: 16 + 16 + 8 B written and read, 16 B of hit written and read, the
 4 B slot map written and read, 12 B of albedo written) at the float4-copy rate.  Scene `sponza_syn` is the benchmark's stand-in.
 
@@ -209,6 +211,8 @@ def measure_albedo(argv, emit):
         cfg8 = make_config(samples=8, monte_carlo=True, seed=1, max_recursion=4)
         surf = torch.empty((n, 32), dtype=torch.float32, device="cuda")
         out = torch.empty_like(rec)
+        split = renderer.render_pixel_split_torch(ds, cam, cfg, None, True)
+        dif, dif_h = split["diffuse"], split["diffuse_halves"]
         prm = capi.denoise_params(DenoiseParams(iterations=5))
         torch.cuda.synchronize()
 
@@ -225,11 +229,14 @@ def measure_albedo(argv, emit):
             "e8": lambda: renderer.render_pixel_parts_torch(ds, cam, cfg8, None, 2),
             "f4": lambda: ds.albedo_pixels_device(cam, cfg, None, n, mean.data_ptr(), stream),
             "f8": lambda: ds.albedo_pixels_device(cam, cfg8, None, n, mean.data_ptr(), stream),
+            "g4": lambda: renderer.render_pixel_split_torch(ds, cam, cfg, None, True),
+            "g8": lambda: renderer.render_pixel_split_torch(ds, cam, cfg8, None, True),
+            "h": lambda: ds.denoise_split_device(w, h, rec.data_ptr(), halves.data_ptr(), dif.data_ptr(), dif_h.data_ptr(), albedo.data_ptr(), out.data_ptr(), None, prm, stream),
         }
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
-                t = timed(fn, 1 if k in ("e", "e8") else CALLS)
+                t = timed(fn, 1 if k in ("e", "e8", "g4", "g8") else CALLS)
                 if r >= WARMUP:
                     runs[k].append(t)
         torch.cuda.synchronize()
@@ -239,14 +246,20 @@ def measure_albedo(argv, emit):
     names = {"a": "(a) rr_surface_pixels_device, albedo only", "b": "(b) rr_surface_pixels_device, records and albedo",
              "c": "(c) resident rays + rr_surface_rays_device + torch gather of base_color", "d": "(d) rr_denoise_records_device, 5 iterations, halves, albedo",
              "e": "(e) rr_render_pixel_parts_device, 4 samples in two halves", "e8": "(e) the same at 8 samples",
-             "f4": "(f) rr_albedo_pixels_device, the frame's mean albedo, 4 samples", "f8": "(f) the same at 8 samples"}
-    emit(f"the albedo guide, {scene} {w}x{h}; device ms per call, median of {ROUNDS} rounds of {CALLS} calls (e: 1 call) [min .. max]; (c)'s albedo equals (a)'s bit for bit: {same}")
-    for k in ("a", "b", "c", "d", "e", "e8", "f4", "f8"):
+             "f4": "(f) rr_albedo_pixels_device, the frame's mean albedo, 4 samples", "f8": "(f) the same at 8 samples",
+             "g4": "(g) rr_render_pixel_split_device, 4 samples in two halves", "g8": "(g) the same at 8 samples",
+             "h": "(h) rr_denoise_split_records_device, 5 iterations, halves, albedo"}
+    emit(f"the albedo guide, {scene} {w}x{h}; device ms per call, median of {ROUNDS} rounds of {CALLS} calls (e, g: 1 call) [min .. max]; (c)'s albedo equals (a)'s bit for bit: {same}")
+    for k in ("a", "b", "c", "d", "e", "e8", "f4", "f8", "g4", "g8", "h"):
         m, lo, hi = med[k]
         emit(f"  {names[k]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
     for f, e, s in (("f4", "e", 4), ("f8", "e8", 8)):
         below = med[f][2] < med[e][1]   # outside the two arms' ranges
         emit(f"  (f) / (e) at {s} samples = {med[f][0] / med[e][0]:.3f}; (f)'s largest below (e)'s smallest: {below}; (f) / (a) = {med[f][0] / med['a'][0]:.2f}")
+    for g, e, s in (("g4", "e", 4), ("g8", "e8", 8)):   # what a caller can do without the call: render the frame twice
+        below = med[g][2] < 2.0 * med[e][1]
+        emit(f"  (g) / (e) at {s} samples = {med[g][0] / med[e][0]:.3f}; (g)'s largest below twice (e)'s smallest: {below}")
+    emit(f"  (h) / (d) = {med['h'][0] / med['d'][0]:.3f}")
     a, c = med["a"], med["c"]
     emit(f"  (a) / (c) = {a[0] / c[0]:.3f}; (c)'s own spread {c[1]:.4f} .. {c[2]:.4f}; (a) / (d) = {a[0] / med['d'][0]:.3f}; (a) / (e) = {a[0] / med['e'][0]:.3f}")
     emit(f"  compulsory traffic of (a): {ALBEDO_BYTES_PER_PIXEL} B per pixel = {n * ALBEDO_BYTES_PER_PIXEL / 1e6:.1f} MB, {floor_ms * 1e3:.1f} us at {HBM_BYTES_PER_S / 1e12:.2f} TB/s: "
