@@ -168,13 +168,13 @@ struct MotionState {
     }
 };
 
-// ---- the host forms of rr_denoise_records, rr_accumulate_records and rr_motion_records: the device's copies of the caller's arrays, argument
-// k of a call in buf[k] (the most arguments: the ten of rr_accumulate_records), each only where the call has it; grown on demand, never
-// shrunk, so a slot holds the largest argument any of the three calls has put there.  One pool serves the three: a host form holds the
-// scene's lock and returns with the null stream idle, on its failing paths as well (IdleOnExit), so no call finds another's copies in
-// use.  Written by staged_host_call (rr_api_query.h).
+// ---- the host forms of the record calls (rr_denoise_records, rr_accumulate_records, rr_accumulate_split_records, rr_motion_records and
+// the rest): the device's copies of the caller's arrays, argument k of a call in buf[k] (the most arguments: the sixteen of
+// rr_accumulate_split_records), each only where the call has it; grown on demand, never shrunk, so a slot holds the largest argument any
+// of the calls has put there.  One pool serves them all: a host form holds the scene's lock and returns with the null stream idle, on
+// its failing paths as well (IdleOnExit), so no call finds another's copies in use.  Written by staged_host_call (rr_api_query.h).
 struct RecordStage {
-    DevBuf buf[10];
+    DevBuf buf[16];
 };
 
 // ---- rr_render_multi (rr_api_multi.h)

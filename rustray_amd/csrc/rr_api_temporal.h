@@ -1,11 +1,12 @@
 // rr_api_temporal.h — temporal reprojection of a frame of records on the device: the previous call's result is gathered into the
 // current frame and the current records are blended into it, the step before rr_denoise_records in a frame-after-frame loop.
-// Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records; tp_frame (for rr_api_motion.h).
+// Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records, rr_accumulate_split_records_device,
+//         rr_accumulate_split_records; tp_frame (for rr_api_motion.h).
 // Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_temporal.h,
 //         kernel 7e of rr_kernels.hip.
 //
-// The call is ONE launch of k_accumulate_records (with or without halves) and, for the bytes, k_record_bytes, on the caller's stream,
-// not waited for.  It keeps no working data.  The host form is the device form behind the staging of every record call
+// The call is ONE launch of k_accumulate_records (with or without halves; the split call: of k_accumulate_split_records) and, for the
+// bytes, k_record_bytes, on the caller's stream, not waited for.  It keeps no working data.  The host form is the device form behind the staging of every record call
 // (staged_host_call, in the handle's pool).
 
 int rr_accumulate_default_params(rr_accumulate_params* out) try {
@@ -26,8 +27,8 @@ struct AccumulateIo {
     rr_radiance* out; rr_radiance* halves_out; float* length_out; uint8_t* rgba8;
 };
 
-// what both forms check before the scene is looked at; `device`: the alignment rule of the device form
-static int check_accumulate_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io) {
+// what both forms of both calls check before the scene is looked at, up to the overlaps; `device`: the alignment rule of the device form
+static int check_accumulate_basics(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io) {
     if (!s) return fail(RR_ERR_INVALID_ARGUMENT, "%s: scene is NULL", fn);
     if (!cam) return fail(RR_ERR_INVALID_ARGUMENT, "%s: camera is NULL", fn);
     if (!prm) return fail(RR_ERR_INVALID_ARGUMENT, "%s: params is NULL", fn);
@@ -54,6 +55,12 @@ static int check_accumulate_args(const char* fn, bool device, const rr_scene* s,
         return fail(RR_ERR_INVALID_ARGUMENT, "%s: records_dev, halves_dev, history_dev, history_halves_dev, out_dev and halves_out_dev must be 16-byte aligned", fn);
     if (device && (((uintptr_t)io.history_length | (uintptr_t)io.motion | (uintptr_t)io.length_out | (uintptr_t)io.rgba8) & 3u))
         return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_length_dev, motion_dev, length_out_dev and rgba8_out_dev must be 4-byte aligned", fn);
+    return RR_OK;
+}
+
+static int check_accumulate_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io) {
+    RR_TRY(check_accumulate_basics(fn, device, s, cam, prm, io));
+    const uint32_t width = cam->width, height = cam->height;
     // overlaps: an output with an input or with another output; out == records and halves_out == halves exactly are the in-place call
     const uint64_t n = (uint64_t)width * height;
     const ArgRange t[10] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {io.history, 32u * n, "history", false, -1},
@@ -75,14 +82,22 @@ static TpFrame tp_frame(const rr_camera* cam) {
 }
 
 // the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
-static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io, hipStream_t st) {
+// split: the diffuse layers of rr_accumulate_split_records (then the SPLIT build of the kernel runs), or NULL
+static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io, hipStream_t st, const TpSplitIo* split = nullptr) {
     const uint32_t W = cam->width, H = cam->height;
     TpFrame f = tp_frame(cam);
     memcpy(f.prev_clip, prm->prev_world_to_clip, sizeof f.prev_clip);
     memcpy(f.prev_eye, prm->prev_eye, sizeof f.prev_eye);
     f.max_history = prm->max_history; f.normal_min = prm->normal_min; f.sigma_depth = prm->sigma_depth; f.snap = prm->snap;
     const dim3 grid((W + DN_TILE_W - 1) / DN_TILE_W, (H + DN_TILE_H - 1) / DN_TILE_H), block(RR_BLOCK);
-    if (io.halves)
+    if (split) {
+        if (io.halves)
+            hipLaunchKernelGGL(k_accumulate_split_records<true>, grid, block, 0, st, f, (const float4*)io.records, (const float4*)io.halves, (const float4*)io.history,
+                               (const float4*)io.history_halves, io.history_length, io.motion, (float4*)io.out, (float4*)io.halves_out, io.length_out, *split);
+        else
+            hipLaunchKernelGGL(k_accumulate_split_records<false>, grid, block, 0, st, f, (const float4*)io.records, (const float4*)nullptr, (const float4*)io.history,
+                               (const float4*)nullptr, io.history_length, io.motion, (float4*)io.out, (float4*)nullptr, io.length_out, *split);
+    } else if (io.halves)
         hipLaunchKernelGGL(k_accumulate_records<true>, grid, block, 0, st, f, (const float4*)io.records, (const float4*)io.halves, (const float4*)io.history,
                            (const float4*)io.history_halves, io.history_length, io.motion, (float4*)io.out, (float4*)io.halves_out, io.length_out);
     else
@@ -126,3 +141,70 @@ int rr_accumulate_records(rr_scene* s, const rr_camera* camera, const rr_accumul
         });
     });
 } RR_GUARD_END("rr_accumulate_records")
+
+// ---- rr_accumulate_split_records: the same call with the diffuse layers of rr_render_pixel_split riding on the taps of the records
+// what the split call checks beyond check_accumulate_basics: what comes with what, the float alignment and all sixteen ranges
+static int check_accumulate_split_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io,
+                                       const TpSplitIo& d) {
+    RR_TRY(check_accumulate_basics(fn, device, s, cam, prm, io));
+    if (!d.diffuse) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse is NULL", fn);
+    if (!d.diffuse_out) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_out is NULL", fn);
+    if ((d.dif_halves != nullptr) != (io.halves != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_halves is required exactly when halves is given", fn);
+    if ((d.dif_halves_out != nullptr) != (io.halves != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_halves_out is required exactly when halves is given", fn);
+    if ((d.history_diffuse != nullptr) != (io.history != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_diffuse is required exactly when history is given", fn);
+    if ((d.history_dif_halves != nullptr) != (io.history_halves != nullptr))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_diffuse_halves is required exactly when history_halves is given", fn);
+    if (device && (((uintptr_t)d.diffuse | (uintptr_t)d.dif_halves | (uintptr_t)d.history_diffuse | (uintptr_t)d.history_dif_halves | (uintptr_t)d.diffuse_out |
+                    (uintptr_t)d.dif_halves_out) & 3u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_dev, diffuse_halves_dev, history_diffuse_dev, history_diffuse_halves_dev, diffuse_out_dev and diffuse_halves_out_dev must be 4-byte aligned", fn);
+    const uint64_t n = (uint64_t)cam->width * cam->height;
+    const ArgRange t[16] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {d.diffuse, 12u * n, "diffuse", false, -1},
+                            {d.dif_halves, 24u * n, "diffuse_halves", false, -1}, {io.history, 32u * n, "history", false, -1},
+                            {io.history_halves, 64u * n, "history_halves", false, -1}, {d.history_diffuse, 12u * n, "history_diffuse", false, -1},
+                            {d.history_dif_halves, 24u * n, "history_diffuse_halves", false, -1}, {io.history_length, 4u * n, "history_length", false, -1},
+                            {io.motion, 12u * n, "motion", false, -1}, {io.out, 32u * n, "out", true, 0}, {io.halves_out, 64u * n, "halves_out", true, 1},
+                            {d.diffuse_out, 12u * n, "diffuse_out", true, 2}, {d.dif_halves_out, 24u * n, "diffuse_halves_out", true, 3},
+                            {io.length_out, 4u * n, "length_out", true, -1}, {io.rgba8, 4u * n, "rgba8_out", true, -1}};
+    return check_arg_ranges(fn, t, 16, false,
+                            " (only out == records, halves_out == halves, diffuse_out == diffuse and diffuse_halves_out == diffuse_halves, in place, are allowed)");
+}
+
+int rr_accumulate_split_records_device(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                                       const float* diffuse, const float* diffuse_halves, const rr_radiance* history, const rr_radiance* history_halves,
+                                       const float* history_diffuse, const float* history_diffuse_halves, const float* history_length, const float* motion,
+                                       rr_radiance* out, rr_radiance* halves_out, float* diffuse_out, float* diffuse_halves_out, float* length_out, uint8_t* rgba8_out,
+                                       void* hip_stream) try {
+    const char* fn = "rr_accumulate_split_records_device";
+    const AccumulateIo io{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out};
+    const TpSplitIo split{diffuse, diffuse_halves, history_diffuse, history_diffuse_halves, diffuse_out, diffuse_halves_out};
+    RR_TRY(check_accumulate_split_args(fn, true, s, camera, prm, io, split));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {diffuse, "diffuse_dev"}, {diffuse_halves, "diffuse_halves_dev"},
+                                      {history, "history_dev"}, {history_halves, "history_halves_dev"}, {history_diffuse, "history_diffuse_dev"},
+                                      {history_diffuse_halves, "history_diffuse_halves_dev"}, {history_length, "history_length_dev"}, {motion, "motion_dev"},
+                                      {out, "out_dev"}, {halves_out, "halves_out_dev"}, {diffuse_out, "diffuse_out_dev"}, {diffuse_halves_out, "diffuse_halves_out_dev"},
+                                      {length_out, "length_out_dev"}, {rgba8_out, "rgba8_out_dev"}}, st, [&] { return accumulate_locked(s, camera, prm, io, st, &split); });
+} RR_GUARD_END("rr_accumulate_split_records_device")
+
+int rr_accumulate_split_records(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_radiance* records, const rr_radiance* halves,
+                                const float* diffuse, const float* diffuse_halves, const rr_radiance* history, const rr_radiance* history_halves,
+                                const float* history_diffuse, const float* history_diffuse_halves, const float* history_length, const float* motion, rr_radiance* out,
+                                rr_radiance* halves_out, float* diffuse_out, float* diffuse_halves_out, float* length_out, uint8_t* rgba8_out) try {
+    const char* fn = "rr_accumulate_split_records";
+    RR_TRY(check_accumulate_split_args(fn, false, s, camera, prm, AccumulateIo{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out},
+                                       TpSplitIo{diffuse, diffuse_halves, history_diffuse, history_diffuse_halves, diffuse_out, diffuse_halves_out}));
+    const size_t n = (size_t)camera->width * camera->height;
+    const StageArg args[16] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(diffuse, 12 * n), stage_input(diffuse_halves, 24 * n),
+                               stage_input(history, 32 * n), stage_input(history_halves, 64 * n), stage_input(history_diffuse, 12 * n),
+                               stage_input(history_diffuse_halves, 24 * n), stage_input(history_length, 4 * n), stage_input(motion, 12 * n),
+                               stage_output(out, 32 * n), stage_output(halves_out, 64 * n), stage_output(diffuse_out, 12 * n), stage_output(diffuse_halves_out, 24 * n),
+                               stage_output(length_out, 4 * n), stage_output(rgba8_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const AccumulateIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const rr_radiance*)d[4], (const rr_radiance*)d[5], (const float*)d[8],
+                                   (const float*)d[9], (rr_radiance*)d[10], (rr_radiance*)d[11], (float*)d[14], (uint8_t*)d[15]};
+            const TpSplitIo split{(const float*)d[2], (const float*)d[3], (const float*)d[6], (const float*)d[7], (float*)d[12], (float*)d[13]};
+            return accumulate_locked(s, camera, prm, dev, nullptr, &split);
+        });
+    });
+} RR_GUARD_END("rr_accumulate_split_records")

@@ -2248,6 +2248,73 @@ __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_records(const TpFrame f
     }
 }
 
+// 7e': the SPLIT build of 7e (rr_accumulate_split_records): the records, halves and length of k_accumulate_records, bit for bit, and the
+// diffuse layers (3 floats a pixel, 3 a half: rr_render_pixel_split's layouts) blended over the same taps with the same weights and
+// length.  A 12-byte diffuse row is three dword loads; consecutive lanes read consecutive rows.  Of a tap the diffuse rows are read last,
+// after its half rows, and only when it is taken.  No LDS.  diffuse_out may be `diffuse` and dif_halves_out `dif_halves`: a lane reads
+// those at its own pixel only, before it writes.  history == NULL: every layer is copied.
+struct TpSplitHistory : TpHistory {
+    const float* __restrict__ history_diffuse;
+    const float* __restrict__ history_dif_halves;
+    RR_DEV void diffuse(unsigned long long q, float* c) const {
+        c[0] = history_diffuse[3ull * q]; c[1] = history_diffuse[3ull * q + 1]; c[2] = history_diffuse[3ull * q + 2];
+    }
+    RR_DEV void diffuse_half(unsigned long long q, int h, float* c) const {
+        const unsigned long long r = 3ull * (2ull * q + (unsigned int)h);
+        c[0] = history_dif_halves[r]; c[1] = history_dif_halves[r + 1]; c[2] = history_dif_halves[r + 2];
+    }
+};
+struct TpSplitIo { // the diffuse pointers of the call, in the order of its arguments
+    const float* diffuse; const float* dif_halves;
+    const float* __restrict__ history_diffuse; const float* __restrict__ history_dif_halves;
+    float* diffuse_out; float* dif_halves_out;
+};
+template <bool HALVES>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_split_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
+                                                                       const float4* __restrict__ history_halves, const float* __restrict__ history_length,
+                                                                       const float* __restrict__ motion, float4* out, float4* halves_out,
+                                                                       float* __restrict__ length_out, const TpSplitIo io) {
+    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
+    if (x >= f.width || y >= f.height) return;
+    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    float4 a0, a1, b0, b1;
+    if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
+    float d[3] = {io.diffuse[3ull * o], io.diffuse[3ull * o + 1], io.diffuse[3ull * o + 2]}, da[3], db[3];
+    if (HALVES)
+        for (int c = 0; c < 3; c++) { da[c] = io.dif_halves[6ull * o + c]; db[c] = io.dif_halves[6ull * o + 3 + c]; }
+    const uint32_t flags = denoise_record_flags(r0, r1);
+    TpMix m;
+    TpSplitMix s;
+    bool kept = false;
+    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
+        const float n_p[3] = {r1.x, r1.y, r1.z};
+        TpSplitHistory hist;
+        hist.history = history; hist.history_halves = history_halves; hist.history_length = history_length;
+        hist.history_diffuse = io.history_diffuse; hist.history_dif_halves = io.history_dif_halves;
+        kept = temporal_history<HALVES, TpSplitHistory, true>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr,
+                                                     hist, &m, &s);
+    }
+    float4 c0 = r0;
+    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
+    out[2ull * o] = c0;
+    out[2ull * o + 1] = r1;
+    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
+    if (kept) temporal_blend_diffuse(s.d, m.a, d, d);
+    io.diffuse_out[3ull * o] = d[0]; io.diffuse_out[3ull * o + 1] = d[1]; io.diffuse_out[3ull * o + 2] = d[2];
+    if (HALVES) {
+        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
+            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
+        }
+        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
+            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
+        }
+        halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
+        if (kept) { temporal_blend_diffuse(s.da, m.a, da, da); temporal_blend_diffuse(s.db, m.a, db, db); }
+        for (int c = 0; c < 3; c++) { io.dif_halves_out[6ull * o + c] = da[c]; io.dif_halves_out[6ull * o + 3 + c] = db[c]; }
+    }
+}
+
 // 7f: the motion of moved items per pixel (rr_motion_records; rr_motion.h has the arithmetic, rustray_amd/temporal.py: motion_records is
 // the yardstick).  One pixel per lane, 32x8 tiles as 7a .. 7e; a record is two 16-byte loads, the answer three dword stores (six with
 // world_out); no LDS.  The table is sorted by id: a lane whose record is valid looks its id up by binary search and reads the 24 floats

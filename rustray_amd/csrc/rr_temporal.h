@@ -85,12 +85,19 @@ RR_SETUP_HD bool temporal_depth_ok(const TpFrame& f, float z_exp, float z_q) {
     return denoise_is_finite(z_q) && __builtin_fabsf(z_exp - z_q) <= f.sigma_depth * z_exp + DN_EPS;
 }
 
+// the history of a pixel's diffuse part (rr_accumulate_split_records): the means of the same taps under the same weights
+struct TpSplitMix {
+    float d[3], da[3], db[3]; // of `diffuse` and (with halves) of the two diffuse half-histories
+};
+
 // The history of pixel (x, y), whose record has DN_FIN and DN_VALID: its depth, normal and id, and its motion (3 floats, or NULL).
-// hist gives the previous frame at pixel index q: length(q); guide(q, n, &id); colour(q, c, &z); with HALVES half(q, h, c).
+// hist gives the previous frame at pixel index q: length(q); guide(q, n, &id); colour(q, c, &z); with HALVES half(q, h, c); with SPLIT
+// diffuse(q, c) and, with HALVES too, diffuse_half(q, h, c), read after the half rows of a tap that is taken: no diffuse value decides
+// anything, so taps, weights, m and the answer are those of the build without SPLIT.  d is written with SPLIT only.
 // false: the pixel takes the no-history path.
-template <bool HALVES, class Hist>
+template <bool HALVES, class Hist, bool SPLIT = false>
 RR_SETUP_HD bool temporal_history(const TpFrame& f, unsigned int x, unsigned int y, float depth, const float* n_p, unsigned int id_p, const float* motion,
-                                  Hist hist, TpMix* m) {
+                                  Hist hist, TpMix* m, TpSplitMix* d = nullptr) {
     float prev[3], fx, fy, z_exp;
     temporal_world(f, x, y, depth, prev);
     if (motion)
@@ -98,6 +105,7 @@ RR_SETUP_HD bool temporal_history(const TpFrame& f, unsigned int x, unsigned int
     if (!temporal_reproject(f, prev, &fx, &fy, &z_exp)) return false;
     const TpTaps t = temporal_taps(fx, fy, f.snap);
     float sum_w = 0.0f, sum_l = 0.0f, sum_c[3] = {0.0f, 0.0f, 0.0f}, sum_a[3] = {0.0f, 0.0f, 0.0f}, sum_b[3] = {0.0f, 0.0f, 0.0f};
+    float sum_d[3] = {0.0f, 0.0f, 0.0f}, sum_da[3] = {0.0f, 0.0f, 0.0f}, sum_db[3] = {0.0f, 0.0f, 0.0f};
     for (int k = 0; k < 4; k++) {
         if (k >= t.n) break;
         const int qx = t.x0 + (k & 1), qy = t.y0 + (k >> 1);
@@ -122,6 +130,16 @@ RR_SETUP_HD bool temporal_history(const TpFrame& f, unsigned int x, unsigned int
             for (int c = 0; c < 3; c++) { sum_a[c] += w * a_q[c]; sum_b[c] += w * b_q[c]; }
         sum_l += w * len_q;
         sum_w += w;
+        if constexpr (SPLIT) {
+            float d_q[3], da_q[3], db_q[3];
+            hist.diffuse(q, d_q);
+            for (int c = 0; c < 3; c++) sum_d[c] += w * d_q[c];
+            if (HALVES) {
+                hist.diffuse_half(q, 0, da_q);
+                hist.diffuse_half(q, 1, db_q);
+                for (int c = 0; c < 3; c++) { sum_da[c] += w * da_q[c]; sum_db[c] += w * db_q[c]; }
+            }
+        }
     }
     if (!(sum_w >= TP_MIN_WEIGHT)) return false;
     for (int c = 0; c < 3; c++) {
@@ -132,8 +150,22 @@ RR_SETUP_HD bool temporal_history(const TpFrame& f, unsigned int x, unsigned int
     const float n1 = sum_l / sum_w + 1.0f;
     m->length = n1 < f.max_history ? n1 : f.max_history; // (a NaN or infinite length becomes max_history)
     m->a = 1.0f / m->length;
+    if constexpr (SPLIT)
+        for (int c = 0; c < 3; c++) {
+            d->d[c] = sum_d[c] / sum_w;
+            d->da[c] = HALVES ? sum_da[c] / sum_w : 0.0f;
+            d->db[c] = HALVES ? sum_db[c] / sum_w : 0.0f;
+        }
+    else { (void)d; (void)sum_d; (void)sum_da; (void)sum_db; }
     return true;
 }
 
 // one channel of one layer: the history moved towards the current colour by a
 RR_SETUP_HD float temporal_blend(float h, float a, float cur) { return h + a * (cur - h); }
+
+// one diffuse layer of a pixel that kept its history (rr_accumulate_split_records): blended where the current triple and the three
+// history means are finite, the current bits otherwise.  out may be cur.
+RR_SETUP_HD void temporal_blend_diffuse(const float* hd, float a, const float* cur, float* out) {
+    const bool ok = temporal_colour_ok(cur) && temporal_colour_ok(hd);
+    for (int c = 0; c < 3; c++) out[c] = ok ? temporal_blend(hd[c], a, cur[c]) : cur[c];
+}

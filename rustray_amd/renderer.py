@@ -267,9 +267,17 @@ class Raytracing:
         call on the same stream); a change of the item count or of any item's id resets the state, and so does a history from a call
         without track_items.  albedo=True: one more call on the same stream (rr_surface_pixels_device) makes this camera's albedo for the
         filter; the accumulation is not changed, it blends un-demodulated colour.  albedo="mean": rr_albedo_pixels_device with the frame's
-        config and table in its place.  albedo="diffuse" raises ValueError: no diffuse part is accumulated over time."""
+        config and table in its place.  albedo="diffuse" raises ValueError: the diffuse part is accumulated over time by
+        render_temporal_split, a pipeline of its own."""
         from .temporal import previous_view
         _check_albedo_mode(albedo, temporal=True)
+        cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
+        return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
+                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo)
+
+    def _temporal_frame(self, state: "TemporalState", samples, seed, motion, track_items: bool):
+        """What render_temporal and render_temporal_split do before their pipeline: the frame's config, and with track_items the moved items
+        against the history (the state notes this frame's) -> (cfg, moved or None)."""
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
             cfg.samples = samples
@@ -285,8 +293,20 @@ class Raytracing:
                 moved = (np.zeros(0, np.uint32), np.zeros((0, 4, 4), np.float32))
         else:
             state.items = None
-        return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo)
+        return cfg, moved
+
+    def render_temporal_split(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
+                              motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False) -> dict:
+        """render_temporal with the frame's direct diffuse light accumulated as layers of its own and the mean albedo applied to it alone:
+        rr_render_pixel_split, (with moved items) rr_motion_records, rr_accumulate_split_records, rr_albedo_pixels and
+        rr_denoise_split_records -- render_temporal_split_torch on this scene and camera, on one stream with no host trip.  The arguments are
+        render_temporal's, without `albedo`; `state` is a TemporalState of this pipeline's (one that render_temporal filled starts anew).
+        The result holds torch tensors: render_temporal's, and diffuse, diffuse_halves, accumulated_diffuse, accumulated_diffuse_halves and
+        albedo."""
+        from .temporal import previous_view
+        cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
+        return render_temporal_split_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
+                                           sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -872,7 +892,8 @@ def _check_albedo_mode(albedo, temporal: bool = False) -> None:
     if isinstance(albedo, str) and albedo not in ("mean", "diffuse"):
         raise ValueError(f'albedo must be False, True, "mean" or "diffuse", not {albedo!r}')
     if temporal and _diffuse_mode(albedo):
-        raise ValueError('albedo="diffuse" is for the single-frame pipelines: the temporal ones accumulate no diffuse part')
+        raise ValueError('albedo="diffuse" is for the single-frame pipelines; over time the diffuse part is accumulated by render_temporal_split '
+                         '(render_temporal_split_torch), a pipeline of its own')
 
 
 def _mean_mode(albedo) -> bool:
@@ -1175,8 +1196,9 @@ def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, p
 # ---------------------------------------------------------------------------
 class TemporalState:
     """What a frame-after-frame loop carries from one rr_accumulate_records call to the next: two sets of device tensors (records (n, 8),
-    halves (n, 2, 8), length (n,)) used in turn -- the call gathers from one set and writes the other --, which of them holds the history,
-    and the view (world_to_clip, eye) the history was rendered from.  reset() forgets the history: the next frame is a first frame."""
+    halves (n, 2, 8), length (n,); for the split pipeline also diffuse (n, 3) and diffuse_halves (n, 2, 3)) used in turn -- the call gathers
+    from one set and writes the other --, which of them holds the history, and the view (world_to_clip, eye) the history was rendered
+    from.  reset() forgets the history: the next frame is a first frame."""
 
     def __init__(self):
         self.sets = [None, None]
@@ -1208,15 +1230,20 @@ class TemporalState:
     def history(self):
         return self.sets[self.current] if self.current is not None else None
 
-    def target(self, n: int, halves: bool, device) -> dict:
-        """The set the next call writes: the one that does not hold the history, (re)allocated when the frame's size changed."""
+    def target(self, n: int, halves: bool, device, diffuse: bool = False) -> dict:
+        """The set the next call writes: the one that does not hold the history, (re)allocated when the frame's size changed.  diffuse:
+        the set of the split pipeline, with diffuse (n, 3) and, with halves, diffuse_halves (n, 2, 3)."""
         import torch
         k = 0 if self.current is None else self.current ^ 1
         t = self.sets[k]
-        if t is None or int(t["records"].shape[0]) != n or t["records"].device != device or (t["halves"] is not None) != halves:
+        if (t is None or int(t["records"].shape[0]) != n or t["records"].device != device or (t["halves"] is not None) != halves
+                or (t.get("diffuse") is not None) != diffuse):
             t = dict(records=torch.empty((n, 8), dtype=torch.float32, device=device),
                      halves=torch.empty((n, 2, 8), dtype=torch.float32, device=device) if halves else None,
                      length=torch.empty((n,), dtype=torch.float32, device=device))
+            if diffuse:
+                t.update(diffuse=torch.empty((n, 3), dtype=torch.float32, device=device),
+                         diffuse_halves=torch.empty((n, 2, 3), dtype=torch.float32, device=device) if halves else None)
             self.sets[k] = t
         return t
 
@@ -1257,6 +1284,44 @@ def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, 
     return result
 
 
+def accumulate_split_torch(device_scene: capi.DeviceScene, cam, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
+                           history_diffuse_halves=None, history_length=None, motion=None, params=None, rgba8: bool = False, in_place: bool = False,
+                           out: Optional[dict] = None) -> dict:
+    """rr_accumulate_split_records_device on torch's current stream of the scene's device: the tensors of accumulate_torch, and `diffuse`
+    (n, 3), `diffuse_halves` (n, 2, 3) or None (exactly when `halves` is), `history_diffuse` (n, 3) and `history_diffuse_halves` (n, 2, 3):
+    the previous call's.  Returns torch tensors, without a host copy and without a synchronisation: the dict of accumulate_torch plus
+    diffuse (n, 3) and diffuse_halves (n, 2, 3) or None.  in_place: written over the four current tensors; out: dict(records, halves,
+    diffuse, diffuse_halves, length) of tensors to write."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), diffuse=(diffuse, (3,)),
+                                                                  diffuse_halves=(diffuse_halves, (2, 3)), history=(history, (8,)),
+                                                                  history_halves=(history_halves, (2, 8)), history_diffuse=(history_diffuse, (3,)),
+                                                                  history_diffuse_halves=(history_diffuse_halves, (2, 3)), history_length=(history_length, ()),
+                                                                  motion=(motion, (3,))), required=("records", "diffuse"))
+    dev = torch.device("cuda", device_scene.device)
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    current = ("records", "halves", "diffuse", "diffuse_halves")
+    shapes = dict(records=(n, 8), halves=(n, 2, 8), diffuse=(n, 3), diffuse_halves=(n, 2, 3))
+    with torch.cuda.device(dev):
+        if in_place:
+            res = {k: t[k] for k in current}
+        elif out is not None:
+            res = {k: out[k] if t[k] is not None else None for k in current}
+        else:
+            res = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) if t[k] is not None else None for k in current}
+        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        device_scene.accumulate_split_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["diffuse"]), ptr(t["diffuse_halves"]), ptr(t["history"]),
+                                             ptr(t["history_halves"]), ptr(t["history_diffuse"]), ptr(t["history_diffuse_halves"]), ptr(t["history_length"]),
+                                             ptr(t["motion"]), ptr(res["records"]), ptr(res["halves"]), ptr(res["diffuse"]), ptr(res["diffuse_halves"]), ptr(length),
+                                             ptr(rgba), params, torch.cuda.current_stream(dev).cuda_stream)
+    result = dict(_record_views(res["records"]), halves=res["halves"], diffuse=res["diffuse"], diffuse_halves=res["diffuse_halves"], length=length)
+    if rgba8:
+        result["rgba"] = rgba
+    return result
+
+
 def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_trans, world: bool = False) -> dict:
     """rr_motion_records_device on torch's current stream of the scene's device: `records` (n, 8) is a contiguous float32 CUDA tensor on
     that device, n = cam.width * cam.height (anything else raises); item_index (k,) and prev_trans (k, 4, 4, math layout) are host arrays:
@@ -1287,8 +1352,8 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     accumulated_halves (n, 2, 8) and length (n,): what the filter read, which `state` now holds as the history; and motion (n, 3) or None:
     what the accumulation read.  albedo=True: rr_surface_pixels_device on the same stream, one call more, makes the albedo of `cam` for the
     filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it.  albedo="mean":
-    rr_albedo_pixels_device with the frame's config and table in its place.  albedo="diffuse" raises ValueError: no diffuse part is
-    accumulated over time."""
+    rr_albedo_pixels_device with the frame's config and table in its place.  albedo="diffuse" raises ValueError: the diffuse part is
+    accumulated over time by render_temporal_split_torch."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
@@ -1319,3 +1384,44 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     if albedo:
         res["albedo"] = guide
     return res
+
+
+def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
+                                sample_xy=None, rgba8: bool = False, view=None, moved=None) -> dict:
+    """render_temporal_torch for the split arm, with no host trip: rr_render_pixel_split_device (cfg.samples even), with moved items
+    rr_motion_records_device, rr_accumulate_split_records_device against the history in `state`, rr_albedo_pixels_device (the mean albedo,
+    as render_denoised_torch(albedo="diffuse") uses) and rr_denoise_split_records_device on the accumulated layers -- four or five calls on
+    torch's current stream, each reading what the ones before wrote without a synchronisation.  The arguments are render_temporal_torch's.
+    A history without a diffuse part (a state render_temporal_torch filled), without halves or of another size resets the state, the
+    items noted for this frame kept.  Returns the dict of render_temporal_torch (without a variance) plus diffuse (n, 3) and diffuse_halves
+    (n, 2, 3), the frame's own, accumulated_diffuse and accumulated_diffuse_halves, what the filter read and `state` now holds, and
+    albedo (n, 3)."""
+    import dataclasses
+    import torch
+    from .temporal import AccumulateParams, previous_view
+    if moved is not None and motion is not None:
+        raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
+    base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)
+    n = int(cam.width) * int(cam.height)
+    hist = state.history()
+    if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None or hist.get("diffuse") is None):
+        items = state.items
+        state.reset()
+        state.items = items      # (the items noted for this frame are those of the history it becomes)
+        hist = None
+    prm = dataclasses.replace(params) if params is not None else AccumulateParams()
+    if hist is not None:
+        prm.prev_world_to_clip, prm.prev_eye = state.view
+    target = state.target(n, True, torch.device("cuda", device_scene.device), diffuse=True)
+    if moved is not None and hist is not None and len(moved[0]):
+        motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
+    h = lambda k: hist[k] if hist else None
+    acc = accumulate_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"), h("halves"),
+                                 h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, out=target)
+    guide = albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
+    res = denoise_split_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["diffuse"], acc["halves"], acc["diffuse_halves"], guide,
+                              denoise_params, rgba8=rgba8)
+    state.advance(target, view if view is not None else previous_view(cam))
+    return dict(res, noisy=base["records"], halves=base["part_records"], diffuse=base["diffuse"], diffuse_halves=base["diffuse_halves"],
+                accumulated=acc["records"], accumulated_halves=acc["halves"], accumulated_diffuse=acc["diffuse"],
+                accumulated_diffuse_halves=acc["diffuse_halves"], length=acc["length"], motion=motion, albedo=guide)

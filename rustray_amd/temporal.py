@@ -113,13 +113,10 @@ def motion_records(records, cam, item_ids, prev_trans, cur_trans_inv):
     return motion, world
 
 
-def accumulate_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None) -> dict:
-    """records (n, 8) float32 rr_radiance records of the whole frame of `cam` (a camera.Camera or an rr_camera) in row-major order;
-    halves (n, 2, 8) or None; history (n, 8), history_halves (n, 2, 8) and history_length (n,): the previous call's records, halves and
-    length, or all None on the first frame; motion (n, 3) or None.  Returns dict(records (n, 8), length (n,), halves (n, 2, 8) or None,
-    taps: dict(x, y (n, 4) int, weight (n, 4) float32, taken (n, 4) bool, reprojected (n,) bool: the pixel reached step 4) -- where each
-    pixel's history came from)."""
-    prm = params or AccumulateParams()
+def _accumulate(records, halves, history, history_halves, history_length, motion, cam, prm, extra=()):
+    """The tap walk and the blends that accumulate_records and accumulate_split_records share.  extra: (current (n, 3), history (n, 3) or
+    None) per extra layer, which rides on the taps and weights of the records and decides nothing.  -> (accumulate_records' dict, the
+    extra layers' outputs)."""
     prm.check()
     pi, vi, W, H = camera_matrices(cam)
     n = W * H
@@ -136,6 +133,7 @@ def accumulate_records(records, halves, history, history_halves, history_length,
 
     out = rec.copy()
     out_h = None if hv is None else hv.copy()
+    out_x = [np.array(cur, F).reshape(n, 3) for cur, _ in extra]
     taps = dict(x=np.zeros((n, 4), np.int64), y=np.zeros((n, 4), np.int64), weight=np.zeros((n, 4), F), taken=np.zeros((n, 4), bool),
                 reprojected=np.zeros(n, bool))
     with np.errstate(all="ignore"):
@@ -143,11 +141,12 @@ def accumulate_records(records, halves, history, history_halves, history_length,
         valid = np.isfinite(rec[:, 3]) & np.isfinite(rec[:, 4:7]).all(-1)
         length = np.where(fin, one, F(0)).astype(F)
         if history is None:
-            return dict(records=out, length=length, halves=out_h, taps=taps)
+            return dict(records=out, length=length, halves=out_h, taps=taps), out_x
         hist = np.ascontiguousarray(history, F).reshape(n, 8)
         hist_h = None if hv is None else np.ascontiguousarray(history_halves, F).reshape(n, 2, 8)
         hist_len = np.ascontiguousarray(history_length, F).reshape(n)
-
+        hist_x = [np.ascontiguousarray(h, F).reshape(n, 3) for _, h in extra]
+        sum_x = [np.zeros((n, 3), F) for _ in extra]
         prev = world_positions(rec, cam)
         if motion is not None:
             prev = prev + np.ascontiguousarray(motion, F).reshape(n, 3)
@@ -189,6 +188,8 @@ def accumulate_records(records, halves, history, history_halves, history_length,
             w = ((tx if k & 1 else one - tx) * (ty if k >> 1 else one - ty)).astype(F)
             for s, layer in zip(sum_c, layers):
                 np.add(s, w[:, None] * layer[q], out=s, where=taken[:, None])
+            for sx, layer in zip(sum_x, hist_x):
+                np.add(sx, w[:, None] * layer[q], out=sx, where=taken[:, None])
             np.add(sum_l, w * hist_len[q], out=sum_l, where=taken)
             np.add(sum_w, w, out=sum_w, where=taken)
             taps["x"][:, k], taps["y"][:, k], taps["weight"][:, k], taps["taken"][:, k] = qx, qy, w, taken
@@ -204,5 +205,47 @@ def accumulate_records(records, halves, history, history_halves, history_length,
             h = s / sum_w[:, None]
             blended = h + a[:, None] * (cur - h)
             dst[...] = np.where((kept & np.isfinite(cur).all(-1))[:, None], blended, cur)
+        for sx, (cur, _), dst in zip(sum_x, extra, out_x):
+            cur = np.ascontiguousarray(cur, F).reshape(n, 3)
+            hd = sx / sum_w[:, None]
+            blended = hd + a[:, None] * (cur - hd)
+            dst[...] = np.where((kept & np.isfinite(cur).all(-1) & np.isfinite(hd).all(-1))[:, None], blended, cur)
         length = np.where(kept, N, length).astype(F)
-    return dict(records=out, length=length, halves=out_h, taps=taps)
+    return dict(records=out, length=length, halves=out_h, taps=taps), out_x
+
+
+def accumulate_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None) -> dict:
+    """records (n, 8) float32 rr_radiance records of the whole frame of `cam` (a camera.Camera or an rr_camera) in row-major order;
+    halves (n, 2, 8) or None; history (n, 8), history_halves (n, 2, 8) and history_length (n,): the previous call's records, halves and
+    length, or all None on the first frame; motion (n, 3) or None.  Returns dict(records (n, 8), length (n,), halves (n, 2, 8) or None,
+    taps: dict(x, y (n, 4) int, weight (n, 4) float32, taken (n, 4) bool, reprojected (n,) bool: the pixel reached step 4) -- where each
+    pixel's history came from)."""
+    return _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams())[0]
+
+
+def accumulate_split_records(records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, history_length,
+                             motion, cam, params: AccumulateParams | None = None) -> dict:
+    """rr_accumulate_split_records in numpy float32: accumulate_records' arguments, and diffuse (n, 3), diffuse_halves (n, 2, 3) or None
+    (exactly when halves is), history_diffuse (n, 3) exactly when history is given and history_diffuse_halves (n, 2, 3) exactly when
+    history_halves is.  The diffuse layers ride on the taps, weights and length of the records: records, halves and length are
+    accumulate_records' bits.  A diffuse layer of a kept pixel is hd + a * (cur - hd) where its current triple and its history mean hd are
+    finite, and its current bits everywhere else.  -> dict(records (n, 8), halves (n, 2, 8) or None, diffuse (n, 3), diffuse_halves
+    (n, 2, 3) or None, length (n,), taps)."""
+    if diffuse is None:
+        raise ValueError("diffuse is required")
+    if (diffuse_halves is None) != (halves is None):
+        raise ValueError("diffuse_halves is required exactly when halves is given")
+    if (history_diffuse is None) != (history is None):
+        raise ValueError("history_diffuse is required exactly when history is given")
+    if (history_diffuse_halves is None) != (history_halves is None):
+        raise ValueError("history_diffuse_halves is required exactly when history_halves is given")
+    n = np.ascontiguousarray(records, F).size // 8
+    layer = lambda a, h: None if a is None else np.ascontiguousarray(a, F).reshape(n, 2, 3)[:, h]
+    flat = lambda a: None if a is None else np.ascontiguousarray(a, F).reshape(n, 3)
+    extra = [(flat(diffuse), flat(history_diffuse))]
+    if diffuse_halves is not None:
+        extra += [(layer(diffuse_halves, h), layer(history_diffuse_halves, h)) for h in (0, 1)]
+    res, out_x = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), extra)
+    res["diffuse"] = out_x[0]
+    res["diffuse_halves"] = None if diffuse_halves is None else np.ascontiguousarray(np.stack([out_x[1], out_x[2]], axis=1))
+    return res

@@ -18,7 +18,12 @@ rounds.
 previous transform shifted by 0.05), or one item, with and without world_out -- next to ITS compulsory traffic: 32 B of records read
 and 12 B of motion written per pixel, 12 more with world_out.  The yardstick is the static-view accumulation with halves of the same run.
 
-usage: temporal_time.py [scene [width height samples]] [--motion] [--out FILE]"""
+--split: rr_accumulate_split_records_device in the same rounds, with halves, static view and 1.3-pixel yaw, on a frame and a history of
+rr_render_pixel_split_device -- next to ITS compulsory traffic: per pixel 36 B of diffuse layers read, 36 B gathered and 36 B written
+beside the 296 B of the record call, 404 B in the static case.  The yardstick is the alternative a caller has without the call: two
+rr_accumulate_records_device calls of the same run and view.
+
+usage: temporal_time.py [scene [width height samples]] [--motion] [--split] [--out FILE]"""
 import math
 import os
 import sys
@@ -58,6 +63,9 @@ def main(argv):
     with_motion = "--motion" in argv
     if with_motion:
         argv.remove("--motion")
+    with_split = "--split" in argv
+    if with_split:
+        argv.remove("--split")
     scene = argv[1] if len(argv) > 1 else "spheres_room"
     w, h, samples = (int(argv[2]), int(argv[3]), int(argv[4])) if len(argv) > 4 else (1280, 720, 4)
     if capi.device_count() < 1:
@@ -111,6 +119,21 @@ def main(argv):
             for k in (len(fs.items), 1):
                 for with_world in (False, True):
                     arms[("motion", k, with_world)] = motion_call(k, with_world)
+        if with_split:
+            cfgs = [make_config(samples=samples, monte_carlo=True, seed=s, max_recursion=4) for s in (1, 2)]
+            sf = [renderer.render_pixel_split_torch(ds, cam, c, None, True) for c in cfgs]
+            sh = renderer.accumulate_split_torch(ds, cam, sf[0]["records"], sf[0]["part_records"], sf[0]["diffuse"], sf[0]["diffuse_halves"])
+            torch.cuda.synchronize()
+            s_out = {k: torch.empty_like(sh[k]) for k in ("records", "halves", "diffuse", "diffuse_halves", "length")}
+
+            def split_call(view):
+                prm = capi.accumulate_params(AccumulateParams(prev_world_to_clip=views[view][0], prev_eye=views[view][1]))
+                cur = [sf[1][k].data_ptr() for k in ("records", "part_records", "diffuse", "diffuse_halves")]
+                old = [sh[k].data_ptr() for k in ("records", "halves", "diffuse", "diffuse_halves", "length")]
+                new = [s_out[k].data_ptr() for k in ("records", "halves", "diffuse", "diffuse_halves", "length")]
+                return lambda: ds.accumulate_split_device(cam, *cur, *old, None, *new, None, prm, stream)
+            for view in ("static", "moved"):
+                arms[("split", view)] = split_call(view)
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
@@ -128,6 +151,15 @@ def main(argv):
         m, lo, hi = _median(v)
         if k == "denoise":
             emit(f"  rr_denoise_records_device, 5 iterations, with halves, rgba8_out, same rounds: {m:.4f} ms [{lo:.4f} .. {hi:.4f}]")
+            continue
+        if k[0] == "split":
+            per_pixel = BYTES_PER_PIXEL[True] + 108
+            floor_ms = n * per_pixel / HBM_BYTES_PER_S * 1e3
+            bm, blo, bhi = _median(runs[(True, k[1])])
+            apart = "outside" if hi < 2 * blo else "NOT outside"
+            emit(f"  rr_accumulate_split_records_device, with halves, {k[1]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the rate of its compulsory "
+                 f"traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / bm:.2f} x rr_accumulate_records_device with halves, {k[1]}; the bar, two "
+                 f"such calls: {2 * bm:.4f} ms [{2 * blo:.4f} .. {2 * bhi:.4f}], {'met' if m < 2 * bm else 'MISSED'}, {apart} the arms' ranges")
             continue
         if k[0] == "motion":
             per_pixel = 44 + (12 if k[2] else 0)
