@@ -1101,3 +1101,17 @@ def math_probe(op: int, a, b=None, c=None, seed: int = 0, device: int = 0):
                                c.ctypes.data_as(C.c_void_p) if c is not None else None, n,
                                *[o.ctypes.data_as(C.c_void_p) for o in outs], C.c_uint64(seed), device))
     return outs
+
+
+def philox_probe(op: int, counters, key, device: int = 0):
+    """rr_math_probe ops 12 (device) and 14 (host) of philox4x32_10: `counters` is (m, 4) uint32
+    (pixel, sample, node, stream), `key` two uint32 words; returns the (m, 2) uint32 words jitter() uses."""
+    ctr = np.ascontiguousarray(counters, np.uint32).reshape(-1, 4)
+    m = len(ctr)
+    a = np.concatenate([ctr[:, 0], ctr[:, 3]]).view(np.float32)
+    b = np.concatenate([ctr[:, 1], np.zeros(m, np.uint32)]).view(np.float32)
+    c = np.concatenate([ctr[:, 2], np.zeros(m, np.uint32)]).view(np.float32)
+    seed = (int(key[0]) & 0xffffffff) | ((int(key[1]) & 0xffffffff) << 32)
+    r0, r1, _ = math_probe(op, a, b, c, seed=seed, device=device)
+    return np.stack([r0.view(np.uint32)[:m], r1.view(np.uint32)[:m]], axis=1)
+

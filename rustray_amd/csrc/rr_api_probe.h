@@ -20,6 +20,16 @@ extern "C" int rr_math_probe(int op, const float* a, const float* b, const float
         for (int i = 0; i < n; i++) out0[i] = rr_cos(a[i] * RR_PI_F);
         return RR_OK;
     }
+    if (op == 14) { // the HOST build of philox4x32_10: the layout of op 12 (k_math_probe), words as bit patterns; needs no device
+        if (!b || !c || !out1) return fail(RR_ERR_INVALID_ARGUMENT, "bad arguments");
+        const int m = n / 2;
+        for (int i = 0; i < m; i++) {
+            uint32_t r0, r1;
+            philox4x32_10(f_bits(a[i]), f_bits(b[i]), f_bits(c[i]), f_bits(a[m + i]), (uint32_t)seed, (uint32_t)(seed >> 32), &r0, &r1);
+            out0[i] = bits_f(r0); out1[i] = bits_f(r1);
+        }
+        return RR_OK;
+    }
     HIP_TRY(hipSetDevice(device));
     DevBuf in[3], o[3];
     const float* src[3] = {a, b, c};

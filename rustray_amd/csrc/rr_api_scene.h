@@ -217,7 +217,7 @@ extern "C" int rr_scene_create(const rr_flat_scene* fs, int device, rr_scene** o
     HIP_TRY(s->data.attrs.upload(r.attrs, 16));
     HIP_TRY(s->data.face_slot.upload(r.face_slot, 16));
     HIP_TRY(s->data.items.upload(r.items, 16));
-    HIP_TRY(s->data.flat_normals.reserve(std::max<size_t>((size_t)r.n_flat_normals * sizeof(float4), 16)));
+    HIP_TRY(s->data.flat_normals.reserve(flat_normals_bytes(r.n_flat_normals)));
     // the host copies that the scene's edits and queries work from
     s->data.tex_width.swap(r.tex_width); s->data.h_textures.swap(r.dtex); s->data.h_dmat.swap(r.dmat); s->data.h_lights.swap(r.dlights);
     s->data.h_items.swap(r.items); s->data.item_host.swap(r.item_host);
@@ -602,7 +602,7 @@ extern "C" int rr_scene_set_items(rr_scene* s, const rr_item* items, uint32_t n_
     DevBuf d_items, d_materials, d_flat_normals, d_item_chunks, d_spans, d_chunk_src, d_derive_chunks, d_tnodes4, d_item_boxes;
     HIP_TRY(d_items.upload(rec.items, 16));
     HIP_TRY(d_materials.upload(dmat, sizeof(DMaterial)));
-    HIP_TRY(d_flat_normals.reserve(std::max<size_t>((size_t)rec.n_flat_normals * sizeof(float4), 16)));
+    HIP_TRY(d_flat_normals.reserve(flat_normals_bytes(rec.n_flat_normals)));
     HIP_TRY(d_item_chunks.upload(chunks, 16));
     HIP_TRY(d_spans.reserve(std::max<size_t>(9 * sizeof(double) * nc, 16))); // room for every chunk: a transform update derives them all
     HIP_TRY(d_chunk_src.upload(chunk_src, 16));

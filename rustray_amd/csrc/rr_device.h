@@ -121,6 +121,7 @@ struct DLight {
     float color[3]; uint32_t type; // RR_LIGHT_*; disabled lights are kept (index = RNG stream) with type | 0x80
 };
 
+#define RR_FLAT_ENTRY_F4 3u // float4 per entry of DSceneView::flat_normals
 struct DSceneView {
     const DItem* items;
     const DNode4* nodes4;   // per-mesh trees; DItem::node_base4 / root4 index it
@@ -130,7 +131,10 @@ struct DSceneView {
     // The world normal of a flat-shaded hit depends on the item's transform and the triangle only: normalize(trans * (+-flat normal, 0))
     // (Shape::intersect, src/shape/mesh.rs:76-98).  k_world_normals evaluates it once per instanced triangle and sign -- with the very
     // device function k_shade used per hit (to_world_normal) -- at scene creation and after a transform update:
-    // flat_normals[item.wn_base + 2 * slot + (negated ? 1 : 0)].xyz.  32 B per instanced triangle.
+    // entry e = item.wn_base + 2 * slot + (negated ? 1 : 0).  Next to the normal, the entry holds what normal mapping derives from that
+    // normal alone -- mapped_normal's tangent and bitangent (tangent_frame, rr_surface.h: the function the per-hit path uses), filled for
+    // every entry: a normal map can be attached later by a texture edit.  flat_normals[RR_FLAT_ENTRY_F4 * e + (0, 1, 2)].xyz = normal,
+    // tangent, bitangent: 96 B per instanced triangle.
     const float4* flat_normals;
     const uint32_t* face_slot; // per mesh triangle: original face index -> leaf-order slot
     const DMaterial* materials;

@@ -441,7 +441,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         f2 uv;
         const bool has_uv = hit_uv(it, it_flags, m, hit_point, gw, hw, &uv);
         // ---- normal mapping (:757-784)
-        f3 surface_normal = mapped_normal(sc, m, has_uv, uv, normal);
+        f3 surface_normal = mapped_normal(sc, m, has_uv, uv, normal, flat_frame_entry(hi, hit.z));
         // the generator is keyed on the FRAME pixel (y * width + x), never on the accumulator slot
         const uint32_t xy = slot_xy[pix];
         RngKey rk; rk.seed_lo = fr.seed_lo; rk.seed_hi = fr.seed_hi;
@@ -679,13 +679,19 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
 // One workgroup per CHUNK of an item's triangles (`chunks`: (item, first triangle) per workgroup, RR_ITEM_CHUNK triangles each, laid out by
 // rr_scene_create: a mesh of a million triangles is 123 workgroups, not one).
 #define RR_ITEM_CHUNK 8192u
-// Triangle `slot` of mesh item `it`: both signs of its flat normal through the item's transform
+// Triangle `slot` of mesh item `it`: both signs of its flat normal through the item's transform, each with its tangent frame
+RR_DEV void flat_world_entry(f3 n, float4* e) {
+    const TangentFrame f = tangent_frame(n);
+    e[0] = make_float4(n.x, n.y, n.z, 0.0f);
+    e[1] = make_float4(f.tangent.x, f.tangent.y, f.tangent.z, 0.0f);
+    e[2] = make_float4(f.bitangent.x, f.bitangent.y, f.bitangent.z, 0.0f);
+}
 RR_DEV void flat_world_normals(const DItem& it, uint32_t slot, const DTri* tris, float4* out) {
     const float4 v3 = tris[it.tri_base + slot].v3;
     const f3 ng = mk3(v3.x, v3.y, v3.z);
-    const f3 p = to_world_normal(it, ng), m = to_world_normal(it, -ng);
-    out[it.wn_base + 2u * slot] = make_float4(p.x, p.y, p.z, 0.0f);
-    out[it.wn_base + 2u * slot + 1u] = make_float4(m.x, m.y, m.z, 0.0f);
+    float4* const e = out + (uint64_t)(it.wn_base + 2u * slot) * RR_FLAT_ENTRY_F4;
+    flat_world_entry(to_world_normal(it, ng), e);
+    flat_world_entry(to_world_normal(it, -ng), e + RR_FLAT_ENTRY_F4);
 }
 __global__ __launch_bounds__(RR_BLOCK) void k_world_normals(const DItem* __restrict__ items, const uint2* __restrict__ chunks, const DTri* __restrict__ tris, float4* __restrict__ out) {
     const uint2 ch = chunks[blockIdx.x];
@@ -698,7 +704,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_world_normals(const DItem* __restr
 // The flat world normals of an EDITED item list (rr_scene_set_items), into the new arena: one workgroup per chunk of the new chunk
 // map, as k_world_normals.  An item whose matrices, mesh records and flag word are bit for bit those of an item of the list before
 // (rr_scene_build.h: plan_item_reuse) takes that item's normals -- chunk_src[chunk] = the old item's wn_base: the chunk's run of
-// 2 * triangles float4 is copied from `old` at the same offset behind that base -- and every other chunk (RR_CHUNK_DERIVE) evaluates
+// 2 * triangles entries is copied from `old` at the same offset behind that base -- and every other chunk (RR_CHUNK_DERIVE) evaluates
 // them as k_world_normals does.  The copied bits are those the evaluation gives: it is a pure function of what was compared.
 // The host bounds both runs: a kept item has the triangle count of the old one, whose run lies inside the old arena.
 #define RR_CHUNK_DERIVE 0xffffffffu // never a wn_base: bases are even
@@ -710,7 +716,8 @@ __global__ __launch_bounds__(RR_BLOCK) void k_world_normals_edit(const DItem* __
     const uint32_t end = min(it.n_tris, ch.y + RR_ITEM_CHUNK);
     const uint32_t src = chunk_src[blockIdx.x];
     if (src != RR_CHUNK_DERIVE) {
-        for (uint32_t k = 2u * ch.y + threadIdx.x; k < 2u * end; k += blockDim.x) out[it.wn_base + k] = old[src + k];
+        const uint64_t per_tri = 2ull * RR_FLAT_ENTRY_F4, to = (uint64_t)it.wn_base * RR_FLAT_ENTRY_F4, from = (uint64_t)src * RR_FLAT_ENTRY_F4;
+        for (uint64_t k = per_tri * ch.y + threadIdx.x; k < per_tri * end; k += blockDim.x) out[to + k] = old[from + k];
         return;
     }
     for (uint32_t slot = ch.y + threadIdx.x; slot < end; slot += blockDim.x) flat_world_normals(it, slot, tris, out);
@@ -2337,6 +2344,9 @@ __global__ __launch_bounds__(RR_BLOCK) void k_motion_records(const TpFrame f, co
 // kernel 8: device self-test of the arithmetic contract (tests/test_device_math.py)
 // op: 0 sincos -> (sin, cos); 1 acos; 2 atan2(a, b); 3 a / b; 4 sqrt(a); 5 jitter(dir = (a, b, c)); 7 cos(a * pi) as jitter() needs it
 // (op 6 is the HOST build of the same rr_cos, rr_api_probe.h rr_math_probe)
+// op 12: philox4x32_10 of caller-given words, as bit patterns: n = 2 m, entry i < m has the counter (a[i], b[i], c[i], a[m + i]) = (pixel,
+// sample, node, stream) and the key (seed_lo, seed_hi); out0[i], out1[i] = the two words jitter() uses.  (op 14 is the HOST build of the same
+// function, rr_api_probe.h.)
 // ---------------------------------------------------------------------------
 __global__ void k_math_probe(int op, const float* a, const float* b, const float* c, int n, float* out0, float* out1, float* out2,
                              uint32_t seed_lo, uint32_t seed_hi) {
@@ -2361,5 +2371,13 @@ __global__ void k_math_probe(int op, const float* a, const float* b, const float
         RngKey k; k.seed_lo = seed_lo; k.seed_hi = seed_hi; k.pixel = (uint32_t)i; k.sample = (uint32_t)(i & 7); k.node = 1u + (uint32_t)(i % 5);
         f3 r = jitter(mk3(a[i], b[i], c[i]), 0.05f, rr_cos(0.05f * RR_PI_F), k, (uint32_t)(i % 3));
         out0[i] = r.x; out1[i] = r.y; out2[i] = r.z;
+    }
+    else if (op == 12) {
+        const int m = n / 2;
+        if (i < m) {
+            uint32_t r0, r1;
+            philox4x32_10(__float_as_uint(a[i]), __float_as_uint(b[i]), __float_as_uint(c[i]), __float_as_uint(a[m + i]), seed_lo, seed_hi, &r0, &r1);
+            out0[i] = __uint_as_float(r0); out1[i] = __uint_as_float(r1);
+        }
     }
 }

@@ -171,15 +171,20 @@ RR_DEV float rr_atan2(float y, float x) {
 }
 
 // ---- Philox4x32-10: the counter-based generator behind jitter() ----------------------------
-#ifndef __HIPCC__ // a plain host compiler (the native tests of the host-only headers) has no such builtin
-static inline uint32_t __umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
-#endif
-RR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                          uint32_t* r0, uint32_t* r1) {
+// A round needs both words of two 32 x 32 products.  Written as one 64-bit product each: on gfx950 that is one v_mad_u64_u32 (4.4
+// cycles of the vector port) where __umulhi and `*` were a v_mul_hi_u32 / v_mul_lo_u32 pair (2 x 4.25 cycles;
+// profiles/r22_valu_issue_int_mul.txt).  The words are the same.
+RR_HD void mul_hi_lo(uint32_t a, uint32_t b, uint32_t* hi, uint32_t* lo) {
+    const uint64_t p = (uint64_t)a * (uint64_t)b;
+    *hi = (uint32_t)(p >> 32); *lo = (uint32_t)p;
+}
+RR_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                         uint32_t* r0, uint32_t* r1) {
 #pragma unroll
     for (int r = 0; r < 10; r++) {
-        uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        uint32_t hi0, lo0, hi1, lo1;
+        mul_hi_lo(0xD2511F53u, c0, &hi0, &lo0);
+        mul_hi_lo(0xCD9E8D57u, c2, &hi1, &lo1);
         uint32_t n0 = hi1 ^ c1 ^ k0;
         uint32_t n2 = hi0 ^ c3 ^ k1;
         c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;

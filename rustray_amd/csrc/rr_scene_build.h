@@ -503,6 +503,10 @@ static void plan_item_reuse(const std::vector<DItem>& old_items, const std::vect
     }
 }
 
+// The size of DSceneView::flat_normals for `n_entries` entries (ItemRecords::n_flat_normals: at most 2^32): RR_FLAT_ENTRY_F4 float4 each --
+// normal, tangent, bitangent --, and an empty table still gets a buffer.
+inline size_t flat_normals_bytes(uint64_t n_entries) { return std::max<size_t>((size_t)n_entries * RR_FLAT_ENTRY_F4 * sizeof(float4), sizeof(float4)); }
+
 // The chunk map of an item list: (item, first triangle) per workgroup of k_world_normals / k_item_spans, RR_HOST_ITEM_CHUNK triangles
 // each; every item has at least one chunk, and the chunks of one item are consecutive.
 #define RR_HOST_ITEM_CHUNK 8192u // = RR_ITEM_CHUNK of rr_kernels.hip (rr_api_scene.h asserts it)

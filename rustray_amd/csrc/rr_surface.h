@@ -6,7 +6,7 @@
 // Offers: c_u8_to_f32 (filled by rr_api_scene.h rr_scene_create); texel, tex_wrap, tex_bilinear, MatR, load_material, uniform_row, load_material_uniform,
 // tex_color (both forms); item_color; area_weights (both forms), sphere_uv, mesh_uv; RngKey, jitter; fresnel; HitItem, load_hit_item,
 // load_hit_item_uniform; the steps of a hit's surface (HitWeights, hit_normal, hit_uv, mapped_normal, roughness_spread, hit_colors,
-// hit_reflectivity, hit_ambient_occlusion) and their composition (SurfaceAt, surface_at).  No macros.
+// hit_reflectivity, tangent_frame, hit_ambient_occlusion) and their composition (SurfaceAt, surface_at).  No macros.
 // Needs: rr_primitives.h (to_local_point, inverse_ray, ray_ball, to_world_normal), rr_walk.h (rr_global), rr_trace.h (ray_nonfinite).
 #pragma once
 #include "rr_walk.h"
@@ -226,6 +226,15 @@ RR_DEV HitItem load_hit_item_uniform(const DItem* items, int idx) {
 // The area weights of a mesh hit and its triangle's attributes: they serve the interpolated normal AND the uv (Mesh::get_normal and
 // Mesh::get_uv compute the same three numbers from the same inputs, src/shape/mesh.rs:105-161, :204-259)
 struct HitWeights { DTriAttr at; float a1, a2, a3; bool have; };
+// The entry of DSceneView::flat_normals that holds a hit's world normal (`hit_z`: the walks' face word, as hit_normal reads it) -- a
+// flat-shaded triangle of an item that does not flip normals --, else RR_NO_FRAME: mapped_normal takes the entry's tangent frame instead
+// of deriving it from the normal.  (A flipped normal is not an entry's: zeros of the frame of -n differ in sign from the negated frame
+// of n, so that frame is derived per hit.)
+#define RR_NO_FRAME 0xffffffffu
+RR_DEV uint32_t flat_frame_entry(const HitItem& hi, uint32_t hit_z) {
+    if (hi.flags & (RR_IF_SPHERE | RR_IF_SMOOTH | RR_IF_FLIP_NORMALS)) return RR_NO_FRAME;
+    return hi.wn_base + 2u * (hit_z & 0x3fffffffu) + ((hit_z >> 30) & 1u);
+}
 
 // World normal: Shape::intersect (mesh.rs:76-98, sphere.rs:61-65).  `hi`: the caller's register copies of the item's words (HitItem);
 // `hit_z`: the walks' face word (leaf-order slot | negated << 30 | back << 31); `gw`: DSceneView::general_w.
@@ -257,7 +266,8 @@ RR_DEV f3 hit_normal(const DSceneView& sc, const DItem& it, const HitItem& hi, c
             if (back) normal = -normal;
         } else {
             // to_world_normal(it, neg ? -ng : ng) with ng = DTri::v3, evaluated once per instanced triangle by k_world_normals
-            const float4 wn = rr_global(sc.flat_normals)[hi.wn_base + 2u * slot + (neg ? 1u : 0u)];
+            const uint32_t entry = hi.wn_base + 2u * slot + (neg ? 1u : 0u);
+            const float4 wn = rr_global(sc.flat_normals)[(uint64_t)entry * RR_FLAT_ENTRY_F4];
             normal = mk3(wn.x, wn.y, wn.z);
         }
         if (it_flags & RR_IF_FLIP_NORMALS) normal = -normal;
@@ -279,15 +289,30 @@ RR_DEV bool hit_uv(const DItem& it, uint32_t it_flags, const MatR& m, f3 hit_poi
     *uv_out = uv;
     return has_uv;
 }
-// normal mapping (:757-784): `normal` where the material has no normal map
-RR_DEV f3 mapped_normal(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, f3 normal) {
+// The tangent frame of normal mapping (:757-784): a function of the normal alone.  k_world_normals evaluates it once per entry of
+// DSceneView::flat_normals, mapped_normal per hit for the normals that are not such an entry's.
+struct TangentFrame { f3 tangent, bitangent; };
+RR_DEV TangentFrame tangent_frame(f3 normal) {
+    f3 tangent = cross3(normal, mk3(0.0f, 1.0f, 0.0f));
+    if (norm3(tangent) <= 0.0001f) tangent = cross3(normal, mk3(0.0f, 0.0f, 1.0f));
+    TangentFrame f;
+    f.tangent = normalize3(tangent);
+    f.bitangent = normalize3(cross3(normal, f.tangent));
+    return f;
+}
+// normal mapping (:757-784): `normal` where the material has no normal map.  `frame_entry`: flat_frame_entry of the hit, or RR_NO_FRAME
+// (smooth-shaded and sphere hits, flipped normals, a caller without a table): the frame is then derived here.
+RR_DEV f3 mapped_normal(const DSceneView& sc, const MatR& m, bool has_uv, f2 uv, f3 normal, uint32_t frame_entry) {
     f3 surface_normal = normal;
     float4 tc;
     if (tex_color(sc, m, has_uv, uv, 3, &tc)) {
-        f3 tangent = cross3(normal, mk3(0.0f, 1.0f, 0.0f));
-        if (norm3(tangent) <= 0.0001f) tangent = cross3(normal, mk3(0.0f, 0.0f, 1.0f));
-        tangent = normalize3(tangent);
-        f3 bitangent = normalize3(cross3(normal, tangent));
+        TangentFrame f;
+        if (frame_entry != RR_NO_FRAME) {
+            const float4* e = &rr_global(sc.flat_normals)[(uint64_t)frame_entry * RR_FLAT_ENTRY_F4];
+            const float4 t = e[1], b = e[2];
+            f.tangent = mk3(t.x, t.y, t.z); f.bitangent = mk3(b.x, b.y, b.z);
+        } else f = tangent_frame(normal);
+        const f3 tangent = f.tangent, bitangent = f.bitangent;
         f3 nm = mk3((tc.x * 2.0f) - 1.0f, (tc.y * 2.0f) - 1.0f, (tc.z * 2.0f) - 1.0f);
         nm.x *= m.normal_map_strength; nm.y *= m.normal_map_strength;
         nm = normalize3(nm);
@@ -349,7 +374,7 @@ RR_DEV SurfaceAt surface_at(const DSceneView& sc, const DItem& it, const MatR& m
     s.position = ro + (rd * hit_dist);
     s.normal = hit_normal(sc, it, hi, m, ro, rd, s.position, hit_z, gw, &w);
     s.has_uv = hit_uv(it, it_flags, m, s.position, gw, w, &s.uv);
-    s.shading_normal = mapped_normal(sc, m, s.has_uv, s.uv, s.normal);
+    s.shading_normal = mapped_normal(sc, m, s.has_uv, s.uv, s.normal, flat_frame_entry(hi, hit_z));
     roughness_spread(sc, m, s.has_uv, s.uv, &s.roughness);
     const HitColors c = hit_colors(sc, m, s.has_uv, s.uv);
     s.ambient_color = c.ambient; s.base_color = c.base; s.specular_color = c.specular; s.alpha = c.alpha;

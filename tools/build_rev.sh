@@ -7,5 +7,7 @@ mkdir -p $d/rustray_amd/csrc $d/include build/variants
 # the files of THAT revision (today's names are wrong for an older one)
 for f in $(git ls-tree --name-only $rev rustray_amd/csrc/); do git show $rev:$f > $d/$f; done
 git show $rev:include/rustray_hip.h > $d/include/rustray_hip.h
-(cd $d/rustray_amd/csrc && hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 "$@" -shared -o $OLDPWD/build/variants/lib_$name.so rr_api.hip rr_bvh.cpp)
+# with THAT revision's flags (the Makefile's FLAGS line)
+flags=$(sed -n 's/^FLAGS ?= //p' $d/rustray_amd/csrc/Makefile | sed 's/\$(ARCH)/gfx950/')
+(cd $d/rustray_amd/csrc && hipcc $flags "$@" -shared -o $OLDPWD/build/variants/lib_$name.so rr_api.hip rr_bvh.cpp)
 rm -rf $d

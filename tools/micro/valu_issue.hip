@@ -22,6 +22,11 @@ __global__ void k(float* out, unsigned long long* stamps, float a, float b) {
     float x0 = threadIdx.x, x1 = a, x2 = b, x3 = a + b, x4 = 1, x5 = 2, x6 = 3, x7 = 4;
     v2f p0{x0, x1}, p1{x2, x3}, p2{x4, x5}, p3{x6, x7};
     const v2f pa{a, a}, pb{b, b};
+    // the integer kinds (the generator behind jitter(): philox4x32_10, rr_math.h): per-lane words, 64-bit accumulators, and wave-uniform words
+    unsigned u0 = threadIdx.x * 2654435761u + 1u, u1 = u0 ^ 0x9E3779B9u, u2 = u0 + 0xBB67AE85u, u3 = ~u0;
+    unsigned long long q0 = u0, q1 = u1, q2 = u2, q3 = u3;
+    const unsigned ua = __float_as_uint(a) | 0xD2511F53u, ub = __float_as_uint(b) | 0xCD9E8D57u; // (uniform: kernel arguments)
+    unsigned s0 = ua, s1 = ub, s2 = ua ^ ub, s3 = ua + ub;
     __syncthreads();
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (int it = 0; it < ITER; it++) {
@@ -53,11 +58,25 @@ __global__ void k(float* out, unsigned long long* stamps, float a, float b) {
                 asm volatile("v_pk_fma_f32 %0, %0, %4, %5\n v_pk_fma_f32 %1, %1, %4, %5\n v_pk_fma_f32 %2, %2, %4, %5\n v_pk_fma_f32 %3, %3, %4, %5" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3) : "v"(pa), "v"(pb));
             } else if (KIND == 12) { // v_min_f32 / v_max_f32 (VOP2)
                 asm volatile("v_min_f32 %0, %0, %4\n v_max_f32 %1, %1, %5\n v_min_f32 %2, %2, %4\n v_max_f32 %3, %3, %5" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(a), "v"(b));
+            } else if (KIND == 13) { // v_mul_lo_u32, 4 independent chains
+                asm volatile("v_mul_lo_u32 %0, %0, %4\n v_mul_lo_u32 %1, %1, %4\n v_mul_lo_u32 %2, %2, %4\n v_mul_lo_u32 %3, %3, %4" : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3) : "v"(ua));
+            } else if (KIND == 14) { // v_mul_hi_u32
+                asm volatile("v_mul_hi_u32 %0, %0, %4\n v_mul_hi_u32 %1, %1, %4\n v_mul_hi_u32 %2, %2, %4\n v_mul_hi_u32 %3, %3, %4" : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3) : "v"(ua));
+            } else if (KIND == 15) { // v_mad_u64_u32: a product's high and low word at once (the 64-bit addend is the chain)
+                asm volatile("v_mad_u64_u32 %0, vcc, %4, %5, %0\n v_mad_u64_u32 %1, vcc, %4, %5, %1\n v_mad_u64_u32 %2, vcc, %4, %5, %2\n v_mad_u64_u32 %3, vcc, %4, %5, %3"
+                             : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3) : "v"(ua), "v"(ub) : "vcc");
+            } else if (KIND == 16) { // v_xor_b32 (VOP2)
+                asm volatile("v_xor_b32 %0, %0, %4\n v_xor_b32 %1, %1, %4\n v_xor_b32 %2, %2, %4\n v_xor_b32 %3, %3, %4" : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3) : "v"(ua));
+            } else if (KIND == 17) { // s_mul_hi_u32 (SALU), 4 independent chains
+                asm volatile("s_mul_hi_u32 %0, %0, %4\n s_mul_hi_u32 %1, %1, %4\n s_mul_hi_u32 %2, %2, %4\n s_mul_hi_u32 %3, %3, %4" : "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3) : "s"(ua));
+            } else if (KIND == 18) { // the pair one product costs today: v_mul_hi_u32 + v_mul_lo_u32 of the same operands
+                asm volatile("v_mul_hi_u32 %0, %1, %4\n v_mul_lo_u32 %1, %1, %4\n v_mul_hi_u32 %2, %3, %4\n v_mul_lo_u32 %3, %3, %4" : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3) : "v"(ua));
             }
         }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (x0 + x1 + x2 + x3 + p0.x + p1.x + p2.x + p3.x + p0.y == 12345.678f) out[0] = 1;
+    if ((u0 ^ u1 ^ u2 ^ u3 ^ s0 ^ s1 ^ s2 ^ s3 ^ (unsigned)(q0 ^ q1 ^ q2 ^ q3) ^ (unsigned)((q0 ^ q1 ^ q2 ^ q3) >> 32)) == 0x12345678u) out[1] = 1;
     if ((threadIdx.x & 63) == 0) { const int w = blockIdx.x * 16 + threadIdx.x / 64; stamps[2 * w] = t1 - t0; stamps[2 * w + 1] = r1 - r0; }
 }
 static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
@@ -89,5 +108,8 @@ int main() {
     run<9>("v_mul_f32 independent (VOP2)", d, stamps); run<7>("v_sub/v_mul plain (VOP2)", d, stamps); run<12>("v_min/v_max (VOP2)", d, stamps);
     run<1>("v_pk_mul_f32", d, stamps); run<2>("v_pk_add_f32", d, stamps); run<11>("v_pk_fma_f32", d, stamps); run<3>("v_max3_f32", d, stamps);
     run<4>("v_cmp+v_cndmask", d, stamps); run<5>("v_mul_f32 dependent", d, stamps); run<6>("s_add_u32", d, stamps);
+    // the integer multiplies of philox4x32_10 (every figure is per instruction: a product costs two of the pair's, one v_mad_u64_u32)
+    run<13>("v_mul_lo_u32", d, stamps); run<14>("v_mul_hi_u32", d, stamps); run<18>("v_mul_hi_u32 + v_mul_lo_u32 pair", d, stamps); run<15>("v_mad_u64_u32", d, stamps);
+    run<16>("v_xor_b32 (VOP2)", d, stamps); run<17>("s_mul_hi_u32", d, stamps);
     return 0;
 }

@@ -2,7 +2,7 @@
 # Developer tool: register / spill / scratch / LDS table of the kernels of rr_api.hip for a set of -D flags (cross-compiles, no GPU).
 # usage: tools/resusage.sh [-DRR_TRACE_WAVES=3 ...]   (the knobs: the block at the top of rustray_amd/csrc/rr_kernels.hip)
 cd "$(dirname "$0")/../rustray_amd/csrc"
-hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -Wno-unused-function "$@" -Rpass-analysis=kernel-resource-usage -c rr_api.hip -o /dev/null 2>&1 | python3 -c "
+hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize --offload-arch=gfx950 -Wno-unused-function "$@" -Rpass-analysis=kernel-resource-usage -c rr_api.hip -o /dev/null 2>&1 | python3 -c "
 import re, sys
 cur = None; rows = {}
 for line in sys.stdin:

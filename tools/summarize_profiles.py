@@ -22,9 +22,11 @@ KERNELS = ("k_trace_closest", "k_trace_closest<true>", "k_trace_closest<false>",
 
 
 def kname(raw):
-    """'void k_shade<true>(DSceneView, ...)' -> 'k_shade<true>'"""
+    """'void k_shade<true>(DSceneView, ...)' -> 'k_shade<true>'; the frame's builds of the kernels that also have a split build,
+    'k_shade<true, false>', keep the name they had before that second parameter: 'k_shade<true>'"""
     n = raw.split("(")[0].strip()
-    return n[5:] if n.startswith("void ") else n
+    n = n[5:] if n.startswith("void ") else n
+    return n.replace(", false>", ">")
 
 
 def with_totals(d, combine):

@@ -6,5 +6,5 @@ set -e
 name=$1; shift
 cd "$(dirname "$0")/../rustray_amd/csrc"
 mkdir -p ../../build/variants
-hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -Wall -Wno-unused-function "$@" -shared -o ../../build/variants/lib_$name.so rr_api.hip rr_bvh.cpp
+hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize --offload-arch=gfx950 -Wall -Wno-unused-function "$@" -shared -o ../../build/variants/lib_$name.so rr_api.hip rr_bvh.cpp
 echo "built build/variants/lib_$name.so ($*)"
