@@ -62,7 +62,9 @@ extern "C" {
  * rr_render_pixel_split, rr_render_pixel_split_device, rr_denoise_split_records and rr_denoise_split_records_device came after those in the
  * same way: a version-3 library may lack these four as well.
  * rr_accumulate_split_records and rr_accumulate_split_records_device came after those in the same way: a version-3 library may lack
- * these two as well. */
+ * these two as well.
+ * rr_history_clamp_default_params, rr_accumulate_clamped_records and rr_accumulate_clamped_records_device (with rr_history_clamp_params, a
+ * struct of its own) came after those, again without a change of any existing struct: a version-3 library may lack these three as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1170,6 +1172,76 @@ int rr_accumulate_split_records(rr_scene* scene, const rr_camera* camera, const 
                                 rr_radiance* out /* n */, rr_radiance* halves_out /* 2n, or NULL */,
                                 float* diffuse_out /* 3n */, float* diffuse_halves_out /* 6n, or NULL */,
                                 float* length_out /* n */, uint8_t* rgba8_out /* or NULL */);
+
+/* Temporal accumulation with the history held to the current frame's colours (neighbourhood variance clipping): rr_accumulate_records,
+ * and before the blend each history mean is clamped to the box mean +- sigma_scale * sd of the current frame's colours in a 3x3 or 5x5
+ * window around the pixel; where the record's history had to be moved, the length is shortened.  rr_accumulate_records decides from id,
+ * normal and depth alone, so an edit that moves no geometry -- rr_scene_update_lights, rr_scene_update_materials,
+ * rr_scene_add_textures, rr_scene_update_item_flags, a moved item's shadow or mirror image on a surface that stood still -- leaves the
+ * stale colour in the blend for up to max_history frames; this call lets it go within a few.  The price is a bias towards the current
+ * frame's noise in a static view (DESIGN.md has the measured figures).  rr_accumulate_params is rr_accumulate_records'.
+ * EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE (rustray_amd/temporal.py: accumulate_clamped_records follows this text in numpy
+ * and gives the same bits).  Steps 1 .. 6 are rr_accumulate_records' up to and including N and a; a pixel that reaches the end of step 6
+ * with its means h (of the records), ha, hb (of the halves, when given), N and a goes on:
+ *   7. Window.  r = radius.  The pixels q = (x + dx, y + dy) are visited with dy = -r .. r outside and dx = -r .. r inside, ascending.  q
+ *      is taken when it lies inside the frame and the three colour floats of records[q] are finite; id, normal and depth are not looked
+ *      at (p itself is always taken: fin_p holds).  Starting from 0: m += 1 (an integer); per channel s1 += c and s2 += c * c, the
+ *      product rounded first.  Then per channel mean = s1 / (float)m; v = s2 / (float)m - mean * mean; sd = sqrtf(v > 0 ? v : 0) (a NaN
+ *      gives 0); e = sigma_scale * sd; lo = mean - e; hi = mean + e.  There is one box per pixel, from the full records: the halves are
+ *      clamped to the same box.
+ *      A channel in which s2 / (float)m, mean * mean or e is not finite HAS NO BOX: lo = -inf, hi = +inf, and nothing is moved in it.
+ *      That settles every overflow: an s2 that overflowed (one colour above about 1.85e19), whether mean * mean is still finite
+ *      (v = inf) or overflowed as well (v = inf - inf, a NaN, which without this rule would give sd = 0 and a box that is the point
+ *      `mean`, dragging the history of every pixel of the window to it); an s1 that overflowed (an infinite mean); an e that did.
+ *   8. Clamp.  Per layer (h, ha, hb) and channel: h' = h < lo ? lo : (h > hi ? hi : h).  A NaN mean stays.
+ *   9. Length.  Only the record layer decides.  If no channel of h was moved, N and a are step 6's.  Otherwise per channel
+ *      u_c = fabsf(h_c - h'_c) / (e_c + EPS) where the channel was moved and 0 where not; t = max(max(u_0, u_1), u_2), each max(a, b)
+ *      being a > b ? a : b; keep = 1.0f / (1.0f + t); N = (N - 1.0f) * keep + 1.0f; a = 1.0f / N.  (e_c of a moved channel is finite
+ *      and >= 0, so u_c is >= 0 or +inf, keep lies in [0, 1] and the new N in [1, N]: no NaN arises.)
+ *   10. Blend.  As step 6, with h', ha', hb' and the new a: out.color = h' + a * (cur - h') per channel, each half with its own clamped
+ *      half-history; a current half whose colour is not finite keeps its bits.  length_out[p] = N.
+ *   What follows from that and the tests hold: every no-history path (the first frame, !fin_p, !valid_p, step 3, sum_w < 2^-6) writes
+ *   rr_accumulate_records' bits.  A pixel in which no channel of any layer leaves its box writes rr_accumulate_records' bits in every
+ *   output.  A pixel in which only a half leaves the box differs from rr_accumulate_records' answer in that half alone.  Depth, normal
+ *   and object_id of every output record are the bits of the current record of that layer.  sigma_scale 0 pulls every history mean
+ *   onto the window's mean.
+ * rr_history_clamp_params: struct_size = sizeof(rr_history_clamp_params); radius 1 (3x3) or 2 (5x5); sigma_scale finite, 0 .. 65536.
+ * rr_history_clamp_default_params writes radius 1 and sigma_scale 0.5 (chosen by measurement: DESIGN.md section 8, item 24); it never
+ * touches a device.
+ * rr_accumulate_clamped_records_device: the arguments of rr_accumulate_records_device behind `clamp`, with its pairing rules.
+ *   The call follows rr_accumulate_records_device: every pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming the
+ *   argument; pageable memory is refused); the record pointers 16-byte aligned, the others 4-byte aligned; ONE launch (and one for the
+ *   bytes) enqueued on `hip_stream` in stream order, not waited for; the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same
+ *   scene; nothing of a frame's state or statistics is touched.  The call keeps no device memory.
+ *   out_dev MAY NOT OVERLAP records_dev AT ALL, not even in place: the window reads the records of other pixels, which another
+ *   workgroup may already have overwritten.  RR_ERR_INVALID_ARGUMENT, and rr_last_error names both and says why.  halves_out_dev ==
+ *   halves_dev stays allowed: halves are read at p only.  Every other overlap between an output and an input, or between two outputs, is
+ *   RR_ERR_INVALID_ARGUMENT naming both.
+ *   Refusals: those of rr_accumulate_records_device; a NULL clamp; a clamp->struct_size other than sizeof(rr_history_clamp_params); a
+ *   radius other than 1 or 2; a sigma_scale that is NaN, infinite, negative or above 65536: RR_ERR_INVALID_ARGUMENT naming the field and
+ *   the function.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ * rr_accumulate_clamped_records: the same on HOST pointers (out may not overlap records there either), the device form on the null
+ * stream behind staging copies in the handle's pool, ten arrays of rr_accumulate_records' sizes; it returns with the outputs written. */
+typedef struct rr_history_clamp_params {
+    uint32_t struct_size;   /* sizeof(rr_history_clamp_params) */
+    uint32_t radius;        /* 1 or 2: a 3x3 or a 5x5 window of the CURRENT frame */
+    float    sigma_scale;   /* k: finite, 0 .. 65536 */
+} rr_history_clamp_params;
+int rr_history_clamp_default_params(rr_history_clamp_params* out);
+int rr_accumulate_clamped_records_device(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                                         const rr_history_clamp_params* clamp,
+                                         const rr_radiance* records_dev /* n */, const rr_radiance* halves_dev /* 2n, or NULL */,
+                                         const rr_radiance* history_dev /* n, or NULL */, const rr_radiance* history_halves_dev /* 2n, or NULL */,
+                                         const float* history_length_dev /* n, or NULL */, const float* motion_dev /* 3n, or NULL */,
+                                         rr_radiance* out_dev /* n; not records_dev */, rr_radiance* halves_out_dev /* 2n, or NULL */,
+                                         float* length_out_dev /* n */, uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream);
+int rr_accumulate_clamped_records(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                                  const rr_history_clamp_params* clamp,
+                                  const rr_radiance* records /* n */, const rr_radiance* halves /* 2n, or NULL */,
+                                  const rr_radiance* history /* n, or NULL */, const rr_radiance* history_halves /* 2n, or NULL */,
+                                  const float* history_length /* n, or NULL */, const float* motion /* 3n, or NULL */,
+                                  rr_radiance* out /* n; not records */, rr_radiance* halves_out /* 2n, or NULL */, float* length_out /* n */,
+                                  uint8_t* rgba8_out /* or NULL */);
 
 /* The motion of moved items per pixel: what rr_accumulate_records takes as motion when items moved between the frame the history was
  * rendered from and the current one (rr_scene_update_transforms, rr_scene_set_items), computed on the device from the records it holds.

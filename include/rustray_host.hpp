@@ -883,6 +883,49 @@ public:
                                             out_dev, halves_out_dev, length_out_dev, rgba8_out_dev, hip_stream);
     }
 
+    // The clamp of accumulate_clamped(): rr_history_clamp_params with the library's defaults filled in.
+    struct HistoryClamp : rr_history_clamp_params {
+        HistoryClamp() { rr_history_clamp_default_params(this); }
+        HistoryClamp(uint32_t radius_, float sigma_scale_) {
+            rr_history_clamp_default_params(this);
+            radius = radius_;
+            sigma_scale = sigma_scale_;
+        }
+    };
+    // accumulate() with the history held to the current frame's colours around each pixel (rr_accumulate_clamped_records): for the frames
+    // after an edit that moves no geometry -- lights, materials, textures, item flags -- and under moving shadows, where accumulate()
+    // would blend the stale colour in for up to max_history frames.  The arguments are accumulate()'s behind `clamp`.
+    History accumulate_clamped(const HistoryClamp& clamp, const rr_radiance* records, const rr_radiance* halves, const History* history,
+                               const rr_accumulate_params* params = nullptr, const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+        History out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_accumulate_params prm;
+        if (params) prm = *params;
+        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
+        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
+        const bool first = !history || history->empty();
+        const rr_camera cam = camera.c_struct();
+        out.records.resize(n);
+        out.length.assign(n, 0.0f);
+        if (halves) out.halves.resize(2 * n);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_accumulate_clamped_records(scene->handle(), &cam, &prm, &clamp, records, halves, first ? nullptr : history->records.data(),
+                                          first || history->halves.empty() ? nullptr : history->halves.data(), first ? nullptr : history->length.data(), motion,
+                                          out.records.data(), halves ? out.halves.data() : nullptr, out.length.data(), rgba8 ? rgba8->data() : nullptr) != RR_OK) {
+            out = History();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_accumulate_clamped_records_device): not waited for; out_dev may not be records_dev
+    int accumulate_clamped_device(const rr_accumulate_params& params, const HistoryClamp& clamp, const rr_radiance* records_dev, const rr_radiance* halves_dev,
+                                  const rr_radiance* history_dev, const rr_radiance* history_halves_dev, const float* history_length_dev, const float* motion_dev,
+                                  rr_radiance* out_dev, rr_radiance* halves_out_dev, float* length_out_dev, uint8_t* rgba8_out_dev, void* hip_stream) const {
+        const rr_camera cam = camera.c_struct();
+        return rr_accumulate_clamped_records_device(scene->handle(), &cam, &params, &clamp, records_dev, halves_dev, history_dev, history_halves_dev,
+                                                    history_length_dev, motion_dev, out_dev, halves_out_dev, length_out_dev, rgba8_out_dev, hip_stream);
+    }
+
     // What accumulate_split() returns and takes back: History plus the accumulated diffuse layers of rr_render_pixel_split.
     struct SplitHistory : History {
         std::vector<float> diffuse, diffuse_halves; // width * height * 3, and twice as many (empty: no halves)

@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_accumulate_split_records", "rr_accumulate_split_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_accumulate_split_records", "rr_accumulate_split_records_device", "rr_history_clamp_default_params", "rr_accumulate_clamped_records", "rr_accumulate_clamped_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -43,6 +43,11 @@ class rr_accumulate_params(C.Structure):
                 ("normal_min", C.c_float), ("sigma_depth", C.c_float), ("snap", C.c_float), ("gamma_correction", C.c_uint32)]
 
 
+class rr_history_clamp_params(C.Structure):
+    """include/rustray_hip.h: the clamp parameters of rr_accumulate_clamped_records."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("sigma_scale", C.c_float)]
+
+
 class RustrayHipError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rustray_hip error {code}: {msg}")
@@ -55,7 +60,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
 LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_history_clamp.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -191,6 +196,11 @@ def lib():
         if hasattr(L, "rr_accumulate_split_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
             L.rr_accumulate_split_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 16
             L.rr_accumulate_split_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 17
+        if hasattr(L, "rr_accumulate_clamped_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
+            L.rr_history_clamp_default_params.argtypes = [C.POINTER(rr_history_clamp_params)]
+            clamped = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params), C.POINTER(rr_history_clamp_params)]
+            L.rr_accumulate_clamped_records.argtypes = clamped + [C.c_void_p] * 10
+            L.rr_accumulate_clamped_records_device.argtypes = clamped + [C.c_void_p] * 11
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -283,6 +293,23 @@ def accumulate_params(params=None) -> rr_accumulate_params:
         p.max_history, p.normal_min = float(params.max_history), float(params.normal_min)
         p.sigma_depth, p.snap = float(params.sigma_depth), float(params.snap)
         p.gamma_correction = 1 if params.gamma_correction else 0
+    return p
+
+
+def history_clamp_default_params() -> rr_history_clamp_params:
+    """rr_history_clamp_default_params: the radius and sigma_scale DESIGN.md's sweep chose (never touches a device)."""
+    p = rr_history_clamp_params()
+    _check(lib().rr_history_clamp_default_params(C.byref(p)))
+    return p
+
+
+def history_clamp_params(clamp=None) -> rr_history_clamp_params:
+    """A temporal.HistoryClampParams (or None: the library's defaults) as the C struct; a C struct is passed through."""
+    if isinstance(clamp, rr_history_clamp_params):
+        return clamp
+    p = history_clamp_default_params()
+    if clamp is not None:
+        p.radius, p.sigma_scale = int(clamp.radius), float(clamp.sigma_scale)
     return p
 
 
@@ -955,6 +982,38 @@ class DeviceScene:
                                                         _ptr(history_diffuse_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
                                                         _ptr(halves_out_ptr), _ptr(diffuse_out_ptr), _ptr(diffuse_halves_out_ptr), _ptr(length_out_ptr),
                                                         _ptr(rgba8_ptr), _ptr(stream_ptr)))
+
+    def accumulate_clamped(self, cam: rr_camera, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
+                           clamp=None, rgba8: bool = False, halves_in_place: bool = False) -> dict:
+        """rr_accumulate_clamped_records: temporal.accumulate_clamped_records on the device, host arrays in and out.  The arguments of
+        accumulate_records, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  Returns dict(records (n, 8), length
+        (n,), halves (n, 2, 8) or None [, rgba (n, 4) uint8]); halves_in_place accumulates into a copy of `halves` (halves_out == halves;
+        out can never be records)."""
+        n = int(cam.width) * int(cam.height)
+        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
+        rec = arr(records, (n, 8))
+        hv = None if halves is None else (np.array(halves, np.float32, order="C").reshape(n, 2, 8) if halves_in_place else arr(halves, (n, 2, 8)))
+        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
+        out = np.zeros((n, 8), np.float32)
+        out_h = None if hv is None else (hv if halves_in_place else np.zeros((n, 2, 8), np.float32))
+        length = np.zeros(n, np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        p, c = accumulate_params(params), history_clamp_params(clamp)
+        _check(lib().rr_accumulate_clamped_records(self._h, C.byref(cam), C.byref(p), C.byref(c), _data(rec), _data(hv), _data(hist), _data(hist_h), _data(hist_l),
+                                                   _data(mv), _data(out), _data(out_h), _data(length), _data(rgba)))
+        res = dict(records=out, length=length, halves=out_h)
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def accumulate_clamped_device(self, cam: rr_camera, records_ptr, halves_ptr, history_ptr, history_halves_ptr, history_length_ptr, motion_ptr, out_ptr,
+                                  halves_out_ptr, length_out_ptr, rgba8_ptr=None, params=None, clamp=None, stream_ptr=None):
+        """rr_accumulate_clamped_records_device: the buffers of accumulate_records_device (out_ptr may NOT be records_ptr; halves_out_ptr
+        may be halves_ptr), all raw device pointers (None where the call has none); enqueued on `stream_ptr`, not waited for."""
+        p, c = accumulate_params(params), history_clamp_params(clamp)
+        _check(lib().rr_accumulate_clamped_records_device(self._h, C.byref(cam), C.byref(p), C.byref(c), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
+                                                          _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
+                                                          _ptr(halves_out_ptr), _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
 
     # -- the motion of moved items per pixel -------------------------------------------
     @staticmethod

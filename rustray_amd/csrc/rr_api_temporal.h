@@ -1,11 +1,13 @@
 // rr_api_temporal.h — temporal reprojection of a frame of records on the device: the previous call's result is gathered into the
 // current frame and the current records are blended into it, the step before rr_denoise_records in a frame-after-frame loop.
 // Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records, rr_accumulate_split_records_device,
-//         rr_accumulate_split_records; tp_frame (for rr_api_motion.h).
+//         rr_accumulate_split_records, rr_history_clamp_default_params, rr_accumulate_clamped_records_device,
+//         rr_accumulate_clamped_records; tp_frame (for rr_api_motion.h).
 // Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_temporal.h,
-//         kernel 7e of rr_kernels.hip.
+//         rr_history_clamp.h, kernels 7e, 7e' and 7e'' of rr_kernels.hip.
 //
-// The call is ONE launch of k_accumulate_records (with or without halves; the split call: of k_accumulate_split_records) and, for the
+// The call is ONE launch of k_accumulate_records (with or without halves; the split call: of k_accumulate_split_records; the clamped
+// call: of k_accumulate_clamped_records) and, for the
 // bytes, k_record_bytes, on the caller's stream, not waited for.  It keeps no working data.  The host form is the device form behind the staging of every record call
 // (staged_host_call, in the handle's pool).
 
@@ -81,15 +83,22 @@ static TpFrame tp_frame(const rr_camera* cam) {
     return f;
 }
 
-// the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
-// split: the diffuse layers of rr_accumulate_split_records (then the SPLIT build of the kernel runs), or NULL
-static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io, hipStream_t st, const TpSplitIo* split = nullptr) {
-    const uint32_t W = cam->width, H = cam->height;
+// the kernel argument of the three accumulation kernels: the camera, the previous view and the scalars of the call; and their grid of 32x8 tiles
+static TpFrame accumulate_frame(const rr_camera* cam, const rr_accumulate_params* prm) {
     TpFrame f = tp_frame(cam);
     memcpy(f.prev_clip, prm->prev_world_to_clip, sizeof f.prev_clip);
     memcpy(f.prev_eye, prm->prev_eye, sizeof f.prev_eye);
     f.max_history = prm->max_history; f.normal_min = prm->normal_min; f.sigma_depth = prm->sigma_depth; f.snap = prm->snap;
-    const dim3 grid((W + DN_TILE_W - 1) / DN_TILE_W, (H + DN_TILE_H - 1) / DN_TILE_H), block(RR_BLOCK);
+    return f;
+}
+static dim3 accumulate_grid(const rr_camera* cam) { return dim3((cam->width + DN_TILE_W - 1) / DN_TILE_W, (cam->height + DN_TILE_H - 1) / DN_TILE_H); }
+
+// the launches of one call on stream st, on buffers the device can address; the caller holds the lock and has taken the stream
+// split: the diffuse layers of rr_accumulate_split_records (then the SPLIT build of the kernel runs), or NULL
+static int accumulate_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const AccumulateIo& io, hipStream_t st, const TpSplitIo* split = nullptr) {
+    const uint32_t W = cam->width, H = cam->height;
+    const TpFrame f = accumulate_frame(cam, prm);
+    const dim3 grid = accumulate_grid(cam), block(RR_BLOCK);
     if (split) {
         if (io.halves)
             hipLaunchKernelGGL(k_accumulate_split_records<true>, grid, block, 0, st, f, (const float4*)io.records, (const float4*)io.halves, (const float4*)io.history,
@@ -208,3 +217,92 @@ int rr_accumulate_split_records(rr_scene* s, const rr_camera* camera, const rr_a
         });
     });
 } RR_GUARD_END("rr_accumulate_split_records")
+
+// ---- rr_accumulate_clamped_records: the same call with the history held to the box of the current frame's colours around each pixel
+int rr_history_clamp_default_params(rr_history_clamp_params* out) try {
+    if (!out) return fail(RR_ERR_INVALID_ARGUMENT, "rr_history_clamp_default_params: out is NULL");
+    memset(out, 0, sizeof *out);
+    out->struct_size = (uint32_t)sizeof(rr_history_clamp_params);
+    out->radius = 1u;        // chosen by measurement: DESIGN.md section 8, item 24
+    out->sigma_scale = 0.5f;
+    return RR_OK;
+} RR_GUARD_END("rr_history_clamp_default_params")
+
+// what the clamped call checks: rr_accumulate_records' rules with `out` allowed nowhere on `records` (the window reads other pixels'
+// records, which another workgroup may already have overwritten), and the clamp's own parameters
+static int check_accumulate_clamped_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm,
+                                         const rr_history_clamp_params* clamp, const AccumulateIo& io) {
+    RR_TRY(check_accumulate_basics(fn, device, s, cam, prm, io));
+    if (!clamp) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp is NULL", fn);
+    if (clamp->struct_size != sizeof(rr_history_clamp_params))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->struct_size %u, expected %u", fn, clamp->struct_size, (unsigned)sizeof(rr_history_clamp_params));
+    if (clamp->radius != 1u && clamp->radius != 2u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->radius %u, must be 1 or 2", fn, clamp->radius);
+    if (!(clamp->sigma_scale >= 0.0f && clamp->sigma_scale <= 65536.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->sigma_scale must lie in 0 .. 65536", fn);
+    const uint64_t n = (uint64_t)cam->width * cam->height;
+    const ArgRange t[10] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {io.history, 32u * n, "history", false, -1},
+                            {io.history_halves, 64u * n, "history_halves", false, -1}, {io.history_length, 4u * n, "history_length", false, -1},
+                            {io.motion, 12u * n, "motion", false, -1}, {io.out, 32u * n, "out", true, -1}, {io.halves_out, 64u * n, "halves_out", true, 1},
+                            {io.length_out, 4u * n, "length_out", true, -1}, {io.rgba8, 4u * n, "rgba8_out", true, -1}};
+    return check_arg_ranges(fn, t, 10, false, " (the window reads the records of other pixels, so out may not be records; only halves_out == halves, in place, is allowed)");
+}
+
+static int accumulate_clamped_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp, const AccumulateIo& io,
+                                     hipStream_t st) {
+    const uint32_t W = cam->width, H = cam->height;
+    const TpFrame f = accumulate_frame(cam, prm);
+    const dim3 grid = accumulate_grid(cam), block(RR_BLOCK);
+    const float k = clamp->sigma_scale;
+    const float4 *rec = (const float4*)io.records, *hv = (const float4*)io.halves, *hist = (const float4*)io.history, *hist_h = (const float4*)io.history_halves;
+    float4 *out = (float4*)io.out, *out_h = (float4*)io.halves_out;
+    if (io.halves && clamp->radius == 1u)
+        hipLaunchKernelGGL((k_accumulate_clamped_records<true, 1>), grid, block, 0, st, f, k, rec, hv, hist, hist_h, io.history_length, io.motion, out, out_h, io.length_out);
+    else if (io.halves)
+        hipLaunchKernelGGL((k_accumulate_clamped_records<true, 2>), grid, block, 0, st, f, k, rec, hv, hist, hist_h, io.history_length, io.motion, out, out_h, io.length_out);
+    else if (clamp->radius == 1u)
+        hipLaunchKernelGGL((k_accumulate_clamped_records<false, 1>), grid, block, 0, st, f, k, rec, (const float4*)nullptr, hist, (const float4*)nullptr, io.history_length,
+                           io.motion, out, (float4*)nullptr, io.length_out);
+    else
+        hipLaunchKernelGGL((k_accumulate_clamped_records<false, 2>), grid, block, 0, st, f, k, rec, (const float4*)nullptr, hist, (const float4*)nullptr, io.history_length,
+                           io.motion, out, (float4*)nullptr, io.length_out);
+    if (io.rgba8) {
+        rr_config cfg{};
+        cfg.gamma_correction = prm->gamma_correction ? 1 : 0;
+        launch_record_bytes(s, &cfg, io.out, W * H, io.rgba8, st);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(RR_ERR_DEVICE, "rr_accumulate_clamped_records: a launch failed");
+    return RR_OK;
+}
+
+int rr_accumulate_clamped_records_device(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp,
+                                         const rr_radiance* records, const rr_radiance* halves, const rr_radiance* history, const rr_radiance* history_halves,
+                                         const float* history_length, const float* motion, rr_radiance* out, rr_radiance* halves_out, float* length_out,
+                                         uint8_t* rgba8_out, void* hip_stream) try {
+    const char* fn = "rr_accumulate_clamped_records_device";
+    const AccumulateIo io{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out};
+    RR_TRY(check_accumulate_clamped_args(fn, true, s, camera, prm, clamp, io));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {history, "history_dev"}, {history_halves, "history_halves_dev"},
+                                      {history_length, "history_length_dev"}, {motion, "motion_dev"}, {out, "out_dev"}, {halves_out, "halves_out_dev"},
+                                      {length_out, "length_out_dev"}, {rgba8_out, "rgba8_out_dev"}}, st,
+                       [&] { return accumulate_clamped_locked(s, camera, prm, clamp, io, st); });
+} RR_GUARD_END("rr_accumulate_clamped_records_device")
+
+int rr_accumulate_clamped_records(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp,
+                                  const rr_radiance* records, const rr_radiance* halves, const rr_radiance* history, const rr_radiance* history_halves,
+                                  const float* history_length, const float* motion, rr_radiance* out, rr_radiance* halves_out, float* length_out,
+                                  uint8_t* rgba8_out) try {
+    const char* fn = "rr_accumulate_clamped_records";
+    RR_TRY(check_accumulate_clamped_args(fn, false, s, camera, prm, clamp,
+                                         AccumulateIo{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out}));
+    const size_t n = (size_t)camera->width * camera->height;
+    const StageArg args[10] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(history, 32 * n), stage_input(history_halves, 64 * n),
+                               stage_input(history_length, 4 * n), stage_input(motion, 12 * n), stage_output(out, 32 * n), stage_output(halves_out, 64 * n),
+                               stage_output(length_out, 4 * n), stage_output(rgba8_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const AccumulateIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const rr_radiance*)d[2], (const rr_radiance*)d[3], (const float*)d[4],
+                                   (const float*)d[5], (rr_radiance*)d[6], (rr_radiance*)d[7], (float*)d[8], (uint8_t*)d[9]};
+            return accumulate_clamped_locked(s, camera, prm, clamp, dev, nullptr);
+        });
+    });
+} RR_GUARD_END("rr_accumulate_clamped_records")

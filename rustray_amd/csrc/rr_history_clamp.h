@@ -1,0 +1,93 @@
+// rr_history_clamp.h — the arithmetic of the neighbourhood clamp that host and device share (rr_accumulate_clamped_records, steps 7 .. 9
+// of its text in include/rustray_hip.h; the yardstick is rustray_amd/temporal.py: accumulate_clamped_records): the sums over the window
+// of the current frame, the box they make, the clamp of one layer's history mean to it and the shorter length of a pixel whose record
+// layer had to be moved.  Plain host logic, no HIP call and no system include: k_accumulate_clamped_records (rr_kernels.hip) applies
+// these functions per lane between temporal_history and the blends, tests/native/temporal_clamp_test.cpp runs them as a host loop.
+//
+// Every step is exact in binary32 in the order written here and must be compiled without contraction, as rr_temporal.h.
+#pragma once
+#include "rr_temporal.h" // TpMix, DN_EPS and denoise_is_finite behind it
+
+// the window of one pixel: how many colours were taken, their sums and the sums of their squares per channel
+struct HcSums {
+    int m;
+    float s1[3], s2[3];
+};
+// the box of one pixel per channel, and the half width e = sigma_scale * sd it was made from.  A channel in which s2 / m, mean * mean or e
+// is not finite -- an s1 or s2 that overflowed, a square of the mean that did, an e that did -- has no box: lo = -inf, hi = +inf,
+// e = +inf, and nothing is moved in it.  (Without the test of the two terms of v a colour above about 1.7e20 would give v = inf - inf,
+// sd = 0 and a box that is the point `mean`, to which its neighbours' histories would be pulled.)
+struct HcBox {
+    float lo[3], hi[3], e[3];
+};
+
+// step 7, the sums: colour(dx, dy, c) gives the colour of pixel (x + dx, y + dy) and says whether it is taken (inside the frame, three
+// finite floats); the pixel itself is always taken.  dy outside, dx inside, both ascending.
+template <class Colour>
+RR_SETUP_HD HcSums history_clamp_sums(int r, Colour colour) {
+    HcSums s;
+    s.m = 0;
+    for (int c = 0; c < 3; c++) s.s1[c] = s.s2[c] = 0.0f;
+    for (int dy = -r; dy <= r; dy++)
+        for (int dx = -r; dx <= r; dx++) {
+            float q[3];
+            if (!colour(dx, dy, q)) continue;
+            s.m += 1;
+            for (int c = 0; c < 3; c++) {
+                const float sq = q[c] * q[c];
+                s.s1[c] += q[c];
+                s.s2[c] += sq;
+            }
+        }
+    return s;
+}
+
+// step 7, the box
+RR_SETUP_HD HcBox history_clamp_box(const HcSums& s, float sigma_scale) {
+    HcBox b;
+    const float m = (float)s.m;
+    for (int c = 0; c < 3; c++) {
+        const float mean = s.s1[c] / m;
+        const float q = s.s2[c] / m, mm = mean * mean;
+        const float v = q - mm;
+        const float sd = __builtin_sqrtf(v > 0.0f ? v : 0.0f); // (a NaN gives 0; with q and mm finite none arises)
+        const float e = sigma_scale * sd;
+        if (denoise_is_finite(q) && denoise_is_finite(mm) && denoise_is_finite(e)) { // (mm finite: so is the mean)
+            b.e[c] = e; b.lo[c] = mean - e; b.hi[c] = mean + e;
+        } else {
+            b.e[c] = __builtin_inff(); b.lo[c] = -__builtin_inff(); b.hi[c] = __builtin_inff();
+        }
+    }
+    return b;
+}
+
+// step 8: one layer's history mean held to the box, in place.  true: a channel was moved.  (A NaN is below and above nothing: it stays.)
+RR_SETUP_HD bool history_clamp_layer(const HcBox& b, float* h) {
+    bool moved = false;
+    for (int c = 0; c < 3; c++) {
+        if (h[c] < b.lo[c]) { h[c] = b.lo[c]; moved = true; }
+        else if (h[c] > b.hi[c]) { h[c] = b.hi[c]; moved = true; }
+    }
+    return moved;
+}
+
+// step 9: the length of a pixel whose record layer went from h to hc != h.  u is 0 in a channel that was not moved; in one that was, e is
+// finite and >= 0, so u is >= 0 or +inf, keep lies in [0, 1] and the new length in [1, N].
+RR_SETUP_HD void history_clamp_length(const HcBox& b, const float* h, const float* hc, TpMix* m) {
+    float u[3];
+    for (int c = 0; c < 3; c++) u[c] = (hc[c] < h[c] || hc[c] > h[c]) ? __builtin_fabsf(h[c] - hc[c]) / (b.e[c] + DN_EPS) : 0.0f;
+    const float t01 = u[0] > u[1] ? u[0] : u[1];
+    const float t = t01 > u[2] ? t01 : u[2];
+    const float keep = 1.0f / (1.0f + t);
+    m->length = (m->length - 1.0f) * keep + 1.0f;
+    m->a = 1.0f / m->length;
+}
+
+// steps 7 .. 9 for a pixel that kept its history: m's three means clamped, its length and a shortened where the record layer moved
+template <bool HALVES, class Colour>
+RR_SETUP_HD void history_clamp(int r, float sigma_scale, Colour colour, TpMix* m) {
+    const HcBox b = history_clamp_box(history_clamp_sums(r, colour), sigma_scale);
+    const float h[3] = {m->h[0], m->h[1], m->h[2]};
+    if (history_clamp_layer(b, m->h)) history_clamp_length(b, h, m->h, m);
+    if (HALVES) { history_clamp_layer(b, m->ha); history_clamp_layer(b, m->hb); }
+}

@@ -25,6 +25,7 @@
 #include "rr_adaptive.h" // half_error and the 8x8-block order of a refinement list (kernels 5l .. 5p)
 #include "rr_denoise.h"  // the arithmetic of the a-trous filter (kernels 7a .. 7d)
 #include "rr_temporal.h" // the arithmetic of the temporal reprojection (kernel 7e)
+#include "rr_history_clamp.h" // the neighbourhood clamp of the history (kernel 7e'')
 #include "rr_motion.h"   // the per-pixel motion of moved items and the call's table (kernel 7f)
 
 // ---------------------------------------------------------------------------
@@ -2319,6 +2320,71 @@ __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_split_records(const TpF
         halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
         if (kept) { temporal_blend_diffuse(s.da, m.a, da, da); temporal_blend_diffuse(s.db, m.a, db, db); }
         for (int c = 0; c < 3; c++) { io.dif_halves_out[6ull * o + c] = da[c]; io.dif_halves_out[6ull * o + 3 + c] = db[c]; }
+    }
+}
+
+// 7e'': 7e with the history held to the colours of the current frame (rr_accumulate_clamped_records; rr_history_clamp.h has the
+// arithmetic of steps 7 .. 9).  The colour rows of `records` for the tile and a halo of R points go through LDS, one float4 per point:
+// the colour and, in w, 1 where the point lies inside the frame with three finite floats, else 0 (34 x 10 at R = 1, 36 x 12 = 6912 B at
+// R = 2).  Row-major, as 7c: the lanes of a tile row read consecutive 16-byte slots of one row of the staged tile at each window
+// position (the compiler reads a slot as ds_read_b96 for the colour and ds_read_b32 for w); the staging writes are ds_write_b128 and
+// walk the tile linearly.  EVERY lane stages and reaches the barrier; a lane outside the frame leaves after it.  Then 7e:
+// temporal_history as there, and for a pixel that kept its history the (2R + 1)^2 window reads, the clamp and the length rule before
+// the blends.  `out` may NOT be `records` (another workgroup's halo reads them); halves_out may be `halves`, read at the lane's pixel only.
+template <bool HALVES, int R>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_clamped_records(const TpFrame f, float sigma_scale, const float4* __restrict__ records, const float4* halves,
+                                                                         const float4* __restrict__ history, const float4* __restrict__ history_halves,
+                                                                         const float* __restrict__ history_length, const float* __restrict__ motion,
+                                                                         float4* __restrict__ out, float4* halves_out, float* __restrict__ length_out) {
+    constexpr int TW = DN_TILE_W + 2 * R, TH = DN_TILE_H + 2 * R;
+    __shared__ float4 s_c[TW * TH];
+    const int x0 = (int)blockIdx.x * DN_TILE_W, y0 = (int)blockIdx.y * DN_TILE_H;
+    for (int e = (int)threadIdx.x; e < TW * TH; e += RR_BLOCK) {
+        const int qx = x0 - R + e % TW, qy = y0 - R + e / TW;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (qx >= 0 && qy >= 0 && qx < f.width && qy < f.height) {
+            c = records[2ull * ((unsigned long long)qy * (unsigned int)f.width + (unsigned int)qx)];
+            c.w = (denoise_is_finite(c.x) && denoise_is_finite(c.y) && denoise_is_finite(c.z)) ? 1.0f : 0.0f;
+        }
+        s_c[e] = c;
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x & (DN_TILE_W - 1), ty = (int)threadIdx.x / DN_TILE_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= f.width || y >= f.height) return;
+    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    float4 a0, a1, b0, b1;
+    if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
+    const uint32_t flags = denoise_record_flags(r0, r1);
+    TpMix m;
+    bool kept = false;
+    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
+        const float n_p[3] = {r1.x, r1.y, r1.z};
+        const TpHistory hist{history, history_halves, history_length};
+        kept = temporal_history<HALVES>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr, hist, &m);
+    }
+    if (kept) {
+        const float4* s_p = s_c + (ty + R) * TW + tx + R;
+        history_clamp<HALVES>(R, sigma_scale, [&](int dx, int dy, float* c) {
+            const float4 q = s_p[dy * TW + dx];
+            c[0] = q.x; c[1] = q.y; c[2] = q.z;
+            return q.w != 0.0f;
+        }, &m);
+    }
+    float4 c0 = r0;
+    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
+    out[2ull * o] = c0;
+    out[2ull * o + 1] = r1;
+    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
+    if (HALVES) {
+        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
+            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
+        }
+        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
+            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
+        }
+        halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
     }
 }
 

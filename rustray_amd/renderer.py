@@ -257,7 +257,7 @@ class Raytracing:
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
     def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
-                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo=False) -> dict:
+                        motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo=False, clamp=None) -> dict:
         """One frame of a frame-after-frame loop at `samples` (default: the config's; even) and `seed` (default: the config's): the frame
         in two halves, blended into the history `state` carries from the previous call (rr_accumulate_records, reprojected through the
         camera of that call), then the filter guided by the accumulated halves.  render_temporal_torch on this scene and camera: three
@@ -268,12 +268,15 @@ class Raytracing:
         without track_items.  albedo=True: one more call on the same stream (rr_surface_pixels_device) makes this camera's albedo for the
         filter; the accumulation is not changed, it blends un-demodulated colour.  albedo="mean": rr_albedo_pixels_device with the frame's
         config and table in its place.  albedo="diffuse" raises ValueError: the diffuse part is accumulated over time by
-        render_temporal_split, a pipeline of its own."""
+        render_temporal_split, a pipeline of its own.  clamp: None or False is rr_accumulate_records; True (the library's defaults) or a
+        temporal.HistoryClampParams puts rr_accumulate_clamped_records in its place, which holds the history to the current frame's colours
+        around each pixel: for frames after an edit of lights, materials, textures or item flags, and under moving shadows."""
         from .temporal import previous_view
         _check_albedo_mode(albedo, temporal=True)
+        clamp = _clamp_params(clamp)         # (refused before the state notes this frame's items)
         cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
         return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo)
+                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo, clamp=clamp)
 
     def _temporal_frame(self, state: "TemporalState", samples, seed, motion, track_items: bool):
         """What render_temporal and render_temporal_split do before their pipeline: the frame's config, and with track_items the moved items
@@ -296,14 +299,15 @@ class Raytracing:
         return cfg, moved
 
     def render_temporal_split(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
-                              motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False) -> dict:
+                              motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, clamp=None) -> dict:
         """render_temporal with the frame's direct diffuse light accumulated as layers of its own and the mean albedo applied to it alone:
         rr_render_pixel_split, (with moved items) rr_motion_records, rr_accumulate_split_records, rr_albedo_pixels and
         rr_denoise_split_records -- render_temporal_split_torch on this scene and camera, on one stream with no host trip.  The arguments are
         render_temporal's, without `albedo`; `state` is a TemporalState of this pipeline's (one that render_temporal filled starts anew).
         The result holds torch tensors: render_temporal's, and diffuse, diffuse_halves, accumulated_diffuse, accumulated_diffuse_halves and
-        albedo."""
+        albedo.  clamp: anything but None or False raises ValueError, the clamped form of the split accumulation is not built."""
         from .temporal import previous_view
+        _no_split_clamp(clamp)
         cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
         return render_temporal_split_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
                                            sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
@@ -1284,6 +1288,56 @@ def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, 
     return result
 
 
+def _clamp_params(clamp):
+    """The `clamp` keyword of the temporal pipelines -> None (off: clamp is None or False) or the clamp to use: the library's defaults as
+    the C struct for True, a temporal.HistoryClampParams (checked) or a C struct as given.  Anything else raises ValueError."""
+    from .temporal import HistoryClampParams
+    if clamp is None or clamp is False:
+        return None
+    if clamp is True:
+        return capi.history_clamp_default_params()
+    if isinstance(clamp, HistoryClampParams):
+        clamp.check()
+        return clamp
+    if isinstance(clamp, capi.rr_history_clamp_params):
+        return clamp
+    raise ValueError("clamp is None or False (off), True (the defaults) or a temporal.HistoryClampParams")
+
+
+def _no_split_clamp(clamp) -> None:
+    if clamp is not None and clamp is not False:
+        raise ValueError("clamp: the split form of the clamped accumulation is not built; render_temporal (render_temporal_torch) takes clamp")
+
+
+def accumulate_clamped_torch(device_scene: capi.DeviceScene, cam, records, halves=None, history=None, history_halves=None, history_length=None, motion=None,
+                             params=None, clamp=None, rgba8: bool = False, out: Optional[dict] = None) -> dict:
+    """rr_accumulate_clamped_records_device on torch's current stream of the scene's device: the tensors and the result of accumulate_torch,
+    and clamp: a temporal.HistoryClampParams or None (the library's defaults).  There is no in_place: `out` may not be `records`, whose
+    neighbours the window reads.  out: dict(records, halves, length) of tensors to write."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)),
+                                                                  history_halves=(history_halves, (2, 8)), history_length=(history_length, ()),
+                                                                  motion=(motion, (3,))))
+    dev = torch.device("cuda", device_scene.device)
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    with torch.cuda.device(dev):
+        if out is not None:
+            res, res_h = out["records"], out["halves"] if t["halves"] is not None else None
+        else:
+            res = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            res_h = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if t["halves"] is not None else None
+        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        device_scene.accumulate_clamped_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["history"]), ptr(t["history_halves"]), ptr(t["history_length"]),
+                                               ptr(t["motion"]), ptr(res), ptr(res_h), ptr(length), ptr(rgba), params, clamp,
+                                               torch.cuda.current_stream(dev).cuda_stream)
+    result = dict(_record_views(res), halves=res_h, length=length)
+    if rgba8:
+        result["rgba"] = rgba
+    return result
+
+
 def accumulate_split_torch(device_scene: capi.DeviceScene, cam, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
                            history_diffuse_halves=None, history_length=None, motion=None, params=None, rgba8: bool = False, in_place: bool = False,
                            out: Optional[dict] = None) -> dict:
@@ -1340,7 +1394,7 @@ def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_
 
 
 def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
-                          sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo=False) -> dict:
+                          sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo=False, clamp=None) -> dict:
     """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
     even), rr_accumulate_records_device against the history in `state`, rr_denoise_records_device with the accumulated halves -- three
     calls on torch's current stream, each reading what the one before wrote without a synchronisation.  params: a
@@ -1353,11 +1407,13 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     what the accumulation read.  albedo=True: rr_surface_pixels_device on the same stream, one call more, makes the albedo of `cam` for the
     filter (returned as `albedo`); the accumulation itself blends un-demodulated colour, as without it.  albedo="mean":
     rr_albedo_pixels_device with the frame's config and table in its place.  albedo="diffuse" raises ValueError: the diffuse part is
-    accumulated over time by render_temporal_split_torch."""
+    accumulated over time by render_temporal_split_torch.  clamp: None or False is rr_accumulate_records_device; True (the library's defaults) or a
+    temporal.HistoryClampParams puts rr_accumulate_clamped_records_device in its place, on the same stream and the same buffers."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
     _check_albedo_mode(albedo, temporal=True)
+    clamp = _clamp_params(clamp)         # (refused before anything is rendered)
     if moved is not None and motion is not None:
         raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
     base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
@@ -1374,8 +1430,12 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     target = state.target(n, True, torch.device("cuda", device_scene.device))
     if moved is not None and hist is not None and len(moved[0]):
         motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
-    acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
-                           hist["length"] if hist else None, motion, prm, out=target)
+    if clamp is None:
+        acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
+                               hist["length"] if hist else None, motion, prm, out=target)
+    else:
+        acc = accumulate_clamped_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None,
+                                       hist["halves"] if hist else None, hist["length"] if hist else None, motion, prm, clamp, out=target)
     guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
     res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], guide, denoise_params, rgba8=rgba8)
     state.advance(target, view if view is not None else previous_view(cam))
@@ -1387,7 +1447,7 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
 
 
 def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
-                                sample_xy=None, rgba8: bool = False, view=None, moved=None) -> dict:
+                                sample_xy=None, rgba8: bool = False, view=None, moved=None, clamp=None) -> dict:
     """render_temporal_torch for the split arm, with no host trip: rr_render_pixel_split_device (cfg.samples even), with moved items
     rr_motion_records_device, rr_accumulate_split_records_device against the history in `state`, rr_albedo_pixels_device (the mean albedo,
     as render_denoised_torch(albedo="diffuse") uses) and rr_denoise_split_records_device on the accumulated layers -- four or five calls on
@@ -1395,10 +1455,11 @@ def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_con
     A history without a diffuse part (a state render_temporal_torch filled), without halves or of another size resets the state, the
     items noted for this frame kept.  Returns the dict of render_temporal_torch (without a variance) plus diffuse (n, 3) and diffuse_halves
     (n, 2, 3), the frame's own, accumulated_diffuse and accumulated_diffuse_halves, what the filter read and `state` now holds, and
-    albedo (n, 3)."""
+    albedo (n, 3).  clamp: anything but None or False raises ValueError, the clamped form of the split accumulation is not built."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
+    _no_split_clamp(clamp)
     if moved is not None and motion is not None:
         raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
     base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)

@@ -19,6 +19,20 @@ MIN_WEIGHT = F(2.0 ** -6)
 
 
 @dataclass
+class HistoryClampParams:
+    """rr_history_clamp_params without its struct_size; the defaults are rr_history_clamp_default_params'."""
+    radius: int = 1
+    sigma_scale: float = 0.5
+
+    def check(self):
+        if self.radius not in (1, 2):
+            raise ValueError(f"radius {self.radius} (1 or 2)")
+        k = F(self.sigma_scale)
+        if not (np.isfinite(k) and 0.0 <= float(k) <= 65536.0):
+            raise ValueError(f"sigma_scale {self.sigma_scale} (finite, 0 .. 65536)")
+
+
+@dataclass
 class AccumulateParams:
     """rr_accumulate_params without its struct_size; the defaults are rr_accumulate_default_params'.  prev_world_to_clip is the 4x4
     matrix as written on paper (row r, column c), the C struct holds it column-major."""
@@ -113,10 +127,12 @@ def motion_records(records, cam, item_ids, prev_trans, cur_trans_inv):
     return motion, world
 
 
-def _accumulate(records, halves, history, history_halves, history_length, motion, cam, prm, extra=()):
-    """The tap walk and the blends that accumulate_records and accumulate_split_records share.  extra: (current (n, 3), history (n, 3) or
-    None) per extra layer, which rides on the taps and weights of the records and decides nothing.  -> (accumulate_records' dict, the
-    extra layers' outputs)."""
+def _accumulate(records, halves, history, history_halves, history_length, motion, cam, prm, extra=(), hook=None):
+    """The tap walk and the blends that accumulate_records, accumulate_split_records and accumulate_clamped_records share.  extra: (current
+    (n, 3), history (n, 3) or None) per extra layer, which rides on the taps and weights of the records and decides nothing.  hook (or
+    None): called between the means and the blend as hook(rec, means, N, kept) with the history means of the records and the two halves
+    (a list of (n, 3)), and gives (means, N) back -- what accumulate_clamped_records does to them.  -> (accumulate_records' dict, the extra
+    layers' outputs)."""
     prm.check()
     pi, vi, W, H = camera_matrices(cam)
     n = W * H
@@ -198,11 +214,13 @@ def _accumulate(records, halves, history, history_halves, history_length, motion
         taps["reprojected"] = alive
         n1 = sum_l / sum_w + one
         N = np.where(n1 < max_history, n1, max_history).astype(F)
+        means = [s / sum_w[:, None] for s in sum_c]
+        if hook is not None:
+            means, N = hook(rec, means, N, kept)
         a = one / N
         currents = [rec[:, 0:3]] + ([] if hv is None else [hv[:, 0, 0:3], hv[:, 1, 0:3]])
         targets = [out[:, 0:3]] + ([] if hv is None else [out_h[:, 0, 0:3], out_h[:, 1, 0:3]])
-        for s, cur, dst in zip(sum_c, currents, targets):
-            h = s / sum_w[:, None]
+        for h, cur, dst in zip(means, currents, targets):
             blended = h + a[:, None] * (cur - h)
             dst[...] = np.where((kept & np.isfinite(cur).all(-1))[:, None], blended, cur)
         for sx, (cur, _), dst in zip(sum_x, extra, out_x):
@@ -248,4 +266,74 @@ def accumulate_split_records(records, halves, diffuse, diffuse_halves, history, 
     res, out_x = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), extra)
     res["diffuse"] = out_x[0]
     res["diffuse_halves"] = None if diffuse_halves is None else np.ascontiguousarray(np.stack([out_x[1], out_x[2]], axis=1))
+    return res
+
+
+def clamp_boxes(records, W: int, H: int, clamp: HistoryClampParams):
+    """Step 7 of rr_accumulate_clamped_records for every pixel of a W x H frame of records (n, 8): (lo, hi, e), each (n, 3) float32, and m
+    (n,), how many pixels of the window were taken.  The (2r + 1)^2 window positions are whole-frame shifts here, in the header's order; a
+    position that is not taken adds nothing.  A channel without a box has lo = -inf, hi = e = +inf.  (A pixel whose own colour is not
+    finite never reaches step 7; what stands here for it means nothing.)"""
+    r, k = int(clamp.radius), F(clamp.sigma_scale)
+    col = np.ascontiguousarray(records, F).reshape(H, W, 8)[:, :, 0:3]
+    ok = np.isfinite(col).all(-1)
+    m = np.zeros((H, W), np.int64)
+    s1, s2 = np.zeros((H, W, 3), F), np.zeros((H, W, 3), F)
+    with np.errstate(all="ignore"):
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                ys, yq = slice(max(0, -dy), min(H, H - dy)), slice(max(0, dy), min(H, H + dy))
+                xs, xq = slice(max(0, -dx), min(W, W - dx)), slice(max(0, dx), min(W, W + dx))
+                if ys.start >= ys.stop or xs.start >= xs.stop:
+                    continue
+                t, c = ok[yq, xq], col[yq, xq]
+                m[ys, xs] += t
+                np.add(s1[ys, xs], c, out=s1[ys, xs], where=t[..., None])
+                np.add(s2[ys, xs], c * c, out=s2[ys, xs], where=t[..., None])
+        mf = m.astype(F)[..., None]
+        mean = s1 / mf
+        q, mm = s2 / mf, mean * mean
+        v = q - mm
+        sd = np.sqrt(np.where(v > 0, v, F(0)).astype(F))
+        e = (k * sd).astype(F)
+        boxed = np.isfinite(q) & np.isfinite(mm) & np.isfinite(e)
+        lo = np.where(boxed, mean - e, F(-np.inf)).astype(F).reshape(-1, 3)
+        hi = np.where(boxed, mean + e, F(np.inf)).astype(F).reshape(-1, 3)
+        e = np.where(boxed, e, F(np.inf)).astype(F).reshape(-1, 3)
+    return lo, hi, e, m.reshape(-1)
+
+
+def accumulate_clamped_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None,
+                               clamp: HistoryClampParams | None = None) -> dict:
+    """rr_accumulate_clamped_records in numpy float32, following steps 7 .. 10 of its text in include/rustray_hip.h: accumulate_records'
+    arguments and a HistoryClampParams (None: the defaults).  The history means of a kept pixel are held to the box of the current
+    frame's colours around it, and the length is shortened where the record layer had to be moved.  -> accumulate_records' dict, and
+    clamped (n, 3) bool: per layer (records, half 0, half 1) whether a channel of that layer's mean was moved (False for a pixel
+    without history and for a layer the call does not have), and box: dict(lo (n, 3), hi (n, 3))."""
+    clamp = clamp or HistoryClampParams()
+    clamp.check()
+    _, _, W, H = camera_matrices(cam)
+    n = W * H
+    lo, hi, e, _ = clamp_boxes(records, W, H, clamp)
+    clamped = np.zeros((n, 3), bool)
+    one = F(1)
+
+    def hook(rec, means, N, kept):
+        held, moved = [], []
+        for h in means:
+            below, above = h < lo, h > hi
+            held.append(np.where(below, lo, np.where(above, hi, h)).astype(F))
+            moved.append((below | above) & kept[:, None])
+        for layer, mv in enumerate(moved):
+            clamped[:, layer] = mv.any(-1)
+        u = np.where(moved[0], np.abs(means[0] - held[0]) / (e + EPS), F(0)).astype(F)
+        t01 = np.where(u[:, 0] > u[:, 1], u[:, 0], u[:, 1])
+        t = np.where(t01 > u[:, 2], t01, u[:, 2])
+        keep = one / (one + t)
+        shorter = ((N - one) * keep + one).astype(F)
+        return held, np.where(clamped[:, 0], shorter, N).astype(F)
+
+    res = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), hook=hook)[0]
+    res["clamped"] = clamped
+    res["box"] = dict(lo=lo, hi=hi)
     return res

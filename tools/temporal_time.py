@@ -23,7 +23,11 @@ rr_render_pixel_split_device -- next to ITS compulsory traffic: per pixel 36 B o
 beside the 296 B of the record call, 404 B in the static case.  The yardstick is the alternative a caller has without the call: two
 rr_accumulate_records_device calls of the same run and view.
 
-usage: temporal_time.py [scene [width height samples]] [--motion] [--split] [--out FILE]"""
+--clamp: rr_accumulate_clamped_records_device in the same rounds, with halves, static view and 1.3-pixel yaw, at radius 1 and 2 (sigma_scale
+1).  The call moves the HBM bytes of a record call -- the window is read from LDS, the halo costs about a third more colour rows, which
+hit in cache --, so the yardstick is the record call of the same run and view.
+
+usage: temporal_time.py [scene [width height samples]] [--motion] [--split] [--clamp] [--out FILE]"""
 import math
 import os
 import sys
@@ -66,6 +70,9 @@ def main(argv):
     with_split = "--split" in argv
     if with_split:
         argv.remove("--split")
+    with_clamp = "--clamp" in argv
+    if with_clamp:
+        argv.remove("--clamp")
     scene = argv[1] if len(argv) > 1 else "spheres_room"
     w, h, samples = (int(argv[2]), int(argv[3]), int(argv[4])) if len(argv) > 4 else (1280, 720, 4)
     if capi.device_count() < 1:
@@ -134,6 +141,18 @@ def main(argv):
                 return lambda: ds.accumulate_split_device(cam, *cur, *old, None, *new, None, prm, stream)
             for view in ("static", "moved"):
                 arms[("split", view)] = split_call(view)
+        if with_clamp:
+            from rustray_amd.temporal import HistoryClampParams
+            c_out, c_out_h = torch.empty_like(rec), torch.empty_like(halves)
+
+            def clamp_call(view, radius):
+                prm = capi.accumulate_params(AccumulateParams(prev_world_to_clip=views[view][0], prev_eye=views[view][1]))
+                clamp = capi.history_clamp_params(HistoryClampParams(radius, 1.0))
+                return lambda: ds.accumulate_clamped_device(cam, rec.data_ptr(), halves.data_ptr(), hist["records"].data_ptr(), hist["halves"].data_ptr(),
+                                                            hist["length"].data_ptr(), None, c_out.data_ptr(), c_out_h.data_ptr(), length.data_ptr(), None, prm, clamp, stream)
+            for view in ("static", "moved"):
+                for radius in (1, 2):
+                    arms[("clamp", view, radius)] = clamp_call(view, radius)
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
@@ -160,6 +179,14 @@ def main(argv):
             emit(f"  rr_accumulate_split_records_device, with halves, {k[1]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the rate of its compulsory "
                  f"traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / bm:.2f} x rr_accumulate_records_device with halves, {k[1]}; the bar, two "
                  f"such calls: {2 * bm:.4f} ms [{2 * blo:.4f} .. {2 * bhi:.4f}], {'met' if m < 2 * bm else 'MISSED'}, {apart} the arms' ranges")
+            continue
+        if k[0] == "clamp":
+            per_pixel = BYTES_PER_PIXEL[True]
+            floor_ms = n * per_pixel / HBM_BYTES_PER_S * 1e3
+            bm, blo, bhi = _median(runs[(True, k[1])])
+            emit(f"  rr_accumulate_clamped_records_device, with halves, {k[1]}, radius {k[2]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the rate of its "
+                 f"compulsory traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / bm:.2f} x rr_accumulate_records_device with halves, {k[1]} "
+                 f"({bm:.4f} ms [{blo:.4f} .. {bhi:.4f}])")
             continue
         if k[0] == "motion":
             per_pixel = 44 + (12 if k[2] else 0)
