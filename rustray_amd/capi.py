@@ -1162,6 +1162,23 @@ def math_probe(op: int, a, b=None, c=None, seed: int = 0, device: int = 0):
     return outs
 
 
+def wave_sums_probe(entry: int, sum_pix, rgb, aux_pix, aux, depth_hi=None, device: int = 0):
+    """rr_math_probe op 13: the wave merges of rr_accumulate.h on one workgroup of 256 lanes (four waves).  `entry`: 0 accum_merged,
+    1 accum_aux_merged, 2 accum_hit_merged, 3 accum_depth_wide_merged.  `sum_pix`, `aux_pix`: (256,) uint32 slots below 128 or
+    0xffffffff; `rgb`: (256, 3) int32; `aux`: (256, 4) int32 (nx, ny, nz, depth); `depth_hi`: (256,) the depth's high words for
+    entry 3.  Returns the int64 sums {"rgb": (3, 128), "normal": (3, 128), "depth": (128,)}."""
+    rgb = np.ascontiguousarray(rgb, np.int32).reshape(256, 3)
+    aux = np.ascontiguousarray(aux, np.int32).reshape(256, 4)
+    words = np.concatenate([np.ascontiguousarray(sum_pix, np.uint32).reshape(256), rgb.T.reshape(-1).view(np.uint32),
+                            np.ascontiguousarray(aux_pix, np.uint32).reshape(256), aux.T.reshape(-1).view(np.uint32)])
+    hi = np.zeros(9 * 256, np.uint32)
+    if depth_hi is not None:
+        hi[:256] = np.ascontiguousarray(depth_hi).astype(np.int64).astype(np.uint32).reshape(256)
+    out0, _, _ = math_probe(13, words.view(np.float32), hi.view(np.float32), None, seed=int(entry), device=device)
+    planes = out0.view(np.int64)[:7 * 128].reshape(7, 128)
+    return {"rgb": planes[0:3].copy(), "normal": planes[3:6].copy(), "depth": planes[6].copy()}
+
+
 def philox_probe(op: int, counters, key, device: int = 0):
     """rr_math_probe ops 12 (device) and 14 (host) of philox4x32_10: `counters` is (m, 4) uint32
     (pixel, sample, node, stream), `key` two uint32 words; returns the (m, 2) uint32 words jitter() uses."""

@@ -1,10 +1,10 @@
 // rr_accumulate.h — layer 5 of the device code: the per-pixel fixed-point accumulators that stand for the reference's f32 sums
 // over samples (src/raytracing.rs:400-417).  Integer adds commute, so the frame does not depend on the order of anything.
 //
-// Offers: to_fix, fix_add, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged (the last three must be
-// called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms).  wave_merge_runs /
-// wave_merge_runs32 / fits25i are this layer's own, and so are its DPP macros (RR_DPP_*, RR_SEG_STEP, RR_SEG_STEP32),
-// un-defined at the end.
+// Offers: to_fix, fix_add, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged, accum_hit_merged (the last four
+// must be called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms).
+// wave_merge_runs / wave_merge_runs32 / fits25i / fits25 / wave_one_pixel / wave_sum32 / wave_sum64 / totals_to_lanes and the *_runs forms of the merges
+// are this layer's own, and so are its DPP macros (RR_DPP_*, RR_SEG_STEP, RR_SEG_STEP32), un-defined at the end.
 // Needs: rr_device.h (DAccum, RR_NF_*), rr_math.h.
 #pragma once
 #include "rr_device.h"
@@ -86,7 +86,7 @@ template <int N> RR_DEV bool wave_merge_runs32(uint32_t pix, int (&v)[N]) {
 RR_DEV bool fits25i(int a, int b, int c) { // |a|, |b|, |c| < 2^25
     return (((uint32_t)(a + (1 << 25)) | (uint32_t)(b + (1 << 25)) | (uint32_t)(c + (1 << 25))) >> 26) == 0u;
 }
-RR_DEV void accum_merged(const DAccum& acc, uint32_t pix, int r, int g, int b) {
+RR_DEV void accum_merged_runs(const DAccum& acc, uint32_t pix, int r, int g, int b) {
     unsigned long long* p = (unsigned long long*)acc.rgb + pix; // one plane per channel
     if (__ballot(!fits25i(r, g, b)) == 0ull) {
         int w[3] = {r, g, b};
@@ -107,7 +107,7 @@ RR_DEV void accum_merged(const DAccum& acc, uint32_t pix, int r, int g, int b) {
 // The aux outputs of the root hits (normal and depth sums, reference src/raytracing.rs:400-402), merged the same way:
 // the samples of a pixel sit in neighbouring lanes, and 64 lanes adding to one address serialise in the L2 atomic
 // units (measured: k_shade 6.5 -> 42.8 ms on sponza_syn when the four aux adds of every primary hit went out unmerged).
-RR_DEV void accum_aux_merged(const DAccum& acc, uint32_t pix, int nx, int ny, int nz, int depth) {
+RR_DEV void accum_aux_merged_runs(const DAccum& acc, uint32_t pix, int nx, int ny, int nz, int depth) {
     if (__ballot(!fits25i(nx, ny, nz) || !fits25i(depth, 0, 0)) == 0ull) {
         int w[4] = {nx, ny, nz, depth};
         if (wave_merge_runs32<4>(pix, w)) {
@@ -136,9 +136,136 @@ RR_DEV void accum_aux_merged(const DAccum& acc, uint32_t pix, int nx, int ny, in
 // Depth terms beyond the 32-bit lane sums (|depth * 2^16| >= 2^25: a root hit farther than 512 units -- a scene modelled in centimetres,
 // a far background), merged like everything else: round 3 sent each of them to its accumulator word as an atomic of its own, 64 lanes
 // of a level-1 packet to ONE word (the cliff accum_aux_merged's comment describes, for depth alone).  All 64 lanes.
-RR_DEV void accum_depth_wide_merged(const DAccum& acc, uint32_t pix, long long depth) {
+RR_DEV void accum_depth_wide_merged_runs(const DAccum& acc, uint32_t pix, long long depth) {
     unsigned long long v[1] = {(unsigned long long)depth};
     if (wave_merge_runs<1>(pix, v) && acc.depth && v[0]) atomicAdd((unsigned long long*)acc.depth + pix, v[0]);
+}
+
+// ---------------------------------------------------------------------------
+// Waves of ONE pixel.  With a sample group of 64 every level-1 packet is 64 samples of one pixel, and the segmented scan above is the
+// general answer to a special question: four runs, one per DPP row, each with a head flag, a flag shift, a select and an add per value
+// and step, and four atomics to the SAME word per channel.  Such a wave needs a plain sum: six DPP adds per value (four inside the rows,
+// row_bcast:15, row_bcast:31) leave it in lane 63; lane k then takes channel k's total, and the packet's adds leave as ONE atomic
+// instruction, one lane per channel.  (Lane 63 issuing one instruction per channel was measured first and is slower than the scan: what
+// a packet pays for is the number of atomic instructions)  The entries below test for the case (two ballots and a
+// readlane) and hand every other wave -- several pixels, smaller sample groups -- to the *_runs forms above, unchanged; the kernels call
+// them where a one-pixel packet can occur and the registers allow it (k_shade<true, false>, k_trace_shadow<true, false>), and the *_runs
+// forms everywhere else.  Integer adds commute: the pixel's sum is the same integer either way.
+// ---------------------------------------------------------------------------
+#define RR_DPP_ADD(v, ctrl) (v) += __builtin_amdgcn_update_dpp(0, (v), ctrl, 0xf, 0xf, true)
+#define RR_DPP_ADD_ROWS(v, ctrl, rows) (v) += __builtin_amdgcn_update_dpp(0, (v), ctrl, rows, 0xf, false) // (the other rows add 0)
+// Do the lanes that have a pixel (a, or b where a lane has no a) all have the same one?  0: no lane has a pixel; 1: yes, *p0; 2: no.
+RR_DEV int wave_one_pixel(uint32_t a, uint32_t b, uint32_t* p0) {
+    const uint32_t any = a != 0xffffffffu ? a : b;
+    const unsigned long long live = __ballot(any != 0xffffffffu);
+    if (live == 0ull) return 0;
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)any, (int)__builtin_ctzll(live));
+    *p0 = first;
+    return __ballot((a != 0xffffffffu && a != first) || (b != 0xffffffffu && b != first)) == 0ull ? 1 : 2;
+}
+// The sums of v[0..N) over the 64 lanes, in lane 63 (the other lanes are left with partial sums).  Wraps like any 32-bit add: the
+// callers bound their terms (fits25).
+template <int N> RR_DEV void wave_sum32(int (&v)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD(v[k], 0xB1); // quad_perm [1,0,3,2]
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD(v[k], 0x4E); // quad_perm [2,3,0,1]
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD(v[k], 0x141); // row_half_mirror
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD(v[k], 0x140); // row_mirror: every lane holds its row's sum
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD_ROWS(v[k], 0x142, 0xa); // row_bcast:15 into rows 1 and 3
+#pragma unroll
+    for (int k = 0; k < N; k++) RR_DPP_ADD_ROWS(v[k], 0x143, 0xc); // row_bcast:31 into rows 2 and 3
+}
+// The same for one 64-bit value (the halves move separately, the add carries): 24 instructions instead of 6, for the rare wide depth.
+RR_DEV unsigned long long wave_sum64(unsigned long long v) {
+#define RR_SUM64_STEP(ctrl, rows, bc)                                                                                      \
+    v += ((unsigned long long)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), ctrl, rows, 0xf, bc) << 32) | \
+         (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, ctrl, rows, 0xf, bc);
+    RR_SUM64_STEP(0xB1, 0xf, true) RR_SUM64_STEP(0x4E, 0xf, true) RR_SUM64_STEP(0x141, 0xf, true) RR_SUM64_STEP(0x140, 0xf, true)
+    RR_SUM64_STEP(0x142, 0xa, false) RR_SUM64_STEP(0x143, 0xc, false)
+#undef RR_SUM64_STEP
+    return v;
+}
+// |w[k]| bounds of the 32-bit wave sum: fits25 admits -2^25 <= w < 2^25 (fits25i's test), so 64 terms sum within
+// [-64 * 2^25, 64 * (2^25 - 1)] = [-2^31, 2^31 - 64]: an int holds the total exactly (tests/test_gpu_wave_sums.py adds 64 of each end).
+template <int N> RR_DEV bool fits25(const int (&w)[N]) {
+    uint32_t m = 0u;
+#pragma unroll
+    for (int k = 0; k < N; k++) m |= (uint32_t)(w[k] + (1 << 25));
+    return (m >> 26) == 0u;
+}
+// The totals side by side: lane k < N takes channel k's total from lane 63 (a readlane and a select each), so that the N adds of a
+// packet leave as ONE atomic instruction with N lanes on N planes instead of N instructions with one lane each (the next packet's
+// first load waits for every one of them: vector memory operations are counted in order).  The other lanes hold 0.
+template <int N> RR_DEV int totals_to_lanes(const int (&w)[N]) {
+    const int lane = (int)(threadIdx.x & 63u);
+    int t = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) { const int total = __builtin_amdgcn_readlane(w[k], 63); if (lane == k) t = total; }
+    return t;
+}
+// The entries.  A lane without a pixel may hold anything in its values (the *_runs forms discard its run): the wave sums need zeros
+// there, written in place before the bound is tested, so that the *_runs forms' own bound ballot is the same expression.  A wave of
+// one pixel with a term beyond 2^25 (rare: a saturating highlight) keeps the segmented 64-bit scan.
+RR_DEV void accum_merged(const DAccum& acc, uint32_t pix, int r, int g, int b) {
+    uint32_t p0 = 0u;
+    const int one = wave_one_pixel(pix, 0xffffffffu, &p0);
+    if (one == 0) return;
+    if (pix == 0xffffffffu) r = g = b = 0;
+    if (one == 1 && __ballot(!fits25i(r, g, b)) == 0ull) {
+        int w[3] = {r, g, b};
+        wave_sum32<3>(w);
+        const int t = totals_to_lanes<3>(w);
+        const uint32_t lane = threadIdx.x & 63u; // channel `lane`; a zero total adds nothing, as in the *_runs forms
+        if (lane < 3u && t) atomicAdd((unsigned long long*)acc.rgb + lane * acc.n + p0, (unsigned long long)(long long)t);
+    } else accum_merged_runs(acc, pix, r, g, b);
+}
+RR_DEV void accum_aux_merged(const DAccum& acc, uint32_t pix, int nx, int ny, int nz, int depth) {
+    uint32_t p0 = 0u;
+    const int one = wave_one_pixel(pix, 0xffffffffu, &p0);
+    if (one == 0) return;
+    if (pix == 0xffffffffu) nx = ny = nz = depth = 0;
+    if (one == 1 && __ballot(!fits25i(nx, ny, nz) || !fits25i(depth, 0, 0)) == 0ull) {
+        int w[4] = {nx, ny, nz, depth};
+        wave_sum32<4>(w);
+        const int t = totals_to_lanes<4>(w);
+        const uint32_t lane = threadIdx.x & 63u;
+        long long* plane = lane < 3u ? acc.normal : acc.depth; // (either may be absent)
+        const uint32_t ch = lane < 3u ? lane : 0u;
+        if (lane < 4u && t && plane) atomicAdd((unsigned long long*)plane + ch * acc.n + p0, (unsigned long long)(long long)t);
+    } else accum_aux_merged_runs(acc, pix, nx, ny, nz, depth);
+}
+RR_DEV void accum_depth_wide_merged(const DAccum& acc, uint32_t pix, long long depth) {
+    uint32_t p0 = 0u;
+    const int one = wave_one_pixel(pix, 0xffffffffu, &p0);
+    if (one == 0) return;
+    if (one == 1) { // (a depth term is clamped to 1e9 * 2^16 < 2^46: 64 of them are far inside 64 bits)
+        const unsigned long long t = wave_sum64(pix != 0xffffffffu ? (unsigned long long)depth : 0ull);
+        if ((threadIdx.x & 63u) == 63u && acc.depth && t) atomicAdd((unsigned long long*)acc.depth + p0, t);
+    } else accum_depth_wide_merged_runs(acc, pix, depth);
+}
+// A shaded hit's colour sums and its root's aux sums together (k_shade: sum_pix and aux_pix are the hit's own pixel, where set): one
+// test, one bound ballot and seven sums where the wave's colour lanes and aux lanes name one pixel, the two entries above otherwise.
+RR_DEV void accum_hit_merged(const DAccum& acc, uint32_t sum_pix, int r, int g, int b, uint32_t aux_pix, int nx, int ny, int nz, int depth) {
+    uint32_t p0 = 0u;
+    const int one = wave_one_pixel(sum_pix, aux_pix, &p0);
+    if (sum_pix == 0xffffffffu) r = g = b = 0;
+    if (aux_pix == 0xffffffffu) nx = ny = nz = depth = 0;
+    int w[7] = {r, g, b, nx, ny, nz, depth};
+    if (one == 1 && __ballot(!fits25(w)) == 0ull) {
+        wave_sum32<7>(w);
+        const int t = totals_to_lanes<7>(w);
+        const uint32_t lane = threadIdx.x & 63u;
+        long long* plane = lane < 3u ? acc.rgb : (lane < 6u ? acc.normal : acc.depth); // (normal or depth may be absent)
+        const uint32_t ch = lane < 3u ? lane : (lane < 6u ? lane - 3u : 0u);
+        if (lane < 7u && t && plane) atomicAdd((unsigned long long*)plane + ch * acc.n + p0, (unsigned long long)(long long)t);
+    } else {
+        accum_merged(acc, sum_pix, r, g, b);
+        accum_aux_merged(acc, aux_pix, nx, ny, nz, depth);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -177,6 +304,8 @@ RR_DEV float resolve_depth_sum(long long fix, uint32_t nf, float n) {
 RR_DEV float resolve_depth(const DAccum& acc, uint32_t p, uint32_t nf, float n) { return resolve_depth_sum(acc.depth[p], nf, n); }
 
 #undef RR_DPP_SHR
+#undef RR_DPP_ADD
+#undef RR_DPP_ADD_ROWS
 #undef RR_DPP_SHL
 #undef RR_DPP_SHR64
 #undef RR_SEG_STEP

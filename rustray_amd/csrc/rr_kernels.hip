@@ -627,16 +627,22 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             }
         }
         if (nf) atomicOr(&acc.flags[pix_of_nf], nf); // rare: a non-finite term
-        accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
-        if constexpr (SPLIT) accum_merged(dacc, dif_pix, dif_r, dif_g, dif_b);
-        if ((acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull) {
-            if (__ballot(aux_d == RR_DEPTH_WIDE) != 0ull) { // hits beyond 512 units: their depth terms in 64 bits, merged per pixel
-                long long wide = 0ll;
-                if (aux_d == RR_DEPTH_WIDE) { wide = to_fix(__uint_as_float(qin.hit[i].x), RR_DEPTH_SCALE, 1.0e9f); aux_d = 0; }
-                accum_depth_wide_merged(acc, wide != 0ll ? aux_pix : 0xffffffffu, wide);
-            }
-            accum_aux_merged(acc, aux_pix, aux_nx, aux_ny, aux_nz, aux_d);
+        // One-pixel packets exist on level 1 only, so only the PRIMARY build asks for them (accum_hit_merged: one test, seven wave sums, one
+        // atomic instruction); the deeper levels' compacted waves would pay for the test and never pass it.  The SPLIT builds sit at 128
+        // VGPRs and spill to scratch with the test in them: they keep the segmented forms too.
+        const bool with_aux = (acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull;
+        if (with_aux && __ballot(aux_d == RR_DEPTH_WIDE) != 0ull) { // hits beyond 512 units: their depth terms in 64 bits, merged per pixel
+            long long wide = 0ll;
+            if (aux_d == RR_DEPTH_WIDE) { wide = to_fix(__uint_as_float(qin.hit[i].x), RR_DEPTH_SCALE, 1.0e9f); aux_d = 0; }
+            if constexpr (SPLIT || !PRIMARY) accum_depth_wide_merged_runs(acc, wide != 0ll ? aux_pix : 0xffffffffu, wide);
+            else accum_depth_wide_merged(acc, wide != 0ll ? aux_pix : 0xffffffffu, wide);
         }
+        if constexpr (SPLIT || !PRIMARY) {
+            accum_merged_runs(acc, sum_pix, sum_r, sum_g, sum_b);
+            if constexpr (SPLIT) accum_merged_runs(dacc, dif_pix, dif_r, dif_g, dif_b);
+            if (with_aux) accum_aux_merged_runs(acc, aux_pix, aux_nx, aux_ny, aux_nz, aux_d);
+        } else if (with_aux) accum_hit_merged(acc, sum_pix, sum_r, sum_g, sum_b, aux_pix, aux_nx, aux_ny, aux_nz, aux_d); // (colour and aux sums in one merge)
+        else accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
         {
             // one allocation for all children of the workgroup iteration: per wave the reflection rays first, then the refraction rays
             const unsigned long long m_refl = __ballot(spawn_refl), m_refr = __ballot(spawn_refr);
@@ -876,8 +882,11 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADOW_WAVES) void k_trace_shadow(DSce
             }
             }
         }
-        accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
-        if constexpr (SPLIT) accum_merged(dacc, sum_pix, dif_r, dif_g, dif_b);
+        // (fixed slots: a packet is the shadow rays of one pixel's hits, and asks for the one-pixel form; the dense queue's packets are
+        // compacted, and the SPLIT builds spill to scratch with the test in them: both keep the segmented form)
+        if constexpr (FIXED && !SPLIT) accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
+        else accum_merged_runs(acc, sum_pix, sum_r, sum_g, sum_b);
+        if constexpr (SPLIT) accum_merged_runs(dacc, sum_pix, dif_r, dif_g, dif_b);
         }
     }
 }
@@ -1870,7 +1879,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_albedo_level1(const DShadeConst* _
                 if (nf) atomicOr(&acc.flags[pix], nf); // rare: a non-finite base colour
             }
         }
-        accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);
+        accum_merged_runs(acc, sum_pix, sum_r, sum_g, sum_b); // (the segmented form: the one-pixel test's scalars take this kernel from 8 waves per SIMD to 7)
     }
 }
 
@@ -2413,6 +2422,11 @@ __global__ __launch_bounds__(RR_BLOCK) void k_motion_records(const TpFrame f, co
 // op 12: philox4x32_10 of caller-given words, as bit patterns: n = 2 m, entry i < m has the counter (a[i], b[i], c[i], a[m + i]) = (pixel,
 // sample, node, stream) and the key (seed_lo, seed_hi); out0[i], out1[i] = the two words jitter() uses.  (op 14 is the HOST build of the same
 // function, rr_api_probe.h.)
+// op 13: the wave merges of rr_accumulate.h as the kernels call them, words as bit patterns: n = 9 * 256, and lane l of the ONE workgroup
+// that works (four waves) takes a[k * 256 + l], k = 0 .. 8: colour pixel, r, g, b, aux pixel, nx, ny, nz, depth (b[l]: the depth's high
+// word for entry 3).  A pixel is a slot below 128 or 0xffffffff (anything else counts as that).  seed_lo picks the entry: 0 accum_merged,
+// 1 accum_aux_merged, 2 accum_hit_merged, 3 accum_depth_wide_merged.  out0, zeroed by the host, is a DAccum of 128 slots: seven planes of
+// 128 64-bit sums (r, g, b, nx, ny, nz, depth).
 // ---------------------------------------------------------------------------
 __global__ void k_math_probe(int op, const float* a, const float* b, const float* c, int n, float* out0, float* out1, float* out2,
                              uint32_t seed_lo, uint32_t seed_hi) {
@@ -2445,5 +2459,17 @@ __global__ void k_math_probe(int op, const float* a, const float* b, const float
             philox4x32_10(__float_as_uint(a[i]), __float_as_uint(b[i]), __float_as_uint(c[i]), __float_as_uint(a[m + i]), seed_lo, seed_hi, &r0, &r1);
             out0[i] = __uint_as_float(r0); out1[i] = __uint_as_float(r1);
         }
+    }
+    else if (op == 13) {
+        if (blockIdx.x != 0 || blockDim.x != 256 || n < 9 * 256) return; // (uniform: all 64 lanes of the four waves go on)
+        int w[9];
+        for (int k = 0; k < 9; k++) w[k] = __float_as_int(a[k * 256 + (int)threadIdx.x]);
+        const uint32_t sum_pix = (uint32_t)w[0] < 128u ? (uint32_t)w[0] : 0xffffffffu, aux_pix = (uint32_t)w[4] < 128u ? (uint32_t)w[4] : 0xffffffffu;
+        DAccum acc;
+        acc.rgb = (long long*)out0; acc.normal = acc.rgb + 3 * 128; acc.depth = acc.rgb + 6 * 128; acc.object_id = nullptr; acc.n = 128ull; acc.flags = nullptr;
+        if (seed_lo == 0u) accum_merged(acc, sum_pix, w[1], w[2], w[3]);
+        else if (seed_lo == 1u) accum_aux_merged(acc, aux_pix, w[5], w[6], w[7], w[8]);
+        else if (seed_lo == 2u) accum_hit_merged(acc, sum_pix, w[1], w[2], w[3], aux_pix, w[5], w[6], w[7], w[8]);
+        else if (seed_lo == 3u) accum_depth_wide_merged(acc, aux_pix, (long long)(((unsigned long long)__float_as_uint(b[threadIdx.x]) << 32) | (uint32_t)w[8]));
     }
 }

@@ -17,10 +17,18 @@ S = "rr_surface.h"     # textures and jitter
 PATCHES = {
     "nojit": [(S, "    if (spread <= 0.0f) return dir;\n    f3 b3 = normalize3(dir);", "    return dir;\n    f3 b3 = normalize3(dir);")],
     "nopow": [(K, "const float light_power = powf(spec_dot, m.shininess);", "const float light_power = spec_dot;")],
-    "noacc": [(K, "        accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);\n        if ((acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull) {\n",
-               "        if (sum_r == 0x7fffffffffffll) acc.flags[0] = (uint32_t)(sum_g + sum_b + aux_nx + aux_ny + aux_nz + aux_d + sum_pix + aux_pix);\n        if (false) {\n")],
-    "noaux": [(K, "        if ((acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull) {\n",
-               "        if (aux_d == 0x7fffffffffffll) acc.flags[0] = (uint32_t)(aux_nx + aux_ny + aux_nz + aux_pix);\n        if (false) {\n")],
+    "noaux": [(K, "        const bool with_aux = (acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull;\n",
+               "        if ((aux_nx ^ aux_ny ^ aux_nz ^ aux_d ^ (int)aux_pix) == 0x5a5a5a5b) acc.flags[0] = aux_pix;\n        const bool with_aux = false;\n")],
+    # The merges and their atomics alone (round 24): every lane sum stays alive behind one runtime comparison, k_shade's and k_trace_shadow's.
+    # (Round 3's "noacc" compared a 32-bit lane sum with a 64-bit constant: the test folded to false and took the shading with it.)
+    "nomerge": [(K, "        const bool with_aux = (acc.normal || acc.depth) && __ballot(aux_pix != 0xffffffffu) != 0ull;\n",
+                 "        if ((sum_r ^ sum_g ^ sum_b ^ aux_nx ^ aux_ny ^ aux_nz ^ aux_d ^ (int)sum_pix ^ (int)aux_pix) == 0x5a5a5a5b) acc.flags[0] = sum_pix;\n        const bool with_aux = false;\n"),
+                (K, "        if constexpr (SPLIT || !PRIMARY) {\n            accum_merged_runs(acc, sum_pix, sum_r, sum_g, sum_b);\n            if constexpr (SPLIT) accum_merged_runs(dacc, dif_pix, dif_r, dif_g, dif_b);\n            if (with_aux) accum_aux_merged_runs(acc, aux_pix, aux_nx, aux_ny, aux_nz, aux_d);\n        } else if (with_aux) accum_hit_merged(acc, sum_pix, sum_r, sum_g, sum_b, aux_pix, aux_nx, aux_ny, aux_nz, aux_d); // (colour and aux sums in one merge)\n        else accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);\n", "")],
+    # k_shade with the colour sums and the aux sums merged by two calls, each with its own one-pixel test, instead of accum_hit_merged
+    "twomerge": [(K, "        } else if (with_aux) accum_hit_merged(acc, sum_pix, sum_r, sum_g, sum_b, aux_pix, aux_nx, aux_ny, aux_nz, aux_d); // (colour and aux sums in one merge)\n        else accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);\n",
+                  "        } else { accum_merged(acc, sum_pix, sum_r, sum_g, sum_b); if (with_aux) accum_aux_merged(acc, aux_pix, aux_nx, aux_ny, aux_nz, aux_d); }\n")],
+    "nomerge_sh": [(K, "        if constexpr (FIXED && !SPLIT) accum_merged(acc, sum_pix, sum_r, sum_g, sum_b);\n        else accum_merged_runs(acc, sum_pix, sum_r, sum_g, sum_b);\n        if constexpr (SPLIT) accum_merged_runs(dacc, sum_pix, dif_r, dif_g, dif_b);\n",
+                    "        if ((sum_r ^ sum_g ^ sum_b ^ (int)sum_pix) == 0x5a5a5a5b) acc.flags[0] = sum_pix;\n")],
     "nosq": [(K, "                if (sq_fixed) sq_wrote |= 1u << lk;", "                if (false) sq_wrote |= 1u << lk;"),
              (K, "                sq.s0[si] = make_float4(so.x, so.y, so.z, limit);\n                sq.s1[si] = make_float4(sd.x, sd.y, sd.z, __uint_as_float((uint32_t)item_idx | (depth << 27)));\n                sq.s2[si] = make_float4(cr, cg, cb, __uint_as_float(pix));\n",
               "                if (so.x + sd.x + cr + cg + cb + limit == 12345.678f) sq.s0[si] = make_float4(so.y, so.z, sd.y, sd.z);\n")],
@@ -48,7 +56,7 @@ def build(name):
                     raise SystemExit(f"{name}: pattern of {part} found {s.count(old)} times in {f}")
                 open(p, "w").write(s.replace(old, new))
         out = os.path.join(ROOT, "build", f"lib_abl_{name}.so")
-        subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-Wno-unused-function",
+        subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "--offload-arch=gfx950", "-Wno-unused-function",
                                "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-shared", "-o", out, "rr_api.hip", "rr_bvh.cpp"],
                               cwd=os.path.join(d, "rustray_amd", "csrc"))
         print("built", out)

@@ -16,7 +16,7 @@ asm = os.path.join(ROOT, "build", "rr_api_g.s")
 csrc = os.path.join(ROOT, "rustray_amd", "csrc")
 os.makedirs(os.path.dirname(asm), exist_ok=True)
 if not os.path.exists(asm) or os.path.getmtime(asm) < max(os.path.getmtime(os.path.join(csrc, f)) for f in LIB_SOURCES):
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-Wno-unused-function",
+    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "--offload-arch=gfx950", "-Wno-unused-function",
                            "-gline-tables-only", "-S", "--cuda-device-only", "-o", asm, "rr_api.hip"], cwd=csrc, stderr=subprocess.DEVNULL)
 lines = open(asm).read().splitlines()
 files = {}
