@@ -64,7 +64,9 @@ extern "C" {
  * rr_accumulate_split_records and rr_accumulate_split_records_device came after those in the same way: a version-3 library may lack
  * these two as well.
  * rr_history_clamp_default_params, rr_accumulate_clamped_records and rr_accumulate_clamped_records_device (with rr_history_clamp_params, a
- * struct of its own) came after those, again without a change of any existing struct: a version-3 library may lack these three as well. */
+ * struct of its own) came after those, again without a change of any existing struct: a version-3 library may lack these three as well.
+ * rr_accumulate_clamped_split_records and rr_accumulate_clamped_split_records_device came after those, without a struct of their own: a
+ * version-3 library may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1242,6 +1244,73 @@ int rr_accumulate_clamped_records(rr_scene* scene, const rr_camera* camera, cons
                                   const float* history_length /* n, or NULL */, const float* motion /* 3n, or NULL */,
                                   rr_radiance* out /* n; not records */, rr_radiance* halves_out /* 2n, or NULL */, float* length_out /* n */,
                                   uint8_t* rgba8_out /* or NULL */);
+
+/* Temporal accumulation of a split frame with the history held to the current frame: rr_accumulate_split_records with the clamp of
+ * rr_accumulate_clamped_records on the colour layers and a clamp of its own on the diffuse layers, in one launch -- the split pipeline
+ * for a scene whose lights, materials, textures or flags are edited while it is shown.  rr_accumulate_params, rr_history_clamp_params,
+ * its ranges and rr_history_clamp_default_params are those of the two calls; the diffuse arrays have rr_accumulate_split_records' layouts.
+ * EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE (rustray_amd/temporal.py: accumulate_clamped_split_records follows this text
+ * in numpy and gives the same bits):
+ *   Colour side.  Steps 1 .. 10 of rr_accumulate_clamped_records for the same records, halves, history, history_halves, history_length,
+ *      motion, params and clamp.  No diffuse value takes part in any decision about taps, sum_w, the colour box, N or a.  Hence out,
+ *      halves_out, length_out and rgba8_out are, bit for bit, what rr_accumulate_clamped_records writes for those arguments.
+ *   Diffuse means.  As rr_accumulate_split_records: for each layer L of diffuse, diffuse half 0 and diffuse half 1 (the halves only when
+ *      halves are given) per channel sum_d += w * d_q in tap order over the taken taps, starting from 0; hd = sum_d / sum_w.  A tap's
+ *      diffuse floats are read after everything else of the tap, and only when it is taken.
+ *   Diffuse box.  One per pixel that kept its history, from the current `diffuse` array (the full layer, not the halves), in the window
+ *      order of step 7: dy = -r .. r outside, dx = -r .. r inside, ascending.  q is taken when it lies inside the frame and the three
+ *      floats of diffuse at q are finite, whatever its colour holds.  The sums m, s1, s2, then mean, v, sd, e = sigma_scale * sd,
+ *      lo = mean - e and hi = mean + e are step 7's, and so is its rule that a channel in which s2 / (float)m, mean * mean or e is not
+ *      finite has no box (lo = -inf, hi = +inf).  Unlike the colour window, p itself may fail the test; if nothing is taken, m = 0,
+ *      s1 / 0.0f = 0.0f / 0.0f is a NaN, so is mean * mean, and by that rule no channel has a box.  Both diffuse halves are clamped to this
+ *      one box.
+ *   Diffuse clamp and blend.  Where the pixel kept its history and, for layer L, the three current floats cur of L at p and the three hd
+ *      are finite: hd' = hd < lo ? lo : (hd > hi ? hi : hd) per channel, and L at p is hd' + a * (cur - hd') with the FINAL a of the
+ *      colour side, after step 9.  In every other case -- no history, the first frame, !fin_p, !valid_p, a current triple that is not
+ *      finite, a history mean that is not finite -- the output holds the bits of the current L at p, as rr_accumulate_split_records says
+ *      (an infinite hd is NOT pulled onto a finite bound).  A moved diffuse layer does not shorten the length: only the record layer
+ *      decides it, in step 9.
+ *   What follows from that and the tests hold: every no-history path writes rr_accumulate_split_records' bits in all outputs.  A pixel
+ *      whose record layer was not moved (so N and a are step 6's) and in which a diffuse layer L stays inside the diffuse box has L's bits
+ *      from rr_accumulate_split_records.  A pixel in which no layer of either kind leaves its box equals rr_accumulate_split_records in
+ *      every output.  With cur and hd' finite and 0 < a <= 1 the diffuse blend cannot generate a NaN: the diffuse outputs are specified bit
+ *      for bit.
+ * rr_accumulate_clamped_split_records_device: the arguments of rr_accumulate_split_records_device in its order, `clamp` behind `params`;
+ * the pairing rules of rr_accumulate_split_records_device.
+ *   The call follows that one: every pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming the argument; pageable
+ *   memory is refused); the record pointers 16-byte aligned, the float pointers 4-byte aligned; ONE launch (and one for the bytes)
+ *   enqueued on `hip_stream` in stream order, not waited for; the scene's lock; RR_ERR_INVALID_ARGUMENT from on_pass of the same scene;
+ *   nothing of a frame's state or statistics is touched.  The call keeps no device memory.
+ *   out_dev MAY NOT OVERLAP records_dev AND diffuse_out_dev MAY NOT OVERLAP diffuse_dev AT ALL, not even in place: the windows read the
+ *   records and the diffuse of other pixels, which another workgroup may already have overwritten.  RR_ERR_INVALID_ARGUMENT, and
+ *   rr_last_error names both and says why.  halves_out_dev == halves_dev and diffuse_halves_out_dev == diffuse_halves_dev stay allowed:
+ *   those are read at p only.  Every other overlap between an output and an input, or between two outputs, is RR_ERR_INVALID_ARGUMENT
+ *   naming both.
+ *   Refusals: those of rr_accumulate_split_records_device and those of rr_accumulate_clamped_records_device for `clamp`, each naming the
+ *   argument or field and the function.  width * height * 2 > 2^30: RR_ERR_UNSUPPORTED before anything is allocated.
+ * rr_accumulate_clamped_split_records: the same on HOST pointers (the two overlaps are refused there too), the device form on the null
+ * stream behind staging copies in the handle's pool, sixteen arrays of rr_accumulate_split_records' sizes; it returns with the outputs
+ * written. */
+int rr_accumulate_clamped_split_records_device(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                                               const rr_history_clamp_params* clamp,
+                                               const rr_radiance* records_dev /* n */, const rr_radiance* halves_dev /* 2n, or NULL */,
+                                               const float* diffuse_dev /* 3n */, const float* diffuse_halves_dev /* 6n; NULL exactly when halves_dev is */,
+                                               const rr_radiance* history_dev /* n, or NULL */, const rr_radiance* history_halves_dev /* 2n, or NULL */,
+                                               const float* history_diffuse_dev /* 3n, or NULL */, const float* history_diffuse_halves_dev /* 6n, or NULL */,
+                                               const float* history_length_dev /* n, or NULL */, const float* motion_dev /* 3n, or NULL */,
+                                               rr_radiance* out_dev /* n; not records_dev */, rr_radiance* halves_out_dev /* 2n, or NULL */,
+                                               float* diffuse_out_dev /* 3n; not diffuse_dev */, float* diffuse_halves_out_dev /* 6n, or NULL */,
+                                               float* length_out_dev /* n */, uint8_t* rgba8_out_dev /* or NULL */, void* hip_stream);
+int rr_accumulate_clamped_split_records(rr_scene* scene, const rr_camera* camera, const rr_accumulate_params* params,
+                                        const rr_history_clamp_params* clamp,
+                                        const rr_radiance* records /* n */, const rr_radiance* halves /* 2n, or NULL */,
+                                        const float* diffuse /* 3n */, const float* diffuse_halves /* 6n; NULL exactly when halves is */,
+                                        const rr_radiance* history /* n, or NULL */, const rr_radiance* history_halves /* 2n, or NULL */,
+                                        const float* history_diffuse /* 3n, or NULL */, const float* history_diffuse_halves /* 6n, or NULL */,
+                                        const float* history_length /* n, or NULL */, const float* motion /* 3n, or NULL */,
+                                        rr_radiance* out /* n; not records */, rr_radiance* halves_out /* 2n, or NULL */,
+                                        float* diffuse_out /* 3n; not diffuse */, float* diffuse_halves_out /* 6n, or NULL */,
+                                        float* length_out /* n */, uint8_t* rgba8_out /* or NULL */);
 
 /* The motion of moved items per pixel: what rr_accumulate_records takes as motion when items moved between the frame the history was
  * rendered from and the current one (rr_scene_update_transforms, rr_scene_set_items), computed on the device from the records it holds.

@@ -972,6 +972,52 @@ public:
                                                   history_halves_dev, history_diffuse_dev, history_diffuse_halves_dev, history_length_dev, motion_dev, out_dev,
                                                   halves_out_dev, diffuse_out_dev, diffuse_halves_out_dev, length_out_dev, rgba8_out_dev, hip_stream);
     }
+    // accumulate_split() with the history held to the current frame (rr_accumulate_clamped_split_records): the colour layers as
+    // accumulate_clamped() holds them, the diffuse layers to the box of the current `diffuse` around each pixel.  The arguments are
+    // accumulate_split()'s behind `clamp`; the result feeds denoise_split as it is.
+    SplitHistory accumulate_clamped_split(const HistoryClamp& clamp, const rr_radiance* records, const rr_radiance* halves, const float* diffuse,
+                                          const float* diffuse_halves, const SplitHistory* history, const rr_accumulate_params* params = nullptr,
+                                          const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+        SplitHistory out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_accumulate_params prm;
+        if (params) prm = *params;
+        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
+        if (!records || !diffuse || n == 0 || n > ((size_t)1 << 29)) return out;
+        const bool first = !history || history->empty();
+        const bool hist_halves = !first && !history->halves.empty();
+        const rr_camera cam = camera.c_struct();
+        out.records.resize(n);
+        out.length.assign(n, 0.0f);
+        out.diffuse.resize(3 * n);
+        if (halves) { out.halves.resize(2 * n); out.diffuse_halves.resize(6 * n); }
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_accumulate_clamped_split_records(scene->handle(), &cam, &prm, &clamp, records, halves, diffuse, diffuse_halves,
+                                                first ? nullptr : history->records.data(), hist_halves ? history->halves.data() : nullptr,
+                                                first || history->diffuse.empty() ? nullptr : history->diffuse.data(),
+                                                hist_halves && !history->diffuse_halves.empty() ? history->diffuse_halves.data() : nullptr,
+                                                first ? nullptr : history->length.data(), motion, out.records.data(), halves ? out.halves.data() : nullptr,
+                                                out.diffuse.data(), halves ? out.diffuse_halves.data() : nullptr, out.length.data(),
+                                                rgba8 ? rgba8->data() : nullptr) != RR_OK) {
+            out = SplitHistory();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_accumulate_clamped_split_records_device): not waited for; out_dev may not be records_dev
+    // and diffuse_out_dev not diffuse_dev
+    int accumulate_clamped_split_device(const rr_accumulate_params& params, const HistoryClamp& clamp, const rr_radiance* records_dev, const rr_radiance* halves_dev,
+                                        const float* diffuse_dev, const float* diffuse_halves_dev, const rr_radiance* history_dev,
+                                        const rr_radiance* history_halves_dev, const float* history_diffuse_dev, const float* history_diffuse_halves_dev,
+                                        const float* history_length_dev, const float* motion_dev, rr_radiance* out_dev, rr_radiance* halves_out_dev,
+                                        float* diffuse_out_dev, float* diffuse_halves_out_dev, float* length_out_dev, uint8_t* rgba8_out_dev,
+                                        void* hip_stream) const {
+        const rr_camera cam = camera.c_struct();
+        return rr_accumulate_clamped_split_records_device(scene->handle(), &cam, &params, &clamp, records_dev, halves_dev, diffuse_dev, diffuse_halves_dev,
+                                                          history_dev, history_halves_dev, history_diffuse_dev, history_diffuse_halves_dev, history_length_dev,
+                                                          motion_dev, out_dev, halves_out_dev, diffuse_out_dev, diffuse_halves_out_dev, length_out_dev,
+                                                          rgba8_out_dev, hip_stream);
+    }
 
     // What motion() returns: width * height * 3 floats of motion, and of world points where asked for.
     struct Motion {

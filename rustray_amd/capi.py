@@ -23,7 +23,7 @@ _LIB = None
 EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
            "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
            "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_accumulate_split_records", "rr_accumulate_split_records_device", "rr_history_clamp_default_params", "rr_accumulate_clamped_records", "rr_accumulate_clamped_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
+           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_accumulate_split_records", "rr_accumulate_split_records_device", "rr_history_clamp_default_params", "rr_accumulate_clamped_records", "rr_accumulate_clamped_records_device", "rr_accumulate_clamped_split_records", "rr_accumulate_clamped_split_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
 
 
 class rr_shadow_hit(C.Structure):
@@ -201,6 +201,10 @@ def lib():
             clamped = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params), C.POINTER(rr_history_clamp_params)]
             L.rr_accumulate_clamped_records.argtypes = clamped + [C.c_void_p] * 10
             L.rr_accumulate_clamped_records_device.argtypes = clamped + [C.c_void_p] * 11
+        if hasattr(L, "rr_accumulate_clamped_split_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
+            clamped = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params), C.POINTER(rr_history_clamp_params)]
+            L.rr_accumulate_clamped_split_records.argtypes = clamped + [C.c_void_p] * 16
+            L.rr_accumulate_clamped_split_records_device.argtypes = clamped + [C.c_void_p] * 17
         L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
         L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
@@ -1014,6 +1018,44 @@ class DeviceScene:
         _check(lib().rr_accumulate_clamped_records_device(self._h, C.byref(cam), C.byref(p), C.byref(c), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
                                                           _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
                                                           _ptr(halves_out_ptr), _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
+
+    def accumulate_clamped_split(self, cam: rr_camera, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
+                                 history_diffuse_halves=None, history_length=None, motion=None, params=None, clamp=None, rgba8: bool = False,
+                                 halves_in_place: bool = False) -> dict:
+        """rr_accumulate_clamped_split_records: temporal.accumulate_clamped_split_records on the device, host arrays in and out.  The
+        arguments of accumulate_split, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  Returns accumulate_split's
+        dict; halves_in_place accumulates into copies of `halves` and `diffuse_halves` (out can never be records, diffuse_out never diffuse)."""
+        n = int(cam.width) * int(cam.height)
+        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
+        cur = lambda a, shape: None if a is None else (np.array(a, np.float32, order="C").reshape(shape) if halves_in_place else arr(a, shape))
+        rec, hv, df, dh = arr(records, (n, 8)), cur(halves, (n, 2, 8)), arr(diffuse, (n, 3)), cur(diffuse_halves, (n, 2, 3))
+        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
+        hist_d, hist_dh = arr(history_diffuse, (n, 3)), arr(history_diffuse_halves, (n, 2, 3))
+        new = lambda a, shape: None if a is None else (a if halves_in_place else np.zeros(shape, np.float32))
+        out, out_h, out_d, out_dh = np.zeros((n, 8), np.float32), new(hv, (n, 2, 8)), np.zeros((n, 3), np.float32), new(dh, (n, 2, 3))
+        length = np.zeros(n, np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        p, c = accumulate_params(params), history_clamp_params(clamp)
+        _check(lib().rr_accumulate_clamped_split_records(self._h, C.byref(cam), C.byref(p), C.byref(c), _data(rec), _data(hv), _data(df), _data(dh), _data(hist),
+                                                         _data(hist_h), _data(hist_d), _data(hist_dh), _data(hist_l), _data(mv), _data(out), _data(out_h), _data(out_d),
+                                                         _data(out_dh), _data(length), _data(rgba)))
+        res = dict(records=out, length=length, halves=out_h, diffuse=out_d, diffuse_halves=out_dh)
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def accumulate_clamped_split_device(self, cam: rr_camera, records_ptr, halves_ptr, diffuse_ptr, diffuse_halves_ptr, history_ptr, history_halves_ptr,
+                                        history_diffuse_ptr, history_diffuse_halves_ptr, history_length_ptr, motion_ptr, out_ptr, halves_out_ptr, diffuse_out_ptr,
+                                        diffuse_halves_out_ptr, length_out_ptr, rgba8_ptr=None, params=None, clamp=None, stream_ptr=None):
+        """rr_accumulate_clamped_split_records_device: the buffers of accumulate_split_device (out_ptr may NOT be records_ptr and
+        diffuse_out_ptr NOT diffuse_ptr; the two halves outputs may be their inputs), all raw device pointers (None where the call has none),
+        in the order of the C arguments; enqueued on `stream_ptr`, not waited for."""
+        p, c = accumulate_params(params), history_clamp_params(clamp)
+        _check(lib().rr_accumulate_clamped_split_records_device(self._h, C.byref(cam), C.byref(p), C.byref(c), _ptr(records_ptr), _ptr(halves_ptr), _ptr(diffuse_ptr),
+                                                                _ptr(diffuse_halves_ptr), _ptr(history_ptr), _ptr(history_halves_ptr), _ptr(history_diffuse_ptr),
+                                                                _ptr(history_diffuse_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
+                                                                _ptr(halves_out_ptr), _ptr(diffuse_out_ptr), _ptr(diffuse_halves_out_ptr), _ptr(length_out_ptr),
+                                                                _ptr(rgba8_ptr), _ptr(stream_ptr)))
 
     # -- the motion of moved items per pixel -------------------------------------------
     @staticmethod

@@ -517,6 +517,43 @@ extern "C" int rh_accumulate_clamped(void* h, float fov, const float* eye, const
     if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
     return 0;
 }
+// Raytracing::accumulate_clamped_split (on_device == 0: host pointers, through a SplitHistory; returns 0, or -1 when the call was refused)
+// and Raytracing::accumulate_clamped_split_device (on_device != 0: device pointers and `stream`; returns its rr_status): radius and
+// sigma_scale as rh_accumulate_clamped takes them, then the arguments of rh_accumulate_split.
+extern "C" int rh_accumulate_clamped_split(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                           uint32_t w, uint32_t hgt, const rr_accumulate_params* params, uint32_t radius, float sigma_scale,
+                                           const rr_radiance* records, const rr_radiance* halves, const float* diffuse, const float* diffuse_halves,
+                                           const rr_radiance* history, const rr_radiance* history_halves, const float* history_diffuse,
+                                           const float* history_diffuse_halves, const float* history_length, const float* motion, rr_radiance* out,
+                                           rr_radiance* halves_out, float* diffuse_out, float* diffuse_halves_out, float* length_out, uint8_t* rgba8, int on_device,
+                                           void* stream) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    const Raytracing::HistoryClamp clamp = radius ? Raytracing::HistoryClamp(radius, sigma_scale) : Raytracing::HistoryClamp();
+    if (on_device)
+        return rt.accumulate_clamped_split_device(*params, clamp, records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse,
+                                                  history_diffuse_halves, history_length, motion, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8,
+                                                  stream);
+    const size_t n = (size_t)w * hgt;
+    Raytracing::SplitHistory hist;
+    if (history) {
+        hist.records.assign(history, history + n);
+        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
+        if (history_diffuse) hist.diffuse.assign(history_diffuse, history_diffuse + 3 * n);
+        if (history_diffuse_halves) hist.diffuse_halves.assign(history_diffuse_halves, history_diffuse_halves + 6 * n);
+        if (history_length) hist.length.assign(history_length, history_length + n);
+    }
+    std::vector<uint8_t> bytes;
+    const Raytracing::SplitHistory r = rt.accumulate_clamped_split(clamp, records, halves, diffuse, diffuse_halves, history ? &hist : nullptr, params, motion,
+                                                                   rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
+    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
+    std::memcpy(diffuse_out, r.diffuse.data(), 3 * n * 4);
+    if (diffuse_halves_out && !r.diffuse_halves.empty()) std::memcpy(diffuse_halves_out, r.diffuse_halves.data(), 6 * n * 4);
+    std::memcpy(length_out, r.length.data(), n * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
 // Raytracing::motion: records = w * h, item_index = n_moved indices, prev_trans = n_moved * 16 floats (column-major); motion_out = w * h * 3
 // floats, world_out the same or NULL; returns 0, or -1 when the call was refused.
 // rh_motion_records_device: Raytracing::motion_device on device pointers and a stream; returns its rr_status.

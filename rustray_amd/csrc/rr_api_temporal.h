@@ -2,12 +2,13 @@
 // current frame and the current records are blended into it, the step before rr_denoise_records in a frame-after-frame loop.
 // Offers: rr_accumulate_default_params, rr_accumulate_records_device, rr_accumulate_records, rr_accumulate_split_records_device,
 //         rr_accumulate_split_records, rr_history_clamp_default_params, rr_accumulate_clamped_records_device,
-//         rr_accumulate_clamped_records; tp_frame (for rr_api_motion.h).
+//         rr_accumulate_clamped_records, rr_accumulate_clamped_split_records_device, rr_accumulate_clamped_split_records; tp_frame (for
+//         rr_api_motion.h).
 // Needs:  rr_api_query.h (check_arg_ranges, record_call, staged_host_call), rr_api_adaptive.h (launch_record_bytes), rr_temporal.h,
-//         rr_history_clamp.h, kernels 7e, 7e' and 7e'' of rr_kernels.hip.
+//         rr_history_clamp.h, kernels 7e, 7e', 7e'' and 7e''' of rr_kernels.hip.
 //
 // The call is ONE launch of k_accumulate_records (with or without halves; the split call: of k_accumulate_split_records; the clamped
-// call: of k_accumulate_clamped_records) and, for the
+// call: of k_accumulate_clamped_records; the clamped split call: of k_accumulate_clamped_split_records) and, for the
 // bytes, k_record_bytes, on the caller's stream, not waited for.  It keeps no working data.  The host form is the device form behind the staging of every record call
 // (staged_host_call, in the handle's pool).
 
@@ -306,3 +307,111 @@ int rr_accumulate_clamped_records(rr_scene* s, const rr_camera* camera, const rr
         });
     });
 } RR_GUARD_END("rr_accumulate_clamped_records")
+
+// ---- rr_accumulate_clamped_split_records: the split call with the colour history held to the box of the current colours and the diffuse
+// history to the box of the current diffuse layer
+// what it checks: the union of the split call's and the clamped call's rules, with `out` allowed nowhere on `records` and `diffuse_out`
+// nowhere on `diffuse` (both windows read other pixels, which another workgroup may already have overwritten)
+static int check_accumulate_clamped_split_args(const char* fn, bool device, const rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm,
+                                               const rr_history_clamp_params* clamp, const AccumulateIo& io, const TpSplitIo& d) {
+    RR_TRY(check_accumulate_basics(fn, device, s, cam, prm, io));
+    if (!clamp) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp is NULL", fn);
+    if (clamp->struct_size != sizeof(rr_history_clamp_params))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->struct_size %u, expected %u", fn, clamp->struct_size, (unsigned)sizeof(rr_history_clamp_params));
+    if (clamp->radius != 1u && clamp->radius != 2u) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->radius %u, must be 1 or 2", fn, clamp->radius);
+    if (!(clamp->sigma_scale >= 0.0f && clamp->sigma_scale <= 65536.0f)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: clamp->sigma_scale must lie in 0 .. 65536", fn);
+    if (!d.diffuse) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse is NULL", fn);
+    if (!d.diffuse_out) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_out is NULL", fn);
+    if ((d.dif_halves != nullptr) != (io.halves != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_halves is required exactly when halves is given", fn);
+    if ((d.dif_halves_out != nullptr) != (io.halves != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_halves_out is required exactly when halves is given", fn);
+    if ((d.history_diffuse != nullptr) != (io.history != nullptr)) return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_diffuse is required exactly when history is given", fn);
+    if ((d.history_dif_halves != nullptr) != (io.history_halves != nullptr))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: history_diffuse_halves is required exactly when history_halves is given", fn);
+    if (device && (((uintptr_t)d.diffuse | (uintptr_t)d.dif_halves | (uintptr_t)d.history_diffuse | (uintptr_t)d.history_dif_halves | (uintptr_t)d.diffuse_out |
+                    (uintptr_t)d.dif_halves_out) & 3u))
+        return fail(RR_ERR_INVALID_ARGUMENT, "%s: diffuse_dev, diffuse_halves_dev, history_diffuse_dev, history_diffuse_halves_dev, diffuse_out_dev and diffuse_halves_out_dev must be 4-byte aligned", fn);
+    const uint64_t n = (uint64_t)cam->width * cam->height;
+    const ArgRange t[16] = {{io.records, 32u * n, "records", false, -1}, {io.halves, 64u * n, "halves", false, -1}, {d.diffuse, 12u * n, "diffuse", false, -1},
+                            {d.dif_halves, 24u * n, "diffuse_halves", false, -1}, {io.history, 32u * n, "history", false, -1},
+                            {io.history_halves, 64u * n, "history_halves", false, -1}, {d.history_diffuse, 12u * n, "history_diffuse", false, -1},
+                            {d.history_dif_halves, 24u * n, "history_diffuse_halves", false, -1}, {io.history_length, 4u * n, "history_length", false, -1},
+                            {io.motion, 12u * n, "motion", false, -1}, {io.out, 32u * n, "out", true, -1}, {io.halves_out, 64u * n, "halves_out", true, 1},
+                            {d.diffuse_out, 12u * n, "diffuse_out", true, -1}, {d.dif_halves_out, 24u * n, "diffuse_halves_out", true, 3},
+                            {io.length_out, 4u * n, "length_out", true, -1}, {io.rgba8, 4u * n, "rgba8_out", true, -1}};
+    return check_arg_ranges(fn, t, 16, false,
+                            " (the windows read the records and the diffuse of other pixels, so out may not be records and diffuse_out may not be diffuse; only "
+                            "halves_out == halves and diffuse_halves_out == diffuse_halves, in place, are allowed)");
+}
+
+static int accumulate_clamped_split_locked(rr_scene* s, const rr_camera* cam, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp,
+                                           const AccumulateIo& io, const TpSplitIo& split, hipStream_t st) {
+    const uint32_t W = cam->width, H = cam->height;
+    const TpFrame f = accumulate_frame(cam, prm);
+    const dim3 grid = accumulate_grid(cam), block(RR_BLOCK);
+    const float k = clamp->sigma_scale;
+    const float4 *rec = (const float4*)io.records, *hv = (const float4*)io.halves, *hist = (const float4*)io.history, *hist_h = (const float4*)io.history_halves;
+    float4 *out = (float4*)io.out, *out_h = (float4*)io.halves_out;
+    if (io.halves && clamp->radius == 1u)
+        hipLaunchKernelGGL((k_accumulate_clamped_split_records<true, 1>), grid, block, 0, st, f, k, rec, hv, hist, hist_h, io.history_length, io.motion, out, out_h,
+                           io.length_out, split);
+    else if (io.halves)
+        hipLaunchKernelGGL((k_accumulate_clamped_split_records<true, 2>), grid, block, 0, st, f, k, rec, hv, hist, hist_h, io.history_length, io.motion, out, out_h,
+                           io.length_out, split);
+    else if (clamp->radius == 1u)
+        hipLaunchKernelGGL((k_accumulate_clamped_split_records<false, 1>), grid, block, 0, st, f, k, rec, (const float4*)nullptr, hist, (const float4*)nullptr,
+                           io.history_length, io.motion, out, (float4*)nullptr, io.length_out, split);
+    else
+        hipLaunchKernelGGL((k_accumulate_clamped_split_records<false, 2>), grid, block, 0, st, f, k, rec, (const float4*)nullptr, hist, (const float4*)nullptr,
+                           io.history_length, io.motion, out, (float4*)nullptr, io.length_out, split);
+    if (io.rgba8) {
+        rr_config cfg{};
+        cfg.gamma_correction = prm->gamma_correction ? 1 : 0;
+        launch_record_bytes(s, &cfg, io.out, W * H, io.rgba8, st);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(RR_ERR_DEVICE, "rr_accumulate_clamped_split_records: a launch failed");
+    return RR_OK;
+}
+
+int rr_accumulate_clamped_split_records_device(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp,
+                                               const rr_radiance* records, const rr_radiance* halves, const float* diffuse, const float* diffuse_halves,
+                                               const rr_radiance* history, const rr_radiance* history_halves, const float* history_diffuse,
+                                               const float* history_diffuse_halves, const float* history_length, const float* motion, rr_radiance* out,
+                                               rr_radiance* halves_out, float* diffuse_out, float* diffuse_halves_out, float* length_out, uint8_t* rgba8_out,
+                                               void* hip_stream) try {
+    const char* fn = "rr_accumulate_clamped_split_records_device";
+    const AccumulateIo io{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out};
+    const TpSplitIo split{diffuse, diffuse_halves, history_diffuse, history_diffuse_halves, diffuse_out, diffuse_halves_out};
+    RR_TRY(check_accumulate_clamped_split_args(fn, true, s, camera, prm, clamp, io, split));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return record_call(s, fn, false, {{records, "records_dev"}, {halves, "halves_dev"}, {diffuse, "diffuse_dev"}, {diffuse_halves, "diffuse_halves_dev"},
+                                      {history, "history_dev"}, {history_halves, "history_halves_dev"}, {history_diffuse, "history_diffuse_dev"},
+                                      {history_diffuse_halves, "history_diffuse_halves_dev"}, {history_length, "history_length_dev"}, {motion, "motion_dev"},
+                                      {out, "out_dev"}, {halves_out, "halves_out_dev"}, {diffuse_out, "diffuse_out_dev"}, {diffuse_halves_out, "diffuse_halves_out_dev"},
+                                      {length_out, "length_out_dev"}, {rgba8_out, "rgba8_out_dev"}}, st,
+                       [&] { return accumulate_clamped_split_locked(s, camera, prm, clamp, io, split, st); });
+} RR_GUARD_END("rr_accumulate_clamped_split_records_device")
+
+int rr_accumulate_clamped_split_records(rr_scene* s, const rr_camera* camera, const rr_accumulate_params* prm, const rr_history_clamp_params* clamp,
+                                        const rr_radiance* records, const rr_radiance* halves, const float* diffuse, const float* diffuse_halves,
+                                        const rr_radiance* history, const rr_radiance* history_halves, const float* history_diffuse, const float* history_diffuse_halves,
+                                        const float* history_length, const float* motion, rr_radiance* out, rr_radiance* halves_out, float* diffuse_out,
+                                        float* diffuse_halves_out, float* length_out, uint8_t* rgba8_out) try {
+    const char* fn = "rr_accumulate_clamped_split_records";
+    RR_TRY(check_accumulate_clamped_split_args(fn, false, s, camera, prm, clamp,
+                                               AccumulateIo{records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8_out},
+                                               TpSplitIo{diffuse, diffuse_halves, history_diffuse, history_diffuse_halves, diffuse_out, diffuse_halves_out}));
+    const size_t n = (size_t)camera->width * camera->height;
+    const StageArg args[16] = {stage_input(records, 32 * n), stage_input(halves, 64 * n), stage_input(diffuse, 12 * n), stage_input(diffuse_halves, 24 * n),
+                               stage_input(history, 32 * n), stage_input(history_halves, 64 * n), stage_input(history_diffuse, 12 * n),
+                               stage_input(history_diffuse_halves, 24 * n), stage_input(history_length, 4 * n), stage_input(motion, 12 * n),
+                               stage_output(out, 32 * n), stage_output(halves_out, 64 * n), stage_output(diffuse_out, 12 * n), stage_output(diffuse_halves_out, 24 * n),
+                               stage_output(length_out, 4 * n), stage_output(rgba8_out, 4 * n)};
+    return record_call(s, fn, false, {}, nullptr, [&] {
+        return staged_host_call(s->record_stage.buf, args, [&](void* const* d) {
+            const AccumulateIo dev{(const rr_radiance*)d[0], (const rr_radiance*)d[1], (const rr_radiance*)d[4], (const rr_radiance*)d[5], (const float*)d[8],
+                                   (const float*)d[9], (rr_radiance*)d[10], (rr_radiance*)d[11], (float*)d[14], (uint8_t*)d[15]};
+            const TpSplitIo split{(const float*)d[2], (const float*)d[3], (const float*)d[6], (const float*)d[7], (float*)d[12], (float*)d[13]};
+            return accumulate_clamped_split_locked(s, camera, prm, clamp, dev, split, nullptr);
+        });
+    });
+} RR_GUARD_END("rr_accumulate_clamped_split_records")

@@ -3,6 +3,9 @@
 // of the current frame, the box they make, the clamp of one layer's history mean to it and the shorter length of a pixel whose record
 // layer had to be moved.  Plain host logic, no HIP call and no system include: k_accumulate_clamped_records (rr_kernels.hip) applies
 // these functions per lane between temporal_history and the blends, tests/native/temporal_clamp_test.cpp runs them as a host loop.
+// history_clamp_split is the same for rr_accumulate_clamped_split_records (k_accumulate_clamped_split_records,
+// tests/native/temporal_clamp_split_test.cpp; the yardstick is accumulate_clamped_split_records): the colour side as it stands, and a
+// box of the current diffuse layer for the three diffuse means.
 //
 // Every step is exact in binary32 in the order written here and must be compiled without contraction, as rr_temporal.h.
 #pragma once
@@ -90,4 +93,20 @@ RR_SETUP_HD void history_clamp(int r, float sigma_scale, Colour colour, TpMix* m
     const float h[3] = {m->h[0], m->h[1], m->h[2]};
     if (history_clamp_layer(b, m->h)) history_clamp_length(b, h, m->h, m);
     if (HALVES) { history_clamp_layer(b, m->ha); history_clamp_layer(b, m->hb); }
+}
+
+// rr_accumulate_clamped_split_records for a pixel that kept its history.  The colour side is history_clamp as it stands: no diffuse value
+// takes part in it.  Then the diffuse box, from the window of the current `diffuse` layer: diffuse(dx, dy, c) as colour above, but taken
+// on its own three floats, so the pixel itself may fail -- with nothing taken m = 0, s1 / 0.0f is a NaN and the channel has no box.  Both
+// diffuse halves are held to this one box.  A layer whose mean is not finite is left alone (it will not be blended: were an infinite mean
+// pulled onto a finite bound, it would be); the length is the colour side's.
+template <bool HALVES, class Colour, class Diffuse>
+RR_SETUP_HD void history_clamp_split(int r, float sigma_scale, Colour colour, Diffuse diffuse, TpMix* m, TpSplitMix* d) {
+    history_clamp<HALVES>(r, sigma_scale, colour, m);
+    const HcBox b = history_clamp_box(history_clamp_sums(r, diffuse), sigma_scale);
+    if (temporal_colour_ok(d->d)) history_clamp_layer(b, d->d);
+    if (HALVES) {
+        if (temporal_colour_ok(d->da)) history_clamp_layer(b, d->da);
+        if (temporal_colour_ok(d->db)) history_clamp_layer(b, d->db);
+    }
 }

@@ -2397,6 +2397,95 @@ __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_clamped_records(const T
     }
 }
 
+// 7e''': 7e'' merged with 7e' (rr_accumulate_clamped_split_records; rr_history_clamp.h: history_clamp_split has the arithmetic).  Two
+// planes of the tile and its halo of R points go through LDS, one float4 per point each: the colour plane of 7e'', and the diffuse plane,
+// the three floats of `diffuse` and, in w, 1 where the point lies inside the frame with three finite DIFFUSE floats, else 0 (2 x 5440 B at
+// R = 1, 2 x 6912 = 13 824 B at R = 2).  Lane e stages point e of both planes: consecutive lanes read the consecutive 12-byte rows of
+// `diffuse` of one row of the staged tile (the compiler merges a lane's three dwords into one global_load_dwordx3, so a wave's load walks
+// that row's bytes without a gap), and write one ds_write_b128 per plane; a window position is a ds_read_b96 and a ds_read_b32 per plane.  EVERY lane stages and reaches the one barrier; a lane outside the frame leaves after it.  Then 7e':
+// temporal_history with the diffuse means, and for a pixel that kept its history the two windows, one after the other, the clamps and the
+// length rule before the blends.  The lane's own diffuse triple is its slot of the diffuse plane.  `out` may NOT be `records` and
+// diffuse_out NOT `diffuse` (another workgroup's halo reads them); halves_out may be `halves` and dif_halves_out `dif_halves`, read at the
+// lane's pixel only.
+template <bool HALVES, int R>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_clamped_split_records(const TpFrame f, float sigma_scale, const float4* __restrict__ records, const float4* halves,
+                                                                               const float4* __restrict__ history, const float4* __restrict__ history_halves,
+                                                                               const float* __restrict__ history_length, const float* __restrict__ motion,
+                                                                               float4* __restrict__ out, float4* halves_out, float* __restrict__ length_out,
+                                                                               const TpSplitIo io) {
+    constexpr int TW = DN_TILE_W + 2 * R, TH = DN_TILE_H + 2 * R;
+    __shared__ float4 s_c[TW * TH];
+    __shared__ float4 s_d[TW * TH];
+    const int x0 = (int)blockIdx.x * DN_TILE_W, y0 = (int)blockIdx.y * DN_TILE_H;
+    for (int e = (int)threadIdx.x; e < TW * TH; e += RR_BLOCK) {
+        const int qx = x0 - R + e % TW, qy = y0 - R + e / TW;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (qx >= 0 && qy >= 0 && qx < f.width && qy < f.height) {
+            const unsigned long long q = (unsigned long long)qy * (unsigned int)f.width + (unsigned int)qx;
+            c = records[2ull * q];
+            c.w = (denoise_is_finite(c.x) && denoise_is_finite(c.y) && denoise_is_finite(c.z)) ? 1.0f : 0.0f;
+            g.x = io.diffuse[3ull * q]; g.y = io.diffuse[3ull * q + 1]; g.z = io.diffuse[3ull * q + 2];
+            g.w = (denoise_is_finite(g.x) && denoise_is_finite(g.y) && denoise_is_finite(g.z)) ? 1.0f : 0.0f;
+        }
+        s_c[e] = c;
+        s_d[e] = g;
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x & (DN_TILE_W - 1), ty = (int)threadIdx.x / DN_TILE_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= f.width || y >= f.height) return;
+    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
+    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
+    float4 a0, a1, b0, b1;
+    if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
+    const float4* s_p = s_c + (ty + R) * TW + tx + R;
+    const float4* s_q = s_d + (ty + R) * TW + tx + R;
+    float d[3] = {s_q->x, s_q->y, s_q->z}, da[3], db[3];
+    if (HALVES)
+        for (int c = 0; c < 3; c++) { da[c] = io.dif_halves[6ull * o + c]; db[c] = io.dif_halves[6ull * o + 3 + c]; }
+    const uint32_t flags = denoise_record_flags(r0, r1);
+    TpMix m;
+    TpSplitMix s;
+    bool kept = false;
+    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
+        const float n_p[3] = {r1.x, r1.y, r1.z};
+        TpSplitHistory hist;
+        hist.history = history; hist.history_halves = history_halves; hist.history_length = history_length;
+        hist.history_diffuse = io.history_diffuse; hist.history_dif_halves = io.history_dif_halves;
+        kept = temporal_history<HALVES, TpSplitHistory, true>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr,
+                                                     hist, &m, &s);
+    }
+    if (kept) {
+        history_clamp_split<HALVES>(R, sigma_scale, [&](int dx, int dy, float* c) {
+            const float4 q = s_p[dy * TW + dx];
+            c[0] = q.x; c[1] = q.y; c[2] = q.z;
+            return q.w != 0.0f;
+        }, [&](int dx, int dy, float* c) {
+            const float4 q = s_q[dy * TW + dx];
+            c[0] = q.x; c[1] = q.y; c[2] = q.z;
+            return q.w != 0.0f;
+        }, &m, &s);
+    }
+    float4 c0 = r0;
+    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
+    out[2ull * o] = c0;
+    out[2ull * o + 1] = r1;
+    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
+    if (kept) temporal_blend_diffuse(s.d, m.a, d, d);
+    io.diffuse_out[3ull * o] = d[0]; io.diffuse_out[3ull * o + 1] = d[1]; io.diffuse_out[3ull * o + 2] = d[2];
+    if (HALVES) {
+        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
+            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
+        }
+        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
+            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
+        }
+        halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
+        if (kept) { temporal_blend_diffuse(s.da, m.a, da, da); temporal_blend_diffuse(s.db, m.a, db, db); }
+        for (int c = 0; c < 3; c++) { io.dif_halves_out[6ull * o + c] = da[c]; io.dif_halves_out[6ull * o + 3 + c] = db[c]; }
+    }
+}
+
 // 7f: the motion of moved items per pixel (rr_motion_records; rr_motion.h has the arithmetic, rustray_amd/temporal.py: motion_records is
 // the yardstick).  One pixel per lane, 32x8 tiles as 7a .. 7e; a record is two 16-byte loads, the answer three dword stores (six with
 // world_out); no LDS.  The table is sorted by id: a lane whose record is valid looks its id up by binary search and reads the 24 floats

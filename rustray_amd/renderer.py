@@ -305,12 +305,29 @@ class Raytracing:
         rr_denoise_split_records -- render_temporal_split_torch on this scene and camera, on one stream with no host trip.  The arguments are
         render_temporal's, without `albedo`; `state` is a TemporalState of this pipeline's (one that render_temporal filled starts anew).
         The result holds torch tensors: render_temporal's, and diffuse, diffuse_halves, accumulated_diffuse, accumulated_diffuse_halves and
-        albedo.  clamp: anything but None or False raises ValueError, the clamped form of the split accumulation is not built."""
+        albedo.  clamp: anything but None or False raises ValueError that names render_temporal_split_clamped, the pipeline with the clamped
+        accumulation."""
         from .temporal import previous_view
         _no_split_clamp(clamp)
         cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
         return render_temporal_split_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
                                            sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
+
+    def render_temporal_split_clamped(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None,
+                                      seed: Optional[int] = None, motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, clamp=True) -> dict:
+        """render_temporal_split with the history held to the current frame (rr_accumulate_clamped_split_records in the place of
+        rr_accumulate_split_records): the colour layers to the box of the current colours around each pixel, the diffuse layers to the box of
+        the current diffuse layer -- render_temporal_split_clamped_torch on this scene and camera, on one stream with no host trip.  For the
+        frames after an edit of lights, materials, textures or item flags, and under moving shadows; a state may go from one of the two
+        pipelines to the other from frame to frame.  clamp: True (the library's defaults) or a temporal.HistoryClampParams; None or False
+        raises ValueError.  The other arguments and the result are render_temporal_split's."""
+        from .temporal import previous_view
+        clamp = _clamp_params(clamp)         # (refused before the state notes this frame's items)
+        if clamp is None:
+            raise ValueError("clamp is True (the defaults) or a temporal.HistoryClampParams; without a clamp the pipeline is render_temporal_split")
+        cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
+        return render_temporal_split_clamped_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
+                                                   sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, clamp=clamp)
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -1306,7 +1323,8 @@ def _clamp_params(clamp):
 
 def _no_split_clamp(clamp) -> None:
     if clamp is not None and clamp is not False:
-        raise ValueError("clamp: the split form of the clamped accumulation is not built; render_temporal (render_temporal_torch) takes clamp")
+        raise ValueError("clamp: the split pipeline with the clamped accumulation is a function of its own, render_temporal_split_clamped "
+                         "(render_temporal_split_clamped_torch); render_temporal_split (render_temporal_split_torch) takes no clamp")
 
 
 def accumulate_clamped_torch(device_scene: capi.DeviceScene, cam, records, halves=None, history=None, history_halves=None, history_length=None, motion=None,
@@ -1370,6 +1388,41 @@ def accumulate_split_torch(device_scene: capi.DeviceScene, cam, records, halves,
                                              ptr(t["history_halves"]), ptr(t["history_diffuse"]), ptr(t["history_diffuse_halves"]), ptr(t["history_length"]),
                                              ptr(t["motion"]), ptr(res["records"]), ptr(res["halves"]), ptr(res["diffuse"]), ptr(res["diffuse_halves"]), ptr(length),
                                              ptr(rgba), params, torch.cuda.current_stream(dev).cuda_stream)
+    result = dict(_record_views(res["records"]), halves=res["halves"], diffuse=res["diffuse"], diffuse_halves=res["diffuse_halves"], length=length)
+    if rgba8:
+        result["rgba"] = rgba
+    return result
+
+
+def accumulate_clamped_split_torch(device_scene: capi.DeviceScene, cam, records, halves, diffuse, diffuse_halves, history=None, history_halves=None,
+                                   history_diffuse=None, history_diffuse_halves=None, history_length=None, motion=None, params=None, clamp=None,
+                                   rgba8: bool = False, out: Optional[dict] = None) -> dict:
+    """rr_accumulate_clamped_split_records_device on torch's current stream of the scene's device: the tensors and the result of
+    accumulate_split_torch, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  There is no in_place: `out` may not
+    be `records` and `diffuse_out` not `diffuse`, whose neighbours the windows read.  out: dict(records, halves, diffuse, diffuse_halves,
+    length) of tensors to write."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), diffuse=(diffuse, (3,)),
+                                                                  diffuse_halves=(diffuse_halves, (2, 3)), history=(history, (8,)),
+                                                                  history_halves=(history_halves, (2, 8)), history_diffuse=(history_diffuse, (3,)),
+                                                                  history_diffuse_halves=(history_diffuse_halves, (2, 3)), history_length=(history_length, ()),
+                                                                  motion=(motion, (3,))), required=("records", "diffuse"))
+    dev = torch.device("cuda", device_scene.device)
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    current = ("records", "halves", "diffuse", "diffuse_halves")
+    shapes = dict(records=(n, 8), halves=(n, 2, 8), diffuse=(n, 3), diffuse_halves=(n, 2, 3))
+    with torch.cuda.device(dev):
+        if out is not None:
+            res = {k: out[k] if t[k] is not None else None for k in current}
+        else:
+            res = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) if t[k] is not None else None for k in current}
+        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        device_scene.accumulate_clamped_split_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["diffuse"]), ptr(t["diffuse_halves"]), ptr(t["history"]),
+                                                     ptr(t["history_halves"]), ptr(t["history_diffuse"]), ptr(t["history_diffuse_halves"]),
+                                                     ptr(t["history_length"]), ptr(t["motion"]), ptr(res["records"]), ptr(res["halves"]), ptr(res["diffuse"]),
+                                                     ptr(res["diffuse_halves"]), ptr(length), ptr(rgba), params, clamp, torch.cuda.current_stream(dev).cuda_stream)
     result = dict(_record_views(res["records"]), halves=res["halves"], diffuse=res["diffuse"], diffuse_halves=res["diffuse_halves"], length=length)
     if rgba8:
         result["rgba"] = rgba
@@ -1455,11 +1508,30 @@ def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_con
     A history without a diffuse part (a state render_temporal_torch filled), without halves or of another size resets the state, the
     items noted for this frame kept.  Returns the dict of render_temporal_torch (without a variance) plus diffuse (n, 3) and diffuse_halves
     (n, 2, 3), the frame's own, accumulated_diffuse and accumulated_diffuse_halves, what the filter read and `state` now holds, and
-    albedo (n, 3).  clamp: anything but None or False raises ValueError, the clamped form of the split accumulation is not built."""
+    albedo (n, 3).  clamp: anything but None or False raises ValueError that names render_temporal_split_clamped_torch, the pipeline with
+    the clamped accumulation."""
+    _no_split_clamp(clamp)
+    return _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, None)
+
+
+def render_temporal_split_clamped_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
+                                        sample_xy=None, rgba8: bool = False, view=None, moved=None, clamp=True) -> dict:
+    """render_temporal_split_torch with rr_accumulate_clamped_split_records_device in the place of rr_accumulate_split_records_device, on
+    the same stream, the same buffers and the state's same diffuse sets: the split frame, with moved items the motion, the clamped split
+    accumulation, the mean albedo, the split filter, with no host trip.  For the frames after an edit of lights, materials, textures or
+    item flags, and under moving shadows.  clamp: True (the library's defaults) or a temporal.HistoryClampParams; None or False is a
+    ValueError here (that is render_temporal_split_torch).  The arguments and the result are render_temporal_split_torch's."""
+    clamp = _clamp_params(clamp)         # (refused before anything is rendered)
+    if clamp is None:
+        raise ValueError("clamp is True (the defaults) or a temporal.HistoryClampParams; without a clamp the pipeline is render_temporal_split_torch")
+    return _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, clamp)
+
+
+def _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, clamp) -> dict:
+    """The frame of render_temporal_split_torch (clamp None) and of render_temporal_split_clamped_torch (a checked clamp)."""
     import dataclasses
     import torch
     from .temporal import AccumulateParams, previous_view
-    _no_split_clamp(clamp)
     if moved is not None and motion is not None:
         raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
     base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)
@@ -1477,8 +1549,12 @@ def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_con
     if moved is not None and hist is not None and len(moved[0]):
         motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
     h = lambda k: hist[k] if hist else None
-    acc = accumulate_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"), h("halves"),
-                                 h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, out=target)
+    if clamp is None:
+        acc = accumulate_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"), h("halves"),
+                                     h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, out=target)
+    else:
+        acc = accumulate_clamped_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"),
+                                             h("halves"), h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, clamp, out=target)
     guide = albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
     res = denoise_split_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["diffuse"], acc["halves"], acc["diffuse_halves"], guide,
                               denoise_params, rgba8=rgba8)

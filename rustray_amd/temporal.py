@@ -130,9 +130,10 @@ def motion_records(records, cam, item_ids, prev_trans, cur_trans_inv):
 def _accumulate(records, halves, history, history_halves, history_length, motion, cam, prm, extra=(), hook=None):
     """The tap walk and the blends that accumulate_records, accumulate_split_records and accumulate_clamped_records share.  extra: (current
     (n, 3), history (n, 3) or None) per extra layer, which rides on the taps and weights of the records and decides nothing.  hook (or
-    None): called between the means and the blend as hook(rec, means, N, kept) with the history means of the records and the two halves
-    (a list of (n, 3)), and gives (means, N) back -- what accumulate_clamped_records does to them.  -> (accumulate_records' dict, the extra
-    layers' outputs)."""
+    None): called between the means and the blend as hook(rec, means, N, kept, means_x) with the history means of the records and the two
+    halves (a list of (n, 3)) and those of the extra layers (another), and gives (means, N, means_x) back -- what accumulate_clamped_records
+    and accumulate_clamped_split_records do to them.  An extra layer is blended where its current triple and the mean the hook gave back are
+    finite.  -> (accumulate_records' dict, the extra layers' outputs)."""
     prm.check()
     pi, vi, W, H = camera_matrices(cam)
     n = W * H
@@ -215,17 +216,17 @@ def _accumulate(records, halves, history, history_halves, history_length, motion
         n1 = sum_l / sum_w + one
         N = np.where(n1 < max_history, n1, max_history).astype(F)
         means = [s / sum_w[:, None] for s in sum_c]
+        means_x = [sx / sum_w[:, None] for sx in sum_x]
         if hook is not None:
-            means, N = hook(rec, means, N, kept)
+            means, N, means_x = hook(rec, means, N, kept, means_x)
         a = one / N
         currents = [rec[:, 0:3]] + ([] if hv is None else [hv[:, 0, 0:3], hv[:, 1, 0:3]])
         targets = [out[:, 0:3]] + ([] if hv is None else [out_h[:, 0, 0:3], out_h[:, 1, 0:3]])
         for h, cur, dst in zip(means, currents, targets):
             blended = h + a[:, None] * (cur - h)
             dst[...] = np.where((kept & np.isfinite(cur).all(-1))[:, None], blended, cur)
-        for sx, (cur, _), dst in zip(sum_x, extra, out_x):
+        for hd, (cur, _), dst in zip(means_x, extra, out_x):
             cur = np.ascontiguousarray(cur, F).reshape(n, 3)
-            hd = sx / sum_w[:, None]
             blended = hd + a[:, None] * (cur - hd)
             dst[...] = np.where((kept & np.isfinite(cur).all(-1) & np.isfinite(hd).all(-1))[:, None], blended, cur)
         length = np.where(kept, N, length).astype(F)
@@ -242,7 +243,7 @@ def accumulate_records(records, halves, history, history_halves, history_length,
 
 
 def accumulate_split_records(records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, history_length,
-                             motion, cam, params: AccumulateParams | None = None) -> dict:
+                             motion, cam, params: AccumulateParams | None = None, _hook=None) -> dict:
     """rr_accumulate_split_records in numpy float32: accumulate_records' arguments, and diffuse (n, 3), diffuse_halves (n, 2, 3) or None
     (exactly when halves is), history_diffuse (n, 3) exactly when history is given and history_diffuse_halves (n, 2, 3) exactly when
     history_halves is.  The diffuse layers ride on the taps, weights and length of the records: records, halves and length are
@@ -263,7 +264,7 @@ def accumulate_split_records(records, halves, diffuse, diffuse_halves, history, 
     extra = [(flat(diffuse), flat(history_diffuse))]
     if diffuse_halves is not None:
         extra += [(layer(diffuse_halves, h), layer(history_diffuse_halves, h)) for h in (0, 1)]
-    res, out_x = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), extra)
+    res, out_x = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), extra, _hook)
     res["diffuse"] = out_x[0]
     res["diffuse_halves"] = None if diffuse_halves is None else np.ascontiguousarray(np.stack([out_x[1], out_x[2]], axis=1))
     return res
@@ -273,9 +274,11 @@ def clamp_boxes(records, W: int, H: int, clamp: HistoryClampParams):
     """Step 7 of rr_accumulate_clamped_records for every pixel of a W x H frame of records (n, 8): (lo, hi, e), each (n, 3) float32, and m
     (n,), how many pixels of the window were taken.  The (2r + 1)^2 window positions are whole-frame shifts here, in the header's order; a
     position that is not taken adds nothing.  A channel without a box has lo = -inf, hi = e = +inf.  (A pixel whose own colour is not
-    finite never reaches step 7; what stands here for it means nothing.)"""
+    finite never reaches step 7; what stands here for it means nothing.)  `records` may also be an (n, 3) array of triples, the current
+    `diffuse` layer of rr_accumulate_clamped_split_records: a position is taken on its three floats in the same way, the pixel itself
+    included, and a window in which nothing is taken has m = 0, a NaN mean and no box."""
     r, k = int(clamp.radius), F(clamp.sigma_scale)
-    col = np.ascontiguousarray(records, F).reshape(H, W, 8)[:, :, 0:3]
+    col = np.ascontiguousarray(records, F).reshape(H, W, -1)[:, :, 0:3]
     ok = np.isfinite(col).all(-1)
     m = np.zeros((H, W), np.int64)
     s1, s2 = np.zeros((H, W, 3), F), np.zeros((H, W, 3), F)
@@ -303,22 +306,13 @@ def clamp_boxes(records, W: int, H: int, clamp: HistoryClampParams):
     return lo, hi, e, m.reshape(-1)
 
 
-def accumulate_clamped_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None,
-                               clamp: HistoryClampParams | None = None) -> dict:
-    """rr_accumulate_clamped_records in numpy float32, following steps 7 .. 10 of its text in include/rustray_hip.h: accumulate_records'
-    arguments and a HistoryClampParams (None: the defaults).  The history means of a kept pixel are held to the box of the current
-    frame's colours around it, and the length is shortened where the record layer had to be moved.  -> accumulate_records' dict, and
-    clamped (n, 3) bool: per layer (records, half 0, half 1) whether a channel of that layer's mean was moved (False for a pixel
-    without history and for a layer the call does not have), and box: dict(lo (n, 3), hi (n, 3))."""
-    clamp = clamp or HistoryClampParams()
-    clamp.check()
-    _, _, W, H = camera_matrices(cam)
-    n = W * H
-    lo, hi, e, _ = clamp_boxes(records, W, H, clamp)
-    clamped = np.zeros((n, 3), bool)
+def _colour_clamp_hook(lo, hi, e, clamped):
+    """Steps 8 and 9 of rr_accumulate_clamped_records as _accumulate's hook: the means of the records and the halves held to the box (lo, hi,
+    e: clamp_boxes'), the length shortened where the record layer was moved; `clamped` (n, 3) bool is filled per layer.  The extra layers'
+    means pass through."""
     one = F(1)
 
-    def hook(rec, means, N, kept):
+    def hook(rec, means, N, kept, means_x):
         held, moved = [], []
         for h in means:
             below, above = h < lo, h > hi
@@ -331,9 +325,64 @@ def accumulate_clamped_records(records, halves, history, history_halves, history
         t = np.where(t01 > u[:, 2], t01, u[:, 2])
         keep = one / (one + t)
         shorter = ((N - one) * keep + one).astype(F)
-        return held, np.where(clamped[:, 0], shorter, N).astype(F)
+        return held, np.where(clamped[:, 0], shorter, N).astype(F), means_x
 
-    res = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(), hook=hook)[0]
+    return hook
+
+
+def accumulate_clamped_records(records, halves, history, history_halves, history_length, motion, cam, params: AccumulateParams | None = None,
+                               clamp: HistoryClampParams | None = None) -> dict:
+    """rr_accumulate_clamped_records in numpy float32, following steps 7 .. 10 of its text in include/rustray_hip.h: accumulate_records'
+    arguments and a HistoryClampParams (None: the defaults).  The history means of a kept pixel are held to the box of the current
+    frame's colours around it, and the length is shortened where the record layer had to be moved.  -> accumulate_records' dict, and
+    clamped (n, 3) bool: per layer (records, half 0, half 1) whether a channel of that layer's mean was moved (False for a pixel
+    without history and for a layer the call does not have), and box: dict(lo (n, 3), hi (n, 3))."""
+    clamp = clamp or HistoryClampParams()
+    clamp.check()
+    _, _, W, H = camera_matrices(cam)
+    lo, hi, e, _ = clamp_boxes(records, W, H, clamp)
+    clamped = np.zeros((W * H, 3), bool)
+    res = _accumulate(records, halves, history, history_halves, history_length, motion, cam, params or AccumulateParams(),
+                      hook=_colour_clamp_hook(lo, hi, e, clamped))[0]
     res["clamped"] = clamped
     res["box"] = dict(lo=lo, hi=hi)
+    return res
+
+
+def accumulate_clamped_split_records(records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves,
+                                     history_length, motion, cam, params: AccumulateParams | None = None, clamp: HistoryClampParams | None = None) -> dict:
+    """rr_accumulate_clamped_split_records in numpy float32, following its text in include/rustray_hip.h: accumulate_split_records'
+    arguments and a HistoryClampParams (None: the defaults).  The colour side is accumulate_clamped_records' (records, halves and length are
+    its bits); each diffuse mean of a kept pixel is held to the box of the current `diffuse` layer around it where that mean and the
+    layer's current triple are finite, and blended with the colour side's final a.  -> accumulate_split_records' dict, and clamped (n, 3)
+    bool as accumulate_clamped_records gives it, diffuse_clamped (n, 3) bool: per diffuse layer (diffuse, half 0, half 1) whether a channel
+    of its mean was moved in a blend that took place (False for a pixel without history, a layer that keeps its current bits and a layer
+    the call does not have), box: dict(lo, hi) of the colours and diffuse_box: dict(lo, hi) of the diffuse layer, each (n, 3)."""
+    clamp = clamp or HistoryClampParams()
+    clamp.check()
+    if diffuse is None:
+        raise ValueError("diffuse is required")
+    _, _, W, H = camera_matrices(cam)
+    n = W * H
+    lo, hi, e, _ = clamp_boxes(records, W, H, clamp)
+    cur_d = np.ascontiguousarray(diffuse, F).reshape(n, 3)
+    dlo, dhi, _, _ = clamp_boxes(cur_d, W, H, clamp)
+    clamped, diffuse_clamped = np.zeros((n, 3), bool), np.zeros((n, 3), bool)
+    colour_hook = _colour_clamp_hook(lo, hi, e, clamped)
+    currents = [cur_d] + ([] if diffuse_halves is None else [np.ascontiguousarray(diffuse_halves, F).reshape(n, 2, 3)[:, h] for h in (0, 1)])
+
+    def hook(rec, means, N, kept, means_x):
+        held, N, _ = colour_hook(rec, means, N, kept, means_x)
+        held_x = []
+        for layer, (hd, cur) in enumerate(zip(means_x, currents)):
+            blends = kept & np.isfinite(cur).all(-1) & np.isfinite(hd).all(-1)
+            below, above = (hd < dlo) & blends[:, None], (hd > dhi) & blends[:, None]
+            held_x.append(np.where(below, dlo, np.where(above, dhi, hd)).astype(F))
+            diffuse_clamped[:, layer] = (below | above).any(-1)
+        return held, N, held_x
+
+    res = accumulate_split_records(records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, history_length,
+                                   motion, cam, params, _hook=hook)
+    res["clamped"], res["diffuse_clamped"] = clamped, diffuse_clamped
+    res["box"], res["diffuse_box"] = dict(lo=lo, hi=hi), dict(lo=dlo, hi=dhi)
     return res

@@ -27,7 +27,12 @@ rr_accumulate_records_device calls of the same run and view.
 1).  The call moves the HBM bytes of a record call -- the window is read from LDS, the halo costs about a third more colour rows, which
 hit in cache --, so the yardstick is the record call of the same run and view.
 
-usage: temporal_time.py [scene [width height samples]] [--motion] [--split] [--clamp] [--out FILE]"""
+--clamp-split: rr_accumulate_clamped_split_records_device in the same rounds (this turns --split and --clamp on), with halves, static view
+and 1.3-pixel yaw, at radius 1 and 2 (sigma_scale 1), on the split frame and history.  The call moves the split call's HBM bytes; the
+two windows are read from LDS.  The bar is what a caller would pay for both effects apart: the sum of the split call and the clamped
+call of the same run, view and radius.
+
+usage: temporal_time.py [scene [width height samples]] [--motion] [--split] [--clamp] [--clamp-split] [--out FILE]"""
 import math
 import os
 import sys
@@ -67,6 +72,10 @@ def main(argv):
     with_motion = "--motion" in argv
     if with_motion:
         argv.remove("--motion")
+    with_clamp_split = "--clamp-split" in argv
+    if with_clamp_split:
+        argv.remove("--clamp-split")
+        argv += [f for f in ("--split", "--clamp") if f not in argv]
     with_split = "--split" in argv
     if with_split:
         argv.remove("--split")
@@ -153,6 +162,19 @@ def main(argv):
             for view in ("static", "moved"):
                 for radius in (1, 2):
                     arms[("clamp", view, radius)] = clamp_call(view, radius)
+        if with_clamp_split:
+            cs_out = {k: torch.empty_like(sh[k]) for k in ("records", "halves", "diffuse", "diffuse_halves", "length")}
+
+            def clamp_split_call(view, radius):
+                prm = capi.accumulate_params(AccumulateParams(prev_world_to_clip=views[view][0], prev_eye=views[view][1]))
+                clamp = capi.history_clamp_params(HistoryClampParams(radius, 1.0))
+                cur = [sf[1][k].data_ptr() for k in ("records", "part_records", "diffuse", "diffuse_halves")]
+                old = [sh[k].data_ptr() for k in ("records", "halves", "diffuse", "diffuse_halves", "length")]
+                new = [cs_out[k].data_ptr() for k in ("records", "halves", "diffuse", "diffuse_halves", "length")]
+                return lambda: ds.accumulate_clamped_split_device(cam, *cur, *old, None, *new, None, prm, clamp, stream)
+            for view in ("static", "moved"):
+                for radius in (1, 2):
+                    arms[("clamp_split", view, radius)] = clamp_split_call(view, radius)
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
@@ -187,6 +209,15 @@ def main(argv):
             emit(f"  rr_accumulate_clamped_records_device, with halves, {k[1]}, radius {k[2]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the rate of its "
                  f"compulsory traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / bm:.2f} x rr_accumulate_records_device with halves, {k[1]} "
                  f"({bm:.4f} ms [{blo:.4f} .. {bhi:.4f}])")
+            continue
+        if k[0] == "clamp_split":
+            per_pixel = BYTES_PER_PIXEL[True] + 108
+            floor_ms = n * per_pixel / HBM_BYTES_PER_S * 1e3
+            (sm, slo, shi), (cm, clo, chi) = _median(runs[("split", k[1])]), _median(runs[("clamp", k[1], k[2])])
+            apart = "outside" if hi < slo + clo else "NOT outside"
+            emit(f"  rr_accumulate_clamped_split_records_device, with halves, {k[1]}, radius {k[2]}: {m:.4f} ms [{lo:.4f} .. {hi:.4f}] = {floor_ms / m:.2f} of the rate "
+                 f"of its compulsory traffic ({per_pixel} B per pixel, {floor_ms * 1e3:.1f} us), {m / sm:.2f} x the split call, {m / cm:.2f} x the clamped call; the "
+                 f"bar, the sum of the two: {sm + cm:.4f} ms [{slo + clo:.4f} .. {shi + chi:.4f}], {'met' if m < sm + cm else 'MISSED'}, {apart} the arms' ranges")
             continue
         if k[0] == "motion":
             per_pixel = 44 + (12 if k[2] else 0)
