@@ -1,7 +1,7 @@
 // rr_accumulate.h — layer 5 of the device code: the per-pixel fixed-point accumulators that stand for the reference's f32 sums
 // over samples (src/raytracing.rs:400-417).  Integer adds commute, so the frame does not depend on the order of anything.
 //
-// Offers: to_fix, fix_add, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged, accum_hit_merged (the last four
+// Offers: to_fix, fix_add, fix_add_at, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged, accum_hit_merged (the last four
 // must be called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms).
 // wave_merge_runs / wave_merge_runs32 / fits25i / fits25 / wave_one_pixel / wave_sum32 / wave_sum64 / totals_to_lanes and the *_runs forms of the merges
 // are this layer's own, and so are its DPP macros (RR_DPP_*, RR_SEG_STEP, RR_SEG_STEP32), un-defined at the end.
@@ -23,10 +23,17 @@ RR_DEV long long to_fix(float v, float scale, float clampv) {
 // a 64-bit add two more, seven to ten times per shaded hit.  A term beyond 2^25 goes straight to its accumulator word as one 64-bit
 // atomic of its own (rare: a saturating highlight, a far hit's depth); a NaN adds nothing (its pixel is flagged).  Every term is
 // rounded to nearest-even by itself either way, and integer adds commute: the pixel's sum is the same integer.
-RR_DEV void fix_add(int& n, float v, float scale, float clampv, long long* plane, uint32_t pix) {
+// fix_add_at: `plane()` names the plane, and is evaluated by a term that goes there only (k_shade fetches the pointer then)
+template <class Plane> RR_DEV void fix_add_at(int& n, float v, float scale, float clampv, Plane plane, uint32_t pix) {
     const float x = v * scale;
     if (rr_abs(x) < 33554432.0f) n += __float2int_rn(x); // (inside every clamp in use: |v| < 2 at scale 2^24, < 512 at 2^16)
-    else { const long long t = to_fix(v, scale, clampv); if (t != 0ll && plane) atomicAdd((unsigned long long*)plane + pix, (unsigned long long)t); }
+    else {
+        const long long t = to_fix(v, scale, clampv);
+        if (t != 0ll) { long long* const p = plane(); if (p) atomicAdd((unsigned long long*)p + pix, (unsigned long long)t); }
+    }
+}
+RR_DEV void fix_add(int& n, float v, float scale, float clampv, long long* plane, uint32_t pix) {
+    fix_add_at(n, v, scale, clampv, [=] { return plane; }, pix);
 }
 
 // A colour contribution of channel `ch`: non-finite values are recorded in `flags` (RR_NF_*), because the reference's f32

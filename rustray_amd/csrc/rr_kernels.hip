@@ -323,17 +323,75 @@ RR_DEV long long* split_planes() { return nullptr; }
 template <class Q> RR_DEV long long* split_planes(long long* planes, Q*) { return planes; }
 RR_DEV float4* split_queue() { return nullptr; }
 template <class Q> RR_DEV Q* split_queue(long long*, Q* queue) { return queue; }
+// The record of light `li` in scalar registers.  The index is the light loop's counter, the same in every lane of either build, and the
+// record arrived as seven vector loads of 64 equal addresses, fetched where the fields are used.  Here its three 16-byte groups are
+// requested together through the constant address space and waited for once, as item_rec_uniform (rr_primitives.h) does for the walks;
+// the empty asm statement reads them where they are loaded.  No kernel writes the lights; edits happen between launches.
+static_assert(sizeof(DLight) == 48 && offsetof(DLight, intensity) == 12 && offsetof(DLight, dir) == 16 && offsetof(DLight, max_angle) == 28 &&
+              offsetof(DLight, color) == 32 && offsetof(DLight, type) == 44, "light_uniform: three 16-byte groups");
+RR_DEV DLight light_uniform(const DLight* lights, uint32_t li) {
+    const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)(uintptr_t)lights + (unsigned long long)li * sizeof(DLight);
+    const rr_f4v g0 = *(const __attribute__((address_space(4))) rr_f4v*)p, g1 = *(const __attribute__((address_space(4))) rr_f4v*)(p + 16),
+                 g2 = *(const __attribute__((address_space(4))) rr_f4v*)(p + 32);
+    asm volatile("" :: "s"(g0), "s"(g1), "s"(g2));
+    DLight L;
+    L.pos[0] = g0.x; L.pos[1] = g0.y; L.pos[2] = g0.z; L.intensity = g0.w;
+    L.dir[0] = g1.x; L.dir[1] = g1.y; L.dir[2] = g1.z; L.max_angle = g1.w;
+    L.color[0] = g2.x; L.color[1] = g2.y; L.color[2] = g2.z; L.type = __float_as_uint(g2.w);
+    return L;
+}
+
+// The arguments of k_shade as its kernel-argument segment holds them (every member is naturally aligned, so the segment's layout is this
+// struct's; the SPLIT builds' two pointers follow it).  What the packet loop uses in every packet and every light -- the hit records, the
+// chunk bounds, the shadow queue -- the kernel takes from its parameters as before, and those stay in SGPRs.  Everything else it reads
+// from the segment WHERE IT IS USED, through the scalar cache: about 60 dwords of parameters held across the loop, on a target with 102
+// SGPRs, were spilled into VGPR lanes, and every use of a spilled one is a v_readlane on the vector port, which is what bounds this
+// kernel.  A parameter that is not named in the body is not loaded at the kernel's entry either.
+struct ShadeArgs {
+    const DShadeConst* kc; const uint32_t* slot_xy; DPrimary pr; DRayQueue qin; const uint32_t* qin_count; uint32_t chunk_begin, chunk_end;
+    DRayQueue qout; uint32_t* qout_count; DShadowQueue sq; uint32_t* sq_counts; uint32_t sq_segcap; unsigned long long* sq_valid; uint32_t sq_cap;
+    DAccum acc; unsigned long long* counters;
+};
+typedef const __attribute__((address_space(4))) char* rr_kernarg_ptr;
+// The segment's address as a value the compiler cannot see through (the empty asm statement): loads behind it are neither hoisted out of
+// the loop the statement stands in nor merged with the entry's own loads of the parameters.
+RR_DEV rr_kernarg_ptr kernarg_segment() {
+    rr_kernarg_ptr p = (rr_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+template <class T> RR_DEV T* rr_global_mut(T* p) { return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p; }
+template <class T> RR_DEV T kernarg_at(rr_kernarg_ptr ka, uint32_t offset) {
+    static_assert(std::is_scalar<T>::value, "member by member: a record's copy constructor takes no reference into the constant address space");
+    const T v = *(const __attribute__((address_space(4))) T*)(ka + offset);
+    if constexpr (std::is_pointer<T>::value) return rr_global_mut(v); // (a pointer loaded from memory is generic: rr_walk.h rr_global)
+    else return v;
+}
+#define RR_SHADE_ARG(ka, member) kernarg_at<decltype(((ShadeArgs*)nullptr)->member)>(ka, (uint32_t)__builtin_offsetof(ShadeArgs, member))
+RR_DEV DAccum shade_arg_accum(rr_kernarg_ptr ka) { // the whole record, for the merges at a packet's end
+    DAccum a;
+    a.rgb = RR_SHADE_ARG(ka, acc.rgb); a.normal = RR_SHADE_ARG(ka, acc.normal); a.depth = RR_SHADE_ARG(ka, acc.depth); a.object_id = RR_SHADE_ARG(ka, acc.object_id);
+    a.n = RR_SHADE_ARG(ka, acc.n); a.flags = RR_SHADE_ARG(ka, acc.flags);
+    return a;
+}
+RR_DEV DPrimary shade_arg_primary(rr_kernarg_ptr ka) {
+    DPrimary p;
+    p.sample_tr = RR_SHADE_ARG(ka, pr.sample_tr);
+    p.at.first_sample = RR_SHADE_ARG(ka, pr.at.first_sample); p.at.first_pix = RR_SHADE_ARG(ka, pr.at.first_pix);
+    p.at.lg_group = RR_SHADE_ARG(ka, pr.at.lg_group); p.at.lg_pixels = RR_SHADE_ARG(ka, pr.at.lg_pixels);
+    p.n = RR_SHADE_ARG(ka, pr.n); p.lg_parts = RR_SHADE_ARG(ka, pr.lg_parts);
+    return p;
+}
 template <bool PRIMARY, bool SPLIT = false, class... Split>
-__global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShadeConst* __restrict__ kc, const uint32_t* __restrict__ slot_xy, DPrimary pr,
+__global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShadeConst* __restrict__ kc, const uint32_t* __restrict__ /* slot_xy */, DPrimary /* pr */,
                                                     DRayQueue qin, const uint32_t* __restrict__ qin_count,
                                                     uint32_t chunk_begin, uint32_t chunk_end,
-                                                    DRayQueue qout, uint32_t* qout_count,
-                                                    DShadowQueue sq, uint32_t* sq_counts, uint32_t sq_segcap, unsigned long long* __restrict__ sq_valid, uint32_t sq_cap,
-                                                    DAccum acc, unsigned long long* counters, Split... split) {
+                                                    DRayQueue /* qout */, uint32_t* /* qout_count */,
+                                                    DShadowQueue sq, uint32_t* /* sq_counts */, uint32_t /* sq_segcap */, unsigned long long* __restrict__ /* sq_valid */, uint32_t sq_cap,
+                                                    DAccum /* acc */, unsigned long long* /* counters */, Split... split) { // (the unnamed ones: ShadeArgs)
     static_assert(sizeof...(Split) == (SPLIT ? 2 : 0), "the SPLIT builds take (long long* diffuse, float4* sq_s3), the others nothing");
-    DAccum dacc = acc; // SPLIT: the diffuse planes behind the colour planes' own interface (fix_add, accum_merged)
     [[maybe_unused]] float4* const sq_s3 = split_queue(split...);
-    if constexpr (SPLIT) dacc.rgb = split_planes(split...);
+    [[maybe_unused]] long long* const dif_rgb = split_planes(split...); // SPLIT: the diffuse planes, laid out as acc.rgb
     // The scene view and the frame constants (90 dwords) are read from a small device record where they are needed
     // instead of arriving as kernel arguments: as arguments they were all live in SGPRs across the whole loop and the
     // kernel spilled 117 of them into VGPR lanes.
@@ -356,6 +414,11 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
     for (uint32_t block_base = chunk_begin + blockIdx.x * RR_BLOCK; block_base < n; block_base += gridDim.x * RR_BLOCK, parity ^= 1u) {
         const uint32_t base = block_base + wave_in_block * RR_WAVE;
         const uint32_t i = base + lane;
+        const rr_kernarg_ptr ka = kernarg_segment(); // (per packet: what is read behind it is read in this packet, where it is used)
+        // the colour, diffuse and normal planes of channel ch, fetched by the rare term that goes to its plane directly (fix_add_at)
+        const auto rgb_plane = [=](uint32_t ch) { return [=] { return RR_SHADE_ARG(ka, acc.rgb) + ch * RR_SHADE_ARG(ka, acc.n); }; };
+        [[maybe_unused]] const auto dif_plane = [=](uint32_t ch) { return [=] { return dif_rgb + ch * RR_SHADE_ARG(ka, acc.n); }; };
+        const auto normal_plane = [=](uint32_t ch) { return [=] { long long* const p = RR_SHADE_ARG(ka, acc.normal); return p ? p + ch * RR_SHADE_ARG(ka, acc.n) : nullptr; }; };
         uint4 hit = make_uint4(0u, 0xffffffffu, 0u, 0u);
         if (i < n) hit = qin.hit[i];
         const int item_idx = (int)hit.y;
@@ -373,8 +436,8 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         const uint32_t sq_slot = i - chunk_begin;
         uint32_t sq_wrote = 0u; // bit k: this lane wrote a ray for the k-th enabled light
         const uint32_t shard = ((base - chunk_begin) / RR_BLOCK) % RR_SQ_SHARDS; // the 4 packets of a workgroup iteration stay together
-        uint32_t* const sq_count = sq_counts + shard * RR_SQ_STRIDE;
-        const uint32_t sq_base = shard * sq_segcap;
+        uint32_t* sq_count = nullptr; uint32_t sq_base = 0u; // (dead with fixed slots)
+        if (!sq_fixed) { sq_count = RR_SHADE_ARG(ka, sq_counts) + shard * RR_SQ_STRIDE; sq_base = shard * RR_SHADE_ARG(ka, sq_segcap); }
         int sum_r = 0, sum_g = 0, sum_b = 0; // this hit's direct adds (32-bit fixed point, fix_add), merged with its neighbours' at the end
         [[maybe_unused]] int dif_r = 0, dif_g = 0, dif_b = 0; // SPLIT: the same for the diffuse parts of a depth-1 hit's unshadowed light terms
         [[maybe_unused]] uint32_t dif_pix = 0xffffffffu;
@@ -389,9 +452,9 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         float4 r0, r1; uint2 r2;
         if (PRIMARY) { // the root node of a path
             f3 po, pd; uint32_t ppix, psmp;
-            primary_ray(fr, kc->ps, pr, i, &po, &pd, &ppix, &psmp);
+            primary_ray(fr, kc->ps, shade_arg_primary(ka), i, &po, &pd, &ppix, &psmp);
             root_record(po, pd, ppix, psmp, &r0, &r1, &r2);
-        } else { r0 = qin.r0[i]; r1 = qin.r1[i]; r2 = qin.r2[i]; }
+        } else { r0 = RR_SHADE_ARG(ka, qin.r0)[i]; r1 = RR_SHADE_ARG(ka, qin.r1)[i]; r2 = RR_SHADE_ARG(ka, qin.r2)[i]; }
         const uint32_t pix = __float_as_uint(r1.w);
         pix_of_nf = pix;
         const uint32_t meta = r2.x, node = r2.y;
@@ -428,9 +491,9 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
                 const float dx = hit_dist * RR_DEPTH_SCALE;
                 aux_d = rr_abs(dx) < 33554432.0f ? __float2int_rn(dx) : RR_DEPTH_WIDE;
             }
-            fix_add(aux_nx, normal.x, RR_FIX_SCALE, RR_FIX_CLAMP, acc.normal, pix);
-            fix_add(aux_ny, normal.y, RR_FIX_SCALE, RR_FIX_CLAMP, acc.normal ? acc.normal + acc.n : nullptr, pix);
-            fix_add(aux_nz, normal.z, RR_FIX_SCALE, RR_FIX_CLAMP, acc.normal ? acc.normal + 2ull * acc.n : nullptr, pix);
+            fix_add_at(aux_nx, normal.x, RR_FIX_SCALE, RR_FIX_CLAMP, normal_plane(0u), pix);
+            fix_add_at(aux_ny, normal.y, RR_FIX_SCALE, RR_FIX_CLAMP, normal_plane(1u), pix);
+            fix_add_at(aux_nz, normal.z, RR_FIX_SCALE, RR_FIX_CLAMP, normal_plane(2u), pix);
             if ((normal.x - normal.x) + (normal.y - normal.y) + (normal.z - normal.z) + (hit_dist - hit_dist) != 0.0f) { // rare: something is not finite
                 if (hit_dist != hit_dist) nf |= RR_NF_DEPTH_NAN;
                 if (normal.x != normal.x) nf |= RR_NF_NORMAL_NAN;
@@ -444,7 +507,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         // ---- normal mapping (:757-784)
         f3 surface_normal = mapped_normal(sc, m, has_uv, uv, normal, flat_frame_entry(hi, hit.z));
         // the generator is keyed on the FRAME pixel (y * width + x), never on the accumulator slot
-        const uint32_t xy = slot_xy[pix];
+        const uint32_t xy = RR_SHADE_ARG(ka, slot_xy)[pix];
         RngKey rk; rk.seed_lo = fr.seed_lo; rk.seed_hi = fr.seed_hi;
         rk.pixel = (xy >> 16) * fr.width + (xy & 0xffffu); rk.sample = sample; rk.node = node;
         const bool mc = fr.monte_carlo != 0u && (m.flags & RR_MF_MONTE_CARLO) != 0u;
@@ -505,18 +568,21 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             sum_pix = pix;
             const float kr_ = thr * (fr.fog_color[0] * fa + ambient_color.x), kg_ = thr * (fr.fog_color[1] * fa + ambient_color.y), kb_ = thr * (fr.fog_color[2] * fa + ambient_color.z);
             nf |= nonfinite_flags(kr_, kg_, kb_);
-            fix_add(sum_r, kr_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb, pix); fix_add(sum_g, kg_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + acc.n, pix);
-            fix_add(sum_b, kb_, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + 2ull * acc.n, pix);
+            fix_add_at(sum_r, kr_, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(0u), pix); fix_add_at(sum_g, kg_, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(1u), pix);
+            fix_add_at(sum_b, kb_, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(2u), pix);
         }
         // ---- object id (:744, :966-969): the last sample's id, passed through fully transparent hits
         const bool child_idc = idc && spawn_refr && approx_equal(alpha, 0.0f);
-        if (acc.object_id && idc && !child_idc && sample + 1u == fr.samples) acc.object_id[pix] = it_id;
+        if (idc && !child_idc && sample + 1u == fr.samples) {
+            uint32_t* const object_id = RR_SHADE_ARG(ka, acc.object_id);
+            if (object_id) object_id[pix] = it_id;
+        }
 
         // ---- lights (:814-920)
         const f3 view_dir = normalize3(-rd);
         uint32_t lk = 0xffffffffu; // ordinal among the enabled lights
         for (uint32_t li = 0; li < sc.n_lights; li++) {
-            const DLight& L = rr_global(sc.lights)[li];
+            const DLight L = light_uniform(sc.lights, li); // (all three groups are requested before the type is tested)
             if (L.type & 0x80u) continue; // disabled
             lk++;
             const f3 lpos = mk3(L.pos[0], L.pos[1], L.pos[2]), ldir = mk3(L.dir[0], L.dir[1], L.dir[2]);
@@ -562,27 +628,27 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             const bool want_shadow = (m.flags & RR_MF_RECEIVE_SHADOW) != 0u && (nonzero || (sc.any_alpha_occluder != 0u && (it_flags & RR_IF_UV_MAY_BE_NAN) != 0u));
             if (!(m.flags & RR_MF_RECEIVE_SHADOW) && nonzero) {
                 nf |= nonfinite_flags(cr, cg, cb);
-                fix_add(sum_r, cr, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb, pix); fix_add(sum_g, cg, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + acc.n, pix);
-                fix_add(sum_b, cb, RR_FIX_SCALE, RR_FIX_CLAMP, acc.rgb + 2ull * acc.n, pix);
+                fix_add_at(sum_r, cr, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(0u), pix); fix_add_at(sum_g, cg, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(1u), pix);
+                fix_add_at(sum_b, cb, RR_FIX_SCALE, RR_FIX_CLAMP, rgb_plane(2u), pix);
                 if constexpr (SPLIT) {
                     if (depth == 1u) {
                         dif_pix = pix;
-                        fix_add(dif_r, dr, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb, pix); fix_add(dif_g, dg, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + dacc.n, pix);
-                        fix_add(dif_b, db, RR_FIX_SCALE, RR_FIX_CLAMP, dacc.rgb + 2ull * dacc.n, pix);
+                        fix_add_at(dif_r, dr, RR_FIX_SCALE, RR_FIX_CLAMP, dif_plane(0u), pix); fix_add_at(dif_g, dg, RR_FIX_SCALE, RR_FIX_CLAMP, dif_plane(1u), pix);
+                        fix_add_at(dif_b, db, RR_FIX_SCALE, RR_FIX_CLAMP, dif_plane(2u), pix);
                     }
                 }
             }
             // Hundreds of unshadowed lights: the 32-bit sums are flushed every 32 enabled lights, whether or not THIS light added a term
             // (inside the branch above a light 31 or 63 with a zero term skipped its flush, and 96 terms can pass 2^31).
             if (!(m.flags & RR_MF_RECEIVE_SHADOW) && (lk & 31u) == 31u) {
-                if (sum_r) atomicAdd((unsigned long long*)acc.rgb + pix, (unsigned long long)(long long)sum_r);
-                if (sum_g) atomicAdd((unsigned long long*)acc.rgb + acc.n + pix, (unsigned long long)(long long)sum_g);
-                if (sum_b) atomicAdd((unsigned long long*)acc.rgb + 2ull * acc.n + pix, (unsigned long long)(long long)sum_b);
+                if (sum_r) atomicAdd((unsigned long long*)rgb_plane(0u)() + pix, (unsigned long long)(long long)sum_r);
+                if (sum_g) atomicAdd((unsigned long long*)rgb_plane(1u)() + pix, (unsigned long long)(long long)sum_g);
+                if (sum_b) atomicAdd((unsigned long long*)rgb_plane(2u)() + pix, (unsigned long long)(long long)sum_b);
                 sum_r = sum_g = sum_b = 0;
                 if constexpr (SPLIT) {
-                    if (dif_r) atomicAdd((unsigned long long*)dacc.rgb + pix, (unsigned long long)(long long)dif_r);
-                    if (dif_g) atomicAdd((unsigned long long*)dacc.rgb + dacc.n + pix, (unsigned long long)(long long)dif_g);
-                    if (dif_b) atomicAdd((unsigned long long*)dacc.rgb + 2ull * dacc.n + pix, (unsigned long long)(long long)dif_b);
+                    if (dif_r) atomicAdd((unsigned long long*)dif_plane(0u)() + pix, (unsigned long long)(long long)dif_r);
+                    if (dif_g) atomicAdd((unsigned long long*)dif_plane(1u)() + pix, (unsigned long long)(long long)dif_g);
+                    if (dif_b) atomicAdd((unsigned long long*)dif_plane(2u)() + pix, (unsigned long long)(long long)dif_b);
                     dif_r = dif_g = dif_b = 0;
                 }
             }
@@ -621,12 +687,16 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         } // active
         if (sq_fixed) { // which lanes of this packet hold a shadow ray, per enabled light (zero words too: the shadow kernel reads them all)
             const uint32_t pk = (base - chunk_begin) / RR_WAVE, n_pk = sq_cap / RR_WAVE;
+            unsigned long long* const sq_valid = RR_SHADE_ARG(ka, sq_valid);
             for (uint32_t k = 0; k < sc.n_enabled_lights; k++) {
                 const unsigned long long mk = __ballot((sq_wrote >> k) & 1u);
                 if (lane == 0) sq_valid[k * n_pk + pk] = mk;
             }
         }
-        if (nf) atomicOr(&acc.flags[pix_of_nf], nf); // rare: a non-finite term
+        if (nf) atomicOr(&RR_SHADE_ARG(ka, acc.flags)[pix_of_nf], nf); // rare: a non-finite term
+        const DAccum acc = shade_arg_accum(ka); // the planes of the merges below, in SGPRs from here to the packet's end only
+        [[maybe_unused]] DAccum dacc = acc; // SPLIT: the diffuse planes behind the colour planes' own interface (accum_merged_runs)
+        if constexpr (SPLIT) dacc.rgb = dif_rgb;
         // One-pixel packets exist on level 1 only, so only the PRIMARY build asks for them (accum_hit_merged: one test, seven wave sums, one
         // atomic instruction); the deeper levels' compacted waves would pay for the test and never pass it.  The SPLIT builds sit at 128
         // VGPRs and spill to scratch with the test in them: they keep the segmented forms too.
@@ -652,7 +722,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             if (threadIdx.x == 0) {
                 uint32_t total = 0;
                 for (uint32_t w2 = 0; w2 < RR_BLOCK / RR_WAVE; w2++) total += s_child_n[parity][w2];
-                s_child_base[parity] = total ? atomicAdd(qout_count, total) : 0u;
+                s_child_base[parity] = total ? atomicAdd(RR_SHADE_ARG(ka, qout_count), total) : 0u;
             }
             __syncthreads();
             uint32_t obase = s_child_base[parity];
@@ -660,11 +730,11 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
             const unsigned long long below = (1ull << lane) - 1ull;
             if (spawn_refl) {
                 const uint32_t oi = obase + (uint32_t)__popcll(m_refl & below);
-                qout.r0[oi] = c1_r0; qout.r1[oi] = c1_r1; qout.r2[oi] = c1_r2;
+                RR_SHADE_ARG(ka, qout.r0)[oi] = c1_r0; RR_SHADE_ARG(ka, qout.r1)[oi] = c1_r1; RR_SHADE_ARG(ka, qout.r2)[oi] = c1_r2;
             }
             if (spawn_refr) {
                 const uint32_t oi = obase + n_refl + (uint32_t)__popcll(m_refr & below);
-                qout.r0[oi] = c2_r0; qout.r1[oi] = c2_r1; qout.r2[oi] = c2_r2;
+                RR_SHADE_ARG(ka, qout.r0)[oi] = c2_r0; RR_SHADE_ARG(ka, qout.r1)[oi] = c2_r1; RR_SHADE_ARG(ka, qout.r2)[oi] = c2_r2;
             }
         }
     }
@@ -675,6 +745,7 @@ __global__ __launch_bounds__(RR_BLOCK, RR_SHADE_WAVES) void k_shade(const DShade
         n_secondary += __shfl_down(n_secondary, off);
     }
     if (lane == 0) {
+        unsigned long long* const counters = RR_SHADE_ARG(kernarg_segment(), counters);
         if (n_shaded) atomicAdd(&counters[RR_CNT_SHADED], (unsigned long long)n_shaded);
         if (n_shadow) atomicAdd(&counters[RR_CNT_SHADOW], (unsigned long long)n_shadow);
         if (n_secondary) atomicAdd(&counters[RR_CNT_SECONDARY], (unsigned long long)n_secondary);

@@ -35,8 +35,17 @@ PATCHES = {
     "notex": [(S, "    if (!(m.flags & (RR_MF_TEX_SLOT0 << slot)) || !has_uv) return false; // slot bit = index >= 0 and width > 0", "    return false;")],
     "nochild": [(K, "        spawn_refl = reflectivity > 0.0f && may_recurse;", "        spawn_refl = false;"),
                 (K, "        if (alpha < 1.0f && may_recurse) {\n            // create_transmission", "        if (alpha < -1.0f && may_recurse) {\n            // create_transmission")],
-    "nolight": [(K, "        for (uint32_t li = 0; li < sc.n_lights; li++) {\n            const DLight& L = rr_global(sc.lights)[li];\n            if (L.type & 0x80u) continue; // disabled",
-                 "        for (uint32_t li = 0; li < sc.n_lights; li++) {\n            const DLight& L = rr_global(sc.lights)[li];\n            if (L.type != 0x7fu) continue;")],
+    "nolight": [(K, "            const DLight L = light_uniform(sc.lights, li); // (all three groups are requested before the type is tested)\n            if (L.type & 0x80u) continue; // disabled",
+                 "            const DLight L = light_uniform(sc.lights, li);\n            if (L.type != 0x7fu) continue;")],
+    # Round 26, the ceiling of hiding a packet's stores behind the next packet's first load.  Both arms trace NO level-1 shadow ray (every
+    # validity word is written as zero, so k_trace_shadow<true> idles in both); "novalid" still writes the three 16-byte records per light
+    # and the object id, "nostores" keeps them behind comparisons that never hold.  k_shade<true> of novalid minus that of nostores is what
+    # those stores cost.  The dense queue of the deeper levels is untouched (its records are read back by k_trace_shadow<false>).
+    "novalid": [(K, "                if (sq_fixed) sq_wrote |= 1u << lk;", "                if (false) sq_wrote |= 1u << lk;")],
+    "nostores": [(K, "                if (sq_fixed) sq_wrote |= 1u << lk;", "                if (false) sq_wrote |= 1u << lk;"),
+                 (K, "                sq.s0[si] = make_float4(so.x, so.y, so.z, limit);\n                sq.s1[si] = make_float4(sd.x, sd.y, sd.z, __uint_as_float((uint32_t)item_idx | (depth << 27)));\n                sq.s2[si] = make_float4(cr, cg, cb, __uint_as_float(pix));\n",
+                  "                if (!sq_fixed || so.x + sd.x + cr + cg + cb + limit == 12345.678f) {\n                sq.s0[si] = make_float4(so.x, so.y, so.z, limit);\n                sq.s1[si] = make_float4(sd.x, sd.y, sd.z, __uint_as_float((uint32_t)item_idx | (depth << 27)));\n                sq.s2[si] = make_float4(cr, cg, cb, __uint_as_float(pix));\n                }\n"),
+                 (K, "            if (object_id) object_id[pix] = it_id;", "            if (object_id && it_id == 0x5a5a5a5bu) object_id[pix] = it_id;")],
 }
 
 

@@ -14,7 +14,7 @@ B="python3 $R/bench.py --no-cpu-baseline --no-extras $*"
 if [ "$mode" != "quick" ]; then
   python3 $R/bench.py --full "$@" > $out/bench_n1.json 2> $out/bench_n1.err || { echo "bench failed"; tail -5 $out/bench_n1.err; exit 1; }
 fi
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $B --steps 3 --warmup 1 > $out/stats_bench.json 2> $out/stats.err || { echo "stats pass failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $B --steps 3 --warmup 1 > $out/stats_bench.json 2> $out/stats.err || { echo "stats pass failed"; exit 1; }
 pass() { # name, counters...
   name=$1; shift
   timeout -k 10 240 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $out/pmc_$name -- $B --steps 1 --warmup 0 > $out/pmc_$name.json 2> $out/pmc_$name.err || { echo "pmc pass $name failed (see pmc_$name.err)"; tail -3 $out/pmc_$name.err; return 1; }
