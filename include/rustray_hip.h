@@ -286,7 +286,8 @@ typedef struct rr_pick_result {
  * caller's stream).  Where such a level is one slice of the ray arena, its closest hits are traced stage by stage as well, on a
  * third stream beside the other two: launches_trace_closest_level1 then counts one launch per stage (not one per batch), and
  * ms_trace_closest_level1 -- with it ms_trace_closest -- is a sum of durations that overlap the shade and shadow launches' in
- * the same way. */
+ * the same way.  The shadow launches of the level's last two stages run beside each other and beside the first launches of level 2
+ * (whose shade and shadow launches join them where their shadow queue fits into the buffer at rest): those durations overlap too. */
 typedef struct rr_frame_stats {
     uint64_t primary_rays;
     uint64_t secondary_rays; /* reflection + refraction */

@@ -3,6 +3,7 @@
 //         launch_trace_closest; FrameEnd, FrameIo and its makers frame_io and pixels_io, frame_end_plan (what an ending implies),
 //         ALL_PLANES; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun and its maker
 //         make_frame_run; launch_shade and launch_shadow (THE launch sites of k_shade and k_trace_shadow), read_back_level_size;
+//         join_shadow, join_shadow_for, drain_shadow (the staged level 1's last shadow launches stay pending while the frame's stream goes on);
 //         run_level (with level 1 in stages on three streams; with FrameEnd::ALBEDO level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h;
 //         with FrameEnd::RECORD_SPLIT level 1 runs the SPLIT builds of the two kernels, serially: rr_api_pixel_split.h); pick_build;
 //         take_stream, begin_frame_stats;
@@ -12,7 +13,7 @@
 //         rr_scene_set_compat, rr_scene_set_tuning, rr_scene_get_tuning.
 // Needs:  rr_api_base.h, rr_sample_table.h (rr_sample_table, cell_size_of, fill_region, check_region), rr_api_handle.h (writes
 //         rr_scene::frame and rr_scene::timing), rr_api_scene.h (ensure_camera_reach; reads rr_scene::data), rr_frame_plan.h (plan_frame,
-//         plan_level1_stages, plan_shade_chunk, level_slice, batch_group),
+//         plan_level1_stages, plan_shade_chunk, level1_tail, chunk_clear_of_tail, level_slice, batch_group),
 //         rr_primary_setup.h, rr_pixel_list.h, the frame kernels of rr_kernels.hip.
 
 // ---------------------------------------------------------------------------
@@ -414,6 +415,10 @@ struct FrameRun {
     bool level1_only = false;          // FrameEnd::ALBEDO: level 1 ends in k_albedo_level1 (R = 0: the level spawns nothing; never in stages)
     // FrameEnd::RECORD_SPLIT: the diffuse planes (3 x acc.n words) and the fourth shadow-queue array; level 1 runs the SPLIT builds, never in stages
     long long* diffuse = nullptr; float4* sq_s3 = nullptr;
+    // the event behind the shadow launches that still run on the handle's other streams while `st` goes on, and the rays of the shadow-queue
+    // allocation they read (join_shadow); nullptr = none.  shadow_rest: while they are pending, the event behind the shadow launch that last
+    // read the buffer in front of theirs, until `st` has waited for it (join_shadow_for); nullptr = no such launch, or waited for
+    hipEvent_t shadow_pending = nullptr, shadow_rest = nullptr; Level1Tail shadow_tail{0, 0, -1, -1};
     DRayQueue queue_at(uint64_t base) const {
         return DRayQueue{s->frame.arena[0].as<float4>() + base, s->frame.arena[1].as<float4>() + base, s->frame.arena[2].as<uint2>() + base, s->frame.arena[3].as<uint4>() + base};
     }
@@ -424,6 +429,42 @@ static FrameRun make_frame_run(rr_scene* s, hipStream_t st, const FramePlan& pla
     return FrameRun{s, st, plan, R, DShadowQueue{s->frame.sq[0].as<float4>(), s->frame.sq[1].as<float4>(), s->frame.sq[2].as<float4>()}, acc, CounterPool{s, st}, pr, cancel,
                     s->n_cus * RR_SHADOW_GRID_WG, // RR_STACK_DEPTH KB of LDS stack per 256-thread workgroup
                     s->n_cus * RR_SHADE_GRID_WG, slot_xy, false, level1_only};
+}
+
+// THE deferred join.  The staged level 1 leaves the shadow launches of its last two stages running on the handle's second and third streams
+// (FrameRun::shadow_pending, the event behind both) so that the next level runs beside them on `st`: its closest-hit launch shares nothing
+// with them but integer atomics.  This makes `st` wait for them and clears the flag.  It stands in front of everything on `st` that may
+// touch what those launches read (their buffers of the shadow queue, the validity words, their counters and head words) or what the frame
+// returns: every launch_shade of the serial loop (with the take_chunk_shadow in front of it) unless the chunk's queue keeps clear of the
+// buffers (join_shadow_for: `st` then waits for the earlier stage's shadow launch that read the buffer it writes, long over as a rule, and
+// the chunk's shade and shadow launches run beside the two as well), the staged path's entry (its fork of the third stream
+// and its first shade launch), start_batch of the next batch, the pass hook's resolve, and the frame's resolve and end event.
+// A frame that ends early is drained by drain_shadow instead.
+static int join_shadow(FrameRun& f) {
+    if (!f.shadow_pending) return RR_OK;
+    HIP_TRY(hipStreamWaitEvent(f.st, f.shadow_pending, 0)); // (stage_tail follows every shadow launch of the level: the one shadow_rest names too)
+    f.shadow_pending = nullptr; f.shadow_rest = nullptr;
+    return RR_OK;
+}
+// In front of the shade launch of the chunk `g` of the serial loop, whose queue starts at ray 0 of the allocation.  A chunk that keeps clear
+// of the two buffers in use (rr_frame_plan.h chunk_clear_of_tail) writes the buffer in front of them, which the shadow launch of an earlier
+// stage read (Level1Tail::rest_stage) and for which no shade launch of the level has waited: `st` waits for THAT launch, once -- every
+// later chunk follows this one on `st` -- instead of for the two that still run.
+static int join_shadow_for(FrameRun& f, const ShadeChunk& g) {
+    if (!f.shadow_pending || !chunk_clear_of_tail(g, f.shadow_tail)) return join_shadow(f);
+    if (f.shadow_rest) {
+        HIP_TRY(hipStreamWaitEvent(f.st, f.shadow_rest, 0));
+        f.shadow_rest = nullptr;
+    }
+    return RR_OK;
+}
+// ... and the way out of a frame that ends early (cancel flag, HIP error, counters_exhausted, arena too small), with launches pending or
+// after a join that failed: the second stream (which has waited for the third) and then `st` are idle when this returns, as
+// run_level1_stages leaves them
+static void drain_shadow(FrameRun& f) {
+    if (f.s->frame.overlap_stream) (void)hipStreamSynchronize(f.s->frame.overlap_stream);
+    f.shadow_pending = nullptr; f.shadow_rest = nullptr;
+    (void)hipStreamSynchronize(f.st);
 }
 
 // Where the shadow rays of one shade chunk go: the queue and its validity words (the handle's, from `ray_offset` / `valid_offset` on: a
@@ -543,10 +584,15 @@ static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* lev
 // its own head word.  The stream forks from `st` where the path begins -- behind the frame's uploads and memsets, the zeroing of the counter
 // pool and the previous batch's last shade launch, which reads hit1 -- and nothing else orders its launches: hit1 covers the level, so they
 // run ahead as far as the CUs allow.  Shade k waits for the event behind closest-hit launch k; the wait of the last stage joins the stream into `st`.
+// The second stream is NOT joined into `st` where the path ends.  When the last stage has been shaded, the shadow launch of the stage before it
+// has only just begun (shadow k trails shade k + 1) and the last stage's would follow it, alone; then level 2, one small launch at a time.
+// Instead the last stage's shadow launch goes to the third stream, beside its predecessor, and both stay pending (join_shadow) while `st`
+// goes on with level 2.
 static int ensure_overlap_stream(rr_scene* s) {
     if (!s->frame.overlap_stream) HIP_TRY(hipStreamCreateWithFlags(&s->frame.overlap_stream, hipStreamNonBlocking));
     if (!s->frame.closest_stream) HIP_TRY(hipStreamCreateWithFlags(&s->frame.closest_stream, hipStreamNonBlocking));
     if (!s->frame.stage_fork) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_fork, hipEventDisableTiming));
+    if (!s->frame.stage_tail) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_tail, hipEventDisableTiming));
     for (int b = 0; b < 3; b++) {
         if (!s->frame.stage_shaded[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_shaded[b], hipEventDisableTiming));
         if (!s->frame.stage_traced[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame.stage_traced[b], hipEventDisableTiming));
@@ -562,6 +608,7 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
     const hipStream_t st = f.st, st2 = s->frame.overlap_stream, st3 = s->frame.closest_stream;
     unsigned long long* counters = s->frame.counters.as<unsigned long long>();
     if (sp.sq_need > s->frame.sq_cap || sp.valid_need * 8 > s->frame.sq_valid.bytes) return fail(RR_ERR_DEVICE, "internal: shadow queue smaller than its stage buffers");
+    RR_TRY(join_shadow(f)); // (a level in several slices: the previous slice's last shadow stage reads the buffers and events this one reuses)
     uint32_t* closest_heads = nullptr; // one per closest-hit launch, RR_SQ_STRIDE words apart, zeroed on `st` before the fork
     if (trace_closest) {
         if (s0 != 0 || s1 != f.pr.n || sp.stage % RR_WAVE != 0) return fail(RR_ERR_DEVICE, "internal: closest-hit stages over a part of level 1");
@@ -578,9 +625,10 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         const bool first = k == 0, last = k + 1 == sp.n_stages;
         const ShadeChunk g = plan_shade_chunk(c0, c1, s->data.n_enabled_lights, true); // (sq_cap <= sp.stage: lights x this many slots fit the buffer)
         const ChunkShadow q = take_chunk_shadow(f, sp.ray_offset[b], sp.valid_offset[b]); // (its head word is zeroed on `st` before the event the second stream waits for)
-        // the first stage's shade and the last stage's shadow run alone: the serial loop's grids.  In between the two launches share the CUs.
+        // the first stage's shade runs alone: the serial loop's grid.  After it the launches share the CUs, the last stage's shadow launch too:
+        // it runs beside the one before it and beside level 2 (rr_kernels.hip, RR_L1_SHADOW_WG: what was measured)
         const uint64_t shade_wg = first ? (uint64_t)f.shade_grid_max : (RR_L1_SHADE_WG ? (uint64_t)s->n_cus * RR_L1_SHADE_WG : g.groups);
-        const uint64_t shadow_wg = last ? (uint64_t)f.shadow_grid : (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
+        const uint64_t shadow_wg = (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
         if (trace_closest) { // the host is stages ahead of the device: launch k is enqueued long before launch k - 1 ends
             {
                 ScopedTimer t(s, st3, TK_CLOSEST, true);
@@ -594,12 +642,21 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         RR_TRY(launch_shade(f, true, qin, count, c0, c1, qout, child_count, g, q, shade_wg, st));
         if (spawns && last) RR_TRY(read_back_level_size(f, child_count)); // behind the last shade stage
         HIP_TRY(hipEventRecord(s->frame.stage_shaded[b], st));
-        HIP_TRY(hipStreamWaitEvent(st2, s->frame.stage_shaded[b], 0));
-        RR_TRY(launch_shadow(f, g, q, shadow_wg, st2));
-        HIP_TRY(hipEventRecord(s->frame.stage_traced[b], st2));
+        // The last stage's shadow launch goes to the third stream, idle by now (its last closest-hit launch ended before this stage was shaded):
+        // on the second stream it would start only when the stage before it has been traced, and run alone.  It reads its own buffer and counters.
+        const hipStream_t st_shadow = last ? st3 : st2;
+        HIP_TRY(hipStreamWaitEvent(st_shadow, s->frame.stage_shaded[b], 0));
+        RR_TRY(launch_shadow(f, g, q, shadow_wg, st_shadow));
+        HIP_TRY(hipEventRecord(s->frame.stage_traced[b], st_shadow));
     }
-    // the second stream joins `st` here: before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
-    HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[sp.buffer_of(sp.n_stages - 1)], 0));
+    // the second stream joins `st` later (join_shadow): before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
+    // ... and the third stream through it: stage_tail, on the second stream, follows the shadow launches of the last two stages
+    HIP_TRY(hipStreamWaitEvent(st2, s->frame.stage_traced[sp.buffer_of(sp.n_stages - 1)], 0));
+    HIP_TRY(hipEventRecord(s->frame.stage_tail, st2));
+    f.shadow_pending = s->frame.stage_tail;
+    f.shadow_tail = level1_tail(sp);
+    // (stage_traced[rest_buffer] was last recorded behind the shadow launch of rest_stage: the two stages after it use the other buffers)
+    f.shadow_rest = f.shadow_tail.rest_stage >= 0 ? s->frame.stage_traced[f.shadow_tail.rest_buffer] : nullptr;
     return RR_OK;
 }
 
@@ -611,6 +668,7 @@ static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueu
     RR_TRY(ensure_overlap_stream(s));
     const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns, trace_closest);
     if (rc != RR_OK) {
+        f.shadow_pending = nullptr; f.shadow_rest = nullptr; // (an earlier slice's: the second stream is drained here)
         (void)hipStreamSynchronize(s->frame.closest_stream);
         (void)hipStreamSynchronize(s->frame.overlap_stream);
         (void)hipStreamSynchronize(f.st);
@@ -673,6 +731,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
                                    f.pr, qin.hit, count, (uint32_t)c0, (uint32_t)c1, f.acc);
                 continue;
             }
+            RR_TRY(join_shadow_for(f, g)); // the chunk's queue starts where the staged level 1 keeps its first buffer
             const ChunkShadow q = take_chunk_shadow(f, 0, 0);
             RR_TRY(launch_shade(f, l1, qin, count, c0, c1, qout, child_count, g, q, (uint64_t)f.shade_grid_max, st));
             // The size of the next level is final once the slice's last shade chunk has run: its read-back is enqueued
@@ -687,6 +746,7 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
         if (m == 0) continue;
         uint64_t level_base = child_base;
+        // (no join in front of bin_level: its kernels read and write the arena and fresh words of the counter pool, nothing a pending shadow launch touches)
         RR_TRY(bin_level(f, child_base, m, &level_base));
         RR_TRY(run_level(f, d + 1, level_base, m, child_count));
     }
@@ -723,6 +783,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_
     for (uint64_t first = first0; first < total_primary; first += B) {
         if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
         const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
+        RR_TRY(join_shadow(f)); // the previous batch's last shadow launch reads counters of the pool that start_batch zeroes
         RR_TRY(f.pool.start_batch());
         uint32_t* level1_count = f.pool.take(1);
         // The batch covers primary indices [first, first + n_batch): index i -> sample i / npix, pixel i % npix.
@@ -736,6 +797,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_
         if (hook && hook->fn && done < total_primary && done % npix == 0) {
             DFrame pf = fr;
             pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
+            RR_TRY(join_shadow(f));
             launch_resolve(f, pf, io);
             RR_TRY(copy_outputs(*hook->host, *io.out, (size_t)fr.width * fr.height, f.st));
             InPass in_pass(s);
@@ -809,7 +871,9 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     FrameRun f = make_frame_run(s, st, plan, R, end.level1_only, acc, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, slot_xy, cancel);
     if (end.split) { f.diffuse = diffuse; f.sq_s3 = s->frame.sq3.as<float4>(); }
     HIP_TRY(hipEventRecord(s->timing.frame_a, st));
-    RR_TRY(run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix));
+    int rc = run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix);
+    if (rc == RR_OK) rc = join_shadow(f); // level 2 empty, or a level 1 that spawns nothing: the join falls here
+    if (rc != RR_OK) { drain_shadow(f); return rc; }
     launch_resolve(f, fr, io);
     HIP_TRY(hipEventRecord(s->timing.frame_b, st));
     HIP_TRY(hipGetLastError());

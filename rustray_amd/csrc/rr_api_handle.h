@@ -95,6 +95,7 @@ struct FrameState {
     // behind stage_fork, and stage_closest[k % 3] follows the closest-hit launch of stage k
     hipStream_t closest_stream = nullptr;
     hipEvent_t stage_fork = nullptr, stage_closest[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t stage_tail = nullptr; // behind the shadow launches of the last two stages: what the frame's stream joins late (rr_api_frame.h join_shadow)
     uint32_t overlap_stages = 0; // level-1 stages of the last frame that ran on the two streams (rr_scene_overlap_stages)
     uint32_t* h_count = nullptr; // pinned, 16 words, by HC_*: what the host waits for (every wait reads its word before the next one is issued)
     std::vector<uint16_t> table_cache; uint16_t table_samples = 0; // built-in sub-sample table of the last sample count
@@ -113,6 +114,7 @@ struct FrameState {
         for (hipEvent_t e : stage_traced) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : stage_closest) if (e) (void)hipEventDestroy(e);
         if (stage_fork) (void)hipEventDestroy(stage_fork);
+        if (stage_tail) (void)hipEventDestroy(stage_tail);
         if (overlap_stream) (void)hipStreamDestroy(overlap_stream);
         if (closest_stream) (void)hipStreamDestroy(closest_stream);
     }

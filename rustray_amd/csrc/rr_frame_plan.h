@@ -195,6 +195,30 @@ inline ShadeChunk plan_shade_chunk(uint64_t c0, uint64_t c1, uint32_t n_enabled_
     return ShadeChunk{fixed, groups, sq_cap, sq_packets, segcap, (shadow_rays + RR_BLOCK - 1) / RR_BLOCK};
 }
 
+// ---- the end of a staged level 1 (rr_api_frame.h join_shadow) ------------------------------------------------------------------
+// When the last stage has been shaded, the shadow launches of the last TWO stages may still run (stage n - 2 trails the shade launches by
+// one stage, stage n - 1 has only just begun), and the frame's stream goes on to level 2 beside them.  [lo, hi) = the rays of the
+// shadow-queue allocation they read: the hull of the two buffers (of the one buffer where the level has a single stage).
+// The rays [0, lo) in front of them belong to the buffers the two do not use, and those are not at rest by themselves: the shadow launch
+// of an EARLIER stage read them, and no shade launch of the level has waited for the latest of those (shade k waits for shadow k - n_buf
+// only).  rest_stage = that stage, the last one before n - 2 whose buffer lies in [0, lo) (-1: there is none), rest_buffer = its buffer:
+// whoever writes [0, lo) without waiting for the two launches of the tail must wait for the shadow launch of rest_stage instead.
+struct Level1Tail { uint64_t lo, hi; int32_t rest_stage, rest_buffer; };
+inline Level1Tail level1_tail(const Level1Stages& sp) {
+    const uint64_t a = sp.ray_offset[sp.buffer_of(sp.n_stages - 1)], b = sp.n_stages >= 2 ? sp.ray_offset[sp.buffer_of(sp.n_stages - 2)] : a;
+    Level1Tail t{std::min(a, b), std::max(a, b) + sp.buf_rays, -1, -1};
+    for (int64_t k = (int64_t)sp.n_stages - 3; k >= 0 && t.rest_stage < 0; k--)
+        if (sp.ray_offset[sp.buffer_of((uint32_t)k)] < t.lo) { t.rest_stage = (int32_t)k; t.rest_buffer = (int32_t)sp.buffer_of((uint32_t)k); }
+    return t;
+}
+// A chunk of the serial loop writes its shadow rays from ray 0 of the allocation on.  May its shade launch run while the launches of
+// `tail` still read their buffers?  Only a chunk of the dense queue (a chunk with fixed slots writes the validity words as well, from word
+// 0 on) whose shards all end in front of the tail: with three buffers and a stage count that is a multiple of three the last two stages
+// use buffers 1 and 2, and a deeper level that fits into buffer 0 need only wait for the shadow launch of rest_stage, which read it last.
+inline bool chunk_clear_of_tail(const ShadeChunk& g, const Level1Tail& tail) {
+    return !g.fixed && g.segcap * RR_SQ_SHARDS <= tail.lo;
+}
+
 // The sample group of the batch [first, first + n): G where the batch holds whole groups of whole sample slices, else 1.
 inline uint32_t batch_group(const FramePlan& p, uint32_t npix, uint64_t first, uint64_t n) {
     return (n % ((uint64_t)npix * p.G) == 0 && first % npix == 0) ? p.G : 1u;

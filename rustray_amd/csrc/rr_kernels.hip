@@ -94,6 +94,10 @@
 #ifndef RR_L1_CLOSEST_FIRST_WG
 #define RR_L1_CLOSEST_FIRST_WG RR_CLOSEST_WAVES // stage 0 (8: 16.71 - 16.76)
 #endif
+// The end of the staged level 1 (round 27, rr_api_frame.h join_shadow; profiles/r27_ab_tail_overlap.txt, profiles/r27_dropped.txt): the shadow
+// launches of the last two stages run beside each other and beside level 2, so the last stage's launch takes RR_L1_SHADOW_WG like the
+// stages before it.  On the serial loop's grid (exactly the resident workgroups), which it had while it ran alone, the medians are the same
+// to 0.03 ms (15.32 - 15.43 against 15.31 - 15.36 ms in the same calls) and the runs spread twice as far.
 #ifndef RR_DYN_FETCH
 #define RR_DYN_FETCH 4 // packets per fetch from the shared head on large launches (more costs locality: +4 % at 8, +10 % at 16)
 #endif
