@@ -102,10 +102,13 @@ static int check_query_pointer(const rr_scene* s, const void* p, const char* fn,
 }
 // every pointer of a device form in one call, in the order given; a NULL one is an optional the caller left out
 struct QueryPointer { const void* p; const char* arg; };
-static int check_query_pointers(const rr_scene* s, const char* fn, std::initializer_list<QueryPointer> pointers) {
-    for (const QueryPointer& q : pointers)
-        if (q.p) RR_TRY(check_query_pointer(s, q.p, fn, q.arg));
+static int check_query_pointers(const rr_scene* s, const char* fn, const QueryPointer* pointers, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (pointers[k].p) RR_TRY(check_query_pointer(s, pointers[k].p, fn, pointers[k].arg));
     return RR_OK;
+}
+static int check_query_pointers(const rr_scene* s, const char* fn, std::initializer_list<QueryPointer> pointers) {
+    return check_query_pointers(s, fn, pointers.begin(), pointers.size());
 }
 
 // The buffers of one call as a table (rr_arg_ranges.h has the rule): the first forbidden overlap, worded.  An output over an input is
@@ -197,19 +200,23 @@ static int staged_host_call(DevBuf* pool, const StageArg (&args)[N], Body body) 
 
 // THE entry of a record call, its arguments checked: `body()` under the scene's lock on stream st, which a call that ends early leaves
 // idle.  `intact`: the call reads the scene (a call that only filters records works on a broken one too).  `pointers`: the caller's
-// buffers of a device form; a host form has none and runs on the null stream.  `prepare()` is what the call refuses from the scene's
-// host state, before it waits for another stream or enqueues anything.
+// buffers of a device form, as a list or as a pointer and a count; a host form has none and runs on the null stream.  `prepare()` is
+// what the call refuses from the scene's host state, before it waits for another stream or enqueues anything.
 template <class Prepare, class Body>
-static int record_call(rr_scene* s, const char* fn, bool intact, std::initializer_list<QueryPointer> pointers, hipStream_t st, Prepare prepare, Body body) {
+static int record_call(rr_scene* s, const char* fn, bool intact, const QueryPointer* pointers, size_t n_pointers, hipStream_t st, Prepare prepare, Body body) {
     RR_TRY(not_in_pass(s, fn));
     std::lock_guard<std::mutex> lk(s->mu);
     if (intact) RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
-    RR_TRY(check_query_pointers(s, fn, pointers));
+    RR_TRY(check_query_pointers(s, fn, pointers, n_pointers));
     RR_TRY(prepare());
     RR_TRY(take_stream(s, st));
     IdleOnExit idle(st);
     return idle.done(body());
+}
+template <class Prepare, class Body>
+static int record_call(rr_scene* s, const char* fn, bool intact, std::initializer_list<QueryPointer> pointers, hipStream_t st, Prepare prepare, Body body) {
+    return record_call(s, fn, intact, pointers.begin(), pointers.size(), st, prepare, body);
 }
 template <class Body>
 static int record_call(rr_scene* s, const char* fn, bool intact, std::initializer_list<QueryPointer> pointers, hipStream_t st, Body body) {

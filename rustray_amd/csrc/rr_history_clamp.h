@@ -1,11 +1,12 @@
 // rr_history_clamp.h — the arithmetic of the neighbourhood clamp that host and device share (rr_accumulate_clamped_records, steps 7 .. 9
 // of its text in include/rustray_hip.h; the yardstick is rustray_amd/temporal.py: accumulate_clamped_records): the sums over the window
 // of the current frame, the box they make, the clamp of one layer's history mean to it and the shorter length of a pixel whose record
-// layer had to be moved.  Plain host logic, no HIP call and no system include: k_accumulate_clamped_records (rr_kernels.hip) applies
-// these functions per lane between temporal_history and the blends, tests/native/temporal_clamp_test.cpp runs them as a host loop.
-// history_clamp_split is the same for rr_accumulate_clamped_split_records (k_accumulate_clamped_split_records,
-// tests/native/temporal_clamp_split_test.cpp; the yardstick is accumulate_clamped_split_records): the colour side as it stands, and a
-// box of the current diffuse layer for the three diffuse means.
+// layer had to be moved.  history_clamp_split is the same for rr_accumulate_clamped_split_records (the yardstick is
+// accumulate_clamped_split_records): the colour side as it stands, and a box of the current diffuse layer for the three diffuse means.
+// At its end temporal_pixel, THE step of one pixel of the four accumulation calls between its loads and its stores.
+// Plain host logic, no HIP call and no system include: accumulate_pixel_body (rr_kernels.hip, kernels 7e and 7e') applies temporal_pixel
+// per lane, kernels 7e'' and 7e''' write the same sequence out between their stores, tests/native/temporal_pixel_test.cpp runs it as a
+// host loop.
 //
 // Every step is exact in binary32 in the order written here and must be compiled without contraction, as rr_temporal.h.
 #pragma once
@@ -109,4 +110,53 @@ RR_SETUP_HD void history_clamp_split(int r, float sigma_scale, Colour colour, Di
         if (temporal_colour_ok(d->da)) history_clamp_layer(b, d->da);
         if (temporal_colour_ok(d->db)) history_clamp_layer(b, d->db);
     }
+}
+
+// ---- one pixel of rr_accumulate_records and its three variants, between its loads and its stores
+// in: the current record and, with HALVES, the colours of its two halves; with SPLIT the diffuse triple and, with HALVES, those of the two
+// halves.  out: every colour blended where the step below says so (the other floats keep their bits), and the length.
+struct TpPixel {
+    float c[3], depth, n[3];
+    unsigned int id;
+    float a[3], b[3];
+    float d[3], da[3], db[3];
+    float length;
+};
+static_assert(__builtin_offsetof(TpPixel, a) == 32, "c, depth, n and id are the eight words of a record, in its order");
+// the window of a call that does not clamp: never read
+struct TpNoWindow {
+    RR_SETUP_HD bool operator()(int, int, float*) const { return false; }
+};
+
+// The step.  hist: the previous frame as temporal_history reads it, not looked at on the first frame (has_history false); motion: the
+// pixel's 3 floats, or NULL.
+// The four calls differ in SPLIT (the diffuse means ride on the taps and are blended) and CLAMPED (a pixel that kept its history has its
+// means held to the box of `colour`, with SPLIT the diffuse means to the box of `diffuse`: windows of radius r as history_clamp_sums
+// takes them).  A pixel keeps its history when its record has DN_FIN and DN_VALID and temporal_history finds one; its length is then N,
+// else 1 where its colour is finite and 0 where not.  A current half whose colour is not finite keeps its bits (the pixel's own colour is
+// finite where anything is blended); a diffuse layer by temporal_blend_diffuse's rule.
+template <bool HALVES, bool SPLIT, bool CLAMPED, class Hist, class Colour, class Diffuse>
+RR_SETUP_HD void temporal_pixel(const TpFrame& f, unsigned int x, unsigned int y, const float* motion, bool has_history, const Hist& hist, int r, float sigma_scale,
+                                Colour colour, Diffuse diffuse, TpPixel* p) {
+    const unsigned int flags = denoise_flags(p->c, p->depth, p->n);
+    TpMix m;
+    TpSplitMix s;
+    bool kept = false;
+    if (has_history && flags == (unsigned int)(DN_FIN | DN_VALID)) kept = temporal_history<HALVES, Hist, SPLIT>(f, x, y, p->depth, p->n, p->id, motion, hist, &m, &s);
+    if (CLAMPED && kept) {
+        if constexpr (SPLIT) history_clamp_split<HALVES>(r, sigma_scale, colour, diffuse, &m, &s);
+        else history_clamp<HALVES>(r, sigma_scale, colour, &m);
+    }
+    if (kept)
+        for (int k = 0; k < 3; k++) p->c[k] = temporal_blend(m.h[k], m.a, p->c[k]);
+    const float length = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
+    if (SPLIT && kept) temporal_blend_diffuse(s.d, m.a, p->d, p->d);
+    if (HALVES) {
+        if (kept && temporal_colour_ok(p->a))
+            for (int k = 0; k < 3; k++) p->a[k] = temporal_blend(m.ha[k], m.a, p->a[k]);
+        if (kept && temporal_colour_ok(p->b))
+            for (int k = 0; k < 3; k++) p->b[k] = temporal_blend(m.hb[k], m.a, p->b[k]);
+        if (SPLIT && kept) { temporal_blend_diffuse(s.da, m.a, p->da, p->da); temporal_blend_diffuse(s.db, m.a, p->db, p->db); }
+    }
+    p->length = length; // (written last: between the branches above, the device compiler merged this store with one of theirs and kept *p in scratch)
 }

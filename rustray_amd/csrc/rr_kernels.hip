@@ -2280,13 +2280,21 @@ __global__ __launch_bounds__(RR_BLOCK) void k_denoise_split_sum(const float4* re
     }
 }
 
-// 7e: temporal reprojection (rr_accumulate_records; rr_temporal.h has the arithmetic, in the order the header states;
-// rustray_amd/temporal.py is the yardstick).  One pixel per lane, 32x8 tiles as 7a .. 7d, so that the 2x2 taps of neighbouring lanes fall
-// into the same 128-byte lines; no LDS: the shifts are sub-tile and the taps hit in cache.  A record is two 16-byte loads and two 16-byte
-// stores.  Of a tap the guide row (normal, id) is read and tested first, then the colour row (colour, depth), then the length, and only then
-// the colour rows of its two half-histories.  The camera, the previous view and the scalars are the kernel argument f.  HALVES: the
-// one-layer call carries no registers for three layers.  history == NULL: the first frame, every pixel takes the no-history path.
+// 7e, 7e': temporal reprojection (rr_accumulate_records, rr_accumulate_split_records; rr_history_clamp.h: temporal_pixel is the step
+// of one pixel, with rr_temporal.h's arithmetic behind it in the order the headers state; rustray_amd/temporal.py is the yardstick).
+// ONE body, accumulate_pixel_body<HALVES, SPLIT>, behind two entries that keep their names, their arguments and their __restrict__
+// promises.  (7e'' and 7e''', the clamped calls, have bodies of their own below, with the step's sequence written out: behind this
+// body they measured 1 to 3 % slower than before)
+// One pixel per lane, 32x8 tiles as 7a .. 7d, so that the 2x2 taps of neighbouring lanes fall into the same 128-byte lines; no LDS: the
+// shifts are sub-tile and the taps hit in cache.  A record is two 16-byte loads and two 16-byte stores.  Of a tap the guide row (normal,
+// id) is read and tested first, then the colour row (colour, depth), then the length, and only then the colour rows of its two
+// half-histories.  The camera, the previous view and the scalars are the kernel argument f.  HALVES: the one-layer call carries no
+// registers for three layers.  history == NULL: the first frame, every pixel takes the no-history path and every layer is copied.
 // out may be `records` and halves_out `halves`: a lane reads those at its own pixel only, before it writes.
+// SPLIT (7e'): the records, halves and length of the build without it, bit for bit, and the diffuse layers (3 floats a pixel, 3 a half:
+// rr_render_pixel_split's layouts) blended over the same taps with the same weights and length.  A 12-byte diffuse row is three dword
+// loads; consecutive lanes read consecutive rows.  Of a tap the diffuse rows are read last, after its half rows, and only when it is
+// taken.  diffuse_out may be `diffuse` and dif_halves_out `dif_halves`, as halves_out.
 struct TpHistory {
     const float4* __restrict__ history;
     const float4* __restrict__ history_halves;
@@ -2305,46 +2313,6 @@ struct TpHistory {
         c[0] = r0.x; c[1] = r0.y; c[2] = r0.z;
     }
 };
-template <bool HALVES>
-__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
-                                                                 const float4* __restrict__ history_halves, const float* __restrict__ history_length,
-                                                                 const float* __restrict__ motion, float4* out, float4* halves_out, float* __restrict__ length_out) {
-    const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
-    if (x >= f.width || y >= f.height) return;
-    const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
-    const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
-    float4 a0, a1, b0, b1;
-    if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
-    const uint32_t flags = denoise_record_flags(r0, r1);
-    TpMix m;
-    bool kept = false;
-    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
-        const float n_p[3] = {r1.x, r1.y, r1.z};
-        const TpHistory hist{history, history_halves, history_length};
-        kept = temporal_history<HALVES>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr, hist, &m);
-    }
-    float4 c0 = r0;
-    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
-    out[2ull * o] = c0;
-    out[2ull * o + 1] = r1;
-    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
-    if (HALVES) {
-        // a current half whose colour is not finite keeps its bits (the pixel's own colour is finite here)
-        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
-            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
-        }
-        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
-            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
-        }
-        halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
-    }
-}
-
-// 7e': the SPLIT build of 7e (rr_accumulate_split_records): the records, halves and length of k_accumulate_records, bit for bit, and the
-// diffuse layers (3 floats a pixel, 3 a half: rr_render_pixel_split's layouts) blended over the same taps with the same weights and
-// length.  A 12-byte diffuse row is three dword loads; consecutive lanes read consecutive rows.  Of a tap the diffuse rows are read last,
-// after its half rows, and only when it is taken.  No LDS.  diffuse_out may be `diffuse` and dif_halves_out `dif_halves`: a lane reads
-// those at its own pixel only, before it writes.  history == NULL: every layer is copied.
 struct TpSplitHistory : TpHistory {
     const float* __restrict__ history_diffuse;
     const float* __restrict__ history_dif_halves;
@@ -2361,55 +2329,57 @@ struct TpSplitIo { // the diffuse pointers of the call, in the order of its argu
     const float* __restrict__ history_diffuse; const float* __restrict__ history_dif_halves;
     float* diffuse_out; float* dif_halves_out;
 };
-template <bool HALVES>
-__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_split_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
-                                                                       const float4* __restrict__ history_halves, const float* __restrict__ history_length,
-                                                                       const float* __restrict__ motion, float4* out, float4* halves_out,
-                                                                       float* __restrict__ length_out, const TpSplitIo io) {
+template <bool HALVES, bool SPLIT>
+RR_DEV void accumulate_pixel_body(const TpFrame& f, const float4* records, const float4* halves, const float4* history, const float4* history_halves,
+                                  const float* history_length, const float* motion, float4* out, float4* halves_out, float* length_out, const TpSplitIo& io) {
     const int x = (int)blockIdx.x * DN_TILE_W + ((int)threadIdx.x & (DN_TILE_W - 1)), y = (int)blockIdx.y * DN_TILE_H + (int)threadIdx.x / DN_TILE_W;
     if (x >= f.width || y >= f.height) return;
     const unsigned long long o = (unsigned long long)y * (unsigned int)f.width + (unsigned int)x;
     const float4 r0 = records[2ull * o], r1 = records[2ull * o + 1];
     float4 a0, a1, b0, b1;
     if (HALVES) { a0 = halves[4ull * o]; a1 = halves[4ull * o + 1]; b0 = halves[4ull * o + 2]; b1 = halves[4ull * o + 3]; }
-    float d[3] = {io.diffuse[3ull * o], io.diffuse[3ull * o + 1], io.diffuse[3ull * o + 2]}, da[3], db[3];
-    if (HALVES)
-        for (int c = 0; c < 3; c++) { da[c] = io.dif_halves[6ull * o + c]; db[c] = io.dif_halves[6ull * o + 3 + c]; }
-    const uint32_t flags = denoise_record_flags(r0, r1);
-    TpMix m;
-    TpSplitMix s;
-    bool kept = false;
-    if (history && flags == (uint32_t)(DN_FIN | DN_VALID)) {
-        const float n_p[3] = {r1.x, r1.y, r1.z};
-        TpSplitHistory hist;
-        hist.history = history; hist.history_halves = history_halves; hist.history_length = history_length;
-        hist.history_diffuse = io.history_diffuse; hist.history_dif_halves = io.history_dif_halves;
-        kept = temporal_history<HALVES, TpSplitHistory, true>(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), motion ? motion + 3ull * o : nullptr,
-                                                     hist, &m, &s);
+    TpPixel p;
+    p.c[0] = r0.x; p.c[1] = r0.y; p.c[2] = r0.z; p.depth = r0.w;
+    p.n[0] = r1.x; p.n[1] = r1.y; p.n[2] = r1.z; p.id = __float_as_uint(r1.w);
+    if (HALVES) { p.a[0] = a0.x; p.a[1] = a0.y; p.a[2] = a0.z; p.b[0] = b0.x; p.b[1] = b0.y; p.b[2] = b0.z; }
+    if constexpr (SPLIT) {
+        p.d[0] = io.diffuse[3ull * o]; p.d[1] = io.diffuse[3ull * o + 1]; p.d[2] = io.diffuse[3ull * o + 2];
+        if (HALVES)
+            for (int c = 0; c < 3; c++) { p.da[c] = io.dif_halves[6ull * o + c]; p.db[c] = io.dif_halves[6ull * o + 3 + c]; }
     }
-    float4 c0 = r0;
-    if (kept) { c0.x = temporal_blend(m.h[0], m.a, r0.x); c0.y = temporal_blend(m.h[1], m.a, r0.y); c0.z = temporal_blend(m.h[2], m.a, r0.z); }
-    out[2ull * o] = c0;
+    TpSplitHistory hist;
+    hist.history = history; hist.history_halves = history_halves; hist.history_length = history_length;
+    hist.history_diffuse = io.history_diffuse; hist.history_dif_halves = io.history_dif_halves;
+    temporal_pixel<HALVES, SPLIT, false>(f, (unsigned int)x, (unsigned int)y, motion ? motion + 3ull * o : nullptr, history != nullptr, hist, 0, 0.0f, TpNoWindow{},
+                                         TpNoWindow{}, &p);
+    out[2ull * o] = make_float4(p.c[0], p.c[1], p.c[2], r0.w);
     out[2ull * o + 1] = r1;
-    length_out[o] = kept ? m.length : ((flags & DN_FIN) ? 1.0f : 0.0f);
-    if (kept) temporal_blend_diffuse(s.d, m.a, d, d);
-    io.diffuse_out[3ull * o] = d[0]; io.diffuse_out[3ull * o + 1] = d[1]; io.diffuse_out[3ull * o + 2] = d[2];
+    length_out[o] = p.length;
+    if constexpr (SPLIT) { io.diffuse_out[3ull * o] = p.d[0]; io.diffuse_out[3ull * o + 1] = p.d[1]; io.diffuse_out[3ull * o + 2] = p.d[2]; }
     if (HALVES) {
-        if (kept && denoise_is_finite(a0.x) && denoise_is_finite(a0.y) && denoise_is_finite(a0.z)) {
-            a0.x = temporal_blend(m.ha[0], m.a, a0.x); a0.y = temporal_blend(m.ha[1], m.a, a0.y); a0.z = temporal_blend(m.ha[2], m.a, a0.z);
-        }
-        if (kept && denoise_is_finite(b0.x) && denoise_is_finite(b0.y) && denoise_is_finite(b0.z)) {
-            b0.x = temporal_blend(m.hb[0], m.a, b0.x); b0.y = temporal_blend(m.hb[1], m.a, b0.y); b0.z = temporal_blend(m.hb[2], m.a, b0.z);
-        }
+        a0.x = p.a[0]; a0.y = p.a[1]; a0.z = p.a[2]; b0.x = p.b[0]; b0.y = p.b[1]; b0.z = p.b[2];
         halves_out[4ull * o] = a0; halves_out[4ull * o + 1] = a1; halves_out[4ull * o + 2] = b0; halves_out[4ull * o + 3] = b1;
-        if (kept) { temporal_blend_diffuse(s.da, m.a, da, da); temporal_blend_diffuse(s.db, m.a, db, db); }
-        for (int c = 0; c < 3; c++) { io.dif_halves_out[6ull * o + c] = da[c]; io.dif_halves_out[6ull * o + 3 + c] = db[c]; }
+        if constexpr (SPLIT)
+            for (int c = 0; c < 3; c++) { io.dif_halves_out[6ull * o + c] = p.da[c]; io.dif_halves_out[6ull * o + 3 + c] = p.db[c]; }
     }
 }
-
-// 7e'': 7e with the history held to the colours of the current frame (rr_accumulate_clamped_records; rr_history_clamp.h has the
-// arithmetic of steps 7 .. 9).  The colour rows of `records` for the tile and a halo of R points go through LDS, one float4 per point:
-// the colour and, in w, 1 where the point lies inside the frame with three finite floats, else 0 (34 x 10 at R = 1, 36 x 12 = 6912 B at
+template <bool HALVES>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
+                                                                 const float4* __restrict__ history_halves, const float* __restrict__ history_length,
+                                                                 const float* __restrict__ motion, float4* out, float4* halves_out, float* __restrict__ length_out) {
+    accumulate_pixel_body<HALVES, false>(f, records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, TpSplitIo{});
+}
+template <bool HALVES>
+__global__ __launch_bounds__(RR_BLOCK) void k_accumulate_split_records(const TpFrame f, const float4* records, const float4* halves, const float4* __restrict__ history,
+                                                                       const float4* __restrict__ history_halves, const float* __restrict__ history_length,
+                                                                       const float* __restrict__ motion, float4* out, float4* halves_out,
+                                                                       float* __restrict__ length_out, const TpSplitIo io) {
+    accumulate_pixel_body<HALVES, true>(f, records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, io);
+}
+// 7e'': 7e with the history held to the colours of the current frame (rr_accumulate_clamped_records; the sequence is
+// temporal_pixel<HALVES, false, true>'s, which tests/native/temporal_pixel_test.cpp runs on the host, written out here with its stores
+// between the blends).  The colour rows of `records` for the tile and a halo of R points go through LDS, one float4 per point: the
+// colour and, in w, 1 where the point lies inside the frame with three finite floats, else 0 (34 x 10 at R = 1, 36 x 12 = 6912 B at
 // R = 2).  Row-major, as 7c: the lanes of a tile row read consecutive 16-byte slots of one row of the staged tile at each window
 // position (the compiler reads a slot as ds_read_b96 for the colour and ds_read_b32 for w); the staging writes are ds_write_b128 and
 // walk the tile linearly.  EVERY lane stages and reaches the barrier; a lane outside the frame leaves after it.  Then 7e:
@@ -2472,16 +2442,17 @@ __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_clamped_records(const T
     }
 }
 
-// 7e''': 7e'' merged with 7e' (rr_accumulate_clamped_split_records; rr_history_clamp.h: history_clamp_split has the arithmetic).  Two
-// planes of the tile and its halo of R points go through LDS, one float4 per point each: the colour plane of 7e'', and the diffuse plane,
-// the three floats of `diffuse` and, in w, 1 where the point lies inside the frame with three finite DIFFUSE floats, else 0 (2 x 5440 B at
-// R = 1, 2 x 6912 = 13 824 B at R = 2).  Lane e stages point e of both planes: consecutive lanes read the consecutive 12-byte rows of
-// `diffuse` of one row of the staged tile (the compiler merges a lane's three dwords into one global_load_dwordx3, so a wave's load walks
-// that row's bytes without a gap), and write one ds_write_b128 per plane; a window position is a ds_read_b96 and a ds_read_b32 per plane.  EVERY lane stages and reaches the one barrier; a lane outside the frame leaves after it.  Then 7e':
-// temporal_history with the diffuse means, and for a pixel that kept its history the two windows, one after the other, the clamps and the
-// length rule before the blends.  The lane's own diffuse triple is its slot of the diffuse plane.  `out` may NOT be `records` and
-// diffuse_out NOT `diffuse` (another workgroup's halo reads them); halves_out may be `halves` and dif_halves_out `dif_halves`, read at the
-// lane's pixel only.
+// 7e''': 7e'' merged with 7e' (rr_accumulate_clamped_split_records; the sequence is temporal_pixel<HALVES, true, true>'s, written out
+// as in 7e'').  Two planes of the tile and its halo of R points go through
+// LDS, one float4 per point each: the colour plane of 7e'', and the diffuse plane, the three floats of `diffuse` and, in w, 1 where the
+// point lies inside the frame with three finite DIFFUSE floats, else 0 (2 x 5440 B at R = 1, 2 x 6912 = 13 824 B at R = 2).  Lane e stages
+// point e of both planes: consecutive lanes read the consecutive 12-byte rows of `diffuse` of one row of the staged tile (the compiler
+// merges a lane's three dwords into one global_load_dwordx3, so a wave's load walks that row's bytes without a gap), and write one
+// ds_write_b128 per plane; a window position is a ds_read_b96 and a ds_read_b32 per plane.  EVERY lane stages and reaches the one
+// barrier; a lane outside the frame leaves after it.  Then 7e': temporal_history with the diffuse means, and for a pixel that kept its
+// history the two windows, one after the other, the clamps and the length rule before the blends.  The lane's own diffuse triple is its
+// slot of the diffuse plane.  `out` may NOT be `records` and diffuse_out NOT `diffuse` (another workgroup's halo reads them); halves_out
+// may be `halves` and dif_halves_out `dif_halves`, read at the lane's pixel only.
 template <bool HALVES, int R>
 __global__ __launch_bounds__(RR_BLOCK) void k_accumulate_clamped_split_records(const TpFrame f, float sigma_scale, const float4* __restrict__ records, const float4* halves,
                                                                                const float4* __restrict__ history, const float4* __restrict__ history_halves,

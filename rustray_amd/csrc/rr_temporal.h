@@ -1,8 +1,8 @@
 // rr_temporal.h — the arithmetic of the temporal reprojection that host and device share (rr_accumulate_records; the yardstick is
 // rustray_amd/temporal.py: accumulate_records): the pinhole ray through a pixel's centre and the world point a record's depth puts on it,
 // the reprojection into the previous frame, the tap list with its snap, the test of one history tap and the blend of one layer.  Plain
-// host logic, no HIP call and no system include: k_accumulate_records (rr_kernels.hip) applies these functions per lane, and
-// tests/native/temporal_test.cpp runs the same functions as a host loop.
+// host logic, no HIP call and no system include: the accumulation kernels (rr_kernels.hip, 7e .. 7e''') apply these functions per lane
+// (7e and 7e' through temporal_pixel, rr_history_clamp.h), and tests/native/temporal_pixel_test.cpp runs that step as a host loop.
 //
 // Every step is exact in binary32 in the order written here (products, sums, one correctly rounded division or square root at a time)
 // and must be compiled without contraction (-ffp-contract=off, as the library is): host, device and numpy give the same bits.  There

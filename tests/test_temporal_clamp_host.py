@@ -6,7 +6,6 @@ import ctypes as C
 import hashlib
 import os
 import re
-import struct
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 
 from rustray_amd import capi
 from rustray_amd.temporal import EPS, HistoryClampParams, accumulate_clamped_records, accumulate_records, accumulate_split_records, clamp_boxes
+from tests import temporal_host_loop
 from tests.denoise_cases import F, same_bits
 from tests.helpers import ROOT, host_api_source
 from tests.temporal_cases import frame_params, temporal_frame
@@ -25,32 +25,10 @@ NEW = ("rr_accumulate_clamped_records_device", "rr_accumulate_clamped_records")
 
 @pytest.fixture(scope="module")
 def host_loop(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("temporal_clamp") / "temporal_clamp_test")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-o", exe, os.path.join(ROOT, "tests", "native", "temporal_clamp_test.cpp")]
-    subprocess.check_call(cmd)
+    exe = temporal_host_loop.build(tmp_path_factory)
 
     def run(tmp_path, cam, prm, clamp, records, halves, history, history_halves, history_length, motion):
-        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        c = cam.c_struct()
-        W, H = int(c.width), int(c.height)
-        with open(src, "wb") as fh:
-            fh.write(struct.pack("<6I", W, H, halves is not None, history is not None, motion is not None, clamp.radius))
-            fh.write(np.array(c.projection_inverse[:], F).tobytes() + np.array(c.view_inverse[:], F).tobytes())
-            fh.write(np.asarray(prm.prev_world_to_clip, F).T.reshape(16).tobytes() + np.asarray(prm.prev_eye, F).tobytes())
-            fh.write(struct.pack("<5f", prm.max_history, prm.normal_min, prm.sigma_depth, prm.snap, clamp.sigma_scale))
-            for a in (records, halves, history, history_halves, history_length, motion):
-                if a is not None:
-                    fh.write(np.ascontiguousarray(a, F).tobytes())
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "temporal clamp test OK" in out.stdout, out.stdout + out.stderr
-        raw = np.fromfile(dst, F)
-        n = W * H
-        hv = halves is not None
-        assert raw.size == (15 + (16 if hv else 0)) * n
-        at = np.cumsum([0, 8 * n, n, 16 * n if hv else 0, 3 * n, 3 * n])
-        part = [raw[a:b] for a, b in zip(at[:-1], at[1:])]
-        return dict(records=part[0].reshape(n, 8), length=part[1], halves=part[2].reshape(n, 2, 8) if hv else None, lo=part[3].reshape(n, 3), hi=part[4].reshape(n, 3))
+        return temporal_host_loop.run(exe, tmp_path, cam, prm, clamp, False, (records, halves, history, history_halves, history_length, motion))
     return run
 
 
@@ -387,7 +365,12 @@ def test_the_new_entry_points_are_guarded_and_bound():
     handle = open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_api_handle.h")).read()
     assert re.search(r"struct RecordStage \{\s*DevBuf buf\[16\];", handle)
     body = src[src.index("int rr_accumulate_clamped_records("):]
-    assert re.search(r"const StageArg args\[10\]", body[:body.index("RR_GUARD_END")])
+    body = re.sub(r"\s+", " ", body[:body.index("RR_GUARD_END")])
+    assert "accumulate_call(" in body and ("AccumulateIo{records, halves, nullptr, nullptr, history, history_halves, nullptr, nullptr, history_length, motion, out, "
+                                           "halves_out, nullptr, nullptr, length_out, rgba8_out}") in body      # ten arrays: the six diffuse rows are left out
+    call = src[src.index("static int accumulate_call("):]
+    call = call[:call.index("\n}\n")]
+    assert re.search(r"StageArg args\[ACC_ROWS\]", call) and "staged_host_call(s->record_stage.buf, args," in call and "enum { ACC_ROWS = 16 }" in src
     # rr_history_clamp.h is plain host logic over rr_temporal.h, which keeps its own include list; the Makefile and LIB_SOURCES know it
     csrc = os.path.join(ROOT, "rustray_amd", "csrc")
     assert re.findall(r'#include\s+(\S+)', open(os.path.join(csrc, "rr_history_clamp.h")).read()) == ['"rr_temporal.h"']

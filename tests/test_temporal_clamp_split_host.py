@@ -7,14 +7,13 @@ import ctypes as C
 import inspect
 import os
 import re
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from rustray_amd import capi
 from rustray_amd.temporal import HistoryClampParams, accumulate_clamped_records, accumulate_split_records, clamp_boxes
+from tests import temporal_host_loop
 from tests.denoise_cases import F, same_bits
 from tests.helpers import ROOT, host_api_source
 from tests.temporal_cases import frame_params
@@ -31,35 +30,10 @@ def _yardstick(*a, **kw):
 
 @pytest.fixture(scope="module")
 def host_loop(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("temporal_clamp_split") / "temporal_clamp_split_test")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-o", exe, os.path.join(ROOT, "tests", "native", "temporal_clamp_split_test.cpp")]
-    subprocess.check_call(cmd)
+    exe = temporal_host_loop.build(tmp_path_factory)
 
     def run(tmp_path, cam, prm, clamp, args):
-        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        c = cam.c_struct()
-        W, H = int(c.width), int(c.height)
-        records, halves, history, motion = args[0], args[1], args[4], args[9]
-        with open(src, "wb") as fh:
-            fh.write(struct.pack("<6I", W, H, halves is not None, history is not None, motion is not None, clamp.radius))
-            fh.write(np.array(c.projection_inverse[:], F).tobytes() + np.array(c.view_inverse[:], F).tobytes())
-            fh.write(np.asarray(prm.prev_world_to_clip, F).T.reshape(16).tobytes() + np.asarray(prm.prev_eye, F).tobytes())
-            fh.write(struct.pack("<5f", prm.max_history, prm.normal_min, prm.sigma_depth, prm.snap, clamp.sigma_scale))
-            for a in args:
-                if a is not None:
-                    fh.write(np.ascontiguousarray(a, F).tobytes())
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "temporal clamp split test OK" in out.stdout, out.stdout + out.stderr
-        raw = np.fromfile(dst, F)
-        n = W * H
-        hv = halves is not None
-        at = np.cumsum([0, 8 * n, n, 16 * n if hv else 0, 3 * n, 6 * n if hv else 0, 3 * n, 3 * n, 3 * n, 3 * n])
-        assert raw.size == at[-1]
-        part = [raw[a:b] for a, b in zip(at[:-1], at[1:])]
-        return dict(records=part[0].reshape(n, 8), length=part[1], halves=part[2].reshape(n, 2, 8) if hv else None, diffuse=part[3].reshape(n, 3),
-                    diffuse_halves=part[4].reshape(n, 2, 3) if hv else None, lo=part[5].reshape(n, 3), hi=part[6].reshape(n, 3), dlo=part[7].reshape(n, 3),
-                    dhi=part[8].reshape(n, 3))
+        return temporal_host_loop.run(exe, tmp_path, cam, prm, clamp, True, tuple(args))
     return run
 
 
@@ -405,8 +379,14 @@ def test_the_new_entry_points_are_guarded_and_bound():
     assert len(re.findall(r"^typedef struct rr_history_clamp_params", header, re.M)) == 1 and "clamped_split" not in "".join(re.findall(r"typedef struct (\w+)", header))
     handle = open(os.path.join(ROOT, "rustray_amd", "csrc", "rr_api_handle.h")).read()
     assert re.search(r"struct RecordStage \{\s*DevBuf buf\[16\];", handle)
-    body = src[src.index("int rr_accumulate_clamped_split_records("):]
-    assert re.search(r"const StageArg args\[16\]", body[:body.index("RR_GUARD_END")])
+    for entry in ("int rr_accumulate_clamped_split_records(", "int rr_accumulate_split_records("):
+        body = src[src.index(entry):]
+        body = re.sub(r"\s+", " ", body[:body.index("RR_GUARD_END")])
+        assert "accumulate_call(" in body and ("AccumulateIo{records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, "
+                                               "history_length, motion, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8_out}") in body
+    call = src[src.index("static int accumulate_call("):]
+    call = call[:call.index("\n}\n")]
+    assert re.search(r"StageArg args\[ACC_ROWS\]", call) and "staged_host_call(s->record_stage.buf, args," in call and "enum { ACC_ROWS = 16 }" in src
     # rr_history_clamp.h stays plain host logic over rr_temporal.h and has the diffuse side next to history_clamp
     csrc = os.path.join(ROOT, "rustray_amd", "csrc")
     clamp_h = open(os.path.join(csrc, "rr_history_clamp.h")).read()

@@ -4,14 +4,13 @@ own properties (a static camera, the incremental mean, a disocclusion); and what
 import ctypes as C
 import os
 import re
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from rustray_amd import capi, temporal
 from rustray_amd.temporal import AccumulateParams, accumulate_records
+from tests import temporal_host_loop
 from tests.denoise_cases import F, same_bits
 from tests.helpers import ROOT, host_api_source
 from tests.temporal_cases import boundary_frames, frame_params, static_frames, temporal_frame
@@ -21,29 +20,11 @@ NEW = ("rr_accumulate_default_params", "rr_accumulate_records_device", "rr_accum
 
 @pytest.fixture(scope="module")
 def host_loop(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("temporal") / "temporal_test")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-o", exe, os.path.join(ROOT, "tests", "native", "temporal_test.cpp")]
-    subprocess.check_call(cmd)
+    exe = temporal_host_loop.build(tmp_path_factory)
 
     def run(tmp_path, cam, prm, records, halves, history, history_halves, history_length, motion):
-        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        c = cam.c_struct()
-        W, H = int(c.width), int(c.height)
-        with open(src, "wb") as fh:
-            fh.write(struct.pack("<5I", W, H, halves is not None, history is not None, motion is not None))
-            fh.write(np.array(c.projection_inverse[:], F).tobytes() + np.array(c.view_inverse[:], F).tobytes())
-            fh.write(np.asarray(prm.prev_world_to_clip, F).T.reshape(16).tobytes() + np.asarray(prm.prev_eye, F).tobytes())
-            fh.write(struct.pack("<4f", prm.max_history, prm.normal_min, prm.sigma_depth, prm.snap))
-            for a in (records, halves, history, history_halves if halves is not None else None, history_length, motion):
-                if a is not None:
-                    fh.write(np.ascontiguousarray(a, F).tobytes())
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "temporal test OK" in out.stdout, out.stdout + out.stderr
-        raw = np.fromfile(dst, F)
-        n = W * H
-        assert raw.size == (9 + (16 if halves is not None else 0)) * n
-        return dict(records=raw[:8 * n].reshape(n, 8), length=raw[8 * n:9 * n], halves=raw[9 * n:].reshape(n, 2, 8) if halves is not None else None)
+        return temporal_host_loop.run(exe, tmp_path, cam, prm, None, False,
+                                      (records, halves, history, history_halves if halves is not None else None, history_length, motion))
     return run
 
 

@@ -5,14 +5,13 @@ colour); a static view; and what the entry points refuse before they touch a dev
 import ctypes as C
 import os
 import re
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from rustray_amd import capi
 from rustray_amd.temporal import accumulate_records, accumulate_split_records
+from tests import temporal_host_loop
 from tests.denoise_cases import F, same_bits
 from tests.helpers import ROOT, host_api_source
 from tests.temporal_cases import frame_params
@@ -25,33 +24,11 @@ KEYS = ("records", "length", "halves", "diffuse", "diffuse_halves")
 
 @pytest.fixture(scope="module")
 def host_loop(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("temporal_split") / "temporal_split_test")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-o", exe, os.path.join(ROOT, "tests", "native", "temporal_split_test.cpp")]
-    subprocess.check_call(cmd)
+    exe = temporal_host_loop.build(tmp_path_factory)
 
     def run(tmp_path, cam, prm, records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, history_length, motion):
-        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        c = cam.c_struct()
-        W, H = int(c.width), int(c.height)
-        with open(src, "wb") as fh:
-            fh.write(struct.pack("<5I", W, H, halves is not None, history is not None, motion is not None))
-            fh.write(np.array(c.projection_inverse[:], F).tobytes() + np.array(c.view_inverse[:], F).tobytes())
-            fh.write(np.asarray(prm.prev_world_to_clip, F).T.reshape(16).tobytes() + np.asarray(prm.prev_eye, F).tobytes())
-            fh.write(struct.pack("<4f", prm.max_history, prm.normal_min, prm.sigma_depth, prm.snap))
-            for a in (records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves, history_length, motion):
-                if a is not None:
-                    fh.write(np.ascontiguousarray(a, F).tobytes())
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "temporal split test OK" in out.stdout, out.stdout + out.stderr
-        raw = np.fromfile(dst, F)
-        n = W * H
-        hv = halves is not None
-        assert raw.size == (12 + (22 if hv else 0)) * n
-        at = np.cumsum([0, 8 * n, n, 16 * n if hv else 0, 3 * n, 6 * n if hv else 0])
-        part = [raw[a:b] for a, b in zip(at[:-1], at[1:])]
-        return dict(records=part[0].reshape(n, 8), length=part[1], halves=part[2].reshape(n, 2, 8) if hv else None, diffuse=part[3].reshape(n, 3),
-                    diffuse_halves=part[4].reshape(n, 2, 3) if hv else None)
+        return temporal_host_loop.run(exe, tmp_path, cam, prm, None, True, (records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse,
+                                                                            history_diffuse_halves, history_length, motion))
     return run
 
 
