@@ -26,6 +26,14 @@ extern "C" int rh_camera(float fov, const float* eye, const float* up, const flo
     return 0;
 }
 
+extern "C" int rh_camera_world_to_clip(float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, uint32_t w, uint32_t h,
+                                       float* world_to_clip16, float* eye3) {
+    Camera c = make_camera(fov, eye, up, dir, cnear, cfar);
+    c.init(w, h);
+    c.world_to_clip(world_to_clip16, eye3);
+    return 0;
+}
+
 static RaytracingConfig from_c(const rr_config* c) {
     RaytracingConfig r;
     r.monte_carlo = c->monte_carlo != 0; r.samples = c->samples; r.focal_length = c->focal_length; r.aperture_size = c->aperture_size;

@@ -37,11 +37,14 @@ def _cam_args(cam: Camera):
             C.c_float(cam.clipping_near), C.c_float(cam.clipping_far))
 
 
-@pytest.mark.parametrize("state", [
+CAMERAS = [
     dict(fov=math.radians(90.0), eye_pos=[0, 0, 0], up=[0, 1, 0], dir=[0, 0, -1], clipping_near=0.001, clipping_far=1000.0),
     dict(fov=math.radians(47.5), eye_pos=[1.5, 2.25, 7.0], up=[0, 1, 0], dir=[-0.3, -0.2, -1.0], clipping_near=0.1, clipping_far=100.0),
     dict(fov=math.radians(70.0), eye_pos=[-4.0, 0.5, -2.0], up=[0.1, 1, 0], dir=[1.0, 0.1, 0.4], clipping_near=0.05, clipping_far=500.0),
-])
+]
+
+
+@pytest.mark.parametrize("state", CAMERAS)
 def test_camera_matrices_equal_the_python_mirror(shim, state):
     """Camera::init / init_matrices (reference src/camera.rs:69-90): both host mirrors hand the library the same bits."""
     st = dict(state, width=1280, height=720)
@@ -55,6 +58,30 @@ def test_camera_matrices_equal_the_python_mirror(shim, state):
     assert list(pi) == list(ref.projection_inverse) and list(vi) == list(ref.view_inverse)
     assert bool(isdef.value) == cam.is_default_cam()
     assert bool(inside.value) == cam.points_in_frustum(np.asarray([pt])) is True
+
+
+@pytest.mark.parametrize("size", [(1280, 720), (37, 29)])
+@pytest.mark.parametrize("state", CAMERAS)
+def test_world_to_clip_equals_previous_view(shim, state, size):
+    """Camera::world_to_clip, what the C++ host hands the next frame as prev_world_to_clip and prev_eye, against temporal.previous_view of
+    the Python mirror: both form projection x view in double from the same doubles and round once, so every word is equal.  (A row of the
+    projection has at most two non-zero entries and one of them meets a 0 or a 1 of the view: the order of a row's sum cannot matter.)
+    Against the definition: a point ahead of the eye lands in the middle of the frame with clip.w its distance ahead."""
+    from rustray_amd.temporal import previous_view
+    st = dict(state, width=size[0], height=size[1])
+    st["fov"] = float(np.float32(st["fov"]))
+    cam = Camera.from_state(st)
+    shim.rh_camera_world_to_clip.argtypes = [C.c_float, C.c_float * 3, C.c_float * 3, C.c_float * 3, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    m, eye = np.zeros(16, np.float32), np.zeros(3, np.float32)
+    assert shim.rh_camera_world_to_clip(*_cam_args(cam), size[0], size[1], m.ctypes.data, eye.ctypes.data) == 0
+    want_m, want_eye = previous_view(cam)
+    got = m.reshape(4, 4).T                                   # column-major -> as written on paper
+    assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(want_m).view(np.uint32)), np.abs(got - want_m).max()
+    assert np.array_equal(eye.view(np.uint32), want_eye.view(np.uint32))
+    d = np.asarray(cam.dir, np.float32).astype(np.float64)
+    p = np.asarray(cam.eye_pos, np.float32).astype(np.float64) + 3.0 * d / np.linalg.norm(d)
+    clip = got.astype(np.float64) @ np.append(p, 1.0)
+    assert abs(clip[3] - 3.0) < 1e-5 and abs(clip[0]) < 1e-5 and abs(clip[1]) < 1e-5
 
 
 def test_config_apply_takes_over_only_non_default_fields(shim):
