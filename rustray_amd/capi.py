@@ -59,7 +59,7 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_probe.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_schedule_log.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_probe.h", "rr_api_schedule_probe.h",
                "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_history_clamp.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
@@ -1130,6 +1130,22 @@ class DeviceScene:
         lib().rr_scene_overlap_stages.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _check(lib().rr_scene_overlap_stages(self._h, C.byref(n)))
         return n.value
+
+    def schedule_record(self, on: bool = True):
+        """rr_test_schedule_record (rr_api_schedule_probe.h, a test entry point outside include/rustray_hip.h): empty the handle's schedule log and
+        record what every frame call enqueues from now on (False: stop)."""
+        lib().rr_test_schedule_record.argtypes = [C.c_void_p, C.c_int]
+        _check(lib().rr_test_schedule_record(self._h, 1 if on else 0))
+
+    def schedule_log(self) -> str:
+        """rr_test_schedule_read: the log as text, one operation per line in host order (tests/launch_order.py parses and checks it)."""
+        L = lib()
+        L.rr_test_schedule_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        need = C.c_uint64(0)
+        _check(L.rr_test_schedule_read(self._h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        _check(L.rr_test_schedule_read(self._h, buf, need.value, C.byref(need)))
+        return buf.value.decode()
 
     def stats(self) -> dict:
         st = rr_frame_stats()

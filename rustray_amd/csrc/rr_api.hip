@@ -44,6 +44,7 @@
 
 #include "rr_api_base.h"     // errors, the no-throw guard, the test fault hook (and rr_scene_build.h behind it), DevBuf
 #include "rr_sample_table.h" // the reference's sub-sample table; regions of a frame (no HIP call)
+#include "rr_schedule_log.h" // the schedule recorder of a frame (off by default): the wrappers of its event and stream calls
 #include "rr_api_handle.h"   // rr_scene in its parts, one per layer below
 #include "rr_api_scene.h"    // scene creation, the view, the top level and its reach, in-place and structural edits
 #include "rr_api_frame.h"    // the frame driver: level walk, level 1 in stages, stats, tuning
@@ -61,3 +62,4 @@
 #include "rr_api_albedo_pixels.h" // rr_albedo_pixels: the frame's albedo averaged over its sub-samples, the albedo guide that is right at an edge pixel
 #include "rr_api_pixel_split.h" // rr_render_pixel_split: the frame's records and, as a sum of its own, the direct diffuse light of the primary hits
 #include "rr_api_probe.h"    // device arithmetic probe, developer counters
+#include "rr_api_schedule_probe.h" // test entry points: switch the schedule recorder on, read its log back

@@ -43,7 +43,8 @@ static int guard_fail(const char* fn) noexcept {
 // update_transforms.upload_tlas (after the top level's rebuild, before its upload), update_materials.device (between the materials'
 // and the items' copy), tlas_reach.upload (a frame's top-level rebuild, before its upload), update_lights.device (after the light
 // records' copy), update_item_flags.device (after the items' copy), add_textures.device (after the grown pool's upload, before it
-// replaces the old one), add_meshes.device and set_items.device (after the new state's upload, before the commit).  Not armed (always, outside the tests): one
+// replaces the old one), add_meshes.device and set_items.device (after the new state's upload, before the commit), level1_stages.stage (once per stage of the staged
+// level 1, in front of the stage's launches: enqueue_level1_stages).  Not armed (always, outside the tests): one
 // acquire load per crossing (it pairs with the release store of rr_test_fault: a thread that sees the kind sees the point's name), and
 // the points sit outside every per-ray and per-triangle loop.
 static std::atomic<int> g_fault_kind{0};

@@ -3,7 +3,8 @@
 //         launch_trace_closest; FrameEnd, FrameIo and its makers frame_io and pixels_io, frame_end_plan (what an ending implies),
 //         ALL_PLANES; make_frame, upload_shade_const, reset_accumulators, queue_budget, grow_ray_queues; CounterPool, FrameRun and its maker
 //         make_frame_run; launch_shade and launch_shadow (THE launch sites of k_shade and k_trace_shadow), read_back_level_size;
-//         join_shadow, join_shadow_for, drain_shadow (the staged level 1's last shadow launches stay pending while the frame's stream goes on);
+//         join_shadow, join_shadow_for, FrameStreamsIdle (the staged level 1's last shadow launches stay pending while the frame's stream goes on;
+//         a frame that ends early, by code or by exception, leaves its three streams idle);
 //         run_level (with level 1 in stages on three streams; with FrameEnd::ALBEDO level 1 ends in k_albedo_level1: rr_api_albedo_pixels.h;
 //         with FrameEnd::RECORD_SPLIT level 1 runs the SPLIT builds of the two kernels, serially: rr_api_pixel_split.h); pick_build;
 //         take_stream, begin_frame_stats;
@@ -41,9 +42,9 @@ static hipEvent_t take_event(rr_scene* s) {
 struct ScopedTimer {
     rr_scene* s; hipStream_t st; TimerKernel kernel; bool level1; hipEvent_t a = nullptr, b = nullptr;
     ScopedTimer(rr_scene* s_, hipStream_t st_, TimerKernel kernel_, bool level1_) : s(s_), st(st_), kernel(kernel_), level1(level1_) {
-        if (s->timing.profiling) { a = take_event(s); b = take_event(s); (void)hipEventRecord(a, st); }
+        if (s->timing.profiling) { a = take_event(s); b = take_event(s); (void)sched_record(s->sched, a, st, "timer"); }
     }
-    ~ScopedTimer() { if (s->timing.profiling) { (void)hipEventRecord(b, st); s->timing.timed.push_back(TimedLaunch{a, b, kernel, level1}); } }
+    ~ScopedTimer() { if (s->timing.profiling) { (void)sched_record(s->sched, b, st, "timer"); s->timing.timed.push_back(TimedLaunch{a, b, kernel, level1}); } }
 };
 
 // the rr_frame_stats fields of each TimerKernel: every launch, and the launches of its level-1 build (binning: time only)
@@ -60,7 +61,7 @@ static const struct {
 static void resolve_timers(rr_scene* s) {
     for (auto& t : s->timing.timed) {
         float ms = 0.0f;
-        if (hipEventSynchronize(t.b) == hipSuccess && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
+        if (sched_sync_event(s->sched, t.b, "timer") == hipSuccess && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
             const auto& f = k_timer_fields[t.kernel];
             s->timing.stats.*f.ms += ms;
             if (f.launches) s->timing.stats.*f.launches += 1;
@@ -90,11 +91,11 @@ static int stage_outputs(rr_scene* s, const rr_frame& host, size_t np, bool zero
     return RR_OK;
 }
 // dev -> host for every buffer both have (np pixels each), on stream st; returns when they are on the host
-static int copy_outputs(const rr_frame& host, const rr_frame& dev, size_t np, hipStream_t st) {
+static int copy_outputs(ScheduleLog& log, const rr_frame& host, const rr_frame& dev, size_t np, hipStream_t st) {
     for (int k = 0; k < 4; k++)
         if (out_buffer(host, k) && out_buffer(dev, k))
-            HIP_TRY(hipMemcpyAsync(out_buffer(host, k), out_buffer(dev, k), np * OUT_ELEM[k], hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(sched_copy(log, out_buffer(host, k), out_buffer(dev, k), np * OUT_ELEM[k], hipMemcpyDeviceToHost, st, "frame -> host"));
+    HIP_TRY(sched_sync_stream(log, st, "copy_outputs"));
     return RR_OK;
 }
 
@@ -119,6 +120,19 @@ static int launch_trace_closest(rr_scene* s, bool primary, DRayQueue q, uint32_t
     if (np == 0 || p0 >= level_packets || wg_per_cu == 0) return fail(RR_ERR_DEVICE, "internal: closest-hit launch of packets %u + %u of %llu", p0, np, (unsigned long long)level_packets);
     const uint64_t packets = std::min<uint64_t>(np, level_packets - p0); // a hit record is written only for a ray below n, whatever the range
     const int grid = (int)std::min<uint64_t>((packets * RR_WAVE + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * wg_per_cu);
+    if (s->sched.on) {
+        // k_trace_closest: a hit record for every ray of its packets that the level has; the <true> build derives the rays (frame constants, sample
+        // offsets, slot centres), stores the level's size plainly and counts its rays; the <false> build reads the size and the ray records
+        const uint64_t i0 = (uint64_t)p0 * RR_WAVE, i1 = std::min<uint64_t>(n, i0 + packets * RR_WAVE);
+        if (primary)
+            sched_launch(s->sched, st, "k_trace_closest<true>", {sa_r(kc, sizeof(DShadeConst), "shade_const"), sa_r(pr.sample_tr, s->frame.sample_tr.bytes, "sample_tr"),
+                                                               sa_r(s->frame.slot_c.p, s->frame.slot_c.bytes, "slot_c"), sa_r(s->frame.pixel_c.p, s->frame.pixel_c.bytes, "pixel_c"),
+                                                               sa_w(count, 4, "level count"), sa_w(q.hit + i0, (i1 - i0) * 16, "hit records"), sa_a(head, 4, "closest head"),
+                                                               sa_a(counters, RR_CNT_WORDS * 8, "counters")});
+        else
+            sched_launch(s->sched, st, "k_trace_closest<false>", {sa_r(count, 4, "level count"), sa_r(q.r0, n * 16, "ray r0"), sa_r(q.r1, n * 16, "ray r1"), sa_r(q.r2, n * 8, "ray r2"),
+                                                                sa_w(q.hit, n * 16, "hit records"), sa_a(head, 4, "closest head")});
+    }
     if (primary) {
         q.r0 = nullptr; q.r1 = nullptr; q.r2 = nullptr;
         hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(RR_BLOCK), 0, st, s->data.view, q, count, head, kc, pr, counters, p0, np);
@@ -137,7 +151,7 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
     if (memcmp(&s->frame.region_cached, &rg, sizeof rg) == 0 && s->frame.region_w == W && s->frame.region_h == H) return RR_OK;
     std::vector<uint32_t> order;
     fill_region(W, H, rg, &s->frame.h_region_xy, &order);
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(sched_sync_stream(s->sched, st, "update_region_map"));
     HIP_TRY(s->frame.region_xy.reserve(std::max<size_t>(s->frame.h_region_xy.size(), 1) * 4));
     HIP_TRY(s->frame.slot_c.reserve(std::max<size_t>(s->frame.h_region_xy.size(), 1) * 8));
     HIP_TRY(s->frame.trace_order.reserve(std::max<size_t>(order.size(), 1) * 4));
@@ -145,11 +159,11 @@ static int update_region_map(rr_scene* s, uint32_t W, uint32_t H, const rr_regio
         // slot_xy[j] = pixel of accumulator slot j; slot_out[j] = its index in the compact output order
         std::vector<uint32_t> slot_xy(order.size());
         for (size_t j = 0; j < order.size(); j++) slot_xy[j] = s->frame.h_region_xy[order[j]];
-        HIP_TRY(hipMemcpy(s->frame.region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(sched_copy_blocking(s->sched, s->frame.region_xy.p, slot_xy.data(), slot_xy.size() * 4, hipMemcpyHostToDevice, "region_xy"));
         std::vector<float> slot_c(slot_xy.size() * 2); // the pixel centres on the screen, as primary_ray adds the sample's offset to them
         primary_slot_centres(slot_xy.data(), slot_xy.size(), W, H, slot_c.data());
-        HIP_TRY(hipMemcpy(s->frame.slot_c.p, slot_c.data(), slot_c.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->frame.trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(sched_copy_blocking(s->sched, s->frame.slot_c.p, slot_c.data(), slot_c.size() * 4, hipMemcpyHostToDevice, "slot_c"));
+        HIP_TRY(sched_copy_blocking(s->sched, s->frame.trace_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, "trace_order"));
     }
     s->frame.region_cached = rg; s->frame.region_w = W; s->frame.region_h = H;
     return RR_OK;
@@ -235,19 +249,23 @@ static int fill_pixel_slots(rr_scene* s, uint32_t W, uint32_t H, const uint32_t*
     HIP_TRY(s->frame.pixel_xy.reserve((size_t)n * 4));
     HIP_TRY(s->frame.pixel_c.reserve((size_t)n * 8));
     HIP_TRY(s->frame.pixel_bad.reserve(4));
-    HIP_TRY(hipMemsetAsync(s->frame.pixel_bad.p, 0xff, 4, st));
+    HIP_TRY(sched_memset(s->sched, s->frame.pixel_bad.p, 0xff, 4, st, "pixel_bad"));
     const int grid = (int)std::min<uint64_t>((n + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
+    // (k_pixel_slots: entry j >> lg_parts read, slot j of both tables written, one atomicMin on the first bad index)
+    if (s->sched.on) sched_launch(s->sched, st, "k_pixel_slots", {sa_r(pixel_xy, (size_t)n_entries * 4, "pixel list"), sa_w(s->frame.pixel_xy.p, (size_t)n * 4, "pixel_xy"),
+                                                                  sa_w(s->frame.pixel_c.p, (size_t)n * 8, "pixel_c"), sa_a(s->frame.pixel_bad.p, 4, "pixel_bad")});
     hipLaunchKernelGGL(k_pixel_slots, dim3(grid), dim3(RR_BLOCK), 0, st, pixel_xy, n_entries, lg_parts, W, H, s->frame.pixel_xy.as<uint32_t>(), s->frame.pixel_c.as<float2>(),
                        s->frame.pixel_bad.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     if (trusted) return RR_OK;
     uint32_t* h = s->frame.h_count + HC_PIXEL_BAD;
-    HIP_TRY(hipMemcpyAsync(h, s->frame.pixel_bad.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(sched_copy(s->sched, h, s->frame.pixel_bad.p, 4, hipMemcpyDeviceToHost, st, "pixel_bad -> h_count"));
+    HIP_TRY(sched_sync_stream(s->sched, st, "fill_pixel_slots"));
+    sched_host_read(s->sched, h, 4, "h_count[HC_PIXEL_BAD]");
     const uint32_t bad = *h;
     if (bad == RR_PIXEL_LIST_OK) return RR_OK;
     uint32_t xy = 0; // (the stream is idle: the entry for the message comes with one more small copy)
-    HIP_TRY(hipMemcpy(&xy, s->frame.pixel_xy.as<uint32_t>() + ((size_t)bad << lg_parts), 4, hipMemcpyDeviceToHost));
+    HIP_TRY(sched_copy_blocking(s->sched, &xy, s->frame.pixel_xy.as<uint32_t>() + ((size_t)bad << lg_parts), 4, hipMemcpyDeviceToHost, "pixel_xy[bad]"));
     return fail(RR_ERR_INVALID_ARGUMENT, "pixel_xy[%u] = (%u, %u) lies outside the frame of %ux%u pixels", bad, xy & 0xffffu, xy >> 16, W, H);
 }
 
@@ -271,8 +289,8 @@ static int upload_shade_const(rr_scene* s, const DFrame& fr, const PrimaryFrame&
     DShadeConst hc;
     hc.sc = s->data.view; hc.fr = fr; hc.ps = ps;
     HIP_TRY(s->frame.shade_const.reserve(sizeof hc));
-    HIP_TRY(hipMemcpyAsync(s->frame.shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st)); // `hc` is a stack local
+    HIP_TRY(sched_copy(s->sched, s->frame.shade_const.p, &hc, sizeof hc, hipMemcpyHostToDevice, st, "shade_const"));
+    HIP_TRY(sched_sync_stream(s->sched, st, "upload_shade_const")); // `hc` is a stack local
     return RR_OK;
 }
 
@@ -298,10 +316,10 @@ static int upload_sample_table(rr_scene* s, const DFrame& fr, const uint16_t* sa
     try { s->frame.tr_table.assign(sample_xy, sample_xy + (size_t)samples * 2); tr.resize((size_t)samples * 2); }
     catch (const std::exception&) { return fail(RR_ERR_OUT_OF_MEMORY, "no host memory for the sample offsets"); }
     primary_sample_offsets(sample_xy, key, tr.data());
-    HIP_TRY(hipStreamSynchronize(st)); // an earlier frame on this stream may still read the buffer
+    HIP_TRY(sched_sync_stream(s->sched, st, "upload_sample_table")); // an earlier frame on this stream may still read the buffer
     HIP_TRY(s->frame.sample_tr.reserve((size_t)samples * 8));
-    HIP_TRY(hipMemcpyAsync(s->frame.sample_tr.p, tr.data(), (size_t)samples * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st)); // `tr` is a local
+    HIP_TRY(sched_copy(s->sched, s->frame.sample_tr.p, tr.data(), (size_t)samples * 8, hipMemcpyHostToDevice, st, "sample_tr"));
+    HIP_TRY(sched_sync_stream(s->sched, st, "upload_sample_table")); // `tr` is a local
     s->frame.tr_key = key; s->frame.tr_valid = true;
     return RR_OK;
 }
@@ -315,23 +333,24 @@ static int reset_accumulators(rr_scene* s, uint32_t npix, const FrameEndPlan& wa
     if (want.split) {
         if (resident || !diffuse) return fail(RR_ERR_DEVICE, "internal: a split frame on resident accumulators");
         HIP_TRY(s->frame.acc_diffuse.reserve((size_t)npix * 24));
-        HIP_TRY(hipMemsetAsync(s->frame.acc_diffuse.p, 0, (size_t)npix * 24, st));
+        HIP_TRY(sched_memset(s->sched, s->frame.acc_diffuse.p, 0, (size_t)npix * 24, st, "acc_diffuse"));
         *diffuse = s->frame.acc_diffuse.as<long long>();
     }
     if (resident) {
         if (resident->n != npix || !resident->rgb || !resident->normal || !resident->depth || !resident->object_id || !resident->flags)
             return fail(RR_ERR_DEVICE, "internal: resident accumulators of %llu slots for a pass of %u", resident->n, npix);
-        HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
+        HIP_TRY(sched_memset(s->sched, s->frame.counters.p, 0, RR_CNT_WORDS * 8, st, "counters"));
         *acc = *resident;
         return RR_OK;
     }
     // (flags, colour, normal, depth, id, counters: the order the memsets have always been enqueued in)
     DevBuf* const plane[5] = {&s->frame.acc_flags, &s->frame.acc_rgb, &s->frame.acc_normal, &s->frame.acc_depth, &s->frame.acc_id};
     const size_t bytes[5] = {4, 24, 24, 8, 4};
+    static const char* const plane_name[5] = {"acc_flags", "acc_rgb", "acc_normal", "acc_depth", "acc_id"};
     const int n_planes = want.aux ? 5 : 2;
     for (int k = 0; k < n_planes; k++) HIP_TRY(plane[k]->reserve((size_t)npix * bytes[k]));
-    for (int k = 0; k < n_planes; k++) HIP_TRY(hipMemsetAsync(plane[k]->p, 0, (size_t)npix * bytes[k], st));
-    HIP_TRY(hipMemsetAsync(s->frame.counters.p, 0, RR_CNT_WORDS * 8, st));
+    for (int k = 0; k < n_planes; k++) HIP_TRY(sched_memset(s->sched, plane[k]->p, 0, (size_t)npix * bytes[k], st, plane_name[k]));
+    HIP_TRY(sched_memset(s->sched, s->frame.counters.p, 0, RR_CNT_WORDS * 8, st, "counters"));
     *acc = DAccum{s->frame.acc_rgb.as<long long>(), want.normal ? s->frame.acc_normal.as<long long>() : nullptr, want.depth ? s->frame.acc_depth.as<long long>() : nullptr,
                   want.id ? s->frame.acc_id.as<uint32_t>() : nullptr, (unsigned long long)npix, s->frame.acc_flags.as<uint32_t>()};
     return RR_OK;
@@ -379,7 +398,7 @@ struct CounterPool {
     size_t pool_segment = 0; // 0 = s->frame.pool, k = s->frame.pool_more[k - 1]
     int start_batch() {
         pool = s->frame.pool.as<uint32_t>(); pool_segment = 0;
-        HIP_TRY(hipMemsetAsync(pool, 0, POOL_WORDS * 4, st));
+        HIP_TRY(sched_memset(s->sched, pool, 0, POOL_WORDS * 4, st, "counter pool"));
         next_word = 0;
         return RR_OK;
     }
@@ -392,7 +411,7 @@ struct CounterPool {
                 if (s->frame.pool_more.back().reserve(POOL_WORDS * 4) != hipSuccess) { s->frame.pool_more.pop_back(); return nullptr; }
             }
             pool = s->frame.pool_more[pool_segment++].as<uint32_t>();
-            if (hipMemsetAsync(pool, 0, POOL_WORDS * 4, st) != hipSuccess) return nullptr;
+            if (sched_memset(s->sched, pool, 0, POOL_WORDS * 4, st, "counter pool segment") != hipSuccess) return nullptr;
             next_word = 0;
         }
         uint32_t* p = pool + next_word; next_word += n; return p;
@@ -439,10 +458,10 @@ static FrameRun make_frame_run(rr_scene* s, hipStream_t st, const FramePlan& pla
 // buffers (join_shadow_for: `st` then waits for the earlier stage's shadow launch that read the buffer it writes, long over as a rule, and
 // the chunk's shade and shadow launches run beside the two as well), the staged path's entry (its fork of the third stream
 // and its first shade launch), start_batch of the next batch, the pass hook's resolve, and the frame's resolve and end event.
-// A frame that ends early is drained by drain_shadow instead.
+// A frame that ends early is drained by FrameStreamsIdle instead.
 static int join_shadow(FrameRun& f) {
     if (!f.shadow_pending) return RR_OK;
-    HIP_TRY(hipStreamWaitEvent(f.st, f.shadow_pending, 0)); // (stage_tail follows every shadow launch of the level: the one shadow_rest names too)
+    HIP_TRY(sched_wait(f.s->sched, f.st, f.shadow_pending, "stage_tail")); // (stage_tail follows every shadow launch of the level: the one shadow_rest names too)
     f.shadow_pending = nullptr; f.shadow_rest = nullptr;
     return RR_OK;
 }
@@ -453,19 +472,32 @@ static int join_shadow(FrameRun& f) {
 static int join_shadow_for(FrameRun& f, const ShadeChunk& g) {
     if (!f.shadow_pending || !chunk_clear_of_tail(g, f.shadow_tail)) return join_shadow(f);
     if (f.shadow_rest) {
-        HIP_TRY(hipStreamWaitEvent(f.st, f.shadow_rest, 0));
+        HIP_TRY(sched_wait(f.s->sched, f.st, f.shadow_rest, "shadow_rest"));
         f.shadow_rest = nullptr;
     }
     return RR_OK;
 }
-// ... and the way out of a frame that ends early (cancel flag, HIP error, counters_exhausted, arena too small), with launches pending or
-// after a join that failed: the second stream (which has waited for the third) and then `st` are idle when this returns, as
-// run_level1_stages leaves them
-static void drain_shadow(FrameRun& f) {
-    if (f.s->frame.overlap_stream) (void)hipStreamSynchronize(f.s->frame.overlap_stream);
-    f.shadow_pending = nullptr; f.shadow_rest = nullptr;
-    (void)hipStreamSynchronize(f.st);
-}
+// ... and THE way out of a frame that ends early -- an error code (cancel flag, HIP error, counters_exhausted, arena too small, a join that
+// failed) or an exception on its way to the ABI guard (CounterPool::take grows a std::vector inside the stage loop) -- with launches pending
+// on any of the three streams: armed at the top of render_region_locked, it waits for the third stream, the second and then `st` on every way
+// out but done(RR_OK).  FrameRun::shadow_pending is a local and is lost on unwinding; the streams are the handle's and are not.
+// (What is waited for is complete, valid launches: nothing is cancelled.  The log's own allocation must not throw out of a destructor.)
+struct FrameStreamsIdle {
+    rr_scene* s; hipStream_t st; bool armed = true;
+    FrameStreamsIdle(rr_scene* s_, hipStream_t st_) : s(s_), st(st_) {}
+    void drain() noexcept {
+        const hipStream_t order[3] = {s->frame.closest_stream, s->frame.overlap_stream, st};
+        for (int k = 0; k < 3; k++) {
+            if (k < 2 && !order[k]) continue; // (never created: no staged frame on this handle yet)
+            try { (void)sched_sync_stream(s->sched, order[k], "frame left early"); }
+            catch (...) { (void)hipStreamSynchronize(order[k]); }
+        }
+    }
+    int done(int rc) { if (rc != RR_OK) drain(); armed = false; return rc; }
+    ~FrameStreamsIdle() { if (armed) drain(); }
+    FrameStreamsIdle(const FrameStreamsIdle&) = delete;
+    FrameStreamsIdle& operator=(const FrameStreamsIdle&) = delete;
+};
 
 // Where the shadow rays of one shade chunk go: the queue and its validity words (the handle's, from `ray_offset` / `valid_offset` on: a
 // stage's buffer) and, from the batch's pool, the chunk's own append counters (on a 128-B line) and the shadow launch's head word.
@@ -506,6 +538,27 @@ static int launch_shade(FrameRun& f, bool level1, const DRayQueue& qin, const ui
     if (split && ((s->data.n_enabled_lights > 0 && !f.sq_s3) || q.SQ.s0 != f.SQ.s0))
         return fail(RR_ERR_DEVICE, "internal: split shade launch without its queue array, or in a stage buffer");
     ScopedTimer t(s, st, TK_SHADE, level1);
+    if (s->sched.on) {
+        // k_shade reads the hits [c0, c1) (and, below level 1, their ray records; on level 1 what primary_ray reads) and the slot -> pixel map; appends
+        // children ANYWHERE in [child_base, M) behind one atomic counter (declared whether or not this level spawns); writes the chunk's shadow rays --
+        // fixed slots: sq_cap per light and the validity words; dense: RR_SQ_SHARDS shards of segcap behind their append counters; adds to the
+        // colour, normal and depth planes, ORs the flags, STORES the object id plainly, counts its work
+        const uint32_t L = s->data.n_enabled_lights;
+        const size_t n_acc = (size_t)f.acc.n, sq_rays = (size_t)(g.fixed ? g.sq_cap * L : (L ? g.segcap * RR_SQ_SHARDS : 0ull));
+        const size_t room = f.plan.M - (size_t)(qout.r0 - s->frame.arena[0].as<float4>()); // rays from child_base to the arena's end
+        sched_launch(s->sched, st, level1 ? (split ? "k_shade<true, SPLIT>" : "k_shade<true>") : "k_shade<false>",
+                     {sa_r(s->frame.shade_const.p, sizeof(DShadeConst), "shade_const"), sa_r(f.slot_xy, n_acc * 4, "slot_xy"),
+                      sa_r(level1 ? f.pr.sample_tr : nullptr, s->frame.sample_tr.bytes, "sample_tr"), sa_r(level1 ? s->frame.slot_c.p : nullptr, s->frame.slot_c.bytes, "slot_c"),
+                      sa_r(level1 ? s->frame.pixel_c.p : nullptr, s->frame.pixel_c.bytes, "pixel_c"), sa_r(count, 4, "level count"), sa_r(qin.hit + c0, (size_t)(c1 - c0) * 16, "hit records"),
+                      sa_r(level1 ? nullptr : qin.r0 + c0, (size_t)(c1 - c0) * 16, "ray r0"), sa_r(level1 ? nullptr : qin.r1 + c0, (size_t)(c1 - c0) * 16, "ray r1"),
+                      sa_r(level1 ? nullptr : qin.r2 + c0, (size_t)(c1 - c0) * 8, "ray r2"), sa_w(qout.r0, room * 16, "child r0"), sa_w(qout.r1, room * 16, "child r1"),
+                      sa_w(qout.r2, room * 8, "child r2"), sa_a(child_count, 4, "child_count"), sa_w(q.SQ.s0, sq_rays * 16, "shadow s0"), sa_w(q.SQ.s1, sq_rays * 16, "shadow s1"),
+                      sa_w(q.SQ.s2, sq_rays * 16, "shadow s2"), sa_w(split ? f.sq_s3 : nullptr, sq_rays * 16, "shadow s3"),
+                      sa_w(g.fixed ? q.valid : nullptr, (size_t)g.sq_packets * 8, "sq_valid"), sa_a(g.fixed || !L ? nullptr : q.counts, RR_SQ_SHARDS * RR_SQ_STRIDE * 4, "shard counts"),
+                      sa_a(f.acc.rgb, n_acc * 24, "acc_rgb"), sa_a(f.acc.normal, n_acc * 24, "acc_normal"), sa_a(f.acc.depth, n_acc * 8, "acc_depth"),
+                      sa_w(f.acc.object_id, n_acc * 4, "acc_id"), sa_a(f.acc.flags, n_acc * 4, "acc_flags"), sa_a(split ? f.diffuse : nullptr, n_acc * 24, "acc_diffuse"),
+                      sa_a(s->frame.counters.p, RR_CNT_WORDS * 8, "counters")});
+    }
     // ONE launch for every build: `extra` is empty, or the two pointers only the SPLIT build takes behind the arguments all builds share
     const auto launch = [&](auto... extra) {
         constexpr bool SP = sizeof...(extra) != 0;
@@ -526,6 +579,17 @@ static int launch_shadow(FrameRun& f, const ShadeChunk& g, const ChunkShadow& q,
         g.sq_packets > 0xffffffffull || g.shadow_wg == 0 || max_wg == 0)
         return fail(RR_ERR_DEVICE, "internal: shadow launch of %llu workgroups with a NULL or out-of-range argument", (unsigned long long)g.shadow_wg);
     ScopedTimer t(f.s, st, TK_SHADOW, g.fixed);
+    if (f.s->sched.on) {
+        // k_trace_shadow reads the chunk's rays as far as launch_shade declares them written (fixed: by the validity words; dense: by the shard counts),
+        // deals its packets behind its own head word, adds to the colour planes and ORs the flags; no other plane, no counter
+        const uint32_t L = f.s->data.n_enabled_lights;
+        const size_t n_acc = (size_t)f.acc.n, sq_rays = (size_t)(g.fixed ? g.sq_cap * L : g.segcap * RR_SQ_SHARDS);
+        sched_launch(f.s->sched, st, g.fixed ? "k_trace_shadow<true>" : (split ? "k_trace_shadow<false, SPLIT>" : "k_trace_shadow<false>"),
+                     {sa_r(q.SQ.s0, sq_rays * 16, "shadow s0"), sa_r(q.SQ.s1, sq_rays * 16, "shadow s1"), sa_r(q.SQ.s2, sq_rays * 16, "shadow s2"),
+                      sa_r(split ? f.sq_s3 : nullptr, sq_rays * 16, "shadow s3"), sa_r(g.fixed ? q.valid : nullptr, (size_t)g.sq_packets * 8, "sq_valid"),
+                      sa_r(g.fixed ? nullptr : q.counts, RR_SQ_SHARDS * RR_SQ_STRIDE * 4, "shard counts"), sa_a(q.head, 4, "shadow head"), sa_a(f.acc.rgb, n_acc * 24, "acc_rgb"),
+                      sa_a(f.acc.flags, n_acc * 4, "acc_flags"), sa_a(split ? f.diffuse : nullptr, n_acc * 24, "acc_diffuse")});
+    }
     const auto launch = [&](auto... extra) { // (as in launch_shade: empty, or the SPLIT builds' two pointers)
         constexpr bool SP = sizeof...(extra) != 0;
         hipLaunchKernelGGL((pick_build<SP>(g.fixed ? k_trace_shadow<true, SP, decltype(extra)...> : k_trace_shadow<false, SP, decltype(extra)...>,
@@ -540,8 +604,8 @@ static int launch_shadow(FrameRun& f, const ShadeChunk& g, const ChunkShadow& q,
 }
 // The size of the next level, final once the last shade launch of a slice has run, on its way to the host (run_level waits for count_ready)
 static int read_back_level_size(FrameRun& f, const uint32_t* child_count) {
-    HIP_TRY(hipMemcpyAsync(f.s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, f.st));
-    HIP_TRY(hipEventRecord(f.s->frame.count_ready, f.st));
+    HIP_TRY(sched_copy(f.s->sched, f.s->frame.h_count + HC_LEVEL, child_count, 4, hipMemcpyDeviceToHost, f.st, "child_count -> h_count"));
+    HIP_TRY(sched_record(f.s->sched, f.s->frame.count_ready, f.st, "count_ready"));
     return RR_OK;
 }
 
@@ -557,10 +621,19 @@ static int bin_level(FrameRun& f, uint64_t child_base, uint64_t m, uint64_t* lev
     uint32_t* hist = f.pool.take(RR_BIN_COUNT);
     if (!bounds || !hist) return RR_OK;
     const int init[8] = {0x7f7fffff, 0x7f7fffff, 0x7f7fffff, (int)0x80800000, (int)0x80800000, (int)0x80800000, 0, 0}; // ordered(+FLT_MAX) x3, ordered(-FLT_MAX) x3
-    HIP_TRY(hipMemcpyAsync(bounds, init, sizeof init, hipMemcpyHostToDevice, f.st));
+    HIP_TRY(sched_copy(s->sched, bounds, init, sizeof init, hipMemcpyHostToDevice, f.st, "bin bounds"));
     const DRayQueue qsrc = f.queue_at(child_base), qdst = f.queue_at(child_base + m);
     const int g = (int)std::min<uint64_t>((m + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8);
     ScopedTimer t(s, f.st, TK_BINNING, false);
+    if (s->sched.on) { // (atomicMin / atomicMax on the bounds: A; the prefix sum rewrites the histogram in place: W)
+        sched_launch(s->sched, f.st, "k_bin_bounds", {sa_r(qsrc.r0, m * 16, "ray r0"), sa_a(bounds, 24, "bin bounds")});
+        sched_launch(s->sched, f.st, "k_bin_count", {sa_r(qsrc.r0, m * 16, "ray r0"), sa_r(qsrc.r1, m * 16, "ray r1"), sa_r(bounds, 24, "bin bounds"), sa_w(qsrc.hit, m * 16, "bin keys"),
+                                                    sa_a(hist, RR_BIN_COUNT * 4, "bin histogram")});
+        sched_launch(s->sched, f.st, "k_bin_prefix", {sa_w(hist, RR_BIN_COUNT * 4, "bin histogram")});
+        sched_launch(s->sched, f.st, "k_bin_scatter", {sa_r(qsrc.hit, m * 16, "bin keys"), sa_r(qsrc.r0, m * 16, "ray r0"), sa_r(qsrc.r1, m * 16, "ray r1"), sa_r(qsrc.r2, m * 8, "ray r2"),
+                                                      sa_w(qdst.r0, m * 16, "sorted r0"), sa_w(qdst.r1, m * 16, "sorted r1"), sa_w(qdst.r2, m * 8, "sorted r2"),
+                                                      sa_a(hist, RR_BIN_COUNT * 4, "bin histogram")});
+    }
     hipLaunchKernelGGL(k_bin_bounds, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds);
     hipLaunchKernelGGL(k_bin_count, dim3(g), dim3(RR_BLOCK), 0, f.st, qsrc, (uint32_t)m, bounds, hist);
     hipLaunchKernelGGL(k_bin_prefix, dim3(1), dim3(1024), 0, f.st, hist);
@@ -601,7 +674,7 @@ static int ensure_overlap_stream(rr_scene* s) {
     return RR_OK;
 }
 
-// enqueues every stage; on any error the caller (run_level1_stages) drains all three streams
+// enqueues every stage; on any error or exception the frame's FrameStreamsIdle waits for all three streams
 static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, uint32_t* count, uint64_t s0, uint64_t s1,
                                  const DRayQueue& qout, uint32_t* child_count, bool spawns, bool trace_closest) {
     rr_scene* s = f.s;
@@ -615,11 +688,12 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         f.pool.align_line();
         closest_heads = f.pool.take(sp.n_stages * RR_SQ_STRIDE);
         if (!closest_heads) return counters_exhausted();
-        HIP_TRY(hipEventRecord(s->frame.stage_fork, st));
-        HIP_TRY(hipStreamWaitEvent(st3, s->frame.stage_fork, 0));
+        HIP_TRY(sched_record(s->sched, s->frame.stage_fork, st, "stage_fork"));
+        HIP_TRY(sched_wait(s->sched, st3, s->frame.stage_fork, "stage_fork"));
     }
     for (uint32_t k = 0; k < sp.n_stages; k++) {
         if (f.cancel && *f.cancel) return fail(RR_ERR_CANCELLED, "cancelled");
+        RR_FAULT_POINT("level1_stages.stage"); // (tests: an exception between two stages, with launches of the earlier ones on all three streams)
         const uint64_t c0 = s0 + sp.begin_of(k), c1 = std::min<uint64_t>(c0 + sp.stage, s1);
         const uint32_t b = sp.buffer_of(k);
         const bool first = k == 0, last = k + 1 == sp.n_stages;
@@ -631,28 +705,33 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
         const uint64_t shadow_wg = (uint64_t)s->n_cus * RR_L1_SHADOW_WG;
         if (trace_closest) { // the host is stages ahead of the device: launch k is enqueued long before launch k - 1 ends
             {
+                // Every launch of k_trace_closest<true> STORES the level's size (*q_count = n, a plain store of the same value).  Launch 0 stores it where
+                // the shade launches read it; launch k > 0 runs beside shade launches that read that word, ordered against them by nothing, so it
+                // is handed the word behind its own head word instead (zeroed with the pool, read by nobody): no store beside a load of one word.
+                static_assert(RR_SQ_STRIDE >= 2, "a closest-hit launch's head word and its copy of the level's size share the launch's stride");
+                uint32_t* const count_k = first ? count : closest_heads + (size_t)k * RR_SQ_STRIDE + 1;
                 ScopedTimer t(s, st3, TK_CLOSEST, true);
-                RR_TRY(launch_trace_closest(s, true, qin, count, closest_heads + (size_t)k * RR_SQ_STRIDE, f.pr.n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st3,
+                RR_TRY(launch_trace_closest(s, true, qin, count_k, closest_heads + (size_t)k * RR_SQ_STRIDE, f.pr.n, s->frame.shade_const.as<DShadeConst>(), f.pr, counters, st3,
                                             (uint32_t)(c0 / RR_WAVE), (uint32_t)(sp.stage / RR_WAVE), first ? RR_L1_CLOSEST_FIRST_WG : RR_L1_CLOSEST_WG));
             }
-            HIP_TRY(hipEventRecord(s->frame.stage_closest[k % 3u], st3));
-            HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_closest[k % 3u], 0));
+            HIP_TRY(sched_record(s->sched, s->frame.stage_closest[k % 3u], st3, "stage_closest", (int)(k % 3u)));
+            HIP_TRY(sched_wait(s->sched, st, s->frame.stage_closest[k % 3u], "stage_closest", (int)(k % 3u)));
         }
-        if (k >= sp.n_buf) HIP_TRY(hipStreamWaitEvent(st, s->frame.stage_traced[b], 0));
+        if (k >= sp.n_buf) HIP_TRY(sched_wait(s->sched, st, s->frame.stage_traced[b], "stage_traced", (int)b));
         RR_TRY(launch_shade(f, true, qin, count, c0, c1, qout, child_count, g, q, shade_wg, st));
         if (spawns && last) RR_TRY(read_back_level_size(f, child_count)); // behind the last shade stage
-        HIP_TRY(hipEventRecord(s->frame.stage_shaded[b], st));
+        HIP_TRY(sched_record(s->sched, s->frame.stage_shaded[b], st, "stage_shaded", (int)b));
         // The last stage's shadow launch goes to the third stream, idle by now (its last closest-hit launch ended before this stage was shaded):
         // on the second stream it would start only when the stage before it has been traced, and run alone.  It reads its own buffer and counters.
         const hipStream_t st_shadow = last ? st3 : st2;
-        HIP_TRY(hipStreamWaitEvent(st_shadow, s->frame.stage_shaded[b], 0));
+        HIP_TRY(sched_wait(s->sched, st_shadow, s->frame.stage_shaded[b], "stage_shaded", (int)b));
         RR_TRY(launch_shadow(f, g, q, shadow_wg, st_shadow));
-        HIP_TRY(hipEventRecord(s->frame.stage_traced[b], st_shadow));
+        HIP_TRY(sched_record(s->sched, s->frame.stage_traced[b], st_shadow, "stage_traced", (int)b));
     }
     // the second stream joins `st` later (join_shadow): before the deeper levels reuse the shadow queue, before k_resolve and before the frame's end event
     // ... and the third stream through it: stage_tail, on the second stream, follows the shadow launches of the last two stages
-    HIP_TRY(hipStreamWaitEvent(st2, s->frame.stage_traced[sp.buffer_of(sp.n_stages - 1)], 0));
-    HIP_TRY(hipEventRecord(s->frame.stage_tail, st2));
+    HIP_TRY(sched_wait(s->sched, st2, s->frame.stage_traced[sp.buffer_of(sp.n_stages - 1)], "stage_traced", (int)sp.buffer_of(sp.n_stages - 1)));
+    HIP_TRY(sched_record(s->sched, s->frame.stage_tail, st2, "stage_tail"));
     f.shadow_pending = s->frame.stage_tail;
     f.shadow_tail = level1_tail(sp);
     // (stage_traced[rest_buffer] was last recorded behind the shadow launch of rest_stage: the two stages after it use the other buffers)
@@ -660,20 +739,13 @@ static int enqueue_level1_stages(FrameRun& f, const Level1Stages& sp, const DRay
     return RR_OK;
 }
 
-// THE one way in and out of the staged path: whatever ends it early (cancel flag, HIP error, counter pool exhausted) leaves all three streams
-// idle, so the handle stays usable and the next frame cannot race a straggler.
+// THE one way into the staged path.  Whatever ends it early (cancel flag, HIP error, counter pool exhausted, an exception) leaves launches on
+// all three streams: the frame's FrameStreamsIdle (render_region_locked) waits for them, so the handle stays usable and the next frame cannot race a straggler.
 static int run_level1_stages(FrameRun& f, const Level1Stages& sp, const DRayQueue& qin, uint32_t* count, uint64_t s0, uint64_t s1,
                              const DRayQueue& qout, uint32_t* child_count, bool spawns, bool trace_closest) {
     rr_scene* s = f.s;
     RR_TRY(ensure_overlap_stream(s));
-    const int rc = enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns, trace_closest);
-    if (rc != RR_OK) {
-        f.shadow_pending = nullptr; f.shadow_rest = nullptr; // (an earlier slice's: the second stream is drained here)
-        (void)hipStreamSynchronize(s->frame.closest_stream);
-        (void)hipStreamSynchronize(s->frame.overlap_stream);
-        (void)hipStreamSynchronize(f.st);
-        return rc;
-    }
+    RR_TRY(enqueue_level1_stages(f, sp, qin, count, s0, s1, qout, child_count, spawns, trace_closest));
     s->frame.overlap_stages += sp.n_stages;
     return RR_OK;
 }
@@ -721,12 +793,17 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
         const bool in_stages = staged(s1 - s0);
         if (in_stages) RR_TRY(run_level1_stages(f, level1_stages(s, s1 - s0), qin, count, s0, s1, qout, child_count, spawns, closest_staged));
         for (uint64_t c0 = s0; c0 < s1 && !in_stages; c0 += f.plan.chunk) {
-            if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+            if (f.cancel && *f.cancel) { (void)sched_sync_stream(s->sched, st, "cancelled"); return fail(RR_ERR_CANCELLED, "cancelled"); }
             const uint64_t c1 = std::min<uint64_t>(c0 + f.plan.chunk, s1);
             const ShadeChunk g = plan_shade_chunk(c0, c1, L, sq_fixed);
             if (f.level1_only) { // the ending of level 1 of rr_albedo_pixels: no shadow slots, no children, no counters of its own
                 if (!l1 || spawns || !f.acc.rgb || !f.acc.flags) return fail(RR_ERR_DEVICE, "internal: albedo launch outside a level 1 that ends its paths");
                 ScopedTimer t(s, st, TK_SHADE, true);
+                if (s->sched.on) // (k_albedo_level1: the hits and what primary_ray reads; colour planes and flags only)
+                    sched_launch(s->sched, st, "k_albedo_level1", {sa_r(s->frame.shade_const.p, sizeof(DShadeConst), "shade_const"), sa_r(f.pr.sample_tr, s->frame.sample_tr.bytes, "sample_tr"),
+                                                                  sa_r(s->frame.slot_c.p, s->frame.slot_c.bytes, "slot_c"), sa_r(s->frame.pixel_c.p, s->frame.pixel_c.bytes, "pixel_c"),
+                                                                  sa_r(count, 4, "level count"), sa_r(qin.hit + c0, (size_t)(c1 - c0) * 16, "hit records"),
+                                                                  sa_a(f.acc.rgb, (size_t)f.acc.n * 24, "acc_rgb"), sa_a(f.acc.flags, (size_t)f.acc.n * 4, "acc_flags")});
                 hipLaunchKernelGGL(k_albedo_level1, dim3((uint32_t)std::min<uint64_t>(g.groups, (uint64_t)f.shade_grid_max)), dim3(RR_BLOCK), 0, st, s->frame.shade_const.as<DShadeConst>(),
                                    f.pr, qin.hit, count, (uint32_t)c0, (uint32_t)c1, f.acc);
                 continue;
@@ -741,7 +818,8 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
             if (L) RR_TRY(launch_shadow(f, g, q, (uint64_t)f.shadow_grid, st, l1 && f.diffuse != nullptr));
         }
         if (!spawns) continue;
-        HIP_TRY(hipEventSynchronize(s->frame.count_ready));
+        HIP_TRY(sched_sync_event(s->sched, s->frame.count_ready, "count_ready"));
+        sched_host_read(s->sched, s->frame.h_count + HC_LEVEL, 4, "h_count[HC_LEVEL]");
         const uint64_t m = s->frame.h_count[HC_LEVEL];
         if (m > M - child_base) return fail(RR_ERR_DEVICE, "internal: level %u holds %llu rays, room for %llu", d + 1, (unsigned long long)m, (unsigned long long)(M - child_base));
         if (m == 0) continue;
@@ -756,6 +834,25 @@ static int run_level(FrameRun& f, uint32_t d, uint64_t base, uint64_t n, uint32_
 static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& io) {
     const dim3 grid((fr.n_region_pixels + RR_BLOCK - 1) / RR_BLOCK), block(RR_BLOCK);
     const uint32_t by_pixel = io.pixel_xy ? 0u : 1u; // a region's answers go to y * width + x, a list's to the entry's index
+    if (f.s->sched.on && io.end != FrameEnd::NONE) {
+        // every resolve reads the planes of its n slots and the slot -> pixel map and writes one answer per pixel: at y * width + x anywhere in the
+        // frame, or at the slot's (the entry's) index; with parts a pixel is K slots and has K part records more
+        ScheduleLog& log = f.s->sched;
+        const size_t n = fr.n_region_pixels, K = (size_t)1 << io.lg_parts, frame_px = (size_t)fr.width * fr.height;
+        const size_t px = io.end == FrameEnd::REGION_BYTES ? (io.frame_layout ? frame_px : n) : (by_pixel ? frame_px : n >> io.lg_parts);
+        const bool split = io.end == FrameEnd::RECORD_SPLIT, parts = io.end == FrameEnd::RECORD_PARTS || split, region = io.end == FrameEnd::REGION_BYTES;
+        const bool records = io.end == FrameEnd::RECORDS || parts;
+        static const char* const name[6] = {"k_resolve", "k_resolve_pixels", "k_resolve_pixel_parts", "k_resolve_albedo", "k_resolve_pixel_split", ""};
+        sched_launch(log, f.st, name[(int)io.end],
+                     {sa_r(f.acc.rgb, n * 24, "acc_rgb"), sa_r(f.acc.normal, n * 24, "acc_normal"), sa_r(f.acc.depth, n * 8, "acc_depth"), sa_r(f.acc.object_id, n * 4, "acc_id"),
+                      sa_r(f.acc.flags, n * 4, "acc_flags"), sa_r(split ? f.diffuse : nullptr, n * 24, "acc_diffuse"), sa_r(region ? nullptr : f.slot_xy, n * 4, "slot_xy"),
+                      sa_r(region ? f.s->frame.region_xy.p : nullptr, n * 4, "region_xy"), sa_r(region ? f.s->frame.trace_order.p : nullptr, n * 4, "trace_order"),
+                      sa_w(region ? io.out->rgba8 : nullptr, px * 4, "out rgba8"), sa_w(region ? io.out->normal : nullptr, px * 12, "out normal"),
+                      sa_w(region ? io.out->depth : nullptr, px * 4, "out depth"), sa_w(region ? io.out->object_id : nullptr, px * 4, "out object_id"),
+                      sa_w(records ? io.radiance : nullptr, px * 32, "out records"), sa_w(io.end == FrameEnd::RECORDS ? io.rgba8 : nullptr, px * 4, "out rgba8"),
+                      sa_w(parts ? io.parts : nullptr, px * K * 32, "out part records"), sa_w(split ? io.diffuse : nullptr, px * 12, "out diffuse"),
+                      sa_w(split ? io.diffuse_parts : nullptr, px * K * 12, "out diffuse parts"), sa_w(io.end == FrameEnd::ALBEDO ? io.albedo : nullptr, px * 12, "out albedo")});
+    }
     switch (io.end) {
     case FrameEnd::NONE: break;
     case FrameEnd::ALBEDO: hipLaunchKernelGGL(k_resolve_albedo, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (uint32_t*)io.albedo); break;
@@ -781,7 +878,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_
     const uint64_t B = f.plan.B, total_primary = first0 + f.plan.total_primary;
     const PassHook* hook = io.hook;
     for (uint64_t first = first0; first < total_primary; first += B) {
-        if (f.cancel && *f.cancel) { (void)hipStreamSynchronize(f.st); return fail(RR_ERR_CANCELLED, "cancelled"); }
+        if (f.cancel && *f.cancel) { (void)sched_sync_stream(s->sched, f.st, "cancelled"); return fail(RR_ERR_CANCELLED, "cancelled"); }
         const uint32_t n_batch = (uint32_t)std::min<uint64_t>(B, total_primary - first);
         RR_TRY(join_shadow(f)); // the previous batch's last shadow launch reads counters of the pool that start_batch zeroes
         RR_TRY(f.pool.start_batch());
@@ -792,14 +889,14 @@ static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_
         RR_TRY(run_level(f, 1, 0, n_batch, level1_count));
         HIP_TRY(hipGetLastError());
         // batches are stream-ordered; only a caller that can cancel needs the host to keep pace with the device
-        if (f.cancel && first + B < total_primary) HIP_TRY(hipStreamSynchronize(f.st));
+        if (f.cancel && first + B < total_primary) HIP_TRY(sched_sync_stream(s->sched, f.st, "keep pace with a cancellable frame"));
         const uint64_t done = first + n_batch;
         if (hook && hook->fn && done < total_primary && done % npix == 0) {
             DFrame pf = fr;
             pf.samples = (uint32_t)(done / npix); // the mean over the sample slices finished so far
             RR_TRY(join_shadow(f));
             launch_resolve(f, pf, io);
-            RR_TRY(copy_outputs(*hook->host, *io.out, (size_t)fr.width * fr.height, f.st));
+            RR_TRY(copy_outputs(s->sched, *hook->host, *io.out, (size_t)fr.width * fr.height, f.st));
             InPass in_pass(s);
             if (hook->fn(hook->user, done, total_primary) != 0) return fail(RR_ERR_CANCELLED, "stopped by the pass callback");
         }
@@ -809,7 +906,7 @@ static int run_batches(FrameRun& f, const DFrame& fr, const FrameIo& io, uint64_
 
 // The handle's frame and query buffers are shared: frames and queries on different streams are serialised.
 static int take_stream(rr_scene* s, hipStream_t st) {
-    if (st != s->frame.last_stream) { HIP_TRY(hipStreamSynchronize(s->frame.last_stream)); s->frame.last_stream = st; }
+    if (st != s->frame.last_stream) { HIP_TRY(sched_sync_stream(s->sched, s->frame.last_stream, "take_stream")); s->frame.last_stream = st; }
     return RR_OK;
 }
 // a frame's (or a radiance query's) statistics start from nothing
@@ -820,8 +917,8 @@ static void begin_frame_stats(rr_scene* s) {
     s->frame.overlap_stages = 0;
 }
 
-static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
-                                const FrameIo io, hipStream_t st, const volatile int* cancel) {
+static int render_region_body(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                              const FrameIo& io, hipStream_t st, const volatile int* cancel) {
     RR_TRY(check_intact(s));
     HIP_TRY(hipSetDevice(s->device));
     RR_TRY(take_stream(s, st));
@@ -870,16 +967,24 @@ static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_conf
     RR_TRY(upload_shade_const(s, fr, primary_frame(slot_c, npix, plan.G), st)); // (after the plan: the index constants follow its sample group)
     FrameRun f = make_frame_run(s, st, plan, R, end.level1_only, acc, DPrimary{s->frame.sample_tr.as<float>(), primary_launch(0, npix, 1u), 0u, io.lg_parts}, slot_xy, cancel);
     if (end.split) { f.diffuse = diffuse; f.sq_s3 = s->frame.sq3.as<float4>(); }
-    HIP_TRY(hipEventRecord(s->timing.frame_a, st));
+    HIP_TRY(sched_record(s->sched, s->timing.frame_a, st, "frame_a"));
     int rc = run_batches(f, fr, io, (uint64_t)(io.samples_from >> io.lg_parts) * npix);
     if (rc == RR_OK) rc = join_shadow(f); // level 2 empty, or a level 1 that spawns nothing: the join falls here
-    if (rc != RR_OK) { drain_shadow(f); return rc; }
+    if (rc != RR_OK) return rc; // (FrameStreamsIdle waits for whatever is pending)
     launch_resolve(f, fr, io);
-    HIP_TRY(hipEventRecord(s->timing.frame_b, st));
+    HIP_TRY(sched_record(s->sched, s->timing.frame_b, st, "frame_b"));
     HIP_TRY(hipGetLastError());
     // a scene that branches more than the arena was sized for gets a larger one for its next frame (within the budget)
     if (s->timing.stats.sliced_levels > 0 && s->frame.arena_factor < 128) s->frame.arena_factor *= 2;
     return RR_OK;
+}
+
+// (the recorder's scope: the log holds what was enqueued between this function's entry and its return, whichever way it is left)
+static int render_region_locked(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
+                                const FrameIo io, hipStream_t st, const volatile int* cancel) {
+    ScheduleScope scope(s->sched, st);
+    FrameStreamsIdle idle(s, st); // (destroyed before `scope`: on unwinding its waits stand in front of the log's end marker, as on an error code)
+    return scope.done(idle.done(render_region_body(s, cam, cfg, sample_xy, io, st, cancel)));
 }
 
 extern "C" int rr_render_region_device(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy,
@@ -905,7 +1010,7 @@ static int render_to_host(rr_scene* s, const rr_camera* cam, const rr_config* cf
     PassHook hook{fn, user, min_passes, out};
     RR_TRY(render_region_locked(s, cam, cfg, sample_xy, frame_io(&WHOLE_FRAME, &dev, true, fn ? &hook : nullptr), nullptr, cancel));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    return copy_outputs(*out, dev, np, nullptr);
+    return copy_outputs(s->sched, *out, dev, np, nullptr);
 }
 
 extern "C" int rr_render(rr_scene* s, const rr_camera* cam, const rr_config* cfg, const uint16_t* sample_xy, const rr_frame* out,
@@ -1010,7 +1115,7 @@ extern "C" int rr_render_progressive_tiles(rr_scene* s, const rr_camera* cam, co
         HIP_TRY(hipStreamSynchronize(nullptr));
         RR_TRY(collect_stats_locked(s));
         sums.add(); // the frame's statistics are the sums over its passes
-        RR_TRY(copy_outputs(*out, dev, np, nullptr));
+        RR_TRY(copy_outputs(s->sched, *out, dev, np, nullptr));
         done += rr_region_pixel_count(W, H, &rg);
         sums.close();
         if (k + 1 < P) {

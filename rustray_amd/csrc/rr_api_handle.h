@@ -236,6 +236,7 @@ struct rr_scene {
     RecordStage record_stage;
     MultiState multi;
     FrameTiming timing;
+    ScheduleLog sched; // the schedule recorder (rr_schedule_log.h): off unless a test switches it on; written by rr_api_frame.h
     // Every release (hipFree in ~DevBuf, the events, streams and pinned memory in the parts' destructors) must run on the scene's
     // device.  A destructor's body runs before its class's members are destroyed, whatever their order of declaration: the
     // hipSetDevice here precedes every one of them, and `device` is a plain int that stays readable throughout.

@@ -243,7 +243,7 @@ extern "C" int rr_render_multi(rr_scene* const* scenes, uint32_t n_scenes, const
     }
     for (int k = 0; k < 4; k++)
         if (host[k]) RR_TRY(rr_deinterleave_device(W, H, TW, TH, n_scenes, (uint32_t)OUT_ELEM[k], s0->multi.cat[k].p, out_buffer(frame_dev, k), s0->device, s0->multi.stream));
-    RR_TRY(copy_outputs(*out, frame_dev, np, s0->multi.stream));
+    RR_TRY(copy_outputs(s0->sched, *out, frame_dev, np, s0->multi.stream));
     s0->timing.stats.multi_devices = n_scenes; s0->timing.stats.multi_peer_links = n_peer; s0->timing.stats.multi_staged_links = n_staged;
     s0->timing.stats.ms_multi_exchange = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_joined).count();
     return RR_OK;

@@ -160,7 +160,8 @@ def test_cancelled_frames_then_a_clean_frame(hip, mixed):
     """(g) a frame stopped by the cancel flag -- set beforehand, and set from the pass callback between the two batches of a progressive
     frame -- returns RR_ERR_CANCELLED, and the frame after it on the same handle is the serial frame.  Neither cancelled frame has a launch
     pending when it ends (the first stops before its first batch, the second behind the join in front of the pass hook's resolve): a flag set
-    while launches are pending is a matter of timing no test can arrange, so drain_shadow with a launch pending is not exercised here."""
+    while launches are pending is a matter of timing no test can arrange; the way out with launches pending on all three streams is
+    tests/test_gpu_launch_order.py's (an injected exception between two stages, and the recorded schedule)."""
     cam = camera_for(mixed, W, H).c_struct()
     cfg = _cfg()
     L = hip.lib()
