@@ -854,25 +854,7 @@ public:
     // (rr_last_error() says why).
     History accumulate(const rr_radiance* records, const rr_radiance* halves, const History* history, const rr_accumulate_params* params = nullptr,
                        const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
-        History out;
-        const size_t n = (size_t)camera.width * camera.height;
-        rr_accumulate_params prm;
-        if (params) prm = *params;
-        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
-        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
-        const bool first = !history || history->empty();
-        const rr_camera cam = camera.c_struct();
-        out.records.resize(n);
-        out.length.assign(n, 0.0f);
-        if (halves) out.halves.resize(2 * n);
-        if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_accumulate_records(scene->handle(), &cam, &prm, records, halves, first ? nullptr : history->records.data(),
-                                  first || history->halves.empty() ? nullptr : history->halves.data(), first ? nullptr : history->length.data(), motion,
-                                  out.records.data(), halves ? out.halves.data() : nullptr, out.length.data(), rgba8 ? rgba8->data() : nullptr) != RR_OK) {
-            out = History();
-            if (rgba8) rgba8->clear();
-        }
-        return out;
+        return colour_part(accumulate_call(false, nullptr, records, halves, nullptr, nullptr, history, nullptr, params, motion, rgba8));
     }
     // the same on DEVICE buffers, in stream order (rr_accumulate_records_device): not waited for
     int accumulate_device(const rr_accumulate_params& params, const rr_radiance* records_dev, const rr_radiance* halves_dev, const rr_radiance* history_dev,
@@ -897,25 +879,7 @@ public:
     // would blend the stale colour in for up to max_history frames.  The arguments are accumulate()'s behind `clamp`.
     History accumulate_clamped(const HistoryClamp& clamp, const rr_radiance* records, const rr_radiance* halves, const History* history,
                                const rr_accumulate_params* params = nullptr, const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
-        History out;
-        const size_t n = (size_t)camera.width * camera.height;
-        rr_accumulate_params prm;
-        if (params) prm = *params;
-        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
-        if (!records || n == 0 || n > ((size_t)1 << 29)) return out;
-        const bool first = !history || history->empty();
-        const rr_camera cam = camera.c_struct();
-        out.records.resize(n);
-        out.length.assign(n, 0.0f);
-        if (halves) out.halves.resize(2 * n);
-        if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_accumulate_clamped_records(scene->handle(), &cam, &prm, &clamp, records, halves, first ? nullptr : history->records.data(),
-                                          first || history->halves.empty() ? nullptr : history->halves.data(), first ? nullptr : history->length.data(), motion,
-                                          out.records.data(), halves ? out.halves.data() : nullptr, out.length.data(), rgba8 ? rgba8->data() : nullptr) != RR_OK) {
-            out = History();
-            if (rgba8) rgba8->clear();
-        }
-        return out;
+        return colour_part(accumulate_call(false, &clamp, records, halves, nullptr, nullptr, history, nullptr, params, motion, rgba8));
     }
     // the same on DEVICE buffers, in stream order (rr_accumulate_clamped_records_device): not waited for; out_dev may not be records_dev
     int accumulate_clamped_device(const rr_accumulate_params& params, const HistoryClamp& clamp, const rr_radiance* records_dev, const rr_radiance* halves_dev,
@@ -930,36 +894,69 @@ public:
     struct SplitHistory : History {
         std::vector<float> diffuse, diffuse_halves; // width * height * 3, and twice as many (empty: no halves)
     };
+
+  private:
+    // THE host form behind accumulate(), accumulate_clamped(), accumulate_split() and accumulate_clamped_split(): the variant by `split`
+    // (the calls with the diffuse layers, which also refuse a frame without `diffuse`) and `clamp` (nullptr: the calls without one).  It
+    // sizes the result, passes a history only when there is one (its halves only when it holds halves; `layers` is the same history seen
+    // as a SplitHistory, nullptr in the calls that are not split), and empties the result and rgba8 when the library refuses or fails.
+    SplitHistory accumulate_call(bool split, const HistoryClamp* clamp, const rr_radiance* records, const rr_radiance* halves, const float* diffuse,
+                                 const float* diffuse_halves, const History* history, const SplitHistory* layers, const rr_accumulate_params* params,
+                                 const float* motion, std::vector<uint8_t>* rgba8) const {
+        SplitHistory out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_accumulate_params prm;
+        if (params) prm = *params;
+        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
+        if (!records || (split && !diffuse) || n == 0 || n > ((size_t)1 << 29)) return out;
+        const bool first = !history || history->empty();
+        const bool hist_halves = !first && !history->halves.empty();
+        const rr_camera cam = camera.c_struct();
+        out.records.resize(n);
+        out.length.assign(n, 0.0f);
+        if (halves) out.halves.resize(2 * n);
+        if (split) out.diffuse.resize(3 * n);
+        if (split && halves) out.diffuse_halves.resize(6 * n);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        // the buffers by the names of the C arguments, in their order: the history, then the outputs
+        const rr_radiance* h = first ? nullptr : history->records.data();
+        const rr_radiance* h_halves = hist_halves ? history->halves.data() : nullptr;
+        const float* h_diffuse = first || !layers || layers->diffuse.empty() ? nullptr : layers->diffuse.data();
+        const float* h_diffuse_halves = hist_halves && layers && !layers->diffuse_halves.empty() ? layers->diffuse_halves.data() : nullptr;
+        const float* h_length = first ? nullptr : history->length.data();
+        rr_radiance* o = out.records.data();
+        rr_radiance* o_halves = halves ? out.halves.data() : nullptr;
+        float* o_diffuse = out.diffuse.data();
+        float* o_diffuse_halves = halves ? out.diffuse_halves.data() : nullptr;
+        float* o_length = out.length.data();
+        uint8_t* bytes = rgba8 ? rgba8->data() : nullptr;
+        rr_scene* s = scene->handle();
+        int rc;
+        if (!split && !clamp) rc = rr_accumulate_records(s, &cam, &prm, records, halves, h, h_halves, h_length, motion, o, o_halves, o_length, bytes);
+        else if (!split) rc = rr_accumulate_clamped_records(s, &cam, &prm, clamp, records, halves, h, h_halves, h_length, motion, o, o_halves, o_length, bytes);
+        else if (!clamp)
+            rc = rr_accumulate_split_records(s, &cam, &prm, records, halves, diffuse, diffuse_halves, h, h_halves, h_diffuse, h_diffuse_halves, h_length, motion, o,
+                                             o_halves, o_diffuse, o_diffuse_halves, o_length, bytes);
+        else
+            rc = rr_accumulate_clamped_split_records(s, &cam, &prm, clamp, records, halves, diffuse, diffuse_halves, h, h_halves, h_diffuse, h_diffuse_halves, h_length,
+                                                     motion, o, o_halves, o_diffuse, o_diffuse_halves, o_length, bytes);
+        if (rc != RR_OK) {
+            out = SplitHistory();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the History a call that is not split returns: the vectors moved out of the helper's result, not copied
+    static History colour_part(SplitHistory&& all) { return History(std::move(static_cast<History&>(all))); }
+
+  public:
     // Temporal accumulation of a split frame (rr_accumulate_split_records): accumulate() with `diffuse` width * height * 3 floats and
     // `diffuse_halves` twice as many (exactly when `halves` is given) blended by the same taps, weights and length.  The result feeds
     // denoise_split as it is.  An empty SplitHistory = refused or failed (rr_last_error() says why).
     SplitHistory accumulate_split(const rr_radiance* records, const rr_radiance* halves, const float* diffuse, const float* diffuse_halves,
                                   const SplitHistory* history, const rr_accumulate_params* params = nullptr, const float* motion = nullptr,
                                   std::vector<uint8_t>* rgba8 = nullptr) const {
-        SplitHistory out;
-        const size_t n = (size_t)camera.width * camera.height;
-        rr_accumulate_params prm;
-        if (params) prm = *params;
-        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
-        if (!records || !diffuse || n == 0 || n > ((size_t)1 << 29)) return out;
-        const bool first = !history || history->empty();
-        const bool hist_halves = !first && !history->halves.empty();
-        const rr_camera cam = camera.c_struct();
-        out.records.resize(n);
-        out.length.assign(n, 0.0f);
-        out.diffuse.resize(3 * n);
-        if (halves) { out.halves.resize(2 * n); out.diffuse_halves.resize(6 * n); }
-        if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_accumulate_split_records(scene->handle(), &cam, &prm, records, halves, diffuse, diffuse_halves, first ? nullptr : history->records.data(),
-                                        hist_halves ? history->halves.data() : nullptr, first || history->diffuse.empty() ? nullptr : history->diffuse.data(),
-                                        hist_halves && !history->diffuse_halves.empty() ? history->diffuse_halves.data() : nullptr,
-                                        first ? nullptr : history->length.data(), motion, out.records.data(), halves ? out.halves.data() : nullptr,
-                                        out.diffuse.data(), halves ? out.diffuse_halves.data() : nullptr, out.length.data(),
-                                        rgba8 ? rgba8->data() : nullptr) != RR_OK) {
-            out = SplitHistory();
-            if (rgba8) rgba8->clear();
-        }
-        return out;
+        return accumulate_call(true, nullptr, records, halves, diffuse, diffuse_halves, history, history, params, motion, rgba8);
     }
     // the same on DEVICE buffers, in stream order (rr_accumulate_split_records_device): not waited for
     int accumulate_split_device(const rr_accumulate_params& params, const rr_radiance* records_dev, const rr_radiance* halves_dev, const float* diffuse_dev,
@@ -978,31 +975,7 @@ public:
     SplitHistory accumulate_clamped_split(const HistoryClamp& clamp, const rr_radiance* records, const rr_radiance* halves, const float* diffuse,
                                           const float* diffuse_halves, const SplitHistory* history, const rr_accumulate_params* params = nullptr,
                                           const float* motion = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
-        SplitHistory out;
-        const size_t n = (size_t)camera.width * camera.height;
-        rr_accumulate_params prm;
-        if (params) prm = *params;
-        else if (rr_accumulate_default_params(&prm) != RR_OK) return out;
-        if (!records || !diffuse || n == 0 || n > ((size_t)1 << 29)) return out;
-        const bool first = !history || history->empty();
-        const bool hist_halves = !first && !history->halves.empty();
-        const rr_camera cam = camera.c_struct();
-        out.records.resize(n);
-        out.length.assign(n, 0.0f);
-        out.diffuse.resize(3 * n);
-        if (halves) { out.halves.resize(2 * n); out.diffuse_halves.resize(6 * n); }
-        if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_accumulate_clamped_split_records(scene->handle(), &cam, &prm, &clamp, records, halves, diffuse, diffuse_halves,
-                                                first ? nullptr : history->records.data(), hist_halves ? history->halves.data() : nullptr,
-                                                first || history->diffuse.empty() ? nullptr : history->diffuse.data(),
-                                                hist_halves && !history->diffuse_halves.empty() ? history->diffuse_halves.data() : nullptr,
-                                                first ? nullptr : history->length.data(), motion, out.records.data(), halves ? out.halves.data() : nullptr,
-                                                out.diffuse.data(), halves ? out.diffuse_halves.data() : nullptr, out.length.data(),
-                                                rgba8 ? rgba8->data() : nullptr) != RR_OK) {
-            out = SplitHistory();
-            if (rgba8) rgba8->clear();
-        }
-        return out;
+        return accumulate_call(true, &clamp, records, halves, diffuse, diffuse_halves, history, history, params, motion, rgba8);
     }
     // the same on DEVICE buffers, in stream order (rr_accumulate_clamped_split_records_device): not waited for; out_dev may not be records_dev
     // and diffuse_out_dev not diffuse_dev

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -18,13 +19,6 @@ from .flat import (RR_ABI_VERSION, FlatScene, rr_camera, rr_config, rr_flat_scen
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RUSTRAY_HIP_LIB") or os.path.join(_HERE, "librustray_hip.so")  # override: developer A/B builds
 _LIB = None
-
-# every symbol include/rustray_hip.h declares (tests/test_abi.py checks the list against the header)
-EXPORTS = ["rr_abi_version", "rr_device_count", "rr_last_error", "rr_scene_create", "rr_scene_destroy", "rr_scene_update_transforms",
-           "rr_scene_update_materials", "rr_scene_update_lights", "rr_scene_update_item_flags", "rr_scene_add_textures", "rr_scene_add_meshes", "rr_scene_set_items", "rr_scene_set_tuning", "rr_scene_get_tuning", "rr_scene_set_compat",
-           "rr_sample_table", "rr_render", "rr_render_multi", "rr_multi_lock_order", "rr_render_progressive", "rr_render_progressive_tiles", "rr_region_pixel_count", "rr_render_region_device",
-           "rr_deinterleave_device", "rr_deinterleave_packed_device", "rr_pick", "rr_trace_rays", "rr_trace_shadow_rays", "rr_shade_rays", "rr_trace_rays_device", "rr_trace_shadow_rays_device", "rr_shade_rays_device", "rr_surface_rays", "rr_surface_rays_device", "rr_render_pixels", "rr_render_pixels_device", "rr_render_pixel_parts", "rr_render_pixel_parts_device", "rr_refine_list_capacity", "rr_refine_list_device", "rr_render_adaptive", "rr_render_adaptive_device", "rr_refine_sublist_device", "rr_render_adaptive_levels", "rr_render_adaptive_levels_device", "rr_render_pixel_prefix", "rr_render_pixel_prefix_device", "rr_render_adaptive_prefix", "rr_render_adaptive_prefix_device", "rr_denoise_default_params", "rr_denoise_records", "rr_denoise_records_device", "rr_accumulate_default_params", "rr_accumulate_records", "rr_accumulate_records_device", "rr_motion_records", "rr_motion_records_device", "rr_surface_pixels", "rr_surface_pixels_device", "rr_albedo_pixels", "rr_albedo_pixels_device", "rr_render_pixel_split", "rr_render_pixel_split_device", "rr_denoise_split_records", "rr_denoise_split_records_device", "rr_accumulate_split_records", "rr_accumulate_split_records_device", "rr_history_clamp_default_params", "rr_accumulate_clamped_records", "rr_accumulate_clamped_records_device", "rr_accumulate_clamped_split_records", "rr_accumulate_clamped_split_records_device", "rr_scene_last_stats", "rr_scene_overlap_stages", "rr_post_process", "rr_post_process_device"]
-
 
 class rr_shadow_hit(C.Structure):
     """include/rustray_hip.h: one record of rr_trace_shadow_rays."""
@@ -86,6 +80,109 @@ def build(force: bool = False) -> str:
     return LIB_PATH
 
 
+class AccumulateRow(NamedTuple):
+    """One buffer of the temporal calls: `name` is the header's parameter (the device forms append _dev, and the methods below _ptr), `shape`
+    and `dtype` those of one pixel, `diffuse` says whether it is one of the six rows only the split calls have.  An output names in `key`
+    its entry of the result dict, which is also the input it may be written over in place."""
+    name: str
+    shape: tuple
+    diffuse: bool
+    key: Optional[str] = None
+    dtype: type = np.float32
+
+
+# THE buffers of rr_accumulate[_clamped][_split]_records[_device], in the order of their arguments: the mirror of AccumulateIo and
+# accumulate_rows in csrc/rr_api_temporal.h.  The calls that are not split take this table without its diffuse rows; that is the only
+# difference between the argument lists.  Signatures, host arrays, device pointers and the torch wrappers (renderer.py) are read off it.
+ACCUMULATE_ROWS = (
+    AccumulateRow("records", (8,), False), AccumulateRow("halves", (2, 8), False),
+    AccumulateRow("diffuse", (3,), True), AccumulateRow("diffuse_halves", (2, 3), True),
+    AccumulateRow("history", (8,), False), AccumulateRow("history_halves", (2, 8), False),
+    AccumulateRow("history_diffuse", (3,), True), AccumulateRow("history_diffuse_halves", (2, 3), True),
+    AccumulateRow("history_length", (), False), AccumulateRow("motion", (3,), False),
+    AccumulateRow("out", (8,), False, "records"), AccumulateRow("halves_out", (2, 8), False, "halves"),
+    AccumulateRow("diffuse_out", (3,), True, "diffuse"), AccumulateRow("diffuse_halves_out", (2, 3), True, "diffuse_halves"),
+    AccumulateRow("length_out", (), False, "length"), AccumulateRow("rgba8", (4,), False, "rgba", np.uint8))
+
+
+def accumulate_rows(split: bool) -> tuple:
+    """The rows of ACCUMULATE_ROWS a call has, in the order of its arguments."""
+    return tuple(r for r in ACCUMULATE_ROWS if split or not r.diffuse)
+
+
+def _accumulate_fn(split: bool, clamped: bool, device: bool) -> str:
+    return "rr_accumulate" + ("_clamped" if clamped else "") + ("_split" if split else "") + "_records" + ("_device" if device else "")
+
+
+def _accumulate_signatures() -> dict:
+    """The eight temporal calls: scene, camera, params [, clamp], one pointer per row of the table [, the stream]."""
+    sigs = {}
+    for split in (False, True):
+        for clamped in (False, True):
+            args = [_V, _CAM, C.POINTER(rr_accumulate_params)] + ([C.POINTER(rr_history_clamp_params)] if clamped else []) + [_V] * len(accumulate_rows(split))
+            sigs[_accumulate_fn(split, clamped, False)] = (args, C.c_int)
+            sigs[_accumulate_fn(split, clamped, True)] = (args + [_V], C.c_int)
+    return sigs
+
+
+_V, _I, _F, _U16, _U32, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_uint16, C.c_uint32, C.c_uint64
+_CAM, _CFG, _DN, _COUNT = C.POINTER(rr_camera), C.POINTER(rr_config), C.POINTER(rr_denoise_params), C.POINTER(C.c_uint32)
+_PIXELS = [_V, _CAM, _CFG, _V, _V, _U32]            # scene, camera, config, sample table, pixel list, n_pixels: how the pixel queries begin
+_PROGRESSIVE = [_V, _CAM, _CFG, _V, C.POINTER(rr_frame), _U32, PASS_FN, _V, _V]
+_ADAPTIVE = [_V, _CAM, _CFG, _U16, _U16, _F, _V, _V, _V, _V, _V, _V, _COUNT, _V]
+
+# every function include/rustray_hip.h declares: name -> (argtypes, restype).  tests/test_temporal_binding_host.py compares the lengths
+# with the header's parameter lists; EXPORTS, what build() and tests/test_abi.py look for in the library, is this table's names.
+_PUBLIC = {
+    "rr_abi_version": ([], _U32), "rr_device_count": ([], _I), "rr_last_error": ([], C.c_char_p),
+    "rr_scene_create": ([C.POINTER(rr_flat_scene), _I, C.POINTER(_V)], _I), "rr_scene_destroy": ([_V], None),
+    "rr_scene_update_transforms": ([_V, _V, _V], _I), "rr_scene_update_materials": ([_V, _V, _U32], _I), "rr_scene_update_lights": ([_V, _V, _U32], _I),
+    "rr_scene_update_item_flags": ([_V, _V, _V, _U32], _I), "rr_scene_add_textures": ([_V, _V, _U32, _COUNT], _I),
+    "rr_scene_add_meshes": ([_V, _V, _U32, _COUNT], _I), "rr_scene_set_items": ([_V, _V, _U32, _V, _U32], _I),
+    "rr_scene_set_tuning": ([_V, C.POINTER(rr_tuning)], _I), "rr_scene_get_tuning": ([_V, C.POINTER(rr_tuning)], _I), "rr_scene_set_compat": ([_V, _U32], _I),
+    "rr_scene_last_stats": ([_V, C.POINTER(rr_frame_stats)], _I), "rr_scene_overlap_stages": ([_V, _COUNT], _I),
+    "rr_sample_table": ([_U16, _V, _COUNT], _I),
+    "rr_render": ([_V, _CAM, _CFG, _V, C.POINTER(rr_frame), _V], _I),
+    "rr_render_multi": ([C.POINTER(_V), _U32, _CAM, _CFG, _V, C.POINTER(rr_frame), _V], _I), "rr_multi_lock_order": ([C.POINTER(_V), _U32, _COUNT], _I),
+    "rr_render_progressive": (_PROGRESSIVE, _I), "rr_render_progressive_tiles": (_PROGRESSIVE, _I),
+    "rr_region_pixel_count": ([_U32, _U32, C.POINTER(rr_region)], _U64),
+    "rr_render_region_device": ([_V, _CAM, _CFG, _V, C.POINTER(rr_region), C.POINTER(rr_frame), _V, _V], _I),
+    "rr_deinterleave_device": ([_U32] * 6 + [_V, _V, _I, _V], _I),
+    "rr_deinterleave_packed_device": ([_U32] * 5 + [_V, _U64, C.POINTER(_U64), _COUNT, C.POINTER(_V), _I, _V], _I),
+    "rr_pick": ([_V, _CAM, _I, _I, C.POINTER(rr_pick_result)], _I),
+    "rr_trace_rays": ([_V, _V, _V, _U32, _U32, _V], _I), "rr_trace_rays_device": ([_V, _V, _V, _U32, _U32, _V, _V], _I),
+    "rr_trace_shadow_rays": ([_V, _V, _V, _V, _U32, _U32, C.POINTER(rr_shadow_hit)], _I), "rr_trace_shadow_rays_device": ([_V, _V, _V, _V, _U32, _U32, _V, _V], _I),
+    "rr_shade_rays": ([_V, _CFG, _V, _V, _U32, _U32, _V, _V, _V], _I), "rr_shade_rays_device": ([_V, _CFG, _V, _V, _U32, _U32, _V, _V, _V, _V], _I),
+    "rr_surface_rays": ([_V, _V, _V, _U32, _U32, _V], _I), "rr_surface_rays_device": ([_V, _V, _V, _U32, _U32, _V, _V], _I),
+    "rr_render_pixels": (_PIXELS + [_V] * 3, _I), "rr_render_pixels_device": (_PIXELS + [_V] * 4, _I),
+    "rr_render_pixel_parts": (_PIXELS + [_U32] + [_V] * 3, _I), "rr_render_pixel_parts_device": (_PIXELS + [_U32] + [_V] * 4, _I),
+    "rr_refine_list_capacity": ([_U32, _U32], _U64), "rr_refine_list_device": ([_V, _U32, _U32, _V, _F, _V, _V, _COUNT, _V], _I),
+    "rr_render_adaptive": (_ADAPTIVE, _I), "rr_render_adaptive_device": (_ADAPTIVE + [_V], _I),
+    "rr_refine_sublist_device": ([_V, _V, _U32, _V, _F, _V, _V, _COUNT, _V], _I),
+    "rr_render_adaptive_levels": ([_V, _CAM, _CFG, _V, _U32, _F] + [_V] * 7, _I), "rr_render_adaptive_levels_device": ([_V, _CAM, _CFG, _V, _U32, _F] + [_V] * 8, _I),
+    "rr_render_pixel_prefix": (_PIXELS + [_U32] + [_V] * 4, _I), "rr_render_pixel_prefix_device": (_PIXELS + [_U32] + [_V] * 5, _I),
+    "rr_render_adaptive_prefix": ([_V, _CAM, _CFG, _V, _V, _U32, _F] + [_V] * 6, _I), "rr_render_adaptive_prefix_device": ([_V, _CAM, _CFG, _V, _V, _U32, _F] + [_V] * 7, _I),
+    "rr_denoise_default_params": ([_DN], _I),
+    "rr_denoise_records": ([_V, _U32, _U32, _DN] + [_V] * 6, _I), "rr_denoise_records_device": ([_V, _U32, _U32, _DN] + [_V] * 7, _I),
+    "rr_denoise_split_records": ([_V, _U32, _U32, _DN] + [_V] * 7, _I), "rr_denoise_split_records_device": ([_V, _U32, _U32, _DN] + [_V] * 8, _I),
+    "rr_accumulate_default_params": ([C.POINTER(rr_accumulate_params)], _I), "rr_history_clamp_default_params": ([C.POINTER(rr_history_clamp_params)], _I),
+    **_accumulate_signatures(),
+    "rr_motion_records": ([_V, _CAM, _V, _V, _U32, _V, _V, _V], _I), "rr_motion_records_device": ([_V, _CAM, _V, _V, _U32, _V, _V, _V, _V], _I),
+    "rr_surface_pixels": ([_V, _CAM, _V, _U32, _V, _V], _I), "rr_surface_pixels_device": ([_V, _CAM, _V, _U32, _V, _V, _V], _I),
+    "rr_albedo_pixels": (_PIXELS + [_V] * 2, _I), "rr_albedo_pixels_device": (_PIXELS + [_V] * 3, _I),
+    "rr_render_pixel_split": (_PIXELS + [_V] * 5, _I), "rr_render_pixel_split_device": (_PIXELS + [_V] * 6, _I),
+    "rr_post_process": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I], _I), "rr_post_process_device": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I, _V], _I),
+}
+# the test entry points the binding calls: exported by the library, declared in no public header
+_TEST_ONLY = {
+    "rr_test_denoise_forms": ([_U32], None),
+    "rr_test_schedule_record": ([_V, _I], _I), "rr_test_schedule_read": ([_V, _V, _U64, C.POINTER(_U64)], _I),
+    "rr_math_probe": ([_I, _V, _V, _V, _I, _V, _V, _V, _U64, _I], _I),
+}
+SIGNATURES = {**_PUBLIC, **_TEST_ONLY}
+EXPORTS = list(_PUBLIC)
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -93,133 +190,18 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                "or `make -C rustray_amd/csrc` — there is no fallback path")
         L = C.CDLL(LIB_PATH)
-        L.rr_last_error.restype = C.c_char_p
-        got = 1
+        developer = bool(os.environ.get("RUSTRAY_HIP_LIB"))   # a developer A/B build of an older revision is the caller's business:
+        got = 1                                               # it may speak another version and lack symbols
         if hasattr(L, "rr_abi_version"):
             L.rr_abi_version.restype = C.c_uint32
             got = L.rr_abi_version()
-        if got != RR_ABI_VERSION and not os.environ.get("RUSTRAY_HIP_LIB"):  # (a developer A/B build of an older revision is the caller's business)
+        if got != RR_ABI_VERSION and not developer:
             raise RuntimeError(f"{LIB_PATH} speaks ABI version {got}, this binding {RR_ABI_VERSION}: rebuild the library")
-        L.rr_region_pixel_count.restype = C.c_uint64
-        L.rr_region_pixel_count.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(rr_region)]
-        L.rr_scene_create.argtypes = [C.POINTER(rr_flat_scene), C.c_int, C.POINTER(C.c_void_p)]
-        L.rr_scene_destroy.argtypes = [C.c_void_p]
-        L.rr_scene_destroy.restype = None
-        L.rr_scene_update_transforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rr_sample_table.argtypes = [C.c_uint16, C.c_void_p, C.POINTER(C.c_uint32)]
-        L.rr_render.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.POINTER(rr_frame), C.c_void_p]
-        L.rr_render_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.POINTER(rr_frame), C.c_void_p]
-        L.rr_render_progressive.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.POINTER(rr_frame),
-                                            C.c_uint32, PASS_FN, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_progressive_tiles") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
-            L.rr_render_progressive_tiles.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.POINTER(rr_frame),
-                                                      C.c_uint32, PASS_FN, C.c_void_p, C.c_void_p]
-        L.rr_render_region_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p,
-                                              C.POINTER(rr_region), C.POINTER(rr_frame), C.c_void_p, C.c_void_p]
-        L.rr_deinterleave_device.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.rr_pick.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_int, C.c_int, C.POINTER(rr_pick_result)]
-        L.rr_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-        if hasattr(L, "rr_trace_shadow_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
-            L.rr_trace_shadow_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_shadow_hit)]
-        if hasattr(L, "rr_shade_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a developer A/B build of an older revision may lack it)
-            L.rr_shade_rays.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_shade_rays_device") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.rr_trace_shadow_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.rr_shade_rays_device.argtypes = [C.c_void_p, C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_surface_rays") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_surface_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-            L.rr_surface_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_render_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_pixel_parts") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_render_pixel_parts.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                C.c_void_p, C.c_void_p]
-            L.rr_render_pixel_parts_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_adaptive") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
-            L.rr_refine_list_capacity.restype = C.c_uint64
-            L.rr_refine_list_capacity.argtypes = [C.c_uint32, C.c_uint32]
-            L.rr_refine_list_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
-            L.rr_render_adaptive.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
-            L.rr_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_uint16, C.c_uint16, C.c_float, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_adaptive_levels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_refine_sublist_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
-            L.rr_render_adaptive_levels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_adaptive_levels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
-                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_render_adaptive_prefix") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
-            L.rr_render_pixel_prefix.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_pixel_prefix_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_adaptive_prefix.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_adaptive_prefix_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
-                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_denoise_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_denoise_default_params.argtypes = [C.POINTER(rr_denoise_params)]
-            L.rr_denoise_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-            L.rr_denoise_records_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_test_denoise_forms.argtypes = [C.c_uint32]
-            L.rr_test_denoise_forms.restype = None
-        if hasattr(L, "rr_accumulate_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_accumulate_default_params.argtypes = [C.POINTER(rr_accumulate_params)]
-            L.rr_accumulate_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 10
-            L.rr_accumulate_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 11
-        if hasattr(L, "rr_motion_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_motion_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_motion_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_surface_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_surface_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.rr_surface_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rr_albedo_pixels") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_albedo_pixels.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-            L.rr_albedo_pixels_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]
-        if hasattr(L, "rr_render_pixel_split") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the four)
-            L.rr_render_pixel_split.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_render_pixel_split_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_config), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rr_denoise_split_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params)] + [C.c_void_p] * 7
-            L.rr_denoise_split_records_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(rr_denoise_params)] + [C.c_void_p] * 8
-        if hasattr(L, "rr_accumulate_split_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_accumulate_split_records.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 16
-            L.rr_accumulate_split_records_device.argtypes = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params)] + [C.c_void_p] * 17
-        if hasattr(L, "rr_accumulate_clamped_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_history_clamp_default_params.argtypes = [C.POINTER(rr_history_clamp_params)]
-            clamped = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params), C.POINTER(rr_history_clamp_params)]
-            L.rr_accumulate_clamped_records.argtypes = clamped + [C.c_void_p] * 10
-            L.rr_accumulate_clamped_records_device.argtypes = clamped + [C.c_void_p] * 11
-        if hasattr(L, "rr_accumulate_clamped_split_records") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            clamped = [C.c_void_p, C.POINTER(rr_camera), C.POINTER(rr_accumulate_params), C.POINTER(rr_history_clamp_params)]
-            L.rr_accumulate_clamped_split_records.argtypes = clamped + [C.c_void_p] * 16
-            L.rr_accumulate_clamped_split_records_device.argtypes = clamped + [C.c_void_p] * 17
-        L.rr_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(rr_frame_stats)]
-        L.rr_scene_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-        if hasattr(L, "rr_scene_update_lights") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the three)
-            L.rr_scene_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-            L.rr_scene_update_item_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-            L.rr_scene_add_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-        if hasattr(L, "rr_scene_set_items") or not os.environ.get("RUSTRAY_HIP_LIB"):   # (a version-3 library may lack the two)
-            L.rr_scene_add_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-            L.rr_scene_set_items.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
-        L.rr_scene_set_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
-        L.rr_scene_get_tuning.argtypes = [C.c_void_p, C.POINTER(rr_tuning)]
-        L.rr_post_process.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.rr_post_process_device.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.rr_math_probe.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_uint64, C.c_int]
+        for name, (argtypes, restype) in SIGNATURES.items():
+            if developer and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)   # (the shipped library lacks none of them: AttributeError)
+            fn.argtypes, fn.restype = argtypes, restype
         _LIB = L
     return _LIB
 
@@ -913,6 +895,40 @@ class DeviceScene:
                                                      _ptr(diffuse_halves_ptr), _ptr(albedo_ptr), _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
 
     # -- temporal reprojection of a frame of records -----------------------------------
+    # The four calls in their two forms are ONE host body and ONE device body over ACCUMULATE_ROWS; the eight methods below are their
+    # signatures and docstrings, and hand their own arguments over by name (locals()), so no buffer is listed by position anywhere.
+    def _accumulate_call(self, split: bool, clamp, device: bool, cam, params, buffers):
+        """rr_accumulate[_clamped][_split]_records[_device]: the variant by (split, clamp: the clamped pair's C struct, else None, device);
+        `buffers`: what follows scene, camera, params and the clamp, in the order of accumulate_rows(split)."""
+        p = accumulate_params(params)
+        head = [self._h, C.byref(cam), C.byref(p)] + ([C.byref(clamp)] if clamp is not None else [])
+        _check(getattr(lib(), _accumulate_fn(split, clamp is not None, device))(*head, *buffers))
+
+    def _accumulate(self, split: bool, clamp, cam, arrays, params, rgba8: bool, in_place=()) -> dict:
+        """The host form.  arrays: the inputs by row name (None where the call has none), as contiguous float32 views of one pixel's shape
+        per row; in_place: the input rows accumulated into private copies, each then the output that names it as its key.  The other
+        outputs are made where their input is present, the length always, the bytes with rgba8 -> the result dict by the outputs' keys."""
+        n = int(cam.width) * int(cam.height)
+        rows, buf = accumulate_rows(split), {}
+        for r in rows:
+            if r.key is None:
+                a = arrays[r.name]
+                if a is not None:
+                    a = (np.array(a, np.float32, order="C") if r.name in in_place else np.ascontiguousarray(a, np.float32)).reshape((n,) + r.shape)
+                buf[r.name] = a
+            elif r.key in in_place:
+                buf[r.name] = buf[r.key]
+            else:
+                wanted = rgba8 if r.key == "rgba" else r.key == "length" or buf[r.key] is not None
+                buf[r.name] = np.zeros((n,) + r.shape, r.dtype) if wanted else None
+        self._accumulate_call(split, clamp, False, cam, params, [_data(buf[r.name]) for r in rows])
+        res = {r.key: buf[r.name] for r in rows if r.key is not None and (r.key != "rgba" or rgba8)}
+        return dict(records=res.pop("records"), length=res.pop("length"), **res)   # (the keys in the order they have always had)
+
+    def _accumulate_device(self, split: bool, clamp, cam, pointers, params, stream_ptr):
+        """The device form.  pointers: raw device pointers by row name + "_ptr" (None where the call has none), then the stream."""
+        self._accumulate_call(split, clamp, True, cam, params, [_ptr(pointers[r.name + "_ptr"]) for r in accumulate_rows(split)] + [_ptr(stream_ptr)])
+
     def accumulate_records(self, cam: rr_camera, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
                            rgba8: bool = False, in_place: bool = False) -> dict:
         """rr_accumulate_records: temporal.accumulate_records on the device, host arrays in and out.  records (n, 8) float32 rr_radiance
@@ -920,22 +936,7 @@ class DeviceScene:
         history_length (n,): the previous call's records, halves and length, or None on the first frame; motion (n, 3) or None; params: a
         temporal.AccumulateParams or None.  Returns dict(records (n, 8), length (n,), halves (n, 2, 8) or None [, rgba (n, 4) uint8]);
         in_place accumulates into copies of `records` and `halves` (out == records, halves_out == halves)."""
-        n = int(cam.width) * int(cam.height)
-        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
-        rec = np.array(records, np.float32, order="C").reshape(n, 8) if in_place else arr(records, (n, 8))
-        hv = None if halves is None else (np.array(halves, np.float32, order="C").reshape(n, 2, 8) if in_place else arr(halves, (n, 2, 8)))
-        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
-        out = rec if in_place else np.zeros((n, 8), np.float32)
-        out_h = None if hv is None else (hv if in_place else np.zeros((n, 2, 8), np.float32))
-        length = np.zeros(n, np.float32)
-        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
-        p = accumulate_params(params)
-        _check(lib().rr_accumulate_records(self._h, C.byref(cam), C.byref(p), _data(rec), _data(hv), _data(hist), _data(hist_h), _data(hist_l), _data(mv),
-                                           _data(out), _data(out_h), _data(length), _data(rgba)))
-        res = dict(records=out, length=length, halves=out_h)
-        if rgba8:
-            res["rgba"] = rgba
-        return res
+        return self._accumulate(False, None, cam, locals(), params, rgba8, ("records", "halves") if in_place else ())
 
     def accumulate_records_device(self, cam: rr_camera, records_ptr, halves_ptr, history_ptr, history_halves_ptr, history_length_ptr, motion_ptr, out_ptr,
                                   halves_out_ptr, length_out_ptr, rgba8_ptr=None, params=None, stream_ptr=None):
@@ -943,10 +944,7 @@ class DeviceScene:
         and halves_out_ptr halves_ptr), optionally twice as many half records each, width * height float32 of length in and out,
         width * height * 3 float32 of motion and width * height x 4 bytes, all raw device pointers (None where the call has none);
         enqueued on `stream_ptr`, not waited for."""
-        p = accumulate_params(params)
-        _check(lib().rr_accumulate_records_device(self._h, C.byref(cam), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
-                                                  _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr), _ptr(halves_out_ptr),
-                                                  _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
+        self._accumulate_device(False, None, cam, locals(), params, stream_ptr)
 
     def accumulate_split(self, cam: rr_camera, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
                          history_diffuse_halves=None, history_length=None, motion=None, params=None, rgba8: bool = False, in_place: bool = False) -> dict:
@@ -955,24 +953,7 @@ class DeviceScene:
         history_diffuse_halves (n, 2, 3): the previous call's diffuse and diffuse_halves.  Returns dict(records (n, 8), length (n,), halves
         (n, 2, 8) or None, diffuse (n, 3), diffuse_halves (n, 2, 3) or None [, rgba (n, 4) uint8]); in_place accumulates into copies of the
         four current arrays (every output is its input)."""
-        n = int(cam.width) * int(cam.height)
-        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
-        cur = lambda a, shape: None if a is None else (np.array(a, np.float32, order="C").reshape(shape) if in_place else arr(a, shape))
-        rec, hv, df, dh = cur(records, (n, 8)), cur(halves, (n, 2, 8)), cur(diffuse, (n, 3)), cur(diffuse_halves, (n, 2, 3))
-        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
-        hist_d, hist_dh = arr(history_diffuse, (n, 3)), arr(history_diffuse_halves, (n, 2, 3))
-        new = lambda a, shape: None if a is None else (a if in_place else np.zeros(shape, np.float32))
-        out, out_h, out_d, out_dh = new(rec, (n, 8)), new(hv, (n, 2, 8)), new(df, (n, 3)), new(dh, (n, 2, 3))
-        length = np.zeros(n, np.float32)
-        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
-        p = accumulate_params(params)
-        _check(lib().rr_accumulate_split_records(self._h, C.byref(cam), C.byref(p), _data(rec), _data(hv), _data(df), _data(dh), _data(hist), _data(hist_h),
-                                                 _data(hist_d), _data(hist_dh), _data(hist_l), _data(mv), _data(out), _data(out_h), _data(out_d), _data(out_dh),
-                                                 _data(length), _data(rgba)))
-        res = dict(records=out, length=length, halves=out_h, diffuse=out_d, diffuse_halves=out_dh)
-        if rgba8:
-            res["rgba"] = rgba
-        return res
+        return self._accumulate(True, None, cam, locals(), params, rgba8, ("records", "halves", "diffuse", "diffuse_halves") if in_place else ())
 
     def accumulate_split_device(self, cam: rr_camera, records_ptr, halves_ptr, diffuse_ptr, diffuse_halves_ptr, history_ptr, history_halves_ptr, history_diffuse_ptr,
                                 history_diffuse_halves_ptr, history_length_ptr, motion_ptr, out_ptr, halves_out_ptr, diffuse_out_ptr, diffuse_halves_out_ptr,
@@ -980,12 +961,7 @@ class DeviceScene:
         """rr_accumulate_split_records_device: the buffers of accumulate_records_device, plus width * height x 3 float32 of diffuse and
         twice as many of its halves, current, history and out (4-byte aligned; an output may be its current input), all raw device pointers
         (None where the call has none), in the order of the C arguments; enqueued on `stream_ptr`, not waited for."""
-        p = accumulate_params(params)
-        _check(lib().rr_accumulate_split_records_device(self._h, C.byref(cam), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(diffuse_ptr),
-                                                        _ptr(diffuse_halves_ptr), _ptr(history_ptr), _ptr(history_halves_ptr), _ptr(history_diffuse_ptr),
-                                                        _ptr(history_diffuse_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
-                                                        _ptr(halves_out_ptr), _ptr(diffuse_out_ptr), _ptr(diffuse_halves_out_ptr), _ptr(length_out_ptr),
-                                                        _ptr(rgba8_ptr), _ptr(stream_ptr)))
+        self._accumulate_device(True, None, cam, locals(), params, stream_ptr)
 
     def accumulate_clamped(self, cam: rr_camera, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
                            clamp=None, rgba8: bool = False, halves_in_place: bool = False) -> dict:
@@ -993,31 +969,13 @@ class DeviceScene:
         accumulate_records, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  Returns dict(records (n, 8), length
         (n,), halves (n, 2, 8) or None [, rgba (n, 4) uint8]); halves_in_place accumulates into a copy of `halves` (halves_out == halves;
         out can never be records)."""
-        n = int(cam.width) * int(cam.height)
-        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
-        rec = arr(records, (n, 8))
-        hv = None if halves is None else (np.array(halves, np.float32, order="C").reshape(n, 2, 8) if halves_in_place else arr(halves, (n, 2, 8)))
-        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
-        out = np.zeros((n, 8), np.float32)
-        out_h = None if hv is None else (hv if halves_in_place else np.zeros((n, 2, 8), np.float32))
-        length = np.zeros(n, np.float32)
-        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
-        p, c = accumulate_params(params), history_clamp_params(clamp)
-        _check(lib().rr_accumulate_clamped_records(self._h, C.byref(cam), C.byref(p), C.byref(c), _data(rec), _data(hv), _data(hist), _data(hist_h), _data(hist_l),
-                                                   _data(mv), _data(out), _data(out_h), _data(length), _data(rgba)))
-        res = dict(records=out, length=length, halves=out_h)
-        if rgba8:
-            res["rgba"] = rgba
-        return res
+        return self._accumulate(False, history_clamp_params(clamp), cam, locals(), params, rgba8, ("halves",) if halves_in_place else ())
 
     def accumulate_clamped_device(self, cam: rr_camera, records_ptr, halves_ptr, history_ptr, history_halves_ptr, history_length_ptr, motion_ptr, out_ptr,
                                   halves_out_ptr, length_out_ptr, rgba8_ptr=None, params=None, clamp=None, stream_ptr=None):
         """rr_accumulate_clamped_records_device: the buffers of accumulate_records_device (out_ptr may NOT be records_ptr; halves_out_ptr
         may be halves_ptr), all raw device pointers (None where the call has none); enqueued on `stream_ptr`, not waited for."""
-        p, c = accumulate_params(params), history_clamp_params(clamp)
-        _check(lib().rr_accumulate_clamped_records_device(self._h, C.byref(cam), C.byref(p), C.byref(c), _ptr(records_ptr), _ptr(halves_ptr), _ptr(history_ptr),
-                                                          _ptr(history_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
-                                                          _ptr(halves_out_ptr), _ptr(length_out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
+        self._accumulate_device(False, history_clamp_params(clamp), cam, locals(), params, stream_ptr)
 
     def accumulate_clamped_split(self, cam: rr_camera, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
                                  history_diffuse_halves=None, history_length=None, motion=None, params=None, clamp=None, rgba8: bool = False,
@@ -1025,24 +983,7 @@ class DeviceScene:
         """rr_accumulate_clamped_split_records: temporal.accumulate_clamped_split_records on the device, host arrays in and out.  The
         arguments of accumulate_split, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  Returns accumulate_split's
         dict; halves_in_place accumulates into copies of `halves` and `diffuse_halves` (out can never be records, diffuse_out never diffuse)."""
-        n = int(cam.width) * int(cam.height)
-        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)
-        cur = lambda a, shape: None if a is None else (np.array(a, np.float32, order="C").reshape(shape) if halves_in_place else arr(a, shape))
-        rec, hv, df, dh = arr(records, (n, 8)), cur(halves, (n, 2, 8)), arr(diffuse, (n, 3)), cur(diffuse_halves, (n, 2, 3))
-        hist, hist_h, hist_l, mv = arr(history, (n, 8)), arr(history_halves, (n, 2, 8)), arr(history_length, (n,)), arr(motion, (n, 3))
-        hist_d, hist_dh = arr(history_diffuse, (n, 3)), arr(history_diffuse_halves, (n, 2, 3))
-        new = lambda a, shape: None if a is None else (a if halves_in_place else np.zeros(shape, np.float32))
-        out, out_h, out_d, out_dh = np.zeros((n, 8), np.float32), new(hv, (n, 2, 8)), np.zeros((n, 3), np.float32), new(dh, (n, 2, 3))
-        length = np.zeros(n, np.float32)
-        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
-        p, c = accumulate_params(params), history_clamp_params(clamp)
-        _check(lib().rr_accumulate_clamped_split_records(self._h, C.byref(cam), C.byref(p), C.byref(c), _data(rec), _data(hv), _data(df), _data(dh), _data(hist),
-                                                         _data(hist_h), _data(hist_d), _data(hist_dh), _data(hist_l), _data(mv), _data(out), _data(out_h), _data(out_d),
-                                                         _data(out_dh), _data(length), _data(rgba)))
-        res = dict(records=out, length=length, halves=out_h, diffuse=out_d, diffuse_halves=out_dh)
-        if rgba8:
-            res["rgba"] = rgba
-        return res
+        return self._accumulate(True, history_clamp_params(clamp), cam, locals(), params, rgba8, ("halves", "diffuse_halves") if halves_in_place else ())
 
     def accumulate_clamped_split_device(self, cam: rr_camera, records_ptr, halves_ptr, diffuse_ptr, diffuse_halves_ptr, history_ptr, history_halves_ptr,
                                         history_diffuse_ptr, history_diffuse_halves_ptr, history_length_ptr, motion_ptr, out_ptr, halves_out_ptr, diffuse_out_ptr,
@@ -1050,12 +991,7 @@ class DeviceScene:
         """rr_accumulate_clamped_split_records_device: the buffers of accumulate_split_device (out_ptr may NOT be records_ptr and
         diffuse_out_ptr NOT diffuse_ptr; the two halves outputs may be their inputs), all raw device pointers (None where the call has none),
         in the order of the C arguments; enqueued on `stream_ptr`, not waited for."""
-        p, c = accumulate_params(params), history_clamp_params(clamp)
-        _check(lib().rr_accumulate_clamped_split_records_device(self._h, C.byref(cam), C.byref(p), C.byref(c), _ptr(records_ptr), _ptr(halves_ptr), _ptr(diffuse_ptr),
-                                                                _ptr(diffuse_halves_ptr), _ptr(history_ptr), _ptr(history_halves_ptr), _ptr(history_diffuse_ptr),
-                                                                _ptr(history_diffuse_halves_ptr), _ptr(history_length_ptr), _ptr(motion_ptr), _ptr(out_ptr),
-                                                                _ptr(halves_out_ptr), _ptr(diffuse_out_ptr), _ptr(diffuse_halves_out_ptr), _ptr(length_out_ptr),
-                                                                _ptr(rgba8_ptr), _ptr(stream_ptr)))
+        self._accumulate_device(True, history_clamp_params(clamp), cam, locals(), params, stream_ptr)
 
     # -- the motion of moved items per pixel -------------------------------------------
     @staticmethod
@@ -1121,26 +1057,22 @@ class DeviceScene:
 
     def set_compat(self, flags: int):
         """rr_scene_set_compat: behaviours of earlier reference binaries (1 = shadows attenuated by the occluder's alpha)."""
-        lib().rr_scene_set_compat.argtypes = [C.c_void_p, C.c_uint32]
         _check(lib().rr_scene_set_compat(self._h, C.c_uint32(flags)))
 
     def overlap_stages(self) -> int:
         """rr_scene_overlap_stages: level-1 stages of the last frame whose shade and shadow launches ran on two streams (0 = serial)."""
         n = C.c_uint32(0)
-        lib().rr_scene_overlap_stages.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _check(lib().rr_scene_overlap_stages(self._h, C.byref(n)))
         return n.value
 
     def schedule_record(self, on: bool = True):
         """rr_test_schedule_record (rr_api_schedule_probe.h, a test entry point outside include/rustray_hip.h): empty the handle's schedule log and
         record what every frame call enqueues from now on (False: stop)."""
-        lib().rr_test_schedule_record.argtypes = [C.c_void_p, C.c_int]
         _check(lib().rr_test_schedule_record(self._h, 1 if on else 0))
 
     def schedule_log(self) -> str:
         """rr_test_schedule_read: the log as text, one operation per line in host order (tests/launch_order.py parses and checks it)."""
         L = lib()
-        L.rr_test_schedule_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         need = C.c_uint64(0)
         _check(L.rr_test_schedule_read(self._h, None, 0, C.byref(need)))
         buf = C.create_string_buffer(need.value)
@@ -1181,11 +1113,8 @@ def deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, packs_ptr
     so = (C.c_uint64 * 4)(*[int(v) for v in section_offset])
     eb = (C.c_uint32 * 4)(*[int(v) for v in elem_bytes])
     dp = (C.c_void_p * 4)(*[C.c_void_p(int(v)) if v else None for v in dst_ptrs])
-    L = lib()
-    L.rr_deinterleave_packed_device.argtypes = [C.c_uint32] * 5 + [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
-                                                C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
-    _check(L.rr_deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, C.c_void_p(packs_ptr), C.c_uint64(pack_stride), so, eb, dp,
-                                           device, _ptr(stream_ptr)))
+    _check(lib().rr_deinterleave_packed_device(width, height, tile_w, tile_h, n_ranks, C.c_void_p(packs_ptr), C.c_uint64(pack_stride), so, eb, dp,
+                                               device, _ptr(stream_ptr)))
 
 
 def post_process(rgba: np.ndarray, normal, object_id, cavity: bool, outline: bool, device: int = 0) -> np.ndarray:

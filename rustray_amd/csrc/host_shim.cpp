@@ -431,6 +431,33 @@ extern "C" int rh_render_denoised_diffuse(void* h, float fov, const float* eye, 
     if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
     return 0;
 }
+// The history the four rh_accumulate* calls hand to Raytracing::accumulate*, from raw pointers of n pixels: empty without `history`
+// (the first frame), a layer empty where its pointer is NULL.  The calls that are not split pass NULL for the two diffuse layers.
+static Raytracing::SplitHistory rh_history(size_t n, const rr_radiance* history, const rr_radiance* history_halves, const float* history_diffuse,
+                                           const float* history_diffuse_halves, const float* history_length) {
+    Raytracing::SplitHistory hist;
+    if (history) {
+        hist.records.assign(history, history + n);
+        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
+        if (history_diffuse) hist.diffuse.assign(history_diffuse, history_diffuse + 3 * n);
+        if (history_diffuse_halves) hist.diffuse_halves.assign(history_diffuse_halves, history_diffuse_halves + 6 * n);
+        if (history_length) hist.length.assign(history_length, history_length + n);
+    }
+    return hist;
+}
+// What such a call returned, copied out: 0, or -1 for an empty result (refused).  `layers`: the result as a SplitHistory, whose diffuse
+// layers go to diffuse_out and diffuse_halves_out, or NULL for the calls that are not split.
+static int rh_history_out(size_t n, const Raytracing::History& r, const Raytracing::SplitHistory* layers, const std::vector<uint8_t>& bytes, rr_radiance* out,
+                          rr_radiance* halves_out, float* diffuse_out, float* diffuse_halves_out, float* length_out, uint8_t* rgba8) {
+    if (r.empty()) return -1;
+    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
+    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
+    if (layers) std::memcpy(diffuse_out, layers->diffuse.data(), 3 * n * 4);
+    if (layers && diffuse_halves_out && !layers->diffuse_halves.empty()) std::memcpy(diffuse_halves_out, layers->diffuse_halves.data(), 6 * n * 4);
+    std::memcpy(length_out, r.length.data(), n * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
 // Raytracing::accumulate: records = w * h, halves = w * h * 2 or NULL, history / history_halves / history_length = the previous call's
 // out / halves_out / length_out or all NULL (the first frame), params or NULL for the defaults, motion = w * h * 3 floats or NULL; out,
 // halves_out (with halves), length_out, rgba8 or NULL; returns 0, or -1 when the call was refused.
@@ -441,20 +468,10 @@ extern "C" int rh_accumulate_records(void* h, float fov, const float* eye, const
                                      rr_radiance* out, rr_radiance* halves_out, float* length_out, uint8_t* rgba8) {
     const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
     const size_t n = (size_t)w * hgt;
-    Raytracing::History hist;
-    if (history) {
-        hist.records.assign(history, history + n);
-        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
-        if (history_length) hist.length.assign(history_length, history_length + n);
-    }
+    const Raytracing::SplitHistory hist = rh_history(n, history, history_halves, nullptr, nullptr, history_length);
     std::vector<uint8_t> bytes;
     const Raytracing::History r = rt.accumulate(records, halves, history ? &hist : nullptr, params, motion, rgba8 ? &bytes : nullptr);
-    if (r.empty()) return -1;
-    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
-    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
-    std::memcpy(length_out, r.length.data(), n * 4);
-    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
-    return 0;
+    return rh_history_out(n, r, nullptr, bytes, out, halves_out, nullptr, nullptr, length_out, rgba8);
 }
 extern "C" int rh_accumulate_records_device(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
                                             uint32_t w, uint32_t hgt, const rr_accumulate_params* params, const rr_radiance* records_dev, const rr_radiance* halves_dev,
@@ -478,24 +495,10 @@ extern "C" int rh_accumulate_split(void* h, float fov, const float* eye, const f
         return rt.accumulate_split_device(*params, records, halves, diffuse, diffuse_halves, history, history_halves, history_diffuse, history_diffuse_halves,
                                           history_length, motion, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8, stream);
     const size_t n = (size_t)w * hgt;
-    Raytracing::SplitHistory hist;
-    if (history) {
-        hist.records.assign(history, history + n);
-        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
-        if (history_diffuse) hist.diffuse.assign(history_diffuse, history_diffuse + 3 * n);
-        if (history_diffuse_halves) hist.diffuse_halves.assign(history_diffuse_halves, history_diffuse_halves + 6 * n);
-        if (history_length) hist.length.assign(history_length, history_length + n);
-    }
+    const Raytracing::SplitHistory hist = rh_history(n, history, history_halves, history_diffuse, history_diffuse_halves, history_length);
     std::vector<uint8_t> bytes;
     const Raytracing::SplitHistory r = rt.accumulate_split(records, halves, diffuse, diffuse_halves, history ? &hist : nullptr, params, motion, rgba8 ? &bytes : nullptr);
-    if (r.empty()) return -1;
-    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
-    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
-    std::memcpy(diffuse_out, r.diffuse.data(), 3 * n * 4);
-    if (diffuse_halves_out && !r.diffuse_halves.empty()) std::memcpy(diffuse_halves_out, r.diffuse_halves.data(), 6 * n * 4);
-    std::memcpy(length_out, r.length.data(), n * 4);
-    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
-    return 0;
+    return rh_history_out(n, r, &r, bytes, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8);
 }
 // Raytracing::accumulate_clamped (on_device == 0: host pointers, through a History; returns 0, or -1 when the call was refused) and
 // Raytracing::accumulate_clamped_device (on_device != 0: device pointers and `stream`; returns its rr_status): radius and sigma_scale, then
@@ -510,20 +513,10 @@ extern "C" int rh_accumulate_clamped(void* h, float fov, const float* eye, const
     if (on_device)
         return rt.accumulate_clamped_device(*params, clamp, records, halves, history, history_halves, history_length, motion, out, halves_out, length_out, rgba8, stream);
     const size_t n = (size_t)w * hgt;
-    Raytracing::History hist;
-    if (history) {
-        hist.records.assign(history, history + n);
-        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
-        if (history_length) hist.length.assign(history_length, history_length + n);
-    }
+    const Raytracing::SplitHistory hist = rh_history(n, history, history_halves, nullptr, nullptr, history_length);
     std::vector<uint8_t> bytes;
     const Raytracing::History r = rt.accumulate_clamped(clamp, records, halves, history ? &hist : nullptr, params, motion, rgba8 ? &bytes : nullptr);
-    if (r.empty()) return -1;
-    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
-    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
-    std::memcpy(length_out, r.length.data(), n * 4);
-    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
-    return 0;
+    return rh_history_out(n, r, nullptr, bytes, out, halves_out, nullptr, nullptr, length_out, rgba8);
 }
 // Raytracing::accumulate_clamped_split (on_device == 0: host pointers, through a SplitHistory; returns 0, or -1 when the call was refused)
 // and Raytracing::accumulate_clamped_split_device (on_device != 0: device pointers and `stream`; returns its rr_status): radius and
@@ -542,25 +535,11 @@ extern "C" int rh_accumulate_clamped_split(void* h, float fov, const float* eye,
                                                   history_diffuse_halves, history_length, motion, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8,
                                                   stream);
     const size_t n = (size_t)w * hgt;
-    Raytracing::SplitHistory hist;
-    if (history) {
-        hist.records.assign(history, history + n);
-        if (history_halves) hist.halves.assign(history_halves, history_halves + 2 * n);
-        if (history_diffuse) hist.diffuse.assign(history_diffuse, history_diffuse + 3 * n);
-        if (history_diffuse_halves) hist.diffuse_halves.assign(history_diffuse_halves, history_diffuse_halves + 6 * n);
-        if (history_length) hist.length.assign(history_length, history_length + n);
-    }
+    const Raytracing::SplitHistory hist = rh_history(n, history, history_halves, history_diffuse, history_diffuse_halves, history_length);
     std::vector<uint8_t> bytes;
     const Raytracing::SplitHistory r = rt.accumulate_clamped_split(clamp, records, halves, diffuse, diffuse_halves, history ? &hist : nullptr, params, motion,
                                                                    rgba8 ? &bytes : nullptr);
-    if (r.empty()) return -1;
-    std::memcpy(out, r.records.data(), n * sizeof(rr_radiance));
-    if (halves_out && !r.halves.empty()) std::memcpy(halves_out, r.halves.data(), 2 * n * sizeof(rr_radiance));
-    std::memcpy(diffuse_out, r.diffuse.data(), 3 * n * 4);
-    if (diffuse_halves_out && !r.diffuse_halves.empty()) std::memcpy(diffuse_halves_out, r.diffuse_halves.data(), 6 * n * 4);
-    std::memcpy(length_out, r.length.data(), n * 4);
-    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
-    return 0;
+    return rh_history_out(n, r, &r, bytes, out, halves_out, diffuse_out, diffuse_halves_out, length_out, rgba8);
 }
 // Raytracing::motion: records = w * h, item_index = n_moved indices, prev_trans = n_moved * 16 floats (column-major); motion_out = w * h * 3
 // floats, world_out the same or NULL; returns 0, or -1 when the call was refused.

@@ -271,12 +271,17 @@ class Raytracing:
         render_temporal_split, a pipeline of its own.  clamp: None or False is rr_accumulate_records; True (the library's defaults) or a
         temporal.HistoryClampParams puts rr_accumulate_clamped_records in its place, which holds the history to the current frame's colours
         around each pixel: for frames after an edit of lights, materials, textures or item flags, and under moving shadows."""
-        from .temporal import previous_view
         _check_albedo_mode(albedo, temporal=True)
-        clamp = _clamp_params(clamp)         # (refused before the state notes this frame's items)
+        return self._render_temporal(render_temporal_torch, state, samples, denoise_params, accumulate_params, seed, motion, sample_xy, rgba8, track_items,
+                                     albedo=albedo, clamp=_clamp_params(clamp))
+
+    def _render_temporal(self, pipeline, state: "TemporalState", samples, denoise_params, accumulate_params, seed, motion, sample_xy, rgba8, track_items, **kw):
+        """What the three render_temporal* methods share, behind their refusals (so a refused call leaves the state as it was): the frame's
+        config and the moved items, then `pipeline`, the method's render_temporal*_torch, on this scene and camera with this camera's view."""
+        from .temporal import previous_view
         cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
-        return render_temporal_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                     sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, albedo=albedo, clamp=clamp)
+        return pipeline(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion, sample_xy=sample_xy, rgba8=rgba8,
+                        view=previous_view(self.camera), moved=moved, **kw)
 
     def _temporal_frame(self, state: "TemporalState", samples, seed, motion, track_items: bool):
         """What render_temporal and render_temporal_split do before their pipeline: the frame's config, and with track_items the moved items
@@ -307,11 +312,8 @@ class Raytracing:
         The result holds torch tensors: render_temporal's, and diffuse, diffuse_halves, accumulated_diffuse, accumulated_diffuse_halves and
         albedo.  clamp: anything but None or False raises ValueError that names render_temporal_split_clamped, the pipeline with the clamped
         accumulation."""
-        from .temporal import previous_view
         _no_split_clamp(clamp)
-        cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
-        return render_temporal_split_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                           sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved)
+        return self._render_temporal(render_temporal_split_torch, state, samples, denoise_params, accumulate_params, seed, motion, sample_xy, rgba8, track_items)
 
     def render_temporal_split_clamped(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None,
                                       seed: Optional[int] = None, motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, clamp=True) -> dict:
@@ -321,13 +323,12 @@ class Raytracing:
         frames after an edit of lights, materials, textures or item flags, and under moving shadows; a state may go from one of the two
         pipelines to the other from frame to frame.  clamp: True (the library's defaults) or a temporal.HistoryClampParams; None or False
         raises ValueError.  The other arguments and the result are render_temporal_split's."""
-        from .temporal import previous_view
         clamp = _clamp_params(clamp)         # (refused before the state notes this frame's items)
         if clamp is None:
             raise ValueError("clamp is True (the defaults) or a temporal.HistoryClampParams; without a clamp the pipeline is render_temporal_split")
-        cfg, moved = self._temporal_frame(state, samples, seed, motion, track_items)
-        return render_temporal_split_clamped_torch(self.device_scene, self.camera.c_struct(), cfg, state, accumulate_params, denoise_params, motion=motion,
-                                                   sample_xy=sample_xy, rgba8=rgba8, view=previous_view(self.camera), moved=moved, clamp=clamp)
+        return self._render_temporal(render_temporal_split_clamped_torch, state, samples, denoise_params, accumulate_params, seed, motion, sample_xy, rgba8, track_items,
+                                     clamp=clamp)
+
 
     def render_adaptive(self, base_samples: int, max_samples: int, threshold: float, sample_xy_base=None, sample_xy_max=None) -> dict:
         """Two sample counts in one frame: every pixel at `base_samples`, and at `max_samples` where the half-buffer estimate of the
@@ -1273,6 +1274,36 @@ class TemporalState:
         self.view, self.frames = view, self.frames + 1
 
 
+def _accumulate_torch(device_scene: capi.DeviceScene, split: bool, clamped: bool, cam, tensors, params, clamp, rgba8: bool, in_place: bool, out) -> dict:
+    """The four accumulate*_torch functions, over the rows of capi.ACCUMULATE_ROWS the call has: `tensors` holds the inputs by row name
+    (the caller's own arguments), checked by _frame_tensors; an output is its input (in_place), the tensor of its key in `out`, or fresh,
+    and None where its input is; the call is the binding's one device body on torch's current stream."""
+    import torch
+    n = int(cam.width) * int(cam.height)
+    rows = capi.accumulate_rows(split)
+    t = _frame_tensors(device_scene, cam.width, cam.height, {r.name: (tensors[r.name], r.shape) for r in rows if r.key is None},
+                       required=("records", "diffuse") if split else ())
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        for r in (r for r in rows if r.key is not None):
+            fresh = lambda: torch.empty((n,) + r.shape, dtype=torch.uint8 if r.dtype is np.uint8 else torch.float32, device=dev)   # (at least 512-byte aligned)
+            if r.key == "rgba":
+                t[r.name] = fresh() if rgba8 else None
+            elif r.key == "length":
+                t[r.name] = out["length"] if out is not None else fresh()
+            elif in_place or t[r.key] is None:
+                t[r.name] = t[r.key]
+            else:
+                t[r.name] = out[r.key] if out is not None else fresh()
+        device_scene._accumulate_device(split, capi.history_clamp_params(clamp) if clamped else None, cam,
+                                        {r.name + "_ptr": t[r.name].data_ptr() if t[r.name] is not None else None for r in rows}, params,
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    result = dict(_record_views(t["out"]), **{r.key: t[r.name] for r in rows if r.key not in (None, "records", "rgba")})
+    if rgba8:
+        result["rgba"] = t["rgba8"]
+    return result
+
+
 def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, history=None, history_halves=None, history_length=None, motion=None, params=None,
                      rgba8: bool = False, in_place: bool = False, out: Optional[dict] = None) -> dict:
     """rr_accumulate_records_device on torch's current stream of the scene's device: `records` (n, 8), `halves` (n, 2, 8) or None, `history`
@@ -1280,29 +1311,7 @@ def accumulate_torch(device_scene: capi.DeviceScene, cam, records, halves=None, 
     float32 CUDA tensors on that device, n = cam.width * cam.height (anything else raises); params: a temporal.AccumulateParams.  Returns
     torch tensors, without a host copy and without a synchronisation: dict(records (n, 8) and its views, halves (n, 2, 8) or None, length
     (n,) [, rgba (n, 4) uint8]).  in_place: written over `records` and `halves`; out: dict(records, halves, length) of tensors to write."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)),
-                                                                  history_halves=(history_halves, (2, 8)), history_length=(history_length, ()),
-                                                                  motion=(motion, (3,))))
-    dev = torch.device("cuda", device_scene.device)
-    ptr = lambda x: x.data_ptr() if x is not None else None
-    with torch.cuda.device(dev):
-        if in_place:
-            res, res_h = t["records"], t["halves"]
-        elif out is not None:
-            res, res_h = out["records"], out["halves"] if t["halves"] is not None else None
-        else:
-            res = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
-            res_h = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if t["halves"] is not None else None
-        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        device_scene.accumulate_records_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["history"]), ptr(t["history_halves"]), ptr(t["history_length"]),
-                                               ptr(t["motion"]), ptr(res), ptr(res_h), ptr(length), ptr(rgba), params, torch.cuda.current_stream(dev).cuda_stream)
-    result = dict(_record_views(res), halves=res_h, length=length)
-    if rgba8:
-        result["rgba"] = rgba
-    return result
+    return _accumulate_torch(device_scene, False, False, cam, locals(), params, None, rgba8, in_place, out)
 
 
 def _clamp_params(clamp):
@@ -1332,28 +1341,7 @@ def accumulate_clamped_torch(device_scene: capi.DeviceScene, cam, records, halve
     """rr_accumulate_clamped_records_device on torch's current stream of the scene's device: the tensors and the result of accumulate_torch,
     and clamp: a temporal.HistoryClampParams or None (the library's defaults).  There is no in_place: `out` may not be `records`, whose
     neighbours the window reads.  out: dict(records, halves, length) of tensors to write."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), history=(history, (8,)),
-                                                                  history_halves=(history_halves, (2, 8)), history_length=(history_length, ()),
-                                                                  motion=(motion, (3,))))
-    dev = torch.device("cuda", device_scene.device)
-    ptr = lambda x: x.data_ptr() if x is not None else None
-    with torch.cuda.device(dev):
-        if out is not None:
-            res, res_h = out["records"], out["halves"] if t["halves"] is not None else None
-        else:
-            res = torch.empty((n, 8), dtype=torch.float32, device=dev)
-            res_h = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if t["halves"] is not None else None
-        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        device_scene.accumulate_clamped_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["history"]), ptr(t["history_halves"]), ptr(t["history_length"]),
-                                               ptr(t["motion"]), ptr(res), ptr(res_h), ptr(length), ptr(rgba), params, clamp,
-                                               torch.cuda.current_stream(dev).cuda_stream)
-    result = dict(_record_views(res), halves=res_h, length=length)
-    if rgba8:
-        result["rgba"] = rgba
-    return result
+    return _accumulate_torch(device_scene, False, True, cam, locals(), params, clamp, rgba8, False, out)
 
 
 def accumulate_split_torch(device_scene: capi.DeviceScene, cam, records, halves, diffuse, diffuse_halves, history=None, history_halves=None, history_diffuse=None,
@@ -1364,34 +1352,7 @@ def accumulate_split_torch(device_scene: capi.DeviceScene, cam, records, halves,
     the previous call's.  Returns torch tensors, without a host copy and without a synchronisation: the dict of accumulate_torch plus
     diffuse (n, 3) and diffuse_halves (n, 2, 3) or None.  in_place: written over the four current tensors; out: dict(records, halves,
     diffuse, diffuse_halves, length) of tensors to write."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), diffuse=(diffuse, (3,)),
-                                                                  diffuse_halves=(diffuse_halves, (2, 3)), history=(history, (8,)),
-                                                                  history_halves=(history_halves, (2, 8)), history_diffuse=(history_diffuse, (3,)),
-                                                                  history_diffuse_halves=(history_diffuse_halves, (2, 3)), history_length=(history_length, ()),
-                                                                  motion=(motion, (3,))), required=("records", "diffuse"))
-    dev = torch.device("cuda", device_scene.device)
-    ptr = lambda x: x.data_ptr() if x is not None else None
-    current = ("records", "halves", "diffuse", "diffuse_halves")
-    shapes = dict(records=(n, 8), halves=(n, 2, 8), diffuse=(n, 3), diffuse_halves=(n, 2, 3))
-    with torch.cuda.device(dev):
-        if in_place:
-            res = {k: t[k] for k in current}
-        elif out is not None:
-            res = {k: out[k] if t[k] is not None else None for k in current}
-        else:
-            res = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) if t[k] is not None else None for k in current}
-        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        device_scene.accumulate_split_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["diffuse"]), ptr(t["diffuse_halves"]), ptr(t["history"]),
-                                             ptr(t["history_halves"]), ptr(t["history_diffuse"]), ptr(t["history_diffuse_halves"]), ptr(t["history_length"]),
-                                             ptr(t["motion"]), ptr(res["records"]), ptr(res["halves"]), ptr(res["diffuse"]), ptr(res["diffuse_halves"]), ptr(length),
-                                             ptr(rgba), params, torch.cuda.current_stream(dev).cuda_stream)
-    result = dict(_record_views(res["records"]), halves=res["halves"], diffuse=res["diffuse"], diffuse_halves=res["diffuse_halves"], length=length)
-    if rgba8:
-        result["rgba"] = rgba
-    return result
+    return _accumulate_torch(device_scene, True, False, cam, locals(), params, None, rgba8, in_place, out)
 
 
 def accumulate_clamped_split_torch(device_scene: capi.DeviceScene, cam, records, halves, diffuse, diffuse_halves, history=None, history_halves=None,
@@ -1401,32 +1362,7 @@ def accumulate_clamped_split_torch(device_scene: capi.DeviceScene, cam, records,
     accumulate_split_torch, and clamp: a temporal.HistoryClampParams or None (the library's defaults).  There is no in_place: `out` may not
     be `records` and `diffuse_out` not `diffuse`, whose neighbours the windows read.  out: dict(records, halves, diffuse, diffuse_halves,
     length) of tensors to write."""
-    import torch
-    n = int(cam.width) * int(cam.height)
-    t = _frame_tensors(device_scene, cam.width, cam.height, dict(records=(records, (8,)), halves=(halves, (2, 8)), diffuse=(diffuse, (3,)),
-                                                                  diffuse_halves=(diffuse_halves, (2, 3)), history=(history, (8,)),
-                                                                  history_halves=(history_halves, (2, 8)), history_diffuse=(history_diffuse, (3,)),
-                                                                  history_diffuse_halves=(history_diffuse_halves, (2, 3)), history_length=(history_length, ()),
-                                                                  motion=(motion, (3,))), required=("records", "diffuse"))
-    dev = torch.device("cuda", device_scene.device)
-    ptr = lambda x: x.data_ptr() if x is not None else None
-    current = ("records", "halves", "diffuse", "diffuse_halves")
-    shapes = dict(records=(n, 8), halves=(n, 2, 8), diffuse=(n, 3), diffuse_halves=(n, 2, 3))
-    with torch.cuda.device(dev):
-        if out is not None:
-            res = {k: out[k] if t[k] is not None else None for k in current}
-        else:
-            res = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) if t[k] is not None else None for k in current}
-        length = out["length"] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
-        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
-        device_scene.accumulate_clamped_split_device(cam, ptr(t["records"]), ptr(t["halves"]), ptr(t["diffuse"]), ptr(t["diffuse_halves"]), ptr(t["history"]),
-                                                     ptr(t["history_halves"]), ptr(t["history_diffuse"]), ptr(t["history_diffuse_halves"]),
-                                                     ptr(t["history_length"]), ptr(t["motion"]), ptr(res["records"]), ptr(res["halves"]), ptr(res["diffuse"]),
-                                                     ptr(res["diffuse_halves"]), ptr(length), ptr(rgba), params, clamp, torch.cuda.current_stream(dev).cuda_stream)
-    result = dict(_record_views(res["records"]), halves=res["halves"], diffuse=res["diffuse"], diffuse_halves=res["diffuse_halves"], length=length)
-    if rgba8:
-        result["rgba"] = rgba
-    return result
+    return _accumulate_torch(device_scene, True, True, cam, locals(), params, clamp, rgba8, False, out)
 
 
 def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_trans, world: bool = False) -> dict:
@@ -1446,6 +1382,54 @@ def motion_torch(device_scene: capi.DeviceScene, cam, records, item_index, prev_
     return dict(motion=motion, world=wout)
 
 
+def _temporal_frame_torch(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, split: bool, clamp, albedo=False) -> dict:
+    """The frame of the three render_temporal*_torch functions, their refusals behind it: the frame's own records, the history check, with
+    moved items the motion, the accumulation into the state's other set, the guide, the filter -- in that order on torch's current stream.
+    split: the arm with the diffuse layers (its producer, a history with a diffuse set, the mean albedo as the guide, the split filter);
+    clamp: None, or the checked clamp of the clamped accumulation; albedo: the guide of the plain arm."""
+    import dataclasses
+    import torch
+    from .temporal import AccumulateParams, previous_view
+    if moved is not None and motion is not None:
+        raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
+    if split:
+        base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)
+    else:
+        base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
+    n = int(cam.width) * int(cam.height)
+    hist = state.history()
+    if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None or (split and hist.get("diffuse") is None)):
+        items = state.items
+        state.reset()
+        state.items = items      # (the items noted for this frame are those of the history it becomes)
+        hist = None
+    prm = dataclasses.replace(params) if params is not None else AccumulateParams()
+    if hist is not None:
+        prm.prev_world_to_clip, prm.prev_eye = state.view
+    target = state.target(n, True, torch.device("cuda", device_scene.device), diffuse=split)
+    if moved is not None and hist is not None and len(moved[0]):
+        motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
+    h = lambda k: hist.get(k) if hist else None
+    acc = _accumulate_torch(device_scene, split, clamp is not None, cam,
+                            dict(records=base["records"], halves=base["part_records"], diffuse=base.get("diffuse"), diffuse_halves=base.get("diffuse_halves"),
+                                 history=h("records"), history_halves=h("halves"), history_diffuse=h("diffuse"), history_diffuse_halves=h("diffuse_halves"),
+                                 history_length=h("length"), motion=motion), prm, clamp, False, False, target)
+    res = dict(noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"], motion=motion)
+    if split:
+        guide = albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
+        out = denoise_split_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["diffuse"], acc["halves"], acc["diffuse_halves"], guide,
+                                  denoise_params, rgba8=rgba8)
+        res.update(diffuse=base["diffuse"], diffuse_halves=base["diffuse_halves"], accumulated_diffuse=acc["diffuse"],
+                   accumulated_diffuse_halves=acc["diffuse_halves"], albedo=guide)
+    else:
+        guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
+        out = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], guide, denoise_params, rgba8=rgba8)
+        if albedo:
+            res["albedo"] = guide
+    state.advance(target, view if view is not None else previous_view(cam))
+    return dict(out, **res)
+
+
 def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
                           sample_xy=None, rgba8: bool = False, view=None, moved=None, albedo=False, clamp=None) -> dict:
     """One frame of a frame-after-frame loop on the device, with no host trip: rr_render_pixel_parts_device at n_parts = 2 (cfg.samples
@@ -1462,41 +1446,9 @@ def render_temporal_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, s
     rr_albedo_pixels_device with the frame's config and table in its place.  albedo="diffuse" raises ValueError: the diffuse part is
     accumulated over time by render_temporal_split_torch.  clamp: None or False is rr_accumulate_records_device; True (the library's defaults) or a
     temporal.HistoryClampParams puts rr_accumulate_clamped_records_device in its place, on the same stream and the same buffers."""
-    import dataclasses
-    import torch
-    from .temporal import AccumulateParams, previous_view
     _check_albedo_mode(albedo, temporal=True)
     clamp = _clamp_params(clamp)         # (refused before anything is rendered)
-    if moved is not None and motion is not None:
-        raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
-    base = render_pixel_parts_torch(device_scene, cam, cfg, None, 2, sample_xy=sample_xy)
-    n = int(cam.width) * int(cam.height)
-    hist = state.history()
-    if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None):
-        items = state.items
-        state.reset()
-        state.items = items      # (the items noted for this frame are those of the history it becomes)
-        hist = None
-    prm = dataclasses.replace(params) if params is not None else AccumulateParams()
-    if hist is not None:
-        prm.prev_world_to_clip, prm.prev_eye = state.view
-    target = state.target(n, True, torch.device("cuda", device_scene.device))
-    if moved is not None and hist is not None and len(moved[0]):
-        motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
-    if clamp is None:
-        acc = accumulate_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None, hist["halves"] if hist else None,
-                               hist["length"] if hist else None, motion, prm, out=target)
-    else:
-        acc = accumulate_clamped_torch(device_scene, cam, base["records"], base["part_records"], hist["records"] if hist else None,
-                                       hist["halves"] if hist else None, hist["length"] if hist else None, motion, prm, clamp, out=target)
-    guide = _albedo_guide_torch(device_scene, cam, cfg, sample_xy, albedo)
-    res = denoise_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["halves"], guide, denoise_params, rgba8=rgba8)
-    state.advance(target, view if view is not None else previous_view(cam))
-    res = dict(res, noisy=base["records"], halves=base["part_records"], accumulated=acc["records"], accumulated_halves=acc["halves"], length=acc["length"],
-               motion=motion)
-    if albedo:
-        res["albedo"] = guide
-    return res
+    return _temporal_frame_torch(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, False, clamp, albedo)
 
 
 def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
@@ -1511,12 +1463,12 @@ def render_temporal_split_torch(device_scene: capi.DeviceScene, cam, cfg: rr_con
     albedo (n, 3).  clamp: anything but None or False raises ValueError that names render_temporal_split_clamped_torch, the pipeline with
     the clamped accumulation."""
     _no_split_clamp(clamp)
-    return _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, None)
+    return _temporal_frame_torch(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, True, None)
 
 
 def render_temporal_split_clamped_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, state: TemporalState, params=None, denoise_params=None, motion=None,
                                         sample_xy=None, rgba8: bool = False, view=None, moved=None, clamp=True) -> dict:
-    """render_temporal_split_torch with rr_accumulate_clamped_split_records_device in the place of rr_accumulate_split_records_device, on
+    """render_temporal_split_torch with the call of accumulate_clamped_split_torch in the place of rr_accumulate_split_records_device, on
     the same stream, the same buffers and the state's same diffuse sets: the split frame, with moved items the motion, the clamped split
     accumulation, the mean albedo, the split filter, with no host trip.  For the frames after an edit of lights, materials, textures or
     item flags, and under moving shadows.  clamp: True (the library's defaults) or a temporal.HistoryClampParams; None or False is a
@@ -1524,41 +1476,4 @@ def render_temporal_split_clamped_torch(device_scene: capi.DeviceScene, cam, cfg
     clamp = _clamp_params(clamp)         # (refused before anything is rendered)
     if clamp is None:
         raise ValueError("clamp is True (the defaults) or a temporal.HistoryClampParams; without a clamp the pipeline is render_temporal_split_torch")
-    return _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, clamp)
-
-
-def _temporal_split_frame(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, clamp) -> dict:
-    """The frame of render_temporal_split_torch (clamp None) and of render_temporal_split_clamped_torch (a checked clamp)."""
-    import dataclasses
-    import torch
-    from .temporal import AccumulateParams, previous_view
-    if moved is not None and motion is not None:
-        raise ValueError("give `moved` (the motion is made on the device) or `motion`, not both")
-    base = render_pixel_split_torch(device_scene, cam, cfg, None, True, sample_xy=sample_xy)
-    n = int(cam.width) * int(cam.height)
-    hist = state.history()
-    if hist is not None and (int(hist["records"].shape[0]) != n or hist["halves"] is None or hist.get("diffuse") is None):
-        items = state.items
-        state.reset()
-        state.items = items      # (the items noted for this frame are those of the history it becomes)
-        hist = None
-    prm = dataclasses.replace(params) if params is not None else AccumulateParams()
-    if hist is not None:
-        prm.prev_world_to_clip, prm.prev_eye = state.view
-    target = state.target(n, True, torch.device("cuda", device_scene.device), diffuse=True)
-    if moved is not None and hist is not None and len(moved[0]):
-        motion = motion_torch(device_scene, cam, base["records"], moved[0], moved[1])["motion"]
-    h = lambda k: hist[k] if hist else None
-    if clamp is None:
-        acc = accumulate_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"), h("halves"),
-                                     h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, out=target)
-    else:
-        acc = accumulate_clamped_split_torch(device_scene, cam, base["records"], base["part_records"], base["diffuse"], base["diffuse_halves"], h("records"),
-                                             h("halves"), h("diffuse"), h("diffuse_halves"), h("length"), motion, prm, clamp, out=target)
-    guide = albedo_pixels_torch(device_scene, cam, cfg, None, sample_xy=sample_xy)
-    res = denoise_split_torch(device_scene, int(cam.width), int(cam.height), acc["records"], acc["diffuse"], acc["halves"], acc["diffuse_halves"], guide,
-                              denoise_params, rgba8=rgba8)
-    state.advance(target, view if view is not None else previous_view(cam))
-    return dict(res, noisy=base["records"], halves=base["part_records"], diffuse=base["diffuse"], diffuse_halves=base["diffuse_halves"],
-                accumulated=acc["records"], accumulated_halves=acc["halves"], accumulated_diffuse=acc["diffuse"],
-                accumulated_diffuse_halves=acc["diffuse_halves"], length=acc["length"], motion=motion, albedo=guide)
+    return _temporal_frame_torch(device_scene, cam, cfg, state, params, denoise_params, motion, sample_xy, rgba8, view, moved, True, clamp)

@@ -36,6 +36,30 @@ def host_api_source() -> str:
     return "\n".join(host)
 
 
+def n_params(arglist: str) -> int:
+    """The number of parameters in the text between a declaration's parentheses.  The callback type of rr_render_progressive has
+    parameters of its own: nested parentheses are folded away before the commas are counted."""
+    depth, flat = 0, []
+    for ch in arglist:
+        if ch == "(":
+            depth += 1
+        elif ch == ")":
+            depth -= 1
+        elif depth == 0:
+            flat.append(ch)
+    t = "".join(flat).strip()
+    return 0 if t in ("", "void") else t.count(",") + 1
+
+
+def arglist_after(text: str, pos: int) -> str:
+    """The text from `pos`, just behind an opening parenthesis, to the parenthesis that closes it."""
+    depth, i = 1, pos
+    while depth:
+        depth += {"(": 1, ")": -1}.get(text[i], 0)
+        i += 1
+    return text[pos:i - 1]
+
+
 def load_scene(name: str) -> FlatScene:
     return FlatScene.load(os.path.join(SCENES, name + ".npz"))
 

@@ -9,7 +9,7 @@ import pytest
 
 from rustray_amd import capi
 from rustray_amd.flat import FlatScene, Item, Material, RR_ITEM_SPHERE, rr_flat_scene
-from tests.helpers import ROOT, host_api_source, load_scene
+from tests.helpers import ROOT, arglist_after, host_api_source, load_scene, n_params
 
 
 def declared_functions():
@@ -221,24 +221,6 @@ def test_every_declared_symbol_is_in_the_rust_block():
     block = doc[doc.index('#[link(name = "rustray_hip")]'):]
     block = block[:block.index("```")]
     block = re.sub(r"//[^\n]*", "", block)
-    # the callback type of rr_render_progressive has parameters of its own: fold nested parentheses away before counting commas
-    def n_params(arglist):
-        depth, flat = 0, []
-        for ch in arglist:
-            if ch == "(":
-                depth += 1
-            elif ch == ")":
-                depth -= 1
-            elif depth == 0:
-                flat.append(ch)
-        t = "".join(flat).strip()
-        return 0 if t in ("", "void") else t.count(",") + 1
-    def arglist_after(text, pos):
-        depth, i = 1, pos
-        while depth:
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        return text[pos:i - 1]
     for name in declared_functions():
         m = re.search(r"\b" + name + r"\s*\(", hdr)
         want = n_params(arglist_after(hdr, m.end()))

@@ -12,9 +12,10 @@ import pytest
 from rustray_amd import denoise
 from rustray_amd.denoise import atrous_denoise
 from rustray_amd.temporal import AccumulateParams, accumulate_records, previous_view
-from tests.denoise_cases import F, differing_words
+from tests.denoise_cases import F
 from tests.helpers import camera_for
 from tests.temporal_cases import frame_params, temporal_frame
+from tests.temporal_device import check_words as _check, device_call
 from tests.test_gpu_pixel_parts import SENTINEL, _cfg
 from tests.test_gpu_shade_rays import _scene
 
@@ -47,63 +48,11 @@ def small_scene(hip):
 
 
 def _device_call(ds, W, H, use_halves, use_motion, first, snap=1 / 64, in_place=False, rgba8=False, stream=None, produce=False):
-    """One rr_accumulate_records_device call on temporal_frame(W, H) with sentinels behind every output -> dict(records, halves, length
-    [, rgba]) as numpy words.  produce: the inputs are made by copy kernels on `stream` and the call follows them without a
-    synchronisation.  The inputs are checked to be what they were."""
-    import torch
-    n = W * H
+    """One rr_accumulate_records_device call on temporal_frame(W, H) through tests/temporal_device.py: sentinels behind every output, the
+    inputs checked to be what they were -> dict(records, halves, length [, rgba]) as numpy words.  in_place: over records and halves."""
     case = temporal_frame(W, H)
-    a = _inputs(case, use_halves, use_motion, first)
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(0)
-    with ctx:
-        src = {k: torch.from_numpy(np.ascontiguousarray(v).copy()).cuda() if v is not None else None for k, v in a.items()}
-        torch.cuda.synchronize()
-        if produce:
-            src = {k: t.clone() if t is not None else None for k, t in src.items()}      # (copy kernels on `stream`; the call is enqueued behind them)
-        out = torch.full((n + 2, 8), SENTINEL, dtype=torch.int32, device="cuda")
-        out_h = torch.full((2 * n + 2, 8), SENTINEL, dtype=torch.int32, device="cuda")
-        length = torch.full((n + 2,), SENTINEL, dtype=torch.int32, device="cuda")
-        rgba = torch.full((n + 2,), SENTINEL, dtype=torch.int32, device="cuda")
-        rec_ptr, hv_ptr = src["records"].data_ptr(), src["halves"].data_ptr() if use_halves else None
-        if in_place:
-            out[:n] = src["records"].view(torch.int32)
-            rec_ptr = out.data_ptr()
-            if use_halves:
-                out_h[:2 * n] = src["halves"].view(torch.int32).reshape(2 * n, 8)
-                hv_ptr = out_h.data_ptr()
-        if not produce:
-            torch.cuda.synchronize()
-        ptr = lambda k: src[k].data_ptr() if src[k] is not None else None
-        ds.accumulate_records_device(case["cam"].c_struct(), rec_ptr, hv_ptr, ptr("history"), ptr("history_halves"), ptr("history_length"), ptr("motion"),
-                                     out.data_ptr(), out_h.data_ptr() if use_halves else None, length.data_ptr(), rgba.data_ptr() if rgba8 else None,
-                                     frame_params(case, snap=snap), stream.cuda_stream if stream is not None else None)
-    torch.cuda.synchronize()
-    o, oh, ln, rg = (t.cpu().numpy().view(np.uint32) for t in (out, out_h, length, rgba))
-    assert (o[n:] == SENTINEL).all() and (oh[2 * n:] == SENTINEL).all() and (ln[n:] == SENTINEL).all() and (rg[n:] == SENTINEL).all(), "words behind an output were written"
-    for k, v in a.items():          # the inputs are what they were
-        if v is not None and not (in_place and k in ("records", "halves")):
-            assert np.array_equal(src[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(v).view(np.uint32)), k
-    if not use_halves:
-        assert (oh == SENTINEL).all()
-    if not rgba8:
-        assert (rg == SENTINEL).all()
-    res = dict(records=o[:n], halves=oh[:2 * n].reshape(n, 2, 8) if use_halves else None, length=ln[:n])
-    if rgba8:
-        res["rgba"] = rg[:n].view(np.uint8).reshape(n, 4)
-    return res
-
-
-def _check(got, want, what):
-    """Every word equal; a word that is a NaN on both sides counts as equal whatever its other bits (a NaN the arithmetic generated has
-    no specified sign or payload)."""
-    for key in ("records", "halves", "length"):
-        if want[key] is None:
-            assert got[key] is None, what
-            continue
-        differ, nans = differing_words(got[key], want[key])
-        if nans:
-            print(f"{what}: {nans} words of {key} are NaNs of other bits on both sides")
-        assert differ == 0, f"{what}: {differ} of {want[key].size} words of {key} differ"
+    return device_call(ds, "plain", case["cam"].c_struct(), frame_params(case, snap=snap), _inputs(case, use_halves, use_motion, first),
+                       in_place=("records", "halves") if in_place else (), rgba8=rgba8, stream=stream, produce=produce)
 
 
 # ---- 1: hand-made frames against the yardstick -------------------------------------------------------------------------------------

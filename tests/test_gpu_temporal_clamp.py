@@ -17,9 +17,10 @@ import pytest
 
 from rustray_amd import denoise
 from rustray_amd.temporal import AccumulateParams, HistoryClampParams, accumulate_clamped_records, accumulate_records, clamp_boxes, previous_view
-from tests.denoise_cases import F, differing_words
+from tests.denoise_cases import F
 from tests.helpers import camera_for
 from tests.temporal_cases import frame_params
+from tests.temporal_device import check_words as _check, device_call
 from tests.temporal_clamp_cases import KEYS, KINDS, clamp_frame, inputs, own_colour_frame
 from tests.test_gpu_pixel_parts import SENTINEL, _cfg
 from tests.test_gpu_shade_rays import _scene
@@ -48,69 +49,16 @@ def small_scene(hip):
 
 
 def _device_call(ds, case, prm, a, clamp, halves_in_place=False, rgba8=False, stream=None, produce=False, plain=False):
-    """One rr_accumulate_clamped_records_device call on the arrays `a` (inputs(...)) with sentinels behind every output -> dict(records,
-    halves, length [, rgba]) as numpy words.  produce: the inputs are made by copy kernels on `stream` and the call follows them without a
-    synchronisation.  plain: rr_accumulate_records_device on the same buffers instead.  The inputs are checked to be what they were."""
-    import torch
-    cam = case["cam"].c_struct()
-    n = int(cam.width) * int(cam.height)
-    a = dict(zip(KEYS, a))
-    use_halves = a["halves"] is not None
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(0)
-    with ctx:
-        src = {k: torch.from_numpy(np.ascontiguousarray(v).copy()).cuda() if v is not None else None for k, v in a.items()}
-        torch.cuda.synchronize()
-        if produce:
-            src = {k: t.clone() if t is not None else None for k, t in src.items()}      # (copy kernels on `stream`; the call is enqueued behind them)
-        words = dict(out=8 * n, halves_out=16 * n, length_out=n, rgba=n)
-        out = {k: torch.full((w + 8,), SENTINEL, dtype=torch.int32, device="cuda") for k, w in words.items()}
-        ptr = {k: (t.data_ptr() if t is not None else None) for k, t in src.items()}
-        if halves_in_place and use_halves:
-            out["halves_out"][:16 * n] = src["halves"].view(torch.int32).reshape(-1)
-            ptr["halves"] = out["halves_out"].data_ptr()
-        if not produce:
-            torch.cuda.synchronize()
-        optr = {k: out[k].data_ptr() for k in OUTS}
-        if not use_halves:
-            optr["halves_out"] = None
-        if not rgba8:
-            optr["rgba"] = None
-        st = stream.cuda_stream if stream is not None else None
-        if plain:
-            ds.accumulate_records_device(cam, *(ptr[k] for k in KEYS), *(optr[k] for k in OUTS), prm, st)
-        else:
-            ds.accumulate_clamped_device(cam, *(ptr[k] for k in KEYS), *(optr[k] for k in OUTS), prm, HistoryClampParams(*clamp), st)
-    torch.cuda.synchronize()
-    got = {k: t.cpu().numpy().view(np.uint32) for k, t in out.items()}
-    for k, w in words.items():
-        assert (got[k][w:] == SENTINEL).all(), f"words behind {k} were written"
-        if optr[k] is None:
-            assert (got[k] == SENTINEL).all(), f"{k} is absent and was written"
-    for k, v in a.items():          # the inputs are what they were
-        if v is not None and not (halves_in_place and k == "halves"):
-            assert np.array_equal(src[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(v).view(np.uint32)), k
-    res = dict(records=got["out"][:8 * n].reshape(n, 8), halves=got["halves_out"][:16 * n].reshape(n, 2, 8) if use_halves else None, length=got["length_out"][:n])
-    if rgba8:
-        res["rgba"] = got["rgba"][:n].view(np.uint8).reshape(n, 4)
-    return res
+    """One rr_accumulate_clamped_records_device call on the arrays `a` (inputs(...)) through tests/temporal_device.py: sentinels behind
+    every output, the inputs checked to be what they were -> dict(records, halves, length [, rgba]) as numpy words.  plain:
+    rr_accumulate_records_device on the same buffers instead."""
+    return device_call(ds, "plain" if plain else "clamped", case["cam"].c_struct(), prm, dict(zip(KEYS, a)), clamp=clamp,
+                       in_place=("halves",) if halves_in_place else (), rgba8=rgba8, stream=stream, produce=produce)
 
 
 def _case_call(ds, kind, W, H, use_halves, use_motion, first, clamp, snap=1 / 64, **kw):
     case = KINDS[kind](W, H)
     return _device_call(ds, case, frame_params(case, snap=snap), inputs(case, use_halves, use_motion, first), clamp, **kw)
-
-
-def _check(got, want, what):
-    """Every word equal; a word that is a NaN on both sides counts as equal whatever its other bits (a NaN the arithmetic generated has no
-    specified sign or payload)."""
-    for key in ("records", "halves", "length"):
-        if want[key] is None:
-            assert got[key] is None, what
-            continue
-        differ, nans = differing_words(got[key], want[key])
-        if nans:
-            print(f"{what}: {nans} words of {key} are NaNs of other bits on both sides")
-        assert differ == 0, f"{what}: {differ} of {np.asarray(want[key]).size} words of {key} differ"
 
 
 # ---- 1: hand-made frames against the yardstick -------------------------------------------------------------------------------------

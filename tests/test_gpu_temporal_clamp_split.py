@@ -19,9 +19,10 @@ import pytest
 
 from rustray_amd import denoise
 from rustray_amd.temporal import AccumulateParams, HistoryClampParams, accumulate_clamped_split_records, previous_view
-from tests.denoise_cases import F, differing_words
+from tests.denoise_cases import F
 from tests.helpers import camera_for
 from tests.temporal_cases import frame_params
+from tests.temporal_device import check_words as _check, device_call
 from tests.temporal_clamp_split_cases import KEYS, KINDS, clamp_split_frame, inputs, own_colour_split_frame
 from tests.test_gpu_pixel_parts import SENTINEL, _cfg
 from tests.test_gpu_shade_rays import _scene
@@ -30,7 +31,6 @@ pytestmark = pytest.mark.gpu
 
 _want = {}
 OUTS = ("out", "halves_out", "diffuse_out", "diffuse_halves_out", "length_out", "rgba")
-COLOUR_KEYS = ("records", "halves", "history", "history_halves", "history_length", "motion")
 SIZES = ((1, 1), (3, 2), (32, 8), (33, 9), (64, 16), (37, 19), (130, 70))
 COMBOS = ((True, True, False), (True, False, False), (False, True, False), (False, False, False), (True, False, True), (False, False, True))
 LAYERS = ("records", "halves", "diffuse", "diffuse_halves", "length")
@@ -53,82 +53,17 @@ def small_scene(hip):
 
 
 def _device_call(ds, case, prm, a, clamp, halves_in_place=False, rgba8=False, stream=None, produce=False, call="clamped_split"):
-    """One rr_accumulate_clamped_split_records_device call on the arrays `a` (inputs(...)) with sentinels behind every output ->
-    dict(records, halves, diffuse, diffuse_halves, length [, rgba]) as numpy words.  produce: the inputs are made by copy kernels on `stream`
-    and the call follows them without a synchronisation.  call="clamped": rr_accumulate_clamped_records_device on the colour buffers
-    instead; call="split": rr_accumulate_split_records_device on all of them.  The inputs are checked to be what they were."""
-    import torch
-    cam = case["cam"].c_struct()
-    n = int(cam.width) * int(cam.height)
-    a = dict(zip(KEYS, a))
-    use_halves = a["halves"] is not None
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(0)
-    with ctx:
-        src = {k: torch.from_numpy(np.ascontiguousarray(v).copy()).cuda() if v is not None else None for k, v in a.items()}
-        torch.cuda.synchronize()
-        if produce:
-            src = {k: t.clone() if t is not None else None for k, t in src.items()}      # (copy kernels on `stream`; the call is enqueued behind them)
-        words = dict(out=8 * n, halves_out=16 * n, diffuse_out=3 * n, diffuse_halves_out=6 * n, length_out=n, rgba=n)
-        out = {k: torch.full((w + 8,), SENTINEL, dtype=torch.int32, device="cuda") for k, w in words.items()}
-        ptr = {k: (t.data_ptr() if t is not None else None) for k, t in src.items()}
-        in_place = dict(halves="halves_out", diffuse_halves="diffuse_halves_out") if halves_in_place and use_halves else {}
-        for k, o in in_place.items():
-            out[o][:words[o]] = src[k].view(torch.int32).reshape(-1)
-            ptr[k] = out[o].data_ptr()
-        if not produce:
-            torch.cuda.synchronize()
-        optr = {k: out[k].data_ptr() for k in OUTS}
-        if not use_halves:
-            optr["halves_out"] = optr["diffuse_halves_out"] = None
-        if not rgba8:
-            optr["rgba"] = None
-        st = stream.cuda_stream if stream is not None else None
-        if call == "clamped":
-            ds.accumulate_clamped_device(cam, *(ptr[k] for k in COLOUR_KEYS), optr["out"], optr["halves_out"], optr["length_out"], optr["rgba"], prm,
-                                         HistoryClampParams(*clamp), st)
-        elif call == "split":
-            ds.accumulate_split_device(cam, *(ptr[k] for k in KEYS), *(optr[k] for k in OUTS), prm, st)
-        else:
-            ds.accumulate_clamped_split_device(cam, *(ptr[k] for k in KEYS), *(optr[k] for k in OUTS), prm, HistoryClampParams(*clamp), st)
-    torch.cuda.synchronize()
-    got = {k: t.cpu().numpy().view(np.uint32) for k, t in out.items()}
-    for k, w in words.items():
-        assert (got[k][w:] == SENTINEL).all(), f"words behind {k} were written"
-        if optr[k] is None or (call == "clamped" and k in ("diffuse_out", "diffuse_halves_out")):
-            assert (got[k] == SENTINEL).all(), f"{k} is absent and was written"
-    for k, v in a.items():          # the inputs are what they were
-        if v is not None and k not in in_place:
-            assert np.array_equal(src[k].cpu().numpy().view(np.uint32), np.ascontiguousarray(v).view(np.uint32)), k
-    res = dict(records=got["out"][:8 * n].reshape(n, 8), halves=got["halves_out"][:16 * n].reshape(n, 2, 8) if use_halves else None,
-               diffuse=got["diffuse_out"][:3 * n].reshape(n, 3), diffuse_halves=got["diffuse_halves_out"][:6 * n].reshape(n, 2, 3) if use_halves else None,
-               length=got["length_out"][:n])
-    if rgba8:
-        res["rgba"] = got["rgba"][:n].view(np.uint8).reshape(n, 4)
-    return res
+    """One rr_accumulate_clamped_split_records_device call on the arrays `a` (inputs(...)) through tests/temporal_device.py: sentinels
+    behind every output, the inputs checked to be what they were -> dict(records, halves, diffuse, diffuse_halves, length [, rgba]) as
+    numpy words.  call="clamped": rr_accumulate_clamped_records_device on the colour buffers instead, the diffuse outputs untouched;
+    call="split": rr_accumulate_split_records_device on all of them."""
+    return device_call(ds, call, case["cam"].c_struct(), prm, dict(zip(KEYS, a)), clamp=clamp, in_place=("halves", "diffuse_halves") if halves_in_place else (),
+                       rgba8=rgba8, stream=stream, produce=produce)
 
 
 def _case_call(ds, kind, W, H, use_halves, use_motion, first, clamp, snap=1 / 64, **kw):
     case = KINDS[kind](W, H)
     return _device_call(ds, case, frame_params(case, snap=snap), inputs(case, use_halves, use_motion, first), clamp, **kw)
-
-
-def _check(got, want, what, diffuse=True):
-    """Every word equal.  In records and halves a word that is a NaN on both sides counts as equal whatever its other bits (a NaN the
-    arithmetic generated has no specified sign or payload); the diffuse words are compared bitwise."""
-    for key in ("records", "halves", "length"):
-        if want[key] is None:
-            assert got[key] is None, what
-            continue
-        differ, nans = differing_words(got[key], want[key])
-        if nans:
-            print(f"{what}: {nans} words of {key} are NaNs of other bits on both sides")
-        assert differ == 0, f"{what}: {differ} of {np.asarray(want[key]).size} words of {key} differ"
-    for key in ("diffuse", "diffuse_halves") if diffuse else ():
-        if want[key] is None:
-            assert got[key] is None, what
-            continue
-        g, w = np.ascontiguousarray(got[key]).view(np.uint32), np.ascontiguousarray(want[key]).view(np.uint32)
-        assert g.shape == w.shape and np.array_equal(g, w), f"{what}: {int((g != w).sum())} of {w.size} words of {key} differ"
 
 
 # ---- 1: hand-made frames against the yardstick -------------------------------------------------------------------------------------
