@@ -2,7 +2,8 @@
 // over samples (src/raytracing.rs:400-417).  Integer adds commute, so the frame does not depend on the order of anything.
 //
 // Offers: to_fix, fix_add, fix_add_at, nonfinite_flags, accum_merged, accum_aux_merged, accum_depth_wide_merged, accum_hit_merged (the last four
-// must be called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms).
+// must be called by all 64 lanes of a wave); from_fix, resolve_color, resolve_normal, resolve_depth (and their *_sum forms); Record, load_record,
+// store_record, load_slot_sums, resolve_record, resolve_record_sums: an rr_radiance from a slot or from sums, every pixel ending's way out.
 // wave_merge_runs / wave_merge_runs32 / fits25i / fits25 / wave_one_pixel / wave_sum32 / wave_sum64 / totals_to_lanes and the *_runs forms of the merges
 // are this layer's own, and so are its DPP macros (RR_DPP_*, RR_SEG_STEP, RR_SEG_STEP32), un-defined at the end.
 // Needs: rr_device.h (DAccum, RR_NF_*), rr_math.h.
@@ -309,6 +310,32 @@ RR_DEV float resolve_depth_sum(long long fix, uint32_t nf, float n) {
     return (nf & RR_NF_DEPTH_NAN) ? __builtin_nanf("") : (float)((double)fix * (1.0 / 65536.0)) / n; // RR_DEPTH_SCALE
 }
 RR_DEV float resolve_depth(const DAccum& acc, uint32_t p, uint32_t nf, float n) { return resolve_depth_sum(acc.depth[p], nf, n); }
+
+// An rr_radiance as the device moves it: two float4 = (colour rgb, depth), (normal xyz, bits(object id)); record o of `out` is its pair.
+struct Record { float4 color_depth, normal_id; };
+RR_DEV Record load_record(const float4* __restrict__ in, unsigned long long i) { return Record{in[2ull * i], in[2ull * i + 1]}; }
+RR_DEV void store_record(float4* __restrict__ out, unsigned long long o, const Record& r) { out[2ull * o] = r.color_depth; out[2ull * o + 1] = r.normal_id; }
+// the seven integer sums of slot p (colour r g b, normal x y z, depth), and their record over n samples: what k_resolve computes BEFORE
+// its clamp.  The kernels that form a pixel's sums across lanes or slots resolve them through the same function, so a pixel has the bytes
+// one slot would have given it (integer adds commute).
+enum { RECORD_SUMS = 7 };
+RR_DEV void load_slot_sums(const DAccum& acc, uint32_t p, long long (&w)[RECORD_SUMS]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { w[k] = acc.rgb[(unsigned long long)k * acc.n + p]; w[3 + k] = acc.normal[(unsigned long long)k * acc.n + p]; }
+    w[6] = acc.depth[p];
+}
+RR_DEV Record resolve_record_sums(const long long (&w)[RECORD_SUMS], uint32_t nf, uint32_t id, float n) {
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n);
+    const f3 nn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
+    return Record{make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n)), make_float4(nn.x, nn.y, nn.z, __uint_as_float(id))};
+}
+RR_DEV Record resolve_record(const DAccum& acc, uint32_t p, float n) {
+    long long w[RECORD_SUMS];
+    load_slot_sums(acc, p, w);
+    return resolve_record_sums(w, acc.flags[p], acc.object_id[p], n);
+}
 
 #undef RR_DPP_SHR
 #undef RR_DPP_ADD

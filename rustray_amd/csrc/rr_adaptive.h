@@ -1,8 +1,8 @@
 // rr_adaptive.h — the arithmetic of adaptive sampling that host and device share: the half-buffer error estimate of one pixel
 // (rustray_amd/adaptive.py: half_error), the order in which a frame's pixels enter a refinement list (refine_list: 8x8 blocks
 // row-major, row-major inside a block), and where the entries of a list go in the list made from it (refine_sublist).  Plain host
-// logic, no HIP calls and no include of its own: k_refine_masks, k_refine_scatter, k_sublist_masks and k_sublist_scatter
-// (rr_kernels.hip) apply these functions per lane, rr_api_adaptive.h and rr_api_levels.h size their buffers with them, and
+// logic, no HIP calls and no include of its own: k_refine_masks and k_refine_scatter (rr_kernels.hip), one body each over the two entry
+// sources below, apply these functions per lane, rr_api_adaptive.h and rr_api_levels.h size their buffers with them, and
 // tests/native/adaptive_order_test.cpp and adaptive_sublist_test.cpp check all of it on the CPU.  Last: where the accumulators of a
 // list's entries lie and where a compaction moves them (rr_render_adaptive_prefix: k_prefix_masks, k_prefix_compact, rr_api_prefix.h;
 // tests/native/adaptive_prefix_test.cpp).
@@ -34,6 +34,13 @@ RR_SETUP_HD float half_error(const float* a, const float* b) {
     }
     return e;
 }
+// of entry i's two part records (rr_render_pixel_parts at K = 2).  V4: four floats x y z w, 16 bytes (the device's float4); a record is
+// two of them and its colour the first one's x y z, so the halves of entry i are parts[4 i] and parts[4 i + 2]: two whole 16-byte loads.
+template <class V4> RR_SETUP_HD float half_error_of_parts(const V4* parts, unsigned long long i) {
+    const V4 a = parts[4ull * i], b = parts[4ull * i + 2];
+    const float ca[3] = {a.x, a.y, a.z}, cb[3] = {b.x, b.y, b.z};
+    return half_error(ca, cb);
+}
 
 // ---- the block order.  Position j of a width x height frame: block j >> 6 of ceil(width / 8) blocks per row, row-major; inside the
 // block row (j >> 3) & 7 and column j & 7.  Blocks at the right and lower border hold positions without a pixel.
@@ -49,6 +56,8 @@ RR_SETUP_HD bool refine_position_pixel(unsigned long long j, unsigned int width,
     *xy = x | (y << 16);
     return true;
 }
+// where the frame keeps what belongs to pixel xy = x | y << 16: y * width + x (< 2^30: every frame's slots fit the accumulators)
+RR_SETUP_HD unsigned int frame_index(unsigned int xy, unsigned int width) { return (xy >> 16) * width + (xy & 0xffffu); }
 // its inverse: the position of pixel (x, y) -- the sort key of adaptive.refine_list
 RR_SETUP_HD unsigned long long refine_pixel_position(unsigned int x, unsigned int y, unsigned int width) {
     return ((unsigned long long)((y >> 3) * refine_blocks_x(width) + (x >> 3)) << 6) + (y & 7u) * 8u + (x & 7u);
@@ -90,6 +99,32 @@ RR_SETUP_HD bool sublist_pad_word(unsigned int total, unsigned int lane, unsigne
     *at = total + lane;
     return true;
 }
+
+// ---- the entry source of a compaction: what differs between the list of a frame and the list of a list.  waves(): the 64-lane groups
+// of the source; entry(wave, lane, &index, &word): false = the lane has no entry (nothing is then written); else *index is where the
+// entry's two part records and its error lie, and *word what it contributes to the output list.  A third source is a third such struct.
+// On wave64 one wave is one 8x8 block of the frame: lane l is the block's pixel l, the ballot of the lanes' flags is the block's
+// 64-bit refine mask, and the blocks row-major ARE the list's order.
+struct FrameSource {
+    unsigned int width, height;
+    RR_SETUP_HD unsigned int waves() const { return refine_blocks(width, height); }
+    RR_SETUP_HD bool entry(unsigned int wave, unsigned int lane, unsigned int* index, unsigned int* word) const {
+        if (!refine_position_pixel(((unsigned long long)wave << 6) | lane, width, height, word)) return false;
+        *index = frame_index(*word, width);
+        return true;
+    }
+};
+// 64 consecutive entries of a list per wave; the entries' coordinates are not interpreted: there is no frame here
+struct ListSource {
+    const unsigned int* list;
+    unsigned int count;
+    RR_SETUP_HD unsigned int waves() const { return sublist_waves(count); }
+    RR_SETUP_HD bool entry(unsigned int wave, unsigned int lane, unsigned int* index, unsigned int* word) const {
+        if (!sublist_lane_entry(wave, lane, count, index)) return false;
+        *word = list[*index];
+        return true;
+    }
+};
 
 // ---- resident accumulators (rr_render_adaptive_prefix): the pixels of a list keep their integer sums from level to level.  A SET holds
 // the two halves of every entry of a padded list in list order: entry i owns slots 2 i (samples s with s mod 2 == 0) and 2 i + 1, which

@@ -1,16 +1,16 @@
 // rr_api_adaptive.h — find the noisy pixels of a frame and refine them, on the device: the list of rustray_amd/adaptive.py (half_error,
 // refine_list) from part records that already lie there, and a frame at two sample counts as ONE call under one hold of the scene's lock.
 // Offers: rr_refine_list_capacity, rr_refine_list_device, rr_render_adaptive, rr_render_adaptive_device; for the fused calls of the layers
-//         behind it: check_refine_frame; ListScratch, list_scratch, await_list_count; refine_list_locked; FusedOut, check_fused_outputs,
-//         device_fused_call, host_fused_call, launch_record_bytes, finish_fused.
+//         behind it: check_refine_frame; ListScratch, list_scratch, await_list_count; compact_list_locked, refine_list_locked; FusedOut,
+//         check_fused_outputs, device_fused_call, host_fused_call, launch_record_bytes, finish_fused.
 // Needs:  rr_api_parts.h (render_pixel_parts_locked: the whole frame in parts), rr_api_query.h (render_pixels_locked, check_query_pointers),
-//         rr_api_frame.h (check_frame_args, take_stream, ScopedTimer, IdleOnExit, PassSums, collect_stats_locked), rr_adaptive.h, kernels
-//         5l .. 5p of rr_kernels.hip.
+//         rr_api_frame.h (check_frame_args, take_stream, ScopedTimer, IdleOnExit, PassSums, collect_stats_locked), rr_adaptive.h (FrameSource),
+//         kernels 5l .. 5p of rr_kernels.hip.
 //
-// The list is three launches (k_refine_masks, k_refine_scan, k_refine_scatter) and one wait, for the 4 bytes of its length.  The fused
-// call is: the frame in parts at base_samples (records straight into `out`), the list, that wait, the padded list through the body of
-// rr_render_pixels at max_samples, k_scatter_records, k_record_bytes.  The host form is the device form behind the staging copy of
-// every fused call (host_fused_call).
+// A list is three launches (k_refine_masks, k_refine_scan, k_refine_scatter over the list's entry source) and one wait, for the 4 bytes of
+// its length.  The fused call is: the frame in parts at base_samples (records straight into `out`), the list, that wait, the padded list
+// through the body of rr_render_pixels at max_samples, k_scatter_level without an error, k_record_bytes.  The host form is the device form
+// behind the staging copy of every fused call (host_fused_call).
 
 // width x height as a frame whose two part records per pixel fit the accumulator slots of a call
 static int check_refine_frame(const char* fn, uint32_t width, uint32_t height, float threshold) {
@@ -42,21 +42,28 @@ static int await_list_count(rr_scene* s, const uint32_t* total, hipStream_t st, 
     return RR_OK;
 }
 
-// The list of a frame's parts on stream st, into list_out (refine_capacity entries) and *count_out (host); the caller holds the lock and has
-// taken the stream.  With kernel_timing the three launches are timed as one re-ordering (rr_frame_stats::ms_binning).
-static int refine_list_locked(rr_scene* s, uint32_t W, uint32_t H, const rr_radiance* parts, float threshold, float* error_out, uint32_t* list_out,
-                              uint32_t* count_out, hipStream_t st) {
-    const uint32_t nb = refine_blocks(W, H);
+// THE list of an entry source (rr_adaptive.h: a frame's blocks, or a list's entries) from its part records, on stream st, into list_out and
+// *count_out (host): three launches and one wait.  The caller holds the lock and has taken the stream.  With kernel_timing the three
+// launches are timed as one re-ordering (rr_frame_stats::ms_binning).  Scratch: list_scratch over the source's waves.
+template <class Source>
+static int compact_list_locked(rr_scene* s, const Source& src, const rr_radiance* parts, float threshold, float* error_out, uint32_t* list_out, uint32_t* count_out,
+                               hipStream_t st) {
+    const uint32_t nw = src.waves();
     ListScratch ls;
-    RR_TRY(list_scratch(s, nb, &ls));
+    RR_TRY(list_scratch(s, nw, &ls));
     {
         ScopedTimer t(s, st, TK_BINNING, false);
-        hipLaunchKernelGGL(k_refine_masks, dim3(ls.grid), dim3(RR_BLOCK), 0, st, (const float4*)parts, W, H, nb, threshold, error_out, ls.masks, ls.counts);
-        hipLaunchKernelGGL(k_refine_scan, dim3(1), dim3(1024), 0, st, ls.counts, nb, ls.total);
-        hipLaunchKernelGGL(k_refine_scatter, dim3(ls.grid), dim3(RR_BLOCK), 0, st, ls.masks, ls.counts, ls.total, W, H, nb, list_out);
+        hipLaunchKernelGGL(k_refine_masks<Source>, dim3(ls.grid), dim3(RR_BLOCK), 0, st, src, (const float4*)parts, threshold, error_out, ls.masks, ls.counts);
+        hipLaunchKernelGGL(k_refine_scan, dim3(1), dim3(1024), 0, st, ls.counts, nw, ls.total);
+        hipLaunchKernelGGL(k_refine_scatter<Source>, dim3(ls.grid), dim3(RR_BLOCK), 0, st, src, ls.masks, ls.counts, ls.total, list_out);
     }
     HIP_TRY(hipGetLastError());
     return await_list_count(s, ls.total, st, count_out);
+}
+// the list of a frame's parts: list_out has refine_capacity entries
+static int refine_list_locked(rr_scene* s, uint32_t W, uint32_t H, const rr_radiance* parts, float threshold, float* error_out, uint32_t* list_out,
+                              uint32_t* count_out, hipStream_t st) {
+    return compact_list_locked(s, FrameSource{W, H}, parts, threshold, error_out, list_out, count_out, st);
 }
 
 uint64_t rr_refine_list_capacity(uint32_t width, uint32_t height) { return refine_capacity(width, height); }
@@ -191,8 +198,8 @@ static int render_adaptive_locked(rr_scene* s, const rr_camera* cam, const rr_co
         c.samples = max_samples;
         RR_TRY(render_pixels_locked(s, cam, &c, sample_xy_max, list, padded, (rr_radiance*)fine, nullptr, st, cancel));
         const int grid = (int)std::min<uint64_t>((count + RR_BLOCK - 1) / RR_BLOCK, (uint64_t)s->n_cus * 8u);
-        hipLaunchKernelGGL(k_scatter_records, dim3(grid), dim3(RR_BLOCK), 0, st, list, s->adaptive.scratch.as<uint32_t>() + 3ull * refine_blocks(W, H), fine, W, max_samples,
-                           (float4*)o.out, o.samples);
+        hipLaunchKernelGGL(k_scatter_level, dim3(grid), dim3(RR_BLOCK), 0, st, list, count, fine, (const float4*)nullptr, W, max_samples, (float4*)o.out, o.samples,
+                           (float*)nullptr); // (no error at max_samples: there are no halves)
         sums.carry(); // rr_scene_last_stats: the sums over the two passes
     }
     sums.close();

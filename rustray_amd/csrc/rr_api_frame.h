@@ -177,7 +177,7 @@ enum class FrameEnd {
     ALBEDO,       // rr_albedo_pixels (rr_api_albedo_pixels.h): level 1 ends in k_albedo_level1 instead of the shade and shadow kernels, nothing spawns,
                   // only the colour planes are accumulated, and k_resolve_albedo writes three floats per pixel to `albedo`
     RECORD_SPLIT, // rr_render_pixel_split (rr_api_pixel_split.h): level 1 runs the SPLIT builds of k_shade and k_trace_shadow, which sum the direct
-                  // diffuse light of the primary hits in three planes of their own; k_resolve_pixel_split writes RECORD_PARTS' outputs (`parts` only
+                  // diffuse light of the primary hits in three planes of their own; k_resolve_pixel_parts<true> writes RECORD_PARTS' outputs (`parts` only
                   // with lg_parts > 0) and the planes as floats to `diffuse` and `diffuse_parts`
     NONE,         // no resolve: the caller reads the accumulators itself (every plane: rr_api_prefix.h)
 };
@@ -856,9 +856,12 @@ static void launch_resolve(const FrameRun& f, const DFrame& fr, const FrameIo& i
     switch (io.end) {
     case FrameEnd::NONE: break;
     case FrameEnd::ALBEDO: hipLaunchKernelGGL(k_resolve_albedo, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (uint32_t*)io.albedo); break;
-    case FrameEnd::RECORD_PARTS: hipLaunchKernelGGL(k_resolve_pixel_parts, grid, block, 0, f.st, fr, f.slot_xy, f.acc, io.lg_parts, by_pixel, (float4*)io.radiance, (float4*)io.parts); break;
+    case FrameEnd::RECORD_PARTS:
+        hipLaunchKernelGGL(k_resolve_pixel_parts<false>, grid, block, 0, f.st, fr, f.slot_xy, f.acc, (const long long*)nullptr, io.lg_parts, by_pixel, (float4*)io.radiance,
+                           (float4*)io.parts, (float*)nullptr, (float*)nullptr);
+        break;
     case FrameEnd::RECORD_SPLIT:
-        hipLaunchKernelGGL(k_resolve_pixel_split, grid, block, 0, f.st, fr, f.slot_xy, f.acc, (const long long*)f.diffuse, io.lg_parts, by_pixel, (float4*)io.radiance,
+        hipLaunchKernelGGL(k_resolve_pixel_parts<true>, grid, block, 0, f.st, fr, f.slot_xy, f.acc, (const long long*)f.diffuse, io.lg_parts, by_pixel, (float4*)io.radiance,
                            (float4*)io.parts, io.diffuse, io.diffuse_parts);
         break;
     case FrameEnd::RECORDS: hipLaunchKernelGGL(k_resolve_pixels, grid, block, 0, f.st, fr, f.slot_xy, f.acc, by_pixel, (float4*)io.radiance, (uint32_t*)io.rgba8); break;

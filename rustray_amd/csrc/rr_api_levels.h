@@ -2,12 +2,12 @@
 // of rustray_amd/adaptive.py) and a frame at up to RR_MAX_ADAPTIVE_LEVELS sample counts as ONE call under one hold of the scene's lock.
 // Offers: rr_refine_sublist_device, rr_render_adaptive_levels, rr_render_adaptive_levels_device.
 //         For rr_api_prefix.h: check_ladder.
-// Needs:  rr_api_adaptive.h (refine_list_locked, list_scratch, await_list_count; FusedOut, check_fused_outputs, device_fused_call,
+// Needs:  rr_api_adaptive.h (refine_list_locked, compact_list_locked; FusedOut, check_fused_outputs, device_fused_call,
 //         host_fused_call, finish_fused), rr_api_parts.h (render_pixel_parts_locked: the whole frame and every list in two parts),
-//         rr_api_query.h (check_query_pointers), rr_api_frame.h (check_frame_args, take_stream, ScopedTimer, IdleOnExit, PassSums,
-//         collect_stats_locked), rr_adaptive.h (ladder_fault), kernels 5m, 5p and 5q .. 5s of rr_kernels.hip.
+//         rr_api_query.h (check_query_pointers), rr_api_frame.h (check_frame_args, take_stream, IdleOnExit, PassSums,
+//         collect_stats_locked), rr_adaptive.h (ListSource, ladder_fault), kernels 5l .. 5p of rr_kernels.hip.
 //
-// The sublist is three launches (k_sublist_masks, k_refine_scan, k_sublist_scatter) and one wait, for the 4 bytes of its length.  The
+// The sublist is the list of rr_api_adaptive.h over a ListSource (k_refine_masks, k_refine_scan, k_refine_scatter and one wait).  The
 // fused call is: the frame in parts at level_samples[0] (records straight into `out`) and its list as rr_render_adaptive makes it; then
 // per level, while the list is not empty, the padded list in parts at the level's count, k_scatter_level, and -- unless the level is
 // the last -- the sublist for the next one; k_record_bytes at the end.  The host form is the device form behind the staging copy of
@@ -18,17 +18,7 @@
 // Scratch: per 64 entries a mask and a count, then the total (list_scratch over the list's waves).
 static int refine_sublist_locked(rr_scene* s, const uint32_t* list, uint32_t count, const rr_radiance* parts, float threshold, float* error_out,
                                  uint32_t* list_out, uint32_t* count_out, hipStream_t st) {
-    const uint32_t nw = sublist_waves(count);
-    ListScratch ls;
-    RR_TRY(list_scratch(s, nw, &ls));
-    {
-        ScopedTimer t(s, st, TK_BINNING, false);
-        hipLaunchKernelGGL(k_sublist_masks, dim3(ls.grid), dim3(RR_BLOCK), 0, st, (const float4*)parts, count, threshold, error_out, ls.masks, ls.counts);
-        hipLaunchKernelGGL(k_refine_scan, dim3(1), dim3(1024), 0, st, ls.counts, nw, ls.total);
-        hipLaunchKernelGGL(k_sublist_scatter, dim3(ls.grid), dim3(RR_BLOCK), 0, st, list, count, ls.masks, ls.counts, ls.total, list_out);
-    }
-    HIP_TRY(hipGetLastError());
-    return await_list_count(s, ls.total, st, count_out);
+    return compact_list_locked(s, ListSource{list, count}, parts, threshold, error_out, list_out, count_out, st);
 }
 
 // (C linkage: the entry points of this layer are declared in include/rustray_hip.h, inside its extern "C" block, and a definition keeps the

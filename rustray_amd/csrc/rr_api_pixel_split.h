@@ -3,7 +3,7 @@
 // texture modulates, which rr_denoise_split_records demodulates alone.
 // Offers: rr_render_pixel_split_device, rr_render_pixel_split.
 // Needs:  rr_api_frame.h (check_frame_args, FrameEnd::RECORD_SPLIT, pixels_io, render_region_locked: level 1 through k_shade<true, true> and
-//         k_trace_shadow<*, true>, ending in k_resolve_pixel_split), rr_api_query.h (check_arg_ranges, record_call, staged_host_call, StageArg),
+//         k_trace_shadow<*, true>, ending in k_resolve_pixel_parts<true>), rr_api_query.h (check_arg_ranges, record_call, staged_host_call, StageArg),
 //         rr_pixel_list.h (pixel_list_first_bad).
 //
 // The body is the frame's: slot table, sample table, batches, level walk and plan, over n_pixels * K accumulator slots (K = 2 with halves,

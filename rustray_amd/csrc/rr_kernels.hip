@@ -1129,7 +1129,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve(DFrame fr, const uint32_t*
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
     if (p >= fr.n_region_pixels) return;
     uint32_t o;
-    if (frame_layout) { uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
+    if (frame_layout) o = frame_index(slot_xy[p], fr.width);
     else o = slot_out[p]; // position in the region's compact output order
     const float n = (float)fr.samples;
     const uint32_t nf = acc.flags[p];
@@ -1165,20 +1165,11 @@ __global__ __launch_bounds__(RR_BLOCK) void k_seed_rays(const float* __restrict_
 }
 
 // What k_resolve computes BEFORE its clamp, per accumulator slot [first, first + n): two float4 per result =
-// (colour rgb, depth), (normal xyz, bits(object id)) -- rr_radiance: resolve_color / resolve_normal / resolve_depth (rr_accumulate.h).
+// (colour rgb, depth), (normal xyz, bits(object id)) -- rr_radiance: resolve_record (rr_accumulate.h).
 __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t first, uint32_t n, uint32_t samples, float4* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t p = first + i;
-    const float ns = (float)samples;
-    const uint32_t nf = acc.flags[p];
-    float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = resolve_color(acc, p, nf, k, ns);
-    const f3 nn = resolve_normal(acc, p, nf, ns);
-    const float depth = resolve_depth(acc, p, nf, ns);
-    out[2ull * i] = make_float4(c[0], c[1], c[2], depth);
-    out[2ull * i + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
+    store_record(out, i, resolve_record(acc, first + i, (float)samples));
 }
 
 // ---------------------------------------------------------------------------
@@ -1191,6 +1182,11 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_rays(DAccum acc, uint32_t 
 // entry is copied like any other -- its centre is plain arithmetic -- and the host refuses the call before a walk reads the table.
 // With parts (rr_render_pixel_parts, lg_parts > 0) entry i becomes the K = 2^lg_parts slots i * K .. i * K + K - 1, all with the entry's pixel
 // and centre: K neighbouring lanes read one word and every store stays as wide as it was.
+RR_DEV void first_bad_merge(uint32_t bad, uint32_t* __restrict__ first_bad) { // every lane's first bad index (0xffffffff = none) -> *first_bad
+#pragma unroll
+    for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
+    if ((threadIdx.x & (RR_WAVE - 1)) == 0u && bad != 0xffffffffu) atomicMin(first_bad, bad);
+}
 __global__ __launch_bounds__(RR_BLOCK) void k_pixel_slots(const uint32_t* __restrict__ pixel_xy, uint32_t n, uint32_t lg_parts, uint32_t width, uint32_t height,
                                                           uint32_t* __restrict__ slot_xy, float2* __restrict__ slot_c, uint32_t* __restrict__ first_bad) {
     const float w = (float)width, h = (float)height;
@@ -1205,9 +1201,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_pixel_slots(const uint32_t* __rest
         slot_xy[j] = xy;
         slot_c[j] = c;
     }
-#pragma unroll
-    for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
-    if ((threadIdx.x & (RR_WAVE - 1)) == 0u && bad != 0xffffffffu) atomicMin(first_bad, bad);
+    first_bad_merge(bad, first_bad);
 }
 
 // 5j: what k_resolve computes BEFORE its clamp, per accumulator slot of a frame, as k_resolve_rays writes it (two float4 = rr_radiance),
@@ -1217,17 +1211,10 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixels(DFrame fr, const ui
                                                              float4* __restrict__ out, uint32_t* __restrict__ rgba8) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
     if (p >= fr.n_region_pixels) return;
-    uint32_t o = p;
-    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
-    const float n = (float)fr.samples;
-    const uint32_t nf = acc.flags[p];
-    float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = resolve_color(acc, p, nf, k, n);
-    const f3 nn = resolve_normal(acc, p, nf, n);
-    const float depth = resolve_depth(acc, p, nf, n);
-    out[2ull * o] = make_float4(c[0], c[1], c[2], depth);
-    out[2ull * o + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(acc.object_id[p]));
+    const uint32_t o = from_xy ? frame_index(slot_xy[p], fr.width) : p;
+    const Record r = resolve_record(acc, p, (float)fr.samples);
+    store_record(out, o, r);
+    const float c[3] = {r.color_depth.x, r.color_depth.y, r.color_depth.z};
     if (rgba8) rgba8[o] = frame_bytes(c, fr.gamma);
 }
 
@@ -1244,130 +1231,100 @@ RR_DEV long long shfl_xor_ll(long long v, int mask) {
     const int lo = __shfl_xor((int)(uint32_t)(unsigned long long)v, mask), hi = __shfl_xor((int)(uint32_t)((unsigned long long)v >> 32), mask);
     return (long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
 }
-__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_parts(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, uint32_t lg_parts, uint32_t from_xy,
-                                                                  float4* __restrict__ out, float4* __restrict__ parts) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
-    const bool live = p < fr.n_region_pixels;                 // (n_region_pixels: the slots, n_pixels * K)
-    const uint32_t K = 1u << lg_parts;
-    long long w[7] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll}; // rgb, normal, depth
-    uint32_t nf = 0u, id = 0u;
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { w[k] = acc.rgb[(unsigned long long)k * acc.n + p]; w[3 + k] = acc.normal[(unsigned long long)k * acc.n + p]; }
-        w[6] = acc.depth[p];
-        nf = acc.flags[p];
-        id = acc.object_id[p];
-    }
-    const float n_part = (float)(fr.samples >> lg_parts);
-    float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n_part);
-    const f3 nn = resolve_normal_sum(w[3], w[4], w[5], nf, n_part);
-    const float depth = resolve_depth_sum(w[6], nf, n_part);
-    for (uint32_t off = 1u; off < K; off <<= 1) { // (wave-uniform trip count)
-#pragma unroll
-        for (int k = 0; k < 7; k++) w[k] += shfl_xor_ll(w[k], (int)off);
-        nf |= (uint32_t)__shfl_xor((int)nf, (int)off);
-    }
-    id = (uint32_t)__shfl((int)id, (int)((threadIdx.x & (RR_WAVE - 1)) | (K - 1u))); // the group's last slot holds sample S - 1
-    if (!live) return;
-    uint32_t o = p >> lg_parts; // the pixel's record index; its parts follow each other at o * K
-    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
-    const unsigned long long q = ((unsigned long long)o << lg_parts) + (p & (K - 1u));
-    parts[2ull * q] = make_float4(c[0], c[1], c[2], depth);
-    parts[2ull * q + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(id));
-    if ((p & (K - 1u)) != 0u) return;
-    const float n = (float)fr.samples;
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = resolve_color_sum(w[k], nf, k, n);
-    const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
-    out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
-    out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
-}
-
-// 5k': the end of rr_render_pixel_split: records and part records exactly as 5k writes them (the same loads, shuffles and resolve functions),
-// and next to them the diffuse planes (`diffuse`: three planes of acc.n words, laid out as acc.rgb) resolved the same way, as floats:
-// dif_out[3 o + c] over all S samples, dif_parts[3 (o K + h) + c] over the part's S / K.  The flags are the colour's: a channel whose record
-// colour is not finite holds the record's value here too.  lg_parts == 0 (no halves wanted): one slot per pixel, `parts` and `dif_parts`
-// are NULL and not written, and the record has k_resolve_pixels' bytes.
-__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_split(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, const long long* __restrict__ diffuse,
+// SPLIT: the end of rr_render_pixel_split: records and part records as above -- the same body -- and next to them the diffuse planes
+// (`diffuse`: three planes of acc.n words, laid out as acc.rgb) resolved the same way, as floats: dif_out[3 o + c] over all S samples,
+// dif_parts[3 (o K + h) + c] over the part's S / K.  The flags are the colour's: a channel whose record colour is not finite holds the
+// record's value here too.  There lg_parts == 0 (no halves wanted) is one slot per pixel: `parts` and `dif_parts` are NULL and not
+// written, and the record has k_resolve_pixels' bytes.  Without SPLIT the three diffuse arguments are NULL and nothing of them is compiled.
+template <bool SPLIT>
+__global__ __launch_bounds__(RR_BLOCK) void k_resolve_pixel_parts(DFrame fr, const uint32_t* __restrict__ slot_xy, DAccum acc, const long long* __restrict__ diffuse,
                                                                   uint32_t lg_parts, uint32_t from_xy, float4* __restrict__ out, float4* __restrict__ parts,
                                                                   float* __restrict__ dif_out, float* __restrict__ dif_parts) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // accumulator slot
     const bool live = p < fr.n_region_pixels;                 // (n_region_pixels: the slots, n_pixels * K)
     const uint32_t K = 1u << lg_parts;
-    long long w[10] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll}; // rgb, normal, depth, diffuse rgb
+    long long w[RECORD_SUMS] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll}, dw[3] = {0ll, 0ll, 0ll}; // rgb, normal, depth; diffuse rgb
     uint32_t nf = 0u, id = 0u;
     if (live) {
+        load_slot_sums(acc, p, w);
+        if (SPLIT) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            w[k] = acc.rgb[(unsigned long long)k * acc.n + p]; w[3 + k] = acc.normal[(unsigned long long)k * acc.n + p];
-            w[7 + k] = diffuse[(unsigned long long)k * acc.n + p];
+            for (int k = 0; k < 3; k++) dw[k] = diffuse[(unsigned long long)k * acc.n + p];
         }
-        w[6] = acc.depth[p];
         nf = acc.flags[p];
         id = acc.object_id[p];
     }
-    const float n_part = (float)(fr.samples >> lg_parts);
-    float c[3], dc[3];
+    id = (uint32_t)__shfl((int)id, (int)((threadIdx.x & (RR_WAVE - 1)) | (K - 1u))); // the group's last slot holds sample S - 1
+    const float n_part = (float)(fr.samples >> lg_parts), n = (float)fr.samples;
+    const Record part = resolve_record_sums(w, nf, id, n_part);
+    float dc[3] = {0.0f, 0.0f, 0.0f};
+    if (SPLIT) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) { c[k] = resolve_color_sum(w[k], nf, k, n_part); dc[k] = resolve_color_sum(w[7 + k], nf, k, n_part); }
-    const f3 nn = resolve_normal_sum(w[3], w[4], w[5], nf, n_part);
-    const float depth = resolve_depth_sum(w[6], nf, n_part);
+        for (int k = 0; k < 3; k++) dc[k] = resolve_color_sum(dw[k], nf, k, n_part);
+    }
     for (uint32_t off = 1u; off < K; off <<= 1) { // (wave-uniform trip count)
 #pragma unroll
-        for (int k = 0; k < 10; k++) w[k] += shfl_xor_ll(w[k], (int)off);
+        for (int k = 0; k < RECORD_SUMS; k++) w[k] += shfl_xor_ll(w[k], (int)off);
+        if (SPLIT) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) dw[k] += shfl_xor_ll(dw[k], (int)off);
+        }
         nf |= (uint32_t)__shfl_xor((int)nf, (int)off);
     }
-    id = (uint32_t)__shfl((int)id, (int)((threadIdx.x & (RR_WAVE - 1)) | (K - 1u))); // the group's last slot holds sample S - 1
     if (!live) return;
-    uint32_t o = p >> lg_parts; // the pixel's record index; its parts follow each other at o * K
-    if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
-    if (parts) {
+    const uint32_t o = from_xy ? frame_index(slot_xy[p], fr.width) : p >> lg_parts; // the pixel's record index; its parts follow each other at o * K
+    if (!SPLIT || parts) {
         const unsigned long long q = ((unsigned long long)o << lg_parts) + (p & (K - 1u));
-        parts[2ull * q] = make_float4(c[0], c[1], c[2], depth);
-        parts[2ull * q + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(id));
+        store_record(parts, q, part);
+        if (SPLIT) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) dif_parts[3ull * q + k] = dc[k];
+            for (int k = 0; k < 3; k++) dif_parts[3ull * q + k] = dc[k];
+        }
     }
     if ((p & (K - 1u)) != 0u) return;
-    const float n = (float)fr.samples;
+    store_record(out, o, resolve_record_sums(w, nf, id, n));
+    if (SPLIT) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) { c[k] = resolve_color_sum(w[k], nf, k, n); dif_out[3ull * o + k] = resolve_color_sum(w[7 + k], nf, k, n); }
-    const f3 fn = resolve_normal_sum(w[3], w[4], w[5], nf, n);
-    out[2ull * o] = make_float4(c[0], c[1], c[2], resolve_depth_sum(w[6], nf, n));
-    out[2ull * o + 1] = make_float4(fn.x, fn.y, fn.z, __uint_as_float(id));
+        for (int k = 0; k < 3; k++) dif_out[3ull * o + k] = resolve_color_sum(dw[k], nf, k, n);
+    }
 }
 
 // ---------------------------------------------------------------------------
-// kernels 5l .. 5p: find the noisy pixels of a frame and refine them on the device (rr_refine_list_device, rr_render_adaptive)
+// kernels 5l .. 5p: find the noisy entries of a frame or of a list and refine them on the device (rr_refine_list_device,
+// rr_refine_sublist_device, rr_render_adaptive, rr_render_adaptive_levels)
 // ---------------------------------------------------------------------------
-// The list of adaptive.refine_list (rustray_amd/adaptive.py) as an order-preserving stream compaction in three launches, and the two
-// passes that put a refined frame together.  The frame's 8x8 blocks, row-major, ARE the list's order (rr_adaptive.h), and on wave64 one
-// wave is one block: lane l is the block's pixel l, __ballot of the lanes' flags is the block's 64-bit refine mask, and a set lane's
-// place inside its block is the number of set bits below it.  No kernel waits for another workgroup: the scan between the two wave
-// kernels is a launch of its own.
+// The lists of adaptive.refine_list and adaptive.refine_sublist (rustray_amd/adaptive.py) as an order-preserving stream compaction in
+// three launches, and the passes that put a refined frame together.  One body per launch serves both lists: what differs is the entry
+// SOURCE (rr_adaptive.h), which tells lane l of wave w whether it has an entry, where the entry's part records lie and which word it
+// adds to the list.  FrameSource: the frame's 8x8 blocks, row-major, ARE the list's order, and on wave64 one wave is one block: lane l
+// is the block's pixel l, __ballot of the lanes' flags is the block's 64-bit refine mask, and a set lane's place inside its block is the
+// number of set bits below it.  ListSource: one wave per 64 consecutive entries of a list; the entries' coordinates are not
+// interpreted: there is no frame there.  No kernel waits for another workgroup: the scan between the two wave kernels is a launch of its own.
 //
-// 5l: parts = the K = 2 part records of the whole frame (k_resolve_pixel_parts, from_xy: two float4 per part at (y * width + x) * 2 + h).
-// A lane loads the colour float4 of its pixel's two halves (the 8 lanes of a block row: 512 consecutive bytes), error_out (or NULL) gets
-// half_error at y * width + x, and lane 0 stores the block's mask and its popcount.  Lanes outside the frame load nothing and flag nothing.
-__global__ __launch_bounds__(RR_BLOCK) void k_refine_masks(const float4* __restrict__ parts, uint32_t width, uint32_t height, uint32_t n_blocks, float threshold,
-                                                           float* __restrict__ error_out, unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
-    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE);
-    for (uint32_t b = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; b < n_blocks; b += waves) { // (wave-uniform)
-        uint32_t xy = 0u;
-        const bool present = refine_position_pixel(((unsigned long long)b << 6) | lane, width, height, &xy);
+// the tail of every masks kernel (5l, 5t): the wave's ballot of `flag` and its popcount, stored by lane 0
+RR_DEV void store_wave_mask(bool flag, uint32_t lane, uint32_t w, unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
+    const unsigned long long mask = __ballot(flag);
+    if (lane == 0u) { masks[w] = mask; counts[w] = (uint32_t)__popcll(mask); }
+}
+
+// 5l: parts = the K = 2 part records of the source (k_resolve_pixel_parts: two float4 per part; a frame's at (y * width + x) * 2 + h, a
+// list's entry i at 2 i + h).  A lane loads the colour of its entry's two halves (the 8 lanes of a block row: 512 consecutive bytes; the
+// lanes of a list's wave: 4 KB), error_out (or NULL) gets half_error at the entry's index, and lane 0 stores the wave's mask and its
+// popcount.  Lanes without an entry -- outside the frame, behind `count` -- load nothing and flag nothing: what lies behind a list, the
+// caller's own pad, is never looked at.
+template <class Source>
+__global__ __launch_bounds__(RR_BLOCK) void k_refine_masks(const Source src, const float4* __restrict__ parts, float threshold, float* __restrict__ error_out,
+                                                           unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = src.waves();
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        uint32_t i = 0u, word = 0u;
         bool flag = false;
-        if (present) {
-            const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
-            const float4 a = parts[4ull * o], c = parts[4ull * o + 2];
-            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
-            const float e = half_error(ca, cb);
-            if (error_out) error_out[o] = e;
+        if (src.entry(w, lane, &i, &word)) {
+            const float e = half_error_of_parts(parts, i);
+            if (error_out) error_out[i] = e;
             flag = e > threshold;
         }
-        const unsigned long long mask = __ballot(flag);
-        if (lane == 0u) { masks[b] = mask; counts[b] = (uint32_t)__popcll(mask); }
+        store_wave_mask(flag, lane, w, masks, counts);
     }
 }
 
@@ -1398,37 +1355,42 @@ __global__ __launch_bounds__(1024) void k_refine_scan(uint32_t* __restrict__ cou
     if (t == 0u) *total = carry;
 }
 
-// 5n: one wave per block again; it reads the block's mask and offset only.  A lane whose bit is set writes its pixel x | y << 16 at
-// offset + (set bits below the lane).  The wave that holds the list's last entry -- the last block with any bit set: its offset plus its
-// popcount is the total -- also writes the pad: copies of that entry up to the next multiple of 64 (fewer than 64: one per lane).
-__global__ __launch_bounds__(RR_BLOCK) void k_refine_scatter(const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ total,
-                                                             uint32_t width, uint32_t height, uint32_t n_blocks, uint32_t* __restrict__ list) {
-    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE);
-    const uint32_t count = *total;
-    for (uint32_t b = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; b < n_blocks; b += waves) { // (wave-uniform)
-        const unsigned long long mask = masks[b];
+// 5n: one wave per block or per 64 entries again.  A lane whose bit is set writes its word -- its pixel x | y << 16, or its entry
+// list[64 w + l] -- at offset + (set bits below the lane).  The wave that holds the list's last entry -- the last one with any bit set:
+// its offset plus its popcount is the total -- also writes the pad: copies of that entry up to the next multiple of 64 (fewer than 64:
+// one per lane); only that wave knows the entry, and it writes nothing another wave writes.  With a ListSource list_out does not
+// overlap the source's list (the host refuses it): a wave may write where another has yet to read.
+template <class Source>
+__global__ __launch_bounds__(RR_BLOCK) void k_refine_scatter(const Source src, const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ offsets,
+                                                             const uint32_t* __restrict__ total, uint32_t* __restrict__ list_out) {
+    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = src.waves();
+    const uint32_t taken = *total;
+    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
+        const unsigned long long mask = masks[w];
         if (mask == 0ull) continue;
-        const uint32_t off = offsets[b];
-        uint32_t xy = 0u;
-        (void)refine_position_pixel(((unsigned long long)b << 6) | lane, width, height, &xy); // (a set bit is a pixel of the frame: k_refine_masks)
-        if ((mask >> lane) & 1ull) list[off + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = xy;
-        if (off + (uint32_t)__popcll(mask) != count) continue;
-        const uint32_t last = (uint32_t)__shfl((int)xy, 63 - __clzll((long long)mask)); // the highest set lane's pixel
-        if (count + lane < refine_padded(count)) list[count + lane] = last;
+        const uint32_t off = offsets[w];
+        uint32_t i = 0u, word = 0u;
+        (void)src.entry(w, lane, &i, &word);
+        if ((mask >> lane) & 1ull) list_out[off + refine_mask_rank(mask, lane)] = word; // (a set bit is a lane with an entry: k_refine_masks)
+        if (!sublist_wave_is_last(mask, off, taken)) continue;
+        const uint32_t last = (uint32_t)__shfl((int)word, (int)sublist_last_lane(mask));
+        uint32_t at = 0u;
+        if (sublist_pad_word(taken, lane, &at)) list_out[at] = last;
     }
 }
 
-// 5o: fine record i (two float4) -> out at the pixel of list entry i, for the `count` entries before the pad; samples_out (or NULL) names
-// the sample count there.  The entries before the pad are distinct pixels of the frame (k_refine_scatter).
-__global__ __launch_bounds__(RR_BLOCK) void k_scatter_records(const uint32_t* __restrict__ list, const uint32_t* __restrict__ count, const float4* __restrict__ fine, uint32_t width,
-                                                              uint16_t max_samples, float4* __restrict__ out, uint16_t* __restrict__ samples_out) {
-    const uint32_t n = *count;
+// 5o: a pass's records over the frame: full record i (two float4) -> out at the pixel of list entry i, for the n entries before the
+// pad; samples_out (or NULL) gets the pass's sample count there and error_out (or NULL) half_error of the entry's two halves at this
+// count, the bits k_refine_masks computes from the same floats (`parts` is read for error_out only: rr_render_adaptive passes neither).
+// The entries before the pad are distinct pixels of the frame: k_refine_scatter's list, or a sub-sequence of it.
+__global__ __launch_bounds__(RR_BLOCK) void k_scatter_level(const uint32_t* __restrict__ list, uint32_t n, const float4* __restrict__ fine, const float4* __restrict__ parts,
+                                                            uint32_t width, uint16_t samples, float4* __restrict__ out, uint16_t* __restrict__ samples_out,
+                                                            float* __restrict__ error_out) {
     for (uint32_t i = blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += gridDim.x * RR_BLOCK) {
-        const uint32_t xy = list[i];
-        const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
-        out[2ull * o] = fine[2ull * i];
-        out[2ull * o + 1] = fine[2ull * i + 1];
-        if (samples_out) samples_out[o] = max_samples;
+        const uint32_t o = frame_index(list[i], width);
+        store_record(out, o, load_record(fine, i));
+        if (samples_out) samples_out[o] = samples;
+        if (error_out) error_out[o] = half_error_of_parts(parts, i);
     }
 }
 
@@ -1442,83 +1404,12 @@ __global__ __launch_bounds__(RR_BLOCK) void k_record_bytes(const float4* __restr
 }
 
 // ---------------------------------------------------------------------------
-// kernels 5q .. 5s: the list of a list, and a level of a frame refined level by level (rr_refine_sublist_device, rr_render_adaptive_levels)
-// ---------------------------------------------------------------------------
-// adaptive.refine_sublist as the compaction above, over the entries of a LIST instead of the blocks of a frame: one wave per 64
-// consecutive entries, k_refine_scan between the two wave kernels as it is, no kernel waiting for another workgroup.  The entries'
-// coordinates are not interpreted: there is no frame here.
-//
-// 5q: parts = the K = 2 part records of the list (k_resolve_pixel_parts on a list: two float4 per part, entry i's halves at 2 i and 2 i + 1).
-// Lane l of wave w loads the colour float4 of the two halves of entry 64 w + l (64 consecutive bytes per lane, 4 KB per wave), error_out
-// (or NULL) gets half_error at the entry's index, and lane 0 stores the wave's mask and its popcount.  Lanes behind `count` load nothing
-// and flag nothing: what lies there -- the caller's own pad -- is never looked at.
-__global__ __launch_bounds__(RR_BLOCK) void k_sublist_masks(const float4* __restrict__ parts, uint32_t count, float threshold, float* __restrict__ error_out,
-                                                            unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts) {
-    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
-    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
-        uint32_t i = 0u;
-        bool flag = false;
-        if (sublist_lane_entry(w, lane, count, &i)) {
-            const float4 a = parts[4ull * i], c = parts[4ull * i + 2];
-            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
-            const float e = half_error(ca, cb);
-            if (error_out) error_out[i] = e;
-            flag = e > threshold;
-        }
-        const unsigned long long mask = __ballot(flag);
-        if (lane == 0u) { masks[w] = mask; counts[w] = (uint32_t)__popcll(mask); }
-    }
-}
-
-// 5r: one wave per 64 entries again.  A lane whose bit is set writes its entry list[64 w + l] at offset + (set bits below the lane); the
-// wave that holds the last taken entry also writes the pad, copies of that entry up to the next multiple of 64.  list_out does not
-// overlap list (the host refuses it): a wave may write where another has yet to read.
-__global__ __launch_bounds__(RR_BLOCK) void k_sublist_scatter(const uint32_t* __restrict__ list, uint32_t count, const unsigned long long* __restrict__ masks,
-                                                              const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ total, uint32_t* __restrict__ list_out) {
-    const uint32_t lane = threadIdx.x & (RR_WAVE - 1), waves = gridDim.x * (RR_BLOCK / RR_WAVE), n_waves = sublist_waves(count);
-    const uint32_t taken = *total;
-    for (uint32_t w = blockIdx.x * (RR_BLOCK / RR_WAVE) + threadIdx.x / RR_WAVE; w < n_waves; w += waves) { // (wave-uniform)
-        const unsigned long long mask = masks[w];
-        if (mask == 0ull) continue;
-        const uint32_t off = offsets[w];
-        uint32_t i = 0u, xy = 0u;
-        if (sublist_lane_entry(w, lane, count, &i)) xy = list[i];
-        if ((mask >> lane) & 1ull) list_out[off + refine_mask_rank(mask, lane)] = xy; // (a set bit is an entry before `count`: k_sublist_masks)
-        if (!sublist_wave_is_last(mask, off, taken)) continue;
-        const uint32_t last = (uint32_t)__shfl((int)xy, (int)sublist_last_lane(mask));
-        uint32_t at = 0u;
-        if (sublist_pad_word(taken, lane, &at)) list_out[at] = last;
-    }
-}
-
-// 5s: a level's records over the frame, in the manner of k_scatter_records: full record i (two float4) -> out at the pixel of list entry
-// i, for the n entries before the pad; samples_out (or NULL) gets the level's count there and error_out (or NULL) half_error of the
-// entry's two halves at this count, the bits k_sublist_masks computes from the same floats.  The entries before the pad are distinct
-// pixels of the frame: a sub-sequence of k_refine_scatter's list.
-__global__ __launch_bounds__(RR_BLOCK) void k_scatter_level(const uint32_t* __restrict__ list, uint32_t n, const float4* __restrict__ fine, const float4* __restrict__ parts,
-                                                            uint32_t width, uint16_t samples, float4* __restrict__ out, uint16_t* __restrict__ samples_out,
-                                                            float* __restrict__ error_out) {
-    for (uint32_t i = blockIdx.x * RR_BLOCK + threadIdx.x; i < n; i += gridDim.x * RR_BLOCK) {
-        const uint32_t xy = list[i];
-        const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
-        out[2ull * o] = fine[2ull * i];
-        out[2ull * o + 1] = fine[2ull * i + 1];
-        if (samples_out) samples_out[o] = samples;
-        if (error_out) {
-            const float4 a = parts[4ull * i], c = parts[4ull * i + 2];
-            const float ca[3] = {a.x, a.y, a.z}, cb[3] = {c.x, c.y, c.z};
-            error_out[o] = half_error(ca, cb);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // kernels 5t, 5u: a level of a frame whose refined pixels KEEP their samples (rr_render_adaptive_prefix)
 // ---------------------------------------------------------------------------
 // The accumulators of a level stay on the device from level to level: entry i of the level's list owns slots 2 i and 2 i + 1 of `acc`
 // (rr_adaptive.h: the halves s mod 2 of rr_render_pixel_parts at K = 2), and the next level adds only the samples the entry does not have
 // yet.  So nothing here reads a float that another kernel wrote: the records, the error and the refine mask of an entry all come from its
-// integer sums in one pass, where k_resolve_pixel_parts, k_scatter_level and k_sublist_masks hand two part records per entry through HBM.
+// integer sums in one pass, where k_resolve_pixel_parts, k_scatter_level and k_refine_masks hand two part records per entry through HBM.
 // One wave per 64 consecutive entries, k_refine_scan between the two wave kernels as it is, no kernel waiting for another workgroup.
 // Level 0 is the whole frame in the region's slot order, which IS the list order of a frame (8x8 blocks row-major, row-major inside);
 // there the pixel of entry i is the slot table's word 2 i (xy_stride 2: k_pixel_slots wrote every entry twice), for a list it is list[i]
@@ -1526,6 +1417,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_scatter_level(const uint32_t* __re
 //
 // the two slots of an entry: one 16-byte access per 8-byte plane, one 8-byte access for the ids and the flags
 struct PrefixEntry { long long w[2][PREFIX_PLANES]; uint32_t id[2], nf[2]; };
+static_assert(PREFIX_PLANES == RECORD_SUMS, "a set's planes are a slot's sums in resolve_record_sums' order");
 RR_DEV void prefix_load_entry(const DAccum& acc, uint32_t i, PrefixEntry* e) {
     const unsigned long long p = prefix_entry_slot(i);
 #pragma unroll
@@ -1568,27 +1460,23 @@ __global__ __launch_bounds__(RR_BLOCK) void k_prefix_masks(DAccum acc, const uin
         if (sublist_lane_entry(w, lane, count, &i)) {
             PrefixEntry e;
             prefix_load_entry(acc, i, &e);
-            float ca[3], cb[3], c[3];
-            const uint32_t nf = e.nf[0] | e.nf[1];
+            float ca[3], cb[3];
+            long long sum[RECORD_SUMS];
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 ca[k] = resolve_color_sum(e.w[0][k], e.nf[0], k, n_half);
                 cb[k] = resolve_color_sum(e.w[1][k], e.nf[1], k, n_half);
-                c[k] = resolve_color_sum(e.w[0][k] + e.w[1][k], nf, k, n_full);
             }
-            const f3 nn = resolve_normal_sum(e.w[0][3] + e.w[1][3], e.w[0][4] + e.w[1][4], e.w[0][5] + e.w[1][5], nf, n_full);
-            const float depth = resolve_depth_sum(e.w[0][6] + e.w[1][6], nf, n_full);
-            const uint32_t xy = xy_table[(unsigned long long)i * xy_stride];
-            const unsigned long long o = (unsigned long long)(xy >> 16) * width + (xy & 0xffffu);
-            out[2ull * o] = make_float4(c[0], c[1], c[2], depth);
-            out[2ull * o + 1] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(e.id[1]));
+#pragma unroll
+            for (int k = 0; k < RECORD_SUMS; k++) sum[k] = e.w[0][k] + e.w[1][k];
+            const uint32_t o = frame_index(xy_table[(unsigned long long)i * xy_stride], width);
+            store_record(out, o, resolve_record_sums(sum, e.nf[0] | e.nf[1], e.id[1], n_full));
             const float err = half_error(ca, cb);
             if (samples_out) samples_out[o] = (uint16_t)samples;
             if (error_out) error_out[o] = err;
             flag = err > threshold;
         }
-        const unsigned long long mask = __ballot(flag);
-        if (lane == 0u) { masks[w] = mask; counts[w] = (uint32_t)__popcll(mask); }
+        store_wave_mask(flag, lane, w, masks, counts);
     }
 }
 
@@ -1754,6 +1642,35 @@ __global__ __launch_bounds__(RR_BLOCK) void k_unpack_hits(const uint4* __restric
 // would share four banks), and so do the lanes of the ds_read_b128 on the way out, which read 8 consecutive units of one ray.
 //   r0[i] = (origin, .), r1[i] = (direction, .): k_pack_rays' records; hits[i]: k_trace_closest's
 //   a miss, or an item index out of range: {0, 0xffffffff, 0, 0} and 112 zero bytes
+//
+// The eight rows of ray i's rr_surface_hit, the miss record included (5h and 5w).  ALL_ROWS = false (the albedo-only build of 5w): a hit
+// fills only row 4, base_color; surface_at is evaluated in full either way and the compiler drops what nothing stores.
+template <bool ALL_ROWS>
+RR_DEV void surface_rows(const DSceneView& sc, const float4* __restrict__ r0, const float4* __restrict__ r1, const uint4* __restrict__ hits, unsigned long long i,
+                         const float* s_lut, uint4 (&row)[8]) {
+    const uint4 h = hits[i];
+    row[0] = make_uint4(0u, 0xffffffffu, 0u, 0u);
+#pragma unroll
+    for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
+    if (!((int32_t)h.y >= 0 && h.y < sc.n_items)) return;
+    const DItem& it = rr_global(sc.items)[h.y];
+    const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
+    const float4 a = r0[i], b = r1[i];
+    const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);
+    row[4] = make_uint4(__float_as_uint(s.base_color.x), __float_as_uint(s.base_color.y), __float_as_uint(s.base_color.z), __float_as_uint(s.base_color.w));
+    if (!ALL_ROWS) return;
+    const uint32_t face = reference_face_id(&it, rr_global(sc.trix), h.z);
+    row[0] = make_uint4(1u, h.y, it.id, face);
+    row[1] = make_uint4(__float_as_uint(s.position.x), __float_as_uint(s.position.y), __float_as_uint(s.position.z), h.x);
+    row[2] = make_uint4(__float_as_uint(s.normal.x), __float_as_uint(s.normal.y), __float_as_uint(s.normal.z), (uint32_t)it.material);
+    row[3] = make_uint4(__float_as_uint(s.shading_normal.x), __float_as_uint(s.shading_normal.y), __float_as_uint(s.shading_normal.z), s.has_uv ? 1u : 0u);
+    row[5] = make_uint4(__float_as_uint(s.ambient_color.x), __float_as_uint(s.ambient_color.y), __float_as_uint(s.ambient_color.z), __float_as_uint(s.alpha));
+    row[6] = make_uint4(__float_as_uint(s.specular_color.x), __float_as_uint(s.specular_color.y), __float_as_uint(s.specular_color.z), __float_as_uint(s.reflectivity));
+    row[7] = make_uint4(__float_as_uint(s.uv.x), __float_as_uint(s.uv.y), __float_as_uint(s.roughness), __float_as_uint(s.ambient_occlusion));
+}
+// where row r of ray t of a round sits in the workgroup's LDS image, in 16-byte units (the swizzle above)
+RR_DEV uint32_t surface_row_unit(uint32_t t, uint32_t r) { return 8u * t + (r ^ (t & 7u)); }
+
 __global__ __launch_bounds__(RR_BLOCK) void k_surface_hits(DSceneView sc, const float4* __restrict__ r0, const float4* __restrict__ r1, const uint4* __restrict__ hits,
                                                            uint32_t n, uint4* __restrict__ out) {
     __shared__ uint4 s_rows[8 * RR_BLOCK];
@@ -1765,36 +1682,17 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_hits(DSceneView sc, const 
     for (unsigned long long base = (unsigned long long)blockIdx.x * RR_BLOCK; base < n; base += (unsigned long long)gridDim.x * RR_BLOCK) { // block-uniform
         const unsigned long long i = base + tid;
         if (i < n) {
-            const uint4 h = hits[i];
             uint4 row[8];
-            row[0] = make_uint4(0u, 0xffffffffu, 0u, 0u);
+            surface_rows<true>(sc, r0, r1, hits, i, s_lut, row);
 #pragma unroll
-            for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
-            if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
-                const DItem& it = rr_global(sc.items)[h.y];
-                const uint32_t face = reference_face_id(&it, rr_global(sc.trix), h.z);
-                const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
-                const float4 a = r0[i], b = r1[i];
-                const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);
-                row[0] = make_uint4(1u, h.y, it.id, face);
-                row[1] = make_uint4(__float_as_uint(s.position.x), __float_as_uint(s.position.y), __float_as_uint(s.position.z), h.x);
-                row[2] = make_uint4(__float_as_uint(s.normal.x), __float_as_uint(s.normal.y), __float_as_uint(s.normal.z), (uint32_t)it.material);
-                row[3] = make_uint4(__float_as_uint(s.shading_normal.x), __float_as_uint(s.shading_normal.y), __float_as_uint(s.shading_normal.z), s.has_uv ? 1u : 0u);
-                row[4] = make_uint4(__float_as_uint(s.base_color.x), __float_as_uint(s.base_color.y), __float_as_uint(s.base_color.z), __float_as_uint(s.base_color.w));
-                row[5] = make_uint4(__float_as_uint(s.ambient_color.x), __float_as_uint(s.ambient_color.y), __float_as_uint(s.ambient_color.z), __float_as_uint(s.alpha));
-                row[6] = make_uint4(__float_as_uint(s.specular_color.x), __float_as_uint(s.specular_color.y), __float_as_uint(s.specular_color.z), __float_as_uint(s.reflectivity));
-                row[7] = make_uint4(__float_as_uint(s.uv.x), __float_as_uint(s.uv.y), __float_as_uint(s.roughness), __float_as_uint(s.ambient_occlusion));
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) s_rows[8u * tid + (k ^ (tid & 7u))] = row[k];
+            for (uint32_t k = 0; k < 8u; k++) s_rows[surface_row_unit(tid, k)] = row[k];
         }
         __syncthreads();
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) {
             const uint32_t u = k * RR_BLOCK + tid;      // unit of the output image: row u % 8 of ray u / 8
-            const uint32_t t = u >> 3;
             const unsigned long long g = 8ull * base + u;
-            if (g < n_rows) out[g] = s_rows[8u * t + ((u & 7u) ^ (t & 7u))];
+            if (g < n_rows) out[g] = s_rows[surface_row_unit(u >> 3, u & 7u)];
         }
         __syncthreads(); // the next round overwrites the image
     }
@@ -1827,7 +1725,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_pixel_rays(const PixelCam cam, uin
             if (!pixel_in_frame(xy, width, height)) bad = min(bad, i);
         } else {
             xy = pixel_of_block_slot(i, width, height);
-            target[i] = (xy >> 16) * width + (xy & 0xffffu);
+            target[i] = frame_index(xy, width);
         }
         float o[3], d[3];
         pixel_ray(cam.proj_inv, cam.view_inv, xy, w, h, o, d);
@@ -1835,11 +1733,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_pixel_rays(const PixelCam cam, uin
         r1[i] = make_float4(d[0], d[1], d[2], 0.0f);
         r2[i] = make_uint2(1u << 16, 1u);
     }
-    if (pixel_xy) { // (kernel-uniform)
-#pragma unroll
-        for (int off = RR_WAVE / 2; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off));
-        if ((threadIdx.x & (RR_WAVE - 1)) == 0u && bad != 0xffffffffu) atomicMin(first_bad, bad);
-    }
+    if (pixel_xy) first_bad_merge(bad, first_bad); // (kernel-uniform)
 }
 
 // 5w: the ending of 5h for these rays.  Ray i answers record target[i] (target == NULL: record i): with RECORDS its rr_surface_hit goes to
@@ -1850,6 +1744,17 @@ __global__ __launch_bounds__(RR_BLOCK) void k_pixel_rays(const PixelCam cam, uin
 // store instruction covers eight whole lines wherever the targets lie.  The albedo leaves lane-strided through a 3 KB image as 5f's words
 // do: consecutive dwords for a list, runs of 24 dwords (a row of an 8x8 block) for a whole frame.
 //   a miss, or an item index out of range: {0, 0xffffffff, 0, 0} and 112 zero bytes; albedo 0, 0, 0
+//
+// The way out of a 3 KB image (5w and 5y).  A workgroup's 3-word-per-entry image (s_albedo: entry t of the round at words 3 t .. 3 t + 2; s_target[t]: its record) ->
+// albedo[3 target + c], lane-strided, for the first in_round entries.  The caller has synchronised behind the image's last store.
+RR_DEV void store_albedo_image(const uint32_t* s_albedo, const uint32_t* s_target, uint32_t tid, uint32_t in_round, uint32_t* __restrict__ albedo) {
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        const uint32_t word = k * RR_BLOCK + tid; // word of the image: channel word % 3 of entry word / 3 of this round
+        const uint32_t t = word / 3u;
+        if (t < in_round) albedo[3ull * s_target[t] + (word - 3u * t)] = s_albedo[word];
+    }
+}
 template <bool RECORDS, bool ALBEDO>
 __global__ __launch_bounds__(RR_BLOCK) void k_surface_pixels(DSceneView sc, const float4* __restrict__ r0, const float4* __restrict__ r1, const uint4* __restrict__ hits,
                                                              uint32_t n, const uint32_t* __restrict__ target, uint4* __restrict__ out, uint32_t* __restrict__ albedo) {
@@ -1864,31 +1769,11 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_pixels(DSceneView sc, cons
         const unsigned long long i = base + tid;
         const uint32_t in_round = (uint32_t)(n - base < RR_BLOCK ? n - base : RR_BLOCK); // rays of this round
         if (i < n) {
-            const uint4 h = hits[i];
             uint4 row[8];
-            row[0] = make_uint4(0u, 0xffffffffu, 0u, 0u);
-#pragma unroll
-            for (int k = 1; k < 8; k++) row[k] = make_uint4(0u, 0u, 0u, 0u);
-            if ((int32_t)h.y >= 0 && h.y < sc.n_items) {
-                const DItem& it = rr_global(sc.items)[h.y];
-                const MatR m = load_material(&rr_global(sc.materials)[it.material], s_lut);
-                const float4 a = r0[i], b = r1[i];
-                const SurfaceAt s = surface_at(sc, it, m, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), __uint_as_float(h.x), h.z);
-                row[4] = make_uint4(__float_as_uint(s.base_color.x), __float_as_uint(s.base_color.y), __float_as_uint(s.base_color.z), __float_as_uint(s.base_color.w));
-                if (RECORDS) {
-                    const uint32_t face = reference_face_id(&it, rr_global(sc.trix), h.z);
-                    row[0] = make_uint4(1u, h.y, it.id, face);
-                    row[1] = make_uint4(__float_as_uint(s.position.x), __float_as_uint(s.position.y), __float_as_uint(s.position.z), h.x);
-                    row[2] = make_uint4(__float_as_uint(s.normal.x), __float_as_uint(s.normal.y), __float_as_uint(s.normal.z), (uint32_t)it.material);
-                    row[3] = make_uint4(__float_as_uint(s.shading_normal.x), __float_as_uint(s.shading_normal.y), __float_as_uint(s.shading_normal.z), s.has_uv ? 1u : 0u);
-                    row[5] = make_uint4(__float_as_uint(s.ambient_color.x), __float_as_uint(s.ambient_color.y), __float_as_uint(s.ambient_color.z), __float_as_uint(s.alpha));
-                    row[6] = make_uint4(__float_as_uint(s.specular_color.x), __float_as_uint(s.specular_color.y), __float_as_uint(s.specular_color.z), __float_as_uint(s.reflectivity));
-                    row[7] = make_uint4(__float_as_uint(s.uv.x), __float_as_uint(s.uv.y), __float_as_uint(s.roughness), __float_as_uint(s.ambient_occlusion));
-                }
-            }
+            surface_rows<RECORDS>(sc, r0, r1, hits, i, s_lut, row);
             if (RECORDS) {
 #pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) s_rows[8u * tid + (k ^ (tid & 7u))] = row[k];
+                for (uint32_t k = 0; k < 8u; k++) s_rows[surface_row_unit(tid, k)] = row[k];
             }
             if (ALBEDO) { s_albedo[3u * tid] = row[4].x; s_albedo[3u * tid + 1u] = row[4].y; s_albedo[3u * tid + 2u] = row[4].z; }
             s_target[tid] = target ? target[i] : (uint32_t)i;
@@ -1899,17 +1784,10 @@ __global__ __launch_bounds__(RR_BLOCK) void k_surface_pixels(DSceneView sc, cons
             for (uint32_t k = 0; k < 8u; k++) {
                 const uint32_t u = k * RR_BLOCK + tid; // unit of the image: row u % 8 of ray u / 8 of this round
                 const uint32_t t = u >> 3;
-                if (t < in_round) out[8ull * s_target[t] + (u & 7u)] = s_rows[8u * t + ((u & 7u) ^ (t & 7u))];
+                if (t < in_round) out[8ull * s_target[t] + (u & 7u)] = s_rows[surface_row_unit(t, u & 7u)];
             }
         }
-        if (ALBEDO) {
-#pragma unroll
-            for (uint32_t k = 0; k < 3u; k++) {
-                const uint32_t word = k * RR_BLOCK + tid; // word of the image: channel word % 3 of ray word / 3 of this round
-                const uint32_t t = word / 3u;
-                if (t < in_round) albedo[3ull * s_target[t] + (word - 3u * t)] = s_albedo[word];
-            }
-        }
+        if (ALBEDO) store_albedo_image(s_albedo, s_target, tid, in_round, albedo);
         __syncthreads(); // the next round overwrites the images
     }
 }
@@ -1969,21 +1847,14 @@ __global__ __launch_bounds__(RR_BLOCK) void k_resolve_albedo(DFrame fr, const ui
     const uint32_t p = base + tid; // accumulator slot
     const uint32_t in_round = base < npix ? min(npix - base, (uint32_t)RR_BLOCK) : 0u; // slots of this workgroup
     if (p < npix) {
-        uint32_t o = p;
-        if (from_xy) { const uint32_t xy = slot_xy[p]; o = (xy >> 16) * fr.width + (xy & 0xffffu); }
         const float n = (float)fr.samples;
         const uint32_t nf = acc.flags[p];
 #pragma unroll
         for (int k = 0; k < 3; k++) s_albedo[3u * tid + k] = __float_as_uint(resolve_color(acc, p, nf, k, n));
-        s_target[tid] = o;
+        s_target[tid] = from_xy ? frame_index(slot_xy[p], fr.width) : p;
     }
     __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < 3u; k++) {
-        const uint32_t word = k * RR_BLOCK + tid; // word of the image: channel word % 3 of slot word / 3 of this workgroup
-        const uint32_t t = word / 3u;
-        if (t < in_round) albedo[3ull * s_target[t] + (word - 3u * t)] = s_albedo[word];
-    }
+    store_albedo_image(s_albedo, s_target, tid, in_round, albedo);
 }
 
 // 5g: stream ids 0 .. n - 1 (rr_shade_rays_device without the caller's)
