@@ -66,7 +66,9 @@ extern "C" {
  * rr_history_clamp_default_params, rr_accumulate_clamped_records and rr_accumulate_clamped_records_device (with rr_history_clamp_params, a
  * struct of its own) came after those, again without a change of any existing struct: a version-3 library may lack these three as well.
  * rr_accumulate_clamped_split_records and rr_accumulate_clamped_split_records_device came after those, without a struct of their own: a
- * version-3 library may lack these two as well. */
+ * version-3 library may lack these two as well.
+ * rr_upsample_default_params, rr_upsample_records and rr_upsample_records_device (with rr_upsample_params, a struct of its own) came
+ * after those, again without a change of any existing struct: a version-3 library may lack these three as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1506,6 +1508,72 @@ int rr_denoise_split_records(rr_scene* scene, uint32_t width, uint32_t height, c
                              const rr_radiance* records, const rr_radiance* halves /* or NULL */,
                              const float* diffuse, const float* diffuse_halves /* NULL exactly when halves is */,
                              const float* albedo /* or NULL */, rr_radiance* out, uint8_t* rgba8_out /* or NULL */);
+
+/* A frame traced at a LOW resolution raised to the full one: a joint-bilateral upsampler guided by the G-buffer of the camera at both
+ * sizes.  Every call above works at the resolution that was traced; this one lets a caller trace low_width x low_height pixels (a quarter
+ * of the primary rays at half the size each way) and show width x height.  The two guides are rr_surface_pixels(_device) of two cameras
+ * with the same matrices and the two sizes, which cost no shading; low and halves_low are rr_render_pixel_parts at n_parts = 2 on the
+ * small camera.  out (and halves_out) is a valid input of rr_denoise_records, rr_accumulate_records and rr_motion_records at width x height.
+ * EVERY STEP IS EXACT IN BINARY32 IN THE ORDER STATED HERE, as for rr_denoise_records: no transcendentals, no contraction, division
+ * correctly rounded; rustray_amd/upsample.py: upsample_records follows this text in numpy and gives the same bits.
+ *   W x H = width x height, w x h = low_width x low_height, 1 <= w <= W <= 65535 and 1 <= h <= H <= 65535; the ratios need not be whole.
+ *   low[q] (w * h records, pixel (x, y) at y * w + x) is the traced colour; halves_low (or NULL) w * h * 2 records in the K = 2 layout;
+ *   guide_low[q] (w * h) and guide[p] (W * H) are rr_surface_hit records, of which only rows 0, 1, 2 and 4 are read: hit, object_id,
+ *   distance, normal, base_color[0 .. 2].
+ *   fin_q: the three colour floats of low[q] are finite.  valid of a guide: hit != 0, and distance and the three normal floats are finite.
+ *   Position of full pixel (x, y) in the low frame: u = (((float)x + 0.5f) * (float)w) / (float)W - 0.5f, x0 = (int)floorf(u),
+ *   fx = u - (float)x0; the same for v, y0, fy with h and H.  The four taps are q = (x0 + dx, y0 + dy), dy outer, dx inner, each in
+ *   {0, 1}; b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy).  r = max((float)W / (float)w, (float)H / (float)h), once per call.
+ *   Guided sum.  A tap is skipped when q is outside the low frame; !fin_q; (guide_low[q].hit != 0) != (guide[p].hit != 0); both hit and
+ *   the object_ids differ; or valid_q != valid_p.  Otherwise wt = b, and if valid_p: cs = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;
+ *   cs = cs > 0 ? cs : 0; normal_power_log2 times cs = cs*cs; wt = wt * cs; t = |z_p - z_q| / ((sigma_depth * |z_p|) * r + EPS),
+ *   wt = wt / (1.0f + t*t); EPS = 2^-20.  With use_albedo and both sides hit, channel k of the tap's colour (and of its two half colours)
+ *   is demodulated by guide_low[q].base_color[k] as rr_denoise_records demodulates: c_k / a_k when 2^-10 < a_k <= FLT_MAX, else as it is.
+ *   sum_c[k] += wt * c_k, sum_w += wt, the halves' sums likewise with the same wt; all sums start at 0.
+ *   Result.  If 0 < sum_w <= FLT_MAX: colour = sum_c / sum_w, with use_albedo and guide[p].hit remodulated by guide[p].base_color[k]
+ *   (* a_k under the same condition); weight = sum_w.  Otherwise the FALLBACK: the same four taps again, a tap skipped only when q is
+ *   outside the frame or !fin_q, weight b, no albedo; colour = sum_c / sum_b when 0 < sum_b <= FLT_MAX, else three zeros; weight = 0.
+ *   The halves follow the colour in both cases.  A half colour that is not finite at a taken tap propagates into the half's sum; as for
+ *   rr_denoise_records, a NaN the arithmetic generates there (0 * inf, a sum of two NaNs) has unspecified sign and payload.
+ *   Guide fields of out[p], and of both halves_out records: for a hit, distance, normal and object_id of guide[p] -- a frame's record
+ *   holds an item's id as it is, so these are the id bits of a pixel all of whose rays hit that item; for a miss the bits
+ *   rr_render_pixels writes for a pixel all of whose rays missed: depth +0, every normal float the NaN 0xffc00000, object_id 0.
+ *   rgba8_out (or NULL): the bytes rr_render_pixels writes for the record out[p], with params->gamma_correction as rr_config's.
+ *   weight_out (or NULL): the weight above, W * H floats; 0 marks the pixels the guide found no tap for (a hole: a surface the low
+ *   frame did not see), which a caller may trace at full resolution.
+ * rr_upsample_params: struct_size = sizeof(rr_upsample_params); normal_power_log2 0 .. 7; sigma_depth finite and above 0.
+ * rr_upsample_default_params writes power 5, sigma_depth 0.05, use_albedo 1, no gamma; it never touches a device.
+ * rr_upsample_records_device follows rr_denoise_records_device: the scene handle serves for its device, its lock and its staging pool;
+ * every pointer is classified before any launch (RR_ERR_INVALID_ARGUMENT naming the argument); work is enqueued on `hip_stream` in stream
+ * order (the inputs may have been produced on that stream without a synchronisation) and the call does not wait inside;
+ * RR_ERR_INVALID_ARGUMENT from on_pass of the same scene; nothing of a frame's state or statistics is touched; a scene edit or
+ * rr_scene_destroy waits for a call in flight.  The call is one launch and keeps no device memory.
+ *   Refusals, in this order: a NULL scene, params, low, guide_low, guide or out; width or height 0 or above 65535, low_width or
+ *   low_height 0 or above the frame's; a struct_size other than sizeof(rr_upsample_params), a power out of range, a sigma_depth that is
+ *   NaN, infinite or <= 0; halves_out without halves_low or the reverse; (device form) low, halves_low, guide_low, guide, out or
+ *   halves_out not 16-byte aligned, rgba8_out or weight_out not 4-byte aligned; any overlap between an output and an input or between
+ *   two outputs (nothing is in place): all RR_ERR_INVALID_ARGUMENT.  Then width * height * 2 > 2^30: RR_ERR_UNSUPPORTED.
+ * rr_upsample_records: the same on HOST pointers, the device form on the null stream behind a staging copy in the pool of staging
+ * buffers the record calls share (32, 64 and 128 B per low pixel, 128 + 32 and 64, 4 and 4 B per pixel, each only where given); it
+ * returns with the outputs written. */
+typedef struct rr_upsample_params {
+    uint32_t struct_size;        /* sizeof(rr_upsample_params) */
+    uint32_t normal_power_log2;  /* 0 .. 7: the normal weight is max(0, n_p . n_q) squared this many times */
+    float    sigma_depth;        /* > 0, finite */
+    uint32_t use_albedo;         /* non-zero: the sum runs on albedo-demodulated colour */
+    uint32_t gamma_correction;   /* rgba8_out only, as rr_config's */
+} rr_upsample_params;
+int rr_upsample_default_params(rr_upsample_params* out);
+int rr_upsample_records_device(rr_scene* scene, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height, const rr_upsample_params* params,
+                               const rr_radiance* low_dev /* low_width * low_height */, const rr_radiance* halves_low_dev /* twice as many, or NULL */,
+                               const rr_surface_hit* guide_low_dev /* low_width * low_height */, const rr_surface_hit* guide_dev /* width * height */,
+                               rr_radiance* out_dev /* width * height */, rr_radiance* halves_out_dev /* width * height * 2; NULL exactly when halves_low_dev is */,
+                               uint8_t* rgba8_out_dev /* or NULL */, float* weight_out_dev /* width * height, or NULL */, void* hip_stream);
+int rr_upsample_records(rr_scene* scene, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height, const rr_upsample_params* params,
+                        const rr_radiance* low /* low_width * low_height */, const rr_radiance* halves_low /* twice as many, or NULL */,
+                        const rr_surface_hit* guide_low /* low_width * low_height */, const rr_surface_hit* guide /* width * height */,
+                        rr_radiance* out /* width * height */, rr_radiance* halves_out /* width * height * 2; NULL exactly when halves_low is */,
+                        uint8_t* rgba8_out /* or NULL */, float* weight_out /* width * height, or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

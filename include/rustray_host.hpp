@@ -840,6 +840,72 @@ public:
         return rr_surface_pixels_device(scene->handle(), &cam, xy_dev, n_pixels, out_dev, albedo_out_dev, hip_stream);
     }
 
+    // The joint-bilateral upsampler to a frame of this camera's size (rr_upsample_records): `low` low_width * low_height records of a frame
+    // traced at that size in row-major order, `halves_low` twice as many in the layout of render_pixel_parts at n_parts = 2 or nullptr,
+    // `guide_low` and `guide` the surface_pixels() of the small camera and of this one; `params` nullptr = rr_upsample_default_params.
+    // Returns width * height records whose depth, normal and id are the full guide's; halves_out (required exactly when halves_low is
+    // given) gets twice as many, weight (or nullptr) the guided sum's weight per pixel (0: the bilinear fallback answered), rgba8 (or
+    // nullptr) the frame's bytes of the records.  An empty vector = refused or failed (rr_last_error() says why).
+    std::vector<rr_radiance> upsample(uint32_t low_width, uint32_t low_height, const rr_radiance* low, const rr_radiance* halves_low, const rr_surface_hit* guide_low,
+                                      const rr_surface_hit* guide, const rr_upsample_params* params = nullptr, std::vector<rr_radiance>* halves_out = nullptr,
+                                      std::vector<float>* weight = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+        std::vector<rr_radiance> out;
+        const size_t n = (size_t)camera.width * camera.height;
+        rr_upsample_params prm;
+        if (params) prm = *params;
+        else if (rr_upsample_default_params(&prm) != RR_OK) return out;
+        if (n == 0 || n > ((size_t)1 << 29)) return out;
+        out.resize(n);
+        if (halves_out) halves_out->assign(2 * n, rr_radiance{});
+        if (weight) weight->assign(n, 0.0f);
+        if (rgba8) rgba8->assign(4 * n, 0);
+        if (rr_upsample_records(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low, halves_low, guide_low, guide, out.data(),
+                                halves_out ? halves_out->data() : nullptr, rgba8 ? rgba8->data() : nullptr, weight ? weight->data() : nullptr) != RR_OK) {
+            out.clear();
+            if (halves_out) halves_out->clear();
+            if (weight) weight->clear();
+            if (rgba8) rgba8->clear();
+        }
+        return out;
+    }
+    // the same on DEVICE buffers, in stream order (rr_upsample_records_device): one launch, not waited for; nothing may overlap
+    int upsample_device(uint32_t low_width, uint32_t low_height, const rr_upsample_params* params, const rr_radiance* low_dev, const rr_radiance* halves_low_dev,
+                        const rr_surface_hit* guide_low_dev, const rr_surface_hit* guide_dev, rr_radiance* out_dev, rr_radiance* halves_out_dev, uint8_t* rgba8_out_dev,
+                        float* weight_out_dev, void* hip_stream) const {
+        rr_upsample_params prm;
+        if (params) prm = *params;
+        else if (const int rc = rr_upsample_default_params(&prm)) return rc;
+        return rr_upsample_records_device(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low_dev, halves_low_dev, guide_low_dev, guide_dev,
+                                          out_dev, halves_out_dev, rgba8_out_dev, weight_out_dev, hip_stream);
+    }
+    // The frame traced at ceil(width / scale) x ceil(height / scale) with this camera's matrices (config.samples even) and raised to full
+    // size: rr_render_pixel_parts at n_parts = 2 on the small camera, rr_surface_pixels on both, upsample() with halves and, with
+    // denoise_params, denoise() with the full guide's albedo.  weight (or nullptr) gets upsample()'s.  An empty vector = refused or failed.
+    std::vector<rr_radiance> render_upsampled(uint32_t scale = 2, const rr_upsample_params* params = nullptr, const rr_denoise_params* denoise_params = nullptr,
+                                              std::vector<uint8_t>* rgba8 = nullptr, std::vector<float>* weight = nullptr) const {
+        const std::vector<rr_radiance> none;
+        if (scale == 0 || camera.width == 0 || camera.height == 0) return none;
+        const rr_camera cam = camera.c_struct();
+        rr_camera low_cam = cam;
+        low_cam.width = (cam.width + scale - 1) / scale;
+        low_cam.height = (cam.height + scale - 1) / scale;
+        const rr_config c = config.c_struct();
+        const size_t nl = (size_t)low_cam.width * low_cam.height, n = (size_t)cam.width * cam.height;
+        if (n > 0x7fffff00u) return none;
+        std::vector<rr_radiance> low(nl), halves_low(2 * nl), halves;
+        std::vector<rr_surface_hit> guide_low(nl), guide(n);
+        if (rr_render_pixel_parts(scene->handle(), &low_cam, &c, nullptr, nullptr, (uint32_t)nl, 2, low.data(), halves_low.data(), nullptr) != RR_OK) return none;
+        if (rr_surface_pixels(scene->handle(), &low_cam, nullptr, (uint32_t)nl, guide_low.data(), nullptr) != RR_OK) return none;
+        if (rr_surface_pixels(scene->handle(), &cam, nullptr, (uint32_t)n, guide.data(), nullptr) != RR_OK) return none;
+        const std::vector<rr_radiance> up = upsample(low_cam.width, low_cam.height, low.data(), halves_low.data(), guide_low.data(), guide.data(), params, &halves, weight,
+                                                     denoise_params ? nullptr : rgba8);
+        if (up.empty() || !denoise_params) return up;
+        std::vector<float> guide_albedo(3 * n);
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) guide_albedo[3 * i + k] = guide[i].base_color[k];
+        return denoise(up.data(), halves.data(), guide_albedo.data(), denoise_params, nullptr, rgba8);
+    }
+
     // What accumulate() returns and takes back as the history of the next call: the accumulated records, halves and lengths.
     struct History {
         std::vector<rr_radiance> records, halves; // width * height, and twice as many in the K = 2 layout (empty: no halves)

@@ -31,6 +31,12 @@ class rr_denoise_params(C.Structure):
                 ("sigma_luminance", C.c_float), ("gamma_correction", C.c_uint32)]
 
 
+class rr_upsample_params(C.Structure):
+    """include/rustray_hip.h: the parameters of rr_upsample_records."""
+    _fields_ = [("struct_size", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_depth", C.c_float), ("use_albedo", C.c_uint32),
+                ("gamma_correction", C.c_uint32)]
+
+
 class rr_accumulate_params(C.Structure):
     """include/rustray_hip.h: the parameters of rr_accumulate_records."""
     _fields_ = [("struct_size", C.c_uint32), ("prev_world_to_clip", C.c_float * 16), ("prev_eye", C.c_float * 3), ("max_history", C.c_float),
@@ -53,8 +59,8 @@ PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 # THE list of the files under csrc/ that librustray_hip.so is built from: rr_bvh.cpp and everything rr_api.hip includes.  The
 # Makefile rule's prerequisites name the same files (tests/test_host.py compares both with the #include lines), and the developer
 # tools that copy or read the sources (tools/ablate.py, tools/static_cost.py, tools/valu_mix.py) import this tuple.
-LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_schedule_log.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_probe.h", "rr_api_schedule_probe.h",
-               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_history_clamp.h", "rr_motion.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
+LIB_SOURCES = ("rr_api.hip", "rr_api_base.h", "rr_sample_table.h", "rr_schedule_log.h", "rr_api_handle.h", "rr_api_scene.h", "rr_api_frame.h", "rr_api_multi.h", "rr_api_post.h", "rr_api_query.h", "rr_api_parts.h", "rr_api_adaptive.h", "rr_api_levels.h", "rr_api_prefix.h", "rr_api_denoise.h", "rr_api_temporal.h", "rr_api_motion.h", "rr_api_surface_pixels.h", "rr_api_albedo_pixels.h", "rr_api_pixel_split.h", "rr_api_upsample.h", "rr_api_probe.h", "rr_api_schedule_probe.h",
+               "rr_kernels.hip", "rr_frame_plan.h", "rr_primary_setup.h", "rr_pixel_list.h", "rr_adaptive.h", "rr_denoise.h", "rr_temporal.h", "rr_history_clamp.h", "rr_motion.h", "rr_upsample.h", "rr_query_pointers.h", "rr_arg_ranges.h", "rr_scene_build.h", "rr_beam.h", "rr_bvh.cpp", "rr_bvh.h", "rr_device.h", "rr_math.h",
                "rr_primitives.h", "rr_walk.h", "rr_trace.h", "rr_surface.h", "rr_accumulate.h")
 
 
@@ -171,6 +177,9 @@ _PUBLIC = {
     "rr_surface_pixels": ([_V, _CAM, _V, _U32, _V, _V], _I), "rr_surface_pixels_device": ([_V, _CAM, _V, _U32, _V, _V, _V], _I),
     "rr_albedo_pixels": (_PIXELS + [_V] * 2, _I), "rr_albedo_pixels_device": (_PIXELS + [_V] * 3, _I),
     "rr_render_pixel_split": (_PIXELS + [_V] * 5, _I), "rr_render_pixel_split_device": (_PIXELS + [_V] * 6, _I),
+    "rr_upsample_default_params": ([C.POINTER(rr_upsample_params)], _I),
+    "rr_upsample_records": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 8, _I),
+    "rr_upsample_records_device": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 9, _I),
     "rr_post_process": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I], _I), "rr_post_process_device": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I, _V], _I),
 }
 # the test entry points the binding calls: exported by the library, declared in no public header
@@ -257,6 +266,24 @@ def denoise_params(params=None) -> rr_denoise_params:
         p.iterations, p.normal_power_log2 = int(params.iterations), int(params.normal_power_log2)
         p.sigma_depth, p.sigma_luminance = float(params.sigma_depth), float(params.sigma_luminance)
         p.gamma_correction = 1 if params.gamma_correction else 0
+    return p
+
+
+def upsample_default_params() -> rr_upsample_params:
+    """rr_upsample_default_params: power 5, sigma_depth 0.05, albedo on, no gamma (never touches a device)."""
+    p = rr_upsample_params()
+    _check(lib().rr_upsample_default_params(C.byref(p)))
+    return p
+
+
+def upsample_params(params=None) -> rr_upsample_params:
+    """An upsample.UpsampleParams (or None: the library's defaults) as the C struct; a C struct is passed through."""
+    if isinstance(params, rr_upsample_params):
+        return params
+    p = upsample_default_params()
+    if params is not None:
+        p.normal_power_log2, p.sigma_depth = int(params.normal_power_log2), float(params.sigma_depth)
+        p.use_albedo, p.gamma_correction = (1 if params.use_albedo else 0), (1 if params.gamma_correction else 0)
     return p
 
 
@@ -893,6 +920,43 @@ class DeviceScene:
         p = denoise_params(params)
         _check(lib().rr_denoise_split_records_device(self._h, C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(records_ptr), _ptr(halves_ptr), _ptr(diffuse_ptr),
                                                      _ptr(diffuse_halves_ptr), _ptr(albedo_ptr), _ptr(out_ptr), _ptr(rgba8_ptr), _ptr(stream_ptr)))
+
+    # -- the joint-bilateral upsampler: a low-resolution frame raised by the G-buffer -------
+    def upsample(self, low_width: int, low_height: int, width: int, height: int, low, guide_low, guide, halves_low=None, params=None, rgba8: bool = False,
+                 weight: bool = True) -> dict:
+        """rr_upsample_records: upsample.upsample_records on the device, host arrays in and out.  low: (w h, 8) float32 rr_radiance records
+        of the low frame in row-major order; halves_low: (w h, 2, 8) or None; guide_low, guide: w h and W H rr_surface_hit records
+        (flat.SURFACE_HIT_DTYPE, what surface_pixels returns); params: an upsample.UpsampleParams or None.  Returns dict(records (W H, 8)
+        float32, halves (W H, 2, 8) or None, and on request weight (W H,) float32 and rgba (W H, 4) uint8)."""
+        from .upsample import guide_array
+        nl, n = int(low_width) * int(low_height), int(width) * int(height)
+        rec = np.ascontiguousarray(low, np.float32).reshape(nl, 8)
+        hv = None if halves_low is None else np.ascontiguousarray(halves_low, np.float32).reshape(nl, 2, 8)
+        gl, gf = guide_array(guide_low, nl), guide_array(guide, n)
+        out = np.zeros((n, 8), np.float32)
+        hout = None if hv is None else np.zeros((n, 2, 8), np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
+        wt = np.zeros(n, np.float32) if weight else None
+        p = upsample_params(params)
+        _check(lib().rr_upsample_records(self._h, C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height), C.byref(p), _data(rec), _data(hv),
+                                         _data(gl), _data(gf), _data(out), _data(hout), _data(rgba), _data(wt)))
+        res = dict(records=out, halves=hout)
+        if weight:
+            res["weight"] = wt
+        if rgba8:
+            res["rgba"] = rgba
+        return res
+
+    def upsample_device(self, low_width: int, low_height: int, width: int, height: int, low_ptr, halves_low_ptr, guide_low_ptr, guide_ptr, out_ptr, halves_out_ptr=None,
+                        rgba8_ptr=None, weight_out_ptr=None, params=None, stream_ptr=None):
+        """rr_upsample_records_device: low_width * low_height 32-byte records (and optionally twice as many half records) and as many
+        128-byte rr_surface_hit records in, width * height surface records in, width * height records (and twice as many half records,
+        exactly when the low halves are given) out, all 16-byte aligned; optionally width * height x 4 bytes and as many float32 of
+        weight; all raw device pointers, none overlapping another; enqueued on `stream_ptr`, not waited for."""
+        p = upsample_params(params)
+        _check(lib().rr_upsample_records_device(self._h, C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(low_ptr),
+                                                _ptr(halves_low_ptr), _ptr(guide_low_ptr), _ptr(guide_ptr), _ptr(out_ptr), _ptr(halves_out_ptr), _ptr(rgba8_ptr),
+                                                _ptr(weight_out_ptr), _ptr(stream_ptr)))
 
     # -- temporal reprojection of a frame of records -----------------------------------
     # The four calls in their two forms are ONE host body and ONE device body over ACCUMULATE_ROWS; the eight methods below are their

@@ -354,6 +354,35 @@ extern "C" int rh_render_denoised(void* h, float fov, const float* eye, const fl
     if (noisy) std::memcpy(noisy, raw.data(), raw.size() * sizeof(rr_radiance));
     return 0;
 }
+// Raytracing::upsample: low = lw * lh records, halves_low = twice as many or NULL, guide_low = lw * lh and guide = w * h surface records,
+// params or NULL for the defaults; out = w * h records, halves_out = w * h * 2 or NULL (exactly when halves_low is), weight = w * h floats
+// or NULL, rgba8 = w * h x 4 bytes or NULL; returns 0, or -1 when the call was refused.
+// rh_render_upsampled: Raytracing::render_upsampled; out = w * h records, weight and rgba8 as above.
+extern "C" int rh_upsample(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                           uint32_t w, uint32_t hgt, uint32_t lw, uint32_t lh, const rr_radiance* low, const rr_radiance* halves_low, const rr_surface_hit* guide_low,
+                           const rr_surface_hit* guide, const rr_upsample_params* params, rr_radiance* out, rr_radiance* halves_out, float* weight, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> hv; std::vector<float> wt; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.upsample(lw, lh, low, halves_low, guide_low, guide, params, halves_out ? &hv : nullptr, weight ? &wt : nullptr, rgba8 ? &bytes : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (halves_out) std::memcpy(halves_out, hv.data(), hv.size() * sizeof(rr_radiance));
+    if (weight) std::memcpy(weight, wt.data(), wt.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
+extern "C" int rh_render_upsampled(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                   uint32_t w, uint32_t hgt, uint32_t scale, const rr_upsample_params* params, const rr_denoise_params* denoise_params, rr_radiance* out,
+                                   float* weight, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<float> wt; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.render_upsampled(scale, params, denoise_params, rgba8 ? &bytes : nullptr, weight ? &wt : nullptr);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (weight) std::memcpy(weight, wt.data(), wt.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
 // rh_render_denoised_albedo: Raytracing::render_denoised with its albedo argument; albedo_out = w * h * 3 floats of Raytracing::albedo or NULL
 extern "C" int rh_render_denoised_albedo(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
                                          uint32_t w, uint32_t hgt, const rr_denoise_params* params, int with_albedo, rr_radiance* out, rr_radiance* noisy, float* albedo_out) {

@@ -61,5 +61,6 @@
 #include "rr_api_surface_pixels.h" // rr_surface_pixels: the G-buffer and the albedo of the camera's pixel-centre rays, what the filter takes as its albedo guide
 #include "rr_api_albedo_pixels.h" // rr_albedo_pixels: the frame's albedo averaged over its sub-samples, the albedo guide that is right at an edge pixel
 #include "rr_api_pixel_split.h" // rr_render_pixel_split: the frame's records and, as a sum of its own, the direct diffuse light of the primary hits
+#include "rr_api_upsample.h" // rr_upsample_records: a frame traced at a low resolution raised to the full one by the G-buffer
 #include "rr_api_probe.h"    // device arithmetic probe, developer counters
 #include "rr_api_schedule_probe.h" // test entry points: switch the schedule recorder on, read its log back

@@ -27,6 +27,7 @@
 #include "rr_temporal.h" // the arithmetic of the temporal reprojection (kernel 7e)
 #include "rr_history_clamp.h" // the neighbourhood clamp of the history (kernel 7e'')
 #include "rr_motion.h"   // the per-pixel motion of moved items and the call's table (kernel 7f)
+#include "rr_upsample.h" // the arithmetic of the joint-bilateral upsampler (kernel 7g)
 
 // ---------------------------------------------------------------------------
 // The numeric knobs of the build, all of them: every one can be overridden with -D (tools/variant.sh, tools/resusage.sh);
@@ -2419,6 +2420,108 @@ __global__ __launch_bounds__(RR_BLOCK) void k_motion_records(const TpFrame f, co
     motion_pixel(f, (unsigned int)x, (unsigned int)y, r0.w, n_p, __float_as_uint(r1.w), table, n_moved, world, m);
     motion_out[3ull * o] = m[0]; motion_out[3ull * o + 1] = m[1]; motion_out[3ull * o + 2] = m[2];
     if (world_out) { world_out[3ull * o] = world[0]; world_out[3ull * o + 1] = world[1]; world_out[3ull * o + 2] = world[2]; }
+}
+
+// 7g: the joint-bilateral upsampler (rr_upsample_records; rr_upsample.h has the arithmetic, rustray_amd/upsample.py: upsample_records is the
+// yardstick).  One full-resolution pixel per lane, 32x8 tiles as 7a .. 7f.  The low-frame pixels a tile's taps touch form a patch of at
+// most 34 x 10 (rr_upsample.h: UP_PATCH_W), from the left tap of the tile's first pixel to the right tap of its last: the workgroup stages
+// it once in LDS -- colour and flags, (normal, distance), (albedo, id) as three float4 arrays, with HALVES the six half-colour floats as a
+// float4 and a float2: 48 or 72 B per patch pixel, 16320 or 24480 B a workgroup -- and every lane takes its four taps from there.  A patch
+// pixel outside the low frame carries no flag.  Global loads are 16 bytes each: of a surface record rows 0, 1, 2 and 4 (of the low guide
+// by the staging lanes, of the full guide by every lane for its own pixel), of a colour record row 0, of a half record row 0.  LDS reads:
+// the lanes of a tile row read entries that are consecutive or, at a ratio above 1, repeated (a broadcast): 16 lanes of a ds_read_b128
+// stay inside one patch row, distinct 16-byte slots of it, as in 7c.  The stores go through store_record, two 16-byte stores a record.
+// No buffer may overlap another (the entry points refuse it): every pointer is __restrict__.
+enum { UP_F_FIN = 1u, UP_F_VALID = 2u, UP_F_HIT = 4u, UP_F_INSIDE = 8u };
+RR_DEV UpGuide upsample_load_guide(const uint4* __restrict__ guide, unsigned long long o) {
+    const uint4 r0 = guide[8ull * o], r1 = guide[8ull * o + 1], r2 = guide[8ull * o + 2], r4 = guide[8ull * o + 4];
+    const float n[3] = {__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z)};
+    const float a[3] = {__uint_as_float(r4.x), __uint_as_float(r4.y), __uint_as_float(r4.z)};
+    return upsample_guide(r0.x, r0.z, __uint_as_float(r1.w), n, a);
+}
+template <bool HALVES>
+__global__ __launch_bounds__(RR_BLOCK) void k_upsample_records(const float4* __restrict__ low, const float4* __restrict__ halves_low, const uint4* __restrict__ guide_low,
+                                                               const uint4* __restrict__ guide, uint32_t low_width, uint32_t low_height, uint32_t width,
+                                                               uint32_t height, const UpCall call, float4* __restrict__ out, float4* __restrict__ halves_out,
+                                                               float* __restrict__ weight_out) {
+    __shared__ float4 s_c[UP_PATCH_W * UP_PATCH_H];
+    __shared__ float4 s_g[UP_PATCH_W * UP_PATCH_H];
+    __shared__ float4 s_a[UP_PATCH_W * UP_PATCH_H];
+    __shared__ float4 s_h4[HALVES ? UP_PATCH_W * UP_PATCH_H : 1];
+    __shared__ float2 s_h2[HALVES ? UP_PATCH_W * UP_PATCH_H : 1];
+    const int X0 = (int)blockIdx.x * UP_TILE_W, Y0 = (int)blockIdx.y * UP_TILE_H;
+    const int X1 = min(X0 + UP_TILE_W, (int)width) - 1, Y1 = min(Y0 + UP_TILE_H, (int)height) - 1; // the tile's last pixel inside the frame
+    int px0, py0, px1, py1;
+    float f_;
+    upsample_position(X0, low_width, width, &px0, &f_);
+    upsample_position(X1, low_width, width, &px1, &f_);
+    upsample_position(Y0, low_height, height, &py0, &f_);
+    upsample_position(Y1, low_height, height, &py1, &f_);
+    const int pw = min(px1 + 2 - px0, (int)UP_PATCH_W), ph = min(py1 + 2 - py0, (int)UP_PATCH_H); // (the bounds hold by themselves: rr_upsample.h)
+    for (int e = (int)threadIdx.x; e < pw * ph; e += RR_BLOCK) {
+        const int qx = px0 + e % pw, qy = py0 + e / pw;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u)), g = c, a = c, h4 = c;
+        float2 h2 = make_float2(0.0f, 0.0f);
+        if (qx >= 0 && qy >= 0 && qx < (int)low_width && qy < (int)low_height) {
+            const unsigned long long oq = (unsigned long long)qy * low_width + (unsigned int)qx;
+            const float4 r0 = low[2ull * oq];
+            const UpGuide gq = upsample_load_guide(guide_low, oq);
+            const float col[3] = {r0.x, r0.y, r0.z};
+            const uint32_t flags = UP_F_INSIDE | (upsample_fin(col) ? UP_F_FIN : 0u) | (gq.valid ? UP_F_VALID : 0u) | (gq.hit ? UP_F_HIT : 0u);
+            c = make_float4(r0.x, r0.y, r0.z, __uint_as_float(flags));
+            g = make_float4(gq.n[0], gq.n[1], gq.n[2], gq.z);
+            a = make_float4(gq.albedo[0], gq.albedo[1], gq.albedo[2], __uint_as_float(gq.id));
+            if (HALVES) {
+                const float4 ha = halves_low[4ull * oq], hb = halves_low[4ull * oq + 2];
+                h4 = make_float4(ha.x, ha.y, ha.z, hb.x);
+                h2 = make_float2(hb.y, hb.z);
+            }
+        }
+        s_c[e] = c; s_g[e] = g; s_a[e] = a;
+        if (HALVES) { s_h4[e] = h4; s_h2[e] = h2; }
+    }
+    __syncthreads();
+    const int x = X0 + ((int)threadIdx.x & (UP_TILE_W - 1)), y = Y0 + (int)threadIdx.x / UP_TILE_W;
+    if (x >= (int)width || y >= (int)height) return;
+    const unsigned long long o = (unsigned long long)y * width + (unsigned int)x;
+    const UpGuide p = upsample_load_guide(guide, o);
+    int x0, y0;
+    float fx, fy;
+    upsample_position(x, low_width, width, &x0, &fx);
+    upsample_position(y, low_height, height, &y0, &fy);
+    UpResult res;
+    upsample_pixel<HALVES>(call, x0, fx, y0, fy, p, [&](int qx, int qy, UpTap* q) {
+        const int i = qx - px0, j = qy - py0;
+        if (i < 0 || j < 0 || i >= pw || j >= ph) return false; // (never: x0 is monotone in x; kept so that no index leaves the patch)
+        const int e = j * pw + i;
+        const float4 c = s_c[e];
+        const uint32_t flags = __float_as_uint(c.w);
+        if (!(flags & UP_F_INSIDE)) return false;
+        const float4 g = s_g[e], a = s_a[e];
+        q->c[0] = c.x; q->c[1] = c.y; q->c[2] = c.z;
+        q->fin = (flags & UP_F_FIN) != 0u;
+        q->g.n[0] = g.x; q->g.n[1] = g.y; q->g.n[2] = g.z; q->g.z = g.w;
+        q->g.albedo[0] = a.x; q->g.albedo[1] = a.y; q->g.albedo[2] = a.z;
+        q->g.id = __float_as_uint(a.w);
+        q->g.hit = (flags & UP_F_HIT) != 0u;
+        q->g.valid = (flags & UP_F_VALID) != 0u;
+        if (HALVES) {
+            const float4 h4 = s_h4[e];
+            const float2 h2 = s_h2[e];
+            q->h[0][0] = h4.x; q->h[0][1] = h4.y; q->h[0][2] = h4.z;
+            q->h[1][0] = h4.w; q->h[1][1] = h2.x; q->h[1][2] = h2.y;
+        }
+        return true;
+    }, &res);
+    unsigned int depth, normal[3], id;
+    upsample_guide_fields(p, &depth, normal, &id);
+    const float4 guide_row = make_float4(__uint_as_float(normal[0]), __uint_as_float(normal[1]), __uint_as_float(normal[2]), __uint_as_float(id));
+    store_record(out, o, Record{make_float4(res.c[0], res.c[1], res.c[2], __uint_as_float(depth)), guide_row});
+    if (HALVES) {
+        store_record(halves_out, 2ull * o, Record{make_float4(res.h[0][0], res.h[0][1], res.h[0][2], __uint_as_float(depth)), guide_row});
+        store_record(halves_out, 2ull * o + 1, Record{make_float4(res.h[1][0], res.h[1][1], res.h[1][2], __uint_as_float(depth)), guide_row});
+    }
+    if (weight_out) weight_out[o] = res.weight;
 }
 
 // ---------------------------------------------------------------------------

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import capi
 from .camera import Camera
-from .flat import FlatScene, make_config, rr_config, rr_region
+from .flat import FlatScene, make_config, rr_camera, rr_config, rr_region
 
 # the in-place steps of Raytracing.apply_scene, in the order they run; RECREATE stands alone
 IN_PLACE_STEPS = ("add_textures", "update_materials", "update_transforms", "update_item_flags", "update_lights")
@@ -255,6 +255,51 @@ class Raytracing:
                 guide = self.device_scene.surface_pixels(cam, records=False, albedo=True)
             return dict(self.denoise(records, halves, guide, params, rgba8=rgba8), noisy=records, albedo=guide)
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
+
+    def upsample(self, low_width: int, low_height: int, low, guide_low, guide, halves_low=None, params=None, rgba8: bool = False) -> dict:
+        """rr_upsample_records to a frame of this camera's size: `low` (w h, 8) and `halves_low` (w h, 2, 8) or None are the records of a
+        frame traced at low_width x low_height, `guide_low` and `guide` the surface_pixels() of the small and of this camera.  Returns
+        dict(records (n, 8), halves (n, 2, 8) or None, weight (n,), color, depth, normal, object_id [, rgba]); bit for bit
+        upsample.upsample_records of the same arrays."""
+        cam = self.camera.c_struct()
+        res = self.device_scene.upsample(low_width, low_height, int(cam.width), int(cam.height), low, guide_low, guide, halves_low, params, rgba8=rgba8)
+        return dict(res, **capi._records(res["records"]))
+
+    def render_upsampled(self, scale=2, samples: Optional[int] = None, params=None, denoise_params=None, fill_holes: bool = False, rgba8: bool = False) -> dict:
+        """The frame traced at ceil(W / scale) x ceil(H / scale) with this camera's matrices and raised to W x H by the G-buffer: one
+        rr_render_pixel_parts call at n_parts = 2 on the small camera, one rr_surface_pixels call on each camera, one rr_upsample_records
+        call with halves, and with `denoise_params` one rr_denoise_records call at full size with the full guide's albedo.  fill_holes:
+        the pixels the guide found no tap for (weight 0) on a surface (guide.hit) are traced at full resolution, one rr_render_pixel_parts
+        call on their list, and written over the records and halves before the filter.  Returns dict(records, halves, weight, color,
+        depth, normal, object_id, low_width, low_height, holes: the list as x | y << 16, count [, variance][, rgba]).
+        render_upsampled_torch is the same on the device, on one stream."""
+        cam = self.camera.c_struct()
+        cfg = rr_config.from_buffer_copy(self.config)
+        if samples is not None:
+            cfg.samples = samples
+        W, H = int(cam.width), int(cam.height)
+        low_cam, w, h = _low_camera(cam, scale)
+        ds = self.device_scene
+        base = ds.render_pixel_parts(low_cam, cfg, n_parts=2)
+        guide_low = ds.surface_pixels(low_cam, records=True, albedo=False)
+        guide = ds.surface_pixels(cam, records=True, albedo=False)
+        res = ds.upsample(w, h, W, H, _pack_records(base), guide_low, guide, _pack_records(base["parts"]), params, rgba8=rgba8)
+        holes = np.zeros(0, np.uint32)
+        if fill_holes:
+            at = np.flatnonzero((res["weight"] == 0) & (guide["hit"] != 0))
+            holes = ((at % W) | ((at // W) << 16)).astype(np.uint32)
+            if len(holes):
+                cfg_b = rr_config.from_buffer_copy(cfg)
+                cfg_b.gamma_correction = capi.upsample_params(params).gamma_correction
+                fine = ds.render_pixel_parts(cam, cfg_b, pixels=holes, n_parts=2)
+                res["records"][at], res["halves"][at] = _pack_records(fine), _pack_records(fine["parts"])
+                if rgba8:
+                    res["rgba"][at] = ds.render_pixels(cam, cfg_b, pixels=holes, rgba8=True)["rgba"]
+        res.update(low_width=w, low_height=h, holes=holes, count=len(holes))
+        if denoise_params is not None:
+            albedo = np.ascontiguousarray(guide["base_color"][:, 0:3])
+            res.update(upsampled=res["records"], **self.device_scene.denoise_records(W, H, res["records"], res["halves"], albedo, denoise_params, rgba8=rgba8))
+        return dict(res, **capi._records(res["records"]))
 
     def render_temporal(self, state: "TemporalState", samples: Optional[int] = None, denoise_params=None, accumulate_params=None, seed: Optional[int] = None,
                         motion=None, sample_xy=None, rgba8: bool = False, track_items: bool = False, albedo=False, clamp=None) -> dict:
@@ -1210,6 +1255,87 @@ def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, p
     res = dict(res, noisy=base["records"], halves=base["part_records"])
     if albedo:
         res["albedo"] = guide
+    return res
+
+
+# ---------------------------------------------------------------------------
+# the joint-bilateral upsampler on torch tensors: a frame traced at a low resolution is raised where it is, on torch's current stream
+# ---------------------------------------------------------------------------
+def _low_camera(cam, scale):
+    """(`cam` with its matrices at ceil(width / scale) x ceil(height / scale), that width, that height); scale >= 1, whole or not."""
+    import math
+    if not float(scale) >= 1.0:
+        raise ValueError(f"scale {scale}: at least 1")
+    low = rr_camera.from_buffer_copy(cam)
+    low.width, low.height = max(1, math.ceil(int(cam.width) / scale)), max(1, math.ceil(int(cam.height) / scale))
+    return low, int(low.width), int(low.height)
+
+
+def upsample_torch(device_scene: capi.DeviceScene, low_width: int, low_height: int, width: int, height: int, low, halves_low, guide_low, guide, params=None,
+                   rgba8: bool = False, weight: bool = True) -> dict:
+    """rr_upsample_records_device on torch's current stream of the scene's device: `low` (w h, 8), `halves_low` (w h, 2, 8) or None,
+    `guide_low` (w h, 32) and `guide` (W H, 32) (the `records` of surface_pixels_torch) are contiguous float32 CUDA tensors on that device
+    (anything else raises).  Returns torch tensors, without a host copy and without a synchronisation: dict(records (W H, 8) float32 and
+    its views color, depth, normal, object_id; halves (W H, 2, 8) or None; on request weight (W H,) float32 and rgba (W H, 4) uint8)."""
+    import torch
+    n = int(width) * int(height)
+    lo = _frame_tensors(device_scene, low_width, low_height, dict(low=(low, (8,)), halves_low=(halves_low, (2, 8)), guide_low=(guide_low, (32,))),
+                        required=("low", "guide_low"))
+    gf = _frame_tensors(device_scene, width, height, dict(guide=(guide, (32,))), required=("guide",))["guide"]
+    hv = lo["halves_low"]
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)   # (torch allocations are at least 512-byte aligned)
+        hout = torch.empty((n, 2, 8), dtype=torch.float32, device=dev) if hv is not None else None
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if rgba8 else None
+        wt = torch.empty((n,), dtype=torch.float32, device=dev) if weight else None
+        device_scene.upsample_device(low_width, low_height, width, height, lo["low"].data_ptr(), hv.data_ptr() if hv is not None else None, lo["guide_low"].data_ptr(),
+                                     gf.data_ptr(), out.data_ptr(), hout.data_ptr() if hout is not None else None, rgba.data_ptr() if rgba8 else None,
+                                     wt.data_ptr() if weight else None, params, torch.cuda.current_stream(dev).cuda_stream)
+    res = dict(_record_views(out), halves=hout)
+    if weight:
+        res["weight"] = wt
+    if rgba8:
+        res["rgba"] = rgba
+    return res
+
+
+def render_upsampled_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, scale=2, params=None, denoise_params=None, fill_holes: bool = False,
+                           rgba8: bool = False, sample_xy=None) -> dict:
+    """Raytracing.render_upsampled on the device, on torch's current stream with no host trip: rr_render_pixel_parts_device at n_parts = 2
+    on the camera at ceil(W / scale) x ceil(H / scale), rr_surface_pixels_device on both cameras, rr_upsample_records_device with halves
+    and, with `denoise_params`, rr_denoise_records_device at full size with the full guide's albedo, each reading what the one before
+    wrote without a synchronisation.  fill_holes: the pixels with weight 0 on a surface (guide.hit) become a list x | y << 16, made with
+    torch on the device (its length is read on the host: one wait), are traced at full resolution by rr_render_pixel_parts_device and
+    written over the records and the halves before the filter.  Returns the dict of upsample_torch plus low (w h, 8), halves_low,
+    guide_low, guide (the tensors the upsampler read), low_width, low_height, holes (the list, int32 bits) and count; with
+    `denoise_params` the records are the filtered ones, `upsampled` those before the filter, and `variance` is there."""
+    import torch
+    W, H = int(cam.width), int(cam.height)
+    low_cam, w, h = _low_camera(cam, scale)
+    base = render_pixel_parts_torch(device_scene, low_cam, cfg, None, 2, sample_xy=sample_xy)
+    guide_low = surface_pixels_torch(device_scene, low_cam, None, records=True, albedo=False)
+    guide = surface_pixels_torch(device_scene, cam, None, records=True, albedo=denoise_params is not None)
+    res = upsample_torch(device_scene, w, h, W, H, base["records"], base["part_records"], guide_low["records"], guide["records"], params, rgba8=rgba8)
+    dev = torch.device("cuda", device_scene.device)
+    with torch.cuda.device(dev):
+        holes = torch.empty((0,), dtype=torch.int32, device=dev)
+        if fill_holes:
+            at = torch.nonzero((res["weight"] == 0) & (guide["hit"] != 0)).reshape(-1)
+            xy = (at % W) | ((at // W) << 16)                       # int64; as the 32 bits of an int32
+            holes = torch.where(xy >= (1 << 31), xy - (1 << 32), xy).to(torch.int32).contiguous()
+    if int(holes.shape[0]):
+        cfg_b = rr_config.from_buffer_copy(cfg)
+        cfg_b.gamma_correction = capi.upsample_params(params).gamma_correction
+        fine = render_pixel_parts_torch(device_scene, cam, cfg_b, holes, 2, sample_xy=sample_xy)
+        res["records"][at], res["halves"][at] = fine["records"], fine["part_records"]
+        if rgba8:
+            res["rgba"][at] = render_pixels_torch(device_scene, cam, cfg_b, holes, sample_xy=sample_xy, rgba8=True)["rgba"]
+    res.update(low=base["records"], halves_low=base["part_records"], guide_low=guide_low["records"], guide=guide["records"], low_width=w, low_height=h,
+               holes=holes, count=int(holes.shape[0]))
+    if denoise_params is not None:
+        filtered = denoise_torch(device_scene, W, H, res["records"], res["halves"], guide["albedo"], denoise_params, rgba8=rgba8)
+        res.update(upsampled=res["records"], **filtered)
     return res
 
 
