@@ -68,7 +68,9 @@ extern "C" {
  * rr_accumulate_clamped_split_records and rr_accumulate_clamped_split_records_device came after those, without a struct of their own: a
  * version-3 library may lack these two as well.
  * rr_upsample_default_params, rr_upsample_records and rr_upsample_records_device (with rr_upsample_params, a struct of its own) came
- * after those, again without a change of any existing struct: a version-3 library may lack these three as well. */
+ * after those, again without a change of any existing struct: a version-3 library may lack these three as well.
+ * rr_upsample_albedo_records and rr_upsample_albedo_records_device came after those, without a struct of their own: a version-3 library
+ * may lack these two as well. */
 #define RR_ABI_VERSION 3u
 
 typedef enum rr_status {
@@ -1555,7 +1557,22 @@ int rr_denoise_split_records(rr_scene* scene, uint32_t width, uint32_t height, c
  *   two outputs (nothing is in place): all RR_ERR_INVALID_ARGUMENT.  Then width * height * 2 > 2^30: RR_ERR_UNSUPPORTED.
  * rr_upsample_records: the same on HOST pointers, the device form on the null stream behind a staging copy in the pool of staging
  * buffers the record calls share (32, 64 and 128 B per low pixel, 128 + 32 and 64, 4 and 4 B per pixel, each only where given); it
- * returns with the outputs written. */
+ * returns with the outputs written.
+ * rr_upsample_albedo_records(_device): rr_upsample_records(_device) with ALBEDO PLANES OF THE CALLER'S OWN, two more inputs after guide:
+ * albedo_low (w * h * 3 floats, or NULL) and albedo (W * H * 3 floats, or NULL), pixel q at [3q .. 3q + 2], the layout rr_albedo_pixels
+ * writes and rr_denoise_records reads.  A low frame's colour is a mean over its pixel's sub-samples, while guide_low[q].base_color is the
+ * albedo under the pixel's centre: on a textured surface the quotient of the two is wrong, and rr_albedo_pixels on the low camera -- the
+ * mean over exactly the rays that made the colour -- is the albedo to divide by.
+ *   Wherever the text above reads guide_low[q].base_color[k], the call reads albedo_low[3q + k] when albedo_low is given; wherever it
+ *   reads guide[p].base_color[k], the call reads albedo[3p + k] when albedo is given.  Nothing else changes: taps, skip rule, weights,
+ *   fallback, halves, the guide fields of out, weight_out, rgba8_out.  With use_albedo == 0 the planes are not read.  The value of a
+ *   plane at a pixel whose guide is not a hit reaches no result (it may be anything, a NaN included).
+ *   So with both planes NULL the call IS rr_upsample_records, bit for bit; with planes it is rr_upsample_records on copies of the guides
+ *   whose base_color[0 .. 2] were overwritten by the planes, bit for bit.  rr_upsample_records(_device) are this call with two NULLs.
+ *   Refusals: those of rr_upsample_records in the same order -- the planes are optional, so no NULL is added; (device form) albedo_low
+ *   or albedo not 4-byte aligned (a plane need NOT be 16-byte aligned), refused where rgba8_out and weight_out are; a plane that
+ *   overlaps out, halves_out, rgba8_out or weight_out (the planes are inputs of 12 B per pixel: they may overlap each other and any other
+ *   input).  The host form stages them with the rest (12 B per low pixel and per pixel more). */
 typedef struct rr_upsample_params {
     uint32_t struct_size;        /* sizeof(rr_upsample_params) */
     uint32_t normal_power_log2;  /* 0 .. 7: the normal weight is max(0, n_p . n_q) squared this many times */
@@ -1574,6 +1591,18 @@ int rr_upsample_records(rr_scene* scene, uint32_t low_width, uint32_t low_height
                         const rr_surface_hit* guide_low /* low_width * low_height */, const rr_surface_hit* guide /* width * height */,
                         rr_radiance* out /* width * height */, rr_radiance* halves_out /* width * height * 2; NULL exactly when halves_low is */,
                         uint8_t* rgba8_out /* or NULL */, float* weight_out /* width * height, or NULL */);
+int rr_upsample_albedo_records_device(rr_scene* scene, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height, const rr_upsample_params* params,
+                                      const rr_radiance* low_dev /* low_width * low_height */, const rr_radiance* halves_low_dev /* twice as many, or NULL */,
+                                      const rr_surface_hit* guide_low_dev /* low_width * low_height */, const rr_surface_hit* guide_dev /* width * height */,
+                                      const float* albedo_low_dev /* low_width * low_height * 3, or NULL */, const float* albedo_dev /* width * height * 3, or NULL */,
+                                      rr_radiance* out_dev /* width * height */, rr_radiance* halves_out_dev /* width * height * 2; NULL exactly when halves_low_dev is */,
+                                      uint8_t* rgba8_out_dev /* or NULL */, float* weight_out_dev /* width * height, or NULL */, void* hip_stream);
+int rr_upsample_albedo_records(rr_scene* scene, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height, const rr_upsample_params* params,
+                               const rr_radiance* low /* low_width * low_height */, const rr_radiance* halves_low /* twice as many, or NULL */,
+                               const rr_surface_hit* guide_low /* low_width * low_height */, const rr_surface_hit* guide /* width * height */,
+                               const float* albedo_low /* low_width * low_height * 3, or NULL */, const float* albedo /* width * height * 3, or NULL */,
+                               rr_radiance* out /* width * height */, rr_radiance* halves_out /* width * height * 2; NULL exactly when halves_low is */,
+                               uint8_t* rgba8_out /* or NULL */, float* weight_out /* width * height, or NULL */);
 
 /* Post-processing of a finished frame (reference run_post_processing, src/post_processing.rs:123-181, called from
  * Run::post_processing, src/run.rs:588-600): outline on object-id edges (:98-121), then cavity = curvature of the

@@ -846,9 +846,12 @@ public:
     // Returns width * height records whose depth, normal and id are the full guide's; halves_out (required exactly when halves_low is
     // given) gets twice as many, weight (or nullptr) the guided sum's weight per pixel (0: the bilinear fallback answered), rgba8 (or
     // nullptr) the frame's bytes of the records.  An empty vector = refused or failed (rr_last_error() says why).
+    // albedo_low (low_width * low_height * 3 floats) and albedo (width * height * 3), each or nullptr: albedo planes in place of the guides'
+    // base colours (rr_upsample_albedo_records), e.g. mean_albedo() of the two cameras; with both nullptr the call is rr_upsample_records.
     std::vector<rr_radiance> upsample(uint32_t low_width, uint32_t low_height, const rr_radiance* low, const rr_radiance* halves_low, const rr_surface_hit* guide_low,
                                       const rr_surface_hit* guide, const rr_upsample_params* params = nullptr, std::vector<rr_radiance>* halves_out = nullptr,
-                                      std::vector<float>* weight = nullptr, std::vector<uint8_t>* rgba8 = nullptr) const {
+                                      std::vector<float>* weight = nullptr, std::vector<uint8_t>* rgba8 = nullptr, const float* albedo_low = nullptr,
+                                      const float* albedo = nullptr) const {
         std::vector<rr_radiance> out;
         const size_t n = (size_t)camera.width * camera.height;
         rr_upsample_params prm;
@@ -859,8 +862,14 @@ public:
         if (halves_out) halves_out->assign(2 * n, rr_radiance{});
         if (weight) weight->assign(n, 0.0f);
         if (rgba8) rgba8->assign(4 * n, 0);
-        if (rr_upsample_records(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low, halves_low, guide_low, guide, out.data(),
-                                halves_out ? halves_out->data() : nullptr, rgba8 ? rgba8->data() : nullptr, weight ? weight->data() : nullptr) != RR_OK) {
+        rr_radiance* const ho = halves_out ? halves_out->data() : nullptr;
+        uint8_t* const bytes = rgba8 ? rgba8->data() : nullptr;
+        float* const wt = weight ? weight->data() : nullptr;
+        const int rc = albedo_low || albedo
+            ? rr_upsample_albedo_records(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low, halves_low, guide_low, guide, albedo_low, albedo,
+                                         out.data(), ho, bytes, wt)
+            : rr_upsample_records(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low, halves_low, guide_low, guide, out.data(), ho, bytes, wt);
+        if (rc != RR_OK) {
             out.clear();
             if (halves_out) halves_out->clear();
             if (weight) weight->clear();
@@ -871,20 +880,30 @@ public:
     // the same on DEVICE buffers, in stream order (rr_upsample_records_device): one launch, not waited for; nothing may overlap
     int upsample_device(uint32_t low_width, uint32_t low_height, const rr_upsample_params* params, const rr_radiance* low_dev, const rr_radiance* halves_low_dev,
                         const rr_surface_hit* guide_low_dev, const rr_surface_hit* guide_dev, rr_radiance* out_dev, rr_radiance* halves_out_dev, uint8_t* rgba8_out_dev,
-                        float* weight_out_dev, void* hip_stream) const {
+                        float* weight_out_dev, void* hip_stream, const float* albedo_low_dev = nullptr, const float* albedo_dev = nullptr) const {
         rr_upsample_params prm;
         if (params) prm = *params;
         else if (const int rc = rr_upsample_default_params(&prm)) return rc;
+        if (albedo_low_dev || albedo_dev)   // (rr_upsample_albedo_records_device: the planes are 4-byte aligned)
+            return rr_upsample_albedo_records_device(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low_dev, halves_low_dev, guide_low_dev,
+                                                     guide_dev, albedo_low_dev, albedo_dev, out_dev, halves_out_dev, rgba8_out_dev, weight_out_dev, hip_stream);
         return rr_upsample_records_device(scene->handle(), low_width, low_height, camera.width, camera.height, &prm, low_dev, halves_low_dev, guide_low_dev, guide_dev,
                                           out_dev, halves_out_dev, rgba8_out_dev, weight_out_dev, hip_stream);
     }
     // The frame traced at ceil(width / scale) x ceil(height / scale) with this camera's matrices (config.samples even) and raised to full
     // size: rr_render_pixel_parts at n_parts = 2 on the small camera, rr_surface_pixels on both, upsample() with halves and, with
     // denoise_params, denoise() with the full guide's albedo.  weight (or nullptr) gets upsample()'s.  An empty vector = refused or failed.
+    // albedo_kind: CENTRE, the guides' pixel-centre albedo; MEAN, the low frame is demodulated by rr_albedo_pixels on the small camera with
+    // this config, the mean over the rays that made the colour (anything else is refused).  full_albedo_samples: 0, or k >= 1:
+    // rr_albedo_pixels on this camera at k samples remodulates and, with denoise_params, guides the full-size filter.  low_denoise_params:
+    // rr_denoise_records at the low size on the low records and halves before the upsampler, with the low albedo in use; the filtered
+    // records are raised without halves and the full-size filter runs without them.
     std::vector<rr_radiance> render_upsampled(uint32_t scale = 2, const rr_upsample_params* params = nullptr, const rr_denoise_params* denoise_params = nullptr,
-                                              std::vector<uint8_t>* rgba8 = nullptr, std::vector<float>* weight = nullptr) const {
+                                              std::vector<uint8_t>* rgba8 = nullptr, std::vector<float>* weight = nullptr, AlbedoGuide albedo_kind = AlbedoGuide::CENTRE,
+                                              uint32_t full_albedo_samples = 0, const rr_denoise_params* low_denoise_params = nullptr) const {
         const std::vector<rr_radiance> none;
         if (scale == 0 || camera.width == 0 || camera.height == 0) return none;
+        if (albedo_kind != AlbedoGuide::CENTRE && albedo_kind != AlbedoGuide::MEAN) return none;
         const rr_camera cam = camera.c_struct();
         rr_camera low_cam = cam;
         low_cam.width = (cam.width + scale - 1) / scale;
@@ -897,13 +916,37 @@ public:
         if (rr_render_pixel_parts(scene->handle(), &low_cam, &c, nullptr, nullptr, (uint32_t)nl, 2, low.data(), halves_low.data(), nullptr) != RR_OK) return none;
         if (rr_surface_pixels(scene->handle(), &low_cam, nullptr, (uint32_t)nl, guide_low.data(), nullptr) != RR_OK) return none;
         if (rr_surface_pixels(scene->handle(), &cam, nullptr, (uint32_t)n, guide.data(), nullptr) != RR_OK) return none;
-        const std::vector<rr_radiance> up = upsample(low_cam.width, low_cam.height, low.data(), halves_low.data(), guide_low.data(), guide.data(), params, &halves, weight,
-                                                     denoise_params ? nullptr : rgba8);
+        std::vector<float> plane_low, plane;
+        if (albedo_kind == AlbedoGuide::MEAN) {
+            plane_low.assign(3 * nl, 0.0f);
+            if (rr_albedo_pixels(scene->handle(), &low_cam, &c, nullptr, nullptr, (uint32_t)nl, plane_low.data(), nullptr) != RR_OK) return none;
+        }
+        if (full_albedo_samples) {
+            rr_config ck = c;
+            ck.samples = full_albedo_samples;
+            plane.assign(3 * n, 0.0f);
+            if (rr_albedo_pixels(scene->handle(), &cam, &ck, nullptr, nullptr, (uint32_t)n, plane.data(), nullptr) != RR_OK) return none;
+        }
+        const auto centre_albedo = [](const std::vector<rr_surface_hit>& g) {
+            std::vector<float> a(3 * g.size());
+            for (size_t i = 0; i < g.size(); i++)
+                for (int k = 0; k < 3; k++) a[3 * i + k] = g[i].base_color[k];
+            return a;
+        };
+        if (low_denoise_params) {
+            const std::vector<float> a = plane_low.empty() ? centre_albedo(guide_low) : plane_low;
+            std::vector<rr_radiance> filtered(nl);
+            if (rr_denoise_records(scene->handle(), low_cam.width, low_cam.height, low_denoise_params, low.data(), halves_low.data(), a.data(), filtered.data(), nullptr,
+                                   nullptr) != RR_OK) return none;
+            low.swap(filtered);
+        }
+        const bool with_halves = !low_denoise_params;
+        const std::vector<rr_radiance> up = upsample(low_cam.width, low_cam.height, low.data(), with_halves ? halves_low.data() : nullptr, guide_low.data(), guide.data(), params,
+                                                     with_halves ? &halves : nullptr, weight, denoise_params ? nullptr : rgba8,
+                                                     plane_low.empty() ? nullptr : plane_low.data(), plane.empty() ? nullptr : plane.data());
         if (up.empty() || !denoise_params) return up;
-        std::vector<float> guide_albedo(3 * n);
-        for (size_t i = 0; i < n; i++)
-            for (int k = 0; k < 3; k++) guide_albedo[3 * i + k] = guide[i].base_color[k];
-        return denoise(up.data(), halves.data(), guide_albedo.data(), denoise_params, nullptr, rgba8);
+        const std::vector<float> guide_albedo = plane.empty() ? centre_albedo(guide) : plane;
+        return denoise(up.data(), with_halves ? halves.data() : nullptr, guide_albedo.data(), denoise_params, nullptr, rgba8);
     }
 
     // What accumulate() returns and takes back as the history of the next call: the accumulated records, halves and lengths.

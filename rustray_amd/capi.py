@@ -180,6 +180,8 @@ _PUBLIC = {
     "rr_upsample_default_params": ([C.POINTER(rr_upsample_params)], _I),
     "rr_upsample_records": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 8, _I),
     "rr_upsample_records_device": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 9, _I),
+    "rr_upsample_albedo_records": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 10, _I),
+    "rr_upsample_albedo_records_device": ([_V] + [_U32] * 4 + [C.POINTER(rr_upsample_params)] + [_V] * 11, _I),
     "rr_post_process": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I], _I), "rr_post_process_device": ([_U32, _U32, _I, _I, _V, _V, _V, _V, _I, _V], _I),
 }
 # the test entry points the binding calls: exported by the library, declared in no public header
@@ -923,11 +925,13 @@ class DeviceScene:
 
     # -- the joint-bilateral upsampler: a low-resolution frame raised by the G-buffer -------
     def upsample(self, low_width: int, low_height: int, width: int, height: int, low, guide_low, guide, halves_low=None, params=None, rgba8: bool = False,
-                 weight: bool = True) -> dict:
+                 weight: bool = True, albedo_low=None, albedo=None) -> dict:
         """rr_upsample_records: upsample.upsample_records on the device, host arrays in and out.  low: (w h, 8) float32 rr_radiance records
         of the low frame in row-major order; halves_low: (w h, 2, 8) or None; guide_low, guide: w h and W H rr_surface_hit records
         (flat.SURFACE_HIT_DTYPE, what surface_pixels returns); params: an upsample.UpsampleParams or None.  Returns dict(records (W H, 8)
-        float32, halves (W H, 2, 8) or None, and on request weight (W H,) float32 and rgba (W H, 4) uint8)."""
+        float32, halves (W H, 2, 8) or None, and on request weight (W H,) float32 and rgba (W H, 4) uint8).  albedo_low (w h, 3) and
+        albedo (W H, 3) float32, each or None: the caller's albedo planes, and the call is rr_upsample_albedo_records; with both None it is
+        rr_upsample_records itself (the same bits either way: the older symbol, so that a library without the newer one still serves)."""
         from .upsample import guide_array
         nl, n = int(low_width) * int(low_height), int(width) * int(height)
         rec = np.ascontiguousarray(low, np.float32).reshape(nl, 8)
@@ -938,8 +942,14 @@ class DeviceScene:
         rgba = np.zeros((n, 4), np.uint8) if rgba8 else None
         wt = np.zeros(n, np.float32) if weight else None
         p = upsample_params(params)
-        _check(lib().rr_upsample_records(self._h, C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height), C.byref(p), _data(rec), _data(hv),
-                                         _data(gl), _data(gf), _data(out), _data(hout), _data(rgba), _data(wt)))
+        size = (C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height))
+        if albedo_low is None and albedo is None:
+            _check(lib().rr_upsample_records(self._h, *size, C.byref(p), _data(rec), _data(hv), _data(gl), _data(gf), _data(out), _data(hout), _data(rgba), _data(wt)))
+        else:
+            al = None if albedo_low is None else np.ascontiguousarray(albedo_low, np.float32).reshape(nl, 3)
+            af = None if albedo is None else np.ascontiguousarray(albedo, np.float32).reshape(n, 3)
+            _check(lib().rr_upsample_albedo_records(self._h, *size, C.byref(p), _data(rec), _data(hv), _data(gl), _data(gf), _data(al), _data(af), _data(out),
+                                                    _data(hout), _data(rgba), _data(wt)))
         res = dict(records=out, halves=hout)
         if weight:
             res["weight"] = wt
@@ -948,15 +958,22 @@ class DeviceScene:
         return res
 
     def upsample_device(self, low_width: int, low_height: int, width: int, height: int, low_ptr, halves_low_ptr, guide_low_ptr, guide_ptr, out_ptr, halves_out_ptr=None,
-                        rgba8_ptr=None, weight_out_ptr=None, params=None, stream_ptr=None):
+                        rgba8_ptr=None, weight_out_ptr=None, params=None, stream_ptr=None, albedo_low=None, albedo=None):
         """rr_upsample_records_device: low_width * low_height 32-byte records (and optionally twice as many half records) and as many
         128-byte rr_surface_hit records in, width * height surface records in, width * height records (and twice as many half records,
         exactly when the low halves are given) out, all 16-byte aligned; optionally width * height x 4 bytes and as many float32 of
-        weight; all raw device pointers, none overlapping another; enqueued on `stream_ptr`, not waited for."""
+        weight; all raw device pointers, none overlapping another; enqueued on `stream_ptr`, not waited for.  albedo_low and albedo: raw
+        device pointers too (albedo_low_dev and albedo_dev of rr_upsample_albedo_records_device: low_width * low_height x 3 and width *
+        height x 3 float32, 4-byte aligned), each or None; with both None the call is rr_upsample_records_device itself."""
         p = upsample_params(params)
-        _check(lib().rr_upsample_records_device(self._h, C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height), C.byref(p), _ptr(low_ptr),
-                                                _ptr(halves_low_ptr), _ptr(guide_low_ptr), _ptr(guide_ptr), _ptr(out_ptr), _ptr(halves_out_ptr), _ptr(rgba8_ptr),
-                                                _ptr(weight_out_ptr), _ptr(stream_ptr)))
+        size = (C.c_uint32(low_width), C.c_uint32(low_height), C.c_uint32(width), C.c_uint32(height))
+        if albedo_low is None and albedo is None:
+            _check(lib().rr_upsample_records_device(self._h, *size, C.byref(p), _ptr(low_ptr), _ptr(halves_low_ptr), _ptr(guide_low_ptr), _ptr(guide_ptr), _ptr(out_ptr),
+                                                    _ptr(halves_out_ptr), _ptr(rgba8_ptr), _ptr(weight_out_ptr), _ptr(stream_ptr)))
+        else:
+            _check(lib().rr_upsample_albedo_records_device(self._h, *size, C.byref(p), _ptr(low_ptr), _ptr(halves_low_ptr), _ptr(guide_low_ptr), _ptr(guide_ptr),
+                                                           _ptr(albedo_low), _ptr(albedo), _ptr(out_ptr), _ptr(halves_out_ptr), _ptr(rgba8_ptr), _ptr(weight_out_ptr),
+                                                           _ptr(stream_ptr)))
 
     # -- temporal reprojection of a frame of records -----------------------------------
     # The four calls in their two forms are ONE host body and ONE device body over ACCUMULATE_ROWS; the eight methods below are their

@@ -371,6 +371,37 @@ extern "C" int rh_upsample(void* h, float fov, const float* eye, const float* up
     if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
     return 0;
 }
+// rh_upsample_albedo: Raytracing::upsample with its albedo planes: albedo_low = lw * lh * 3 floats or NULL, albedo = w * h * 3 floats or NULL
+extern "C" int rh_upsample_albedo(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                  uint32_t w, uint32_t hgt, uint32_t lw, uint32_t lh, const rr_radiance* low, const rr_radiance* halves_low, const rr_surface_hit* guide_low,
+                                  const rr_surface_hit* guide, const float* albedo_low, const float* albedo, const rr_upsample_params* params, rr_radiance* out,
+                                  rr_radiance* halves_out, float* weight, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<rr_radiance> hv; std::vector<float> wt; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.upsample(lw, lh, low, halves_low, guide_low, guide, params, halves_out ? &hv : nullptr, weight ? &wt : nullptr, rgba8 ? &bytes : nullptr,
+                                                   albedo_low, albedo);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (halves_out) std::memcpy(halves_out, hv.data(), hv.size() * sizeof(rr_radiance));
+    if (weight) std::memcpy(weight, wt.data(), wt.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
+// rh_render_upsampled_albedo: Raytracing::render_upsampled with its albedo options: mean != 0 is AlbedoGuide::MEAN, full_albedo_samples 0 = none,
+// low_denoise_params or NULL
+extern "C" int rh_render_upsampled_albedo(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
+                                          uint32_t w, uint32_t hgt, uint32_t scale, const rr_upsample_params* params, const rr_denoise_params* denoise_params, int mean,
+                                          uint32_t full_albedo_samples, const rr_denoise_params* low_denoise_params, rr_radiance* out, float* weight, uint8_t* rgba8) {
+    const Raytracing& rt = rh_with(h, fov, eye, up, dir, cnear, cfar, cfg, w, hgt);
+    std::vector<float> wt; std::vector<uint8_t> bytes;
+    const std::vector<rr_radiance> r = rt.render_upsampled(scale, params, denoise_params, rgba8 ? &bytes : nullptr, weight ? &wt : nullptr,
+                                                           mean ? Raytracing::AlbedoGuide::MEAN : Raytracing::AlbedoGuide::CENTRE, full_albedo_samples, low_denoise_params);
+    if (r.empty()) return -1;
+    std::memcpy(out, r.data(), r.size() * sizeof(rr_radiance));
+    if (weight) std::memcpy(weight, wt.data(), wt.size() * 4);
+    if (rgba8) std::memcpy(rgba8, bytes.data(), bytes.size());
+    return 0;
+}
 extern "C" int rh_render_upsampled(void* h, float fov, const float* eye, const float* up, const float* dir, float cnear, float cfar, const rr_config* cfg,
                                    uint32_t w, uint32_t hgt, uint32_t scale, const rr_upsample_params* params, const rr_denoise_params* denoise_params, rr_radiance* out,
                                    float* weight, uint8_t* rgba8) {

@@ -2431,17 +2431,31 @@ __global__ __launch_bounds__(RR_BLOCK) void k_motion_records(const TpFrame f, co
 // by the staging lanes, of the full guide by every lane for its own pixel), of a colour record row 0, of a half record row 0.  LDS reads:
 // the lanes of a tile row read entries that are consecutive or, at a ratio above 1, repeated (a broadcast): 16 lanes of a ds_read_b128
 // stay inside one patch row, distinct 16-byte slots of it, as in 7c.  The stores go through store_record, two 16-byte stores a record.
-// No buffer may overlap another (the entry points refuse it): every pointer is __restrict__.
+// No output may overlap another buffer (the entry points refuse it) and the inputs are only read: every pointer is __restrict__.
+// PLANES (rr_upsample_albedo_records with at least one plane): the albedo in use comes from the caller's planes -- the staging lanes fill
+// s_a[e].xyz from albedo_low, every lane its own p.albedo from albedo, three dword loads at a 12-byte stride each (a tile row reads 384
+// consecutive bytes of `albedo`) in place of the 16-byte load of row 4, which is then not issued; either plane may be NULL, a test of a
+// kernel argument that is uniform over the launch.  The LDS layout and everything behind the loads are those of the builds without.
 enum { UP_F_FIN = 1u, UP_F_VALID = 2u, UP_F_HIT = 4u, UP_F_INSIDE = 8u };
-RR_DEV UpGuide upsample_load_guide(const uint4* __restrict__ guide, unsigned long long o) {
-    const uint4 r0 = guide[8ull * o], r1 = guide[8ull * o + 1], r2 = guide[8ull * o + 2], r4 = guide[8ull * o + 4];
+// A guide as the sum takes it.  PLANES with a `plane` (rr_upsample_albedo_records: 3 floats a pixel, 4-byte aligned and no more, so three
+// dword loads and never a wider one) takes the albedo in use from there and leaves row 4 of the surface record unread.
+template <bool PLANES>
+RR_DEV UpGuide upsample_load_guide(const uint4* __restrict__ guide, unsigned long long o, const float* __restrict__ plane) {
+    const uint4 r0 = guide[8ull * o], r1 = guide[8ull * o + 1], r2 = guide[8ull * o + 2];
     const float n[3] = {__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z)};
-    const float a[3] = {__uint_as_float(r4.x), __uint_as_float(r4.y), __uint_as_float(r4.z)};
+    float a[3];
+    if (PLANES && plane) {
+        a[0] = plane[3ull * o]; a[1] = plane[3ull * o + 1]; a[2] = plane[3ull * o + 2];
+    } else {
+        const uint4 r4 = guide[8ull * o + 4];
+        a[0] = __uint_as_float(r4.x); a[1] = __uint_as_float(r4.y); a[2] = __uint_as_float(r4.z);
+    }
     return upsample_guide(r0.x, r0.z, __uint_as_float(r1.w), n, a);
 }
-template <bool HALVES>
+template <bool HALVES, bool PLANES>
 __global__ __launch_bounds__(RR_BLOCK) void k_upsample_records(const float4* __restrict__ low, const float4* __restrict__ halves_low, const uint4* __restrict__ guide_low,
-                                                               const uint4* __restrict__ guide, uint32_t low_width, uint32_t low_height, uint32_t width,
+                                                               const uint4* __restrict__ guide, const float* __restrict__ albedo_low,
+                                                               const float* __restrict__ albedo, uint32_t low_width, uint32_t low_height, uint32_t width,
                                                                uint32_t height, const UpCall call, float4* __restrict__ out, float4* __restrict__ halves_out,
                                                                float* __restrict__ weight_out) {
     __shared__ float4 s_c[UP_PATCH_W * UP_PATCH_H];
@@ -2465,7 +2479,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_upsample_records(const float4* __r
         if (qx >= 0 && qy >= 0 && qx < (int)low_width && qy < (int)low_height) {
             const unsigned long long oq = (unsigned long long)qy * low_width + (unsigned int)qx;
             const float4 r0 = low[2ull * oq];
-            const UpGuide gq = upsample_load_guide(guide_low, oq);
+            const UpGuide gq = upsample_load_guide<PLANES>(guide_low, oq, albedo_low);
             const float col[3] = {r0.x, r0.y, r0.z};
             const uint32_t flags = UP_F_INSIDE | (upsample_fin(col) ? UP_F_FIN : 0u) | (gq.valid ? UP_F_VALID : 0u) | (gq.hit ? UP_F_HIT : 0u);
             c = make_float4(r0.x, r0.y, r0.z, __uint_as_float(flags));
@@ -2484,7 +2498,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_upsample_records(const float4* __r
     const int x = X0 + ((int)threadIdx.x & (UP_TILE_W - 1)), y = Y0 + (int)threadIdx.x / UP_TILE_W;
     if (x >= (int)width || y >= (int)height) return;
     const unsigned long long o = (unsigned long long)y * width + (unsigned int)x;
-    const UpGuide p = upsample_load_guide(guide, o);
+    const UpGuide p = upsample_load_guide<PLANES>(guide, o, albedo);
     int x0, y0;
     float fx, fy;
     upsample_position(x, low_width, width, &x0, &fx);

@@ -256,23 +256,35 @@ class Raytracing:
             return dict(self.denoise(records, halves, guide, params, rgba8=rgba8), noisy=records, albedo=guide)
         return dict(self.denoise(records, halves, None, params, rgba8=rgba8), noisy=records)
 
-    def upsample(self, low_width: int, low_height: int, low, guide_low, guide, halves_low=None, params=None, rgba8: bool = False) -> dict:
+    def upsample(self, low_width: int, low_height: int, low, guide_low, guide, halves_low=None, params=None, rgba8: bool = False, albedo_low=None,
+                 albedo=None) -> dict:
         """rr_upsample_records to a frame of this camera's size: `low` (w h, 8) and `halves_low` (w h, 2, 8) or None are the records of a
         frame traced at low_width x low_height, `guide_low` and `guide` the surface_pixels() of the small and of this camera.  Returns
         dict(records (n, 8), halves (n, 2, 8) or None, weight (n,), color, depth, normal, object_id [, rgba]); bit for bit
-        upsample.upsample_records of the same arrays."""
+        upsample.upsample_records of the same arrays.  albedo_low (w h, 3) and albedo (n, 3), each or None: albedo planes in place of
+        the guides' base colours (rr_upsample_albedo_records), e.g. mean_albedo() of the two cameras."""
         cam = self.camera.c_struct()
-        res = self.device_scene.upsample(low_width, low_height, int(cam.width), int(cam.height), low, guide_low, guide, halves_low, params, rgba8=rgba8)
+        res = self.device_scene.upsample(low_width, low_height, int(cam.width), int(cam.height), low, guide_low, guide, halves_low, params, rgba8=rgba8,
+                                         albedo_low=albedo_low, albedo=albedo)
         return dict(res, **capi._records(res["records"]))
 
-    def render_upsampled(self, scale=2, samples: Optional[int] = None, params=None, denoise_params=None, fill_holes: bool = False, rgba8: bool = False) -> dict:
+    def render_upsampled(self, scale=2, samples: Optional[int] = None, params=None, denoise_params=None, fill_holes: bool = False, rgba8: bool = False,
+                         albedo=True, full_albedo_samples: Optional[int] = None, low_denoise_params=None) -> dict:
         """The frame traced at ceil(W / scale) x ceil(H / scale) with this camera's matrices and raised to W x H by the G-buffer: one
         rr_render_pixel_parts call at n_parts = 2 on the small camera, one rr_surface_pixels call on each camera, one rr_upsample_records
         call with halves, and with `denoise_params` one rr_denoise_records call at full size with the full guide's albedo.  fill_holes:
         the pixels the guide found no tap for (weight 0) on a surface (guide.hit) are traced at full resolution, one rr_render_pixel_parts
         call on their list, and written over the records and halves before the filter.  Returns dict(records, halves, weight, color,
-        depth, normal, object_id, low_width, low_height, holes: the list as x | y << 16, count [, variance][, rgba]).
+        depth, normal, object_id, low_width, low_height, holes: the list as x | y << 16, count, albedo_low, albedo: the planes the
+        upsampler took, or None [, variance][, rgba]).
+        albedo: True, the guides' pixel-centre albedo; "mean": the low frame is demodulated by rr_albedo_pixels on the small camera with
+        the low frame's config -- the mean over the rays that made the colour (rr_upsample_albedo_records).  full_albedo_samples: None,
+        or k >= 1: rr_albedo_pixels on this camera at k samples remodulates in place of the full guide's centre albedo and, with
+        `denoise_params`, is the full-size filter's albedo.  low_denoise_params: rr_denoise_records at the LOW size on the low records and
+        halves before the upsampler, with the low albedo in use; the filtered records are raised without halves (`halves` is None,
+        fill_holes writes records only, and the full-size filter runs without halves); `low_filtered` holds them.
         render_upsampled_torch is the same on the device, on one stream."""
+        _check_upsampled_options(albedo, full_albedo_samples)
         cam = self.camera.c_struct()
         cfg = rr_config.from_buffer_copy(self.config)
         if samples is not None:
@@ -283,7 +295,15 @@ class Raytracing:
         base = ds.render_pixel_parts(low_cam, cfg, n_parts=2)
         guide_low = ds.surface_pixels(low_cam, records=True, albedo=False)
         guide = ds.surface_pixels(cam, records=True, albedo=False)
-        res = ds.upsample(w, h, W, H, _pack_records(base), guide_low, guide, _pack_records(base["parts"]), params, rgba8=rgba8)
+        low, halves_low = _pack_records(base), _pack_records(base["parts"])
+        albedo_low = ds.albedo_pixels(low_cam, cfg) if _mean_mode(albedo) else None
+        albedo_full = ds.albedo_pixels(cam, _config_at(cfg, full_albedo_samples)) if full_albedo_samples is not None else None
+        low_filtered = None
+        if low_denoise_params is not None:
+            guide_albedo = albedo_low if albedo_low is not None else np.ascontiguousarray(guide_low["base_color"][:, 0:3])
+            low = low_filtered = ds.denoise_records(w, h, low, halves_low, guide_albedo, low_denoise_params, variance=False)["records"]
+            halves_low = None
+        res = ds.upsample(w, h, W, H, low, guide_low, guide, halves_low, params, rgba8=rgba8, albedo_low=albedo_low, albedo=albedo_full)
         holes = np.zeros(0, np.uint32)
         if fill_holes:
             at = np.flatnonzero((res["weight"] == 0) & (guide["hit"] != 0))
@@ -292,12 +312,16 @@ class Raytracing:
                 cfg_b = rr_config.from_buffer_copy(cfg)
                 cfg_b.gamma_correction = capi.upsample_params(params).gamma_correction
                 fine = ds.render_pixel_parts(cam, cfg_b, pixels=holes, n_parts=2)
-                res["records"][at], res["halves"][at] = _pack_records(fine), _pack_records(fine["parts"])
+                res["records"][at] = _pack_records(fine)
+                if res["halves"] is not None:
+                    res["halves"][at] = _pack_records(fine["parts"])
                 if rgba8:
                     res["rgba"][at] = ds.render_pixels(cam, cfg_b, pixels=holes, rgba8=True)["rgba"]
-        res.update(low_width=w, low_height=h, holes=holes, count=len(holes))
+        res.update(low_width=w, low_height=h, holes=holes, count=len(holes), albedo_low=albedo_low, albedo=albedo_full)
+        if low_filtered is not None:
+            res["low_filtered"] = low_filtered
         if denoise_params is not None:
-            albedo = np.ascontiguousarray(guide["base_color"][:, 0:3])
+            albedo = albedo_full if albedo_full is not None else np.ascontiguousarray(guide["base_color"][:, 0:3])
             res.update(upsampled=res["records"], **self.device_scene.denoise_records(W, H, res["records"], res["halves"], albedo, denoise_params, rgba8=rgba8))
         return dict(res, **capi._records(res["records"]))
 
@@ -1261,6 +1285,24 @@ def render_denoised_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, p
 # ---------------------------------------------------------------------------
 # the joint-bilateral upsampler on torch tensors: a frame traced at a low resolution is raised where it is, on torch's current stream
 # ---------------------------------------------------------------------------
+def _check_upsampled_options(albedo, full_albedo_samples) -> None:
+    """The `albedo` and `full_albedo_samples` arguments of the upsampling pipelines: True (the guides' pixel-centre albedo) or "mean"
+    (rr_albedo_pixels on the small camera); None or a whole number of samples, at least 1."""
+    if not (albedo is True or _mean_mode(albedo)):
+        raise ValueError(f'albedo must be True or "mean", not {albedo!r}')
+    if full_albedo_samples is not None:
+        k = full_albedo_samples
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"full_albedo_samples must be None or a whole number of samples, at least 1, not {k!r}")
+
+
+def _config_at(cfg: rr_config, samples) -> rr_config:
+    """`cfg` at `samples` samples."""
+    c = rr_config.from_buffer_copy(cfg)
+    c.samples = int(samples)
+    return c
+
+
 def _low_camera(cam, scale):
     """(`cam` with its matrices at ceil(width / scale) x ceil(height / scale), that width, that height); scale >= 1, whole or not."""
     import math
@@ -1272,16 +1314,19 @@ def _low_camera(cam, scale):
 
 
 def upsample_torch(device_scene: capi.DeviceScene, low_width: int, low_height: int, width: int, height: int, low, halves_low, guide_low, guide, params=None,
-                   rgba8: bool = False, weight: bool = True) -> dict:
+                   rgba8: bool = False, weight: bool = True, albedo_low=None, albedo=None) -> dict:
     """rr_upsample_records_device on torch's current stream of the scene's device: `low` (w h, 8), `halves_low` (w h, 2, 8) or None,
     `guide_low` (w h, 32) and `guide` (W H, 32) (the `records` of surface_pixels_torch) are contiguous float32 CUDA tensors on that device
     (anything else raises).  Returns torch tensors, without a host copy and without a synchronisation: dict(records (W H, 8) float32 and
-    its views color, depth, normal, object_id; halves (W H, 2, 8) or None; on request weight (W H,) float32 and rgba (W H, 4) uint8)."""
+    its views color, depth, normal, object_id; halves (W H, 2, 8) or None; on request weight (W H,) float32 and rgba (W H, 4) uint8).
+    albedo_low (w h, 3) and albedo (W H, 3), each or None: albedo planes in place of the guides' base colours, tensors of the same kind
+    (rr_upsample_albedo_records_device; a view that is only 4-byte aligned will do)."""
     import torch
     n = int(width) * int(height)
-    lo = _frame_tensors(device_scene, low_width, low_height, dict(low=(low, (8,)), halves_low=(halves_low, (2, 8)), guide_low=(guide_low, (32,))),
-                        required=("low", "guide_low"))
-    gf = _frame_tensors(device_scene, width, height, dict(guide=(guide, (32,))), required=("guide",))["guide"]
+    lo = _frame_tensors(device_scene, low_width, low_height, dict(low=(low, (8,)), halves_low=(halves_low, (2, 8)), guide_low=(guide_low, (32,)),
+                                                                  albedo_low=(albedo_low, (3,))), required=("low", "guide_low"))
+    fl = _frame_tensors(device_scene, width, height, dict(guide=(guide, (32,)), albedo=(albedo, (3,))), required=("guide",))
+    gf, al, af = fl["guide"], lo["albedo_low"], fl["albedo"]
     hv = lo["halves_low"]
     dev = torch.device("cuda", device_scene.device)
     with torch.cuda.device(dev):
@@ -1291,7 +1336,8 @@ def upsample_torch(device_scene: capi.DeviceScene, low_width: int, low_height: i
         wt = torch.empty((n,), dtype=torch.float32, device=dev) if weight else None
         device_scene.upsample_device(low_width, low_height, width, height, lo["low"].data_ptr(), hv.data_ptr() if hv is not None else None, lo["guide_low"].data_ptr(),
                                      gf.data_ptr(), out.data_ptr(), hout.data_ptr() if hout is not None else None, rgba.data_ptr() if rgba8 else None,
-                                     wt.data_ptr() if weight else None, params, torch.cuda.current_stream(dev).cuda_stream)
+                                     wt.data_ptr() if weight else None, params, torch.cuda.current_stream(dev).cuda_stream,
+                                     albedo_low=al.data_ptr() if al is not None else None, albedo=af.data_ptr() if af is not None else None)
     res = dict(_record_views(out), halves=hout)
     if weight:
         res["weight"] = wt
@@ -1301,7 +1347,7 @@ def upsample_torch(device_scene: capi.DeviceScene, low_width: int, low_height: i
 
 
 def render_upsampled_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, scale=2, params=None, denoise_params=None, fill_holes: bool = False,
-                           rgba8: bool = False, sample_xy=None) -> dict:
+                           rgba8: bool = False, sample_xy=None, albedo=True, full_albedo_samples: Optional[int] = None, low_denoise_params=None) -> dict:
     """Raytracing.render_upsampled on the device, on torch's current stream with no host trip: rr_render_pixel_parts_device at n_parts = 2
     on the camera at ceil(W / scale) x ceil(H / scale), rr_surface_pixels_device on both cameras, rr_upsample_records_device with halves
     and, with `denoise_params`, rr_denoise_records_device at full size with the full guide's albedo, each reading what the one before
@@ -1309,14 +1355,28 @@ def render_upsampled_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, 
     torch on the device (its length is read on the host: one wait), are traced at full resolution by rr_render_pixel_parts_device and
     written over the records and the halves before the filter.  Returns the dict of upsample_torch plus low (w h, 8), halves_low,
     guide_low, guide (the tensors the upsampler read), low_width, low_height, holes (the list, int32 bits) and count; with
-    `denoise_params` the records are the filtered ones, `upsampled` those before the filter, and `variance` is there."""
+    `denoise_params` the records are the filtered ones, `upsampled` those before the filter, and `variance` is there.
+    albedo, full_albedo_samples and low_denoise_params as Raytracing.render_upsampled takes them: rr_albedo_pixels_device on the small
+    camera (with the low frame's cfg and sample_xy) and on `cam` at full_albedo_samples, rr_upsample_albedo_records_device, and
+    rr_denoise_records_device at the low size before it, all on the same stream; the result holds albedo_low and albedo (the planes the
+    upsampler took, or None) and with low_denoise_params low_filtered."""
+    _check_upsampled_options(albedo, full_albedo_samples)
     import torch
     W, H = int(cam.width), int(cam.height)
     low_cam, w, h = _low_camera(cam, scale)
     base = render_pixel_parts_torch(device_scene, low_cam, cfg, None, 2, sample_xy=sample_xy)
-    guide_low = surface_pixels_torch(device_scene, low_cam, None, records=True, albedo=False)
-    guide = surface_pixels_torch(device_scene, cam, None, records=True, albedo=denoise_params is not None)
-    res = upsample_torch(device_scene, w, h, W, H, base["records"], base["part_records"], guide_low["records"], guide["records"], params, rgba8=rgba8)
+    mean = _mean_mode(albedo)
+    guide_low = surface_pixels_torch(device_scene, low_cam, None, records=True, albedo=low_denoise_params is not None and not mean)
+    guide = surface_pixels_torch(device_scene, cam, None, records=True, albedo=denoise_params is not None and full_albedo_samples is None)
+    albedo_low = albedo_pixels_torch(device_scene, low_cam, cfg, None, sample_xy=sample_xy) if mean else None
+    albedo_full = albedo_pixels_torch(device_scene, cam, _config_at(cfg, full_albedo_samples), None) if full_albedo_samples is not None else None
+    low, halves_low, low_filtered = base["records"], base["part_records"], None
+    if low_denoise_params is not None:
+        low = low_filtered = denoise_torch(device_scene, w, h, low, halves_low, albedo_low if mean else guide_low["albedo"], low_denoise_params,
+                                           variance=False)["records"]
+        halves_low = None
+    res = upsample_torch(device_scene, w, h, W, H, low, halves_low, guide_low["records"], guide["records"], params, rgba8=rgba8, albedo_low=albedo_low,
+                         albedo=albedo_full)
     dev = torch.device("cuda", device_scene.device)
     with torch.cuda.device(dev):
         holes = torch.empty((0,), dtype=torch.int32, device=dev)
@@ -1328,13 +1388,18 @@ def render_upsampled_torch(device_scene: capi.DeviceScene, cam, cfg: rr_config, 
         cfg_b = rr_config.from_buffer_copy(cfg)
         cfg_b.gamma_correction = capi.upsample_params(params).gamma_correction
         fine = render_pixel_parts_torch(device_scene, cam, cfg_b, holes, 2, sample_xy=sample_xy)
-        res["records"][at], res["halves"][at] = fine["records"], fine["part_records"]
+        res["records"][at] = fine["records"]
+        if res["halves"] is not None:
+            res["halves"][at] = fine["part_records"]
         if rgba8:
             res["rgba"][at] = render_pixels_torch(device_scene, cam, cfg_b, holes, sample_xy=sample_xy, rgba8=True)["rgba"]
     res.update(low=base["records"], halves_low=base["part_records"], guide_low=guide_low["records"], guide=guide["records"], low_width=w, low_height=h,
-               holes=holes, count=int(holes.shape[0]))
+               holes=holes, count=int(holes.shape[0]), albedo_low=albedo_low, albedo=albedo_full)
+    if low_filtered is not None:
+        res["low_filtered"] = low_filtered
     if denoise_params is not None:
-        filtered = denoise_torch(device_scene, W, H, res["records"], res["halves"], guide["albedo"], denoise_params, rgba8=rgba8)
+        filtered = denoise_torch(device_scene, W, H, res["records"], res["halves"], albedo_full if albedo_full is not None else guide["albedo"], denoise_params,
+                                 rgba8=rgba8)
         res.update(upsampled=res["records"], **filtered)
     return res
 

@@ -125,10 +125,20 @@ def _low_arrays(low, halves_low, w, h):
     return rec[..., 0:3], (None if hv is None else hv[..., 0:3]), np.isfinite(rec[..., 0:3]).all(-1)
 
 
-def upsample_records(low, halves_low, guide_low, guide, w: int, h: int, W: int, H: int, params: UpsampleParams | None = None) -> dict:
+def _albedo_plane(plane, n: int, what: str) -> np.ndarray:
+    a = np.ascontiguousarray(plane, F)
+    if a.size != 3 * n:
+        raise ValueError(f"{what}: {a.size} floats for {n} pixels x 3")
+    return a.reshape(n, 3)
+
+
+def upsample_records(low, halves_low, guide_low, guide, w: int, h: int, W: int, H: int, params: UpsampleParams | None = None, *, albedo_low=None,
+                     albedo=None) -> dict:
     """low: (w * h, 8) float32 rr_radiance records of the low frame in row-major order; halves_low: (w * h, 2, 8) in the layout of
     render_pixel_parts at n_parts = 2, or None; guide_low, guide: w * h and W * H rr_surface_hit records (flat.SURFACE_HIT_DTYPE, or
-    (n, 32) float32).  Returns dict(records (W * H, 8) float32, halves (W * H, 2, 8) or None, weight (W * H,) float32)."""
+    (n, 32) float32).  albedo_low (w * h, 3) and albedo (W * H, 3), each or None (rr_upsample_albedo_records): the plane stands wherever
+    the header reads the base_color[0 .. 2] of guide_low and of guide; with use_albedo off they are not read.  Returns dict(records
+    (W * H, 8) float32, halves (W * H, 2, 8) or None, weight (W * H,) float32)."""
     prm = params or UpsampleParams()
     prm.check()
     w, h, W, H = int(w), int(h), int(W), int(H)
@@ -141,6 +151,10 @@ def upsample_records(low, halves_low, guide_low, guide, w: int, h: int, W: int, 
         low_c, low_h, fin_q = _low_arrays(low, halves_low, w, h)
         hit_q, valid_q, id_q, z_q, n_q, a_q = _guide_fields(g_low, h, w)
         hit_p, valid_p, id_p, z_p, n_p, a_p = _guide_fields(g_full, H, W)
+        if albedo_low is not None and prm.use_albedo:
+            a_q = _albedo_plane(albedo_low, w * h, "albedo_low").reshape(h, w, 3)
+        if albedo is not None and prm.use_albedo:
+            a_p = _albedo_plane(albedo, n, "albedo").reshape(H, W, 3)
         sum_c, sum_w = np.zeros((H, W, 3), F), np.zeros((H, W), F)
         sum_h = None if low_h is None else np.zeros((H, W, 2, 3), F)
         demod = bool(prm.use_albedo) & hit_p

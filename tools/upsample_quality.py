@@ -10,6 +10,11 @@ are, against that reference over the whole frame:
   bilinear   upsample.bilinear_records of the same low frame: the same rays without the guide
   equal rays the full-resolution frame at S / 4 samples: the same number of primary rays, spent per displayed pixel
 and the share of hole pixels (weight 0 on a surface) of the guided arm, which a caller may trace at full resolution.
+Four more arms with albedo planes (rr_upsample_albedo_records), the same scenes, seeds and reference in the same run:
+  (e) mean low       the guided arm with albedo="mean": the low frame demodulated by rr_albedo_pixels on the small camera
+  (f) mean both      (e) plus full_albedo_samples = S: remodulated by rr_albedo_pixels at full size with S samples
+  (g) low filtered   (e) plus low_denoise_params at the filter's defaults: the low frame filtered before it is raised
+  (h) equal rays, filtered   render_denoised(albedo="mean") at full size with S / 4 samples: the opponent of (g)
 
 usage: upsample_quality.py [width height samples] [--out FILE] [scene ...]   (default: 640 360 8, sponza_syn monkey)"""
 import os
@@ -22,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main(argv):
     from rustray_amd import capi, synthetic
+    from rustray_amd.denoise import DenoiseParams
     from rustray_amd.flat import make_config
     from rustray_amd.renderer import Raytracing, _low_camera, _pack_records
     from rustray_amd.upsample import UpsampleParams, bilinear_records
@@ -63,11 +69,18 @@ def main(argv):
             low = _pack_records(rt.device_scene.render_pixel_parts(low_cam, rt.config, n_parts=2))
             guide = rt.surface_pixels()
             plain = bilinear_records(low, None, guide, w, h, W, H)
+            mean_low = rt.render_upsampled(scale=2, albedo="mean")
+            mean_both = rt.render_upsampled(scale=2, albedo="mean", full_albedo_samples=S)
+            low_filtered = rt.render_upsampled(scale=2, albedo="mean", low_denoise_params=DenoiseParams())
             rt.config = make_config(samples=S // 4, monte_carlo=True, seed=1, max_recursion=4)
             equal = rt.render_pixels()
+            equal_filtered = rt.render_denoised(albedo="mean")
             holes = int(((guided["weight"] == 0) & (guide["hit"] != 0)).sum())
             emit(f"  {scene}: guided {mse(guided['color'], ref):.4e}, no albedo {mse(unmodulated['color'], ref):.4e}, bilinear {mse(plain['records'][:, 0:3], ref):.4e}, equal rays ({S // 4} samples at full size) "
                  f"{mse(equal['color'], ref):.4e}; holes {holes} of {W * H} = {holes / (W * H):.3%}")
+            emit(f"  {scene}, albedo planes: (e) mean low {mse(mean_low['color'], ref):.4e}, (f) mean both ({S} samples at full size) {mse(mean_both['color'], ref):.4e}, "
+                 f"(g) mean low, low frame filtered {mse(low_filtered['color'], ref):.4e}, (h) equal rays ({S // 4} samples at full size), filtered, mean albedo "
+                 f"{mse(equal_filtered['color'], ref):.4e}")
         finally:
             rt.close()
     if out_path:

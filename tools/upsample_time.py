@@ -13,8 +13,14 @@ back-to-back calls on one stream, divided by CALLS; WARMUP rounds, then the medi
 Then the whole frame at the last size, one call each per round:
   (e) render_upsampled_torch(scale=2) with the filter behind it     (f) render_denoised_torch at full size with the centre albedo
 and the share of hole pixels (weight 0 on a surface) of the upsampled frame.  Scene `sponza_syn` is the benchmark's stand-in.
+--albedo: rr_upsample_albedo_records_device beside the call above, in the same rounds:
+  (a) as above                                                   (a1) the same with the low albedo plane   (a2) with both planes
+  (c) the copy of (a)'s bytes; the planes add 12 B per low pixel and per full pixel to the bytes counted for (a1) and (a2)
+and the whole frame at the last size:
+  (e), (f) as above   (e1) render_upsampled_torch(scale=2, albedo="mean") + filter   (e2) the same with full_albedo_samples = samples
+  (e3) (e1) with low_denoise_params at the filter's defaults and no filter at full size.
 
-usage: upsample_time.py [scene [samples]] [--out FILE]"""
+usage: upsample_time.py [scene [samples]] [--albedo] [--out FILE]"""
 import os
 import sys
 
@@ -54,6 +60,8 @@ def measure(argv, emit):
     from rustray_amd.denoise import DenoiseParams
     from rustray_amd.flat import make_config
     from tests.helpers import camera_for, load_scene
+    with_planes = "--albedo" in argv
+    argv = [a for a in argv if a != "--albedo"]
     scene = argv[1] if len(argv) > 1 else "sponza_syn"
     samples = int(argv[2]) if len(argv) > 2 else 4
     if capi.device_count() < 1:
@@ -90,6 +98,12 @@ def measure(argv, emit):
             src_b, dst_b = torch.empty(bytes_b // 2, dtype=torch.uint8, device="cuda"), torch.empty(bytes_b // 2, dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
             low, hv = base["records"], base["part_records"]
+            if with_planes:
+                a_low = renderer.albedo_pixels_torch(ds, low_cam, cfg, None)
+                a_full = renderer.albedo_pixels_torch(ds, cam, cfg, None)
+                torch.cuda.synchronize()
+            planes_call = lambda al, af: ds.upsample_device(w, h, W, H, low.data_ptr(), hv.data_ptr(), g_low.data_ptr(), g_full.data_ptr(), out.data_ptr(),
+                                                            hout.data_ptr(), None, wt.data_ptr(), prm, stream, albedo_low=al, albedo=af)
             arms = {
                 "a": lambda: ds.upsample_device(w, h, W, H, low.data_ptr(), hv.data_ptr(), g_low.data_ptr(), g_full.data_ptr(), out.data_ptr(), hout.data_ptr(), None,
                                                 wt.data_ptr(), prm, stream),
@@ -97,6 +111,9 @@ def measure(argv, emit):
                 "c": lambda: dst_a.copy_(src_a),      # (a copy reads and writes each of its bytes: half of the call's bytes each way)
                 "d": lambda: dst_b.copy_(src_b),
             }
+            if with_planes:
+                arms["a1"] = lambda: planes_call(a_low.data_ptr(), None)
+                arms["a2"] = lambda: planes_call(a_low.data_ptr(), a_full.data_ptr())
             runs = {k: [] for k in arms}
             for r in range(WARMUP + ROUNDS):
                 for k, fn in arms.items():
@@ -111,10 +128,19 @@ def measure(argv, emit):
                 m, lo, hi = med[k]
                 emit(f"    {name}: {m * 1e3:.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}], {nbytes / 1e6:.1f} MB, {nbytes / m / 1e9:.2f} TB/s")
             emit(f"    (a) / (c) = {med['a'][0] / med['c'][0]:.2f}, (b) / (d) = {med['b'][0] / med['d'][0]:.2f}")
+            if with_planes:
+                for k, name, nbytes in (("a1", "(a1) (a) with the low albedo plane", bytes_a + 12 * nl), ("a2", "(a2) (a) with both albedo planes", bytes_a + 12 * (nl + n))):
+                    m, lo, hi = med[k]
+                    emit(f"    {name}: {m * 1e3:.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}], {nbytes / 1e6:.1f} MB, {nbytes / m / 1e9:.2f} TB/s")
+                emit(f"    (a1) / (a) = {med['a1'][0] / med['a'][0]:.3f}, (a2) / (a) = {med['a2'][0] / med['a'][0]:.3f}, (a2) / (c) = {med['a2'][0] / med['c'][0]:.2f}")
         # ---- the whole frame at the last size
         dprm = DenoiseParams()
         arms = {"e": lambda: renderer.render_upsampled_torch(ds, cam, cfg, scale=2, denoise_params=dprm),
                 "f": lambda: renderer.render_denoised_torch(ds, cam, cfg, dprm, albedo=True)}
+        if with_planes:
+            arms["e1"] = lambda: renderer.render_upsampled_torch(ds, cam, cfg, scale=2, denoise_params=dprm, albedo="mean")
+            arms["e2"] = lambda: renderer.render_upsampled_torch(ds, cam, cfg, scale=2, denoise_params=dprm, albedo="mean", full_albedo_samples=samples)
+            arms["e3"] = lambda: renderer.render_upsampled_torch(ds, cam, cfg, scale=2, albedo="mean", low_denoise_params=dprm)
         runs = {k: [] for k in arms}
         for r in range(WARMUP + ROUNDS):
             for k, fn in arms.items():
@@ -128,6 +154,10 @@ def measure(argv, emit):
     emit(f"the whole frame, {scene} {W}x{H}, {samples} samples in two halves, the filter at its defaults; ms per frame between device events, median of {ROUNDS} [min .. max]")
     emit(f"  (e) render_upsampled_torch(scale=2) + filter: {e[0]:.3f} ms [{e[1]:.3f} .. {e[2]:.3f}]")
     emit(f"  (f) render_denoised_torch at full size, centre albedo: {f[0]:.3f} ms [{f[1]:.3f} .. {f[2]:.3f}]")
+    for k, name in (("e1", '(e1) (e) with albedo="mean"'), ("e2", f"(e2) (e1) with full_albedo_samples = {samples}"),
+                    ("e3", "(e3) (e1) with the low frame filtered and no filter at full size")) if with_planes else ():
+        m = _median(runs[k])
+        emit(f"  {name}: {m[0]:.3f} ms [{m[1]:.3f} .. {m[2]:.3f}], / (e) = {m[0] / e[0]:.3f}, / (f) = {m[0] / f[0]:.3f}")
     emit(f"  (e) / (f) = {e[0] / f[0]:.3f}; hole pixels (weight 0 on a surface): {holes} of {W * H} = {holes / (W * H):.4%}")
 
 
